@@ -27,13 +27,6 @@ for _p in (ROOT, PKG):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-# HIP maps the streams of a process onto GPU_MAX_HW_QUEUES hardware queues (default 4) in creation order; two streams that land on
-# one queue run their kernels one after the other.  At N > 1 a rank has the caller's stream, the exchange's stream, RCCL's and the
-# loader's fetch and sampler streams: with 4 queues the cold fill and the row exchange can end up on the same one and lose their
-# overlap (seen on one GPU: two logical ranks' fills serialised on queue 4, tools/dist_overlap_trace.py).  Must be set before the
-# HIP runtime starts; a value already in the environment wins.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 T_PROCESS_START = time.time()
 # Every watchdog deadline of a run is cut off at T_PROCESS_START + this many seconds, so that a hang ends with the JSON line (with an
 # "error" field) and a non-zero exit code BEFORE a driver's own limit kills the job silently (its limit: 600 s).  --time-budget S or
@@ -239,7 +232,39 @@ def parse_args():
                     help=f"seconds, counted from the start of the launcher: every watchdog deadline is cut off there, and extra legs that would "
                          f"not fit are skipped (default {DEFAULT_BUDGET_S:.0f}, or COALA_BENCH_BUDGET_S): a hang ends with the line + a non-zero code "
                          f"before a driver's 600 s limit")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what its last timed step delivered as DIR/<name>.npy (see dump_outputs): "
+                         "with the same arguments the inputs are the same from run to run, so two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, batch, feat, seed=0):
+    """What fetch_feature returned in the last timed step, as .npy files under out_dir, DUMP_LIMIT_BYTES at most in all:
+    input_nodes and seeds (float64: node ids are exact below 2^53) and features (float32 [rows, dim]).  When the whole feature
+    tensor does not fit, a fixed seeded sample of its rows is written instead, in ascending order, and feature_rows (float64)
+    holds their positions in the delivered tensor.  -> {name: shape} of the files written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"input_nodes": batch[0].detach().cpu().numpy().astype(np.float64)}
+    if len(batch) > 1 and torch.is_tensor(batch[1]):
+        arrays["seeds"] = batch[1].detach().cpu().numpy().astype(np.float64)
+    n, dim = feat.shape
+    left = DUMP_LIMIT_BYTES - 4096 - sum(a.nbytes for a in arrays.values())   # (4096: room for the files' .npy headers)
+    if n * dim * 4 <= left:
+        arrays["features"] = feat.detach().cpu().numpy()
+    else:
+        keep = left // (dim * 4 + 8)     # a sampled row costs its float32 values and its float64 position
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        arrays["features"] = feat[torch.from_numpy(rows).to(feat.device)].cpu().numpy()
+        arrays["feature_rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def _maybe_stall(where, rank):
@@ -705,6 +730,9 @@ def _main_body(args, fanout, world, rank, local_rank, single_dev, dev_index, dev
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, batches[args.warmup + args.steps - 1], out, seed=args.seed)
+        log(f"last timed step's outputs written to {args.dump_outputs}: {dumped}")
     live.clear()
 
     hit, miss, bad = cache.stats()

@@ -31,9 +31,22 @@ def _line(out):
     return json.loads(lines[0])
 
 
-def test_bench_single_gpu_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL], capture_output=True, text=True, timeout=900)
+def test_bench_single_gpu_contract(tmp_path):
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--dump-outputs", str(dump)], capture_output=True, text=True,
+                         timeout=900)
     d = _line(out)
+    # --dump-outputs: the last timed step's rows (or a fixed sample of them) equal the synthetic table's formula
+    import numpy as np
+    import torch
+    from COALA_GNN.synthetic import feature_rows_torch
+    files = {f.stem: np.load(f) for f in dump.iterdir()}
+    assert {"input_nodes", "seeds", "features"} <= set(files) <= {"input_nodes", "seeds", "features", "feature_rows"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64_000_000
+    assert len(files["seeds"]) == 1024
+    rows = files.get("feature_rows", np.arange(len(files["input_nodes"]))).astype(np.int64)
+    ids = torch.from_numpy(files["input_nodes"][rows].astype(np.int64))
+    assert np.array_equal(files["features"], feature_rows_torch(ids, 1024, 0).numpy())
     assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["steps"] == 10 and d["warmup"] == 3 and d["value"] > 0
     assert d["vs_baseline"] is None and d["scaling"] == "weak" and "workload" in d["config"]
     r = d["roofline"]

@@ -24,7 +24,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, "coala-gnn_amd")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import COALA_GNN_Pybind as P  # noqa: E402

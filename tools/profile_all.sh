@@ -1,9 +1,6 @@
 #!/bin/bash
 # GPU box: everything under profiles/ for one round.  PART=1: the rocprofv3 passes over bench.py (default, all-hit, configs[3] shape);
 # PART=2: the probes; unset: both (more than one gpurun call's time limit since round 3).  Summaries land in gpurun_out/profiles_out/.
-# the profiler's preloaded library starts the HIP runtime before python does: bench.py's os.environ.setdefault comes too late there,
-# so the queue count it reports has to be exported by the shell that starts the profiler
-export GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-8}
 R=${GRAFT_REPO_ROOT:-$PWD}
 export ROUND=${ROUND:-r04} TMPDIR=/tmp
 O=$R/gpurun_out/profiles_out
