@@ -399,11 +399,12 @@ __global__ __launch_bounds__(kBlock) void mean_aggregate_backward_kernel(const i
         const int cnt = __builtin_popcountll(__ballot(mine >= 0));
         if (!cnt) continue;
         const float inv = 1.0f / (float)cnt;
-        for (int c = lane; c < dim; c += 64) {
-            const float g = grad_out[d * dim + c] * inv;
+        for (int c0 = 0; c0 < dim; c0 += 64) { // wave-uniform trip count: the shuffles below read lanes that are past `dim`
+            const int c = c0 + lane;
+            const float g = c < dim ? grad_out[d * dim + c] * inv : 0.0f;
             for (int j = 0; j < fanout; ++j) {
                 const int32_t idx = __shfl(mine, j);
-                if (idx >= 0) unsafeAtomicAdd(grad_src + (int64_t)idx * dim + c, g);
+                if (idx >= 0 && c < dim) unsafeAtomicAdd(grad_src + (int64_t)idx * dim + c, g);
             }
         }
     }

@@ -54,3 +54,70 @@ def synth_colors(num_rows, num_colors, topk=10, seed=0):
     tk = rng.integers(0, num_colors + 1, size=(num_colors, topk)).astype(np.int64)
     sc = rng.random((num_colors, topk))
     return color, tk, sc
+
+
+def csc_from_columns(columns):
+    """int64 CSC (indptr[N+1], indices[E]) from explicit in-neighbour lists: columns[v] holds the in-neighbours of node v in
+    CSC order.  Nothing is cleaned up: repeated entries and v itself (a self-loop) stay as given."""
+    deg = np.array([len(c) for c in columns], dtype=np.int64)
+    indptr = np.zeros(len(columns) + 1, dtype=np.int64)
+    np.cumsum(deg, out=indptr[1:])
+    parts = [np.asarray(c, dtype=np.int64).reshape(-1) for c in columns if len(c)]
+    indices = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+    return indptr, indices
+
+
+def edge_case_graph(fanouts, n_plain=200, hub_degree=0, seed=0):
+    """A CSC graph built around the sampler's edges, for the fan-outs given.  For every degree in {0, 1, 200} and {f-1, f, f+1, 2f}
+    of each f there are three nodes: one with in-neighbours drawn at random, one whose column holds the node itself, one whose
+    column repeats a single neighbour in half of its entries.  Then n_plain nodes of in-degree 0..8, and with hub_degree > 0 a last
+    node with that many in-edges.  -> (indptr, indices, special): special = every node above except the plain ones (hub included)."""
+    rng = np.random.default_rng(seed)
+    degrees = sorted({0, 1, 200} | {d for f in fanouts for d in (f - 1, f, f + 1, 2 * f) if d >= 0})
+    n_special = 3 * len(degrees)
+    n = n_special + n_plain + (1 if hub_degree else 0)
+    columns = []
+    for d in degrees:
+        for kind in range(3):
+            v = len(columns)
+            col = rng.integers(0, n, size=d)
+            if d and kind == 1:
+                col[rng.integers(0, d)] = v                        # self-loop
+            if d > 1 and kind == 2:
+                col[rng.permutation(d)[: d // 2 + 1]] = col[0]     # one neighbour in half the column
+            columns.append(col)
+    columns += [rng.integers(0, n, size=rng.integers(0, 9)) for _ in range(n_plain)]
+    if hub_degree:
+        columns.append(rng.integers(0, n, size=hub_degree))
+    indptr, indices = csc_from_columns(columns)
+    special = np.arange(n_special, dtype=np.int64)
+    if hub_degree:
+        special = np.append(special, n - 1)
+    return indptr, indices, special
+
+
+def check_block_properties(indptr, indices, dst, f, src, loc):
+    """The sampler's published properties of one block, independent of any twin: the destination nodes come first in the source
+    list, the source list has no repeats, dst d has min(deg, f) valid entries and they come before the -1 padding, every valid
+    entry is an in-neighbour of d, and no node is picked more often than it occurs in d's column (distinct positions)."""
+    n = len(dst)
+    assert np.array_equal(src[:n], dst), "destination nodes are not first"
+    assert len(np.unique(src)) == len(src), "repeated source node"
+    deg = indptr[dst + 1] - indptr[dst]
+    valid = loc >= 0
+    assert np.array_equal(valid.sum(1), np.minimum(deg, f)), "count != min(deg, fanout)"
+    assert not np.any(valid[:, 1:] & ~valid[:, :-1]), "-1 padding before a valid entry"
+    if not valid.any():
+        return
+    N = len(indptr) - 1
+    rows, cols = np.nonzero(valid)
+    picked = src[loc[rows, cols]]
+    starts = indptr[dst]
+    run = np.zeros(n, dtype=np.int64)
+    np.cumsum(deg[:-1], out=run[1:])
+    pos = np.repeat(starts - run, deg) + np.arange(int(deg.sum()))
+    up, cp = np.unique(dst[rows] * N + picked, return_counts=True)
+    uc, cc = np.unique(np.repeat(dst, deg) * N + indices[pos], return_counts=True)
+    at = np.minimum(np.searchsorted(uc, up), len(uc) - 1)
+    assert np.array_equal(uc[at], up), "a picked node is not in its destination's CSC column"
+    assert np.all(cp <= cc[at]), "a node picked more often than its column holds it"

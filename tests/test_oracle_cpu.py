@@ -178,3 +178,65 @@ def test_openmp_row_gather_is_a_gather(oracle, threads):
     assert 1 <= used <= threads
     assert out[:3333].tobytes() == table[idx].tobytes() and (out[3333:] == -1.0).all()
     assert oracle.gather_rows_mt(table, idx[:0], out, threads) >= 1 and out[:3333].tobytes() == table[idx].tobytes()
+
+
+# ------------------------------------------------------------------ the sampler twin against a plain restatement of the draw
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def _sample_key(seed, step, layer, v):
+    h = _splitmix64(seed ^ ((0x9E3779B97F4A7C15 * (layer + 1)) & _M64))
+    h = _splitmix64(h ^ ((step * 0xD1B54A32D192ED03) & _M64))
+    return _splitmix64(h ^ v)
+
+
+def _draw_row(ip, ix, v, f, seed, step, layer):
+    """The documented draw of one destination node, on Python ints: every in-neighbour (CSC order) when deg <= f, else Floyd's
+    f distinct positions with r = splitmix64(key + c), t = (r * (j + 1)) >> 64, and j itself when t was already chosen."""
+    if v < 0 or v >= len(ip) - 1:
+        return [-1] * f
+    start, deg = int(ip[v]), int(ip[v + 1] - ip[v])
+    if deg <= f:
+        return [int(x) for x in ix[start:start + deg]] + [-1] * (f - deg)
+    key = _sample_key(seed, step, layer, v)
+    chosen = []
+    for c, j in enumerate(range(deg - f, deg)):
+        t = (_splitmix64((key + c) & _M64) * (j + 1)) >> 64
+        chosen.append(j if t in chosen else t)
+    return [int(ix[start + t]) for t in chosen]
+
+
+def _compact(dst, nbr):
+    """Source list = dst nodes, then every other neighbour in order of first appearance; nbr -> index in that list."""
+    where = {}
+    for k in list(dst) + [x for row in nbr for x in row]:
+        if k >= 0 and k not in where:
+            where[k] = len(where)
+    return np.array(list(where), dtype=np.int64), np.array([[where.get(x, -1) for x in row] for row in nbr], dtype=np.int32).reshape(len(nbr), -1)
+
+
+@pytest.mark.parametrize("f", range(1, 33))
+def test_sampler_twin_matches_python_restatement(oracle, f):
+    """oracle.sample_blocks (the CPU twin every GPU sampler test trusts) equals a plain-Python restatement of the draw at every fan-out
+    the kernels accept, on a graph with degrees 0, 1, f-1, f, f+1, 2f and 200, self-loops and repeated edges; seeds and steps near
+    2^64 so that every 64-bit product wraps."""
+    from _util import edge_case_graph
+    ip, ix, special = edge_case_graph([f], n_plain=40, seed=f)
+    seeds = np.concatenate([special, np.arange(len(special), len(ip) - 1, 3)])
+    np.random.default_rng(f).shuffle(seeds)
+    fan = [f, f % 5 + 1]                                   # second layer: every sampled node drawn again
+    for seed, step in ((0, 0), (7, 3), (_M64, _M64 - 1)):
+        dst = seeds
+        for layer, (src, local, nbr) in enumerate(oracle.sample_blocks(ip, ix, seeds, fan, seed, step)):
+            want = [_draw_row(ip, ix, int(v), fan[layer], seed, step, layer) for v in dst]
+            assert nbr.tolist() == want, f"draw differs at layer {layer}"
+            w_src, w_local = _compact(dst.tolist(), want)
+            assert np.array_equal(src, w_src) and np.array_equal(local, w_local)
+            dst = src
