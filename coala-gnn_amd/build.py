@@ -38,13 +38,11 @@ def build_lib(force=False, verbose=False, dev=False):
     dev=True: libcoala_hip_dev.so with -DCOALA_DEV_KNOBS (launch-geometry knobs from the environment, for tools/k1_insitu.py and
     friends; select it with COALA_HIP_LIB).  The product library reads no tuning knobs."""
     out = DEV_LIB_PATH if dev else LIB_PATH
-    if dev and os.environ.get("COALA_EXTRA_HIPCC_FLAGS"):   # an experimental variant of the development build (-DK1_NT_STORES ...): its own file
-        out = os.path.join(LIB_DIR, "libcoala_hip_var.so")
     if not force and not dev and not needs_build():
         return out
-    # the development build is rebuilt only when a source is newer than it (or extra flags ask for another variant): the GPU tests ask for it
-    # once per launch shape, and a compile of the whole library is ~50 s
-    if dev and not force and not os.environ.get("COALA_EXTRA_HIPCC_FLAGS") and os.path.exists(out) and \
+    # the development build is rebuilt only when a source is newer than it: the GPU tests ask for it once per launch shape, and a compile
+    # of the whole library is ~50 s
+    if dev and not force and os.path.exists(out) and \
             os.path.getmtime(out) >= max(os.path.getmtime(p) for p in sources() + HEADERS + [os.path.abspath(__file__)]):
         return out
     os.makedirs(LIB_DIR, exist_ok=True)
@@ -54,7 +52,6 @@ def build_lib(force=False, verbose=False, dev=False):
            "-mllvm", "-amdgpu-kernarg-preload-count=16"]
     if dev:
         cmd.append("-DCOALA_DEV_KNOBS")
-        cmd += os.environ.get("COALA_EXTRA_HIPCC_FLAGS", "").split()
     cmd += sources() + ["-o", out + ".tmp", "-lrt", "-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
     if verbose:
         print(" ".join(cmd))

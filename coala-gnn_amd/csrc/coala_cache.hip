@@ -178,15 +178,13 @@ struct Geo {
 // that K2 walks is pushed with one atomicExch on the set's own head word.  (Measured alternatives: a miss-list append
 // per chunk or per wave serialises at ~12 ns per same-address atomic -- 4096 waves = 49 us, as long as the whole hit
 // gather; a block-level append needs LDS staging and a trailing barrier and still costs 5-7 us.)
-#ifndef K1_MIN_WAVES
-#define K1_MIN_WAVES 4 // waves per SIMD the register allocator must leave room for (5 on 4-KiB lines spills: 17.5 -> 20.9 us on the default workload)
-#endif
+constexpr int kK1MinWaves = 4; // waves per SIMD the register allocator must leave room for (5 on 4-KiB lines spills: 17.5 -> 20.9 us on the default workload)
 // Row(-pair)s a wave keeps in flight (passes): 4 for every line size and both tag widths = 16 KiB of 4-KiB lines, 4 KiB of 512-B lines
 // (8 rows).  More passes on short lines were measured in situ on the configs[3] shape (512-B lines, 16 GiB cache, 315 k rows per
 // minibatch at 62 % hits; tools/k1_insitu.py, profiles/r03_k1_insitu_papers100m.txt): 2 / 4 / 8 / 16 passes -> 51.2 / 51.0 / 53.4 /
 // (72 k rows) 44.5 us: a launch of this size is one chunk per wave, so its waves overlap each other, not their own chunks, and fewer,
 // fatter waves lose more parallelism than they gain bytes in flight.
-constexpr int k1_np32(int /*cache_dim*/) { return 4; }
+constexpr int kK1Passes = 4;
 constexpr int64_t kK1SingleMaxChunks = 1 << 20; // launches up to this many chunks (4-8 M rows) get one wave per chunk (SINGLE)
 constexpr int kK1Waves = 2; // waves per block (measured: 2048 x 128 threads beats 1024 x 256 and 256 x 1024 by 3-20 %)
 #ifdef COALA_DEV_KNOBS          // development builds only (build.py --dev -> libcoala_hip_dev.so): launch geometry from the environment
@@ -195,47 +193,21 @@ constexpr int kK1MaxWaves = 4;
 constexpr int kK1MaxWaves = kK1Waves;
 #endif
 
-__device__ __forceinline__ float first_of(float v) { return v; }
-__device__ __forceinline__ float first_of(vfloat4 v) { return v.x; }
 template <typename V> __device__ __forceinline__ V nt_load(const V* p) { return __builtin_nontemporal_load(p); }
 template <typename V> __device__ __forceinline__ void nt_store(V v, V* p) { __builtin_nontemporal_store(v, p); }
+
 // K1's row moves: nontemporal loads of the lines (touched once per batch: keeps them from displacing the tag sets; plain loads are
 // 3 us slower on an all-hit batch and no faster at 32 % hits -- 17.4 us either way in situ, as is a per-chunk choice between the two), plain stores of the output rows (0.3-0.4 us faster than
-// nontemporal ones in situ and on the all-hit batch, and the consumer reads them next).  Development builds can flip either
-// with -DK1_PLAIN_LOADS / -DK1_NT_STORES (tools/k1_insitu.py).
-template <typename V> __device__ __forceinline__ V k1_load(const V* p) {
-#ifdef K1_PLAIN_LOADS
-    return *p;
-#else
-    return __builtin_nontemporal_load(p);
-#endif
-}
-template <typename V> __device__ __forceinline__ void k1_store(V v, V* p) {
-#ifdef K1_NT_STORES
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-
-// NOMISS is a development switch (tools/k1_insitu.py --stages: where a launch's time goes; such launches run on a generation nobody
-// consumes): 0 = the product kernel; 1 = no miss bookkeeping; 11 / 12 / 13 = the dependency chain cut short after the id loads /
-// after the tag loads and the probe / after the line loads of the hit rows (no stores).
+// nontemporal ones in situ and on the all-hit batch, and the consumer reads them next).
 // SINGLE: the grid has one wave per chunk (every launch up to kK1SingleMaxChunks chunks): no loop and no prefetch state for later
 // chunks, which is what the software pipeline's registers are for (4-KiB lines: 76 instead of 110 VGPRs, 6 instead of 4 waves per SIMD) and
 // whose id / tag loads a one-chunk wave issues for chunks it never has.  The product's choice for lines of 1 KiB and more; 512-B lines keep
 // the looping kernel (8-row waves gain from the pipeline whenever a wave does run two chunks, and lose nothing when it does not).
 // Round 4, the last K1 experiment (profiles/r04_k1_min_waves.txt): on 512-B lines the looping kernel needs 66 VGPRs = 7 waves per SIMD; bounded to 8
-// waves (-DK1_MIN_WAVES_SHORT=8) the configs[3] variant fits 64 registers without a spill -- and is no faster in the product's block shape: 11.3 against
+// waves the configs[3] variant fits 64 registers without a spill -- and is no faster in the product's block shape: 11.3 against
 // 11.4 us at ~72 k rows, 44-48 against 49 us at ~289 k (the development build's 256-thread blocks gained 7 % at 72 k rows).  Not adopted.
-#ifndef K1_MIN_WAVES_SHORT
-#define K1_MIN_WAVES_SHORT K1_MIN_WAVES
-#endif
-template <int CD, typename TAG, bool FULL, bool REDIR> constexpr int k1_min_waves() {
-    return (CD <= 128 && sizeof(TAG) == 4 && FULL && !REDIR) ? K1_MIN_WAVES_SHORT : K1_MIN_WAVES;
-}
-template <int CD, int VEC, typename TAG, int NP = 4, bool FULL = false, int NOMISS = 0, bool REDIR = false, bool SINGLE = false>
-__global__ __launch_bounds__(64 * kK1MaxWaves, (k1_min_waves<CD, TAG, FULL, REDIR>())) void probe_gather_kernel(const int64_t* __restrict__ idx, float* __restrict__ out,
+template <int CD, int VEC, typename TAG, int NP, bool FULL, bool REDIR, bool SINGLE>
+__global__ __launch_bounds__(64 * kK1MaxWaves, kK1MinWaves) void probe_gather_kernel(const int64_t* __restrict__ idx, float* __restrict__ out,
                                                                     int64_t n, uint32_t gen, uint32_t n_blocks, CacheDev c, Redirect rd) {
     // Argument order and the explicit block count are deliberate: with kernarg preloading (build.py: -mllvm -amdgpu-kernarg-preload-count=16)
     // the leading scalar arguments arrive in SGPRs, and with the compile-time block shape the first id load needs nothing from
@@ -305,10 +277,6 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, (k1_min_waves<CD, TAG, FULL, REDI
 
     int64_t chunk = wave;
     Ids ids_next = load_ids(chunk);
-    if (NOMISS == 11) { // (development) ids only
-        if (ids_next.id[0] == 0x7FFFFFFFFFFFFFF1ull) out[0] = 1.f;
-        return;
-    }
     Tags tags = load_tags(ids_next);
     if (!SINGLE) ids_next = load_ids(chunk + n_waves);
 
@@ -348,7 +316,7 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, (k1_min_waves<CD, TAG, FULL, REDI
             bad_b[t] = __ballot(bad_l[t]);
             lead_l[t] = tags.valid[t] && (lane % TG::LPS) == 0;
             // ---- misses: push the row on its set's chain (the old head comes back behind the row loads)
-            imiss_l[t] = NOMISS == 0 && lead_l[t] && tags.ok[t] && !hit;
+            imiss_l[t] = lead_l[t] && tags.ok[t] && !hit;
             prev[t] = 0;
             if (imiss_l[t]) {
                 const unsigned long long tag = ((unsigned long long)gen << 32) | (unsigned long long)(base + t * TG::SPL + lane / TG::LPS + 1);
@@ -360,13 +328,7 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, (k1_min_waves<CD, TAG, FULL, REDI
             bool any = false;
 #pragma unroll
             for (int t = 0; t < TSTEPS; ++t) any = any || imiss_l[t] || bad_l[t];
-#ifndef K1_NO_FILL_FLAG   // (development A/B of what the flag costs K1: profiles/r04_k2_dynamic_deal.txt)
-            if (NOMISS == 0 && __ballot(any) != 0 && lane == 0) fill_flag[gen & 1u] = 1u;
-#endif
-        }
-        if (NOMISS == 12) { // (development) ids + tag sets + the probe
-            if ((hit_b[0] ^ bad_b[0]) == 0x123456789ABCDEFull && lead_l[0]) out[0] = 1.f;
-            return;
+            if (__ballot(any) != 0 && lane == 0) fill_flag[gen & 1u] = 1u;   // (what the flag costs K1: profiles/r04_k2_dynamic_deal.txt)
         }
         // row q of the chunk: its tag step, and the first of its lanes there
         auto row_slot = [&](int q) { return (uint32_t)__builtin_amdgcn_readlane((int)slot_v[q / TG::SPL], TG::LPS * (q % TG::SPL)); };
@@ -393,21 +355,8 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, (k1_min_waves<CD, TAG, FULL, REDI
 #pragma unroll
             for (int v = 0; v < G::VPL; ++v) {
                 const uint32_t u = v * G::LPR + l_in;
-                if (h && (FULL || u < nunits)) val[p][v] = k1_load(src + u);
+                if (h && (FULL || u < nunits)) val[p][v] = nt_load(src + u);
             }
-        }
-        if (NOMISS == 13) { // (development) + the line loads of the hit rows, nothing stored
-            float acc = 0.f;
-#pragma unroll
-            for (int p = 0; p < G::PASSES; ++p) {
-                const bool h_a = row_hit(p * G::RPP), h_b = row_hit(p * G::RPP + (G::RPP - 1));
-                const bool h = (G::RPP == 2 && sub) ? h_b : h_a;
-#pragma unroll
-                for (int v = 0; v < G::VPL; ++v)
-                    if (h && (FULL || (uint32_t)(v * G::LPR + l_in) < nunits)) acc += first_of(val[p][v]);
-            }
-            if (acc == 123456.789f) out[0] = acc;
-            return;
         }
         if (!SINGLE) {
             tags = load_tags(ids_next);
@@ -431,7 +380,7 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, (k1_min_waves<CD, TAG, FULL, REDI
             for (int v = 0; v < G::VPL; ++v) {
                 const uint32_t u = v * G::LPR + l_in;
                 if (FULL || u < nunits) {
-                    if (h) k1_store(val[p][v], dst + u);
+                    if (h) dst[u] = val[p][v];
                     else if (bad) dst[u] = V(0.0f); // rejected id: zero row (kept inline: hoisting it out costs 12 VGPRs and 10 % speed)
                 }
             }
@@ -440,7 +389,7 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, (k1_min_waves<CD, TAG, FULL, REDI
         //      row), so the array never needs clearing between batches
 #pragma unroll
         for (int t = 0; t < TSTEPS; ++t) {
-            if (NOMISS == 0 && lead_l[t]) {
+            if (lead_l[t]) {
                 uint32_t w = 0u;
                 if (imiss_l[t]) w = kLinkMiss | (((uint32_t)(prev[t] >> 32) == gen) ? (uint32_t)prev[t] : 0u);
                 else if (bad_l[t]) w = kLinkBad;
@@ -450,11 +399,6 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, (k1_min_waves<CD, TAG, FULL, REDI
         if (SINGLE) break;
     }
 }
-
-#ifdef COALA_DEV_KNOBS
-// Development only (tools/k1_insitu.py --stages): the launch + drain cost of K1's grid with nothing in it.
-__global__ __launch_bounds__(64 * kK1MaxWaves, K1_MIN_WAVES) void k1_empty_kernel() {}
-#endif
 
 // ---------------------------------------------------------------------------------------------------------- K2
 // Rank + fill.  isolated_cache.h:197-210 (round robin in batch order), :417-474 (miss path), :323-331 (cold read).
@@ -500,9 +444,7 @@ __global__ __launch_bounds__(256) void miss_fill_kernel(CacheDev c, const int64_
     uint32_t* ticket = reinterpret_cast<uint32_t*>(c.stats + 2 * kStatBlocks) + (dyn_slot < 0 ? 0 : dyn_slot);
     const bool dyn = dyn_slot >= 0;
     // nothing to fill in the whole batch (the probe's waves set the flag when they find a miss or a rejected id): no scan at all
-#ifndef K1_NO_FILL_FLAG
     if (reinterpret_cast<const uint32_t*>(c.stats + 2 * kStatBlocks)[2 * kFillSlots + (gen & 1u)] == 0u) return;
-#endif
     const int64_t n_deal = dyn ? 1 : n_waves;
     const int64_t even8 = n_tiles / (n_waves * 8);
     const int claim_min = even8 < 1 ? 1 : (even8 > U ? U : (int)even8);
@@ -849,6 +791,80 @@ __global__ __launch_bounds__(256) void route_scatter_kernel(const int64_t* __res
 
 // ============================================================================================================ host
 
+namespace {
+
+// How K1 and K2 are launched.  Fixed at handle creation: launch_shape() sets the product's choice, which development builds
+// (build.py --dev -> libcoala_hip_dev.so, -DCOALA_DEV_KNOBS) then override from the environment (apply_dev_knobs).
+struct LaunchShape {
+    int k1_grid_cap;    // K1 blocks of the looping kernel
+    int k1_waves;       // K1 waves per block
+    bool k1_single;     // one wave per chunk, loop-free K1 (launches up to kK1SingleMaxChunks chunks)
+    int k1_passes;      // development builds: rows(-pairs) in flight per wave in K1 (COALA_K1_PASSES = 2 | 4 | 8 | 16); 0 = kK1Passes
+    int k2_grid_cap;    // K2 blocks
+    int k2_tile_rows;   // rows per verdict tile of K2; 0 = one chunk
+    int k2_sparse_max;  // tiles with at most this many misses are streamed compacted (0 = never)
+    int k2_unit_tiles;  // 1 = K2 deals its tiles dynamically (0 = static: wave w takes tiles w, w + n_waves, ...)
+};
+
+LaunchShape launch_shape(uint32_t cache_dim, bool host_tier) {
+    LaunchShape s;
+    // K1 blocks: one chunk per wave up to 131,072 rows.  Measured (tools/k1_insitu.py, tools/k1_bench): 28.5 k rows at 32 %
+    // hits in situ: 2048 blocks -> 22.3 us, 4096 -> 20.7, 8192 -> 20.6; all-hit 36,864 rows: 53.8 / 53.1 / 51.4 us;
+    // all-hit 123,904 rows: 192.5 / 192.3 / 190.1 / 185.3 us at 2048 / 4096 / 8192 / 16384; 1.08 M x 512 B: 232 -> 227 us
+    s.k1_grid_cap = 16384;
+    s.k1_waves = kK1Waves;
+    // one wave per chunk, no loop, no prefetch state for later chunks: with the lane-parallel probe it is ahead on every line of 1 KiB and more
+    // (default workload 17.5 -> 16.35 us, its all-hit leg 58.8 -> 56.6 us, 262,144 x 1 KiB and 123,904 x 4 KiB at every hit ratio:
+    // profiles/r03_k1_single_lane_parallel.txt) and behind on 512-B lines, whose 8-row waves need the software pipeline (12.3 vs 13.3 us at 72 k rows)
+    s.k1_single = cache_dim >= 256;
+    s.k1_passes = 0;
+    // K2 blocks: 24-64 when the cold tier is host memory.  The link, not the chip, is the limit, and
+    // what matters is the bytes of PCIe reads in flight (blocks x 4 waves x 16 KB): ~1 MB
+    // already runs the link at 56.0 GB/s; 4 MB (64 blocks) gives 56.6 GB/s but queues every
+    // other host access of the GPU -- AQL packets, kernargs, completion signals of kernels
+    // on OTHER streams -- behind ~50 us of reads: a 9-kernel sampler call overlapping the
+    // fill took 1.8 ms instead of 0.22 ms, and the prefetching epoch 11.7 s instead of 9.2 s.
+    // Full grid: 53.7 GB/s; 8 blocks: 43.1 GB/s.
+    // host tier: ~1 MB of reads in flight (blocks x 4 waves x rows-per-wave x line bytes).  A wave holds 16 KB of 4-KiB lines
+    // but only 4 KB of 512-B or 1-KiB lines, and with short lines the per-chunk ranking latency dominates, so the
+    // count scales with the line size: 24 / 32 / 64 / 64 blocks for cache_dim 1024 / 512 / 256 / 128
+    // (measured at cache_dim 128, 111 M x 128 table: 32 / 64 / 128 blocks -> 42.9 / 55.2 / 52.7 GB/s; 16 -> 22.4).
+    // 4-KiB lines: 16 / 20 / 24 / 32 blocks take 1417 / 1420 / 1445 / 1507 us per fill of the default workload on their own, and
+    // 1.550-1.585 / 1.526 / 1.524 / 1.529 ms per step (fill + gap) beside a consumer's training kernels, which stretch the
+    // fill by ~5 %: 20 blocks cost 0.2 % alone and give 1.5 % under load (profiles/r03_k2_grid_under_load.txt) -- that was the STATIC deal of tiles.
+    // With the dynamic deal (below) a few more blocks cost nothing alone, and what counts is a multiple of the 8 XCDs, whose turn it is block by
+    // block: 24 / 32 blocks run the loader's step in 1.438 / 1.441 ms alone and 1.452 / 1.450 beside the training kernels, 20 / 22 / 26 / 28 blocks in
+    // 1.448 / 1.448 / 1.445 / 1.456 and 1.470-1.479 / 1.467 / 1.467 / 1.461; 40: 1.448 and 1.480 (profiles/r04_k2_grid_under_load.txt)
+    const int host_blocks = std::min(64, std::max(24, 16 * 1024 / (int)cache_dim));
+    s.k2_grid_cap = host_tier ? host_blocks : kStatBlocks;
+    // verdict tile: 64 rows behind the narrow host-tier grid, one chunk behind the wide HBM-tier grid (miss_fill_kernel)
+    s.k2_tile_rows = host_tier ? 64 : 0;
+    // tiles with at most 32 of 64 rows missing are streamed compacted (tools/k2_sparse_probe.py, 28.5 k rows x 4 KiB: 32 % misses
+    // 52.4 -> 55.2 GB/s, 16 %: 47.4 -> 54.6, 8 %: 42.5 -> 52.1, 4 %: 36 -> 47; the 68 % default batch is unchanged, 48 costs it 1 %)
+    s.k2_sparse_max = host_tier ? 32 : 0;
+    // host tier: the tiles are dealt dynamically (miss_fill_kernel).  With 80-256 waves and a miss count that varies from tile to tile a static deal
+    // leaves the waves' shares 15-30 % apart and the last ones streaming alone (tools/k2_sparse_probe.py, 28.5 k rows x 4 KiB, static -> dynamic:
+    // 100 % misses 52.4 -> 56.7 GB/s, 68 % (the default workload) 55.8 -> 56.3, 32 % 52.7 -> 55.9, 16 % (the 8-GPU steady state) 50.4 -> 54.8,
+    // 8 % 49.7 -> 53.2, 2 % 42.7 -> 45.3; a launch with nothing to fill 4 -> 8 us: profiles/r04_k2_dynamic_deal.txt)
+    s.k2_unit_tiles = host_tier ? 1 : 0;
+    return s;
+}
+
+#ifdef COALA_DEV_KNOBS
+void apply_dev_knobs(LaunchShape& s) {
+    if (const char* e = getenv("COALA_K1_PASSES")) { int v = atoi(e); if (v == 2 || v == 4 || v == 8 || v == 16) s.k1_passes = v; }
+    if (const char* e = getenv("COALA_K1_GRID")) { int g = atoi(e); if (g >= 1 && g <= 65535) s.k1_grid_cap = g; }
+    if (const char* e = getenv("COALA_K1_WAVES")) { int w = atoi(e); if (w == 1 || w == 2 || w == 4) s.k1_waves = w; }
+    if (const char* e = getenv("COALA_K1_SINGLE")) s.k1_single = atoi(e) != 0;
+    if (const char* e = getenv("COALA_K2_TILE_ROWS")) { int t = atoi(e); if (t == 0 || t == 8 || t == 16 || t == 32 || t == 64) s.k2_tile_rows = t; }
+    if (const char* e = getenv("COALA_K2_GRID")) { int g = atoi(e); if (g >= 1 && g <= kStatBlocks) s.k2_grid_cap = g; }
+    if (const char* e = getenv("COALA_K2_SPARSE")) { int g = atoi(e); if (g >= 0 && g <= 64) s.k2_sparse_max = g; }
+    if (const char* e = getenv("COALA_K2_UNIT_TILES")) { int g = atoi(e); if (g >= 0 && g <= 1) s.k2_unit_tiles = g; }   // 0: the static deal
+}
+#endif
+
+} // namespace
+
 struct coala_cache {
     coala_cache_config_t cfg;
     CacheDev d;
@@ -871,13 +887,7 @@ struct coala_cache {
     bool order_set = false;
     hipEvent_t order_ev = nullptr;
     uint64_t table_bytes = 0;
-    int k2_grid_cap = kStatBlocks;        // K2 blocks: 24-64 when the cold tier is host memory.  The link, not the chip, is the limit, and
-                                          // what matters is the bytes of PCIe reads in flight (blocks x 4 waves x 16 KB): ~1 MB
-                                          // already runs the link at 56.0 GB/s; 4 MB (64 blocks) gives 56.6 GB/s but queues every
-                                          // other host access of the GPU -- AQL packets, kernargs, completion signals of kernels
-                                          // on OTHER streams -- behind ~50 us of reads: a 9-kernel sampler call overlapping the
-                                          // fill took 1.8 ms instead of 0.22 ms, and the prefetching epoch 11.7 s instead of 9.2 s.
-                                          // Full grid: 53.7 GB/s; 8 blocks: 43.1 GB/s.  COALA_K2_GRID overrides.
+    LaunchShape shape;                    // K1 / K2 launch shapes (launch_shape)
     int32_t* color_pin = nullptr;         // pinned staging for coala_cache_color_counts
     int32_t* color_pin_async = nullptr;   // pinned staging + event of a pending coala_cache_color_counts_async
     hipEvent_t color_ev = nullptr;
@@ -886,16 +896,7 @@ struct coala_cache {
     std::vector<std::pair<int64_t, int64_t>> open_filled; // position ranges of the open batch already handed to a fill (sorted)
     int64_t open_filled_rows = 0;
     Redirect open_redirect{0, 0, nullptr, nullptr};       // the open batch's redirect (set by the probe, reused by its fills)
-    int k2_tile_rows = 0;                 // rows per verdict tile of K2: 64 for a host cold tier, 0 = one chunk (COALA_K2_TILE_ROWS)
-    int k2_sparse_max = 0;                // tiles with at most this many misses are streamed compacted (host tier; 0 = never)
-    int k2_unit_tiles = 0;                // host tier: 1 = K2 deals its tiles dynamically (0 = static: wave w takes tiles w, w + n_waves, ...)
     int fill_launches = 0;                // fill launches of the current batch so far: each takes its own ticket counter (kFillSlots per batch)
-    int k1_passes = 0;                    // development builds: rows(-pairs) in flight per wave in K1 (COALA_K1_PASSES = 2 | 4 | 8 | 16); 0 = the product's choice per line size
-    int k1_grid_cap = 16384;              // K1 blocks: one chunk per wave up to 131,072 rows.  Measured (tools/k1_insitu.py, tools/k1_bench): 28.5 k rows at 32 %
-                                          // hits in situ: 2048 blocks -> 22.3 us, 4096 -> 20.7, 8192 -> 20.6; all-hit 36,864 rows: 53.8 / 53.1 / 51.4 us;
-                                          // all-hit 123,904 rows: 192.5 / 192.3 / 190.1 / 185.3 us at 2048 / 4096 / 8192 / 16384; 1.08 M x 512 B: 232 -> 227 us
-    int k1_waves = kK1Waves;              // K1 waves per block
-    int k1_single = -1;                   // one wave per chunk, loop-free K1: -1 = by line size (lines of 1 KiB and more), 0 / 1 = COALA_K1_SINGLE of the development build
     uint64_t rows_total = 0;              // rows submitted since the last stats reset (hits = rows - misses - rejected)
     uint64_t cum_hit = 0, cum_miss = 0;   // totals folded in whenever coala_cache_stats resets the device counters
     uint64_t prof_hit0 = 0, prof_miss0 = 0; // totals at the last profile reset
@@ -1088,9 +1089,6 @@ int coala_cache_create(const coala_cache_config_t* cfg, coala_cache_t** out) {
     d.cold = cfg->cold_table;
     // 32-bit tags whenever every id fits (0xFFFFFFFF is the empty tag): a set is then one 128-B line instead of two
     d.tag32 = (!(cfg->flags & COALA_FLAG_TAG64) && cfg->num_rows <= 0xFFFFFFFFull) ? 1u : 0u;
-#ifdef COALA_DEV_KNOBS
-    if (const char* e = getenv("COALA_K1_TAG64")) if (atoi(e) == 1) d.tag32 = 0u;
-#endif
     const uint64_t tag_bytes = d.tag32 ? 4 : 8;
     int rc = COALA_OK;
     auto alloc = [&](void** p, uint64_t bytes) -> int {
@@ -1134,42 +1132,13 @@ int coala_cache_create(const coala_cache_config_t* cfg, coala_cache_t** out) {
             d.node_color = h->node_color_dev;
         }
         h->gen = 0;
-#ifdef COALA_DEV_KNOBS
-        if (const char* e = getenv("COALA_K1_PASSES")) { int v = atoi(e); if (v == 2 || v == 4 || v == 8 || v == 16) h->k1_passes = v; }
-        if (const char* e = getenv("COALA_K1_GRID")) { int g = atoi(e); if (g >= 1 && g <= 65535) h->k1_grid_cap = g; }
-        if (const char* e = getenv("COALA_K1_WAVES")) { int w = atoi(e); if (w == 1 || w == 2 || w == 4) h->k1_waves = w; }
-        if (const char* e = getenv("COALA_K1_SINGLE")) h->k1_single = atoi(e) != 0 ? 1 : 0;
-#endif
         {
             hipPointerAttribute_t attr;
             const bool host_tier = hipPointerGetAttributes(&attr, cfg->cold_table) == hipSuccess && attr.type == hipMemoryTypeHost;
             (void)hipGetLastError(); // an unregistered pointer is reported as an error: not ours to keep
-            // host tier: ~1 MB of reads in flight (blocks x 4 waves x rows-per-wave x line bytes).  A wave holds 16 KB of 4-KiB lines
-            // but only 4 KB of 512-B or 1-KiB lines, and with short lines the per-chunk ranking latency dominates, so the
-            // count scales with the line size: 24 / 32 / 64 / 64 blocks for cache_dim 1024 / 512 / 256 / 128
-            // (measured at cache_dim 128, 111 M x 128 table: 32 / 64 / 128 blocks -> 42.9 / 55.2 / 52.7 GB/s; 16 -> 22.4).
-            // 4-KiB lines: 16 / 20 / 24 / 32 blocks take 1417 / 1420 / 1445 / 1507 us per fill of the default workload on their own, and
-            // 1.550-1.585 / 1.526 / 1.524 / 1.529 ms per step (fill + gap) beside a consumer's training kernels, which stretch the
-            // fill by ~5 %: 20 blocks cost 0.2 % alone and give 1.5 % under load (profiles/r03_k2_grid_under_load.txt) -- that was the STATIC deal of tiles.
-            // With the dynamic deal (below) a few more blocks cost nothing alone, and what counts is a multiple of the 8 XCDs, whose turn it is block by
-            // block: 24 / 32 blocks run the loader's step in 1.438 / 1.441 ms alone and 1.452 / 1.450 beside the training kernels, 20 / 22 / 26 / 28 blocks in
-            // 1.448 / 1.448 / 1.445 / 1.456 and 1.470-1.479 / 1.467 / 1.467 / 1.461; 40: 1.448 and 1.480 (profiles/r04_k2_grid_under_load.txt)
-            const int host_blocks = std::min(64, std::max(24, 16 * 1024 / (int)d.cache_dim));
-            h->k2_grid_cap = host_tier ? host_blocks : kStatBlocks;
-            h->k2_tile_rows = host_tier ? 64 : 0;
-            // tiles with at most 32 of 64 rows missing are streamed compacted (tools/k2_sparse_probe.py, 28.5 k rows x 4 KiB: 32 % misses
-            // 52.4 -> 55.2 GB/s, 16 %: 47.4 -> 54.6, 8 %: 42.5 -> 52.1, 4 %: 36 -> 47; the 68 % default batch is unchanged, 48 costs it 1 %)
-            h->k2_sparse_max = host_tier ? 32 : 0;
-            // host tier: the tiles are dealt dynamically (miss_fill_kernel).  With 80-256 waves and a miss count that varies from tile to tile a static deal
-            // leaves the waves' shares 15-30 % apart and the last ones streaming alone (tools/k2_sparse_probe.py, 28.5 k rows x 4 KiB, static -> dynamic:
-            // 100 % misses 52.4 -> 56.7 GB/s, 68 % (the default workload) 55.8 -> 56.3, 32 % 52.7 -> 55.9, 16 % (the 8-GPU steady state) 50.4 -> 54.8,
-            // 8 % 49.7 -> 53.2, 2 % 42.7 -> 45.3; a launch with nothing to fill 4 -> 8 us: profiles/r04_k2_dynamic_deal.txt)
-            h->k2_unit_tiles = host_tier ? 1 : 0;
+            h->shape = launch_shape(d.cache_dim, host_tier);
 #ifdef COALA_DEV_KNOBS
-            if (const char* e = getenv("COALA_K2_TILE_ROWS")) { int t = atoi(e); if (t == 0 || t == 8 || t == 16 || t == 32 || t == 64) h->k2_tile_rows = t; }
-            if (const char* e = getenv("COALA_K2_GRID")) { int g = atoi(e); if (g >= 1 && g <= kStatBlocks) h->k2_grid_cap = g; }
-            if (const char* e = getenv("COALA_K2_SPARSE")) { int g = atoi(e); if (g >= 0 && g <= 64) h->k2_sparse_max = g; }
-            if (const char* e = getenv("COALA_K2_UNIT_TILES")) { int g = atoi(e); if (g >= 0 && g <= 1) h->k2_unit_tiles = g; }   // 0: the static deal
+            apply_dev_knobs(h->shape);
 #endif
         }
         if (cfg->max_batch) rc = ensure_scratch(h, cfg->max_batch, nullptr);
@@ -1376,26 +1345,20 @@ static int read_feature_impl(coala_cache_t* h, float* out, const int64_t* idx, i
                 using GK = Geo<CD, VEC, NP>;
                 using GR = Geo<CD, VEC, NPR>;
                 const int64_t chunks = redir ? (n + GR::R - 1) / GR::R : (n + GK::R - 1) / GK::R;
-                // one wave per chunk, no loop, no prefetch state for later chunks: with the lane-parallel probe it is ahead on every line of 1 KiB and more
-                // (default workload 17.5 -> 16.35 us, its all-hit leg 58.8 -> 56.6 us, 262,144 x 1 KiB and 123,904 x 4 KiB at every hit ratio:
-                // profiles/r03_k1_single_lane_parallel.txt) and behind on 512-B lines, whose 8-row waves need the software pipeline (12.3 vs 13.3 us at 72 k rows)
-                const bool want_single = h->k1_single < 0 ? (CD >= 256) : (h->k1_single != 0);
-                const bool single = want_single && chunks <= kK1SingleMaxChunks;
-                const dim3 grid(grid_for(chunks, h->k1_waves, single ? (int)((kK1SingleMaxChunks + h->k1_waves - 1) / h->k1_waves) : h->k1_grid_cap)), block(64 * h->k1_waves);
-                if (single) {
-                    if (redir && full) ps.launch(probe_gather_kernel<CD, VEC, TAG, NPR, true, 0, true, true>, grid, block, idx, out, n, gen, (uint32_t)grid.x, d, rd);
-                    else if (redir) ps.launch(probe_gather_kernel<CD, VEC, TAG, NPR, false, 0, true, true>, grid, block, idx, out, n, gen, (uint32_t)grid.x, d, rd);
-                    else if (full) ps.launch(probe_gather_kernel<CD, VEC, TAG, NP, true, 0, false, true>, grid, block, idx, out, n, gen, (uint32_t)grid.x, d, rd);
-                    else ps.launch(probe_gather_kernel<CD, VEC, TAG, NP, false, 0, false, true>, grid, block, idx, out, n, gen, (uint32_t)grid.x, d, rd);
-                } else if (redir && full) ps.launch(probe_gather_kernel<CD, VEC, TAG, NPR, true, 0, true>, grid, block, idx, out, n, gen, (uint32_t)grid.x, d, rd);
-                else if (redir) ps.launch(probe_gather_kernel<CD, VEC, TAG, NPR, false, 0, true>, grid, block, idx, out, n, gen, (uint32_t)grid.x, d, rd);
-                else if (full) ps.launch(probe_gather_kernel<CD, VEC, TAG, NP, true>, grid, block, idx, out, n, gen, (uint32_t)grid.x, d, rd);
-                else ps.launch(probe_gather_kernel<CD, VEC, TAG, NP, false>, grid, block, idx, out, n, gen, (uint32_t)grid.x, d, rd);
+                const LaunchShape& ls = h->shape;
+                const bool single = ls.k1_single && chunks <= kK1SingleMaxChunks;
+                const dim3 grid(grid_for(chunks, ls.k1_waves, single ? (int)((kK1SingleMaxChunks + ls.k1_waves - 1) / ls.k1_waves) : ls.k1_grid_cap)), block(64 * ls.k1_waves);
+                auto pick = [&](auto single_c) {
+                    constexpr bool S = decltype(single_c)::value;
+                    if (redir) return full ? probe_gather_kernel<CD, VEC, TAG, NPR, true, true, S> : probe_gather_kernel<CD, VEC, TAG, NPR, false, true, S>;
+                    return full ? probe_gather_kernel<CD, VEC, TAG, NP, true, false, S> : probe_gather_kernel<CD, VEC, TAG, NP, false, false, S>;
+                };
+                ps.launch(single ? pick(std::true_type{}) : pick(std::false_type{}), grid, block, idx, out, n, gen, (uint32_t)grid.x, d, rd);
             };
 #ifdef COALA_DEV_KNOBS
-            if (h->k1_passes) { // development builds: rows in flight per wave from the environment
+            if (h->shape.k1_passes) { // development builds: rows in flight per wave from the environment
                 auto by_np = [&](auto tag_c) {
-                    switch (h->k1_passes) {
+                    switch (h->shape.k1_passes) {
                         case 2: launch_k1(tag_c, std::integral_constant<int, 2>{}); break;
                         case 8: launch_k1(tag_c, std::integral_constant<int, 8>{}); break;
                         case 16: launch_k1(tag_c, std::integral_constant<int, (Geo<CD, VEC, 16>::R <= 32 ? 16 : 8)>{}); break;
@@ -1405,26 +1368,25 @@ static int read_feature_impl(coala_cache_t* h, float* out, const int64_t* idx, i
                 if (d.tag32) by_np(uint32_t{}); else by_np(uint64_t{});
             } else
 #endif
-            if (d.tag32) launch_k1(uint32_t{}, std::integral_constant<int, k1_np32(CD)>{});
-            else launch_k1(uint64_t{}, std::integral_constant<int, 4>{});
+            if (d.tag32) launch_k1(uint32_t{}, std::integral_constant<int, kK1Passes>{});
+            else launch_k1(uint64_t{}, std::integral_constant<int, kK1Passes>{});
         }
         if ((phases & kPhaseFill) && fill_rows > 0) {
-            // verdict tile: 64 rows behind the narrow host-tier grid, one chunk behind the wide HBM-tier grid (see the kernel)
-            const int tile_rows = h->k2_tile_rows > 0 ? h->k2_tile_rows : G::R;
+            const int tile_rows = h->shape.k2_tile_rows > 0 ? h->shape.k2_tile_rows : G::R;
             return for_each_range_set(begins, ends, n_ranges, [&](const RangeSet& rs) -> int {
                 const bool last_set = ++set_no == n_sets;
                 ProfScope ps(h, s, 2, 0, nullptr, last_set ? fe_end : nullptr);
                 if (rode && last_set) rode[1] = ps.on ? ps.b : fe_end;
                 const int64_t tiles = ((int64_t)rs.total + tile_rows - 1) / tile_rows;
-                const dim3 grid(grid_for(tiles, 4, h->k2_grid_cap));
+                const dim3 grid(grid_for(tiles, 4, h->shape.k2_grid_cap));
                 // dynamic deal (host tier, more tiles than waves, one of the batch's first kFillSlots fill launches): this launch's ticket counter
                 const int64_t waves = (int64_t)grid.x * 4;
                 int dyn_slot = -1;
-                if (h->k2_unit_tiles > 0 && tiles > waves && tiles < 0x7FFFFFFF && h->fill_launches < kFillSlots)
+                if (h->shape.k2_unit_tiles > 0 && tiles > waves && tiles < 0x7FFFFFFF && h->fill_launches < kFillSlots)
                     dyn_slot = (int)((gen & 1u) * kFillSlots) + h->fill_launches;
                 h->fill_launches++;
-                if (redir) ps.launch(miss_fill_kernel<CD, VEC, true>, grid, dim3(256), d, idx, out, tile_rows, h->k2_sparse_max, gen, rs, rd, dyn_slot);
-                else ps.launch(miss_fill_kernel<CD, VEC, false>, grid, dim3(256), d, idx, out, tile_rows, h->k2_sparse_max, gen, rs, rd, dyn_slot);
+                if (redir) ps.launch(miss_fill_kernel<CD, VEC, true>, grid, dim3(256), d, idx, out, tile_rows, h->shape.k2_sparse_max, gen, rs, rd, dyn_slot);
+                else ps.launch(miss_fill_kernel<CD, VEC, false>, grid, dim3(256), d, idx, out, tile_rows, h->shape.k2_sparse_max, gen, rs, rd, dyn_slot);
                 return COALA_OK;
             });
         }
@@ -1575,36 +1537,6 @@ int coala_cache_scatter(coala_cache_t* h, float* out, const float* src, const in
     const int64_t b = 0;
     return coala_cache_scatter_ranges(h, out, src, map, &b, &n, 1, stream);
 }
-
-#ifdef COALA_DEV_KNOBS
-// not part of the ABI.  stage 0: empty kernel on K1's grid; 1: + ids; 2: + tag sets, ballots; 3: + line loads of the hit rows (no stores);
-// 4: the product kernel without miss bookkeeping; 5: the product kernel (on a generation nobody consumes).  Any line size / tag width.
-int coala_dev_k1_stage(coala_cache_t* h, float* out, const int64_t* idx, int64_t n, int stage, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    CacheDev d = h->d;
-    return dispatch_geo(d.cache_dim, true, [&](auto geo) -> int {
-        constexpr int CD = geo_cd(geo);
-        constexpr int VEC = geo_vec(geo);
-        using GK = Geo<CD, VEC, 4>;
-        const int64_t chunks = (n + GK::R - 1) / GK::R;
-        const dim3 grid(grid_for(chunks, h->k1_waves, h->k1_grid_cap)), block(64 * h->k1_waves);
-        const Redirect rd{0, 0, nullptr, nullptr};
-        auto go = [&](auto tag_c) {
-            using TAG = decltype(tag_c);
-            switch (stage) {
-                case 0: hipLaunchKernelGGL(k1_empty_kernel, grid, block, 0, s); break;
-                case 1: hipLaunchKernelGGL((probe_gather_kernel<CD, VEC, TAG, 4, true, 11>), grid, block, 0, s, idx, out, n, 0xFFFFFFF0u, (uint32_t)grid.x, d, rd); break;
-                case 2: hipLaunchKernelGGL((probe_gather_kernel<CD, VEC, TAG, 4, true, 12>), grid, block, 0, s, idx, out, n, 0xFFFFFFF0u, (uint32_t)grid.x, d, rd); break;
-                case 3: hipLaunchKernelGGL((probe_gather_kernel<CD, VEC, TAG, 4, true, 13>), grid, block, 0, s, idx, out, n, 0xFFFFFFF0u, (uint32_t)grid.x, d, rd); break;
-                case 4: hipLaunchKernelGGL((probe_gather_kernel<CD, VEC, TAG, 4, true, 1>), grid, block, 0, s, idx, out, n, 0xFFFFFFF0u, (uint32_t)grid.x, d, rd); break;
-                default: hipLaunchKernelGGL((probe_gather_kernel<CD, VEC, TAG, 4, true, 0>), grid, block, 0, s, idx, out, n, 0xFFFFFFF1u, (uint32_t)grid.x, d, rd); break;
-            }
-        };
-        if (d.tag32) go(uint32_t{}); else go(uint64_t{});
-        return COALA_OK;
-    });
-}
-#endif
 
 int coala_cache_color_counts(coala_cache_t* h, int32_t* dst, int32_t n_entries, void* stream) {
     if (!h || !dst) return fail(COALA_EINVAL, "null argument");

@@ -287,7 +287,6 @@ struct coala_comm {
     // coala_comm_fetch_events: begin / end events of a bucketed fetch without packets of their own on the caller's stream; a ring of triples
     // (begin on the probe's launch, end on the last fill launch of the caller's stream, end behind the last row round on the communicator's stream)
     int fetch_events = 0;           // 0 off, 1 end events only, 2 begin event too (coala_comm_fetch_events)
-    bool plain_events = false;      // development builds, COALA_COMM_PLAIN_EVENTS=1: every event recorded behind its kernel, every round waited for (the round-3 form; tools/dist_packets_probe.py)
     static constexpr int kFetchRing = 2048;
     std::vector<hipEvent_t> fev;    // [3 * kFetchRing], created on first use
     uint64_t fev_calls = 0;
@@ -315,9 +314,6 @@ int finish_create(coala_comm* c) {
         const int r = atoi(e);
         if (r >= 1 && r <= kMaxRounds) c->rounds = r;
     }
-#ifdef COALA_DEV_KNOBS
-    if (const char* e = getenv("COALA_COMM_PLAIN_EVENTS")) c->plain_events = atoi(e) != 0;
-#endif
     // The communication stream gets the highest stream priority: HIP keeps priority levels on separate hardware queues, so the row
     // exchange can never be queued behind the cold fill it is meant to run beside (with equal priorities the streams of a process
     // share GPU_MAX_HW_QUEUES = 4 queues in creation order), and its few workgroups are scheduled ahead of the fill's.
@@ -721,7 +717,7 @@ static int fetch_impl(coala_cache_t* h, coala_comm_t* c, float* out, const int64
     // Events of this fetch.  Every hipEventRecord on the caller's stream is one more barrier packet between the kernels of a saturated
     // stream (6-12 us each: DESIGN.md section 6), so whatever can ride ON a launch does: the hand-over events of the fill rounds always, and
     // -- opt-in, bucketed fetches: coala_comm_fetch_events -- the begin / end events a caller needs for timing and for its consumer's stream.
-    const bool ev_mode = c->fetch_events && bucketed && n > 0 && !c->plain_events;
+    const bool ev_mode = c->fetch_events && bucketed && n > 0;
     hipEvent_t ev_begin = nullptr, ev_end_st = nullptr, ev_end_cs = nullptr;
     if (ev_mode) {
         if (c->fev.empty()) c->fev.assign(3 * (size_t)coala_comm::kFetchRing, nullptr);
@@ -733,7 +729,7 @@ static int fetch_impl(coala_cache_t* h, coala_comm_t* c, float* out, const int64
         ev_end_cs = c->fev[3 * slot + 2];
     }
     hipEvent_t rode = nullptr;
-    if ((rc = coala_serve_probe_redirect_ev_(h, c->rows_send, c->recv_ids, (int64_t)total_recv, &rd, st, c->plain_events ? nullptr : ev_begin, &rode))) return broke(rc);
+    if ((rc = coala_serve_probe_redirect_ev_(h, c->rows_send, c->recv_ids, (int64_t)total_recv, &rd, st, ev_begin, &rode))) return broke(rc);
     if (ev_begin && rode != ev_begin && hipEventRecord(ev_begin, st) != hipSuccess) return broke(fail(COALA_EHIP, "hipEventRecord failed"));
     // 6. rounds: fill slice k of every peer's segment on the caller's stream, ship it on the comm stream while slice k+1 fills
     const int K = (G == 1 && !loop) ? 1 : c->rounds;
@@ -767,8 +763,7 @@ static int fetch_impl(coala_cache_t* h, coala_comm_t* c, float* out, const int64
         // the last round's is the fetch's end event on this stream
         const bool last = k == K - 1;
         hipEvent_t fill_ev = (last && ev_end_st) ? ev_end_st : (exchange_rows ? c->ev_fill[k] : nullptr);
-        if ((rc = coala_serve_fill_ranges_ev_(h, c->rows_send, c->recv_ids, (int64_t)total_recv, fb.data(), fe.data(), nr, st, c->plain_events ? nullptr : fill_ev, &rode))) return broke(rc);
-        if (c->plain_events) rode = nullptr;
+        if ((rc = coala_serve_fill_ranges_ev_(h, c->rows_send, c->recv_ids, (int64_t)total_recv, fb.data(), fe.data(), nr, st, fill_ev, &rode))) return broke(rc);
         const bool must_be_mine = fill_ev && fill_ev == ev_end_st;    // handed out to the caller: a borrowed event will not do
         if (fill_ev && (rode == nullptr || (must_be_mine && rode != fill_ev)) && hipEventRecord(fill_ev, st) != hipSuccess)
             return broke(fail(COALA_EHIP, "hipEventRecord failed"));
@@ -808,7 +803,7 @@ static int fetch_impl(coala_cache_t* h, coala_comm_t* c, float* out, const int64
         }
         // 7. un-permute round by round as the rows arrive (bucketed: nothing to un-permute, and the communicator's stream completes its rounds
         //    in order -- the caller's stream waits for the last one only; the workspaces are safe to reuse behind that wait)
-        for (int k = (bucketed && !c->plain_events) ? K - 1 : 0; k < K; ++k) {
+        for (int k = bucketed ? K - 1 : 0; k < K; ++k) {
             if (hipStreamWaitEvent(st, x_evs[k], 0) != hipSuccess) return broke(fail(COALA_EHIP, "hipStreamWaitEvent failed"));
             if (!bucketed && (rc = coala_cache_scatter_ranges(h, out, c->rows_recv, c->map, sb.data() + (size_t)k * G, se.data() + (size_t)k * G, G, st)))
                 return broke(rc);

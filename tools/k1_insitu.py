@@ -43,36 +43,6 @@ batches = [sampler.sample(graph, train_ids[s * batch: (s + 1) * batch].cuda(), s
 torch.cuda.synchronize()
 print(f"# setup {time.time() - t0:.1f}s; rows per minibatch ~{sum(b.numel() for b in batches[400:]) / 220:.0f}", flush=True)
 ctrl = P.SSD_GNN_SSD_Controllers(1, 4096, 1024, 0, 0, dim, True)
-if "--stages" in sys.argv:
-    # where the fixed cost goes: K1's dependency chain cut after each link (development switch of the kernel itself: any line size
-    # and tag width), launched right behind a real step's cold fill, on K1's own grid
-    import ctypes as C
-    from COALA_GNN_Pybind import current_stream
-    L = C.CDLL(os.environ["COALA_HIP_LIB"])
-    L.coala_dev_k1_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
-    cache = P.Isolated_Cache(ctrl, None, 0, 1, cache_mb, table.device_ptr, num_rows=rows, sync=False, max_batch=max_rows)
-    out = torch.empty((max_rows, dim), dtype=torch.float32, device="cuda")
-    for b in batches[:420]:
-        cache.read_feature(out.data_ptr(), b.data_ptr(), b.numel())
-    torch.cuda.synchronize()
-    names = {-1: "empty event bracket", 0: "empty kernel on K1's grid (launch + drain)", 1: "+ ids", 2: "+ tag sets, ballots", 3: "+ line loads of the hit rows (no stores)",
-             4: "product kernel without miss bookkeeping", 5: "product kernel"}
-    print(f"# dim {dim}, tags {cache.geometry().tag_set_bytes} B/set, cache {cache_mb} MiB; separate hipEvent brackets (each contains the ~4.5 us of the empty bracket)")
-    for stage in (-1, 0, 1, 2, 3, 4, 5, 4, 5):
-        evs = []
-        for k, b in enumerate(batches[420:619]):
-            cache.read_feature(out.data_ptr(), b.data_ptr(), b.numel())      # a real step: K1 + the PCIe-bound K2
-            nxt = batches[421 + k]
-            a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            if stage >= 0:
-                L.coala_dev_k1_stage(cache._h, out.data_ptr(), nxt.data_ptr(), nxt.numel(), stage, current_stream())
-            e.record()
-            evs.append((a, e))
-        torch.cuda.synchronize()
-        us = sorted(x.elapsed_time(y) * 1e3 for x, y in evs)
-        print(f"stage {stage:2d} {names[stage]:45s} mean {sum(us) / len(us):6.2f} us   median {us[len(us) // 2]:6.2f} us", flush=True)
-    sys.exit(0)
 variants = [a for a in sys.argv[1:] if not a.startswith("--")] or ["GRID=2048"]
 # OUT_BUFFERS=n: the fetches rotate over n output buffers.  bench.py and the loaders get a fresh tensor from the manager for every fetch (two
 # or three blocks of torch's allocator in rotation); with ONE buffer the rows of step s may still sit in the 256 MiB Infinity Cache when step
