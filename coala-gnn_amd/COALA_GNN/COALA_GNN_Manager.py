@@ -414,6 +414,22 @@ def owner_counts_present(mgr, batch):
     return oc is not None and oc.numel() == mgr.MPI_comm_manager.local_size and batch[2][0].src_nodes is batch[0]
 
 
+SAMPLER_ITEM_LIMIT = 8192 * 1024   # items one sampled layer may hold (COALA_GNN.sampler.ITEM_LIMIT)
+
+
+def request_buffer_rows(batch_size, fan_out, num_rows=None):
+    """Rows one minibatch may request, which sizes the fetch buffers: batch_size * prod(f + 1) for fixed fan-outs (:79-81).  A list
+    with a full layer (-1, every in-edge) has no such product; its input nodes are distinct node ids of one sampled layer, so they are
+    bounded by the sampler's item limit and by the table's row count."""
+    fan = [int(f) for f in fan_out]
+    if -1 in fan:
+        return SAMPLER_ITEM_LIMIT if num_rows is None else min(SAMPLER_ITEM_LIMIT, int(num_rows))
+    n = batch_size
+    for f in fan:
+        n *= f + 1
+    return n
+
+
 class COALA_GNN_Manager(object):
     def __init__(self, node_distributor, num_ssds, page_size, num_elems, ssd_read_offset, cache_size,  # MB
                  batch_size, fan_out, dim, MPI_comm_manager, device, cache_backend="nvshmem", sim_buf=None,
@@ -453,9 +469,7 @@ class COALA_GNN_Manager(object):
         device_id = getattr(MPI_comm_manager, "device_index", MPI_comm_manager.local_rank)
         self.SSD_Controllers = SSD_GNN_SSD_Controllers(num_ssds, page_size, num_elems, ssd_read_offset, device_id, dim,
                                                        self.is_simulation)
-        self.max_sample_size = batch_size                     # :79-81
-        for i in fan_out:
-            self.max_sample_size *= (int(i) + 1)
+        self.max_sample_size = request_buffer_rows(batch_size, fan_out, num_rows)   # :79-81
 
         dm = None if node_distributor is None else node_distributor.distribute_manager
         G = MPI_comm_manager.local_size

@@ -11,9 +11,11 @@ import torch
 
 from COALA_GNN_Pybind import _capi, current_stream
 
-__all__ = ["NeighborSampler", "CSCGraph", "Block"]
+__all__ = ["NeighborSampler", "CSCGraph", "Block", "ITEM_LIMIT"]
 
 _lib = _capi.load()
+
+ITEM_LIMIT = 8192 * 1024   # items (destination nodes + neighbour slots) one layer may hold (coala_sampler.hip: kMaxTiles * kTile)
 
 
 class CSCGraph(object):
@@ -27,10 +29,18 @@ class CSCGraph(object):
         self.num_edges = self.indices.numel()
         self.device = self.indptr.device
         self.ndata = dict(ndata or {})
+        self._max_in_degree = None
         self._h = C.c_void_p()
         dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _capi.check(_lib.coala_sampler_create(dev, self.indptr.data_ptr(), self.indices.data_ptr(), self.num_nodes,
                                               self.num_edges, C.byref(self._h)))
+
+    @property
+    def max_in_degree(self):
+        """Largest in-degree of the graph: bounds the buffers of a full layer (fan-out -1).  Computed once, on first use."""
+        if self._max_in_degree is None:
+            self._max_in_degree = int((self.indptr[1:] - self.indptr[:-1]).max().item()) if self.num_nodes > 0 else 0
+        return self._max_in_degree
 
     def close(self):
         if getattr(self, "_h", None):
@@ -70,13 +80,43 @@ class _MeanAggregate(torch.autograd.Function):
         return grad_src, None
 
 
+class _MeanAggregateCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_mean_aggregate_csr): row d averages h_src[indices[indptr[d]:indptr[d+1]]]."""
+
+    @staticmethod
+    def forward(ctx, h_src, indptr, indices):
+        h = h_src.contiguous()
+        n_dst = indptr.numel() - 1
+        out = torch.empty((n_dst, h.shape[1]), dtype=torch.float32, device=h.device)
+        _capi.check(_lib.coala_block_mean_aggregate_csr(h.device.index or 0, indptr.data_ptr(), indices.data_ptr(), h.data_ptr(), out.data_ptr(),
+                                                        n_dst, h.shape[1], current_stream()))
+        ctx.save_for_backward(indptr, indices)
+        ctx.src_shape = h.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        indptr, indices = ctx.saved_tensors
+        g = grad_out.contiguous()
+        grad_src = torch.zeros(ctx.src_shape, dtype=torch.float32, device=g.device)
+        _capi.check(_lib.coala_block_mean_aggregate_csr_backward(g.device.index or 0, indptr.data_ptr(), indices.data_ptr(), g.data_ptr(),
+                                                                 grad_src.data_ptr(), indptr.numel() - 1, g.shape[1], current_stream()))
+        return grad_src, None, None
+
+
 class Block(object):
-    """One message-flow block in fixed-stride form: dst node d aggregates src rows nbr[d, j] >= 0.
+    """One message-flow block: dst node d aggregates src rows nbr[d, j] >= 0 (fixed-stride form, a fixed fan-out), or
+    indices[indptr[d]:indptr[d+1]] (ragged CSR form, a full layer: nbr is None).
     The first num_dst source nodes ARE the destination nodes (DGL's to_block convention)."""
 
-    def __init__(self, src_nodes, nbr, num_dst, graph=None, dst_in_src=None, dst_nodes=None, owner_counts=None, owner_counts_host=None):
+    def __init__(self, src_nodes, nbr, num_dst, graph=None, dst_in_src=None, dst_nodes=None, owner_counts=None, owner_counts_host=None,
+                 indptr=None, indices=None):
         self.src_nodes = src_nodes          # int64 [num_src] global ids
-        self.nbr = nbr                      # int32 [num_dst, fanout], -1 padded
+        self.nbr = nbr                      # int32 [num_dst, fanout], -1 padded; None for a full layer
+        self.indptr = indptr                # int64 [num_dst + 1] (full layer) or None
+        self.indices = indices              # int32 [E]: local source index of each in-edge (full layer) or None
         self.num_src = int(src_nodes.numel())
         self.num_dst = int(num_dst)
         # Owner-bucketed input layer (NeighborSampler(bucket_by_owner=G)): src_nodes is bucket 0 | bucket 1 | ... (stable inside a
@@ -100,8 +140,7 @@ class Block(object):
     def tensors(self):
         """Every device tensor this block holds (for cross-stream lifetime bookkeeping by the prefetching loader)."""
         yield self.src_nodes
-        yield self.nbr
-        for t in (self.dst_in_src, self.owner_counts):
+        for t in (self.nbr, self.indptr, self.indices, self.dst_in_src, self.owner_counts):
             if t is not None:
                 yield t
         for d in (self.srcdata, self.dstdata):
@@ -123,12 +162,24 @@ class Block(object):
 
     def mean_aggregate(self, h_src):
         """Mean of the sampled neighbours' rows for every dst node: fp32 [num_dst, dim] (GraphSAGE 'mean').  Native kernel for
-        fp32 rows on the GPU (fan-out <= 32); plain torch otherwise."""
+        fp32 rows on the GPU (fan-out <= 32, or the ragged form of a full layer); plain torch otherwise."""
+        if self.nbr is None:
+            if h_src.is_cuda and h_src.dtype == torch.float32 and self.indptr.is_cuda and self.indices.is_cuda:
+                return _MeanAggregateCSR.apply(h_src, self.indptr.contiguous(), self.indices.contiguous())
+            return self.mean_aggregate_torch(h_src)
         if h_src.is_cuda and h_src.dtype == torch.float32 and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
             return _MeanAggregate.apply(h_src, self.nbr)
         return self.mean_aggregate_torch(h_src)
 
     def mean_aggregate_torch(self, h_src):
+        if self.nbr is None:   # ragged: sum the rows of each segment, divide by its length (an empty segment gives zeros)
+            deg = self.indptr[1:] - self.indptr[:-1]
+            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg)
+            idx = self.indices.to(torch.int64)
+            valid = (idx >= 0).unsqueeze(-1).to(h_src.dtype)
+            out = torch.zeros((self.num_dst,) + tuple(h_src.shape[1:]), dtype=h_src.dtype, device=h_src.device)
+            out.index_add_(0, rows.to(h_src.device), h_src[idx.clamp_min(0).to(h_src.device)] * valid.to(h_src.device))
+            return out / deg.clamp_min(1).unsqueeze(-1).to(device=h_src.device, dtype=h_src.dtype)
         valid = self.nbr >= 0
         idx = self.nbr.clamp_min(0).to(torch.int64)
         g = h_src[idx] * valid.unsqueeze(-1).to(h_src.dtype)
@@ -143,6 +194,9 @@ class NeighborSampler(object):
         self.fanouts = [int(f) for f in fanouts]
         if not 1 <= len(self.fanouts) <= 8:
             raise ValueError("1..8 layers")
+        for f in self.fanouts:   # -1: every in-edge (DGL's full neighbourhood); the block of such a layer is ragged (Block.indptr)
+            if f != -1 and not 1 <= f <= 32:
+                raise ValueError(f"fan-out {f}: each fan-out must be 1..32, or -1 for every in-edge")
         self.seed = int(seed)
         self.step = 0
         # G > 0: deliver the input nodes bucketed by owner = id % G, the layout the owner-partitioned cache fetches without a
@@ -169,13 +223,27 @@ class NeighborSampler(object):
         n = seeds.numel()
         rev = list(reversed(self.fanouts))          # DGL samples the output layer first
         L = len(rev)
-        caps = [n]
+        full = -1 in rev
+        # capacities (include/coala_hip.h, coala_sampler_layer_t): exact host bounds up to the first full layer; a full layer holds
+        # at most cap * max_in_degree edges and never more than ITEM_LIMIT items, which bounds every layer behind it
+        caps, src_caps, edge_caps = [n], [], []
+        bounded = False
         for f in rev:
-            caps.append(caps[-1] * (f + 1))
-        src = [torch.empty(max(caps[l + 1], 1), dtype=torch.int64, device=g.device) for l in range(L)]
-        nbr = [torch.empty(max(caps[l] * rev[l], 1), dtype=torch.int32, device=g.device) for l in range(L)]
-        src_p = (C.c_void_p * L)(*[t.data_ptr() for t in src])
-        nbr_p = (C.c_void_p * L)(*[t.data_ptr() for t in nbr])
+            cap = caps[-1]
+            if f == -1:
+                edge_caps.append(min(cap * g.max_in_degree, ITEM_LIMIT))
+                src_caps.append(min(cap + edge_caps[-1], ITEM_LIMIT))
+                bounded = True
+            elif bounded:
+                src_caps.append(min(cap * (f + 1), ITEM_LIMIT))
+                edge_caps.append(min(cap * f, ITEM_LIMIT))
+            else:
+                src_caps.append(cap * (f + 1))
+                edge_caps.append(cap * f)
+            caps.append(src_caps[-1])
+        src = [torch.empty(max(src_caps[l], 1), dtype=torch.int64, device=g.device) for l in range(L)]
+        nbr = [torch.empty(max(edge_caps[l], 1), dtype=torch.int32, device=g.device) for l in range(L)]
+        ind = [torch.empty(caps[l] + 1, dtype=torch.int64, device=g.device) if rev[l] == -1 else None for l in range(L)]
         fan = (C.c_int32 * L)(*rev)
         st = self.step if step is None else int(step)
         G = self.bucket_by_owner
@@ -189,19 +257,31 @@ class NeighborSampler(object):
             extra = (bucketed, counts, dst_in_src)
         ticket = C.c_int64(-1)
         # three launches per layer, nothing else: no host wait here (n_src_host = NULL)
-        _capi.check(_lib.coala_sampler_sample(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, src_p, nbr_p, None,
-                                              C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
+        if full:
+            lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr() if ind[l] is not None else None,
+                                                                src_caps[l], edge_caps[l]) for l in range(L)])
+            _capi.check(_lib.coala_sampler_sample_layers(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, None, None,
+                                                         C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
+        else:
+            src_p = (C.c_void_p * L)(*[t.data_ptr() for t in src])
+            nbr_p = (C.c_void_p * L)(*[t.data_ptr() for t in nbr])
+            _capi.check(_lib.coala_sampler_sample(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, src_p, nbr_p, None,
+                                                  C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
         if step is None:
             self.step += 1
-        return (g, seeds, n, rev, src, nbr, extra, ticket.value)
+        return (g, seeds, n, rev, src, nbr, extra, ticket.value, ind)
 
     def sample_end(self, pending):
         """Wait for the counts of a sample_begin (an event wait: only for that call's kernels) and build the blocks."""
-        g, seeds, n, rev, src, nbr, extra, ticket = pending
+        g, seeds, n, rev, src, nbr, extra, ticket, ind = pending
         L, G = len(rev), self.bucket_by_owner
         n_src = (C.c_int64 * L)()
+        n_edges = (C.c_int64 * L)()
         ch = (C.c_int64 * G)() if G > 0 else None
-        _capi.check(_lib.coala_sampler_wait(g._h, ticket, n_src, ch))
+        if -1 in rev:   # raises when the device refused a full layer (or the fixed layers behind it) for its size
+            _capi.check(_lib.coala_sampler_wait_layers(g._h, ticket, n_src, n_edges, ch))
+        else:
+            _capi.check(_lib.coala_sampler_wait(g._h, ticket, n_src, ch))
         counts_host = list(ch) if G > 0 else None
         if G > 0:
             bucketed, counts, dst_in_src = extra
@@ -209,12 +289,17 @@ class NeighborSampler(object):
         n_dst = n
         for l in range(L):
             ns = int(n_src[l])
-            nbr_l = nbr[l][: n_dst * rev[l]].view(n_dst, rev[l])
+            if rev[l] == -1:       # ragged block: CSR over the destination nodes
+                nbr_l = None
+                csr = dict(indptr=ind[l][: n_dst + 1], indices=nbr[l][: int(n_edges[l])])
+            else:
+                nbr_l = nbr[l][: n_dst * rev[l]].view(n_dst, rev[l])
+                csr = {}
             if G > 0 and l == L - 1:   # the input layer: owner-bucketed source list
                 blocks.insert(0, Block(bucketed[:ns], nbr_l, n_dst, graph=g if l == 0 else None, dst_in_src=dst_in_src[:n_dst],
-                                       dst_nodes=src[l][:n_dst], owner_counts=counts, owner_counts_host=counts_host))
+                                       dst_nodes=src[l][:n_dst], owner_counts=counts, owner_counts_host=counts_host, **csr))
             else:
-                blocks.insert(0, Block(src[l][:ns], nbr_l, n_dst, graph=g if l == 0 else None))
+                blocks.insert(0, Block(src[l][:ns], nbr_l, n_dst, graph=g if l == 0 else None, **csr))
             n_dst = ns
         input_nodes = blocks[0].src_nodes
         return input_nodes, seeds, blocks

@@ -42,6 +42,11 @@ class SamplerBucketing(C.Structure):
                 ("dst_in_src", C.c_void_p)]
 
 
+class SamplerLayer(C.Structure):
+    _fields_ = [("src_nodes", C.c_void_p), ("nbr_local", C.c_void_p), ("indptr_local", C.c_void_p), ("src_cap", C.c_int64),
+                ("edge_cap", C.c_int64)]
+
+
 class CommProfile(C.Structure):
     _fields_ = [("rows_ms", C.c_double), ("calls", C.c_uint64), ("remote_rows_in", C.c_uint64)]
 
@@ -113,6 +118,11 @@ SYMBOLS = {
     "coala_block_mean_aggregate": (_I, [_I, _VP, _VP, _VP, _I64, _I, _I, _VP]),
     "coala_block_mean_aggregate_backward": (_I, [_I, _VP, _VP, _VP, _I64, _I, _I, _VP]),
     "coala_sampler_wait": (_I, [_VP, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
+    "coala_sampler_sample_layers": (_I, [_VP, _VP, _I64, C.POINTER(C.c_int32), _I, _U64, _U64, C.POINTER(SamplerLayer), C.POINTER(_I64),
+                                    C.POINTER(_I64), C.POINTER(SamplerBucketing), C.POINTER(_I64), _VP]),
+    "coala_sampler_wait_layers": (_I, [_VP, _I64, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
+    "coala_block_mean_aggregate_csr": (_I, [_I, _VP, _VP, _VP, _VP, _I64, _I, _VP]),
+    "coala_block_mean_aggregate_csr_backward": (_I, [_I, _VP, _VP, _VP, _VP, _I64, _I, _VP]),
     "coala_shm_open": (_I, [C.c_char_p, _U64, _I, _I, C.POINTER(_VP)]),
     "coala_shm_host_ptr": (_VP, [_VP]),
     "coala_shm_device_ptr": (_VP, [_VP]),

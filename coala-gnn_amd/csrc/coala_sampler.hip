@@ -14,6 +14,25 @@
 //     whatever order the hash-table inserts land in;
 //   * nbr_local[d*f + j] = index of the j-th sampled neighbour of dst d inside the source list, or -1.
 //
+// Full layers (fan-out -1, DGL's "every in-edge"; coala_sampler_sample_layers):
+//   * dst d (node v) gets every in-edge indices[indptr[v] .. indptr[v+1]) in CSC order, repeated edges and self-loops kept, an
+//     empty segment for degree 0 (what a fixed layer returns when deg <= f);
+//   * source nodes: the same rule -- dst nodes first, then every other neighbour in order of first appearance in the row-major
+//     (d, edge) scan;
+//   * block in CSR form: indptr_local int64[n_dst + 1] = exclusive scan of the degrees, nbr_local int32[E] = local source index of
+//     each edge;
+//   * no randomness is drawn; fixed layers of the same list keep their layer index l as the RNG key;
+//   * limit: n_dst + E <= kMaxTiles * kTile items (8,388,608), n_dst + E <= src_cap and E <= edge_cap.  Only the device knows E,
+//     so the check is made there: a refused layer reports 0 items, every later kernel of the call sees empty layers and does
+//     nothing, and coala_sampler_wait_layers returns the error with the layer and its item count.  Fixed layers behind a full
+//     layer have a device-known destination count; their worst-case bound n_dst * (f + 1) is checked on the device by the full
+//     layer's scan_assign in the same way.  Nothing is written past the caller's capacities; the handle stays usable.
+//   Launches: degree_scan (degrees -> indptr_local and E, the single-pass tile-ticket scan of scan_assign with the same status
+//   words), full_insert (one thread per item position p < n_dst + E: a binary search in indptr_local finds the destination, so a
+//   hub of 10^6 in-edges is spread over the whole grid), then scan_assign / relabel_clear in their full-layer instantiations.
+//   The hash table of a full layer is sized by its device-known item count: the kernel in front of the layer (the previous layer's
+//   relabel_clear, run after this layer's degree_scan, or table_clear for a first layer) clears exactly that much.
+//
 // Three launches per layer, nothing else on the stream (round 1: five launches + a memset per layer, a D2H copy and a stream
 // synchronisation per call):
 //   sample_insert   draw + hash insert;
@@ -50,6 +69,17 @@ constexpr int kMaxTiles = 8192;             // tiles per layer (8.4 M items): st
 constexpr int kRing = 8;                    // calls whose counts may be outstanding at once
 constexpr int kMaxParts = 64;
 constexpr int kRouteTile = 64 * kItems;     // ids per wave step of the bucketing phases
+constexpr int64_t kItemLimit = (int64_t)kMaxTiles * kTile;
+constexpr int kFull = -1;                   // fan-out of a full layer: every in-edge
+// device count words of layer l, relative to its base counts_dev + l: [0] n_dst, [kItemsOff] items, [kEdgesOff] edges of a full
+// layer (both 0 when it was refused); counts_dev[l + 1] is layer l's source count, counts_dev[kMaxLayers + 1 ..] the bucket bases
+constexpr int kItemsOff = COALA_SAMPLER_MAX_LAYERS + 1 + kMaxParts;
+constexpr int kEdgesOff = kItemsOff + COALA_SAMPLER_MAX_LAYERS + 1;
+constexpr int kCountsWords = kEdgesOff + COALA_SAMPLER_MAX_LAYERS + 1;
+// pinned host words of a call, relative to the slot + l: [0] n_src, [kPinEdges] E, [kPinRefused] the layer was refused,
+// [kPinOver] the fixed layers behind it were refused; the bucket sizes follow at kPinParts
+constexpr int kPinEdges = COALA_SAMPLER_MAX_LAYERS, kPinRefused = 2 * COALA_SAMPLER_MAX_LAYERS, kPinOver = 3 * COALA_SAMPLER_MAX_LAYERS;
+constexpr int kPinParts = 4 * COALA_SAMPLER_MAX_LAYERS;
 
 __host__ __device__ inline uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
@@ -88,10 +118,32 @@ struct Table {
     uint32_t* local_of_slot;  // [table] index of the key in the source list
 };
 
+constexpr unsigned long long kAggregate = 1ull << 32, kInclusive = 2ull << 32; // look-back status (scan_assign_kernel)
+
 __device__ __forceinline__ void clear_table(const Table& t, uint32_t tbl) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < tbl; i += gridDim.x * blockDim.x) {
         t.keys[i] = kEmpty;
         t.minpos[i] = 0xFFFFFFFFu;
+    }
+}
+
+// Item p (key k) into the hash table: CAS on the key, then atomicMin of the first position; k < 0 (no neighbour) is not inserted.
+__device__ __forceinline__ void hash_insert(const Table& tb, uint32_t mask, int64_t k, int64_t p, uint32_t* __restrict__ slot_of_item) {
+    if (k < 0) {
+        slot_of_item[p] = 0xFFFFFFFFu;
+    } else {
+        uint32_t s = hash_slot(k, mask);
+        while (true) {
+            const long long cur = tb.keys[s];
+            if (cur == k) break;
+            if (cur == kEmpty) {
+                const long long old = atomicCAS((unsigned long long*)(tb.keys + s), (unsigned long long)kEmpty, (unsigned long long)k);
+                if (old == kEmpty || old == k) break;
+            }
+            s = (s + 1) & mask;
+        }
+        atomicMin(tb.minpos + s, (uint32_t)p);
+        slot_of_item[p] = s;
     }
 }
 
@@ -138,26 +190,120 @@ __global__ __launch_bounds__(kBlock) void sample_insert_kernel(Graph g, const in
         int64_t p = -1;
         if (active && gl < fanout) { k = nb; p = n_dst + d * fanout + gl; }
         else if (active && gl == fanout) { k = v; p = d; }
-        if (p >= 0) {
-            if (k < 0) {
-                slot_of_item[p] = 0xFFFFFFFFu;
-            } else {
-                uint32_t s = hash_slot(k, mask);
-                while (true) {
-                    const long long cur = tb.keys[s];
-                    if (cur == k) break;
-                    if (cur == kEmpty) {
-                        const long long old = atomicCAS((unsigned long long*)(tb.keys + s), (unsigned long long)kEmpty, (unsigned long long)k);
-                        if (old == kEmpty || old == k) break;
-                    }
-                    s = (s + 1) & mask;
-                }
-                atomicMin(tb.minpos + s, (uint32_t)p);
-                slot_of_item[p] = s;
-            }
-        }
+        if (p >= 0) hash_insert(tb, mask, k, p, slot_of_item);
     }
 }
+
+__device__ __forceinline__ uint32_t sat_add(uint32_t a, uint32_t b) { // degree sums saturate: past 2^32 - 1 a layer is refused anyway
+    const uint32_t c = a + b;
+    return c < a ? 0xFFFFFFFFu : c;
+}
+
+__device__ __forceinline__ int64_t in_degree(const Graph& g, int64_t v) { return (v >= 0 && v < g.num_nodes) ? g.indptr[v + 1] - g.indptr[v] : 0; }
+
+// Full layer, pass 1: degrees of the destination nodes -> indptr_local (exclusive scan) and E, with the tile ticket and the
+// generation-tagged look-back status words of scan_assign_kernel (one scheme, shared counters).  The block of the last tile
+// checks the layer against its capacities and publishes n_dst (first layer), the item and edge counts -- 0 and 0 when refused.
+__global__ __launch_bounds__(kBlock) void degree_scan_kernel(Graph g, const int64_t* __restrict__ dst, const int64_t* __restrict__ n_dst_dev,
+                                                             int64_t n_dst_value, int64_t* __restrict__ base, unsigned long long* __restrict__ status,
+                                                             unsigned long long* __restrict__ ticket, unsigned long long ticket_base,
+                                                             unsigned long long gen, int64_t* __restrict__ indptr_local, int64_t item_cap,
+                                                             int64_t edge_cap, int64_t* __restrict__ pin) {
+    __shared__ uint32_t s_woff[kWavesPerBlock];
+    __shared__ unsigned long long s_tile;
+    __shared__ uint32_t s_prefix;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
+    const int64_t n_tiles = n_dst > 0 ? (n_dst + kTile - 1) / kTile : 1; // tile 0 always runs: it publishes an empty layer too
+    if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1ull) - ticket_base;
+    __syncthreads();
+    const int64_t tile = (int64_t)s_tile;
+    if (tile >= n_tiles) return;
+    const int64_t first = tile * kTile + (int64_t)threadIdx.x * kItems;
+    uint32_t dg[kItems];
+    uint32_t c = 0;
+    for (int i = 0; i < kItems; ++i) {
+        const int64_t deg = first + i < n_dst ? in_degree(g, dst[first + i]) : 0;
+        dg[i] = deg > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)deg;
+        c = sat_add(c, dg[i]);
+    }
+    uint32_t incl = c; // inclusive scan inside the wave
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t v = __shfl_up(incl, off);
+        if (lane >= off) incl = sat_add(incl, v);
+    }
+    if (lane == 63) s_woff[w] = incl;
+    __syncthreads();
+    uint32_t wbase = 0, total = 0;
+    for (int q = 0; q < kWavesPerBlock; ++q) {
+        if (q < w) wbase = sat_add(wbase, s_woff[q]);
+        total = sat_add(total, s_woff[q]);
+    }
+    if (threadIdx.x == 0) {
+        const unsigned long long tag = gen << 34;
+        uint32_t prefix = 0;
+        if (tile > 0) {
+            __hip_atomic_store(status + tile, tag | kAggregate | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int64_t t = tile - 1; t >= 0;) { // decoupled look-back
+                const unsigned long long v = __hip_atomic_load(status + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if ((v >> 34) != gen || !(v & (kAggregate | kInclusive))) { __builtin_amdgcn_s_sleep(1); continue; } // not published yet
+                prefix = sat_add(prefix, (uint32_t)v);
+                if (v & kInclusive) break;
+                --t;
+            }
+        }
+        __hip_atomic_store(status + tile, tag | kInclusive | sat_add(prefix, total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_prefix = prefix;
+        if (tile == n_tiles - 1) { // the layer's totals, and the capacity check
+            const int64_t edges = (int64_t)sat_add(prefix, total);
+            const int64_t items = n_dst + edges;
+            const bool ok = items <= item_cap && edges <= edge_cap;
+            indptr_local[n_dst] = edges;
+            if (!n_dst_dev) base[0] = n_dst;
+            base[kItemsOff] = ok ? items : 0;
+            base[kEdgesOff] = ok ? edges : 0;
+            pin[kPinEdges] = edges;
+            pin[kPinRefused] = ok ? 0 : 1;
+        }
+    }
+    __syncthreads();
+    uint32_t run = sat_add(s_prefix, sat_add(wbase, incl - c));
+    for (int i = 0; i < kItems; ++i) {
+        if (first + i < n_dst) indptr_local[first + i] = (int64_t)run;
+        run = sat_add(run, dg[i]);
+    }
+}
+
+// Full layer, pass 2: item p < n_dst is destination node p; item n_dst + q is edge q of the layer, whose destination a binary
+// search in indptr_local finds (load-balanced over edges: a hub's edges are spread over the whole grid).  The edge's neighbour is
+// stored (scan_assign reads it back) and inserted exactly as sample_insert_kernel inserts its items.
+__global__ __launch_bounds__(kBlock) void full_insert_kernel(Graph g, const int64_t* __restrict__ dst, const int64_t* __restrict__ base,
+                                                             const int64_t* __restrict__ indptr_local, int64_t* __restrict__ nbr, Table tb,
+                                                             uint32_t* __restrict__ slot_of_item) {
+    const int64_t n_dst = base[0];
+    const int64_t n_items = base[kItemsOff];
+    const uint32_t mask = table_size(n_items) - 1;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_items; p += (int64_t)gridDim.x * blockDim.x) {
+        int64_t k;
+        if (p < n_dst) {
+            k = dst[p];
+        } else {
+            const int64_t q = p - n_dst;
+            int64_t lo = 0, hi = n_dst - 1; // the last d with indptr_local[d] <= q (q < E, so d < n_dst and deg(d) > 0)
+            while (lo < hi) {
+                const int64_t mid = (lo + hi + 1) >> 1;
+                if (indptr_local[mid] <= q) lo = mid;
+                else hi = mid - 1;
+            }
+            k = g.indices[g.indptr[dst[lo]] + (q - indptr_local[lo])];
+            nbr[q] = k;
+        }
+        hash_insert(tb, mask, k, p, slot_of_item);
+    }
+}
+
+// first layer full: its table size is known on the device only
+__global__ __launch_bounds__(kBlock) void table_clear_kernel(Table tb, const int64_t* __restrict__ items_dev) { clear_table(tb, table_size(*items_dev)); }
 
 __device__ __forceinline__ uint32_t first_flag(const uint32_t* __restrict__ slot_of_item, const uint32_t* __restrict__ minpos, int64_t p,
                                                int64_t n_items) {
@@ -170,7 +316,9 @@ __device__ __forceinline__ uint32_t first_flag(const uint32_t* __restrict__ slot
 // publishes the tile's count as an AGGREGATE, looks back over its predecessors until it meets an INCLUSIVE prefix, publishes its
 // own INCLUSIVE prefix and numbers its first occurrences.  Status words carry the launch's generation: nothing to reset.
 //   word = gen << 34 | status << 32 | value          status: 1 = aggregate, 2 = inclusive prefix
-constexpr unsigned long long kAggregate = 1ull << 32, kInclusive = 2ull << 32;
+// FULL (a fan-out -1 layer): n_dst and the item count come from the layer's device words (n_dst_dev = its base), and n_dst_value
+// is the largest source count the fixed layers behind it accept: above it the next layers see 0 destination nodes.
+template <bool FULL>
 __global__ __launch_bounds__(kBlock) void scan_assign_kernel(const int64_t* __restrict__ dst, const int64_t* __restrict__ nbr,
                                                              const int64_t* __restrict__ n_dst_dev, int64_t n_dst_value, int fanout,
                                                              const uint32_t* __restrict__ slot_of_item, Table tb, unsigned long long* __restrict__ status,
@@ -181,14 +329,18 @@ __global__ __launch_bounds__(kBlock) void scan_assign_kernel(const int64_t* __re
     __shared__ unsigned long long s_tile;
     __shared__ uint32_t s_prefix;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
-    const int64_t n_items = n_dst * (fanout + 1);
+    const int64_t n_dst = FULL ? *n_dst_dev : n_dst_dev ? *n_dst_dev : n_dst_value;
+    const int64_t n_items = FULL ? n_dst_dev[kItemsOff] : n_dst * (fanout + 1);
     const int64_t n_tiles = (n_items + kTile - 1) / kTile;
     if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1ull) - ticket_base;
     __syncthreads();
     const int64_t tile = (int64_t)s_tile;
     if (tile >= n_tiles) { // launched for the capacity; the block that would own the first unused tile reports an empty layer
-        if (tile == 0 && threadIdx.x == 0) { *n_src_dev = 0; *n_src_host = 0; }
+        if (tile == 0 && threadIdx.x == 0) {
+            *n_src_dev = 0;
+            *n_src_host = 0;
+            if constexpr (FULL) n_src_host[kPinOver] = 0;
+        }
         return;
     }
     const int64_t base = tile * kTile + (int64_t)threadIdx.x * kItems;
@@ -223,8 +375,16 @@ __global__ __launch_bounds__(kBlock) void scan_assign_kernel(const int64_t* __re
         __hip_atomic_store(status + tile, tag | kInclusive | (prefix + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_prefix = prefix;
         if (tile == n_tiles - 1) { // layer l+1 (and the host) read the number of source nodes from here
-            *n_src_dev = (int64_t)(prefix + total);
-            *n_src_host = (int64_t)(prefix + total);
+            if constexpr (FULL) {
+                const int64_t n_src = (int64_t)(prefix + total);
+                const bool over = n_src > n_dst_value;
+                *n_src_dev = over ? 0 : n_src;
+                *n_src_host = n_src;
+                n_src_host[kPinOver] = over ? 1 : 0;
+            } else {
+                *n_src_dev = (int64_t)(prefix + total);
+                *n_src_host = (int64_t)(prefix + total);
+            }
         }
     }
     __syncthreads();
@@ -240,17 +400,21 @@ __global__ __launch_bounds__(kBlock) void scan_assign_kernel(const int64_t* __re
 }
 
 // neighbour -> local index in the source list; alongside, the hash table for what comes next is cleared (keys / minpos are no
-// longer read by this layer): next_items_dev != null -> the next layer's size is read from the device, else next_items (next call)
+// longer read by this layer): next_items_dev != null -> the next layer's size is read from the device, else next_items (next call).
+// FULL: this layer's edge count is read from its device words; NEXT_FULL: so is the next layer's item count (its degree_scan ran
+// before this kernel).
+template <bool FULL, bool NEXT_FULL>
 __global__ __launch_bounds__(kBlock) void relabel_clear_kernel(const int64_t* __restrict__ n_dst_dev, int64_t n_dst_value, int fanout, const uint32_t* __restrict__ slot_of_item,
                                                                Table tb, int32_t* __restrict__ nbr_local, const int64_t* __restrict__ next_n_dst_dev,
                                                                int next_fanout, int64_t next_items) {
     const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
-    const int64_t n_nbr = n_dst * fanout;
+    const int64_t n_nbr = FULL ? n_dst_dev[kEdgesOff] : n_dst * fanout;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n_nbr; q += (int64_t)gridDim.x * blockDim.x) {
         const uint32_t s = slot_of_item[n_dst + q];
         nbr_local[q] = (s == 0xFFFFFFFFu) ? -1 : (int32_t)tb.local_of_slot[s];
     }
-    clear_table(tb, table_size(next_n_dst_dev ? *next_n_dst_dev * (next_fanout + 1) : next_items));
+    if constexpr (NEXT_FULL) clear_table(tb, table_size(next_n_dst_dev[kItemsOff]));
+    else clear_table(tb, table_size(next_n_dst_dev ? *next_n_dst_dev * (next_fanout + 1) : next_items));
 }
 
 // ---------------------------------------------------------------------------------------------------------- owner bucketing
@@ -347,11 +511,12 @@ __global__ __launch_bounds__(kBlock) void bucket_scatter_kernel(const int64_t* _
     }
 }
 
+template <bool FULL>
 __global__ __launch_bounds__(kBlock) void bucket_reindex_kernel(const int64_t* __restrict__ n_dst_dev, int64_t n_dst_value, int fanout,
                                                                 const uint32_t* __restrict__ new_of_old, int32_t* __restrict__ nbr_local,
                                                                 int32_t* __restrict__ dst_in_src) {
     const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
-    const int64_t n_nbr = n_dst * fanout;
+    const int64_t n_nbr = FULL ? n_dst_dev[kEdgesOff] : n_dst * fanout;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n_nbr; q += (int64_t)gridDim.x * blockDim.x) {
         const int32_t o = nbr_local[q];
         if (o >= 0) nbr_local[q] = (int32_t)new_of_old[o];
@@ -410,6 +575,62 @@ __global__ __launch_bounds__(kBlock) void mean_aggregate_backward_kernel(const i
     }
 }
 
+// The same op on a ragged (CSR) block, the form of a full layer: row d is idx[indptr[d] .. indptr[d+1]).  One wave per row as in
+// the dense kernels; the row's indices are read 64 at a time and broadcast by shuffle, and the sum runs in CSC order, so a row both
+// forms can express gives the dense kernel's bits.  A hub row is aggregated by one wave (splitting it is not done).
+template <int VEC>
+__global__ __launch_bounds__(kBlock) void mean_aggregate_csr_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                    const float* __restrict__ h_src, float* __restrict__ out, int64_t n_dst, int dim) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int units = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        const int64_t beg = indptr[d], end = indptr[d + 1];
+        const float inv = end > beg ? 1.0f / (float)(end - beg) : 0.0f;
+        for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+            const int u = u0 + lane;
+            vf acc = vf(0.0f);
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
+                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && u < units) acc += *reinterpret_cast<const vf*>(h_src + (int64_t)s * dim + (int64_t)u * VEC);
+                }
+            }
+            if (u < units) *reinterpret_cast<vf*>(out + d * dim + (int64_t)u * VEC) = acc * inv;
+        }
+    }
+}
+
+// grad_src[idx[e]] += grad_out[d] / deg(d) for the edges e of row d (grad_src zeroed by the caller; hardware float atomics)
+__global__ __launch_bounds__(kBlock) void mean_aggregate_csr_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                             const float* __restrict__ grad_out, float* __restrict__ grad_src,
+                                                                             int64_t n_dst, int dim) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        const int64_t beg = indptr[d], end = indptr[d + 1];
+        if (end <= beg) continue;
+        const float inv = 1.0f / (float)(end - beg);
+        for (int c0 = 0; c0 < dim; c0 += 64) { // wave-uniform trip count: the shuffles below read lanes that are past `dim`
+            const int c = c0 + lane;
+            const float g = c < dim ? grad_out[d * dim + c] * inv : 0.0f;
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
+                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && c < dim) unsafeAtomicAdd(grad_src + (int64_t)s * dim + c, g);
+                }
+            }
+        }
+    }
+}
+
 int grid1d(int64_t n, int block, int cap) {
     int64_t g = (n + block - 1) / block;
     if (g < 1) g = 1;
@@ -417,6 +638,15 @@ int grid1d(int64_t n, int block, int cap) {
     return (int)g;
 }
 
+} // namespace
+
+namespace {
+struct RingInfo { // what coala_sampler_wait_layers needs of a call to read its counts and explain a refusal
+    int n_layers = 0, n_parts = 0;
+    int64_t n_seeds = 0;
+    int32_t fanouts[COALA_SAMPLER_MAX_LAYERS] = {};
+    int64_t src_cap[COALA_SAMPLER_MAX_LAYERS] = {}, edge_cap[COALA_SAMPLER_MAX_LAYERS] = {};
+};
 } // namespace
 
 struct coala_sampler {
@@ -433,19 +663,18 @@ struct coala_sampler {
     unsigned long long* status = nullptr;  // [kMaxTiles] look-back status words (generation-tagged, never reset)
     unsigned long long* ticket = nullptr;  // tile ticket counter, monotonic across launches
     unsigned long long ticket_total = 0, scan_gen = 0;
-    int64_t* counts_dev = nullptr;         // [kMaxLayers + 1] source counts of the call in flight; then [kMaxParts] bucket bases
-    // pinned host ring: per call [kMaxLayers source counts][kMaxParts bucket sizes], and an event recorded behind the last kernel
+    int64_t* counts_dev = nullptr;         // [kCountsWords]: source counts of the call in flight, bucket bases, full-layer words
+    // pinned host ring: per call kSlot words (kPinEdges .. kPinParts), and an event recorded behind the last kernel
     int64_t* counts_pinned = nullptr; // host pointer
     int64_t* counts_pinned_dev = nullptr;
     hipEvent_t done[kRing] = {};
-    int ring_layers[kRing] = {};
-    int ring_parts[kRing] = {};
+    RingInfo ring[kRing];
     uint64_t calls = 0;
     hipStream_t last_stream = nullptr; // stream of the previous call
 };
 
 namespace {
-constexpr int kSlot = COALA_SAMPLER_MAX_LAYERS + kMaxParts; // int64 words per ring slot
+constexpr int kSlot = kPinParts + kMaxParts; // int64 words per ring slot
 
 int grow(void** p, uint64_t* cap, uint64_t need, size_t elem, hipStream_t st) {
     if (need <= *cap) return COALA_OK;
@@ -465,6 +694,288 @@ int ilog2_exact(uint64_t v) {
     while ((1ull << s) != v) ++s;
     return s;
 }
+
+int check_call(const coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+               const coala_sampler_bucketing_t* bucketing) {
+    if (!s || (!seeds && n_seeds > 0) || !fanouts) return fail(COALA_EINVAL, "null argument");
+    if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
+    if (n_seeds < 0 || n_seeds > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad n_seeds");
+    const int n_parts = bucketing ? bucketing->n_parts : 0;
+    if (n_parts < 0 || n_parts > kMaxParts) return fail(COALA_EINVAL, "bucketing: n_parts must be 0..%d", kMaxParts);
+    if (n_parts > 0 && (!bucketing->bucketed_nodes || !bucketing->counts || !bucketing->dst_in_src)) return fail(COALA_EINVAL, "bucketing: null buffer");
+    return COALA_OK;
+}
+
+// Fixed layers behind full layer l (up to the next full layer) have a destination count known on the device only.  Layer j of them
+// holds at most n_src_l * P_j destination nodes (P_j = product of (f + 1) of the fixed layers between), i.e. n_dst * (f_j + 1)
+// items and n_dst * f_j neighbours.  With n_src >= 0: the first such layer that n_src overflows (-1: none), its worst-case item
+// count in *items_out and its bound in *limit_out.  With n_src < 0: -1, and the largest n_src they all accept in *limit_out.
+int fixed_run_check(const RingInfo& r, int l, int64_t n_src, int64_t* items_out, int64_t* limit_out, const char** what) {
+    int64_t most = INT64_MAX;
+    int64_t mult = 1; // P_j, capped above the item limit
+    for (int j = l + 1; j < r.n_layers && r.fanouts[j] != kFull; ++j) {
+        const int64_t f = r.fanouts[j];
+        const int64_t item_lim = std::min<int64_t>(kItemLimit, r.src_cap[j]);
+        if (n_src >= 0) {
+            const int64_t items = n_src * mult * (f + 1);
+            if (items > item_lim || n_src * mult * f > r.edge_cap[j]) {
+                *items_out = items;
+                *limit_out = items > item_lim ? item_lim : r.edge_cap[j];
+                *what = items > kItemLimit ? "the item limit" : items > item_lim ? "its src_cap" : "its edge_cap (neighbour entries)";
+                return j;
+            }
+        } else {
+            most = std::min(most, std::min(item_lim / (mult * (f + 1)), r.edge_cap[j] / (mult * f)));
+        }
+        mult = std::min<int64_t>(mult * (f + 1), kItemLimit + 1);
+    }
+    if (n_src < 0) *limit_out = most;
+    return -1;
+}
+
+int wait_impl(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host) {
+    if (!s) return fail(COALA_EINVAL, "null sampler");
+    if (ticket < 0 || (uint64_t)ticket >= s->calls || s->calls - (uint64_t)ticket > kRing)
+        return fail(COALA_EINVAL, "ticket %lld is not one of the last %d calls", (long long)ticket, kRing);
+    HIPCHK(hipSetDevice(s->device));
+    const int slot = (int)((uint64_t)ticket % kRing);
+    HIPCHK(hipEventSynchronize(s->done[slot])); // the kernels behind this event stored the counts into pinned host memory
+    const int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
+    const RingInfo& r = s->ring[slot];
+    if (n_src_host)
+        for (int l = 0; l < r.n_layers; ++l) n_src_host[l] = pin[l];
+    if (n_edges_host)
+        for (int l = 0; l < r.n_layers; ++l)
+            n_edges_host[l] = r.fanouts[l] == kFull ? pin[kPinEdges + l] : (l ? pin[l - 1] : r.n_seeds) * r.fanouts[l];
+    if (bucket_counts_host)
+        for (int g = 0; g < r.n_parts; ++g) bucket_counts_host[g] = pin[kPinParts + g];
+    for (int l = 0; l < r.n_layers; ++l) { // device-side refusals, in layer order: the first one is the cause
+        if (r.fanouts[l] != kFull) continue;
+        const int64_t n_dst = l ? pin[l - 1] : r.n_seeds;
+        if (pin[kPinRefused + l]) {
+            const long long e = pin[kPinEdges + l], items = n_dst + e;
+            if (items > kItemLimit)
+                return fail(COALA_EINVAL, "layer %d holds %lld items (%lld destination nodes + %lld edges): over the limit of %lld", l, items,
+                            (long long)n_dst, e, (long long)kItemLimit);
+            if (items > r.src_cap[l])
+                return fail(COALA_EINVAL, "layer %d holds %lld items (%lld destination nodes + %lld edges): over its src_cap of %lld", l, items,
+                            (long long)n_dst, e, (long long)r.src_cap[l]);
+            return fail(COALA_EINVAL, "layer %d holds %lld items (%lld destination nodes + %lld edges): over its edge_cap of %lld", l, items,
+                        (long long)n_dst, e, (long long)r.edge_cap[l]);
+        }
+        if (pin[kPinOver + l]) {
+            int64_t items = 0, lim = 0;
+            const char* what = "";
+            const int j = fixed_run_check(r, l, pin[l], &items, &lim, &what);
+            return fail(COALA_EINVAL, "layer %d would hold %lld items (%lld source nodes of full layer %d, fan-out %d behind it): over %s of %lld", j,
+                        (long long)items, (long long)pin[l], l, j >= 0 ? r.fanouts[j] : 0, what, (long long)lim);
+        }
+    }
+    return COALA_OK;
+}
+
+int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed, uint64_t step,
+                const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
+                int64_t* ticket_out, void* stream) {
+    int rc;
+    if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, bucketing))) return rc;
+    if (!layers) return fail(COALA_EINVAL, "null argument");
+    for (int l = 0; l < n_layers; ++l) {
+        const int f = fanouts[l];
+        if (f != kFull && (f < 1 || f > 32)) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (or -1: every in-edge)", f);
+        const coala_sampler_layer_t& y = layers[l];
+        if (!y.src_nodes || !y.nbr_local || (f == kFull && !y.indptr_local)) return fail(COALA_EINVAL, "layer %d: null buffer", l);
+        if (y.src_cap < 0 || y.edge_cap < 0) return fail(COALA_EINVAL, "layer %d: negative capacity", l);
+    }
+    const int n_parts = bucketing ? bucketing->n_parts : 0;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(s->device));
+    // the handle's scratch (hash table, scan state) is ordered by the stream of its calls: a caller that moves to another stream
+    // first waits there for the previous call's last kernel
+    if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
+    s->last_stream = st;
+    // capacities: layer l has at most dst_cap[l] dst nodes, items_cap[l] items (dst nodes + neighbour slots), nbr_cap[l] neighbour
+    // entries.  Up to the first full layer they are exact host bounds (cap_l * (f + 1)) and checked here; a full layer and the fixed
+    // layers behind it are checked on the device against the caller's capacities and the item limit.
+    RingInfo info;
+    info.n_layers = n_layers;
+    info.n_parts = n_parts;
+    info.n_seeds = n_seeds;
+    int64_t dst_cap[COALA_SAMPLER_MAX_LAYERS], items_cap[COALA_SAMPLER_MAX_LAYERS], nbr_cap[COALA_SAMPLER_MAX_LAYERS];
+    int64_t cap = n_seeds;
+    bool host_bound = true;
+    uint64_t max_items = 0, max_nbr = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        const int f = fanouts[l];
+        const coala_sampler_layer_t& y = layers[l];
+        info.fanouts[l] = f;
+        info.src_cap[l] = y.src_cap;
+        info.edge_cap[l] = y.edge_cap;
+        dst_cap[l] = cap;
+        if (f == kFull) {
+            host_bound = false;
+            items_cap[l] = std::min<int64_t>(kItemLimit, y.src_cap);
+            nbr_cap[l] = std::min<int64_t>(kItemLimit, y.edge_cap);
+        } else if (host_bound) {
+            const uint64_t items = (uint64_t)cap * (uint64_t)(f + 1);
+            if (items > (uint64_t)kItemLimit) return fail(COALA_EINVAL, "layer %d would hold %llu items (limit %d)", l, (unsigned long long)items, kMaxTiles * kTile);
+            if ((uint64_t)y.src_cap < items || (uint64_t)y.edge_cap < (uint64_t)cap * f)
+                return fail(COALA_EINVAL, "layer %d: src_cap %lld / edge_cap %lld below the %llu / %llu its fan-out of %d needs", l, (long long)y.src_cap,
+                            (long long)y.edge_cap, (unsigned long long)items, (unsigned long long)cap * f, f);
+            items_cap[l] = (int64_t)items;
+            nbr_cap[l] = cap * f;
+        } else {
+            items_cap[l] = std::min(std::min<int64_t>(cap * (f + 1), kItemLimit), y.src_cap);
+            nbr_cap[l] = std::min(std::min<int64_t>(cap * f, kItemLimit), y.edge_cap);
+        }
+        if ((uint64_t)items_cap[l] > max_items) max_items = (uint64_t)items_cap[l];
+        if ((uint64_t)nbr_cap[l] > max_nbr) max_nbr = (uint64_t)nbr_cap[l];
+        cap = items_cap[l];
+    }
+    const uint64_t table = table_size((int64_t)max_items);
+    const uint64_t wave_tiles = ((uint64_t)cap + kRouteTile - 1) / kRouteTile;
+    if ((rc = grow((void**)&s->nbr_global, &s->nbr_cap, max_nbr ? max_nbr : 1, sizeof(int64_t), st))) return rc;
+    if ((rc = grow((void**)&s->slot_of_item, &s->item_cap, max_items ? max_items : 1, sizeof(uint32_t), st))) return rc;
+    if (n_parts > 0) {
+        if ((rc = grow((void**)&s->wave_counts, &s->wc_cap, (wave_tiles + 1) * (uint64_t)n_parts, sizeof(uint32_t), st))) return rc;
+        if ((rc = grow((void**)&s->new_of_old, &s->noo_cap, (uint64_t)cap ? (uint64_t)cap : 1, sizeof(uint32_t), st))) return rc;
+    }
+    if (table > s->table_cap) {
+        HIPCHK(hipStreamSynchronize(st));
+        for (void** p : {(void**)&s->tb.keys, (void**)&s->tb.local_of_slot})
+            if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
+        HIPCHK(hipMalloc((void**)&s->tb.keys, table * (sizeof(long long) + sizeof(uint32_t)))); // keys, then the first-position words
+        HIPCHK(hipMalloc((void**)&s->tb.local_of_slot, table * sizeof(uint32_t)));
+        s->table_cap = table;
+        s->tb.minpos = reinterpret_cast<uint32_t*>(s->tb.keys + table);
+        s->clean_items = 0;
+    }
+    const uint64_t ticket = s->calls;
+    const int slot = (int)(ticket % kRing);
+    if (ticket >= kRing) HIPCHK(hipEventSynchronize(s->done[slot])); // the ring slot's previous user has finished writing it
+    int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
+    int64_t* pin_dev = s->counts_pinned_dev + (size_t)slot * kSlot;
+    s->ring[slot] = info;
+    if (n_seeds == 0) {
+        for (int l = 0; l < n_layers; ++l) {
+            pin[l] = pin[kPinEdges + l] = pin[kPinRefused + l] = pin[kPinOver + l] = 0;
+            if (fanouts[l] == kFull) HIPCHK(hipMemsetAsync(layers[l].indptr_local, 0, sizeof(int64_t), st));
+        }
+        for (int g = 0; g < n_parts; ++g) pin[kPinParts + g] = 0;
+        if (n_parts > 0) HIPCHK(hipMemsetAsync(bucketing->counts, 0, (size_t)n_parts * sizeof(int64_t), st));
+    } else {
+        const bool first_full = fanouts[0] == kFull;
+        // what the last kernel leaves clean for the next call: the first layer's table of this call, or -- when that size is known on
+        // the device only -- the extent the previous call left clean
+        const uint64_t items0 = first_full ? std::max<uint64_t>(s->clean_items, 1) : (uint64_t)n_seeds * (uint64_t)(fanouts[0] + 1);
+        // the first layer's table: normally left clean by the previous call's last kernel
+        if (!first_full && (s->clean_items == 0 || table_size((int64_t)items0) > table_size((int64_t)s->clean_items))) {
+            const uint32_t t0 = table_size((int64_t)items0);
+            HIPCHK(hipMemsetAsync(s->tb.keys, 0xFF, (size_t)t0 * sizeof(long long), st));
+            HIPCHK(hipMemsetAsync(s->tb.minpos, 0xFF, (size_t)t0 * sizeof(uint32_t), st));
+        }
+        auto next_gen = [&]() -> int {
+            if ((++s->scan_gen & 0x3FFFFFFFull) == 0) { // 2^30 scans: the generation tag wraps -> clear the status words once
+                HIPCHK(hipMemsetAsync(s->status, 0, kMaxTiles * sizeof(unsigned long long), st));
+                s->scan_gen++;
+            }
+            return COALA_OK;
+        };
+        auto degree_scan = [&](int l, const int64_t* dst_l, const int64_t* n_dst_dev_l) -> int {
+            const int tiles = grid1d(dst_cap[l], kTile, kMaxTiles);
+            int r;
+            if ((r = next_gen())) return r;
+            hipLaunchKernelGGL(degree_scan_kernel, dim3(tiles), dim3(kBlock), 0, st, s->g, dst_l, n_dst_dev_l, n_seeds, s->counts_dev + l, s->status,
+                               s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, layers[l].indptr_local, items_cap[l],
+                               std::min<int64_t>(kItemLimit, layers[l].edge_cap), pin_dev + l);
+            s->ticket_total += (unsigned long long)tiles;
+            return COALA_OK;
+        };
+        if (first_full) {
+            if ((rc = degree_scan(0, seeds, nullptr))) return rc;
+            hipLaunchKernelGGL(table_clear_kernel, dim3(grid1d(table_size(items_cap[0]), kBlock, 4096)), dim3(kBlock), 0, st, s->tb,
+                               (const int64_t*)(s->counts_dev + kItemsOff));
+        }
+        const int64_t* n_dst_dev = nullptr;            // first layer: the seed count travels as a kernel argument
+        const int64_t* dst = seeds;
+        for (int l = 0; l < n_layers; ++l) {
+            const int f = fanouts[l];
+            const bool full = f == kFull;
+            const int64_t cap_l = dst_cap[l];
+            int64_t* base = s->counts_dev + l;
+            int64_t* n_src_dev = s->counts_dev + l + 1;
+            int64_t* const src_out = layers[l].src_nodes;
+            int32_t* const nbr_out = layers[l].nbr_local;
+            const dim3 blk(kBlock);
+            const int tiles = grid1d(items_cap[l], kTile, kMaxTiles);
+            if (full) {
+                hipLaunchKernelGGL(full_insert_kernel, dim3(grid1d(items_cap[l], kBlock, 8192)), blk, 0, st, s->g, dst, (const int64_t*)base,
+                                   (const int64_t*)layers[l].indptr_local, s->nbr_global, s->tb, s->slot_of_item);
+                int64_t max_src = 0;
+                int64_t unused_items = 0;
+                const char* unused_what = nullptr;
+                fixed_run_check(info, l, -1, &unused_items, &max_src, &unused_what);
+                if ((rc = next_gen())) return rc;
+                hipLaunchKernelGGL(scan_assign_kernel<true>, dim3(tiles), blk, 0, st, dst, s->nbr_global, (const int64_t*)base, max_src, 0, s->slot_of_item,
+                                   s->tb, s->status, s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, src_out, n_src_dev, pin_dev + l);
+            } else {
+                const dim3 gs(grid1d(cap_l * (f < 16 ? 16 : f < 32 ? 32 : 64), kBlock, 8192));
+                if (f < 16)
+                    hipLaunchKernelGGL(sample_insert_kernel<16>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb, s->slot_of_item);
+                else if (f < 32)
+                    hipLaunchKernelGGL(sample_insert_kernel<32>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb, s->slot_of_item);
+                else
+                    hipLaunchKernelGGL(sample_insert_kernel<64>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb, s->slot_of_item);
+                if ((rc = next_gen())) return rc;
+                hipLaunchKernelGGL(scan_assign_kernel<false>, dim3(tiles), blk, 0, st, dst, s->nbr_global, n_dst_dev, n_seeds, f, s->slot_of_item, s->tb,
+                                   s->status, s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, src_out, n_src_dev, pin_dev + l);
+            }
+            s->ticket_total += (unsigned long long)tiles;
+            const bool last = l + 1 == n_layers;
+            const bool next_full = !last && fanouts[l + 1] == kFull;
+            // a full next layer: its degree scan runs now, so that this layer's relabel_clear knows how much table to clear for it
+            if (next_full && (rc = degree_scan(l + 1, src_out, n_src_dev))) return rc;
+            const int64_t clear_cap = last ? (int64_t)table_size((int64_t)items0) : (int64_t)table_size(items_cap[l + 1]);
+            const int64_t* rdev = full ? (const int64_t*)base : n_dst_dev; // a full layer reads n_dst and E from its base
+            const int64_t* next_dev = last ? (const int64_t*)nullptr : (const int64_t*)n_src_dev;
+            const int next_f = last ? 0 : fanouts[l + 1];
+            const dim3 gr(grid1d(std::max<int64_t>(nbr_cap[l], clear_cap), kBlock, 4096));
+            if (full && next_full)
+                hipLaunchKernelGGL((relabel_clear_kernel<true, true>), gr, blk, 0, st, rdev, n_seeds, f, s->slot_of_item, s->tb, nbr_out, next_dev, next_f, (int64_t)items0);
+            else if (full)
+                hipLaunchKernelGGL((relabel_clear_kernel<true, false>), gr, blk, 0, st, rdev, n_seeds, f, s->slot_of_item, s->tb, nbr_out, next_dev, next_f, (int64_t)items0);
+            else if (next_full)
+                hipLaunchKernelGGL((relabel_clear_kernel<false, true>), gr, blk, 0, st, rdev, n_seeds, f, s->slot_of_item, s->tb, nbr_out, next_dev, next_f, (int64_t)items0);
+            else
+                hipLaunchKernelGGL((relabel_clear_kernel<false, false>), gr, blk, 0, st, rdev, n_seeds, f, s->slot_of_item, s->tb, nbr_out, next_dev, next_f, (int64_t)items0);
+            if (last && n_parts > 0) {
+                const uint32_t P = (uint32_t)n_parts;
+                const int pshift = ilog2_exact((uint64_t)n_parts);
+                int64_t* bases = s->counts_dev + COALA_SAMPLER_MAX_LAYERS + 1;
+                const dim3 gw(grid1d(((items_cap[l] + kRouteTile - 1) / kRouteTile) * 64, kBlock, 4096));
+                hipLaunchKernelGGL(bucket_count_kernel, gw, blk, 0, st, src_out, n_src_dev, P, pshift, s->wave_counts);
+                hipLaunchKernelGGL(bucket_scan_kernel, dim3(1), dim3(64 * (n_parts < 16 ? n_parts : 16)), 0, st, s->wave_counts, n_src_dev, P,
+                                   bucketing->counts, pin_dev + kPinParts, bases);
+                hipLaunchKernelGGL(bucket_scatter_kernel, gw, blk, 0, st, src_out, n_src_dev, P, pshift, s->wave_counts, bases,
+                                   bucketing->bucketed_nodes, s->new_of_old);
+                const dim3 gb(grid1d(full ? std::max(nbr_cap[l], cap_l) : cap_l * f, kBlock, 4096));
+                if (full)
+                    hipLaunchKernelGGL(bucket_reindex_kernel<true>, gb, blk, 0, st, rdev, n_seeds, f, s->new_of_old, nbr_out, bucketing->dst_in_src);
+                else
+                    hipLaunchKernelGGL(bucket_reindex_kernel<false>, gb, blk, 0, st, rdev, n_seeds, f, s->new_of_old, nbr_out, bucketing->dst_in_src);
+            }
+            dst = src_out;
+            n_dst_dev = n_src_dev;
+        }
+        s->clean_items = items0;
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(s->done[slot], st));
+    s->calls++;
+    if (ticket_out) *ticket_out = (int64_t)ticket;
+    if (n_src_host || n_edges_host) return wait_impl(s, (int64_t)ticket, n_src_host, n_edges_host, nullptr);
+    return COALA_OK;
+}
 } // namespace
 
 extern "C" {
@@ -482,7 +993,8 @@ int coala_sampler_create(int device, const int64_t* indptr, const int64_t* indic
               hipMemset(s->status, 0, kMaxTiles * sizeof(unsigned long long)) == hipSuccess &&
               hipMalloc((void**)&s->ticket, sizeof(unsigned long long)) == hipSuccess &&
               hipMemset(s->ticket, 0, sizeof(unsigned long long)) == hipSuccess &&
-              hipMalloc((void**)&s->counts_dev, (COALA_SAMPLER_MAX_LAYERS + 1 + kMaxParts) * sizeof(int64_t)) == hipSuccess &&
+              hipMalloc((void**)&s->counts_dev, kCountsWords * sizeof(int64_t)) == hipSuccess &&
+              hipMemset(s->counts_dev, 0, kCountsWords * sizeof(int64_t)) == hipSuccess &&
               hipHostMalloc((void**)&s->counts_pinned, kRing * kSlot * sizeof(int64_t), hipHostMallocMapped) == hipSuccess &&
               hipHostGetDevicePointer((void**)&s->counts_pinned_dev, s->counts_pinned, 0) == hipSuccess;
     for (int i = 0; i < kRing && ok; ++i) ok = hipEventCreateWithFlags(&s->done[i], hipEventDisableTiming) == hipSuccess;
@@ -533,138 +1045,64 @@ int coala_block_mean_aggregate_backward(int device, const int32_t* nbr, const fl
     return COALA_OK;
 }
 
-int coala_sampler_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* bucket_counts_host) {
-    if (!s) return fail(COALA_EINVAL, "null sampler");
-    if (ticket < 0 || (uint64_t)ticket >= s->calls || s->calls - (uint64_t)ticket > kRing)
-        return fail(COALA_EINVAL, "ticket %lld is not one of the last %d calls", (long long)ticket, kRing);
-    HIPCHK(hipSetDevice(s->device));
-    const int slot = (int)((uint64_t)ticket % kRing);
-    HIPCHK(hipEventSynchronize(s->done[slot])); // the kernels behind this event stored the counts into pinned host memory
-    const int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
-    if (n_src_host)
-        for (int l = 0; l < s->ring_layers[slot]; ++l) n_src_host[l] = pin[l];
-    if (bucket_counts_host)
-        for (int g = 0; g < s->ring_parts[slot]; ++g) bucket_counts_host[g] = pin[COALA_SAMPLER_MAX_LAYERS + g];
+int coala_block_mean_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int64_t n_dst, int dim,
+                                   void* stream) {
+    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
+    if (n_dst == 0) return COALA_OK;
+    if (!indptr || !indices || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
+    const bool v4 = dim % 4 == 0 && ((reinterpret_cast<uintptr_t>(h_src) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
+    if (v4) hipLaunchKernelGGL(mean_aggregate_csr_kernel<4>, grid, blk, 0, (hipStream_t)stream, indptr, indices, h_src, out, n_dst, dim);
+    else hipLaunchKernelGGL(mean_aggregate_csr_kernel<1>, grid, blk, 0, (hipStream_t)stream, indptr, indices, h_src, out, n_dst, dim);
+    HIPCHK(hipGetLastError());
     return COALA_OK;
+}
+
+int coala_block_mean_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* grad_out, float* grad_src,
+                                            int64_t n_dst, int dim, void* stream) {
+    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
+    if (n_dst == 0) return COALA_OK;
+    if (!indptr || !indices || !grad_out || !grad_src) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(mean_aggregate_csr_backward_kernel, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, indptr,
+                       indices, grad_out, grad_src, n_dst, dim);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+int coala_sampler_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* bucket_counts_host) {
+    return wait_impl(s, ticket, n_src_host, nullptr, bucket_counts_host);
+}
+
+int coala_sampler_wait_layers(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host) {
+    return wait_impl(s, ticket, n_src_host, n_edges_host, bucket_counts_host);
 }
 
 int coala_sampler_sample(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
                          uint64_t seed, uint64_t step, int64_t* const* src_nodes_out, int32_t* const* nbr_local_out,
                          int64_t* n_src_host, const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
     if (!s || (!seeds && n_seeds > 0) || !fanouts || !src_nodes_out || !nbr_local_out) return fail(COALA_EINVAL, "null argument");
-    if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
-    if (n_seeds < 0 || n_seeds > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad n_seeds");
-    const int n_parts = bucketing ? bucketing->n_parts : 0;
-    if (n_parts < 0 || n_parts > kMaxParts) return fail(COALA_EINVAL, "bucketing: n_parts must be 0..%d", kMaxParts);
-    if (n_parts > 0 && (!bucketing->bucketed_nodes || !bucketing->counts || !bucketing->dst_in_src)) return fail(COALA_EINVAL, "bucketing: null buffer");
-    hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(s->device));
-    // the handle's scratch (hash table, scan state) is ordered by the stream of its calls: a caller that moves to another stream
-    // first waits there for the previous call's last kernel
-    if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
-    s->last_stream = st;
-    // capacities: layer l has at most cap_l dst nodes and cap_l*(f_l+1) source nodes
+    int rc;
+    if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, bucketing))) return rc;
+    // fixed fan-outs only, into the dense buffers: cap_{l+1} = cap_l * (f + 1) source nodes, cap_l * f neighbour entries
+    coala_sampler_layer_t layers[COALA_SAMPLER_MAX_LAYERS];
     int64_t cap = n_seeds;
-    uint64_t max_items = 0, max_nbr = 0;
     for (int l = 0; l < n_layers; ++l) {
         const int f = fanouts[l];
         if (f < 1 || f > 32) return fail(COALA_EINVAL, "fan-out %d outside 1..32", f);
         const uint64_t items = (uint64_t)cap * (uint64_t)(f + 1);
         if (items > (uint64_t)kMaxTiles * kTile) return fail(COALA_EINVAL, "layer %d would hold %llu items (limit %d)", l, (unsigned long long)items, kMaxTiles * kTile);
-        if (items > max_items) max_items = items;
-        if ((uint64_t)cap * f > max_nbr) max_nbr = (uint64_t)cap * f;
+        layers[l] = coala_sampler_layer_t{src_nodes_out[l], nbr_local_out[l], nullptr, (int64_t)items, cap * f};
         cap = (int64_t)items;
     }
-    const uint64_t table = table_size((int64_t)max_items);
-    const uint64_t wave_tiles = ((uint64_t)cap + kRouteTile - 1) / kRouteTile;
-    int rc;
-    if ((rc = grow((void**)&s->nbr_global, &s->nbr_cap, max_nbr ? max_nbr : 1, sizeof(int64_t), st))) return rc;
-    if ((rc = grow((void**)&s->slot_of_item, &s->item_cap, max_items ? max_items : 1, sizeof(uint32_t), st))) return rc;
-    if (n_parts > 0) {
-        if ((rc = grow((void**)&s->wave_counts, &s->wc_cap, (wave_tiles + 1) * (uint64_t)n_parts, sizeof(uint32_t), st))) return rc;
-        if ((rc = grow((void**)&s->new_of_old, &s->noo_cap, (uint64_t)cap ? (uint64_t)cap : 1, sizeof(uint32_t), st))) return rc;
-    }
-    if (table > s->table_cap) {
-        HIPCHK(hipStreamSynchronize(st));
-        for (void** p : {(void**)&s->tb.keys, (void**)&s->tb.local_of_slot})
-            if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
-        HIPCHK(hipMalloc((void**)&s->tb.keys, table * (sizeof(long long) + sizeof(uint32_t)))); // keys, then the first-position words
-        HIPCHK(hipMalloc((void**)&s->tb.local_of_slot, table * sizeof(uint32_t)));
-        s->table_cap = table;
-        s->tb.minpos = reinterpret_cast<uint32_t*>(s->tb.keys + table);
-        s->clean_items = 0;
-    }
-    const uint64_t ticket = s->calls;
-    const int slot = (int)(ticket % kRing);
-    if (ticket >= kRing) HIPCHK(hipEventSynchronize(s->done[slot])); // the ring slot's previous user has finished writing it
-    int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
-    int64_t* pin_dev = s->counts_pinned_dev + (size_t)slot * kSlot;
-    s->ring_layers[slot] = n_layers;
-    s->ring_parts[slot] = n_parts;
-    if (n_seeds == 0) {
-        for (int l = 0; l < n_layers; ++l) pin[l] = 0;
-        for (int g = 0; g < n_parts; ++g) pin[COALA_SAMPLER_MAX_LAYERS + g] = 0;
-        if (n_parts > 0) HIPCHK(hipMemsetAsync(bucketing->counts, 0, (size_t)n_parts * sizeof(int64_t), st));
-    } else {
-        // the first layer's table: normally left clean by the previous call's last kernel
-        const uint64_t items0 = (uint64_t)n_seeds * (uint64_t)(fanouts[0] + 1);
-        if (s->clean_items == 0 || table_size((int64_t)items0) > table_size((int64_t)s->clean_items)) {
-            const uint32_t t0 = table_size((int64_t)items0);
-            HIPCHK(hipMemsetAsync(s->tb.keys, 0xFF, (size_t)t0 * sizeof(long long), st));
-            HIPCHK(hipMemsetAsync(s->tb.minpos, 0xFF, (size_t)t0 * sizeof(uint32_t), st));
-        }
-        const int64_t* n_dst_dev = nullptr;            // first layer: the seed count travels as a kernel argument
-        const int64_t* dst = seeds;
-        cap = n_seeds;
-        for (int l = 0; l < n_layers; ++l) {
-            const int f = fanouts[l];
-            const int64_t items_cap = cap * (f + 1);
-            int64_t* n_src_dev = s->counts_dev + l + 1;
-            const dim3 gs(grid1d(cap * (f < 16 ? 16 : f < 32 ? 32 : 64), kBlock, 8192)), blk(kBlock);
-            if (f < 16)
-                hipLaunchKernelGGL(sample_insert_kernel<16>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb, s->slot_of_item);
-            else if (f < 32)
-                hipLaunchKernelGGL(sample_insert_kernel<32>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb, s->slot_of_item);
-            else
-                hipLaunchKernelGGL(sample_insert_kernel<64>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb, s->slot_of_item);
-            const int tiles = grid1d(items_cap, kTile, kMaxTiles);
-            if ((++s->scan_gen & 0x3FFFFFFFull) == 0) { // 2^30 scans: the generation tag wraps -> clear the status words once
-                HIPCHK(hipMemsetAsync(s->status, 0, kMaxTiles * sizeof(unsigned long long), st));
-                s->scan_gen++;
-            }
-            hipLaunchKernelGGL(scan_assign_kernel, dim3(tiles), blk, 0, st, dst, s->nbr_global, n_dst_dev, n_seeds, f, s->slot_of_item, s->tb, s->status,
-                               s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, src_nodes_out[l], n_src_dev, pin_dev + l);
-            s->ticket_total += (unsigned long long)tiles;
-            const bool last = l + 1 == n_layers;
-            const int64_t clear_cap = last ? (int64_t)table_size((int64_t)items0) : (int64_t)table_size(items_cap * (fanouts[l + 1] + 1));
-            hipLaunchKernelGGL(relabel_clear_kernel, dim3(grid1d(std::max<int64_t>(cap * f, clear_cap), kBlock, 4096)), blk, 0, st, n_dst_dev, n_seeds, f,
-                               s->slot_of_item, s->tb, nbr_local_out[l], last ? (const int64_t*)nullptr : (const int64_t*)n_src_dev,
-                               last ? 0 : fanouts[l + 1], (int64_t)items0);
-            if (last && n_parts > 0) {
-                const uint32_t P = (uint32_t)n_parts;
-                const int pshift = ilog2_exact((uint64_t)n_parts);
-                int64_t* bases = s->counts_dev + COALA_SAMPLER_MAX_LAYERS + 1;
-                const dim3 gw(grid1d(((items_cap + kRouteTile - 1) / kRouteTile) * 64, kBlock, 4096));
-                hipLaunchKernelGGL(bucket_count_kernel, gw, blk, 0, st, src_nodes_out[l], n_src_dev, P, pshift, s->wave_counts);
-                hipLaunchKernelGGL(bucket_scan_kernel, dim3(1), dim3(64 * (n_parts < 16 ? n_parts : 16)), 0, st, s->wave_counts, n_src_dev, P,
-                                   bucketing->counts, pin_dev + COALA_SAMPLER_MAX_LAYERS, bases);
-                hipLaunchKernelGGL(bucket_scatter_kernel, gw, blk, 0, st, src_nodes_out[l], n_src_dev, P, pshift, s->wave_counts, bases,
-                                   bucketing->bucketed_nodes, s->new_of_old);
-                hipLaunchKernelGGL(bucket_reindex_kernel, dim3(grid1d(cap * f, kBlock, 4096)), blk, 0, st, n_dst_dev, n_seeds, f, s->new_of_old,
-                                   nbr_local_out[l], bucketing->dst_in_src);
-            }
-            dst = src_nodes_out[l];
-            n_dst_dev = n_src_dev;
-            cap = items_cap;
-        }
-        s->clean_items = items0;
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventRecord(s->done[slot], st));
-    s->calls++;
-    if (ticket_out) *ticket_out = (int64_t)ticket;
-    if (n_src_host) return coala_sampler_wait(s, (int64_t)ticket, n_src_host, nullptr);
-    return COALA_OK;
+    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, nullptr, bucketing, ticket_out, stream);
+}
+
+int coala_sampler_sample_layers(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed,
+                                uint64_t step, const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host,
+                                const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
+    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream);
 }
 
 } // extern "C"

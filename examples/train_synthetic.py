@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--nodes", type=int, default=200_000)
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--fan_out", type=str, default="5,5")
+    ap.add_argument("--eval_fan_out", type=str, default=None,
+                    help="fan-outs of the evaluation loader (default: --fan_out); -1 takes every in-edge, e.g. -1,-1 for full neighbourhoods")
     ap.add_argument("--batch_size", type=int, default=1024)
     ap.add_argument("--hidden_channels", type=int, default=128)
     ap.add_argument("--num_classes", type=int, default=19)
@@ -59,6 +61,9 @@ def main():
     device = "cuda:" + str(comm.local_rank)
     comm.initialize_nested_process_group(args.cache_backend)            # :267
     fan_out = [int(f) for f in args.fan_out.split(",")]
+    eval_fan_out = fan_out if args.eval_fan_out is None else [int(f) for f in args.eval_fan_out.split(",")]
+    if len(eval_fan_out) != len(fan_out):
+        ap.error("--eval_fan_out needs as many layers as --fan_out")
 
     dataset = None
     if args.path:   # IGBDatast_Shared_CSC_UVA / OGBDataset_Shared_UVA (:273-285): CSC in HBM, features in shared pinned host memory
@@ -134,7 +139,8 @@ def main():
 
     # evaluation over the test nodes through a second loader, as the reference does (:156-195)
     test_nd = Node_Distributor(comm, test_ids, args.batch_size, *files, parsing_method=args.distribution)
-    test_loader = COALA_GNN_DataLoader(SSD_INFO(1, args.dim * 4, 1024, 0), test_nd, g, sampler, args.batch_size, args.dim, fan_out,
+    eval_sampler = sampler if eval_fan_out == fan_out else NeighborSampler(eval_fan_out)
+    test_loader = COALA_GNN_DataLoader(SSD_INFO(1, args.dim * 4, 1024, 0), test_nd, g, eval_sampler, args.batch_size, args.dim, eval_fan_out,
                                        args.cache_size, device, refresh_counter=args.refresh_counter,
                                        cache_backend=args.cache_backend, sim_buf=feat, shuffle=False, num_rows=args.nodes)
     model.eval()

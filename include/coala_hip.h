@@ -339,7 +339,8 @@ int coala_sampler_destroy(coala_sampler_t* s);
  *   n_src_host[l]    : HOST int64, number of source nodes of block l.  Non-NULL: the call returns when the counts are there (it
  *                      waits on an event behind the sampler's one kernel, not on the stream).  NULL: the call only enqueues;
  *                      collect the counts later with coala_sampler_wait(ticket) -- up to 8 calls may be outstanding.
- * The whole multi-layer sample is ONE kernel launch (a persistent kernel with grid barriers between its phases).
+ * The sample is a short sequence of kernels on `stream` (three per layer, four more for the bucketing); the layers read their sizes
+ * from device memory, so nothing waits in between.
  * Randomness: counter-based, keyed by (seed, step, layer, node id): same arguments, same sample.
  *
  * bucketing (nullable): additionally deliver the input nodes of the LAST layer bucketed by owner = id % n_parts, stable inside
@@ -360,6 +361,38 @@ int coala_sampler_sample(coala_sampler_t* s, const int64_t* seeds, int64_t n_see
 /* Counts of an earlier call (its ticket): n_src_host[n_layers] and, when it bucketed, bucket_counts_host[n_parts] (either NULL). */
 int coala_sampler_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* bucket_counts_host);
 
+/* Per-layer outputs, for fixed and full layers alike (coala_sampler_sample_layers).  fanouts[l] is 1..32, or -1 for a FULL layer:
+ * every in-edge of every destination node, in CSC order (repeated edges and self-loops kept, degree 0 gives an empty segment); it
+ * draws no random numbers, and fixed layers keep their layer index l as the RNG key.  The source list follows the same rule as a
+ * fixed layer: the dst nodes first, then every other neighbour in order of first appearance in the row-major (d, edge) scan.
+ * A full layer's block is CSR: indptr_local int64[n_dst + 1] (exclusive scan of the degrees) and nbr_local int32[E] (local source
+ * index of each edge).
+ * Capacities, with dst_cap_0 = n_seeds:
+ *   fixed layer, no full layer before it: src_cap >= dst_cap * (f + 1), edge_cap >= dst_cap * f, and dst_cap * (f + 1) <= 8,388,608
+ *     (checked here: COALA_EINVAL); dst_cap of the next layer = dst_cap * (f + 1);
+ *   full layer: indptr_local holds dst_cap + 1 entries; its item count n_dst + E must stay <= min(8,388,608, src_cap) and E <= edge_cap;
+ *     dst_cap of the next layer = min(8,388,608, src_cap);
+ *   fixed layer behind a full layer: its worst case n_dst * (f + 1) must stay <= min(8,388,608, src_cap), n_dst * f <= edge_cap;
+ *     dst_cap of the next layer = min(dst_cap * (f + 1), 8,388,608, src_cap).
+ * The last two are known on the device only and are checked there: the call's remaining kernels then see empty layers and write
+ * nothing past the capacities, and coala_sampler_wait_layers (or this call, when it waits) returns COALA_EINVAL with a message that
+ * names the layer and its item count.  The handle stays usable.  With `bucketing`, bucketed_nodes holds dst_cap of the layer after
+ * the last one, dst_in_src the last layer's dst_cap; a full input layer's nbr_local then indexes bucketed_nodes. */
+typedef struct coala_sampler_layer {
+    int64_t* src_nodes;    /* device int64[src_cap]: source nodes of the block                                    */
+    int32_t* nbr_local;    /* device int32[edge_cap]: fixed -> [n_dst, f] -1 padded; full -> [E]                 */
+    int64_t* indptr_local; /* full layer: device int64[dst_cap + 1]; fixed layer: unused (NULL)                   */
+    int64_t src_cap;
+    int64_t edge_cap;
+} coala_sampler_layer_t;
+/* As coala_sampler_sample, with per-layer outputs and fan-out -1.  n_edges_host[l] (nullable, HOST): E of a full layer, n_dst * f of
+ * a fixed one.  coala_sampler_sample keeps refusing -1: its dense outputs cannot hold a full layer. */
+int coala_sampler_sample_layers(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, int64_t* n_src_host,
+                                int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream);
+/* Counts of an earlier call, with the edge counts of its layers; returns the device-side refusal of a full layer, if any. */
+int coala_sampler_wait_layers(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host);
+
 /* Block op for the consumer of these blocks (the native Block objects stand where DGL blocks stand in
  * examples/sbatch_ssd_gnn_train.py:138-141; dgl.nn.SAGEConv's "mean" reduces to this): out[d, :] = mean over the valid j of
  * h_src[nbr[d, j], :]; nbr int32 [n_dst, fanout] (-1 padded, fan-out <= 32), fp32 rows of `dim` floats.  The backward adds
@@ -367,6 +400,13 @@ int coala_sampler_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, 
 int coala_block_mean_aggregate(int device, const int32_t* nbr, const float* h_src, float* out, int64_t n_dst, int fanout, int dim, void* stream);
 int coala_block_mean_aggregate_backward(int device, const int32_t* nbr, const float* grad_out, float* grad_src, int64_t n_dst, int fanout,
                                         int dim, void* stream);
+/* The same op on a ragged (CSR) block, the form of a full layer: row d averages h_src[indices[e]] for e in
+ * [indptr[d], indptr[d+1]), summed in that order (bit-identical to the dense op on any row both can express); an empty row gives
+ * zeros.  One wave aggregates a row, so a hub row of 10^6 edges runs on one wave. */
+int coala_block_mean_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int64_t n_dst,
+                                   int dim, void* stream);
+int coala_block_mean_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* grad_out, float* grad_src,
+                                            int64_t n_dst, int dim, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Shared pinned-host ("UVA") region.  Replaces SharedUVAManager (COALA_GNN_Modules/shared_UVA.cuh:26-115):
