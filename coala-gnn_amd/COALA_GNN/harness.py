@@ -1,12 +1,14 @@
-"""Small consumer of the loader's 4-tuple, used by bench.py's epoch leg and the tests: a 2-layer GraphSAGE (mean) in plain
-torch on the native Block objects.  Stands where examples/models.py:DistSAGE + dgl.nn.SAGEConv stand in the reference's
-training script (examples/sbatch_ssd_gnn_train.py:98-145); the model itself is out of scope (dense compute downstream of
-the path), this is harness plumbing."""
+"""Small consumers of the loader's 4-tuple on the native Block objects.  SageMean, a 2-layer GraphSAGE (mean) in plain torch, is
+used by bench.py's epoch leg and the tests; it stands where examples/models.py:DistSAGE + dgl.nn.SAGEConv stand in the reference's
+training script (examples/sbatch_ssd_gnn_train.py:98-145).  GAT and GCN mirror the reference's examples/models.py:GAT and :GCN on
+COALA_GNN.nn's GATConv and GraphConv (--model_type gat|gcn); GAT's attention step is a native kernel (Block.gat_aggregate)."""
 import time
 
 import torch
 
-__all__ = ["SageMean", "train_steps", "FlatGradAllReduce"]
+from .nn import GATConv, GraphConv
+
+__all__ = ["SageMean", "GAT", "GCN", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -21,6 +23,43 @@ class SageMean(torch.nn.Module):
             h = self.lin_self[i](b.dst_rows(h)) + self.lin_nbr[i](b.mean_aggregate(h))
             if i + 1 < len(blocks):
                 h = torch.relu(h)
+        return h
+
+
+class GAT(torch.nn.Module):
+    """examples/models.py:GAT: n_layers GATConv layers of num_heads heads, no activation between them (as in the reference), the
+    heads flattened between layers; the last layer's heads are averaged and passed through log_softmax."""
+
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, num_heads):
+        super().__init__()
+        dims = [in_feats] + [n_hidden * num_heads] * (n_layers - 1)
+        outs = [n_hidden] * (n_layers - 1) + [n_classes]
+        self.layers = torch.nn.ModuleList(GATConv((dims[i], dims[i]), outs[i], num_heads) for i in range(n_layers))
+
+    def forward(self, blocks, x):
+        h = x
+        for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+            h = layer(block, (h, block.dst_rows(h)))
+            if i + 1 < len(self.layers):
+                h = h.flatten(1)
+        return h.mean(1).log_softmax(dim=-1)
+
+
+class GCN(torch.nn.Module):
+    """examples/models.py:GCN: n_layers GraphConv layers (norm='both'), dropout then relu between them."""
+
+    def __init__(self, in_feats, h_feats, num_classes, num_layers=2, dropout=0.2):
+        super().__init__()
+        dims = [in_feats] + [h_feats] * (num_layers - 1) + [num_classes]
+        self.layers = torch.nn.ModuleList(GraphConv(dims[i], dims[i + 1]) for i in range(num_layers))
+        self.dropout = torch.nn.Dropout(dropout)
+
+    def forward(self, blocks, x):
+        h = x
+        for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+            h = layer(block, (h, block.dst_rows(h)))
+            if i + 1 < len(self.layers):
+                h = torch.relu(self.dropout(h))
         return h
 
 

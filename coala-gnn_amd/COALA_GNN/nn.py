@@ -1,0 +1,98 @@
+"""GATConv and GraphConv on the native Block objects, for the reference's GAT and GCN models (examples/models.py; DGL is not
+installed on the MI355X image).  Both take (block, (h_src, h_dst)) as DGL's modules do on a block.
+
+GATConv's projections are dense and stay in torch; its attention step (score, per-destination softmax, weighted sum) is
+Block.gat_aggregate, a native kernel on both block forms.  GraphConv reduces to Block.mean_aggregate times the in-degree."""
+import torch
+
+__all__ = ["GATConv", "GraphConv"]
+
+
+class GATConv(torch.nn.Module):
+    """Graph attention layer with separate source and destination projections (DGL 1.x GATConv given a tuple in_feats).
+
+    Semantics, for destination node d, head h and the valid in-edges j of d (source s_j) in the block:
+        feat_src = fc_src(feat_drop(h_src)).view(-1, H, D);   feat_dst = fc_dst(feat_drop(h_dst)).view(-1, H, D)
+        el[s, h] = sum_k feat_src[s, h, k] * attn_l[0, h, k];   er[d, h] = sum_k feat_dst[d, h, k] * attn_r[0, h, k]
+        e_j = leaky_relu(el[s_j, h] + er[d, h], negative_slope);   a_j = softmax of e over d's in-edges
+        out[d, h, :] = sum_j a_j feat_src[s_j, h, :] + bias.view(H, D);   then activation, if any
+    -> [num_dst, H, D].  A destination without an in-edge gets the bias alone (DGL's allow_zero_in_degree=True).
+    Parameters, with the names and shapes of DGL 1.x for a tuple in_feats, so that such a state_dict loads:
+        fc_src.weight [H * D, in_src], fc_dst.weight [H * D, in_dst] (no bias), attn_l [1, H, D], attn_r [1, H, D], bias [H * D].
+    Initialisation: Xavier-normal with the gain of relu for fc_src, fc_dst, attn_l and attn_r; bias zero.
+    h_dst must be the destination rows of h_src: block.dst_rows(h_src) (h_src[:num_dst] unless the block is owner-bucketed).
+    Attention dropout and residual connections are not provided."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, negative_slope=0.2, bias=True, activation=None):
+        super().__init__()
+        in_src, in_dst = in_feats if isinstance(in_feats, (tuple, list)) else (in_feats, in_feats)
+        self._num_heads, self._out_feats = num_heads, out_feats
+        self.fc_src = torch.nn.Linear(in_src, out_feats * num_heads, bias=False)
+        self.fc_dst = torch.nn.Linear(in_dst, out_feats * num_heads, bias=False)
+        self.attn_l = torch.nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.attn_r = torch.nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.bias = torch.nn.Parameter(torch.empty(num_heads * out_feats)) if bias else None
+        self.feat_drop = torch.nn.Dropout(feat_drop)
+        self.negative_slope = negative_slope
+        self.activation = activation
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        for w in (self.fc_src.weight, self.fc_dst.weight, self.attn_l, self.attn_r):
+            torch.nn.init.xavier_normal_(w, gain=gain)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, block, feat):
+        h_src, h_dst = feat
+        H, D = self._num_heads, self._out_feats
+        feat_src = self.fc_src(self.feat_drop(h_src)).view(-1, H, D)
+        feat_dst = self.fc_dst(self.feat_drop(h_dst)).view(-1, H, D)
+        el = (feat_src * self.attn_l).sum(-1)
+        er = (feat_dst * self.attn_r).sum(-1)
+        rst = block.gat_aggregate(el, er, feat_src, self.negative_slope)
+        if self.bias is not None:
+            rst = rst + self.bias.view(1, H, D)
+        if self.activation is not None:
+            rst = self.activation(rst)
+        return rst
+
+
+class GraphConv(torch.nn.Module):
+    """Graph convolution with norm='both' (DGL GraphConv's default), on a block:
+        out[d] = in_deg(d)^-1/2 * sum_j out_deg(s_j)^-1/2 * h_src[s_j] @ weight + bias,   then activation, if any
+    with the degrees counted over the valid edges of the block and clamped to at least 1.  weight [in_feats, out_feats] (Xavier-uniform),
+    bias [out_feats] (zero): DGL's names and shapes.  The projection is applied before the aggregation when in_feats > out_feats, after
+    it otherwise, as DGL does.  h_dst is accepted for DGL's calling convention and unused.
+    Deviation: a destination without an in-edge gets the bias alone; DGL raises unless allow_zero_in_degree=True, and then gives the
+    same row."""
+
+    def __init__(self, in_feats, out_feats, bias=True, activation=None):
+        super().__init__()
+        self._in_feats, self._out_feats = in_feats, out_feats
+        self.weight = torch.nn.Parameter(torch.empty(in_feats, out_feats))
+        self.bias = torch.nn.Parameter(torch.empty(out_feats)) if bias else None
+        self.activation = activation
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        torch.nn.init.xavier_uniform_(self.weight)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, block, feat):
+        h_src = feat[0] if isinstance(feat, (tuple, list)) else feat
+        out_deg = block.out_degrees().to(device=h_src.device, dtype=h_src.dtype).clamp_min(1)
+        in_deg = block.in_degrees().to(device=h_src.device, dtype=h_src.dtype).clamp_min(1)
+        h = h_src * out_deg.pow(-0.5).unsqueeze(-1)
+        if self._in_feats > self._out_feats:
+            h = h @ self.weight
+        rst = block.mean_aggregate(h) * in_deg.sqrt().unsqueeze(-1)   # sum * in_deg^-1/2 = mean * in_deg^1/2; 0 without in-edges
+        if self._in_feats <= self._out_feats:
+            rst = rst @ self.weight
+        if self.bias is not None:
+            rst = rst + self.bias
+        if self.activation is not None:
+            rst = self.activation(rst)
+        return rst

@@ -106,6 +106,67 @@ class _MeanAggregateCSR(torch.autograd.Function):
         return grad_src, None, None
 
 
+def _gat_contig(el, er, feat_src):
+    return el.contiguous(), er.contiguous(), feat_src.contiguous()
+
+
+class _GatAggregate(torch.autograd.Function):
+    """DGL GATConv's attention step on a fixed block (coala_block_gat_aggregate): per head, a softmax of leaky_relu(el[s] + er[d]) over
+    the valid nbr[d, j], then the weighted sum of feat_src[s].  One kernel forward, one backward (gradients for el, er and feat_src)."""
+
+    @staticmethod
+    def forward(ctx, el, er, feat_src, nbr, negative_slope):
+        el, er, f = _gat_contig(el, er, feat_src)
+        n_dst, fanout = nbr.shape
+        H, D = f.shape[1], f.shape[2]
+        out = torch.empty((n_dst, H, D), dtype=torch.float32, device=f.device)
+        lse = torch.empty((n_dst, H), dtype=torch.float32, device=f.device)
+        _capi.check(_lib.coala_block_gat_aggregate(f.device.index or 0, nbr.data_ptr(), el.data_ptr(), er.data_ptr(), f.data_ptr(), out.data_ptr(),
+                                                   lse.data_ptr(), n_dst, fanout, H, D, negative_slope, current_stream()))
+        ctx.save_for_backward(el, er, f, nbr, out, lse)
+        ctx.slope = negative_slope
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        el, er, f, nbr, out, lse = ctx.saved_tensors
+        g = grad_out.contiguous()
+        grad_feat, grad_el, grad_er = torch.zeros_like(f), torch.zeros_like(el), torch.empty_like(er)
+        _capi.check(_lib.coala_block_gat_aggregate_backward(f.device.index or 0, nbr.data_ptr(), el.data_ptr(), er.data_ptr(), f.data_ptr(),
+                                                            out.data_ptr(), lse.data_ptr(), g.data_ptr(), grad_feat.data_ptr(), grad_el.data_ptr(),
+                                                            grad_er.data_ptr(), nbr.shape[0], nbr.shape[1], f.shape[1], f.shape[2], ctx.slope,
+                                                            current_stream()))
+        return grad_el, grad_er, grad_feat, None, None
+
+
+class _GatAggregateCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_gat_aggregate_csr): row d's edges are indices[indptr[d]:indptr[d+1]]."""
+
+    @staticmethod
+    def forward(ctx, el, er, feat_src, indptr, indices, negative_slope):
+        el, er, f = _gat_contig(el, er, feat_src)
+        n_dst = indptr.numel() - 1
+        H, D = f.shape[1], f.shape[2]
+        out = torch.empty((n_dst, H, D), dtype=torch.float32, device=f.device)
+        lse = torch.empty((n_dst, H), dtype=torch.float32, device=f.device)
+        _capi.check(_lib.coala_block_gat_aggregate_csr(f.device.index or 0, indptr.data_ptr(), indices.data_ptr(), el.data_ptr(), er.data_ptr(),
+                                                       f.data_ptr(), out.data_ptr(), lse.data_ptr(), n_dst, H, D, negative_slope, current_stream()))
+        ctx.save_for_backward(el, er, f, indptr, indices, out, lse)
+        ctx.slope = negative_slope
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        el, er, f, indptr, indices, out, lse = ctx.saved_tensors
+        g = grad_out.contiguous()
+        grad_feat, grad_el, grad_er = torch.zeros_like(f), torch.zeros_like(el), torch.empty_like(er)
+        _capi.check(_lib.coala_block_gat_aggregate_csr_backward(f.device.index or 0, indptr.data_ptr(), indices.data_ptr(), el.data_ptr(),
+                                                                er.data_ptr(), f.data_ptr(), out.data_ptr(), lse.data_ptr(), g.data_ptr(),
+                                                                grad_feat.data_ptr(), grad_el.data_ptr(), grad_er.data_ptr(), indptr.numel() - 1,
+                                                                f.shape[1], f.shape[2], ctx.slope, current_stream()))
+        return grad_el, grad_er, grad_feat, None, None, None
+
+
 class Block(object):
     """One message-flow block: dst node d aggregates src rows nbr[d, j] >= 0 (fixed-stride form, a fixed fan-out), or
     indices[indptr[d]:indptr[d+1]] (ragged CSR form, a full layer: nbr is None).
@@ -184,6 +245,68 @@ class Block(object):
         idx = self.nbr.clamp_min(0).to(torch.int64)
         g = h_src[idx] * valid.unsqueeze(-1).to(h_src.dtype)
         return g.sum(1) / valid.sum(1).clamp_min(1).unsqueeze(-1).to(h_src.dtype)
+
+    def num_src_nodes(self):   # DGL's block API (examples/models.py calls block.num_dst_nodes())
+        return self.num_src
+
+    def num_dst_nodes(self):
+        """Number of destination nodes.  On an owner-bucketed input block h[:num_dst_nodes()] is NOT the destination rows of a
+        per-source tensor h: use dst_rows(h)."""
+        return self.num_dst
+
+    def _edges(self):
+        """(row, local source index) of every valid edge, int64 on the block's device."""
+        if self.nbr is None:
+            deg = self.indptr[1:] - self.indptr[:-1]
+            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg)
+            src = self.indices.to(torch.int64)
+        else:
+            rows = torch.arange(self.num_dst, device=self.nbr.device).repeat_interleave(self.nbr.shape[1])
+            src = self.nbr.reshape(-1).to(torch.int64)
+        valid = src >= 0
+        return rows[valid], src[valid]
+
+    def in_degrees(self):
+        """Valid in-edges of every destination node within the block: int64 [num_dst] (DGL's block.in_degrees())."""
+        if self.nbr is not None:
+            return (self.nbr >= 0).sum(1)
+        rows, _ = self._edges()
+        return torch.bincount(rows, minlength=self.num_dst)
+
+    def out_degrees(self):
+        """Edges leaving every source node within the block: int64 [num_src] (DGL's block.out_degrees())."""
+        _, src = self._edges()
+        return torch.bincount(src, minlength=self.num_src)
+
+    def gat_aggregate(self, el, er, feat_src, negative_slope=0.2):
+        """DGL GATConv's attention step: for every dst node d and head h, a softmax over d's valid in-edges of
+        leaky_relu(el[s, h] + er[d, h], negative_slope), then sum_j a_j feat_src[s_j, h, :].  el [num_src, H], er [num_dst, H],
+        feat_src [num_src, H, D] -> fp32 [num_dst, H, D]; a dst node without an in-edge gets zeros.  Native kernels (gradients for
+        all three inputs) for fp32 GPU tensors, fan-out <= 32 or the ragged form of a full layer, and H <= 16; plain torch otherwise."""
+        native = (el.is_cuda and er.is_cuda and feat_src.is_cuda and all(t.dtype == torch.float32 for t in (el, er, feat_src))
+                  and feat_src.dim() == 3 and feat_src.shape[1] <= 16)
+        if self.nbr is None:
+            if native and self.indptr.is_cuda and self.indices.is_cuda:
+                return _GatAggregateCSR.apply(el, er, feat_src, self.indptr.contiguous(), self.indices.contiguous(), float(negative_slope))
+        elif native and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
+            return _GatAggregate.apply(el, er, feat_src, self.nbr, float(negative_slope))
+        return self.gat_aggregate_torch(el, er, feat_src, negative_slope)
+
+    def gat_aggregate_torch(self, el, er, feat_src, negative_slope=0.2):
+        """gat_aggregate in plain torch, any device and dtype: an edge-list softmax (scatter max, exp, index_add) that materialises the
+        gathered [E, H, D] source rows.  The fallback of gat_aggregate, and its reference."""
+        rows, src = self._edges()
+        dev = feat_src.device
+        rows, src = rows.to(dev), src.to(dev)
+        H = feat_src.shape[1]
+        e = torch.nn.functional.leaky_relu(el[src] + er[rows], negative_slope)              # [E, H]
+        m = torch.full((self.num_dst, H), float("-inf"), dtype=e.dtype, device=dev)
+        m = m.scatter_reduce(0, rows.unsqueeze(1).expand(-1, H), e.detach(), "amax").detach()   # the shift cancels in the softmax
+        p = torch.exp(e - m[rows])
+        l = torch.zeros((self.num_dst, H), dtype=e.dtype, device=dev).index_add(0, rows, p)
+        a = p / l[rows]
+        out = torch.zeros((self.num_dst,) + tuple(feat_src.shape[1:]), dtype=feat_src.dtype, device=dev)
+        return out.index_add(0, rows, a.unsqueeze(-1).to(feat_src.dtype) * feat_src[src])
 
 
 class NeighborSampler(object):

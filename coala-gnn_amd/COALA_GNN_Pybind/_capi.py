@@ -123,6 +123,10 @@ SYMBOLS = {
     "coala_sampler_wait_layers": (_I, [_VP, _I64, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     "coala_block_mean_aggregate_csr": (_I, [_I, _VP, _VP, _VP, _VP, _I64, _I, _VP]),
     "coala_block_mean_aggregate_csr_backward": (_I, [_I, _VP, _VP, _VP, _VP, _I64, _I, _VP]),
+    "coala_block_gat_aggregate": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _I, C.c_float, _VP]),
+    "coala_block_gat_aggregate_backward": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _I, C.c_float, _VP]),
+    "coala_block_gat_aggregate_csr": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, C.c_float, _VP]),
+    "coala_block_gat_aggregate_csr_backward": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, C.c_float, _VP]),
     "coala_shm_open": (_I, [C.c_char_p, _U64, _I, _I, C.POINTER(_VP)]),
     "coala_shm_host_ptr": (_VP, [_VP]),
     "coala_shm_device_ptr": (_VP, [_VP]),

@@ -4,6 +4,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
 --path -- on a dataset directory in the reference's on-disk layout (--data IGB --dataset_size medium | --data OGB; :202-213, :273-285).
 
   python examples/train_synthetic.py --nodes 200000 --dim 128 --epochs 2
+  python examples/train_synthetic.py --model_type gat --num_heads 4 --fan_out 5,5 --eval_fan_out=-1,-1
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -21,7 +22,7 @@ import torch  # noqa: E402
 
 from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
-from COALA_GNN.harness import SageMean  # noqa: E402
+from COALA_GNN.harness import GAT, GCN, SageMean  # noqa: E402
 from COALA_GNN.sampler import NeighborSampler  # noqa: E402
 from COALA_GNN.synthetic import alloc_pinned_table, powerlaw_csc  # noqa: E402
 
@@ -49,7 +50,9 @@ def main():
     # accepted so that the reference's command lines (examples/4GB_script.sh, Cache_compare_script.sh, Distribution_compare_script.sh) run as they are
     ap.add_argument("--num_layers", type=int, default=None, help="must equal the number of fan-outs when given")
     ap.add_argument("--feat_cpu", action="store_true", help="features in pinned host memory: always the case here (the NVMe tier is out of scope)")
-    ap.add_argument("--model_type", type=str, default="sage", choices=["sage"], help="the harness model; the reference's GAT is dense compute outside the path")
+    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "sage", "gcn"],
+                    help="sage: GraphSAGE (mean); gat: GAT with --num_heads heads (native attention aggregation); gcn: GraphConv, norm='both'")
+    ap.add_argument("--num_heads", type=int, default=4, help="attention heads of --model_type gat")
     args = ap.parse_args()
     if args.num_layers is not None and args.num_layers != len(args.fan_out.split(",")) and args.num_layers != 2:
         ap.error("--num_layers does not match --fan_out")   # (the reference's own scripts pass --num_layers 2 with a 3-entry fan-out: tolerated)
@@ -104,7 +107,12 @@ def main():
                                         args.cache_size, device, refresh_counter=args.refresh_counter,
                                         cache_backend=args.cache_backend, sim_buf=feat, shuffle=False, num_rows=args.nodes,
                                         prefetch=args.prefetch)                                             # :82-95
-    model = SageMean(args.dim, args.hidden_channels, args.num_classes, len(fan_out)).to(device)
+    if args.model_type == "gat":                                                                            # :220-231
+        model = GAT(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads).to(device)
+    elif args.model_type == "gcn":
+        model = GCN(args.dim, args.hidden_channels, args.num_classes, len(fan_out)).to(device)
+    else:
+        model = SageMean(args.dim, args.hidden_channels, args.num_classes, len(fan_out)).to(device)
     if comm.global_size > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[comm.local_rank])             # :112
     loss_fcn = torch.nn.CrossEntropyLoss().to(device)

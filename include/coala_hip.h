@@ -407,6 +407,33 @@ int coala_block_mean_aggregate_csr(int device, const int64_t* indptr, const int3
                                    int dim, void* stream);
 int coala_block_mean_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* grad_out, float* grad_src,
                                             int64_t n_dst, int dim, void* stream);
+/* GAT attention aggregation (DGL GATConv's message step; its projections are dense and stay outside).  For dst d, head h and the
+ * valid in-edges j of d with source s_j:
+ *   z_j = el[s_j, h] + er[d, h];  e_j = leaky_relu(z_j, negative_slope);  a_j = exp(e_j - m) / sum_k exp(e_k - m), m = max_k e_k;
+ *   out[d, h, :] = sum_j a_j feat[s_j, h, :].
+ * el fp32 [n_src, heads], er fp32 [n_dst, heads], feat fp32 [n_src, heads, dim], out fp32 [n_dst, heads, dim], all contiguous;
+ * heads 1..16, dim >= 1, heads * dim < 2^31.  A row without a valid edge gives exactly 0.
+ * Saved state: lse fp32 [n_dst, heads] = m + log(sum_k exp(e_k - m)), the log-sum-exp of the row's scores (-inf for a row without a
+ * valid edge); the backward recomputes a_j = exp(e_j - lse) from it.
+ * Fixed form: nbr int32 [n_dst, fanout], -1 padded, fan-out 1..32.  CSR form: the edges of row d are indices[indptr[d] .. indptr[d+1])
+ * (indptr int64 [n_dst + 1], indices int32), any degree: one wave takes a row 64 edges at a time with an online max and rescale.  The
+ * forward is deterministic; a fixed row whose valid entries come first, in CSC order, gives the bits of the same CSR row (out, lse and
+ * the backward's grad_er).
+ * Backward, with g = grad_out [n_dst, heads, dim] and out / lse from the forward:
+ *   t_j = a_j (<g[d, h, :], feat[s_j, h, :]> - <g[d, h, :], out[d, h, :]>) (z_j > 0 ? 1 : negative_slope);
+ *   grad_feat[s_j, h, :] += a_j g[d, h, :];  grad_el[s_j, h] += t_j;  grad_er[d, h] = sum_j t_j.
+ * grad_feat [n_src, heads, dim] and grad_el [n_src, heads] are accumulated with hardware float atomics: the caller zeroes them, and the
+ * order of the additions varies.  grad_er [n_dst, heads] is written whole. */
+int coala_block_gat_aggregate(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, float* out, float* lse,
+                              int64_t n_dst, int fanout, int heads, int dim, float negative_slope, void* stream);
+int coala_block_gat_aggregate_backward(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, const float* out,
+                                       const float* lse, const float* grad_out, float* grad_feat, float* grad_el, float* grad_er, int64_t n_dst,
+                                       int fanout, int heads, int dim, float negative_slope, void* stream);
+int coala_block_gat_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er, const float* feat,
+                                  float* out, float* lse, int64_t n_dst, int heads, int dim, float negative_slope, void* stream);
+int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er,
+                                           const float* feat, const float* out, const float* lse, const float* grad_out, float* grad_feat,
+                                           float* grad_el, float* grad_er, int64_t n_dst, int heads, int dim, float negative_slope, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Shared pinned-host ("UVA") region.  Replaces SharedUVAManager (COALA_GNN_Modules/shared_UVA.cuh:26-115):
