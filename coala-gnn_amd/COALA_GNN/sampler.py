@@ -19,9 +19,10 @@ ITEM_LIMIT = 8192 * 1024   # items (destination nodes + neighbour slots) one lay
 
 
 class CSCGraph(object):
-    """int64 CSC (indptr[N+1], indices[E]) resident on one GPU + per-node data (labels...)."""
+    """int64 CSC (indptr[N+1], indices[E]) resident on one GPU + per-node data (labels...) + per-edge data in CSC order (edge weights
+    for NeighborSampler(prob=key))."""
 
-    def __init__(self, indptr, indices, ndata=None):
+    def __init__(self, indptr, indices, ndata=None, edata=None):
         assert indptr.dtype == torch.int64 and indices.dtype == torch.int64
         assert indptr.is_cuda and indices.is_cuda, "the CSC arrays must be device tensors (HBM or a pinned-host alias)"
         self.indptr, self.indices = indptr.contiguous(), indices.contiguous()
@@ -29,6 +30,8 @@ class CSCGraph(object):
         self.num_edges = self.indices.numel()
         self.device = self.indptr.device
         self.ndata = dict(ndata or {})
+        self.edata = dict(edata or {})
+        self._weights = {}   # edata key -> (the entry, its version, the validated fp32 device copy)
         self._max_in_degree = None
         self._h = C.c_void_p()
         dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
@@ -41,6 +44,25 @@ class CSCGraph(object):
         if self._max_in_degree is None:
             self._max_in_degree = int((self.indptr[1:] - self.indptr[:-1]).max().item()) if self.num_nodes > 0 else 0
         return self._max_in_degree
+
+    def edge_weights(self, key):
+        """edata[key] as a contiguous fp32 tensor on the graph's device, validated once (num_edges values, finite, >= 0) and cached
+        until the entry is replaced or modified in place.  KeyError when the key is missing, ValueError (naming it) when bad."""
+        if key not in self.edata:
+            raise KeyError(f"edata has no {key!r}: the edge weights of NeighborSampler(prob={key!r}) (keys: {sorted(self.edata)})")
+        t = self.edata[key]
+        hit = self._weights.get(key)
+        if hit is not None and hit[0] is t and hit[1] == t._version:
+            return hit[2]
+        if not isinstance(t, torch.Tensor) or t.is_complex():
+            raise ValueError(f"edata[{key!r}]: edge weights must be a real tensor")
+        if t.dim() != 1 or t.numel() != self.num_edges:
+            raise ValueError(f"edata[{key!r}]: edge weights must have shape ({self.num_edges},) in CSC order, got {tuple(t.shape)}")
+        w = t.to(device=self.device, dtype=torch.float32).contiguous()
+        if w.numel() and bool((~torch.isfinite(w) | (w < 0)).any()):
+            raise ValueError(f"edata[{key!r}]: edge weights must be finite and >= 0 (as fp32)")
+        self._weights[key] = (t, t._version, w)
+        return w
 
     def close(self):
         if getattr(self, "_h", None):
@@ -313,7 +335,7 @@ class NeighborSampler(object):
     stream_safe = True  # every kernel and allocation of sample() goes to torch's current stream
     completes_on_host = True  # sample() / sample_end() return after the host has seen the event behind the sample's last kernel (coala_sampler_wait)
 
-    def __init__(self, fanouts, seed=0, bucket_by_owner=0):
+    def __init__(self, fanouts, seed=0, bucket_by_owner=0, prob=None):
         self.fanouts = [int(f) for f in fanouts]
         if not 1 <= len(self.fanouts) <= 8:
             raise ValueError("1..8 layers")
@@ -327,10 +349,14 @@ class NeighborSampler(object):
         self.bucket_by_owner = int(bucket_by_owner)
         if not 0 <= self.bucket_by_owner <= 64:
             raise ValueError("bucket_by_owner must be 0..64")
+        # DGL's prob=: the edata key of non-negative per-edge weights.  A fixed layer then draws f distinct edges of positive weight
+        # with probability proportional to it (all of them when there are at most f; never one of weight 0); a -1 layer still takes
+        # every in-edge
+        self.prob = prob
 
     @staticmethod
-    def make_graph(indptr, indices, ndata=None):
-        return CSCGraph(indptr, indices, ndata)
+    def make_graph(indptr, indices, ndata=None, edata=None):
+        return CSCGraph(indptr, indices, ndata, edata)
 
     def sample(self, g, seed_nodes, step=None):
         """-> (input_nodes, output_nodes, blocks), blocks[0] is the input layer (DGL order)."""
@@ -342,6 +368,7 @@ class NeighborSampler(object):
         loader launches step t+1's sample right behind step t's fetch -- never waits for the sampler at all."""
         if isinstance(g, tuple):
             g = CSCGraph(*g)
+        weights = g.edge_weights(self.prob) if self.prob is not None else None   # raises before any launch
         seeds = seed_nodes.to(g.device, dtype=torch.int64).contiguous()
         n = seeds.numel()
         rev = list(reversed(self.fanouts))          # DGL samples the output layer first
@@ -380,11 +407,16 @@ class NeighborSampler(object):
             extra = (bucketed, counts, dst_in_src)
         ticket = C.c_int64(-1)
         # three launches per layer, nothing else: no host wait here (n_src_host = NULL)
-        if full:
+        if full or weights is not None:
             lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr() if ind[l] is not None else None,
                                                                 src_caps[l], edge_caps[l]) for l in range(L)])
-            _capi.check(_lib.coala_sampler_sample_layers(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, None, None,
-                                                         C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
+            if weights is not None:
+                _capi.check(_lib.coala_sampler_sample_layers_weighted(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, weights.data_ptr(), None,
+                                                                      None, C.byref(bk) if bk is not None else None, C.byref(ticket),
+                                                                      current_stream()))
+            else:
+                _capi.check(_lib.coala_sampler_sample_layers(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, None, None,
+                                                             C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
         else:
             src_p = (C.c_void_p * L)(*[t.data_ptr() for t in src])
             nbr_p = (C.c_void_p * L)(*[t.data_ptr() for t in nbr])
@@ -392,16 +424,16 @@ class NeighborSampler(object):
                                                   C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
         if step is None:
             self.step += 1
-        return (g, seeds, n, rev, src, nbr, extra, ticket.value, ind)
+        return (g, seeds, n, rev, src, nbr, extra, ticket.value, ind, weights)
 
     def sample_end(self, pending):
         """Wait for the counts of a sample_begin (an event wait: only for that call's kernels) and build the blocks."""
-        g, seeds, n, rev, src, nbr, extra, ticket, ind = pending
+        g, seeds, n, rev, src, nbr, extra, ticket, ind, weights = pending
         L, G = len(rev), self.bucket_by_owner
         n_src = (C.c_int64 * L)()
         n_edges = (C.c_int64 * L)()
         ch = (C.c_int64 * G)() if G > 0 else None
-        if -1 in rev:   # raises when the device refused a full layer (or the fixed layers behind it) for its size
+        if -1 in rev or weights is not None:   # raises when the device refused a full layer (or the fixed layers behind it) for its size
             _capi.check(_lib.coala_sampler_wait_layers(g._h, ticket, n_src, n_edges, ch))
         else:
             _capi.check(_lib.coala_sampler_wait(g._h, ticket, n_src, ch))

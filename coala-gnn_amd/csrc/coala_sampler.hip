@@ -33,6 +33,27 @@
 //   The hash table of a full layer is sized by its device-known item count: the kernel in front of the layer (the previous layer's
 //   relabel_clear, run after this layer's degree_scan, or table_clear for a first layer) clears exactly that much.
 //
+// Weighted fixed layers (DGL's NeighborSampler(fanouts, prob=...); coala_sampler_sample_layers_weighted), fan-out f in 1..32.
+// Destination node v's in-edges sit at CSC positions indptr[v] + j, 0 <= j < deg, with fp32 weights w[indptr[v] + j] (finite,
+// >= 0, CSC order, validated by the caller):
+//   * P = number of edges with w > 0.  P <= f: the row takes exactly those P edges (DGL's rule for replace=False);
+//   * otherwise f distinct positive-weight edges, by weighted sampling without replacement with Efraimidis-Spirakis keys, in fp64:
+//       r_j = splitmix64((sample_key(seed, step, layer, v) ^ kWeightedStream) + j),  u_j = (r_j >> 11) * 2^-53,
+//       E_j = -log1p(-u_j)  (Exp(1)),  key_j = E_j / (double)w_j;
+//     the f smallest (key_j, j) pairs win, a tie going to the lower position.  A weight-0 edge is never a candidate, whatever the
+//     key of a positive edge (a key may be +inf without an edge of weight 0 ever overtaking it).  E_j depends on (seed, step,
+//     layer, v, j) only: not on the batch, the grid or the order in which waves run.  (A 24-bit fp32 uniform would quantise the
+//     smallest exponentials of a 10^6-edge row to ~6 % and bias ties toward low positions: hence 53 bits and fp64.)
+//   * the chosen edges are written in ascending CSC position, valid entries first, then -1: a row with every weight positive and
+//     deg <= f is the uniform path's row, bit for bit.  Source list, first appearance, item limit, refusal and bucketing are those of
+//     a uniform fixed layer; an out-of-range destination id gives an empty row.
+//   * full layers (-1) of a weighted list keep every in-edge and read no weights.
+//   Launches: weighted_select<GS> replaces sample_insert (GS lanes per row stream the row in GS-edge chunks, keep the running
+//   best f spread over the lanes, and pay for a shuffle merge only when a chunk holds a key below the f-th best); a row of more
+//   than kHubDegree in-edges goes on a per-layer device list instead (atomic counter; capacity num_edges / (kHubDegree + 1), sized
+//   at create time -- a row that finds the list full is scanned in place), and weighted_select_hub runs each listed row on a block
+//   of 16 waves, merging their best-f lists in LDS.  Then scan_assign / relabel_clear / bucketing run unchanged.
+//
 // Three launches per layer, nothing else on the stream (round 1: five launches + a memset per layer, a D2H copy and a stream
 // synchronisation per call):
 //   sample_insert   draw + hash insert;
@@ -191,6 +212,177 @@ __global__ __launch_bounds__(kBlock) void sample_insert_kernel(Graph g, const in
         if (active && gl < fanout) { k = nb; p = n_dst + d * fanout + gl; }
         else if (active && gl == fanout) { k = v; p = d; }
         if (p >= 0) hash_insert(tb, mask, k, p, slot_of_item);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- weighted layers
+constexpr uint64_t kWeightedStream = 0x6A09E667F3BCC909ull; // xor on sample_key: the weighted draws' own stream
+constexpr int64_t kHubDegree = 4096;                          // rows with more in-edges go to weighted_select_hub
+constexpr int kHubBlock = 1024;
+constexpr int kHubWaves = kHubBlock / 64;
+constexpr int kHubGrid = 256;
+constexpr unsigned long long kNoKey = ~0ull; // above every fp64 key (+inf included): a weight-0 edge, or an empty slot
+constexpr int64_t kNoPos = INT64_MAX;
+
+// Bits of key_j (non-negative fp64, so its bits order like its value), or kNoKey for a weight of 0.  The weight's sign and
+// magnitude are read from its bits: a denormal weight counts as positive whatever the float mode.
+__device__ __forceinline__ unsigned long long weighted_key(uint64_t wkey, int64_t j, float wj) {
+    if ((int32_t)__float_as_uint(wj) <= 0) return kNoKey;
+    const uint64_t r = splitmix64(wkey + (uint64_t)j);
+    const double u = (double)(r >> 11) * 0x1.0p-53;
+    return (unsigned long long)__double_as_longlong(-log1p(-u) / (double)wj);
+}
+
+__device__ __forceinline__ bool kp_less(unsigned long long ak, int64_t ap, unsigned long long bk, int64_t bp) {
+    return ak < bk || (ak == bk && ap < bp);
+}
+
+// One compare-exchange of a bitonic network across lanes lane ^ m (inside a GS-lane group): keep the smaller pair or the larger.
+__device__ __forceinline__ void bitonic_step(unsigned long long& k, int64_t& p, int m, bool take_min) {
+    const unsigned long long ok = __shfl_xor(k, m);
+    const int64_t op = __shfl_xor(p, m);
+    if (take_min == kp_less(ok, op, k, p)) {
+        k = ok;
+        p = op;
+    }
+}
+
+template <int GS>
+__device__ __forceinline__ void group_sort(unsigned long long& k, int64_t& p, int gl) { // ascending over the group's lanes
+    for (int s = 2; s <= GS; s <<= 1)
+        for (int m = s >> 1; m > 0; m >>= 1) bitonic_step(k, p, m, ((gl & s) == 0) == ((gl & m) == 0));
+}
+
+// The group's running best list (lane i holds the i-th smallest (key, pos) seen) takes one candidate per lane.  Nothing happens
+// unless some candidate is below the f-th best; otherwise the candidates are sorted, merged against the list reversed (the lower
+// half of a bitonic merge) and the list is re-sorted.  Every lane of the group must call it.
+template <int GS>
+__device__ __forceinline__ void group_offer(unsigned long long& bk, int64_t& bp, unsigned long long ck, int64_t cp, int gl, int gbase,
+                                            uint64_t gmask, int fanout) {
+    const unsigned long long tk = __shfl(bk, gbase + fanout - 1);
+    const int64_t tp = __shfl(bp, gbase + fanout - 1);
+    if (!(__ballot(kp_less(ck, cp, tk, tp)) & gmask)) return;
+    group_sort<GS>(ck, cp, gl);
+    const unsigned long long rk = __shfl(ck, gbase + GS - 1 - gl);
+    const int64_t rp = __shfl(cp, gbase + GS - 1 - gl);
+    if (kp_less(rk, rp, bk, bp)) {
+        bk = rk;
+        bp = rp;
+    }
+    for (int m = GS >> 1; m > 0; m >>= 1) bitonic_step(bk, bp, m, (gl & m) == 0);
+}
+
+// Lanes gl < fanout of the group: the gl-th chosen position in ascending order, or -1.  The winners are the lanes < fanout of
+// the best list that hold a key; they are sorted by position.
+template <int GS>
+__device__ __forceinline__ int64_t group_picks(unsigned long long bk, int64_t bp, int gl, int fanout) {
+    unsigned long long pk = (gl < fanout && bk != kNoKey) ? (unsigned long long)bp : (unsigned long long)kNoPos;
+    int64_t unused = 0;
+    group_sort<GS>(pk, unused, gl);
+    return (gl < fanout && pk != (unsigned long long)kNoPos) ? (int64_t)pk : -1;
+}
+
+// Weighted fixed layer, in place of sample_insert_kernel: GS lanes (16/32/64 >= fanout + 1) per destination node stream its row in
+// GS-edge chunks through group_offer, then lanes < fanout write and insert the chosen neighbours in position order, and lane
+// `fanout` inserts the node itself -- the items and positions of sample_insert_kernel.  A row of more than kHubDegree in-edges is put
+// on the hub list for weighted_select_hub_kernel (its node is still inserted here); when the list is full the group scans it itself.
+template <int GS>
+__global__ __launch_bounds__(kBlock) void weighted_select_kernel(Graph g, const float* __restrict__ w, const int64_t* __restrict__ dst,
+                                                                 const int64_t* __restrict__ n_dst_dev, int64_t n_dst_value, int fanout,
+                                                                 uint64_t seed, uint64_t step, int layer, int64_t* __restrict__ nbr, Table tb,
+                                                                 uint32_t* __restrict__ slot_of_item, int64_t* __restrict__ hubs,
+                                                                 unsigned long long* __restrict__ n_hubs, int64_t hub_cap) {
+    constexpr int GPW = 64 / GS;
+    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
+    const uint32_t mask = table_size(n_dst * (fanout + 1)) - 1;
+    const int lane = threadIdx.x & 63;
+    const int gl = lane % GS;
+    const int gbase = lane - gl;
+    const uint64_t gmask = (GS == 64) ? ~0ull : (((1ull << GS) - 1ull) << gbase);
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    for (int64_t d0 = wave * GPW; d0 < n_dst; d0 += n_waves * GPW) { // wave-uniform; the row loop below is group-uniform
+        const int64_t d = d0 + lane / GS;
+        const bool active = d < n_dst;
+        const int64_t v = active ? dst[d] : -1;
+        const bool okv = active && v >= 0 && v < g.num_nodes;
+        const int64_t start = okv ? g.indptr[v] : 0;
+        const int64_t deg = okv ? g.indptr[v + 1] - start : 0;
+        unsigned long long hs = kNoKey;
+        if (gl == 0 && deg > kHubDegree) {
+            hs = atomicAdd(n_hubs, 1ull);
+            if (hs < (unsigned long long)hub_cap) hubs[hs] = d;
+        }
+        hs = __shfl(hs, gbase);
+        if (hs >= (unsigned long long)hub_cap) { // not a listed hub: this group selects the row
+            const uint64_t wkey = sample_key(seed, step, layer, (uint64_t)v) ^ kWeightedStream;
+            unsigned long long bk = kNoKey;
+            int64_t bp = kNoPos;
+            for (int64_t c0 = 0; c0 < deg; c0 += GS) {
+                const int64_t j = c0 + gl;
+                const unsigned long long ck = j < deg ? weighted_key(wkey, j, w[start + j]) : kNoKey;
+                group_offer<GS>(bk, bp, ck, ck == kNoKey ? kNoPos : j, gl, gbase, gmask, fanout);
+            }
+            const int64_t pick = group_picks<GS>(bk, bp, gl, fanout);
+            const int64_t nb = pick >= 0 ? g.indices[start + pick] : kEmpty;
+            if (active && gl < fanout) {
+                nbr[d * fanout + gl] = nb;
+                hash_insert(tb, mask, nb, n_dst + d * fanout + gl, slot_of_item);
+            }
+        }
+        if (active && gl == fanout) hash_insert(tb, mask, v, d, slot_of_item);
+    }
+}
+
+// The rows weighted_select_kernel listed: one block of kHubWaves waves per row (grid-stride over the list, whose length is read
+// here).  Wave q streams chunks q, q + kHubWaves, ... of the row through its own best list; the waves' best f go to LDS, wave 0
+// merges them, sorts the winners by position, writes the row and inserts it.  An empty list ends every block at once.
+__global__ __launch_bounds__(kHubBlock) void weighted_select_hub_kernel(Graph g, const float* __restrict__ w, const int64_t* __restrict__ dst,
+                                                                        const int64_t* __restrict__ n_dst_dev, int64_t n_dst_value, int fanout,
+                                                                        uint64_t seed, uint64_t step, int layer, int64_t* __restrict__ nbr,
+                                                                        Table tb, uint32_t* __restrict__ slot_of_item,
+                                                                        const int64_t* __restrict__ hubs,
+                                                                        const unsigned long long* __restrict__ n_hubs, int64_t hub_cap) {
+    __shared__ unsigned long long s_k[kHubWaves * 32];
+    __shared__ int64_t s_p[kHubWaves * 32];
+    const unsigned long long cnt = min(*n_hubs, (unsigned long long)hub_cap);
+    if ((unsigned long long)blockIdx.x >= cnt) return;
+    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
+    const uint32_t mask = table_size(n_dst * (fanout + 1)) - 1;
+    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    for (unsigned long long i = blockIdx.x; i < cnt; i += gridDim.x) { // block-uniform
+        const int64_t d = hubs[i];
+        const int64_t v = dst[d]; // listed rows have a valid id and more than kHubDegree in-edges
+        const int64_t start = g.indptr[v];
+        const int64_t deg = g.indptr[v + 1] - start;
+        const uint64_t wkey = sample_key(seed, step, layer, (uint64_t)v) ^ kWeightedStream;
+        unsigned long long bk = kNoKey;
+        int64_t bp = kNoPos;
+        for (int64_t c0 = (int64_t)q * 64; c0 < deg; c0 += kHubWaves * 64) { // wave-uniform
+            const int64_t j = c0 + lane;
+            const unsigned long long ck = j < deg ? weighted_key(wkey, j, w[start + j]) : kNoKey;
+            group_offer<64>(bk, bp, ck, ck == kNoKey ? kNoPos : j, lane, 0, ~0ull, fanout);
+        }
+        __syncthreads(); // wave 0 has read the previous row's lists
+        if (lane < fanout) {
+            s_k[q * 32 + lane] = bk;
+            s_p[q * 32 + lane] = bp;
+        }
+        __syncthreads();
+        if (q == 0) {
+            const int others = (kHubWaves - 1) * fanout; // the lists of waves 1.., fanout entries each
+            for (int e0 = 0; e0 < others; e0 += 64) {
+                const int e = e0 + lane;
+                const int at = e < others ? (1 + e / fanout) * 32 + e % fanout : 0;
+                group_offer<64>(bk, bp, e < others ? s_k[at] : kNoKey, e < others ? s_p[at] : kNoPos, lane, 0, ~0ull, fanout);
+            }
+            const int64_t pick = group_picks<64>(bk, bp, lane, fanout);
+            if (lane < fanout) {
+                const int64_t nb = pick >= 0 ? g.indices[start + pick] : kEmpty;
+                nbr[d * fanout + lane] = nb;
+                hash_insert(tb, mask, nb, n_dst + d * fanout + lane, slot_of_item);
+            }
+        }
     }
 }
 
@@ -866,6 +1058,10 @@ struct coala_sampler {
     unsigned long long* ticket = nullptr;  // tile ticket counter, monotonic across launches
     unsigned long long ticket_total = 0, scan_gen = 0;
     int64_t* counts_dev = nullptr;         // [kCountsWords]: source counts of the call in flight, bucket bases, full-layer words
+    // weighted layers: the rows of more than kHubDegree in-edges of a layer (at most num_edges / (kHubDegree + 1) distinct nodes)
+    int64_t* hubs = nullptr;               // [hub_cap] destination indices, reused layer after layer
+    int64_t hub_cap = 0;
+    unsigned long long* hub_count = nullptr; // [COALA_SAMPLER_MAX_LAYERS] list lengths of the call in flight
     // pinned host ring: per call kSlot words (kPinEdges .. kPinParts), and an event recorded behind the last kernel
     int64_t* counts_pinned = nullptr; // host pointer
     int64_t* counts_pinned_dev = nullptr;
@@ -976,9 +1172,10 @@ int wait_impl(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* 
     return COALA_OK;
 }
 
+// weights: null for uniform fixed layers, else the fp32 edge weights of weighted fixed layers (CSC order)
 int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed, uint64_t step,
                 const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
-                int64_t* ticket_out, void* stream) {
+                int64_t* ticket_out, void* stream, const float* weights) {
     int rc;
     if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, bucketing))) return rc;
     if (!layers) return fail(COALA_EINVAL, "null argument");
@@ -1076,6 +1273,7 @@ int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const
             HIPCHK(hipMemsetAsync(s->tb.keys, 0xFF, (size_t)t0 * sizeof(long long), st));
             HIPCHK(hipMemsetAsync(s->tb.minpos, 0xFF, (size_t)t0 * sizeof(uint32_t), st));
         }
+        if (weights && s->hub_cap > 0) HIPCHK(hipMemsetAsync(s->hub_count, 0, (size_t)n_layers * sizeof(unsigned long long), st));
         auto next_gen = [&]() -> int {
             if ((++s->scan_gen & 0x3FFFFFFFull) == 0) { // 2^30 scans: the generation tag wraps -> clear the status words once
                 HIPCHK(hipMemsetAsync(s->status, 0, kMaxTiles * sizeof(unsigned long long), st));
@@ -1122,7 +1320,22 @@ int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const
                                    s->tb, s->status, s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, src_out, n_src_dev, pin_dev + l);
             } else {
                 const dim3 gs(grid1d(cap_l * (f < 16 ? 16 : f < 32 ? 32 : 64), kBlock, 8192));
-                if (f < 16)
+                if (weights) {
+                    unsigned long long* nh = s->hub_count + l;
+                    if (f < 16)
+                        hipLaunchKernelGGL(weighted_select_kernel<16>, gs, blk, 0, st, s->g, weights, dst, n_dst_dev, n_seeds, f, seed, step, l,
+                                           s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap);
+                    else if (f < 32)
+                        hipLaunchKernelGGL(weighted_select_kernel<32>, gs, blk, 0, st, s->g, weights, dst, n_dst_dev, n_seeds, f, seed, step, l,
+                                           s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap);
+                    else
+                        hipLaunchKernelGGL(weighted_select_kernel<64>, gs, blk, 0, st, s->g, weights, dst, n_dst_dev, n_seeds, f, seed, step, l,
+                                           s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap);
+                    if (s->hub_cap > 0) // no launch on a graph that cannot hold a row of more than kHubDegree in-edges
+                        hipLaunchKernelGGL(weighted_select_hub_kernel, dim3((unsigned)std::min<int64_t>(std::min<int64_t>(kHubGrid, s->hub_cap), std::max<int64_t>(cap_l, 1))),
+                                           dim3(kHubBlock), 0, st, s->g, weights, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb,
+                                           s->slot_of_item, (const int64_t*)s->hubs, (const unsigned long long*)nh, s->hub_cap);
+                } else if (f < 16)
                     hipLaunchKernelGGL(sample_insert_kernel<16>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb, s->slot_of_item);
                 else if (f < 32)
                     hipLaunchKernelGGL(sample_insert_kernel<32>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb, s->slot_of_item);
@@ -1191,12 +1404,16 @@ int coala_sampler_create(int device, const int64_t* indptr, const int64_t* indic
     s->device = device;
     s->g = Graph{indptr, indices, num_nodes};
     s->num_edges = num_edges;
+    s->hub_cap = std::min<int64_t>(num_nodes, num_edges / (kHubDegree + 1));
     bool ok = hipMalloc((void**)&s->status, kMaxTiles * sizeof(unsigned long long)) == hipSuccess &&
               hipMemset(s->status, 0, kMaxTiles * sizeof(unsigned long long)) == hipSuccess &&
               hipMalloc((void**)&s->ticket, sizeof(unsigned long long)) == hipSuccess &&
               hipMemset(s->ticket, 0, sizeof(unsigned long long)) == hipSuccess &&
               hipMalloc((void**)&s->counts_dev, kCountsWords * sizeof(int64_t)) == hipSuccess &&
               hipMemset(s->counts_dev, 0, kCountsWords * sizeof(int64_t)) == hipSuccess &&
+              hipMalloc((void**)&s->hub_count, COALA_SAMPLER_MAX_LAYERS * sizeof(unsigned long long)) == hipSuccess &&
+              hipMemset(s->hub_count, 0, COALA_SAMPLER_MAX_LAYERS * sizeof(unsigned long long)) == hipSuccess &&
+              (s->hub_cap == 0 || hipMalloc((void**)&s->hubs, (size_t)s->hub_cap * sizeof(int64_t)) == hipSuccess) &&
               hipHostMalloc((void**)&s->counts_pinned, kRing * kSlot * sizeof(int64_t), hipHostMallocMapped) == hipSuccess &&
               hipHostGetDevicePointer((void**)&s->counts_pinned_dev, s->counts_pinned, 0) == hipSuccess;
     for (int i = 0; i < kRing && ok; ++i) ok = hipEventCreateWithFlags(&s->done[i], hipEventDisableTiming) == hipSuccess;
@@ -1212,7 +1429,8 @@ int coala_sampler_destroy(coala_sampler_t* s) {
     if (!s) return COALA_OK;
     (void)hipSetDevice(s->device);
     (void)hipDeviceSynchronize();
-    void* ptrs[] = {s->nbr_global, s->tb.keys, s->tb.local_of_slot, s->slot_of_item, s->wave_counts, s->new_of_old, s->status, s->ticket, s->counts_dev};
+    void* ptrs[] = {s->nbr_global, s->tb.keys, s->tb.local_of_slot, s->slot_of_item, s->wave_counts, s->new_of_old, s->status, s->ticket, s->counts_dev,
+                     s->hubs, s->hub_count};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (s->counts_pinned) (void)hipHostFree(s->counts_pinned);
@@ -1298,13 +1516,22 @@ int coala_sampler_sample(coala_sampler_t* s, const int64_t* seeds, int64_t n_see
         layers[l] = coala_sampler_layer_t{src_nodes_out[l], nbr_local_out[l], nullptr, (int64_t)items, cap * f};
         cap = (int64_t)items;
     }
-    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, nullptr, bucketing, ticket_out, stream);
+    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, nullptr, bucketing, ticket_out, stream, nullptr);
 }
 
 int coala_sampler_sample_layers(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed,
                                 uint64_t step, const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host,
                                 const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
-    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream);
+    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream, nullptr);
+}
+
+int coala_sampler_sample_layers_weighted(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                         uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const float* edge_weights,
+                                         int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
+                                         int64_t* ticket_out, void* stream) {
+    if (!edge_weights) return fail(COALA_EINVAL, "null edge_weights");
+    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream,
+                       edge_weights);
 }
 
 } // extern "C"

@@ -34,6 +34,9 @@ def main():
     ap.add_argument("--fan_out", type=str, default="5,5")
     ap.add_argument("--eval_fan_out", type=str, default=None,
                     help="fan-outs of the evaluation loader (default: --fan_out); -1 takes every in-edge, e.g. -1,-1 for full neighbourhoods")
+    ap.add_argument("--edge_weights", type=str, default="none", choices=["none", "random"],
+                    help="random: seeded edge weights in (0, 1] with ~10%% zeros, sampled in proportion by the training sampler (DGL's "
+                         "prob=); evaluation stays uniform")
     ap.add_argument("--batch_size", type=int, default=1024)
     ap.add_argument("--hidden_channels", type=int, default=128)
     ap.add_argument("--num_classes", type=int, default=19)
@@ -101,8 +104,14 @@ def main():
 
     train_nid = train_ids[torch.randperm(n_train, generator=torch.Generator().manual_seed(0))]               # :62-65
     nd = Node_Distributor(comm, train_nid, args.batch_size, *files, parsing_method=args.distribution)      # :68
-    sampler = NeighborSampler(fan_out)                                                                      # :70-72
-    g = sampler.make_graph(indptr, indices, ndata={"labels": labels})
+    edata, prob = {}, None
+    if args.edge_weights == "random":   # in CSC order, aligned with `indices`
+        gw = torch.Generator(device=indices.device).manual_seed(1)
+        w = 1.0 - torch.rand(indices.numel(), generator=gw, device=indices.device)
+        w[torch.rand(indices.numel(), generator=gw, device=indices.device) < 0.1] = 0.0
+        edata, prob = {"w": w}, "w"
+    sampler = NeighborSampler(fan_out, prob=prob)                                                           # :70-72
+    g = sampler.make_graph(indptr, indices, ndata={"labels": labels}, edata=edata)
     train_loader = COALA_GNN_DataLoader(SSD_INFO(1, args.dim * 4, 1024, 0), nd, g, sampler, args.batch_size, args.dim, fan_out,
                                         args.cache_size, device, refresh_counter=args.refresh_counter,
                                         cache_backend=args.cache_backend, sim_buf=feat, shuffle=False, num_rows=args.nodes,
@@ -147,7 +156,7 @@ def main():
 
     # evaluation over the test nodes through a second loader, as the reference does (:156-195)
     test_nd = Node_Distributor(comm, test_ids, args.batch_size, *files, parsing_method=args.distribution)
-    eval_sampler = sampler if eval_fan_out == fan_out else NeighborSampler(eval_fan_out)
+    eval_sampler = sampler if eval_fan_out == fan_out and prob is None else NeighborSampler(eval_fan_out)
     test_loader = COALA_GNN_DataLoader(SSD_INFO(1, args.dim * 4, 1024, 0), test_nd, g, eval_sampler, args.batch_size, args.dim, eval_fan_out,
                                        args.cache_size, device, refresh_counter=args.refresh_counter,
                                        cache_backend=args.cache_backend, sim_buf=feat, shuffle=False, num_rows=args.nodes)

@@ -390,6 +390,16 @@ typedef struct coala_sampler_layer {
 int coala_sampler_sample_layers(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
                                 uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, int64_t* n_src_host,
                                 int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream);
+/* As coala_sampler_sample_layers, with edge-weighted fixed layers (DGL's NeighborSampler(fanouts, prob=...), replace=False).
+ * edge_weights: device fp32[num_edges] in CSC order (aligned with `indices`), finite and >= 0 (the caller validates them), borrowed for
+ * the call.  A fixed layer draws f distinct edges of positive weight with probability proportional to the weight (Efraimidis-Spirakis
+ * keys; the exact rule is in the header of coala_sampler.hip), takes every positive-weight edge when there are at most f, never takes
+ * a weight-0 edge, and lists them in CSC order, -1 padded.  Full layers (-1) keep every in-edge and read no weights.  Outputs,
+ * capacities, refusals and bucketing are those of coala_sampler_sample_layers; counts come back through coala_sampler_wait_layers. */
+int coala_sampler_sample_layers_weighted(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                         uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const float* edge_weights,
+                                         int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
+                                         int64_t* ticket_out, void* stream);
 /* Counts of an earlier call, with the edge counts of its layers; returns the device-side refusal of a full layer, if any. */
 int coala_sampler_wait_layers(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host);
 
