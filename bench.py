@@ -12,7 +12,12 @@ in pinned host memory), GraphSAGE fan-out 5,5, batch 1024, isolated 4 GiB cache.
 
 Prints ONE JSON line (rank 0) with metric/value/... plus "roofline" (probe+gather kernel: HIP events attached to every one of its
 launches in the timed region, on the stream it is launched on -- the kernel's own begin/end timestamps, which is also what
-rocprofv3 reports) and "cpu_baseline" (the C oracle, one host core, bounded sample).
+rocprofv3 reports), "roofline_cold_fill" and, at N>1, "exchange" (both from the same timed region).
+
+A plain run does only what that line needs: set-up, warm-up, the timed steps, --dump-outputs.  --full adds everything that takes
+runs of its own after the timed region: the all-hit leg of the probe+gather kernel ("roofline_allhit"), the box's device-to-device
+blit rate, "cpu_baseline" (the C oracle, one host core, bounded sample, and the CPU gather / sampler sweeps), the end-to-end epoch
+leg, the fan-out 10,10 leg and the colour-affinity leg.
 """
 import argparse
 import collections
@@ -187,6 +192,9 @@ def parse_args():
     ap.add_argument("--backend", type=str, default=None, help="isolated | nccl | nvshmem (default: isolated at N=1, nccl otherwise)")
     ap.add_argument("--mode", type=str, default="minibatch", choices=["minibatch", "allhit", "allmiss"],
                     help="minibatch: sampler-produced ids (the metric). allhit/allmiss: kernel micro-benchmarks on unique uniform ids")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the extra legs (all-hit kernel leg, box blit rate, CPU baselines, epoch, fan-out "
+                         "10,10, colour affinity); the --no-* switches below and their sizes apply to them.  Off: the headline line only")
     ap.add_argument("--cpu-baseline-batches", type=int, default=120)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-allhit", action="store_true", help="skip the extra all-hit leg of the probe+gather kernel")
@@ -782,7 +790,7 @@ def _main_body(args, fanout, world, rank, local_rank, single_dev, dev_index, dev
     # algorithmic bytes per launch (DESIGN.md "Kernels"): every probed row reads its int64 id and one 32x8 B tag set;
     # every hit additionally reads a dim*4 line and writes a dim*4 output row  (B_row = 2*dim*4+8+256)
     launches = max(prof.gather_launches, 1)
-    box_copy = _box_copy_gbs(device) if rank == 0 else None   # how fast THIS box is (boxes differ by up to 10 %): torch's D2D blit, untimed, after the timed region
+    box_copy = _box_copy_gbs(device) if (rank == 0 and args.full) else None   # how fast THIS box is (boxes differ by up to 10 %): torch's D2D blit, untimed, after the timed region
     tag_set_bytes = int(cache.geometry().tag_set_bytes)   # 128: 32-bit tags (every id < 2^32), 256: the reference's 64-bit tags
     alg_bytes = prof.gather_rows * (8 + tag_set_bytes) + prof.gather_hits * (2 * args.dim * 4)
     k_ms = prof.gather_ms / launches
@@ -802,11 +810,11 @@ def _main_body(args, fanout, world, rank, local_rank, single_dev, dev_index, dev
         "cold_fill_avg_us": round(prof.fill_ms / max(prof.fill_launches, 1) * 1e3, 2),
     }
 
-    # ---------------------------------------------------------------- extra leg (N=1): the hit path alone
+    # ---------------------------------------------------------------- extra leg (--full, N=1): the hit path alone
     # BASELINE.md section 4 micro-benchmark: N = max rows per minibatch, unique uniform ids, cache pre-warmed with exactly
     # those ids, so every row is a hit and the probe+gather kernel moves B_row = 2*dim*4 + 8 + 256 bytes per row.
     roofline_allhit = None
-    if world == 1 and args.mode == "minibatch" and not args.no_allhit:
+    if args.full and world == 1 and args.mode == "minibatch" and not args.no_allhit:
         # (a) STEADY STATE: `sets` disjoint id sets, all pre-warmed, fetched in rotation.  One set is max_rows lines + as many output
         #     rows (151 + 151 MB at 36,864 x 4 KiB); by the time a set comes round again the other sets have pushed 4x that through the
         #     256 MiB Infinity Cache, so no launch finds its lines there -- these are HBM reads.  This is `frac`.
@@ -900,7 +908,7 @@ def _main_body(args, fanout, world, rank, local_rank, single_dev, dev_index, dev
                          "note": "rows read zero-copy from pinned host memory; a pinned hipMemcpy H2D reaches 57.5 GB/s on this box"}
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and host_array is not None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and host_array is not None:
         cpu_baseline = run_cpu_baseline(args, host_array, [b[0] for b in batches[args.warmup:]], fanout, graph, seeds_for)
 
     if rank == 0:
@@ -928,7 +936,7 @@ def _main_body(args, fanout, world, rank, local_rank, single_dev, dev_index, dev
                        "cold_tier_register_s": round(getattr(table, "register_s", 0.0), 2) or None,
                        "cold_tier_numa_node": [d.get("cold_tier_node_middle_page") for d in numa_all],
                        "numa": [{k: d.get(k) for k in ("mode", "gpu_numa_node", "bound_node", "cpus", "applied", "why") if d.get(k) is not None} for d in numa_all],
-                       "prewarm_steps": args.prewarm, "rows_scale_factor": rows_scale,
+                       "prewarm_steps": args.prewarm, "rows_scale_factor": rows_scale, "full": bool(args.full),
                        "steps_per_epoch": steps_per_epoch,
                        "epoch_time_s_fetch_only_extrapolated": round(ms_per_step * steps_per_epoch / 1e3, 2)},
             "roofline": roofline,
@@ -941,7 +949,7 @@ def _main_body(args, fanout, world, rank, local_rank, single_dev, dev_index, dev
     else:
         line = None
 
-    # ---------------------------------------------------------------- extra legs: epoch (end to end) and fan-out 10,10
+    # ---------------------------------------------------------------- extra legs (--full): epoch (end to end), fan-out 10,10, colour affinity
     # They run last and never cost the headline number silently: at N>1 a rank-local exception or a stall ends the whole job
     # with a non-zero exit code, after rank 0 has printed the line with an "error" field (RankGuard).
     guard.line = line
@@ -959,7 +967,7 @@ def _main_body(args, fanout, world, rank, local_rank, single_dev, dev_index, dev
         return ok, {"skipped": f"{left:.0f} s of the run's {guard.budget_s:.0f} s time budget were left, this leg wants {need_s:.0f} s (--time-budget)"}
 
     _maybe_stall("extra_legs", rank)
-    fits, skipped = leg_fits("epoch leg", 75.0) if (args.mode == "minibatch" and args.epoch_steps != 0) else (False, None)
+    fits, skipped = leg_fits("epoch leg", 75.0) if (args.full and args.mode == "minibatch" and args.epoch_steps != 0) else (False, None)
     if skipped is not None and not fits and rank == 0:
         line["epoch"] = skipped
     if fits:
@@ -975,7 +983,7 @@ def _main_body(args, fanout, world, rank, local_rank, single_dev, dev_index, dev
     # BASELINE.json configs[2] names fan-out 10,10 for the 8-GPU run: a short fetch-only measurement of that batch shape on the
     # same table / graph / cache size, at EVERY N (so that its per-N curve has an origin at N = 1), next to the weak-scaling
     # `value` above, which keeps the N = 1 fan-out so that the driver's per-N values stay comparable
-    if args.mode == "minibatch" and args.fanout == "5,5" and not args.no_fanout_leg:
+    if args.full and args.mode == "minibatch" and args.fanout == "5,5" and not args.no_fanout_leg:
         fits, skipped = leg_fits("fan-out 10,10 leg", 30.0)
         if fits:
             guard.arm(120.0, "fan-out 10,10 leg")
@@ -986,14 +994,14 @@ def _main_body(args, fanout, world, rank, local_rank, single_dev, dev_index, dev
     # N=1 only: the reference's distribution comparison (examples/Distribution_compare_script.sh:26-34) on one box -- two domains
     # x 1 rank on this GPU, real colours from the native colouring tool, node_color against baseline.  A child process: a failure
     # there is reported in the object and never costs the line.
-    if world >= 2 and world % 2 == 0 and args.mode == "minibatch" and not args.no_color_affinity_leg and args.affinity_nodes > 0:
+    if args.full and world >= 2 and world % 2 == 0 and args.mode == "minibatch" and not args.no_color_affinity_leg and args.affinity_nodes > 0:
         fits, skipped = leg_fits("colour-affinity leg", 70.0)
         if fits:
             guard.arm(120.0, "colour-affinity leg (set-up)")
             skipped = run_color_affinity_domains(args, world, rank, dev_index, device, single_dev, backend, guard)
         if rank == 0:
             line[f"color_affinity_2x{world // 2}"] = skipped
-    if world == 1 and args.mode == "minibatch" and not args.no_color_affinity_leg:
+    if args.full and world == 1 and args.mode == "minibatch" and not args.no_color_affinity_leg:
         fits, skipped = leg_fits("colour-affinity leg", 60.0)
         guard.disarm()     # (a child process with a timeout of its own, inside what is left of the budget)
         line["color_affinity"] = run_color_affinity_leg(timeout_s=max(30.0, min(400.0, guard.remaining() - 15.0))) if fits else skipped

@@ -9,7 +9,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--rows", "300000", "--prewarm", "20", "--steps", "10", "--warmup", "3", "--cache-mb", "256", "--epoch-steps", "12",
+SMALL = ["--rows", "300000", "--prewarm", "20", "--steps", "10", "--warmup", "3", "--cache-mb", "256", "--full", "--epoch-steps", "12",
          "--cpu-baseline-batches", "2", "--allhit-launches", "5", "--no-color-affinity-leg"]
 REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config", "roofline", "cpu_baseline"}
@@ -58,6 +58,20 @@ def test_bench_single_gpu_contract(tmp_path):
     assert e["serial"]["steps"] == 12 and e["prefetch"] is None and e["serial"]["ms_per_step"] > 0   # one loader in the line (--epoch-prefetch adds the other)
     x = d["config_fanout_10_10"]                # the 10,10 batch shape has an N = 1 origin too
     assert x["value"] > 0 and x["steps"] == 60 and x["rows_per_step_per_gpu"] > d["config"]["rows_per_step_per_gpu"]
+
+
+def test_bench_plain_run_is_the_headline_line_only(tmp_path):
+    """Without --full the run stops at what the headline line needs: the timed region's own figures are there, no extra leg has run."""
+    plain = SMALL[:SMALL.index("--full")]
+    dump = tmp_path / "dump"
+    d = _line(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *plain, "--dump-outputs", str(dump)], capture_output=True,
+                             text=True, timeout=900))
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d) and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["steps"] == 10 and d["warmup"] == 3 and d["config"]["full"] is False
+    assert 0 < d["roofline"]["frac"] < 1 and d["roofline"]["box_d2d_blit_gbs"] is None and d["roofline_cold_fill"]["achieved"] > 0
+    assert d["roofline_allhit"] is None and d["cpu_baseline"] is None and d["epoch"] is None
+    assert "config_fanout_10_10" not in d and "color_affinity" not in d
+    assert {f.stem for f in dump.iterdir()} >= {"input_nodes", "seeds", "features"}
 
 
 def test_bench_two_ranks_on_one_gpu_with_epoch_leg():
