@@ -4,27 +4,76 @@ import ctypes as C
 import numpy as np
 
 
-class PinnedTable:
-    """fp32 [rows, dim] table in pinned host memory visible to the GPU (the cold tier), filled on the host."""
+SENTINEL = np.float32(-7.25e33)   # what the padding around a guarded region holds
+GUARD = 67                         # floats of sentinel behind every guarded region
 
-    def __init__(self, P, feat, device=0):
+
+def check_guards(flat, off, n):
+    """flat: 1-D fp32 numpy array; asserts that everything outside flat[off : off + n] still holds SENTINEL, bit for bit."""
+    pad = np.concatenate([flat[:off], flat[off + n:]])
+    bad = np.flatnonzero(pad.view(np.int32) != SENTINEL.view(np.int32))
+    if len(bad):
+        k = int(bad[0])
+        where = f"{off - k} floats before" if k < off else f"{k - off} floats after the end of"
+        raise AssertionError(f"write outside the region: {len(bad)} padding floats changed, the first {where} the region")
+
+
+class Guarded:
+    """fp32 [rows, dim] region at float offset `off` of a torch buffer padded with SENTINEL: `off` floats before it, GUARD after.
+    `fill`: a scalar or an array of the region's shape.  An odd `off` puts the region off 16-byte alignment."""
+
+    def __init__(self, torch, rows, dim, off=0, fill=-2.0, device="cuda"):
+        self.off, self.shape, self.n = off, (rows, dim), rows * dim
+        self.flat = torch.full((off + self.n + GUARD,), float(SENTINEL), dtype=torch.float32, device=device)
+        if np.isscalar(fill):
+            self.flat[off: off + self.n] = float(fill)
+        else:
+            self.flat[off: off + self.n] = torch.from_numpy(np.ascontiguousarray(fill, dtype=np.float32).reshape(-1)).to(device)
+
+    @property
+    def ptr(self):
+        return self.flat.data_ptr() + 4 * self.off
+
+    def region(self):
+        """-> the region as a numpy array, after asserting that the padding around it is unchanged."""
+        h = self.flat.cpu().numpy()
+        check_guards(h, self.off, self.n)
+        return h[self.off: self.off + self.n].reshape(self.shape)
+
+
+class PinnedTable:
+    """fp32 [rows, dim] table in pinned host memory visible to the GPU (the cold tier), filled on the host.
+    offset (a number of floats, 0 included): the table starts that far into its allocation (1: off 16-byte alignment), and the
+    allocation holds SENTINEL before it and GUARD floats of it after it (guards_intact).  offset=None: the table alone."""
+
+    def __init__(self, P, feat, device=0, offset=None):
         from COALA_GNN_Pybind import _capi
         self._capi = _capi
         L = _capi.load()
         hp, dp = C.c_void_p(), C.c_void_p()
-        _capi.check(L.coala_pinned_alloc(feat.nbytes, device, C.byref(hp), C.byref(dp)))
-        self.host_ptr, self.device_ptr = hp.value, dp.value
-        buf = (C.c_float * feat.size).from_address(self.host_ptr)
-        self.array = np.frombuffer(buf, dtype=np.float32).reshape(feat.shape)
+        padded = offset is not None
+        offset = offset or 0
+        total = feat.size + (offset + GUARD if padded else 0)
+        _capi.check(L.coala_pinned_alloc(4 * total, device, C.byref(hp), C.byref(dp)))
+        self.host_ptr, self.device_ptr = hp.value, dp.value + 4 * offset
+        buf = (C.c_float * total).from_address(self.host_ptr)
+        self._flat = np.frombuffer(buf, dtype=np.float32)
+        self._flat[...] = SENTINEL
+        self.offset = offset
+        self.array = self._flat[offset: offset + feat.size].reshape(feat.shape)
         self.array[...] = feat
         self.rows, self.dim = feat.shape
+
+    def guards_intact(self):
+        check_guards(self._flat, self.offset, self.rows * self.dim)
+        return True
 
     def data_ptr(self):  # what COALA_GNN_Manager reads from sim_buf
         return self.device_ptr
 
     def close(self):
         if self.host_ptr:
-            self.array = None
+            self.array = self._flat = None
             self._capi.load().coala_pinned_free(self.host_ptr)
             self.host_ptr = 0
 
