@@ -1,0 +1,121 @@
+"""Autograd wrappers of the native block ops that `Block` (sampler.py) hands to a model: mean aggregation (SAGEConv's "mean") and GAT
+attention aggregation, on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the
+kernels are in coala-gnn_amd/csrc/coala_block_ops.hip (C ABI: coala_block_*)."""
+import torch
+
+from COALA_GNN_Pybind import _capi, current_stream
+
+_lib = _capi.load()
+
+
+class _MeanAggregate(torch.autograd.Function):
+    """out[d] = mean of h_src[nbr[d, j]] over the valid j (coala_block_mean_aggregate): one kernel forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, h_src, nbr):
+        h = h_src.contiguous()
+        n_dst, fanout = nbr.shape
+        out = torch.empty((n_dst, h.shape[1]), dtype=torch.float32, device=h.device)
+        _capi.check(_lib.coala_block_mean_aggregate(h.device.index or 0, nbr.data_ptr(), h.data_ptr(), out.data_ptr(), n_dst, fanout, h.shape[1],
+                                                    current_stream()))
+        ctx.save_for_backward(nbr)
+        ctx.src_shape = h.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        (nbr,) = ctx.saved_tensors
+        g = grad_out.contiguous()
+        grad_src = torch.zeros(ctx.src_shape, dtype=torch.float32, device=g.device)
+        _capi.check(_lib.coala_block_mean_aggregate_backward(g.device.index or 0, nbr.data_ptr(), g.data_ptr(), grad_src.data_ptr(), nbr.shape[0],
+                                                             nbr.shape[1], g.shape[1], current_stream()))
+        return grad_src, None
+
+
+class _MeanAggregateCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_mean_aggregate_csr): row d averages h_src[indices[indptr[d]:indptr[d+1]]]."""
+
+    @staticmethod
+    def forward(ctx, h_src, indptr, indices):
+        h = h_src.contiguous()
+        n_dst = indptr.numel() - 1
+        out = torch.empty((n_dst, h.shape[1]), dtype=torch.float32, device=h.device)
+        _capi.check(_lib.coala_block_mean_aggregate_csr(h.device.index or 0, indptr.data_ptr(), indices.data_ptr(), h.data_ptr(), out.data_ptr(),
+                                                        n_dst, h.shape[1], current_stream()))
+        ctx.save_for_backward(indptr, indices)
+        ctx.src_shape = h.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        indptr, indices = ctx.saved_tensors
+        g = grad_out.contiguous()
+        grad_src = torch.zeros(ctx.src_shape, dtype=torch.float32, device=g.device)
+        _capi.check(_lib.coala_block_mean_aggregate_csr_backward(g.device.index or 0, indptr.data_ptr(), indices.data_ptr(), g.data_ptr(),
+                                                                 grad_src.data_ptr(), indptr.numel() - 1, g.shape[1], current_stream()))
+        return grad_src, None, None
+
+
+def _gat_contig(el, er, feat_src):
+    return el.contiguous(), er.contiguous(), feat_src.contiguous()
+
+
+class _GatAggregate(torch.autograd.Function):
+    """DGL GATConv's attention step on a fixed block (coala_block_gat_aggregate): per head, a softmax of leaky_relu(el[s] + er[d]) over
+    the valid nbr[d, j], then the weighted sum of feat_src[s].  One kernel forward, one backward (gradients for el, er and feat_src)."""
+
+    @staticmethod
+    def forward(ctx, el, er, feat_src, nbr, negative_slope):
+        el, er, f = _gat_contig(el, er, feat_src)
+        n_dst, fanout = nbr.shape
+        H, D = f.shape[1], f.shape[2]
+        out = torch.empty((n_dst, H, D), dtype=torch.float32, device=f.device)
+        lse = torch.empty((n_dst, H), dtype=torch.float32, device=f.device)
+        _capi.check(_lib.coala_block_gat_aggregate(f.device.index or 0, nbr.data_ptr(), el.data_ptr(), er.data_ptr(), f.data_ptr(), out.data_ptr(),
+                                                   lse.data_ptr(), n_dst, fanout, H, D, negative_slope, current_stream()))
+        ctx.save_for_backward(el, er, f, nbr, out, lse)
+        ctx.slope = negative_slope
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        el, er, f, nbr, out, lse = ctx.saved_tensors
+        g = grad_out.contiguous()
+        grad_feat, grad_el, grad_er = torch.zeros_like(f), torch.zeros_like(el), torch.empty_like(er)
+        _capi.check(_lib.coala_block_gat_aggregate_backward(f.device.index or 0, nbr.data_ptr(), el.data_ptr(), er.data_ptr(), f.data_ptr(),
+                                                            out.data_ptr(), lse.data_ptr(), g.data_ptr(), grad_feat.data_ptr(), grad_el.data_ptr(),
+                                                            grad_er.data_ptr(), nbr.shape[0], nbr.shape[1], f.shape[1], f.shape[2], ctx.slope,
+                                                            current_stream()))
+        return grad_el, grad_er, grad_feat, None, None
+
+
+class _GatAggregateCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_gat_aggregate_csr): row d's edges are indices[indptr[d]:indptr[d+1]]."""
+
+    @staticmethod
+    def forward(ctx, el, er, feat_src, indptr, indices, negative_slope):
+        el, er, f = _gat_contig(el, er, feat_src)
+        n_dst = indptr.numel() - 1
+        H, D = f.shape[1], f.shape[2]
+        out = torch.empty((n_dst, H, D), dtype=torch.float32, device=f.device)
+        lse = torch.empty((n_dst, H), dtype=torch.float32, device=f.device)
+        _capi.check(_lib.coala_block_gat_aggregate_csr(f.device.index or 0, indptr.data_ptr(), indices.data_ptr(), el.data_ptr(), er.data_ptr(),
+                                                       f.data_ptr(), out.data_ptr(), lse.data_ptr(), n_dst, H, D, negative_slope, current_stream()))
+        ctx.save_for_backward(el, er, f, indptr, indices, out, lse)
+        ctx.slope = negative_slope
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        el, er, f, indptr, indices, out, lse = ctx.saved_tensors
+        g = grad_out.contiguous()
+        grad_feat, grad_el, grad_er = torch.zeros_like(f), torch.zeros_like(el), torch.empty_like(er)
+        _capi.check(_lib.coala_block_gat_aggregate_csr_backward(f.device.index or 0, indptr.data_ptr(), indices.data_ptr(), el.data_ptr(),
+                                                                er.data_ptr(), f.data_ptr(), out.data_ptr(), lse.data_ptr(), g.data_ptr(),
+                                                                grad_feat.data_ptr(), grad_el.data_ptr(), grad_er.data_ptr(), indptr.numel() - 1,
+                                                                f.shape[1], f.shape[2], ctx.slope, current_stream()))
+        return grad_el, grad_er, grad_feat, None, None, None

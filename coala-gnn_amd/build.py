@@ -5,7 +5,7 @@ import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("coala_cache.hip", "coala_sampler.hip", "coala_host.cpp", "coala_coloring.cpp", "coala_comm.cpp")]
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("coala_cache.hip", "coala_sampler.hip", "coala_block_ops.hip", "coala_host.cpp", "coala_coloring.cpp", "coala_comm.cpp")]
 PYBIND_SRC = os.path.join(_HERE, "csrc", "coala_pybind.cpp")
 HEADERS = [os.path.join(_ROOT, "include", "coala_hip.h"), os.path.join(_HERE, "csrc", "coala_internal.h")]
 LIB_DIR = os.path.join(_HERE, "lib")

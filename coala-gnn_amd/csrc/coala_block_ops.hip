@@ -1,0 +1,459 @@
+// coala_block_ops.hip -- what a model computes on a sampled block (coala_sampler.hip makes the blocks), for gfx950: mean aggregation
+// (DGL's SAGEConv "mean") and GAT attention aggregation (GATConv's message step), forward and backward, on fixed blocks
+// (nbr_local[n_dst, fanout], -1 = no neighbour) and on the CSR blocks of full layers.  Stateless entry points: no handle, every
+// launch on the caller's stream.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <type_traits>
+
+#include "../../include/coala_hip.h"
+#include "coala_internal.h"
+
+#define fail coala_fail_
+#define HIPCHK COALA_HIPCHK
+
+namespace {
+
+// The one dense-side primitive a consumer of these blocks needs (DGL's SAGEConv "mean" reduces to it): out[d] = mean of the rows
+// h_src[nbr[d, j]] over the valid j.  One wave per destination row, 16-B accesses, the neighbour indices read once per wave.
+// Replaces gather -> mask -> sum -> divide in eager torch (four passes over a [n_dst, fanout, dim] intermediate).
+template <int VEC>
+__global__ __launch_bounds__(kBlock) void mean_aggregate_kernel(const int32_t* __restrict__ nbr, const float* __restrict__ h_src,
+                                                                float* __restrict__ out, int64_t n_dst, int fanout, int dim) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int units = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        const int32_t mine = lane < fanout ? nbr[d * fanout + lane] : -1; // fan-out <= 32: one load per wave
+        const int cnt = __builtin_popcountll(__ballot(mine >= 0));
+        const float inv = cnt ? 1.0f / (float)cnt : 0.0f;
+        for (int u0 = 0; u0 < units; u0 += 64) {
+            const int u = u0 + lane;
+            vf acc = vf(0.0f);
+            for (int j = 0; j < fanout; ++j) {
+                const int32_t idx = __shfl(mine, j);
+                if (idx >= 0 && u < units) acc += *reinterpret_cast<const vf*>(h_src + (int64_t)idx * dim + (int64_t)u * VEC);
+            }
+            if (u < units) *reinterpret_cast<vf*>(out + d * dim + (int64_t)u * VEC) = acc * inv;
+        }
+    }
+}
+
+// grad_src[nbr[d, j]] += grad_out[d] / cnt[d]   (grad_src zeroed by the caller; hardware float atomics: summation order varies)
+__global__ __launch_bounds__(kBlock) void mean_aggregate_backward_kernel(const int32_t* __restrict__ nbr, const float* __restrict__ grad_out,
+                                                                         float* __restrict__ grad_src, int64_t n_dst, int fanout, int dim) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        const int32_t mine = lane < fanout ? nbr[d * fanout + lane] : -1;
+        const int cnt = __builtin_popcountll(__ballot(mine >= 0));
+        if (!cnt) continue;
+        const float inv = 1.0f / (float)cnt;
+        for (int c0 = 0; c0 < dim; c0 += 64) { // wave-uniform trip count: the shuffles below read lanes that are past `dim`
+            const int c = c0 + lane;
+            const float g = c < dim ? grad_out[d * dim + c] * inv : 0.0f;
+            for (int j = 0; j < fanout; ++j) {
+                const int32_t idx = __shfl(mine, j);
+                if (idx >= 0 && c < dim) unsafeAtomicAdd(grad_src + (int64_t)idx * dim + c, g);
+            }
+        }
+    }
+}
+
+// The same op on a ragged (CSR) block, the form of a full layer: row d is idx[indptr[d] .. indptr[d+1]).  One wave per row as in
+// the dense kernels; the row's indices are read 64 at a time and broadcast by shuffle, and the sum runs in CSC order, so a row both
+// forms can express gives the dense kernel's bits.  A hub row is aggregated by one wave (splitting it is not done).
+template <int VEC>
+__global__ __launch_bounds__(kBlock) void mean_aggregate_csr_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                    const float* __restrict__ h_src, float* __restrict__ out, int64_t n_dst, int dim) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int units = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        const int64_t beg = indptr[d], end = indptr[d + 1];
+        const float inv = end > beg ? 1.0f / (float)(end - beg) : 0.0f;
+        for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+            const int u = u0 + lane;
+            vf acc = vf(0.0f);
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
+                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && u < units) acc += *reinterpret_cast<const vf*>(h_src + (int64_t)s * dim + (int64_t)u * VEC);
+                }
+            }
+            if (u < units) *reinterpret_cast<vf*>(out + d * dim + (int64_t)u * VEC) = acc * inv;
+        }
+    }
+}
+
+// grad_src[idx[e]] += grad_out[d] / deg(d) for the edges e of row d (grad_src zeroed by the caller; hardware float atomics)
+__global__ __launch_bounds__(kBlock) void mean_aggregate_csr_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                             const float* __restrict__ grad_out, float* __restrict__ grad_src,
+                                                                             int64_t n_dst, int dim) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        const int64_t beg = indptr[d], end = indptr[d + 1];
+        if (end <= beg) continue;
+        const float inv = 1.0f / (float)(end - beg);
+        for (int c0 = 0; c0 < dim; c0 += 64) { // wave-uniform trip count: the shuffles below read lanes that are past `dim`
+            const int c = c0 + lane;
+            const float g = c < dim ? grad_out[d * dim + c] * inv : 0.0f;
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
+                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && c < dim) unsafeAtomicAdd(grad_src + (int64_t)s * dim + c, g);
+                }
+            }
+        }
+    }
+}
+
+// GAT attention on a block (DGL GATConv's message step; its projections fc_src / fc_dst and the attn_l / attn_r products are dense
+// and stay in torch).  For dst d, head h and the valid in-edges j of d (source s_j):
+//   z_j = el[s_j, h] + er[d, h],  e_j = leaky_relu(z_j, slope),  a_j = softmax of e over the row,  out[d, h, :] = sum_j a_j feat[s_j, h, :]
+// One wave per destination row, in both block forms: the row's indices are read 64 at a time (a fixed row of fan-out <= 32 is one
+// chunk) and broadcast by shuffle.  Per chunk a lane per edge computes its edge's score for every head once, into LDS; the feature
+// lanes then sum the rows with those weights, never writing a [n_dst, fanout, H, D] intermediate.  The softmax runs online over the
+// chunks: running max m and sum l per head; the partial sum is rescaled by exp(m_old - m_new) when the max grows, and it waits in
+// `out`, unnormalised, between the chunks of a row of more than 64 edges.  The fixed and the CSR kernels are the same code on the
+// same lanes, so a fixed row whose valid entries come first, in CSC order, gives the bits of its CSR row.
+constexpr int kGatMaxHeads = 16;
+constexpr float kNegInf = -__builtin_inff();
+
+__device__ __forceinline__ void wave_lds_sync() { // LDS written by some lanes of a wave, read by others (rocPRIM's wave_barrier)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+    for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+__device__ __forceinline__ float wave_sum(float v) { // butterfly: every lane ends with the same bits
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// acc[h] += the sum of x over the lanes of head h, for the 64 floats c0 + lane of a [H * dim] row (a head's floats are contiguous):
+// a segmented inclusive scan, then the last lane of each head's segment adds its total.  Every lane must call it.
+__device__ __forceinline__ void head_segment_add(float* acc, float x, int lane, int c0, int dim, int hd) {
+    const int c = c0 + lane;
+    const int h = c < hd ? c / dim : 0;
+    const int start = c < hd ? max(h * dim - c0, 0) : hd - c0; // first lane of this lane's segment in the pass
+    for (int o = 1; o < 64; o <<= 1) {
+        const float y = __shfl_up(x, o);
+        if (lane - o >= start) x += y;
+    }
+    if (c < hd && (lane == 63 || c + 1 == hd || (c + 1) % dim == 0)) acc[h] += x;
+}
+
+// Row d's indices: idx[beg .. end), nbr[d * fanout ..] for the fixed form, indices[indptr[d] .. indptr[d+1]) for the CSR form.
+template <bool CSR>
+__device__ __forceinline__ void gat_row(const int64_t* indptr, int fanout, int64_t d, int64_t* beg, int64_t* end) {
+    *beg = CSR ? indptr[d] : d * fanout;
+    *end = CSR ? indptr[d + 1] : *beg + fanout;
+}
+
+template <int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void gat_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
+                                                               const float* __restrict__ el, const float* __restrict__ er,
+                                                               const float* __restrict__ feat, float* __restrict__ out, float* __restrict__ lse,
+                                                               int64_t n_dst, int heads, int dim, float slope) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];  // exp(e_j - m) of the chunk, [edge][head]
+    __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];  // per head: running max, running sum, the chunk's rescale factor
+    const int lane = threadIdx.x & 63;
+    float* w = w_lds[threadIdx.x >> 6];
+    float* m_run = st_lds[threadIdx.x >> 6];
+    float* l_run = m_run + kGatMaxHeads;
+    float* scl = l_run + kGatMaxHeads;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int hd = heads * dim, units = hd / VEC, upl = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        wave_lds_sync(); // the previous row has read m_run / l_run
+        if (lane < heads) {
+            m_run[lane] = kNegInf;
+            l_run[lane] = 0.0f;
+        }
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+            const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
+            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+            wave_lds_sync(); // the previous chunk has read w and scl; m_run / l_run are set
+            for (int h = 0; h < heads; ++h) {
+                float e = kNegInf;
+                if (mine >= 0) {
+                    const float z = el[(int64_t)mine * heads + h] + er[d * heads + h];
+                    e = z > 0.0f ? z : z * slope;
+                }
+                const float mo = m_run[h];
+                const float mn = fmaxf(mo, wave_max(e));
+                const float p = mine >= 0 ? expf(e - mn) : 0.0f;
+                const float sum = wave_sum(p);
+                const float sc = mo == mn ? 1.0f : (mo == kNegInf ? 0.0f : expf(mo - mn));
+                w[lane * kGatMaxHeads + h] = p;
+                if (lane == 0) {
+                    m_run[h] = mn;
+                    l_run[h] = l_run[h] * sc + sum;
+                    scl[h] = sc;
+                }
+            }
+            wave_lds_sync();
+            const bool first = e0 == beg, last = e0 + 64 >= end;
+            for (int u0 = 0; u0 < units; u0 += 64) {
+                const int u = u0 + lane;
+                const int hu = u < units ? u / upl : 0;
+                float* o = out + d * hd + (int64_t)u * VEC;
+                vf acc = vf(0.0f);
+                if (!first && u < units) acc = *reinterpret_cast<const vf*>(o) * scl[hu];
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && u < units) acc += w[j * kGatMaxHeads + hu] * *reinterpret_cast<const vf*>(feat + (int64_t)s * hd + (int64_t)u * VEC);
+                }
+                if (u < units) {
+                    if (last) acc *= l_run[hu] > 0.0f ? 1.0f / l_run[hu] : 0.0f;
+                    *reinterpret_cast<vf*>(o) = acc;
+                }
+            }
+        }
+        if (beg == end) // no chunk ran: an empty CSR row
+            for (int u = lane; u < units; u += 64) *reinterpret_cast<vf*>(out + d * hd + (int64_t)u * VEC) = vf(0.0f);
+        wave_lds_sync();
+        if (lane < heads) lse[d * heads + lane] = l_run[lane] > 0.0f ? m_run[lane] + logf(l_run[lane]) : kNegInf;
+    }
+}
+
+// Backward, a_j = exp(e_j - lse[d, h]) recomputed from the saved log-sum-exp:
+//   grad_feat[s_j, h, :] += a_j g[d, h, :],  t_j = a_j (<g[d, h, :], feat[s_j, h, :]> - <g[d, h, :], out[d, h, :]>) (z_j > 0 ? 1 : slope),
+//   grad_el[s_j, h] += t_j,  grad_er[d, h] = sum_j t_j.
+// A lane per float of the [H * dim] row, 64 at a time; the per-head dot products are summed by head_segment_add into LDS in a fixed
+// order.  grad_feat and grad_el take hardware float atomics (zeroed by the caller); grad_er is written whole, one tree per chunk.
+template <bool CSR>
+__global__ __launch_bounds__(kBlock) void gat_aggregate_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                        int fanout, const float* __restrict__ el, const float* __restrict__ er,
+                                                                        const float* __restrict__ feat, const float* __restrict__ out,
+                                                                        const float* __restrict__ lse, const float* __restrict__ grad_out,
+                                                                        float* __restrict__ grad_feat, float* __restrict__ grad_el,
+                                                                        float* __restrict__ grad_er, int64_t n_dst, int heads, int dim, float slope) {
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // a_j of the chunk, [edge][head]
+    __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g, feat_j>, [edge][head]
+    __shared__ float hs_lds[kWavesPerBlock][2 * kGatMaxHeads];   // per head: <g, out>, the sum of t_j so far
+    const int lane = threadIdx.x & 63;
+    float* w = w_lds[threadIdx.x >> 6];
+    float* dot = dot_lds[threadIdx.x >> 6];
+    float* gout = hs_lds[threadIdx.x >> 6];
+    float* ter = gout + kGatMaxHeads;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int hd = heads * dim;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        const float* g = grad_out + d * hd;
+        wave_lds_sync(); // the previous row has read gout / ter
+        if (lane < heads) {
+            gout[lane] = 0.0f;
+            ter[lane] = 0.0f;
+        }
+        wave_lds_sync();
+        for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count
+            const int c = c0 + lane;
+            head_segment_add(gout, c < hd ? g[c] * out[d * hd + c] : 0.0f, lane, c0, dim, hd);
+        }
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
+            const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
+            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+            wave_lds_sync(); // the previous chunk has read w and dot
+            for (int h = 0; h < heads; ++h) {
+                float a = 0.0f;
+                if (mine >= 0) {
+                    const float z = el[(int64_t)mine * heads + h] + er[d * heads + h];
+                    a = expf((z > 0.0f ? z : z * slope) - lse[d * heads + h]);
+                }
+                w[lane * kGatMaxHeads + h] = a;
+                dot[lane * kGatMaxHeads + h] = 0.0f;
+            }
+            wave_lds_sync();
+            for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: head_segment_add shuffles across every lane
+                const int c = c0 + lane;
+                const int hc = c < hd ? c / dim : 0;
+                const float gc = c < hd ? g[c] : 0.0f;
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s < 0) continue; // wave-uniform
+                    float x = 0.0f;
+                    if (c < hd) {
+                        x = gc * feat[(int64_t)s * hd + c];
+                        unsafeAtomicAdd(grad_feat + (int64_t)s * hd + c, w[j * kGatMaxHeads + hc] * gc);
+                    }
+                    head_segment_add(dot + j * kGatMaxHeads, x, lane, c0, dim, hd);
+                }
+            }
+            wave_lds_sync();
+            for (int h = 0; h < heads; ++h) {
+                float t = 0.0f;
+                if (mine >= 0) {
+                    const float z = el[(int64_t)mine * heads + h] + er[d * heads + h];
+                    t = w[lane * kGatMaxHeads + h] * (dot[lane * kGatMaxHeads + h] - gout[h]) * (z > 0.0f ? 1.0f : slope);
+                    unsafeAtomicAdd(grad_el + (int64_t)mine * heads + h, t);
+                }
+                const float ts = wave_sum(t);
+                if (lane == 0) ter[h] += ts;
+            }
+        }
+        wave_lds_sync();
+        if (lane < heads) grad_er[d * heads + lane] = ter[lane];
+    }
+}
+
+} // namespace
+
+namespace {
+// 16-B accesses need a row length of whole float4s and both row arrays on a 16-B boundary
+bool vec4_ok(int dim, const void* a, const void* b) {
+    return dim % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
+}
+
+// f(std::integral_constant<int, VEC>): the float4 instantiation of a forward kernel, or its scalar one
+template <typename F>
+void dispatch_vec(bool vec4, F&& f) {
+    if (vec4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 1>{});
+}
+
+int gat_check(int64_t n_dst, int heads, int dim) {
+    if (n_dst < 0 || heads < 1 || heads > kGatMaxHeads || dim < 1 || (int64_t)heads * dim > INT32_MAX)
+        return fail(COALA_EINVAL, "bad block shape (heads 1..%d, dim >= 1, n_dst >= 0)", kGatMaxHeads);
+    return COALA_OK;
+}
+} // namespace
+
+extern "C" {
+
+int coala_block_mean_aggregate(int device, const int32_t* nbr, const float* h_src, float* out, int64_t n_dst, int fanout, int dim, void* stream) {
+    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+    if (n_dst == 0) return COALA_OK;
+    if (!nbr || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
+    dispatch_vec(vec4_ok(dim, h_src, out), [&](auto vec) {
+        hipLaunchKernelGGL(mean_aggregate_kernel<decltype(vec)::value>, grid, blk, 0, (hipStream_t)stream, nbr, h_src, out, n_dst, fanout, dim);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+int coala_block_mean_aggregate_backward(int device, const int32_t* nbr, const float* grad_out, float* grad_src, int64_t n_dst, int fanout,
+                                        int dim, void* stream) {
+    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+    if (n_dst == 0) return COALA_OK;
+    if (!nbr || !grad_out || !grad_src) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(mean_aggregate_backward_kernel, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, nbr, grad_out,
+                       grad_src, n_dst, fanout, dim);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+int coala_block_mean_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int64_t n_dst, int dim,
+                                   void* stream) {
+    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
+    if (n_dst == 0) return COALA_OK;
+    if (!indptr || !indices || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
+    dispatch_vec(vec4_ok(dim, h_src, out), [&](auto vec) {
+        hipLaunchKernelGGL(mean_aggregate_csr_kernel<decltype(vec)::value>, grid, blk, 0, (hipStream_t)stream, indptr, indices, h_src, out, n_dst, dim);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+int coala_block_mean_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* grad_out, float* grad_src,
+                                            int64_t n_dst, int dim, void* stream) {
+    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
+    if (n_dst == 0) return COALA_OK;
+    if (!indptr || !indices || !grad_out || !grad_src) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(mean_aggregate_csr_backward_kernel, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, indptr,
+                       indices, grad_out, grad_src, n_dst, dim);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+int coala_block_gat_aggregate(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, float* out, float* lse,
+                              int64_t n_dst, int fanout, int heads, int dim, float negative_slope, void* stream) {
+    if (fanout < 1 || fanout > 32) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+    if (int rc = gat_check(n_dst, heads, dim)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if (!nbr || !el || !er || !feat || !out || !lse) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
+    dispatch_vec(vec4_ok(dim, feat, out), [&](auto vec) {
+        hipLaunchKernelGGL((gat_aggregate_kernel<decltype(vec)::value, false>), grid, blk, 0, (hipStream_t)stream, nullptr, nbr, fanout, el, er, feat,
+                           out, lse, n_dst, heads, dim, negative_slope);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+int coala_block_gat_aggregate_backward(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, const float* out,
+                                       const float* lse, const float* grad_out, float* grad_feat, float* grad_el, float* grad_er, int64_t n_dst,
+                                       int fanout, int heads, int dim, float negative_slope, void* stream) {
+    if (fanout < 1 || fanout > 32) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+    if (int rc = gat_check(n_dst, heads, dim)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if (!nbr || !el || !er || !feat || !out || !lse || !grad_out || !grad_feat || !grad_el || !grad_er) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(gat_aggregate_backward_kernel<false>, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, nullptr,
+                       nbr, fanout, el, er, feat, out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim, negative_slope);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+int coala_block_gat_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er, const float* feat,
+                                  float* out, float* lse, int64_t n_dst, int heads, int dim, float negative_slope, void* stream) {
+    if (int rc = gat_check(n_dst, heads, dim)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if (!indptr || !indices || !el || !er || !feat || !out || !lse) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
+    dispatch_vec(vec4_ok(dim, feat, out), [&](auto vec) {
+        hipLaunchKernelGGL((gat_aggregate_kernel<decltype(vec)::value, true>), grid, blk, 0, (hipStream_t)stream, indptr, indices, 0, el, er, feat, out,
+                           lse, n_dst, heads, dim, negative_slope);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er,
+                                           const float* feat, const float* out, const float* lse, const float* grad_out, float* grad_feat,
+                                           float* grad_el, float* grad_er, int64_t n_dst, int heads, int dim, float negative_slope, void* stream) {
+    if (int rc = gat_check(n_dst, heads, dim)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if (!indptr || !indices || !el || !er || !feat || !out || !lse || !grad_out || !grad_feat || !grad_el || !grad_er)
+        return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(gat_aggregate_backward_kernel<true>, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, indptr,
+                       indices, 0, el, er, feat, out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim, negative_slope);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+} // extern "C"

@@ -15,6 +15,17 @@ int coala_fail_(int code, const char* fmt, ...) __attribute__((format(printf, 2,
                                __LINE__);                                                                    \
     } while (0)
 
+// Launch geometry of the sampler (coala_sampler.hip) and of the block ops (coala_block_ops.hip).
+constexpr int kBlock = 256; // threads per block
+constexpr int kWavesPerBlock = kBlock / 64;
+
+inline int grid1d(int64_t n, int block, int cap) {
+    int64_t g = (n + block - 1) / block;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (int)g;
+}
+
 // The split-phase serve calls with an event ON a launch instead of behind it (coala_cache.hip; used by the distributed fetch, coala_comm.cpp):
 // begin_ev rides on the probe's launch, end_ev on the last fill launch of the call.  *rode = the event that really rides there: the caller's, or
 // the handle's own profiling event of that launch (a profiling handle keeps the dispatches' event slots: fine to wait on, not to time with), or

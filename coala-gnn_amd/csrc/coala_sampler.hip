@@ -69,9 +69,8 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
 #include <new>
-#include <vector>
+#include <type_traits>
 
 #include "../../include/coala_hip.h"
 #include "coala_internal.h"
@@ -82,8 +81,6 @@
 namespace {
 
 constexpr long long kEmpty = -1;
-constexpr int kBlock = 256;                 // threads per block
-constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kItems = 4;                   // items per thread in the scan phases
 constexpr int kTile = kBlock * kItems;      // items per block tile
 constexpr int kMaxTiles = 8192;             // tiles per layer (8.4 M items): status words of the single-pass scan
@@ -612,6 +609,8 @@ __global__ __launch_bounds__(kBlock) void relabel_clear_kernel(const int64_t* __
 // ---------------------------------------------------------------------------------------------------------- owner bucketing
 // Stable partition of the input nodes by owner = id % n_parts (same ballot / prefix-sum scheme as the cache's route kernels), then
 // the last block is re-indexed through the permutation.
+// (A copy of the cache's owner_of / route_count / route_scan / route_scatter, kept apart on purpose: coala_cache.hip's recorded PMC passes hold
+// only while that file's bytes do.  Merge them with the next change that re-takes those passes.)
 __device__ __forceinline__ uint32_t owner_of(uint64_t id, uint32_t n_parts, int pshift) {
     if (pshift >= 0) return (uint32_t)id & (n_parts - 1);
     if ((id >> 32) == 0) return (uint32_t)id % n_parts;
@@ -717,333 +716,15 @@ __global__ __launch_bounds__(kBlock) void bucket_reindex_kernel(const int64_t* _
         dst_in_src[d] = (int32_t)new_of_old[d]; // the dst nodes are the first n_dst entries of the unbucketed list
 }
 
-// ---------------------------------------------------------------------------------------------------------- block ops
-// The one dense-side primitive a consumer of these blocks needs (DGL's SAGEConv "mean" reduces to it): out[d] = mean of the rows
-// h_src[nbr[d, j]] over the valid j.  One wave per destination row, 16-B accesses, the neighbour indices read once per wave.
-// Replaces gather -> mask -> sum -> divide in eager torch (four passes over a [n_dst, fanout, dim] intermediate).
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void mean_aggregate_kernel(const int32_t* __restrict__ nbr, const float* __restrict__ h_src,
-                                                                float* __restrict__ out, int64_t n_dst, int fanout, int dim) {
-    typedef float vf __attribute__((ext_vector_type(VEC)));
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int units = dim / VEC;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        const int32_t mine = lane < fanout ? nbr[d * fanout + lane] : -1; // fan-out <= 32: one load per wave
-        const int cnt = __builtin_popcountll(__ballot(mine >= 0));
-        const float inv = cnt ? 1.0f / (float)cnt : 0.0f;
-        for (int u0 = 0; u0 < units; u0 += 64) {
-            const int u = u0 + lane;
-            vf acc = vf(0.0f);
-            for (int j = 0; j < fanout; ++j) {
-                const int32_t idx = __shfl(mine, j);
-                if (idx >= 0 && u < units) acc += *reinterpret_cast<const vf*>(h_src + (int64_t)idx * dim + (int64_t)u * VEC);
-            }
-            if (u < units) *reinterpret_cast<vf*>(out + d * dim + (int64_t)u * VEC) = acc * inv;
-        }
-    }
-}
-
-// grad_src[nbr[d, j]] += grad_out[d] / cnt[d]   (grad_src zeroed by the caller; hardware float atomics: summation order varies)
-__global__ __launch_bounds__(kBlock) void mean_aggregate_backward_kernel(const int32_t* __restrict__ nbr, const float* __restrict__ grad_out,
-                                                                         float* __restrict__ grad_src, int64_t n_dst, int fanout, int dim) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        const int32_t mine = lane < fanout ? nbr[d * fanout + lane] : -1;
-        const int cnt = __builtin_popcountll(__ballot(mine >= 0));
-        if (!cnt) continue;
-        const float inv = 1.0f / (float)cnt;
-        for (int c0 = 0; c0 < dim; c0 += 64) { // wave-uniform trip count: the shuffles below read lanes that are past `dim`
-            const int c = c0 + lane;
-            const float g = c < dim ? grad_out[d * dim + c] * inv : 0.0f;
-            for (int j = 0; j < fanout; ++j) {
-                const int32_t idx = __shfl(mine, j);
-                if (idx >= 0 && c < dim) unsafeAtomicAdd(grad_src + (int64_t)idx * dim + c, g);
-            }
-        }
-    }
-}
-
-// The same op on a ragged (CSR) block, the form of a full layer: row d is idx[indptr[d] .. indptr[d+1]).  One wave per row as in
-// the dense kernels; the row's indices are read 64 at a time and broadcast by shuffle, and the sum runs in CSC order, so a row both
-// forms can express gives the dense kernel's bits.  A hub row is aggregated by one wave (splitting it is not done).
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void mean_aggregate_csr_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
-                                                                    const float* __restrict__ h_src, float* __restrict__ out, int64_t n_dst, int dim) {
-    typedef float vf __attribute__((ext_vector_type(VEC)));
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int units = dim / VEC;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        const int64_t beg = indptr[d], end = indptr[d + 1];
-        const float inv = end > beg ? 1.0f / (float)(end - beg) : 0.0f;
-        for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
-            const int u = u0 + lane;
-            vf acc = vf(0.0f);
-            for (int64_t e0 = beg; e0 < end; e0 += 64) {
-                const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
-                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
-                for (int j = 0; j < n; ++j) {
-                    const int32_t s = __shfl(mine, j);
-                    if (s >= 0 && u < units) acc += *reinterpret_cast<const vf*>(h_src + (int64_t)s * dim + (int64_t)u * VEC);
-                }
-            }
-            if (u < units) *reinterpret_cast<vf*>(out + d * dim + (int64_t)u * VEC) = acc * inv;
-        }
-    }
-}
-
-// grad_src[idx[e]] += grad_out[d] / deg(d) for the edges e of row d (grad_src zeroed by the caller; hardware float atomics)
-__global__ __launch_bounds__(kBlock) void mean_aggregate_csr_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
-                                                                             const float* __restrict__ grad_out, float* __restrict__ grad_src,
-                                                                             int64_t n_dst, int dim) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        const int64_t beg = indptr[d], end = indptr[d + 1];
-        if (end <= beg) continue;
-        const float inv = 1.0f / (float)(end - beg);
-        for (int c0 = 0; c0 < dim; c0 += 64) { // wave-uniform trip count: the shuffles below read lanes that are past `dim`
-            const int c = c0 + lane;
-            const float g = c < dim ? grad_out[d * dim + c] * inv : 0.0f;
-            for (int64_t e0 = beg; e0 < end; e0 += 64) {
-                const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
-                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
-                for (int j = 0; j < n; ++j) {
-                    const int32_t s = __shfl(mine, j);
-                    if (s >= 0 && c < dim) unsafeAtomicAdd(grad_src + (int64_t)s * dim + c, g);
-                }
-            }
-        }
-    }
-}
-
-// GAT attention on a block (DGL GATConv's message step; its projections fc_src / fc_dst and the attn_l / attn_r products are dense
-// and stay in torch).  For dst d, head h and the valid in-edges j of d (source s_j):
-//   z_j = el[s_j, h] + er[d, h],  e_j = leaky_relu(z_j, slope),  a_j = softmax of e over the row,  out[d, h, :] = sum_j a_j feat[s_j, h, :]
-// One wave per destination row, in both block forms: the row's indices are read 64 at a time (a fixed row of fan-out <= 32 is one
-// chunk) and broadcast by shuffle.  Per chunk a lane per edge computes its edge's score for every head once, into LDS; the feature
-// lanes then sum the rows with those weights, never writing a [n_dst, fanout, H, D] intermediate.  The softmax runs online over the
-// chunks: running max m and sum l per head; the partial sum is rescaled by exp(m_old - m_new) when the max grows, and it waits in
-// `out`, unnormalised, between the chunks of a row of more than 64 edges.  The fixed and the CSR kernels are the same code on the
-// same lanes, so a fixed row whose valid entries come first, in CSC order, gives the bits of its CSR row.
-constexpr int kGatMaxHeads = 16;
-constexpr float kNegInf = -__builtin_inff();
-
-__device__ __forceinline__ void wave_lds_sync() { // LDS written by some lanes of a wave, read by others (rocPRIM's wave_barrier)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v) { // butterfly: every lane ends with the same bits
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// acc[h] += the sum of x over the lanes of head h, for the 64 floats c0 + lane of a [H * dim] row (a head's floats are contiguous):
-// a segmented inclusive scan, then the last lane of each head's segment adds its total.  Every lane must call it.
-__device__ __forceinline__ void head_segment_add(float* acc, float x, int lane, int c0, int dim, int hd) {
-    const int c = c0 + lane;
-    const int h = c < hd ? c / dim : 0;
-    const int start = c < hd ? max(h * dim - c0, 0) : hd - c0; // first lane of this lane's segment in the pass
-    for (int o = 1; o < 64; o <<= 1) {
-        const float y = __shfl_up(x, o);
-        if (lane - o >= start) x += y;
-    }
-    if (c < hd && (lane == 63 || c + 1 == hd || (c + 1) % dim == 0)) acc[h] += x;
-}
-
-// Row d's indices: idx[beg .. end), nbr[d * fanout ..] for the fixed form, indices[indptr[d] .. indptr[d+1]) for the CSR form.
-template <bool CSR>
-__device__ __forceinline__ void gat_row(const int64_t* indptr, int fanout, int64_t d, int64_t* beg, int64_t* end) {
-    *beg = CSR ? indptr[d] : d * fanout;
-    *end = CSR ? indptr[d + 1] : *beg + fanout;
-}
-
-template <int VEC, bool CSR>
-__global__ __launch_bounds__(kBlock) void gat_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
-                                                               const float* __restrict__ el, const float* __restrict__ er,
-                                                               const float* __restrict__ feat, float* __restrict__ out, float* __restrict__ lse,
-                                                               int64_t n_dst, int heads, int dim, float slope) {
-    typedef float vf __attribute__((ext_vector_type(VEC)));
-    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];  // exp(e_j - m) of the chunk, [edge][head]
-    __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];  // per head: running max, running sum, the chunk's rescale factor
-    const int lane = threadIdx.x & 63;
-    float* w = w_lds[threadIdx.x >> 6];
-    float* m_run = st_lds[threadIdx.x >> 6];
-    float* l_run = m_run + kGatMaxHeads;
-    float* scl = l_run + kGatMaxHeads;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int hd = heads * dim, units = hd / VEC, upl = dim / VEC;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        int64_t beg, end;
-        gat_row<CSR>(indptr, fanout, d, &beg, &end);
-        wave_lds_sync(); // the previous row has read m_run / l_run
-        if (lane < heads) {
-            m_run[lane] = kNegInf;
-            l_run[lane] = 0.0f;
-        }
-        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
-            const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
-            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
-            wave_lds_sync(); // the previous chunk has read w and scl; m_run / l_run are set
-            for (int h = 0; h < heads; ++h) {
-                float e = kNegInf;
-                if (mine >= 0) {
-                    const float z = el[(int64_t)mine * heads + h] + er[d * heads + h];
-                    e = z > 0.0f ? z : z * slope;
-                }
-                const float mo = m_run[h];
-                const float mn = fmaxf(mo, wave_max(e));
-                const float p = mine >= 0 ? expf(e - mn) : 0.0f;
-                const float sum = wave_sum(p);
-                const float sc = mo == mn ? 1.0f : (mo == kNegInf ? 0.0f : expf(mo - mn));
-                w[lane * kGatMaxHeads + h] = p;
-                if (lane == 0) {
-                    m_run[h] = mn;
-                    l_run[h] = l_run[h] * sc + sum;
-                    scl[h] = sc;
-                }
-            }
-            wave_lds_sync();
-            const bool first = e0 == beg, last = e0 + 64 >= end;
-            for (int u0 = 0; u0 < units; u0 += 64) {
-                const int u = u0 + lane;
-                const int hu = u < units ? u / upl : 0;
-                float* o = out + d * hd + (int64_t)u * VEC;
-                vf acc = vf(0.0f);
-                if (!first && u < units) acc = *reinterpret_cast<const vf*>(o) * scl[hu];
-                for (int j = 0; j < n; ++j) {
-                    const int32_t s = __shfl(mine, j);
-                    if (s >= 0 && u < units) acc += w[j * kGatMaxHeads + hu] * *reinterpret_cast<const vf*>(feat + (int64_t)s * hd + (int64_t)u * VEC);
-                }
-                if (u < units) {
-                    if (last) acc *= l_run[hu] > 0.0f ? 1.0f / l_run[hu] : 0.0f;
-                    *reinterpret_cast<vf*>(o) = acc;
-                }
-            }
-        }
-        if (beg == end) // no chunk ran: an empty CSR row
-            for (int u = lane; u < units; u += 64) *reinterpret_cast<vf*>(out + d * hd + (int64_t)u * VEC) = vf(0.0f);
-        wave_lds_sync();
-        if (lane < heads) lse[d * heads + lane] = l_run[lane] > 0.0f ? m_run[lane] + logf(l_run[lane]) : kNegInf;
-    }
-}
-
-// Backward, a_j = exp(e_j - lse[d, h]) recomputed from the saved log-sum-exp:
-//   grad_feat[s_j, h, :] += a_j g[d, h, :],  t_j = a_j (<g[d, h, :], feat[s_j, h, :]> - <g[d, h, :], out[d, h, :]>) (z_j > 0 ? 1 : slope),
-//   grad_el[s_j, h] += t_j,  grad_er[d, h] = sum_j t_j.
-// A lane per float of the [H * dim] row, 64 at a time; the per-head dot products are summed by head_segment_add into LDS in a fixed
-// order.  grad_feat and grad_el take hardware float atomics (zeroed by the caller); grad_er is written whole, one tree per chunk.
-template <bool CSR>
-__global__ __launch_bounds__(kBlock) void gat_aggregate_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
-                                                                        int fanout, const float* __restrict__ el, const float* __restrict__ er,
-                                                                        const float* __restrict__ feat, const float* __restrict__ out,
-                                                                        const float* __restrict__ lse, const float* __restrict__ grad_out,
-                                                                        float* __restrict__ grad_feat, float* __restrict__ grad_el,
-                                                                        float* __restrict__ grad_er, int64_t n_dst, int heads, int dim, float slope) {
-    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // a_j of the chunk, [edge][head]
-    __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g, feat_j>, [edge][head]
-    __shared__ float hs_lds[kWavesPerBlock][2 * kGatMaxHeads];   // per head: <g, out>, the sum of t_j so far
-    const int lane = threadIdx.x & 63;
-    float* w = w_lds[threadIdx.x >> 6];
-    float* dot = dot_lds[threadIdx.x >> 6];
-    float* gout = hs_lds[threadIdx.x >> 6];
-    float* ter = gout + kGatMaxHeads;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int hd = heads * dim;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        int64_t beg, end;
-        gat_row<CSR>(indptr, fanout, d, &beg, &end);
-        const float* g = grad_out + d * hd;
-        wave_lds_sync(); // the previous row has read gout / ter
-        if (lane < heads) {
-            gout[lane] = 0.0f;
-            ter[lane] = 0.0f;
-        }
-        wave_lds_sync();
-        for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count
-            const int c = c0 + lane;
-            head_segment_add(gout, c < hd ? g[c] * out[d * hd + c] : 0.0f, lane, c0, dim, hd);
-        }
-        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
-            const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
-            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
-            wave_lds_sync(); // the previous chunk has read w and dot
-            for (int h = 0; h < heads; ++h) {
-                float a = 0.0f;
-                if (mine >= 0) {
-                    const float z = el[(int64_t)mine * heads + h] + er[d * heads + h];
-                    a = expf((z > 0.0f ? z : z * slope) - lse[d * heads + h]);
-                }
-                w[lane * kGatMaxHeads + h] = a;
-                dot[lane * kGatMaxHeads + h] = 0.0f;
-            }
-            wave_lds_sync();
-            for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: head_segment_add shuffles across every lane
-                const int c = c0 + lane;
-                const int hc = c < hd ? c / dim : 0;
-                const float gc = c < hd ? g[c] : 0.0f;
-                for (int j = 0; j < n; ++j) {
-                    const int32_t s = __shfl(mine, j);
-                    if (s < 0) continue; // wave-uniform
-                    float x = 0.0f;
-                    if (c < hd) {
-                        x = gc * feat[(int64_t)s * hd + c];
-                        unsafeAtomicAdd(grad_feat + (int64_t)s * hd + c, w[j * kGatMaxHeads + hc] * gc);
-                    }
-                    head_segment_add(dot + j * kGatMaxHeads, x, lane, c0, dim, hd);
-                }
-            }
-            wave_lds_sync();
-            for (int h = 0; h < heads; ++h) {
-                float t = 0.0f;
-                if (mine >= 0) {
-                    const float z = el[(int64_t)mine * heads + h] + er[d * heads + h];
-                    t = w[lane * kGatMaxHeads + h] * (dot[lane * kGatMaxHeads + h] - gout[h]) * (z > 0.0f ? 1.0f : slope);
-                    unsafeAtomicAdd(grad_el + (int64_t)mine * heads + h, t);
-                }
-                const float ts = wave_sum(t);
-                if (lane == 0) ter[h] += ts;
-            }
-        }
-        wave_lds_sync();
-        if (lane < heads) grad_er[d * heads + lane] = ter[lane];
-    }
-}
-
-int grid1d(int64_t n, int block, int cap) {
-    int64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
-
-} // namespace
-
-namespace {
-struct RingInfo { // what coala_sampler_wait_layers needs of a call to read its counts and explain a refusal
-    int n_layers = 0, n_parts = 0;
-    int64_t n_seeds = 0;
-    int32_t fanouts[COALA_SAMPLER_MAX_LAYERS] = {};
-    int64_t src_cap[COALA_SAMPLER_MAX_LAYERS] = {}, edge_cap[COALA_SAMPLER_MAX_LAYERS] = {};
-};
 } // namespace
 
 struct coala_sampler {
+    struct RingInfo { // what coala_sampler_wait_layers needs of a call to read its counts and explain a refusal
+        int n_layers = 0, n_parts = 0;
+        int64_t n_seeds = 0;
+        int32_t fanouts[COALA_SAMPLER_MAX_LAYERS] = {};
+        int64_t src_cap[COALA_SAMPLER_MAX_LAYERS] = {}, edge_cap[COALA_SAMPLER_MAX_LAYERS] = {};
+    };
     int device = 0;
     Graph g{};
     int64_t num_edges = 0;
@@ -1072,6 +753,7 @@ struct coala_sampler {
 };
 
 namespace {
+using RingInfo = coala_sampler::RingInfo;
 constexpr int kSlot = kPinParts + kMaxParts; // int64 words per ring slot
 
 int grow(void** p, uint64_t* cap, uint64_t need, size_t elem, hipStream_t st) {
@@ -1094,13 +776,21 @@ int ilog2_exact(uint64_t v) {
 }
 
 int check_call(const coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
-               const coala_sampler_bucketing_t* bucketing) {
+               const coala_sampler_layer_t* layers, const coala_sampler_bucketing_t* bucketing) {
     if (!s || (!seeds && n_seeds > 0) || !fanouts) return fail(COALA_EINVAL, "null argument");
     if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
     if (n_seeds < 0 || n_seeds > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad n_seeds");
     const int n_parts = bucketing ? bucketing->n_parts : 0;
     if (n_parts < 0 || n_parts > kMaxParts) return fail(COALA_EINVAL, "bucketing: n_parts must be 0..%d", kMaxParts);
     if (n_parts > 0 && (!bucketing->bucketed_nodes || !bucketing->counts || !bucketing->dst_in_src)) return fail(COALA_EINVAL, "bucketing: null buffer");
+    if (!layers) return fail(COALA_EINVAL, "null argument");
+    for (int l = 0; l < n_layers; ++l) {
+        const int f = fanouts[l];
+        if (f != kFull && (f < 1 || f > 32)) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (or -1: every in-edge)", f);
+        const coala_sampler_layer_t& y = layers[l];
+        if (!y.src_nodes || !y.nbr_local || (f == kFull && !y.indptr_local)) return fail(COALA_EINVAL, "layer %d: null buffer", l);
+        if (y.src_cap < 0 || y.edge_cap < 0) return fail(COALA_EINVAL, "layer %d: negative capacity", l);
+    }
     return COALA_OK;
 }
 
@@ -1172,219 +862,258 @@ int wait_impl(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* 
     return COALA_OK;
 }
 
-// weights: null for uniform fixed layers, else the fp32 edge weights of weighted fixed layers (CSC order)
-int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed, uint64_t step,
-                const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
-                int64_t* ticket_out, void* stream, const float* weights) {
-    int rc;
-    if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, bucketing))) return rc;
-    if (!layers) return fail(COALA_EINVAL, "null argument");
-    for (int l = 0; l < n_layers; ++l) {
-        const int f = fanouts[l];
-        if (f != kFull && (f < 1 || f > 32)) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (or -1: every in-edge)", f);
-        const coala_sampler_layer_t& y = layers[l];
-        if (!y.src_nodes || !y.nbr_local || (f == kFull && !y.indptr_local)) return fail(COALA_EINVAL, "layer %d: null buffer", l);
-        if (y.src_cap < 0 || y.edge_cap < 0) return fail(COALA_EINVAL, "layer %d: negative capacity", l);
-    }
-    const int n_parts = bucketing ? bucketing->n_parts : 0;
-    hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(s->device));
-    // the handle's scratch (hash table, scan state) is ordered by the stream of its calls: a caller that moves to another stream
-    // first waits there for the previous call's last kernel
-    if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
-    s->last_stream = st;
-    // capacities: layer l has at most dst_cap[l] dst nodes, items_cap[l] items (dst nodes + neighbour slots), nbr_cap[l] neighbour
-    // entries.  Up to the first full layer they are exact host bounds (cap_l * (f + 1)) and checked here; a full layer and the fixed
-    // layers behind it are checked on the device against the caller's capacities and the item limit.
-    RingInfo info;
-    info.n_layers = n_layers;
-    info.n_parts = n_parts;
-    info.n_seeds = n_seeds;
+// A template parameter chosen at run time: f gets the value as a std::integral_constant, so each templated launch is written once
+// (the idiom of dispatch_geo in coala_cache.hip).  GS: lanes per destination row of sample_insert / weighted_select.
+template <typename F>
+void dispatch_group(int fanout, F&& f) {
+    if (fanout < 16) f(std::integral_constant<int, 16>{});
+    else if (fanout < 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
+template <typename F>
+void dispatch_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// What the launches of a call are made from: its arguments, and the capacities the host derives from them (plan_call).
+struct Plan {
+    const int64_t* seeds;
+    uint64_t seed, step;
+    const coala_sampler_layer_t* layers;
+    const coala_sampler_bucketing_t* bucketing;
+    const float* weights; // null for uniform fixed layers, else the fp32 edge weights of weighted fixed layers (CSC order)
+    hipStream_t st;
+    RingInfo info;        // n_seeds, the fan-outs, n_parts and the caller's capacities
+    // layer l has at most dst_cap[l] dst nodes, items_cap[l] items (dst nodes + neighbour slots), nbr_cap[l] neighbour entries
     int64_t dst_cap[COALA_SAMPLER_MAX_LAYERS], items_cap[COALA_SAMPLER_MAX_LAYERS], nbr_cap[COALA_SAMPLER_MAX_LAYERS];
+    uint64_t max_items, max_nbr;
+    int64_t* pin_dev;     // the call's ring slot, as the device sees it
+    uint64_t items0;      // what the last kernel leaves clean for the next call (launch_call)
+};
+
+// Capacities.  Up to the first full layer they are exact host bounds (cap_l * (f + 1)) and checked here; a full layer and the fixed
+// layers behind it are checked on the device against the caller's capacities and the item limit.
+int plan_call(Plan& p, int64_t n_seeds, const int32_t* fanouts, int n_layers, int n_parts) {
+    p.info.n_layers = n_layers;
+    p.info.n_parts = n_parts;
+    p.info.n_seeds = n_seeds;
+    p.max_items = p.max_nbr = 0;
     int64_t cap = n_seeds;
     bool host_bound = true;
-    uint64_t max_items = 0, max_nbr = 0;
     for (int l = 0; l < n_layers; ++l) {
         const int f = fanouts[l];
-        const coala_sampler_layer_t& y = layers[l];
-        info.fanouts[l] = f;
-        info.src_cap[l] = y.src_cap;
-        info.edge_cap[l] = y.edge_cap;
-        dst_cap[l] = cap;
+        const coala_sampler_layer_t& y = p.layers[l];
+        p.info.fanouts[l] = f;
+        p.info.src_cap[l] = y.src_cap;
+        p.info.edge_cap[l] = y.edge_cap;
+        p.dst_cap[l] = cap;
         if (f == kFull) {
             host_bound = false;
-            items_cap[l] = std::min<int64_t>(kItemLimit, y.src_cap);
-            nbr_cap[l] = std::min<int64_t>(kItemLimit, y.edge_cap);
+            p.items_cap[l] = std::min<int64_t>(kItemLimit, y.src_cap);
+            p.nbr_cap[l] = std::min<int64_t>(kItemLimit, y.edge_cap);
         } else if (host_bound) {
             const uint64_t items = (uint64_t)cap * (uint64_t)(f + 1);
             if (items > (uint64_t)kItemLimit) return fail(COALA_EINVAL, "layer %d would hold %llu items (limit %d)", l, (unsigned long long)items, kMaxTiles * kTile);
             if ((uint64_t)y.src_cap < items || (uint64_t)y.edge_cap < (uint64_t)cap * f)
                 return fail(COALA_EINVAL, "layer %d: src_cap %lld / edge_cap %lld below the %llu / %llu its fan-out of %d needs", l, (long long)y.src_cap,
                             (long long)y.edge_cap, (unsigned long long)items, (unsigned long long)cap * f, f);
-            items_cap[l] = (int64_t)items;
-            nbr_cap[l] = cap * f;
+            p.items_cap[l] = (int64_t)items;
+            p.nbr_cap[l] = cap * f;
         } else {
-            items_cap[l] = std::min(std::min<int64_t>(cap * (f + 1), kItemLimit), y.src_cap);
-            nbr_cap[l] = std::min(std::min<int64_t>(cap * f, kItemLimit), y.edge_cap);
+            p.items_cap[l] = std::min(std::min<int64_t>(cap * (f + 1), kItemLimit), y.src_cap);
+            p.nbr_cap[l] = std::min(std::min<int64_t>(cap * f, kItemLimit), y.edge_cap);
         }
-        if ((uint64_t)items_cap[l] > max_items) max_items = (uint64_t)items_cap[l];
-        if ((uint64_t)nbr_cap[l] > max_nbr) max_nbr = (uint64_t)nbr_cap[l];
-        cap = items_cap[l];
+        if ((uint64_t)p.items_cap[l] > p.max_items) p.max_items = (uint64_t)p.items_cap[l];
+        if ((uint64_t)p.nbr_cap[l] > p.max_nbr) p.max_nbr = (uint64_t)p.nbr_cap[l];
+        cap = p.items_cap[l];
     }
-    const uint64_t table = table_size((int64_t)max_items);
-    const uint64_t wave_tiles = ((uint64_t)cap + kRouteTile - 1) / kRouteTile;
-    if ((rc = grow((void**)&s->nbr_global, &s->nbr_cap, max_nbr ? max_nbr : 1, sizeof(int64_t), st))) return rc;
-    if ((rc = grow((void**)&s->slot_of_item, &s->item_cap, max_items ? max_items : 1, sizeof(uint32_t), st))) return rc;
+    return COALA_OK;
+}
+
+int grow_workspace(coala_sampler_t* s, const Plan& p) {
+    int rc;
+    const int n_parts = p.info.n_parts;
+    const uint64_t cap = (uint64_t)p.items_cap[p.info.n_layers - 1]; // source nodes of the last layer
+    const uint64_t table = table_size((int64_t)p.max_items);
+    const uint64_t wave_tiles = (cap + kRouteTile - 1) / kRouteTile;
+    if ((rc = grow((void**)&s->nbr_global, &s->nbr_cap, p.max_nbr ? p.max_nbr : 1, sizeof(int64_t), p.st))) return rc;
+    if ((rc = grow((void**)&s->slot_of_item, &s->item_cap, p.max_items ? p.max_items : 1, sizeof(uint32_t), p.st))) return rc;
     if (n_parts > 0) {
-        if ((rc = grow((void**)&s->wave_counts, &s->wc_cap, (wave_tiles + 1) * (uint64_t)n_parts, sizeof(uint32_t), st))) return rc;
-        if ((rc = grow((void**)&s->new_of_old, &s->noo_cap, (uint64_t)cap ? (uint64_t)cap : 1, sizeof(uint32_t), st))) return rc;
+        if ((rc = grow((void**)&s->wave_counts, &s->wc_cap, (wave_tiles + 1) * (uint64_t)n_parts, sizeof(uint32_t), p.st))) return rc;
+        if ((rc = grow((void**)&s->new_of_old, &s->noo_cap, cap ? cap : 1, sizeof(uint32_t), p.st))) return rc;
     }
     if (table > s->table_cap) {
-        HIPCHK(hipStreamSynchronize(st));
-        for (void** p : {(void**)&s->tb.keys, (void**)&s->tb.local_of_slot})
-            if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
+        HIPCHK(hipStreamSynchronize(p.st));
+        for (void** q : {(void**)&s->tb.keys, (void**)&s->tb.local_of_slot})
+            if (*q) { HIPCHK(hipFree(*q)); *q = nullptr; }
         HIPCHK(hipMalloc((void**)&s->tb.keys, table * (sizeof(long long) + sizeof(uint32_t)))); // keys, then the first-position words
         HIPCHK(hipMalloc((void**)&s->tb.local_of_slot, table * sizeof(uint32_t)));
         s->table_cap = table;
         s->tb.minpos = reinterpret_cast<uint32_t*>(s->tb.keys + table);
         s->clean_items = 0;
     }
+    return COALA_OK;
+}
+
+// No seeds: nothing is launched; the counts are written from the host and the device-side outputs a caller reads are zeroed.
+int empty_call(const Plan& p, int64_t* pin) {
+    for (int l = 0; l < p.info.n_layers; ++l) {
+        pin[l] = pin[kPinEdges + l] = pin[kPinRefused + l] = pin[kPinOver + l] = 0;
+        if (p.info.fanouts[l] == kFull) HIPCHK(hipMemsetAsync(p.layers[l].indptr_local, 0, sizeof(int64_t), p.st));
+    }
+    for (int g = 0; g < p.info.n_parts; ++g) pin[kPinParts + g] = 0;
+    if (p.info.n_parts > 0) HIPCHK(hipMemsetAsync(p.bucketing->counts, 0, (size_t)p.info.n_parts * sizeof(int64_t), p.st));
+    return COALA_OK;
+}
+
+// The generation tag of the next single-pass scan (degree_scan, scan_assign).
+int next_gen(coala_sampler_t* s, hipStream_t st) {
+    if ((++s->scan_gen & 0x3FFFFFFFull) == 0) { // 2^30 scans: the generation tag wraps -> clear the status words once
+        HIPCHK(hipMemsetAsync(s->status, 0, kMaxTiles * sizeof(unsigned long long), st));
+        s->scan_gen++;
+    }
+    return COALA_OK;
+}
+
+// Full layer l: degrees -> indptr_local, and its edge and item counts into its device words.
+int degree_scan(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, const int64_t* n_dst_dev) {
+    const int tiles = grid1d(p.dst_cap[l], kTile, kMaxTiles);
+    if (int rc = next_gen(s, p.st)) return rc;
+    hipLaunchKernelGGL(degree_scan_kernel, dim3(tiles), dim3(kBlock), 0, p.st, s->g, dst, n_dst_dev, p.info.n_seeds, s->counts_dev + l, s->status,
+                       s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, p.layers[l].indptr_local, p.items_cap[l],
+                       std::min<int64_t>(kItemLimit, p.layers[l].edge_cap), p.pin_dev + l);
+    s->ticket_total += (unsigned long long)tiles;
+    return COALA_OK;
+}
+
+// Layer l over the destination nodes dst[0 .. *n_dst_dev) (n_dst_dev null: the seeds, whose count travels as a kernel argument).
+int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, const int64_t* n_dst_dev) {
+    const int64_t n_seeds = p.info.n_seeds;
+    const int f = p.info.fanouts[l];
+    const bool full = f == kFull;
+    const int64_t cap_l = p.dst_cap[l];
+    int64_t* base = s->counts_dev + l;
+    int64_t* n_src_dev = s->counts_dev + l + 1;
+    int64_t* const src_out = p.layers[l].src_nodes;
+    int32_t* const nbr_out = p.layers[l].nbr_local;
+    const dim3 blk(kBlock);
+    const int tiles = grid1d(p.items_cap[l], kTile, kMaxTiles);
+    const int64_t* rdev = full ? (const int64_t*)base : n_dst_dev; // a full layer reads n_dst and E from its base
+    hipStream_t st = p.st;
+    int rc;
+    int64_t max_src = 0; // full layer: the most source nodes the fixed layers behind it accept
+    if (full) {
+        hipLaunchKernelGGL(full_insert_kernel, dim3(grid1d(p.items_cap[l], kBlock, 8192)), blk, 0, st, s->g, dst, (const int64_t*)base,
+                           (const int64_t*)p.layers[l].indptr_local, s->nbr_global, s->tb, s->slot_of_item);
+        int64_t unused_items = 0;
+        const char* unused_what = nullptr;
+        fixed_run_check(p.info, l, -1, &unused_items, &max_src, &unused_what);
+    } else {
+        unsigned long long* nh = s->hub_count + l;
+        dispatch_group(f, [&](auto gs_c) {
+            constexpr int GS = decltype(gs_c)::value;
+            const dim3 gs(grid1d(cap_l * GS, kBlock, 8192));
+            if (p.weights)
+                hipLaunchKernelGGL(weighted_select_kernel<GS>, gs, blk, 0, st, s->g, p.weights, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l,
+                                   s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap);
+            else
+                hipLaunchKernelGGL(sample_insert_kernel<GS>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l, s->nbr_global, s->tb,
+                                   s->slot_of_item);
+        });
+        if (p.weights && s->hub_cap > 0) // no launch on a graph that cannot hold a row of more than kHubDegree in-edges
+            hipLaunchKernelGGL(weighted_select_hub_kernel, dim3((unsigned)std::min<int64_t>(std::min<int64_t>(kHubGrid, s->hub_cap), std::max<int64_t>(cap_l, 1))),
+                               dim3(kHubBlock), 0, st, s->g, p.weights, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l, s->nbr_global, s->tb,
+                               s->slot_of_item, (const int64_t*)s->hubs, (const unsigned long long*)nh, s->hub_cap);
+    }
+    if ((rc = next_gen(s, st))) return rc;
+    dispatch_bool(full, [&](auto full_c) { // a full layer: n_dst from its base, and max_src in place of the seed count
+        hipLaunchKernelGGL(scan_assign_kernel<decltype(full_c)::value>, dim3(tiles), blk, 0, st, dst, s->nbr_global, rdev, full ? max_src : n_seeds,
+                           full ? 0 : f, s->slot_of_item, s->tb, s->status, s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, src_out,
+                           n_src_dev, p.pin_dev + l);
+    });
+    s->ticket_total += (unsigned long long)tiles;
+    const bool last = l + 1 == p.info.n_layers;
+    const bool next_full = !last && p.info.fanouts[l + 1] == kFull;
+    // a full next layer: its degree scan runs now, so that this layer's relabel_clear knows how much table to clear for it
+    if (next_full && (rc = degree_scan(s, p, l + 1, src_out, n_src_dev))) return rc;
+    const int64_t clear_cap = last ? (int64_t)table_size((int64_t)p.items0) : (int64_t)table_size(p.items_cap[l + 1]);
+    const int64_t* next_dev = last ? (const int64_t*)nullptr : (const int64_t*)n_src_dev;
+    const int next_f = last ? 0 : p.info.fanouts[l + 1];
+    const dim3 gr(grid1d(std::max<int64_t>(p.nbr_cap[l], clear_cap), kBlock, 4096));
+    dispatch_bool(full, [&](auto full_c) {
+        dispatch_bool(next_full, [&](auto next_full_c) {
+            hipLaunchKernelGGL((relabel_clear_kernel<decltype(full_c)::value, decltype(next_full_c)::value>), gr, blk, 0, st, rdev, n_seeds, f,
+                               s->slot_of_item, s->tb, nbr_out, next_dev, next_f, (int64_t)p.items0);
+        });
+    });
+    if (last && p.info.n_parts > 0) { // owner bucketing of the source list, and the block re-indexed through the permutation
+        const uint32_t P = (uint32_t)p.info.n_parts;
+        const int pshift = ilog2_exact((uint64_t)P);
+        int64_t* bases = s->counts_dev + COALA_SAMPLER_MAX_LAYERS + 1;
+        const dim3 gw(grid1d(((p.items_cap[l] + kRouteTile - 1) / kRouteTile) * 64, kBlock, 4096));
+        hipLaunchKernelGGL(bucket_count_kernel, gw, blk, 0, st, src_out, n_src_dev, P, pshift, s->wave_counts);
+        hipLaunchKernelGGL(bucket_scan_kernel, dim3(1), dim3(64 * (P < 16 ? P : 16)), 0, st, s->wave_counts, n_src_dev, P, p.bucketing->counts,
+                           p.pin_dev + kPinParts, bases);
+        hipLaunchKernelGGL(bucket_scatter_kernel, gw, blk, 0, st, src_out, n_src_dev, P, pshift, s->wave_counts, bases,
+                           p.bucketing->bucketed_nodes, s->new_of_old);
+        const dim3 gb(grid1d(full ? std::max(p.nbr_cap[l], cap_l) : cap_l * f, kBlock, 4096));
+        dispatch_bool(full, [&](auto full_c) {
+            hipLaunchKernelGGL(bucket_reindex_kernel<decltype(full_c)::value>, gb, blk, 0, st, rdev, n_seeds, f, s->new_of_old, nbr_out,
+                               p.bucketing->dst_in_src);
+        });
+    }
+    return COALA_OK;
+}
+
+// Every launch of a call with seeds: the first layer's table, then the layers, each reading its destination nodes from the one before.
+int launch_call(coala_sampler_t* s, Plan& p) {
+    int rc;
+    const int n_layers = p.info.n_layers;
+    const bool first_full = p.info.fanouts[0] == kFull;
+    // what the last kernel leaves clean for the next call: the first layer's table of this call, or -- when that size is known on
+    // the device only -- the extent the previous call left clean
+    p.items0 = first_full ? std::max<uint64_t>(s->clean_items, 1) : (uint64_t)p.info.n_seeds * (uint64_t)(p.info.fanouts[0] + 1);
+    // the first layer's table: normally left clean by the previous call's last kernel
+    if (!first_full && (s->clean_items == 0 || table_size((int64_t)p.items0) > table_size((int64_t)s->clean_items))) {
+        const uint32_t t0 = table_size((int64_t)p.items0);
+        HIPCHK(hipMemsetAsync(s->tb.keys, 0xFF, (size_t)t0 * sizeof(long long), p.st));
+        HIPCHK(hipMemsetAsync(s->tb.minpos, 0xFF, (size_t)t0 * sizeof(uint32_t), p.st));
+    }
+    if (p.weights && s->hub_cap > 0) HIPCHK(hipMemsetAsync(s->hub_count, 0, (size_t)n_layers * sizeof(unsigned long long), p.st));
+    if (first_full) {
+        if ((rc = degree_scan(s, p, 0, p.seeds, nullptr))) return rc;
+        hipLaunchKernelGGL(table_clear_kernel, dim3(grid1d(table_size(p.items_cap[0]), kBlock, 4096)), dim3(kBlock), 0, p.st, s->tb,
+                           (const int64_t*)(s->counts_dev + kItemsOff));
+    }
+    for (int l = 0; l < n_layers; ++l) // layer l > 0 reads its destination nodes and their count from layer l - 1's outputs
+        if ((rc = launch_layer(s, p, l, l ? p.layers[l - 1].src_nodes : p.seeds, l ? s->counts_dev + l : nullptr))) return rc;
+    s->clean_items = p.items0;
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed, uint64_t step,
+                const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
+                int64_t* ticket_out, void* stream, const float* weights) {
+    int rc;
+    if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, layers, bucketing))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(s->device));
+    // the handle's scratch (hash table, scan state) is ordered by the stream of its calls: a caller that moves to another stream
+    // first waits there for the previous call's last kernel
+    if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
+    s->last_stream = st;
+    Plan p{seeds, seed, step, layers, bucketing, weights, st};
+    if ((rc = plan_call(p, n_seeds, fanouts, n_layers, bucketing ? bucketing->n_parts : 0))) return rc;
+    if ((rc = grow_workspace(s, p))) return rc;
     const uint64_t ticket = s->calls;
     const int slot = (int)(ticket % kRing);
     if (ticket >= kRing) HIPCHK(hipEventSynchronize(s->done[slot])); // the ring slot's previous user has finished writing it
-    int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
-    int64_t* pin_dev = s->counts_pinned_dev + (size_t)slot * kSlot;
-    s->ring[slot] = info;
-    if (n_seeds == 0) {
-        for (int l = 0; l < n_layers; ++l) {
-            pin[l] = pin[kPinEdges + l] = pin[kPinRefused + l] = pin[kPinOver + l] = 0;
-            if (fanouts[l] == kFull) HIPCHK(hipMemsetAsync(layers[l].indptr_local, 0, sizeof(int64_t), st));
-        }
-        for (int g = 0; g < n_parts; ++g) pin[kPinParts + g] = 0;
-        if (n_parts > 0) HIPCHK(hipMemsetAsync(bucketing->counts, 0, (size_t)n_parts * sizeof(int64_t), st));
-    } else {
-        const bool first_full = fanouts[0] == kFull;
-        // what the last kernel leaves clean for the next call: the first layer's table of this call, or -- when that size is known on
-        // the device only -- the extent the previous call left clean
-        const uint64_t items0 = first_full ? std::max<uint64_t>(s->clean_items, 1) : (uint64_t)n_seeds * (uint64_t)(fanouts[0] + 1);
-        // the first layer's table: normally left clean by the previous call's last kernel
-        if (!first_full && (s->clean_items == 0 || table_size((int64_t)items0) > table_size((int64_t)s->clean_items))) {
-            const uint32_t t0 = table_size((int64_t)items0);
-            HIPCHK(hipMemsetAsync(s->tb.keys, 0xFF, (size_t)t0 * sizeof(long long), st));
-            HIPCHK(hipMemsetAsync(s->tb.minpos, 0xFF, (size_t)t0 * sizeof(uint32_t), st));
-        }
-        if (weights && s->hub_cap > 0) HIPCHK(hipMemsetAsync(s->hub_count, 0, (size_t)n_layers * sizeof(unsigned long long), st));
-        auto next_gen = [&]() -> int {
-            if ((++s->scan_gen & 0x3FFFFFFFull) == 0) { // 2^30 scans: the generation tag wraps -> clear the status words once
-                HIPCHK(hipMemsetAsync(s->status, 0, kMaxTiles * sizeof(unsigned long long), st));
-                s->scan_gen++;
-            }
-            return COALA_OK;
-        };
-        auto degree_scan = [&](int l, const int64_t* dst_l, const int64_t* n_dst_dev_l) -> int {
-            const int tiles = grid1d(dst_cap[l], kTile, kMaxTiles);
-            int r;
-            if ((r = next_gen())) return r;
-            hipLaunchKernelGGL(degree_scan_kernel, dim3(tiles), dim3(kBlock), 0, st, s->g, dst_l, n_dst_dev_l, n_seeds, s->counts_dev + l, s->status,
-                               s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, layers[l].indptr_local, items_cap[l],
-                               std::min<int64_t>(kItemLimit, layers[l].edge_cap), pin_dev + l);
-            s->ticket_total += (unsigned long long)tiles;
-            return COALA_OK;
-        };
-        if (first_full) {
-            if ((rc = degree_scan(0, seeds, nullptr))) return rc;
-            hipLaunchKernelGGL(table_clear_kernel, dim3(grid1d(table_size(items_cap[0]), kBlock, 4096)), dim3(kBlock), 0, st, s->tb,
-                               (const int64_t*)(s->counts_dev + kItemsOff));
-        }
-        const int64_t* n_dst_dev = nullptr;            // first layer: the seed count travels as a kernel argument
-        const int64_t* dst = seeds;
-        for (int l = 0; l < n_layers; ++l) {
-            const int f = fanouts[l];
-            const bool full = f == kFull;
-            const int64_t cap_l = dst_cap[l];
-            int64_t* base = s->counts_dev + l;
-            int64_t* n_src_dev = s->counts_dev + l + 1;
-            int64_t* const src_out = layers[l].src_nodes;
-            int32_t* const nbr_out = layers[l].nbr_local;
-            const dim3 blk(kBlock);
-            const int tiles = grid1d(items_cap[l], kTile, kMaxTiles);
-            if (full) {
-                hipLaunchKernelGGL(full_insert_kernel, dim3(grid1d(items_cap[l], kBlock, 8192)), blk, 0, st, s->g, dst, (const int64_t*)base,
-                                   (const int64_t*)layers[l].indptr_local, s->nbr_global, s->tb, s->slot_of_item);
-                int64_t max_src = 0;
-                int64_t unused_items = 0;
-                const char* unused_what = nullptr;
-                fixed_run_check(info, l, -1, &unused_items, &max_src, &unused_what);
-                if ((rc = next_gen())) return rc;
-                hipLaunchKernelGGL(scan_assign_kernel<true>, dim3(tiles), blk, 0, st, dst, s->nbr_global, (const int64_t*)base, max_src, 0, s->slot_of_item,
-                                   s->tb, s->status, s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, src_out, n_src_dev, pin_dev + l);
-            } else {
-                const dim3 gs(grid1d(cap_l * (f < 16 ? 16 : f < 32 ? 32 : 64), kBlock, 8192));
-                if (weights) {
-                    unsigned long long* nh = s->hub_count + l;
-                    if (f < 16)
-                        hipLaunchKernelGGL(weighted_select_kernel<16>, gs, blk, 0, st, s->g, weights, dst, n_dst_dev, n_seeds, f, seed, step, l,
-                                           s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap);
-                    else if (f < 32)
-                        hipLaunchKernelGGL(weighted_select_kernel<32>, gs, blk, 0, st, s->g, weights, dst, n_dst_dev, n_seeds, f, seed, step, l,
-                                           s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap);
-                    else
-                        hipLaunchKernelGGL(weighted_select_kernel<64>, gs, blk, 0, st, s->g, weights, dst, n_dst_dev, n_seeds, f, seed, step, l,
-                                           s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap);
-                    if (s->hub_cap > 0) // no launch on a graph that cannot hold a row of more than kHubDegree in-edges
-                        hipLaunchKernelGGL(weighted_select_hub_kernel, dim3((unsigned)std::min<int64_t>(std::min<int64_t>(kHubGrid, s->hub_cap), std::max<int64_t>(cap_l, 1))),
-                                           dim3(kHubBlock), 0, st, s->g, weights, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb,
-                                           s->slot_of_item, (const int64_t*)s->hubs, (const unsigned long long*)nh, s->hub_cap);
-                } else if (f < 16)
-                    hipLaunchKernelGGL(sample_insert_kernel<16>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb, s->slot_of_item);
-                else if (f < 32)
-                    hipLaunchKernelGGL(sample_insert_kernel<32>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb, s->slot_of_item);
-                else
-                    hipLaunchKernelGGL(sample_insert_kernel<64>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, seed, step, l, s->nbr_global, s->tb, s->slot_of_item);
-                if ((rc = next_gen())) return rc;
-                hipLaunchKernelGGL(scan_assign_kernel<false>, dim3(tiles), blk, 0, st, dst, s->nbr_global, n_dst_dev, n_seeds, f, s->slot_of_item, s->tb,
-                                   s->status, s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, src_out, n_src_dev, pin_dev + l);
-            }
-            s->ticket_total += (unsigned long long)tiles;
-            const bool last = l + 1 == n_layers;
-            const bool next_full = !last && fanouts[l + 1] == kFull;
-            // a full next layer: its degree scan runs now, so that this layer's relabel_clear knows how much table to clear for it
-            if (next_full && (rc = degree_scan(l + 1, src_out, n_src_dev))) return rc;
-            const int64_t clear_cap = last ? (int64_t)table_size((int64_t)items0) : (int64_t)table_size(items_cap[l + 1]);
-            const int64_t* rdev = full ? (const int64_t*)base : n_dst_dev; // a full layer reads n_dst and E from its base
-            const int64_t* next_dev = last ? (const int64_t*)nullptr : (const int64_t*)n_src_dev;
-            const int next_f = last ? 0 : fanouts[l + 1];
-            const dim3 gr(grid1d(std::max<int64_t>(nbr_cap[l], clear_cap), kBlock, 4096));
-            if (full && next_full)
-                hipLaunchKernelGGL((relabel_clear_kernel<true, true>), gr, blk, 0, st, rdev, n_seeds, f, s->slot_of_item, s->tb, nbr_out, next_dev, next_f, (int64_t)items0);
-            else if (full)
-                hipLaunchKernelGGL((relabel_clear_kernel<true, false>), gr, blk, 0, st, rdev, n_seeds, f, s->slot_of_item, s->tb, nbr_out, next_dev, next_f, (int64_t)items0);
-            else if (next_full)
-                hipLaunchKernelGGL((relabel_clear_kernel<false, true>), gr, blk, 0, st, rdev, n_seeds, f, s->slot_of_item, s->tb, nbr_out, next_dev, next_f, (int64_t)items0);
-            else
-                hipLaunchKernelGGL((relabel_clear_kernel<false, false>), gr, blk, 0, st, rdev, n_seeds, f, s->slot_of_item, s->tb, nbr_out, next_dev, next_f, (int64_t)items0);
-            if (last && n_parts > 0) {
-                const uint32_t P = (uint32_t)n_parts;
-                const int pshift = ilog2_exact((uint64_t)n_parts);
-                int64_t* bases = s->counts_dev + COALA_SAMPLER_MAX_LAYERS + 1;
-                const dim3 gw(grid1d(((items_cap[l] + kRouteTile - 1) / kRouteTile) * 64, kBlock, 4096));
-                hipLaunchKernelGGL(bucket_count_kernel, gw, blk, 0, st, src_out, n_src_dev, P, pshift, s->wave_counts);
-                hipLaunchKernelGGL(bucket_scan_kernel, dim3(1), dim3(64 * (n_parts < 16 ? n_parts : 16)), 0, st, s->wave_counts, n_src_dev, P,
-                                   bucketing->counts, pin_dev + kPinParts, bases);
-                hipLaunchKernelGGL(bucket_scatter_kernel, gw, blk, 0, st, src_out, n_src_dev, P, pshift, s->wave_counts, bases,
-                                   bucketing->bucketed_nodes, s->new_of_old);
-                const dim3 gb(grid1d(full ? std::max(nbr_cap[l], cap_l) : cap_l * f, kBlock, 4096));
-                if (full)
-                    hipLaunchKernelGGL(bucket_reindex_kernel<true>, gb, blk, 0, st, rdev, n_seeds, f, s->new_of_old, nbr_out, bucketing->dst_in_src);
-                else
-                    hipLaunchKernelGGL(bucket_reindex_kernel<false>, gb, blk, 0, st, rdev, n_seeds, f, s->new_of_old, nbr_out, bucketing->dst_in_src);
-            }
-            dst = src_out;
-            n_dst_dev = n_src_dev;
-        }
-        s->clean_items = items0;
-        HIPCHK(hipGetLastError());
-    }
+    p.pin_dev = s->counts_pinned_dev + (size_t)slot * kSlot;
+    s->ring[slot] = p.info;
+    if ((rc = n_seeds == 0 ? empty_call(p, s->counts_pinned + (size_t)slot * kSlot) : launch_call(s, p))) return rc;
     HIPCHK(hipEventRecord(s->done[slot], st));
     s->calls++;
     if (ticket_out) *ticket_out = (int64_t)ticket;
@@ -1440,57 +1169,6 @@ int coala_sampler_destroy(coala_sampler_t* s) {
     return COALA_OK;
 }
 
-int coala_block_mean_aggregate(int device, const int32_t* nbr, const float* h_src, float* out, int64_t n_dst, int fanout, int dim, void* stream) {
-    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
-    if (n_dst == 0) return COALA_OK;
-    if (!nbr || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
-    const bool v4 = dim % 4 == 0 && ((reinterpret_cast<uintptr_t>(h_src) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
-    if (v4) hipLaunchKernelGGL(mean_aggregate_kernel<4>, grid, blk, 0, (hipStream_t)stream, nbr, h_src, out, n_dst, fanout, dim);
-    else hipLaunchKernelGGL(mean_aggregate_kernel<1>, grid, blk, 0, (hipStream_t)stream, nbr, h_src, out, n_dst, fanout, dim);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-int coala_block_mean_aggregate_backward(int device, const int32_t* nbr, const float* grad_out, float* grad_src, int64_t n_dst, int fanout,
-                                        int dim, void* stream) {
-    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
-    if (n_dst == 0) return COALA_OK;
-    if (!nbr || !grad_out || !grad_src) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(mean_aggregate_backward_kernel, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, nbr, grad_out,
-                       grad_src, n_dst, fanout, dim);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-int coala_block_mean_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int64_t n_dst, int dim,
-                                   void* stream) {
-    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
-    if (n_dst == 0) return COALA_OK;
-    if (!indptr || !indices || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
-    const bool v4 = dim % 4 == 0 && ((reinterpret_cast<uintptr_t>(h_src) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
-    if (v4) hipLaunchKernelGGL(mean_aggregate_csr_kernel<4>, grid, blk, 0, (hipStream_t)stream, indptr, indices, h_src, out, n_dst, dim);
-    else hipLaunchKernelGGL(mean_aggregate_csr_kernel<1>, grid, blk, 0, (hipStream_t)stream, indptr, indices, h_src, out, n_dst, dim);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-int coala_block_mean_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* grad_out, float* grad_src,
-                                            int64_t n_dst, int dim, void* stream) {
-    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
-    if (n_dst == 0) return COALA_OK;
-    if (!indptr || !indices || !grad_out || !grad_src) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(mean_aggregate_csr_backward_kernel, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, indptr,
-                       indices, grad_out, grad_src, n_dst, dim);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
 int coala_sampler_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* bucket_counts_host) {
     return wait_impl(s, ticket, n_src_host, nullptr, bucket_counts_host);
 }
@@ -1503,18 +1181,15 @@ int coala_sampler_sample(coala_sampler_t* s, const int64_t* seeds, int64_t n_see
                          uint64_t seed, uint64_t step, int64_t* const* src_nodes_out, int32_t* const* nbr_local_out,
                          int64_t* n_src_host, const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
     if (!s || (!seeds && n_seeds > 0) || !fanouts || !src_nodes_out || !nbr_local_out) return fail(COALA_EINVAL, "null argument");
-    int rc;
-    if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, bucketing))) return rc;
-    // fixed fan-outs only, into the dense buffers: cap_{l+1} = cap_l * (f + 1) source nodes, cap_l * f neighbour entries
+    // fixed fan-outs only, into the dense buffers: cap_{l+1} = cap_l * (f + 1) source nodes, cap_l * f neighbour entries.  sample_impl
+    // checks the rest from n_seeds itself; a cap it will refuse (negative, or past the item limit) is clamped so that no product overflows
     coala_sampler_layer_t layers[COALA_SAMPLER_MAX_LAYERS];
-    int64_t cap = n_seeds;
-    for (int l = 0; l < n_layers; ++l) {
+    int64_t cap = std::min(std::max<int64_t>(n_seeds, 0), kItemLimit + 1);
+    for (int l = 0; l < n_layers && l < COALA_SAMPLER_MAX_LAYERS; ++l) {
         const int f = fanouts[l];
         if (f < 1 || f > 32) return fail(COALA_EINVAL, "fan-out %d outside 1..32", f);
-        const uint64_t items = (uint64_t)cap * (uint64_t)(f + 1);
-        if (items > (uint64_t)kMaxTiles * kTile) return fail(COALA_EINVAL, "layer %d would hold %llu items (limit %d)", l, (unsigned long long)items, kMaxTiles * kTile);
-        layers[l] = coala_sampler_layer_t{src_nodes_out[l], nbr_local_out[l], nullptr, (int64_t)items, cap * f};
-        cap = (int64_t)items;
+        layers[l] = coala_sampler_layer_t{src_nodes_out[l], nbr_local_out[l], nullptr, cap * (f + 1), cap * f};
+        cap = std::min(cap * (f + 1), kItemLimit + 1);
     }
     return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, nullptr, bucketing, ticket_out, stream, nullptr);
 }
@@ -1532,85 +1207,6 @@ int coala_sampler_sample_layers_weighted(coala_sampler_t* s, const int64_t* seed
     if (!edge_weights) return fail(COALA_EINVAL, "null edge_weights");
     return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream,
                        edge_weights);
-}
-
-} // extern "C"
-
-namespace {
-int gat_check(int64_t n_dst, int heads, int dim) {
-    if (n_dst < 0 || heads < 1 || heads > kGatMaxHeads || dim < 1 || (int64_t)heads * dim > INT32_MAX)
-        return fail(COALA_EINVAL, "bad block shape (heads 1..%d, dim >= 1, n_dst >= 0)", kGatMaxHeads);
-    return COALA_OK;
-}
-
-bool gat_v4(int dim, const float* feat, const float* out) {
-    return dim % 4 == 0 && ((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
-}
-} // namespace
-
-extern "C" {
-
-int coala_block_gat_aggregate(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, float* out, float* lse,
-                              int64_t n_dst, int fanout, int heads, int dim, float negative_slope, void* stream) {
-    if (fanout < 1 || fanout > 32) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
-    if (n_dst == 0) return COALA_OK;
-    if (!nbr || !el || !er || !feat || !out || !lse) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
-    if (gat_v4(dim, feat, out))
-        hipLaunchKernelGGL((gat_aggregate_kernel<4, false>), grid, blk, 0, (hipStream_t)stream, nullptr, nbr, fanout, el, er, feat, out, lse, n_dst,
-                           heads, dim, negative_slope);
-    else
-        hipLaunchKernelGGL((gat_aggregate_kernel<1, false>), grid, blk, 0, (hipStream_t)stream, nullptr, nbr, fanout, el, er, feat, out, lse, n_dst,
-                           heads, dim, negative_slope);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-int coala_block_gat_aggregate_backward(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, const float* out,
-                                       const float* lse, const float* grad_out, float* grad_feat, float* grad_el, float* grad_er, int64_t n_dst,
-                                       int fanout, int heads, int dim, float negative_slope, void* stream) {
-    if (fanout < 1 || fanout > 32) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
-    if (n_dst == 0) return COALA_OK;
-    if (!nbr || !el || !er || !feat || !out || !lse || !grad_out || !grad_feat || !grad_el || !grad_er) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(gat_aggregate_backward_kernel<false>, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, nullptr,
-                       nbr, fanout, el, er, feat, out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim, negative_slope);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-int coala_block_gat_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er, const float* feat,
-                                  float* out, float* lse, int64_t n_dst, int heads, int dim, float negative_slope, void* stream) {
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
-    if (n_dst == 0) return COALA_OK;
-    if (!indptr || !indices || !el || !er || !feat || !out || !lse) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
-    if (gat_v4(dim, feat, out))
-        hipLaunchKernelGGL((gat_aggregate_kernel<4, true>), grid, blk, 0, (hipStream_t)stream, indptr, indices, 0, el, er, feat, out, lse, n_dst,
-                           heads, dim, negative_slope);
-    else
-        hipLaunchKernelGGL((gat_aggregate_kernel<1, true>), grid, blk, 0, (hipStream_t)stream, indptr, indices, 0, el, er, feat, out, lse, n_dst,
-                           heads, dim, negative_slope);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er,
-                                           const float* feat, const float* out, const float* lse, const float* grad_out, float* grad_feat,
-                                           float* grad_el, float* grad_er, int64_t n_dst, int heads, int dim, float negative_slope, void* stream) {
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
-    if (n_dst == 0) return COALA_OK;
-    if (!indptr || !indices || !el || !er || !feat || !out || !lse || !grad_out || !grad_feat || !grad_el || !grad_er)
-        return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(gat_aggregate_backward_kernel<true>, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, indptr,
-                       indices, 0, el, er, feat, out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim, negative_slope);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
 }
 
 } // extern "C"

@@ -1,4 +1,4 @@
-"""GPU tests of the block op (coala_block_mean_aggregate[_backward] in coala_sampler.hip) against a float64 reference.
+"""GPU tests of the block op (coala_block_mean_aggregate[_backward] in coala_block_ops.hip) against a float64 reference.
 
 Called directly through the C ABI with hand-made int32 neighbour arrays: -1 anywhere in a row, rows without any valid entry, a
 source repeated within a row, fan-outs 1..32, dims that take the 16-byte path (dim % 4 == 0, aligned buffers), the scalar path

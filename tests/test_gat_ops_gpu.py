@@ -1,4 +1,4 @@
-"""GPU tests of the GAT attention kernels (coala_block_gat_aggregate[_csr][_backward] in coala_sampler.hip) against float64.
+"""GPU tests of the GAT attention kernels (coala_block_gat_aggregate[_csr][_backward] in coala_block_ops.hip) against float64.
 
 Called through the C ABI on hand-made blocks: fixed rows with -1 anywhere, rows without a valid edge, repeated sources, fan-outs
 1..32; CSR rows of degree 0 to past one 64-edge chunk and a hub of 1,000,003 in-edges; heads 1, 2, 4, 8; D in {1, 3, 16, 64, 65,

@@ -26,7 +26,7 @@ for stream in (None, torch.cuda.Stream()):
             nbr = [torch.empty(caps[l] * 5, dtype=torch.int32, device="cuda") for l in range(L)]
             src_p = (C.c_void_p * L)(*[t.data_ptr() for t in src]); nbr_p = (C.c_void_p * L)(*[t.data_ptr() for t in nbr])
             fan = (C.c_int32 * L)(*rev); n_src = (C.c_int64 * L)(); t2 = clk()
-            _capi.check(_lib.coala_sampler_sample(g._h, seeds.data_ptr(), n, fan, L, 0, it, src_p, nbr_p, n_src, current_stream())); t3 = clk()
+            _capi.check(_lib.coala_sampler_sample(g._h, seeds.data_ptr(), n, fan, L, 0, it, src_p, nbr_p, n_src, None, None, current_stream())); t3 = clk()
             blocks = []; n_dst = n
             for l in range(L):
                 ns = int(n_src[l])
