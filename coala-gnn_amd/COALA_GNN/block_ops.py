@@ -1,5 +1,5 @@
-"""Autograd wrappers of the native block ops that `Block` (sampler.py) hands to a model: mean aggregation (SAGEConv's "mean") and GAT
-attention aggregation, on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the
+"""Autograd wrappers of the native block ops that `Block` (sampler.py) hands to a model: mean aggregation (SAGEConv's "mean"), weighted
+sum aggregation (DGL's u_mul_e_sum, the edge_weight= path of GraphConv / SAGEConv) and GAT attention aggregation, on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the
 kernels are in coala-gnn_amd/csrc/coala_block_ops.hip (C ABI: coala_block_*)."""
 import torch
 
@@ -58,6 +58,64 @@ class _MeanAggregateCSR(torch.autograd.Function):
         _capi.check(_lib.coala_block_mean_aggregate_csr_backward(g.device.index or 0, indptr.data_ptr(), indices.data_ptr(), g.data_ptr(),
                                                                  grad_src.data_ptr(), indptr.numel() - 1, g.shape[1], current_stream()))
         return grad_src, None, None
+
+
+class _WeightedSum(torch.autograd.Function):
+    """out[d] = sum over the valid j of w[d, j] * h_src[nbr[d, j]] (coala_block_weighted_sum): one kernel forward, one backward that
+    gives grad_src and grad_w together; a gradient nobody asked for is neither computed nor allocated."""
+
+    @staticmethod
+    def forward(ctx, h_src, w, nbr):
+        h, w = h_src.contiguous(), w.contiguous()
+        n_dst, fanout = nbr.shape
+        out = torch.empty((n_dst, h.shape[1]), dtype=torch.float32, device=h.device)
+        _capi.check(_lib.coala_block_weighted_sum(h.device.index or 0, nbr.data_ptr(), w.data_ptr(), h.data_ptr(), out.data_ptr(), n_dst, fanout,
+                                                  h.shape[1], current_stream()))
+        ctx.save_for_backward(h, w, nbr)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        need_src, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not need_src and not need_w:
+            return None, None, None
+        h, w, nbr = ctx.saved_tensors
+        g = grad_out.contiguous()
+        grad_src = torch.zeros_like(h) if need_src else None
+        grad_w = torch.empty_like(w) if need_w else None
+        _capi.check(_lib.coala_block_weighted_sum_backward(g.device.index or 0, nbr.data_ptr(), w.data_ptr(), h.data_ptr(), g.data_ptr(),
+                                                           grad_src.data_ptr() if need_src else None, grad_w.data_ptr() if need_w else None,
+                                                           nbr.shape[0], nbr.shape[1], g.shape[1], current_stream()))
+        return grad_src, grad_w, None
+
+
+class _WeightedSumCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_weighted_sum_csr): row d sums w[e] * h_src[indices[e]] over e in indptr[d]:indptr[d+1]."""
+
+    @staticmethod
+    def forward(ctx, h_src, w, indptr, indices):
+        h, w = h_src.contiguous(), w.contiguous()
+        n_dst = indptr.numel() - 1
+        out = torch.empty((n_dst, h.shape[1]), dtype=torch.float32, device=h.device)
+        _capi.check(_lib.coala_block_weighted_sum_csr(h.device.index or 0, indptr.data_ptr(), indices.data_ptr(), w.data_ptr(), h.data_ptr(),
+                                                      out.data_ptr(), n_dst, h.shape[1], current_stream()))
+        ctx.save_for_backward(h, w, indptr, indices)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        need_src, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not need_src and not need_w:
+            return None, None, None, None
+        h, w, indptr, indices = ctx.saved_tensors
+        g = grad_out.contiguous()
+        grad_src = torch.zeros_like(h) if need_src else None
+        grad_w = torch.empty_like(w) if need_w else None
+        _capi.check(_lib.coala_block_weighted_sum_csr_backward(g.device.index or 0, indptr.data_ptr(), indices.data_ptr(), w.data_ptr(),
+                                                               h.data_ptr(), g.data_ptr(), grad_src.data_ptr() if need_src else None,
+                                                               grad_w.data_ptr() if need_w else None, indptr.numel() - 1, g.shape[1],
+                                                               current_stream()))
+        return grad_src, grad_w, None, None
 
 
 def _gat_contig(el, er, feat_src):

@@ -1,14 +1,15 @@
 """Small consumers of the loader's 4-tuple on the native Block objects.  SageMean, a 2-layer GraphSAGE (mean) in plain torch, is
 used by bench.py's epoch leg and the tests; it stands where examples/models.py:DistSAGE + dgl.nn.SAGEConv stand in the reference's
 training script (examples/sbatch_ssd_gnn_train.py:98-145).  GAT and GCN mirror the reference's examples/models.py:GAT and :GCN on
-COALA_GNN.nn's GATConv and GraphConv (--model_type gat|gcn); GAT's attention step is a native kernel (Block.gat_aggregate)."""
+COALA_GNN.nn's GATConv and GraphConv (--model_type gat|gcn); GAT's attention step is a native kernel (Block.gat_aggregate).  GCN and
+SAGE take edge_weight=<edata key> and then hand block.edata[key] to their layers (blocks sampled with NeighborSampler(edge_ids=True))."""
 import time
 
 import torch
 
-from .nn import GATConv, GraphConv
+from .nn import GATConv, GraphConv, SAGEConv
 
-__all__ = ["SageMean", "GAT", "GCN", "train_steps", "FlatGradAllReduce"]
+__all__ = ["SageMean", "SAGE", "GAT", "GCN", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -48,18 +49,42 @@ class GAT(torch.nn.Module):
 class GCN(torch.nn.Module):
     """examples/models.py:GCN: n_layers GraphConv layers (norm='both'), dropout then relu between them."""
 
-    def __init__(self, in_feats, h_feats, num_classes, num_layers=2, dropout=0.2):
+    def __init__(self, in_feats, h_feats, num_classes, num_layers=2, dropout=0.2, edge_weight=None):
         super().__init__()
         dims = [in_feats] + [h_feats] * (num_layers - 1) + [num_classes]
         self.layers = torch.nn.ModuleList(GraphConv(dims[i], dims[i + 1]) for i in range(num_layers))
         self.dropout = torch.nn.Dropout(dropout)
+        self.edge_weight = edge_weight   # edata key of the per-edge weight every layer multiplies its messages by, or None
 
     def forward(self, blocks, x):
         h = x
         for i, (layer, block) in enumerate(zip(self.layers, blocks)):
-            h = layer(block, (h, block.dst_rows(h)))
+            if self.edge_weight is None:
+                h = layer(block, (h, block.dst_rows(h)))
+            else:
+                h = layer(block, (h, block.dst_rows(h)), edge_weight=block.edata[self.edge_weight])
             if i + 1 < len(self.layers):
                 h = torch.relu(self.dropout(h))
+        return h
+
+
+class SAGE(torch.nn.Module):
+    """GraphSAGE on COALA_GNN.nn.SAGEConv ('mean', or 'gcn' as the reference's RSAGE model uses), relu between the layers; with
+    edge_weight=<edata key> every layer weighs its messages by block.edata[key]."""
+
+    def __init__(self, in_feats, h_feats, num_classes, num_layers=2, aggregator_type="mean", edge_weight=None):
+        super().__init__()
+        dims = [in_feats] + [h_feats] * (num_layers - 1) + [num_classes]
+        self.layers = torch.nn.ModuleList(SAGEConv(dims[i], dims[i + 1], aggregator_type) for i in range(num_layers))
+        self.edge_weight = edge_weight
+
+    def forward(self, blocks, x):
+        h = x
+        for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+            w = None if self.edge_weight is None else block.edata[self.edge_weight]
+            h = layer(block, (h, block.dst_rows(h)), edge_weight=w)
+            if i + 1 < len(self.layers):
+                h = torch.relu(h)
         return h
 
 

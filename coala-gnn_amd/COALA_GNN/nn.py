@@ -2,10 +2,12 @@
 installed on the MI355X image).  Both take (block, (h_src, h_dst)) as DGL's modules do on a block.
 
 GATConv's projections are dense and stay in torch; its attention step (score, per-destination softmax, weighted sum) is
-Block.gat_aggregate, a native kernel on both block forms.  GraphConv reduces to Block.mean_aggregate times the in-degree."""
+Block.gat_aggregate, a native kernel on both block forms.  GraphConv reduces to Block.mean_aggregate times the in-degree.  With
+edge_weight= (one value per neighbour slot, e.g. block.edata['w'] of a block sampled with edge_ids=True) GraphConv and SAGEConv
+aggregate with Block.weighted_sum_aggregate, DGL's u_mul_e_sum."""
 import torch
 
-__all__ = ["GATConv", "GraphConv"]
+__all__ = ["GATConv", "GraphConv", "SAGEConv"]
 
 
 class GATConv(torch.nn.Module):
@@ -65,6 +67,8 @@ class GraphConv(torch.nn.Module):
     with the degrees counted over the valid edges of the block and clamped to at least 1.  weight [in_feats, out_feats] (Xavier-uniform),
     bias [out_feats] (zero): DGL's names and shapes.  The projection is applied before the aggregation when in_feats > out_feats, after
     it otherwise, as DGL does.  h_dst is accepted for DGL's calling convention and unused.
+    edge_weight (one value per neighbour slot, shaped like block.edata['_ID']; padding slots unread): the message is h_src[s_j] * w_j,
+    DGL's rule -- the sum replaces the unweighted one and both degrees stay the unweighted counts of valid edges.
     Deviation: a destination without an in-edge gets the bias alone; DGL raises unless allow_zero_in_degree=True, and then gives the
     same row."""
 
@@ -81,16 +85,76 @@ class GraphConv(torch.nn.Module):
         if self.bias is not None:
             torch.nn.init.zeros_(self.bias)
 
-    def forward(self, block, feat):
+    def forward(self, block, feat, edge_weight=None):
         h_src = feat[0] if isinstance(feat, (tuple, list)) else feat
         out_deg = block.out_degrees().to(device=h_src.device, dtype=h_src.dtype).clamp_min(1)
         in_deg = block.in_degrees().to(device=h_src.device, dtype=h_src.dtype).clamp_min(1)
         h = h_src * out_deg.pow(-0.5).unsqueeze(-1)
         if self._in_feats > self._out_feats:
             h = h @ self.weight
-        rst = block.mean_aggregate(h) * in_deg.sqrt().unsqueeze(-1)   # sum * in_deg^-1/2 = mean * in_deg^1/2; 0 without in-edges
+        if edge_weight is None:
+            rst = block.mean_aggregate(h) * in_deg.sqrt().unsqueeze(-1)   # sum * in_deg^-1/2 = mean * in_deg^1/2; 0 without in-edges
+        else:
+            rst = block.weighted_sum_aggregate(h, edge_weight) * in_deg.pow(-0.5).unsqueeze(-1)
         if self._in_feats <= self._out_feats:
             rst = rst @ self.weight
+        if self.bias is not None:
+            rst = rst + self.bias
+        if self.activation is not None:
+            rst = self.activation(rst)
+        return rst
+
+
+class SAGEConv(torch.nn.Module):
+    """GraphSAGE layer on a block, with DGL SAGEConv's parameter names so that such a state_dict loads:
+        'mean':  out[d] = fc_self(h_dst[d]) + fc_neigh(mean_j h_src[s_j]) + bias
+        'gcn':   out[d] = fc_neigh((sum_j h_src[s_j] + h_dst[d]) / (in_deg(d) + 1)) + bias        (no fc_self)
+    over the valid in-edges j of d in the block; fc_self.weight / fc_neigh.weight [out_feats, in_feats] (no bias of their own,
+    Xavier-uniform with the gain of relu), bias [out_feats] (zero).  With edge_weight (one value per neighbour slot, shaped like
+    block.edata['_ID']) every message is h_src[s_j] * w_j while the divisor stays the unweighted in-degree: DGL's rule.  The
+    projection runs before the aggregation when in_feats > out_feats, as DGL does.  feat is h_src or (h_src, h_dst); without h_dst
+    the destination rows are block.dst_rows(h_src).  A destination without an in-edge gets fc_self(h_dst) + bias ('mean') or
+    fc_neigh(h_dst) + bias ('gcn').  The 'pool' and 'lstm' aggregators, feat_drop and norm are not provided."""
+
+    def __init__(self, in_feats, out_feats, aggregator_type="mean", bias=True, activation=None):
+        super().__init__()
+        if aggregator_type not in ("mean", "gcn"):
+            raise ValueError(f"aggregator_type {aggregator_type!r}: 'mean' or 'gcn'")
+        in_src, in_dst = in_feats if isinstance(in_feats, (tuple, list)) else (in_feats, in_feats)
+        self._in_src_feats, self._out_feats, self._aggre_type = in_src, out_feats, aggregator_type
+        self.fc_neigh = torch.nn.Linear(in_src, out_feats, bias=False)
+        if aggregator_type != "gcn":
+            self.fc_self = torch.nn.Linear(in_dst, out_feats, bias=False)
+        self.bias = torch.nn.Parameter(torch.empty(out_feats)) if bias else None
+        self.activation = activation
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        torch.nn.init.xavier_uniform_(self.fc_neigh.weight, gain=gain)
+        if self._aggre_type != "gcn":
+            torch.nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, block, feat, edge_weight=None):
+        h_src, h_dst = feat if isinstance(feat, (tuple, list)) else (feat, block.dst_rows(feat))
+        lin_before = self._in_src_feats > self._out_feats
+        h = self.fc_neigh(h_src) if lin_before else h_src
+        deg = block.in_degrees().to(device=h.device, dtype=h.dtype).unsqueeze(-1)
+        if self._aggre_type == "mean":
+            if edge_weight is None:
+                neigh = block.mean_aggregate(h)
+            else:
+                neigh = block.weighted_sum_aggregate(h, edge_weight) / deg.clamp_min(1)
+            rst = self.fc_self(h_dst) + (neigh if lin_before else self.fc_neigh(neigh))
+        else:
+            if edge_weight is None:
+                total = block.mean_aggregate(h) * deg
+            else:
+                total = block.weighted_sum_aggregate(h, edge_weight)
+            neigh = (total + (self.fc_neigh(h_dst) if lin_before else h_dst)) / (deg + 1)
+            rst = neigh if lin_before else self.fc_neigh(neigh)
         if self.bias is not None:
             rst = rst + self.bias
         if self.activation is not None:

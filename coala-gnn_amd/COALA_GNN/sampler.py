@@ -11,12 +11,13 @@ import torch
 
 from COALA_GNN_Pybind import _capi, current_stream
 
-from .block_ops import _GatAggregate, _GatAggregateCSR, _MeanAggregate, _MeanAggregateCSR
+from .block_ops import _GatAggregate, _GatAggregateCSR, _MeanAggregate, _MeanAggregateCSR, _WeightedSum, _WeightedSumCSR
 
-__all__ = ["NeighborSampler", "CSCGraph", "Block", "ITEM_LIMIT"]
+__all__ = ["NeighborSampler", "CSCGraph", "Block", "ITEM_LIMIT", "EID"]
 
 _lib = _capi.load()
 
+EID = "_ID"   # DGL's dgl.EID: block.edata[EID] is the position of every sampled edge in the graph's CSC `indices` array
 ITEM_LIMIT = 8192 * 1024   # items (destination nodes + neighbour slots) one layer may hold (coala_sampler.hip: kMaxTiles * kTile)
 
 
@@ -78,13 +79,44 @@ class CSCGraph(object):
             pass
 
 
+class _EdgeData(dict):
+    """block.edata of a block sampled with NeighborSampler(edge_ids=True): holds '_ID' (the CSC position of every neighbour slot, -1
+    on padding); every other key of graph.edata is gathered through it on first access -- padding slots give 0 -- and kept."""
+
+    def __init__(self, eid, graph):
+        super().__init__({EID: eid})
+        self._source = graph.edata if graph is not None else {}
+
+    def __missing__(self, key):
+        src = self._source[key]               # KeyError for a key the graph does not have
+        eid = self[EID]
+        idx = eid.clamp_min(0)
+        v = src[idx.to(src.device)].to(eid.device)
+        v = v * (eid >= 0).to(v.dtype).view(eid.shape + (1,) * (v.dim() - eid.dim()))
+        self[key] = v
+        return v
+
+    def __contains__(self, key):
+        return dict.__contains__(self, key) or key in self._source
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+    def keys(self):
+        return list(dict.keys(self)) + [k for k in self._source if not dict.__contains__(self, k)]
+
+    def materialised(self):
+        """The tensors made so far (what Block.tensors() reports: a lazy entry nobody read holds no memory)."""
+        return list(dict.values(self))
+
+
 class Block(object):
     """One message-flow block: dst node d aggregates src rows nbr[d, j] >= 0 (fixed-stride form, a fixed fan-out), or
     indices[indptr[d]:indptr[d+1]] (ragged CSR form, a full layer: nbr is None).
     The first num_dst source nodes ARE the destination nodes (DGL's to_block convention)."""
 
     def __init__(self, src_nodes, nbr, num_dst, graph=None, dst_in_src=None, dst_nodes=None, owner_counts=None, owner_counts_host=None,
-                 indptr=None, indices=None):
+                 indptr=None, indices=None, eid=None, edata_graph=None):
         self.src_nodes = src_nodes          # int64 [num_src] global ids
         self.nbr = nbr                      # int32 [num_dst, fanout], -1 padded; None for a full layer
         self.indptr = indptr                # int64 [num_dst + 1] (full layer) or None
@@ -98,6 +130,9 @@ class Block(object):
         self.owner_counts_host = owner_counts_host
         self.srcdata = {"_ID": src_nodes}
         self.dstdata = {"_ID": src_nodes[: self.num_dst] if dst_nodes is None else dst_nodes}
+        # NeighborSampler(edge_ids=True): edata['_ID'] int64, shaped like nbr ([num_dst, fanout], -1 padded) or like indices ([E]), and
+        # every graph.edata entry gathered through it on first access; an empty dict otherwise
+        self.edata = _EdgeData(eid, edata_graph if edata_graph is not None else graph) if eid is not None else {}
         if graph is not None:
             for k, v in graph.ndata.items():  # blocks[-1].dstdata['labels'] (examples/sbatch_ssd_gnn_train.py:138)
                 self.dstdata[k] = v[self.dstdata["_ID"]] if v.device == src_nodes.device else v[self.dstdata["_ID"].cpu()]
@@ -119,6 +154,9 @@ class Block(object):
             for v in d.values():
                 if isinstance(v, torch.Tensor):
                     yield v
+        for v in (self.edata.materialised() if isinstance(self.edata, _EdgeData) else self.edata.values()):
+            if isinstance(v, torch.Tensor):
+                yield v
 
     def number_of_src_nodes(self):
         return self.num_src
@@ -156,6 +194,37 @@ class Block(object):
         idx = self.nbr.clamp_min(0).to(torch.int64)
         g = h_src[idx] * valid.unsqueeze(-1).to(h_src.dtype)
         return g.sum(1) / valid.sum(1).clamp_min(1).unsqueeze(-1).to(h_src.dtype)
+
+    def weighted_sum_aggregate(self, h_src, w):
+        """Sum of the sampled neighbours' rows, each times its edge's weight, for every dst node: [num_dst, dim] (DGL's u_mul_e_sum,
+        the edge_weight= path of GraphConv / SAGEConv).  w has one value per neighbour slot -- the shape of edata['_ID']: [num_dst,
+        fanout] (padding slots are not read) or [E] on a ragged block.  Native kernels, with gradients for h_src and w, under the
+        conditions of mean_aggregate (fp32 rows on the GPU; fan-out <= 32, or the ragged form); plain torch otherwise."""
+        slots = self.indices if self.nbr is None else self.nbr
+        if tuple(w.shape) != tuple(slots.shape):
+            raise ValueError(f"edge weights of shape {tuple(w.shape)}: this block takes one per neighbour slot, {tuple(slots.shape)}")
+        native = h_src.is_cuda and h_src.dtype == torch.float32 and h_src.dim() == 2 and w.is_cuda and w.dtype == torch.float32
+        if self.nbr is None:
+            if native and self.indptr.is_cuda and self.indices.is_cuda:
+                return _WeightedSumCSR.apply(h_src, w, self.indptr.contiguous(), self.indices.contiguous())
+        elif native and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
+            return _WeightedSum.apply(h_src, w, self.nbr)
+        return self.weighted_sum_aggregate_torch(h_src, w)
+
+    def weighted_sum_aggregate_torch(self, h_src, w):
+        """weighted_sum_aggregate in plain torch, any device and dtype: its fallback, and its reference."""
+        dev = h_src.device
+        w = w.to(device=dev, dtype=h_src.dtype)
+        if self.nbr is None:
+            deg = self.indptr[1:] - self.indptr[:-1]
+            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg).to(dev)
+            idx = self.indices.to(device=dev, dtype=torch.int64)
+            valid = (idx >= 0).to(h_src.dtype)
+            out = torch.zeros((self.num_dst,) + tuple(h_src.shape[1:]), dtype=h_src.dtype, device=dev)
+            return out.index_add(0, rows, h_src[idx.clamp_min(0)] * (w * valid).unsqueeze(-1))
+        valid = (self.nbr >= 0).to(device=dev, dtype=h_src.dtype)
+        idx = self.nbr.clamp_min(0).to(device=dev, dtype=torch.int64)
+        return (h_src[idx] * (w * valid).unsqueeze(-1)).sum(1)
 
     def num_src_nodes(self):   # DGL's block API (examples/models.py calls block.num_dst_nodes())
         return self.num_src
@@ -224,7 +293,7 @@ class NeighborSampler(object):
     stream_safe = True  # every kernel and allocation of sample() goes to torch's current stream
     completes_on_host = True  # sample() / sample_end() return after the host has seen the event behind the sample's last kernel (coala_sampler_wait)
 
-    def __init__(self, fanouts, seed=0, bucket_by_owner=0, prob=None):
+    def __init__(self, fanouts, seed=0, bucket_by_owner=0, prob=None, edge_ids=False):
         self.fanouts = [int(f) for f in fanouts]
         if not 1 <= len(self.fanouts) <= 8:
             raise ValueError("1..8 layers")
@@ -242,6 +311,9 @@ class NeighborSampler(object):
         # with probability proportional to it (all of them when there are at most f; never one of weight 0); a -1 layer still takes
         # every in-edge
         self.prob = prob
+        # every block carries edata: '_ID' (DGL's dgl.EID; the CSC position of each sampled edge, written by the sampling kernels) and,
+        # through it, graph.edata.  Off: edata is empty and the calls that know nothing of edge ids are made
+        self.edge_ids = bool(edge_ids)
 
     @staticmethod
     def make_graph(indptr, indices, ndata=None, edata=None):
@@ -295,8 +367,16 @@ class NeighborSampler(object):
             bk = _capi.SamplerBucketing(G, 0, bucketed.data_ptr(), counts.data_ptr(), dst_in_src.data_ptr())
             extra = (bucketed, counts, dst_in_src)
         ticket = C.c_int64(-1)
+        eid = [torch.empty(max(edge_caps[l], 1), dtype=torch.int64, device=g.device) for l in range(L)] if self.edge_ids else None
         # three launches per layer, nothing else: no host wait here (n_src_host = NULL)
-        if full or weights is not None:
+        if eid is not None:
+            lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr() if ind[l] is not None else None,
+                                                                src_caps[l], edge_caps[l]) for l in range(L)])
+            eid_p = (C.c_void_p * L)(*[t.data_ptr() for t in eid])
+            _capi.check(_lib.coala_sampler_sample_layers_edge_ids(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay,
+                                                                  weights.data_ptr() if weights is not None else None, eid_p, None, None,
+                                                                  C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
+        elif full or weights is not None:
             lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr() if ind[l] is not None else None,
                                                                 src_caps[l], edge_caps[l]) for l in range(L)])
             if weights is not None:
@@ -313,16 +393,16 @@ class NeighborSampler(object):
                                                   C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
         if step is None:
             self.step += 1
-        return (g, seeds, n, rev, src, nbr, extra, ticket.value, ind, weights)
+        return (g, seeds, n, rev, src, nbr, extra, ticket.value, ind, weights, eid)
 
     def sample_end(self, pending):
         """Wait for the counts of a sample_begin (an event wait: only for that call's kernels) and build the blocks."""
-        g, seeds, n, rev, src, nbr, extra, ticket, ind, weights = pending
+        g, seeds, n, rev, src, nbr, extra, ticket, ind, weights, eid = pending
         L, G = len(rev), self.bucket_by_owner
         n_src = (C.c_int64 * L)()
         n_edges = (C.c_int64 * L)()
         ch = (C.c_int64 * G)() if G > 0 else None
-        if -1 in rev or weights is not None:   # raises when the device refused a full layer (or the fixed layers behind it) for its size
+        if -1 in rev or weights is not None or eid is not None:   # raises when the device refused a full layer (or the fixed layers behind it) for its size
             _capi.check(_lib.coala_sampler_wait_layers(g._h, ticket, n_src, n_edges, ch))
         else:
             _capi.check(_lib.coala_sampler_wait(g._h, ticket, n_src, ch))
@@ -336,14 +416,16 @@ class NeighborSampler(object):
             if rev[l] == -1:       # ragged block: CSR over the destination nodes
                 nbr_l = None
                 csr = dict(indptr=ind[l][: n_dst + 1], indices=nbr[l][: int(n_edges[l])])
+                if eid is not None:
+                    csr["eid"] = eid[l][: int(n_edges[l])]
             else:
                 nbr_l = nbr[l][: n_dst * rev[l]].view(n_dst, rev[l])
-                csr = {}
+                csr = {} if eid is None else dict(eid=eid[l][: n_dst * rev[l]].view(n_dst, rev[l]))
             if G > 0 and l == L - 1:   # the input layer: owner-bucketed source list
-                blocks.insert(0, Block(bucketed[:ns], nbr_l, n_dst, graph=g if l == 0 else None, dst_in_src=dst_in_src[:n_dst],
+                blocks.insert(0, Block(bucketed[:ns], nbr_l, n_dst, graph=g if l == 0 else None, edata_graph=g, dst_in_src=dst_in_src[:n_dst],
                                        dst_nodes=src[l][:n_dst], owner_counts=counts, owner_counts_host=counts_host, **csr))
             else:
-                blocks.insert(0, Block(src[l][:ns], nbr_l, n_dst, graph=g if l == 0 else None, **csr))
+                blocks.insert(0, Block(src[l][:ns], nbr_l, n_dst, graph=g if l == 0 else None, edata_graph=g, **csr))
             n_dst = ns
         input_nodes = blocks[0].src_nodes
         return input_nodes, seeds, blocks

@@ -1,5 +1,6 @@
 // coala_block_ops.hip -- what a model computes on a sampled block (coala_sampler.hip makes the blocks), for gfx950: mean aggregation
-// (DGL's SAGEConv "mean") and GAT attention aggregation (GATConv's message step), forward and backward, on fixed blocks
+// (DGL's SAGEConv "mean"), weighted sum aggregation (DGL's u_mul_e_sum: GraphConv / SAGEConv with edge_weight=) and GAT attention
+// aggregation (GATConv's message step), forward and backward, on fixed blocks
 // (nbr_local[n_dst, fanout], -1 = no neighbour) and on the CSR blocks of full layers.  Stateless entry points: no handle, every
 // launch on the caller's stream.
 #include <hip/hip_runtime.h>
@@ -322,6 +323,107 @@ __global__ __launch_bounds__(kBlock) void gat_aggregate_backward_kernel(const in
     }
 }
 
+
+// Weighted sum aggregation (DGL's u_mul_e_sum, what GraphConv / SAGEConv compute with edge_weight=): out[d] = sum over the valid edges
+// j of row d of w_j * h_src[s_j], one weight per neighbour slot (w is laid out like the block's index array).  The mean kernel's
+// mapping: one wave per destination row, a lane per 16 bytes of the row, the row's indices and weights read 64 at a time (a fixed row
+// of fan-out <= 32 is one chunk) and broadcast by shuffle; the sum runs in slot order with one fma per term.  A byte mover like the
+// mean: per row it reads deg * (dim * 4 + 8) bytes and writes dim * 4.  The fixed and the CSR kernels are the same code on the same
+// lanes, so a row both forms can express gives the same bits.
+template <int VEC, typename V>
+__device__ __forceinline__ void axpy(V& acc, float a, const V& x) {
+    for (int i = 0; i < VEC; ++i) acc[i] = __builtin_fmaf(a, x[i], acc[i]);
+}
+
+template <int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void weighted_sum_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                              const float* __restrict__ w, int fanout, const float* __restrict__ h_src,
+                                                              float* __restrict__ out, int64_t n_dst, int dim) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int units = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+            const int u = u0 + lane;
+            vf acc = vf(0.0f);
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                const bool have = e0 + lane < end;
+                const int32_t mine = have ? idx[e0 + lane] : -1;
+                const float wm = have ? w[e0 + lane] : 0.0f;
+                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    const float wj = __shfl(wm, j);
+                    if (s >= 0 && u < units) axpy<VEC>(acc, wj, *reinterpret_cast<const vf*>(h_src + (int64_t)s * dim + (int64_t)u * VEC));
+                }
+            }
+            if (u < units) *reinterpret_cast<vf*>(out + d * dim + (int64_t)u * VEC) = acc;
+        }
+    }
+}
+
+// Both gradients of the weighted sum in one launch, either of them optional (null):
+//   grad_src[s_j] += w_j * grad_out[d]          hardware float atomics into a buffer the caller zeroed: summation order varies;
+//   grad_w[slot j] = <grad_out[d], h_src[s_j]>   each lane sums its 16-byte units of the row with fmas, a butterfly adds the 64 lanes
+//                                               (a fixed order), and lane j of the chunk keeps edge j's value; 0 on a padding slot.
+// One wave per row; per edge it reads the row of h_src (grad_w only) and adds into the row of grad_src; grad_out[d] stays in
+// registers when the row is at most 64 units long and comes from the cache otherwise.  Measured: with a lane per 16 bytes an atomic
+// instruction of the wave touches 64 floats 16 bytes apart, and the grad_src part runs at a quarter of the mean backward's rate
+// (361 against 89 us on the 5,5 input block at dim 1024); giving the atomics the mean backward's lane-per-float mapping is the
+// known next step (profiles/r08_edge_ids_weighted_sum.txt).
+template <int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void weighted_sum_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                       const float* __restrict__ w, int fanout, const float* __restrict__ h_src,
+                                                                       const float* __restrict__ grad_out, float* __restrict__ grad_src,
+                                                                       float* __restrict__ grad_w, int64_t n_dst, int dim) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int units = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        const float* g = grad_out + d * dim;
+        const vf g0 = lane < units ? *reinterpret_cast<const vf*>(g + (int64_t)lane * VEC) : vf(0.0f);
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
+            const bool have = e0 + lane < end;
+            const int32_t mine = have ? idx[e0 + lane] : -1;
+            const float wm = have ? w[e0 + lane] : 0.0f;
+            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+            float gw = 0.0f;
+            for (int j = 0; j < n; ++j) {
+                const int32_t s = __shfl(mine, j);
+                if (s < 0) continue; // wave-uniform
+                const float wj = __shfl(wm, j);
+                float part = 0.0f;
+                for (int u0 = 0; u0 < units; u0 += 64) {
+                    const int u = u0 + lane;
+                    if (u < units) {
+                        const vf gv = u0 == 0 ? g0 : *reinterpret_cast<const vf*>(g + (int64_t)u * VEC);
+                        const int64_t at = (int64_t)s * dim + (int64_t)u * VEC;
+                        if (grad_src)
+                            for (int i = 0; i < VEC; ++i) unsafeAtomicAdd(grad_src + at + i, wj * gv[i]);
+                        if (grad_w) {
+                            const vf hv = *reinterpret_cast<const vf*>(h_src + at);
+                            for (int i = 0; i < VEC; ++i) part = __builtin_fmaf(gv[i], hv[i], part);
+                        }
+                    }
+                }
+                if (grad_w) { // wave-uniform
+                    const float tot = wave_sum(part);
+                    if (lane == j) gw = tot;
+                }
+            }
+            if (grad_w && have) grad_w[e0 + lane] = gw;
+        }
+    }
+}
+
 } // namespace
 
 namespace {
@@ -454,6 +556,66 @@ int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, co
                        indices, 0, el, er, feat, out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim, negative_slope);
     HIPCHK(hipGetLastError());
     return COALA_OK;
+}
+
+} // extern "C"
+
+namespace {
+template <bool CSR>
+int weighted_sum_launch(int device, const int64_t* indptr, const int32_t* idx, const float* w, int fanout, const float* h_src, float* out,
+                        int64_t n_dst, int dim, void* stream) {
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !w || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
+    dispatch_vec(vec4_ok(dim, h_src, out), [&](auto vec) {
+        hipLaunchKernelGGL((weighted_sum_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, w, fanout, h_src, out,
+                           n_dst, dim);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+template <bool CSR>
+int weighted_sum_backward_launch(int device, const int64_t* indptr, const int32_t* idx, const float* w, int fanout, const float* h_src,
+                                 const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int dim, void* stream) {
+    if (n_dst == 0 || (!grad_src && !grad_w)) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !w || !grad_out || (grad_w && !h_src)) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
+    dispatch_vec(vec4_ok(dim, grad_out, grad_w ? h_src : nullptr), [&](auto vec) {
+        hipLaunchKernelGGL((weighted_sum_backward_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, w, fanout,
+                           h_src, grad_out, grad_src, grad_w, n_dst, dim);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+} // namespace
+
+extern "C" {
+
+int coala_block_weighted_sum(int device, const int32_t* nbr, const float* w, const float* h_src, float* out, int64_t n_dst, int fanout, int dim,
+                             void* stream) {
+    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+    return weighted_sum_launch<false>(device, nullptr, nbr, w, fanout, h_src, out, n_dst, dim, stream);
+}
+
+int coala_block_weighted_sum_backward(int device, const int32_t* nbr, const float* w, const float* h_src, const float* grad_out, float* grad_src,
+                                      float* grad_w, int64_t n_dst, int fanout, int dim, void* stream) {
+    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+    return weighted_sum_backward_launch<false>(device, nullptr, nbr, w, fanout, h_src, grad_out, grad_src, grad_w, n_dst, dim, stream);
+}
+
+int coala_block_weighted_sum_csr(int device, const int64_t* indptr, const int32_t* indices, const float* w, const float* h_src, float* out,
+                                 int64_t n_dst, int dim, void* stream) {
+    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
+    return weighted_sum_launch<true>(device, indptr, indices, w, 0, h_src, out, n_dst, dim, stream);
+}
+
+int coala_block_weighted_sum_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* w, const float* h_src,
+                                          const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int dim, void* stream) {
+    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
+    return weighted_sum_backward_launch<true>(device, indptr, indices, w, 0, h_src, grad_out, grad_src, grad_w, n_dst, dim, stream);
 }
 
 } // extern "C"

@@ -54,6 +54,13 @@
 //   at create time -- a row that finds the list full is scanned in place), and weighted_select_hub runs each listed row on a block
 //   of 16 waves, merging their best-f lists in LDS.  Then scan_assign / relabel_clear / bucketing run unchanged.
 //
+// Edge ids (coala_sampler_sample_layers_edge_ids), added to the contract of every layer kind above: with edge_ids_out[l] non-null the
+// kernel that reads a neighbour also stores where it read it, eid[slot] = indptr[v] + j (the edge's position in `indices`), int64,
+// laid out like the layer's nbr_local ([n_dst, f] or [E]); -1 where the slot holds no neighbour.  It is one 8-byte vector store from
+// the lane that holds the position (sample_insert, weighted_select, weighted_select_hub, full_insert), behind a wave-uniform test
+// of the pointer: no launch, no pass and no draw is added, and a null pointer leaves the kernels' memory traffic as it was.  A refused
+// layer runs over 0 items and so stores nothing.  Bucketing permutes source indices, not slots: the ids are the same with it.
+//
 // Three launches per layer, nothing else on the stream (round 1: five launches + a memset per layer, a D2H copy and a stream
 // synchronisation per call):
 //   sample_insert   draw + hash insert;
@@ -172,7 +179,7 @@ __device__ __forceinline__ void hash_insert(const Table& tb, uint32_t mask, int6
 template <int GS>
 __global__ __launch_bounds__(kBlock) void sample_insert_kernel(Graph g, const int64_t* __restrict__ dst, const int64_t* __restrict__ n_dst_dev,
                                                                int64_t n_dst_value /* used when n_dst_dev is null: the first layer */, int fanout, uint64_t seed, uint64_t step, int layer, int64_t* __restrict__ nbr,
-                                                               Table tb, uint32_t* __restrict__ slot_of_item) {
+                                                               Table tb, uint32_t* __restrict__ slot_of_item, int64_t* __restrict__ eid) {
     constexpr int GPW = 64 / GS; // groups per wave
     const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
     const uint32_t mask = table_size(n_dst * (fanout + 1)) - 1;
@@ -202,7 +209,10 @@ __global__ __launch_bounds__(kBlock) void sample_insert_kernel(Graph g, const in
         int64_t pick = -1;
         if (gl < fanout) pick = (deg <= fanout) ? (gl < deg ? (int64_t)gl : -1) : chosen;
         const int64_t nb = (okv && pick >= 0) ? g.indices[start + pick] : kEmpty;
-        if (active && gl < fanout) nbr[d * fanout + gl] = nb;
+        if (active && gl < fanout) {
+            nbr[d * fanout + gl] = nb;
+            if (eid) eid[d * fanout + gl] = nb >= 0 ? start + pick : -1;
+        }
         // ---- hash insert: neighbours at positions n_dst + d*fanout + gl, the node itself at position d
         int64_t k = kEmpty;
         int64_t p = -1;
@@ -288,7 +298,8 @@ __global__ __launch_bounds__(kBlock) void weighted_select_kernel(Graph g, const 
                                                                  const int64_t* __restrict__ n_dst_dev, int64_t n_dst_value, int fanout,
                                                                  uint64_t seed, uint64_t step, int layer, int64_t* __restrict__ nbr, Table tb,
                                                                  uint32_t* __restrict__ slot_of_item, int64_t* __restrict__ hubs,
-                                                                 unsigned long long* __restrict__ n_hubs, int64_t hub_cap) {
+                                                                 unsigned long long* __restrict__ n_hubs, int64_t hub_cap,
+                                                                 int64_t* __restrict__ eid) {
     constexpr int GPW = 64 / GS;
     const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
     const uint32_t mask = table_size(n_dst * (fanout + 1)) - 1;
@@ -324,6 +335,7 @@ __global__ __launch_bounds__(kBlock) void weighted_select_kernel(Graph g, const 
             const int64_t nb = pick >= 0 ? g.indices[start + pick] : kEmpty;
             if (active && gl < fanout) {
                 nbr[d * fanout + gl] = nb;
+                if (eid) eid[d * fanout + gl] = nb >= 0 ? start + pick : -1;
                 hash_insert(tb, mask, nb, n_dst + d * fanout + gl, slot_of_item);
             }
         }
@@ -339,7 +351,8 @@ __global__ __launch_bounds__(kHubBlock) void weighted_select_hub_kernel(Graph g,
                                                                         uint64_t seed, uint64_t step, int layer, int64_t* __restrict__ nbr,
                                                                         Table tb, uint32_t* __restrict__ slot_of_item,
                                                                         const int64_t* __restrict__ hubs,
-                                                                        const unsigned long long* __restrict__ n_hubs, int64_t hub_cap) {
+                                                                        const unsigned long long* __restrict__ n_hubs, int64_t hub_cap,
+                                                                        int64_t* __restrict__ eid) {
     __shared__ unsigned long long s_k[kHubWaves * 32];
     __shared__ int64_t s_p[kHubWaves * 32];
     const unsigned long long cnt = min(*n_hubs, (unsigned long long)hub_cap);
@@ -377,6 +390,7 @@ __global__ __launch_bounds__(kHubBlock) void weighted_select_hub_kernel(Graph g,
             if (lane < fanout) {
                 const int64_t nb = pick >= 0 ? g.indices[start + pick] : kEmpty;
                 nbr[d * fanout + lane] = nb;
+                if (eid) eid[d * fanout + lane] = nb >= 0 ? start + pick : -1;
                 hash_insert(tb, mask, nb, n_dst + d * fanout + lane, slot_of_item);
             }
         }
@@ -465,10 +479,10 @@ __global__ __launch_bounds__(kBlock) void degree_scan_kernel(Graph g, const int6
 
 // Full layer, pass 2: item p < n_dst is destination node p; item n_dst + q is edge q of the layer, whose destination a binary
 // search in indptr_local finds (load-balanced over edges: a hub's edges are spread over the whole grid).  The edge's neighbour is
-// stored (scan_assign reads it back) and inserted exactly as sample_insert_kernel inserts its items.
+// stored (scan_assign reads it back) and inserted exactly as sample_insert_kernel inserts its items; eid (nullable) takes its position.
 __global__ __launch_bounds__(kBlock) void full_insert_kernel(Graph g, const int64_t* __restrict__ dst, const int64_t* __restrict__ base,
                                                              const int64_t* __restrict__ indptr_local, int64_t* __restrict__ nbr, Table tb,
-                                                             uint32_t* __restrict__ slot_of_item) {
+                                                             uint32_t* __restrict__ slot_of_item, int64_t* __restrict__ eid) {
     const int64_t n_dst = base[0];
     const int64_t n_items = base[kItemsOff];
     const uint32_t mask = table_size(n_items) - 1;
@@ -484,8 +498,10 @@ __global__ __launch_bounds__(kBlock) void full_insert_kernel(Graph g, const int6
                 if (indptr_local[mid] <= q) lo = mid;
                 else hi = mid - 1;
             }
-            k = g.indices[g.indptr[dst[lo]] + (q - indptr_local[lo])];
+            const int64_t e = g.indptr[dst[lo]] + (q - indptr_local[lo]);
+            k = g.indices[e];
             nbr[q] = k;
+            if (eid) eid[q] = e;
         }
         hash_insert(tb, mask, k, p, slot_of_item);
     }
@@ -884,6 +900,7 @@ struct Plan {
     const coala_sampler_layer_t* layers;
     const coala_sampler_bucketing_t* bucketing;
     const float* weights; // null for uniform fixed layers, else the fp32 edge weights of weighted fixed layers (CSC order)
+    int64_t* const* edge_ids; // null, or per layer: null or device int64[edge_cap], the CSC position of every neighbour slot
     hipStream_t st;
     RingInfo info;        // n_seeds, the fan-outs, n_parts and the caller's capacities
     // layer l has at most dst_cap[l] dst nodes, items_cap[l] items (dst nodes + neighbour slots), nbr_cap[l] neighbour entries
@@ -1002,11 +1019,12 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
     const int tiles = grid1d(p.items_cap[l], kTile, kMaxTiles);
     const int64_t* rdev = full ? (const int64_t*)base : n_dst_dev; // a full layer reads n_dst and E from its base
     hipStream_t st = p.st;
+    int64_t* const eid = p.edge_ids ? p.edge_ids[l] : nullptr;
     int rc;
     int64_t max_src = 0; // full layer: the most source nodes the fixed layers behind it accept
     if (full) {
         hipLaunchKernelGGL(full_insert_kernel, dim3(grid1d(p.items_cap[l], kBlock, 8192)), blk, 0, st, s->g, dst, (const int64_t*)base,
-                           (const int64_t*)p.layers[l].indptr_local, s->nbr_global, s->tb, s->slot_of_item);
+                           (const int64_t*)p.layers[l].indptr_local, s->nbr_global, s->tb, s->slot_of_item, eid);
         int64_t unused_items = 0;
         const char* unused_what = nullptr;
         fixed_run_check(p.info, l, -1, &unused_items, &max_src, &unused_what);
@@ -1017,15 +1035,15 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
             const dim3 gs(grid1d(cap_l * GS, kBlock, 8192));
             if (p.weights)
                 hipLaunchKernelGGL(weighted_select_kernel<GS>, gs, blk, 0, st, s->g, p.weights, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l,
-                                   s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap);
+                                   s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap, eid);
             else
                 hipLaunchKernelGGL(sample_insert_kernel<GS>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l, s->nbr_global, s->tb,
-                                   s->slot_of_item);
+                                   s->slot_of_item, eid);
         });
         if (p.weights && s->hub_cap > 0) // no launch on a graph that cannot hold a row of more than kHubDegree in-edges
             hipLaunchKernelGGL(weighted_select_hub_kernel, dim3((unsigned)std::min<int64_t>(std::min<int64_t>(kHubGrid, s->hub_cap), std::max<int64_t>(cap_l, 1))),
                                dim3(kHubBlock), 0, st, s->g, p.weights, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l, s->nbr_global, s->tb,
-                               s->slot_of_item, (const int64_t*)s->hubs, (const unsigned long long*)nh, s->hub_cap);
+                               s->slot_of_item, (const int64_t*)s->hubs, (const unsigned long long*)nh, s->hub_cap, eid);
     }
     if ((rc = next_gen(s, st))) return rc;
     dispatch_bool(full, [&](auto full_c) { // a full layer: n_dst from its base, and max_src in place of the seed count
@@ -1096,7 +1114,7 @@ int launch_call(coala_sampler_t* s, Plan& p) {
 
 int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed, uint64_t step,
                 const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
-                int64_t* ticket_out, void* stream, const float* weights) {
+                int64_t* ticket_out, void* stream, const float* weights, int64_t* const* edge_ids = nullptr) {
     int rc;
     if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, layers, bucketing))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1105,7 +1123,7 @@ int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const
     // first waits there for the previous call's last kernel
     if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
     s->last_stream = st;
-    Plan p{seeds, seed, step, layers, bucketing, weights, st};
+    Plan p{seeds, seed, step, layers, bucketing, weights, edge_ids, st};
     if ((rc = plan_call(p, n_seeds, fanouts, n_layers, bucketing ? bucketing->n_parts : 0))) return rc;
     if ((rc = grow_workspace(s, p))) return rc;
     const uint64_t ticket = s->calls;
@@ -1207,6 +1225,14 @@ int coala_sampler_sample_layers_weighted(coala_sampler_t* s, const int64_t* seed
     if (!edge_weights) return fail(COALA_EINVAL, "null edge_weights");
     return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream,
                        edge_weights);
+}
+
+int coala_sampler_sample_layers_edge_ids(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                         uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const float* edge_weights,
+                                         int64_t* const* edge_ids_out, int64_t* n_src_host, int64_t* n_edges_host,
+                                         const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
+    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream,
+                       edge_weights, edge_ids_out);
 }
 
 } // extern "C"

@@ -5,6 +5,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
 
   python examples/train_synthetic.py --nodes 200000 --dim 128 --epochs 2
   python examples/train_synthetic.py --model_type gat --num_heads 4 --fan_out 5,5 --eval_fan_out=-1,-1
+  python examples/train_synthetic.py --model_type gcn --edge_weights random --use_edge_weight
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -22,7 +23,7 @@ import torch  # noqa: E402
 
 from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
-from COALA_GNN.harness import GAT, GCN, SageMean  # noqa: E402
+from COALA_GNN.harness import GAT, GCN, SAGE, SageMean  # noqa: E402
 from COALA_GNN.sampler import NeighborSampler  # noqa: E402
 from COALA_GNN.synthetic import alloc_pinned_table, powerlaw_csc  # noqa: E402
 
@@ -37,6 +38,9 @@ def main():
     ap.add_argument("--edge_weights", type=str, default="none", choices=["none", "random"],
                     help="random: seeded edge weights in (0, 1] with ~10%% zeros, sampled in proportion by the training sampler (DGL's "
                          "prob=); evaluation stays uniform")
+    ap.add_argument("--use_edge_weight", action="store_true",
+                    help="with --edge_weights random: the blocks carry their edge ids (NeighborSampler(edge_ids=True)) and the gcn / sage "
+                         "layers multiply every message by its edge's weight, block.edata['w'] (DGL's edge_weight=); gat ignores it")
     ap.add_argument("--batch_size", type=int, default=1024)
     ap.add_argument("--hidden_channels", type=int, default=128)
     ap.add_argument("--num_classes", type=int, default=19)
@@ -110,7 +114,10 @@ def main():
         w = 1.0 - torch.rand(indices.numel(), generator=gw, device=indices.device)
         w[torch.rand(indices.numel(), generator=gw, device=indices.device) < 0.1] = 0.0
         edata, prob = {"w": w}, "w"
-    sampler = NeighborSampler(fan_out, prob=prob)                                                           # :70-72
+    if args.use_edge_weight and prob is None:
+        ap.error("--use_edge_weight needs --edge_weights random")
+    ew = "w" if args.use_edge_weight and args.model_type != "gat" else None
+    sampler = NeighborSampler(fan_out, prob=prob, edge_ids=ew is not None)                                  # :70-72
     g = sampler.make_graph(indptr, indices, ndata={"labels": labels}, edata=edata)
     train_loader = COALA_GNN_DataLoader(SSD_INFO(1, args.dim * 4, 1024, 0), nd, g, sampler, args.batch_size, args.dim, fan_out,
                                         args.cache_size, device, refresh_counter=args.refresh_counter,
@@ -119,7 +126,9 @@ def main():
     if args.model_type == "gat":                                                                            # :220-231
         model = GAT(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads).to(device)
     elif args.model_type == "gcn":
-        model = GCN(args.dim, args.hidden_channels, args.num_classes, len(fan_out)).to(device)
+        model = GCN(args.dim, args.hidden_channels, args.num_classes, len(fan_out), edge_weight=ew).to(device)
+    elif ew is not None:
+        model = SAGE(args.dim, args.hidden_channels, args.num_classes, len(fan_out), edge_weight=ew).to(device)
     else:
         model = SageMean(args.dim, args.hidden_channels, args.num_classes, len(fan_out)).to(device)
     if comm.global_size > 1:
@@ -156,7 +165,7 @@ def main():
 
     # evaluation over the test nodes through a second loader, as the reference does (:156-195)
     test_nd = Node_Distributor(comm, test_ids, args.batch_size, *files, parsing_method=args.distribution)
-    eval_sampler = sampler if eval_fan_out == fan_out and prob is None else NeighborSampler(eval_fan_out)
+    eval_sampler = sampler if eval_fan_out == fan_out and prob is None else NeighborSampler(eval_fan_out, edge_ids=ew is not None)
     test_loader = COALA_GNN_DataLoader(SSD_INFO(1, args.dim * 4, 1024, 0), test_nd, g, eval_sampler, args.batch_size, args.dim, eval_fan_out,
                                        args.cache_size, device, refresh_counter=args.refresh_counter,
                                        cache_backend=args.cache_backend, sim_buf=feat, shuffle=False, num_rows=args.nodes)

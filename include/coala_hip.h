@@ -400,6 +400,19 @@ int coala_sampler_sample_layers_weighted(coala_sampler_t* s, const int64_t* seed
                                          uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const float* edge_weights,
                                          int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
                                          int64_t* ticket_out, void* stream);
+/* As coala_sampler_sample_layers (edge_weights NULL) or coala_sampler_sample_layers_weighted (edge_weights given), and additionally
+ * the CSC position of every sampled edge.  edge_ids_out: NULL, or an array of n_layers device pointers, each NULL (not wanted) or
+ * int64[edge_cap of that layer], laid out exactly like the layer's nbr_local (fixed layer: [n_dst, f]; full layer: [E]).  Entry
+ * (d, j) is the position e in the graph's `indices` array of the edge that slot holds -- indptr[v_d] <= e < indptr[v_d + 1] and
+ * indices[e] is the neighbour -- and -1 where nbr_local is -1.  The ids of a fixed row are pairwise distinct (the draw is without
+ * replacement), which tells repeated edges apart; a full row's ids are indptr[v] .. indptr[v + 1] - 1 in order.  The draw, the source
+ * lists, nbr_local, indptr_local, the capacities, the refusals and the ticket / wait protocol are those of the calls above, bit for
+ * bit for the same (seed, step); a refused layer writes nothing to its edge_ids_out.  The ids are stored by the kernels that read the
+ * neighbours (one 8-byte store per slot): no launch is added, and a NULL array or entry costs nothing. */
+int coala_sampler_sample_layers_edge_ids(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                         uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const float* edge_weights,
+                                         int64_t* const* edge_ids_out, int64_t* n_src_host, int64_t* n_edges_host,
+                                         const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream);
 /* Counts of an earlier call, with the edge counts of its layers; returns the device-side refusal of a full layer, if any. */
 int coala_sampler_wait_layers(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host);
 
@@ -417,6 +430,26 @@ int coala_block_mean_aggregate_csr(int device, const int64_t* indptr, const int3
                                    int dim, void* stream);
 int coala_block_mean_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* grad_out, float* grad_src,
                                             int64_t n_dst, int dim, void* stream);
+/* Weighted sum aggregation (DGL's u_mul_e_sum: GraphConv / SAGEConv with edge_weight=): out[d, :] = sum over the valid j of
+ * w[d, j] * h_src[nbr[d, j], :]; nbr int32 [n_dst, fanout] (-1 padded, fan-out 1..32), w fp32 [n_dst, fanout] (one weight per slot; a
+ * padding slot's weight is not used), fp32 rows of `dim` floats; a row without a valid entry gives zeros.  The CSR form sums
+ * w[e] * h_src[indices[e]] over e in [indptr[d], indptr[d+1]) in that order (w fp32 [E]), one wave per row.  The sum runs in slot order
+ * with one fma per term, and both forms run the same code: bit-identical on any row both can express.  Bad shapes are refused with
+ * COALA_EINVAL and nothing is launched.
+ * Backward, both gradients in one launch, either output may be NULL (not wanted):
+ *   grad_src[s_j, :] += w_j * grad_out[d, :]        hardware float atomics: the caller zeroes grad_src [n_src, dim], the order varies;
+ *   grad_w[d, j] = <grad_out[d, :], h_src[s_j, :]>   shaped like w, written whole, 0 on a padding slot; deterministic, and the same bits
+ *                                                   in both forms.  h_src is read only when grad_w is given.
+ * Bytes per row of deg valid edges: forward reads deg * (4 dim + 8) and writes 4 dim; backward reads 4 dim + 8 deg (+ 4 dim deg for
+ * grad_w), adds 4 dim deg through atomics and writes 4 per slot. */
+int coala_block_weighted_sum(int device, const int32_t* nbr, const float* w, const float* h_src, float* out, int64_t n_dst, int fanout, int dim,
+                             void* stream);
+int coala_block_weighted_sum_backward(int device, const int32_t* nbr, const float* w, const float* h_src, const float* grad_out, float* grad_src,
+                                      float* grad_w, int64_t n_dst, int fanout, int dim, void* stream);
+int coala_block_weighted_sum_csr(int device, const int64_t* indptr, const int32_t* indices, const float* w, const float* h_src, float* out,
+                                 int64_t n_dst, int dim, void* stream);
+int coala_block_weighted_sum_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* w, const float* h_src,
+                                          const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int dim, void* stream);
 /* GAT attention aggregation (DGL GATConv's message step; its projections are dense and stay outside).  For dst d, head h and the
  * valid in-edges j of d with source s_j:
  *   z_j = el[s_j, h] + er[d, h];  e_j = leaky_relu(z_j, negative_slope);  a_j = exp(e_j - m) / sum_k exp(e_k - m), m = max_k e_k;
