@@ -13,7 +13,7 @@ from COALA_GNN_Pybind import _capi, current_stream
 
 from .block_ops import _GatAggregate, _GatAggregateCSR, _MeanAggregate, _MeanAggregateCSR, _WeightedSum, _WeightedSumCSR
 
-__all__ = ["NeighborSampler", "CSCGraph", "Block", "ITEM_LIMIT", "EID"]
+__all__ = ["NeighborSampler", "LaborSampler", "CSCGraph", "Block", "ITEM_LIMIT", "EID"]
 
 _lib = _capi.load()
 
@@ -81,13 +81,19 @@ class CSCGraph(object):
 
 class _EdgeData(dict):
     """block.edata of a block sampled with NeighborSampler(edge_ids=True): holds '_ID' (the CSC position of every neighbour slot, -1
-    on padding); every other key of graph.edata is gathered through it on first access -- padding slots give 0 -- and kept."""
+    on padding); every other key of graph.edata is gathered through it on first access -- padding slots give 0 -- and kept.
+    `lazy` (key -> function of no arguments) holds entries the sampler computes itself on first access (LaborSampler's
+    'edge_weights'); they come before graph.edata, and they exist without edge ids (eid None: no '_ID', nothing gathered)."""
 
-    def __init__(self, eid, graph):
-        super().__init__({EID: eid})
-        self._source = graph.edata if graph is not None else {}
+    def __init__(self, eid, graph, lazy=None):
+        super().__init__({EID: eid} if eid is not None else {})
+        self._source = graph.edata if graph is not None and eid is not None else {}
+        self._lazy = dict(lazy or {})
 
     def __missing__(self, key):
+        if key in self._lazy:
+            v = self[key] = self._lazy[key]()
+            return v
         src = self._source[key]               # KeyError for a key the graph does not have
         eid = self[EID]
         idx = eid.clamp_min(0)
@@ -97,13 +103,14 @@ class _EdgeData(dict):
         return v
 
     def __contains__(self, key):
-        return dict.__contains__(self, key) or key in self._source
+        return dict.__contains__(self, key) or key in self._lazy or key in self._source
 
     def get(self, key, default=None):
         return self[key] if key in self else default
 
     def keys(self):
-        return list(dict.keys(self)) + [k for k in self._source if not dict.__contains__(self, k)]
+        own = list(dict.keys(self)) + [k for k in self._lazy if not dict.__contains__(self, k)]
+        return own + [k for k in self._source if k not in own]
 
     def materialised(self):
         """The tensors made so far (what Block.tensors() reports: a lazy entry nobody read holds no memory)."""
@@ -116,7 +123,7 @@ class Block(object):
     The first num_dst source nodes ARE the destination nodes (DGL's to_block convention)."""
 
     def __init__(self, src_nodes, nbr, num_dst, graph=None, dst_in_src=None, dst_nodes=None, owner_counts=None, owner_counts_host=None,
-                 indptr=None, indices=None, eid=None, edata_graph=None):
+                 indptr=None, indices=None, eid=None, edata_graph=None, edata_lazy=None):
         self.src_nodes = src_nodes          # int64 [num_src] global ids
         self.nbr = nbr                      # int32 [num_dst, fanout], -1 padded; None for a full layer
         self.indptr = indptr                # int64 [num_dst + 1] (full layer) or None
@@ -131,8 +138,9 @@ class Block(object):
         self.srcdata = {"_ID": src_nodes}
         self.dstdata = {"_ID": src_nodes[: self.num_dst] if dst_nodes is None else dst_nodes}
         # NeighborSampler(edge_ids=True): edata['_ID'] int64, shaped like nbr ([num_dst, fanout], -1 padded) or like indices ([E]), and
-        # every graph.edata entry gathered through it on first access; an empty dict otherwise
-        self.edata = _EdgeData(eid, edata_graph if edata_graph is not None else graph) if eid is not None else {}
+        # every graph.edata entry gathered through it on first access; LaborSampler: 'edge_weights', computed on first access, with or
+        # without edge ids; an empty dict otherwise
+        self.edata = _EdgeData(eid, edata_graph if edata_graph is not None else graph, edata_lazy) if eid is not None or edata_lazy else {}
         if graph is not None:
             for k, v in graph.ndata.items():  # blocks[-1].dstdata['labels'] (examples/sbatch_ssd_gnn_train.py:138)
                 self.dstdata[k] = v[self.dstdata["_ID"]] if v.device == src_nodes.device else v[self.dstdata["_ID"].cpu()]
@@ -330,18 +338,19 @@ class NeighborSampler(object):
         if isinstance(g, tuple):
             g = CSCGraph(*g)
         weights = g.edge_weights(self.prob) if self.prob is not None else None   # raises before any launch
+        ragged = self._ragged
         seeds = seed_nodes.to(g.device, dtype=torch.int64).contiguous()
         n = seeds.numel()
         rev = list(reversed(self.fanouts))          # DGL samples the output layer first
         L = len(rev)
-        full = -1 in rev
+        full = any(ragged(f) for f in rev)
         # capacities (include/coala_hip.h, coala_sampler_layer_t): exact host bounds up to the first full layer; a full layer holds
         # at most cap * max_in_degree edges and never more than ITEM_LIMIT items, which bounds every layer behind it
         caps, src_caps, edge_caps = [n], [], []
         bounded = False
         for f in rev:
             cap = caps[-1]
-            if f == -1:
+            if ragged(f):   # a LABOR layer takes ~cap * f edges, but only the device knows: the bound is the full layer's
                 edge_caps.append(min(cap * g.max_in_degree, ITEM_LIMIT))
                 src_caps.append(min(cap + edge_caps[-1], ITEM_LIMIT))
                 bounded = True
@@ -354,7 +363,7 @@ class NeighborSampler(object):
             caps.append(src_caps[-1])
         src = [torch.empty(max(src_caps[l], 1), dtype=torch.int64, device=g.device) for l in range(L)]
         nbr = [torch.empty(max(edge_caps[l], 1), dtype=torch.int32, device=g.device) for l in range(L)]
-        ind = [torch.empty(caps[l] + 1, dtype=torch.int64, device=g.device) if rev[l] == -1 else None for l in range(L)]
+        ind = [torch.empty(caps[l] + 1, dtype=torch.int64, device=g.device) if ragged(rev[l]) else None for l in range(L)]
         fan = (C.c_int32 * L)(*rev)
         st = self.step if step is None else int(step)
         G = self.bucket_by_owner
@@ -369,6 +378,17 @@ class NeighborSampler(object):
         ticket = C.c_int64(-1)
         eid = [torch.empty(max(edge_caps[l], 1), dtype=torch.int64, device=g.device) for l in range(L)] if self.edge_ids else None
         # three launches per layer, nothing else: no host wait here (n_src_host = NULL)
+        self._enqueue(g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket)
+        if step is None:
+            self.step += 1
+        return (g, seeds, n, rev, src, nbr, extra, ticket.value, ind, weights, eid)
+
+    def _ragged(self, f):
+        """Whether a layer of fan-out f gives a ragged (CSR) block, whose size only the device knows."""
+        return f == -1
+
+    def _enqueue(self, g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket):
+        """The C ABI call of sample_begin, on the current stream."""
         if eid is not None:
             lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr() if ind[l] is not None else None,
                                                                 src_caps[l], edge_caps[l]) for l in range(L)])
@@ -376,7 +396,7 @@ class NeighborSampler(object):
             _capi.check(_lib.coala_sampler_sample_layers_edge_ids(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay,
                                                                   weights.data_ptr() if weights is not None else None, eid_p, None, None,
                                                                   C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
-        elif full or weights is not None:
+        elif any(t is not None for t in ind) or weights is not None:
             lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr() if ind[l] is not None else None,
                                                                 src_caps[l], edge_caps[l]) for l in range(L)])
             if weights is not None:
@@ -391,9 +411,6 @@ class NeighborSampler(object):
             nbr_p = (C.c_void_p * L)(*[t.data_ptr() for t in nbr])
             _capi.check(_lib.coala_sampler_sample(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, src_p, nbr_p, None,
                                                   C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
-        if step is None:
-            self.step += 1
-        return (g, seeds, n, rev, src, nbr, extra, ticket.value, ind, weights, eid)
 
     def sample_end(self, pending):
         """Wait for the counts of a sample_begin (an event wait: only for that call's kernels) and build the blocks."""
@@ -402,7 +419,7 @@ class NeighborSampler(object):
         n_src = (C.c_int64 * L)()
         n_edges = (C.c_int64 * L)()
         ch = (C.c_int64 * G)() if G > 0 else None
-        if -1 in rev or weights is not None or eid is not None:   # raises when the device refused a full layer (or the fixed layers behind it) for its size
+        if any(t is not None for t in ind) or weights is not None or eid is not None:   # raises when the device refused a full layer (or the fixed layers behind it) for its size
             _capi.check(_lib.coala_sampler_wait_layers(g._h, ticket, n_src, n_edges, ch))
         else:
             _capi.check(_lib.coala_sampler_wait(g._h, ticket, n_src, ch))
@@ -413,9 +430,9 @@ class NeighborSampler(object):
         n_dst = n
         for l in range(L):
             ns = int(n_src[l])
-            if rev[l] == -1:       # ragged block: CSR over the destination nodes
+            if ind[l] is not None:   # ragged block: CSR over the destination nodes
                 nbr_l = None
-                csr = dict(indptr=ind[l][: n_dst + 1], indices=nbr[l][: int(n_edges[l])])
+                csr = dict(indptr=ind[l][: n_dst + 1], indices=nbr[l][: int(n_edges[l])], **self._block_extras(ind[l][: n_dst + 1], int(n_edges[l]), rev[l]))
                 if eid is not None:
                     csr["eid"] = eid[l][: int(n_edges[l])]
             else:
@@ -429,3 +446,48 @@ class NeighborSampler(object):
             n_dst = ns
         input_nodes = blocks[0].src_nodes
         return input_nodes, seeds, blocks
+
+    def _block_extras(self, indptr, n_edges, f):
+        """More Block arguments for a ragged layer of fan-out f."""
+        return {}
+
+
+class LaborSampler(NeighborSampler):
+    """Layer-neighbour sampling, DGL's dgl.dataloading.LaborSampler with importance_sampling=0 (Balin & Catalyurek, "Layer-Neighbor
+    Sampling -- Defusing Neighborhood Explosion in GNNs", NeurIPS 2023), in place of NeighborSampler: same interface, same loader.
+    A layer draws one random number per SOURCE node and shares it among its destination nodes, so destination nodes with a common
+    neighbour agree on taking it: every row still holds `fanout` neighbours in expectation (all of them when it has no more), but
+    the batch has fewer distinct input nodes to fetch.  The rule is in the header of coala_sampler.hip.
+
+    Every block is ragged (Block.indptr / Block.indices, nbr is None), whatever the fan-out; -1 is the full layer of NeighborSampler.
+    block.edata['edge_weights'] (fp32 [E], made on first access) is 1 / in_degree(d) of the edge's row in the block, DGL's
+    Hajek-normalised weight -- all taken edges of a LABOR-0 row have the same inclusion probability.
+    layer_dependency=True uses the same random numbers in every layer of a call (DGL's option of that name).
+    A row's length is random, so the buffers are those of a full layer (cap * max_in_degree edges, at most ITEM_LIMIT items); the
+    loader sizes its fetch buffers from its fan_out argument as batch * prod(f + 1), the bound of NeighborSampler's input nodes."""
+
+    def __init__(self, fanouts, seed=0, bucket_by_owner=0, edge_ids=False, layer_dependency=False, importance_sampling=0, prob=None):
+        if prob is not None:
+            raise ValueError("LaborSampler: prob= (weighted LABOR) is not supported")
+        if importance_sampling != 0:
+            raise ValueError(f"LaborSampler: importance_sampling={importance_sampling!r} is not supported, only 0 (LABOR-0)")
+        super().__init__(fanouts, seed=seed, bucket_by_owner=bucket_by_owner, edge_ids=edge_ids)
+        self.layer_dependency = bool(layer_dependency)
+        self.importance_sampling = 0
+
+    def _ragged(self, f):
+        return True
+
+    def _enqueue(self, g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket):
+        lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr(), src_caps[l], edge_caps[l])
+                                         for l in range(L)])
+        eid_p = (C.c_void_p * L)(*[t.data_ptr() for t in eid]) if eid is not None else None
+        _capi.check(_lib.coala_sampler_sample_layers_labor(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, eid_p, int(self.layer_dependency),
+                                                           None, None, C.byref(bk) if bk is not None else None, C.byref(ticket),
+                                                           current_stream()))
+
+    def _block_extras(self, indptr, n_edges, f):
+        def edge_weights():
+            deg = indptr[1:] - indptr[:-1]
+            return torch.repeat_interleave(1.0 / deg.to(torch.float32), deg, output_size=n_edges)
+        return dict(edata_lazy={"edge_weights": edge_weights})

@@ -54,6 +54,27 @@
 //   at create time -- a row that finds the list full is scanned in place), and weighted_select_hub runs each listed row on a block
 //   of 16 waves, merging their best-f lists in LDS.  Then scan_assign / relabel_clear / bucketing run unchanged.
 //
+// LABOR layers (DGL's LaborSampler(fanouts, importance_sampling=0), Balin & Catalyurek, NeurIPS 2023; coala_sampler_sample_layers_labor),
+// fan-out k in 1..32.  One random number per SOURCE node, shared by every destination node of the layer: destination nodes with a
+// common neighbour agree on taking it, so the source list shrinks while a row still holds k neighbours in expectation.
+//   * labor_key(seed, step, layer) = splitmix64(splitmix64(seed ^ 0x9E3779B97F4A7C15 * (layer + 1)) ^ step * 0xD1B54A32D192ED03)
+//     ^ kLaborStream: the two outer rounds of sample_key and a stream constant of its own, so a LABOR layer never replays the draws
+//     of a uniform or weighted layer.  With layer_dependency the layer index is dropped (the first round hashes `seed` alone): every
+//     layer of the call then sees the same r_t;
+//   * r_t = splitmix64(labor_key ^ (uint64)t) for source node t;
+//   * destination node v with in-degree deg: deg <= k takes every in-edge (the uniform path's rule); otherwise the in-edge at CSC
+//     position e = indptr[v] + j with t = indices[e] is taken iff mulhi64(r_t, (uint64)deg) < k -- probability ceil(k 2^64 / deg) /
+//     2^64, exact integer arithmetic; repeated edges t -> v are taken or left together; r_t depends on neither v nor j;
+//   * the block is ragged, as a full layer's: taken edges in ascending CSC position inside a row, rows in destination order,
+//     indptr_local int64[n_dst + 1], nbr_local int32[E]; source list, first appearance, item limit (n_dst + E, E known on the device
+//     only), refusal and bucketing are those of a full layer; an out-of-range destination id gives an empty row; a -1 layer of a
+//     LABOR list is the full layer above.
+//   Launches: labor_count_scan stands where degree_scan stands (a lane group per row counts its taken edges with ballots, a row of
+//   more than kHubDegree in-edges is counted by the whole block; then degree_scan's tile-ticket scan, capacity check and count
+//   words), labor_insert where full_insert stands (the same test again, survivors compacted to indptr_local[d] + rank by ballot
+//   prefix, stored with their edge id when asked and hash-inserted; a hub row again on the whole block), then scan_assign /
+//   relabel_clear in their full-layer instantiations and the bucketing kernels, unchanged.  No launch, memset or host wait is added.
+//
 // Edge ids (coala_sampler_sample_layers_edge_ids), added to the contract of every layer kind above: with edge_ids_out[l] non-null the
 // kernel that reads a neighbour also stores where it read it, eid[slot] = indptr[v] + j (the edge's position in `indices`), int64,
 // laid out like the layer's nbr_local ([n_dst, f] or [E]); -1 where the slot holds no neighbour.  It is one 8-byte vector store from
@@ -507,6 +528,243 @@ __global__ __launch_bounds__(kBlock) void full_insert_kernel(Graph g, const int6
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------- LABOR layers
+constexpr uint64_t kLaborStream = 0xBB67AE8584CAA73Bull; // xor on the two outer rounds of sample_key: the LABOR draws' own stream
+constexpr int kLaborGroup = 16;                           // lanes per destination row
+constexpr int kLaborHubList = 32;                         // hub rows a block defers per pass; one more is counted by its group
+
+__host__ __device__ inline uint64_t labor_key(uint64_t seed, uint64_t step, int layer, bool layer_dependency) {
+    uint64_t h = splitmix64(layer_dependency ? seed : seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(layer + 1)));
+    h = splitmix64(h ^ (step * 0xD1B54A32D192ED03ull));
+    return h ^ kLaborStream;
+}
+
+// The LABOR test of an in-edge from source node t into a row of deg in-edges.
+__device__ __forceinline__ bool labor_take(uint64_t lkey, int64_t t, int64_t deg, int fanout) {
+    return deg <= fanout || __umul64hi(splitmix64(lkey ^ (uint64_t)t), (uint64_t)deg) < (uint64_t)fanout;
+}
+
+// Taken edges among positions [from, to) of a row, by one wave: the wave-uniform total (trip count and ballots are wave-uniform).
+__device__ __forceinline__ uint32_t labor_wave_count(const Graph& g, uint64_t lkey, int64_t start, int64_t deg, int fanout, int64_t from,
+                                                     int64_t to, int lane) {
+    uint32_t n = 0;
+    for (int64_t c0 = from; c0 < to; c0 += 64) {
+        const int64_t j = c0 + lane;
+        const bool take = j < to && labor_take(lkey, g.indices[start + j], deg, fanout);
+        n += (uint32_t)__builtin_popcountll(__ballot(take));
+    }
+    return n;
+}
+
+// LABOR layer, pass 1, where degree_scan_kernel stands: the count of taken edges of every destination node -> indptr_local
+// (exclusive scan) and E.  A tile is `rows` destination nodes (a power of two, 64 .. kTile, chosen by the host so that the layer's
+// capacity fits kMaxTiles tiles: small tiles spread the edge reads of a small batch over many blocks).  kLaborGroup lanes count a
+// row, 64 / kLaborGroup rows per wave step; a row of more than kHubDegree in-edges is put on the block's list and counted by all its
+// waves afterwards.  Then the scan, the capacity check and the published words of degree_scan_kernel, over the counts in LDS.
+__global__ __launch_bounds__(kBlock) void labor_count_scan_kernel(Graph g, const int64_t* __restrict__ dst, const int64_t* __restrict__ n_dst_dev,
+                                                                  int64_t n_dst_value, int rows, int fanout, uint64_t lkey,
+                                                                  int64_t* __restrict__ base, unsigned long long* __restrict__ status,
+                                                                  unsigned long long* __restrict__ ticket, unsigned long long ticket_base,
+                                                                  unsigned long long gen, int64_t* __restrict__ indptr_local, int64_t item_cap,
+                                                                  int64_t edge_cap, int64_t* __restrict__ pin) {
+    constexpr int GS = kLaborGroup, GPB = kBlock / GS;
+    __shared__ uint32_t s_cnt[kTile];
+    __shared__ int s_hub[kLaborHubList];
+    __shared__ int s_nhub;
+    __shared__ uint32_t s_woff[kWavesPerBlock];
+    __shared__ unsigned long long s_tile;
+    __shared__ uint32_t s_prefix;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
+    const int64_t n_tiles = n_dst > 0 ? (n_dst + rows - 1) / rows : 1; // tile 0 always runs: it publishes an empty layer too
+    if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1ull) - ticket_base;
+    __syncthreads();
+    const int64_t tile = (int64_t)s_tile;
+    if (tile >= n_tiles) return;
+    const int64_t row0 = tile * rows;
+    // ---- counts of the tile's rows
+    const int gl = lane % GS, gbase = lane - gl;
+    const uint64_t gmask = ((1ull << GS) - 1ull) << gbase;
+    for (int r0 = 0; r0 < rows; r0 += GPB * kLaborHubList) { // block-uniform: the list holds the hubs of one stretch of rows
+        if (threadIdx.x == 0) s_nhub = 0;
+        __syncthreads();
+        const int r_end = min(rows, r0 + GPB * kLaborHubList);
+        for (int r = r0 + (int)threadIdx.x / GS; r < r_end; r += GPB) { // wave-uniform trip count: r0, r_end are multiples of GPB
+            const int64_t d = row0 + r;
+            const int64_t v = d < n_dst ? dst[d] : -1;
+            const bool okv = v >= 0 && v < g.num_nodes;
+            const int64_t start = okv ? g.indptr[v] : 0;
+            int64_t deg = okv ? g.indptr[v + 1] - start : 0;
+            int at = kLaborHubList;
+            if (gl == 0 && deg > kHubDegree) at = atomicAdd(&s_nhub, 1);
+            at = __shfl(at, gbase);
+            if (at < kLaborHubList) { // deferred to the whole block; a row that finds the list full is counted here
+                if (gl == 0) s_hub[at] = r;
+                deg = 0;
+            }
+            uint32_t n = 0;
+            int64_t longest = deg; // the wave's rows run in step
+            for (int off = GS; off < 64; off <<= 1) longest = max(longest, __shfl_xor(longest, off));
+            for (int64_t c0 = 0; c0 < longest; c0 += GS) {
+                const int64_t j = c0 + gl;
+                const bool take = j < deg && labor_take(lkey, g.indices[start + j], deg, fanout);
+                n += (uint32_t)__builtin_popcountll(__ballot(take) & gmask);
+            }
+            if (gl == 0) s_cnt[r] = n; // a deferred row: 0 for now
+        }
+        __syncthreads();
+        const int n_hub = min(s_nhub, kLaborHubList);
+        for (int i = 0; i < n_hub; ++i) { // block-uniform: every wave counts its share of the row
+            const int r = s_hub[i];
+            const int64_t v = dst[row0 + r];
+            const int64_t start = g.indptr[v];
+            const int64_t deg = g.indptr[v + 1] - start;
+            const int64_t seg = ((deg + kWavesPerBlock - 1) / kWavesPerBlock + 63) & ~63ll;
+            const uint32_t n = labor_wave_count(g, lkey, start, deg, fanout, min(deg, w * seg), min(deg, (w + 1) * seg), lane);
+            if (lane == 0 && n) atomicAdd(&s_cnt[r], n);
+        }
+        __syncthreads();
+    }
+    // ---- degree_scan_kernel's scan over the counts
+    const int at = (int)threadIdx.x * kItems;
+    const int64_t first = row0 + at;
+    uint32_t dg[kItems];
+    uint32_t c = 0;
+    for (int i = 0; i < kItems; ++i) {
+        dg[i] = (at + i < rows && first + i < n_dst) ? s_cnt[at + i] : 0;
+        c = sat_add(c, dg[i]);
+    }
+    uint32_t incl = c; // inclusive scan inside the wave
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t v = __shfl_up(incl, off);
+        if (lane >= off) incl = sat_add(incl, v);
+    }
+    if (lane == 63) s_woff[w] = incl;
+    __syncthreads();
+    uint32_t wbase = 0, total = 0;
+    for (int q = 0; q < kWavesPerBlock; ++q) {
+        if (q < w) wbase = sat_add(wbase, s_woff[q]);
+        total = sat_add(total, s_woff[q]);
+    }
+    if (threadIdx.x == 0) {
+        const unsigned long long tag = gen << 34;
+        uint32_t prefix = 0;
+        if (tile > 0) {
+            __hip_atomic_store(status + tile, tag | kAggregate | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int64_t t = tile - 1; t >= 0;) { // decoupled look-back
+                const unsigned long long v = __hip_atomic_load(status + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if ((v >> 34) != gen || !(v & (kAggregate | kInclusive))) { __builtin_amdgcn_s_sleep(1); continue; } // not published yet
+                prefix = sat_add(prefix, (uint32_t)v);
+                if (v & kInclusive) break;
+                --t;
+            }
+        }
+        __hip_atomic_store(status + tile, tag | kInclusive | sat_add(prefix, total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_prefix = prefix;
+        if (tile == n_tiles - 1) { // the layer's totals, and the capacity check
+            const int64_t edges = (int64_t)sat_add(prefix, total);
+            const int64_t items = n_dst + edges;
+            const bool ok = items <= item_cap && edges <= edge_cap;
+            indptr_local[n_dst] = edges;
+            if (!n_dst_dev) base[0] = n_dst;
+            base[kItemsOff] = ok ? items : 0;
+            base[kEdgesOff] = ok ? edges : 0;
+            pin[kPinEdges] = edges;
+            pin[kPinRefused] = ok ? 0 : 1;
+        }
+    }
+    __syncthreads();
+    uint32_t run = sat_add(s_prefix, sat_add(wbase, incl - c));
+    for (int i = 0; i < kItems; ++i) {
+        if (at + i < rows && first + i < n_dst) indptr_local[first + i] = (int64_t)run;
+        run = sat_add(run, dg[i]);
+    }
+}
+
+// Edge at position j of row d passed the test (take) or not: the survivors of the lanes in `among` go to slots slot0 + rank, rank by
+// ballot prefix; the neighbour is stored (scan_assign reads it back), its edge id when asked, and it is inserted at item position
+// n_dst + slot.  Returns the number of survivors among the lanes.  Every lane of the wave must call it.
+__device__ __forceinline__ uint32_t labor_emit(bool take, uint64_t among, int lane, int64_t t, int64_t e, int64_t slot0, int64_t n_dst,
+                                               int64_t* __restrict__ nbr, int64_t* __restrict__ eid, const Table& tb, uint32_t mask,
+                                               uint32_t* __restrict__ slot_of_item) {
+    const uint64_t m = __ballot(take) & among;
+    if (take) {
+        const int64_t q = slot0 + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+        nbr[q] = t;
+        if (eid) eid[q] = e;
+        hash_insert(tb, mask, t, n_dst + q, slot_of_item);
+    }
+    return (uint32_t)__builtin_popcountll(m);
+}
+
+// LABOR layer, pass 2, where full_insert_kernel stands: item p < n_dst is destination node p; item n_dst + q is taken edge q of the
+// layer.  kLaborGroup lanes walk a row, evaluate the test again and compact the survivors into the row's segment of nbr, which starts
+// at indptr_local[d]; a block takes kBlock / kLaborGroup rows per step, and the rows of more than kHubDegree in-edges among them are
+// then done by the whole block: every wave counts its contiguous share, the shares are ranked through LDS, and a second walk emits.
+// A refused layer (0 items) does nothing.
+__global__ __launch_bounds__(kBlock) void labor_insert_kernel(Graph g, const int64_t* __restrict__ dst, const int64_t* __restrict__ base,
+                                                              const int64_t* __restrict__ indptr_local, int fanout, uint64_t lkey,
+                                                              int64_t* __restrict__ nbr, Table tb, uint32_t* __restrict__ slot_of_item,
+                                                              int64_t* __restrict__ eid) {
+    constexpr int GS = kLaborGroup, GPB = kBlock / GS;
+    __shared__ int64_t s_hub[GPB];
+    __shared__ int s_nhub;
+    __shared__ uint32_t s_wcnt[kWavesPerBlock];
+    const int64_t n_dst = base[0];
+    const int64_t n_items = base[kItemsOff];
+    if (n_items == 0) return;
+    const uint32_t mask = table_size(n_items) - 1;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int gl = lane % GS, gbase = lane - gl;
+    const uint64_t gmask = ((1ull << GS) - 1ull) << gbase;
+    for (int64_t d0 = (int64_t)blockIdx.x * GPB; d0 < n_dst; d0 += (int64_t)gridDim.x * GPB) { // block-uniform
+        if (threadIdx.x == 0) s_nhub = 0;
+        __syncthreads();
+        const int64_t d = d0 + (int)threadIdx.x / GS;
+        const bool active = d < n_dst;
+        const int64_t v = active ? dst[d] : -1;
+        const bool okv = v >= 0 && v < g.num_nodes;
+        const int64_t start = okv ? g.indptr[v] : 0;
+        int64_t deg = okv ? g.indptr[v + 1] - start : 0;
+        if (deg > kHubDegree) { // at most GPB of them: the list cannot fill up
+            if (gl == 0) s_hub[atomicAdd(&s_nhub, 1)] = d;
+            deg = 0;
+        }
+        if (active && gl == 0) hash_insert(tb, mask, v, d, slot_of_item);
+        int64_t slot = deg > 0 ? indptr_local[d] : 0;
+        int64_t longest = deg;
+        for (int off = GS; off < 64; off <<= 1) longest = max(longest, __shfl_xor(longest, off));
+        for (int64_t c0 = 0; c0 < longest; c0 += GS) { // wave-uniform
+            const int64_t j = c0 + gl;
+            const int64_t t = j < deg ? g.indices[start + j] : -1;
+            const bool take = j < deg && labor_take(lkey, t, deg, fanout);
+            slot += labor_emit(take, gmask, lane, t, start + j, slot, n_dst, nbr, eid, tb, mask, slot_of_item);
+        }
+        __syncthreads();
+        const int n_hub = s_nhub;
+        for (int i = 0; i < n_hub; ++i) { // block-uniform
+            const int64_t hd = s_hub[i];
+            const int64_t hv = dst[hd];
+            const int64_t hstart = g.indptr[hv];
+            const int64_t hdeg = g.indptr[hv + 1] - hstart;
+            const int64_t seg = ((hdeg + kWavesPerBlock - 1) / kWavesPerBlock + 63) & ~63ll;
+            const int64_t from = min(hdeg, w * seg), to = min(hdeg, (w + 1) * seg);
+            const uint32_t mine = labor_wave_count(g, lkey, hstart, hdeg, fanout, from, to, lane);
+            if (lane == 0) s_wcnt[w] = mine;
+            __syncthreads();
+            int64_t hslot = indptr_local[hd];
+            for (int q = 0; q < w; ++q) hslot += s_wcnt[q];
+            for (int64_t c0 = from; c0 < to; c0 += 64) { // wave-uniform
+                const int64_t j = c0 + lane;
+                const int64_t t = j < to ? g.indices[hstart + j] : -1;
+                const bool take = j < to && labor_take(lkey, t, hdeg, fanout);
+                hslot += labor_emit(take, ~0ull, lane, t, hstart + j, hslot, n_dst, nbr, eid, tb, mask, slot_of_item);
+            }
+            __syncthreads(); // s_wcnt is rewritten for the next row
+        }
+    }
+}
+
 // first layer full: its table size is known on the device only
 __global__ __launch_bounds__(kBlock) void table_clear_kernel(Table tb, const int64_t* __restrict__ items_dev) { clear_table(tb, table_size(*items_dev)); }
 
@@ -737,7 +995,9 @@ __global__ __launch_bounds__(kBlock) void bucket_reindex_kernel(const int64_t* _
 struct coala_sampler {
     struct RingInfo { // what coala_sampler_wait_layers needs of a call to read its counts and explain a refusal
         int n_layers = 0, n_parts = 0;
+        bool labor = false; // fixed fan-outs are LABOR layers: every layer of the call is ragged
         int64_t n_seeds = 0;
+        bool ragged(int l) const { return labor || fanouts[l] == -1; } // CSR block, sizes known on the device only
         int32_t fanouts[COALA_SAMPLER_MAX_LAYERS] = {};
         int64_t src_cap[COALA_SAMPLER_MAX_LAYERS] = {}, edge_cap[COALA_SAMPLER_MAX_LAYERS] = {};
     };
@@ -792,7 +1052,7 @@ int ilog2_exact(uint64_t v) {
 }
 
 int check_call(const coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
-               const coala_sampler_layer_t* layers, const coala_sampler_bucketing_t* bucketing) {
+               const coala_sampler_layer_t* layers, const coala_sampler_bucketing_t* bucketing, bool labor) {
     if (!s || (!seeds && n_seeds > 0) || !fanouts) return fail(COALA_EINVAL, "null argument");
     if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
     if (n_seeds < 0 || n_seeds > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad n_seeds");
@@ -804,7 +1064,7 @@ int check_call(const coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, 
         const int f = fanouts[l];
         if (f != kFull && (f < 1 || f > 32)) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (or -1: every in-edge)", f);
         const coala_sampler_layer_t& y = layers[l];
-        if (!y.src_nodes || !y.nbr_local || (f == kFull && !y.indptr_local)) return fail(COALA_EINVAL, "layer %d: null buffer", l);
+        if (!y.src_nodes || !y.nbr_local || ((labor || f == kFull) && !y.indptr_local)) return fail(COALA_EINVAL, "layer %d: null buffer", l);
         if (y.src_cap < 0 || y.edge_cap < 0) return fail(COALA_EINVAL, "layer %d: negative capacity", l);
     }
     return COALA_OK;
@@ -817,7 +1077,7 @@ int check_call(const coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, 
 int fixed_run_check(const RingInfo& r, int l, int64_t n_src, int64_t* items_out, int64_t* limit_out, const char** what) {
     int64_t most = INT64_MAX;
     int64_t mult = 1; // P_j, capped above the item limit
-    for (int j = l + 1; j < r.n_layers && r.fanouts[j] != kFull; ++j) {
+    for (int j = l + 1; j < r.n_layers && !r.ragged(j); ++j) {
         const int64_t f = r.fanouts[j];
         const int64_t item_lim = std::min<int64_t>(kItemLimit, r.src_cap[j]);
         if (n_src >= 0) {
@@ -850,11 +1110,11 @@ int wait_impl(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* 
         for (int l = 0; l < r.n_layers; ++l) n_src_host[l] = pin[l];
     if (n_edges_host)
         for (int l = 0; l < r.n_layers; ++l)
-            n_edges_host[l] = r.fanouts[l] == kFull ? pin[kPinEdges + l] : (l ? pin[l - 1] : r.n_seeds) * r.fanouts[l];
+            n_edges_host[l] = r.ragged(l) ? pin[kPinEdges + l] : (l ? pin[l - 1] : r.n_seeds) * r.fanouts[l];
     if (bucket_counts_host)
         for (int g = 0; g < r.n_parts; ++g) bucket_counts_host[g] = pin[kPinParts + g];
     for (int l = 0; l < r.n_layers; ++l) { // device-side refusals, in layer order: the first one is the cause
-        if (r.fanouts[l] != kFull) continue;
+        if (!r.ragged(l)) continue;
         const int64_t n_dst = l ? pin[l - 1] : r.n_seeds;
         if (pin[kPinRefused + l]) {
             const long long e = pin[kPinEdges + l], items = n_dst + e;
@@ -902,6 +1162,7 @@ struct Plan {
     const float* weights; // null for uniform fixed layers, else the fp32 edge weights of weighted fixed layers (CSC order)
     int64_t* const* edge_ids; // null, or per layer: null or device int64[edge_cap], the CSC position of every neighbour slot
     hipStream_t st;
+    bool layer_dependency; // LABOR (info.labor): one key for every layer of the call
     RingInfo info;        // n_seeds, the fan-outs, n_parts and the caller's capacities
     // layer l has at most dst_cap[l] dst nodes, items_cap[l] items (dst nodes + neighbour slots), nbr_cap[l] neighbour entries
     int64_t dst_cap[COALA_SAMPLER_MAX_LAYERS], items_cap[COALA_SAMPLER_MAX_LAYERS], nbr_cap[COALA_SAMPLER_MAX_LAYERS];
@@ -912,7 +1173,8 @@ struct Plan {
 
 // Capacities.  Up to the first full layer they are exact host bounds (cap_l * (f + 1)) and checked here; a full layer and the fixed
 // layers behind it are checked on the device against the caller's capacities and the item limit.
-int plan_call(Plan& p, int64_t n_seeds, const int32_t* fanouts, int n_layers, int n_parts) {
+int plan_call(Plan& p, int64_t n_seeds, const int32_t* fanouts, int n_layers, int n_parts, bool labor) {
+    p.info.labor = labor;
     p.info.n_layers = n_layers;
     p.info.n_parts = n_parts;
     p.info.n_seeds = n_seeds;
@@ -926,7 +1188,7 @@ int plan_call(Plan& p, int64_t n_seeds, const int32_t* fanouts, int n_layers, in
         p.info.src_cap[l] = y.src_cap;
         p.info.edge_cap[l] = y.edge_cap;
         p.dst_cap[l] = cap;
-        if (f == kFull) {
+        if (labor || f == kFull) {
             host_bound = false;
             p.items_cap[l] = std::min<int64_t>(kItemLimit, y.src_cap);
             p.nbr_cap[l] = std::min<int64_t>(kItemLimit, y.edge_cap);
@@ -978,7 +1240,7 @@ int grow_workspace(coala_sampler_t* s, const Plan& p) {
 int empty_call(const Plan& p, int64_t* pin) {
     for (int l = 0; l < p.info.n_layers; ++l) {
         pin[l] = pin[kPinEdges + l] = pin[kPinRefused + l] = pin[kPinOver + l] = 0;
-        if (p.info.fanouts[l] == kFull) HIPCHK(hipMemsetAsync(p.layers[l].indptr_local, 0, sizeof(int64_t), p.st));
+        if (p.info.ragged(l)) HIPCHK(hipMemsetAsync(p.layers[l].indptr_local, 0, sizeof(int64_t), p.st));
     }
     for (int g = 0; g < p.info.n_parts; ++g) pin[kPinParts + g] = 0;
     if (p.info.n_parts > 0) HIPCHK(hipMemsetAsync(p.bucketing->counts, 0, (size_t)p.info.n_parts * sizeof(int64_t), p.st));
@@ -994,10 +1256,21 @@ int next_gen(coala_sampler_t* s, hipStream_t st) {
     return COALA_OK;
 }
 
-// Full layer l: degrees -> indptr_local, and its edge and item counts into its device words.
+// Ragged layer l: degrees (full) or counts of taken edges (LABOR) -> indptr_local, and its edge and item counts into its device words.
 int degree_scan(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, const int64_t* n_dst_dev) {
-    const int tiles = grid1d(p.dst_cap[l], kTile, kMaxTiles);
     if (int rc = next_gen(s, p.st)) return rc;
+    if (p.info.fanouts[l] != kFull) {
+        int rows = 64; // destination nodes per tile: the smallest power of two with which dst_cap fits kMaxTiles tiles
+        while (rows < kTile && (p.dst_cap[l] + rows - 1) / rows > kMaxTiles) rows <<= 1;
+        const int tiles = grid1d(p.dst_cap[l], rows, kMaxTiles);
+        hipLaunchKernelGGL(labor_count_scan_kernel, dim3(tiles), dim3(kBlock), 0, p.st, s->g, dst, n_dst_dev, p.info.n_seeds, rows, p.info.fanouts[l],
+                           labor_key(p.seed, p.step, l, p.layer_dependency), s->counts_dev + l, s->status, s->ticket, s->ticket_total,
+                           s->scan_gen & 0x3FFFFFFFull, p.layers[l].indptr_local, p.items_cap[l],
+                           std::min<int64_t>(kItemLimit, p.layers[l].edge_cap), p.pin_dev + l);
+        s->ticket_total += (unsigned long long)tiles;
+        return COALA_OK;
+    }
+    const int tiles = grid1d(p.dst_cap[l], kTile, kMaxTiles);
     hipLaunchKernelGGL(degree_scan_kernel, dim3(tiles), dim3(kBlock), 0, p.st, s->g, dst, n_dst_dev, p.info.n_seeds, s->counts_dev + l, s->status,
                        s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, p.layers[l].indptr_local, p.items_cap[l],
                        std::min<int64_t>(kItemLimit, p.layers[l].edge_cap), p.pin_dev + l);
@@ -1009,7 +1282,7 @@ int degree_scan(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, co
 int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, const int64_t* n_dst_dev) {
     const int64_t n_seeds = p.info.n_seeds;
     const int f = p.info.fanouts[l];
-    const bool full = f == kFull;
+    const bool full = p.info.ragged(l); // the ragged form: a full layer, or a LABOR layer
     const int64_t cap_l = p.dst_cap[l];
     int64_t* base = s->counts_dev + l;
     int64_t* n_src_dev = s->counts_dev + l + 1;
@@ -1023,8 +1296,13 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
     int rc;
     int64_t max_src = 0; // full layer: the most source nodes the fixed layers behind it accept
     if (full) {
-        hipLaunchKernelGGL(full_insert_kernel, dim3(grid1d(p.items_cap[l], kBlock, 8192)), blk, 0, st, s->g, dst, (const int64_t*)base,
-                           (const int64_t*)p.layers[l].indptr_local, s->nbr_global, s->tb, s->slot_of_item, eid);
+        if (f == kFull)
+            hipLaunchKernelGGL(full_insert_kernel, dim3(grid1d(p.items_cap[l], kBlock, 8192)), blk, 0, st, s->g, dst, (const int64_t*)base,
+                               (const int64_t*)p.layers[l].indptr_local, s->nbr_global, s->tb, s->slot_of_item, eid);
+        else
+            hipLaunchKernelGGL(labor_insert_kernel, dim3(grid1d(cap_l * kLaborGroup, kBlock, 8192)), blk, 0, st, s->g, dst, (const int64_t*)base,
+                               (const int64_t*)p.layers[l].indptr_local, f, labor_key(p.seed, p.step, l, p.layer_dependency), s->nbr_global,
+                               s->tb, s->slot_of_item, eid);
         int64_t unused_items = 0;
         const char* unused_what = nullptr;
         fixed_run_check(p.info, l, -1, &unused_items, &max_src, &unused_what);
@@ -1053,7 +1331,7 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
     });
     s->ticket_total += (unsigned long long)tiles;
     const bool last = l + 1 == p.info.n_layers;
-    const bool next_full = !last && p.info.fanouts[l + 1] == kFull;
+    const bool next_full = !last && p.info.ragged(l + 1);
     // a full next layer: its degree scan runs now, so that this layer's relabel_clear knows how much table to clear for it
     if (next_full && (rc = degree_scan(s, p, l + 1, src_out, n_src_dev))) return rc;
     const int64_t clear_cap = last ? (int64_t)table_size((int64_t)p.items0) : (int64_t)table_size(p.items_cap[l + 1]);
@@ -1089,7 +1367,7 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
 int launch_call(coala_sampler_t* s, Plan& p) {
     int rc;
     const int n_layers = p.info.n_layers;
-    const bool first_full = p.info.fanouts[0] == kFull;
+    const bool first_full = p.info.ragged(0);
     // what the last kernel leaves clean for the next call: the first layer's table of this call, or -- when that size is known on
     // the device only -- the extent the previous call left clean
     p.items0 = first_full ? std::max<uint64_t>(s->clean_items, 1) : (uint64_t)p.info.n_seeds * (uint64_t)(p.info.fanouts[0] + 1);
@@ -1114,17 +1392,18 @@ int launch_call(coala_sampler_t* s, Plan& p) {
 
 int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed, uint64_t step,
                 const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
-                int64_t* ticket_out, void* stream, const float* weights, int64_t* const* edge_ids = nullptr) {
+                int64_t* ticket_out, void* stream, const float* weights, int64_t* const* edge_ids = nullptr, bool labor = false,
+                bool layer_dependency = false) {
     int rc;
-    if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, layers, bucketing))) return rc;
+    if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, layers, bucketing, labor))) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(s->device));
     // the handle's scratch (hash table, scan state) is ordered by the stream of its calls: a caller that moves to another stream
     // first waits there for the previous call's last kernel
     if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
     s->last_stream = st;
-    Plan p{seeds, seed, step, layers, bucketing, weights, edge_ids, st};
-    if ((rc = plan_call(p, n_seeds, fanouts, n_layers, bucketing ? bucketing->n_parts : 0))) return rc;
+    Plan p{seeds, seed, step, layers, bucketing, weights, edge_ids, st, layer_dependency};
+    if ((rc = plan_call(p, n_seeds, fanouts, n_layers, bucketing ? bucketing->n_parts : 0, labor))) return rc;
     if ((rc = grow_workspace(s, p))) return rc;
     const uint64_t ticket = s->calls;
     const int slot = (int)(ticket % kRing);
@@ -1233,6 +1512,14 @@ int coala_sampler_sample_layers_edge_ids(coala_sampler_t* s, const int64_t* seed
                                          const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
     return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream,
                        edge_weights, edge_ids_out);
+}
+
+int coala_sampler_sample_layers_labor(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                      uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, int64_t* const* edge_ids_out,
+                                      int layer_dependency, int64_t* n_src_host, int64_t* n_edges_host,
+                                      const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
+    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream,
+                       nullptr, edge_ids_out, true, layer_dependency != 0);
 }
 
 } // extern "C"

@@ -6,6 +6,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --nodes 200000 --dim 128 --epochs 2
   python examples/train_synthetic.py --model_type gat --num_heads 4 --fan_out 5,5 --eval_fan_out=-1,-1
   python examples/train_synthetic.py --model_type gcn --edge_weights random --use_edge_weight
+  python examples/train_synthetic.py --sampler labor --fan_out 10,10
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -24,7 +25,7 @@ import torch  # noqa: E402
 from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
 from COALA_GNN.harness import GAT, GCN, SAGE, SageMean  # noqa: E402
-from COALA_GNN.sampler import NeighborSampler  # noqa: E402
+from COALA_GNN.sampler import LaborSampler, NeighborSampler  # noqa: E402
 from COALA_GNN.synthetic import alloc_pinned_table, powerlaw_csc  # noqa: E402
 
 
@@ -35,6 +36,9 @@ def main():
     ap.add_argument("--fan_out", type=str, default="5,5")
     ap.add_argument("--eval_fan_out", type=str, default=None,
                     help="fan-outs of the evaluation loader (default: --fan_out); -1 takes every in-edge, e.g. -1,-1 for full neighbourhoods")
+    ap.add_argument("--sampler", type=str, default="neighbor", choices=["neighbor", "labor"],
+                    help="labor: layer-neighbour sampling (LaborSampler) -- the same expected fan-out per node, fewer input nodes to fetch")
+    ap.add_argument("--layer_dependency", action="store_true", help="with --sampler labor: the same random numbers in every layer")
     ap.add_argument("--edge_weights", type=str, default="none", choices=["none", "random"],
                     help="random: seeded edge weights in (0, 1] with ~10%% zeros, sampled in proportion by the training sampler (DGL's "
                          "prob=); evaluation stays uniform")
@@ -117,7 +121,14 @@ def main():
     if args.use_edge_weight and prob is None:
         ap.error("--use_edge_weight needs --edge_weights random")
     ew = "w" if args.use_edge_weight and args.model_type != "gat" else None
-    sampler = NeighborSampler(fan_out, prob=prob, edge_ids=ew is not None)                                  # :70-72
+    if args.sampler == "labor":
+        if prob is not None:
+            ap.error("--sampler labor does not sample by edge weight (--edge_weights)")
+        sampler = LaborSampler(fan_out, layer_dependency=args.layer_dependency)
+    else:
+        if args.layer_dependency:
+            ap.error("--layer_dependency needs --sampler labor")
+        sampler = NeighborSampler(fan_out, prob=prob, edge_ids=ew is not None)                              # :70-72
     g = sampler.make_graph(indptr, indices, ndata={"labels": labels}, edata=edata)
     train_loader = COALA_GNN_DataLoader(SSD_INFO(1, args.dim * 4, 1024, 0), nd, g, sampler, args.batch_size, args.dim, fan_out,
                                         args.cache_size, device, refresh_counter=args.refresh_counter,
@@ -154,11 +165,14 @@ def main():
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()
+            if count == 1:
+                first_loss = loss.item()
         torch.cuda.synchronize()
         print(f"Epoch Time: {time.time() - epoch_start}")
         print(f"Total number of iterations: {count}")
         print(f"Number of sampled nodes : {num_sampled_nodes}")
         train_loader.print_stats()
+    print(f"first loss {first_loss:.4f}")
     print(f"final loss {loss.item():.4f}")
     comm.global_comm.Barrier()
     del train_loader

@@ -381,7 +381,7 @@ int coala_sampler_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, 
 typedef struct coala_sampler_layer {
     int64_t* src_nodes;    /* device int64[src_cap]: source nodes of the block                                    */
     int32_t* nbr_local;    /* device int32[edge_cap]: fixed -> [n_dst, f] -1 padded; full -> [E]                 */
-    int64_t* indptr_local; /* full layer: device int64[dst_cap + 1]; fixed layer: unused (NULL)                   */
+    int64_t* indptr_local; /* full or LABOR layer: device int64[dst_cap + 1]; fixed layer: unused (NULL)          */
     int64_t src_cap;
     int64_t edge_cap;
 } coala_sampler_layer_t;
@@ -413,7 +413,24 @@ int coala_sampler_sample_layers_edge_ids(coala_sampler_t* s, const int64_t* seed
                                          uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const float* edge_weights,
                                          int64_t* const* edge_ids_out, int64_t* n_src_host, int64_t* n_edges_host,
                                          const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream);
-/* Counts of an earlier call, with the edge counts of its layers; returns the device-side refusal of a full layer, if any. */
+/* LABOR layer-neighbour sampling (DGL's LaborSampler(fanouts, importance_sampling=0); Balin & Catalyurek, NeurIPS 2023): as
+ * coala_sampler_sample_layers_edge_ids without edge weights, but a fan-out k in 1..32 is a LABOR layer.  One random number r_t per
+ * SOURCE node t is shared by every destination node of the layer: a destination node of in-degree deg <= k takes every in-edge;
+ * otherwise its in-edge from t is taken iff mulhi64(r_t, deg) < k, r_t = splitmix64(labor_key(seed, step, l) ^ t) (the key is in the
+ * header of coala_sampler.hip).  A row holds k neighbours in expectation, repeated edges are taken or left together, and destination
+ * nodes that share a neighbour agree on it, so the source list is shorter than that of k independent picks per row.
+ * layer_dependency != 0 drops the layer index from the key: every layer of the call sees the same r_t.
+ * Every layer's block is CSR, exactly as a full layer's: indptr_local int64[n_dst + 1] is required for every layer, nbr_local holds
+ * the E taken edges (ascending CSC position inside a row, rows in destination order), edge_ids_out (NULL, or per layer NULL or
+ * int64[edge_cap]) their CSC positions.  E is known on the device only: capacities, the device-side refusal (n_dst + E over
+ * min(8,388,608, src_cap), or E over edge_cap), the source-list rule, bucketing and the ticket / wait protocol are those of a full
+ * layer; n_edges_host[l] is E.  A -1 entry is a full layer.  An out-of-range destination id gives an empty row.  Same arguments,
+ * same sample.  Two launches stand where a full layer's degree_scan and full_insert stand; nothing is added to the stream. */
+int coala_sampler_sample_layers_labor(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                      uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, int64_t* const* edge_ids_out,
+                                      int layer_dependency, int64_t* n_src_host, int64_t* n_edges_host,
+                                      const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream);
+/* Counts of an earlier call, with the edge counts of its layers; returns the device-side refusal of a full or LABOR layer, if any. */
 int coala_sampler_wait_layers(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host);
 
 /* Block op for the consumer of these blocks (the native Block objects stand where DGL blocks stand in
