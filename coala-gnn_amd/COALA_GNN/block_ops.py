@@ -1,5 +1,6 @@
 """Autograd wrappers of the native block ops that `Block` (sampler.py) hands to a model: mean aggregation (SAGEConv's "mean"), weighted
-sum aggregation (DGL's u_mul_e_sum, the edge_weight= path of GraphConv / SAGEConv) and GAT attention aggregation, on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the
+sum aggregation (DGL's u_mul_e_sum, the edge_weight= path of GraphConv / SAGEConv), max aggregation (DGL's fn.max: SAGEConv's "pool",
+GINConv's "max") and GAT attention aggregation, on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the
 kernels are in coala-gnn_amd/csrc/coala_block_ops.hip (C ABI: coala_block_*)."""
 import torch
 
@@ -116,6 +117,59 @@ class _WeightedSumCSR(torch.autograd.Function):
                                                                grad_w.data_ptr() if need_w else None, indptr.numel() - 1, g.shape[1],
                                                                current_stream()))
         return grad_src, grad_w, None, None
+
+
+def _max_backward(ctx, grad_out):
+    """grad_src[arg[d, c], c] += grad_out[d, c] (coala_block_max_aggregate_backward): one kernel for both block forms."""
+    (arg,) = ctx.saved_tensors
+    g = grad_out.contiguous()
+    grad_src = torch.zeros(ctx.src_shape, dtype=torch.float32, device=g.device)
+    _capi.check(_lib.coala_block_max_aggregate_backward(g.device.index or 0, arg.data_ptr(), g.data_ptr(), grad_src.data_ptr(), arg.shape[0],
+                                                        arg.shape[1], current_stream()))
+    return grad_src
+
+
+class _MaxAggregate(torch.autograd.Function):
+    """out[d, c] = max of h_src[nbr[d, j], c] over the valid j, ties to the first slot (coala_block_max_aggregate): one kernel forward,
+    which also saves the winning source of every element -- skipped when h_src needs no gradient -- and one backward."""
+
+    @staticmethod
+    def forward(ctx, h_src, nbr):
+        h = h_src.contiguous()
+        n_dst, fanout = nbr.shape
+        out = torch.empty((n_dst, h.shape[1]), dtype=torch.float32, device=h.device)
+        arg = torch.empty((n_dst, h.shape[1]), dtype=torch.int32, device=h.device) if ctx.needs_input_grad[0] else None
+        _capi.check(_lib.coala_block_max_aggregate(h.device.index or 0, nbr.data_ptr(), h.data_ptr(), out.data_ptr(),
+                                                   arg.data_ptr() if arg is not None else None, n_dst, fanout, h.shape[1], current_stream()))
+        if arg is not None:
+            ctx.save_for_backward(arg)
+        ctx.src_shape = h.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _max_backward(ctx, grad_out), None
+
+
+class _MaxAggregateCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_max_aggregate_csr): row d takes the maximum over h_src[indices[indptr[d]:indptr[d+1]]]."""
+
+    @staticmethod
+    def forward(ctx, h_src, indptr, indices):
+        h = h_src.contiguous()
+        n_dst = indptr.numel() - 1
+        out = torch.empty((n_dst, h.shape[1]), dtype=torch.float32, device=h.device)
+        arg = torch.empty((n_dst, h.shape[1]), dtype=torch.int32, device=h.device) if ctx.needs_input_grad[0] else None
+        _capi.check(_lib.coala_block_max_aggregate_csr(h.device.index or 0, indptr.data_ptr(), indices.data_ptr(), h.data_ptr(), out.data_ptr(),
+                                                       arg.data_ptr() if arg is not None else None, n_dst, h.shape[1], current_stream()))
+        if arg is not None:
+            ctx.save_for_backward(arg)
+        ctx.src_shape = h.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _max_backward(ctx, grad_out), None, None
 
 
 def _gat_contig(el, er, feat_src):

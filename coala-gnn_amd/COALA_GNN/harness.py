@@ -2,14 +2,15 @@
 used by bench.py's epoch leg and the tests; it stands where examples/models.py:DistSAGE + dgl.nn.SAGEConv stand in the reference's
 training script (examples/sbatch_ssd_gnn_train.py:98-145).  GAT and GCN mirror the reference's examples/models.py:GAT and :GCN on
 COALA_GNN.nn's GATConv and GraphConv (--model_type gat|gcn); GAT's attention step is a native kernel (Block.gat_aggregate).  GCN and
-SAGE take edge_weight=<edata key> and then hand block.edata[key] to their layers (blocks sampled with NeighborSampler(edge_ids=True))."""
+SAGE take edge_weight=<edata key> and then hand block.edata[key] to their layers (blocks sampled with NeighborSampler(edge_ids=True)).
+SAGE(aggregator_type='pool') and GIN (--model_type gin) are the models on the native max aggregation (Block.max_aggregate)."""
 import time
 
 import torch
 
-from .nn import GATConv, GraphConv, SAGEConv
+from .nn import GATConv, GINConv, GraphConv, SAGEConv
 
-__all__ = ["SageMean", "SAGE", "GAT", "GCN", "train_steps", "FlatGradAllReduce"]
+__all__ = ["SageMean", "SAGE", "GAT", "GCN", "GIN", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -69,8 +70,8 @@ class GCN(torch.nn.Module):
 
 
 class SAGE(torch.nn.Module):
-    """GraphSAGE on COALA_GNN.nn.SAGEConv ('mean', or 'gcn' as the reference's RSAGE model uses), relu between the layers; with
-    edge_weight=<edata key> every layer weighs its messages by block.edata[key]."""
+    """GraphSAGE on COALA_GNN.nn.SAGEConv ('mean', 'gcn' as the reference's RSAGE model uses, or 'pool', the max-pooling aggregator),
+    relu between the layers; with edge_weight=<edata key> every layer weighs its messages by block.edata[key]."""
 
     def __init__(self, in_feats, h_feats, num_classes, num_layers=2, aggregator_type="mean", edge_weight=None):
         super().__init__()
@@ -83,6 +84,26 @@ class SAGE(torch.nn.Module):
         for i, (layer, block) in enumerate(zip(self.layers, blocks)):
             w = None if self.edge_weight is None else block.edata[self.edge_weight]
             h = layer(block, (h, block.dst_rows(h)), edge_weight=w)
+            if i + 1 < len(self.layers):
+                h = torch.relu(h)
+        return h
+
+
+class GIN(torch.nn.Module):
+    """num_layers GINConv layers ('sum', 'max' or 'mean'), each with a two-layer MLP (Linear, relu, Linear) as its apply_func, relu
+    between the layers; learn_eps makes every layer's eps a parameter."""
+
+    def __init__(self, in_feats, h_feats, num_classes, num_layers=2, aggregator_type="sum", learn_eps=False):
+        super().__init__()
+        dims = [in_feats] + [h_feats] * (num_layers - 1) + [num_classes]
+        self.layers = torch.nn.ModuleList(
+            GINConv(torch.nn.Sequential(torch.nn.Linear(dims[i], h_feats), torch.nn.ReLU(), torch.nn.Linear(h_feats, dims[i + 1])),
+                    aggregator_type, learn_eps=learn_eps) for i in range(num_layers))
+
+    def forward(self, blocks, x):
+        h = x
+        for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+            h = layer(block, (h, block.dst_rows(h)))
             if i + 1 < len(self.layers):
                 h = torch.relu(h)
         return h

@@ -1,13 +1,15 @@
-"""GATConv and GraphConv on the native Block objects, for the reference's GAT and GCN models (examples/models.py; DGL is not
-installed on the MI355X image).  Both take (block, (h_src, h_dst)) as DGL's modules do on a block.
+"""GATConv, GraphConv, SAGEConv and GINConv on the native Block objects, for the reference's GAT and GCN models (examples/models.py;
+DGL is not installed on the MI355X image) and for DGL models ported to them.  All take (block, (h_src, h_dst)) as DGL's modules do on
+a block.
 
 GATConv's projections are dense and stay in torch; its attention step (score, per-destination softmax, weighted sum) is
 Block.gat_aggregate, a native kernel on both block forms.  GraphConv reduces to Block.mean_aggregate times the in-degree.  With
 edge_weight= (one value per neighbour slot, e.g. block.edata['w'] of a block sampled with edge_ids=True) GraphConv and SAGEConv
-aggregate with Block.weighted_sum_aggregate, DGL's u_mul_e_sum."""
+aggregate with Block.weighted_sum_aggregate, DGL's u_mul_e_sum.  SAGEConv's 'pool' and GINConv's 'max' take their maximum with
+Block.max_aggregate (DGL's fn.max), a native kernel as well; GINConv's 'sum' is Block.weighted_sum_aggregate with unit weights."""
 import torch
 
-__all__ = ["GATConv", "GraphConv", "SAGEConv"]
+__all__ = ["GATConv", "GraphConv", "SAGEConv", "GINConv"]
 
 
 class GATConv(torch.nn.Module):
@@ -109,19 +111,25 @@ class SAGEConv(torch.nn.Module):
     """GraphSAGE layer on a block, with DGL SAGEConv's parameter names so that such a state_dict loads:
         'mean':  out[d] = fc_self(h_dst[d]) + fc_neigh(mean_j h_src[s_j]) + bias
         'gcn':   out[d] = fc_neigh((sum_j h_src[s_j] + h_dst[d]) / (in_deg(d) + 1)) + bias        (no fc_self)
+        'pool':  out[d] = fc_self(h_dst[d]) + fc_neigh(max_j relu(fc_pool(h_src))[s_j]) + bias    (element-wise maximum)
     over the valid in-edges j of d in the block; fc_self.weight / fc_neigh.weight [out_feats, in_feats] (no bias of their own,
-    Xavier-uniform with the gain of relu), bias [out_feats] (zero).  With edge_weight (one value per neighbour slot, shaped like
-    block.edata['_ID']) every message is h_src[s_j] * w_j while the divisor stays the unweighted in-degree: DGL's rule.  The
-    projection runs before the aggregation when in_feats > out_feats, as DGL does.  feat is h_src or (h_src, h_dst); without h_dst
-    the destination rows are block.dst_rows(h_src).  A destination without an in-edge gets fc_self(h_dst) + bias ('mean') or
-    fc_neigh(h_dst) + bias ('gcn').  The 'pool' and 'lstm' aggregators, feat_drop and norm are not provided."""
+    Xavier-uniform with the gain of relu), bias [out_feats] (zero); 'pool' adds fc_pool.weight [in_src, in_src] (Xavier-uniform with
+    the gain of relu) and fc_pool.bias [in_src].  With edge_weight (one value per neighbour slot, shaped like block.edata['_ID'])
+    every message is h_src[s_j] * w_j -- relu(fc_pool(h_src))[s_j] * w_j for 'pool', whose maximum then runs in plain torch -- while the
+    divisor stays the unweighted in-degree: DGL's rule.  The projection runs before the aggregation when in_feats > out_feats, as DGL
+    does ('pool' always projects after it, as in DGL).  feat is h_src or (h_src, h_dst); without h_dst the destination rows are
+    block.dst_rows(h_src).  A destination without an in-edge gets fc_self(h_dst) + bias ('mean', 'pool': its maximum is 0, DGL's
+    reducer) or fc_neigh(h_dst) + bias ('gcn').  The maximum is Block.max_aggregate: ties give their gradient to the first edge.
+    The 'lstm' aggregator, feat_drop and norm are not provided."""
 
     def __init__(self, in_feats, out_feats, aggregator_type="mean", bias=True, activation=None):
         super().__init__()
-        if aggregator_type not in ("mean", "gcn"):
-            raise ValueError(f"aggregator_type {aggregator_type!r}: 'mean' or 'gcn'")
+        if aggregator_type not in ("mean", "gcn", "pool"):
+            raise ValueError(f"aggregator_type {aggregator_type!r}: 'mean', 'gcn' or 'pool'")
         in_src, in_dst = in_feats if isinstance(in_feats, (tuple, list)) else (in_feats, in_feats)
         self._in_src_feats, self._out_feats, self._aggre_type = in_src, out_feats, aggregator_type
+        if aggregator_type == "pool":
+            self.fc_pool = torch.nn.Linear(in_src, in_src)
         self.fc_neigh = torch.nn.Linear(in_src, out_feats, bias=False)
         if aggregator_type != "gcn":
             self.fc_self = torch.nn.Linear(in_dst, out_feats, bias=False)
@@ -131,6 +139,8 @@ class SAGEConv(torch.nn.Module):
 
     def reset_parameters(self):
         gain = torch.nn.init.calculate_gain("relu")
+        if self._aggre_type == "pool":
+            torch.nn.init.xavier_uniform_(self.fc_pool.weight, gain=gain)
         torch.nn.init.xavier_uniform_(self.fc_neigh.weight, gain=gain)
         if self._aggre_type != "gcn":
             torch.nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
@@ -139,6 +149,13 @@ class SAGEConv(torch.nn.Module):
 
     def forward(self, block, feat, edge_weight=None):
         h_src, h_dst = feat if isinstance(feat, (tuple, list)) else (feat, block.dst_rows(feat))
+        if self._aggre_type == "pool":
+            h = torch.relu(self.fc_pool(h_src))
+            neigh = block.max_aggregate(h) if edge_weight is None else block.max_aggregate_torch(h, edge_weight)
+            rst = self.fc_self(h_dst) + self.fc_neigh(neigh)
+            if self.bias is not None:
+                rst = rst + self.bias
+            return rst if self.activation is None else self.activation(rst)
         lin_before = self._in_src_feats > self._out_feats
         h = self.fc_neigh(h_src) if lin_before else h_src
         deg = block.in_degrees().to(device=h.device, dtype=h.dtype).unsqueeze(-1)
@@ -157,6 +174,51 @@ class SAGEConv(torch.nn.Module):
             rst = neigh if lin_before else self.fc_neigh(neigh)
         if self.bias is not None:
             rst = rst + self.bias
+        if self.activation is not None:
+            rst = self.activation(rst)
+        return rst
+
+
+class GINConv(torch.nn.Module):
+    """Graph isomorphism layer on a block, DGL GINConv's signature and names:
+        out[d] = apply_func((1 + eps) * h_dst[d] + agg_j h_src[s_j]),   then activation, if any
+    over the valid in-edges j of d in the block, agg one of 'sum', 'max' (element-wise) and 'mean'.  eps has shape [1] and the name
+    'eps': a buffer holding init_eps, or a parameter with learn_eps=True; apply_func (any callable, usually an MLP) is registered under
+    that name when it is a module.  'sum' is Block.weighted_sum_aggregate with unit weights on the valid slots -- an exact slot-order
+    sum, unlike mean * in_deg -- 'mean' is Block.mean_aggregate and 'max' is Block.max_aggregate (ties give their gradient to the first
+    edge).  With edge_weight (one value per neighbour slot, shaped like block.edata['_ID']) every message is h_src[s_j] * w_j, DGL's
+    u_mul_e: 'sum' takes the weights in place of the units, 'mean' divides that sum by the unweighted in-degree, and 'max' runs in
+    plain torch.  feat is h_src or (h_src, h_dst); without h_dst the destination rows are block.dst_rows(h_src).  A destination
+    without an in-edge gets apply_func((1 + eps) * h_dst[d]): every aggregate is 0 there, DGL's reducers."""
+
+    def __init__(self, apply_func=None, aggregator_type="sum", init_eps=0, learn_eps=False, activation=None):
+        super().__init__()
+        if aggregator_type not in ("sum", "max", "mean"):
+            raise ValueError(f"aggregator_type {aggregator_type!r}: 'sum', 'max' or 'mean'")
+        self.apply_func = apply_func
+        self._aggregator_type = aggregator_type
+        self.activation = activation
+        eps = torch.tensor([float(init_eps)], dtype=torch.float32)
+        if learn_eps:
+            self.eps = torch.nn.Parameter(eps)
+        else:
+            self.register_buffer("eps", eps)
+
+    def forward(self, block, feat, edge_weight=None):
+        h_src, h_dst = feat if isinstance(feat, (tuple, list)) else (feat, block.dst_rows(feat))
+        if self._aggregator_type == "max":
+            neigh = block.max_aggregate(h_src) if edge_weight is None else block.max_aggregate_torch(h_src, edge_weight)
+        elif self._aggregator_type == "mean" and edge_weight is None:
+            neigh = block.mean_aggregate(h_src)
+        else:
+            slots = block.indices if block.nbr is None else block.nbr
+            w = edge_weight if edge_weight is not None else torch.ones(slots.shape, dtype=h_src.dtype, device=h_src.device)
+            neigh = block.weighted_sum_aggregate(h_src, w)
+            if self._aggregator_type == "mean":
+                neigh = neigh / block.in_degrees().to(device=neigh.device, dtype=neigh.dtype).clamp_min(1).unsqueeze(-1)
+        rst = (1 + self.eps) * h_dst + neigh
+        if self.apply_func is not None:
+            rst = self.apply_func(rst)
         if self.activation is not None:
             rst = self.activation(rst)
         return rst

@@ -11,7 +11,8 @@ import torch
 
 from COALA_GNN_Pybind import _capi, current_stream
 
-from .block_ops import _GatAggregate, _GatAggregateCSR, _MeanAggregate, _MeanAggregateCSR, _WeightedSum, _WeightedSumCSR
+from .block_ops import (_GatAggregate, _GatAggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate, _MeanAggregateCSR, _WeightedSum,
+                        _WeightedSumCSR)
 
 __all__ = ["NeighborSampler", "LaborSampler", "CSCGraph", "Block", "ITEM_LIMIT", "EID"]
 
@@ -233,6 +234,62 @@ class Block(object):
         valid = (self.nbr >= 0).to(device=dev, dtype=h_src.dtype)
         idx = self.nbr.clamp_min(0).to(device=dev, dtype=torch.int64)
         return (h_src[idx] * (w * valid).unsqueeze(-1)).sum(1)
+
+    def max_aggregate(self, h_src):
+        """Element-wise maximum of the sampled neighbours' rows for every dst node: fp32 [num_dst, dim] (DGL's fn.max: SAGEConv 'pool',
+        GINConv 'max').  torch.max(dim)'s rule over the valid slots in slot order: ties keep the first slot, which alone receives the
+        gradient; a NaN propagates; a dst node without an in-edge gets zeros (DGL's reducer).  Native kernels under the conditions of
+        mean_aggregate (fp32 2-D rows on the GPU; fan-out <= 32, or the ragged form); plain torch otherwise."""
+        native = h_src.is_cuda and h_src.dtype == torch.float32 and h_src.dim() == 2
+        if self.nbr is None:
+            if native and self.indptr.is_cuda and self.indices.is_cuda:
+                return _MaxAggregateCSR.apply(h_src, self.indptr.contiguous(), self.indices.contiguous())
+        elif native and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
+            return _MaxAggregate.apply(h_src, self.nbr)
+        return self.max_aggregate_torch(h_src)
+
+    def max_aggregate_torch(self, h_src, w=None, return_arg=False):
+        """max_aggregate in plain torch, any device and dtype: its fallback, and its reference.  The winner of every (row, column) is
+        found first -- the first NaN if the row holds one, else the first slot that equals the maximum -- and the output is gathered
+        through it, so the gradient goes to that slot alone.  w (one value per neighbour slot, as weighted_sum_aggregate takes): the
+        messages are h_src[s_j] * w_j (DGL's u_mul_e, then max).  return_arg: -> (out, arg), arg the int32 local source index of every
+        winner, -1 for a row without a valid edge."""
+        dev = h_src.device
+        trail = tuple(h_src.shape[1:])
+        ones = (1,) * len(trail)
+        if self.nbr is None:
+            deg = self.indptr[1:] - self.indptr[:-1]
+            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg).to(dev)
+            src = self.indices.to(device=dev, dtype=torch.int64)
+        else:
+            f = self.nbr.shape[1]
+            rows = torch.arange(self.num_dst, device=dev).repeat_interleave(f)
+            src = self.nbr.reshape(-1).to(device=dev, dtype=torch.int64)
+        E = src.numel()
+        if E == 0:
+            out = torch.zeros((self.num_dst,) + trail, dtype=h_src.dtype, device=dev)
+            return (out, torch.full(out.shape, -1, dtype=torch.int32, device=dev)) if return_arg else out
+        msg = h_src[src.clamp_min(0)]                                             # [E, ...]: every slot's message, in slot order
+        if w is not None:
+            msg = msg * w.reshape(-1).to(device=dev, dtype=h_src.dtype).view((E,) + ones)
+        v = msg.detach()
+        valid = (src >= 0).view((E,) + ones).expand_as(v)
+        nan = valid & torch.isnan(v)
+        at = rows.view((E,) + ones).expand_as(v)
+        shape = (self.num_dst,) + trail
+        vmax = torch.full(shape, float("-inf"), dtype=v.dtype, device=dev).scatter_reduce(
+            0, at, torch.where(valid & ~nan, v, torch.full_like(v, float("-inf"))), "amax")
+        has_nan = torch.zeros(shape, dtype=torch.int8, device=dev).scatter_reduce(0, at, nan.to(torch.int8), "amax").bool()
+        wins = torch.where(has_nan[rows], nan, valid & ~nan & (v == vmax[rows]))
+        slot = torch.arange(E, device=dev).view((E,) + ones).expand_as(v)
+        first = torch.full(shape, E, dtype=torch.int64, device=dev).scatter_reduce(0, at, torch.where(wins, slot, torch.full_like(slot, E)), "amin")
+        some = first < E
+        first = first.clamp_max(E - 1)
+        out = torch.where(some, msg.gather(0, first), torch.zeros((), dtype=msg.dtype, device=dev))
+        if not return_arg:
+            return out
+        arg = torch.where(some, src.view((E,) + ones).expand_as(v).gather(0, first), torch.full_like(first, -1)).to(torch.int32)
+        return out, arg
 
     def num_src_nodes(self):   # DGL's block API (examples/models.py calls block.num_dst_nodes())
         return self.num_src

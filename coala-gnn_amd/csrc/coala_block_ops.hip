@@ -1,8 +1,8 @@
 // coala_block_ops.hip -- what a model computes on a sampled block (coala_sampler.hip makes the blocks), for gfx950: mean aggregation
-// (DGL's SAGEConv "mean"), weighted sum aggregation (DGL's u_mul_e_sum: GraphConv / SAGEConv with edge_weight=) and GAT attention
-// aggregation (GATConv's message step), forward and backward, on fixed blocks
-// (nbr_local[n_dst, fanout], -1 = no neighbour) and on the CSR blocks of full layers.  Stateless entry points: no handle, every
-// launch on the caller's stream.
+// (DGL's SAGEConv "mean"), weighted sum aggregation (DGL's u_mul_e_sum: GraphConv / SAGEConv with edge_weight=), max aggregation
+// (DGL's fn.max: SAGEConv "pool", GINConv "max") and GAT attention aggregation (GATConv's message step), forward and backward, on
+// fixed blocks (nbr_local[n_dst, fanout], -1 = no neighbour) and on the CSR blocks of full layers.  Stateless entry points: no
+// handle, every launch on the caller's stream.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -424,6 +424,74 @@ __global__ __launch_bounds__(kBlock) void weighted_sum_backward_kernel(const int
     }
 }
 
+// Max aggregation (DGL's fn.max reducer, what SAGEConv "pool" and GINConv "max" compute): out[d, c] = max over the valid edges j of row
+// d of h_src[s_j, c], and arg[d, c] = the s_j of the winning edge (int32, the local source index), which is all the backward needs.
+// The weighted sum's mapping: one wave per destination row, a lane per 16 bytes of the row, the row's indices read 64 at a time (a
+// fixed row of fan-out <= 32 is one chunk) and broadcast by shuffle.  The rule, torch.max(dim)'s: the running maximum starts from the
+// first valid slot, a later slot replaces it when v > best, or when v is NaN and best is not -- ties (+-0 included) keep the first slot
+// in slot order, a NaN propagates with arg at the first NaN, a row of -inf gives -inf and a valid arg.  A row without a valid edge
+// gives out = 0 and arg = -1 (DGL's max reducer at zero in-degree).  arg may be null (inference): nothing is stored for it.  A
+// maximum rounds nothing, and the fixed and the CSR kernels are the same code on the same lanes: both forms give the same bits.
+// A byte mover like the mean: per row it reads deg * (dim * 4 + 4) bytes and writes dim * 4 (dim * 8 with arg).
+template <int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void max_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
+                                                               const float* __restrict__ h_src, float* __restrict__ out,
+                                                               int32_t* __restrict__ arg, int64_t n_dst, int dim) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    typedef int32_t vi __attribute__((ext_vector_type(VEC)));
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int units = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+            const int u = u0 + lane;
+            vf best = vf(0.0f);
+            vi at = vi(-1);
+            bool any = false; // wave-uniform: a valid slot has been seen
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
+                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s < 0) continue; // wave-uniform
+                    if (u < units) {
+                        const vf v = *reinterpret_cast<const vf*>(h_src + (int64_t)s * dim + (int64_t)u * VEC);
+                        for (int i = 0; i < VEC; ++i) { // selects, no branches: the lanes of a wave disagree element by element
+                            const bool take = !any | (v[i] > best[i]) | ((v[i] != v[i]) & (best[i] == best[i]));
+                            best[i] = take ? v[i] : best[i];
+                            at[i] = take ? s : at[i];
+                        }
+                    }
+                    any = true;
+                }
+            }
+            if (u < units) {
+                *reinterpret_cast<vf*>(out + d * dim + (int64_t)u * VEC) = best;
+                if (arg) *reinterpret_cast<vi*>(arg + d * dim + (int64_t)u * VEC) = at;
+            }
+        }
+    }
+}
+
+// grad_src[arg[d, c], c] += grad_out[d, c] wherever arg[d, c] >= 0 (grad_src zeroed by the caller; hardware float atomics: summation
+// order varies).  One kernel for both block forms: it needs no neighbour list.  The mean backward's mapping, a lane per float: lane c
+// reads arg[d, c] and grad_out[d, c] coalesced and issues one atomic, where the mean backward issues deg.  Per row it reads dim * 8
+// bytes and adds dim * 4 through atomics.
+__global__ __launch_bounds__(kBlock) void max_aggregate_backward_kernel(const int32_t* __restrict__ arg, const float* __restrict__ grad_out,
+                                                                        float* __restrict__ grad_src, int64_t n_dst, int dim) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    for (int64_t d = wave; d < n_dst; d += n_waves)
+        for (int c = lane; c < dim; c += 64) {
+            const int32_t s = arg[d * dim + c];
+            if (s >= 0) unsafeAtomicAdd(grad_src + (int64_t)s * dim + c, grad_out[d * dim + c]);
+        }
+}
+
 } // namespace
 
 namespace {
@@ -616,6 +684,51 @@ int coala_block_weighted_sum_csr_backward(int device, const int64_t* indptr, con
                                           const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int dim, void* stream) {
     if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
     return weighted_sum_backward_launch<true>(device, indptr, indices, w, 0, h_src, grad_out, grad_src, grad_w, n_dst, dim, stream);
+}
+
+} // extern "C"
+
+namespace {
+template <bool CSR>
+int max_aggregate_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* h_src, float* out, int32_t* arg,
+                         int64_t n_dst, int dim, void* stream) {
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
+    dispatch_vec(vec4_ok(dim, h_src, out) && vec4_ok(dim, arg, nullptr), [&](auto vec) {
+        hipLaunchKernelGGL((max_aggregate_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, fanout, h_src, out,
+                           arg, n_dst, dim);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+} // namespace
+
+extern "C" {
+
+int coala_block_max_aggregate(int device, const int32_t* nbr, const float* h_src, float* out, int32_t* arg, int64_t n_dst, int fanout, int dim,
+                              void* stream) {
+    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+    return max_aggregate_launch<false>(device, nullptr, nbr, fanout, h_src, out, arg, n_dst, dim, stream);
+}
+
+int coala_block_max_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int32_t* arg,
+                                  int64_t n_dst, int dim, void* stream) {
+    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
+    return max_aggregate_launch<true>(device, indptr, indices, 0, h_src, out, arg, n_dst, dim, stream);
+}
+
+int coala_block_max_aggregate_backward(int device, const int32_t* arg, const float* grad_out, float* grad_src, int64_t n_dst, int dim,
+                                       void* stream) {
+    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
+    if (n_dst == 0) return COALA_OK;
+    if (!arg || !grad_out || !grad_src) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(max_aggregate_backward_kernel, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, arg, grad_out,
+                       grad_src, n_dst, dim);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
 }
 
 } // extern "C"

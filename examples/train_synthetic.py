@@ -7,6 +7,8 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --model_type gat --num_heads 4 --fan_out 5,5 --eval_fan_out=-1,-1
   python examples/train_synthetic.py --model_type gcn --edge_weights random --use_edge_weight
   python examples/train_synthetic.py --sampler labor --fan_out 10,10
+  python examples/train_synthetic.py --sage_aggregator pool
+  python examples/train_synthetic.py --model_type gin --gin_aggregator max
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -24,7 +26,7 @@ import torch  # noqa: E402
 
 from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
-from COALA_GNN.harness import GAT, GCN, SAGE, SageMean  # noqa: E402
+from COALA_GNN.harness import GAT, GCN, GIN, SAGE, SageMean  # noqa: E402
 from COALA_GNN.sampler import LaborSampler, NeighborSampler  # noqa: E402
 from COALA_GNN.synthetic import alloc_pinned_table, powerlaw_csc  # noqa: E402
 
@@ -44,7 +46,7 @@ def main():
                          "prob=); evaluation stays uniform")
     ap.add_argument("--use_edge_weight", action="store_true",
                     help="with --edge_weights random: the blocks carry their edge ids (NeighborSampler(edge_ids=True)) and the gcn / sage "
-                         "layers multiply every message by its edge's weight, block.edata['w'] (DGL's edge_weight=); gat ignores it")
+                         "layers multiply every message by its edge's weight, block.edata['w'] (DGL's edge_weight=); gat and gin ignore it")
     ap.add_argument("--batch_size", type=int, default=1024)
     ap.add_argument("--hidden_channels", type=int, default=128)
     ap.add_argument("--num_classes", type=int, default=19)
@@ -61,8 +63,12 @@ def main():
     # accepted so that the reference's command lines (examples/4GB_script.sh, Cache_compare_script.sh, Distribution_compare_script.sh) run as they are
     ap.add_argument("--num_layers", type=int, default=None, help="must equal the number of fan-outs when given")
     ap.add_argument("--feat_cpu", action="store_true", help="features in pinned host memory: always the case here (the NVMe tier is out of scope)")
-    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "sage", "gcn"],
-                    help="sage: GraphSAGE (mean); gat: GAT with --num_heads heads (native attention aggregation); gcn: GraphConv, norm='both'")
+    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "sage", "gcn", "gin"],
+                    help="sage: GraphSAGE (--sage_aggregator); gat: GAT with --num_heads heads (native attention aggregation); gcn: GraphConv, "
+                         "norm='both'; gin: GINConv layers (--gin_aggregator), an MLP in each")
+    ap.add_argument("--sage_aggregator", type=str, default="mean", choices=["mean", "gcn", "pool"],
+                    help="aggregator of --model_type sage; pool: the maximum of relu(fc_pool(h)) over the neighbours (native max aggregation)")
+    ap.add_argument("--gin_aggregator", type=str, default="sum", choices=["sum", "max", "mean"], help="aggregator of --model_type gin")
     ap.add_argument("--num_heads", type=int, default=4, help="attention heads of --model_type gat")
     args = ap.parse_args()
     if args.num_layers is not None and args.num_layers != len(args.fan_out.split(",")) and args.num_layers != 2:
@@ -120,7 +126,7 @@ def main():
         edata, prob = {"w": w}, "w"
     if args.use_edge_weight and prob is None:
         ap.error("--use_edge_weight needs --edge_weights random")
-    ew = "w" if args.use_edge_weight and args.model_type != "gat" else None
+    ew = "w" if args.use_edge_weight and args.model_type not in ("gat", "gin") else None
     if args.sampler == "labor":
         if prob is not None:
             ap.error("--sampler labor does not sample by edge weight (--edge_weights)")
@@ -138,8 +144,10 @@ def main():
         model = GAT(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads).to(device)
     elif args.model_type == "gcn":
         model = GCN(args.dim, args.hidden_channels, args.num_classes, len(fan_out), edge_weight=ew).to(device)
-    elif ew is not None:
-        model = SAGE(args.dim, args.hidden_channels, args.num_classes, len(fan_out), edge_weight=ew).to(device)
+    elif args.model_type == "gin":
+        model = GIN(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.gin_aggregator).to(device)
+    elif ew is not None or args.sage_aggregator != "mean":
+        model = SAGE(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.sage_aggregator, edge_weight=ew).to(device)
     else:
         model = SageMean(args.dim, args.hidden_channels, args.num_classes, len(fan_out)).to(device)
     if comm.global_size > 1:

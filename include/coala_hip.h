@@ -467,6 +467,25 @@ int coala_block_weighted_sum_csr(int device, const int64_t* indptr, const int32_
                                  int64_t n_dst, int dim, void* stream);
 int coala_block_weighted_sum_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* w, const float* h_src,
                                           const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int dim, void* stream);
+/* Max aggregation (DGL's fn.max reducer: SAGEConv "pool", GINConv "max"): out[d, c] = max over the valid j of h_src[nbr[d, j], c], and
+ * arg[d, c] = the local source index of the winning slot (int32 [n_dst, dim], the only state the backward needs; NULL for inference:
+ * nothing is stored).  nbr int32 [n_dst, fanout] (-1 padded, fan-out 1..32), fp32 rows of `dim` floats; the CSR form takes the maximum
+ * over e in [indptr[d], indptr[d+1]), any degree, one wave per row.  The rule is torch.max(dim)'s: the running maximum starts from the
+ * first valid slot, and a later slot replaces it when its value is greater, or is NaN while the maximum is not.  So ties (+-0
+ * included) keep the first slot in slot order, a NaN propagates with arg at the first NaN, and a row of -inf gives -inf with a valid
+ * arg.  A row without a valid entry gives out = 0 and arg = -1 (DGL's reducer at zero in-degree).  Nothing is rounded and both forms
+ * run the same code: out and arg are deterministic, and bit-identical on any row both forms can express.  Bad shapes are refused with
+ * COALA_EINVAL (fan-out 1..32, dim >= 1, n_dst >= 0); n_dst == 0 launches nothing.
+ * Backward, one entry point for both forms: grad_src[arg[d, c], c] += grad_out[d, c] wherever arg[d, c] >= 0, hardware float atomics:
+ * the caller zeroes grad_src [n_src, dim], the order varies.
+ * Bytes per row of deg valid edges: forward reads deg * (4 dim + 4) and writes 4 dim (8 dim with arg); backward reads 8 dim and adds
+ * 4 dim through atomics. */
+int coala_block_max_aggregate(int device, const int32_t* nbr, const float* h_src, float* out, int32_t* arg, int64_t n_dst, int fanout, int dim,
+                              void* stream);
+int coala_block_max_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int32_t* arg,
+                                  int64_t n_dst, int dim, void* stream);
+int coala_block_max_aggregate_backward(int device, const int32_t* arg, const float* grad_out, float* grad_src, int64_t n_dst, int dim,
+                                       void* stream);
 /* GAT attention aggregation (DGL GATConv's message step; its projections are dense and stay outside).  For dst d, head h and the
  * valid in-edges j of d with source s_j:
  *   z_j = el[s_j, h] + er[d, h];  e_j = leaky_relu(z_j, negative_slope);  a_j = exp(e_j - m) / sum_k exp(e_k - m), m = max_k e_k;
