@@ -1,6 +1,6 @@
 """Autograd wrappers of the native block ops that `Block` (sampler.py) hands to a model: mean aggregation (SAGEConv's "mean"), weighted
 sum aggregation (DGL's u_mul_e_sum, the edge_weight= path of GraphConv / SAGEConv), max aggregation (DGL's fn.max: SAGEConv's "pool",
-GINConv's "max") and GAT attention aggregation, on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the
+GINConv's "max"), the relation-typed sum (RelGraphConv's message step) and GAT attention aggregation, on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the
 kernels are in coala-gnn_amd/csrc/coala_block_ops.hip (C ABI: coala_block_*)."""
 import torch
 
@@ -117,6 +117,65 @@ class _WeightedSumCSR(torch.autograd.Function):
                                                                grad_w.data_ptr() if need_w else None, indptr.numel() - 1, g.shape[1],
                                                                current_stream()))
         return grad_src, grad_w, None, None
+
+
+def _rel_backward(ctx, grad_out, h, etype, w, entry, head):
+    """Both gradients of the relation-typed sum in one launch (coala_block_rel_sum[_csr]_backward); `head` holds the arguments that
+    describe the block.  A gradient nobody asked for is neither computed nor allocated; w None: no grad_w."""
+    need_src, need_w = ctx.needs_input_grad[0], w is not None and ctx.needs_input_grad[1]
+    if not need_src and not need_w:
+        return None, None
+    g = grad_out.contiguous()
+    grad_src = torch.zeros_like(h) if need_src else None
+    grad_w = torch.empty_like(w) if need_w else None
+    _capi.check(entry(g.device.index or 0, *head, etype.data_ptr(), w.data_ptr() if w is not None else None, h.data_ptr(), g.data_ptr(),
+                      grad_src.data_ptr() if need_src else None, grad_w.data_ptr() if need_w else None, *ctx.tail, current_stream()))
+    return grad_src, grad_w
+
+
+class _RelSum(torch.autograd.Function):
+    """out[d, r] = sum over the valid j with etype[d, j] == r of w[d, j] * h_src[nbr[d, j]] (coala_block_rel_sum): [n_dst, R, dim], one
+    kernel forward, one backward that gives grad_src and grad_w together.  w None: unit weights (a null pointer), and no grad_w."""
+
+    @staticmethod
+    def forward(ctx, h_src, w, nbr, etype, num_rels):
+        h = h_src.contiguous()
+        w = w.contiguous() if w is not None else None
+        n_dst, fanout = nbr.shape
+        out = torch.empty((n_dst, num_rels, h.shape[1]), dtype=torch.float32, device=h.device)
+        _capi.check(_lib.coala_block_rel_sum(h.device.index or 0, nbr.data_ptr(), etype.data_ptr(), w.data_ptr() if w is not None else None,
+                                             h.data_ptr(), out.data_ptr(), n_dst, fanout, num_rels, h.shape[1], current_stream()))
+        ctx.save_for_backward(*((h, nbr, etype) + ((w,) if w is not None else ())))
+        ctx.tail = (n_dst, fanout, num_rels, h.shape[1])
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        h, nbr, etype, *w = ctx.saved_tensors
+        return _rel_backward(ctx, grad_out, h, etype, w[0] if w else None, _lib.coala_block_rel_sum_backward, (nbr.data_ptr(),)) + (None,) * 3
+
+
+class _RelSumCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_rel_sum_csr): etype and w have one value per entry of indices."""
+
+    @staticmethod
+    def forward(ctx, h_src, w, indptr, indices, etype, num_rels):
+        h = h_src.contiguous()
+        w = w.contiguous() if w is not None else None
+        n_dst = indptr.numel() - 1
+        out = torch.empty((n_dst, num_rels, h.shape[1]), dtype=torch.float32, device=h.device)
+        _capi.check(_lib.coala_block_rel_sum_csr(h.device.index or 0, indptr.data_ptr(), indices.data_ptr(), etype.data_ptr(),
+                                                 w.data_ptr() if w is not None else None, h.data_ptr(), out.data_ptr(), n_dst, num_rels,
+                                                 h.shape[1], current_stream()))
+        ctx.save_for_backward(*((h, indptr, indices, etype) + ((w,) if w is not None else ())))
+        ctx.tail = (n_dst, num_rels, h.shape[1])
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        h, indptr, indices, etype, *w = ctx.saved_tensors
+        return _rel_backward(ctx, grad_out, h, etype, w[0] if w else None, _lib.coala_block_rel_sum_csr_backward,
+                             (indptr.data_ptr(), indices.data_ptr())) + (None,) * 4
 
 
 def _max_backward(ctx, grad_out):

@@ -3,14 +3,16 @@ used by bench.py's epoch leg and the tests; it stands where examples/models.py:D
 training script (examples/sbatch_ssd_gnn_train.py:98-145).  GAT and GCN mirror the reference's examples/models.py:GAT and :GCN on
 COALA_GNN.nn's GATConv and GraphConv (--model_type gat|gcn); GAT's attention step is a native kernel (Block.gat_aggregate).  GCN and
 SAGE take edge_weight=<edata key> and then hand block.edata[key] to their layers (blocks sampled with NeighborSampler(edge_ids=True)).
-SAGE(aggregator_type='pool') and GIN (--model_type gin) are the models on the native max aggregation (Block.max_aggregate)."""
+SAGE(aggregator_type='pool') and GIN (--model_type gin) are the models on the native max aggregation (Block.max_aggregate).  RGCN
+(--model_type rgcn) mirrors examples/models.py:RGCN on a homogenised graph: RelGraphConv layers, one weight matrix per edge type, on the
+native relation-typed sum (Block.rel_sum_aggregate)."""
 import time
 
 import torch
 
-from .nn import GATConv, GINConv, GraphConv, SAGEConv
+from .nn import GATConv, GINConv, GraphConv, RelGraphConv, SAGEConv
 
-__all__ = ["SageMean", "SAGE", "GAT", "GCN", "GIN", "train_steps", "FlatGradAllReduce"]
+__all__ = ["SageMean", "SAGE", "GAT", "GCN", "GIN", "RGCN", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -106,6 +108,41 @@ class GIN(torch.nn.Module):
             h = layer(block, (h, block.dst_rows(h)))
             if i + 1 < len(self.layers):
                 h = torch.relu(h)
+        return h
+
+
+class RGCN(torch.nn.Module):
+    """R-GCN on a homogenised heterograph (one id space, one feature table, an integer type per edge): num_layers RelGraphConv layers
+    with a self-loop, dropout then relu between them.  Every layer reads its edge types from block.edata[etype_key] -- gathered from
+    graph.edata through the block's edge ids, so the blocks must come from a sampler made with edge_ids=True -- and normalises every
+    message by 1 / c_{d,r}, the number of d's in-edges of that relation within the block (Block.rel_in_degrees): the R-GCN paper's
+    per-relation mean."""
+
+    def __init__(self, in_feats, h_feats, num_classes, num_layers, num_rels, regularizer=None, num_bases=None, dropout=0.2, etype_key="etype"):
+        super().__init__()
+        dims = [in_feats] + [h_feats] * (num_layers - 1) + [num_classes]
+        self.layers = torch.nn.ModuleList(RelGraphConv(dims[i], dims[i + 1], num_rels, regularizer, num_bases) for i in range(num_layers))
+        self.dropout = torch.nn.Dropout(dropout)
+        self.num_rels, self.etype_key = num_rels, etype_key
+
+    def forward(self, blocks, x):
+        h = x
+        for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+            if "_ID" not in block.edata:
+                raise ValueError("RGCN needs the edge ids of its blocks to find their edge types: make the sampler with edge_ids=True")
+            etype = block.edata[self.etype_key].to(h.device)
+            t = etype.to(torch.int64)
+            cnt = block.rel_in_degrees(etype, self.num_rels).to(h.device)
+            in_range = (t >= 0) & (t < self.num_rels)
+            rows = torch.arange(block.num_dst, device=h.device)
+            if block.nbr is None:
+                rows = torch.repeat_interleave(rows, (block.indptr[1:] - block.indptr[:-1]).to(h.device))
+            else:
+                rows = rows.unsqueeze(1).expand_as(t)
+            norm = 1.0 / cnt[rows, t.clamp(0, self.num_rels - 1)].clamp_min(1).to(h.dtype) * in_range.to(h.dtype)
+            h = layer(block, (h, block.dst_rows(h)), etype, norm)
+            if i + 1 < len(self.layers):
+                h = torch.relu(self.dropout(h))
         return h
 
 

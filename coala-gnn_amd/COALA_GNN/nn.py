@@ -1,4 +1,4 @@
-"""GATConv, GraphConv, SAGEConv and GINConv on the native Block objects, for the reference's GAT and GCN models (examples/models.py;
+"""GATConv, GraphConv, SAGEConv, GINConv and RelGraphConv on the native Block objects, for the reference's GAT and GCN models (examples/models.py;
 DGL is not installed on the MI355X image) and for DGL models ported to them.  All take (block, (h_src, h_dst)) as DGL's modules do on
 a block.
 
@@ -6,10 +6,12 @@ GATConv's projections are dense and stay in torch; its attention step (score, pe
 Block.gat_aggregate, a native kernel on both block forms.  GraphConv reduces to Block.mean_aggregate times the in-degree.  With
 edge_weight= (one value per neighbour slot, e.g. block.edata['w'] of a block sampled with edge_ids=True) GraphConv and SAGEConv
 aggregate with Block.weighted_sum_aggregate, DGL's u_mul_e_sum.  SAGEConv's 'pool' and GINConv's 'max' take their maximum with
-Block.max_aggregate (DGL's fn.max), a native kernel as well; GINConv's 'sum' is Block.weighted_sum_aggregate with unit weights."""
+Block.max_aggregate (DGL's fn.max), a native kernel as well; GINConv's 'sum' is Block.weighted_sum_aggregate with unit weights.
+RelGraphConv (one weight matrix per edge type) sums the messages per relation with Block.rel_sum_aggregate, a native kernel, and applies
+all its weight matrices in one GEMM."""
 import torch
 
-__all__ = ["GATConv", "GraphConv", "SAGEConv", "GINConv"]
+__all__ = ["GATConv", "GraphConv", "SAGEConv", "GINConv", "RelGraphConv"]
 
 
 class GATConv(torch.nn.Module):
@@ -222,3 +224,92 @@ class GINConv(torch.nn.Module):
         if self.activation is not None:
             rst = self.activation(rst)
         return rst
+
+
+class _RelWeight(torch.nn.Module):
+    """The per-relation weights of RelGraphConv under DGL's name `linear_r` (dgl.nn.TypedLinear's parameters): W [num_rels, in, out],
+    or with regularizer='basis' W [num_bases, in, out] and coeff [num_rels, num_bases]."""
+
+    def __init__(self, in_feat, out_feat, num_rels, regularizer, num_bases):
+        super().__init__()
+        self.in_feat, self.out_feat, self.num_rels = in_feat, out_feat, num_rels
+        if regularizer is None:
+            self.W = torch.nn.Parameter(torch.empty(num_rels, in_feat, out_feat))
+        else:
+            self.W = torch.nn.Parameter(torch.empty(num_bases, in_feat, out_feat))
+            self.coeff = torch.nn.Parameter(torch.empty(num_rels, num_bases))
+        self.regularizer = regularizer
+        self.reset_parameters()
+
+    def reset_parameters(self):   # dgl.nn.TypedLinear.reset_parameters
+        with torch.no_grad():
+            bound = 1.0 / self.in_feat ** 0.5
+            self.W.uniform_(-bound, bound)
+            if self.regularizer == "basis":
+                torch.nn.init.xavier_uniform_(self.coeff, gain=torch.nn.init.calculate_gain("relu"))
+
+    def weight(self):
+        """[num_rels, in, out]: W itself, or W_r = sum_b coeff[r, b] W[b]"""
+        if self.regularizer is None:
+            return self.W
+        return (self.coeff @ self.W.view(self.W.shape[0], -1)).view(self.num_rels, self.in_feat, self.out_feat)
+
+
+class RelGraphConv(torch.nn.Module):
+    """Relational graph convolution (Schlichtkrull et al., "Modeling Relational Data with Graph Convolutional Networks") on a block,
+    DGL 1.x RelGraphConv's signature: forward(block, feat, etypes, norm=None) with
+        out[d] = sum_j norm_j * h_src[s_j] @ W[etypes_j]
+    over the valid in-edges j of d, then, in DGL's order: layer norm, + h_bias, + h_dst[d] @ loop_weight, activation, dropout.
+    feat is h_src or (h_src, h_dst); without h_dst the destination rows are block.dst_rows(h_src).  etypes (any integer dtype) and norm
+    have one value per neighbour slot, shaped like block.edata['_ID'] -- e.g. block.edata['etype'] of a block sampled with
+    edge_ids=True; norm is also taken as [E, 1], as DGL passes it.  An edge whose type is outside [0, num_rels) sends nothing.
+    The messages are never formed: Block.rel_sum_aggregate sums norm_j * h_src[s_j] per (destination, relation) in one native kernel,
+    and  out = that.view(num_dst, num_rels * in_feat) @ W.view(num_rels * in_feat, out_feat)  applies every relation's matrix in one GEMM.
+    regularizer: None -- W [num_rels, in_feat, out_feat]; 'basis' -- W [num_bases, in_feat, out_feat] and coeff [num_rels, num_bases],
+    W_r = sum_b coeff[r, b] W[b] (num_bases defaults to num_rels).  'bdd' is not provided.
+    Parameters, with the names and shapes of DGL 1.x so that such a state_dict loads:
+        linear_r.W, linear_r.coeff ('basis' only), h_bias [out_feat] (bias=True), loop_weight [in_feat, out_feat] (self_loop=True),
+        layer_norm_weight.weight / layer_norm_weight.bias [out_feat] (layer_norm=True).
+    The names are those of DGL's source (dgl/nn/pytorch/conv/relgraphconv.py and linear.py) as recorded; DGL is not installed where
+    this was written, so no checkpoint saved by DGL has been loaded.
+    Initialisation, DGL's: W uniform in +-1/sqrt(in_feat), coeff and loop_weight Xavier-uniform with the gain of relu, h_bias zero."""
+
+    def __init__(self, in_feat, out_feat, num_rels, regularizer=None, num_bases=None, bias=True, activation=None, self_loop=True,
+                 dropout=0.0, layer_norm=False):
+        super().__init__()
+        if isinstance(num_rels, bool) or not isinstance(num_rels, int) or not 1 <= num_rels <= 64:
+            raise ValueError(f"num_rels {num_rels!r}: 1..64 relations")
+        if regularizer == "bdd":
+            raise ValueError("regularizer 'bdd' (block-diagonal decomposition) is not provided: None or 'basis'")
+        if regularizer not in (None, "basis"):
+            raise ValueError(f"regularizer {regularizer!r}: None or 'basis'")
+        if regularizer == "basis":
+            num_bases = num_rels if num_bases is None else int(num_bases)
+            if num_bases < 1:
+                raise ValueError("num_bases must be >= 1")
+        self.in_feat, self.out_feat, self.num_rels = in_feat, out_feat, num_rels
+        self.linear_r = _RelWeight(in_feat, out_feat, num_rels, regularizer, num_bases)
+        self.h_bias = torch.nn.Parameter(torch.zeros(out_feat)) if bias else None
+        self.loop_weight = torch.nn.Parameter(torch.empty(in_feat, out_feat)) if self_loop else None
+        if self_loop:
+            torch.nn.init.xavier_uniform_(self.loop_weight, gain=torch.nn.init.calculate_gain("relu"))
+        self.layer_norm_weight = torch.nn.LayerNorm(out_feat, elementwise_affine=True) if layer_norm else None
+        self.activation = activation
+        self.dropout = torch.nn.Dropout(dropout)
+
+    def forward(self, block, feat, etypes, norm=None):
+        h_src, h_dst = feat if isinstance(feat, (tuple, list)) else (feat, None)
+        if norm is not None and norm.dim() == etypes.dim() + 1 and norm.shape[-1] == 1:
+            norm = norm.squeeze(-1)
+        agg = block.rel_sum_aggregate(h_src, etypes, self.num_rels, norm)                       # [num_dst, R, in]
+        W = self.linear_r.weight().to(agg.dtype)
+        h = agg.reshape(agg.shape[0], self.num_rels * self.in_feat) @ W.reshape(self.num_rels * self.in_feat, self.out_feat)
+        if self.layer_norm_weight is not None:
+            h = self.layer_norm_weight(h)
+        if self.h_bias is not None:
+            h = h + self.h_bias
+        if self.loop_weight is not None:
+            h = h + (block.dst_rows(h_src) if h_dst is None else h_dst) @ self.loop_weight
+        if self.activation is not None:
+            h = self.activation(h)
+        return self.dropout(h)

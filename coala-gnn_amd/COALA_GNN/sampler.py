@@ -11,8 +11,8 @@ import torch
 
 from COALA_GNN_Pybind import _capi, current_stream
 
-from .block_ops import (_GatAggregate, _GatAggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate, _MeanAggregateCSR, _WeightedSum,
-                        _WeightedSumCSR)
+from .block_ops import (_GatAggregate, _GatAggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate, _MeanAggregateCSR, _RelSum,
+                        _RelSumCSR, _WeightedSum, _WeightedSumCSR)
 
 __all__ = ["NeighborSampler", "LaborSampler", "CSCGraph", "Block", "ITEM_LIMIT", "EID"]
 
@@ -234,6 +234,73 @@ class Block(object):
         valid = (self.nbr >= 0).to(device=dev, dtype=h_src.dtype)
         idx = self.nbr.clamp_min(0).to(device=dev, dtype=torch.int64)
         return (h_src[idx] * (w * valid).unsqueeze(-1)).sum(1)
+
+    def _rel_args(self, etype, num_rels, w):
+        """The checks of rel_sum_aggregate / rel_sum_aggregate_torch / rel_in_degrees -> the block's slot array."""
+        slots = self.indices if self.nbr is None else self.nbr
+        if isinstance(num_rels, bool) or not isinstance(num_rels, int) or not 1 <= num_rels <= 64:
+            raise ValueError(f"num_rels {num_rels!r}: 1..64 relations")
+        if not isinstance(etype, torch.Tensor) or etype.is_floating_point() or etype.is_complex() or etype.dtype == torch.bool:
+            raise ValueError("edge types must be an integer tensor")
+        if tuple(etype.shape) != tuple(slots.shape):
+            raise ValueError(f"edge types of shape {tuple(etype.shape)}: this block takes one per neighbour slot, {tuple(slots.shape)}")
+        if w is not None and tuple(w.shape) != tuple(slots.shape):
+            raise ValueError(f"edge weights of shape {tuple(w.shape)}: this block takes one per neighbour slot, {tuple(slots.shape)}")
+        return slots
+
+    def rel_sum_aggregate(self, h_src, etype, num_rels, w=None):
+        """Sum of the sampled neighbours' rows per relation, for every dst node: [num_dst, num_rels, dim], out[d, r] = the sum over d's
+        valid edges j of type etype_j == r of w_j * h_src[s_j] (RelGraphConv's message step: the result viewed as [num_dst, R * dim]
+        times W viewed as [R * dim, out] is sum_j w_j W[etype_j] h_src[s_j]).  etype: any integer dtype, one value per neighbour slot
+        -- the shape of edata['_ID'] -- converted once to contiguous int32; w: one weight per slot, or None for 1.  A padding slot's
+        type and weight are not used; a valid edge whose type is outside [0, num_rels) contributes nothing; a relation absent from a
+        row, and a row without an edge, give zeros.  Native kernels, with gradients for h_src and w, under the conditions of
+        weighted_sum_aggregate; rel_sum_aggregate_torch otherwise."""
+        self._rel_args(etype, num_rels, w)
+        native = (h_src.is_cuda and h_src.dtype == torch.float32 and h_src.dim() == 2 and etype.is_cuda
+                  and (w is None or (w.is_cuda and w.dtype == torch.float32)))
+        if native:
+            lo, hi = -(1 << 31), (1 << 31) - 1   # a type that int32 cannot hold is out of range either way: -1
+            t32 = etype if etype.dtype == torch.int32 else torch.where((etype < lo) | (etype > hi), -1, etype).to(torch.int32)
+            if self.nbr is None:
+                if self.indptr.is_cuda and self.indices.is_cuda:
+                    return _RelSumCSR.apply(h_src, w, self.indptr.contiguous(), self.indices.contiguous(), t32.contiguous(), num_rels)
+            elif self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
+                return _RelSum.apply(h_src, w, self.nbr, t32.contiguous(), num_rels)
+        return self.rel_sum_aggregate_torch(h_src, etype, num_rels, w)
+
+    def rel_sum_aggregate_torch(self, h_src, etype, num_rels, w=None):
+        """rel_sum_aggregate in plain torch, any device and dtype, both block forms, the same skip rules: its fallback, and its
+        reference.  It gathers an [E, dim] intermediate and index_adds it into num_dst * num_rels rows."""
+        slots = self._rel_args(etype, num_rels, w)
+        dev = h_src.device
+        src = slots.reshape(-1).to(device=dev, dtype=torch.int64)
+        t = etype.reshape(-1).to(device=dev, dtype=torch.int64)
+        if self.nbr is None:
+            deg = self.indptr[1:] - self.indptr[:-1]
+            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg).to(dev)
+        else:
+            rows = torch.arange(self.num_dst, device=dev).repeat_interleave(self.nbr.shape[1])
+        keep = (src >= 0) & (t >= 0) & (t < num_rels)
+        msg = h_src[src[keep]]
+        if w is not None:
+            msg = msg * w.reshape(-1).to(device=dev, dtype=h_src.dtype)[keep].view((-1,) + (1,) * (h_src.dim() - 1))
+        out = torch.zeros((self.num_dst * num_rels,) + tuple(h_src.shape[1:]), dtype=h_src.dtype, device=dev)
+        return out.index_add(0, rows[keep] * num_rels + t[keep], msg).view((self.num_dst, num_rels) + tuple(h_src.shape[1:]))
+
+    def rel_in_degrees(self, etype, num_rels):
+        """Valid in-edges of every destination node per relation: int64 [num_dst, num_rels], the c_{i,r} of the R-GCN paper; an edge
+        whose type is outside [0, num_rels) is counted nowhere."""
+        slots = self._rel_args(etype, num_rels, None)
+        dev = slots.device
+        src, t = slots.reshape(-1), etype.reshape(-1).to(device=dev, dtype=torch.int64)
+        if self.nbr is None:
+            deg = self.indptr[1:] - self.indptr[:-1]
+            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg).to(dev)
+        else:
+            rows = torch.arange(self.num_dst, device=dev).repeat_interleave(self.nbr.shape[1])
+        keep = (src >= 0) & (t >= 0) & (t < num_rels)
+        return torch.bincount(rows[keep] * num_rels + t[keep], minlength=self.num_dst * num_rels).view(self.num_dst, num_rels)
 
     def max_aggregate(self, h_src):
         """Element-wise maximum of the sampled neighbours' rows for every dst node: fp32 [num_dst, dim] (DGL's fn.max: SAGEConv 'pool',

@@ -117,6 +117,14 @@ def powerlaw_csc(num_nodes, avg_degree, seed=0, device="cuda", skew=3.0, max_deg
     return indptr, src
 
 
+def edge_types_by_source(indices, num_rels):
+    """int64 [E] synthetic edge types in CSC order: indices % num_rels.  The source node's "type" (its id modulo num_rels) fixes the
+    relation of every edge leaving it, as in a homogenised heterograph whose relations are told apart by their source node type."""
+    if not 1 <= int(num_rels):
+        raise ValueError("num_rels must be >= 1")
+    return indices.to(torch.int64) % int(num_rels)
+
+
 def community_csc(num_nodes, avg_degree, community=2048, p_in=0.9, seed=0, device="cuda", max_degree=None):
     """Seeded CSC graph with planted communities (blocks of `community` consecutive ids): an in-neighbour comes from the node's
     own block with probability p_in, from anywhere otherwise; in-degrees Pareto as in powerlaw_csc.  The power-law generator

@@ -134,6 +134,10 @@ SYMBOLS = {
     "coala_block_max_aggregate": (_I, [_I, _VP, _VP, _VP, _VP, _I64, _I, _I, _VP]),
     "coala_block_max_aggregate_csr": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _I64, _I, _VP]),
     "coala_block_max_aggregate_backward": (_I, [_I, _VP, _VP, _VP, _I64, _I, _VP]),
+    "coala_block_rel_sum": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _I, _VP]),
+    "coala_block_rel_sum_backward": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _I, _VP]),
+    "coala_block_rel_sum_csr": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _VP]),
+    "coala_block_rel_sum_csr_backward": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _VP]),
     "coala_block_mean_aggregate_csr": (_I, [_I, _VP, _VP, _VP, _VP, _I64, _I, _VP]),
     "coala_block_mean_aggregate_csr_backward": (_I, [_I, _VP, _VP, _VP, _VP, _I64, _I, _VP]),
     "coala_block_gat_aggregate": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _I, C.c_float, _VP]),

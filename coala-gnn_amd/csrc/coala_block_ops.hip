@@ -1,6 +1,7 @@
 // coala_block_ops.hip -- what a model computes on a sampled block (coala_sampler.hip makes the blocks), for gfx950: mean aggregation
 // (DGL's SAGEConv "mean"), weighted sum aggregation (DGL's u_mul_e_sum: GraphConv / SAGEConv with edge_weight=), max aggregation
-// (DGL's fn.max: SAGEConv "pool", GINConv "max") and GAT attention aggregation (GATConv's message step), forward and backward, on
+// (DGL's fn.max: SAGEConv "pool", GINConv "max"), the relation-typed sum (RelGraphConv's message step) and GAT attention aggregation
+// (GATConv's message step), forward and backward, on
 // fixed blocks (nbr_local[n_dst, fanout], -1 = no neighbour) and on the CSR blocks of full layers.  Stateless entry points: no
 // handle, every launch on the caller's stream.
 #include <hip/hip_runtime.h>
@@ -492,6 +493,132 @@ __global__ __launch_bounds__(kBlock) void max_aggregate_backward_kernel(const in
         }
 }
 
+// Relation-typed sum (DGL RelGraphConv's message step, before its weights): out[d, r, :] = sum over the valid edges j of row d with
+// etype_j == r of w_j * h_src[s_j, :], so that out.view(n_dst, R * dim) @ W.view(R * dim, out_dim) is sum_j w_j W[etype_j] h[s_j] in one
+// GEMM.  etype is laid out like the block's index array, and so is w (null: every weight is 1).  The weighted sum's mapping and its
+// arithmetic: one wave per destination row, a lane per 16 bytes, indices / types / weights read 64 at a time; a relation's sum runs in
+// slot order with one fma per term from +0, so out[:, r, :] has the bits of weighted_sum_kernel with w * [etype == r] (a term of weight
+// 0 leaves a finite fma accumulator as it is).  A wave cannot hold R * dim accumulators, so it walks r = 0 .. R-1: every lane ORs the
+// types of its slots into a 64-bit mask (hence R <= 64) and a ballot tells whether r is in the row; an absent relation stores zeros, a
+// present one takes the ballot of its edges in each chunk and visits only those, in ascending slot order.  A row of at most 64 slots
+// keeps its (index, type, weight) words in registers; a longer one streams them again per present relation (12 bytes an edge).  Every
+// h_src row is read once.  A valid slot whose type is outside [0, R) matches no r: it contributes nothing, and its type is only
+// ever compared.  Per row of deg edges: reads deg * (4 dim + 12), writes 4 dim R.
+template <int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void rel_sum_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                         const int32_t* __restrict__ etype, const float* __restrict__ w, int fanout,
+                                                         const float* __restrict__ h_src, float* __restrict__ out, int64_t n_dst, int num_rels,
+                                                         int dim) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int units = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        // the first chunk stays in registers; -1 as a type matches no relation (padding, past the end, out of range)
+        int32_t mine0 = -1, t0 = -1;
+        float w0 = 1.0f;
+        uint64_t seen = 0; // the relations among this lane's slots
+        for (int64_t e0 = beg; e0 < end; e0 += 64) {
+            if (e0 + lane >= end) continue;
+            const int32_t s = idx[e0 + lane];
+            int32_t t = s >= 0 ? etype[e0 + lane] : -1;
+            if (t < 0 || t >= num_rels) t = -1;
+            if (t >= 0) seen |= 1ull << t;
+            if (e0 == beg) {
+                mine0 = s, t0 = t;
+                if (w && t >= 0) w0 = w[e0 + lane];
+            }
+        }
+        for (int r = 0; r < num_rels; ++r) {
+            float* o = out + (d * num_rels + r) * dim;
+            if (!__ballot((seen >> r) & 1)) { // wave-uniform
+                for (int u = lane; u < units; u += 64) *reinterpret_cast<vf*>(o + (int64_t)u * VEC) = vf(0.0f);
+                continue;
+            }
+            for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+                const int u = u0 + lane;
+                vf acc = vf(0.0f);
+                for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                    int32_t mine = mine0, t = t0;
+                    float wm = w0;
+                    if (e0 != beg) { // wave-uniform
+                        const bool have = e0 + lane < end;
+                        mine = have ? idx[e0 + lane] : -1;
+                        t = have && mine >= 0 ? etype[e0 + lane] : -1;
+                        wm = w && t == r ? w[e0 + lane] : 1.0f;
+                    }
+                    uint64_t hit = __ballot(t == r); // t == r >= 0 only on a valid slot
+                    while (hit) {
+                        const int j = __builtin_ctzll(hit);
+                        hit &= hit - 1;
+                        const int32_t s = __shfl(mine, j);
+                        const float wj = __shfl(wm, j);
+                        if (u < units) axpy<VEC>(acc, wj, *reinterpret_cast<const vf*>(h_src + (int64_t)s * dim + (int64_t)u * VEC));
+                    }
+                }
+                if (u < units) *reinterpret_cast<vf*>(o + (int64_t)u * VEC) = acc;
+            }
+        }
+    }
+}
+
+// Both gradients of the relation-typed sum in one launch, either of them optional (null); with g_j = grad_out[d, etype_j, :]:
+//   grad_src[s_j] += w_j * g_j          hardware float atomics into a buffer the caller zeroed, a lane per float (the mean backward's
+//                                       mapping: an atomic instruction of the wave covers 256 contiguous bytes); the order varies;
+//   grad_w[slot j] = <g_j, h_src[s_j]>   the weighted sum backward's arithmetic on its lanes -- each lane sums its 16-byte units with
+//                                       fmas, a butterfly adds the 64 lanes, lane j of the chunk keeps edge j's value -- so with R = 1
+//                                       it gives that kernel's bits; 0 on a padding slot and on a type outside [0, R).
+// One wave per row; only the edges with a type in range are visited.  g_j is read from the cache per edge, in each of the two layouts.
+template <int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void rel_sum_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                  const int32_t* __restrict__ etype, const float* __restrict__ w, int fanout,
+                                                                  const float* __restrict__ h_src, const float* __restrict__ grad_out,
+                                                                  float* __restrict__ grad_src, float* __restrict__ grad_w, int64_t n_dst,
+                                                                  int num_rels, int dim) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int units = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
+            const bool have = e0 + lane < end;
+            const int32_t mine = have ? idx[e0 + lane] : -1;
+            int32_t t = mine >= 0 ? etype[e0 + lane] : -1;
+            if (t < 0 || t >= num_rels) t = -1;
+            const float wm = w && t >= 0 ? w[e0 + lane] : 1.0f;
+            float gw = 0.0f;
+            uint64_t todo = __ballot(t >= 0);
+            while (todo) {
+                const int j = __builtin_ctzll(todo);
+                todo &= todo - 1;
+                const int32_t s = __shfl(mine, j);
+                const float* g = grad_out + (d * num_rels + __shfl(t, j)) * dim;
+                if (grad_src) { // wave-uniform
+                    const float wj = __shfl(wm, j);
+                    for (int c = lane; c < dim; c += 64) unsafeAtomicAdd(grad_src + (int64_t)s * dim + c, wj * g[c]);
+                }
+                if (grad_w) { // wave-uniform
+                    float part = 0.0f;
+                    for (int u = lane; u < units; u += 64) {
+                        const vf gv = *reinterpret_cast<const vf*>(g + (int64_t)u * VEC);
+                        const vf hv = *reinterpret_cast<const vf*>(h_src + (int64_t)s * dim + (int64_t)u * VEC);
+                        for (int i = 0; i < VEC; ++i) part = __builtin_fmaf(gv[i], hv[i], part);
+                    }
+                    const float tot = wave_sum(part);
+                    if (lane == j) gw = tot;
+                }
+            }
+            if (grad_w && have) grad_w[e0 + lane] = gw;
+        }
+    }
+}
+
 } // namespace
 
 namespace {
@@ -729,6 +856,74 @@ int coala_block_max_aggregate_backward(int device, const int32_t* arg, const flo
                        grad_src, n_dst, dim);
     HIPCHK(hipGetLastError());
     return COALA_OK;
+}
+
+} // extern "C"
+
+namespace {
+constexpr int kMaxRels = 64; // a row's relations are a 64-bit mask
+
+template <bool CSR>
+int rel_sum_launch(int device, const int64_t* indptr, const int32_t* idx, const int32_t* etype, const float* w, int fanout, const float* h_src,
+                   float* out, int64_t n_dst, int num_rels, int dim, void* stream) {
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !etype || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
+    dispatch_vec(vec4_ok(dim, h_src, out), [&](auto vec) {
+        hipLaunchKernelGGL((rel_sum_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, etype, w, fanout, h_src, out,
+                           n_dst, num_rels, dim);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+template <bool CSR>
+int rel_sum_backward_launch(int device, const int64_t* indptr, const int32_t* idx, const int32_t* etype, const float* w, int fanout,
+                            const float* h_src, const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int num_rels, int dim,
+                            void* stream) {
+    if (n_dst == 0 || (!grad_src && !grad_w)) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !etype || !grad_out || (grad_w && !h_src)) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
+    dispatch_vec(vec4_ok(dim, grad_out, grad_w ? h_src : nullptr), [&](auto vec) { // the weighted sum backward's choice: the same bits at R = 1
+        hipLaunchKernelGGL((rel_sum_backward_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, etype, w, fanout,
+                           h_src, grad_out, grad_src, grad_w, n_dst, num_rels, dim);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+bool rel_shape_ok(int64_t n_dst, int num_rels, int dim) { return n_dst >= 0 && dim >= 1 && num_rels >= 1 && num_rels <= kMaxRels; }
+} // namespace
+
+extern "C" {
+
+int coala_block_rel_sum(int device, const int32_t* nbr, const int32_t* etype, const float* w, const float* h_src, float* out, int64_t n_dst,
+                        int fanout, int num_rels, int dim, void* stream) {
+    if (!rel_shape_ok(n_dst, num_rels, dim) || fanout < 1 || fanout > 32)
+        return fail(COALA_EINVAL, "bad block shape (fan-out 1..32, relations 1..%d)", kMaxRels);
+    return rel_sum_launch<false>(device, nullptr, nbr, etype, w, fanout, h_src, out, n_dst, num_rels, dim, stream);
+}
+
+int coala_block_rel_sum_backward(int device, const int32_t* nbr, const int32_t* etype, const float* w, const float* h_src, const float* grad_out,
+                                 float* grad_src, float* grad_w, int64_t n_dst, int fanout, int num_rels, int dim, void* stream) {
+    if (!rel_shape_ok(n_dst, num_rels, dim) || fanout < 1 || fanout > 32)
+        return fail(COALA_EINVAL, "bad block shape (fan-out 1..32, relations 1..%d)", kMaxRels);
+    return rel_sum_backward_launch<false>(device, nullptr, nbr, etype, w, fanout, h_src, grad_out, grad_src, grad_w, n_dst, num_rels, dim, stream);
+}
+
+int coala_block_rel_sum_csr(int device, const int64_t* indptr, const int32_t* indices, const int32_t* etype, const float* w, const float* h_src,
+                            float* out, int64_t n_dst, int num_rels, int dim, void* stream) {
+    if (!rel_shape_ok(n_dst, num_rels, dim)) return fail(COALA_EINVAL, "bad block shape (relations 1..%d)", kMaxRels);
+    return rel_sum_launch<true>(device, indptr, indices, etype, w, 0, h_src, out, n_dst, num_rels, dim, stream);
+}
+
+int coala_block_rel_sum_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const int32_t* etype, const float* w,
+                                     const float* h_src, const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int num_rels,
+                                     int dim, void* stream) {
+    if (!rel_shape_ok(n_dst, num_rels, dim)) return fail(COALA_EINVAL, "bad block shape (relations 1..%d)", kMaxRels);
+    return rel_sum_backward_launch<true>(device, indptr, indices, etype, w, 0, h_src, grad_out, grad_src, grad_w, n_dst, num_rels, dim, stream);
 }
 
 } // extern "C"

@@ -9,6 +9,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --sampler labor --fan_out 10,10
   python examples/train_synthetic.py --sage_aggregator pool
   python examples/train_synthetic.py --model_type gin --gin_aggregator max
+  python examples/train_synthetic.py --model_type rgcn --num_rels 4 --rgcn_regularizer basis --num_bases 2
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -26,9 +27,9 @@ import torch  # noqa: E402
 
 from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
-from COALA_GNN.harness import GAT, GCN, GIN, SAGE, SageMean  # noqa: E402
+from COALA_GNN.harness import GAT, GCN, GIN, RGCN, SAGE, SageMean  # noqa: E402
 from COALA_GNN.sampler import LaborSampler, NeighborSampler  # noqa: E402
-from COALA_GNN.synthetic import alloc_pinned_table, powerlaw_csc  # noqa: E402
+from COALA_GNN.synthetic import alloc_pinned_table, edge_types_by_source, powerlaw_csc  # noqa: E402
 
 
 def main():
@@ -63,13 +64,17 @@ def main():
     # accepted so that the reference's command lines (examples/4GB_script.sh, Cache_compare_script.sh, Distribution_compare_script.sh) run as they are
     ap.add_argument("--num_layers", type=int, default=None, help="must equal the number of fan-outs when given")
     ap.add_argument("--feat_cpu", action="store_true", help="features in pinned host memory: always the case here (the NVMe tier is out of scope)")
-    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "sage", "gcn", "gin"],
+    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "sage", "gcn", "gin", "rgcn"],
                     help="sage: GraphSAGE (--sage_aggregator); gat: GAT with --num_heads heads (native attention aggregation); gcn: GraphConv, "
-                         "norm='both'; gin: GINConv layers (--gin_aggregator), an MLP in each")
+                         "norm='both'; gin: GINConv layers (--gin_aggregator), an MLP in each; rgcn: RelGraphConv layers, one weight matrix per edge "
+                         "type (--num_rels synthetic types, the source node's id modulo --num_rels; native relation-typed sum)")
     ap.add_argument("--sage_aggregator", type=str, default="mean", choices=["mean", "gcn", "pool"],
                     help="aggregator of --model_type sage; pool: the maximum of relu(fc_pool(h)) over the neighbours (native max aggregation)")
     ap.add_argument("--gin_aggregator", type=str, default="sum", choices=["sum", "max", "mean"], help="aggregator of --model_type gin")
     ap.add_argument("--num_heads", type=int, default=4, help="attention heads of --model_type gat")
+    ap.add_argument("--num_rels", type=int, default=4, help="edge types of --model_type rgcn (1..64)")
+    ap.add_argument("--rgcn_regularizer", type=str, default="none", choices=["none", "basis"], help="weight regularizer of --model_type rgcn")
+    ap.add_argument("--num_bases", type=int, default=None, help="bases of --rgcn_regularizer basis (default: --num_rels)")
     args = ap.parse_args()
     if args.num_layers is not None and args.num_layers != len(args.fan_out.split(",")) and args.num_layers != 2:
         ap.error("--num_layers does not match --fan_out")   # (the reference's own scripts pass --num_layers 2 with a 3-entry fan-out: tolerated)
@@ -126,15 +131,21 @@ def main():
         edata, prob = {"w": w}, "w"
     if args.use_edge_weight and prob is None:
         ap.error("--use_edge_weight needs --edge_weights random")
-    ew = "w" if args.use_edge_weight and args.model_type not in ("gat", "gin") else None
+    ew = "w" if args.use_edge_weight and args.model_type not in ("gat", "gin", "rgcn") else None
+    rgcn = args.model_type == "rgcn"
+    if rgcn:   # the edge types of a homogenised heterograph, in CSC order; the blocks find theirs through their edge ids
+        if not 1 <= args.num_rels <= 64:
+            ap.error("--num_rels must be 1..64")
+        edata = dict(edata, etype=edge_types_by_source(indices, args.num_rels))
+    edge_ids = ew is not None or rgcn
     if args.sampler == "labor":
         if prob is not None:
             ap.error("--sampler labor does not sample by edge weight (--edge_weights)")
-        sampler = LaborSampler(fan_out, layer_dependency=args.layer_dependency)
+        sampler = LaborSampler(fan_out, layer_dependency=args.layer_dependency, edge_ids=edge_ids)
     else:
         if args.layer_dependency:
             ap.error("--layer_dependency needs --sampler labor")
-        sampler = NeighborSampler(fan_out, prob=prob, edge_ids=ew is not None)                              # :70-72
+        sampler = NeighborSampler(fan_out, prob=prob, edge_ids=edge_ids)                            # :70-72
     g = sampler.make_graph(indptr, indices, ndata={"labels": labels}, edata=edata)
     train_loader = COALA_GNN_DataLoader(SSD_INFO(1, args.dim * 4, 1024, 0), nd, g, sampler, args.batch_size, args.dim, fan_out,
                                         args.cache_size, device, refresh_counter=args.refresh_counter,
@@ -146,6 +157,9 @@ def main():
         model = GCN(args.dim, args.hidden_channels, args.num_classes, len(fan_out), edge_weight=ew).to(device)
     elif args.model_type == "gin":
         model = GIN(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.gin_aggregator).to(device)
+    elif rgcn:
+        model = RGCN(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_rels,
+                     None if args.rgcn_regularizer == "none" else args.rgcn_regularizer, args.num_bases).to(device)
     elif ew is not None or args.sage_aggregator != "mean":
         model = SAGE(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.sage_aggregator, edge_weight=ew).to(device)
     else:
@@ -187,7 +201,7 @@ def main():
 
     # evaluation over the test nodes through a second loader, as the reference does (:156-195)
     test_nd = Node_Distributor(comm, test_ids, args.batch_size, *files, parsing_method=args.distribution)
-    eval_sampler = sampler if eval_fan_out == fan_out and prob is None else NeighborSampler(eval_fan_out, edge_ids=ew is not None)
+    eval_sampler = sampler if eval_fan_out == fan_out and prob is None else NeighborSampler(eval_fan_out, edge_ids=edge_ids)
     test_loader = COALA_GNN_DataLoader(SSD_INFO(1, args.dim * 4, 1024, 0), test_nd, g, eval_sampler, args.batch_size, args.dim, eval_fan_out,
                                        args.cache_size, device, refresh_counter=args.refresh_counter,
                                        cache_backend=args.cache_backend, sim_buf=feat, shuffle=False, num_rows=args.nodes)

@@ -486,6 +486,33 @@ int coala_block_max_aggregate_csr(int device, const int64_t* indptr, const int32
                                   int64_t n_dst, int dim, void* stream);
 int coala_block_max_aggregate_backward(int device, const int32_t* arg, const float* grad_out, float* grad_src, int64_t n_dst, int dim,
                                        void* stream);
+/* Relation-typed sum (the message step of DGL's RelGraphConv, before its weights): out[d, r, :] = sum over the valid j of row d with
+ * etype[d, j] == r of w[d, j] * h_src[nbr[d, j], :], so that out viewed as [n_dst, num_rels * dim] times W viewed as [num_rels * dim, o]
+ * is sum_j w_j W[etype_j] h_src[s_j] in one GEMM.  etype int32, one value per neighbour slot, laid out like nbr ([n_dst, fanout]) or
+ * like indices ([E]); w fp32 in the same layout, or NULL: every weight is 1; out fp32 [n_dst, num_rels, dim], written whole: a
+ * relation absent from a row stores exact zeros, and so does a row without a valid entry.  A padding slot's etype and w are never used;
+ * a valid slot whose type is outside [0, num_rels) contributes nothing and is never used as an index.  The sum of a relation runs in
+ * slot order with one fma per term from +0, the weighted sum's arithmetic: on finite inputs out[:, r, :] has the bits of
+ * coala_block_weighted_sum with w * [etype == r] (with num_rels == 1 and every type 0: with w), and both forms run the same code:
+ * bit-identical on any row both can express.  Refused with COALA_EINVAL and nothing launched: fan-out outside 1..32, dim < 1,
+ * n_dst < 0, num_rels outside 1..64 (a row's relations are kept as a 64-bit mask); n_dst == 0 launches nothing.
+ * Backward, both gradients in one launch, either output may be NULL (not wanted); grad_out fp32 [n_dst, num_rels, dim]:
+ *   grad_src[s_j, :] += w_j * grad_out[d, etype_j, :]        hardware float atomics: the caller zeroes grad_src, the order varies;
+ *   grad_w[d, j] = <grad_out[d, etype_j, :], h_src[s_j, :]>   shaped like w, written whole, 0 on a padding slot and on a type out of
+ *                                                            range; deterministic, the same bits in both forms, and with num_rels
+ *                                                            == 1 those of coala_block_weighted_sum_backward.  h_src is read only
+ *                                                            when grad_w is given.
+ * Bytes per row of deg valid edges: forward reads deg * (4 dim + 12), plus 12 deg again per relation present when deg > 64, and writes
+ * 4 dim num_rels; backward reads 12 deg + 4 dim deg (+ 8 dim deg for grad_w), adds 4 dim deg through atomics and writes 4 per slot. */
+int coala_block_rel_sum(int device, const int32_t* nbr, const int32_t* etype, const float* w, const float* h_src, float* out, int64_t n_dst,
+                        int fanout, int num_rels, int dim, void* stream);
+int coala_block_rel_sum_backward(int device, const int32_t* nbr, const int32_t* etype, const float* w, const float* h_src, const float* grad_out,
+                                 float* grad_src, float* grad_w, int64_t n_dst, int fanout, int num_rels, int dim, void* stream);
+int coala_block_rel_sum_csr(int device, const int64_t* indptr, const int32_t* indices, const int32_t* etype, const float* w, const float* h_src,
+                            float* out, int64_t n_dst, int num_rels, int dim, void* stream);
+int coala_block_rel_sum_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const int32_t* etype, const float* w,
+                                     const float* h_src, const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int num_rels,
+                                     int dim, void* stream);
 /* GAT attention aggregation (DGL GATConv's message step; its projections are dense and stay outside).  For dst d, head h and the
  * valid in-edges j of d with source s_j:
  *   z_j = el[s_j, h] + er[d, h];  e_j = leaky_relu(z_j, negative_slope);  a_j = exp(e_j - m) / sum_k exp(e_k - m), m = max_k e_k;
