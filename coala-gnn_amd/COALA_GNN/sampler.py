@@ -181,28 +181,33 @@ class Block(object):
 
     def mean_aggregate(self, h_src):
         """Mean of the sampled neighbours' rows for every dst node: fp32 [num_dst, dim] (GraphSAGE 'mean').  Native kernel for
-        fp32 rows on the GPU (fan-out <= 32, or the ragged form of a full layer); plain torch otherwise."""
+        fp32 2-D rows on the GPU (fan-out <= 32, or the ragged form of a full layer); plain torch otherwise.  A tensor with more than
+        two dimensions ([num_src, H, D], GAT's output) takes the torch path, which keeps the trailing shape -- the rule of
+        weighted_sum_aggregate, max_aggregate and rel_sum_aggregate -- and is not flattened for the kernel, which reads shape[1] as
+        the row width."""
+        native = h_src.is_cuda and h_src.dtype == torch.float32 and h_src.dim() == 2
         if self.nbr is None:
-            if h_src.is_cuda and h_src.dtype == torch.float32 and self.indptr.is_cuda and self.indices.is_cuda:
+            if native and self.indptr.is_cuda and self.indices.is_cuda:
                 return _MeanAggregateCSR.apply(h_src, self.indptr.contiguous(), self.indices.contiguous())
-            return self.mean_aggregate_torch(h_src)
-        if h_src.is_cuda and h_src.dtype == torch.float32 and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
+        elif native and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
             return _MeanAggregate.apply(h_src, self.nbr)
         return self.mean_aggregate_torch(h_src)
 
     def mean_aggregate_torch(self, h_src):
+        """mean_aggregate in plain torch, any device and dtype, h_src [num_src, ...] -> [num_dst, ...]: its fallback, and its reference."""
+        ones = (1,) * (h_src.dim() - 1)
         if self.nbr is None:   # ragged: sum the rows of each segment, divide by its length (an empty segment gives zeros)
             deg = self.indptr[1:] - self.indptr[:-1]
             rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg)
             idx = self.indices.to(torch.int64)
-            valid = (idx >= 0).unsqueeze(-1).to(h_src.dtype)
+            valid = (idx >= 0).view((-1,) + ones).to(h_src.dtype)
             out = torch.zeros((self.num_dst,) + tuple(h_src.shape[1:]), dtype=h_src.dtype, device=h_src.device)
             out.index_add_(0, rows.to(h_src.device), h_src[idx.clamp_min(0).to(h_src.device)] * valid.to(h_src.device))
-            return out / deg.clamp_min(1).unsqueeze(-1).to(device=h_src.device, dtype=h_src.dtype)
-        valid = self.nbr >= 0
-        idx = self.nbr.clamp_min(0).to(torch.int64)
-        g = h_src[idx] * valid.unsqueeze(-1).to(h_src.dtype)
-        return g.sum(1) / valid.sum(1).clamp_min(1).unsqueeze(-1).to(h_src.dtype)
+            return out / deg.clamp_min(1).view((-1,) + ones).to(device=h_src.device, dtype=h_src.dtype)
+        valid = (self.nbr >= 0).to(h_src.device)
+        idx = self.nbr.clamp_min(0).to(device=h_src.device, dtype=torch.int64)
+        g = h_src[idx] * valid.view(tuple(valid.shape) + ones).to(h_src.dtype)
+        return g.sum(1) / valid.sum(1).clamp_min(1).view((-1,) + ones).to(h_src.dtype)
 
     def weighted_sum_aggregate(self, h_src, w):
         """Sum of the sampled neighbours' rows, each times its edge's weight, for every dst node: [num_dst, dim] (DGL's u_mul_e_sum,
@@ -221,8 +226,10 @@ class Block(object):
         return self.weighted_sum_aggregate_torch(h_src, w)
 
     def weighted_sum_aggregate_torch(self, h_src, w):
-        """weighted_sum_aggregate in plain torch, any device and dtype: its fallback, and its reference."""
+        """weighted_sum_aggregate in plain torch, any device and dtype, h_src [num_src, ...] -> [num_dst, ...]: its fallback, and its
+        reference."""
         dev = h_src.device
+        ones = (1,) * (h_src.dim() - 1)
         w = w.to(device=dev, dtype=h_src.dtype)
         if self.nbr is None:
             deg = self.indptr[1:] - self.indptr[:-1]
@@ -230,10 +237,10 @@ class Block(object):
             idx = self.indices.to(device=dev, dtype=torch.int64)
             valid = (idx >= 0).to(h_src.dtype)
             out = torch.zeros((self.num_dst,) + tuple(h_src.shape[1:]), dtype=h_src.dtype, device=dev)
-            return out.index_add(0, rows, h_src[idx.clamp_min(0)] * (w * valid).unsqueeze(-1))
+            return out.index_add(0, rows, h_src[idx.clamp_min(0)] * (w * valid).view((-1,) + ones))
         valid = (self.nbr >= 0).to(device=dev, dtype=h_src.dtype)
         idx = self.nbr.clamp_min(0).to(device=dev, dtype=torch.int64)
-        return (h_src[idx] * (w * valid).unsqueeze(-1)).sum(1)
+        return (h_src[idx] * (w * valid).view(tuple(valid.shape) + ones)).sum(1)
 
     def _rel_args(self, etype, num_rels, w):
         """The checks of rel_sum_aggregate / rel_sum_aggregate_torch / rel_in_degrees -> the block's slot array."""

@@ -1,0 +1,395 @@
+"""float64 reference of whole models on sampled blocks, written in GLOBAL node ids and CSC edge positions only (tests only).
+
+A block is decoded once, by edges_of(), into triples (dst_gid, src_gid, eid); that is the only place a local index (nbr, indices,
+indptr, dst_in_src) is read, and only to translate it.  Everything after that works on [N, d] arrays indexed by global node id and
+on the triples: a layer's degrees are counts over its triples, edge weights and types are graph.edata[key][eid].  Nothing here
+imports or calls Block, block_ops or any *_aggregate.
+
+The formulas are those of the docstrings of COALA_GNN/nn.py and harness.py, run through torch autograd on the CPU with index_add on
+global ids; run() evaluates them in float64 or float32 (every array cast down: the rounding scale of the GPU tolerance), and in an
+'abs' mode -- every input replaced by its absolute value, every subtraction by an addition, relu by the identity, the winners of
+the maxima kept -- which gives, for every output and every gradient, the magnitude of the same sums taken over absolute values
+(the scale of the float64 agreement bound).  For the softmax of GAT and the final log_softmax the abs mode adds the magnitude of
+the term that autograd subtracts (a_k * out for the attention, softmax for log_softmax), so the magnitude is never below the sum of
+the absolute values of the true gradient's terms.
+
+Kink gap: the smallest relative distance of the float64 evaluation to a discontinuity of the gradient -- |z| / max|z| over every
+relu (and GAT leaky_relu) pre-activation of a live row, and (winner - runner-up) / max|message| over every maximum with candidates
+from at least two different source nodes.  Two ties are not kinks and are not counted: slots of the same source node with the same
+message (a repeated edge: the gradient reaches the same row either way), and a tie at exactly 0 (in these models an exact zero
+message comes from a relu or from a zero edge weight and carries no gradient whichever slot wins)."""
+import numpy as np
+import torch
+
+MODELS = ("sagemean", "sage_mean", "sage_gcn", "sage_pool", "sage_mean_w", "sage_gcn_w", "sage_pool_w", "gcn", "gcn_w", "gat",
+          "gin_sum", "gin_max", "gin_mean", "rgcn", "rgcn_basis")
+
+
+def _np(t):
+    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
+# ------------------------------------------------------------------------------------------------ decoding and validation
+class Layer(object):
+    """One decoded block: tri int64 [E, 3] (dst_gid, src_gid, eid), or [E, 2] without edge ids, in slot order; dst / src: the global
+    ids of its destination and source lists; self_ids: the node whose row serves as h_dst of every destination (dst itself)."""
+
+    def __init__(self, tri, dst, src, fixed):
+        self.tri, self.dst, self.src, self.fixed = tri, dst, src, fixed
+        self.self_ids = dst
+
+
+def edges_of(block):
+    """-> int64 [E, 3] triples (dst_gid, src_gid, eid) of every valid slot in slot order; [E, 2] pairs without edge ids."""
+    return decode(block).tri
+
+
+def decode(block):
+    src = _np(block.src_nodes).astype(np.int64)
+    dst = _np(block.dstdata["_ID"]).astype(np.int64)
+    assert len(dst) == block.num_dst and len(src) == block.num_src
+    eid = _np(block.edata["_ID"]).astype(np.int64) if "_ID" in block.edata else None
+    if block.nbr is None:
+        ip = _np(block.indptr).astype(np.int64)
+        loc = _np(block.indices).astype(np.int64)
+        assert len(ip) == len(dst) + 1 and ip[0] == 0 and ip[-1] == len(loc) and np.all(np.diff(ip) >= 0)
+        rows = np.repeat(np.arange(len(dst)), np.diff(ip))
+    else:
+        nbr = _np(block.nbr).astype(np.int64)
+        assert nbr.shape[0] == len(dst)
+        rows = np.repeat(np.arange(len(dst)), nbr.shape[1])
+        loc = nbr.reshape(-1)
+    assert np.all((loc >= -1) & (loc < len(src))), "a local source index outside the source list"
+    valid = loc >= 0
+    cols = [dst[rows[valid]], src[loc[valid]]]
+    if eid is not None:
+        eid = eid.reshape(-1)
+        assert eid.shape == loc.shape, "edata['_ID'] is not shaped like the slot array"
+        assert np.all(eid[~valid] == -1), "a padding slot carries an edge id"
+        cols.append(eid[valid])
+    return Layer(np.stack(cols, 1) if valid.any() else np.zeros((0, len(cols)), dtype=np.int64), dst, src, block.nbr is not None)
+
+
+def check_edges(indptr, indices, layers, fanouts, seeds, weights=None, labels=None, block_labels=None, labor=False):
+    """The integer part, exact.  layers: decoded blocks in model order (input layer first), fanouts in the same order."""
+    deg_all = np.diff(indptr)
+    for l, (lay, f) in enumerate(zip(layers, fanouts)):
+        tri, dst = lay.tri, lay.dst
+        d, s = tri[:, 0], tri[:, 1]
+        assert len(np.unique(dst)) == len(dst) and len(np.unique(lay.src)) == len(lay.src), "a node listed twice"
+        assert np.all((s >= 0) & (s < len(deg_all)))
+        per_row = np.bincount(d, minlength=len(deg_all))[dst]
+        if tri.shape[1] == 3:
+            e = tri[:, 2]
+            assert np.all((e >= indptr[d]) & (e < indptr[d + 1])), f"layer {l}: an edge id outside its destination's column"
+            assert np.all(indices[e] == s), f"layer {l}: indices[eid] is not the source node"
+            assert len(np.unique(e)) == len(e), f"layer {l}: an edge id appears twice"
+            if weights is not None and f != -1:
+                assert np.all(weights[e] > 0), f"layer {l}: a weighted layer took an edge of weight 0"
+        else:   # no edge ids: (dst, src) must name an in-edge, taken no more often than the column holds it
+            N = len(deg_all)
+            have, cnt = np.unique(np.repeat(np.arange(N), deg_all) * N + indices, return_counts=True)
+            took, tcnt = np.unique(d * N + s, return_counts=True)
+            at = np.minimum(np.searchsorted(have, took), len(have) - 1)
+            assert np.array_equal(have[at], took) and np.all(tcnt <= cnt[at]), f"layer {l}: a sampled pair is not an in-edge"
+        if f == -1:
+            assert np.array_equal(per_row, deg_all[dst]), f"layer {l}: a full layer must hold every in-edge"
+        elif labor:
+            assert np.all(per_row <= deg_all[dst]) and np.all(per_row[deg_all[dst] <= f] == deg_all[dst][deg_all[dst] <= f])
+        elif weights is not None:
+            run = np.concatenate([[0], np.cumsum(weights > 0)])
+            pos = run[indptr[dst + 1]] - run[indptr[dst]]
+            assert np.array_equal(per_row, np.minimum(f, pos)), f"layer {l}: a weighted layer holds min(f, positive edges) per row"
+        else:
+            assert np.array_equal(per_row, np.minimum(f, deg_all[dst])), f"layer {l}: a fixed layer holds min(f, deg) per row"
+        assert set(np.unique(s)) | set(dst) == set(lay.src), f"layer {l}: the source list is not the destinations and their neighbours"
+        if l + 1 < len(layers):
+            assert np.array_equal(dst, layers[l + 1].src), f"layer {l}: the destinations are not the next block's source nodes"
+        else:
+            assert np.array_equal(dst, np.asarray(seeds)), "the last block's destinations are not the seeds"
+    if labels is not None:
+        assert np.array_equal(np.asarray(block_labels).reshape(-1), labels[np.asarray(seeds)]), "dstdata['labels'] != labels[seeds]"
+
+
+# ------------------------------------------------------------------------------------------------ the formulas
+class _Ctx(object):
+    def __init__(self, mode, dtype, N, replay=None):
+        self.mode, self.dtype, self.N = mode, dtype, N
+        self.pre, self.gaps = [], []        # pre-activations (and max candidates) in call order; relative kink gaps
+        self.winners = [] if replay is None else replay
+        self._k = 0
+
+    def t(self, a, grad=False):
+        a = np.abs(a) if self.mode == "abs" else a
+        return torch.tensor(np.asarray(a), dtype=self.dtype).requires_grad_(grad)
+
+    def kink(self, z, rows):
+        """Record pre-activation z [N, ...] on its live rows."""
+        if self.mode == "abs":
+            return
+        v = z.detach()[rows]
+        self.pre.append(v)
+        if v.numel():
+            self.gaps.append(float(v.abs().min() / v.abs().max()))
+
+    def relu(self, z, rows):
+        self.kink(z, rows)
+        return z if self.mode == "abs" else torch.relu(z)
+
+    def seg_sum(self, msg, dst):
+        return torch.zeros((self.N,) + tuple(msg.shape[1:]), dtype=self.dtype).index_add(0, dst, msg)
+
+    def count(self, idx):
+        return torch.zeros(self.N, dtype=self.dtype).index_add(0, idx, torch.ones(len(idx), dtype=self.dtype))
+
+    def seg_max(self, msg, dst, src):
+        """Element-wise maximum of the messages msg [E, d] per destination; the first edge that holds it gets the gradient; 0 for a
+        destination without an edge."""
+        E, d = msg.shape
+        if E == 0:
+            return torch.zeros(self.N, d, dtype=self.dtype)
+        at = dst.view(E, 1).expand(E, d)
+        slot = torch.arange(E).view(E, 1).expand(E, d)
+        if self.mode == "abs":
+            first = self.winners[self._k]
+            self._k += 1
+        else:
+            v = msg.detach()
+            vmax = torch.full((self.N, d), float("-inf"), dtype=self.dtype).scatter_reduce(0, at, v, "amax")
+            first = torch.full((self.N, d), E, dtype=torch.int64).scatter_reduce(0, at, torch.where(v == vmax[dst], slot, E), "amin")
+            self.winners.append(first)
+            self.pre.append(v)
+            # runner-up among the candidates of another source node
+            wsrc = src[first.clamp_max(E - 1)]                                   # [N, d] source node of the winner
+            other = src.view(E, 1).expand(E, d) != wsrc[dst]
+            second = torch.full((self.N, d), float("-inf"), dtype=self.dtype).scatter_reduce(
+                0, at, torch.where(other, v, torch.full_like(v, float("-inf"))), "amax")
+            ok = torch.isfinite(second) & ~((vmax == 0) & (second == 0))
+            if ok.any():
+                self.gaps.append(float(((vmax - second)[ok]).min() / v.abs().max()))
+        some = first < E
+        return torch.where(some, msg.gather(0, first.clamp_max(E - 1)), torch.zeros((), dtype=self.dtype))
+
+
+class _Graph(object):
+    """What a layer function sees of one decoded block, as tensors in the context's dtype."""
+
+    def __init__(self, ctx, lay, edata):
+        self.dst = torch.from_numpy(np.ascontiguousarray(lay.tri[:, 0]))
+        self.src = torch.from_numpy(np.ascontiguousarray(lay.tri[:, 1]))
+        self.eid = lay.tri[:, 2] if lay.tri.shape[1] == 3 else None
+        self.dst_ids = torch.from_numpy(np.ascontiguousarray(lay.dst))
+        self.src_ids = torch.from_numpy(np.ascontiguousarray(lay.src))
+        self.self_ids = torch.from_numpy(np.ascontiguousarray(lay.self_ids))
+        self.in_deg = ctx.count(self.dst)
+        self.out_deg = ctx.count(self.src)
+        self._ctx, self._edata = ctx, edata
+
+    def weight(self, key):
+        if key == "edge_weights":   # LaborSampler's: 1 / (edges of the row within the layer), rounded to fp32 as the sampler stores it
+            deg = np.bincount(self.dst.numpy(), minlength=self._ctx.N).astype(np.float32)
+            with np.errstate(divide="ignore"):
+                return self._ctx.t((np.float32(1.0) / deg)[self.dst.numpy()])
+        return self._ctx.t(np.asarray(self._edata[key])[self.eid])
+
+    def etype(self, key="etype"):
+        return torch.from_numpy(np.asarray(self._edata[key])[self.eid].astype(np.int64))
+
+    def dst_rows(self, h):
+        """h with the rows of the destination nodes replaced by the rows the model takes for them (the same, unless a fault is
+        injected through Layer.self_ids)."""
+        if torch.equal(self.self_ids, self.dst_ids):
+            return h
+        return h.index_copy(0, self.dst_ids, h[self.self_ids])
+
+    def only_dst(self, out):
+        m = torch.zeros(out.shape[0], dtype=out.dtype)
+        m[self.dst_ids] = 1
+        return out * m.view((-1,) + (1,) * (out.dim() - 1))
+
+
+def _lin(h, W, b=None):
+    out = h @ W.t()
+    return out if b is None else out + b
+
+
+def _weighted_sum(ctx, g, h, wkey):
+    msg = h[g.src] if wkey is None else h[g.src] * g.weight(wkey).unsqueeze(-1)
+    return ctx.seg_sum(msg, g.dst)
+
+
+def _sage(ctx, g, P, p, h, agg, wkey):
+    hd = g.dst_rows(h)
+    deg = g.in_deg.unsqueeze(-1)
+    if agg == "pool":
+        hp = ctx.relu(_lin(h, P[p + "fc_pool.weight"], P[p + "fc_pool.bias"]), g.src_ids)
+        msg = hp[g.src] if wkey is None else hp[g.src] * g.weight(wkey).unsqueeze(-1)
+        return _lin(hd, P[p + "fc_self.weight"]) + _lin(ctx.seg_max(msg, g.dst, g.src), P[p + "fc_neigh.weight"]) + P[p + "bias"]
+    total = _weighted_sum(ctx, g, h, wkey)
+    if agg == "mean":
+        return _lin(hd, P[p + "fc_self.weight"]) + _lin(total / deg.clamp_min(1), P[p + "fc_neigh.weight"]) + P[p + "bias"]
+    return _lin((total + hd) / (deg + 1), P[p + "fc_neigh.weight"]) + P[p + "bias"]
+
+
+def _graphconv(ctx, g, P, p, h, wkey):
+    hs = h * g.out_deg.clamp_min(1).pow(-0.5).unsqueeze(-1)
+    total = _weighted_sum(ctx, g, hs, wkey) * g.in_deg.clamp_min(1).pow(-0.5).unsqueeze(-1)
+    return total @ P[p + "weight"] + P[p + "bias"]
+
+
+def _gin(ctx, g, P, p, h, agg):
+    hd = g.dst_rows(h)
+    if agg == "max":
+        neigh = ctx.seg_max(h[g.src], g.dst, g.src)
+    else:
+        neigh = ctx.seg_sum(h[g.src], g.dst)
+        if agg == "mean":
+            neigh = neigh / g.in_deg.clamp_min(1).unsqueeze(-1)
+    z = (1 + P[p + "eps"]) * hd + neigh
+    z = ctx.relu(_lin(z, P[p + "apply_func.0.weight"], P[p + "apply_func.0.bias"]), g.dst_ids)
+    return _lin(z, P[p + "apply_func.2.weight"], P[p + "apply_func.2.bias"])
+
+
+def _rgcn(ctx, g, P, p, h, num_rels):
+    hd = g.dst_rows(h)
+    t = g.etype()
+    W = P[p + "linear_r.W"]
+    if p + "linear_r.coeff" in P:
+        W = torch.einsum("rb,bio->rio", P[p + "linear_r.coeff"], W)
+    out = torch.zeros(ctx.N, W.shape[2], dtype=ctx.dtype)
+    for r in range(num_rels):
+        k = t == r
+        c = ctx.count(g.dst[k]).clamp_min(1)                       # c_{d, r}: d's in-edges of relation r within the layer
+        out = out + (ctx.seg_sum(h[g.src[k]], g.dst[k]) / c.unsqueeze(-1)) @ W[r]
+    return out + P[p + "h_bias"] + hd @ P[p + "loop_weight"]
+
+
+def _gat(ctx, g, P, p, h, heads, slope=0.2):
+    hd = g.dst_rows(h)
+    fs = _lin(h, P[p + "fc_src.weight"]).view(ctx.N, heads, -1)
+    fd = _lin(hd, P[p + "fc_dst.weight"]).view(ctx.N, heads, -1)
+    el, er = (fs * P[p + "attn_l"]).sum(-1), (fd * P[p + "attn_r"]).sum(-1)
+    z = el[g.src] + er[g.dst]
+    if ctx.mode != "abs":
+        ctx.pre.append(z.detach())
+        if z.numel():
+            ctx.gaps.append(float(z.detach().abs().min() / z.detach().abs().max()))
+    e = z if ctx.mode == "abs" else torch.nn.functional.leaky_relu(z, slope)
+    m = torch.full((ctx.N, heads), float("-inf"), dtype=ctx.dtype).scatter_reduce(0, g.dst.view(-1, 1).expand(-1, heads), e.detach(), "amax")
+    pexp = torch.exp(e - m[g.dst])
+    l = ctx.seg_sum(pexp, g.dst)
+    if ctx.mode == "abs":   # every term of d out / d e_k = a_k (fs_k - out) taken positive
+        a = pexp / l.detach()[g.dst]
+        out = ctx.seg_sum(a.unsqueeze(-1) * fs[g.src], g.dst)
+        out = out + ctx.seg_sum(a - a.detach(), g.dst).unsqueeze(-1) * out.detach()
+    else:
+        a = pexp / l[g.dst]
+        out = ctx.seg_sum(a.unsqueeze(-1) * fs[g.src], g.dst)
+    return out + P[p + "bias"].view(1, heads, -1)
+
+
+def _forward(ctx, kind, P, X, layers, edata, heads, num_rels):
+    h = X
+    L = len(layers)
+    for i, lay in enumerate(layers):
+        g = _Graph(ctx, lay, edata)
+        p = f"layers.{i}."
+        if kind == "sagemean":
+            mean = ctx.seg_sum(h[g.src], g.dst) / g.in_deg.clamp_min(1).unsqueeze(-1)
+            out = _lin(g.dst_rows(h), P[f"lin_self.{i}.weight"], P[f"lin_self.{i}.bias"]) + _lin(mean, P[f"lin_nbr.{i}.weight"])
+        elif kind.startswith("sage_"):
+            agg = kind.split("_")[1]
+            wkey = None if kind.count("_") == 1 else kind.split("_", 2)[2]
+            out = _sage(ctx, g, P, p, h, agg, {"w": "w", "ew": "edge_weights", None: None}[wkey])
+        elif kind in ("gcn", "gcn_w"):
+            out = _graphconv(ctx, g, P, p, h, "w" if kind == "gcn_w" else None)
+        elif kind.startswith("gin_"):
+            out = _gin(ctx, g, P, p, h, kind[4:])
+        elif kind.startswith("rgcn"):
+            out = _rgcn(ctx, g, P, p, h, num_rels)
+        elif kind == "gat":
+            out = _gat(ctx, g, P, p, h, heads)
+        else:
+            raise ValueError(kind)
+        out = g.only_dst(out)
+        if i + 1 < L:
+            h = out.flatten(1) if kind == "gat" else ctx.relu(out, g.dst_ids)
+        else:
+            h = out
+    seeds = torch.from_numpy(np.ascontiguousarray(layers[-1].dst))
+    h = h[seeds]
+    if kind == "gat":
+        h = h.mean(1)
+        h = h + torch.logsumexp(h, -1, keepdim=True) if ctx.mode == "abs" else h.log_softmax(-1)
+    return h
+
+
+class Result(object):
+    """logits [n_seeds, classes], grads {parameter name: array}, grad_X [N, in]; pre: the recorded pre-activations; gap: the kink gap."""
+
+    def arrays(self):
+        """Every compared array under a name: 'logits', 'grad_X', and the parameters' names."""
+        return dict(logits=self.logits, grad_X=self.grad_X, **self.grads)
+
+
+def run(kind, params, X, Cmat, layers, edata, mode="real", dtype=torch.float64, heads=2, num_rels=3, replay=None):
+    """params: {name: numpy array} (the model's named parameters).  The loss is (logits * Cmat).sum()."""
+    ctx = _Ctx(mode, dtype, X.shape[0], replay)
+    P = {k: ctx.t(v, grad=True) for k, v in params.items()}
+    Xt = ctx.t(X, grad=True)
+    logits = _forward(ctx, kind, P, Xt, layers, edata, heads, num_rels)
+    (logits * ctx.t(Cmat)).sum().backward()
+    r = Result()
+    r.logits = logits.detach().double().numpy()
+    r.grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)).double().numpy() for k, v in P.items()}
+    r.grad_X = (Xt.grad if Xt.grad is not None else torch.zeros_like(Xt)).double().numpy()
+    r.pre, r.gap, r.winners = ctx.pre, (min(ctx.gaps) if ctx.gaps else float("inf")), ctx.winners
+    return r
+
+
+class Evaluation(object):
+    """The reference of one case: ref (float64), ref32 (float32), mag (the abs mode), gap (kink gap of ref), tau (10 times the largest
+    float32-float64 difference of a pre-activation, relative to that pre-activation array's largest magnitude)."""
+
+    def __init__(self, kind, params, X, Cmat, layers, edata, **kw):
+        self.args, self.kw = (kind, params, X, Cmat, layers, edata), kw
+        self.ref = run(kind, params, X, Cmat, layers, edata, **kw)
+        self.ref32 = run(kind, params, X, Cmat, layers, edata, dtype=torch.float32, **kw)
+        self.mag = run(kind, params, X, Cmat, layers, edata, mode="abs", replay=self.ref.winners, **kw)
+        self.gap = self.ref.gap
+        d = [float((a.double() - b).abs().max() / b.abs().max()) for a, b in zip(self.ref32.pre, self.ref.pre) if b.numel()]
+        self.tau = 10.0 * max(d) if d else 0.0
+
+    def tolerance(self, name, factor=4.0, eps=2.0 ** -24):
+        """-> (bound, E32) of the kernel path for one array: factor * E32, and never below 8 eps times the largest magnitude."""
+        r64, r32 = self.ref.arrays()[name], self.ref32.arrays()[name]
+        e32 = float(np.abs(r32 - r64).max()) if r64.size else 0.0
+        return max(factor * e32, 8.0 * eps * (float(np.abs(r64).max()) if r64.size else 0.0)), e32
+
+    def check_float64(self, got, what=""):
+        """got: {name: array} of a float64 evaluation on the torch fallbacks.  Only the summation order differs: within
+        64 * 2^-53 * (the same sums over absolute values)."""
+        want, mag = self.ref.arrays(), self.mag.arrays()
+        assert set(got) == set(want), (sorted(got), sorted(want))
+        for k in want:
+            assert got[k].shape == want[k].shape, (what, k, got[k].shape, want[k].shape)
+            bad = np.abs(got[k] - want[k]) > 64 * 2.0 ** -53 * mag[k]
+            assert not bad.any(), f"{what} {k}: {int(bad.sum())} elements off, largest error {np.abs(got[k] - want[k]).max():.3e}, " \
+                                  f"bound there {64 * 2.0 ** -53 * mag[k][bad].min():.3e}"
+
+    def check_kernel(self, got, what="", factor=4.0, log=print, scalar_factor=None):
+        """got: {name: array} from the fp32 kernel path.  Prints E32, the measured ratio and the magnitude of the same sums over
+        absolute values for every array, then asserts.  scalar_factor, if given, replaces factor for one-element arrays, whose E32
+        is a single draw of the rounding error and not a maximum over many elements."""
+        want, mag = self.ref.arrays(), self.mag.arrays()
+        assert set(got) == set(want), (sorted(got), sorted(want))
+        worst = []
+        for k in sorted(want):
+            assert got[k].shape == want[k].shape, (what, k, got[k].shape, want[k].shape)
+            tol, e32 = self.tolerance(k, scalar_factor if scalar_factor is not None and want[k].size == 1 else factor)
+            err = float(np.abs(got[k] - want[k]).max()) if want[k].size else 0.0
+            log(f"{what} {k}: error {err:.3e} E32 {e32:.3e} ratio {err / e32 if e32 else float('nan'):.2f} bound {tol:.3e} "
+                f"abs-sum {float(mag[k].max()) if mag[k].size else 0.0:.3e}")
+            if not err <= tol:
+                worst.append((k, err, tol))
+        assert not worst, f"{what}: " + "; ".join(f"{k} off by {e:.3e} (bound {t:.3e})" for k, e, t in worst)

@@ -1,0 +1,298 @@
+"""One table of (sampler, bucketing, model) cases on one small graph, shared by test_models_global_cpu.py (blocks built from the
+numpy restatements of the samplers, float64 torch fallbacks) and test_models_global_gpu.py (the real samplers, fp32 native kernels).
+Tests only.
+
+The graph (numpy, fixed seed): N = 2000 nodes, in-degrees Poisson(6) -- columns without repeats -- and, all among the 48 seeds:
+HUB of in-degree 300 (more than the 64-edge chunk of the CSR kernels and than fan-out 32), ZERO of in-degree 0, LOOP whose column holds
+itself, MULTI whose column holds one neighbour twice.  The two copies of MULTI's repeated edge carry the same weight and type: a
+uniform fixed layer may name either position for a neighbour it took once, and the numpy twin (which knows neighbours, not
+positions) then still describes the same arithmetic.  edata: 'w' fp32 in [0.1, 1) with 41 exact zeros, 'etype' in [0, 3);
+ndata: 'labels'.  Feature width 20, hidden 12, 5 classes, 2 GAT heads.
+
+`step` of a case is the sampler's step and seeds the model's parameters and the loss matrix Cmat.  It is chosen on the CPU (STEPS
+below) so that the float64 reference stays clear of every gradient discontinuity: kink gap >= tau (see _global_ref)."""
+import collections
+import functools
+
+import numpy as np
+import torch
+
+import _global_ref as R
+from _edge_id_ref import full_ids
+from _full_ref import bucketed, fixed_layer, full_layer
+from _labor_ref import edge_weights as labor_edge_weights
+from _labor_ref import reference_layers as labor_layers
+from _util import csc_from_columns
+from _weighted_ref import weighted_layer
+
+N, IN, HID, NCLS, HEADS, NRELS, NSEEDS = 2000, 20, 12, 5, 2, 3, 48
+HUB, ZERO, LOOP, MULTI = 17, 23, 31, 40
+SAMPLER_SEED = 11
+
+Graph = collections.namedtuple("Graph", "indptr indices w etype labels X seeds")
+Case = collections.namedtuple("Case", "id sampler G edge_ids model step")
+
+SAMPLERS = {   # name -> (class, fan-outs in model order, prob)
+    "ns55": ("ns", [5, 5], None), "nsFF": ("ns", [-1, -1], None), "ns4F": ("ns", [4, -1], None), "nsF4": ("ns", [-1, 4], None),
+    "ns333": ("ns", [3, 3, 3], None), "w55": ("ns", [5, 5], "w"), "labor55": ("labor", [5, 5], None),
+}
+NEEDS_EDATA = ("sage_mean_w", "sage_gcn_w", "sage_pool_w", "gcn_w", "rgcn", "rgcn_basis")   # read graph.edata through the edge ids
+IGNORES_DST_ROWS = ("gcn", "gcn_w")                                                       # GraphConv has no self term
+
+
+@functools.lru_cache(None)
+def graph():
+    rng = np.random.default_rng(2024)
+    deg = rng.poisson(6, N)
+    deg[HUB], deg[ZERO], deg[LOOP], deg[MULTI] = 300, 0, 5, 6
+    columns = [rng.choice(N, size=d, replace=False) for d in deg]
+    columns[LOOP] = np.array([LOOP] + [v for v in columns[LOOP] if v != LOOP][:4])
+    columns[MULTI][1] = columns[MULTI][0]
+    indptr, indices = csc_from_columns(columns)
+    E = len(indices)
+    w = (0.1 + 0.9 * rng.random(E)).astype(np.float32)
+    w[rng.choice(E, size=40, replace=False)] = 0.0
+    w[indptr[HUB] + 3] = 0.0
+    etype = rng.integers(0, NRELS, size=E).astype(np.int64)
+    a = indptr[MULTI]
+    w[a] = w[a + 1] = np.float32(0.625)
+    etype[a + 1] = etype[a]
+    labels = rng.integers(0, NCLS, size=N).astype(np.int64)
+    X = rng.standard_normal((N, IN)).astype(np.float32)
+    plain = next(v for v in range(100, N) if 3 <= deg[v] <= 6 and np.all(w[indptr[v]:indptr[v + 1]] > 0))
+    special = [plain, HUB, ZERO, LOOP, MULTI]
+    others = [v for v in rng.permutation(N) if v not in special][: NSEEDS - len(special)]
+    seeds = np.array(special + others, dtype=np.int64)
+    assert len(np.unique(seeds)) == NSEEDS and (np.diff(indptr) == 0).sum() >= 1 and np.diff(indptr).max() == 300
+    return Graph(indptr, indices, w, etype, labels, X, seeds)
+
+
+# Steps found on the CPU: the first step in 0, 1, 2, ... at which the kink gap of the float64 reference is at least 1.5 tau and each of
+# the three single faults moves the logits by at least 1500 times the GPU tolerance (the tests ask for tau and 1000).  A case not
+# listed uses step 0.  Measured at these steps, "case gap/tau", over the whole table: gap 1.9e-06 .. 3.2e-04, tau 1.2e-06 .. 3.1e-06,
+# smallest gap / tau 1.48 (nsFF-b0-gin_sum); the smallest move of the logits by a fault is 1505 times the tolerance.
+#   ns55-b0-sagemean 2.0e-05/2.0e-06; ns55-b0-sage_mean 7.7e-05/2.0e-06; ns55-b0-sage_gcn 5.3e-05/2.0e-06;
+#   ns55-b0-sage_pool 7.3e-06/1.8e-06; ns55-b0-sage_mean_w 1.7e-04/2.6e-06; ns55-b0-sage_gcn_w 1.1e-04/1.3e-06;
+#   ns55-b0-sage_pool_w 7.0e-06/2.0e-06; ns55-b0-gcn 8.4e-05/1.3e-06; ns55-b0-gcn_w 1.0e-05/1.5e-06; ns55-b0-gat 2.8e-04/1.6e-06;
+#   ns55-b0-gin_sum 1.7e-05/1.8e-06; ns55-b0-gin_max 1.4e-05/1.9e-06; ns55-b0-gin_mean 3.3e-05/1.6e-06; ns55-b0-rgcn 1.8e-05/1.7e-06;
+#   ns55-b0-rgcn_basis 3.2e-04/1.4e-06; ns55-b3-sagemean 2.0e-05/2.0e-06; ns55-b3-sage_mean 7.7e-05/2.0e-06;
+#   ns55-b3-sage_gcn 5.3e-05/2.0e-06; ns55-b3-sage_pool 7.3e-06/1.8e-06; ns55-b3-sage_mean_w 1.7e-04/2.6e-06;
+#   ns55-b3-sage_gcn_w 1.1e-04/1.3e-06; ns55-b3-sage_pool_w 7.0e-06/2.0e-06; ns55-b3-gcn 8.4e-05/1.3e-06;
+#   ns55-b3-gcn_w 1.0e-05/1.5e-06; ns55-b3-gat 2.8e-04/1.6e-06; ns55-b3-gin_sum 1.7e-05/1.8e-06; ns55-b3-gin_max 1.4e-05/1.9e-06;
+#   ns55-b3-gin_mean 3.3e-05/1.6e-06; ns55-b3-rgcn 1.8e-05/1.7e-06; ns55-b3-rgcn_basis 3.2e-04/1.4e-06;
+#   nsFF-b0-sagemean 7.5e-06/1.6e-06; nsFF-b0-sage_mean 1.3e-04/2.4e-06; nsFF-b0-sage_gcn 9.0e-05/1.3e-06;
+#   nsFF-b0-sage_pool 1.8e-05/1.9e-06; nsFF-b0-sage_mean_w 9.9e-05/2.0e-06; nsFF-b0-sage_gcn_w 4.5e-05/1.3e-06;
+#   nsFF-b0-sage_pool_w 7.0e-06/1.9e-06; nsFF-b0-gcn 4.5e-06/2.9e-06; nsFF-b0-gcn_w 2.5e-05/2.1e-06; nsFF-b0-gat 9.7e-05/1.5e-06;
+#   nsFF-b0-gin_sum 3.4e-06/2.3e-06; nsFF-b0-gin_max 3.7e-06/1.7e-06; nsFF-b0-gin_mean 2.0e-05/1.7e-06; nsFF-b0-rgcn 1.7e-05/1.4e-06;
+#   nsFF-b0-rgcn_basis 5.4e-06/1.5e-06; nsFF-b3-sagemean 7.5e-06/1.6e-06; nsFF-b3-sage_mean 1.3e-04/2.4e-06;
+#   nsFF-b3-sage_gcn 9.0e-05/1.3e-06; nsFF-b3-sage_pool 1.8e-05/1.9e-06; nsFF-b3-sage_mean_w 9.9e-05/2.0e-06;
+#   nsFF-b3-sage_gcn_w 4.5e-05/1.3e-06; nsFF-b3-sage_pool_w 7.0e-06/1.9e-06; nsFF-b3-gcn 4.5e-06/2.9e-06;
+#   nsFF-b3-gcn_w 2.5e-05/2.1e-06; nsFF-b3-gat 9.7e-05/1.5e-06; nsFF-b3-gin_sum 3.4e-06/2.3e-06; nsFF-b3-gin_max 3.7e-06/1.7e-06;
+#   nsFF-b3-gin_mean 2.0e-05/1.7e-06; nsFF-b3-rgcn 1.7e-05/1.4e-06; nsFF-b3-rgcn_basis 5.4e-06/1.5e-06;
+#   ns4F-b0-sagemean 2.4e-05/1.8e-06; ns4F-b0-sage_mean 9.5e-05/2.0e-06; ns4F-b0-sage_gcn 5.3e-05/2.0e-06;
+#   ns4F-b0-sage_pool 8.4e-06/2.5e-06; ns4F-b3-sage_mean_w 6.6e-05/1.9e-06; ns4F-b3-sage_gcn_w 4.6e-06/1.3e-06;
+#   ns4F-b3-sage_pool_w 1.0e-05/1.8e-06; ns4F-b3-gcn 5.8e-05/1.7e-06; nsF4-b0-gcn_w 1.9e-06/1.2e-06; nsF4-b0-gat 1.5e-04/1.7e-06;
+#   nsF4-b0-gin_sum 2.4e-05/3.1e-06; nsF4-b0-gin_max 4.0e-06/1.8e-06; nsF4-b3-gin_mean 5.3e-05/1.5e-06; nsF4-b3-rgcn 1.6e-04/1.3e-06;
+#   nsF4-b3-rgcn_basis 6.5e-06/1.8e-06; nsF4-b3-sagemean 7.5e-06/1.6e-06; ns333-b0-sage_mean 1.8e-05/1.5e-06;
+#   ns333-b0-sage_gcn 3.7e-05/2.1e-06; ns333-b0-sage_pool 1.7e-05/2.1e-06; ns333-b0-sage_mean_w 2.2e-05/1.4e-06;
+#   ns333-b3-sage_gcn_w 1.1e-05/2.4e-06; ns333-b3-sage_pool_w 3.4e-06/2.1e-06; ns333-b3-gcn 9.5e-05/2.2e-06;
+#   ns333-b3-gcn_w 6.2e-05/1.5e-06; w55-b0-gat 2.8e-04/1.5e-06; w55-b0-gin_sum 2.0e-05/1.9e-06; w55-b0-gin_max 9.7e-06/1.5e-06;
+#   w55-b0-gin_mean 6.2e-06/1.6e-06; w55-b3-rgcn 1.8e-05/1.4e-06; w55-b3-rgcn_basis 5.3e-06/1.5e-06; w55-b3-sagemean 6.7e-05/1.2e-06;
+#   w55-b3-sage_mean 1.7e-04/2.1e-06; labor55-b0-sage_gcn 5.3e-05/2.0e-06; labor55-b0-sage_pool 1.1e-05/1.9e-06;
+#   labor55-b0-sage_mean_w 1.4e-04/2.4e-06; labor55-b0-sage_gcn_w 4.5e-05/1.3e-06; labor55-b3-sage_pool_w 1.8e-05/1.8e-06;
+#   labor55-b3-gcn 2.5e-05/1.6e-06; labor55-b3-gcn_w 1.9e-05/1.5e-06; labor55-b3-gat 2.2e-04/1.4e-06;
+#   labor55-b0-sage_mean_ew 1.7e-04/2.0e-06; labor55-b3-sage_mean_ew 1.7e-04/2.0e-06; labor55-b3-sage_mean_ew-noeid 1.7e-04/2.0e-06;
+#   ns55-b3-sage_mean-noeid 7.7e-05/2.0e-06; nsFF-b0-sagemean-noeid 7.5e-06/1.6e-06;
+STEPS = {
+    "ns55-b0-sage_gcn_w": 1, "ns55-b0-sage_pool_w": 2, "ns55-b3-sage_gcn_w": 1, "ns55-b3-sage_pool_w": 2, "nsFF-b0-sage_gcn": 1,
+    "nsFF-b0-sage_gcn_w": 1, "nsFF-b0-sage_pool_w": 2, "nsFF-b0-gcn_w": 14, "nsFF-b0-gin_sum": 6, "nsFF-b3-sage_gcn": 1,
+    "nsFF-b3-sage_gcn_w": 1, "nsFF-b3-sage_pool_w": 2, "nsFF-b3-gcn_w": 14, "nsFF-b3-gin_sum": 6, "ns4F-b3-sage_gcn_w": 1,
+    "ns4F-b3-gcn": 2, "nsF4-b0-gcn_w": 1, "nsF4-b0-gin_sum": 1, "ns333-b0-sage_pool": 1, "ns333-b3-gcn": 4, "ns333-b3-gcn_w": 3,
+    "w55-b0-gin_max": 1, "w55-b3-sagemean": 1, "labor55-b0-sage_gcn_w": 1, "labor55-b3-gcn": 2, "labor55-b3-gcn_w": 2,
+}
+
+
+def _cases():
+    out = []
+
+    def add(s, G, eids, m):
+        cid = f"{s}-b{G}-{m}" + ("" if eids else "-noeid")
+        out.append(Case(cid, s, G, eids, m, STEPS.get(cid, 0)))
+
+    for s in ("ns55", "nsFF"):
+        for G in (0, 3):
+            for m in R.MODELS:
+                add(s, G, True, m)
+    k = 0
+    for s in ("ns4F", "nsF4", "ns333", "w55", "labor55"):
+        for G in (0, 3):
+            for _ in range(4):
+                add(s, G, True, R.MODELS[k % len(R.MODELS)])
+                k += 1
+    for G in (0, 3):
+        add("labor55", G, True, "sage_mean_ew")     # LaborSampler's own edata['edge_weights']
+    add("labor55", 3, False, "sage_mean_ew")        # ... which exists without edge ids
+    add("ns55", 3, False, "sage_mean")              # the path without edge ids is decoded too
+    add("nsFF", 0, False, "sagemean")
+    return out
+
+
+CASES = _cases()
+GRAD_CASES = CASES   # every case compares its gradients on the GPU
+
+
+def make_model(kind, n_layers, seed):
+    """The harness model of a case, fp32 on the CPU, dropout 0; every 1-D parameter (the biases, zero at initialisation, and GIN's eps)
+    is drawn from N(0, 0.3) so that none of them is invisible."""
+    from COALA_GNN.harness import GAT, GCN, GIN, RGCN, SAGE, SageMean
+    torch.manual_seed(1000 + seed)
+    if kind == "sagemean":
+        m = SageMean(IN, HID, NCLS, n_layers)
+    elif kind.startswith("sage_"):
+        parts = kind.split("_")
+        key = {"w": "w", "ew": "edge_weights"}[parts[2]] if len(parts) == 3 else None
+        m = SAGE(IN, HID, NCLS, n_layers, aggregator_type=parts[1], edge_weight=key)
+    elif kind in ("gcn", "gcn_w"):
+        m = GCN(IN, HID, NCLS, n_layers, dropout=0.0, edge_weight="w" if kind == "gcn_w" else None)
+    elif kind == "gat":
+        m = GAT(IN, HID, NCLS, n_layers, HEADS)
+    elif kind.startswith("gin_"):
+        m = GIN(IN, HID, NCLS, n_layers, aggregator_type=kind[4:], learn_eps=True)
+    elif kind in ("rgcn", "rgcn_basis"):
+        m = RGCN(IN, HID, NCLS, n_layers, NRELS, regularizer="basis" if kind == "rgcn_basis" else None,
+                 num_bases=2 if kind == "rgcn_basis" else None, dropout=0.0)
+    else:
+        raise ValueError(kind)
+    with torch.no_grad():
+        for p in m.parameters():
+            if p.dim() == 1:
+                p.normal_(0.0, 0.3)
+    return m
+
+
+def loss_matrix(step):
+    return np.random.default_rng(5000 + step).standard_normal((NSEEDS, NCLS)).astype(np.float32)
+
+
+def params_of(model):
+    return {k: v.detach().cpu().numpy() for k, v in model.named_parameters()}
+
+
+def run_model(model, blocks, X, Cmat):
+    """The product path: feat = X[input_nodes] with requires_grad, forward, (logits * Cmat).sum().backward() -> {name: float64 array}
+    with 'logits', every parameter's gradient and 'grad_X' (feat.grad scattered to [N, in] by input_nodes).  X, Cmat: tensors on the
+    model's device in its dtype."""
+    input_nodes = blocks[0].src_nodes
+    feat = X[input_nodes.to(X.device)].clone().requires_grad_(True)
+    return finish(model, model(blocks, feat), feat, input_nodes, X.shape, Cmat)
+
+
+def finish(model, logits, feat, input_nodes, shape, Cmat):
+    model.zero_grad()
+    (logits * Cmat).sum().backward()
+    grad_X = torch.zeros(shape, dtype=feat.dtype, device=feat.device).index_add(0, input_nodes.to(feat.device), feat.grad)
+    out = {"logits": logits, "grad_X": grad_X}
+    for k, p in model.named_parameters():
+        out[k] = p.grad if p.grad is not None else torch.zeros_like(p)
+    return {k: v.detach().double().cpu().numpy() for k, v in out.items()}
+
+
+class HostGraph(object):
+    """What Block needs of a graph for edata and labels, on the host (a CSCGraph needs a GPU)."""
+
+    def __init__(self, g):
+        self.edata = {"w": torch.from_numpy(g.w), "etype": torch.from_numpy(g.etype)}
+        self.ndata = {"labels": torch.from_numpy(g.labels)}
+
+
+def uniform_eids(indptr, indices, dst, src, loc):
+    """Edge ids of the twin's uniform fixed layer on a multigraph: the k-th slot of a row that holds neighbour t gets the k-th position
+    of t in the row's column (_edge_id_ref.uniform_ids needs a graph without repeated edges)."""
+    eid = np.full(loc.shape, -1, dtype=np.int64)
+    for r, v in enumerate(dst):
+        col = indices[indptr[v]:indptr[v + 1]]
+        seen = {}
+        for j in np.flatnonzero(loc[r] >= 0):
+            t = src[loc[r, j]]
+            k = seen.get(t, 0)
+            seen[t] = k + 1
+            eid[r, j] = indptr[v] + np.flatnonzero(col == t)[k]
+    return eid
+
+
+LOADER_SAMPLER_SEED, LOADER_MODEL_SEED = 5, 0
+
+
+def loader_train_ids():
+    """The training ids of the loader test: three batches of NSEEDS (the loader stops one global batch before the end).  With the
+    'baseline' distributor batch k is ids[k * NSEEDS: (k + 1) * NSEEDS] and is sampled at step k.  Kink gap / tau of the first two
+    batches with GCN(edge_weight='w') at LOADER_MODEL_SEED, measured on the CPU (test_loader_batches_stay_clear_of_kinks):
+    8.3e-06 / 1.3e-06 and 1.9e-04 / 1.4e-06."""
+    return torch.randperm(N, generator=torch.Generator().manual_seed(0))[: NSEEDS * 3]
+
+
+def reference_blocks(oracle, case, seeds=None, sampler_seed=SAMPLER_SEED):
+    """The blocks of a case from the numpy restatements of the samplers, as CPU Block objects in model order."""
+    from COALA_GNN.sampler import Block
+    g = graph()
+    if seeds is not None:
+        g = g._replace(seeds=np.asarray(seeds, dtype=np.int64))
+    SAMPLER_SEED = sampler_seed
+    cls, fanouts, prob = SAMPLERS[case.sampler]
+    rev = list(reversed(fanouts))
+    layers = []   # sampling order: (src, indptr_local or None, nbr_local, eid)
+    if cls == "labor":
+        layers = labor_layers(g.indptr, g.indices, g.seeds, rev, SAMPLER_SEED, case.step)
+    else:
+        dst = g.seeds
+        for l, f in enumerate(rev):
+            if f == -1:
+                src, ip, loc = full_layer(g.indptr, g.indices, dst)
+                eid = full_ids(g.indptr, dst)
+            elif prob is not None:
+                src, loc, pos, _ = weighted_layer(g.indptr, g.indices, g.w, dst, f, SAMPLER_SEED, case.step, l)
+                ip, eid = None, np.where(pos >= 0, g.indptr[dst][:, None] + pos, -1)
+            else:
+                src, loc = fixed_layer(oracle, g.indptr, g.indices, dst, f, SAMPLER_SEED, case.step, l)
+                ip, eid = None, uniform_eids(g.indptr, g.indices, dst, src, loc)
+            layers.append((src, ip, loc, eid))
+            dst = src
+    host = HostGraph(g)
+    blocks = []
+    n_dst_nodes = g.seeds
+    for l, (src, ip, loc, eid) in enumerate(layers):
+        kw = {}
+        loc = np.asarray(loc)
+        if case.G and l == len(layers) - 1:
+            ids, sizes, new_of_old = bucketed(src, case.G)
+            loc = np.where(loc >= 0, new_of_old[np.maximum(loc, 0)], -1)
+            kw = dict(dst_in_src=torch.from_numpy(new_of_old[: len(n_dst_nodes)].astype(np.int32)), dst_nodes=torch.from_numpy(src[: len(n_dst_nodes)].copy()),
+                      owner_counts_host=sizes.tolist())
+            src = ids
+        if case.edge_ids:
+            kw["eid"] = torch.from_numpy(np.ascontiguousarray(eid, dtype=np.int64))
+        if cls == "labor":
+            kw["edata_lazy"] = {"edge_weights": (lambda ip=ip: torch.from_numpy(labor_edge_weights(ip)))}
+        if ip is not None:
+            kw.update(indptr=torch.from_numpy(np.ascontiguousarray(ip, dtype=np.int64)), indices=torch.from_numpy(loc.astype(np.int32)))
+            nbr = None
+        else:
+            nbr = torch.from_numpy(loc.astype(np.int32))
+        blocks.insert(0, Block(torch.from_numpy(np.ascontiguousarray(src, dtype=np.int64)), nbr, len(n_dst_nodes), graph=host if l == 0 else None,
+                               edata_graph=host, **kw))
+        n_dst_nodes = layers[l][0]
+    return blocks
+
+
+def evaluate(case, blocks, model, seeds=None, X=None):
+    """Decode and validate the blocks, then the reference of the case -> (R.Evaluation, decoded layers).  seeds, X: another batch and
+    another feature table than the graph's own (the loader test)."""
+    g = graph()
+    seeds = g.seeds if seeds is None else np.asarray(seeds)
+    cls, fanouts, prob = SAMPLERS[case.sampler]
+    layers = [R.decode(b) for b in blocks]
+    R.check_edges(g.indptr, g.indices, layers, fanouts, seeds, weights=g.w if prob else None, labels=g.labels,
+                  block_labels=R._np(blocks[-1].dstdata["labels"]), labor=cls == "labor")
+    ev = R.Evaluation(case.model, params_of(model), g.X if X is None else X, loss_matrix(case.step)[: len(seeds)], layers,
+                      {"w": g.w, "etype": g.etype}, heads=HEADS, num_rels=NRELS)
+    return ev, layers

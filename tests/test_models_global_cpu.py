@@ -1,0 +1,167 @@
+"""The global-id float64 reference of tests/_global_ref.py proves itself here, without a GPU.
+
+Every case of tests/_model_cases.py is built from the numpy restatements of the samplers (_full_ref, _weighted_ref, _labor_ref,
+_edge_id_ref, the oracle's uniform twin) as CPU Block objects -- plain and owner-bucketed -- and the harness model runs on them in
+.double() on the torch fallbacks.
+  agreement   logits, every parameter gradient and grad_X agree with the reference within 64 * 2^-53 * (the same sums over absolute
+              values): both sides are float64, only the summation order differs.
+  teeth       three single faults, each in the reference's inputs with the blocks held fixed -- one neighbour of the input block
+              replaced by another node; the destination rows of a bucketed input block taken as h[:num_dst]; edata shifted by one
+              edge -- each move the logits by at least 1000 times the GPU test's tolerance.  A fault runs where the model can see it:
+              GraphConv has no self term (no destination rows), and only the weighted and the relational models read edata.
+  kink        the reference's kink gap is at least tau for every case whose gradients the GPU test compares (all of them).
+The dispatch-parity twin (tests/_dispatch_parity.py) checks the shape contract of Block.*_aggregate on the CPU."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import _dispatch_parity as DP
+import _global_ref as R
+import _model_cases as MC
+
+_ORACLE = {}
+
+
+@functools.lru_cache(None)
+def _built(cid):
+    case = next(c for c in MC.CASES if c.id == cid)
+    blocks = MC.reference_blocks(_ORACLE["o"], case)
+    model = MC.make_model(case.model, len(blocks), case.step)
+    ev, layers = MC.evaluate(case, blocks, model)
+    return case, blocks, model, ev, layers
+
+
+@pytest.fixture
+def built(oracle, hiplib, request):
+    _ORACLE["o"] = oracle
+    return _built(request.param)
+
+
+IDS = [c.id for c in MC.CASES]
+
+
+def test_case_table_covers_what_it_must():
+    g = MC.graph()
+    deg = np.diff(g.indptr)
+    assert len(g.indptr) - 1 == 2000 and 5.5 < deg.mean() < 6.5 and deg[MC.HUB] == 300 and deg[MC.ZERO] == 0
+    assert MC.LOOP in g.indices[g.indptr[MC.LOOP]:g.indptr[MC.LOOP + 1]]
+    col = g.indices[g.indptr[MC.MULTI]:g.indptr[MC.MULTI + 1]]
+    assert len(np.unique(col)) == len(col) - 1
+    assert (g.w == 0).sum() >= 3 and g.w.dtype == np.float32 and g.w.min() >= 0 and set(np.unique(g.etype)) == {0, 1, 2}
+    assert len(g.seeds) == 48 and {MC.HUB, MC.ZERO, MC.LOOP, MC.MULTI} <= set(g.seeds.tolist())
+    assert len(IDS) == len(set(IDS)) and 90 <= len(IDS) <= 130
+    for s in MC.SAMPLERS:
+        assert {c.G for c in MC.CASES if c.sampler == s} == {0, 3}
+    for m in R.MODELS:
+        assert {(c.sampler, c.G) for c in MC.CASES if c.model == m} >= {("ns55", 0), ("ns55", 3), ("nsFF", 0), ("nsFF", 3)}
+    assert any(not c.edge_ids for c in MC.CASES)
+    assert all(c.edge_ids for c in MC.CASES if c.model in MC.NEEDS_EDATA)
+
+
+def test_blocks_come_from_the_restatements_the_sampler_tests_use():
+    """The GPU sampler tests compare the kernels with these very functions."""
+    import _edge_id_ref
+    import _full_ref
+    import _labor_ref
+    import _weighted_ref
+    import test_sampler_edge_ids_gpu
+    import test_sampler_full_gpu
+    import test_sampler_labor_gpu
+    import test_sampler_weighted_gpu
+    assert MC.full_layer is _full_ref.full_layer is test_sampler_full_gpu.full_layer is test_sampler_weighted_gpu.full_layer
+    assert MC.bucketed is _full_ref.bucketed is test_sampler_full_gpu.bucketed is test_sampler_labor_gpu.bucketed
+    assert MC.fixed_layer is _full_ref.fixed_layer and _edge_id_ref.fixed_layer is _full_ref.fixed_layer
+    assert test_sampler_full_gpu.reference_layers.__globals__["fixed_layer"] is MC.fixed_layer
+    assert MC.full_ids is _edge_id_ref.full_ids is test_sampler_edge_ids_gpu.full_ids
+    assert MC.weighted_layer is _weighted_ref.weighted_layer is _edge_id_ref.weighted_layer
+    assert test_sampler_weighted_gpu.reference_layers.__globals__["weighted_layer"] is MC.weighted_layer
+    assert MC.labor_layers is _labor_ref.reference_layers is test_sampler_labor_gpu.reference_layers
+    assert MC.labor_edge_weights is _labor_ref.edge_weights is test_sampler_labor_gpu.edge_weights
+
+
+def test_uniform_edge_ids_on_a_multigraph_agree_with_the_simple_graph_rule(oracle):
+    """Without a repeated edge in sight MC.uniform_eids gives what _edge_id_ref.uniform_ids gives."""
+    from _edge_id_ref import uniform_ids
+    g = MC.graph()
+    keep = np.ones(len(g.indices), dtype=bool)
+    keep[g.indptr[MC.MULTI] + 1] = False                       # the graph without its one repeated edge
+    indices = g.indices[keep]
+    indptr = g.indptr.copy()
+    indptr[MC.MULTI + 1:] -= 1
+    src, loc = MC.fixed_layer(oracle, indptr, indices, g.seeds, 5, MC.SAMPLER_SEED, 0, 0)
+    assert np.array_equal(MC.uniform_eids(indptr, indices, g.seeds, src, loc), uniform_ids(oracle, indptr, indices, g.seeds, 5, MC.SAMPLER_SEED, 0, 0))
+
+
+@pytest.mark.parametrize("built", IDS, indirect=True)
+def test_reference_agrees_with_float64_fallbacks(built):
+    case, blocks, model, ev, layers = built
+    g = MC.graph()
+    m64 = MC.make_model(case.model, len(blocks), case.step).double()
+    got = MC.run_model(m64, blocks, torch.from_numpy(g.X).double(), torch.from_numpy(MC.loss_matrix(case.step)).double())
+    ev.check_float64(got, case.id)
+    if case.G:
+        assert blocks[0].dst_in_src is not None and not torch.equal(blocks[0].src_nodes[: blocks[0].num_dst], blocks[0].dstdata["_ID"])
+
+
+def _moved(ev, layers=None, edata=None):
+    kind, params, X, Cmat, lay0, ed0 = ev.args
+    r = R.run(kind, params, X, Cmat, lay0 if layers is None else layers, ed0 if edata is None else edata, **ev.kw)
+    return float(np.abs(r.logits - ev.ref.logits).max())
+
+
+@pytest.mark.parametrize("built", IDS, indirect=True)
+def test_single_faults_move_the_reference(built):
+    case, blocks, model, ev, layers = built
+    g = MC.graph()
+    need = 1000.0 * ev.tolerance("logits")[0]
+    # 1. one valid neighbour of the input block replaced by another node: the first edge of the first seed, by the feature table's
+    #    largest row (the next largest if that is the neighbour itself)
+    big = np.argsort(-np.abs(g.X).sum(1))[:2]
+    lay = R.Layer(layers[0].tri.copy(), layers[0].dst, layers[0].src, layers[0].fixed)
+    assert lay.tri[0, 0] == g.seeds[0]
+    lay.tri[0, 1] = big[0] if lay.tri[0, 1] != big[0] else big[1]
+    moved = _moved(ev, layers=[lay] + layers[1:])
+    print(f"{case.id}: neighbour replaced: logits move {moved:.3e}, need {need:.3e}")
+    assert moved >= need
+    # 2. h[:num_dst] on the bucketed input block: destination k gets the row of the k-th node of the bucketed source list
+    if case.G and case.model not in MC.IGNORES_DST_ROWS:
+        lay = R.Layer(layers[0].tri, layers[0].dst, layers[0].src, layers[0].fixed)
+        lay.self_ids = layers[0].src[: len(layers[0].dst)]
+        assert not np.array_equal(lay.self_ids, lay.dst)
+        moved = _moved(ev, layers=[lay] + layers[1:])
+        print(f"{case.id}: destination rows un-bucketed: logits move {moved:.3e}, need {need:.3e}")
+        assert moved >= need
+    # 3. edata shifted by one edge
+    if case.model in MC.NEEDS_EDATA:
+        moved = _moved(ev, edata={k: np.roll(v, 1) for k, v in ev.args[5].items()})
+        print(f"{case.id}: edata shifted: logits move {moved:.3e}, need {need:.3e}")
+        assert moved >= need
+
+
+@pytest.mark.parametrize("built", [c.id for c in MC.GRAD_CASES], indirect=True)
+def test_kink_condition(built):
+    case, blocks, model, ev, layers = built
+    print(f"{case.id}: step {case.step} kink gap {ev.gap:.3e} tau {ev.tau:.3e}")
+    assert ev.gap >= ev.tau
+
+
+def test_loader_batches_stay_clear_of_kinks(oracle, hiplib):
+    """The two batches of the GPU file's loader test, rebuilt from the uniform twin: their kink gap is at least tau."""
+    ids = MC.loader_train_ids().numpy()
+    model = MC.make_model("gcn_w", 2, MC.LOADER_MODEL_SEED)
+    for k in range(2):
+        seeds = ids[k * MC.NSEEDS: (k + 1) * MC.NSEEDS]
+        case = MC.Case("loader-gcn_w", "ns55", 0, True, "gcn_w", k)
+        blocks = MC.reference_blocks(oracle, case, seeds=seeds, sampler_seed=MC.LOADER_SAMPLER_SEED)
+        ev, _ = MC.evaluate(case._replace(step=MC.LOADER_MODEL_SEED), blocks, model, seeds=seeds)
+        print(f"loader batch {k}: kink gap {ev.gap:.3e} tau {ev.tau:.3e}")
+        assert ev.gap >= 1.5 * ev.tau
+
+
+@pytest.mark.parametrize("inp", DP.INPUTS)
+@pytest.mark.parametrize("form", DP.FORMS)
+@pytest.mark.parametrize("op", DP.OPS)
+def test_dispatch_parity_cpu(hiplib, op, form, inp):
+    DP.check("cpu", op, form, inp)
