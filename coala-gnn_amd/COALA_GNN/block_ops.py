@@ -1,6 +1,6 @@
 """Autograd wrappers of the native block ops that `Block` (sampler.py) hands to a model: mean aggregation (SAGEConv's "mean"), weighted
 sum aggregation (DGL's u_mul_e_sum, the edge_weight= path of GraphConv / SAGEConv), max aggregation (DGL's fn.max: SAGEConv's "pool",
-GINConv's "max"), the relation-typed sum (RelGraphConv's message step) and GAT attention aggregation, on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the
+GINConv's "max"), the relation-typed sum (RelGraphConv's message step) and GAT / GATv2 attention aggregation, on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the
 kernels are in coala-gnn_amd/csrc/coala_block_ops.hip (C ABI: coala_block_*)."""
 import torch
 
@@ -290,3 +290,70 @@ class _GatAggregateCSR(torch.autograd.Function):
                                                                 grad_feat.data_ptr(), grad_el.data_ptr(), grad_er.data_ptr(), indptr.numel() - 1,
                                                                 f.shape[1], f.shape[2], ctx.slope, current_stream()))
         return grad_el, grad_er, grad_feat, None, None, None
+
+
+def _gatv2_parts(n_dst):
+    """Rows of the grad_attn partials buffer, which is also the backward's grid: one block per four destination rows, 1024 at the most."""
+    return max(1, min(-(-n_dst // 4), 1024))
+
+
+def _gatv2_forward(ctx, feat_src, feat_dst, attn, entry, index, n_dst, tail, negative_slope):
+    """One launch (coala_block_gatv2_aggregate[_csr]); `index` (the block's index tensors) and `tail` describe the block.  lse is the state of
+    the backward alone: it is computed, but not kept, when nothing needs a gradient."""
+    fs, fd, at = feat_src.contiguous(), feat_dst.contiguous(), attn.contiguous()
+    H, D = fs.shape[1], fs.shape[2]
+    out = torch.empty((n_dst, H, D), dtype=torch.float32, device=fs.device)
+    lse = torch.empty((n_dst, H), dtype=torch.float32, device=fs.device)
+    _capi.check(entry(fs.device.index or 0, *(t.data_ptr() for t in index), fs.data_ptr(), fd.data_ptr(), at.data_ptr(), out.data_ptr(),
+                      lse.data_ptr(), n_dst, *tail, H, D, negative_slope, current_stream()))
+    if any(ctx.needs_input_grad[:3]):
+        ctx.save_for_backward(fs, fd, at, out, lse, *index)
+    ctx.slope = negative_slope
+    return out
+
+
+def _gatv2_backward(ctx, grad_out, entry):
+    """All three gradients in one launch (coala_block_gatv2_aggregate[_csr]_backward); a gradient nobody asked for is neither computed
+    nor allocated.  grad_attn comes as [parts, H * D] partial sums, one row per block of the launch, and is their sum over dim 0."""
+    need_src, need_dst, need_attn = ctx.needs_input_grad[:3]
+    if not (need_src or need_dst or need_attn):
+        return None, None, None
+    fs, fd, at, out, lse, *index = ctx.saved_tensors
+    n_dst, tail = out.shape[0], ((index[0].shape[1],) if len(index) == 1 else ())
+    g = grad_out.contiguous()
+    H, D = fs.shape[1], fs.shape[2]
+    parts = _gatv2_parts(n_dst)
+    grad_src = torch.zeros_like(fs) if need_src else None
+    grad_dst = torch.empty_like(fd) if need_dst else None
+    partials = (torch.zeros if n_dst == 0 else torch.empty)((parts, H * D), dtype=torch.float32, device=fs.device) if need_attn else None
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    _capi.check(entry(fs.device.index or 0, *(t.data_ptr() for t in index), fs.data_ptr(), fd.data_ptr(), at.data_ptr(), out.data_ptr(), lse.data_ptr(), g.data_ptr(),
+                      ptr(grad_src), ptr(grad_dst), ptr(partials), parts, n_dst, *tail, H, D, ctx.slope, current_stream()))
+    return grad_src, grad_dst, partials.sum(0).view_as(at) if need_attn else None
+
+
+class _Gatv2Aggregate(torch.autograd.Function):
+    """DGL GATv2Conv's attention step on a fixed block (coala_block_gatv2_aggregate): per head, a softmax over the valid nbr[d, j] of
+    sum_c attn[h, c] leaky_relu(feat_src[s, h, c] + feat_dst[d, h, c]), then the weighted sum of feat_src[s].  One kernel forward, one
+    backward (gradients for feat_src, feat_dst and attn); no [E, H, D] intermediate in either."""
+
+    @staticmethod
+    def forward(ctx, feat_src, feat_dst, attn, nbr, negative_slope):
+        return _gatv2_forward(ctx, feat_src, feat_dst, attn, _lib.coala_block_gatv2_aggregate, (nbr,), nbr.shape[0], (nbr.shape[1],), negative_slope)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _gatv2_backward(ctx, grad_out, _lib.coala_block_gatv2_aggregate_backward) + (None,) * 2
+
+
+class _Gatv2AggregateCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_gatv2_aggregate_csr): row d's edges are indices[indptr[d]:indptr[d+1]]."""
+
+    @staticmethod
+    def forward(ctx, feat_src, feat_dst, attn, indptr, indices, negative_slope):
+        return _gatv2_forward(ctx, feat_src, feat_dst, attn, _lib.coala_block_gatv2_aggregate_csr, (indptr, indices), indptr.numel() - 1, (),
+                              negative_slope)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _gatv2_backward(ctx, grad_out, _lib.coala_block_gatv2_aggregate_csr_backward) + (None,) * 3

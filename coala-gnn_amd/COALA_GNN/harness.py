@@ -1,7 +1,8 @@
 """Small consumers of the loader's 4-tuple on the native Block objects.  SageMean, a 2-layer GraphSAGE (mean) in plain torch, is
 used by bench.py's epoch leg and the tests; it stands where examples/models.py:DistSAGE + dgl.nn.SAGEConv stand in the reference's
 training script (examples/sbatch_ssd_gnn_train.py:98-145).  GAT and GCN mirror the reference's examples/models.py:GAT and :GCN on
-COALA_GNN.nn's GATConv and GraphConv (--model_type gat|gcn); GAT's attention step is a native kernel (Block.gat_aggregate).  GCN and
+COALA_GNN.nn's GATConv and GraphConv (--model_type gat|gcn); GAT's attention step is a native kernel (Block.gat_aggregate), and so is that
+of GATv2, the same model on GATv2Conv layers (--model_type gatv2, Block.gatv2_aggregate).  GCN and
 SAGE take edge_weight=<edata key> and then hand block.edata[key] to their layers (blocks sampled with NeighborSampler(edge_ids=True)).
 SAGE(aggregator_type='pool') and GIN (--model_type gin) are the models on the native max aggregation (Block.max_aggregate).  RGCN
 (--model_type rgcn) mirrors examples/models.py:RGCN on a homogenised graph: RelGraphConv layers, one weight matrix per edge type, on the
@@ -10,9 +11,9 @@ import time
 
 import torch
 
-from .nn import GATConv, GINConv, GraphConv, RelGraphConv, SAGEConv
+from .nn import GATConv, GATv2Conv, GINConv, GraphConv, RelGraphConv, SAGEConv
 
-__all__ = ["SageMean", "SAGE", "GAT", "GCN", "GIN", "RGCN", "train_steps", "FlatGradAllReduce"]
+__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -39,6 +40,26 @@ class GAT(torch.nn.Module):
         dims = [in_feats] + [n_hidden * num_heads] * (n_layers - 1)
         outs = [n_hidden] * (n_layers - 1) + [n_classes]
         self.layers = torch.nn.ModuleList(GATConv((dims[i], dims[i]), outs[i], num_heads) for i in range(n_layers))
+
+    def forward(self, blocks, x):
+        h = x
+        for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+            h = layer(block, (h, block.dst_rows(h)))
+            if i + 1 < len(self.layers):
+                h = h.flatten(1)
+        return h.mean(1).log_softmax(dim=-1)
+
+
+class GATv2(torch.nn.Module):
+    """GAT's shape on GATv2Conv layers: n_layers layers of num_heads heads, no activation between them, the heads flattened between
+    layers; the last layer's heads are averaged and passed through log_softmax.  share_weights: every layer uses one projection for the
+    source and the destination rows (GATv2Conv's share_weights)."""
+
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, num_heads, share_weights=False):
+        super().__init__()
+        dims = [in_feats] + [n_hidden * num_heads] * (n_layers - 1)
+        outs = [n_hidden] * (n_layers - 1) + [n_classes]
+        self.layers = torch.nn.ModuleList(GATv2Conv(dims[i], outs[i], num_heads, share_weights=share_weights) for i in range(n_layers))
 
     def forward(self, blocks, x):
         h = x

@@ -1,9 +1,10 @@
-"""GATConv, GraphConv, SAGEConv, GINConv and RelGraphConv on the native Block objects, for the reference's GAT and GCN models (examples/models.py;
+"""GATConv, GATv2Conv, GraphConv, SAGEConv, GINConv and RelGraphConv on the native Block objects, for the reference's GAT and GCN models (examples/models.py;
 DGL is not installed on the MI355X image) and for DGL models ported to them.  All take (block, (h_src, h_dst)) as DGL's modules do on
 a block.
 
 GATConv's projections are dense and stay in torch; its attention step (score, per-destination softmax, weighted sum) is
-Block.gat_aggregate, a native kernel on both block forms.  GraphConv reduces to Block.mean_aggregate times the in-degree.  With
+Block.gat_aggregate, a native kernel on both block forms; GATv2Conv's, whose score is a dot product over the whole [H, D] row per edge,
+is Block.gatv2_aggregate, a native kernel as well, without the [E, H, D] intermediates of the formula.  GraphConv reduces to Block.mean_aggregate times the in-degree.  With
 edge_weight= (one value per neighbour slot, e.g. block.edata['w'] of a block sampled with edge_ids=True) GraphConv and SAGEConv
 aggregate with Block.weighted_sum_aggregate, DGL's u_mul_e_sum.  SAGEConv's 'pool' and GINConv's 'max' take their maximum with
 Block.max_aggregate (DGL's fn.max), a native kernel as well; GINConv's 'sum' is Block.weighted_sum_aggregate with unit weights.
@@ -11,7 +12,7 @@ RelGraphConv (one weight matrix per edge type) sums the messages per relation wi
 all its weight matrices in one GEMM."""
 import torch
 
-__all__ = ["GATConv", "GraphConv", "SAGEConv", "GINConv", "RelGraphConv"]
+__all__ = ["GATConv", "GATv2Conv", "GraphConv", "SAGEConv", "GINConv", "RelGraphConv"]
 
 
 class GATConv(torch.nn.Module):
@@ -60,6 +61,61 @@ class GATConv(torch.nn.Module):
         rst = block.gat_aggregate(el, er, feat_src, self.negative_slope)
         if self.bias is not None:
             rst = rst + self.bias.view(1, H, D)
+        if self.activation is not None:
+            rst = self.activation(rst)
+        return rst
+
+
+class GATv2Conv(torch.nn.Module):
+    """GATv2 attention layer (Brody et al., "How Attentive are Graph Attention Networks?"; DGL 1.x GATv2Conv).
+
+    Semantics, for destination node d, head h and the valid in-edges j of d (source s_j) in the block:
+        feat_src = fc_src(feat_drop(h_src)).view(-1, H, D);   feat_dst = fc_dst(feat_drop(h_dst)).view(-1, H, D)
+        e_j = sum_c attn[0, h, c] * leaky_relu(feat_src[s_j, h, c] + feat_dst[d, h, c], negative_slope);   a_j = softmax of e over d's in-edges
+        out[d, h, :] = sum_j a_j feat_src[s_j, h, :];   then activation, if any
+    -> [num_dst, H, D].  A destination without an in-edge gets zeros (DGL's allow_zero_in_degree=True).
+    Parameters, with the names and shapes of DGL 1.x, so that such a state_dict loads with strict=True:
+        fc_src.weight [H * D, in_src], fc_src.bias [H * D], fc_dst.weight [H * D, in_dst], fc_dst.bias [H * D], attn [1, H, D].
+    The bias flag is the bias of the two Linears, as in DGL: there is no separate bias parameter, and with bias=False the two bias keys
+    are absent.  DGL is not installed where this was written: the names are those of DGL's source as remembered, and they are what this
+    layer fixes.
+    share_weights=True with a single in_feats: fc_dst is fc_src (one weight in parameters(), no fc_dst.* key of its own values), and
+    the layer takes feat_dst = block.dst_rows(feat_src) -- DGL's feat_src[:num_dst], right on owner-bucketed blocks too -- instead
+    of a second projection; h_dst is then not read.  Otherwise h_dst must be the destination rows of h_src: block.dst_rows(h_src).
+    Initialisation: Xavier-normal with the gain of relu for fc_src.weight, fc_dst.weight and attn; biases zero.
+    Attention dropout and residual connections are not provided."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, negative_slope=0.2, bias=True, share_weights=False, activation=None):
+        super().__init__()
+        paired = isinstance(in_feats, (tuple, list))
+        in_src, in_dst = in_feats if paired else (in_feats, in_feats)
+        self._num_heads, self._out_feats = num_heads, out_feats
+        self.share_weights = bool(share_weights) and not paired
+        self.fc_src = torch.nn.Linear(in_src, out_feats * num_heads, bias=bias)
+        self.fc_dst = self.fc_src if self.share_weights else torch.nn.Linear(in_dst, out_feats * num_heads, bias=bias)
+        self.attn = torch.nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.feat_drop = torch.nn.Dropout(feat_drop)
+        self.negative_slope = negative_slope
+        self.activation = activation
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        for w in (self.fc_src.weight, self.fc_dst.weight, self.attn):
+            torch.nn.init.xavier_normal_(w, gain=gain)
+        for b in (self.fc_src.bias, self.fc_dst.bias):
+            if b is not None:
+                torch.nn.init.zeros_(b)
+
+    def forward(self, block, feat):
+        h_src, h_dst = feat
+        H, D = self._num_heads, self._out_feats
+        feat_src = self.fc_src(self.feat_drop(h_src)).view(-1, H, D)
+        if self.share_weights:
+            feat_dst = block.dst_rows(feat_src)
+        else:
+            feat_dst = self.fc_dst(self.feat_drop(h_dst)).view(-1, H, D)
+        rst = block.gatv2_aggregate(feat_src, feat_dst, self.attn, self.negative_slope)
         if self.activation is not None:
             rst = self.activation(rst)
         return rst

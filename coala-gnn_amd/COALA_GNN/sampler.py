@@ -11,8 +11,8 @@ import torch
 
 from COALA_GNN_Pybind import _capi, current_stream
 
-from .block_ops import (_GatAggregate, _GatAggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate, _MeanAggregateCSR, _RelSum,
-                        _RelSumCSR, _WeightedSum, _WeightedSumCSR)
+from .block_ops import (_GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
+                        _MeanAggregateCSR, _RelSum, _RelSumCSR, _WeightedSum, _WeightedSumCSR)
 
 __all__ = ["NeighborSampler", "LaborSampler", "CSCGraph", "Block", "ITEM_LIMIT", "EID"]
 
@@ -426,6 +426,43 @@ class Block(object):
         a = p / l[rows]
         out = torch.zeros((self.num_dst,) + tuple(feat_src.shape[1:]), dtype=feat_src.dtype, device=dev)
         return out.index_add(0, rows, a.unsqueeze(-1).to(feat_src.dtype) * feat_src[src])
+
+    def gatv2_aggregate(self, feat_src, feat_dst, attn, negative_slope=0.2):
+        """DGL GATv2Conv's attention step: for every dst node d and head h, a softmax over d's valid in-edges of
+        sum_c attn[h, c] * leaky_relu(feat_src[s, h, c] + feat_dst[d, h, c], negative_slope), then sum_j a_j feat_src[s_j, h, :].
+        feat_src [num_src, H, D], feat_dst [num_dst, H, D], attn [H, D] or [1, H, D] -> [num_dst, H, D]; a dst node without an in-edge
+        gets zeros.  Native kernels (gradients for all three inputs, no [E, H, D] intermediate) under the conditions of gat_aggregate:
+        fp32 GPU tensors, fan-out <= 32 or the ragged form of a full layer, and H <= 16; plain torch otherwise."""
+        if attn.dim() == 3 and attn.shape[0] == 1:
+            attn = attn[0]
+        if feat_src.dim() != 3 or tuple(attn.shape) != tuple(feat_src.shape[1:]) or tuple(feat_dst.shape) != (self.num_dst,) + tuple(attn.shape):
+            raise ValueError(f"feat_src {tuple(feat_src.shape)}, feat_dst {tuple(feat_dst.shape)}, attn {tuple(attn.shape)}: this block takes "
+                             f"[{self.num_src}, H, D], [{self.num_dst}, H, D] and [H, D] or [1, H, D]")
+        native = (feat_src.is_cuda and feat_dst.is_cuda and attn.is_cuda and all(t.dtype == torch.float32 for t in (feat_src, feat_dst, attn))
+                  and feat_src.shape[1] <= 16)
+        if self.nbr is None:
+            if native and self.indptr.is_cuda and self.indices.is_cuda:
+                return _Gatv2AggregateCSR.apply(feat_src, feat_dst, attn, self.indptr.contiguous(), self.indices.contiguous(), float(negative_slope))
+        elif native and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
+            return _Gatv2Aggregate.apply(feat_src, feat_dst, attn, self.nbr, float(negative_slope))
+        return self.gatv2_aggregate_torch(feat_src, feat_dst, attn, negative_slope)
+
+    def gatv2_aggregate_torch(self, feat_src, feat_dst, attn, negative_slope=0.2):
+        """gatv2_aggregate in plain torch, any device and dtype: an edge-list softmax that materialises [E, H, D] (the gathered source
+        rows, their sum with the destination rows, its leaky_relu).  The fallback of gatv2_aggregate, and its reference."""
+        rows, src = self._edges()
+        dev = feat_src.device
+        rows, src = rows.to(dev), src.to(dev)
+        H = feat_src.shape[1]
+        fs = feat_src[src]                                                                       # [E, H, D]
+        e = (torch.nn.functional.leaky_relu(fs + feat_dst[rows], negative_slope) * attn.reshape((1,) + tuple(feat_src.shape[1:]))).sum(-1)
+        m = torch.full((self.num_dst, H), float("-inf"), dtype=e.dtype, device=dev)
+        m = m.scatter_reduce(0, rows.unsqueeze(1).expand(-1, H), e.detach(), "amax").detach()   # the shift cancels in the softmax
+        p = torch.exp(e - m[rows])
+        l = torch.zeros((self.num_dst, H), dtype=e.dtype, device=dev).index_add(0, rows, p)
+        a = p / l[rows]
+        out = torch.zeros((self.num_dst,) + tuple(feat_src.shape[1:]), dtype=feat_src.dtype, device=dev)
+        return out.index_add(0, rows, a.unsqueeze(-1).to(feat_src.dtype) * fs)
 
 
 class NeighborSampler(object):

@@ -1,7 +1,7 @@
 // coala_block_ops.hip -- what a model computes on a sampled block (coala_sampler.hip makes the blocks), for gfx950: mean aggregation
 // (DGL's SAGEConv "mean"), weighted sum aggregation (DGL's u_mul_e_sum: GraphConv / SAGEConv with edge_weight=), max aggregation
-// (DGL's fn.max: SAGEConv "pool", GINConv "max"), the relation-typed sum (RelGraphConv's message step) and GAT attention aggregation
-// (GATConv's message step), forward and backward, on
+// (DGL's fn.max: SAGEConv "pool", GINConv "max"), the relation-typed sum (RelGraphConv's message step) and GAT / GATv2 attention aggregation
+// (GATConv's and GATv2Conv's message steps), forward and backward, on
 // fixed blocks (nbr_local[n_dst, fanout], -1 = no neighbour) and on the CSR blocks of full layers.  Stateless entry points: no
 // handle, every launch on the caller's stream.
 #include <hip/hip_runtime.h>
@@ -324,6 +324,231 @@ __global__ __launch_bounds__(kBlock) void gat_aggregate_backward_kernel(const in
     }
 }
 
+// GATv2 attention on a block (DGL GATv2Conv's message step; the projections fc_src / fc_dst stay in torch).  For dst d, head h and the
+// valid in-edges j of d (source s_j):
+//   z_jc = feat_src[s_j, h, c] + feat_dst[d, h, c],  e_j = sum_c attn[h, c] leaky_relu(z_jc, slope),  a_j = softmax of e over the row,
+//   out[d, h, :] = sum_j a_j feat_src[s_j, h, :]
+// The score does not split into a per-source and a per-destination scalar as GAT's does: it is a dot product over the [H * D] row per
+// edge.  gat_aggregate_kernel's mapping and its online softmax, with one step in front of every chunk, the score pass: a lane per
+// float of the row, 64 floats at a time, attn and feat_dst[d] of the pass in registers, the chunk's edges in the inner loop, and the
+// per-head sums added into the LDS [edge][head] array by head_segment_add in a fixed order.  The weighted sum then reads the chunk's
+// source rows a second time (at most 64 rows: from the cache), so the HBM bytes are GAT's plus feat_dst, and nothing of size E is
+// written.  The fixed and the CSR kernels are the same code on the same lanes.
+// e[j * kGatMaxHeads + h] += edge j's score of head h, for the n edges of a chunk; with DOT also dot[..] += <g[h, :], feat_src[s_j, h, :]>.
+template <bool DOT>
+__device__ __forceinline__ void gatv2_score_pass(float* e, float* dot, int32_t mine, int n, const float* __restrict__ feat_src,
+                                                 const float* __restrict__ fd, const float* __restrict__ attn, const float* __restrict__ g,
+                                                 int lane, int hd, int dim, float slope) {
+    for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: head_segment_add shuffles across every lane
+        const int c = c0 + lane;
+        const bool in = c < hd;
+        const float a = in ? attn[c] : 0.0f;
+        const float b = in ? fd[c] : 0.0f;
+        const float gc = DOT && in ? g[c] : 0.0f;
+        for (int j = 0; j < n; ++j) {
+            const int32_t s = __shfl(mine, j);
+            if (s < 0) continue; // wave-uniform
+            const float f = in ? feat_src[(int64_t)s * hd + c] : 0.0f;
+            const float z = f + b;
+            head_segment_add(e + j * kGatMaxHeads, in ? a * (z > 0.0f ? z : z * slope) : 0.0f, lane, c0, dim, hd);
+            if (DOT) head_segment_add(dot + j * kGatMaxHeads, gc * f, lane, c0, dim, hd);
+        }
+    }
+}
+
+template <int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void gatv2_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
+                                                                 const float* __restrict__ feat_src, const float* __restrict__ feat_dst,
+                                                                 const float* __restrict__ attn, float* __restrict__ out,
+                                                                 float* __restrict__ lse, int64_t n_dst, int heads, int dim, float slope) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];  // the chunk's scores e_j, then exp(e_j - m), [edge][head]
+    __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];  // per head: running max, running sum, the chunk's rescale factor
+    const int lane = threadIdx.x & 63;
+    float* w = w_lds[threadIdx.x >> 6];
+    float* m_run = st_lds[threadIdx.x >> 6];
+    float* l_run = m_run + kGatMaxHeads;
+    float* scl = l_run + kGatMaxHeads;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int hd = heads * dim, units = hd / VEC, upl = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        wave_lds_sync(); // the previous row has read m_run / l_run
+        if (lane < heads) {
+            m_run[lane] = kNegInf;
+            l_run[lane] = 0.0f;
+        }
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+            const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
+            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+            wave_lds_sync(); // the previous chunk has read w and scl; m_run / l_run are set
+            for (int h = 0; h < heads; ++h) w[lane * kGatMaxHeads + h] = 0.0f;
+            wave_lds_sync();
+            gatv2_score_pass<false>(w, nullptr, mine, n, feat_src, feat_dst + d * hd, attn, nullptr, lane, hd, dim, slope);
+            wave_lds_sync();
+            for (int h = 0; h < heads; ++h) { // lane j reads and rewrites only edge j's words
+                const float e = mine >= 0 ? w[lane * kGatMaxHeads + h] : kNegInf;
+                const float mo = m_run[h];
+                const float mn = fmaxf(mo, wave_max(e));
+                const float p = mine >= 0 ? expf(e - mn) : 0.0f;
+                const float sum = wave_sum(p);
+                const float sc = mo == mn ? 1.0f : (mo == kNegInf ? 0.0f : expf(mo - mn));
+                w[lane * kGatMaxHeads + h] = p;
+                if (lane == 0) {
+                    m_run[h] = mn;
+                    l_run[h] = l_run[h] * sc + sum;
+                    scl[h] = sc;
+                }
+            }
+            wave_lds_sync();
+            const bool first = e0 == beg, last = e0 + 64 >= end;
+            for (int u0 = 0; u0 < units; u0 += 64) {
+                const int u = u0 + lane;
+                const int hu = u < units ? u / upl : 0;
+                float* o = out + d * hd + (int64_t)u * VEC;
+                vf acc = vf(0.0f);
+                if (!first && u < units) acc = *reinterpret_cast<const vf*>(o) * scl[hu];
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && u < units)
+                        acc += w[j * kGatMaxHeads + hu] * *reinterpret_cast<const vf*>(feat_src + (int64_t)s * hd + (int64_t)u * VEC);
+                }
+                if (u < units) {
+                    if (last) acc *= l_run[hu] > 0.0f ? 1.0f / l_run[hu] : 0.0f;
+                    *reinterpret_cast<vf*>(o) = acc;
+                }
+            }
+        }
+        if (beg == end) // no chunk ran: an empty CSR row
+            for (int u = lane; u < units; u += 64) *reinterpret_cast<vf*>(out + d * hd + (int64_t)u * VEC) = vf(0.0f);
+        wave_lds_sync();
+        if (lane < heads) lse[d * heads + lane] = l_run[lane] > 0.0f ? m_run[lane] + logf(l_run[lane]) : kNegInf;
+    }
+}
+
+// Backward, all three gradients in one launch, each of them optional (null).  a_j = exp(e_j - lse[d, h]) with e_j recomputed by a second
+// score pass, which also sums dot_j = <g[d, h, :], feat_src[s_j, h, :]>; then per edge and head t_j = a_j (dot_j - <g, out>), and a
+// third walk over the chunk's rows, a lane per float c, with k_jc = z_jc > 0 ? 1 : slope:
+//   grad_src[s_j, c] += a_j g[d, c] + t_j attn[c] k_jc   hardware float atomics (zeroed by the caller), 256 contiguous bytes per wave
+//                                                        instruction: the only atomics;
+//   grad_dst[d, c]    = sum_j t_j attn[c] k_jc           summed in slot order in a register, stored once per chunk (a later chunk of a
+//                                                        long row adds to what the earlier ones stored);
+//   grad_attn[c]      = sum_d sum_j t_j leaky_relu(z_jc)  no atomics: lane c keeps the sum over its wave's rows, the waves of a block add
+//                                                        theirs through LDS in wave order, and block b stores row b of the caller's
+//                                                        partials [gridDim.x, H * D]; the caller sums the rows.  The same grid gives
+//                                                        the same bits.
+// RP > 0: the row is at most RP 64-float passes long and the grad_attn sums are RP registers.  RP == 0: any row length; a block is then
+// one wave (the host launches 64 threads) and adds each pass's sum into its own partials row, the same lane at the same address.
+template <int RP, bool CSR>
+__global__ __launch_bounds__(kBlock) void gatv2_aggregate_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                          int fanout, const float* __restrict__ feat_src,
+                                                                          const float* __restrict__ feat_dst, const float* __restrict__ attn,
+                                                                          const float* __restrict__ out, const float* __restrict__ lse,
+                                                                          const float* __restrict__ grad_out, float* __restrict__ grad_src,
+                                                                          float* __restrict__ grad_dst, float* __restrict__ grad_attn_parts,
+                                                                          int64_t n_dst, int heads, int dim, float slope) {
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // the chunk's scores e_j, then a_j, [edge][head]
+    __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g, feat_src_j>, then t_j, [edge][head]
+    __shared__ float hs_lds[kWavesPerBlock][kGatMaxHeads];       // per head: <g, out>
+    static_assert(RP * 64 <= 64 * kGatMaxHeads, "the waves' grad_attn sums are combined through w_lds");
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+    float* w = w_lds[wv];
+    float* dot = dot_lds[wv];
+    float* gout = hs_lds[wv];
+    const int64_t wave = (int64_t)blockIdx.x * wpb + wv;
+    const int64_t n_waves = (int64_t)gridDim.x * wpb;
+    const int hd = heads * dim;
+    float* prow = grad_attn_parts ? grad_attn_parts + (int64_t)blockIdx.x * hd : nullptr;
+    float ga_reg[RP > 0 ? RP : 1];
+    for (int p = 0; p < (RP > 0 ? RP : 1); ++p) ga_reg[p] = 0.0f;
+    if (RP == 0 && prow)
+        for (int c = lane; c < hd; c += 64) prow[c] = 0.0f;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        const float* g = grad_out + d * hd;
+        const float* fd = feat_dst + d * hd;
+        wave_lds_sync(); // the previous row has read gout
+        if (lane < heads) gout[lane] = 0.0f;
+        wave_lds_sync();
+        for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count
+            const int c = c0 + lane;
+            head_segment_add(gout, c < hd ? g[c] * out[d * hd + c] : 0.0f, lane, c0, dim, hd);
+        }
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
+            const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
+            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+            const bool first = e0 == beg;
+            wave_lds_sync(); // the previous chunk has read w and dot
+            for (int h = 0; h < heads; ++h) {
+                w[lane * kGatMaxHeads + h] = 0.0f;
+                dot[lane * kGatMaxHeads + h] = 0.0f;
+            }
+            wave_lds_sync();
+            gatv2_score_pass<true>(w, dot, mine, n, feat_src, fd, attn, g, lane, hd, dim, slope);
+            wave_lds_sync();
+            for (int h = 0; h < heads; ++h) { // lane j reads and rewrites only edge j's words
+                float a = 0.0f, t = 0.0f;
+                if (mine >= 0) {
+                    a = expf(w[lane * kGatMaxHeads + h] - lse[d * heads + h]);
+                    t = a * (dot[lane * kGatMaxHeads + h] - gout[h]);
+                }
+                w[lane * kGatMaxHeads + h] = a;
+                dot[lane * kGatMaxHeads + h] = t;
+            }
+            wave_lds_sync();
+            auto pass = [&](int c0, float& ga_sum) {
+                const int c = c0 + lane;
+                const bool in = c < hd;
+                const int hc = in ? c / dim : 0;
+                const float at = in ? attn[c] : 0.0f;
+                const float b = in ? fd[c] : 0.0f;
+                const float gc = in ? g[c] : 0.0f;
+                float gd = 0.0f, ga = 0.0f;
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && in) { // every lane takes the shuffle above
+                        const float z = feat_src[(int64_t)s * hd + c] + b;
+                        const float tj = dot[j * kGatMaxHeads + hc];
+                        const float u = tj * at * (z > 0.0f ? 1.0f : slope);
+                        if (grad_src) unsafeAtomicAdd(grad_src + (int64_t)s * hd + c, w[j * kGatMaxHeads + hc] * gc + u);
+                        gd += u;
+                        ga += tj * (z > 0.0f ? z : z * slope);
+                    }
+                }
+                if (in && grad_dst) grad_dst[d * hd + c] = first ? gd : grad_dst[d * hd + c] + gd;
+                ga_sum += ga;
+            };
+            if constexpr (RP > 0) {
+#pragma unroll
+                for (int p = 0; p < RP; ++p)
+                    if (p * 64 < hd) pass(p * 64, ga_reg[p]);
+            } else {
+                for (int c0 = 0; c0 < hd; c0 += 64) {
+                    float ga = 0.0f;
+                    pass(c0, ga);
+                    if (prow && c0 + lane < hd) prow[c0 + lane] += ga;
+                }
+            }
+        }
+        if (beg == end && grad_dst) // no chunk ran: an empty CSR row
+            for (int c = lane; c < hd; c += 64) grad_dst[d * hd + c] = 0.0f;
+    }
+    if constexpr (RP > 0) {
+        if (!prow) return; // block-uniform
+        __syncthreads(); // every wave of the block is past its rows: w_lds is free
+#pragma unroll
+        for (int p = 0; p < RP; ++p) w[p * 64 + lane] = ga_reg[p];
+        __syncthreads();
+        for (int c = threadIdx.x; c < hd; c += kBlock) {
+            float sum = w_lds[0][c];
+            for (int k = 1; k < kWavesPerBlock; ++k) sum += w_lds[k][c];
+            prow[c] = sum;
+        }
+    }
+}
 
 // Weighted sum aggregation (DGL's u_mul_e_sum, what GraphConv / SAGEConv compute with edge_weight=): out[d] = sum over the valid edges
 // j of row d of w_j * h_src[s_j], one weight per neighbour slot (w is laid out like the block's index array).  The mean kernel's
@@ -751,6 +976,88 @@ int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, co
                        indices, 0, el, er, feat, out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim, negative_slope);
     HIPCHK(hipGetLastError());
     return COALA_OK;
+}
+
+} // extern "C"
+
+namespace {
+template <bool CSR>
+int gatv2_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* feat_src, const float* feat_dst,
+                 const float* attn, float* out, float* lse, int64_t n_dst, int heads, int dim, float slope, void* stream) {
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !feat_src || !feat_dst || !attn || !out || !lse) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
+    dispatch_vec(vec4_ok(dim, feat_src, out), [&](auto vec) {
+        hipLaunchKernelGGL((gatv2_aggregate_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, fanout, feat_src,
+                           feat_dst, attn, out, lse, n_dst, heads, dim, slope);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+// The grad_attn partials rule: with a partials buffer the grid is exactly `parts` blocks and block b stores row b.  The sums of a row
+// of at most 1024 floats stay in registers (RP = 1, 2, 4, 8 or 16 passes of 64 floats, four waves a block); a longer row takes the
+// RP = 0 kernel, one wave a block.  Without a partials buffer the grid is that of the other block ops.
+template <bool CSR>
+int gatv2_backward_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* feat_src, const float* feat_dst,
+                          const float* attn, const float* out, const float* lse, const float* grad_out, float* grad_src, float* grad_dst,
+                          float* grad_attn_parts, int parts, int64_t n_dst, int heads, int dim, float slope, void* stream) {
+    if (grad_attn_parts && parts < 1) return fail(COALA_EINVAL, "bad block shape (parts >= 1)");
+    if (n_dst == 0 || (!grad_src && !grad_dst && !grad_attn_parts)) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !feat_src || !feat_dst || !attn || !out || !lse || !grad_out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const int passes = (heads * dim + 63) / 64;
+    const bool regs = grad_attn_parts && passes <= kGatMaxHeads;
+    const dim3 grid(grad_attn_parts ? parts : grid1d(n_dst * 64, kBlock, 8192)), blk(grad_attn_parts && !regs ? 64 : kBlock);
+    auto launch = [&](auto rp) {
+        hipLaunchKernelGGL((gatv2_aggregate_backward_kernel<decltype(rp)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, fanout,
+                           feat_src, feat_dst, attn, out, lse, grad_out, grad_src, grad_dst, grad_attn_parts, n_dst, heads, dim, slope);
+    };
+    if (!regs) launch(std::integral_constant<int, 0>{});
+    else if (passes <= 1) launch(std::integral_constant<int, 1>{});
+    else if (passes <= 2) launch(std::integral_constant<int, 2>{});
+    else if (passes <= 4) launch(std::integral_constant<int, 4>{});
+    else if (passes <= 8) launch(std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 16>{});
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+} // namespace
+
+extern "C" {
+
+int coala_block_gatv2_aggregate(int device, const int32_t* nbr, const float* feat_src, const float* feat_dst, const float* attn, float* out,
+                                float* lse, int64_t n_dst, int fanout, int heads, int dim, float negative_slope, void* stream) {
+    if (fanout < 1 || fanout > 32) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+    if (int rc = gat_check(n_dst, heads, dim)) return rc;
+    return gatv2_launch<false>(device, nullptr, nbr, fanout, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, negative_slope, stream);
+}
+
+int coala_block_gatv2_aggregate_backward(int device, const int32_t* nbr, const float* feat_src, const float* feat_dst, const float* attn,
+                                         const float* out, const float* lse, const float* grad_out, float* grad_src, float* grad_dst,
+                                         float* grad_attn_parts, int parts, int64_t n_dst, int fanout, int heads, int dim, float negative_slope,
+                                         void* stream) {
+    if (fanout < 1 || fanout > 32) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+    if (int rc = gat_check(n_dst, heads, dim)) return rc;
+    return gatv2_backward_launch<false>(device, nullptr, nbr, fanout, feat_src, feat_dst, attn, out, lse, grad_out, grad_src, grad_dst,
+                                        grad_attn_parts, parts, n_dst, heads, dim, negative_slope, stream);
+}
+
+int coala_block_gatv2_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* feat_src, const float* feat_dst,
+                                    const float* attn, float* out, float* lse, int64_t n_dst, int heads, int dim, float negative_slope,
+                                    void* stream) {
+    if (int rc = gat_check(n_dst, heads, dim)) return rc;
+    return gatv2_launch<true>(device, indptr, indices, 0, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, negative_slope, stream);
+}
+
+int coala_block_gatv2_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* feat_src,
+                                             const float* feat_dst, const float* attn, const float* out, const float* lse, const float* grad_out,
+                                             float* grad_src, float* grad_dst, float* grad_attn_parts, int parts, int64_t n_dst, int heads,
+                                             int dim, float negative_slope, void* stream) {
+    if (int rc = gat_check(n_dst, heads, dim)) return rc;
+    return gatv2_backward_launch<true>(device, indptr, indices, 0, feat_src, feat_dst, attn, out, lse, grad_out, grad_src, grad_dst,
+                                       grad_attn_parts, parts, n_dst, heads, dim, negative_slope, stream);
 }
 
 } // extern "C"

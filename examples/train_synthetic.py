@@ -5,6 +5,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
 
   python examples/train_synthetic.py --nodes 200000 --dim 128 --epochs 2
   python examples/train_synthetic.py --model_type gat --num_heads 4 --fan_out 5,5 --eval_fan_out=-1,-1
+  python examples/train_synthetic.py --model_type gatv2 --num_heads 4 --share_weights
   python examples/train_synthetic.py --model_type gcn --edge_weights random --use_edge_weight
   python examples/train_synthetic.py --sampler labor --fan_out 10,10
   python examples/train_synthetic.py --sage_aggregator pool
@@ -27,7 +28,7 @@ import torch  # noqa: E402
 
 from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
-from COALA_GNN.harness import GAT, GCN, GIN, RGCN, SAGE, SageMean  # noqa: E402
+from COALA_GNN.harness import GAT, GCN, GIN, RGCN, SAGE, GATv2, SageMean  # noqa: E402
 from COALA_GNN.sampler import LaborSampler, NeighborSampler  # noqa: E402
 from COALA_GNN.synthetic import alloc_pinned_table, edge_types_by_source, powerlaw_csc  # noqa: E402
 
@@ -64,14 +65,19 @@ def main():
     # accepted so that the reference's command lines (examples/4GB_script.sh, Cache_compare_script.sh, Distribution_compare_script.sh) run as they are
     ap.add_argument("--num_layers", type=int, default=None, help="must equal the number of fan-outs when given")
     ap.add_argument("--feat_cpu", action="store_true", help="features in pinned host memory: always the case here (the NVMe tier is out of scope)")
-    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "sage", "gcn", "gin", "rgcn"],
-                    help="sage: GraphSAGE (--sage_aggregator); gat: GAT with --num_heads heads (native attention aggregation); gcn: GraphConv, "
+    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "gatv2", "sage", "gcn", "gin", "rgcn"],
+                    help="sage: GraphSAGE (--sage_aggregator); gat: GAT with --num_heads heads (native attention aggregation); gatv2: the same model on GATv2Conv layers (--share_weights); gcn: GraphConv, "
                          "norm='both'; gin: GINConv layers (--gin_aggregator), an MLP in each; rgcn: RelGraphConv layers, one weight matrix per edge "
                          "type (--num_rels synthetic types, the source node's id modulo --num_rels; native relation-typed sum)")
     ap.add_argument("--sage_aggregator", type=str, default="mean", choices=["mean", "gcn", "pool"],
                     help="aggregator of --model_type sage; pool: the maximum of relu(fc_pool(h)) over the neighbours (native max aggregation)")
     ap.add_argument("--gin_aggregator", type=str, default="sum", choices=["sum", "max", "mean"], help="aggregator of --model_type gin")
-    ap.add_argument("--num_heads", type=int, default=4, help="attention heads of --model_type gat")
+    ap.add_argument("--seed", type=int, default=0,
+                    help="seed of torch's generators, set before the model is built: its initial weights (and dropout masks) are the same "
+                         "from run to run, as the synthetic data and the samplers' draws already are; negative: not seeded")
+    ap.add_argument("--num_heads", type=int, default=4, help="attention heads of --model_type gat and gatv2")
+    ap.add_argument("--share_weights", action="store_true",
+                    help="--model_type gatv2: one projection for the source and the destination rows of every layer (GATv2Conv's share_weights)")
     ap.add_argument("--num_rels", type=int, default=4, help="edge types of --model_type rgcn (1..64)")
     ap.add_argument("--rgcn_regularizer", type=str, default="none", choices=["none", "basis"], help="weight regularizer of --model_type rgcn")
     ap.add_argument("--num_bases", type=int, default=None, help="bases of --rgcn_regularizer basis (default: --num_rels)")
@@ -131,7 +137,7 @@ def main():
         edata, prob = {"w": w}, "w"
     if args.use_edge_weight and prob is None:
         ap.error("--use_edge_weight needs --edge_weights random")
-    ew = "w" if args.use_edge_weight and args.model_type not in ("gat", "gin", "rgcn") else None
+    ew = "w" if args.use_edge_weight and args.model_type not in ("gat", "gatv2", "gin", "rgcn") else None
     rgcn = args.model_type == "rgcn"
     if rgcn:   # the edge types of a homogenised heterograph, in CSC order; the blocks find theirs through their edge ids
         if not 1 <= args.num_rels <= 64:
@@ -151,8 +157,12 @@ def main():
                                         args.cache_size, device, refresh_counter=args.refresh_counter,
                                         cache_backend=args.cache_backend, sim_buf=feat, shuffle=False, num_rows=args.nodes,
                                         prefetch=args.prefetch)                                             # :82-95
+    if args.seed >= 0:
+        torch.manual_seed(args.seed)
     if args.model_type == "gat":                                                                            # :220-231
         model = GAT(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads).to(device)
+    elif args.model_type == "gatv2":
+        model = GATv2(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads, args.share_weights).to(device)
     elif args.model_type == "gcn":
         model = GCN(args.dim, args.hidden_channels, args.num_classes, len(fan_out), edge_weight=ew).to(device)
     elif args.model_type == "gin":

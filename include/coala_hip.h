@@ -540,6 +540,48 @@ int coala_block_gat_aggregate_csr(int device, const int64_t* indptr, const int32
 int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er,
                                            const float* feat, const float* out, const float* lse, const float* grad_out, float* grad_feat,
                                            float* grad_el, float* grad_er, int64_t n_dst, int heads, int dim, float negative_slope, void* stream);
+/* GATv2 attention aggregation (DGL GATv2Conv's message step; its projections are dense and stay outside).  The score does not split
+ * into a per-source and a per-destination scalar: for dst d, head h and the valid in-edges j of d with source s_j,
+ *   z_jc = feat_src[s_j, h, c] + feat_dst[d, h, c];  e_j = sum_c attn[h, c] * leaky_relu(z_jc, negative_slope);
+ *   a_j = exp(e_j - m) / sum_k exp(e_k - m), m = max_k e_k;  out[d, h, :] = sum_j a_j feat_src[s_j, h, :].
+ * feat_src fp32 [n_src, heads, dim], feat_dst fp32 [n_dst, heads, dim], attn fp32 [heads, dim], out fp32 [n_dst, heads, dim], all
+ * contiguous; heads 1..16, dim >= 1, heads * dim < 2^31.  A row without a valid edge gives exactly 0.  lse fp32 [n_dst, heads] is the
+ * log-sum-exp of the row's scores (-inf for a row without a valid edge), the state the backward needs besides out.
+ * Fixed form: nbr int32 [n_dst, fanout], -1 padded, fan-out 1..32.  CSR form: the edges of row d are indices[indptr[d] .. indptr[d+1]),
+ * any degree: one wave takes a row 64 edges at a time, GAT's online max and rescale.  Per chunk the scores are summed into on-chip
+ * memory first, then the chunk's source rows are read a second time (from the cache) for the weighted sum: no buffer of a size
+ * proportional to the number of edges exists.  The forward is deterministic, and a fixed row whose valid entries come first, in CSC
+ * order, gives the bits of the same CSR row (out, lse and the backward's grad_dst).
+ * Backward, with g = grad_out [n_dst, heads, dim], out / lse from the forward, a_j = exp(e_j - lse) from recomputed scores,
+ * t_j = a_j (<g[d, h, :], feat_src[s_j, h, :]> - <g[d, h, :], out[d, h, :]>) and k_jc = z_jc > 0 ? 1 : negative_slope:
+ *   grad_src[s_j, h, c] += a_j g[d, h, c] + t_j attn[h, c] k_jc   hardware float atomics: the caller zeroes grad_src [n_src, heads, dim],
+ *                                                                the order of the additions varies;
+ *   grad_dst[d, h, c]    = sum_j t_j attn[h, c] k_jc              [n_dst, heads, dim], written whole, in slot order: deterministic;
+ *   grad_attn[h, c]      = sum_d sum_j t_j leaky_relu(z_jc)        delivered as partial sums, without atomics.
+ * Each of the three outputs may be NULL (not wanted: not computed); with all three NULL nothing is launched.
+ * The grad_attn rule: grad_attn_parts is fp32 [parts, heads * dim], parts >= 1 chosen by the caller (for instance
+ * min(ceil(n_dst / 4), 1024)).  The launch then has exactly `parts` blocks; block b sums the rows its waves take (row d belongs to
+ * wave d mod the number of waves) in a fixed order and stores row b of the buffer whole, zeros if it took no row.  grad_attn is the
+ * sum of the buffer over its first dimension, which the caller takes; the same parts gives the same bits, run after run.  A row of
+ * heads * dim <= 1024 floats runs four waves a block, a longer one a single wave a block.
+ * Refused with COALA_EINVAL and nothing launched: "bad block shape" (fan-out outside 1..32, heads outside 1..16, dim < 1, n_dst < 0,
+ * parts < 1 with a partials buffer), "null buffer"; n_dst == 0 launches nothing and reads no pointer.
+ * Bytes per row of deg valid edges, hd = heads * dim: the forward reads deg * (4 hd + 4) + 8 hd from memory (GAT's plus feat_dst and
+ * attn; the second read of a source row is a cache hit) and writes 4 hd; the backward reads deg * (4 hd + 4) + 16 hd, adds 4 hd deg
+ * through atomics and writes 4 hd. */
+int coala_block_gatv2_aggregate(int device, const int32_t* nbr, const float* feat_src, const float* feat_dst, const float* attn, float* out,
+                                float* lse, int64_t n_dst, int fanout, int heads, int dim, float negative_slope, void* stream);
+int coala_block_gatv2_aggregate_backward(int device, const int32_t* nbr, const float* feat_src, const float* feat_dst, const float* attn,
+                                         const float* out, const float* lse, const float* grad_out, float* grad_src, float* grad_dst,
+                                         float* grad_attn_parts, int parts, int64_t n_dst, int fanout, int heads, int dim, float negative_slope,
+                                         void* stream);
+int coala_block_gatv2_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* feat_src, const float* feat_dst,
+                                    const float* attn, float* out, float* lse, int64_t n_dst, int heads, int dim, float negative_slope,
+                                    void* stream);
+int coala_block_gatv2_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* feat_src,
+                                             const float* feat_dst, const float* attn, const float* out, const float* lse, const float* grad_out,
+                                             float* grad_src, float* grad_dst, float* grad_attn_parts, int parts, int64_t n_dst, int heads,
+                                             int dim, float negative_slope, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Shared pinned-host ("UVA") region.  Replaces SharedUVAManager (COALA_GNN_Modules/shared_UVA.cuh:26-115):
