@@ -179,30 +179,48 @@ class Block(object):
     def to(self, device):
         return self
 
+    def _native_index(self):
+        """The block's index tensors as the native ops take them, (nbr,) or (indptr, indices); None when they cannot: the tensors are
+        not on the GPU, or nbr is not contiguous or has a fan-out above 32."""
+        if self.nbr is None:
+            if self.indptr.is_cuda and self.indices.is_cuda:
+                return self.indptr.contiguous(), self.indices.contiguous()
+        elif self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
+            return (self.nbr,)
+        return None
+
+    def _slots(self, dev=None):
+        """(row, local source index) of every neighbour slot in slot order, valid or not (-1: a padding slot): int64, on `dev` or, by
+        default, on the block's device."""
+        if self.nbr is None:
+            deg = self.indptr[1:] - self.indptr[:-1]
+            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg)
+            src = self.indices.to(torch.int64)
+        else:
+            rows = torch.arange(self.num_dst, device=self.nbr.device).repeat_interleave(self.nbr.shape[1])
+            src = self.nbr.reshape(-1).to(torch.int64)
+        return (rows, src) if dev is None else (rows.to(dev), src.to(dev))
+
     def mean_aggregate(self, h_src):
         """Mean of the sampled neighbours' rows for every dst node: fp32 [num_dst, dim] (GraphSAGE 'mean').  Native kernel for
         fp32 2-D rows on the GPU (fan-out <= 32, or the ragged form of a full layer); plain torch otherwise.  A tensor with more than
         two dimensions ([num_src, H, D], GAT's output) takes the torch path, which keeps the trailing shape -- the rule of
         weighted_sum_aggregate, max_aggregate and rel_sum_aggregate -- and is not flattened for the kernel, which reads shape[1] as
         the row width."""
-        native = h_src.is_cuda and h_src.dtype == torch.float32 and h_src.dim() == 2
-        if self.nbr is None:
-            if native and self.indptr.is_cuda and self.indices.is_cuda:
-                return _MeanAggregateCSR.apply(h_src, self.indptr.contiguous(), self.indices.contiguous())
-        elif native and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
-            return _MeanAggregate.apply(h_src, self.nbr)
+        index = self._native_index() if h_src.is_cuda and h_src.dtype == torch.float32 and h_src.dim() == 2 else None
+        if index is not None:
+            return (_MeanAggregateCSR if self.nbr is None else _MeanAggregate).apply(h_src, *index)
         return self.mean_aggregate_torch(h_src)
 
     def mean_aggregate_torch(self, h_src):
         """mean_aggregate in plain torch, any device and dtype, h_src [num_src, ...] -> [num_dst, ...]: its fallback, and its reference."""
         ones = (1,) * (h_src.dim() - 1)
         if self.nbr is None:   # ragged: sum the rows of each segment, divide by its length (an empty segment gives zeros)
-            deg = self.indptr[1:] - self.indptr[:-1]
-            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg)
-            idx = self.indices.to(torch.int64)
+            rows, idx = self._slots(h_src.device)
             valid = (idx >= 0).view((-1,) + ones).to(h_src.dtype)
             out = torch.zeros((self.num_dst,) + tuple(h_src.shape[1:]), dtype=h_src.dtype, device=h_src.device)
-            out.index_add_(0, rows.to(h_src.device), h_src[idx.clamp_min(0).to(h_src.device)] * valid.to(h_src.device))
+            out.index_add_(0, rows, h_src[idx.clamp_min(0)] * valid)
+            deg = self.indptr[1:] - self.indptr[:-1]
             return out / deg.clamp_min(1).view((-1,) + ones).to(device=h_src.device, dtype=h_src.dtype)
         valid = (self.nbr >= 0).to(h_src.device)
         idx = self.nbr.clamp_min(0).to(device=h_src.device, dtype=torch.int64)
@@ -218,11 +236,9 @@ class Block(object):
         if tuple(w.shape) != tuple(slots.shape):
             raise ValueError(f"edge weights of shape {tuple(w.shape)}: this block takes one per neighbour slot, {tuple(slots.shape)}")
         native = h_src.is_cuda and h_src.dtype == torch.float32 and h_src.dim() == 2 and w.is_cuda and w.dtype == torch.float32
-        if self.nbr is None:
-            if native and self.indptr.is_cuda and self.indices.is_cuda:
-                return _WeightedSumCSR.apply(h_src, w, self.indptr.contiguous(), self.indices.contiguous())
-        elif native and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
-            return _WeightedSum.apply(h_src, w, self.nbr)
+        index = self._native_index() if native else None
+        if index is not None:
+            return (_WeightedSumCSR if self.nbr is None else _WeightedSum).apply(h_src, w, *index)
         return self.weighted_sum_aggregate_torch(h_src, w)
 
     def weighted_sum_aggregate_torch(self, h_src, w):
@@ -232,9 +248,7 @@ class Block(object):
         ones = (1,) * (h_src.dim() - 1)
         w = w.to(device=dev, dtype=h_src.dtype)
         if self.nbr is None:
-            deg = self.indptr[1:] - self.indptr[:-1]
-            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg).to(dev)
-            idx = self.indices.to(device=dev, dtype=torch.int64)
+            rows, idx = self._slots(dev)
             valid = (idx >= 0).to(h_src.dtype)
             out = torch.zeros((self.num_dst,) + tuple(h_src.shape[1:]), dtype=h_src.dtype, device=dev)
             return out.index_add(0, rows, h_src[idx.clamp_min(0)] * (w * valid).view((-1,) + ones))
@@ -266,28 +280,20 @@ class Block(object):
         self._rel_args(etype, num_rels, w)
         native = (h_src.is_cuda and h_src.dtype == torch.float32 and h_src.dim() == 2 and etype.is_cuda
                   and (w is None or (w.is_cuda and w.dtype == torch.float32)))
-        if native:
+        index = self._native_index() if native else None
+        if index is not None:
             lo, hi = -(1 << 31), (1 << 31) - 1   # a type that int32 cannot hold is out of range either way: -1
             t32 = etype if etype.dtype == torch.int32 else torch.where((etype < lo) | (etype > hi), -1, etype).to(torch.int32)
-            if self.nbr is None:
-                if self.indptr.is_cuda and self.indices.is_cuda:
-                    return _RelSumCSR.apply(h_src, w, self.indptr.contiguous(), self.indices.contiguous(), t32.contiguous(), num_rels)
-            elif self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
-                return _RelSum.apply(h_src, w, self.nbr, t32.contiguous(), num_rels)
+            return (_RelSumCSR if self.nbr is None else _RelSum).apply(h_src, w, *index, t32.contiguous(), num_rels)
         return self.rel_sum_aggregate_torch(h_src, etype, num_rels, w)
 
     def rel_sum_aggregate_torch(self, h_src, etype, num_rels, w=None):
         """rel_sum_aggregate in plain torch, any device and dtype, both block forms, the same skip rules: its fallback, and its
         reference.  It gathers an [E, dim] intermediate and index_adds it into num_dst * num_rels rows."""
-        slots = self._rel_args(etype, num_rels, w)
+        self._rel_args(etype, num_rels, w)
         dev = h_src.device
-        src = slots.reshape(-1).to(device=dev, dtype=torch.int64)
+        rows, src = self._slots(dev)
         t = etype.reshape(-1).to(device=dev, dtype=torch.int64)
-        if self.nbr is None:
-            deg = self.indptr[1:] - self.indptr[:-1]
-            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg).to(dev)
-        else:
-            rows = torch.arange(self.num_dst, device=dev).repeat_interleave(self.nbr.shape[1])
         keep = (src >= 0) & (t >= 0) & (t < num_rels)
         msg = h_src[src[keep]]
         if w is not None:
@@ -298,14 +304,9 @@ class Block(object):
     def rel_in_degrees(self, etype, num_rels):
         """Valid in-edges of every destination node per relation: int64 [num_dst, num_rels], the c_{i,r} of the R-GCN paper; an edge
         whose type is outside [0, num_rels) is counted nowhere."""
-        slots = self._rel_args(etype, num_rels, None)
-        dev = slots.device
-        src, t = slots.reshape(-1), etype.reshape(-1).to(device=dev, dtype=torch.int64)
-        if self.nbr is None:
-            deg = self.indptr[1:] - self.indptr[:-1]
-            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg).to(dev)
-        else:
-            rows = torch.arange(self.num_dst, device=dev).repeat_interleave(self.nbr.shape[1])
+        dev = self._rel_args(etype, num_rels, None).device
+        rows, src = self._slots(dev)
+        t = etype.reshape(-1).to(device=dev, dtype=torch.int64)
         keep = (src >= 0) & (t >= 0) & (t < num_rels)
         return torch.bincount(rows[keep] * num_rels + t[keep], minlength=self.num_dst * num_rels).view(self.num_dst, num_rels)
 
@@ -314,12 +315,9 @@ class Block(object):
         GINConv 'max').  torch.max(dim)'s rule over the valid slots in slot order: ties keep the first slot, which alone receives the
         gradient; a NaN propagates; a dst node without an in-edge gets zeros (DGL's reducer).  Native kernels under the conditions of
         mean_aggregate (fp32 2-D rows on the GPU; fan-out <= 32, or the ragged form); plain torch otherwise."""
-        native = h_src.is_cuda and h_src.dtype == torch.float32 and h_src.dim() == 2
-        if self.nbr is None:
-            if native and self.indptr.is_cuda and self.indices.is_cuda:
-                return _MaxAggregateCSR.apply(h_src, self.indptr.contiguous(), self.indices.contiguous())
-        elif native and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
-            return _MaxAggregate.apply(h_src, self.nbr)
+        index = self._native_index() if h_src.is_cuda and h_src.dtype == torch.float32 and h_src.dim() == 2 else None
+        if index is not None:
+            return (_MaxAggregateCSR if self.nbr is None else _MaxAggregate).apply(h_src, *index)
         return self.max_aggregate_torch(h_src)
 
     def max_aggregate_torch(self, h_src, w=None, return_arg=False):
@@ -331,14 +329,7 @@ class Block(object):
         dev = h_src.device
         trail = tuple(h_src.shape[1:])
         ones = (1,) * len(trail)
-        if self.nbr is None:
-            deg = self.indptr[1:] - self.indptr[:-1]
-            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg).to(dev)
-            src = self.indices.to(device=dev, dtype=torch.int64)
-        else:
-            f = self.nbr.shape[1]
-            rows = torch.arange(self.num_dst, device=dev).repeat_interleave(f)
-            src = self.nbr.reshape(-1).to(device=dev, dtype=torch.int64)
+        rows, src = self._slots(dev)
         E = src.numel()
         if E == 0:
             out = torch.zeros((self.num_dst,) + trail, dtype=h_src.dtype, device=dev)
@@ -375,13 +366,7 @@ class Block(object):
 
     def _edges(self):
         """(row, local source index) of every valid edge, int64 on the block's device."""
-        if self.nbr is None:
-            deg = self.indptr[1:] - self.indptr[:-1]
-            rows = torch.repeat_interleave(torch.arange(self.num_dst, device=deg.device), deg)
-            src = self.indices.to(torch.int64)
-        else:
-            rows = torch.arange(self.num_dst, device=self.nbr.device).repeat_interleave(self.nbr.shape[1])
-            src = self.nbr.reshape(-1).to(torch.int64)
+        rows, src = self._slots()
         valid = src >= 0
         return rows[valid], src[valid]
 
@@ -404,11 +389,9 @@ class Block(object):
         all three inputs) for fp32 GPU tensors, fan-out <= 32 or the ragged form of a full layer, and H <= 16; plain torch otherwise."""
         native = (el.is_cuda and er.is_cuda and feat_src.is_cuda and all(t.dtype == torch.float32 for t in (el, er, feat_src))
                   and feat_src.dim() == 3 and feat_src.shape[1] <= 16)
-        if self.nbr is None:
-            if native and self.indptr.is_cuda and self.indices.is_cuda:
-                return _GatAggregateCSR.apply(el, er, feat_src, self.indptr.contiguous(), self.indices.contiguous(), float(negative_slope))
-        elif native and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
-            return _GatAggregate.apply(el, er, feat_src, self.nbr, float(negative_slope))
+        index = self._native_index() if native else None
+        if index is not None:
+            return (_GatAggregateCSR if self.nbr is None else _GatAggregate).apply(el, er, feat_src, *index, float(negative_slope))
         return self.gat_aggregate_torch(el, er, feat_src, negative_slope)
 
     def gat_aggregate_torch(self, el, er, feat_src, negative_slope=0.2):
@@ -440,11 +423,9 @@ class Block(object):
                              f"[{self.num_src}, H, D], [{self.num_dst}, H, D] and [H, D] or [1, H, D]")
         native = (feat_src.is_cuda and feat_dst.is_cuda and attn.is_cuda and all(t.dtype == torch.float32 for t in (feat_src, feat_dst, attn))
                   and feat_src.shape[1] <= 16)
-        if self.nbr is None:
-            if native and self.indptr.is_cuda and self.indices.is_cuda:
-                return _Gatv2AggregateCSR.apply(feat_src, feat_dst, attn, self.indptr.contiguous(), self.indices.contiguous(), float(negative_slope))
-        elif native and self.nbr.is_cuda and self.nbr.is_contiguous() and self.nbr.shape[1] <= 32:
-            return _Gatv2Aggregate.apply(feat_src, feat_dst, attn, self.nbr, float(negative_slope))
+        index = self._native_index() if native else None
+        if index is not None:
+            return (_Gatv2AggregateCSR if self.nbr is None else _Gatv2Aggregate).apply(feat_src, feat_dst, attn, *index, float(negative_slope))
         return self.gatv2_aggregate_torch(feat_src, feat_dst, attn, negative_slope)
 
     def gatv2_aggregate_torch(self, feat_src, feat_dst, attn, negative_slope=0.2):

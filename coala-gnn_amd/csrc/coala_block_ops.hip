@@ -1,9 +1,15 @@
 // coala_block_ops.hip -- what a model computes on a sampled block (coala_sampler.hip makes the blocks), for gfx950: mean aggregation
 // (DGL's SAGEConv "mean"), weighted sum aggregation (DGL's u_mul_e_sum: GraphConv / SAGEConv with edge_weight=), max aggregation
-// (DGL's fn.max: SAGEConv "pool", GINConv "max"), the relation-typed sum (RelGraphConv's message step) and GAT / GATv2 attention aggregation
-// (GATConv's and GATv2Conv's message steps), forward and backward, on
-// fixed blocks (nbr_local[n_dst, fanout], -1 = no neighbour) and on the CSR blocks of full layers.  Stateless entry points: no
-// handle, every launch on the caller's stream.
+// (DGL's fn.max: SAGEConv "pool", GINConv "max"), the relation-typed sum (RelGraphConv's message step) and GAT / GATv2 attention
+// aggregation (GATConv's and GATv2Conv's message steps), forward and backward, on fixed blocks (nbr_local[n_dst, fanout], -1 = no
+// neighbour) and on the CSR blocks of full layers.  Stateless entry points: no handle, every launch on the caller's stream.
+//
+// Layout of the file: the device helpers every kernel walks a row with (which rows a wave takes, a row's bounds in either block form,
+// the 64-index chunk load, the wave reductions); then one `template <bool CSR>` kernel per op and direction, each written out top to
+// bottom on those helpers; then one `*_launch<CSR>` per kernel (shape check, n_dst == 0, null check, launch); then the C entry
+// points, which only forward.  The fixed and the CSR instantiation of a kernel are the same code on the same lanes -- a fixed row of
+// fan-out <= 32 is a row of one chunk -- so a row both forms can express gives the same bits in both.  A hub row is aggregated by one
+// wave (splitting it is not done).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -17,122 +23,30 @@
 
 namespace {
 
-// The one dense-side primitive a consumer of these blocks needs (DGL's SAGEConv "mean" reduces to it): out[d] = mean of the rows
-// h_src[nbr[d, j]] over the valid j.  One wave per destination row, 16-B accesses, the neighbour indices read once per wave.
-// Replaces gather -> mask -> sum -> divide in eager torch (four passes over a [n_dst, fanout, dim] intermediate).
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void mean_aggregate_kernel(const int32_t* __restrict__ nbr, const float* __restrict__ h_src,
-                                                                float* __restrict__ out, int64_t n_dst, int fanout, int dim) {
-    typedef float vf __attribute__((ext_vector_type(VEC)));
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int units = dim / VEC;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        const int32_t mine = lane < fanout ? nbr[d * fanout + lane] : -1; // fan-out <= 32: one load per wave
-        const int cnt = __builtin_popcountll(__ballot(mine >= 0));
-        const float inv = cnt ? 1.0f / (float)cnt : 0.0f;
-        for (int u0 = 0; u0 < units; u0 += 64) {
-            const int u = u0 + lane;
-            vf acc = vf(0.0f);
-            for (int j = 0; j < fanout; ++j) {
-                const int32_t idx = __shfl(mine, j);
-                if (idx >= 0 && u < units) acc += *reinterpret_cast<const vf*>(h_src + (int64_t)idx * dim + (int64_t)u * VEC);
-            }
-            if (u < units) *reinterpret_cast<vf*>(out + d * dim + (int64_t)u * VEC) = acc * inv;
-        }
-    }
+// One wave per destination row: this thread's lane, its wave's first row and the stride to the wave's next row, for a grid of blocks
+// of `waves` waves -- `const auto [lane, wave, n_waves] = wave_rows(); for (int64_t d = wave; d < n_dst; d += n_waves)`.
+struct WaveRows {
+    int lane;
+    int64_t wave, n_waves;
+};
+
+__device__ __forceinline__ WaveRows wave_rows(int waves = kWavesPerBlock) {
+    return {(int)(threadIdx.x & 63), (int64_t)blockIdx.x * waves + (threadIdx.x >> 6), (int64_t)gridDim.x * waves};
 }
 
-// grad_src[nbr[d, j]] += grad_out[d] / cnt[d]   (grad_src zeroed by the caller; hardware float atomics: summation order varies)
-__global__ __launch_bounds__(kBlock) void mean_aggregate_backward_kernel(const int32_t* __restrict__ nbr, const float* __restrict__ grad_out,
-                                                                         float* __restrict__ grad_src, int64_t n_dst, int fanout, int dim) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        const int32_t mine = lane < fanout ? nbr[d * fanout + lane] : -1;
-        const int cnt = __builtin_popcountll(__ballot(mine >= 0));
-        if (!cnt) continue;
-        const float inv = 1.0f / (float)cnt;
-        for (int c0 = 0; c0 < dim; c0 += 64) { // wave-uniform trip count: the shuffles below read lanes that are past `dim`
-            const int c = c0 + lane;
-            const float g = c < dim ? grad_out[d * dim + c] * inv : 0.0f;
-            for (int j = 0; j < fanout; ++j) {
-                const int32_t idx = __shfl(mine, j);
-                if (idx >= 0 && c < dim) unsafeAtomicAdd(grad_src + (int64_t)idx * dim + c, g);
-            }
-        }
-    }
+// Row d's indices: idx[beg .. end), nbr[d * fanout ..] for the fixed form, indices[indptr[d] .. indptr[d+1]) for the CSR form.
+template <bool CSR>
+__device__ __forceinline__ void row_range(const int64_t* indptr, int fanout, int64_t d, int64_t* beg, int64_t* end) {
+    *beg = CSR ? indptr[d] : d * fanout;
+    *end = CSR ? indptr[d + 1] : *beg + fanout;
 }
 
-// The same op on a ragged (CSR) block, the form of a full layer: row d is idx[indptr[d] .. indptr[d+1]).  One wave per row as in
-// the dense kernels; the row's indices are read 64 at a time and broadcast by shuffle, and the sum runs in CSC order, so a row both
-// forms can express gives the dense kernel's bits.  A hub row is aggregated by one wave (splitting it is not done).
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void mean_aggregate_csr_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
-                                                                    const float* __restrict__ h_src, float* __restrict__ out, int64_t n_dst, int dim) {
-    typedef float vf __attribute__((ext_vector_type(VEC)));
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int units = dim / VEC;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        const int64_t beg = indptr[d], end = indptr[d + 1];
-        const float inv = end > beg ? 1.0f / (float)(end - beg) : 0.0f;
-        for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
-            const int u = u0 + lane;
-            vf acc = vf(0.0f);
-            for (int64_t e0 = beg; e0 < end; e0 += 64) {
-                const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
-                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
-                for (int j = 0; j < n; ++j) {
-                    const int32_t s = __shfl(mine, j);
-                    if (s >= 0 && u < units) acc += *reinterpret_cast<const vf*>(h_src + (int64_t)s * dim + (int64_t)u * VEC);
-                }
-            }
-            if (u < units) *reinterpret_cast<vf*>(out + d * dim + (int64_t)u * VEC) = acc * inv;
-        }
-    }
+// The chunk of a row at e0: lane j takes idx[e0 + j] into *mine, -1 past the row's end; -> the chunk's length, min(64, end - e0).
+// The indices then go round by __shfl(mine, j), j < n, which every lane of the wave must execute.
+__device__ __forceinline__ int load_chunk(const int32_t* idx, int64_t e0, int64_t end, int lane, int32_t* mine) {
+    *mine = e0 + lane < end ? idx[e0 + lane] : -1;
+    return end - e0 < 64 ? (int)(end - e0) : 64;
 }
-
-// grad_src[idx[e]] += grad_out[d] / deg(d) for the edges e of row d (grad_src zeroed by the caller; hardware float atomics)
-__global__ __launch_bounds__(kBlock) void mean_aggregate_csr_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
-                                                                             const float* __restrict__ grad_out, float* __restrict__ grad_src,
-                                                                             int64_t n_dst, int dim) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        const int64_t beg = indptr[d], end = indptr[d + 1];
-        if (end <= beg) continue;
-        const float inv = 1.0f / (float)(end - beg);
-        for (int c0 = 0; c0 < dim; c0 += 64) { // wave-uniform trip count: the shuffles below read lanes that are past `dim`
-            const int c = c0 + lane;
-            const float g = c < dim ? grad_out[d * dim + c] * inv : 0.0f;
-            for (int64_t e0 = beg; e0 < end; e0 += 64) {
-                const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
-                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
-                for (int j = 0; j < n; ++j) {
-                    const int32_t s = __shfl(mine, j);
-                    if (s >= 0 && c < dim) unsafeAtomicAdd(grad_src + (int64_t)s * dim + c, g);
-                }
-            }
-        }
-    }
-}
-
-// GAT attention on a block (DGL GATConv's message step; its projections fc_src / fc_dst and the attn_l / attn_r products are dense
-// and stay in torch).  For dst d, head h and the valid in-edges j of d (source s_j):
-//   z_j = el[s_j, h] + er[d, h],  e_j = leaky_relu(z_j, slope),  a_j = softmax of e over the row,  out[d, h, :] = sum_j a_j feat[s_j, h, :]
-// One wave per destination row, in both block forms: the row's indices are read 64 at a time (a fixed row of fan-out <= 32 is one
-// chunk) and broadcast by shuffle.  Per chunk a lane per edge computes its edge's score for every head once, into LDS; the feature
-// lanes then sum the rows with those weights, never writing a [n_dst, fanout, H, D] intermediate.  The softmax runs online over the
-// chunks: running max m and sum l per head; the partial sum is rescaled by exp(m_old - m_new) when the max grows, and it waits in
-// `out`, unnormalised, between the chunks of a row of more than 64 edges.  The fixed and the CSR kernels are the same code on the
-// same lanes, so a fixed row whose valid entries come first, in CSC order, gives the bits of its CSR row.
-constexpr int kGatMaxHeads = 16;
-constexpr float kNegInf = -__builtin_inff();
 
 __device__ __forceinline__ void wave_lds_sync() { // LDS written by some lanes of a wave, read by others (rocPRIM's wave_barrier)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -150,6 +64,90 @@ __device__ __forceinline__ float wave_sum(float v) { // butterfly: every lane en
     return v;
 }
 
+template <int VEC, typename V>
+__device__ __forceinline__ void axpy(V& acc, float a, const V& x) { // one fma per term
+    for (int i = 0; i < VEC; ++i) acc[i] = __builtin_fmaf(a, x[i], acc[i]);
+}
+
+// Mean aggregation, the one dense-side primitive a consumer of these blocks needs (DGL's SAGEConv "mean" reduces to it): out[d] = the
+// mean of the rows h_src[s_j] over the valid slots j of row d.  One wave per destination row, 16-B accesses, the row's indices read
+// 64 at a time and broadcast by shuffle; the sum starts from +0 and runs in slot order, so a row both forms can express gives the
+// same bits.  The first chunk stays in registers over the passes of a long feature row: a fixed row is that chunk alone, read once.
+// The two forms divide differently: the fixed form by the number of valid entries, the CSR form by the row's length (the rule of
+// Block.mean_aggregate_torch; a sampled CSR row holds no -1).  Replaces gather -> mask -> sum -> divide in eager torch (four passes
+// over a [n_dst, fanout, dim] intermediate).
+template <int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void mean_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
+                                                                const float* __restrict__ h_src, float* __restrict__ out, int64_t n_dst, int dim) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    const auto [lane, wave, n_waves] = wave_rows();
+    const int units = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        int32_t mine0;
+        const int n0 = load_chunk(idx, beg, end, lane, &mine0);
+        const float cnt = CSR ? (float)(end - beg) : (float)__builtin_popcountll(__ballot(mine0 >= 0));
+        const float inv = cnt > 0.0f ? 1.0f / cnt : 0.0f;
+        for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+            const int u = u0 + lane;
+            vf acc = vf(0.0f);
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                int32_t mine = mine0;
+                int n = n0;
+                if (e0 != beg) n = load_chunk(idx, e0, end, lane, &mine); // wave-uniform
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && u < units) acc += *reinterpret_cast<const vf*>(h_src + (int64_t)s * dim + (int64_t)u * VEC);
+                }
+            }
+            if (u < units) *reinterpret_cast<vf*>(out + d * dim + (int64_t)u * VEC) = acc * inv;
+        }
+    }
+}
+
+// grad_src[s_j] += grad_out[d] / cnt(d) for the valid slots j of row d, cnt the forward's divisor (grad_src zeroed by the caller;
+// hardware float atomics: summation order varies).  A lane per float: an atomic instruction of the wave covers 256 contiguous bytes.
+template <bool CSR>
+__global__ __launch_bounds__(kBlock) void mean_aggregate_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                         int fanout, const float* __restrict__ grad_out,
+                                                                         float* __restrict__ grad_src, int64_t n_dst, int dim) {
+    const auto [lane, wave, n_waves] = wave_rows();
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        int32_t mine0;
+        const int n0 = load_chunk(idx, beg, end, lane, &mine0);
+        const float cnt = CSR ? (float)(end - beg) : (float)__builtin_popcountll(__ballot(mine0 >= 0));
+        if (!(cnt > 0.0f)) continue;
+        const float inv = 1.0f / cnt;
+        for (int c0 = 0; c0 < dim; c0 += 64) { // wave-uniform trip count: the shuffles below read lanes that are past `dim`
+            const int c = c0 + lane;
+            const float g = c < dim ? grad_out[d * dim + c] * inv : 0.0f;
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                int32_t mine = mine0;
+                int n = n0;
+                if (e0 != beg) n = load_chunk(idx, e0, end, lane, &mine); // wave-uniform
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && c < dim) unsafeAtomicAdd(grad_src + (int64_t)s * dim + c, g);
+                }
+            }
+        }
+    }
+}
+
+// GAT attention on a block (DGL GATConv's message step; its projections fc_src / fc_dst and the attn_l / attn_r products are dense
+// and stay in torch).  For dst d, head h and the valid in-edges j of d (source s_j):
+//   z_j = el[s_j, h] + er[d, h],  e_j = leaky_relu(z_j, slope),  a_j = softmax of e over the row,  out[d, h, :] = sum_j a_j feat[s_j, h, :]
+// One wave per destination row, in both block forms.  Per chunk a lane per edge computes its edge's score for every head once, into
+// LDS; the feature lanes then sum the rows with those weights, never writing a [n_dst, fanout, H, D] intermediate.  The softmax runs
+// online over the chunks: running max m and sum l per head; the partial sum is rescaled by exp(m_old - m_new) when the max grows, and
+// it waits in `out`, unnormalised, between the chunks of a row of more than 64 edges.  GATv2 below differs only in how a chunk's
+// scores come about, so the softmax step, the weighted sum and the two ends of a row are the functions that follow, for both.
+constexpr int kGatMaxHeads = 16;
+constexpr float kNegInf = -__builtin_inff();
+
 // acc[h] += the sum of x over the lanes of head h, for the 64 floats c0 + lane of a [H * dim] row (a head's floats are contiguous):
 // a segmented inclusive scan, then the last lane of each head's segment adds its total.  Every lane must call it.
 __device__ __forceinline__ void head_segment_add(float* acc, float x, int lane, int c0, int dim, int hd) {
@@ -163,11 +161,81 @@ __device__ __forceinline__ void head_segment_add(float* acc, float x, int lane, 
     if (c < hd && (lane == 63 || c + 1 == hd || (c + 1) % dim == 0)) acc[h] += x;
 }
 
-// Row d's indices: idx[beg .. end), nbr[d * fanout ..] for the fixed form, indices[indptr[d] .. indptr[d+1]) for the CSR form.
-template <bool CSR>
-__device__ __forceinline__ void gat_row(const int64_t* indptr, int fanout, int64_t d, int64_t* beg, int64_t* end) {
-    *beg = CSR ? indptr[d] : d * fanout;
-    *end = CSR ? indptr[d + 1] : *beg + fanout;
+// A wave's LDS in the attention forward kernels.
+struct SoftmaxLds {
+    float* w;     // [64][kGatMaxHeads], [edge][head]: exp(e_j - m) of the chunk
+    float* m_run; // per head: the running max,
+    float* l_run; // the running sum,
+    float* scl;   // and the chunk's rescale factor
+};
+
+__device__ __forceinline__ SoftmaxLds softmax_lds(float* w, float* st) { return {w, st, st + kGatMaxHeads, st + 2 * kGatMaxHeads}; }
+
+__device__ __forceinline__ void softmax_row_begin(const SoftmaxLds& s, int lane, int heads) {
+    wave_lds_sync(); // the previous row has read m_run / l_run
+    if (lane < heads) {
+        s.m_run[lane] = kNegInf;
+        s.l_run[lane] = 0.0f;
+    }
+}
+
+// One head's step of the online softmax over a chunk: lane j brings edge j's score e (-inf and !valid: no edge in this lane) and
+// leaves p_j = exp(e_j - m) in w; lane 0 updates the head's running max and sum and stores the factor that rescales the earlier
+// chunks' sum.  Every lane must call it.
+__device__ __forceinline__ void softmax_chunk_step(const SoftmaxLds& s, int h, float e, bool valid, int lane) {
+    const float mo = s.m_run[h];
+    const float mn = fmaxf(mo, wave_max(e));
+    const float p = valid ? expf(e - mn) : 0.0f;
+    const float sum = wave_sum(p);
+    const float sc = mo == mn ? 1.0f : (mo == kNegInf ? 0.0f : expf(mo - mn));
+    s.w[lane * kGatMaxHeads + h] = p;
+    if (lane == 0) {
+        s.m_run[h] = mn;
+        s.l_run[h] = s.l_run[h] * sc + sum;
+        s.scl[h] = sc;
+    }
+}
+
+// out_row[h, :] = (first chunk ? 0 : out_row[h, :] * scl[h]) + sum over the chunk's valid edges j of w[j][h] * feat[s_j, h, :], divided
+// by the row's sum on the last chunk.  A lane per VEC floats of the [H * dim] row.
+template <int VEC>
+__device__ __forceinline__ void softmax_accumulate(const SoftmaxLds& s, float* out_row, const float* __restrict__ feat, int32_t mine, int n,
+                                                   bool first, bool last, int lane, int hd, int units, int upl) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+        const int u = u0 + lane;
+        const int hu = u < units ? u / upl : 0;
+        float* o = out_row + (int64_t)u * VEC;
+        vf acc = vf(0.0f);
+        if (!first && u < units) acc = *reinterpret_cast<const vf*>(o) * s.scl[hu];
+        for (int j = 0; j < n; ++j) {
+            const int32_t src = __shfl(mine, j);
+            if (src >= 0 && u < units) acc += s.w[j * kGatMaxHeads + hu] * *reinterpret_cast<const vf*>(feat + (int64_t)src * hd + (int64_t)u * VEC);
+        }
+        if (u < units) {
+            if (last) acc *= s.l_run[hu] > 0.0f ? 1.0f / s.l_run[hu] : 0.0f;
+            *reinterpret_cast<vf*>(o) = acc;
+        }
+    }
+}
+
+// A row's end: zeros when no chunk ran (an empty CSR row), and the log-sum-exp per head, which is all the backward keeps.
+template <int VEC>
+__device__ __forceinline__ void softmax_row_end(const SoftmaxLds& s, float* out_row, float* lse_row, bool empty, int lane, int heads, int units) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    if (empty)
+        for (int u = lane; u < units; u += 64) *reinterpret_cast<vf*>(out_row + (int64_t)u * VEC) = vf(0.0f);
+    wave_lds_sync();
+    if (lane < heads) lse_row[lane] = s.l_run[lane] > 0.0f ? s.m_run[lane] + logf(s.l_run[lane]) : kNegInf;
+}
+
+// gout[h] += <g[h, :], o[h, :]> for the heads of one [H * dim] row, in head_segment_add's fixed order (the backward kernels' pre-pass
+// over grad_out[d] and out[d]).  Every lane must call it.
+__device__ __forceinline__ void head_dots(float* gout, const float* __restrict__ g, const float* __restrict__ o, int lane, int dim, int hd) {
+    for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count
+        const int c = c0 + lane;
+        head_segment_add(gout, c < hd ? g[c] * o[c] : 0.0f, lane, c0, dim, hd);
+    }
 }
 
 template <int VEC, bool CSR>
@@ -175,69 +243,31 @@ __global__ __launch_bounds__(kBlock) void gat_aggregate_kernel(const int64_t* __
                                                                const float* __restrict__ el, const float* __restrict__ er,
                                                                const float* __restrict__ feat, float* __restrict__ out, float* __restrict__ lse,
                                                                int64_t n_dst, int heads, int dim, float slope) {
-    typedef float vf __attribute__((ext_vector_type(VEC)));
-    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];  // exp(e_j - m) of the chunk, [edge][head]
-    __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];  // per head: running max, running sum, the chunk's rescale factor
-    const int lane = threadIdx.x & 63;
-    float* w = w_lds[threadIdx.x >> 6];
-    float* m_run = st_lds[threadIdx.x >> 6];
-    float* l_run = m_run + kGatMaxHeads;
-    float* scl = l_run + kGatMaxHeads;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];
+    __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];
+    const auto [lane, wave, n_waves] = wave_rows();
+    const SoftmaxLds s = softmax_lds(w_lds[threadIdx.x >> 6], st_lds[threadIdx.x >> 6]);
     const int hd = heads * dim, units = hd / VEC, upl = dim / VEC;
     for (int64_t d = wave; d < n_dst; d += n_waves) {
         int64_t beg, end;
-        gat_row<CSR>(indptr, fanout, d, &beg, &end);
-        wave_lds_sync(); // the previous row has read m_run / l_run
-        if (lane < heads) {
-            m_run[lane] = kNegInf;
-            l_run[lane] = 0.0f;
-        }
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        softmax_row_begin(s, lane, heads);
         for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
-            const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
-            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
             wave_lds_sync(); // the previous chunk has read w and scl; m_run / l_run are set
-            for (int h = 0; h < heads; ++h) {
+            for (int h = 0; h < heads; ++h) { // the score is a scalar per edge and head: straight into the softmax step
                 float e = kNegInf;
                 if (mine >= 0) {
                     const float z = el[(int64_t)mine * heads + h] + er[d * heads + h];
                     e = z > 0.0f ? z : z * slope;
                 }
-                const float mo = m_run[h];
-                const float mn = fmaxf(mo, wave_max(e));
-                const float p = mine >= 0 ? expf(e - mn) : 0.0f;
-                const float sum = wave_sum(p);
-                const float sc = mo == mn ? 1.0f : (mo == kNegInf ? 0.0f : expf(mo - mn));
-                w[lane * kGatMaxHeads + h] = p;
-                if (lane == 0) {
-                    m_run[h] = mn;
-                    l_run[h] = l_run[h] * sc + sum;
-                    scl[h] = sc;
-                }
+                softmax_chunk_step(s, h, e, mine >= 0, lane);
             }
             wave_lds_sync();
-            const bool first = e0 == beg, last = e0 + 64 >= end;
-            for (int u0 = 0; u0 < units; u0 += 64) {
-                const int u = u0 + lane;
-                const int hu = u < units ? u / upl : 0;
-                float* o = out + d * hd + (int64_t)u * VEC;
-                vf acc = vf(0.0f);
-                if (!first && u < units) acc = *reinterpret_cast<const vf*>(o) * scl[hu];
-                for (int j = 0; j < n; ++j) {
-                    const int32_t s = __shfl(mine, j);
-                    if (s >= 0 && u < units) acc += w[j * kGatMaxHeads + hu] * *reinterpret_cast<const vf*>(feat + (int64_t)s * hd + (int64_t)u * VEC);
-                }
-                if (u < units) {
-                    if (last) acc *= l_run[hu] > 0.0f ? 1.0f / l_run[hu] : 0.0f;
-                    *reinterpret_cast<vf*>(o) = acc;
-                }
-            }
+            softmax_accumulate<VEC>(s, out + d * hd, feat, mine, n, e0 == beg, e0 + 64 >= end, lane, hd, units, upl);
         }
-        if (beg == end) // no chunk ran: an empty CSR row
-            for (int u = lane; u < units; u += 64) *reinterpret_cast<vf*>(out + d * hd + (int64_t)u * VEC) = vf(0.0f);
-        wave_lds_sync();
-        if (lane < heads) lse[d * heads + lane] = l_run[lane] > 0.0f ? m_run[lane] + logf(l_run[lane]) : kNegInf;
+        softmax_row_end<VEC>(s, out + d * hd, lse + d * heads, beg == end, lane, heads, units);
     }
 }
 
@@ -256,17 +286,15 @@ __global__ __launch_bounds__(kBlock) void gat_aggregate_backward_kernel(const in
     __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // a_j of the chunk, [edge][head]
     __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g, feat_j>, [edge][head]
     __shared__ float hs_lds[kWavesPerBlock][2 * kGatMaxHeads];   // per head: <g, out>, the sum of t_j so far
-    const int lane = threadIdx.x & 63;
+    const auto [lane, wave, n_waves] = wave_rows();
     float* w = w_lds[threadIdx.x >> 6];
     float* dot = dot_lds[threadIdx.x >> 6];
     float* gout = hs_lds[threadIdx.x >> 6];
     float* ter = gout + kGatMaxHeads;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
     const int hd = heads * dim;
     for (int64_t d = wave; d < n_dst; d += n_waves) {
         int64_t beg, end;
-        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
         const float* g = grad_out + d * hd;
         wave_lds_sync(); // the previous row has read gout / ter
         if (lane < heads) {
@@ -274,13 +302,10 @@ __global__ __launch_bounds__(kBlock) void gat_aggregate_backward_kernel(const in
             ter[lane] = 0.0f;
         }
         wave_lds_sync();
-        for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count
-            const int c = c0 + lane;
-            head_segment_add(gout, c < hd ? g[c] * out[d * hd + c] : 0.0f, lane, c0, dim, hd);
-        }
+        head_dots(gout, g, out + d * hd, lane, dim, hd);
         for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
-            const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
-            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
             wave_lds_sync(); // the previous chunk has read w and dot
             for (int h = 0; h < heads; ++h) {
                 float a = 0.0f;
@@ -333,7 +358,7 @@ __global__ __launch_bounds__(kBlock) void gat_aggregate_backward_kernel(const in
 // float of the row, 64 floats at a time, attn and feat_dst[d] of the pass in registers, the chunk's edges in the inner loop, and the
 // per-head sums added into the LDS [edge][head] array by head_segment_add in a fixed order.  The weighted sum then reads the chunk's
 // source rows a second time (at most 64 rows: from the cache), so the HBM bytes are GAT's plus feat_dst, and nothing of size E is
-// written.  The fixed and the CSR kernels are the same code on the same lanes.
+// written.
 // e[j * kGatMaxHeads + h] += edge j's score of head h, for the n edges of a chunk; with DOT also dot[..] += <g[h, :], feat_src[s_j, h, :]>.
 template <bool DOT>
 __device__ __forceinline__ void gatv2_score_pass(float* e, float* dot, int32_t mine, int n, const float* __restrict__ feat_src,
@@ -361,70 +386,29 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_kernel(const int64_t* 
                                                                  const float* __restrict__ feat_src, const float* __restrict__ feat_dst,
                                                                  const float* __restrict__ attn, float* __restrict__ out,
                                                                  float* __restrict__ lse, int64_t n_dst, int heads, int dim, float slope) {
-    typedef float vf __attribute__((ext_vector_type(VEC)));
-    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];  // the chunk's scores e_j, then exp(e_j - m), [edge][head]
-    __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];  // per head: running max, running sum, the chunk's rescale factor
-    const int lane = threadIdx.x & 63;
-    float* w = w_lds[threadIdx.x >> 6];
-    float* m_run = st_lds[threadIdx.x >> 6];
-    float* l_run = m_run + kGatMaxHeads;
-    float* scl = l_run + kGatMaxHeads;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads]; // the chunk's scores e_j first, [edge][head]
+    __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];
+    const auto [lane, wave, n_waves] = wave_rows();
+    const SoftmaxLds s = softmax_lds(w_lds[threadIdx.x >> 6], st_lds[threadIdx.x >> 6]);
     const int hd = heads * dim, units = hd / VEC, upl = dim / VEC;
     for (int64_t d = wave; d < n_dst; d += n_waves) {
         int64_t beg, end;
-        gat_row<CSR>(indptr, fanout, d, &beg, &end);
-        wave_lds_sync(); // the previous row has read m_run / l_run
-        if (lane < heads) {
-            m_run[lane] = kNegInf;
-            l_run[lane] = 0.0f;
-        }
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        softmax_row_begin(s, lane, heads);
         for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
-            const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
-            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
             wave_lds_sync(); // the previous chunk has read w and scl; m_run / l_run are set
-            for (int h = 0; h < heads; ++h) w[lane * kGatMaxHeads + h] = 0.0f;
+            for (int h = 0; h < heads; ++h) s.w[lane * kGatMaxHeads + h] = 0.0f;
             wave_lds_sync();
-            gatv2_score_pass<false>(w, nullptr, mine, n, feat_src, feat_dst + d * hd, attn, nullptr, lane, hd, dim, slope);
+            gatv2_score_pass<false>(s.w, nullptr, mine, n, feat_src, feat_dst + d * hd, attn, nullptr, lane, hd, dim, slope);
             wave_lds_sync();
-            for (int h = 0; h < heads; ++h) { // lane j reads and rewrites only edge j's words
-                const float e = mine >= 0 ? w[lane * kGatMaxHeads + h] : kNegInf;
-                const float mo = m_run[h];
-                const float mn = fmaxf(mo, wave_max(e));
-                const float p = mine >= 0 ? expf(e - mn) : 0.0f;
-                const float sum = wave_sum(p);
-                const float sc = mo == mn ? 1.0f : (mo == kNegInf ? 0.0f : expf(mo - mn));
-                w[lane * kGatMaxHeads + h] = p;
-                if (lane == 0) {
-                    m_run[h] = mn;
-                    l_run[h] = l_run[h] * sc + sum;
-                    scl[h] = sc;
-                }
-            }
+            for (int h = 0; h < heads; ++h) // lane j reads and rewrites only edge j's words
+                softmax_chunk_step(s, h, mine >= 0 ? s.w[lane * kGatMaxHeads + h] : kNegInf, mine >= 0, lane);
             wave_lds_sync();
-            const bool first = e0 == beg, last = e0 + 64 >= end;
-            for (int u0 = 0; u0 < units; u0 += 64) {
-                const int u = u0 + lane;
-                const int hu = u < units ? u / upl : 0;
-                float* o = out + d * hd + (int64_t)u * VEC;
-                vf acc = vf(0.0f);
-                if (!first && u < units) acc = *reinterpret_cast<const vf*>(o) * scl[hu];
-                for (int j = 0; j < n; ++j) {
-                    const int32_t s = __shfl(mine, j);
-                    if (s >= 0 && u < units)
-                        acc += w[j * kGatMaxHeads + hu] * *reinterpret_cast<const vf*>(feat_src + (int64_t)s * hd + (int64_t)u * VEC);
-                }
-                if (u < units) {
-                    if (last) acc *= l_run[hu] > 0.0f ? 1.0f / l_run[hu] : 0.0f;
-                    *reinterpret_cast<vf*>(o) = acc;
-                }
-            }
+            softmax_accumulate<VEC>(s, out + d * hd, feat_src, mine, n, e0 == beg, e0 + 64 >= end, lane, hd, units, upl);
         }
-        if (beg == end) // no chunk ran: an empty CSR row
-            for (int u = lane; u < units; u += 64) *reinterpret_cast<vf*>(out + d * hd + (int64_t)u * VEC) = vf(0.0f);
-        wave_lds_sync();
-        if (lane < heads) lse[d * heads + lane] = l_run[lane] > 0.0f ? m_run[lane] + logf(l_run[lane]) : kNegInf;
+        softmax_row_end<VEC>(s, out + d * hd, lse + d * heads, beg == end, lane, heads, units);
     }
 }
 
@@ -453,33 +437,30 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_backward_kernel(const 
     __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g, feat_src_j>, then t_j, [edge][head]
     __shared__ float hs_lds[kWavesPerBlock][kGatMaxHeads];       // per head: <g, out>
     static_assert(RP * 64 <= 64 * kGatMaxHeads, "the waves' grad_attn sums are combined through w_lds");
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+    const int wv = threadIdx.x >> 6, wpb = blockDim.x >> 6; // one wave a block at RP == 0
+    const WaveRows wr = wave_rows(wpb);
+    const int lane = wr.lane; // a lambda below captures it
     float* w = w_lds[wv];
     float* dot = dot_lds[wv];
     float* gout = hs_lds[wv];
-    const int64_t wave = (int64_t)blockIdx.x * wpb + wv;
-    const int64_t n_waves = (int64_t)gridDim.x * wpb;
     const int hd = heads * dim;
     float* prow = grad_attn_parts ? grad_attn_parts + (int64_t)blockIdx.x * hd : nullptr;
     float ga_reg[RP > 0 ? RP : 1];
     for (int p = 0; p < (RP > 0 ? RP : 1); ++p) ga_reg[p] = 0.0f;
     if (RP == 0 && prow)
         for (int c = lane; c < hd; c += 64) prow[c] = 0.0f;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
+    for (int64_t d = wr.wave; d < n_dst; d += wr.n_waves) {
         int64_t beg, end;
-        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
         const float* g = grad_out + d * hd;
         const float* fd = feat_dst + d * hd;
         wave_lds_sync(); // the previous row has read gout
         if (lane < heads) gout[lane] = 0.0f;
         wave_lds_sync();
-        for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count
-            const int c = c0 + lane;
-            head_segment_add(gout, c < hd ? g[c] * out[d * hd + c] : 0.0f, lane, c0, dim, hd);
-        }
+        head_dots(gout, g, out + d * hd, lane, dim, hd);
         for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
-            const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
-            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
             const bool first = e0 == beg;
             wave_lds_sync(); // the previous chunk has read w and dot
             for (int h = 0; h < heads; ++h) {
@@ -556,31 +537,23 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_backward_kernel(const 
 // of fan-out <= 32 is one chunk) and broadcast by shuffle; the sum runs in slot order with one fma per term.  A byte mover like the
 // mean: per row it reads deg * (dim * 4 + 8) bytes and writes dim * 4.  The fixed and the CSR kernels are the same code on the same
 // lanes, so a row both forms can express gives the same bits.
-template <int VEC, typename V>
-__device__ __forceinline__ void axpy(V& acc, float a, const V& x) {
-    for (int i = 0; i < VEC; ++i) acc[i] = __builtin_fmaf(a, x[i], acc[i]);
-}
-
 template <int VEC, bool CSR>
 __global__ __launch_bounds__(kBlock) void weighted_sum_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
                                                               const float* __restrict__ w, int fanout, const float* __restrict__ h_src,
                                                               float* __restrict__ out, int64_t n_dst, int dim) {
     typedef float vf __attribute__((ext_vector_type(VEC)));
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const auto [lane, wave, n_waves] = wave_rows();
     const int units = dim / VEC;
     for (int64_t d = wave; d < n_dst; d += n_waves) {
         int64_t beg, end;
-        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
         for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
             const int u = u0 + lane;
             vf acc = vf(0.0f);
             for (int64_t e0 = beg; e0 < end; e0 += 64) {
-                const bool have = e0 + lane < end;
-                const int32_t mine = have ? idx[e0 + lane] : -1;
-                const float wm = have ? w[e0 + lane] : 0.0f;
-                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+                int32_t mine;
+                const int n = load_chunk(idx, e0, end, lane, &mine);
+                const float wm = e0 + lane < end ? w[e0 + lane] : 0.0f;
                 for (int j = 0; j < n; ++j) {
                     const int32_t s = __shfl(mine, j);
                     const float wj = __shfl(wm, j);
@@ -607,20 +580,18 @@ __global__ __launch_bounds__(kBlock) void weighted_sum_backward_kernel(const int
                                                                        const float* __restrict__ grad_out, float* __restrict__ grad_src,
                                                                        float* __restrict__ grad_w, int64_t n_dst, int dim) {
     typedef float vf __attribute__((ext_vector_type(VEC)));
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const auto [lane, wave, n_waves] = wave_rows();
     const int units = dim / VEC;
     for (int64_t d = wave; d < n_dst; d += n_waves) {
         int64_t beg, end;
-        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
         const float* g = grad_out + d * dim;
         const vf g0 = lane < units ? *reinterpret_cast<const vf*>(g + (int64_t)lane * VEC) : vf(0.0f);
         for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
             const bool have = e0 + lane < end;
-            const int32_t mine = have ? idx[e0 + lane] : -1;
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
             const float wm = have ? w[e0 + lane] : 0.0f;
-            const int n = end - e0 < 64 ? (int)(end - e0) : 64;
             float gw = 0.0f;
             for (int j = 0; j < n; ++j) {
                 const int32_t s = __shfl(mine, j);
@@ -665,21 +636,19 @@ __global__ __launch_bounds__(kBlock) void max_aggregate_kernel(const int64_t* __
                                                                int32_t* __restrict__ arg, int64_t n_dst, int dim) {
     typedef float vf __attribute__((ext_vector_type(VEC)));
     typedef int32_t vi __attribute__((ext_vector_type(VEC)));
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const auto [lane, wave, n_waves] = wave_rows();
     const int units = dim / VEC;
     for (int64_t d = wave; d < n_dst; d += n_waves) {
         int64_t beg, end;
-        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
         for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
             const int u = u0 + lane;
             vf best = vf(0.0f);
             vi at = vi(-1);
             bool any = false; // wave-uniform: a valid slot has been seen
             for (int64_t e0 = beg; e0 < end; e0 += 64) {
-                const int32_t mine = e0 + lane < end ? idx[e0 + lane] : -1;
-                const int n = end - e0 < 64 ? (int)(end - e0) : 64;
+                int32_t mine;
+                const int n = load_chunk(idx, e0, end, lane, &mine);
                 for (int j = 0; j < n; ++j) {
                     const int32_t s = __shfl(mine, j);
                     if (s < 0) continue; // wave-uniform
@@ -708,9 +677,7 @@ __global__ __launch_bounds__(kBlock) void max_aggregate_kernel(const int64_t* __
 // bytes and adds dim * 4 through atomics.
 __global__ __launch_bounds__(kBlock) void max_aggregate_backward_kernel(const int32_t* __restrict__ arg, const float* __restrict__ grad_out,
                                                                         float* __restrict__ grad_src, int64_t n_dst, int dim) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const auto [lane, wave, n_waves] = wave_rows();
     for (int64_t d = wave; d < n_dst; d += n_waves)
         for (int c = lane; c < dim; c += 64) {
             const int32_t s = arg[d * dim + c];
@@ -735,13 +702,11 @@ __global__ __launch_bounds__(kBlock) void rel_sum_kernel(const int64_t* __restri
                                                          const float* __restrict__ h_src, float* __restrict__ out, int64_t n_dst, int num_rels,
                                                          int dim) {
     typedef float vf __attribute__((ext_vector_type(VEC)));
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const auto [lane, wave, n_waves] = wave_rows();
     const int units = dim / VEC;
     for (int64_t d = wave; d < n_dst; d += n_waves) {
         int64_t beg, end;
-        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
         // the first chunk stays in registers; -1 as a type matches no relation (padding, past the end, out of range)
         int32_t mine0 = -1, t0 = -1;
         float w0 = 1.0f;
@@ -770,9 +735,8 @@ __global__ __launch_bounds__(kBlock) void rel_sum_kernel(const int64_t* __restri
                     int32_t mine = mine0, t = t0;
                     float wm = w0;
                     if (e0 != beg) { // wave-uniform
-                        const bool have = e0 + lane < end;
-                        mine = have ? idx[e0 + lane] : -1;
-                        t = have && mine >= 0 ? etype[e0 + lane] : -1;
+                        load_chunk(idx, e0, end, lane, &mine);
+                        t = mine >= 0 ? etype[e0 + lane] : -1;
                         wm = w && t == r ? w[e0 + lane] : 1.0f;
                     }
                     uint64_t hit = __ballot(t == r); // t == r >= 0 only on a valid slot
@@ -804,16 +768,15 @@ __global__ __launch_bounds__(kBlock) void rel_sum_backward_kernel(const int64_t*
                                                                   float* __restrict__ grad_src, float* __restrict__ grad_w, int64_t n_dst,
                                                                   int num_rels, int dim) {
     typedef float vf __attribute__((ext_vector_type(VEC)));
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const auto [lane, wave, n_waves] = wave_rows();
     const int units = dim / VEC;
     for (int64_t d = wave; d < n_dst; d += n_waves) {
         int64_t beg, end;
-        gat_row<CSR>(indptr, fanout, d, &beg, &end);
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
         for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
             const bool have = e0 + lane < end;
-            const int32_t mine = have ? idx[e0 + lane] : -1;
+            int32_t mine;
+            load_chunk(idx, e0, end, lane, &mine);
             int32_t t = mine >= 0 ? etype[e0 + lane] : -1;
             if (t < 0 || t >= num_rels) t = -1;
             const float wm = w && t >= 0 ? w[e0 + lane] : 1.0f;
@@ -844,153 +807,116 @@ __global__ __launch_bounds__(kBlock) void rel_sum_backward_kernel(const int64_t*
     }
 }
 
-} // namespace
-
-namespace {
 // 16-B accesses need a row length of whole float4s and both row arrays on a 16-B boundary
 bool vec4_ok(int dim, const void* a, const void* b) {
     return dim % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
 }
 
-// f(std::integral_constant<int, VEC>): the float4 instantiation of a forward kernel, or its scalar one
+// f(std::integral_constant<int, VEC>): the float4 instantiation of a kernel, or its scalar one
 template <typename F>
 void dispatch_vec(bool vec4, F&& f) {
     if (vec4) f(std::integral_constant<int, 4>{});
     else f(std::integral_constant<int, 1>{});
 }
 
-int gat_check(int64_t n_dst, int heads, int dim) {
+dim3 row_grid(int64_t n_dst) { return dim3(grid1d(n_dst * 64, kBlock, 8192)); } // one wave per destination row
+
+// Every launch below runs the same checks in the same order: the shape, then n_dst == 0 is done, then the null buffers.  The fixed
+// form of an entry passes indptr = nullptr and its fan-out, the CSR form fanout = 0.
+template <bool CSR>
+bool fanout_ok(int fanout) { return CSR || (fanout >= 1 && fanout <= 32); }
+
+template <bool CSR>
+int shape_check(int64_t n_dst, int fanout, int dim) {
+    if (n_dst >= 0 && dim >= 1 && fanout_ok<CSR>(fanout)) return COALA_OK;
+    return CSR ? fail(COALA_EINVAL, "bad block shape") : fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+}
+
+template <bool CSR>
+int gat_shape_check(int64_t n_dst, int fanout, int heads, int dim) {
+    if (!fanout_ok<CSR>(fanout)) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
     if (n_dst < 0 || heads < 1 || heads > kGatMaxHeads || dim < 1 || (int64_t)heads * dim > INT32_MAX)
         return fail(COALA_EINVAL, "bad block shape (heads 1..%d, dim >= 1, n_dst >= 0)", kGatMaxHeads);
     return COALA_OK;
 }
-} // namespace
 
-extern "C" {
+constexpr int kMaxRels = 64; // a row's relations are a 64-bit mask
 
-int coala_block_mean_aggregate(int device, const int32_t* nbr, const float* h_src, float* out, int64_t n_dst, int fanout, int dim, void* stream) {
-    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+template <bool CSR>
+int rel_shape_check(int64_t n_dst, int fanout, int num_rels, int dim) {
+    if (n_dst >= 0 && dim >= 1 && num_rels >= 1 && num_rels <= kMaxRels && fanout_ok<CSR>(fanout)) return COALA_OK;
+    return CSR ? fail(COALA_EINVAL, "bad block shape (relations 1..%d)", kMaxRels)
+               : fail(COALA_EINVAL, "bad block shape (fan-out 1..32, relations 1..%d)", kMaxRels);
+}
+
+template <bool CSR>
+int mean_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* h_src, float* out, int64_t n_dst, int dim,
+                void* stream) {
+    if (int rc = shape_check<CSR>(n_dst, fanout, dim)) return rc;
     if (n_dst == 0) return COALA_OK;
-    if (!nbr || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
+    if ((CSR && !indptr) || !idx || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
     dispatch_vec(vec4_ok(dim, h_src, out), [&](auto vec) {
-        hipLaunchKernelGGL(mean_aggregate_kernel<decltype(vec)::value>, grid, blk, 0, (hipStream_t)stream, nbr, h_src, out, n_dst, fanout, dim);
+        hipLaunchKernelGGL((mean_aggregate_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx,
+                           fanout, h_src, out, n_dst, dim);
     });
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
 
-int coala_block_mean_aggregate_backward(int device, const int32_t* nbr, const float* grad_out, float* grad_src, int64_t n_dst, int fanout,
-                                        int dim, void* stream) {
-    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+template <bool CSR>
+int mean_backward_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* grad_out, float* grad_src, int64_t n_dst,
+                         int dim, void* stream) {
+    if (int rc = shape_check<CSR>(n_dst, fanout, dim)) return rc;
     if (n_dst == 0) return COALA_OK;
-    if (!nbr || !grad_out || !grad_src) return fail(COALA_EINVAL, "null buffer");
+    if ((CSR && !indptr) || !idx || !grad_out || !grad_src) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(mean_aggregate_backward_kernel, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, nbr, grad_out,
-                       grad_src, n_dst, fanout, dim);
+    hipLaunchKernelGGL(mean_aggregate_backward_kernel<CSR>, row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx, fanout, grad_out,
+                       grad_src, n_dst, dim);
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
 
-int coala_block_mean_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int64_t n_dst, int dim,
-                                   void* stream) {
-    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
+template <bool CSR>
+int gat_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* el, const float* er, const float* feat, float* out,
+               float* lse, int64_t n_dst, int heads, int dim, float slope, void* stream) {
+    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
     if (n_dst == 0) return COALA_OK;
-    if (!indptr || !indices || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
+    if ((CSR && !indptr) || !idx || !el || !er || !feat || !out || !lse) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
-    dispatch_vec(vec4_ok(dim, h_src, out), [&](auto vec) {
-        hipLaunchKernelGGL(mean_aggregate_csr_kernel<decltype(vec)::value>, grid, blk, 0, (hipStream_t)stream, indptr, indices, h_src, out, n_dst, dim);
-    });
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-int coala_block_mean_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* grad_out, float* grad_src,
-                                            int64_t n_dst, int dim, void* stream) {
-    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
-    if (n_dst == 0) return COALA_OK;
-    if (!indptr || !indices || !grad_out || !grad_src) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(mean_aggregate_csr_backward_kernel, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, indptr,
-                       indices, grad_out, grad_src, n_dst, dim);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-int coala_block_gat_aggregate(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, float* out, float* lse,
-                              int64_t n_dst, int fanout, int heads, int dim, float negative_slope, void* stream) {
-    if (fanout < 1 || fanout > 32) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
-    if (n_dst == 0) return COALA_OK;
-    if (!nbr || !el || !er || !feat || !out || !lse) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
     dispatch_vec(vec4_ok(dim, feat, out), [&](auto vec) {
-        hipLaunchKernelGGL((gat_aggregate_kernel<decltype(vec)::value, false>), grid, blk, 0, (hipStream_t)stream, nullptr, nbr, fanout, el, er, feat,
-                           out, lse, n_dst, heads, dim, negative_slope);
+        hipLaunchKernelGGL((gat_aggregate_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx,
+                           fanout, el, er, feat, out, lse, n_dst, heads, dim, slope);
     });
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
 
-int coala_block_gat_aggregate_backward(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, const float* out,
-                                       const float* lse, const float* grad_out, float* grad_feat, float* grad_el, float* grad_er, int64_t n_dst,
-                                       int fanout, int heads, int dim, float negative_slope, void* stream) {
-    if (fanout < 1 || fanout > 32) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
+template <bool CSR>
+int gat_backward_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* el, const float* er, const float* feat,
+                        const float* out, const float* lse, const float* grad_out, float* grad_feat, float* grad_el, float* grad_er,
+                        int64_t n_dst, int heads, int dim, float slope, void* stream) {
+    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
     if (n_dst == 0) return COALA_OK;
-    if (!nbr || !el || !er || !feat || !out || !lse || !grad_out || !grad_feat || !grad_el || !grad_er) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(gat_aggregate_backward_kernel<false>, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, nullptr,
-                       nbr, fanout, el, er, feat, out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim, negative_slope);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-int coala_block_gat_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er, const float* feat,
-                                  float* out, float* lse, int64_t n_dst, int heads, int dim, float negative_slope, void* stream) {
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
-    if (n_dst == 0) return COALA_OK;
-    if (!indptr || !indices || !el || !er || !feat || !out || !lse) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
-    dispatch_vec(vec4_ok(dim, feat, out), [&](auto vec) {
-        hipLaunchKernelGGL((gat_aggregate_kernel<decltype(vec)::value, true>), grid, blk, 0, (hipStream_t)stream, indptr, indices, 0, el, er, feat, out,
-                           lse, n_dst, heads, dim, negative_slope);
-    });
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er,
-                                           const float* feat, const float* out, const float* lse, const float* grad_out, float* grad_feat,
-                                           float* grad_el, float* grad_er, int64_t n_dst, int heads, int dim, float negative_slope, void* stream) {
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
-    if (n_dst == 0) return COALA_OK;
-    if (!indptr || !indices || !el || !er || !feat || !out || !lse || !grad_out || !grad_feat || !grad_el || !grad_er)
+    if ((CSR && !indptr) || !idx || !el || !er || !feat || !out || !lse || !grad_out || !grad_feat || !grad_el || !grad_er)
         return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(gat_aggregate_backward_kernel<true>, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, indptr,
-                       indices, 0, el, er, feat, out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim, negative_slope);
+    hipLaunchKernelGGL(gat_aggregate_backward_kernel<CSR>, row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx, fanout, el, er, feat,
+                       out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim, slope);
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
 
-} // extern "C"
-
-namespace {
 template <bool CSR>
 int gatv2_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* feat_src, const float* feat_dst,
                  const float* attn, float* out, float* lse, int64_t n_dst, int heads, int dim, float slope, void* stream) {
+    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
     if (n_dst == 0) return COALA_OK;
     if ((CSR && !indptr) || !idx || !feat_src || !feat_dst || !attn || !out || !lse) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
     dispatch_vec(vec4_ok(dim, feat_src, out), [&](auto vec) {
-        hipLaunchKernelGGL((gatv2_aggregate_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, fanout, feat_src,
-                           feat_dst, attn, out, lse, n_dst, heads, dim, slope);
+        hipLaunchKernelGGL((gatv2_aggregate_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx,
+                           fanout, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, slope);
     });
     HIPCHK(hipGetLastError());
     return COALA_OK;
@@ -1003,13 +929,14 @@ template <bool CSR>
 int gatv2_backward_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* feat_src, const float* feat_dst,
                           const float* attn, const float* out, const float* lse, const float* grad_out, float* grad_src, float* grad_dst,
                           float* grad_attn_parts, int parts, int64_t n_dst, int heads, int dim, float slope, void* stream) {
+    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
     if (grad_attn_parts && parts < 1) return fail(COALA_EINVAL, "bad block shape (parts >= 1)");
     if (n_dst == 0 || (!grad_src && !grad_dst && !grad_attn_parts)) return COALA_OK;
     if ((CSR && !indptr) || !idx || !feat_src || !feat_dst || !attn || !out || !lse || !grad_out) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
     const int passes = (heads * dim + 63) / 64;
     const bool regs = grad_attn_parts && passes <= kGatMaxHeads;
-    const dim3 grid(grad_attn_parts ? parts : grid1d(n_dst * 64, kBlock, 8192)), blk(grad_attn_parts && !regs ? 64 : kBlock);
+    const dim3 grid(grad_attn_parts ? dim3(parts) : row_grid(n_dst)), blk(grad_attn_parts && !regs ? 64 : kBlock);
     auto launch = [&](auto rp) {
         hipLaunchKernelGGL((gatv2_aggregate_backward_kernel<decltype(rp)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, fanout,
                            feat_src, feat_dst, attn, out, lse, grad_out, grad_src, grad_dst, grad_attn_parts, n_dst, heads, dim, slope);
@@ -1023,56 +950,17 @@ int gatv2_backward_launch(int device, const int64_t* indptr, const int32_t* idx,
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
-} // namespace
 
-extern "C" {
-
-int coala_block_gatv2_aggregate(int device, const int32_t* nbr, const float* feat_src, const float* feat_dst, const float* attn, float* out,
-                                float* lse, int64_t n_dst, int fanout, int heads, int dim, float negative_slope, void* stream) {
-    if (fanout < 1 || fanout > 32) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
-    return gatv2_launch<false>(device, nullptr, nbr, fanout, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, negative_slope, stream);
-}
-
-int coala_block_gatv2_aggregate_backward(int device, const int32_t* nbr, const float* feat_src, const float* feat_dst, const float* attn,
-                                         const float* out, const float* lse, const float* grad_out, float* grad_src, float* grad_dst,
-                                         float* grad_attn_parts, int parts, int64_t n_dst, int fanout, int heads, int dim, float negative_slope,
-                                         void* stream) {
-    if (fanout < 1 || fanout > 32) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
-    return gatv2_backward_launch<false>(device, nullptr, nbr, fanout, feat_src, feat_dst, attn, out, lse, grad_out, grad_src, grad_dst,
-                                        grad_attn_parts, parts, n_dst, heads, dim, negative_slope, stream);
-}
-
-int coala_block_gatv2_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* feat_src, const float* feat_dst,
-                                    const float* attn, float* out, float* lse, int64_t n_dst, int heads, int dim, float negative_slope,
-                                    void* stream) {
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
-    return gatv2_launch<true>(device, indptr, indices, 0, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, negative_slope, stream);
-}
-
-int coala_block_gatv2_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* feat_src,
-                                             const float* feat_dst, const float* attn, const float* out, const float* lse, const float* grad_out,
-                                             float* grad_src, float* grad_dst, float* grad_attn_parts, int parts, int64_t n_dst, int heads,
-                                             int dim, float negative_slope, void* stream) {
-    if (int rc = gat_check(n_dst, heads, dim)) return rc;
-    return gatv2_backward_launch<true>(device, indptr, indices, 0, feat_src, feat_dst, attn, out, lse, grad_out, grad_src, grad_dst,
-                                       grad_attn_parts, parts, n_dst, heads, dim, negative_slope, stream);
-}
-
-} // extern "C"
-
-namespace {
 template <bool CSR>
 int weighted_sum_launch(int device, const int64_t* indptr, const int32_t* idx, const float* w, int fanout, const float* h_src, float* out,
                         int64_t n_dst, int dim, void* stream) {
+    if (int rc = shape_check<CSR>(n_dst, fanout, dim)) return rc;
     if (n_dst == 0) return COALA_OK;
     if ((CSR && !indptr) || !idx || !w || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
     dispatch_vec(vec4_ok(dim, h_src, out), [&](auto vec) {
-        hipLaunchKernelGGL((weighted_sum_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, w, fanout, h_src, out,
-                           n_dst, dim);
+        hipLaunchKernelGGL((weighted_sum_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx, w,
+                           fanout, h_src, out, n_dst, dim);
     });
     HIPCHK(hipGetLastError());
     return COALA_OK;
@@ -1081,105 +969,53 @@ int weighted_sum_launch(int device, const int64_t* indptr, const int32_t* idx, c
 template <bool CSR>
 int weighted_sum_backward_launch(int device, const int64_t* indptr, const int32_t* idx, const float* w, int fanout, const float* h_src,
                                  const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int dim, void* stream) {
+    if (int rc = shape_check<CSR>(n_dst, fanout, dim)) return rc;
     if (n_dst == 0 || (!grad_src && !grad_w)) return COALA_OK;
     if ((CSR && !indptr) || !idx || !w || !grad_out || (grad_w && !h_src)) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
     dispatch_vec(vec4_ok(dim, grad_out, grad_w ? h_src : nullptr), [&](auto vec) {
-        hipLaunchKernelGGL((weighted_sum_backward_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, w, fanout,
-                           h_src, grad_out, grad_src, grad_w, n_dst, dim);
+        hipLaunchKernelGGL((weighted_sum_backward_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr,
+                           idx, w, fanout, h_src, grad_out, grad_src, grad_w, n_dst, dim);
     });
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
-} // namespace
 
-extern "C" {
-
-int coala_block_weighted_sum(int device, const int32_t* nbr, const float* w, const float* h_src, float* out, int64_t n_dst, int fanout, int dim,
-                             void* stream) {
-    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
-    return weighted_sum_launch<false>(device, nullptr, nbr, w, fanout, h_src, out, n_dst, dim, stream);
-}
-
-int coala_block_weighted_sum_backward(int device, const int32_t* nbr, const float* w, const float* h_src, const float* grad_out, float* grad_src,
-                                      float* grad_w, int64_t n_dst, int fanout, int dim, void* stream) {
-    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
-    return weighted_sum_backward_launch<false>(device, nullptr, nbr, w, fanout, h_src, grad_out, grad_src, grad_w, n_dst, dim, stream);
-}
-
-int coala_block_weighted_sum_csr(int device, const int64_t* indptr, const int32_t* indices, const float* w, const float* h_src, float* out,
-                                 int64_t n_dst, int dim, void* stream) {
-    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
-    return weighted_sum_launch<true>(device, indptr, indices, w, 0, h_src, out, n_dst, dim, stream);
-}
-
-int coala_block_weighted_sum_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* w, const float* h_src,
-                                          const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int dim, void* stream) {
-    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
-    return weighted_sum_backward_launch<true>(device, indptr, indices, w, 0, h_src, grad_out, grad_src, grad_w, n_dst, dim, stream);
-}
-
-} // extern "C"
-
-namespace {
 template <bool CSR>
-int max_aggregate_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* h_src, float* out, int32_t* arg,
-                         int64_t n_dst, int dim, void* stream) {
+int max_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* h_src, float* out, int32_t* arg, int64_t n_dst,
+               int dim, void* stream) {
+    if (int rc = shape_check<CSR>(n_dst, fanout, dim)) return rc;
     if (n_dst == 0) return COALA_OK;
     if ((CSR && !indptr) || !idx || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
     dispatch_vec(vec4_ok(dim, h_src, out) && vec4_ok(dim, arg, nullptr), [&](auto vec) {
-        hipLaunchKernelGGL((max_aggregate_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, fanout, h_src, out,
-                           arg, n_dst, dim);
+        hipLaunchKernelGGL((max_aggregate_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx,
+                           fanout, h_src, out, arg, n_dst, dim);
     });
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
-} // namespace
 
-extern "C" {
-
-int coala_block_max_aggregate(int device, const int32_t* nbr, const float* h_src, float* out, int32_t* arg, int64_t n_dst, int fanout, int dim,
-                              void* stream) {
-    if (n_dst < 0 || fanout < 1 || fanout > 32 || dim < 1) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
-    return max_aggregate_launch<false>(device, nullptr, nbr, fanout, h_src, out, arg, n_dst, dim, stream);
-}
-
-int coala_block_max_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int32_t* arg,
-                                  int64_t n_dst, int dim, void* stream) {
-    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
-    return max_aggregate_launch<true>(device, indptr, indices, 0, h_src, out, arg, n_dst, dim, stream);
-}
-
-int coala_block_max_aggregate_backward(int device, const int32_t* arg, const float* grad_out, float* grad_src, int64_t n_dst, int dim,
-                                       void* stream) {
-    if (n_dst < 0 || dim < 1) return fail(COALA_EINVAL, "bad block shape");
+int max_backward_launch(int device, const int32_t* arg, const float* grad_out, float* grad_src, int64_t n_dst, int dim, void* stream) {
+    if (int rc = shape_check<true>(n_dst, 0, dim)) return rc; // one kernel for both forms: no neighbour list, no fan-out
     if (n_dst == 0) return COALA_OK;
     if (!arg || !grad_out || !grad_src) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(max_aggregate_backward_kernel, dim3(grid1d(n_dst * 64, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, arg, grad_out,
-                       grad_src, n_dst, dim);
+    hipLaunchKernelGGL(max_aggregate_backward_kernel, row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, arg, grad_out, grad_src, n_dst, dim);
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
-
-} // extern "C"
-
-namespace {
-constexpr int kMaxRels = 64; // a row's relations are a 64-bit mask
 
 template <bool CSR>
 int rel_sum_launch(int device, const int64_t* indptr, const int32_t* idx, const int32_t* etype, const float* w, int fanout, const float* h_src,
                    float* out, int64_t n_dst, int num_rels, int dim, void* stream) {
+    if (int rc = rel_shape_check<CSR>(n_dst, fanout, num_rels, dim)) return rc;
     if (n_dst == 0) return COALA_OK;
     if ((CSR && !indptr) || !idx || !etype || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
     dispatch_vec(vec4_ok(dim, h_src, out), [&](auto vec) {
-        hipLaunchKernelGGL((rel_sum_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, etype, w, fanout, h_src, out,
-                           n_dst, num_rels, dim);
+        hipLaunchKernelGGL((rel_sum_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx, etype, w,
+                           fanout, h_src, out, n_dst, num_rels, dim);
     });
     HIPCHK(hipGetLastError());
     return COALA_OK;
@@ -1189,47 +1025,147 @@ template <bool CSR>
 int rel_sum_backward_launch(int device, const int64_t* indptr, const int32_t* idx, const int32_t* etype, const float* w, int fanout,
                             const float* h_src, const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int num_rels, int dim,
                             void* stream) {
+    if (int rc = rel_shape_check<CSR>(n_dst, fanout, num_rels, dim)) return rc;
     if (n_dst == 0 || (!grad_src && !grad_w)) return COALA_OK;
     if ((CSR && !indptr) || !idx || !etype || !grad_out || (grad_w && !h_src)) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    const dim3 grid(grid1d(n_dst * 64, kBlock, 8192)), blk(kBlock);
     dispatch_vec(vec4_ok(dim, grad_out, grad_w ? h_src : nullptr), [&](auto vec) { // the weighted sum backward's choice: the same bits at R = 1
-        hipLaunchKernelGGL((rel_sum_backward_kernel<decltype(vec)::value, CSR>), grid, blk, 0, (hipStream_t)stream, indptr, idx, etype, w, fanout,
-                           h_src, grad_out, grad_src, grad_w, n_dst, num_rels, dim);
+        hipLaunchKernelGGL((rel_sum_backward_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx,
+                           etype, w, fanout, h_src, grad_out, grad_src, grad_w, n_dst, num_rels, dim);
     });
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
 
-bool rel_shape_ok(int64_t n_dst, int num_rels, int dim) { return n_dst >= 0 && dim >= 1 && num_rels >= 1 && num_rels <= kMaxRels; }
 } // namespace
 
+// The C ABI (include/coala_hip.h): every entry forwards to its launch, the fixed form with <false>, a null indptr and its fan-out, the
+// CSR form with <true> and fan-out 0.
 extern "C" {
+
+int coala_block_mean_aggregate(int device, const int32_t* nbr, const float* h_src, float* out, int64_t n_dst, int fanout, int dim, void* stream) {
+    return mean_launch<false>(device, nullptr, nbr, fanout, h_src, out, n_dst, dim, stream);
+}
+
+int coala_block_mean_aggregate_backward(int device, const int32_t* nbr, const float* grad_out, float* grad_src, int64_t n_dst, int fanout,
+                                        int dim, void* stream) {
+    return mean_backward_launch<false>(device, nullptr, nbr, fanout, grad_out, grad_src, n_dst, dim, stream);
+}
+
+int coala_block_mean_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int64_t n_dst, int dim,
+                                   void* stream) {
+    return mean_launch<true>(device, indptr, indices, 0, h_src, out, n_dst, dim, stream);
+}
+
+int coala_block_mean_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* grad_out, float* grad_src,
+                                            int64_t n_dst, int dim, void* stream) {
+    return mean_backward_launch<true>(device, indptr, indices, 0, grad_out, grad_src, n_dst, dim, stream);
+}
+
+int coala_block_gat_aggregate(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, float* out, float* lse,
+                              int64_t n_dst, int fanout, int heads, int dim, float negative_slope, void* stream) {
+    return gat_launch<false>(device, nullptr, nbr, fanout, el, er, feat, out, lse, n_dst, heads, dim, negative_slope, stream);
+}
+
+int coala_block_gat_aggregate_backward(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, const float* out,
+                                       const float* lse, const float* grad_out, float* grad_feat, float* grad_el, float* grad_er, int64_t n_dst,
+                                       int fanout, int heads, int dim, float negative_slope, void* stream) {
+    return gat_backward_launch<false>(device, nullptr, nbr, fanout, el, er, feat, out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim,
+                                      negative_slope, stream);
+}
+
+int coala_block_gat_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er, const float* feat,
+                                  float* out, float* lse, int64_t n_dst, int heads, int dim, float negative_slope, void* stream) {
+    return gat_launch<true>(device, indptr, indices, 0, el, er, feat, out, lse, n_dst, heads, dim, negative_slope, stream);
+}
+
+int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er,
+                                           const float* feat, const float* out, const float* lse, const float* grad_out, float* grad_feat,
+                                           float* grad_el, float* grad_er, int64_t n_dst, int heads, int dim, float negative_slope, void* stream) {
+    return gat_backward_launch<true>(device, indptr, indices, 0, el, er, feat, out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim,
+                                     negative_slope, stream);
+}
+
+int coala_block_gatv2_aggregate(int device, const int32_t* nbr, const float* feat_src, const float* feat_dst, const float* attn, float* out,
+                                float* lse, int64_t n_dst, int fanout, int heads, int dim, float negative_slope, void* stream) {
+    return gatv2_launch<false>(device, nullptr, nbr, fanout, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, negative_slope, stream);
+}
+
+int coala_block_gatv2_aggregate_backward(int device, const int32_t* nbr, const float* feat_src, const float* feat_dst, const float* attn,
+                                         const float* out, const float* lse, const float* grad_out, float* grad_src, float* grad_dst,
+                                         float* grad_attn_parts, int parts, int64_t n_dst, int fanout, int heads, int dim, float negative_slope,
+                                         void* stream) {
+    return gatv2_backward_launch<false>(device, nullptr, nbr, fanout, feat_src, feat_dst, attn, out, lse, grad_out, grad_src, grad_dst,
+                                        grad_attn_parts, parts, n_dst, heads, dim, negative_slope, stream);
+}
+
+int coala_block_gatv2_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* feat_src, const float* feat_dst,
+                                    const float* attn, float* out, float* lse, int64_t n_dst, int heads, int dim, float negative_slope,
+                                    void* stream) {
+    return gatv2_launch<true>(device, indptr, indices, 0, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, negative_slope, stream);
+}
+
+int coala_block_gatv2_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* feat_src,
+                                             const float* feat_dst, const float* attn, const float* out, const float* lse, const float* grad_out,
+                                             float* grad_src, float* grad_dst, float* grad_attn_parts, int parts, int64_t n_dst, int heads,
+                                             int dim, float negative_slope, void* stream) {
+    return gatv2_backward_launch<true>(device, indptr, indices, 0, feat_src, feat_dst, attn, out, lse, grad_out, grad_src, grad_dst,
+                                       grad_attn_parts, parts, n_dst, heads, dim, negative_slope, stream);
+}
+
+int coala_block_weighted_sum(int device, const int32_t* nbr, const float* w, const float* h_src, float* out, int64_t n_dst, int fanout, int dim,
+                             void* stream) {
+    return weighted_sum_launch<false>(device, nullptr, nbr, w, fanout, h_src, out, n_dst, dim, stream);
+}
+
+int coala_block_weighted_sum_backward(int device, const int32_t* nbr, const float* w, const float* h_src, const float* grad_out, float* grad_src,
+                                      float* grad_w, int64_t n_dst, int fanout, int dim, void* stream) {
+    return weighted_sum_backward_launch<false>(device, nullptr, nbr, w, fanout, h_src, grad_out, grad_src, grad_w, n_dst, dim, stream);
+}
+
+int coala_block_weighted_sum_csr(int device, const int64_t* indptr, const int32_t* indices, const float* w, const float* h_src, float* out,
+                                 int64_t n_dst, int dim, void* stream) {
+    return weighted_sum_launch<true>(device, indptr, indices, w, 0, h_src, out, n_dst, dim, stream);
+}
+
+int coala_block_weighted_sum_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* w, const float* h_src,
+                                          const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int dim, void* stream) {
+    return weighted_sum_backward_launch<true>(device, indptr, indices, w, 0, h_src, grad_out, grad_src, grad_w, n_dst, dim, stream);
+}
+
+int coala_block_max_aggregate(int device, const int32_t* nbr, const float* h_src, float* out, int32_t* arg, int64_t n_dst, int fanout, int dim,
+                              void* stream) {
+    return max_launch<false>(device, nullptr, nbr, fanout, h_src, out, arg, n_dst, dim, stream);
+}
+
+int coala_block_max_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int32_t* arg,
+                                  int64_t n_dst, int dim, void* stream) {
+    return max_launch<true>(device, indptr, indices, 0, h_src, out, arg, n_dst, dim, stream);
+}
+
+int coala_block_max_aggregate_backward(int device, const int32_t* arg, const float* grad_out, float* grad_src, int64_t n_dst, int dim,
+                                       void* stream) {
+    return max_backward_launch(device, arg, grad_out, grad_src, n_dst, dim, stream);
+}
 
 int coala_block_rel_sum(int device, const int32_t* nbr, const int32_t* etype, const float* w, const float* h_src, float* out, int64_t n_dst,
                         int fanout, int num_rels, int dim, void* stream) {
-    if (!rel_shape_ok(n_dst, num_rels, dim) || fanout < 1 || fanout > 32)
-        return fail(COALA_EINVAL, "bad block shape (fan-out 1..32, relations 1..%d)", kMaxRels);
     return rel_sum_launch<false>(device, nullptr, nbr, etype, w, fanout, h_src, out, n_dst, num_rels, dim, stream);
 }
 
 int coala_block_rel_sum_backward(int device, const int32_t* nbr, const int32_t* etype, const float* w, const float* h_src, const float* grad_out,
                                  float* grad_src, float* grad_w, int64_t n_dst, int fanout, int num_rels, int dim, void* stream) {
-    if (!rel_shape_ok(n_dst, num_rels, dim) || fanout < 1 || fanout > 32)
-        return fail(COALA_EINVAL, "bad block shape (fan-out 1..32, relations 1..%d)", kMaxRels);
     return rel_sum_backward_launch<false>(device, nullptr, nbr, etype, w, fanout, h_src, grad_out, grad_src, grad_w, n_dst, num_rels, dim, stream);
 }
 
 int coala_block_rel_sum_csr(int device, const int64_t* indptr, const int32_t* indices, const int32_t* etype, const float* w, const float* h_src,
                             float* out, int64_t n_dst, int num_rels, int dim, void* stream) {
-    if (!rel_shape_ok(n_dst, num_rels, dim)) return fail(COALA_EINVAL, "bad block shape (relations 1..%d)", kMaxRels);
     return rel_sum_launch<true>(device, indptr, indices, etype, w, 0, h_src, out, n_dst, num_rels, dim, stream);
 }
 
 int coala_block_rel_sum_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const int32_t* etype, const float* w,
                                      const float* h_src, const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int num_rels,
                                      int dim, void* stream) {
-    if (!rel_shape_ok(n_dst, num_rels, dim)) return fail(COALA_EINVAL, "bad block shape (relations 1..%d)", kMaxRels);
     return rel_sum_backward_launch<true>(device, indptr, indices, etype, w, 0, h_src, grad_out, grad_src, grad_w, n_dst, num_rels, dim, stream);
 }
 
