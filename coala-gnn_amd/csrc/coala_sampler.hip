@@ -27,8 +27,8 @@
 //     nothing, and coala_sampler_wait_layers returns the error with the layer and its item count.  Fixed layers behind a full
 //     layer have a device-known destination count; their worst-case bound n_dst * (f + 1) is checked on the device by the full
 //     layer's scan_assign in the same way.  Nothing is written past the caller's capacities; the handle stays usable.
-//   Launches: degree_scan (degrees -> indptr_local and E, the single-pass tile-ticket scan of scan_assign with the same status
-//   words), full_insert (one thread per item position p < n_dst + E: a binary search in indptr_local finds the destination, so a
+//   Launches: degree_scan (degrees -> indptr_local and E: tile_scan, the single-pass tile-ticket scan of scan_assign, on the same
+//   status words; publish_ragged_layer makes the check), full_insert (one thread per item position p < n_dst + E: a binary search in indptr_local finds the destination, so a
 //   hub of 10^6 in-edges is spread over the whole grid), then scan_assign / relabel_clear in their full-layer instantiations.
 //   The hash table of a full layer is sized by its device-known item count: the kernel in front of the layer (the previous layer's
 //   relabel_clear, run after this layer's degree_scan, or table_clear for a first layer) clears exactly that much.
@@ -70,8 +70,8 @@
 //     only), refusal and bucketing are those of a full layer; an out-of-range destination id gives an empty row; a -1 layer of a
 //     LABOR list is the full layer above.
 //   Launches: labor_count_scan stands where degree_scan stands (a lane group per row counts its taken edges with ballots, a row of
-//   more than kHubDegree in-edges is counted by the whole block; then degree_scan's tile-ticket scan, capacity check and count
-//   words), labor_insert where full_insert stands (the same test again, survivors compacted to indptr_local[d] + rank by ballot
+//   more than kHubDegree in-edges is counted by the whole block; then degree_scan's tile_scan and publish_ragged_layer: the same
+//   capacity check and count words), labor_insert where full_insert stands (the same test again, survivors compacted to indptr_local[d] + rank by ballot
 //   prefix, stored with their edge id when asked and hash-inserted; a hub row again on the whole block), then scan_assign /
 //   relabel_clear in their full-layer instantiations and the bucketing kernels, unchanged.  No launch, memset or host wait is added.
 //
@@ -164,8 +164,6 @@ struct Table {
     uint32_t* local_of_slot;  // [table] index of the key in the source list
 };
 
-constexpr unsigned long long kAggregate = 1ull << 32, kInclusive = 2ull << 32; // look-back status (scan_assign_kernel)
-
 __device__ __forceinline__ void clear_table(const Table& t, uint32_t tbl) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < tbl; i += gridDim.x * blockDim.x) {
         t.keys[i] = kEmpty;
@@ -193,6 +191,56 @@ __device__ __forceinline__ void hash_insert(const Table& tb, uint32_t mask, int6
     }
 }
 
+__device__ __forceinline__ uint32_t sat_add(uint32_t a, uint32_t b) { // degree sums saturate: past 2^32 - 1 a layer is refused anyway
+    const uint32_t c = a + b;
+    return c < a ? 0xFFFFFFFFu : c;
+}
+
+// The layer's destination count: from device memory behind an earlier layer, by value for the first layer.
+__device__ __forceinline__ int64_t layer_n_dst(const int64_t* __restrict__ n_dst_dev, int64_t n_dst_value) { return n_dst_dev ? *n_dst_dev : n_dst_value; }
+
+// Row header of the kernels that put a lane group on a destination row: GS lanes of a wave per row, `gl` the lane inside its group,
+// `gbase` the group's first lane, `gmask` the group's lanes in a ballot.
+struct LaneGroup {
+    int gl, gbase;
+    uint64_t gmask;
+};
+
+template <int GS>
+__device__ __forceinline__ LaneGroup lane_group(int lane) {
+    const int gl = lane % GS, gbase = lane - gl;
+    return {gl, gbase, (GS == 64) ? ~0ull : (((1ull << GS) - 1ull) << gbase)};
+}
+
+struct Row { // destination d of a layer: its node, whether that is a node of the graph, and its in-edges indices[start .. start + deg)
+    int64_t v;
+    bool ok;
+    int64_t start, deg;
+};
+
+// d >= n_dst (a lane past the layer) gives v = -1; that and any id outside the graph give an empty row: the one statement of the
+// contract's "an out-of-range destination id gives an empty row".
+__device__ __forceinline__ Row dst_row(const Graph& g, const int64_t* __restrict__ dst, int64_t d, int64_t n_dst) {
+    const int64_t v = d < n_dst ? dst[d] : -1;
+    const bool ok = v >= 0 && v < g.num_nodes;
+    const int64_t start = ok ? g.indptr[v] : 0;
+    return {v, ok, start, ok ? g.indptr[v + 1] - start : 0};
+}
+
+// A row that an earlier pass put on a hub list: d < n_dst and the id is valid (its degree was read), so the loads are unconditional.
+__device__ __forceinline__ Row listed_row(const Graph& g, const int64_t* __restrict__ dst, int64_t d) {
+    const int64_t v = dst[d];
+    const int64_t start = g.indptr[v];
+    return {v, true, start, g.indptr[v + 1] - start};
+}
+
+// Slot q = d * fanout + c of a fixed layer takes neighbour nb, read at CSC position e (nb < 0: the slot is empty); eid is nullable.
+// The slot's hash insert (item n_dst + q) stays with the caller: sample_insert_kernel shares that loop with the node's own insert.
+__device__ __forceinline__ void emit_fixed_slot(int64_t* __restrict__ nbr, int64_t* __restrict__ eid, int64_t q, int64_t nb, int64_t e) {
+    nbr[q] = nb;
+    if (eid) eid[q] = nb >= 0 ? e : -1;
+}
+
 // Sample + insert, a lane per sampled neighbour: GS lanes (16/32/64 >= fanout+1) work on one destination node.  Lane c < fanout
 // draws Floyd's c-th candidate on its own, the duplicate resolution walks c = 0..fanout-1 with one shuffle + one ballot per
 // step (bit-identical to the sequential loop of the CPU twin), then every lane loads ITS neighbour and inserts it into the
@@ -202,21 +250,16 @@ __global__ __launch_bounds__(kBlock) void sample_insert_kernel(Graph g, const in
                                                                int64_t n_dst_value /* used when n_dst_dev is null: the first layer */, int fanout, uint64_t seed, uint64_t step, int layer, int64_t* __restrict__ nbr,
                                                                Table tb, uint32_t* __restrict__ slot_of_item, int64_t* __restrict__ eid) {
     constexpr int GPW = 64 / GS; // groups per wave
-    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
+    const int64_t n_dst = layer_n_dst(n_dst_dev, n_dst_value);
     const uint32_t mask = table_size(n_dst * (fanout + 1)) - 1;
     const int lane = threadIdx.x & 63;
-    const int gl = lane % GS;
-    const int gbase = lane - gl;
-    const uint64_t gmask = (GS == 64) ? ~0ull : (((1ull << GS) - 1ull) << gbase);
+    const auto [gl, gbase, gmask] = lane_group<GS>(lane);
     const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
     for (int64_t d0 = wave * GPW; d0 < n_dst; d0 += n_waves * GPW) { // wave-uniform trip count: ballots below need every lane
         const int64_t d = d0 + lane / GS;
         const bool active = d < n_dst;
-        const int64_t v = active ? dst[d] : -1;
-        const bool okv = active && v >= 0 && v < g.num_nodes;
-        const int64_t start = okv ? g.indptr[v] : 0;
-        const int64_t deg = okv ? g.indptr[v + 1] - start : 0;
+        const auto [v, okv, start, deg] = dst_row(g, dst, d, n_dst);
         // candidate of lane c = gl (Floyd step j = deg - fanout + c)
         const uint64_t key = sample_key(seed, step, layer, (uint64_t)v);
         const int64_t jmine = deg - fanout + gl;
@@ -231,8 +274,7 @@ __global__ __launch_bounds__(kBlock) void sample_insert_kernel(Graph g, const in
         if (gl < fanout) pick = (deg <= fanout) ? (gl < deg ? (int64_t)gl : -1) : chosen;
         const int64_t nb = (okv && pick >= 0) ? g.indices[start + pick] : kEmpty;
         if (active && gl < fanout) {
-            nbr[d * fanout + gl] = nb;
-            if (eid) eid[d * fanout + gl] = nb >= 0 ? start + pick : -1;
+            emit_fixed_slot(nbr, eid, d * fanout + gl, nb, start + pick);
         }
         // ---- hash insert: neighbours at positions n_dst + d*fanout + gl, the node itself at position d
         int64_t k = kEmpty;
@@ -322,21 +364,16 @@ __global__ __launch_bounds__(kBlock) void weighted_select_kernel(Graph g, const 
                                                                  unsigned long long* __restrict__ n_hubs, int64_t hub_cap,
                                                                  int64_t* __restrict__ eid) {
     constexpr int GPW = 64 / GS;
-    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
+    const int64_t n_dst = layer_n_dst(n_dst_dev, n_dst_value);
     const uint32_t mask = table_size(n_dst * (fanout + 1)) - 1;
     const int lane = threadIdx.x & 63;
-    const int gl = lane % GS;
-    const int gbase = lane - gl;
-    const uint64_t gmask = (GS == 64) ? ~0ull : (((1ull << GS) - 1ull) << gbase);
+    const auto [gl, gbase, gmask] = lane_group<GS>(lane);
     const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
     for (int64_t d0 = wave * GPW; d0 < n_dst; d0 += n_waves * GPW) { // wave-uniform; the row loop below is group-uniform
         const int64_t d = d0 + lane / GS;
         const bool active = d < n_dst;
-        const int64_t v = active ? dst[d] : -1;
-        const bool okv = active && v >= 0 && v < g.num_nodes;
-        const int64_t start = okv ? g.indptr[v] : 0;
-        const int64_t deg = okv ? g.indptr[v + 1] - start : 0;
+        const auto [v, okv, start, deg] = dst_row(g, dst, d, n_dst);
         unsigned long long hs = kNoKey;
         if (gl == 0 && deg > kHubDegree) {
             hs = atomicAdd(n_hubs, 1ull);
@@ -355,8 +392,7 @@ __global__ __launch_bounds__(kBlock) void weighted_select_kernel(Graph g, const 
             const int64_t pick = group_picks<GS>(bk, bp, gl, fanout);
             const int64_t nb = pick >= 0 ? g.indices[start + pick] : kEmpty;
             if (active && gl < fanout) {
-                nbr[d * fanout + gl] = nb;
-                if (eid) eid[d * fanout + gl] = nb >= 0 ? start + pick : -1;
+                emit_fixed_slot(nbr, eid, d * fanout + gl, nb, start + pick);
                 hash_insert(tb, mask, nb, n_dst + d * fanout + gl, slot_of_item);
             }
         }
@@ -378,14 +414,12 @@ __global__ __launch_bounds__(kHubBlock) void weighted_select_hub_kernel(Graph g,
     __shared__ int64_t s_p[kHubWaves * 32];
     const unsigned long long cnt = min(*n_hubs, (unsigned long long)hub_cap);
     if ((unsigned long long)blockIdx.x >= cnt) return;
-    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
+    const int64_t n_dst = layer_n_dst(n_dst_dev, n_dst_value);
     const uint32_t mask = table_size(n_dst * (fanout + 1)) - 1;
     const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
     for (unsigned long long i = blockIdx.x; i < cnt; i += gridDim.x) { // block-uniform
         const int64_t d = hubs[i];
-        const int64_t v = dst[d]; // listed rows have a valid id and more than kHubDegree in-edges
-        const int64_t start = g.indptr[v];
-        const int64_t deg = g.indptr[v + 1] - start;
+        const auto [v, listed, start, deg] = listed_row(g, dst, d); // more than kHubDegree in-edges
         const uint64_t wkey = sample_key(seed, step, layer, (uint64_t)v) ^ kWeightedStream;
         unsigned long long bk = kNoKey;
         int64_t bp = kNoPos;
@@ -410,58 +444,61 @@ __global__ __launch_bounds__(kHubBlock) void weighted_select_hub_kernel(Graph g,
             const int64_t pick = group_picks<64>(bk, bp, lane, fanout);
             if (lane < fanout) {
                 const int64_t nb = pick >= 0 ? g.indices[start + pick] : kEmpty;
-                nbr[d * fanout + lane] = nb;
-                if (eid) eid[d * fanout + lane] = nb >= 0 ? start + pick : -1;
+                emit_fixed_slot(nbr, eid, d * fanout + lane, nb, start + pick);
                 hash_insert(tb, mask, nb, n_dst + d * fanout + lane, slot_of_item);
             }
         }
     }
 }
 
-__device__ __forceinline__ uint32_t sat_add(uint32_t a, uint32_t b) { // degree sums saturate: past 2^32 - 1 a layer is refused anyway
-    const uint32_t c = a + b;
-    return c < a ? 0xFFFFFFFFu : c;
+// ---------------------------------------------------------------------------------------------------------- single-pass tile scan
+// Single-pass scan over the tiles of a layer (degree_scan_kernel, labor_count_scan_kernel, scan_assign_kernel): a block takes the
+// next tile with an atomic ticket (so every predecessor of its tile has already started), publishes the tile's count as an
+// AGGREGATE, looks back over its predecessors until it meets an INCLUSIVE prefix and publishes its own INCLUSIVE prefix.  Status
+// words carry the launch's generation: nothing to reset, and every scan of a handle shares the one ticket and the one status array.
+//   word = gen << 34 | status << 32 | value          status: 1 = aggregate, 2 = inclusive prefix
+// This is the only place where blocks wait on each other: relaxed agent-scope atomics on the status words, nothing else is ordered.
+constexpr unsigned long long kAggregate = 1ull << 32, kInclusive = 2ull << 32;
+
+struct TileScan {
+    uint32_t excl;  // exclusive prefix of this thread's count over the whole layer
+    uint32_t total; // inclusive total through this tile
+    bool last;      // this block owns the layer's last tile
+};
+
+template <bool SAT> // degree sums saturate; first-occurrence counts stay below kItemLimit and add plainly
+__device__ __forceinline__ uint32_t scan_add(uint32_t a, uint32_t b) {
+    if constexpr (SAT) return sat_add(a, b);
+    else return a + b;
 }
 
-__device__ __forceinline__ int64_t in_degree(const Graph& g, int64_t v) { return (v >= 0 && v < g.num_nodes) ? g.indptr[v + 1] - g.indptr[v] : 0; }
-
-// Full layer, pass 1: degrees of the destination nodes -> indptr_local (exclusive scan) and E, with the tile ticket and the
-// generation-tagged look-back status words of scan_assign_kernel (one scheme, shared counters).  The block of the last tile
-// checks the layer against its capacities and publishes n_dst (first layer), the item and edge counts -- 0 and 0 when refused.
-__global__ __launch_bounds__(kBlock) void degree_scan_kernel(Graph g, const int64_t* __restrict__ dst, const int64_t* __restrict__ n_dst_dev,
-                                                             int64_t n_dst_value, int64_t* __restrict__ base, unsigned long long* __restrict__ status,
-                                                             unsigned long long* __restrict__ ticket, unsigned long long ticket_base,
-                                                             unsigned long long gen, int64_t* __restrict__ indptr_local, int64_t item_cap,
-                                                             int64_t edge_cap, int64_t* __restrict__ pin) {
-    __shared__ uint32_t s_woff[kWavesPerBlock];
+// The block's tile: ticket order is start order.  Block-uniform; ends in a barrier.
+__device__ __forceinline__ int64_t take_tile(unsigned long long* __restrict__ ticket, unsigned long long ticket_base) {
     __shared__ unsigned long long s_tile;
-    __shared__ uint32_t s_prefix;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
-    const int64_t n_tiles = n_dst > 0 ? (n_dst + kTile - 1) / kTile : 1; // tile 0 always runs: it publishes an empty layer too
     if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1ull) - ticket_base;
     __syncthreads();
-    const int64_t tile = (int64_t)s_tile;
-    if (tile >= n_tiles) return;
-    const int64_t first = tile * kTile + (int64_t)threadIdx.x * kItems;
-    uint32_t dg[kItems];
-    uint32_t c = 0;
-    for (int i = 0; i < kItems; ++i) {
-        const int64_t deg = first + i < n_dst ? in_degree(g, dst[first + i]) : 0;
-        dg[i] = deg > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)deg;
-        c = sat_add(c, dg[i]);
-    }
+    return (int64_t)s_tile;
+}
+
+// Every thread of the block of `tile` (< n_tiles) calls it with its count c: wave inclusive scan, the waves combined through LDS,
+// then thread 0 chains the tile to its predecessors.  Ends in a barrier.
+template <bool SAT>
+__device__ __forceinline__ TileScan tile_scan(unsigned long long* __restrict__ status, unsigned long long gen, int64_t tile, int64_t n_tiles,
+                                              uint32_t c) {
+    __shared__ uint32_t s_woff[kWavesPerBlock];
+    __shared__ uint32_t s_prefix;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     uint32_t incl = c; // inclusive scan inside the wave
     for (int off = 1; off < 64; off <<= 1) {
         const uint32_t v = __shfl_up(incl, off);
-        if (lane >= off) incl = sat_add(incl, v);
+        if (lane >= off) incl = scan_add<SAT>(incl, v);
     }
     if (lane == 63) s_woff[w] = incl;
     __syncthreads();
     uint32_t wbase = 0, total = 0;
     for (int q = 0; q < kWavesPerBlock; ++q) {
-        if (q < w) wbase = sat_add(wbase, s_woff[q]);
-        total = sat_add(total, s_woff[q]);
+        if (q < w) wbase = scan_add<SAT>(wbase, s_woff[q]);
+        total = scan_add<SAT>(total, s_woff[q]);
     }
     if (threadIdx.x == 0) {
         const unsigned long long tag = gen << 34;
@@ -471,27 +508,55 @@ __global__ __launch_bounds__(kBlock) void degree_scan_kernel(Graph g, const int6
             for (int64_t t = tile - 1; t >= 0;) { // decoupled look-back
                 const unsigned long long v = __hip_atomic_load(status + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if ((v >> 34) != gen || !(v & (kAggregate | kInclusive))) { __builtin_amdgcn_s_sleep(1); continue; } // not published yet
-                prefix = sat_add(prefix, (uint32_t)v);
+                prefix = scan_add<SAT>(prefix, (uint32_t)v);
                 if (v & kInclusive) break;
                 --t;
             }
         }
-        __hip_atomic_store(status + tile, tag | kInclusive | sat_add(prefix, total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(status + tile, tag | kInclusive | scan_add<SAT>(prefix, total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_prefix = prefix;
-        if (tile == n_tiles - 1) { // the layer's totals, and the capacity check
-            const int64_t edges = (int64_t)sat_add(prefix, total);
-            const int64_t items = n_dst + edges;
-            const bool ok = items <= item_cap && edges <= edge_cap;
-            indptr_local[n_dst] = edges;
-            if (!n_dst_dev) base[0] = n_dst;
-            base[kItemsOff] = ok ? items : 0;
-            base[kEdgesOff] = ok ? edges : 0;
-            pin[kPinEdges] = edges;
-            pin[kPinRefused] = ok ? 0 : 1;
-        }
     }
     __syncthreads();
-    uint32_t run = sat_add(s_prefix, sat_add(wbase, incl - c));
+    const uint32_t prefix = s_prefix;
+    return {scan_add<SAT>(prefix, scan_add<SAT>(wbase, incl - c)), scan_add<SAT>(prefix, total), tile == n_tiles - 1};
+}
+
+// Last tile of a ragged layer (full or LABOR), one thread: the layer's totals and the capacity check.  A refused layer publishes 0
+// items and 0 edges, so every later kernel of the call does nothing; coala_sampler_wait_layers builds its message from the pinned words.
+__device__ __forceinline__ void publish_ragged_layer(int64_t n_dst, int64_t edges, bool first_layer, int64_t item_cap, int64_t edge_cap,
+                                                     int64_t* __restrict__ indptr_local, int64_t* __restrict__ base, int64_t* __restrict__ pin) {
+    const int64_t items = n_dst + edges;
+    const bool ok = items <= item_cap && edges <= edge_cap;
+    indptr_local[n_dst] = edges;
+    if (first_layer) base[0] = n_dst;
+    base[kItemsOff] = ok ? items : 0;
+    base[kEdgesOff] = ok ? edges : 0;
+    pin[kPinEdges] = edges;
+    pin[kPinRefused] = ok ? 0 : 1;
+}
+
+// Full layer, pass 1: degrees of the destination nodes -> indptr_local (exclusive scan) and E, by tile_scan.  The block of the last
+// tile checks the layer against its capacities and publishes n_dst (first layer), the item and edge counts (publish_ragged_layer).
+__global__ __launch_bounds__(kBlock) void degree_scan_kernel(Graph g, const int64_t* __restrict__ dst, const int64_t* __restrict__ n_dst_dev,
+                                                             int64_t n_dst_value, int64_t* __restrict__ base, unsigned long long* __restrict__ status,
+                                                             unsigned long long* __restrict__ ticket, unsigned long long ticket_base,
+                                                             unsigned long long gen, int64_t* __restrict__ indptr_local, int64_t item_cap,
+                                                             int64_t edge_cap, int64_t* __restrict__ pin) {
+    const int64_t n_dst = layer_n_dst(n_dst_dev, n_dst_value);
+    const int64_t n_tiles = n_dst > 0 ? (n_dst + kTile - 1) / kTile : 1; // tile 0 always runs: it publishes an empty layer too
+    const int64_t tile = take_tile(ticket, ticket_base);
+    if (tile >= n_tiles) return;
+    const int64_t first = tile * kTile + (int64_t)threadIdx.x * kItems;
+    uint32_t dg[kItems];
+    uint32_t c = 0;
+    for (int i = 0; i < kItems; ++i) {
+        const int64_t deg = dst_row(g, dst, first + i, n_dst).deg;
+        dg[i] = deg > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)deg;
+        c = sat_add(c, dg[i]);
+    }
+    const TileScan ts = tile_scan<true>(status, gen, tile, n_tiles, c);
+    if (ts.last && threadIdx.x == 0) publish_ragged_layer(n_dst, (int64_t)ts.total, !n_dst_dev, item_cap, edge_cap, indptr_local, base, pin);
+    uint32_t run = ts.excl;
     for (int i = 0; i < kItems; ++i) {
         if (first + i < n_dst) indptr_local[first + i] = (int64_t)run;
         run = sat_add(run, dg[i]);
@@ -544,6 +609,12 @@ __device__ __forceinline__ bool labor_take(uint64_t lkey, int64_t t, int64_t deg
     return deg <= fanout || __umul64hi(splitmix64(lkey ^ (uint64_t)t), (uint64_t)deg) < (uint64_t)fanout;
 }
 
+// A hub row of deg in-edges done by the whole block: wave w takes the contiguous share [hub_share(deg, w), hub_share(deg, w + 1)),
+// whole 64-edge steps except at the row's end.
+__device__ __forceinline__ int64_t hub_share(int64_t deg, int w) {
+    return min(deg, w * (((deg + kWavesPerBlock - 1) / kWavesPerBlock + 63) & ~63ll));
+}
+
 // Taken edges among positions [from, to) of a row, by one wave: the wave-uniform total (trip count and ballots are wave-uniform).
 __device__ __forceinline__ uint32_t labor_wave_count(const Graph& g, uint64_t lkey, int64_t start, int64_t deg, int fanout, int64_t from,
                                                      int64_t to, int lane) {
@@ -571,30 +642,21 @@ __global__ __launch_bounds__(kBlock) void labor_count_scan_kernel(Graph g, const
     __shared__ uint32_t s_cnt[kTile];
     __shared__ int s_hub[kLaborHubList];
     __shared__ int s_nhub;
-    __shared__ uint32_t s_woff[kWavesPerBlock];
-    __shared__ unsigned long long s_tile;
-    __shared__ uint32_t s_prefix;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
+    const int64_t n_dst = layer_n_dst(n_dst_dev, n_dst_value);
     const int64_t n_tiles = n_dst > 0 ? (n_dst + rows - 1) / rows : 1; // tile 0 always runs: it publishes an empty layer too
-    if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1ull) - ticket_base;
-    __syncthreads();
-    const int64_t tile = (int64_t)s_tile;
+    const int64_t tile = take_tile(ticket, ticket_base);
     if (tile >= n_tiles) return;
     const int64_t row0 = tile * rows;
     // ---- counts of the tile's rows
-    const int gl = lane % GS, gbase = lane - gl;
-    const uint64_t gmask = ((1ull << GS) - 1ull) << gbase;
+    const auto [gl, gbase, gmask] = lane_group<GS>(lane);
     for (int r0 = 0; r0 < rows; r0 += GPB * kLaborHubList) { // block-uniform: the list holds the hubs of one stretch of rows
         if (threadIdx.x == 0) s_nhub = 0;
         __syncthreads();
         const int r_end = min(rows, r0 + GPB * kLaborHubList);
         for (int r = r0 + (int)threadIdx.x / GS; r < r_end; r += GPB) { // wave-uniform trip count: r0, r_end are multiples of GPB
-            const int64_t d = row0 + r;
-            const int64_t v = d < n_dst ? dst[d] : -1;
-            const bool okv = v >= 0 && v < g.num_nodes;
-            const int64_t start = okv ? g.indptr[v] : 0;
-            int64_t deg = okv ? g.indptr[v + 1] - start : 0;
+            const Row row = dst_row(g, dst, row0 + r, n_dst);
+            int64_t deg = row.deg; // 0 once the row is deferred
             int at = kLaborHubList;
             if (gl == 0 && deg > kHubDegree) at = atomicAdd(&s_nhub, 1);
             at = __shfl(at, gbase);
@@ -607,7 +669,7 @@ __global__ __launch_bounds__(kBlock) void labor_count_scan_kernel(Graph g, const
             for (int off = GS; off < 64; off <<= 1) longest = max(longest, __shfl_xor(longest, off));
             for (int64_t c0 = 0; c0 < longest; c0 += GS) {
                 const int64_t j = c0 + gl;
-                const bool take = j < deg && labor_take(lkey, g.indices[start + j], deg, fanout);
+                const bool take = j < deg && labor_take(lkey, g.indices[row.start + j], deg, fanout);
                 n += (uint32_t)__builtin_popcountll(__ballot(take) & gmask);
             }
             if (gl == 0) s_cnt[r] = n; // a deferred row: 0 for now
@@ -616,11 +678,8 @@ __global__ __launch_bounds__(kBlock) void labor_count_scan_kernel(Graph g, const
         const int n_hub = min(s_nhub, kLaborHubList);
         for (int i = 0; i < n_hub; ++i) { // block-uniform: every wave counts its share of the row
             const int r = s_hub[i];
-            const int64_t v = dst[row0 + r];
-            const int64_t start = g.indptr[v];
-            const int64_t deg = g.indptr[v + 1] - start;
-            const int64_t seg = ((deg + kWavesPerBlock - 1) / kWavesPerBlock + 63) & ~63ll;
-            const uint32_t n = labor_wave_count(g, lkey, start, deg, fanout, min(deg, w * seg), min(deg, (w + 1) * seg), lane);
+            const Row hub = listed_row(g, dst, row0 + r);
+            const uint32_t n = labor_wave_count(g, lkey, hub.start, hub.deg, fanout, hub_share(hub.deg, w), hub_share(hub.deg, w + 1), lane);
             if (lane == 0 && n) atomicAdd(&s_cnt[r], n);
         }
         __syncthreads();
@@ -634,47 +693,9 @@ __global__ __launch_bounds__(kBlock) void labor_count_scan_kernel(Graph g, const
         dg[i] = (at + i < rows && first + i < n_dst) ? s_cnt[at + i] : 0;
         c = sat_add(c, dg[i]);
     }
-    uint32_t incl = c; // inclusive scan inside the wave
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off);
-        if (lane >= off) incl = sat_add(incl, v);
-    }
-    if (lane == 63) s_woff[w] = incl;
-    __syncthreads();
-    uint32_t wbase = 0, total = 0;
-    for (int q = 0; q < kWavesPerBlock; ++q) {
-        if (q < w) wbase = sat_add(wbase, s_woff[q]);
-        total = sat_add(total, s_woff[q]);
-    }
-    if (threadIdx.x == 0) {
-        const unsigned long long tag = gen << 34;
-        uint32_t prefix = 0;
-        if (tile > 0) {
-            __hip_atomic_store(status + tile, tag | kAggregate | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (int64_t t = tile - 1; t >= 0;) { // decoupled look-back
-                const unsigned long long v = __hip_atomic_load(status + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((v >> 34) != gen || !(v & (kAggregate | kInclusive))) { __builtin_amdgcn_s_sleep(1); continue; } // not published yet
-                prefix = sat_add(prefix, (uint32_t)v);
-                if (v & kInclusive) break;
-                --t;
-            }
-        }
-        __hip_atomic_store(status + tile, tag | kInclusive | sat_add(prefix, total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_prefix = prefix;
-        if (tile == n_tiles - 1) { // the layer's totals, and the capacity check
-            const int64_t edges = (int64_t)sat_add(prefix, total);
-            const int64_t items = n_dst + edges;
-            const bool ok = items <= item_cap && edges <= edge_cap;
-            indptr_local[n_dst] = edges;
-            if (!n_dst_dev) base[0] = n_dst;
-            base[kItemsOff] = ok ? items : 0;
-            base[kEdgesOff] = ok ? edges : 0;
-            pin[kPinEdges] = edges;
-            pin[kPinRefused] = ok ? 0 : 1;
-        }
-    }
-    __syncthreads();
-    uint32_t run = sat_add(s_prefix, sat_add(wbase, incl - c));
+    const TileScan ts = tile_scan<true>(status, gen, tile, n_tiles, c);
+    if (ts.last && threadIdx.x == 0) publish_ragged_layer(n_dst, (int64_t)ts.total, !n_dst_dev, item_cap, edge_cap, indptr_local, base, pin);
+    uint32_t run = ts.excl;
     for (int i = 0; i < kItems; ++i) {
         if (at + i < rows && first + i < n_dst) indptr_local[first + i] = (int64_t)run;
         run = sat_add(run, dg[i]);
@@ -715,50 +736,44 @@ __global__ __launch_bounds__(kBlock) void labor_insert_kernel(Graph g, const int
     if (n_items == 0) return;
     const uint32_t mask = table_size(n_items) - 1;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int gl = lane % GS, gbase = lane - gl;
-    const uint64_t gmask = ((1ull << GS) - 1ull) << gbase;
+    const auto [gl, gbase, gmask] = lane_group<GS>(lane);
     for (int64_t d0 = (int64_t)blockIdx.x * GPB; d0 < n_dst; d0 += (int64_t)gridDim.x * GPB) { // block-uniform
         if (threadIdx.x == 0) s_nhub = 0;
         __syncthreads();
         const int64_t d = d0 + (int)threadIdx.x / GS;
         const bool active = d < n_dst;
-        const int64_t v = active ? dst[d] : -1;
-        const bool okv = v >= 0 && v < g.num_nodes;
-        const int64_t start = okv ? g.indptr[v] : 0;
-        int64_t deg = okv ? g.indptr[v + 1] - start : 0;
+        const Row row = dst_row(g, dst, d, n_dst);
+        int64_t deg = row.deg; // 0 once the row is deferred
         if (deg > kHubDegree) { // at most GPB of them: the list cannot fill up
             if (gl == 0) s_hub[atomicAdd(&s_nhub, 1)] = d;
             deg = 0;
         }
-        if (active && gl == 0) hash_insert(tb, mask, v, d, slot_of_item);
+        if (active && gl == 0) hash_insert(tb, mask, row.v, d, slot_of_item);
         int64_t slot = deg > 0 ? indptr_local[d] : 0;
         int64_t longest = deg;
         for (int off = GS; off < 64; off <<= 1) longest = max(longest, __shfl_xor(longest, off));
         for (int64_t c0 = 0; c0 < longest; c0 += GS) { // wave-uniform
             const int64_t j = c0 + gl;
-            const int64_t t = j < deg ? g.indices[start + j] : -1;
+            const int64_t t = j < deg ? g.indices[row.start + j] : -1;
             const bool take = j < deg && labor_take(lkey, t, deg, fanout);
-            slot += labor_emit(take, gmask, lane, t, start + j, slot, n_dst, nbr, eid, tb, mask, slot_of_item);
+            slot += labor_emit(take, gmask, lane, t, row.start + j, slot, n_dst, nbr, eid, tb, mask, slot_of_item);
         }
         __syncthreads();
         const int n_hub = s_nhub;
         for (int i = 0; i < n_hub; ++i) { // block-uniform
             const int64_t hd = s_hub[i];
-            const int64_t hv = dst[hd];
-            const int64_t hstart = g.indptr[hv];
-            const int64_t hdeg = g.indptr[hv + 1] - hstart;
-            const int64_t seg = ((hdeg + kWavesPerBlock - 1) / kWavesPerBlock + 63) & ~63ll;
-            const int64_t from = min(hdeg, w * seg), to = min(hdeg, (w + 1) * seg);
-            const uint32_t mine = labor_wave_count(g, lkey, hstart, hdeg, fanout, from, to, lane);
+            const Row hub = listed_row(g, dst, hd);
+            const int64_t from = hub_share(hub.deg, w), to = hub_share(hub.deg, w + 1);
+            const uint32_t mine = labor_wave_count(g, lkey, hub.start, hub.deg, fanout, from, to, lane);
             if (lane == 0) s_wcnt[w] = mine;
             __syncthreads();
             int64_t hslot = indptr_local[hd];
             for (int q = 0; q < w; ++q) hslot += s_wcnt[q];
             for (int64_t c0 = from; c0 < to; c0 += 64) { // wave-uniform
                 const int64_t j = c0 + lane;
-                const int64_t t = j < to ? g.indices[hstart + j] : -1;
-                const bool take = j < to && labor_take(lkey, t, hdeg, fanout);
-                hslot += labor_emit(take, ~0ull, lane, t, hstart + j, hslot, n_dst, nbr, eid, tb, mask, slot_of_item);
+                const int64_t t = j < to ? g.indices[hub.start + j] : -1;
+                const bool take = j < to && labor_take(lkey, t, hub.deg, fanout);
+                hslot += labor_emit(take, ~0ull, lane, t, hub.start + j, hslot, n_dst, nbr, eid, tb, mask, slot_of_item);
             }
             __syncthreads(); // s_wcnt is rewritten for the next row
         }
@@ -775,11 +790,8 @@ __device__ __forceinline__ uint32_t first_flag(const uint32_t* __restrict__ slot
     return (s != 0xFFFFFFFFu && minpos[s] == (uint32_t)p) ? 1u : 0u;
 }
 
-// Single-pass scan: a block takes the next tile with an atomic ticket (so every predecessor of its tile has already started),
-// publishes the tile's count as an AGGREGATE, looks back over its predecessors until it meets an INCLUSIVE prefix, publishes its
-// own INCLUSIVE prefix and numbers its first occurrences.  Status words carry the launch's generation: nothing to reset.
-//   word = gen << 34 | status << 32 | value          status: 1 = aggregate, 2 = inclusive prefix
-// FULL (a fan-out -1 layer): n_dst and the item count come from the layer's device words (n_dst_dev = its base), and n_dst_value
+// First-occurrence flags -> positions in the source list, in one pass (tile_scan); the block of the last tile publishes the source
+// count.  FULL (a fan-out -1 layer): n_dst and the item count come from the layer's device words (n_dst_dev = its base), and n_dst_value
 // is the largest source count the fixed layers behind it accept: above it the next layers see 0 destination nodes.
 template <bool FULL>
 __global__ __launch_bounds__(kBlock) void scan_assign_kernel(const int64_t* __restrict__ dst, const int64_t* __restrict__ nbr,
@@ -788,16 +800,10 @@ __global__ __launch_bounds__(kBlock) void scan_assign_kernel(const int64_t* __re
                                                              unsigned long long* __restrict__ ticket, unsigned long long ticket_base,
                                                              unsigned long long gen, int64_t* __restrict__ src_nodes, int64_t* __restrict__ n_src_dev,
                                                              int64_t* __restrict__ n_src_host) {
-    __shared__ uint32_t s_woff[kWavesPerBlock];
-    __shared__ unsigned long long s_tile;
-    __shared__ uint32_t s_prefix;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t n_dst = FULL ? *n_dst_dev : n_dst_dev ? *n_dst_dev : n_dst_value;
+    const int64_t n_dst = FULL ? *n_dst_dev : layer_n_dst(n_dst_dev, n_dst_value);
     const int64_t n_items = FULL ? n_dst_dev[kItemsOff] : n_dst * (fanout + 1);
     const int64_t n_tiles = (n_items + kTile - 1) / kTile;
-    if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1ull) - ticket_base;
-    __syncthreads();
-    const int64_t tile = (int64_t)s_tile;
+    const int64_t tile = take_tile(ticket, ticket_base);
     if (tile >= n_tiles) { // launched for the capacity; the block that would own the first unused tile reports an empty layer
         if (tile == 0 && threadIdx.x == 0) {
             *n_src_dev = 0;
@@ -810,48 +816,15 @@ __global__ __launch_bounds__(kBlock) void scan_assign_kernel(const int64_t* __re
     uint32_t fl[kItems];
     uint32_t c = 0;
     for (int i = 0; i < kItems; ++i) { fl[i] = first_flag(slot_of_item, tb.minpos, base + i, n_items); c += fl[i]; }
-    uint32_t incl = c; // inclusive scan inside the wave
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
+    const TileScan ts = tile_scan<false>(status, gen, tile, n_tiles, c);
+    if (ts.last && threadIdx.x == 0) { // layer l+1 (and the host) read the number of source nodes from here
+        const int64_t n_src = (int64_t)ts.total;
+        const bool over = FULL && n_src > n_dst_value;
+        *n_src_dev = over ? 0 : n_src;
+        *n_src_host = n_src;
+        if constexpr (FULL) n_src_host[kPinOver] = over ? 1 : 0;
     }
-    if (lane == 63) s_woff[w] = incl;
-    __syncthreads();
-    uint32_t wbase = 0, total = 0;
-    for (int q = 0; q < kWavesPerBlock; ++q) {
-        if (q < w) wbase += s_woff[q];
-        total += s_woff[q];
-    }
-    if (threadIdx.x == 0) {
-        const unsigned long long tag = gen << 34;
-        uint32_t prefix = 0;
-        if (tile > 0) {
-            __hip_atomic_store(status + tile, tag | kAggregate | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (int64_t t = tile - 1; t >= 0;) { // decoupled look-back
-                const unsigned long long v = __hip_atomic_load(status + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((v >> 34) != gen || !(v & (kAggregate | kInclusive))) { __builtin_amdgcn_s_sleep(1); continue; } // not published yet
-                prefix += (uint32_t)v;
-                if (v & kInclusive) break;
-                --t;
-            }
-        }
-        __hip_atomic_store(status + tile, tag | kInclusive | (prefix + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_prefix = prefix;
-        if (tile == n_tiles - 1) { // layer l+1 (and the host) read the number of source nodes from here
-            if constexpr (FULL) {
-                const int64_t n_src = (int64_t)(prefix + total);
-                const bool over = n_src > n_dst_value;
-                *n_src_dev = over ? 0 : n_src;
-                *n_src_host = n_src;
-                n_src_host[kPinOver] = over ? 1 : 0;
-            } else {
-                *n_src_dev = (int64_t)(prefix + total);
-                *n_src_host = (int64_t)(prefix + total);
-            }
-        }
-    }
-    __syncthreads();
-    uint32_t run = s_prefix + wbase + incl - c;
+    uint32_t run = ts.excl;
     for (int i = 0; i < kItems; ++i) {
         if (fl[i]) {
             const int64_t p = base + i;
@@ -870,7 +843,7 @@ template <bool FULL, bool NEXT_FULL>
 __global__ __launch_bounds__(kBlock) void relabel_clear_kernel(const int64_t* __restrict__ n_dst_dev, int64_t n_dst_value, int fanout, const uint32_t* __restrict__ slot_of_item,
                                                                Table tb, int32_t* __restrict__ nbr_local, const int64_t* __restrict__ next_n_dst_dev,
                                                                int next_fanout, int64_t next_items) {
-    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
+    const int64_t n_dst = layer_n_dst(n_dst_dev, n_dst_value);
     const int64_t n_nbr = FULL ? n_dst_dev[kEdgesOff] : n_dst * fanout;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n_nbr; q += (int64_t)gridDim.x * blockDim.x) {
         const uint32_t s = slot_of_item[n_dst + q];
@@ -980,7 +953,7 @@ template <bool FULL>
 __global__ __launch_bounds__(kBlock) void bucket_reindex_kernel(const int64_t* __restrict__ n_dst_dev, int64_t n_dst_value, int fanout,
                                                                 const uint32_t* __restrict__ new_of_old, int32_t* __restrict__ nbr_local,
                                                                 int32_t* __restrict__ dst_in_src) {
-    const int64_t n_dst = n_dst_dev ? *n_dst_dev : n_dst_value;
+    const int64_t n_dst = layer_n_dst(n_dst_dev, n_dst_value);
     const int64_t n_nbr = FULL ? n_dst_dev[kEdgesOff] : n_dst * fanout;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n_nbr; q += (int64_t)gridDim.x * blockDim.x) {
         const int32_t o = nbr_local[q];
