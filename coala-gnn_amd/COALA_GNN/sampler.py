@@ -14,12 +14,51 @@ from COALA_GNN_Pybind import _capi, current_stream
 from .block_ops import (_GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
                         _MeanAggregateCSR, _RelSum, _RelSumCSR, _WeightedSum, _WeightedSumCSR)
 
-__all__ = ["NeighborSampler", "LaborSampler", "CSCGraph", "Block", "ITEM_LIMIT", "EID"]
+__all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "sort_csc_by_etype", "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT",
+           "EID"]
 
 _lib = _capi.load()
 
 EID = "_ID"   # DGL's dgl.EID: block.edata[EID] is the position of every sampled edge in the graph's CSC `indices` array
 ITEM_LIMIT = 8192 * 1024   # items (destination nodes + neighbour slots) one layer may hold (coala_sampler.hip: kMaxTiles * kTile)
+
+
+def sort_csc_by_etype(indptr, indices, etype):
+    """Sort the in-edges of every node by edge type, DGL's dgl.sort_csc_by_tag: -> (indices_sorted, etype_sorted, perm).  Stable by
+    (row, type): edges of one type keep their CSC order.  perm (int64 [E]) maps new positions to old, indices_sorted = indices[perm],
+    so any other per-edge data is carried along as edata[key][perm].  Plain torch on the tensors' device; indptr is unchanged.
+    RelNeighborSampler needs a graph in this order."""
+    if etype.dim() != 1 or etype.numel() != indices.numel():
+        raise ValueError(f"edge types must have shape ({indices.numel()},) in CSC order, got {tuple(etype.shape)}")
+    if etype.is_floating_point() or etype.is_complex() or etype.dtype == torch.bool:
+        raise ValueError("edge types must be an integer tensor")
+    deg = indptr[1:] - indptr[:-1]
+    rows = torch.repeat_interleave(torch.arange(deg.numel(), device=indptr.device), deg, output_size=indices.numel())
+    by_type = torch.sort(etype.to(indptr.device), stable=True).indices
+    perm = by_type[torch.sort(rows[by_type], stable=True).indices]
+    return indices[perm], etype[perm], perm
+
+
+def check_etype_sorted(indptr, etype, num_rels, name="etype"):
+    """What RelNeighborSampler asks of a graph's edge types, on the tensors' device: an integer tensor of num_edges values in
+    [0, num_rels), non-decreasing inside every row of the CSC.  ValueError (naming sort_csc_by_etype) otherwise."""
+    E = int(indptr[-1].item()) if indptr.numel() else 0
+    if not isinstance(etype, torch.Tensor) or etype.is_floating_point() or etype.is_complex() or etype.dtype == torch.bool:
+        raise ValueError(f"edata[{name!r}]: edge types must be an integer tensor")
+    if etype.dim() != 1 or etype.numel() != E:
+        raise ValueError(f"edata[{name!r}]: edge types must have shape ({E},) in CSC order, got {tuple(etype.shape)}")
+    if E == 0:
+        return
+    t = etype.to(indptr.device)
+    if bool(((t < 0) | (t >= num_rels)).any()):
+        raise ValueError(f"edata[{name!r}]: edge types must lie in [0, {num_rels}) (num_rels={num_rels})")
+    drop = t[1:] < t[:-1]                                  # drop[p - 1]: the type falls from position p - 1 to p
+    starts = indptr[1:-1]
+    starts = starts[(starts > 0) & (starts < E)]           # ... which it may where a row starts
+    drop[starts - 1] = False
+    if bool(drop.any()):
+        raise ValueError(f"edata[{name!r}]: edge types must be non-decreasing inside every row of the CSC; sort the graph with "
+                         f"COALA_GNN.sampler.sort_csc_by_etype(indptr, indices, etype)")
 
 
 class CSCGraph(object):
@@ -36,6 +75,7 @@ class CSCGraph(object):
         self.ndata = dict(ndata or {})
         self.edata = dict(edata or {})
         self._weights = {}   # edata key -> (the entry, its version, the validated fp32 device copy)
+        self._etypes = {}    # edata key -> (the entry, its version, num_rels, the validated int32 device copy)
         self._max_in_degree = None
         self._h = C.c_void_p()
         dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
@@ -68,7 +108,23 @@ class CSCGraph(object):
         self._weights[key] = (t, t._version, w)
         return w
 
+    def edge_types(self, key, num_rels):
+        """edata[key] as a contiguous int32 tensor on the graph's device for RelNeighborSampler, checked once on the device
+        (check_etype_sorted: num_edges values in [0, num_rels), non-decreasing inside every row) and cached until the entry is replaced or
+        modified in place, or close().  KeyError when the key is missing, ValueError (naming sort_csc_by_etype) when bad."""
+        if key not in self.edata:
+            raise KeyError(f"edata has no {key!r}: the edge types of RelNeighborSampler(etype={key!r}) (keys: {sorted(self.edata)})")
+        t = self.edata[key]
+        hit = self._etypes.get(key)
+        if hit is not None and hit[0] is t and hit[1] == t._version and hit[2] == num_rels:
+            return hit[3]
+        check_etype_sorted(self.indptr, t, num_rels, key)
+        t32 = t.to(device=self.device, dtype=torch.int32).contiguous()
+        self._etypes[key] = (t, t._version, num_rels, t32)
+        return t32
+
     def close(self):
+        self._etypes = {}
         if getattr(self, "_h", None):
             _lib.coala_sampler_destroy(self._h)
             self._h = C.c_void_p()
@@ -500,7 +556,7 @@ class NeighborSampler(object):
         for f in rev:
             cap = caps[-1]
             if ragged(f):   # a LABOR layer takes ~cap * f edges, but only the device knows: the bound is the full layer's
-                edge_caps.append(min(cap * g.max_in_degree, ITEM_LIMIT))
+                edge_caps.append(min(cap * self._row_bound(g, f), ITEM_LIMIT))
                 src_caps.append(min(cap + edge_caps[-1], ITEM_LIMIT))
                 bounded = True
             elif bounded:
@@ -535,6 +591,10 @@ class NeighborSampler(object):
     def _ragged(self, f):
         """Whether a layer of fan-out f gives a ragged (CSR) block, whose size only the device knows."""
         return f == -1
+
+    def _row_bound(self, g, f):
+        """The most edges a row of a ragged layer of fan-out f can hold, known on the host."""
+        return g.max_in_degree
 
     def _enqueue(self, g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket):
         """The C ABI call of sample_begin, on the current stream."""
@@ -640,3 +700,59 @@ class LaborSampler(NeighborSampler):
             deg = indptr[1:] - indptr[:-1]
             return torch.repeat_interleave(1.0 / deg.to(torch.float32), deg, output_size=n_edges)
         return dict(edata_lazy={"edge_weights": edge_weights})
+
+
+class RelNeighborSampler(NeighborSampler):
+    """Neighbour sampling with a fan-out per edge type, what DGL's NeighborSampler does on a heterograph (on a homogenised graph:
+    dgl.sort_csc_by_tag, then sample_etype_neighbors(etype_sorted=True)), in place of NeighborSampler: same interface, same loader.
+    The graph carries its edge types in graph.edata[etype] (any integer dtype, CSC order, values in [0, num_rels)), and the in-edges of
+    every node must be sorted by type -- sort_csc_by_etype does that.  The first sample from a graph checks it once on the device and
+    keeps an int32 copy on the CSCGraph (until close()); a graph that fails raises ValueError before anything is launched.
+
+    fanouts: one entry per layer (model order, as NeighborSampler's), each an int applied to every relation (as DGL does) or a
+    sequence of num_rels ints.  Per relation: 0 takes nothing, -1 every in-edge of that type, f in 1..32 at most f of them, drawn
+    without replacement (all when the node has at most f); a layer needs one non-zero entry.  The rule is in the header of
+    coala_sampler.hip: relations draw from streams of their own, and with num_rels == 1 a row holds the edges NeighborSampler draws.
+
+    Every block is ragged (Block.indptr / Block.indices, nbr is None); a row lists its edges in ascending CSC position, so grouped by
+    relation.  With edge_ids (the default here: RelGraphConv reads block.edata[etype] through them) the blocks carry edata.
+    self.fanouts holds the per-layer totals -- the sum of a layer's fan-outs, or -1 when one of them is -1.  A layer without a -1 holds at
+    most min(total, max_in_degree) edges per row, which sizes its buffers; one with a -1 is sized as a full layer.  The loader sizes its
+    fetch buffers from its fan_out argument and knows nothing of relations: pass it these totals (sampler.fanouts)."""
+
+    def __init__(self, fanouts, num_rels, etype="etype", seed=0, bucket_by_owner=0, edge_ids=True, prob=None):
+        if prob is not None:
+            raise ValueError("RelNeighborSampler: prob= (weighted draws per relation) is not supported")
+        if isinstance(num_rels, bool) or not isinstance(num_rels, int) or not 1 <= num_rels <= 64:
+            raise ValueError(f"num_rels {num_rels!r}: 1..64 relations")
+        fanouts = list(fanouts)
+        super().__init__([-1] * len(fanouts), seed=seed, bucket_by_owner=bucket_by_owner, edge_ids=edge_ids)
+        self.num_rels, self.etype = num_rels, etype
+        self.rel_fanouts = []
+        for f in fanouts:
+            per_rel = [int(x) for x in f] if hasattr(f, "__iter__") else [int(f)] * num_rels
+            if len(per_rel) != num_rels:
+                raise ValueError(f"fan-outs {per_rel}: a layer takes one int, or one per relation ({num_rels})")
+            for x in per_rel:
+                if not -1 <= x <= 32:
+                    raise ValueError(f"fan-out {x}: each fan-out must be 0..32, or -1 for every in-edge of the relation")
+            if not any(per_rel):
+                raise ValueError(f"fan-outs {per_rel}: a layer must take edges of at least one relation")
+            self.rel_fanouts.append(per_rel)
+        self.fanouts = [-1 if -1 in per_rel else sum(per_rel) for per_rel in self.rel_fanouts]
+
+    def _ragged(self, f):
+        return True
+
+    def _row_bound(self, g, f):
+        return g.max_in_degree if f == -1 else min(f, g.max_in_degree)
+
+    def _enqueue(self, g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket):
+        types = g.edge_types(self.etype, self.num_rels)   # raises before any launch
+        lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr(), src_caps[l], edge_caps[l])
+                                         for l in range(L)])
+        eid_p = (C.c_void_p * L)(*[t.data_ptr() for t in eid]) if eid is not None else None
+        rel_fan = (C.c_int32 * (L * self.num_rels))(*[f for per_rel in reversed(self.rel_fanouts) for f in per_rel])
+        _capi.check(_lib.coala_sampler_sample_layers_rel(g._h, seeds.data_ptr(), n, rel_fan, self.num_rels, L, self.seed, st, lay, types.data_ptr(),
+                                                         eid_p, None, None, C.byref(bk) if bk is not None else None, C.byref(ticket),
+                                                         current_stream()))

@@ -75,6 +75,30 @@
 //   prefix, stored with their edge id when asked and hash-inserted; a hub row again on the whole block), then scan_assign /
 //   relabel_clear in their full-layer instantiations and the bucketing kernels, unchanged.  No launch, memset or host wait is added.
 //
+// Relation layers (DGL's NeighborSampler on a heterograph: a fan-out per edge type; on a homogenised graph dgl.sort_csc_by_tag +
+// sample_etype_neighbors(etype_sorted=True); coala_sampler_sample_layers_rel).  The graph has num_rels relations (1..64) and an int32
+// type per edge in CSC order, NON-DECREASING INSIDE EVERY ROW (the caller's duty; not verified here).  The in-edges of relation r of
+// node v are then one segment [s_r, s_r + deg_r) of [indptr[v], indptr[v+1]): s_r is the lower bound of r among the row's types (s_0
+// the row's start), s_r + deg_r the lower bound of r + 1.  A layer has one fan-out per relation, f_r in {-1, 0, 1..32}:
+//   * f_r == 0: the relation contributes nothing;
+//   * f_r == -1 or deg_r <= f_r: every edge of the segment is taken;
+//   * otherwise f_r distinct positions of the segment, relative to s_r, by sample_insert_kernel's Floyd loop with deg := deg_r,
+//     fanout := f_r and r(j) = splitmix64(sample_key(seed, step, layer, v) + 64 r + j), t = mulhi64(r(j), deg_r - f_r + j + 1): the
+//     counters 64 r + j (j < 32) never collide between relations, and relation 0 replays the uniform sampler's draws;
+//   * the block is ragged, as a LABOR layer's: taken edges of a row in ascending CSC position (hence grouped by relation), rows in
+//     destination order, indptr_local int64[n_dst + 1], nbr_local int32[E], edge ids when asked; source list, first appearance, item
+//     limit (checked on the device), refusal and bucketing are those of a full layer; an out-of-range destination id gives an empty
+//     row.  A layer whose fan-outs are all -1 IS the full layer (it runs degree_scan / full_insert and reads no types); with one
+//     relation and fan-out f a row holds the edges NeighborSampler([f]) draws at the same seed and step, in ascending order.
+//   * types that are not sorted give rows that are not what the rule says, but nothing is read or written out of bounds: every
+//     boundary is a position inside the row, a segment of negative length counts as empty, and both passes compute the same counts.
+//   Launches: rel_count_scan stands where degree_scan / labor_count_scan stand (a lane group per row, lane r finds the end of
+//   relation r by binary search over the types: a row is never walked, so there is no hub list; then the tile scan and
+//   publish_ragged_layer of the other two), rel_insert where full_insert / labor_insert stand (the same boundaries again; per drawn
+//   relation the Floyd draws with a lane per candidate and the picks sorted inside the group; a taken-whole segment copied in lane
+//   strides, one of more than kHubDegree edges by the whole block), then scan_assign / relabel_clear in their full-layer
+//   instantiations and the bucketing kernels, unchanged.  The fan-outs travel by value in the kernel arguments.
+//
 // Edge ids (coala_sampler_sample_layers_edge_ids), added to the contract of every layer kind above: with edge_ids_out[l] non-null the
 // kernel that reads a neighbour also stores where it read it, eid[slot] = indptr[v] + j (the edge's position in `indices`), int64,
 // laid out like the layer's nbr_local ([n_dst, f] or [E]); -1 where the slot holds no neighbour.  It is one 8-byte vector store from
@@ -535,6 +559,29 @@ __device__ __forceinline__ void publish_ragged_layer(int64_t n_dst, int64_t edge
     pin[kPinRefused] = ok ? 0 : 1;
 }
 
+// A tile of `rows` destination nodes (row0 ..) whose edge counts sit in LDS (s_cnt, complete behind a barrier): degree_scan_kernel's
+// scan over them -> indptr_local and, from the last tile, the layer's totals.  The tail of labor_count_scan_kernel and rel_count_scan_kernel.
+__device__ __forceinline__ void scan_row_counts(const uint32_t* s_cnt, int rows, int64_t row0, int64_t n_dst, int64_t tile, int64_t n_tiles,
+                                                unsigned long long* __restrict__ status, unsigned long long gen, bool first_layer,
+                                                int64_t item_cap, int64_t edge_cap, int64_t* __restrict__ indptr_local,
+                                                int64_t* __restrict__ base, int64_t* __restrict__ pin) {
+    const int at = (int)threadIdx.x * kItems;
+    const int64_t first = row0 + at;
+    uint32_t dg[kItems];
+    uint32_t c = 0;
+    for (int i = 0; i < kItems; ++i) {
+        dg[i] = (at + i < rows && first + i < n_dst) ? s_cnt[at + i] : 0;
+        c = sat_add(c, dg[i]);
+    }
+    const TileScan ts = tile_scan<true>(status, gen, tile, n_tiles, c);
+    if (ts.last && threadIdx.x == 0) publish_ragged_layer(n_dst, (int64_t)ts.total, first_layer, item_cap, edge_cap, indptr_local, base, pin);
+    uint32_t run = ts.excl;
+    for (int i = 0; i < kItems; ++i) {
+        if (at + i < rows && first + i < n_dst) indptr_local[first + i] = (int64_t)run;
+        run = sat_add(run, dg[i]);
+    }
+}
+
 // Full layer, pass 1: degrees of the destination nodes -> indptr_local (exclusive scan) and E, by tile_scan.  The block of the last
 // tile checks the layer against its capacities and publishes n_dst (first layer), the item and edge counts (publish_ragged_layer).
 __global__ __launch_bounds__(kBlock) void degree_scan_kernel(Graph g, const int64_t* __restrict__ dst, const int64_t* __restrict__ n_dst_dev,
@@ -684,22 +731,7 @@ __global__ __launch_bounds__(kBlock) void labor_count_scan_kernel(Graph g, const
         }
         __syncthreads();
     }
-    // ---- degree_scan_kernel's scan over the counts
-    const int at = (int)threadIdx.x * kItems;
-    const int64_t first = row0 + at;
-    uint32_t dg[kItems];
-    uint32_t c = 0;
-    for (int i = 0; i < kItems; ++i) {
-        dg[i] = (at + i < rows && first + i < n_dst) ? s_cnt[at + i] : 0;
-        c = sat_add(c, dg[i]);
-    }
-    const TileScan ts = tile_scan<true>(status, gen, tile, n_tiles, c);
-    if (ts.last && threadIdx.x == 0) publish_ragged_layer(n_dst, (int64_t)ts.total, !n_dst_dev, item_cap, edge_cap, indptr_local, base, pin);
-    uint32_t run = ts.excl;
-    for (int i = 0; i < kItems; ++i) {
-        if (at + i < rows && first + i < n_dst) indptr_local[first + i] = (int64_t)run;
-        run = sat_add(run, dg[i]);
-    }
+    scan_row_counts(s_cnt, rows, row0, n_dst, tile, n_tiles, status, gen, !n_dst_dev, item_cap, edge_cap, indptr_local, base, pin);
 }
 
 // Edge at position j of row d passed the test (take) or not: the survivors of the lanes in `among` go to slots slot0 + rank, rank by
@@ -777,6 +809,156 @@ __global__ __launch_bounds__(kBlock) void labor_insert_kernel(Graph g, const int
             }
             __syncthreads(); // s_wcnt is rewritten for the next row
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- relation layers
+constexpr int kMaxRels = 64;
+constexpr int kRelHubList = kBlock; // a block step holds kBlock / GS rows of at most GS relations each: its deferred segments always fit
+
+struct RelFan { // the fan-outs of one layer, by value in the kernel arguments
+    int8_t f[kMaxRels]; // -1, 0, 1..32; 0 past num_rels
+    int32_t num_rels;
+};
+
+struct RelSeg { // relation `gl` of a row, on lane gl of the row's group: its in-edges [s, s + deg) and how many of them the layer takes
+    int64_t s, deg, take;
+};
+
+// First position in [lo, hi) whose type is not below `key` (hi when there is none).
+__device__ __forceinline__ int64_t type_lower_bound(const int32_t* __restrict__ etype, int64_t lo, int64_t hi, int32_t key) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (etype[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Lane gl < num_rels of the group finds where relation gl ends; its start is the end of relation gl - 1 (the row's start for gl = 0).
+// Every boundary lies inside the row whatever the types hold; a segment of negative length (types not sorted) counts as empty.
+// Every lane of the wave must call it.
+__device__ __forceinline__ RelSeg rel_segment(const int32_t* __restrict__ etype, const RelFan& fan, const Row& row, int gl, int gbase) {
+    const bool mine = gl < fan.num_rels;
+    const int64_t row_end = row.start + row.deg;
+    const int64_t end = mine ? type_lower_bound(etype, row.start, row_end, gl + 1) : row_end;
+    const int64_t prev = __shfl(end, gbase + (gl > 0 ? gl - 1 : 0));
+    const int64_t s = gl > 0 ? prev : row.start;
+    const int64_t deg = mine ? max(end - s, (int64_t)0) : 0;
+    const int f = fan.f[gl];
+    return {s, deg, (!mine || f == 0) ? 0 : (f < 0 || deg <= f) ? deg : (int64_t)f};
+}
+
+// Relation layer, pass 1, where degree_scan_kernel stands: the number of taken edges of every destination node -> indptr_local
+// (exclusive scan) and E.  Tiles of `rows` destination nodes as in labor_count_scan_kernel; GS lanes per row (GS >= num_rels), the
+// row's count is the sum of its relations' takes.  No row is walked: a hub costs its binary searches.
+template <int GS>
+__global__ __launch_bounds__(kBlock) void rel_count_scan_kernel(Graph g, const int32_t* __restrict__ etype, RelFan fan, const int64_t* __restrict__ dst,
+                                                                const int64_t* __restrict__ n_dst_dev, int64_t n_dst_value, int rows,
+                                                                int64_t* __restrict__ base, unsigned long long* __restrict__ status,
+                                                                unsigned long long* __restrict__ ticket, unsigned long long ticket_base,
+                                                                unsigned long long gen, int64_t* __restrict__ indptr_local, int64_t item_cap,
+                                                                int64_t edge_cap, int64_t* __restrict__ pin) {
+    constexpr int GPB = kBlock / GS;
+    __shared__ uint32_t s_cnt[kTile];
+    const int lane = threadIdx.x & 63;
+    const int64_t n_dst = layer_n_dst(n_dst_dev, n_dst_value);
+    const int64_t n_tiles = n_dst > 0 ? (n_dst + rows - 1) / rows : 1; // tile 0 always runs: it publishes an empty layer too
+    const int64_t tile = take_tile(ticket, ticket_base);
+    if (tile >= n_tiles) return;
+    const int64_t row0 = tile * rows;
+    const auto [gl, gbase, gmask] = lane_group<GS>(lane);
+    for (int r = (int)threadIdx.x / GS; r < rows; r += GPB) { // wave-uniform trip count: rows is a multiple of GPB
+        const Row row = dst_row(g, dst, row0 + r, n_dst);
+        int64_t n = rel_segment(etype, fan, row, gl, gbase).take;
+        for (int off = 1; off < GS; off <<= 1) n += __shfl_xor(n, off);
+        if (gl == 0) s_cnt[r] = n > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)n;
+    }
+    __syncthreads();
+    scan_row_counts(s_cnt, rows, row0, n_dst, tile, n_tiles, status, gen, !n_dst_dev, item_cap, edge_cap, indptr_local, base, pin);
+}
+
+// Relation layer, pass 2, where full_insert_kernel stands: item p < n_dst is destination node p; item n_dst + q is taken edge q of the
+// layer.  GS lanes per row (GS >= num_rels and >= every fan-out) find the boundaries again; relation r's taken edges start at
+// indptr_local[d] + the takes of the relations before it.  Then relation by relation (the fan-out is the layer's, so the branches are
+// wave-uniform): a drawn relation runs sample_insert_kernel's Floyd loop on the segment with a lane per candidate and sorts the picks
+// over the group's lanes (rows with deg_r <= f_r hold positions 0 .. deg_r - 1 there); a -1 relation is copied in lane strides, and
+// a segment of more than kHubDegree edges goes on the block's list and is copied by all its threads afterwards.  A refused layer
+// (0 items) does nothing.
+template <int GS>
+__global__ __launch_bounds__(kBlock) void rel_insert_kernel(Graph g, const int32_t* __restrict__ etype, RelFan fan, const int64_t* __restrict__ dst,
+                                                            const int64_t* __restrict__ base, const int64_t* __restrict__ indptr_local,
+                                                            uint64_t seed, uint64_t step, int layer, int64_t* __restrict__ nbr, Table tb,
+                                                            uint32_t* __restrict__ slot_of_item, int64_t* __restrict__ eid) {
+    constexpr int GPB = kBlock / GS;
+    __shared__ int64_t s_hub[kRelHubList][3]; // first CSC position, length, first slot
+    __shared__ int s_nhub;
+    const int64_t n_dst = base[0];
+    const int64_t n_items = base[kItemsOff];
+    if (n_items == 0) return;
+    const uint32_t mask = table_size(n_items) - 1;
+    const int lane = threadIdx.x & 63;
+    const auto [gl, gbase, gmask] = lane_group<GS>(lane);
+    // slot q of the layer takes the edge at CSC position e: the neighbour is stored (scan_assign reads it back), its edge id when asked
+    const auto emit = [&](int64_t q, int64_t e) {
+        const int64_t t = g.indices[e];
+        nbr[q] = t;
+        if (eid) eid[q] = e;
+        hash_insert(tb, mask, t, n_dst + q, slot_of_item);
+    };
+    for (int64_t d0 = (int64_t)blockIdx.x * GPB; d0 < n_dst; d0 += (int64_t)gridDim.x * GPB) { // block-uniform
+        if (threadIdx.x == 0) s_nhub = 0;
+        __syncthreads();
+        const int64_t d = d0 + (int)threadIdx.x / GS;
+        const Row row = dst_row(g, dst, d, n_dst);
+        if (d < n_dst && gl == 0) hash_insert(tb, mask, row.v, d, slot_of_item);
+        const RelSeg sg = rel_segment(etype, fan, row, gl, gbase);
+        int64_t incl = sg.take; // inclusive scan of the takes over the group's lanes
+        for (int off = 1; off < GS; off <<= 1) {
+            const int64_t v = __shfl_up(incl, off);
+            if (gl >= off) incl += v;
+        }
+        const int64_t slot0 = (row.deg > 0 ? indptr_local[d] : 0) + incl - sg.take;
+        const uint64_t key = sample_key(seed, step, layer, (uint64_t)row.v);
+        for (int r = 0; r < fan.num_rels; ++r) { // wave-uniform, and so is every branch on f
+            const int f = fan.f[r];
+            if (f == 0) continue;
+            const int64_t s_r = __shfl(sg.s, gbase + r), deg_r = __shfl(sg.deg, gbase + r), q_r = __shfl(slot0, gbase + r);
+            if (f < 0) { // taken whole, whatever its length
+                int at = -1;
+                if (gl == 0 && deg_r > kHubDegree) at = atomicAdd(&s_nhub, 1);
+                at = __shfl(at, gbase);
+                if (at >= 0) { // deferred to the whole block
+                    if (gl == 0) {
+                        s_hub[at][0] = s_r;
+                        s_hub[at][1] = deg_r;
+                        s_hub[at][2] = q_r;
+                    }
+                } else {
+                    for (int64_t j = gl; j < deg_r; j += GS) emit(q_r + j, s_r + j);
+                }
+                continue;
+            }
+            // candidate of lane c = gl (Floyd step j = deg_r - f + c), positions relative to s_r
+            const bool drawn = deg_r > f;
+            const int64_t t = (drawn && gl < f) ? (int64_t)__umul64hi(splitmix64(key + (uint64_t)(kMaxRels * r + gl)), (uint64_t)(deg_r - f + gl + 1)) : -1;
+            int64_t chosen = -2;
+            for (int c = 0; c < f; ++c) {
+                const int64_t tc = __shfl(t, gbase + c);
+                const uint64_t dupm = __ballot(gl < c && chosen == tc) & gmask;
+                if (gl == c) chosen = dupm ? (deg_r - f + c) : tc;
+            }
+            unsigned long long pk = (unsigned long long)kNoPos; // lane i ends up with the i-th smallest pick
+            if (gl < f && (drawn || gl < deg_r)) pk = (unsigned long long)(drawn ? chosen : (int64_t)gl);
+            int64_t unused = 0;
+            group_sort<GS>(pk, unused, gl);
+            if (gl < min(deg_r, (int64_t)f)) emit(q_r + gl, s_r + (int64_t)pk);
+        }
+        __syncthreads();
+        const int n_hub = s_nhub;
+        for (int i = 0; i < n_hub; ++i) // block-uniform
+            for (int64_t j = threadIdx.x; j < s_hub[i][1]; j += kBlock) emit(s_hub[i][2] + j, s_hub[i][0] + j);
+        __syncthreads(); // the list is rewritten in the next step
     }
 }
 
@@ -969,9 +1151,10 @@ struct coala_sampler {
     struct RingInfo { // what coala_sampler_wait_layers needs of a call to read its counts and explain a refusal
         int n_layers = 0, n_parts = 0;
         bool labor = false; // fixed fan-outs are LABOR layers: every layer of the call is ragged
+        bool rel = false;   // relation layers (a fan-out per relation): every layer of the call is ragged
         int64_t n_seeds = 0;
-        bool ragged(int l) const { return labor || fanouts[l] == -1; } // CSR block, sizes known on the device only
-        int32_t fanouts[COALA_SAMPLER_MAX_LAYERS] = {};
+        bool ragged(int l) const { return labor || rel || fanouts[l] == -1; } // CSR block, sizes known on the device only
+        int32_t fanouts[COALA_SAMPLER_MAX_LAYERS] = {}; // of a relation call: -1 for a layer whose fan-outs are all -1, else 0
         int64_t src_cap[COALA_SAMPLER_MAX_LAYERS] = {}, edge_cap[COALA_SAMPLER_MAX_LAYERS] = {};
     };
     int device = 0;
@@ -1025,7 +1208,7 @@ int ilog2_exact(uint64_t v) {
 }
 
 int check_call(const coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
-               const coala_sampler_layer_t* layers, const coala_sampler_bucketing_t* bucketing, bool labor) {
+               const coala_sampler_layer_t* layers, const coala_sampler_bucketing_t* bucketing, bool labor, bool rel) {
     if (!s || (!seeds && n_seeds > 0) || !fanouts) return fail(COALA_EINVAL, "null argument");
     if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
     if (n_seeds < 0 || n_seeds > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad n_seeds");
@@ -1035,9 +1218,9 @@ int check_call(const coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, 
     if (!layers) return fail(COALA_EINVAL, "null argument");
     for (int l = 0; l < n_layers; ++l) {
         const int f = fanouts[l];
-        if (f != kFull && (f < 1 || f > 32)) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (or -1: every in-edge)", f);
+        if (!rel && f != kFull && (f < 1 || f > 32)) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (or -1: every in-edge)", f);
         const coala_sampler_layer_t& y = layers[l];
-        if (!y.src_nodes || !y.nbr_local || ((labor || f == kFull) && !y.indptr_local)) return fail(COALA_EINVAL, "layer %d: null buffer", l);
+        if (!y.src_nodes || !y.nbr_local || ((labor || rel || f == kFull) && !y.indptr_local)) return fail(COALA_EINVAL, "layer %d: null buffer", l);
         if (y.src_cap < 0 || y.edge_cap < 0) return fail(COALA_EINVAL, "layer %d: negative capacity", l);
     }
     return COALA_OK;
@@ -1136,6 +1319,8 @@ struct Plan {
     int64_t* const* edge_ids; // null, or per layer: null or device int64[edge_cap], the CSC position of every neighbour slot
     hipStream_t st;
     bool layer_dependency; // LABOR (info.labor): one key for every layer of the call
+    const RelFan* rel;     // relation layers (info.rel): the fan-outs of every layer, and the int32 edge types (CSC order)
+    const int32_t* etype;
     RingInfo info;        // n_seeds, the fan-outs, n_parts and the caller's capacities
     // layer l has at most dst_cap[l] dst nodes, items_cap[l] items (dst nodes + neighbour slots), nbr_cap[l] neighbour entries
     int64_t dst_cap[COALA_SAMPLER_MAX_LAYERS], items_cap[COALA_SAMPLER_MAX_LAYERS], nbr_cap[COALA_SAMPLER_MAX_LAYERS];
@@ -1148,6 +1333,7 @@ struct Plan {
 // layers behind it are checked on the device against the caller's capacities and the item limit.
 int plan_call(Plan& p, int64_t n_seeds, const int32_t* fanouts, int n_layers, int n_parts, bool labor) {
     p.info.labor = labor;
+    p.info.rel = p.rel != nullptr;
     p.info.n_layers = n_layers;
     p.info.n_parts = n_parts;
     p.info.n_seeds = n_seeds;
@@ -1161,7 +1347,7 @@ int plan_call(Plan& p, int64_t n_seeds, const int32_t* fanouts, int n_layers, in
         p.info.src_cap[l] = y.src_cap;
         p.info.edge_cap[l] = y.edge_cap;
         p.dst_cap[l] = cap;
-        if (labor || f == kFull) {
+        if (p.info.ragged(l)) {
             host_bound = false;
             p.items_cap[l] = std::min<int64_t>(kItemLimit, y.src_cap);
             p.nbr_cap[l] = std::min<int64_t>(kItemLimit, y.edge_cap);
@@ -1229,17 +1415,34 @@ int next_gen(coala_sampler_t* s, hipStream_t st) {
     return COALA_OK;
 }
 
-// Ragged layer l: degrees (full) or counts of taken edges (LABOR) -> indptr_local, and its edge and item counts into its device words.
+// Lanes per destination row of the relation kernels: one per relation, and one per candidate of the largest fan-out (dispatch_group's
+// argument: it gives a group of more lanes than that).
+int rel_group(const RelFan& fan) {
+    int need = fan.num_rels;
+    for (int r = 0; r < fan.num_rels; ++r) need = std::max<int>(need, fan.f[r]);
+    return need - 1;
+}
+
+// Ragged layer l: degrees (full) or counts of taken edges (LABOR, relations) -> indptr_local, and its edge and item counts into its
+// device words.
 int degree_scan(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, const int64_t* n_dst_dev) {
     if (int rc = next_gen(s, p.st)) return rc;
     if (p.info.fanouts[l] != kFull) {
         int rows = 64; // destination nodes per tile: the smallest power of two with which dst_cap fits kMaxTiles tiles
         while (rows < kTile && (p.dst_cap[l] + rows - 1) / rows > kMaxTiles) rows <<= 1;
         const int tiles = grid1d(p.dst_cap[l], rows, kMaxTiles);
-        hipLaunchKernelGGL(labor_count_scan_kernel, dim3(tiles), dim3(kBlock), 0, p.st, s->g, dst, n_dst_dev, p.info.n_seeds, rows, p.info.fanouts[l],
-                           labor_key(p.seed, p.step, l, p.layer_dependency), s->counts_dev + l, s->status, s->ticket, s->ticket_total,
-                           s->scan_gen & 0x3FFFFFFFull, p.layers[l].indptr_local, p.items_cap[l],
-                           std::min<int64_t>(kItemLimit, p.layers[l].edge_cap), p.pin_dev + l);
+        if (p.rel)
+            dispatch_group(rel_group(p.rel[l]), [&](auto gs_c) {
+                hipLaunchKernelGGL(rel_count_scan_kernel<decltype(gs_c)::value>, dim3(tiles), dim3(kBlock), 0, p.st, s->g, p.etype, p.rel[l], dst,
+                                   n_dst_dev, p.info.n_seeds, rows, s->counts_dev + l, s->status, s->ticket, s->ticket_total,
+                                   s->scan_gen & 0x3FFFFFFFull, p.layers[l].indptr_local, p.items_cap[l],
+                                   std::min<int64_t>(kItemLimit, p.layers[l].edge_cap), p.pin_dev + l);
+            });
+        else
+            hipLaunchKernelGGL(labor_count_scan_kernel, dim3(tiles), dim3(kBlock), 0, p.st, s->g, dst, n_dst_dev, p.info.n_seeds, rows, p.info.fanouts[l],
+                               labor_key(p.seed, p.step, l, p.layer_dependency), s->counts_dev + l, s->status, s->ticket, s->ticket_total,
+                               s->scan_gen & 0x3FFFFFFFull, p.layers[l].indptr_local, p.items_cap[l],
+                               std::min<int64_t>(kItemLimit, p.layers[l].edge_cap), p.pin_dev + l);
         s->ticket_total += (unsigned long long)tiles;
         return COALA_OK;
     }
@@ -1272,6 +1475,13 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
         if (f == kFull)
             hipLaunchKernelGGL(full_insert_kernel, dim3(grid1d(p.items_cap[l], kBlock, 8192)), blk, 0, st, s->g, dst, (const int64_t*)base,
                                (const int64_t*)p.layers[l].indptr_local, s->nbr_global, s->tb, s->slot_of_item, eid);
+        else if (p.rel)
+            dispatch_group(rel_group(p.rel[l]), [&](auto gs_c) {
+                constexpr int GS = decltype(gs_c)::value;
+                hipLaunchKernelGGL(rel_insert_kernel<GS>, dim3(grid1d(cap_l * GS, kBlock, 8192)), blk, 0, st, s->g, p.etype, p.rel[l], dst,
+                                   (const int64_t*)base, (const int64_t*)p.layers[l].indptr_local, p.seed, p.step, l, s->nbr_global, s->tb,
+                                   s->slot_of_item, eid);
+            });
         else
             hipLaunchKernelGGL(labor_insert_kernel, dim3(grid1d(cap_l * kLaborGroup, kBlock, 8192)), blk, 0, st, s->g, dst, (const int64_t*)base,
                                (const int64_t*)p.layers[l].indptr_local, f, labor_key(p.seed, p.step, l, p.layer_dependency), s->nbr_global,
@@ -1366,16 +1576,16 @@ int launch_call(coala_sampler_t* s, Plan& p) {
 int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed, uint64_t step,
                 const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
                 int64_t* ticket_out, void* stream, const float* weights, int64_t* const* edge_ids = nullptr, bool labor = false,
-                bool layer_dependency = false) {
+                bool layer_dependency = false, const RelFan* rel = nullptr, const int32_t* etype = nullptr) {
     int rc;
-    if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, layers, bucketing, labor))) return rc;
+    if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, layers, bucketing, labor, rel != nullptr))) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(s->device));
     // the handle's scratch (hash table, scan state) is ordered by the stream of its calls: a caller that moves to another stream
     // first waits there for the previous call's last kernel
     if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
     s->last_stream = st;
-    Plan p{seeds, seed, step, layers, bucketing, weights, edge_ids, st, layer_dependency};
+    Plan p{seeds, seed, step, layers, bucketing, weights, edge_ids, st, layer_dependency, rel, etype};
     if ((rc = plan_call(p, n_seeds, fanouts, n_layers, bucketing ? bucketing->n_parts : 0, labor))) return rc;
     if ((rc = grow_workspace(s, p))) return rc;
     const uint64_t ticket = s->calls;
@@ -1493,6 +1703,33 @@ int coala_sampler_sample_layers_labor(coala_sampler_t* s, const int64_t* seeds, 
                                       const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
     return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream,
                        nullptr, edge_ids_out, true, layer_dependency != 0);
+}
+
+int coala_sampler_sample_layers_rel(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* rel_fanouts, int num_rels,
+                                    int n_layers, uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const int32_t* etype,
+                                    int64_t* const* edge_ids_out, int64_t* n_src_host, int64_t* n_edges_host,
+                                    const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
+    if (!rel_fanouts) return fail(COALA_EINVAL, "null argument");
+    if (!etype) return fail(COALA_EINVAL, "null etype");
+    if (num_rels < 1 || num_rels > kMaxRels) return fail(COALA_EINVAL, "num_rels must be 1..%d", kMaxRels);
+    if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
+    RelFan fan[COALA_SAMPLER_MAX_LAYERS] = {};
+    int32_t kind[COALA_SAMPLER_MAX_LAYERS]; // what the rest of the call needs of a layer: -1 (all -1: the full layer), else 0
+    for (int l = 0; l < n_layers; ++l) {
+        fan[l].num_rels = num_rels;
+        bool all_full = true, some = false;
+        for (int r = 0; r < num_rels; ++r) {
+            const int f = rel_fanouts[(size_t)l * num_rels + r];
+            if (f < -1 || f > 32) return fail(COALA_EINVAL, "layer %d, relation %d: fan-out %d outside 0..32 (or -1: every in-edge)", l, r, f);
+            fan[l].f[r] = (int8_t)f;
+            all_full = all_full && f == kFull;
+            some = some || f != 0;
+        }
+        if (!some) return fail(COALA_EINVAL, "layer %d: every relation has fan-out 0", l);
+        kind[l] = all_full ? kFull : 0;
+    }
+    return sample_impl(s, seeds, n_seeds, kind, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream, nullptr,
+                       edge_ids_out, false, false, fan, etype);
 }
 
 } // extern "C"

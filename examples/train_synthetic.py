@@ -11,6 +11,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --sage_aggregator pool
   python examples/train_synthetic.py --model_type gin --gin_aggregator max
   python examples/train_synthetic.py --model_type rgcn --num_rels 4 --rgcn_regularizer basis --num_bases 2
+  python examples/train_synthetic.py --model_type rgcn --num_rels 4 --sampler rel --rel_fan_out "10,3,0,-1;5,5,5,5"
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -29,7 +30,7 @@ import torch  # noqa: E402
 from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
 from COALA_GNN.harness import GAT, GCN, GIN, RGCN, SAGE, GATv2, SageMean  # noqa: E402
-from COALA_GNN.sampler import LaborSampler, NeighborSampler  # noqa: E402
+from COALA_GNN.sampler import LaborSampler, NeighborSampler, RelNeighborSampler, sort_csc_by_etype  # noqa: E402
 from COALA_GNN.synthetic import alloc_pinned_table, edge_types_by_source, powerlaw_csc  # noqa: E402
 
 
@@ -40,8 +41,13 @@ def main():
     ap.add_argument("--fan_out", type=str, default="5,5")
     ap.add_argument("--eval_fan_out", type=str, default=None,
                     help="fan-outs of the evaluation loader (default: --fan_out); -1 takes every in-edge, e.g. -1,-1 for full neighbourhoods")
-    ap.add_argument("--sampler", type=str, default="neighbor", choices=["neighbor", "labor"],
-                    help="labor: layer-neighbour sampling (LaborSampler) -- the same expected fan-out per node, fewer input nodes to fetch")
+    ap.add_argument("--sampler", type=str, default="neighbor", choices=["neighbor", "labor", "rel"],
+                    help="labor: layer-neighbour sampling (LaborSampler) -- the same expected fan-out per node, fewer input nodes to fetch; "
+                         "rel: a fan-out per edge type (RelNeighborSampler, --rel_fan_out; needs --model_type rgcn)")
+    ap.add_argument("--rel_fan_out", type=str, default=None,
+                    help="with --sampler rel, in place of --fan_out: layers separated by ';', the --num_rels relations of a layer by ',' "
+                         "(-1: every in-edge of the type, 0: none); a single number per layer applies to every relation, "
+                         "e.g. \"10,3,0,-1;5,5,5,5\" or \"5;5\"")
     ap.add_argument("--layer_dependency", action="store_true", help="with --sampler labor: the same random numbers in every layer")
     ap.add_argument("--edge_weights", type=str, default="none", choices=["none", "random"],
                     help="random: seeded edge weights in (0, 1] with ~10%% zeros, sampled in proportion by the training sampler (DGL's "
@@ -91,6 +97,16 @@ def main():
     comm = MPI_Comm_Manager(node_rank)                                  # sbatch_ssd_gnn_train.py:262
     device = "cuda:" + str(comm.local_rank)
     comm.initialize_nested_process_group(args.cache_backend)            # :267
+    rel_fan_out = None
+    if args.sampler == "rel":
+        if args.model_type != "rgcn" or not args.rel_fan_out or args.edge_weights != "none" or args.layer_dependency:
+            ap.error("--sampler rel needs --model_type rgcn and --rel_fan_out, and takes neither --edge_weights nor --layer_dependency")
+        rel_fan_out = [[int(f) for f in layer.split(",")] for layer in args.rel_fan_out.split(";")]
+        rel_fan_out = [layer[0] if len(layer) == 1 else layer for layer in rel_fan_out]
+        # what the loader sizes its fetch buffers from: the per-layer totals (RelNeighborSampler.fanouts), -1 for a layer with a -1
+        args.fan_out = ",".join(str(f) for f in RelNeighborSampler(rel_fan_out, args.num_rels).fanouts)
+    elif args.rel_fan_out:
+        ap.error("--rel_fan_out needs --sampler rel")
     fan_out = [int(f) for f in args.fan_out.split(",")]
     eval_fan_out = fan_out if args.eval_fan_out is None else [int(f) for f in args.eval_fan_out.split(",")]
     if len(eval_fan_out) != len(fan_out):
@@ -143,11 +159,15 @@ def main():
         if not 1 <= args.num_rels <= 64:
             ap.error("--num_rels must be 1..64")
         edata = dict(edata, etype=edge_types_by_source(indices, args.num_rels))
+        if rel_fan_out is not None:   # RelNeighborSampler wants every node's in-edges sorted by type (no other edata to carry along here)
+            indices, edata["etype"], _ = sort_csc_by_etype(indptr, indices, edata["etype"])
     edge_ids = ew is not None or rgcn
     if args.sampler == "labor":
         if prob is not None:
             ap.error("--sampler labor does not sample by edge weight (--edge_weights)")
         sampler = LaborSampler(fan_out, layer_dependency=args.layer_dependency, edge_ids=edge_ids)
+    elif rel_fan_out is not None:
+        sampler = RelNeighborSampler(rel_fan_out, args.num_rels)
     else:
         if args.layer_dependency:
             ap.error("--layer_dependency needs --sampler labor")

@@ -430,7 +430,26 @@ int coala_sampler_sample_layers_labor(coala_sampler_t* s, const int64_t* seeds, 
                                       uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, int64_t* const* edge_ids_out,
                                       int layer_dependency, int64_t* n_src_host, int64_t* n_edges_host,
                                       const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream);
-/* Counts of an earlier call, with the edge counts of its layers; returns the device-side refusal of a full or LABOR layer, if any. */
+/* Relation layers: a fan-out per edge type (DGL's NeighborSampler on a heterograph; on a homogenised graph dgl.sort_csc_by_tag followed by
+ * sample_etype_neighbors(etype_sorted=True)).  etype: DEVICE int32[num_edges] in CSC order (aligned with `indices`), values in
+ * [0, num_rels), borrowed for the call.  The types MUST BE NON-DECREASING INSIDE EVERY ROW [indptr[v], indptr[v + 1]): the in-edges of
+ * relation r of a node are then one segment of its row, found by binary search.  This call does not verify the order -- that is the
+ * caller's duty (COALA_GNN.sampler.sort_csc_by_etype sorts a graph; RelNeighborSampler checks it once per graph).  Types out of
+ * order give rows that are not what the rule says, but nothing is read or written out of bounds.
+ * rel_fanouts: HOST int32[n_layers][num_rels], layers in sampling order.  Relation r of layer l with f = rel_fanouts[l][r] and deg_r
+ * in-edges of that type: f == 0 takes none, f == -1 or deg_r <= f takes them all, otherwise f distinct edges of the segment by the
+ * uniform sampler's draw with the counters 64 r + j (the exact rule is in the header of coala_sampler.hip; with num_rels == 1 a row holds
+ * the edges coala_sampler_sample_layers_edge_ids draws at the same seed and step).  A layer whose fan-outs are all -1 is a full layer.
+ * Every layer's block is CSR, exactly as a LABOR layer's: indptr_local is required for every layer, nbr_local holds the E taken edges in
+ * ascending CSC position inside a row (hence grouped by relation), edge_ids_out (NULL, or per layer NULL or int64[edge_cap]) their
+ * CSC positions.  Capacities, the device-side refusal, the source-list rule, bucketing and the ticket / wait protocol are those of a
+ * full layer; counts come back through coala_sampler_wait_layers.  COALA_EINVAL (with a message) for num_rels outside 1..64, a fan-out
+ * outside {-1, 0..32}, a layer whose fan-outs are all 0, or a NULL etype. */
+int coala_sampler_sample_layers_rel(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* rel_fanouts, int num_rels,
+                                    int n_layers, uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const int32_t* etype,
+                                    int64_t* const* edge_ids_out, int64_t* n_src_host, int64_t* n_edges_host,
+                                    const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream);
+/* Counts of an earlier call, with the edge counts of its layers; returns the device-side refusal of a full, LABOR or relation layer, if any. */
 int coala_sampler_wait_layers(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host);
 
 /* Block op for the consumer of these blocks (the native Block objects stand where DGL blocks stand in
