@@ -1,7 +1,7 @@
 """Autograd wrappers of the native block ops that `Block` (sampler.py) hands to a model: mean aggregation (SAGEConv's "mean"), weighted
 sum aggregation (DGL's u_mul_e_sum, the edge_weight= path of GraphConv / SAGEConv), max aggregation (DGL's fn.max: SAGEConv's "pool",
-GINConv's "max"), the relation-typed sum (RelGraphConv's message step) and GAT / GATv2 attention aggregation, on fixed blocks and on
-the ragged CSR blocks of full layers.  One kernel forward, one backward each; the kernels are in coala-gnn_amd/csrc/coala_block_ops.hip
+GINConv's "max"), the relation-typed sum (RelGraphConv's message step), GAT / GATv2 attention aggregation and relation-typed GAT
+attention (RelGATConv's message step), on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the kernels are in coala-gnn_amd/csrc/coala_block_ops.hip
 (C ABI: coala_block_*).  Every op has one forward and one backward body for both block forms, which take the C entry and the block's
 index tensors -- (nbr,) or (indptr, indices); the two Function classes of an op are shells that name the entries, and they stay two
 because Block's callers and the tests tell by the class which form ran."""
@@ -339,3 +339,58 @@ class _Gatv2AggregateCSR(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         return _gatv2_backward(ctx, grad_out, _lib.coala_block_gatv2_aggregate_csr_backward) + (None,) * 3
+
+
+def _rel_gat_forward(ctx, el, er, feat, rows, etype, num_rels, entry, index, negative_slope):
+    """Per head and relation, a softmax of leaky_relu(el[row] + er[d, r]) over row d's entries of type r, then the weighted sum of
+    feat[row] over all of them (coala_block_rel_gat_aggregate[_csr]).  rows (int32, -1: no edge) and etype (int32) are laid out like
+    the block's index array, which the kernel reads only for its shape: rows stands in its place.  The log-sum-exp per (row, relation,
+    head) is the state of the backward."""
+    el, er, f = el.contiguous(), er.contiguous(), feat.contiguous()
+    idx, n_dst, fan = _block(index)
+    H, D = f.shape[1], f.shape[2]
+    out = torch.empty((n_dst, H, D), dtype=torch.float32, device=f.device)
+    lse = torch.empty((n_dst, num_rels, H), dtype=torch.float32, device=f.device)
+    _capi.check(entry(f.device.index or 0, *idx[:-1], rows.data_ptr(), etype.data_ptr(), el.data_ptr(), er.data_ptr(), f.data_ptr(),
+                      out.data_ptr(), lse.data_ptr(), n_dst, *fan, num_rels, H, D, negative_slope, current_stream()))
+    ctx.save_for_backward(el, er, f, lse, rows, etype, *index)
+    ctx.slope, ctx.num_rels = negative_slope, num_rels
+    return out
+
+
+def _rel_gat_backward(ctx, grad_out, entry):
+    """-> (grad_el, grad_er, grad_feat), one launch."""
+    el, er, f, lse, rows, etype, *index = ctx.saved_tensors
+    idx, n_dst, fan = _block(index)
+    g = grad_out.contiguous()
+    grad_feat, grad_el, grad_er = torch.zeros_like(f), torch.zeros_like(el), torch.empty_like(er)
+    _capi.check(entry(f.device.index or 0, *idx[:-1], rows.data_ptr(), etype.data_ptr(), el.data_ptr(), er.data_ptr(), f.data_ptr(),
+                      lse.data_ptr(), g.data_ptr(), grad_feat.data_ptr(), grad_el.data_ptr(), grad_er.data_ptr(), n_dst, *fan, ctx.num_rels,
+                      f.shape[1], f.shape[2], ctx.slope, current_stream()))
+    return grad_el, grad_er, grad_feat
+
+
+class _RelGatAggregate(torch.autograd.Function):
+    """Relation-typed GAT attention on a fixed block (coala_block_rel_gat_aggregate): one kernel forward, one backward (gradients for
+    el, er and feat)."""
+
+    @staticmethod
+    def forward(ctx, el, er, feat, rows, etype, num_rels, nbr, negative_slope):
+        return _rel_gat_forward(ctx, el, er, feat, rows, etype, num_rels, _lib.coala_block_rel_gat_aggregate, (nbr,), negative_slope)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _rel_gat_backward(ctx, grad_out, _lib.coala_block_rel_gat_aggregate_backward) + (None,) * 5
+
+
+class _RelGatAggregateCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_rel_gat_aggregate_csr): rows and etype have one value per entry of indices."""
+
+    @staticmethod
+    def forward(ctx, el, er, feat, rows, etype, num_rels, indptr, indices, negative_slope):
+        return _rel_gat_forward(ctx, el, er, feat, rows, etype, num_rels, _lib.coala_block_rel_gat_aggregate_csr, (indptr, indices),
+                                negative_slope)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _rel_gat_backward(ctx, grad_out, _lib.coala_block_rel_gat_aggregate_csr_backward) + (None,) * 6

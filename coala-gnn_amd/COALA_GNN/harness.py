@@ -6,14 +6,15 @@ of GATv2, the same model on GATv2Conv layers (--model_type gatv2, Block.gatv2_ag
 SAGE take edge_weight=<edata key> and then hand block.edata[key] to their layers (blocks sampled with NeighborSampler(edge_ids=True)).
 SAGE(aggregator_type='pool') and GIN (--model_type gin) are the models on the native max aggregation (Block.max_aggregate).  RGCN
 (--model_type rgcn) mirrors examples/models.py:RGCN on a homogenised graph: RelGraphConv layers, one weight matrix per edge type, on the
-native relation-typed sum (Block.rel_sum_aggregate)."""
+native relation-typed sum (Block.rel_sum_aggregate).  RGAT and RSAGE (--model_type rgat|rsage) mirror examples/models.py:RGAT and :RSAGE
+the same way, on RelGATConv (the native relation-typed attention, Block.rel_gat_aggregate) and RelSAGEConv."""
 import time
 
 import torch
 
-from .nn import GATConv, GATv2Conv, GINConv, GraphConv, RelGraphConv, SAGEConv
+from .nn import GATConv, GATv2Conv, GINConv, GraphConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv
 
-__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "train_steps", "FlatGradAllReduce"]
+__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "RGAT", "RSAGE", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -165,6 +166,61 @@ class RGCN(torch.nn.Module):
             if i + 1 < len(self.layers):
                 h = torch.relu(self.dropout(h))
         return h
+
+
+def _block_etypes(block, key, model):
+    """block.edata[key] for a model that reads its edge types from the blocks; RGCN's ValueError when they carry no edge ids."""
+    if "_ID" not in block.edata:
+        raise ValueError(f"{model} needs the edge ids of its blocks to find their edge types: make the sampler with edge_ids=True")
+    return block.edata[key]
+
+
+class RGAT(torch.nn.Module):
+    """examples/models.py:RGAT on a homogenised heterograph (RGCN's input: one id space, one feature table, an integer type per edge):
+    num_layers RelGATConv layers of n_heads heads of h_feats // n_heads features -- one GATConv per edge type, summed -- the heads
+    flattened after every layer, relu then dropout between the layers, and a final Linear(h_feats, num_classes).  Every layer reads its
+    edge types from block.edata[etype_key], so the blocks must come from a sampler made with edge_ids=True."""
+
+    def __init__(self, in_feats, h_feats, num_classes, num_layers, num_rels, n_heads=4, dropout=0.2, etype_key="etype"):
+        super().__init__()
+        if h_feats % n_heads:
+            raise ValueError(f"h_feats {h_feats} is not a multiple of n_heads {n_heads}")
+        dims = [in_feats] + [h_feats] * (num_layers - 1)
+        self.layers = torch.nn.ModuleList(RelGATConv(dims[i], h_feats // n_heads, n_heads, num_rels) for i in range(num_layers))
+        self.dropout = torch.nn.Dropout(dropout)
+        self.linear = torch.nn.Linear(h_feats, num_classes)
+        self.num_rels, self.etype_key = num_rels, etype_key
+
+    def forward(self, blocks, x):
+        h = x
+        for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+            etype = _block_etypes(block, self.etype_key, "RGAT").to(h.device)
+            h = layer(block, (h, block.dst_rows(h)), etype).flatten(1)
+            if i + 1 < len(self.layers):
+                h = self.dropout(torch.relu(h))
+        return self.linear(h)
+
+
+class RSAGE(torch.nn.Module):
+    """examples/models.py:RSAGE on a homogenised heterograph: num_layers RelSAGEConv layers of h_feats features -- one SAGEConv 'gcn' per
+    edge type, summed -- relu then dropout between the layers, and a final Linear(h_feats, num_classes).  Edge types as for RGAT."""
+
+    def __init__(self, in_feats, h_feats, num_classes, num_layers, num_rels, dropout=0.2, etype_key="etype"):
+        super().__init__()
+        dims = [in_feats] + [h_feats] * (num_layers - 1)
+        self.layers = torch.nn.ModuleList(RelSAGEConv(dims[i], h_feats, num_rels) for i in range(num_layers))
+        self.dropout = torch.nn.Dropout(dropout)
+        self.linear = torch.nn.Linear(h_feats, num_classes)
+        self.num_rels, self.etype_key = num_rels, etype_key
+
+    def forward(self, blocks, x):
+        h = x
+        for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+            etype = _block_etypes(block, self.etype_key, "RSAGE").to(h.device)
+            h = layer(block, (h, block.dst_rows(h)), etype)
+            if i + 1 < len(self.layers):
+                h = self.dropout(torch.relu(h))
+        return self.linear(h)
 
 
 class FlatGradAllReduce(object):

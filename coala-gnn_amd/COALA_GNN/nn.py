@@ -1,4 +1,4 @@
-"""GATConv, GATv2Conv, GraphConv, SAGEConv, GINConv and RelGraphConv on the native Block objects, for the reference's GAT and GCN models (examples/models.py;
+"""GATConv, GATv2Conv, GraphConv, SAGEConv, GINConv, RelGraphConv, RelGATConv and RelSAGEConv on the native Block objects, for the reference's GAT and GCN models (examples/models.py;
 DGL is not installed on the MI355X image) and for DGL models ported to them.  All take (block, (h_src, h_dst)) as DGL's modules do on
 a block.
 
@@ -9,10 +9,12 @@ edge_weight= (one value per neighbour slot, e.g. block.edata['w'] of a block sam
 aggregate with Block.weighted_sum_aggregate, DGL's u_mul_e_sum.  SAGEConv's 'pool' and GINConv's 'max' take their maximum with
 Block.max_aggregate (DGL's fn.max), a native kernel as well; GINConv's 'sum' is Block.weighted_sum_aggregate with unit weights.
 RelGraphConv (one weight matrix per edge type) sums the messages per relation with Block.rel_sum_aggregate, a native kernel, and applies
-all its weight matrices in one GEMM."""
+all its weight matrices in one GEMM.  RelGATConv and RelSAGEConv are the layers of the reference's heterogeneous models RGAT and RSAGE
+on a homogenised block -- HeteroGraphConv over one GATConv, or one SAGEConv 'gcn', per edge type, summed: RelGATConv's softmax per
+(destination, relation) is Block.rel_gat_aggregate, a native kernel; RelSAGEConv needs Block.rel_sum_aggregate and one GEMM."""
 import torch
 
-__all__ = ["GATConv", "GATv2Conv", "GraphConv", "SAGEConv", "GINConv", "RelGraphConv"]
+__all__ = ["GATConv", "GATv2Conv", "GraphConv", "SAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv"]
 
 
 class GATConv(torch.nn.Module):
@@ -369,3 +371,154 @@ class RelGraphConv(torch.nn.Module):
         if self.activation is not None:
             h = self.activation(h)
         return self.dropout(h)
+
+
+def _check_num_rels(num_rels):
+    if isinstance(num_rels, bool) or not isinstance(num_rels, int) or not 1 <= num_rels <= 64:
+        raise ValueError(f"num_rels {num_rels!r}: 1..64 relations")
+
+
+class RelGATConv(torch.nn.Module):
+    """Graph attention with one GATConv per edge type, summed over the types, on a homogenised block: what DGL computes with
+    HeteroGraphConv({etype: GATConv(in_feats, out_feats, num_heads)}, aggregate='sum') -- the layer of the reference's RGAT model -- in
+    the int in_feats form, where a GATConv has one projection `fc` and takes feat_dst = feat_src[:num_dst].
+
+    forward(block, (h_src, h_dst), etype) -> [num_dst, H, D]; etype (any integer dtype) has one value per neighbour slot, shaped like
+    block.edata['_ID'].  For destination d, head h, relation r and the valid in-edges j of d with etype_j == r (source s_j):
+        f_r(x) = (fc_weight[r] @ x).view(H, D);   el_j = <f_r(h_src[s_j])[h], attn_l[r, h]>;   er = <f_r(h_dst[d])[h], attn_r[r, h]>
+        a_j = softmax over those j of leaky_relu(el_j + er, negative_slope)
+        out[d, h, :] = sum_r (sum_j a_j f_r(h_src[s_j])[h, :] + bias[r].view(H, D)[h]);   then activation, if any
+    Every relation's bias is added to every destination, as with DGL's allow_zero_in_degree=True, where a GATConv gives a node without
+    in-edges its bias.  An edge whose type is outside [0, num_rels) sends nothing.  h_dst must be block.dst_rows(h_src).
+    Parameters, stacked over the relations: fc_weight [R, H * D, in_feats], attn_l [R, H, D], attn_r [R, H, D], bias [R, H * D]; slice
+    r holds fc.weight, attn_l[0], attn_r[0] and bias of relation r's DGL GATConv (from_gatconvs shows the mapping), and is initialised
+    as GATConv.reset_parameters does: Xavier-normal with the gain of relu, bias zero.
+    The projection does not cost R times the source rows: only the (source, relation) pairs that occur on a valid edge are projected,
+    one GEMM per relation on its slice of the pairs (sorted by etype * num_src + src, so a relation's pairs are contiguous), and
+    Block.rel_gat_aggregate reads them in its packed form.  The per-relation pair counts cost one host read per layer call, and the packed form's row check a second.  The
+    destination side is one [num_dst, in] x [in, R * H] GEMM with the vectors fc_weight[r, h]^T attn_r[r, h].
+    One difference from DGL: HeteroGraphConv skips a relation that has no edge anywhere in the block, bias included; this layer adds
+    every relation's bias always.  Attention dropout and residual connections are not provided."""
+
+    def __init__(self, in_feats, out_feats, num_heads, num_rels, feat_drop=0.0, negative_slope=0.2, bias=True, activation=None):
+        super().__init__()
+        _check_num_rels(num_rels)
+        self._in_feats, self._out_feats, self._num_heads, self.num_rels = in_feats, out_feats, num_heads, num_rels
+        self.fc_weight = torch.nn.Parameter(torch.empty(num_rels, num_heads * out_feats, in_feats))
+        self.attn_l = torch.nn.Parameter(torch.empty(num_rels, num_heads, out_feats))
+        self.attn_r = torch.nn.Parameter(torch.empty(num_rels, num_heads, out_feats))
+        self.bias = torch.nn.Parameter(torch.empty(num_rels, num_heads * out_feats)) if bias else None
+        self.feat_drop = torch.nn.Dropout(feat_drop)
+        self.negative_slope = negative_slope
+        self.activation = activation
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        with torch.no_grad():
+            for r in range(self.num_rels):   # a slice at a time: the fans are those of one GATConv's fc [H * D, in] and attn [1, H, D]
+                torch.nn.init.xavier_normal_(self.fc_weight[r], gain=gain)
+                torch.nn.init.xavier_normal_(self.attn_l[r:r + 1], gain=gain)
+                torch.nn.init.xavier_normal_(self.attn_r[r:r + 1], gain=gain)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    @classmethod
+    def from_gatconvs(cls, convs, activation=None):
+        """The layer that computes sum_r convs[r] on relation r's edges, from R COALA_GNN.nn.GATConv modules whose fc_src and fc_dst
+        hold the same weights (DGL's single `fc`): fc_weight[r] = fc_src.weight, attn_l[r] = attn_l[0], attn_r[r] = attn_r[0],
+        bias[r] = bias.  The parameters are copied."""
+        convs = list(convs)
+        c0 = convs[0]
+        for c in convs:
+            if not torch.equal(c.fc_src.weight, c.fc_dst.weight):
+                raise ValueError("from_gatconvs takes GATConv modules whose fc_src and fc_dst hold the same weights")
+            if (tuple(c.fc_src.weight.shape), c._num_heads, c.bias is None) != (tuple(c0.fc_src.weight.shape), c0._num_heads, c0.bias is None):
+                raise ValueError("from_gatconvs takes GATConv modules of one shape")
+        layer = cls(c0.fc_src.in_features, c0._out_feats, c0._num_heads, len(convs), feat_drop=c0.feat_drop.p,
+                    negative_slope=c0.negative_slope, bias=c0.bias is not None, activation=activation)
+        layer.to(device=c0.attn_l.device, dtype=c0.attn_l.dtype)
+        with torch.no_grad():
+            for r, c in enumerate(convs):
+                layer.fc_weight[r] = c.fc_src.weight
+                layer.attn_l[r] = c.attn_l[0]
+                layer.attn_r[r] = c.attn_r[0]
+                if c.bias is not None:
+                    layer.bias[r] = c.bias
+        return layer
+
+    def forward(self, block, feat, etype):
+        h_src, h_dst = feat
+        R, H, D = self.num_rels, self._num_heads, self._out_feats
+        h_src, h_dst = self.feat_drop(h_src), self.feat_drop(h_dst)
+        dev = h_src.device
+        _, src = block._slots(dev)
+        t = etype.reshape(-1).to(device=dev, dtype=torch.int64)
+        keep = (src >= 0) & (t >= 0) & (t < R)
+        pairs, inv = torch.unique(t[keep] * block.num_src + src[keep], return_inverse=True)   # sorted: grouped by relation
+        rows = torch.full_like(src, -1)
+        rows[keep] = inv
+        pair_rel, pair_src = pairs // block.num_src, pairs % block.num_src
+        counts = torch.bincount(pair_rel, minlength=R).tolist()                              # the host read
+        parts, off = [], 0
+        for r, c in enumerate(counts):
+            if c:
+                parts.append(h_src[pair_src[off:off + c]] @ self.fc_weight[r].t())
+                off += c
+        feat_pairs = (torch.cat(parts) if parts else h_src.new_zeros((0, H * D))).view(-1, H, D)
+        el = (feat_pairs * self.attn_l[pair_rel]).sum(-1)
+        w_r = (self.fc_weight.view(R, H, D, -1) * self.attn_r.unsqueeze(-1)).sum(2)           # [R, H, in]: fc_weight[r, h]^T attn_r[r, h]
+        er = (h_dst @ w_r.view(R * H, -1).t()).view(-1, R, H)
+        rst = block.rel_gat_aggregate(el, er, feat_pairs, etype, R, rows=rows.view(etype.shape), negative_slope=self.negative_slope)
+        if self.bias is not None:
+            rst = rst + self.bias.sum(0).view(1, H, D)
+        if self.activation is not None:
+            rst = self.activation(rst)
+        return rst
+
+
+class RelSAGEConv(torch.nn.Module):
+    """GraphSAGE 'gcn' with one SAGEConv per edge type, summed over the types, on a homogenised block: what DGL computes with
+    HeteroGraphConv({etype: SAGEConv(in_feats, out_feats, 'gcn')}, aggregate='sum'), the layer of the reference's RSAGE model.
+
+    forward(block, feat, etype) -> [num_dst, out_feats]; feat is h_src or (h_src, h_dst) -- without h_dst the destination rows are
+    block.dst_rows(h_src) -- and etype (any integer dtype) has one value per neighbour slot, shaped like block.edata['_ID']:
+        h_neigh[d, r] = (sum over d's valid in-edges j of type r of h_src[s_j] + h_dst[d]) / (c[d, r] + 1)
+        out[d] = sum_r (fc_neigh_weight[r] @ h_neigh[d, r] + bias[r]);   then activation, if any
+    with c[d, r] the number of those edges (Block.rel_in_degrees).  No fc_self, as in SAGEConv 'gcn'; a relation without an edge at d
+    sends fc_neigh_weight[r] @ h_dst[d] + bias[r], SAGEConv's row for a node without in-edges.  An edge whose type is outside
+    [0, num_rels) sends nothing.  The sums are Block.rel_sum_aggregate, a native kernel, and all R matrices are applied in one GEMM:
+    h_neigh viewed as [num_dst, R * in] times the weights viewed as [R * in, out].
+    Parameters, stacked over the relations: fc_neigh_weight [R, out_feats, in_feats] (slice r is fc_neigh.weight of relation r's
+    SAGEConv; Xavier-uniform with the gain of relu, per slice) and bias [R, out_feats] (zero).
+    As RelGATConv, and unlike DGL's HeteroGraphConv, it does not skip a relation that has no edge anywhere in the block."""
+
+    def __init__(self, in_feats, out_feats, num_rels, bias=True, activation=None):
+        super().__init__()
+        _check_num_rels(num_rels)
+        self._in_feats, self._out_feats, self.num_rels = in_feats, out_feats, num_rels
+        self.fc_neigh_weight = torch.nn.Parameter(torch.empty(num_rels, out_feats, in_feats))
+        self.bias = torch.nn.Parameter(torch.empty(num_rels, out_feats)) if bias else None
+        self.activation = activation
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        with torch.no_grad():
+            for r in range(self.num_rels):
+                torch.nn.init.xavier_uniform_(self.fc_neigh_weight[r], gain=gain)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def forward(self, block, feat, etype):
+        h_src, h_dst = feat if isinstance(feat, (tuple, list)) else (feat, block.dst_rows(feat))
+        R = self.num_rels
+        z = block.rel_sum_aggregate(h_src, etype, R)                                           # [num_dst, R, in]
+        c = block.rel_in_degrees(etype, R).to(device=z.device, dtype=z.dtype)
+        h_neigh = (z + h_dst.unsqueeze(1)) / (c + 1).unsqueeze(-1)
+        rst = h_neigh.reshape(z.shape[0], R * self._in_feats) @ self.fc_neigh_weight.transpose(1, 2).reshape(R * self._in_feats, self._out_feats)
+        if self.bias is not None:
+            rst = rst + self.bias.sum(0)
+        if self.activation is not None:
+            rst = self.activation(rst)
+        return rst

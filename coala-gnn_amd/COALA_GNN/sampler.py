@@ -12,7 +12,7 @@ import torch
 from COALA_GNN_Pybind import _capi, current_stream
 
 from .block_ops import (_GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
-                        _MeanAggregateCSR, _RelSum, _RelSumCSR, _WeightedSum, _WeightedSumCSR)
+                        _MeanAggregateCSR, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _WeightedSum, _WeightedSumCSR)
 
 __all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "sort_csc_by_etype", "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT",
            "EID"]
@@ -500,6 +500,78 @@ class Block(object):
         a = p / l[rows]
         out = torch.zeros((self.num_dst,) + tuple(feat_src.shape[1:]), dtype=feat_src.dtype, device=dev)
         return out.index_add(0, rows, a.unsqueeze(-1).to(feat_src.dtype) * fs)
+
+    def _rel_gat_args(self, el, er, feat, etype, num_rels, rows):
+        """The checks of rel_gat_aggregate / rel_gat_aggregate_torch -> (el [P, H], feat [P, H, D]): the tables as the packed form takes
+        them, the dense form's viewed as [num_src * R, ...]."""
+        slots = self._rel_args(etype, num_rels, None)
+        R = num_rels
+        if rows is None:
+            ok = feat.dim() == 4 and tuple(feat.shape[:2]) == (self.num_src, R) and tuple(el.shape) == tuple(feat.shape[:3])
+            want = f"[{self.num_src}, {R}, H], [{self.num_dst}, {R}, H] and [{self.num_src}, {R}, H, D]"
+        else:
+            if not isinstance(rows, torch.Tensor) or rows.is_floating_point() or rows.is_complex() or rows.dtype == torch.bool:
+                raise ValueError("rows must be an integer tensor")
+            if tuple(rows.shape) != tuple(slots.shape):
+                raise ValueError(f"rows of shape {tuple(rows.shape)}: this block takes one per neighbour slot, {tuple(slots.shape)}")
+            ok = feat.dim() == 3 and tuple(el.shape) == tuple(feat.shape[:2])
+            want = f"[P, H], [{self.num_dst}, {R}, H] and [P, H, D]"
+        if not ok or tuple(er.shape) != (self.num_dst, R, feat.shape[-2]):
+            raise ValueError(f"el {tuple(el.shape)}, er {tuple(er.shape)}, feat {tuple(feat.shape)}: this block takes {want}")
+        H = feat.shape[-2]
+        return el.reshape(-1, H), feat.reshape(-1, H, feat.shape[-1])
+
+    def rel_gat_aggregate(self, el, er, feat, etype, num_rels, rows=None, negative_slope=0.2):
+        """Relation-typed GAT attention (RelGATConv's message step; DGL's HeteroGraphConv over one GATConv per edge type, summed): for
+        every dst node d, head h and relation r, a softmax of leaky_relu(el[.., h] + er[d, r, h], negative_slope) over d's valid
+        in-edges of type r alone, then out[d, h, :] = sum_r sum_j a_j feat[.., h, :] -> [num_dst, H, D].  etype: any integer dtype, one
+        value per neighbour slot, the shape of edata['_ID'].  er is [num_dst, R, H].  Which row of el / feat an edge reads:
+          rows=None (dense): el [num_src, R, H], feat [num_src, R, H, D]; an edge of type r from source s reads el[s, r], feat[s, r];
+          rows given (packed): el [P, H], feat [P, H, D]; rows has one integer per neighbour slot and the edge in slot j reads row
+            rows_j < P (IndexError otherwise; on the native path that check is one host read per call).  A slot is then an edge
+            exactly when rows_j >= 0: the block's own index array is not read.
+        A relation absent from a row contributes nothing; a row without a valid edge gives zeros; a valid edge whose type is outside
+        [0, num_rels) contributes nothing and receives no gradient.  Native kernels (one forward, one backward with gradients for el,
+        er and feat) under the conditions of gat_aggregate -- fp32 GPU tensors, fan-out <= 32 or the ragged form, H <= 16 -- and
+        R * H <= 256, for tables that are not empty; rel_gat_aggregate_torch otherwise."""
+        el2, feat2 = self._rel_gat_args(el, er, feat, etype, num_rels, rows)
+        R, H = num_rels, feat2.shape[1]
+        native = (all(t.is_cuda and t.dtype == torch.float32 for t in (el, er, feat)) and etype.is_cuda and (rows is None or rows.is_cuda)
+                  and H <= 16 and R * H <= 256 and 0 < feat2.shape[0] < (1 << 31) and feat2.shape[2] > 0)
+        index = self._native_index() if native else None
+        if index is None:
+            return self.rel_gat_aggregate_torch(el, er, feat, etype, num_rels, rows, negative_slope)
+        t = etype.to(torch.int64)
+        if rows is None:
+            src = index[-1].to(torch.int64)
+            row = torch.where((src >= 0) & (t >= 0) & (t < R), src * R + t, -1)
+        else:
+            row = torch.where((t >= 0) & (t < R), rows.to(torch.int64), -1).clamp_min(-1)
+            if row.numel() and int(row.max()) >= feat2.shape[0]:   # one host read: the kernels do not check an index they are given
+                raise IndexError(f"rows holds {int(row.max())}: el and feat have {feat2.shape[0]} rows")
+        t32 = t.clamp(-1, R).to(torch.int32)   # the kernel only compares a type with [0, R)
+        fn = _RelGatAggregateCSR if self.nbr is None else _RelGatAggregate
+        return fn.apply(el2, er, feat2, row.to(torch.int32).contiguous(), t32.contiguous(), R, *index, float(negative_slope))
+
+    def rel_gat_aggregate_torch(self, el, er, feat, etype, num_rels, rows=None, negative_slope=0.2):
+        """rel_gat_aggregate in plain torch, any device and dtype, both block forms, the same skip rules: an edge-list softmax keyed by
+        dst * R + etype that materialises the gathered [E, H, D] rows.  The fallback of rel_gat_aggregate, and its reference."""
+        el2, feat2 = self._rel_gat_args(el, er, feat, etype, num_rels, rows)
+        dev = feat.device
+        R, H = num_rels, feat2.shape[1]
+        dst, src = self._slots(dev)
+        t = etype.reshape(-1).to(device=dev, dtype=torch.int64)
+        row = src * R + t if rows is None else rows.reshape(-1).to(device=dev, dtype=torch.int64)
+        keep = ((src >= 0) if rows is None else (row >= 0)) & (t >= 0) & (t < R)
+        dst, row, key = dst[keep], row[keep], dst[keep] * R + t[keep]
+        e = torch.nn.functional.leaky_relu(el2[row] + er.reshape(-1, H)[key], negative_slope)       # [E, H]
+        m = torch.full((self.num_dst * R, H), float("-inf"), dtype=e.dtype, device=dev)
+        m = m.scatter_reduce(0, key.unsqueeze(1).expand(-1, H), e.detach(), "amax").detach()        # the shift cancels in the softmax
+        p = torch.exp(e - m[key])
+        l = torch.zeros((self.num_dst * R, H), dtype=e.dtype, device=dev).index_add(0, key, p)
+        a = p / l[key]
+        out = torch.zeros((self.num_dst,) + tuple(feat2.shape[1:]), dtype=feat2.dtype, device=dev)
+        return out.index_add(0, dst, a.unsqueeze(-1).to(feat2.dtype) * feat2[row])
 
 
 class NeighborSampler(object):

@@ -1,7 +1,7 @@
 // coala_block_ops.hip -- what a model computes on a sampled block (coala_sampler.hip makes the blocks), for gfx950: mean aggregation
 // (DGL's SAGEConv "mean"), weighted sum aggregation (DGL's u_mul_e_sum: GraphConv / SAGEConv with edge_weight=), max aggregation
-// (DGL's fn.max: SAGEConv "pool", GINConv "max"), the relation-typed sum (RelGraphConv's message step) and GAT / GATv2 attention
-// aggregation (GATConv's and GATv2Conv's message steps), forward and backward, on fixed blocks (nbr_local[n_dst, fanout], -1 = no
+// (DGL's fn.max: SAGEConv "pool", GINConv "max"), the relation-typed sum (RelGraphConv's message step), GAT / GATv2 attention
+// aggregation (GATConv's and GATv2Conv's message steps) and relation-typed GAT attention (a softmax per destination and relation), forward and backward, on fixed blocks (nbr_local[n_dst, fanout], -1 = no
 // neighbour) and on the CSR blocks of full layers.  Stateless entry points: no handle, every launch on the caller's stream.
 //
 // Layout of the file: the device helpers every kernel walks a row with (which rows a wave takes, a row's bounds in either block form,
@@ -807,6 +807,244 @@ __global__ __launch_bounds__(kBlock) void rel_sum_backward_kernel(const int64_t*
     }
 }
 
+// Relation-typed GAT attention on a block (the message step of DGL's HeteroGraphConv over one GATConv per edge type, aggregate='sum', on
+// a homogenised block): the softmax runs per (destination, relation), and the relations' results are summed.  Every slot carries the
+// row of el / feat its edge reads (row, -1 = padding; it stands where nbr / indices stand in the other ops) and its type.  For dst d,
+// head h, relation r and the slots j of d with row_j >= 0 and etype_j == r:
+//   e_j = leaky_relu(el[row_j, h] + er[d, r, h], slope),  a_j = softmax of e over those j,  out[d, h, :] = sum_r sum_j a_j feat[row_j, h, :]
+// One wave per destination row.  The scores are scalars per edge and head, so a first pass over the row's chunks costs no feature
+// traffic: it keeps the running max and sum of every (relation, head) in LDS (hence R * H <= kRelGatMaxStates), visiting per chunk
+// only the relations present in it -- a ballot on the first live lane's type peels them off one by one -- with a masked wave_max /
+// wave_sum each.  The second pass then knows every group's max m and sum l: a_j = exp(e_j - m) / l, and the sum over edges and
+// relations is one plain weighted sum into out[d], with softmax_accumulate's lane mapping and nothing to rescale.  A row of at most 64
+// slots (every fixed row) keeps its (row, type) words in registers between the passes.  A slot whose type is outside [0, R) is
+// treated as padding.  lse[d, r, h] = m + log(l), -inf where (d, r) has no edge, is all the backward keeps.
+constexpr int kRelGatMaxStates = 256;
+
+// load_chunk for a typed row: lane j also takes slot e0 + j's type into *t; a padding slot, a slot past the row's end and a slot whose
+// type is outside [0, num_rels) all leave with *mine == *t == -1.
+__device__ __forceinline__ int load_rel_chunk(const int32_t* row, const int32_t* etype, int64_t e0, int64_t end, int lane, int num_rels,
+                                              int32_t* mine, int32_t* t) {
+    const int n = load_chunk(row, e0, end, lane, mine);
+    *t = *mine >= 0 ? etype[e0 + lane] : -1;
+    if (*t < 0 || *t >= num_rels) *t = *mine = -1;
+    return n;
+}
+
+template <int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void rel_gat_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ row,
+                                                                   const int32_t* __restrict__ etype, int fanout, const float* __restrict__ el,
+                                                                   const float* __restrict__ er, const float* __restrict__ feat,
+                                                                   float* __restrict__ out, float* __restrict__ lse, int64_t n_dst, int num_rels,
+                                                                   int heads, int dim, float slope) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // a_j of the chunk, [edge][head]
+    __shared__ float st_lds[kWavesPerBlock][2 * kRelGatMaxStates]; // per (relation, head): the running max; the running sum, then 1 / sum
+    const auto [lane, wave, n_waves] = wave_rows();
+    float* w = w_lds[threadIdx.x >> 6];
+    float* m_run = st_lds[threadIdx.x >> 6];
+    float* l_run = m_run + kRelGatMaxStates;
+    const int hd = heads * dim, units = hd / VEC, upl = dim / VEC, rh = num_rels * heads;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        const float* er_d = er + d * rh;
+        wave_lds_sync(); // the previous row has read m_run / l_run
+        for (int i = lane; i < rh; i += 64) {
+            m_run[i] = kNegInf;
+            l_run[i] = 0.0f;
+        }
+        int32_t mine0 = -1, t0 = -1; // the first chunk stays in registers
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts: the ballots and shuffles below need every lane
+            int32_t mine, t;
+            load_rel_chunk(row, etype, e0, end, lane, num_rels, &mine, &t);
+            if (e0 == beg) mine0 = mine, t0 = t;
+            wave_lds_sync(); // m_run / l_run are set
+            uint64_t todo = __ballot(t >= 0);
+            while (todo) { // the relations present in the chunk, by first slot
+                const int r = __shfl(t, __builtin_ctzll(todo));
+                const bool in = t == r;
+                todo &= ~__ballot(in);
+                for (int h = 0; h < heads; ++h) { // an online softmax step of group (r, h): lane 0 keeps its max and sum
+                    float e = kNegInf;
+                    if (in) {
+                        const float z = el[(int64_t)mine * heads + h] + er_d[r * heads + h];
+                        e = z > 0.0f ? z : z * slope;
+                    }
+                    const float mo = m_run[r * heads + h];
+                    const float mn = fmaxf(mo, wave_max(e));
+                    const float sum = wave_sum(in ? expf(e - mn) : 0.0f);
+                    if (lane == 0) {
+                        m_run[r * heads + h] = mn;
+                        l_run[r * heads + h] = l_run[r * heads + h] * (mo == mn ? 1.0f : (mo == kNegInf ? 0.0f : expf(mo - mn))) + sum;
+                    }
+                }
+            }
+        }
+        wave_lds_sync();
+        for (int i = lane; i < rh; i += 64) {
+            const float l = l_run[i];
+            lse[d * rh + i] = l > 0.0f ? m_run[i] + logf(l) : kNegInf;
+            l_run[i] = l > 0.0f ? 1.0f / l : 0.0f;
+        }
+        if (beg == end) // no chunk runs: an empty CSR row
+            for (int u = lane; u < units; u += 64) *reinterpret_cast<vf*>(out + d * hd + (int64_t)u * VEC) = vf(0.0f);
+        for (int64_t e0 = beg; e0 < end; e0 += 64) {
+            int32_t mine = mine0, t = t0;
+            int n = end - beg < 64 ? (int)(end - beg) : 64;
+            if (e0 != beg) n = load_rel_chunk(row, etype, e0, end, lane, num_rels, &mine, &t); // wave-uniform
+            wave_lds_sync(); // 1 / l is stored; the previous chunk has read w
+            for (int h = 0; h < heads; ++h) {
+                float a = 0.0f;
+                if (t >= 0) {
+                    const float z = el[(int64_t)mine * heads + h] + er_d[t * heads + h];
+                    a = expf((z > 0.0f ? z : z * slope) - m_run[t * heads + h]) * l_run[t * heads + h];
+                }
+                w[lane * kGatMaxHeads + h] = a;
+            }
+            wave_lds_sync();
+            for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+                const int u = u0 + lane;
+                const int hu = u < units ? u / upl : 0;
+                float* o = out + d * hd + (int64_t)u * VEC;
+                vf acc = vf(0.0f);
+                if (e0 != beg && u < units) acc = *reinterpret_cast<const vf*>(o);
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && u < units) acc += w[j * kGatMaxHeads + hu] * *reinterpret_cast<const vf*>(feat + (int64_t)s * hd + (int64_t)u * VEC);
+                }
+                if (u < units) *reinterpret_cast<vf*>(o) = acc;
+            }
+        }
+    }
+}
+
+// One chunk of the backward below: lane j takes slot e0 + j's (row, type), and leaves in LDS, for every head, a_j = exp(e_j - lse) in w
+// and <g[h, :], feat[row_j, h, :]> in dot (gat_aggregate_backward_kernel's walk: a lane per float of the [H * dim] row, the per-head
+// sums by head_segment_add in a fixed order); with ADD also grad_feat[row_j, h, :] += a_j g[h, :].  -> the chunk's length.
+template <bool ADD>
+__device__ __forceinline__ int rel_gat_chunk_dots(float* w, float* dot, const int32_t* __restrict__ row, const int32_t* __restrict__ etype,
+                                                  int64_t e0, int64_t end, int lane, int num_rels, int heads, int dim,
+                                                  const float* __restrict__ el, const float* __restrict__ er_d,
+                                                  const float* __restrict__ lse_d, const float* __restrict__ feat, const float* __restrict__ g,
+                                                  float* __restrict__ grad_feat, float slope, int32_t* mine_out, int32_t* t_out) {
+    const int hd = heads * dim;
+    int32_t mine, t;
+    const int n = load_rel_chunk(row, etype, e0, end, lane, num_rels, &mine, &t);
+    wave_lds_sync(); // the previous chunk has read w and dot
+    for (int h = 0; h < heads; ++h) {
+        float a = 0.0f;
+        if (t >= 0) {
+            const float z = el[(int64_t)mine * heads + h] + er_d[t * heads + h];
+            a = expf((z > 0.0f ? z : z * slope) - lse_d[t * heads + h]);
+        }
+        w[lane * kGatMaxHeads + h] = a;
+        dot[lane * kGatMaxHeads + h] = 0.0f;
+    }
+    wave_lds_sync();
+    for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: head_segment_add shuffles across every lane
+        const int c = c0 + lane;
+        const int hc = c < hd ? c / dim : 0;
+        const float gc = c < hd ? g[c] : 0.0f;
+        for (int j = 0; j < n; ++j) {
+            const int32_t s = __shfl(mine, j);
+            if (s < 0) continue; // wave-uniform
+            float x = 0.0f;
+            if (c < hd) {
+                x = gc * feat[(int64_t)s * hd + c];
+                if (ADD) unsafeAtomicAdd(grad_feat + (int64_t)s * hd + c, w[j * kGatMaxHeads + hc] * gc);
+            }
+            head_segment_add(dot + j * kGatMaxHeads, x, lane, c0, dim, hd);
+        }
+    }
+    wave_lds_sync();
+    *mine_out = mine, *t_out = t;
+    return n;
+}
+
+// Backward, a_j = exp(e_j - lse[d, etype_j, h]) recomputed from the saved log-sum-exp; with dot_j = <g[d, h, :], feat[row_j, h, :]> and
+// G[r, h] = sum over the edges j of relation r of a_j dot_j -- relation r's <g, out_r>, which the stored out, summed over relations,
+// cannot give:
+//   grad_feat[row_j, h, :] += a_j g[d, h, :],  t_j = a_j (dot_j - G[etype_j, h]) (z_j > 0 ? 1 : slope),
+//   grad_el[row_j, h] += t_j,  grad_er[d, r, h] = sum of t_j over relation r's edges.
+// A first walk over the row's chunks gives a, dot and grad_feat, and adds every group's G in LDS (one masked wave_sum per relation
+// present and head, in chunk order).  A row of one chunk -- every fixed row -- then forms t from the a and dot still in LDS; a longer
+// row walks its source rows a second time.  grad_feat and grad_el take hardware float atomics (zeroed by the caller); grad_er is summed
+// in LDS in a fixed order and written whole.
+template <bool CSR>
+__global__ __launch_bounds__(kBlock) void rel_gat_aggregate_backward_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ row, const int32_t* __restrict__ etype, int fanout,
+    const float* __restrict__ el, const float* __restrict__ er, const float* __restrict__ feat, const float* __restrict__ lse,
+    const float* __restrict__ grad_out, float* __restrict__ grad_feat, float* __restrict__ grad_el, float* __restrict__ grad_er, int64_t n_dst,
+    int num_rels, int heads, int dim, float slope) {
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];     // a_j of the chunk, [edge][head]
+    __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads];   // <g, feat_j>, [edge][head]
+    __shared__ float gs_lds[kWavesPerBlock][2 * kRelGatMaxStates]; // per (relation, head): G, the sum of t_j so far
+    const WaveRows wr = wave_rows();
+    const int lane = wr.lane; // a lambda below captures it
+    float* w = w_lds[threadIdx.x >> 6];
+    float* dot = dot_lds[threadIdx.x >> 6];
+    float* G = gs_lds[threadIdx.x >> 6];
+    float* ter = G + kRelGatMaxStates;
+    const int hd = heads * dim, rh = num_rels * heads;
+    for (int64_t d = wr.wave; d < n_dst; d += wr.n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        const float* g = grad_out + d * hd;
+        const float* er_d = er + d * rh;
+        const float* lse_d = lse + d * rh;
+        wave_lds_sync(); // the previous row has read G / ter
+        for (int i = lane; i < rh; i += 64) {
+            G[i] = 0.0f;
+            ter[i] = 0.0f;
+        }
+        // t_j of the chunk whose a and dot are in LDS, into grad_el and ter
+        auto t_step = [&](int32_t mine, int32_t t) {
+            uint64_t todo = __ballot(t >= 0);
+            while (todo) {
+                const int r = __shfl(t, __builtin_ctzll(todo));
+                const bool in = t == r;
+                todo &= ~__ballot(in);
+                for (int h = 0; h < heads; ++h) {
+                    float tv = 0.0f;
+                    if (in) {
+                        const float z = el[(int64_t)mine * heads + h] + er_d[r * heads + h];
+                        tv = w[lane * kGatMaxHeads + h] * (dot[lane * kGatMaxHeads + h] - G[r * heads + h]) * (z > 0.0f ? 1.0f : slope);
+                        unsafeAtomicAdd(grad_el + (int64_t)mine * heads + h, tv);
+                    }
+                    const float ts = wave_sum(tv);
+                    if (lane == 0) ter[r * heads + h] += ts;
+                }
+            }
+        };
+        int32_t mine = -1, t = -1;
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
+            rel_gat_chunk_dots<true>(w, dot, row, etype, e0, end, lane, num_rels, heads, dim, el, er_d, lse_d, feat, g, grad_feat, slope, &mine, &t);
+            uint64_t todo = __ballot(t >= 0);
+            while (todo) {
+                const int r = __shfl(t, __builtin_ctzll(todo));
+                const bool in = t == r;
+                todo &= ~__ballot(in);
+                for (int h = 0; h < heads; ++h) {
+                    const float gs = wave_sum(in ? w[lane * kGatMaxHeads + h] * dot[lane * kGatMaxHeads + h] : 0.0f);
+                    if (lane == 0) G[r * heads + h] += gs;
+                }
+            }
+        }
+        wave_lds_sync(); // G is whole
+        if (end - beg <= 64) { // wave-uniform: the one chunk's a and dot are still in LDS
+            t_step(mine, t);
+        } else {
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                rel_gat_chunk_dots<false>(w, dot, row, etype, e0, end, lane, num_rels, heads, dim, el, er_d, lse_d, feat, g, nullptr, slope, &mine, &t);
+                t_step(mine, t);
+            }
+        }
+        wave_lds_sync();
+        for (int i = lane; i < rh; i += 64) grad_er[d * rh + i] = ter[i];
+    }
+}
+
 // 16-B accesses need a row length of whole float4s and both row arrays on a 16-B boundary
 bool vec4_ok(int dim, const void* a, const void* b) {
     return dim % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
@@ -847,6 +1085,14 @@ int rel_shape_check(int64_t n_dst, int fanout, int num_rels, int dim) {
     if (n_dst >= 0 && dim >= 1 && num_rels >= 1 && num_rels <= kMaxRels && fanout_ok<CSR>(fanout)) return COALA_OK;
     return CSR ? fail(COALA_EINVAL, "bad block shape (relations 1..%d)", kMaxRels)
                : fail(COALA_EINVAL, "bad block shape (fan-out 1..32, relations 1..%d)", kMaxRels);
+}
+
+template <bool CSR>
+int rel_gat_shape_check(int64_t n_dst, int fanout, int num_rels, int heads, int dim) {
+    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
+    if (num_rels < 1 || num_rels > kMaxRels || num_rels * heads > kRelGatMaxStates)
+        return fail(COALA_EINVAL, "bad block shape (relations 1..%d, relations * heads <= %d)", kMaxRels, kRelGatMaxStates);
+    return COALA_OK;
 }
 
 template <bool CSR>
@@ -1037,6 +1283,36 @@ int rel_sum_backward_launch(int device, const int64_t* indptr, const int32_t* id
     return COALA_OK;
 }
 
+template <bool CSR>
+int rel_gat_launch(int device, const int64_t* indptr, const int32_t* row, const int32_t* etype, int fanout, const float* el, const float* er,
+                   const float* feat, float* out, float* lse, int64_t n_dst, int num_rels, int heads, int dim, float slope, void* stream) {
+    if (int rc = rel_gat_shape_check<CSR>(n_dst, fanout, num_rels, heads, dim)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !row || !etype || !el || !er || !feat || !out || !lse) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    dispatch_vec(vec4_ok(dim, feat, out), [&](auto vec) {
+        hipLaunchKernelGGL((rel_gat_aggregate_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, row,
+                           etype, fanout, el, er, feat, out, lse, n_dst, num_rels, heads, dim, slope);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+template <bool CSR>
+int rel_gat_backward_launch(int device, const int64_t* indptr, const int32_t* row, const int32_t* etype, int fanout, const float* el,
+                            const float* er, const float* feat, const float* lse, const float* grad_out, float* grad_feat, float* grad_el,
+                            float* grad_er, int64_t n_dst, int num_rels, int heads, int dim, float slope, void* stream) {
+    if (int rc = rel_gat_shape_check<CSR>(n_dst, fanout, num_rels, heads, dim)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !row || !etype || !el || !er || !feat || !lse || !grad_out || !grad_feat || !grad_el || !grad_er)
+        return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(rel_gat_aggregate_backward_kernel<CSR>, row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, row, etype, fanout,
+                       el, er, feat, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, num_rels, heads, dim, slope);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
 } // namespace
 
 // The C ABI (include/coala_hip.h): every entry forwards to its launch, the fixed form with <false>, a null indptr and its fan-out, the
@@ -1167,6 +1443,34 @@ int coala_block_rel_sum_csr_backward(int device, const int64_t* indptr, const in
                                      const float* h_src, const float* grad_out, float* grad_src, float* grad_w, int64_t n_dst, int num_rels,
                                      int dim, void* stream) {
     return rel_sum_backward_launch<true>(device, indptr, indices, etype, w, 0, h_src, grad_out, grad_src, grad_w, n_dst, num_rels, dim, stream);
+}
+
+int coala_block_rel_gat_aggregate(int device, const int32_t* row, const int32_t* etype, const float* el, const float* er, const float* feat,
+                                  float* out, float* lse, int64_t n_dst, int fanout, int num_rels, int heads, int dim, float negative_slope,
+                                  void* stream) {
+    return rel_gat_launch<false>(device, nullptr, row, etype, fanout, el, er, feat, out, lse, n_dst, num_rels, heads, dim, negative_slope, stream);
+}
+
+int coala_block_rel_gat_aggregate_backward(int device, const int32_t* row, const int32_t* etype, const float* el, const float* er,
+                                           const float* feat, const float* lse, const float* grad_out, float* grad_feat, float* grad_el,
+                                           float* grad_er, int64_t n_dst, int fanout, int num_rels, int heads, int dim, float negative_slope,
+                                           void* stream) {
+    return rel_gat_backward_launch<false>(device, nullptr, row, etype, fanout, el, er, feat, lse, grad_out, grad_feat, grad_el, grad_er, n_dst,
+                                          num_rels, heads, dim, negative_slope, stream);
+}
+
+int coala_block_rel_gat_aggregate_csr(int device, const int64_t* indptr, const int32_t* row, const int32_t* etype, const float* el,
+                                      const float* er, const float* feat, float* out, float* lse, int64_t n_dst, int num_rels, int heads, int dim,
+                                      float negative_slope, void* stream) {
+    return rel_gat_launch<true>(device, indptr, row, etype, 0, el, er, feat, out, lse, n_dst, num_rels, heads, dim, negative_slope, stream);
+}
+
+int coala_block_rel_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* row, const int32_t* etype, const float* el,
+                                               const float* er, const float* feat, const float* lse, const float* grad_out, float* grad_feat,
+                                               float* grad_el, float* grad_er, int64_t n_dst, int num_rels, int heads, int dim,
+                                               float negative_slope, void* stream) {
+    return rel_gat_backward_launch<true>(device, indptr, row, etype, 0, el, er, feat, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, num_rels,
+                                         heads, dim, negative_slope, stream);
 }
 
 } // extern "C"

@@ -559,6 +559,46 @@ int coala_block_gat_aggregate_csr(int device, const int64_t* indptr, const int32
 int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er,
                                            const float* feat, const float* out, const float* lse, const float* grad_out, float* grad_feat,
                                            float* grad_el, float* grad_er, int64_t n_dst, int heads, int dim, float negative_slope, void* stream);
+/* Relation-typed GAT attention aggregation (the message step of DGL's HeteroGraphConv over one GATConv per edge type, aggregate =
+ * 'sum', on a homogenised block): GAT's rule with the softmax per (destination, relation) and the relations' results summed.  Every
+ * neighbour slot carries `row`, the row of el / feat that its edge reads (int32, -1 on a padding slot; it stands where nbr / indices
+ * stand in the other entries, and the caller guarantees 0 <= row < P), and `etype` (int32), both laid out like the block's index array:
+ * [n_dst, fanout], or [E] beside indptr.  For dst d, head h, relation r and the slots j of d with row_j >= 0 and etype_j == r:
+ *   z_j = el[row_j, h] + er[d, r, h];  e_j = leaky_relu(z_j, negative_slope);  a_j = exp(e_j - m) / sum_k exp(e_k - m) over those j;
+ *   out[d, h, :] = sum_r sum_j a_j feat[row_j, h, :].
+ * el fp32 [P, heads], feat fp32 [P, heads, dim], er fp32 [n_dst, num_rels, heads], out fp32 [n_dst, heads, dim], all contiguous.  A
+ * relation absent from a row contributes nothing; a row without a valid edge gives exactly 0; a valid slot whose type is outside
+ * [0, num_rels) contributes nothing, receives no gradient, and its type is only ever compared.  A padding slot's etype is not read.
+ * Saved state: lse fp32 [n_dst, num_rels, heads], the log-sum-exp of the scores of (d, r), -inf where (d, r) has no edge.
+ * Limits: heads 1..16, fan-out 1..32 or the CSR form (any degree, one wave takes a row 64 slots at a time), num_rels 1..64 and
+ * num_rels * heads <= 256 (a wave keeps two floats per (relation, head) on chip), dim >= 1, heads * dim < 2^31.  Anything else is
+ * refused with COALA_EINVAL ("bad block shape", "null buffer") and nothing is launched; n_dst == 0 launches nothing and reads no pointer.
+ * out and lse are deterministic, and both forms run the same code: bit-identical on a row both can express (a fixed row whose valid
+ * entries come first).
+ * Backward, with g = grad_out [n_dst, heads, dim], a_j = exp(e_j - lse[d, etype_j, h]), dot_j = <g[d, h, :], feat[row_j, h, :]> and
+ * G[r, h] = sum of a_j dot_j over relation r's slots:
+ *   t_j = a_j (dot_j - G[etype_j, h]) (z_j > 0 ? 1 : negative_slope);
+ *   grad_feat[row_j, h, :] += a_j g[d, h, :];  grad_el[row_j, h] += t_j;  grad_er[d, r, h] = sum of t_j over relation r's slots.
+ * grad_feat [P, heads, dim] and grad_el [P, heads] are accumulated with hardware float atomics: the caller zeroes them, and the order
+ * of the additions varies.  grad_er [n_dst, num_rels, heads] is written whole (0 where (d, r) has no edge), deterministic, the same
+ * bits in both forms.  The forward's out is not needed.
+ * Bytes per row of deg valid edges, hd = heads * dim: the forward reads deg * (4 hd + 8 + 4 heads) + 4 num_rels heads and writes
+ * 4 hd + 4 num_rels heads; the backward reads deg * (4 hd + 8) + 4 hd + 8 num_rels heads, adds 4 hd deg through atomics and writes
+ * 4 num_rels heads; a row of more than 64 slots reads its source rows twice in the backward (the second time from the cache). */
+int coala_block_rel_gat_aggregate(int device, const int32_t* row, const int32_t* etype, const float* el, const float* er, const float* feat,
+                                  float* out, float* lse, int64_t n_dst, int fanout, int num_rels, int heads, int dim, float negative_slope,
+                                  void* stream);
+int coala_block_rel_gat_aggregate_backward(int device, const int32_t* row, const int32_t* etype, const float* el, const float* er,
+                                           const float* feat, const float* lse, const float* grad_out, float* grad_feat, float* grad_el,
+                                           float* grad_er, int64_t n_dst, int fanout, int num_rels, int heads, int dim, float negative_slope,
+                                           void* stream);
+int coala_block_rel_gat_aggregate_csr(int device, const int64_t* indptr, const int32_t* row, const int32_t* etype, const float* el,
+                                      const float* er, const float* feat, float* out, float* lse, int64_t n_dst, int num_rels, int heads, int dim,
+                                      float negative_slope, void* stream);
+int coala_block_rel_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* row, const int32_t* etype, const float* el,
+                                               const float* er, const float* feat, const float* lse, const float* grad_out, float* grad_feat,
+                                               float* grad_el, float* grad_er, int64_t n_dst, int num_rels, int heads, int dim,
+                                               float negative_slope, void* stream);
 /* GATv2 attention aggregation (DGL GATv2Conv's message step; its projections are dense and stay outside).  The score does not split
  * into a per-source and a per-destination scalar: for dst d, head h and the valid in-edges j of d with source s_j,
  *   z_jc = feat_src[s_j, h, c] + feat_dst[d, h, c];  e_j = sum_c attn[h, c] * leaky_relu(z_jc, negative_slope);
