@@ -1,7 +1,7 @@
 """Autograd wrappers of the native block ops that `Block` (sampler.py) hands to a model: mean aggregation (SAGEConv's "mean"), weighted
 sum aggregation (DGL's u_mul_e_sum, the edge_weight= path of GraphConv / SAGEConv), max aggregation (DGL's fn.max: SAGEConv's "pool",
-GINConv's "max"), the relation-typed sum (RelGraphConv's message step), GAT / GATv2 attention aggregation and relation-typed GAT
-attention (RelGATConv's message step), on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the kernels are in coala-gnn_amd/csrc/coala_block_ops.hip
+GINConv's "max"), the relation-typed sum (RelGraphConv's message step), GAT / GATv2 attention aggregation, scaled dot-product
+attention (DotGatConv's and HGTConv's message step) and relation-typed GAT attention (RelGATConv's message step), on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the kernels are in coala-gnn_amd/csrc/coala_block_ops.hip
 (C ABI: coala_block_*).  Every op has one forward and one backward body for both block forms, which take the C entry and the block's
 index tensors -- (nbr,) or (indptr, indices); the two Function classes of an op are shells that name the entries, and they stay two
 because Block's callers and the tests tell by the class which form ran."""
@@ -394,3 +394,63 @@ class _RelGatAggregateCSR(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         return _rel_gat_backward(ctx, grad_out, _lib.coala_block_rel_gat_aggregate_csr_backward) + (None,) * 6
+
+
+def _dot_gat_forward(ctx, q, k, v, rows, scale, entry, index):
+    """Per head, a softmax of scale * <q[d], k[row]> over row d's entries with row >= 0, then the weighted sum of v[row]
+    (coala_block_dot_gat_aggregate[_csr]); no [E, H, D] intermediate.  rows (int32, -1: no edge) is laid out like the block's index
+    array, which the kernel reads only for its shape: rows stands in its place.  out and the log-sum-exp per (row, head) are the state
+    of the backward, kept only when something needs a gradient."""
+    qc, kc, vc = q.contiguous(), k.contiguous(), v.contiguous()
+    idx, n_dst, fan = _block(index)
+    H, D = kc.shape[1], kc.shape[2]
+    out = torch.empty((n_dst, H, D), dtype=torch.float32, device=kc.device)
+    lse = torch.empty((n_dst, H), dtype=torch.float32, device=kc.device)
+    _capi.check(entry(kc.device.index or 0, *idx[:-1], rows.data_ptr(), qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                      n_dst, *fan, H, D, scale, current_stream()))
+    if any(ctx.needs_input_grad[:3]):
+        ctx.save_for_backward(qc, kc, vc, out, lse, rows, *index)
+    ctx.scale = scale
+    return out
+
+
+def _dot_gat_backward(ctx, grad_out, entry):
+    """-> (grad_q, grad_k, grad_v), one launch (coala_block_dot_gat_aggregate[_csr]_backward); a gradient nobody asked for is neither
+    computed nor allocated."""
+    need_q, need_k, need_v = ctx.needs_input_grad[:3]
+    if not (need_q or need_k or need_v):
+        return None, None, None
+    q, k, v, out, lse, rows, *index = ctx.saved_tensors
+    idx, n_dst, fan = _block(index)
+    g = grad_out.contiguous()
+    grad_q = torch.empty_like(q) if need_q else None
+    grad_k = torch.zeros_like(k) if need_k else None
+    grad_v = torch.zeros_like(v) if need_v else None
+    _capi.check(entry(k.device.index or 0, *idx[:-1], rows.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                      g.data_ptr(), _ptr(grad_q), _ptr(grad_k), _ptr(grad_v), n_dst, *fan, k.shape[1], k.shape[2], ctx.scale, current_stream()))
+    return grad_q, grad_k, grad_v
+
+
+class _DotGatAggregate(torch.autograd.Function):
+    """Scaled dot-product attention on a fixed block (coala_block_dot_gat_aggregate): one kernel forward, one backward (gradients for q,
+    k and v)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rows, scale, nbr):
+        return _dot_gat_forward(ctx, q, k, v, rows, scale, _lib.coala_block_dot_gat_aggregate, (nbr,))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _dot_gat_backward(ctx, grad_out, _lib.coala_block_dot_gat_aggregate_backward) + (None,) * 3
+
+
+class _DotGatAggregateCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_dot_gat_aggregate_csr): rows has one value per entry of indices."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rows, scale, indptr, indices):
+        return _dot_gat_forward(ctx, q, k, v, rows, scale, _lib.coala_block_dot_gat_aggregate_csr, (indptr, indices))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _dot_gat_backward(ctx, grad_out, _lib.coala_block_dot_gat_aggregate_csr_backward) + (None,) * 4

@@ -7,14 +7,16 @@ SAGE take edge_weight=<edata key> and then hand block.edata[key] to their layers
 SAGE(aggregator_type='pool') and GIN (--model_type gin) are the models on the native max aggregation (Block.max_aggregate).  RGCN
 (--model_type rgcn) mirrors examples/models.py:RGCN on a homogenised graph: RelGraphConv layers, one weight matrix per edge type, on the
 native relation-typed sum (Block.rel_sum_aggregate).  RGAT and RSAGE (--model_type rgat|rsage) mirror examples/models.py:RGAT and :RSAGE
-the same way, on RelGATConv (the native relation-typed attention, Block.rel_gat_aggregate) and RelSAGEConv."""
+the same way, on RelGATConv (the native relation-typed attention, Block.rel_gat_aggregate) and RelSAGEConv.  HGT (--model_type hgt) is the
+Heterogeneous Graph Transformer on HGTConv layers, and DotGAT is GAT's shape on DotGatConv layers; both attend with the native scaled
+dot-product kernel (Block.dot_gat_aggregate)."""
 import time
 
 import torch
 
-from .nn import GATConv, GATv2Conv, GINConv, GraphConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv
+from .nn import DotGatConv, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv
 
-__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "RGAT", "RSAGE", "train_steps", "FlatGradAllReduce"]
+__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -221,6 +223,55 @@ class RSAGE(torch.nn.Module):
             if i + 1 < len(self.layers):
                 h = self.dropout(torch.relu(h))
         return self.linear(h)
+
+
+class HGT(torch.nn.Module):
+    """Heterogeneous Graph Transformer on a homogenised heterograph (RGCN's input, plus an integer type per node): num_layers HGTConv
+    layers of num_heads heads of h_feats // num_heads features, and a final Linear(h_feats, num_classes).  HGTConv brings its own skip
+    connection, dropout and LayerNorm (use_norm), so nothing stands between the layers.  ntype is the graph's node-type table
+    [num_nodes], given at construction or per call (forward(blocks, x, ntype=...)); every layer indexes it with block.srcdata['_ID'].
+    Every layer reads its edge types from block.edata[etype_key], so the blocks must come from a sampler made with edge_ids=True."""
+
+    def __init__(self, in_feats, h_feats, num_classes, num_layers, num_heads, num_ntypes, num_rels, dropout=0.2, use_norm=True, ntype=None,
+                 etype_key="etype"):
+        super().__init__()
+        if h_feats % num_heads:
+            raise ValueError(f"h_feats {h_feats} is not a multiple of num_heads {num_heads}")
+        dims = [in_feats] + [h_feats] * (num_layers - 1)
+        self.layers = torch.nn.ModuleList(HGTConv(dims[i], h_feats // num_heads, num_heads, num_ntypes, num_rels, dropout, use_norm)
+                                          for i in range(num_layers))
+        self.linear = torch.nn.Linear(h_feats, num_classes)
+        self.ntype, self.num_rels, self.etype_key = ntype, num_rels, etype_key
+
+    def forward(self, blocks, x, ntype=None):
+        table = self.ntype if ntype is None else ntype
+        if table is None:
+            raise ValueError("HGT needs the graph's node-type table [num_nodes]: HGT(..., ntype=) or forward(blocks, x, ntype=)")
+        h = x
+        for layer, block in zip(self.layers, blocks):
+            etype = _block_etypes(block, self.etype_key, "HGT").to(h.device)
+            nt = table[block.srcdata["_ID"].to(table.device)].to(h.device)
+            h = layer(block, (h, block.dst_rows(h)), nt, etype)
+        return self.linear(h)
+
+
+class DotGAT(torch.nn.Module):
+    """GAT's shape on DotGatConv layers: n_layers layers of num_heads heads, no activation between them, the heads flattened between
+    layers; the last layer's heads are averaged and passed through log_softmax."""
+
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, num_heads):
+        super().__init__()
+        dims = [in_feats] + [n_hidden * num_heads] * (n_layers - 1)
+        outs = [n_hidden] * (n_layers - 1) + [n_classes]
+        self.layers = torch.nn.ModuleList(DotGatConv(dims[i], outs[i], num_heads) for i in range(n_layers))
+
+    def forward(self, blocks, x):
+        h = x
+        for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+            h = layer(block, h)
+            if i + 1 < len(self.layers):
+                h = h.flatten(1)
+        return h.mean(1).log_softmax(dim=-1)
 
 
 class FlatGradAllReduce(object):

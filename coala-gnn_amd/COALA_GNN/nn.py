@@ -11,10 +11,13 @@ Block.max_aggregate (DGL's fn.max), a native kernel as well; GINConv's 'sum' is 
 RelGraphConv (one weight matrix per edge type) sums the messages per relation with Block.rel_sum_aggregate, a native kernel, and applies
 all its weight matrices in one GEMM.  RelGATConv and RelSAGEConv are the layers of the reference's heterogeneous models RGAT and RSAGE
 on a homogenised block -- HeteroGraphConv over one GATConv, or one SAGEConv 'gcn', per edge type, summed: RelGATConv's softmax per
-(destination, relation) is Block.rel_gat_aggregate, a native kernel; RelSAGEConv needs Block.rel_sum_aggregate and one GEMM."""
+(destination, relation) is Block.rel_gat_aggregate, a native kernel; RelSAGEConv needs Block.rel_sum_aggregate and one GEMM.
+DotGatConv and HGTConv (the Heterogeneous Graph Transformer, on a homogenised block with a type per node and per edge) attend with a
+scaled dot product, Block.dot_gat_aggregate, a native kernel without [E, H, D] intermediates; HGTConv applies its per-relation D x D
+matrices per (source, relation) pair, not per edge, and folds the relation prior into the attention matrix."""
 import torch
 
-__all__ = ["GATConv", "GATv2Conv", "GraphConv", "SAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv"]
+__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv"]
 
 
 class GATConv(torch.nn.Module):
@@ -378,6 +381,22 @@ def _check_num_rels(num_rels):
         raise ValueError(f"num_rels {num_rels!r}: 1..64 relations")
 
 
+def _pack_pairs(block, etype, num_rels, dev):
+    """The (source, relation) pairs that occur on a valid edge of the block, sorted by relation * num_src + source so that a relation's
+    pairs are contiguous: -> (rows, pair_rel, pair_src, counts).  rows (int64, one value per neighbour slot, flat) is the slot's pair,
+    -1 on a padding slot and on a type outside [0, num_rels); pair_rel / pair_src [P] are every pair's relation and local source;
+    counts is the number of pairs per relation as a Python list -- the one host read."""
+    _, src = block._slots(dev)
+    t = etype.reshape(-1).to(device=dev, dtype=torch.int64)
+    keep = (src >= 0) & (t >= 0) & (t < num_rels)
+    pairs, inv = torch.unique(t[keep] * block.num_src + src[keep], return_inverse=True)   # sorted: grouped by relation
+    rows = torch.full_like(src, -1)
+    rows[keep] = inv
+    pair_rel, pair_src = pairs // block.num_src, pairs % block.num_src
+    counts = torch.bincount(pair_rel, minlength=num_rels).tolist()                        # the host read
+    return rows, pair_rel, pair_src, counts
+
+
 class RelGATConv(torch.nn.Module):
     """Graph attention with one GATConv per edge type, summed over the types, on a homogenised block: what DGL computes with
     HeteroGraphConv({etype: GATConv(in_feats, out_feats, num_heads)}, aggregate='sum') -- the layer of the reference's RGAT model -- in
@@ -451,15 +470,7 @@ class RelGATConv(torch.nn.Module):
         h_src, h_dst = feat
         R, H, D = self.num_rels, self._num_heads, self._out_feats
         h_src, h_dst = self.feat_drop(h_src), self.feat_drop(h_dst)
-        dev = h_src.device
-        _, src = block._slots(dev)
-        t = etype.reshape(-1).to(device=dev, dtype=torch.int64)
-        keep = (src >= 0) & (t >= 0) & (t < R)
-        pairs, inv = torch.unique(t[keep] * block.num_src + src[keep], return_inverse=True)   # sorted: grouped by relation
-        rows = torch.full_like(src, -1)
-        rows[keep] = inv
-        pair_rel, pair_src = pairs // block.num_src, pairs % block.num_src
-        counts = torch.bincount(pair_rel, minlength=R).tolist()                              # the host read
+        rows, pair_rel, pair_src, counts = _pack_pairs(block, etype, R, h_src.device)
         parts, off = [], 0
         for r, c in enumerate(counts):
             if c:
@@ -522,3 +533,149 @@ class RelSAGEConv(torch.nn.Module):
         if self.activation is not None:
             rst = self.activation(rst)
         return rst
+
+
+class DotGatConv(torch.nn.Module):
+    """Dot-product attention layer (DGL 1.x DotGatConv; PyG's TransformerConv without edge features, bias, root weight and a separate
+    value projection).  forward(block, feat) -> [num_dst, H, out_feats]; feat is h_src or (h_src, h_dst) -- without h_dst the destination
+    rows are block.dst_rows(h_src).  For destination d, head h and the valid in-edges j of d (source s_j):
+        q = fc_dst(h_dst).view(-1, H, D);   k = v = fc_src(h_src).view(-1, H, D)
+        a_j = softmax over d's in-edges of <q[d, h], k[s_j, h]> / sqrt(D);   out[d, h, :] = sum_j a_j v[s_j, h, :]
+    A destination without an in-edge gets zeros (DGL's allow_zero_in_degree=True).  Parameters, DGL's names and shapes: fc.weight
+    [H * D, in_feats] for an int in_feats (one projection for both sides), fc_src.weight [H * D, in_src] and fc_dst.weight
+    [H * D, in_dst] for a pair; no bias.  Initialisation: torch.nn.Linear's default, as in DGL.  The attention step is
+    Block.dot_gat_aggregate, a native kernel.  get_attention is not provided."""
+
+    def __init__(self, in_feats, out_feats, num_heads):
+        super().__init__()
+        self._num_heads, self._out_feats = num_heads, out_feats
+        if isinstance(in_feats, (tuple, list)):
+            self.fc_src = torch.nn.Linear(in_feats[0], out_feats * num_heads, bias=False)
+            self.fc_dst = torch.nn.Linear(in_feats[1], out_feats * num_heads, bias=False)
+        else:
+            self.fc = torch.nn.Linear(in_feats, out_feats * num_heads, bias=False)
+
+    def forward(self, block, feat):
+        h_src, h_dst = feat if isinstance(feat, (tuple, list)) else (feat, None)
+        H, D = self._num_heads, self._out_feats
+        fc_src, fc_dst = (self.fc, self.fc) if hasattr(self, "fc") else (self.fc_src, self.fc_dst)
+        k = fc_src(h_src).view(-1, H, D)
+        if h_dst is None:
+            q = block.dst_rows(k) if fc_dst is fc_src else fc_dst(block.dst_rows(h_src)).view(-1, H, D)
+        else:
+            q = fc_dst(h_dst).view(-1, H, D)
+        return block.dot_gat_aggregate(q, k, k, scale=float(D) ** -0.5)
+
+
+def _typed_linear(x, W, types, counts):
+    """x[i] @ W[types[i]] for x [N, in], W [T, in, out]: one GEMM per type on its slice of the rows sorted by type.  counts: rows per type,
+    a Python list (the caller's host read)."""
+    if W.shape[0] == 1:
+        return x @ W[0]
+    order = torch.argsort(types, stable=True)
+    xs = x[order]
+    parts, off = [], 0
+    for t, c in enumerate(counts):
+        if c:
+            parts.append(xs[off:off + c] @ W[t])
+            off += c
+    ys = torch.cat(parts) if parts else x.new_zeros((0, W.shape[2]))
+    back = torch.empty_like(order)
+    back[order] = torch.arange(order.numel(), device=order.device)
+    return ys[back]
+
+
+class HGTConv(torch.nn.Module):
+    """Heterogeneous Graph Transformer layer (Hu et al., "Heterogeneous Graph Transformer"; DGL 1.x HGTConv) on a homogenised block:
+    one id space, an integer type per node and per edge.
+
+    forward(block, x, ntype, etype) -> [num_dst, H * D], H = num_heads, D = head_size.  x is h_src or (h_src, h_dst) -- without h_dst the
+    destination rows are block.dst_rows(h_src); ntype [num_src] (any integer dtype) is the type of every source node in the block's
+    source order (the destinations' types are block.dst_rows(ntype)); etype (any integer dtype) has one value per neighbour slot,
+    shaped like block.edata['_ID'].  For destination d and the valid in-edges j of d (source s_j, type r_j), tau(.) a node's type:
+        K = x_s @ k_weight[tau(s)],  V = x_s @ v_weight[tau(s)],  Q = x_d @ q_weight[tau(d)],  each viewed as [H, D]
+        e_j[h] = (K[s_j, h] @ rel_att[r_j, h]) . Q[d, h] * rel_pri[r_j, h] / sqrt(D);   a = softmax of e over all of d's in-edges
+        m[d, h] = sum_j a_j[h] (V[s_j, h] @ rel_msg[r_j, h])
+        y = dropout(m.view(H * D) @ a_weight[tau(d)]);   alpha = sigmoid(skip[tau(d)])
+        out = y * alpha + (x_d if in_size == H * D else x_d @ residual_w) * (1 - alpha);   then LayerNorm, if use_norm
+    An edge whose type is outside [0, num_etypes) sends nothing; a destination without an edge has m = 0, so the skip path alone remains;
+    a node type outside [0, num_ntypes) raises ValueError.
+    Parameters, stacked: k_weight, q_weight, v_weight [T, in_size, H * D]; a_weight [T, H * D, H * D]; rel_att, rel_msg [R, H, D, D];
+    rel_pri [R, H] (ones); skip [T] (ones); residual_w [in_size, H * D] only when in_size != H * D (Xavier-uniform); norm.weight /
+    norm.bias with use_norm.  The typed weights are initialised as DGL's TypedLinear does, uniform in +-1/sqrt(fan-in) per slice.
+    DGL is not installed where this was written.  The correspondence to DGL's names, written from memory of its source
+    (dgl/nn/pytorch/conv/hgtconv.py) and not checked against a checkpoint: k_weight = linear_k.W, q_weight = linear_q.W, v_weight =
+    linear_v.W, a_weight = linear_a.W; rel_att[:, h] = relation_att.{h}.W, rel_msg[:, h] = relation_msg.{h}.W ([R, D, D] each);
+    rel_pri[:, h] = relation_pri.{h} ([R]); skip, residual_w and norm.* keep their names.
+    How it runs: the typed linears are one GEMM per node type on a sorted slice.  The D x D relation matrices are applied per (source,
+    relation) pair that occurs on a valid edge -- P <= E rows, RelGATConv's packing -- not per edge: per relation one batched matmul
+    over the heads for K and one for V, on that relation's slice of the pairs, with rel_pri[r, h] / sqrt(D) folded into rel_att[r, h]
+    (the score is linear in K).  One Block.dot_gat_aggregate call in its packed form then does the softmax over all of a node's
+    in-edges and the weighted sum, in a native kernel that needs no edge types.  Host reads per call: the node counts per type (source
+    and destination side together, one read; they also carry the range check) and the pair counts per relation (one read).
+    Attention dropout is not provided."""
+
+    def __init__(self, in_size, head_size, num_heads, num_ntypes, num_etypes, dropout=0.2, use_norm=False):
+        super().__init__()
+        for name, n in (("num_ntypes", num_ntypes), ("num_etypes", num_etypes)):
+            if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+                raise ValueError(f"{name} {n!r}: at least one type")
+        self.in_size, self.head_size, self.num_heads = in_size, head_size, num_heads
+        self.num_ntypes, self.num_etypes = num_ntypes, num_etypes
+        T, R, H, D = num_ntypes, num_etypes, num_heads, head_size
+        P = torch.nn.Parameter
+        self.k_weight, self.q_weight, self.v_weight = (P(torch.empty(T, in_size, H * D)) for _ in range(3))
+        self.a_weight = P(torch.empty(T, H * D, H * D))
+        self.rel_att, self.rel_msg = P(torch.empty(R, H, D, D)), P(torch.empty(R, H, D, D))
+        self.rel_pri = P(torch.ones(R, H))
+        self.skip = P(torch.ones(T))
+        self.residual_w = P(torch.empty(in_size, H * D)) if in_size != H * D else None
+        self.drop = torch.nn.Dropout(dropout)
+        self.norm = torch.nn.LayerNorm(H * D) if use_norm else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            for w in (self.k_weight, self.q_weight, self.v_weight, self.a_weight, self.rel_att, self.rel_msg):
+                bound = 1.0 / w.shape[-2] ** 0.5            # dgl.nn.TypedLinear.reset_parameters: the same bound for every slice
+                w.uniform_(-bound, bound)
+            self.rel_pri.fill_(1.0)
+            self.skip.fill_(1.0)
+            if self.residual_w is not None:
+                torch.nn.init.xavier_uniform_(self.residual_w)
+
+    def forward(self, block, x, ntype, etype):
+        h_src, h_dst = x if isinstance(x, (tuple, list)) else (x, block.dst_rows(x))
+        T, R, H, D = self.num_ntypes, self.num_etypes, self.num_heads, self.head_size
+        dev = h_src.device
+        if not isinstance(ntype, torch.Tensor) or ntype.is_floating_point() or ntype.is_complex() or ntype.dtype == torch.bool:
+            raise ValueError("node types must be an integer tensor")
+        if tuple(ntype.shape) != (block.num_src,):
+            raise ValueError(f"node types of shape {tuple(ntype.shape)}: this block takes one per source node, ({block.num_src},)")
+        nt_src = ntype.to(device=dev, dtype=torch.int64)
+        nt_dst = block.dst_rows(nt_src)
+        binned = [torch.bincount(torch.where((t < 0) | (t >= T), T, t), minlength=T + 1) for t in (nt_src, nt_dst)]
+        cnt = torch.cat(binned).tolist()                                                     # host read 1: nodes per type
+        cnt_src, cnt_dst = cnt[:T], cnt[T + 1: 2 * T + 1]
+        if cnt[T] or cnt[2 * T + 1]:
+            raise ValueError(f"node types must lie in [0, {T}) (num_ntypes={T})")
+        k = _typed_linear(h_src, self.k_weight, nt_src, cnt_src).view(-1, H, D)
+        v = _typed_linear(h_src, self.v_weight, nt_src, cnt_src).view(-1, H, D)
+        q = _typed_linear(h_dst, self.q_weight, nt_dst, cnt_dst).view(-1, H, D)
+        rows, pair_rel, pair_src, counts = _pack_pairs(block, etype, R, dev)                 # host read 2: pairs per relation
+        att = self.rel_att * (self.rel_pri * (float(D) ** -0.5)).view(R, H, 1, 1)            # the prior and 1 / sqrt(D), folded in
+        k_parts, v_parts, off = [], [], 0
+        for r, c in enumerate(counts):
+            if c:
+                s = pair_src[off:off + c]
+                k_parts.append(torch.bmm(k[s].transpose(0, 1), att[r]).transpose(0, 1))       # [c, H, D]
+                v_parts.append(torch.bmm(v[s].transpose(0, 1), self.rel_msg[r]).transpose(0, 1))
+                off += c
+        k_pairs = torch.cat(k_parts) if k_parts else k.new_zeros((0, H, D))
+        v_pairs = torch.cat(v_parts) if v_parts else v.new_zeros((0, H, D))
+        m = block.dot_gat_aggregate(q, k_pairs, v_pairs, rows=rows.to(torch.int32).view(etype.shape), scale=1.0, validate=False)
+        y = self.drop(_typed_linear(m.reshape(-1, H * D), self.a_weight, nt_dst, cnt_dst))
+        alpha = torch.sigmoid(self.skip[nt_dst]).unsqueeze(-1)
+        res = h_dst if self.residual_w is None else h_dst @ self.residual_w
+        out = y * alpha + res * (1 - alpha)
+        return out if self.norm is None else self.norm(out)

@@ -11,7 +11,7 @@ import torch
 
 from COALA_GNN_Pybind import _capi, current_stream
 
-from .block_ops import (_GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
+from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
                         _MeanAggregateCSR, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _WeightedSum, _WeightedSumCSR)
 
 __all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "sort_csc_by_etype", "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT",
@@ -572,6 +572,77 @@ class Block(object):
         a = p / l[key]
         out = torch.zeros((self.num_dst,) + tuple(feat2.shape[1:]), dtype=feat2.dtype, device=dev)
         return out.index_add(0, dst, a.unsqueeze(-1).to(feat2.dtype) * feat2[row])
+
+
+    def _dot_gat_args(self, q, k, v, rows, scale):
+        """The checks of dot_gat_aggregate / dot_gat_aggregate_torch -> the scale as a float (None: D ** -0.5)."""
+        slots = self.indices if self.nbr is None else self.nbr
+        P = "P" if rows is not None else str(self.num_src)
+        ok = k.dim() == 3 and tuple(v.shape) == tuple(k.shape) and tuple(q.shape) == (self.num_dst,) + tuple(k.shape[1:])
+        if ok and rows is None:
+            ok = k.shape[0] == self.num_src
+        if not ok:
+            raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}: this block takes [{self.num_dst}, H, D], "
+                             f"[{P}, H, D] and [{P}, H, D]")
+        if rows is not None:
+            if not isinstance(rows, torch.Tensor) or rows.is_floating_point() or rows.is_complex() or rows.dtype == torch.bool:
+                raise ValueError("rows must be an integer tensor")
+            if tuple(rows.shape) != tuple(slots.shape):
+                raise ValueError(f"rows of shape {tuple(rows.shape)}: this block takes one per neighbour slot, {tuple(slots.shape)}")
+        return float(k.shape[2]) ** -0.5 if scale is None else float(scale)
+
+    def dot_gat_aggregate(self, q, k, v, rows=None, scale=None, validate=True):
+        """Scaled dot-product attention (the message step of DGL's DotGatConv and HGTConv, PyG's TransformerConv without edge features):
+        for every dst node d and head h, a softmax over d's in-edges j of scale * <q[d, h, :], k[.., h, :]>, then sum_j a_j v[.., h, :]
+        -> [num_dst, H, D]; scale=None means D ** -0.5.  q is [num_dst, H, D].  Which row of k / v an edge reads:
+          rows=None (dense): k and v are [num_src, H, D] and the edge in a slot reads the row of its source, the block's own index;
+          rows given (packed): k and v are [P, H, D]; rows has one integer per neighbour slot -- rel_gat_aggregate's packed form -- and
+            the edge in slot j reads row rows_j < P (IndexError otherwise; on the native path that check is one host read per call,
+            which validate=False skips for a caller whose rows are an inverse index by construction).  A slot is then an edge exactly
+            when rows_j >= 0: the block's own index array is not read.
+        A dst node without an edge gets zeros.  k is v is allowed: autograd sums the two gradients.  Native kernels (one forward, one
+        backward with gradients for q, k and v, no [E, H, D] intermediate) under the conditions of gat_aggregate -- fp32 GPU tensors,
+        fan-out <= 32 or the ragged form, H <= 16 -- for tables that are not empty; dot_gat_aggregate_torch otherwise.  rows that is
+        already contiguous int32 is handed to the kernels as it is."""
+        scale = self._dot_gat_args(q, k, v, rows, scale)
+        native = (all(t.is_cuda and t.dtype == torch.float32 for t in (q, k, v)) and (rows is None or rows.is_cuda) and k.shape[1] <= 16
+                  and 0 < k.shape[0] < (1 << 31) and k.shape[1] > 0 and k.shape[2] > 0)
+        index = self._native_index() if native else None
+        if index is None:
+            return self.dot_gat_aggregate_torch(q, k, v, rows, scale)
+        if rows is None:
+            row = index[-1]
+        else:
+            if validate and rows.numel() and int(rows.max()) >= k.shape[0]:   # one host read: the kernels do not check an index they are given
+                raise IndexError(f"rows holds {int(rows.max())}: k and v have {k.shape[0]} rows")
+            row = rows
+            if row.dtype != torch.int32:
+                row = row.clamp(-1, (1 << 31) - 1).to(torch.int32)
+            row = row.contiguous()
+        fn = _DotGatAggregateCSR if self.nbr is None else _DotGatAggregate
+        return fn.apply(q, k, v, row, scale, *index)
+
+    def dot_gat_aggregate_torch(self, q, k, v, rows=None, scale=None):
+        """dot_gat_aggregate in plain torch, any device and dtype, both block forms, the dense and the packed form: an edge-list softmax
+        that materialises the gathered [E, H, D] rows of k and v and their product with q.  The fallback of dot_gat_aggregate, and its
+        reference."""
+        scale = self._dot_gat_args(q, k, v, rows, scale)
+        dev = k.device
+        dst, src = self._slots(dev)
+        row = src if rows is None else rows.reshape(-1).to(device=dev, dtype=torch.int64)
+        keep = row >= 0
+        dst, row = dst[keep], row[keep]
+        if rows is not None and row.numel() and int(row.max()) >= k.shape[0]:   # the dense form's rows are the block's own
+            raise IndexError(f"rows holds {int(row.max())}: k and v have {k.shape[0]} rows")
+        H = k.shape[1]
+        e = (q[dst] * k[row]).sum(-1) * scale                                                   # [E, H]
+        m = torch.full((self.num_dst, H), float("-inf"), dtype=e.dtype, device=dev)
+        m = m.scatter_reduce(0, dst.unsqueeze(1).expand(-1, H), e.detach(), "amax").detach()   # the shift cancels in the softmax
+        p = torch.exp(e - m[dst])
+        l = torch.zeros((self.num_dst, H), dtype=e.dtype, device=dev).index_add(0, dst, p)
+        a = p / l[dst]
+        out = torch.zeros((self.num_dst,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev)
+        return out.index_add(0, dst, a.unsqueeze(-1).to(v.dtype) * v[row])
 
 
 class NeighborSampler(object):

@@ -154,7 +154,11 @@ SYMBOLS = {
     "coala_block_rel_gat_aggregate_backward": (_I, [_I] + [_VP] * 10 + [_I64, _I, _I, _I, _I, C.c_float, _VP]),
     "coala_block_rel_gat_aggregate_csr": (_I, [_I] + [_VP] * 8 + [_I64, _I, _I, _I, C.c_float, _VP]),
     "coala_block_rel_gat_aggregate_csr_backward": (_I, [_I] + [_VP] * 11 + [_I64, _I, _I, _I, C.c_float, _VP]),
-    "coala_shm_open": (_I, [C.c_char_p, _U64, _I, _I, C.POINTER(_VP)]),
+    "coala_block_dot_gat_aggregate": (_I, [_I] + [_VP] * 6 + [_I64, _I, _I, _I, C.c_float, _VP]),
+    "coala_block_dot_gat_aggregate_backward": (_I, [_I] + [_VP] * 10 + [_I64, _I, _I, _I, C.c_float, _VP]),
+    "coala_block_dot_gat_aggregate_csr": (_I, [_I] + [_VP] * 7 + [_I64, _I, _I, C.c_float, _VP]),
+    "coala_block_dot_gat_aggregate_csr_backward": (_I, [_I] + [_VP] * 11 + [_I64, _I, _I, C.c_float, _VP]),
+    "coala_shm_open":(_I, [C.c_char_p, _U64, _I, _I, C.POINTER(_VP)]),
     "coala_shm_host_ptr": (_VP, [_VP]),
     "coala_shm_device_ptr": (_VP, [_VP]),
     "coala_shm_close": (_I, [_VP, _I]),

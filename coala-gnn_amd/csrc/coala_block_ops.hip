@@ -1,7 +1,8 @@
 // coala_block_ops.hip -- what a model computes on a sampled block (coala_sampler.hip makes the blocks), for gfx950: mean aggregation
 // (DGL's SAGEConv "mean"), weighted sum aggregation (DGL's u_mul_e_sum: GraphConv / SAGEConv with edge_weight=), max aggregation
 // (DGL's fn.max: SAGEConv "pool", GINConv "max"), the relation-typed sum (RelGraphConv's message step), GAT / GATv2 attention
-// aggregation (GATConv's and GATv2Conv's message steps) and relation-typed GAT attention (a softmax per destination and relation), forward and backward, on fixed blocks (nbr_local[n_dst, fanout], -1 = no
+// aggregation (GATConv's and GATv2Conv's message steps), scaled dot-product attention (DotGatConv's and HGTConv's message step) and
+// relation-typed GAT attention (a softmax per destination and relation), forward and backward, on fixed blocks (nbr_local[n_dst, fanout], -1 = no
 // neighbour) and on the CSR blocks of full layers.  Stateless entry points: no handle, every launch on the caller's stream.
 //
 // Layout of the file: the device helpers every kernel walks a row with (which rows a wave takes, a row's bounds in either block form,
@@ -528,6 +529,140 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_backward_kernel(const 
             for (int k = 1; k < kWavesPerBlock; ++k) sum += w_lds[k][c];
             prow[c] = sum;
         }
+    }
+}
+
+// Scaled dot-product attention on a block (the message step of DGL's DotGatConv and HGTConv, PyG's TransformerConv without edge
+// features; the projections stay in torch).  Every slot carries the row of k / v its edge reads (row, -1 = no edge; the block's own
+// index array in the dense form).  For dst d, head h and the slots j of d with row_j >= 0:
+//   e_j = scale <q[d, h, :], k[row_j, h, :]>,  a_j = softmax of e over the row,  out[d, h, :] = sum_j a_j v[row_j, h, :]
+// gatv2_aggregate_kernel with another score pass: a lane per float of the [H * D] row, 64 floats at a time, q[d] of the pass in
+// registers, the chunk's edges in the inner loop, the per-head sums added into the LDS [edge][head] array by head_segment_add in a
+// fixed order; the scale is applied to the finished sum.  The weighted sum then reads the chunk's v rows.  Nothing of size E is written.
+// e[j * kGatMaxHeads + h] += <q[d, h, :], k[row_j, h, :]> for the n slots of a chunk; with DOT also dot[..] += <g[h, :], v[row_j, h, :]>.
+template <bool DOT>
+__device__ __forceinline__ void dot_score_pass(float* e, float* dot, int32_t mine, int n, const float* __restrict__ k,
+                                               const float* __restrict__ qd, const float* __restrict__ v, const float* __restrict__ g, int lane,
+                                               int hd, int dim) {
+    for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: head_segment_add shuffles across every lane
+        const int c = c0 + lane;
+        const bool in = c < hd;
+        const float qc = in ? qd[c] : 0.0f;
+        const float gc = DOT && in ? g[c] : 0.0f;
+        for (int j = 0; j < n; ++j) {
+            const int32_t s = __shfl(mine, j);
+            if (s < 0) continue; // wave-uniform
+            head_segment_add(e + j * kGatMaxHeads, in ? qc * k[(int64_t)s * hd + c] : 0.0f, lane, c0, dim, hd);
+            if (DOT) head_segment_add(dot + j * kGatMaxHeads, in ? gc * v[(int64_t)s * hd + c] : 0.0f, lane, c0, dim, hd);
+        }
+    }
+}
+
+template <int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void dot_gat_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ row, int fanout,
+                                                                   const float* __restrict__ q, const float* __restrict__ k,
+                                                                   const float* __restrict__ v, float* __restrict__ out, float* __restrict__ lse,
+                                                                   int64_t n_dst, int heads, int dim, float scale) {
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads]; // the chunk's dot products first, [edge][head]
+    __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];
+    const auto [lane, wave, n_waves] = wave_rows();
+    const SoftmaxLds s = softmax_lds(w_lds[threadIdx.x >> 6], st_lds[threadIdx.x >> 6]);
+    const int hd = heads * dim, units = hd / VEC, upl = dim / VEC;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        softmax_row_begin(s, lane, heads);
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+            int32_t mine;
+            const int n = load_chunk(row, e0, end, lane, &mine);
+            wave_lds_sync(); // the previous chunk has read w and scl; m_run / l_run are set
+            for (int h = 0; h < heads; ++h) s.w[lane * kGatMaxHeads + h] = 0.0f;
+            wave_lds_sync();
+            dot_score_pass<false>(s.w, nullptr, mine, n, k, q + d * hd, nullptr, nullptr, lane, hd, dim);
+            wave_lds_sync();
+            for (int h = 0; h < heads; ++h) // lane j reads and rewrites only edge j's words
+                softmax_chunk_step(s, h, mine >= 0 ? scale * s.w[lane * kGatMaxHeads + h] : kNegInf, mine >= 0, lane);
+            wave_lds_sync();
+            softmax_accumulate<VEC>(s, out + d * hd, v, mine, n, e0 == beg, e0 + 64 >= end, lane, hd, units, upl);
+        }
+        softmax_row_end<VEC>(s, out + d * hd, lse + d * heads, beg == end, lane, heads, units);
+    }
+}
+
+// Backward, all three gradients in one launch, each of them optional (null).  A second score pass gives the dot products again and
+// dot_j = <g[d, h, :], v[row_j, h, :]>; then per edge and head a_j = exp(e_j - lse[d, h]) and t_j = a_j (dot_j - <g, out>), and a third
+// walk over the chunk's rows, a lane per float c:
+//   grad_v[row_j, c] += a_j g[d, c]             hardware float atomics (zeroed by the caller), 256 contiguous bytes per wave instruction;
+//   grad_k[row_j, c] += scale t_j q[d, c]       the same;
+//   grad_q[d, c]      = scale sum_j t_j k[row_j, c]   summed in slot order in a register, scaled and stored once per chunk (a later
+//                                               chunk of a long row adds to what the earlier ones stored): no atomics.
+template <bool CSR>
+__global__ __launch_bounds__(kBlock) void dot_gat_aggregate_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ row,
+                                                                            int fanout, const float* __restrict__ q, const float* __restrict__ k,
+                                                                            const float* __restrict__ v, const float* __restrict__ out,
+                                                                            const float* __restrict__ lse, const float* __restrict__ grad_out,
+                                                                            float* __restrict__ grad_q, float* __restrict__ grad_k,
+                                                                            float* __restrict__ grad_v, int64_t n_dst, int heads, int dim,
+                                                                            float scale) {
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // the chunk's dot products <q, k_j>, then a_j, [edge][head]
+    __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g, v_j>, then t_j, [edge][head]
+    __shared__ float hs_lds[kWavesPerBlock][kGatMaxHeads];       // per head: <g, out>
+    const auto [lane, wave, n_waves] = wave_rows();
+    float* w = w_lds[threadIdx.x >> 6];
+    float* dot = dot_lds[threadIdx.x >> 6];
+    float* gout = hs_lds[threadIdx.x >> 6];
+    const int hd = heads * dim;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        const float* g = grad_out + d * hd;
+        const float* qd = q + d * hd;
+        wave_lds_sync(); // the previous row has read gout
+        if (lane < heads) gout[lane] = 0.0f;
+        wave_lds_sync();
+        head_dots(gout, g, out + d * hd, lane, dim, hd);
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
+            int32_t mine;
+            const int n = load_chunk(row, e0, end, lane, &mine);
+            wave_lds_sync(); // the previous chunk has read w and dot
+            for (int h = 0; h < heads; ++h) {
+                w[lane * kGatMaxHeads + h] = 0.0f;
+                dot[lane * kGatMaxHeads + h] = 0.0f;
+            }
+            wave_lds_sync();
+            dot_score_pass<true>(w, dot, mine, n, k, qd, v, g, lane, hd, dim);
+            wave_lds_sync();
+            for (int h = 0; h < heads; ++h) { // lane j reads and rewrites only edge j's words
+                float a = 0.0f, t = 0.0f;
+                if (mine >= 0) {
+                    a = expf(scale * w[lane * kGatMaxHeads + h] - lse[d * heads + h]);
+                    t = a * (dot[lane * kGatMaxHeads + h] - gout[h]);
+                }
+                w[lane * kGatMaxHeads + h] = a;
+                dot[lane * kGatMaxHeads + h] = t;
+            }
+            wave_lds_sync();
+            for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: the shuffles below need every lane
+                const int c = c0 + lane;
+                const bool in = c < hd;
+                const int hc = in ? c / dim : 0;
+                const float gc = in ? g[c] : 0.0f;
+                const float qc = in ? qd[c] : 0.0f;
+                float gq = 0.0f;
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && in) { // every lane takes the shuffle above
+                        const float tj = dot[j * kGatMaxHeads + hc];
+                        if (grad_v) unsafeAtomicAdd(grad_v + (int64_t)s * hd + c, w[j * kGatMaxHeads + hc] * gc);
+                        if (grad_k) unsafeAtomicAdd(grad_k + (int64_t)s * hd + c, scale * tj * qc);
+                        if (grad_q) gq = __builtin_fmaf(tj, k[(int64_t)s * hd + c], gq);
+                    }
+                }
+                if (in && grad_q) grad_q[d * hd + c] = e0 == beg ? scale * gq : grad_q[d * hd + c] + scale * gq;
+            }
+        }
+        if (beg == end && grad_q) // no chunk ran: an empty CSR row
+            for (int c = lane; c < hd; c += 64) grad_q[d * hd + c] = 0.0f;
     }
 }
 
@@ -1198,6 +1333,35 @@ int gatv2_backward_launch(int device, const int64_t* indptr, const int32_t* idx,
 }
 
 template <bool CSR>
+int dot_gat_launch(int device, const int64_t* indptr, const int32_t* row, int fanout, const float* q, const float* k, const float* v, float* out,
+                   float* lse, int64_t n_dst, int heads, int dim, float scale, void* stream) {
+    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !row || !q || !k || !v || !out || !lse) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    dispatch_vec(vec4_ok(dim, v, out), [&](auto vec) {
+        hipLaunchKernelGGL((dot_gat_aggregate_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, row,
+                           fanout, q, k, v, out, lse, n_dst, heads, dim, scale);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+template <bool CSR>
+int dot_gat_backward_launch(int device, const int64_t* indptr, const int32_t* row, int fanout, const float* q, const float* k, const float* v,
+                            const float* out, const float* lse, const float* grad_out, float* grad_q, float* grad_k, float* grad_v,
+                            int64_t n_dst, int heads, int dim, float scale, void* stream) {
+    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
+    if (n_dst == 0 || (!grad_q && !grad_k && !grad_v)) return COALA_OK;
+    if ((CSR && !indptr) || !row || !q || !k || !v || !out || !lse || !grad_out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(dot_gat_aggregate_backward_kernel<CSR>, row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, row, fanout, q, k, v,
+                       out, lse, grad_out, grad_q, grad_k, grad_v, n_dst, heads, dim, scale);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+template <bool CSR>
 int weighted_sum_launch(int device, const int64_t* indptr, const int32_t* idx, const float* w, int fanout, const float* h_src, float* out,
                         int64_t n_dst, int dim, void* stream) {
     if (int rc = shape_check<CSR>(n_dst, fanout, dim)) return rc;
@@ -1387,6 +1551,30 @@ int coala_block_gatv2_aggregate_csr_backward(int device, const int64_t* indptr, 
                                              int dim, float negative_slope, void* stream) {
     return gatv2_backward_launch<true>(device, indptr, indices, 0, feat_src, feat_dst, attn, out, lse, grad_out, grad_src, grad_dst,
                                        grad_attn_parts, parts, n_dst, heads, dim, negative_slope, stream);
+}
+
+int coala_block_dot_gat_aggregate(int device, const int32_t* row, const float* q, const float* k, const float* v, float* out, float* lse,
+                                  int64_t n_dst, int fanout, int heads, int dim, float scale, void* stream) {
+    return dot_gat_launch<false>(device, nullptr, row, fanout, q, k, v, out, lse, n_dst, heads, dim, scale, stream);
+}
+
+int coala_block_dot_gat_aggregate_backward(int device, const int32_t* row, const float* q, const float* k, const float* v, const float* out,
+                                           const float* lse, const float* grad_out, float* grad_q, float* grad_k, float* grad_v, int64_t n_dst,
+                                           int fanout, int heads, int dim, float scale, void* stream) {
+    return dot_gat_backward_launch<false>(device, nullptr, row, fanout, q, k, v, out, lse, grad_out, grad_q, grad_k, grad_v, n_dst, heads, dim, scale,
+                                          stream);
+}
+
+int coala_block_dot_gat_aggregate_csr(int device, const int64_t* indptr, const int32_t* row, const float* q, const float* k, const float* v,
+                                      float* out, float* lse, int64_t n_dst, int heads, int dim, float scale, void* stream) {
+    return dot_gat_launch<true>(device, indptr, row, 0, q, k, v, out, lse, n_dst, heads, dim, scale, stream);
+}
+
+int coala_block_dot_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* row, const float* q, const float* k,
+                                               const float* v, const float* out, const float* lse, const float* grad_out, float* grad_q,
+                                               float* grad_k, float* grad_v, int64_t n_dst, int heads, int dim, float scale, void* stream) {
+    return dot_gat_backward_launch<true>(device, indptr, row, 0, q, k, v, out, lse, grad_out, grad_q, grad_k, grad_v, n_dst, heads, dim, scale,
+                                         stream);
 }
 
 int coala_block_weighted_sum(int device, const int32_t* nbr, const float* w, const float* h_src, float* out, int64_t n_dst, int fanout, int dim,

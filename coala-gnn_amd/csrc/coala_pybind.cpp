@@ -354,4 +354,34 @@ PYBIND11_MODULE(_coala_pybind, m) {
         check(coala_cache_fetch_distributed_bucketed(ptr<coala_cache_t>(h), ptr<coala_comm_t>(c), ptr<float>(out), ptr<const int64_t>(idx), n,
                                                      ptr<const int64_t>(counts), stream_of(stream)));
     });
+    // scaled dot-product attention on a block (coala_block_dot_gat_aggregate*); a gradient that is not wanted is passed as 0
+    m.def("block_dot_gat_aggregate", [](int device, uint64_t row, uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, int64_t n_dst,
+                                        int fanout, int heads, int dim, float scale, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_dot_gat_aggregate(device, ptr<const int32_t>(row), ptr<const float>(q), ptr<const float>(k), ptr<const float>(v),
+                                            ptr<float>(out), ptr<float>(lse), n_dst, fanout, heads, dim, scale, stream_of(stream)));
+    });
+    m.def("block_dot_gat_aggregate_backward", [](int device, uint64_t row, uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse,
+                                                 uint64_t grad_out, uint64_t grad_q, uint64_t grad_k, uint64_t grad_v, int64_t n_dst, int fanout,
+                                                 int heads, int dim, float scale, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_dot_gat_aggregate_backward(device, ptr<const int32_t>(row), ptr<const float>(q), ptr<const float>(k), ptr<const float>(v),
+                                                     ptr<const float>(out), ptr<const float>(lse), ptr<const float>(grad_out), ptr<float>(grad_q),
+                                                     ptr<float>(grad_k), ptr<float>(grad_v), n_dst, fanout, heads, dim, scale, stream_of(stream)));
+    });
+    m.def("block_dot_gat_aggregate_csr", [](int device, uint64_t indptr, uint64_t row, uint64_t q, uint64_t k, uint64_t v, uint64_t out,
+                                            uint64_t lse, int64_t n_dst, int heads, int dim, float scale, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_dot_gat_aggregate_csr(device, ptr<const int64_t>(indptr), ptr<const int32_t>(row), ptr<const float>(q), ptr<const float>(k),
+                                                ptr<const float>(v), ptr<float>(out), ptr<float>(lse), n_dst, heads, dim, scale, stream_of(stream)));
+    });
+    m.def("block_dot_gat_aggregate_csr_backward", [](int device, uint64_t indptr, uint64_t row, uint64_t q, uint64_t k, uint64_t v, uint64_t out,
+                                                     uint64_t lse, uint64_t grad_out, uint64_t grad_q, uint64_t grad_k, uint64_t grad_v,
+                                                     int64_t n_dst, int heads, int dim, float scale, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_dot_gat_aggregate_csr_backward(device, ptr<const int64_t>(indptr), ptr<const int32_t>(row), ptr<const float>(q),
+                                                         ptr<const float>(k), ptr<const float>(v), ptr<const float>(out), ptr<const float>(lse),
+                                                         ptr<const float>(grad_out), ptr<float>(grad_q), ptr<float>(grad_k), ptr<float>(grad_v),
+                                                         n_dst, heads, dim, scale, stream_of(stream)));
+    });
 }

@@ -14,6 +14,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --model_type rgcn --num_rels 4 --sampler rel --rel_fan_out "10,3,0,-1;5,5,5,5"
   python examples/train_synthetic.py --model_type rgat --num_rels 4 --num_heads 4 --sampler rel --rel_fan_out "10,3,0,-1;5,5,5,5"
   python examples/train_synthetic.py --model_type rsage --num_rels 4
+  python examples/train_synthetic.py --model_type hgt --num_heads 4 --num_rels 4 --num_ntypes 3
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -31,7 +32,7 @@ import torch  # noqa: E402
 
 from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
-from COALA_GNN.harness import GAT, GCN, GIN, RGAT, RGCN, RSAGE, SAGE, GATv2, SageMean  # noqa: E402
+from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, GATv2, SageMean  # noqa: E402
 from COALA_GNN.sampler import LaborSampler, NeighborSampler, RelNeighborSampler, sort_csc_by_etype  # noqa: E402
 from COALA_GNN.synthetic import alloc_pinned_table, edge_types_by_source, powerlaw_csc  # noqa: E402
 
@@ -45,7 +46,7 @@ def main():
                     help="fan-outs of the evaluation loader (default: --fan_out); -1 takes every in-edge, e.g. -1,-1 for full neighbourhoods")
     ap.add_argument("--sampler", type=str, default="neighbor", choices=["neighbor", "labor", "rel"],
                     help="labor: layer-neighbour sampling (LaborSampler) -- the same expected fan-out per node, fewer input nodes to fetch; "
-                         "rel: a fan-out per edge type (RelNeighborSampler, --rel_fan_out; needs --model_type rgcn, rgat or rsage)")
+                         "rel: a fan-out per edge type (RelNeighborSampler, --rel_fan_out; needs --model_type rgcn, rgat, rsage or hgt)")
     ap.add_argument("--rel_fan_out", type=str, default=None,
                     help="with --sampler rel, in place of --fan_out: layers separated by ';', the --num_rels relations of a layer by ',' "
                          "(-1: every in-edge of the type, 0: none); a single number per layer applies to every relation, "
@@ -73,7 +74,7 @@ def main():
     # accepted so that the reference's command lines (examples/4GB_script.sh, Cache_compare_script.sh, Distribution_compare_script.sh) run as they are
     ap.add_argument("--num_layers", type=int, default=None, help="must equal the number of fan-outs when given")
     ap.add_argument("--feat_cpu", action="store_true", help="features in pinned host memory: always the case here (the NVMe tier is out of scope)")
-    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "gatv2", "sage", "gcn", "gin", "rgcn", "rgat", "rsage"],
+    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "gatv2", "sage", "gcn", "gin", "rgcn", "rgat", "rsage", "hgt"],
                     help="sage: GraphSAGE (--sage_aggregator); gat: GAT with --num_heads heads (native attention aggregation); gatv2: the same model on GATv2Conv layers (--share_weights); gcn: GraphConv, "
                          "norm='both'; gin: GINConv layers (--gin_aggregator), an MLP in each; rgcn: RelGraphConv layers, one weight matrix per edge "
                          "type (--num_rels synthetic types, the source node's id modulo --num_rels; native relation-typed sum); rgat: RelGATConv layers, "
@@ -88,7 +89,10 @@ def main():
     ap.add_argument("--num_heads", type=int, default=4, help="attention heads of --model_type gat, gatv2 and rgat")
     ap.add_argument("--share_weights", action="store_true",
                     help="--model_type gatv2: one projection for the source and the destination rows of every layer (GATv2Conv's share_weights)")
-    ap.add_argument("--num_rels", type=int, default=4, help="edge types of --model_type rgcn, rgat and rsage (1..64)")
+    ap.add_argument("--num_rels", type=int, default=4, help="edge types of --model_type rgcn, rgat, rsage and hgt (1..64)")
+    ap.add_argument("--num_ntypes", type=int, default=3,
+                    help="node types of --model_type hgt (the Heterogeneous Graph Transformer on the native scaled dot-product attention): "
+                         "synthetic, a node's id modulo --num_ntypes")
     ap.add_argument("--rgcn_regularizer", type=str, default="none", choices=["none", "basis"], help="weight regularizer of --model_type rgcn")
     ap.add_argument("--num_bases", type=int, default=None, help="bases of --rgcn_regularizer basis (default: --num_rels)")
     args = ap.parse_args()
@@ -103,8 +107,8 @@ def main():
     comm.initialize_nested_process_group(args.cache_backend)            # :267
     rel_fan_out = None
     if args.sampler == "rel":
-        if args.model_type not in ("rgcn", "rgat", "rsage") or not args.rel_fan_out or args.edge_weights != "none" or args.layer_dependency:
-            ap.error("--sampler rel needs --model_type rgcn, rgat or rsage and --rel_fan_out, and takes neither --edge_weights nor "
+        if args.model_type not in ("rgcn", "rgat", "rsage", "hgt") or not args.rel_fan_out or args.edge_weights != "none" or args.layer_dependency:
+            ap.error("--sampler rel needs --model_type rgcn, rgat, rsage or hgt and --rel_fan_out, and takes neither --edge_weights nor "
                      "--layer_dependency")
         rel_fan_out = [[int(f) for f in layer.split(",")] for layer in args.rel_fan_out.split(";")]
         rel_fan_out = [layer[0] if len(layer) == 1 else layer for layer in rel_fan_out]
@@ -116,8 +120,10 @@ def main():
     eval_fan_out = fan_out if args.eval_fan_out is None else [int(f) for f in args.eval_fan_out.split(",")]
     if len(eval_fan_out) != len(fan_out):
         ap.error("--eval_fan_out needs as many layers as --fan_out")
-    if args.model_type == "rgat" and (args.num_heads < 1 or args.hidden_channels % args.num_heads):
-        ap.error("--model_type rgat needs --hidden_channels to be a multiple of --num_heads")
+    if args.model_type in ("rgat", "hgt") and (args.num_heads < 1 or args.hidden_channels % args.num_heads):
+        ap.error(f"--model_type {args.model_type} needs --hidden_channels to be a multiple of --num_heads")
+    if args.model_type == "hgt" and args.num_ntypes < 1:
+        ap.error("--num_ntypes must be at least 1")
 
     dataset = None
     if args.path:   # IGBDatast_Shared_CSC_UVA / OGBDataset_Shared_UVA (:273-285): CSC in HBM, features in shared pinned host memory
@@ -160,8 +166,8 @@ def main():
         edata, prob = {"w": w}, "w"
     if args.use_edge_weight and prob is None:
         ap.error("--use_edge_weight needs --edge_weights random")
-    ew = "w" if args.use_edge_weight and args.model_type not in ("gat", "gatv2", "gin", "rgcn", "rgat", "rsage") else None
-    typed = args.model_type in ("rgcn", "rgat", "rsage")   # the models on typed edges
+    ew = "w" if args.use_edge_weight and args.model_type not in ("gat", "gatv2", "gin", "rgcn", "rgat", "rsage", "hgt") else None
+    typed = args.model_type in ("rgcn", "rgat", "rsage", "hgt")   # the models on typed edges
     if typed:   # the edge types of a homogenised heterograph, in CSC order; the blocks find theirs through their edge ids
         if not 1 <= args.num_rels <= 64:
             ap.error("--num_rels must be 1..64")
@@ -196,6 +202,10 @@ def main():
         model = GIN(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.gin_aggregator).to(device)
     elif args.model_type == "rgat":
         model = RGAT(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_rels, args.num_heads).to(device)
+    elif args.model_type == "hgt":
+        ntype = torch.arange(args.nodes, device=device) % args.num_ntypes                                   # the graph's node-type table
+        model = HGT(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads, args.num_ntypes, args.num_rels,
+                    ntype=ntype).to(device)
     elif args.model_type == "rsage":
         model = RSAGE(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_rels).to(device)
     elif args.model_type == "rgcn":

@@ -641,6 +641,41 @@ int coala_block_gatv2_aggregate_csr_backward(int device, const int64_t* indptr, 
                                              const float* feat_dst, const float* attn, const float* out, const float* lse, const float* grad_out,
                                              float* grad_src, float* grad_dst, float* grad_attn_parts, int parts, int64_t n_dst, int heads,
                                              int dim, float negative_slope, void* stream);
+/* Scaled dot-product attention aggregation (the message step of DGL's DotGatConv and HGTConv and of PyG's TransformerConv without edge
+ * features; the projections are dense and stay outside).  Every neighbour slot carries the row of k / v its edge reads: row int32, -1
+ * = no edge, laid out [n_dst, fanout] (fan-out 1..32) or, for the CSR form, along indptr (slot e of row d for indptr[d] <= e <
+ * indptr[d+1], any degree).  A caller whose k / v have one row per source node passes the block's own index array.  For dst d, head h
+ * and the slots j of d with row_j >= 0:
+ *   e_j = scale * <q[d, h, :], k[row_j, h, :]>;  a_j = exp(e_j - m) / sum_i exp(e_i - m), m = max_i e_i;
+ *   out[d, h, :] = sum_j a_j v[row_j, h, :];  lse[d, h] = m + log sum_i exp(e_i - m).
+ * q fp32 [n_dst, heads, dim], k and v fp32 [P, heads, dim] (k == v allowed), out fp32 [n_dst, heads, dim], lse fp32 [n_dst, heads], all
+ * contiguous; heads 1..16, dim >= 1, heads * dim < 2^31, P < 2^31.  A row index is never checked: every row_j >= 0 must be < P.  A row
+ * without an edge gives out exactly 0 and lse -inf.  16-byte accesses when dim % 4 == 0 and v and out are 16-byte aligned, scalar ones
+ * otherwise.  One wave takes a row 64 slots at a time, GAT's online max and rescale; per chunk the dot products are summed into on-chip
+ * memory first, then the chunk's v rows are read for the weighted sum: no buffer of a size proportional to the number of edges exists.
+ * Backward, with g = grad_out [n_dst, heads, dim], out / lse from the forward, a_j = exp(e_j - lse) from recomputed scores and
+ * t_j = a_j (<g[d, h, :], v[row_j, h, :]> - <g[d, h, :], out[d, h, :]>):
+ *   grad_v[row_j, h, :] += a_j g[d, h, :]              hardware float atomics: the caller zeroes grad_v [P, heads, dim], the order varies;
+ *   grad_k[row_j, h, :] += scale t_j q[d, h, :]        the same, grad_k [P, heads, dim];
+ *   grad_q[d, h, :]      = scale sum_j t_j k[row_j, h, :]   [n_dst, heads, dim], written whole, summed in slot order: no atomics.
+ * Each of the three outputs may be NULL (not wanted: not computed); with all three NULL nothing is launched.
+ * Determinism: out, lse and grad_q are bitwise reproducible, and a fixed row whose valid entries come first gives the bits of the same
+ * CSR row; grad_k and grad_v depend on the order of the atomics.
+ * Refused with COALA_EINVAL and nothing launched: "bad block shape" (fan-out outside 1..32, heads outside 1..16, dim < 1, n_dst < 0),
+ * "null buffer"; n_dst == 0 launches nothing and reads no pointer.  The grid is capped as for the other block ops.
+ * Bytes per row of deg edges, hd = heads * dim: the forward reads deg * (8 hd + 4) + 4 hd (k and v rows, the slot words, q) and writes
+ * 4 hd + 4 heads; the backward reads deg * (8 hd + 4) + 12 hd (the second read of a k row is a cache hit), adds 8 hd deg through
+ * atomics and writes 4 hd. */
+int coala_block_dot_gat_aggregate(int device, const int32_t* row, const float* q, const float* k, const float* v, float* out, float* lse,
+                                  int64_t n_dst, int fanout, int heads, int dim, float scale, void* stream);
+int coala_block_dot_gat_aggregate_backward(int device, const int32_t* row, const float* q, const float* k, const float* v, const float* out,
+                                           const float* lse, const float* grad_out, float* grad_q, float* grad_k, float* grad_v, int64_t n_dst,
+                                           int fanout, int heads, int dim, float scale, void* stream);
+int coala_block_dot_gat_aggregate_csr(int device, const int64_t* indptr, const int32_t* row, const float* q, const float* k, const float* v,
+                                      float* out, float* lse, int64_t n_dst, int heads, int dim, float scale, void* stream);
+int coala_block_dot_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* row, const float* q, const float* k,
+                                               const float* v, const float* out, const float* lse, const float* grad_out, float* grad_q,
+                                               float* grad_k, float* grad_v, int64_t n_dst, int heads, int dim, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Shared pinned-host ("UVA") region.  Replaces SharedUVAManager (COALA_GNN_Modules/shared_UVA.cuh:26-115):
