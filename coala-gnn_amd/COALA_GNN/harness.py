@@ -9,14 +9,15 @@ SAGE(aggregator_type='pool') and GIN (--model_type gin) are the models on the na
 native relation-typed sum (Block.rel_sum_aggregate).  RGAT and RSAGE (--model_type rgat|rsage) mirror examples/models.py:RGAT and :RSAGE
 the same way, on RelGATConv (the native relation-typed attention, Block.rel_gat_aggregate) and RelSAGEConv.  HGT (--model_type hgt) is the
 Heterogeneous Graph Transformer on HGTConv layers, and DotGAT is GAT's shape on DotGatConv layers; both attend with the native scaled
-dot-product kernel (Block.dot_gat_aggregate)."""
+dot-product kernel (Block.dot_gat_aggregate).  PinSAGE (--model_type pinsage) is the network of DGL's PinSAGE example on WeightedSAGEConv
+layers, for blocks sampled by random walks (RandomWalkNeighborSampler): the visit counts weigh the neighbours."""
 import time
 
 import torch
 
-from .nn import DotGatConv, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv
+from .nn import DotGatConv, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv, WeightedSAGEConv
 
-__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "train_steps", "FlatGradAllReduce"]
+__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "PinSAGE", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -272,6 +273,27 @@ class DotGAT(torch.nn.Module):
             if i + 1 < len(self.layers):
                 h = h.flatten(1)
         return h.mean(1).log_softmax(dim=-1)
+
+
+class PinSAGE(torch.nn.Module):
+    """The network of DGL's PinSAGE example (SAGENet: WeightedSAGEConv layers of h_feats features, every one weighing its neighbours by
+    block.edata[weight_key], the visit counts of RandomWalkNeighborSampler) with a Linear(h_feats, num_classes) on top for node
+    classification.  Every layer's output rows have unit L2 norm, so nothing stands between the layers."""
+
+    def __init__(self, in_feats, h_feats, num_classes, num_layers=2, weight_key="weights", dropout=0.0):
+        super().__init__()
+        dims = [in_feats] + [h_feats] * (num_layers - 1)
+        self.layers = torch.nn.ModuleList(WeightedSAGEConv(dims[i], h_feats, h_feats, dropout=dropout) for i in range(num_layers))
+        self.linear = torch.nn.Linear(h_feats, num_classes)
+        self.weight_key = weight_key
+
+    def forward(self, blocks, x):
+        h = x
+        for layer, block in zip(self.layers, blocks):
+            if self.weight_key not in block.edata:
+                raise ValueError(f"PinSAGE needs block.edata[{self.weight_key!r}]: sample the blocks with RandomWalkNeighborSampler")
+            h = layer(block, (h, block.dst_rows(h)), block.edata[self.weight_key])
+        return self.linear(h)
 
 
 class FlatGradAllReduce(object):

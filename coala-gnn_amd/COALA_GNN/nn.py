@@ -14,10 +14,12 @@ on a homogenised block -- HeteroGraphConv over one GATConv, or one SAGEConv 'gcn
 (destination, relation) is Block.rel_gat_aggregate, a native kernel; RelSAGEConv needs Block.rel_sum_aggregate and one GEMM.
 DotGatConv and HGTConv (the Heterogeneous Graph Transformer, on a homogenised block with a type per node and per edge) attend with a
 scaled dot product, Block.dot_gat_aggregate, a native kernel without [E, H, D] intermediates; HGTConv applies its per-relation D x D
-matrices per (source, relation) pair, not per edge, and folds the relation prior into the attention matrix."""
+matrices per (source, relation) pair, not per edge, and folds the relation prior into the attention matrix.
+WeightedSAGEConv is the layer of DGL's PinSAGE example on blocks sampled by random walks (RandomWalkNeighborSampler): the visit counts
+in block.edata['weights'] weigh the neighbours' rows through Block.weighted_sum_aggregate."""
 import torch
 
-__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv"]
+__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv"]
 
 
 class GATConv(torch.nn.Module):
@@ -240,6 +242,45 @@ class SAGEConv(torch.nn.Module):
         if self.activation is not None:
             rst = self.activation(rst)
         return rst
+
+
+class WeightedSAGEConv(torch.nn.Module):
+    """The convolution of DGL's PinSAGE example (examples/pytorch/pinsage/layers.py: WeightedSAGEConv) on a block, with its parameter
+    names Q and W:
+        n[d] = sum_j w_j * act(Q h_src[s_j]) / max(sum_j w_j, 1)
+        z[d] = act(W [n[d] || h_dst[d]]),    out[d] = z[d] / ||z[d]||_2  (a zero norm counts as 1)
+    over the valid slots j of d; weights has one value per neighbour slot, shaped like block.nbr -- block.edata['weights'] of a block
+    from RandomWalkNeighborSampler, the visit counts (0 on padding).  Q: Linear(in_feats, hidden_feats), W: Linear(in_feats +
+    hidden_feats, out_feats), Xavier-uniform with the gain of relu and zero biases, as in the example; dropout (the example uses 0.5)
+    is applied to h_src before Q and to the concatenation before W.  The weighted sum is Block.weighted_sum_aggregate, a native kernel
+    with gradients; feat is h_src or (h_src, h_dst)."""
+
+    def __init__(self, in_feats, hidden_feats, out_feats, act=torch.relu, dropout=0.0):
+        super().__init__()
+        self.act = act
+        self.Q = torch.nn.Linear(in_feats, hidden_feats)
+        self.W = torch.nn.Linear(in_feats + hidden_feats, out_feats)
+        self.dropout = torch.nn.Dropout(dropout)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        for lin in (self.Q, self.W):
+            torch.nn.init.xavier_uniform_(lin.weight, gain=gain)
+            torch.nn.init.zeros_(lin.bias)
+
+    def forward(self, block, feat, weights):
+        h_src, h_dst = feat if isinstance(feat, (tuple, list)) else (feat, block.dst_rows(feat))
+        w = weights.to(device=h_src.device, dtype=h_src.dtype)
+        valid = (block.nbr >= 0) if block.nbr is not None else None
+        n = block.weighted_sum_aggregate(self.act(self.Q(self.dropout(h_src))), w)
+        if valid is None:   # ragged block: one weight per edge, summed per row
+            ws = torch.zeros(block.num_dst, dtype=w.dtype, device=w.device).index_add(0, block._slots(w.device)[0], w)
+        else:
+            ws = (w * valid.to(device=w.device, dtype=w.dtype)).sum(1)
+        z = self.act(self.W(self.dropout(torch.cat([n / ws.clamp_min(1).unsqueeze(1), h_dst], 1))))
+        norm = z.norm(2, 1, keepdim=True)
+        return z / torch.where(norm == 0, torch.ones_like(norm), norm)
 
 
 class GINConv(torch.nn.Module):

@@ -14,8 +14,8 @@ from COALA_GNN_Pybind import _capi, current_stream
 from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
                         _MeanAggregateCSR, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _WeightedSum, _WeightedSumCSR)
 
-__all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "sort_csc_by_etype", "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT",
-           "EID"]
+__all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "RandomWalkNeighborSampler", "random_walk", "sort_csc_by_etype",
+           "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT", "EID"]
 
 _lib = _capi.load()
 
@@ -899,3 +899,91 @@ class RelNeighborSampler(NeighborSampler):
         _capi.check(_lib.coala_sampler_sample_layers_rel(g._h, seeds.data_ptr(), n, rel_fan, self.num_rels, L, self.seed, st, lay, types.data_ptr(),
                                                          eid_p, None, None, C.byref(bk) if bk is not None else None, C.byref(ticket),
                                                          current_stream()))
+
+
+def _walk_threshold(prob, name):
+    """floor(prob * 2^53) as an int: the integer the walk kernels compare 53 random bits with.  The product is exact in fp64."""
+    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 <= float(prob) < 1.0:
+        raise ValueError(f"{name} {prob!r}: a probability in [0, 1)")
+    return int(float(prob) * 9007199254740992.0)
+
+
+class RandomWalkNeighborSampler(NeighborSampler):
+    """Importance-based neighbour sampling by random walks, DGL's dgl.sampling.RandomWalkNeighborSampler / PinSAGESampler on a homogeneous
+    graph (Ying et al., "Graph Convolutional Neural Networks for Web-Scale Recommender Systems", KDD 2018), in place of NeighborSampler:
+    same sample / sample_begin / sample_end, same loader.  From every destination node num_random_walks walks of num_traversals hops
+    start; a hop after the first ends the walk with probability termination_prob.  The node's neighbours are the num_neighbors nodes
+    the walks visit most often (a tie goes to the smaller id), most visited first.  The rule is in the header of coala_sampler.hip.
+
+    num_neighbors: an int (one layer) or one per layer in model order, each 1..32; it is self.fanouts, what the loader is given: the
+    input nodes are bounded as NeighborSampler's, batch * prod(k + 1).  num_traversals 1..16, num_random_walks 1..64, their product at
+    most 512; termination_prob in [0, 1).  A walk follows in-edges, the direction the CSC is stored in: DGL's walk on a symmetric graph.
+    Every block is fixed-stride (Block.nbr [num_dst, k], -1 padded).  block.edata[weight_column] is fp32 [num_dst, k], the visit count
+    of every slot (0 on padding), made on first access from the int32 counts the kernel wrote (block.edata['visit_counts']): what
+    Block.weighted_sum_aggregate and SAGEConv / GraphConv (edge_weight=) take.  A chosen neighbour is a node the walks reached, not an edge of the graph: there are no
+    edge ids, and prob= is not supported."""
+
+    def __init__(self, num_neighbors, num_traversals, termination_prob, num_random_walks, seed=0, bucket_by_owner=0, weight_column="weights",
+                 prob=None, edge_ids=False):
+        if prob is not None:
+            raise ValueError("RandomWalkNeighborSampler: prob= (weighted walks) is not supported")
+        if edge_ids:
+            raise ValueError("RandomWalkNeighborSampler: edge_ids is not supported: a chosen neighbour is not an edge of the graph")
+        ks = [num_neighbors] if isinstance(num_neighbors, int) else list(num_neighbors)
+        for k in ks:
+            if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 32:
+                raise ValueError(f"num_neighbors {k!r}: each layer keeps 1..32 neighbours")
+        for name, x, hi in (("num_traversals", num_traversals, 16), ("num_random_walks", num_random_walks, 64)):
+            if isinstance(x, bool) or not isinstance(x, int) or not 1 <= x <= hi:
+                raise ValueError(f"{name} {x!r}: 1..{hi}")
+        if num_traversals * num_random_walks > 512:
+            raise ValueError(f"num_random_walks * num_traversals = {num_traversals * num_random_walks}: at most 512 visits per node")
+        self.term_threshold = _walk_threshold(termination_prob, "termination_prob")
+        super().__init__(ks, seed=seed, bucket_by_owner=bucket_by_owner)
+        self.num_neighbors = list(self.fanouts)
+        self.num_traversals, self.num_random_walks, self.termination_prob = num_traversals, num_random_walks, float(termination_prob)
+        self.weight_column = weight_column
+        self._counts = None   # the count buffers of the call _enqueue just made, on their way into sample_begin's result
+
+    def sample_begin(self, g, seed_nodes, step=None):
+        pending = super().sample_begin(g, seed_nodes, step)
+        counts, self._counts = self._counts, None
+        return pending + (counts,)
+
+    def _enqueue(self, g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket):
+        lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), None, src_caps[l], edge_caps[l]) for l in range(L)])
+        self._counts = [torch.empty(max(edge_caps[l], 1), dtype=torch.int32, device=g.device) for l in range(L)]
+        cnt_p = (C.c_void_p * L)(*[t.data_ptr() for t in self._counts])
+        walk = _capi.SamplerWalk(self.num_traversals, self.num_random_walks, self.term_threshold)
+        _capi.check(_lib.coala_sampler_sample_layers_walk(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, C.byref(walk), cnt_p, None, None,
+                                                          C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
+
+    def sample_end(self, pending):
+        counts = pending[-1]
+        input_nodes, seeds, blocks = super().sample_end(pending[:-1])
+        for l, b in enumerate(reversed(blocks)):   # counts are in sampling order, blocks in model order
+            c = counts[l][: b.nbr.numel()].view(b.nbr.shape)
+            b.edata = _EdgeData(None, None, {self.weight_column: lambda c=c: c.to(torch.float32)})
+            b.edata["visit_counts"] = c   # the kernel's int32 counts: held by the block, so Block.tensors() reports their buffer
+        return input_nodes, seeds, blocks
+
+
+def random_walk(g, nodes, length, restart_prob=0.0, num_walks=1, seed=0, step=0):
+    """Random walks over a CSCGraph, DGL's dgl.sampling.random_walk on a homogeneous graph: -> int64 [n, num_walks, length + 1] on the
+    graph's device.  [i, w, 0] is nodes[i], then the nodes walk w visits; a hop after the first ends the walk with probability
+    restart_prob, a node without an in-edge ends it, and -1 fills the rest.  An out-of-range start node gives a row of -1.  A walk
+    follows in-edges (DGL's walk on a symmetric graph).  length 1..16, num_walks 1..64.
+    Unlike DGL's, the walks are a function of (seed, step, start node, w) -- they are walk w of that node in the first sampled layer of
+    RandomWalkNeighborSampler(num_traversals=length, termination_prob=restart_prob, seed=seed) at that step -- so a start node given
+    twice gets the same traces twice: ask for num_walks independent walks from one node instead of repeating it."""
+    for name, x, hi in (("length", length, 16), ("num_walks", num_walks, 64)):
+        if isinstance(x, bool) or not isinstance(x, int) or not 1 <= x <= hi:
+            raise ValueError(f"{name} {x!r}: 1..{hi}")
+    thr = _walk_threshold(restart_prob, "restart_prob")
+    if isinstance(g, tuple):
+        g = CSCGraph(*g)
+    nodes = nodes.to(g.device, dtype=torch.int64).contiguous()
+    out = torch.empty((nodes.numel(), num_walks, length + 1), dtype=torch.int64, device=g.device)
+    _capi.check(_lib.coala_sampler_random_walk(g._h, nodes.data_ptr(), nodes.numel(), num_walks, length, thr, int(seed) & ((1 << 64) - 1),
+                                               int(step) & ((1 << 64) - 1), 0, out.data_ptr(), current_stream()))
+    return out

@@ -47,6 +47,10 @@ class SamplerLayer(C.Structure):
                 ("edge_cap", C.c_int64)]
 
 
+class SamplerWalk(C.Structure):
+    _fields_ = [("num_traversals", C.c_int32), ("num_random_walks", C.c_int32), ("term_threshold", C.c_uint64)]
+
+
 class CommProfile(C.Structure):
     _fields_ = [("rows_ms", C.c_double), ("calls", C.c_uint64), ("remote_rows_in", C.c_uint64)]
 
@@ -129,6 +133,9 @@ SYMBOLS = {
                                           _I, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(SamplerBucketing), C.POINTER(_I64), _VP]),
     "coala_sampler_sample_layers_rel": (_I, [_VP, _VP, _I64, C.POINTER(C.c_int32), _I, _I, _U64, _U64, C.POINTER(SamplerLayer), _VP,
                                         C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(SamplerBucketing), C.POINTER(_I64), _VP]),
+    "coala_sampler_sample_layers_walk": (_I, [_VP, _VP, _I64, C.POINTER(C.c_int32), _I, _U64, _U64, C.POINTER(SamplerLayer), C.POINTER(SamplerWalk),
+                                         C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(SamplerBucketing), C.POINTER(_I64), _VP]),
+    "coala_sampler_random_walk": (_I, [_VP, _VP, _I64, _I, _I, _U64, _U64, _U64, _I, _VP, _VP]),
     "coala_block_weighted_sum": (_I, [_I, _VP, _VP, _VP, _VP, _I64, _I, _I, _VP]),
     "coala_block_weighted_sum_backward": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _VP]),
     "coala_block_weighted_sum_csr": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _I64, _I, _VP]),

@@ -99,6 +99,28 @@
 //   strides, one of more than kHubDegree edges by the whole block), then scan_assign / relabel_clear in their full-layer
 //   instantiations and the bucketing kernels, unchanged.  The fan-outs travel by value in the kernel arguments.
 //
+// Random-walk layers (DGL's dgl.sampling.RandomWalkNeighborSampler / PinSAGESampler on a homogeneous graph; coala_sampler_sample_layers_walk):
+// a node's neighbours are the k nodes its short random walks visit most often, and the visit counts go to the model as edge weights.
+// A layer has k = num_neighbors (the fan-out, 1..32), T = num_traversals (1..16), W = num_random_walks (1..64, W T <= 512) and a
+// termination threshold thr = floor(termination_prob * 2^53), an integer the host computes (termination_prob in [0, 1): exact in fp64).
+//   * keys: destination node v (a node of the graph) of sampled layer l has wkey = sample_key(seed, step, l, v) ^ kWalkStream,
+//     kWalkStream = 0x3C6EF372FE94F82B: a stream of its own, so a walk layer never replays the draws of another layer kind;
+//   * walk w (0 <= w < W) starts at u = v; hop h = 0 .. T-1, with c = 2 (16 w + h):
+//       1. h >= 1 and (splitmix64(wkey + c) >> 11) < thr: the walk ends (the first hop is never terminated, as in DGL);
+//       2. deg = indptr[u+1] - indptr[u]; deg == 0: the walk ends;
+//       3. u = indices[indptr[u] + mulhi64(splitmix64(wkey + c + 1), deg)], and this visit of u is recorded.
+//     A step follows an IN-edge, the direction every sampler here reads the CSC in; on a symmetric graph this is DGL's walk.  The
+//     visits of v's walks depend on (seed, step, l, v) only: not on the batch, v's place in it, the grid or the order of the waves;
+//   * selection: count(u) = recorded visits of u over the W walks (u == v counts like any other node, as in DGL).  The row takes the
+//     min(k, distinct visited) nodes of largest count, a tie going to the smaller node id, written in that order, valid entries
+//     first, then -1; the per-slot visit count is int32, 0 on padding.  An out-of-range destination id, or a node of in-degree 0,
+//     gives an empty row.  A chosen neighbour is a node, not an edge of the graph: there are no edge ids;
+//   * source list, first appearance, nbr_local, the item limit and its refusal, and owner bucketing are a uniform fixed layer's.
+//   Launches: walk_select<GS> replaces sample_insert (GS lanes per row, GS >= max(W, k + 1): a lane per walk writes its visits to
+//   fixed positions of an LDS array, the group counts them by all-pairs comparison and takes k rounds of arg-max on (count, -id));
+//   a walk never scans a row, so there is no hub list and no ragged form.  scan_assign / relabel_clear / bucketing run unchanged:
+//   three launches per layer, no memset, no host wait.  coala_sampler_random_walk stores the traces of the same walks (walk_trace).
+//
 // Edge ids (coala_sampler_sample_layers_edge_ids), added to the contract of every layer kind above: with edge_ids_out[l] non-null the
 // kernel that reads a neighbour also stores where it read it, eid[slot] = indptr[v] + j (the edge's position in `indices`), int64,
 // laid out like the layer's nbr_local ([n_dst, f] or [E]); -1 where the slot holds no neighbour.  It is one 8-byte vector store from
@@ -471,6 +493,141 @@ __global__ __launch_bounds__(kHubBlock) void weighted_select_hub_kernel(Graph g,
                 emit_fixed_slot(nbr, eid, d * fanout + lane, nb, start + pick);
                 hash_insert(tb, mask, nb, n_dst + d * fanout + lane, slot_of_item);
             }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- random-walk layers
+constexpr uint64_t kWalkStream = 0x3C6EF372FE94F82Bull; // xor on sample_key: the walks' own stream
+constexpr int kMaxWalkLength = 16, kMaxWalks = 64, kMaxVisits = 512;
+constexpr uint64_t kWalkThresholdMax = 1ull << 53; // term_threshold = floor(p * 2^53), p < 1
+
+struct WalkParams {
+    int T, W;     // hops per walk, walks per node
+    uint64_t thr; // a hop h >= 1 ends the walk when (draw >> 11) < thr
+};
+
+// Walk w of node v (a node of the graph): visit(h, u) for every hop h < T, u the node the hop reached or -1 once the walk has ended.
+// The draws are counters 2 (16 w + h) (termination) and 2 (16 w + h) + 1 (the step) on wkey.  A neighbour id outside the graph (a
+// broken CSC) ends the walk instead of being followed.
+template <typename F>
+__device__ __forceinline__ void random_walk(const Graph& g, uint64_t wkey, int64_t v, int w, const WalkParams& wp, F&& visit) {
+    int64_t u = v;
+    bool ended = false;
+    for (int h = 0; h < wp.T; ++h) {
+        const uint64_t c = 2ull * (uint64_t)(kMaxWalkLength * w + h);
+        if (!ended && h >= 1 && (splitmix64(wkey + c) >> 11) < wp.thr) ended = true;
+        if (!ended) {
+            const int64_t start = g.indptr[u];
+            const int64_t deg = g.indptr[u + 1] - start;
+            if (deg <= 0) {
+                ended = true;
+            } else {
+                u = g.indices[start + (int64_t)__umul64hi(splitmix64(wkey + c + 1), (uint64_t)deg)];
+                if (u < 0 || u >= g.num_nodes) ended = true;
+            }
+        }
+        visit(h, ended ? kEmpty : u);
+    }
+}
+
+// Walk layer, in place of sample_insert_kernel: GS lanes (16/32/64 >= max(W, fanout + 1)) per destination node, RPB = kBlock / GS rows
+// per block step.  Lane w < W runs walk w and stores its visits at vis[w T + h] of the group's LDS array (-1 once ended): fixed
+// positions, no atomics.  Behind a barrier every lane counts, for its entries i = gl, gl + GS, ..., how often the node occurs among
+// all W T entries; the entry that is the node's first occurrence keeps the count, the others 0.  Then `fanout` rounds of a group
+// arg-max on (count, -id) over the entries still standing: round j's winner goes to lane j, and its owner retires it.  Lanes
+// < fanout write and insert their slots, lane `fanout` inserts the node itself -- the items and positions of sample_insert_kernel.
+// The row loop is block-uniform (barriers), the rounds and their shuffles run for every lane of the wave.
+// Dynamic LDS: RPB * W T int64 visits, then RPB * W T int32 counts.
+template <int GS>
+__global__ __launch_bounds__(kBlock) void walk_select_kernel(Graph g, const int64_t* __restrict__ dst, const int64_t* __restrict__ n_dst_dev,
+                                                             int64_t n_dst_value, int fanout, WalkParams wp, uint64_t seed, uint64_t step, int layer,
+                                                             int64_t* __restrict__ nbr, int32_t* __restrict__ visit_counts, Table tb,
+                                                             uint32_t* __restrict__ slot_of_item) {
+    constexpr int RPB = kBlock / GS; // rows per block step
+    extern __shared__ int64_t s_walk[];
+    const int n_vis = wp.W * wp.T;
+    const int grp = (int)threadIdx.x / GS;
+    int64_t* const vis = s_walk + (size_t)grp * n_vis;
+    int32_t* const cnt = reinterpret_cast<int32_t*>(s_walk + (size_t)RPB * n_vis) + (size_t)grp * n_vis;
+    const int64_t n_dst = layer_n_dst(n_dst_dev, n_dst_value);
+    const uint32_t mask = table_size(n_dst * (fanout + 1)) - 1;
+    const int gl = (int)threadIdx.x % GS;
+    for (int64_t d0 = (int64_t)blockIdx.x * RPB; d0 < n_dst; d0 += (int64_t)gridDim.x * RPB) { // block-uniform
+        const int64_t d = d0 + grp;
+        const bool active = d < n_dst;
+        const Row row = dst_row(g, dst, d, n_dst);
+        const int64_t v = row.v;
+        if (gl < wp.W) {
+            if (row.ok) {
+                const uint64_t wkey = sample_key(seed, step, layer, (uint64_t)v) ^ kWalkStream;
+                random_walk(g, wkey, v, gl, wp, [&](int h, int64_t u) { vis[gl * wp.T + h] = u; });
+            } else {
+                for (int h = 0; h < wp.T; ++h) vis[gl * wp.T + h] = kEmpty;
+            }
+        }
+        __syncthreads();
+        for (int i = gl; i < n_vis; i += GS) {
+            const int64_t x = vis[i];
+            int32_t c = 0;
+            if (x >= 0) {
+                bool first = true;
+                for (int j = 0; j < n_vis; ++j) {
+                    const bool same = vis[j] == x;
+                    c += same ? 1 : 0;
+                    first = first && !(same && j < i);
+                }
+                if (!first) c = 0;
+            }
+            cnt[i] = c;
+        }
+        // fanout rounds of arg-max on (count, -id); an entry of count 0 never wins
+        int64_t my_id = kEmpty;
+        int32_t my_cnt = 0;
+        for (int r = 0; r < fanout; ++r) { // wave-uniform: fanout is a kernel argument
+            int32_t bc = 0;
+            int64_t bid = kEmpty;
+            int bi = -1;
+            for (int i = gl; i < n_vis; i += GS) {
+                const int32_t c = cnt[i];
+                const int64_t x = vis[i];
+                if (c > bc || (c == bc && c > 0 && x < bid)) { bc = c; bid = x; bi = i; }
+            }
+            for (int m = GS >> 1; m > 0; m >>= 1) {
+                const int32_t oc = __shfl_xor(bc, m);
+                const int64_t oid = __shfl_xor(bid, m);
+                const int oi = __shfl_xor(bi, m);
+                if (oc > bc || (oc == bc && oc > 0 && oid < bid)) { bc = oc; bid = oid; bi = oi; }
+            }
+            if (bi >= 0 && bi % GS == gl) cnt[bi] = 0; // the owner retires the winner: only this lane reads cnt[bi]
+            if (gl == r) { my_id = bc > 0 ? bid : kEmpty; my_cnt = bc; }
+        }
+        if (active && gl < fanout) {
+            const int64_t q = d * fanout + gl;
+            emit_fixed_slot(nbr, nullptr, q, my_id, 0);
+            if (visit_counts) visit_counts[q] = my_cnt;
+            hash_insert(tb, mask, my_id, n_dst + q, slot_of_item);
+        } else if (active && gl == fanout) {
+            hash_insert(tb, mask, v, d, slot_of_item);
+        }
+        __syncthreads(); // every lane has read vis before the next step's walks overwrite it
+    }
+}
+
+// coala_sampler_random_walk: one thread per (start node, walk); traces[i, w, 0] is the start node, then the hops, -1 once ended.
+__global__ __launch_bounds__(kBlock) void walk_trace_kernel(Graph g, const int64_t* __restrict__ nodes, int64_t n, WalkParams wp, uint64_t seed,
+                                                            uint64_t step, int layer, int64_t* __restrict__ traces) {
+    const int64_t total = n * wp.W;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = t / wp.W;
+        const int w = (int)(t % wp.W);
+        const int64_t v = nodes[i];
+        int64_t* const row = traces + t * (wp.T + 1);
+        if (v >= 0 && v < g.num_nodes) {
+            row[0] = v;
+            random_walk(g, sample_key(seed, step, layer, (uint64_t)v) ^ kWalkStream, v, w, wp, [&](int h, int64_t u) { row[1 + h] = u; });
+        } else {
+            for (int h = 0; h <= wp.T; ++h) row[h] = kEmpty;
         }
     }
 }
@@ -1321,6 +1478,8 @@ struct Plan {
     bool layer_dependency; // LABOR (info.labor): one key for every layer of the call
     const RelFan* rel;     // relation layers (info.rel): the fan-outs of every layer, and the int32 edge types (CSC order)
     const int32_t* etype;
+    const coala_sampler_walk_t* walk;    // random-walk layers: every fixed layer of the call is one; null otherwise
+    int32_t* const* visit_counts;        // walk layers: null, or per layer null or device int32[edge_cap], the visit count of every slot
     RingInfo info;        // n_seeds, the fan-outs, n_parts and the caller's capacities
     // layer l has at most dst_cap[l] dst nodes, items_cap[l] items (dst nodes + neighbour slots), nbr_cap[l] neighbour entries
     int64_t dst_cap[COALA_SAMPLER_MAX_LAYERS], items_cap[COALA_SAMPLER_MAX_LAYERS], nbr_cap[COALA_SAMPLER_MAX_LAYERS];
@@ -1454,6 +1613,17 @@ int degree_scan(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, co
     return COALA_OK;
 }
 
+WalkParams walk_params(const coala_sampler_walk_t& w) { return {w.num_traversals, w.num_random_walks, w.term_threshold}; }
+
+// walk_select_kernel for layer l: its dynamic LDS holds the visits (int64) and their counts (int32) of the kBlock / GS rows of a block.
+template <int GS>
+void launch_walk_select(coala_sampler_t* s, const Plan& p, int l, dim3 grid, const int64_t* dst, const int64_t* n_dst_dev) {
+    const WalkParams wp = walk_params(*p.walk);
+    const size_t lds = (size_t)(kBlock / GS) * (size_t)(wp.W * wp.T) * (sizeof(int64_t) + sizeof(int32_t));
+    hipLaunchKernelGGL(walk_select_kernel<GS>, grid, dim3(kBlock), lds, p.st, s->g, dst, n_dst_dev, p.info.n_seeds, p.info.fanouts[l], wp, p.seed,
+                       p.step, l, s->nbr_global, p.visit_counts ? p.visit_counts[l] : nullptr, s->tb, s->slot_of_item);
+}
+
 // Layer l over the destination nodes dst[0 .. *n_dst_dev) (n_dst_dev null: the seeds, whose count travels as a kernel argument).
 int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, const int64_t* n_dst_dev) {
     const int64_t n_seeds = p.info.n_seeds;
@@ -1491,10 +1661,12 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
         fixed_run_check(p.info, l, -1, &unused_items, &max_src, &unused_what);
     } else {
         unsigned long long* nh = s->hub_count + l;
-        dispatch_group(f, [&](auto gs_c) {
+        dispatch_group(p.walk ? std::max(f, p.walk->num_random_walks - 1) : f, [&](auto gs_c) { // a walk layer: a lane per walk too
             constexpr int GS = decltype(gs_c)::value;
             const dim3 gs(grid1d(cap_l * GS, kBlock, 8192));
-            if (p.weights)
+            if (p.walk)
+                launch_walk_select<GS>(s, p, l, gs, dst, n_dst_dev);
+            else if (p.weights)
                 hipLaunchKernelGGL(weighted_select_kernel<GS>, gs, blk, 0, st, s->g, p.weights, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l,
                                    s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap, eid);
             else
@@ -1576,7 +1748,8 @@ int launch_call(coala_sampler_t* s, Plan& p) {
 int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed, uint64_t step,
                 const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
                 int64_t* ticket_out, void* stream, const float* weights, int64_t* const* edge_ids = nullptr, bool labor = false,
-                bool layer_dependency = false, const RelFan* rel = nullptr, const int32_t* etype = nullptr) {
+                bool layer_dependency = false, const RelFan* rel = nullptr, const int32_t* etype = nullptr,
+                const coala_sampler_walk_t* walk = nullptr, int32_t* const* visit_counts = nullptr) {
     int rc;
     if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, layers, bucketing, labor, rel != nullptr))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1585,7 +1758,7 @@ int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const
     // first waits there for the previous call's last kernel
     if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
     s->last_stream = st;
-    Plan p{seeds, seed, step, layers, bucketing, weights, edge_ids, st, layer_dependency, rel, etype};
+    Plan p{seeds, seed, step, layers, bucketing, weights, edge_ids, st, layer_dependency, rel, etype, walk, visit_counts};
     if ((rc = plan_call(p, n_seeds, fanouts, n_layers, bucketing ? bucketing->n_parts : 0, labor))) return rc;
     if ((rc = grow_workspace(s, p))) return rc;
     const uint64_t ticket = s->calls;
@@ -1730,6 +1903,41 @@ int coala_sampler_sample_layers_rel(coala_sampler_t* s, const int64_t* seeds, in
     }
     return sample_impl(s, seeds, n_seeds, kind, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream, nullptr,
                        edge_ids_out, false, false, fan, etype);
+}
+
+int coala_sampler_sample_layers_walk(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                     uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const coala_sampler_walk_t* walk,
+                                     int32_t* const* visit_counts_out, int64_t* n_src_host, int64_t* n_edges_host,
+                                     const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
+    if (!fanouts || !layers || !walk) return fail(COALA_EINVAL, "null argument");
+    if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
+    const int T = walk->num_traversals, W = walk->num_random_walks;
+    if (T < 1 || T > kMaxWalkLength) return fail(COALA_EINVAL, "num_traversals %d outside 1..%d", T, kMaxWalkLength);
+    if (W < 1 || W > kMaxWalks) return fail(COALA_EINVAL, "num_random_walks %d outside 1..%d", W, kMaxWalks);
+    if (W * T > kMaxVisits) return fail(COALA_EINVAL, "num_random_walks * num_traversals = %d: over the limit of %d visits", W * T, kMaxVisits);
+    if (walk->term_threshold >= kWalkThresholdMax) return fail(COALA_EINVAL, "term_threshold must be below 2^53 (termination_prob < 1)");
+    for (int l = 0; l < n_layers; ++l) {
+        if (fanouts[l] < 1 || fanouts[l] > 32) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (a walk layer keeps 1..32 neighbours)", fanouts[l]);
+        if (layers[l].indptr_local) return fail(COALA_EINVAL, "layer %d: a walk layer is fixed-stride, indptr_local must be NULL", l);
+    }
+    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream, nullptr,
+                       nullptr, false, false, nullptr, nullptr, walk, visit_counts_out);
+}
+
+int coala_sampler_random_walk(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t term_threshold,
+                              uint64_t seed, uint64_t step, int layer, int64_t* traces_out, void* stream) {
+    if (!s || (n > 0 && (!nodes || !traces_out))) return fail(COALA_EINVAL, "null argument");
+    if (n < 0 || n > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad node count");
+    if (num_walks < 1 || num_walks > kMaxWalks) return fail(COALA_EINVAL, "num_walks %d outside 1..%d", num_walks, kMaxWalks);
+    if (length < 1 || length > kMaxWalkLength) return fail(COALA_EINVAL, "length %d outside 1..%d", length, kMaxWalkLength);
+    if (term_threshold >= kWalkThresholdMax) return fail(COALA_EINVAL, "term_threshold must be below 2^53 (restart_prob < 1)");
+    if (layer < 0 || layer >= COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "layer must be 0..%d", COALA_SAMPLER_MAX_LAYERS - 1);
+    if (n == 0) return COALA_OK;
+    HIPCHK(hipSetDevice(s->device));
+    hipLaunchKernelGGL(walk_trace_kernel, dim3(grid1d(n * num_walks, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, s->g, nodes, n,
+                       WalkParams{length, num_walks, term_threshold}, seed, step, layer, traces_out);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
 }
 
 } // extern "C"

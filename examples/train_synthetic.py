@@ -15,6 +15,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --model_type rgat --num_rels 4 --num_heads 4 --sampler rel --rel_fan_out "10,3,0,-1;5,5,5,5"
   python examples/train_synthetic.py --model_type rsage --num_rels 4
   python examples/train_synthetic.py --model_type hgt --num_heads 4 --num_rels 4 --num_ntypes 3
+  python examples/train_synthetic.py --sampler pinsage --model_type pinsage --num_traversals 2 --termination_prob 0.5 --num_random_walks 10
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -32,8 +33,8 @@ import torch  # noqa: E402
 
 from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
-from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, GATv2, SageMean  # noqa: E402
-from COALA_GNN.sampler import LaborSampler, NeighborSampler, RelNeighborSampler, sort_csc_by_etype  # noqa: E402
+from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, GATv2, PinSAGE, SageMean  # noqa: E402
+from COALA_GNN.sampler import LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler, sort_csc_by_etype  # noqa: E402
 from COALA_GNN.synthetic import alloc_pinned_table, edge_types_by_source, powerlaw_csc  # noqa: E402
 
 
@@ -44,9 +45,14 @@ def main():
     ap.add_argument("--fan_out", type=str, default="5,5")
     ap.add_argument("--eval_fan_out", type=str, default=None,
                     help="fan-outs of the evaluation loader (default: --fan_out); -1 takes every in-edge, e.g. -1,-1 for full neighbourhoods")
-    ap.add_argument("--sampler", type=str, default="neighbor", choices=["neighbor", "labor", "rel"],
+    ap.add_argument("--sampler", type=str, default="neighbor", choices=["neighbor", "labor", "rel", "pinsage"],
                     help="labor: layer-neighbour sampling (LaborSampler) -- the same expected fan-out per node, fewer input nodes to fetch; "
-                         "rel: a fan-out per edge type (RelNeighborSampler, --rel_fan_out; needs --model_type rgcn, rgat, rsage or hgt)")
+                         "rel: a fan-out per edge type (RelNeighborSampler, --rel_fan_out; needs --model_type rgcn, rgat, rsage or hgt); "
+                         "pinsage: the --fan_out most visited nodes of short random walks, with their visit counts as edge weights "
+                         "(RandomWalkNeighborSampler; --num_traversals, --termination_prob, --num_random_walks)")
+    ap.add_argument("--num_traversals", type=int, default=2, help="with --sampler pinsage: hops per walk (1..16)")
+    ap.add_argument("--termination_prob", type=float, default=0.5, help="with --sampler pinsage: a hop after the first ends the walk with this probability")
+    ap.add_argument("--num_random_walks", type=int, default=10, help="with --sampler pinsage: walks per node (1..64)")
     ap.add_argument("--rel_fan_out", type=str, default=None,
                     help="with --sampler rel, in place of --fan_out: layers separated by ';', the --num_rels relations of a layer by ',' "
                          "(-1: every in-edge of the type, 0: none); a single number per layer applies to every relation, "
@@ -74,12 +80,12 @@ def main():
     # accepted so that the reference's command lines (examples/4GB_script.sh, Cache_compare_script.sh, Distribution_compare_script.sh) run as they are
     ap.add_argument("--num_layers", type=int, default=None, help="must equal the number of fan-outs when given")
     ap.add_argument("--feat_cpu", action="store_true", help="features in pinned host memory: always the case here (the NVMe tier is out of scope)")
-    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "gatv2", "sage", "gcn", "gin", "rgcn", "rgat", "rsage", "hgt"],
+    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "gatv2", "sage", "gcn", "gin", "rgcn", "rgat", "rsage", "hgt", "pinsage"],
                     help="sage: GraphSAGE (--sage_aggregator); gat: GAT with --num_heads heads (native attention aggregation); gatv2: the same model on GATv2Conv layers (--share_weights); gcn: GraphConv, "
                          "norm='both'; gin: GINConv layers (--gin_aggregator), an MLP in each; rgcn: RelGraphConv layers, one weight matrix per edge "
                          "type (--num_rels synthetic types, the source node's id modulo --num_rels; native relation-typed sum); rgat: RelGATConv layers, "
                          "a GATConv of --num_heads heads per edge type, summed (native relation-typed attention); rsage: RelSAGEConv layers, a SAGEConv "
-                         "'gcn' per edge type, summed")
+                         "'gcn' per edge type, summed; pinsage: WeightedSAGEConv layers on the visit counts of --sampler pinsage")
     ap.add_argument("--sage_aggregator", type=str, default="mean", choices=["mean", "gcn", "pool"],
                     help="aggregator of --model_type sage; pool: the maximum of relu(fc_pool(h)) over the neighbours (native max aggregation)")
     ap.add_argument("--gin_aggregator", type=str, default="sum", choices=["sum", "max", "mean"], help="aggregator of --model_type gin")
@@ -124,6 +130,10 @@ def main():
         ap.error(f"--model_type {args.model_type} needs --hidden_channels to be a multiple of --num_heads")
     if args.model_type == "hgt" and args.num_ntypes < 1:
         ap.error("--num_ntypes must be at least 1")
+    if (args.model_type == "pinsage") != (args.sampler == "pinsage"):
+        ap.error("--model_type pinsage and --sampler pinsage go together: the model reads the visit counts the sampler puts on its blocks")
+    if args.sampler == "pinsage" and (args.edge_weights != "none" or args.layer_dependency or eval_fan_out != fan_out):
+        ap.error("--sampler pinsage takes neither --edge_weights, --layer_dependency nor --eval_fan_out")
 
     dataset = None
     if args.path:   # IGBDatast_Shared_CSC_UVA / OGBDataset_Shared_UVA (:273-285): CSC in HBM, features in shared pinned host memory
@@ -181,6 +191,8 @@ def main():
         sampler = LaborSampler(fan_out, layer_dependency=args.layer_dependency, edge_ids=edge_ids)
     elif rel_fan_out is not None:
         sampler = RelNeighborSampler(rel_fan_out, args.num_rels)
+    elif args.sampler == "pinsage":
+        sampler = RandomWalkNeighborSampler(fan_out, args.num_traversals, args.termination_prob, args.num_random_walks)
     else:
         if args.layer_dependency:
             ap.error("--layer_dependency needs --sampler labor")
@@ -208,6 +220,8 @@ def main():
                     ntype=ntype).to(device)
     elif args.model_type == "rsage":
         model = RSAGE(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_rels).to(device)
+    elif args.model_type == "pinsage":
+        model = PinSAGE(args.dim, args.hidden_channels, args.num_classes, len(fan_out)).to(device)
     elif args.model_type == "rgcn":
         model = RGCN(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_rels,
                      None if args.rgcn_regularizer == "none" else args.rgcn_regularizer, args.num_bases).to(device)

@@ -449,6 +449,33 @@ int coala_sampler_sample_layers_rel(coala_sampler_t* s, const int64_t* seeds, in
                                     int n_layers, uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const int32_t* etype,
                                     int64_t* const* edge_ids_out, int64_t* n_src_host, int64_t* n_edges_host,
                                     const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream);
+/* Random-walk layers (DGL's dgl.sampling.RandomWalkNeighborSampler / PinSAGESampler on a homogeneous graph): as coala_sampler_sample_layers,
+ * but every layer is a walk layer.  From every destination node num_random_walks walks of num_traversals hops each start; a hop follows
+ * a uniformly drawn in-edge, and a hop after the first ends the walk with probability term_threshold / 2^53 (term_threshold =
+ * floor(termination_prob * 2^53) < 2^53, computed by the caller); a node without an in-edge ends it too.  The row of a destination node
+ * holds the fanouts[l] (1..32) most visited nodes, most visited first, a tie going to the smaller node id, -1 padded -- a fixed-stride
+ * block exactly as a uniform fixed layer's: indptr_local must be NULL, -1 fan-outs are refused, capacities, the source-list rule,
+ * bucketing and the ticket / wait protocol are those of coala_sampler_sample_layers (n_edges_host[l] = n_dst * fanouts[l]).
+ * visit_counts_out: NULL, or an array of n_layers device pointers, each NULL or int32[edge_cap of that layer] laid out like nbr_local:
+ * how often the slot's node was visited, 0 on padding.  The draws are keyed by (seed, step, layer, destination node) on a stream of
+ * their own (the exact rule is in the header of coala_sampler.hip): same arguments, same sample, whatever the batch.  Limits:
+ * num_traversals 1..16, num_random_walks 1..64, their product <= 512; COALA_EINVAL (with a message) before any launch otherwise.
+ * One launch stands where a uniform layer's sample_insert stands; nothing is added to the stream. */
+typedef struct coala_sampler_walk {
+    int32_t num_traversals;   /* hops per walk, 1..16                           */
+    int32_t num_random_walks; /* walks per destination node, 1..64              */
+    uint64_t term_threshold;  /* floor(termination_prob * 2^53), below 2^53     */
+} coala_sampler_walk_t;
+int coala_sampler_sample_layers_walk(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                     uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const coala_sampler_walk_t* walk,
+                                     int32_t* const* visit_counts_out, int64_t* n_src_host, int64_t* n_edges_host,
+                                     const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream);
+/* The walks themselves (DGL's dgl.sampling.random_walk): traces_out device int64[n, num_walks, length + 1]; traces_out[i, w, 0] =
+ * nodes[i], then the nodes walk w of nodes[i] visits, -1 once it has ended.  An out-of-range start node gives a row of -1.  By
+ * definition this is walk w of node nodes[i] in sampled layer `layer` (0..7) of coala_sampler_sample_layers_walk at the same seed,
+ * step and term_threshold: repeated start nodes get identical traces.  One kernel on `stream`; nothing is waited for. */
+int coala_sampler_random_walk(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t term_threshold,
+                              uint64_t seed, uint64_t step, int layer, int64_t* traces_out, void* stream);
 /* Counts of an earlier call, with the edge counts of its layers; returns the device-side refusal of a full, LABOR or relation layer, if any. */
 int coala_sampler_wait_layers(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host);
 
