@@ -1727,7 +1727,9 @@ int launch_call(coala_sampler_t* s, Plan& p) {
     // the device only -- the extent the previous call left clean
     p.items0 = first_full ? std::max<uint64_t>(s->clean_items, 1) : (uint64_t)p.info.n_seeds * (uint64_t)(p.info.fanouts[0] + 1);
     // the first layer's table: normally left clean by the previous call's last kernel
-    if (!first_full && (s->clean_items == 0 || table_size((int64_t)p.items0) > table_size((int64_t)s->clean_items))) {
+    const bool stale = !first_full && (s->clean_items == 0 || table_size((int64_t)p.items0) > table_size((int64_t)s->clean_items));
+    s->clean_items = 0; // from here on the table is written: a call that fails half-way leaves no clean extent behind
+    if (stale) {
         const uint32_t t0 = table_size((int64_t)p.items0);
         HIPCHK(hipMemsetAsync(s->tb.keys, 0xFF, (size_t)t0 * sizeof(long long), p.st));
         HIPCHK(hipMemsetAsync(s->tb.minpos, 0xFF, (size_t)t0 * sizeof(uint32_t), p.st));

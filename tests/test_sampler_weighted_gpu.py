@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from _full_ref import bucketed, full_layer
+from _sampler_sweep import TIE, check_weighted_call as _check_call
 from _util import csc_from_columns, edge_case_graph
 from _weighted_ref import inclusion_probabilities, reference_layers
 
@@ -21,7 +22,6 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIMIT = 8192 * 1024
-TIE = 1e-12
 
 
 def _to_gpu(torch, *arrays):
@@ -50,41 +50,6 @@ def _patterned_weights(ip, f, seed):
     w[kind == 6] = 0.5
     assert np.float32(1e-40) > 0
     return w
-
-
-def _check_call(smp, g, ip, ix, w, seeds, step, stream=None):
-    """One weighted sample: every layer equal to the restatement (near-tie rows excepted and counted).  -> (blocks, tolerated rows)"""
-    import torch
-    if stream is None:
-        _, _, blocks = smp.sample(g, torch.from_numpy(seeds).cuda(), step=step)
-    else:
-        with torch.cuda.stream(stream):
-            _, _, blocks = smp.sample(g, torch.from_numpy(seeds).cuda(), step=step)
-        stream.synchronize()
-    rev = list(reversed(smp.fanouts))
-    ref = reference_layers(ip, ix, w, seeds, rev, smp.seed, step)
-    n_dst, tolerated = len(seeds), 0
-    for l, (src_r, ind_r, loc_r, margin) in enumerate(ref):
-        b = blocks[len(rev) - 1 - l]
-        where = f"layer {l} of {rev}, {len(seeds)} seeds, step {step}"
-        assert b.num_dst == n_dst, where
-        src = b.src_nodes.cpu().numpy()
-        if ind_r is not None:
-            assert np.array_equal(src, src_r) and np.array_equal(b.indptr.cpu().numpy(), ind_r), where
-            assert np.array_equal(b.indices.cpu().numpy(), loc_r), where
-        else:
-            loc = b.nbr.cpu().numpy()
-            got = np.where(loc >= 0, src[np.maximum(loc, 0)], -1)
-            want = np.where(loc_r >= 0, src_r[np.maximum(loc_r, 0)], -1)
-            bad = np.nonzero((got != want).any(1))[0]
-            assert np.all(margin[bad] < TIE), f"rows {bad[:8]} differ beyond a near tie: {where}"
-            tolerated += len(bad)
-            if len(bad):     # the source lists of this layer and the next differ from here on: stop comparing
-                return blocks, tolerated
-            assert np.array_equal(src, src_r), f"source list differs: {where}"
-            assert np.array_equal(loc, loc_r), f"nbr_local differs: {where}"
-        n_dst = len(src_r)
-    return blocks, tolerated
 
 
 # ------------------------------------------------------------------------------------------------ 1. exactness
