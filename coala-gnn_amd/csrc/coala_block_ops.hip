@@ -1099,11 +1099,14 @@ __device__ __forceinline__ int rel_gat_chunk_dots(float* w, float* dot, const in
 
 // Backward, a_j = exp(e_j - lse[d, etype_j, h]) recomputed from the saved log-sum-exp; with dot_j = <g[d, h, :], feat[row_j, h, :]> and
 // G[r, h] = sum over the edges j of relation r of a_j dot_j -- relation r's <g, out_r>, which the stored out, summed over relations,
-// cannot give:
-//   grad_feat[row_j, h, :] += a_j g[d, h, :],  t_j = a_j (dot_j - G[etype_j, h]) (z_j > 0 ? 1 : slope),
+// cannot give -- and S[r, h] = sum of a_j over the same edges:
+//   grad_feat[row_j, h, :] += a_j g[d, h, :],  t_j = a_j (dot_j - G[etype_j, h] / S[etype_j, h]) (z_j > 0 ? 1 : slope),
 //   grad_el[row_j, h] += t_j,  grad_er[d, r, h] = sum of t_j over relation r's edges.
-// A first walk over the row's chunks gives a, dot and grad_feat, and adds every group's G in LDS (one masked wave_sum per relation
-// present and head, in chunk order).  A row of one chunk -- every fixed row -- then forms t from the a and dot still in LDS; a longer
+// S is 1 but for the rounding of lse and of expf.  Without the division the sum of a group's a_j (dot_j - G), zero in exact
+// arithmetic, is (1 - S) G, an error of one sign per group that whatever sums the t_j over edges afterwards (the gradients of attn_l
+// and attn_r) does not cancel.
+// A first walk over the row's chunks gives a, dot and grad_feat, and adds every group's G and S in LDS (two masked wave_sums per
+// relation present and head, in chunk order).  A row of one chunk -- every fixed row -- then forms t from the a and dot still in LDS; a longer
 // row walks its source rows a second time.  grad_feat and grad_el take hardware float atomics (zeroed by the caller); grad_er is summed
 // in LDS in a fixed order and written whole.
 template <bool CSR>
@@ -1114,13 +1117,14 @@ __global__ __launch_bounds__(kBlock) void rel_gat_aggregate_backward_kernel(
     int num_rels, int heads, int dim, float slope) {
     __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];     // a_j of the chunk, [edge][head]
     __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads];   // <g, feat_j>, [edge][head]
-    __shared__ float gs_lds[kWavesPerBlock][2 * kRelGatMaxStates]; // per (relation, head): G, the sum of t_j so far
+    __shared__ float gs_lds[kWavesPerBlock][3 * kRelGatMaxStates]; // per (relation, head): G, then G / S; the sum of t_j so far; S
     const WaveRows wr = wave_rows();
     const int lane = wr.lane; // a lambda below captures it
     float* w = w_lds[threadIdx.x >> 6];
     float* dot = dot_lds[threadIdx.x >> 6];
     float* G = gs_lds[threadIdx.x >> 6];
     float* ter = G + kRelGatMaxStates;
+    float* S = ter + kRelGatMaxStates;
     const int hd = heads * dim, rh = num_rels * heads;
     for (int64_t d = wr.wave; d < n_dst; d += wr.n_waves) {
         int64_t beg, end;
@@ -1132,6 +1136,7 @@ __global__ __launch_bounds__(kBlock) void rel_gat_aggregate_backward_kernel(
         for (int i = lane; i < rh; i += 64) {
             G[i] = 0.0f;
             ter[i] = 0.0f;
+            S[i] = 0.0f;
         }
         // t_j of the chunk whose a and dot are in LDS, into grad_el and ter
         auto t_step = [&](int32_t mine, int32_t t) {
@@ -1161,12 +1166,19 @@ __global__ __launch_bounds__(kBlock) void rel_gat_aggregate_backward_kernel(
                 const bool in = t == r;
                 todo &= ~__ballot(in);
                 for (int h = 0; h < heads; ++h) {
-                    const float gs = wave_sum(in ? w[lane * kGatMaxHeads + h] * dot[lane * kGatMaxHeads + h] : 0.0f);
-                    if (lane == 0) G[r * heads + h] += gs;
+                    const float a = in ? w[lane * kGatMaxHeads + h] : 0.0f;
+                    const float gs = wave_sum(a * dot[lane * kGatMaxHeads + h]);
+                    const float ss = wave_sum(a);
+                    if (lane == 0) {
+                        G[r * heads + h] += gs;
+                        S[r * heads + h] += ss;
+                    }
                 }
             }
         }
-        wave_lds_sync(); // G is whole
+        wave_lds_sync(); // G and S are whole
+        for (int i = lane; i < rh; i += 64) G[i] = S[i] > 0.0f ? G[i] / S[i] : 0.0f; // a group without an edge is never read
+        wave_lds_sync();
         if (end - beg <= 64) { // wave-uniform: the one chunk's a and dot are still in LDS
             t_step(mine, t);
         } else {

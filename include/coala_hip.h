@@ -603,8 +603,9 @@ int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, co
  * out and lse are deterministic, and both forms run the same code: bit-identical on a row both can express (a fixed row whose valid
  * entries come first).
  * Backward, with g = grad_out [n_dst, heads, dim], a_j = exp(e_j - lse[d, etype_j, h]), dot_j = <g[d, h, :], feat[row_j, h, :]> and
- * G[r, h] = sum of a_j dot_j over relation r's slots:
- *   t_j = a_j (dot_j - G[etype_j, h]) (z_j > 0 ? 1 : negative_slope);
+ * G[r, h] = sum of a_j dot_j, S[r, h] = sum of a_j over relation r's slots (S is 1 up to rounding; dividing by it makes a group's
+ * a_j (dot_j - G / S) sum to zero as the exact ones do):
+ *   t_j = a_j (dot_j - G[etype_j, h] / S[etype_j, h]) (z_j > 0 ? 1 : negative_slope);
  *   grad_feat[row_j, h, :] += a_j g[d, h, :];  grad_el[row_j, h] += t_j;  grad_er[d, r, h] = sum of t_j over relation r's slots.
  * grad_feat [P, heads, dim] and grad_el [P, heads] are accumulated with hardware float atomics: the caller zeroes them, and the order
  * of the additions varies.  grad_er [n_dst, num_rels, heads] is written whole (0 where (d, r) has no edge), deterministic, the same

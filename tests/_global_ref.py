@@ -8,21 +8,38 @@ imports or calls Block, block_ops or any *_aggregate.
 The formulas are those of the docstrings of COALA_GNN/nn.py and harness.py, run through torch autograd on the CPU with index_add on
 global ids; run() evaluates them in float64 or float32 (every array cast down: the rounding scale of the GPU tolerance), and in an
 'abs' mode -- every input replaced by its absolute value, every subtraction by an addition, relu by the identity, the winners of
-the maxima kept -- which gives, for every output and every gradient, the magnitude of the same sums taken over absolute values
-(the scale of the float64 agreement bound).  For the softmax of GAT and the final log_softmax the abs mode adds the magnitude of
-the term that autograd subtracts (a_k * out for the attention, softmax for log_softmax), so the magnitude is never below the sum of
-the absolute values of the true gradient's terms.
+the maxima kept -- which gives, for every output and every gradient, the magnitude of the same sums taken over absolute values (the
+scale of the float64 agreement bound).  For the softmax of GAT and the final log_softmax the abs mode adds the magnitude of the term
+that autograd subtracts (a_k * out for the attention, softmax for log_softmax), so the magnitude is never below the sum of the
+absolute values of the true gradient's terms.  The typed models (MODELS_TYPED) follow the same rule wherever autograd subtracts: the
+softmax of GATv2 and the per-relation softmax of RGAT (a_k * out of that softmax), PinSAGE's L2 normalisation (z <z, dz> / |z|^3
+next to dz / |z|) and the final log_softmax.
+
+For the typed models the abs mode replays, like the winners of a maximum, the two non-linear coefficients of the float64 evaluation:
+the attention a (the scores of absolute values would give another, nearly one-hot softmax) and PinSAGE's row z with its norm (the
+abs mode's own z is several times the true one; divided by the true norm it would give rows above unit size that grow per layer, and
+a bound above the values it bounds).  The price: for these models the magnitude is no longer a pure sum over absolute values.  The
+value that leaves a softmax or a normalisation is the true one (a, z / |z|), so the rounding of the scores and of z enters the bound
+through the first-order terms of the gradients only, not through the value; what follows such a value is again a sum of absolute
+values.  test_models_global_cpu.py asserts that the bound stays far below the values it bounds.
 
 Kink gap: the smallest relative distance of the float64 evaluation to a discontinuity of the gradient -- |z| / max|z| over every
 relu (and GAT leaky_relu) pre-activation of a live row, and (winner - runner-up) / max|message| over every maximum with candidates
 from at least two different source nodes.  Two ties are not kinks and are not counted: slots of the same source node with the same
 message (a repeated edge: the gradient reaches the same row either way), and a tie at exactly 0 (in these models an exact zero
-message comes from a relu or from a zero edge weight and carries no gradient whichever slot wins)."""
+message comes from a relu or from a zero edge weight and carries no gradient whichever slot wins).  GATv2's leaky_relu sits on
+the element-wise sum fs[src] + fd[dst] (E * H * D values per layer, every one counted); PinSAGE's normalisation has its kink at a
+row of zero norm: |z| / max |z| over the destination rows, so a live row of exactly zero norm gives gap 0.
+
+run(..., fault=) switches on one deliberate mistake of the reference itself (the teeth tests of test_models_global_cpu.py):
+'softmax_over_all' takes RGAT's softmax over all of a destination's edges instead of per relation, 'out_of_range_as_0' lets an
+edge whose type is outside [0, num_rels) through as relation 0."""
 import numpy as np
 import torch
 
 MODELS = ("sagemean", "sage_mean", "sage_gcn", "sage_pool", "sage_mean_w", "sage_gcn_w", "sage_pool_w", "gcn", "gcn_w", "gat",
           "gin_sum", "gin_max", "gin_mean", "rgcn", "rgcn_basis")
+MODELS_TYPED = ("gatv2", "gatv2_shared", "rgat", "rsage", "pinsage")
 
 
 def _np(t):
@@ -70,8 +87,22 @@ def decode(block):
     return Layer(np.stack(cols, 1) if valid.any() else np.zeros((0, len(cols)), dtype=np.int64), dst, src, block.nbr is not None)
 
 
-def check_edges(indptr, indices, layers, fanouts, seeds, weights=None, labels=None, block_labels=None, labor=False):
-    """The integer part, exact.  layers: decoded blocks in model order (input layer first), fanouts in the same order."""
+def slot_data(block, key):
+    """block.edata[key] of the valid slots in slot order (the order of decode's rows): per-slot data of a block without edge ids, such
+    as the visit counts of a random-walk block.  Padding slots must hold 0."""
+    v = _np(block.edata[key]).reshape(-1)
+    loc = _np(block.indices if block.nbr is None else block.nbr).reshape(-1)
+    assert v.shape == loc.shape, f"edata[{key!r}] is not shaped like the slot array"
+    assert np.all(v[loc < 0] == 0), f"a padding slot carries a value in edata[{key!r}]"
+    return v[loc >= 0]
+
+
+def check_edges(indptr, indices, layers, fanouts, seeds, weights=None, labels=None, block_labels=None, labor=False, rel_etype=None,
+                walk=None, visits=None):
+    """The integer part, exact.  layers: decoded blocks in model order (input layer first), fanouts in the same order.
+    rel_etype: the graph's edge types, for the layers of a relation sampler -- every entry of fanouts is then one fan-out per relation.
+    walk: for random-walk layers, per layer the int64 [E, 3] rows (dst_gid, src_gid, visit count) of the sampler's restatement in slot
+    order; visits: the decoded blocks' own counts per layer.  A walk's neighbour is no edge of the graph: the rows must be equal."""
     deg_all = np.diff(indptr)
     for l, (lay, f) in enumerate(zip(layers, fanouts)):
         tri, dst = lay.tri, lay.dst
@@ -79,7 +110,12 @@ def check_edges(indptr, indices, layers, fanouts, seeds, weights=None, labels=No
         assert len(np.unique(dst)) == len(dst) and len(np.unique(lay.src)) == len(lay.src), "a node listed twice"
         assert np.all((s >= 0) & (s < len(deg_all)))
         per_row = np.bincount(d, minlength=len(deg_all))[dst]
-        if tri.shape[1] == 3:
+        if walk is not None:
+            assert tri.shape[1] == 2 and lay.fixed, f"layer {l}: a walk block is fixed-stride and has no edge ids"
+            got = np.concatenate([tri, np.asarray(visits[l]).astype(np.int64).reshape(-1, 1)], 1)
+            assert got.shape == walk[l].shape and np.array_equal(got, walk[l]), f"layer {l}: (dst, src, visit count) differ from the restatement"
+            assert np.all(got[:, 2] > 0) and np.all(per_row <= f), f"layer {l}: a chosen neighbour was never visited, or a row holds more than {f}"
+        elif tri.shape[1] == 3:
             e = tri[:, 2]
             assert np.all((e >= indptr[d]) & (e < indptr[d + 1])), f"layer {l}: an edge id outside its destination's column"
             assert np.all(indices[e] == s), f"layer {l}: indices[eid] is not the source node"
@@ -92,7 +128,19 @@ def check_edges(indptr, indices, layers, fanouts, seeds, weights=None, labels=No
             took, tcnt = np.unique(d * N + s, return_counts=True)
             at = np.minimum(np.searchsorted(have, took), len(have) - 1)
             assert np.array_equal(have[at], took) and np.all(tcnt <= cnt[at]), f"layer {l}: a sampled pair is not an in-edge"
-        if f == -1:
+        if walk is not None:
+            pass
+        elif rel_etype is not None:
+            R, N = len(f), len(deg_all)
+            assert tri.shape[1] == 3, f"layer {l}: a relation layer needs its edge ids"
+            fr = np.asarray(f, dtype=np.int64)
+            have = np.bincount(np.repeat(np.arange(N), deg_all) * R + rel_etype, minlength=N * R).reshape(N, R)[dst]
+            took = np.bincount(d * R + rel_etype[e], minlength=N * R).reshape(N, R)[dst]
+            assert np.array_equal(took, np.where(fr < 0, have, np.minimum(fr, have))), \
+                f"layer {l}: per (row, relation) a layer holds every edge for fan-out -1, none for 0, min(f_r, deg_r) otherwise"
+            same_row = d[1:] == d[:-1]
+            assert np.all(e[1:][same_row] > e[:-1][same_row]), f"layer {l}: edge ids must ascend within a row"
+        elif f == -1:
             assert np.array_equal(per_row, deg_all[dst]), f"layer {l}: a full layer must hold every in-edge"
         elif labor:
             assert np.all(per_row <= deg_all[dst]) and np.all(per_row[deg_all[dst] <= f] == deg_all[dst][deg_all[dst] <= f])
@@ -123,11 +171,11 @@ class _Ctx(object):
         a = np.abs(a) if self.mode == "abs" else a
         return torch.tensor(np.asarray(a), dtype=self.dtype).requires_grad_(grad)
 
-    def kink(self, z, rows):
-        """Record pre-activation z [N, ...] on its live rows."""
+    def kink(self, z, rows=None):
+        """Record pre-activation z [N, ...] on its live rows (rows None: z has one row per edge, all of them live)."""
         if self.mode == "abs":
             return
-        v = z.detach()[rows]
+        v = z.detach() if rows is None else z.detach()[rows]
         self.pre.append(v)
         if v.numel():
             self.gaps.append(float(v.abs().min() / v.abs().max()))
@@ -288,7 +336,97 @@ def _gat(ctx, g, P, p, h, heads, slope=0.2):
     return out + P[p + "bias"].view(1, heads, -1)
 
 
-def _forward(ctx, kind, P, X, layers, edata, heads, num_rels):
+def _attend(ctx, e, msg, dst):
+    """Softmax of the scores e [E, H] over the edges of each destination, then the sum of a * msg [E, H, D] per destination -> [N, H, D].
+    The abs mode keeps the attention a of the float64 evaluation (replayed like the winners of a maximum: the scores of absolute
+    values would give another, nearly one-hot softmax) and takes every term of d out / d e_k = a_k (msg_k - out) positive."""
+    H = e.shape[1]
+    if ctx.mode == "abs":
+        a = ctx.winners[ctx._k]
+        ctx._k += 1
+        de = e - e.detach()
+        a = a * (1 + de + ctx.seg_sum(a * de, dst)[dst])
+        return ctx.seg_sum(a.unsqueeze(-1) * msg, dst)
+    m = torch.full((ctx.N, H), float("-inf"), dtype=ctx.dtype).scatter_reduce(0, dst.view(-1, 1).expand(-1, H), e.detach(), "amax")
+    pexp = torch.exp(e - m[dst])
+    a = pexp / ctx.seg_sum(pexp, dst)[dst]
+    ctx.winners.append(a.detach())
+    return ctx.seg_sum(a.unsqueeze(-1) * msg, dst)
+
+
+def _leaky(ctx, z, slope):
+    ctx.kink(z)
+    return z if ctx.mode == "abs" else torch.nn.functional.leaky_relu(z, slope)
+
+
+def _gatv2(ctx, g, P, p, h, heads, shared, slope=0.2):
+    fs = _lin(h, P[p + "fc_src.weight"], P[p + "fc_src.bias"]).view(ctx.N, heads, -1)
+    if shared:
+        fd = g.dst_rows(fs)
+    else:
+        fd = _lin(g.dst_rows(h), P[p + "fc_dst.weight"], P[p + "fc_dst.bias"]).view(ctx.N, heads, -1)
+    e = (_leaky(ctx, fs[g.src] + fd[g.dst], slope) * P[p + "attn"]).sum(-1)
+    return _attend(ctx, e, fs[g.src], g.dst)
+
+
+def _rel_types(g, num_rels, fault):
+    t = g.etype()
+    return torch.where((t < 0) | (t >= num_rels), 0, t) if fault == "out_of_range_as_0" else t
+
+
+def _rgat(ctx, g, P, p, h, heads, num_rels, fault, slope=0.2):
+    hd = g.dst_rows(h)
+    t = _rel_types(g, num_rels, fault)
+    assert P[p + "fc_weight"].shape[0] == num_rels
+    out, scores, msgs, dsts = 0, [], [], []
+    for r in range(num_rels):
+        k = t == r
+        f = _lin(h, P[p + "fc_weight"][r]).view(ctx.N, heads, -1)
+        fdst = _lin(hd, P[p + "fc_weight"][r]).view(ctx.N, heads, -1)
+        el, er = (f * P[p + "attn_l"][r]).sum(-1), (fdst * P[p + "attn_r"][r]).sum(-1)
+        e = _leaky(ctx, el[g.src[k]] + er[g.dst[k]], slope)
+        if fault == "softmax_over_all":
+            scores.append(e), msgs.append(f[g.src[k]]), dsts.append(g.dst[k])
+        else:
+            out = out + _attend(ctx, e, f[g.src[k]], g.dst[k])                # the softmax of relation r's edges alone
+    if fault == "softmax_over_all":
+        out = _attend(ctx, torch.cat(scores), torch.cat(msgs), torch.cat(dsts))
+    return out + P[p + "bias"].sum(0).view(1, heads, -1)
+
+
+def _rsage(ctx, g, P, p, h, num_rels, fault):
+    hd = g.dst_rows(h)
+    t = _rel_types(g, num_rels, fault)
+    assert P[p + "fc_neigh_weight"].shape[0] == num_rels
+    out = 0
+    for r in range(num_rels):
+        k = t == r
+        c = ctx.count(g.dst[k])                                        # c_{d, r}
+        h_neigh = (ctx.seg_sum(h[g.src[k]], g.dst[k]) + hd) / (c + 1).unsqueeze(-1)
+        out = out + _lin(h_neigh, P[p + "fc_neigh_weight"][r], P[p + "bias"][r])
+    return out
+
+
+def _pinsage(ctx, g, P, p, h, w):
+    q = ctx.relu(_lin(h, P[p + "Q.weight"], P[p + "Q.bias"]), torch.unique(g.src))
+    n = ctx.seg_sum(q[g.src] * w.unsqueeze(-1), g.dst) / ctx.seg_sum(w, g.dst).clamp_min(1).unsqueeze(-1)
+    z = ctx.relu(_lin(torch.cat([n, g.dst_rows(h)], 1), P[p + "W.weight"], P[p + "W.bias"]), g.dst_ids)
+    if ctx.mode == "abs":
+        # d (z / |z|) = dz / |z| - z <z, dz> / |z|^3 with both terms taken positive.  The coefficients z and |z| are those of the float64
+        # evaluation, replayed: they are at most 1 / |z| together, where the abs mode's own z (a sum of absolute values, relu the
+        # identity) in their place is several times larger and enters squared, in every layer.  The same linear map gives the value: the
+        # abs mode's z stands for dz, being the scale of the rounding of the true z.
+        zr, norm = ctx.winners[ctx._k]
+        ctx._k += 1
+        return z / norm + zr * (zr * z).sum(1, keepdim=True) / norm ** 3
+    norm = z.norm(2, 1, keepdim=True)
+    ctx.kink(norm, g.dst_ids)
+    norm = torch.where(norm == 0, torch.ones_like(norm), norm)
+    ctx.winners.append((z.detach(), norm.detach()))
+    return z / norm
+
+
+def _forward(ctx, kind, P, X, layers, edata, heads, num_rels, fault=None, visits=None):
     h = X
     L = len(layers)
     for i, lay in enumerate(layers):
@@ -309,18 +447,30 @@ def _forward(ctx, kind, P, X, layers, edata, heads, num_rels):
             out = _rgcn(ctx, g, P, p, h, num_rels)
         elif kind == "gat":
             out = _gat(ctx, g, P, p, h, heads)
+        elif kind in ("gatv2", "gatv2_shared"):
+            out = _gatv2(ctx, g, P, p, h, heads, kind == "gatv2_shared")
+        elif kind == "rgat":
+            out = _rgat(ctx, g, P, p, h, heads, num_rels, fault).flatten(1)
+        elif kind == "rsage":
+            out = _rsage(ctx, g, P, p, h, num_rels, fault)
+        elif kind == "pinsage":
+            out = _pinsage(ctx, g, P, p, h, ctx.t(visits[i]))
         else:
             raise ValueError(kind)
         out = g.only_dst(out)
-        if i + 1 < L:
-            h = out.flatten(1) if kind == "gat" else ctx.relu(out, g.dst_ids)
+        if kind == "pinsage":               # unit rows: nothing stands between the layers
+            h = out
+        elif i + 1 < L:
+            h = out.flatten(1) if kind in ("gat", "gatv2", "gatv2_shared") else ctx.relu(out, g.dst_ids)
         else:
             h = out
     seeds = torch.from_numpy(np.ascontiguousarray(layers[-1].dst))
     h = h[seeds]
-    if kind == "gat":
+    if kind in ("gat", "gatv2", "gatv2_shared"):
         h = h.mean(1)
         h = h + torch.logsumexp(h, -1, keepdim=True) if ctx.mode == "abs" else h.log_softmax(-1)
+    elif kind in ("rgat", "rsage", "pinsage"):
+        h = _lin(h, P["linear.weight"], P["linear.bias"])
     return h
 
 
@@ -332,12 +482,13 @@ class Result(object):
         return dict(logits=self.logits, grad_X=self.grad_X, **self.grads)
 
 
-def run(kind, params, X, Cmat, layers, edata, mode="real", dtype=torch.float64, heads=2, num_rels=3, replay=None):
-    """params: {name: numpy array} (the model's named parameters).  The loss is (logits * Cmat).sum()."""
+def run(kind, params, X, Cmat, layers, edata, mode="real", dtype=torch.float64, heads=2, num_rels=3, replay=None, fault=None, visits=None):
+    """params: {name: numpy array} (the model's named parameters).  The loss is (logits * Cmat).sum().  visits: for 'pinsage', per layer
+    the visit counts of the valid slots in slot order (the rows of Layer.tri); fault: see the module's docstring."""
     ctx = _Ctx(mode, dtype, X.shape[0], replay)
     P = {k: ctx.t(v, grad=True) for k, v in params.items()}
     Xt = ctx.t(X, grad=True)
-    logits = _forward(ctx, kind, P, Xt, layers, edata, heads, num_rels)
+    logits = _forward(ctx, kind, P, Xt, layers, edata, heads, num_rels, fault, visits)
     (logits * ctx.t(Cmat)).sum().backward()
     r = Result()
     r.logits = logits.detach().double().numpy()
@@ -377,16 +528,17 @@ class Evaluation(object):
             assert not bad.any(), f"{what} {k}: {int(bad.sum())} elements off, largest error {np.abs(got[k] - want[k]).max():.3e}, " \
                                   f"bound there {64 * 2.0 ** -53 * mag[k][bad].min():.3e}"
 
-    def check_kernel(self, got, what="", factor=4.0, log=print, scalar_factor=None):
+    def check_kernel(self, got, what="", factor=4.0, log=print, scalar_factor=None, factors=None):
         """got: {name: array} from the fp32 kernel path.  Prints E32, the measured ratio and the magnitude of the same sums over
         absolute values for every array, then asserts.  scalar_factor, if given, replaces factor for one-element arrays, whose E32
-        is a single draw of the rounding error and not a maximum over many elements."""
+        is a single draw of the rounding error and not a maximum over many elements; factors: {array name: its own factor}."""
         want, mag = self.ref.arrays(), self.mag.arrays()
         assert set(got) == set(want), (sorted(got), sorted(want))
         worst = []
         for k in sorted(want):
             assert got[k].shape == want[k].shape, (what, k, got[k].shape, want[k].shape)
-            tol, e32 = self.tolerance(k, scalar_factor if scalar_factor is not None and want[k].size == 1 else factor)
+            f = (factors or {}).get(k, scalar_factor if scalar_factor is not None and want[k].size == 1 else factor)
+            tol, e32 = self.tolerance(k, f)
             err = float(np.abs(got[k] - want[k]).max()) if want[k].size else 0.0
             log(f"{what} {k}: error {err:.3e} E32 {e32:.3e} ratio {err / e32 if e32 else float('nan'):.2f} bound {tol:.3e} "
                 f"abs-sum {float(mag[k].max()) if mag[k].size else 0.0:.3e}")

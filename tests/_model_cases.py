@@ -10,7 +10,14 @@ positions) then still describes the same arithmetic.  edata: 'w' fp32 in [0.1, 1
 ndata: 'labels'.  Feature width 20, hidden 12, 5 classes, 2 GAT heads.
 
 `step` of a case is the sampler's step and seeds the model's parameters and the loss matrix Cmat.  It is chosen on the CPU (STEPS
-below) so that the float64 reference stays clear of every gradient discontinuity: kink gap >= tau (see _global_ref)."""
+below) so that the float64 reference stays clear of every gradient discontinuity: kink gap >= tau (see _global_ref).
+
+CASES_TYPED is a second table of the same shape for the models of R.MODELS_TYPED -- GATv2 with and without shared weights, RGAT, RSAGE
+and PinSAGE -- on the same graph, samplers and seeding rule (2 heads, 3 relations, hidden 12), with steps of its own (STEPS_TYPED).  It
+adds the blocks of RelNeighborSampler ("rel", sampled on typed_graph(): graph() with every column sorted by edge type; twin
+_rel_fanout_ref) and of RandomWalkNeighborSampler ("walk55", "walk333"; twin _pinsage_ref, whose visit counts are the blocks'
+edata['weights'] and the reference's weights), and two models of two relations ("-r2") that must drop the graph's type-2 edges.  CASES,
+STEPS and R.MODELS are a table of their own: the round-robin of _cases() indexes R.MODELS, so nothing is appended there."""
 import collections
 import functools
 
@@ -22,6 +29,10 @@ from _edge_id_ref import full_ids
 from _full_ref import bucketed, fixed_layer, full_layer
 from _labor_ref import edge_weights as labor_edge_weights
 from _labor_ref import reference_layers as labor_layers
+from _pinsage_ref import reference_layers as walk_layers
+from _pinsage_ref import threshold as walk_threshold
+from _rel_fanout_ref import reference_layers as rel_layers
+from _rel_fanout_ref import sort_by_type
 from _util import csc_from_columns
 from _weighted_ref import weighted_layer
 
@@ -35,6 +46,9 @@ Case = collections.namedtuple("Case", "id sampler G edge_ids model step")
 SAMPLERS = {   # name -> (class, fan-outs in model order, prob)
     "ns55": ("ns", [5, 5], None), "nsFF": ("ns", [-1, -1], None), "ns4F": ("ns", [4, -1], None), "nsF4": ("ns", [-1, 4], None),
     "ns333": ("ns", [3, 3, 3], None), "w55": ("ns", [5, 5], "w"), "labor55": ("labor", [5, 5], None),
+}
+SAMPLERS_TYPED = {   # the samplers of CASES_TYPED only: "rel" -> fan-outs per relation, on typed_graph(); "walk" -> (T, W, p) in place of prob
+    "rel": ("rel", [[2, 3, 1], [-1, 2, 0]], None), "walk55": ("walk", [5, 5], (2, 10, 0.5)), "walk333": ("walk", [3, 3, 3], (2, 10, 0.5)),
 }
 NEEDS_EDATA = ("sage_mean_w", "sage_gcn_w", "sage_pool_w", "gcn_w", "rgcn", "rgcn_basis")   # read graph.edata through the edge ids
 IGNORES_DST_ROWS = ("gcn", "gcn_w")                                                       # GraphConv has no self term
@@ -141,10 +155,91 @@ CASES = _cases()
 GRAD_CASES = CASES   # every case compares its gradients on the GPU
 
 
-def make_model(kind, n_layers, seed):
+@functools.lru_cache(None)
+def typed_graph():
+    """graph() with every column stably sorted by edge type (what RelNeighborSampler asks for): indices, w and etype permuted together."""
+    g = graph()
+    perm = sort_by_type(g.indptr, g.etype)
+    return g._replace(indices=g.indices[perm], w=g.w[perm], etype=g.etype[perm])
+
+
+def sampler_of(case):
+    """-> (class, fan-outs in model order, prob or walk parameters) of a case of either table."""
+    return SAMPLERS[case.sampler] if case.sampler in SAMPLERS else SAMPLERS_TYPED[case.sampler]
+
+
+def graph_of(case):
+    return typed_graph() if sampler_of(case)[0] == "rel" else graph()
+
+
+def num_rels_of(case):
+    """The relations the case's model is built with: 2 for the '-r2' cases, whose models must drop the graph's type-2 edges."""
+    return 2 if case.id.endswith("-r2") else NRELS
+
+
+# The typed table's steps, by the same rule, searched over steps 0 .. 63: the first step at which the kink gap is at least 1.5 tau and
+# every fault that applies to the case (test_models_global_cpu.typed_faults) moves the logits by at least 1500 times the GPU tolerance
+# (the tests ask for tau and 1000).  Every case found its step, so none was replaced.  GATv2 without shared weights counts E * H * D
+# leaky_relu arguments per layer and needs a later step everywhere; step 0 serves the others except walk333.  Measured at these steps,
+# "case gap/tau": gap 3.1e-06 .. 1.5e-04, tau 1.0e-06 .. 2.9e-06, smallest gap / tau 1.55 (ns4F-b0-gatv2); the
+# smallest move of the logits by a fault is 27728 times the tolerance.
+#   ns55-b0-gatv2 5.4e-06/2.1e-06; ns55-b0-gatv2_shared 1.7e-05/2.3e-06; ns55-b0-rgat 1.3e-04/2.1e-06; ns55-b0-rsage
+#   6.7e-05/1.3e-06; ns55-b3-gatv2 5.4e-06/2.1e-06; ns55-b3-gatv2_shared 1.7e-05/2.3e-06; ns55-b3-rgat 1.3e-04/2.1e-06;
+#   ns55-b3-rsage 6.7e-05/1.3e-06; nsFF-b0-gatv2 4.4e-06/1.5e-06; nsFF-b0-gatv2_shared 5.8e-06/2.1e-06; nsFF-b0-rgat
+#   7.0e-05/2.0e-06; nsFF-b0-rsage 8.2e-06/1.2e-06; nsFF-b3-gatv2 4.4e-06/1.5e-06; nsFF-b3-gatv2_shared 5.8e-06/2.1e-06;
+#   nsFF-b3-rgat 7.0e-05/2.0e-06; nsFF-b3-rsage 8.2e-06/1.2e-06; ns4F-b0-gatv2 3.1e-06/2.0e-06; ns4F-b0-gatv2_shared
+#   6.2e-06/2.5e-06; ns4F-b3-rgat 8.1e-05/2.1e-06; ns4F-b3-rsage 6.0e-05/1.3e-06; nsF4-b0-gatv2 4.8e-06/2.0e-06;
+#   nsF4-b0-gatv2_shared 6.5e-06/2.1e-06; nsF4-b3-rgat 1.5e-04/2.3e-06; nsF4-b3-rsage 7.2e-05/1.4e-06; ns333-b0-gatv2
+#   1.5e-05/2.9e-06; ns333-b0-gatv2_shared 6.6e-06/1.7e-06; ns333-b3-rgat 5.8e-05/2.7e-06; ns333-b3-rsage 3.2e-05/1.6e-06;
+#   w55-b0-gatv2 9.2e-06/2.2e-06; w55-b0-gatv2_shared 6.5e-06/2.1e-06; w55-b3-rgat 1.0e-04/2.3e-06; w55-b3-rsage 7.2e-05/1.4e-06;
+#   labor55-b0-gatv2 9.2e-06/2.0e-06; labor55-b0-gatv2_shared 6.5e-06/2.6e-06; labor55-b3-rgat 9.0e-05/2.1e-06; labor55-b3-rsage
+#   6.6e-05/1.3e-06; rel-b0-rgat 1.7e-05/1.8e-06; rel-b0-rsage 7.2e-05/1.4e-06; rel-b3-rgat 1.7e-05/1.8e-06; rel-b3-rsage
+#   7.2e-05/1.4e-06; walk55-b0-pinsage 4.5e-05/2.2e-06; walk55-b3-pinsage 4.5e-05/2.2e-06; walk333-b0-pinsage 8.7e-06/2.1e-06;
+#   ns55-b3-rgat-r2 3.7e-05/2.1e-06; ns55-b3-rsage-r2 9.5e-05/1.0e-06;
+STEPS_TYPED = {
+    "ns55-b0-gatv2": 1, "ns55-b3-gatv2": 1, "nsFF-b0-gatv2": 3, "nsFF-b3-gatv2": 3, "ns4F-b0-gatv2": 1, "nsF4-b0-gatv2": 1,
+    "ns333-b0-gatv2": 1, "w55-b0-gatv2": 1, "labor55-b0-gatv2": 1, "walk333-b0-pinsage": 2,
+}
+
+
+def _cases_typed():
+    out = []
+
+    def add(s, G, m, suffix=""):
+        cid = f"{s}-b{G}-{m}{suffix}"
+        out.append(Case(cid, s, G, not s.startswith("walk"), m, STEPS_TYPED.get(cid, 0)))
+
+    four = R.MODELS_TYPED[:4]
+    for s in ("ns55", "nsFF"):
+        for G in (0, 3):
+            for m in four:
+                add(s, G, m)
+    # Four models dealt two per cell: the period is one pair of G, so on these five samplers both GATv2 models meet only the plain
+    # blocks (G = 0) and RGAT and RSAGE only the bucketed ones (G = 3).  Every model meets both G on ns55 and nsFF above.
+    k = 0
+    for s in ("ns4F", "nsF4", "ns333", "w55", "labor55"):
+        for G in (0, 3):
+            for _ in range(2):
+                add(s, G, four[k % 4])
+                k += 1
+    for G in (0, 3):
+        for m in ("rgat", "rsage"):
+            add("rel", G, m)                        # RelNeighborSampler's blocks, on typed_graph()
+    for s, G in (("walk55", 0), ("walk55", 3), ("walk333", 0)):
+        add(s, G, "pinsage")                        # RandomWalkNeighborSampler's blocks: no edge ids, edata['weights']
+    for m in ("rgat", "rsage"):
+        add("ns55", 3, m, "-r2")                    # models of two relations on the graph of three
+    return out
+
+
+CASES_TYPED = _cases_typed()
+
+
+def make_model(kind, n_layers, seed, num_rels=NRELS):
     """The harness model of a case, fp32 on the CPU, dropout 0; every 1-D parameter (the biases, zero at initialisation, and GIN's eps)
-    is drawn from N(0, 0.3) so that none of them is invisible."""
-    from COALA_GNN.harness import GAT, GCN, GIN, RGCN, SAGE, SageMean
+    is drawn from N(0, 0.3) so that none of them is invisible -- and so are the biases of RGAT's and RSAGE's layers, zero at
+    initialisation too, which are stacked over the relations and so 2-D."""
+    from COALA_GNN.harness import GAT, GATv2, GCN, GIN, RGAT, RGCN, RSAGE, SAGE, PinSAGE, SageMean
     torch.manual_seed(1000 + seed)
     if kind == "sagemean":
         m = SageMean(IN, HID, NCLS, n_layers)
@@ -161,11 +256,19 @@ def make_model(kind, n_layers, seed):
     elif kind in ("rgcn", "rgcn_basis"):
         m = RGCN(IN, HID, NCLS, n_layers, NRELS, regularizer="basis" if kind == "rgcn_basis" else None,
                  num_bases=2 if kind == "rgcn_basis" else None, dropout=0.0)
+    elif kind in ("gatv2", "gatv2_shared"):
+        m = GATv2(IN, HID, NCLS, n_layers, HEADS, share_weights=kind == "gatv2_shared")
+    elif kind == "rgat":
+        m = RGAT(IN, HID, NCLS, n_layers, num_rels, n_heads=HEADS, dropout=0.0)
+    elif kind == "rsage":
+        m = RSAGE(IN, HID, NCLS, n_layers, num_rels, dropout=0.0)
+    elif kind == "pinsage":
+        m = PinSAGE(IN, HID, NCLS, n_layers)
     else:
         raise ValueError(kind)
     with torch.no_grad():
-        for p in m.parameters():
-            if p.dim() == 1:
+        for name, p in m.named_parameters():
+            if p.dim() == 1 or (kind in ("rgat", "rsage") and name.endswith(".bias")):
                 p.normal_(0.0, 0.3)
     return m
 
@@ -234,15 +337,22 @@ def loader_train_ids():
 def reference_blocks(oracle, case, seeds=None, sampler_seed=SAMPLER_SEED):
     """The blocks of a case from the numpy restatements of the samplers, as CPU Block objects in model order."""
     from COALA_GNN.sampler import Block
-    g = graph()
+    g = graph_of(case)
     if seeds is not None:
         g = g._replace(seeds=np.asarray(seeds, dtype=np.int64))
     SAMPLER_SEED = sampler_seed
-    cls, fanouts, prob = SAMPLERS[case.sampler]
+    cls, fanouts, prob = sampler_of(case)
     rev = list(reversed(fanouts))
     layers = []   # sampling order: (src, indptr_local or None, nbr_local, eid)
+    counts = None
     if cls == "labor":
         layers = labor_layers(g.indptr, g.indices, g.seeds, rev, SAMPLER_SEED, case.step)
+    elif cls == "rel":
+        layers = rel_layers(g.indptr, g.indices, g.etype, g.seeds, rev, SAMPLER_SEED, case.step)
+    elif cls == "walk":
+        walked = walk_twin(case.sampler, case.step)
+        layers = [(src, None, loc, None) for src, loc, cnt, nbr in walked]
+        counts = [cnt for src, loc, cnt, nbr in walked]
     else:
         dst = g.seeds
         for l, f in enumerate(rev):
@@ -273,6 +383,8 @@ def reference_blocks(oracle, case, seeds=None, sampler_seed=SAMPLER_SEED):
             kw["eid"] = torch.from_numpy(np.ascontiguousarray(eid, dtype=np.int64))
         if cls == "labor":
             kw["edata_lazy"] = {"edge_weights": (lambda ip=ip: torch.from_numpy(labor_edge_weights(ip)))}
+        if counts is not None:   # the twin's visit counts, as RandomWalkNeighborSampler delivers them: fp32, shaped like nbr, 0 on padding
+            kw["edata_lazy"] = {"weights": (lambda c=counts[l]: torch.from_numpy(c.astype(np.float32)))}
         if ip is not None:
             kw.update(indptr=torch.from_numpy(np.ascontiguousarray(ip, dtype=np.int64)), indices=torch.from_numpy(loc.astype(np.int32)))
             nbr = None
@@ -284,15 +396,40 @@ def reference_blocks(oracle, case, seeds=None, sampler_seed=SAMPLER_SEED):
     return blocks
 
 
+@functools.lru_cache(None)
+def walk_twin(sampler, step):
+    """The layers of a walk sampler of SAMPLERS_TYPED from its restatement, in sampling order: [(src, nbr_local, counts, nbr), ...]"""
+    g = graph()
+    cls, ks, (T, W, p) = SAMPLERS_TYPED[sampler]
+    return walk_layers(g.indptr, g.indices, g.seeds, list(reversed(ks)), T, W, walk_threshold(p), SAMPLER_SEED, step)
+
+
+def walk_rows(sampler, step):
+    """The restatement's (dst_gid, src_gid, visit count) rows per layer in model order, in slot order, from its global neighbour ids alone."""
+    g = graph()
+    out, dst = [], g.seeds
+    for src, loc, cnt, nbr in walk_twin(sampler, step):
+        keep = nbr >= 0
+        out.insert(0, np.stack([np.broadcast_to(dst[:, None], nbr.shape)[keep], nbr[keep], cnt[keep].astype(np.int64)], 1))
+        dst = src
+    return out
+
+
 def evaluate(case, blocks, model, seeds=None, X=None):
     """Decode and validate the blocks, then the reference of the case -> (R.Evaluation, decoded layers).  seeds, X: another batch and
     another feature table than the graph's own (the loader test)."""
-    g = graph()
+    g = graph_of(case)
     seeds = g.seeds if seeds is None else np.asarray(seeds)
-    cls, fanouts, prob = SAMPLERS[case.sampler]
+    cls, fanouts, prob = sampler_of(case)
     layers = [R.decode(b) for b in blocks]
-    R.check_edges(g.indptr, g.indices, layers, fanouts, seeds, weights=g.w if prob else None, labels=g.labels,
-                  block_labels=R._np(blocks[-1].dstdata["labels"]), labor=cls == "labor")
+    kw, more = {}, {}
+    if cls == "rel":
+        kw = dict(rel_etype=g.etype)
+    elif cls == "walk":   # the blocks' own counts go to the reference as data, once they are the restatement's
+        more = dict(visits=[R.slot_data(b, "weights") for b in blocks])
+        kw = dict(walk=walk_rows(case.sampler, case.step), **more)
+    R.check_edges(g.indptr, g.indices, layers, fanouts, seeds, weights=g.w if prob and cls == "ns" else None, labels=g.labels,
+                  block_labels=R._np(blocks[-1].dstdata["labels"]), labor=cls == "labor", **kw)
     ev = R.Evaluation(case.model, params_of(model), g.X if X is None else X, loss_matrix(case.step)[: len(seeds)], layers,
-                      {"w": g.w, "etype": g.etype}, heads=HEADS, num_rels=NRELS)
+                      {"w": g.w, "etype": g.etype}, heads=HEADS, num_rels=num_rels_of(case), **more)
     return ev, layers

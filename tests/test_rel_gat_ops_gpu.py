@@ -27,7 +27,8 @@ edges of any relation in nc 64-slot chunks (1 for a fixed row); z_j = el + er, x
             summed in at most P = ceil(D / 64) + 8 levels (product, 6-step lane scan, one LDS add per 64-float pass): d dot_j =
             gamma(P) sum |g f|.  G = sum over the group of a_j dot_j is a product, a 6-level tree per chunk and an add per chunk:
             dG <= sum_j a_j d dot_j + (eta_b + u + gamma(6 + nc)) sum_j |a_j dot_j|.  t_j = a_j (dot_j - G) k_j:
-            |dt_j| <= k_j (a_j (d dot_j + dG) + |a_j (dot_j - G)| (eta_b + 3u)).
+            |dt_j| <= k_j (a_j (d dot_j + dG) + |a_j (dot_j - G)| (eta_b + 3u)).  (The kernel subtracts G / S, S = sum of the group's
+            a_j: that removes the part of eta_b common to the group from dG, and is held to the bound as derived without it.)
             grad_feat[p]: sum over its K_p contributions of a_j g, atomics in any order: (eta_b + u + gamma(K_p)) sum a_j |g|.
             grad_el[p]: sum |dt_j| + gamma(K_p) sum |t_j|.  grad_er[d, r]: sum |dt_j| + gamma(6 + nc) sum |t_j|."""
 import numpy as np
