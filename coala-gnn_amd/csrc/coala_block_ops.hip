@@ -149,6 +149,14 @@ __global__ __launch_bounds__(kBlock) void mean_aggregate_backward_kernel(const i
 constexpr int kGatMaxHeads = 16;
 constexpr float kNegInf = -__builtin_inff();
 
+// GAT's and RelGAT's score from z = el + er: the slope product is one rounded product in the forward and in the backward alike, never
+// contracted into the subtraction that follows it (e - m, e - lse), so the backward's e_j is the forward's bit for bit (dot_score below
+// is the same rule for the dot-product score).
+__device__ __forceinline__ float leaky_score(float z, float slope) {
+#pragma clang fp contract(off)
+    return z > 0.0f ? z : z * slope;
+}
+
 // acc[h] += the sum of x over the lanes of head h, for the 64 floats c0 + lane of a [H * dim] row (a head's floats are contiguous):
 // a segmented inclusive scan, then the last lane of each head's segment adds its total.  Every lane must call it.
 __device__ __forceinline__ void head_segment_add(float* acc, float x, int lane, int c0, int dim, int hd) {
@@ -259,10 +267,7 @@ __global__ __launch_bounds__(kBlock) void gat_aggregate_kernel(const int64_t* __
             wave_lds_sync(); // the previous chunk has read w and scl; m_run / l_run are set
             for (int h = 0; h < heads; ++h) { // the score is a scalar per edge and head: straight into the softmax step
                 float e = kNegInf;
-                if (mine >= 0) {
-                    const float z = el[(int64_t)mine * heads + h] + er[d * heads + h];
-                    e = z > 0.0f ? z : z * slope;
-                }
+                if (mine >= 0) e = leaky_score(el[(int64_t)mine * heads + h] + er[d * heads + h], slope);
                 softmax_chunk_step(s, h, e, mine >= 0, lane);
             }
             wave_lds_sync();
@@ -272,7 +277,14 @@ __global__ __launch_bounds__(kBlock) void gat_aggregate_kernel(const int64_t* __
     }
 }
 
-// Backward, a_j = exp(e_j - lse[d, h]) recomputed from the saved log-sum-exp:
+// The backward kernels of the four attention ops recompute a weight as exp(e_j - lse) from the saved fp32 log-sum-exp.  Those sum over a
+// softmax group to S = 1 + O(u |lse|), not to 1: lse is rounded at the scores' common offset.  Every backward therefore divides by the
+// group's own S, summed in a fixed order (a wave_sum per 64-slot chunk, chunk after chunk), so that the weights sum to 1 within a few u
+// whatever the offset, grad_feat / grad_v / grad_src add up over the table to grad_out, and an error of lse itself cancels.  A row of
+// one chunk -- every fixed row -- takes S from the chunk already in registers; a longer row walks its scores once more in front.
+__device__ __forceinline__ float normalised(float a, float sum) { return sum > 0.0f ? a / sum : 0.0f; }
+
+// Backward, a_j = exp(e_j - lse[d, h]) / S recomputed from the saved log-sum-exp, S the row's sum of exp(e_j - lse[d, h]):
 //   grad_feat[s_j, h, :] += a_j g[d, h, :],  t_j = a_j (<g[d, h, :], feat[s_j, h, :]> - <g[d, h, :], out[d, h, :]>) (z_j > 0 ? 1 : slope),
 //   grad_el[s_j, h] += t_j,  grad_er[d, h] = sum_j t_j.
 // A lane per float of the [H * dim] row, 64 at a time; the per-head dot products are summed by head_segment_add into LDS in a fixed
@@ -286,12 +298,13 @@ __global__ __launch_bounds__(kBlock) void gat_aggregate_backward_kernel(const in
                                                                         float* __restrict__ grad_er, int64_t n_dst, int heads, int dim, float slope) {
     __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // a_j of the chunk, [edge][head]
     __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g, feat_j>, [edge][head]
-    __shared__ float hs_lds[kWavesPerBlock][2 * kGatMaxHeads];   // per head: <g, out>, the sum of t_j so far
+    __shared__ float hs_lds[kWavesPerBlock][3 * kGatMaxHeads];   // per head: <g, out>, the sum of t_j so far, S of a row of several chunks
     const auto [lane, wave, n_waves] = wave_rows();
     float* w = w_lds[threadIdx.x >> 6];
     float* dot = dot_lds[threadIdx.x >> 6];
     float* gout = hs_lds[threadIdx.x >> 6];
     float* ter = gout + kGatMaxHeads;
+    float* ssum = ter + kGatMaxHeads;
     const int hd = heads * dim;
     for (int64_t d = wave; d < n_dst; d += n_waves) {
         int64_t beg, end;
@@ -301,20 +314,32 @@ __global__ __launch_bounds__(kBlock) void gat_aggregate_backward_kernel(const in
         if (lane < heads) {
             gout[lane] = 0.0f;
             ter[lane] = 0.0f;
+            ssum[lane] = 0.0f;
         }
         wave_lds_sync();
         head_dots(gout, g, out + d * hd, lane, dim, hd);
+        const bool one = end - beg <= 64; // wave-uniform: the row is one chunk
+        if (!one) {                       // S per head, chunk after chunk (lane 0 alone touches ssum)
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                int32_t mine;
+                load_chunk(idx, e0, end, lane, &mine);
+                for (int h = 0; h < heads; ++h) {
+                    float a = 0.0f;
+                    if (mine >= 0) a = expf(leaky_score(el[(int64_t)mine * heads + h] + er[d * heads + h], slope) - lse[d * heads + h]);
+                    const float sum = wave_sum(a);
+                    if (lane == 0) ssum[h] += sum;
+                }
+            }
+            wave_lds_sync();
+        }
         for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
             int32_t mine;
             const int n = load_chunk(idx, e0, end, lane, &mine);
             wave_lds_sync(); // the previous chunk has read w and dot
             for (int h = 0; h < heads; ++h) {
                 float a = 0.0f;
-                if (mine >= 0) {
-                    const float z = el[(int64_t)mine * heads + h] + er[d * heads + h];
-                    a = expf((z > 0.0f ? z : z * slope) - lse[d * heads + h]);
-                }
-                w[lane * kGatMaxHeads + h] = a;
+                if (mine >= 0) a = expf(leaky_score(el[(int64_t)mine * heads + h] + er[d * heads + h], slope) - lse[d * heads + h]);
+                w[lane * kGatMaxHeads + h] = normalised(a, one ? wave_sum(a) : ssum[h]);
                 dot[lane * kGatMaxHeads + h] = 0.0f;
             }
             wave_lds_sync();
@@ -413,9 +438,9 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_kernel(const int64_t* 
     }
 }
 
-// Backward, all three gradients in one launch, each of them optional (null).  a_j = exp(e_j - lse[d, h]) with e_j recomputed by a second
-// score pass, which also sums dot_j = <g[d, h, :], feat_src[s_j, h, :]>; then per edge and head t_j = a_j (dot_j - <g, out>), and a
-// third walk over the chunk's rows, a lane per float c, with k_jc = z_jc > 0 ? 1 : slope:
+// Backward, all three gradients in one launch, each of them optional (null).  a_j = exp(e_j - lse[d, h]) / S (`normalised` above) with e_j
+// recomputed by a second score pass, which also sums dot_j = <g[d, h, :], feat_src[s_j, h, :]>; then per edge and head
+// t_j = a_j (dot_j - <g, out>), and a third walk over the chunk's rows, a lane per float c, with k_jc = z_jc > 0 ? 1 : slope:
 //   grad_src[s_j, c] += a_j g[d, c] + t_j attn[c] k_jc   hardware float atomics (zeroed by the caller), 256 contiguous bytes per wave
 //                                                        instruction: the only atomics;
 //   grad_dst[d, c]    = sum_j t_j attn[c] k_jc           summed in slot order in a register, stored once per chunk (a later chunk of a
@@ -436,7 +461,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_backward_kernel(const 
                                                                           int64_t n_dst, int heads, int dim, float slope) {
     __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // the chunk's scores e_j, then a_j, [edge][head]
     __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g, feat_src_j>, then t_j, [edge][head]
-    __shared__ float hs_lds[kWavesPerBlock][kGatMaxHeads];       // per head: <g, out>
+    __shared__ float hs_lds[kWavesPerBlock][2 * kGatMaxHeads];   // per head: <g, out>, S of a row of several chunks
     static_assert(RP * 64 <= 64 * kGatMaxHeads, "the waves' grad_attn sums are combined through w_lds");
     const int wv = threadIdx.x >> 6, wpb = blockDim.x >> 6; // one wave a block at RP == 0
     const WaveRows wr = wave_rows(wpb);
@@ -444,6 +469,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_backward_kernel(const 
     float* w = w_lds[wv];
     float* dot = dot_lds[wv];
     float* gout = hs_lds[wv];
+    float* ssum = gout + kGatMaxHeads;
     const int hd = heads * dim;
     float* prow = grad_attn_parts ? grad_attn_parts + (int64_t)blockIdx.x * hd : nullptr;
     float ga_reg[RP > 0 ? RP : 1];
@@ -456,9 +482,26 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_backward_kernel(const 
         const float* g = grad_out + d * hd;
         const float* fd = feat_dst + d * hd;
         wave_lds_sync(); // the previous row has read gout
-        if (lane < heads) gout[lane] = 0.0f;
+        if (lane < heads) gout[lane] = ssum[lane] = 0.0f;
         wave_lds_sync();
         head_dots(gout, g, out + d * hd, lane, dim, hd);
+        const bool one = end - beg <= 64; // wave-uniform: the row is one chunk
+        if (!one) {                       // S per head from a score pass of its own, chunk after chunk (lane 0 alone touches ssum)
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                int32_t mine;
+                const int n = load_chunk(idx, e0, end, lane, &mine);
+                wave_lds_sync(); // the previous chunk has read w
+                for (int h = 0; h < heads; ++h) w[lane * kGatMaxHeads + h] = 0.0f;
+                wave_lds_sync();
+                gatv2_score_pass<false>(w, nullptr, mine, n, feat_src, fd, attn, nullptr, lane, hd, dim, slope);
+                wave_lds_sync();
+                for (int h = 0; h < heads; ++h) {
+                    const float sum = wave_sum(mine >= 0 ? expf(w[lane * kGatMaxHeads + h] - lse[d * heads + h]) : 0.0f);
+                    if (lane == 0) ssum[h] += sum;
+                }
+            }
+            wave_lds_sync();
+        }
         for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
             int32_t mine;
             const int n = load_chunk(idx, e0, end, lane, &mine);
@@ -473,10 +516,9 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_backward_kernel(const 
             wave_lds_sync();
             for (int h = 0; h < heads; ++h) { // lane j reads and rewrites only edge j's words
                 float a = 0.0f, t = 0.0f;
-                if (mine >= 0) {
-                    a = expf(w[lane * kGatMaxHeads + h] - lse[d * heads + h]);
-                    t = a * (dot[lane * kGatMaxHeads + h] - gout[h]);
-                }
+                if (mine >= 0) a = expf(w[lane * kGatMaxHeads + h] - lse[d * heads + h]);
+                a = normalised(a, one ? wave_sum(a) : ssum[h]);
+                if (mine >= 0) t = a * (dot[lane * kGatMaxHeads + h] - gout[h]);
                 w[lane * kGatMaxHeads + h] = a;
                 dot[lane * kGatMaxHeads + h] = t;
             }
@@ -538,7 +580,18 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_backward_kernel(const 
 //   e_j = scale <q[d, h, :], k[row_j, h, :]>,  a_j = softmax of e over the row,  out[d, h, :] = sum_j a_j v[row_j, h, :]
 // gatv2_aggregate_kernel with another score pass: a lane per float of the [H * D] row, 64 floats at a time, q[d] of the pass in
 // registers, the chunk's edges in the inner loop, the per-head sums added into the LDS [edge][head] array by head_segment_add in a
-// fixed order; the scale is applied to the finished sum.  The weighted sum then reads the chunk's v rows.  Nothing of size E is written.
+// fixed order; the scale is applied to the finished sum by dot_score, in both directions.  The weighted sum then reads the chunk's v rows.
+// Nothing of size E is written.
+//
+// A slot's score from its finished dot product: one rounded product, never contracted into the subtraction that follows it (e - m in
+// the forward, e - lse in the backward).  Fused, the backward's fma(scale, qk, -lse) would take the product unrounded while the
+// forward's maximum and lse are made of rounded scores: a_j = exp(e_j - lse) is then off by u |e_j|, edge by edge, the a_j of a row no
+// longer sum to what lse says, and sum_j t_j, zero in exact arithmetic, grows with the scores' common offset.
+__device__ __forceinline__ float dot_score(float scale, float qk) {
+#pragma clang fp contract(off)
+    return scale * qk;
+}
+
 // e[j * kGatMaxHeads + h] += <q[d, h, :], k[row_j, h, :]> for the n slots of a chunk; with DOT also dot[..] += <g[h, :], v[row_j, h, :]>.
 template <bool DOT>
 __device__ __forceinline__ void dot_score_pass(float* e, float* dot, int32_t mine, int n, const float* __restrict__ k,
@@ -581,7 +634,7 @@ __global__ __launch_bounds__(kBlock) void dot_gat_aggregate_kernel(const int64_t
             dot_score_pass<false>(s.w, nullptr, mine, n, k, q + d * hd, nullptr, nullptr, lane, hd, dim);
             wave_lds_sync();
             for (int h = 0; h < heads; ++h) // lane j reads and rewrites only edge j's words
-                softmax_chunk_step(s, h, mine >= 0 ? scale * s.w[lane * kGatMaxHeads + h] : kNegInf, mine >= 0, lane);
+                softmax_chunk_step(s, h, mine >= 0 ? dot_score(scale, s.w[lane * kGatMaxHeads + h]) : kNegInf, mine >= 0, lane);
             wave_lds_sync();
             softmax_accumulate<VEC>(s, out + d * hd, v, mine, n, e0 == beg, e0 + 64 >= end, lane, hd, units, upl);
         }
@@ -590,8 +643,8 @@ __global__ __launch_bounds__(kBlock) void dot_gat_aggregate_kernel(const int64_t
 }
 
 // Backward, all three gradients in one launch, each of them optional (null).  A second score pass gives the dot products again and
-// dot_j = <g[d, h, :], v[row_j, h, :]>; then per edge and head a_j = exp(e_j - lse[d, h]) and t_j = a_j (dot_j - <g, out>), and a third
-// walk over the chunk's rows, a lane per float c:
+// dot_j = <g[d, h, :], v[row_j, h, :]>; then per edge and head a_j = exp(e_j - lse[d, h]) / S (`normalised` above), e_j the forward's bit for bit (dot_score), and
+// t_j = a_j (dot_j - <g, out>), and a third walk over the chunk's rows, a lane per float c:
 //   grad_v[row_j, c] += a_j g[d, c]             hardware float atomics (zeroed by the caller), 256 contiguous bytes per wave instruction;
 //   grad_k[row_j, c] += scale t_j q[d, c]       the same;
 //   grad_q[d, c]      = scale sum_j t_j k[row_j, c]   summed in slot order in a register, scaled and stored once per chunk (a later
@@ -606,11 +659,12 @@ __global__ __launch_bounds__(kBlock) void dot_gat_aggregate_backward_kernel(cons
                                                                             float scale) {
     __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // the chunk's dot products <q, k_j>, then a_j, [edge][head]
     __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g, v_j>, then t_j, [edge][head]
-    __shared__ float hs_lds[kWavesPerBlock][kGatMaxHeads];       // per head: <g, out>
+    __shared__ float hs_lds[kWavesPerBlock][2 * kGatMaxHeads];   // per head: <g, out>, S of a row of several chunks
     const auto [lane, wave, n_waves] = wave_rows();
     float* w = w_lds[threadIdx.x >> 6];
     float* dot = dot_lds[threadIdx.x >> 6];
     float* gout = hs_lds[threadIdx.x >> 6];
+    float* ssum = gout + kGatMaxHeads;
     const int hd = heads * dim;
     for (int64_t d = wave; d < n_dst; d += n_waves) {
         int64_t beg, end;
@@ -618,9 +672,26 @@ __global__ __launch_bounds__(kBlock) void dot_gat_aggregate_backward_kernel(cons
         const float* g = grad_out + d * hd;
         const float* qd = q + d * hd;
         wave_lds_sync(); // the previous row has read gout
-        if (lane < heads) gout[lane] = 0.0f;
+        if (lane < heads) gout[lane] = ssum[lane] = 0.0f;
         wave_lds_sync();
         head_dots(gout, g, out + d * hd, lane, dim, hd);
+        const bool one = end - beg <= 64; // wave-uniform: the row is one chunk
+        if (!one) {                       // S per head from a score pass of its own, chunk after chunk (lane 0 alone touches ssum)
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                int32_t mine;
+                const int n = load_chunk(row, e0, end, lane, &mine);
+                wave_lds_sync(); // the previous chunk has read w
+                for (int h = 0; h < heads; ++h) w[lane * kGatMaxHeads + h] = 0.0f;
+                wave_lds_sync();
+                dot_score_pass<false>(w, nullptr, mine, n, k, qd, nullptr, nullptr, lane, hd, dim);
+                wave_lds_sync();
+                for (int h = 0; h < heads; ++h) {
+                    const float sum = wave_sum(mine >= 0 ? expf(dot_score(scale, w[lane * kGatMaxHeads + h]) - lse[d * heads + h]) : 0.0f);
+                    if (lane == 0) ssum[h] += sum;
+                }
+            }
+            wave_lds_sync();
+        }
         for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
             int32_t mine;
             const int n = load_chunk(row, e0, end, lane, &mine);
@@ -634,10 +705,9 @@ __global__ __launch_bounds__(kBlock) void dot_gat_aggregate_backward_kernel(cons
             wave_lds_sync();
             for (int h = 0; h < heads; ++h) { // lane j reads and rewrites only edge j's words
                 float a = 0.0f, t = 0.0f;
-                if (mine >= 0) {
-                    a = expf(scale * w[lane * kGatMaxHeads + h] - lse[d * heads + h]);
-                    t = a * (dot[lane * kGatMaxHeads + h] - gout[h]);
-                }
+                if (mine >= 0) a = expf(dot_score(scale, w[lane * kGatMaxHeads + h]) - lse[d * heads + h]);
+                a = normalised(a, one ? wave_sum(a) : ssum[h]);
+                if (mine >= 0) t = a * (dot[lane * kGatMaxHeads + h] - gout[h]);
                 w[lane * kGatMaxHeads + h] = a;
                 dot[lane * kGatMaxHeads + h] = t;
             }
@@ -1002,10 +1072,7 @@ __global__ __launch_bounds__(kBlock) void rel_gat_aggregate_kernel(const int64_t
                 todo &= ~__ballot(in);
                 for (int h = 0; h < heads; ++h) { // an online softmax step of group (r, h): lane 0 keeps its max and sum
                     float e = kNegInf;
-                    if (in) {
-                        const float z = el[(int64_t)mine * heads + h] + er_d[r * heads + h];
-                        e = z > 0.0f ? z : z * slope;
-                    }
+                    if (in) e = leaky_score(el[(int64_t)mine * heads + h] + er_d[r * heads + h], slope);
                     const float mo = m_run[r * heads + h];
                     const float mn = fmaxf(mo, wave_max(e));
                     const float sum = wave_sum(in ? expf(e - mn) : 0.0f);
@@ -1031,10 +1098,8 @@ __global__ __launch_bounds__(kBlock) void rel_gat_aggregate_kernel(const int64_t
             wave_lds_sync(); // 1 / l is stored; the previous chunk has read w
             for (int h = 0; h < heads; ++h) {
                 float a = 0.0f;
-                if (t >= 0) {
-                    const float z = el[(int64_t)mine * heads + h] + er_d[t * heads + h];
-                    a = expf((z > 0.0f ? z : z * slope) - m_run[t * heads + h]) * l_run[t * heads + h];
-                }
+                if (t >= 0)
+                    a = expf(leaky_score(el[(int64_t)mine * heads + h] + er_d[t * heads + h], slope) - m_run[t * heads + h]) * l_run[t * heads + h];
                 w[lane * kGatMaxHeads + h] = a;
             }
             wave_lds_sync();
@@ -1054,15 +1119,16 @@ __global__ __launch_bounds__(kBlock) void rel_gat_aggregate_kernel(const int64_t
     }
 }
 
-// One chunk of the backward below: lane j takes slot e0 + j's (row, type), and leaves in LDS, for every head, a_j = exp(e_j - lse) in w
-// and <g[h, :], feat[row_j, h, :]> in dot (gat_aggregate_backward_kernel's walk: a lane per float of the [H * dim] row, the per-head
+// One chunk of the backward below: lane j takes slot e0 + j's (row, type), and leaves in LDS, for every head, a_j = exp(e_j - lse) in w,
+// divided by its group's S[type_j, h] where S is given, and <g[h, :], feat[row_j, h, :]> in dot (gat_aggregate_backward_kernel's walk: a lane per float of the [H * dim] row, the per-head
 // sums by head_segment_add in a fixed order); with ADD also grad_feat[row_j, h, :] += a_j g[h, :].  -> the chunk's length.
 template <bool ADD>
 __device__ __forceinline__ int rel_gat_chunk_dots(float* w, float* dot, const int32_t* __restrict__ row, const int32_t* __restrict__ etype,
                                                   int64_t e0, int64_t end, int lane, int num_rels, int heads, int dim,
                                                   const float* __restrict__ el, const float* __restrict__ er_d,
-                                                  const float* __restrict__ lse_d, const float* __restrict__ feat, const float* __restrict__ g,
-                                                  float* __restrict__ grad_feat, float slope, int32_t* mine_out, int32_t* t_out) {
+                                                  const float* __restrict__ lse_d, const float* S, const float* __restrict__ feat,
+                                                  const float* __restrict__ g, float* __restrict__ grad_feat, float slope, int32_t* mine_out,
+                                                  int32_t* t_out) {
     const int hd = heads * dim;
     int32_t mine, t;
     const int n = load_rel_chunk(row, etype, e0, end, lane, num_rels, &mine, &t);
@@ -1070,8 +1136,8 @@ __device__ __forceinline__ int rel_gat_chunk_dots(float* w, float* dot, const in
     for (int h = 0; h < heads; ++h) {
         float a = 0.0f;
         if (t >= 0) {
-            const float z = el[(int64_t)mine * heads + h] + er_d[t * heads + h];
-            a = expf((z > 0.0f ? z : z * slope) - lse_d[t * heads + h]);
+            a = expf(leaky_score(el[(int64_t)mine * heads + h] + er_d[t * heads + h], slope) - lse_d[t * heads + h]);
+            if (S) a = normalised(a, S[t * heads + h]);
         }
         w[lane * kGatMaxHeads + h] = a;
         dot[lane * kGatMaxHeads + h] = 0.0f;
@@ -1097,17 +1163,17 @@ __device__ __forceinline__ int rel_gat_chunk_dots(float* w, float* dot, const in
     return n;
 }
 
-// Backward, a_j = exp(e_j - lse[d, etype_j, h]) recomputed from the saved log-sum-exp; with dot_j = <g[d, h, :], feat[row_j, h, :]> and
-// G[r, h] = sum over the edges j of relation r of a_j dot_j -- relation r's <g, out_r>, which the stored out, summed over relations,
-// cannot give -- and S[r, h] = sum of a_j over the same edges:
+// Backward, p_j = exp(e_j - lse[d, etype_j, h]) recomputed from the saved log-sum-exp; with dot_j = <g[d, h, :], feat[row_j, h, :]>,
+// G[r, h] = sum over the edges j of relation r of p_j dot_j -- relation r's <g, out_r>, which the stored out, summed over relations,
+// cannot give -- S[r, h] = sum of p_j over the same edges, and a_j = p_j / S[etype_j, h] (`normalised` above):
 //   grad_feat[row_j, h, :] += a_j g[d, h, :],  t_j = a_j (dot_j - G[etype_j, h] / S[etype_j, h]) (z_j > 0 ? 1 : slope),
 //   grad_el[row_j, h] += t_j,  grad_er[d, r, h] = sum of t_j over relation r's edges.
-// S is 1 but for the rounding of lse and of expf.  Without the division the sum of a group's a_j (dot_j - G), zero in exact
+// S is 1 but for the rounding of lse and of expf.  Without the division of G the sum of a group's p_j (dot_j - G), zero in exact
 // arithmetic, is (1 - S) G, an error of one sign per group that whatever sums the t_j over edges afterwards (the gradients of attn_l
-// and attn_r) does not cancel.
-// A first walk over the row's chunks gives a, dot and grad_feat, and adds every group's G and S in LDS (two masked wave_sums per
-// relation present and head, in chunk order).  A row of one chunk -- every fixed row -- then forms t from the a and dot still in LDS; a longer
-// row walks its source rows a second time.  grad_feat and grad_el take hardware float atomics (zeroed by the caller); grad_er is summed
+// and attn_r) does not cancel; without that of p_j a group's grad_feat adds up to S g.
+// A first walk over the row's chunks gives p and dot and adds every group's G and S in LDS (two masked wave_sums per relation present
+// and head, in chunk order).  A row of one chunk -- every fixed row -- then divides the p still in LDS, adds grad_feat from them and forms
+// t; a longer row walks its source rows a second time, now with S, for grad_feat and t.  grad_feat and grad_el take hardware float atomics (zeroed by the caller); grad_er is summed
 // in LDS in a fixed order and written whole.
 template <bool CSR>
 __global__ __launch_bounds__(kBlock) void rel_gat_aggregate_backward_kernel(
@@ -1159,7 +1225,8 @@ __global__ __launch_bounds__(kBlock) void rel_gat_aggregate_backward_kernel(
         };
         int32_t mine = -1, t = -1;
         for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
-            rel_gat_chunk_dots<true>(w, dot, row, etype, e0, end, lane, num_rels, heads, dim, el, er_d, lse_d, feat, g, grad_feat, slope, &mine, &t);
+            rel_gat_chunk_dots<false>(w, dot, row, etype, e0, end, lane, num_rels, heads, dim, el, er_d, lse_d, nullptr, feat, g, nullptr, slope, &mine,
+                                      &t);
             uint64_t todo = __ballot(t >= 0);
             while (todo) {
                 const int r = __shfl(t, __builtin_ctzll(todo));
@@ -1179,11 +1246,25 @@ __global__ __launch_bounds__(kBlock) void rel_gat_aggregate_backward_kernel(
         wave_lds_sync(); // G and S are whole
         for (int i = lane; i < rh; i += 64) G[i] = S[i] > 0.0f ? G[i] / S[i] : 0.0f; // a group without an edge is never read
         wave_lds_sync();
-        if (end - beg <= 64) { // wave-uniform: the one chunk's a and dot are still in LDS
+        if (end - beg <= 64) { // wave-uniform: the one chunk's p and dot are still in LDS; lane j divides its own words
+            const int n = (int)(end - beg);
+            if (t >= 0)
+                for (int h = 0; h < heads; ++h) w[lane * kGatMaxHeads + h] = normalised(w[lane * kGatMaxHeads + h], S[t * heads + h]);
+            wave_lds_sync();
+            for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: the shuffles below need every lane
+                const int c = c0 + lane;
+                const int hc = c < hd ? c / dim : 0;
+                const float gc = c < hd ? g[c] : 0.0f;
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && c < hd) unsafeAtomicAdd(grad_feat + (int64_t)s * hd + c, w[j * kGatMaxHeads + hc] * gc);
+                }
+            }
             t_step(mine, t);
         } else {
             for (int64_t e0 = beg; e0 < end; e0 += 64) {
-                rel_gat_chunk_dots<false>(w, dot, row, etype, e0, end, lane, num_rels, heads, dim, el, er_d, lse_d, feat, g, nullptr, slope, &mine, &t);
+                rel_gat_chunk_dots<true>(w, dot, row, etype, e0, end, lane, num_rels, heads, dim, el, er_d, lse_d, S, feat, g, grad_feat, slope, &mine,
+                                         &t);
                 t_step(mine, t);
             }
         }

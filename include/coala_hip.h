@@ -566,7 +566,11 @@ int coala_block_rel_sum_csr_backward(int device, const int64_t* indptr, const in
  * el fp32 [n_src, heads], er fp32 [n_dst, heads], feat fp32 [n_src, heads, dim], out fp32 [n_dst, heads, dim], all contiguous;
  * heads 1..16, dim >= 1, heads * dim < 2^31.  A row without a valid edge gives exactly 0.
  * Saved state: lse fp32 [n_dst, heads] = m + log(sum_k exp(e_k - m)), the log-sum-exp of the row's scores (-inf for a row without a
- * valid edge); the backward recomputes a_j = exp(e_j - lse) from it.
+ * valid edge); the backward recomputes p_j = exp(e_j - lse) from it and takes a_j = p_j / S, S = sum_k p_k of the row, summed in a fixed
+ * order.  The p_j sum to 1 + O(u |lse|), lse being one fp32 word; divided by their own sum the a_j sum to 1 within a few u whatever
+ * offset the row's scores share, so grad_feat adds up over the sources to grad_out and sum_j t_j stays at rounding level.  The same
+ * holds for the GATv2, dot-product and relation-typed entries below (there per relation).  The leaky_relu product of a score is one
+ * rounded product in both directions, so the backward's e_j is the forward's bit for bit.
  * Fixed form: nbr int32 [n_dst, fanout], -1 padded, fan-out 1..32.  CSR form: the edges of row d are indices[indptr[d] .. indptr[d+1])
  * (indptr int64 [n_dst + 1], indices int32), any degree: one wave takes a row 64 edges at a time with an online max and rescale.  The
  * forward is deterministic; a fixed row whose valid entries come first, in CSC order, gives the bits of the same CSR row (out, lse and
@@ -602,9 +606,9 @@ int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, co
  * refused with COALA_EINVAL ("bad block shape", "null buffer") and nothing is launched; n_dst == 0 launches nothing and reads no pointer.
  * out and lse are deterministic, and both forms run the same code: bit-identical on a row both can express (a fixed row whose valid
  * entries come first).
- * Backward, with g = grad_out [n_dst, heads, dim], a_j = exp(e_j - lse[d, etype_j, h]), dot_j = <g[d, h, :], feat[row_j, h, :]> and
- * G[r, h] = sum of a_j dot_j, S[r, h] = sum of a_j over relation r's slots (S is 1 up to rounding; dividing by it makes a group's
- * a_j (dot_j - G / S) sum to zero as the exact ones do):
+ * Backward, with g = grad_out [n_dst, heads, dim], p_j = exp(e_j - lse[d, etype_j, h]), dot_j = <g[d, h, :], feat[row_j, h, :]>,
+ * G[r, h] = sum of p_j dot_j, S[r, h] = sum of p_j over relation r's slots and a_j = p_j / S[etype_j, h] (S is 1 up to the rounding of
+ * lse; dividing by it makes a group's a_j sum to 1 and its a_j (dot_j - G / S) sum to zero as the exact ones do):
  *   t_j = a_j (dot_j - G[etype_j, h] / S[etype_j, h]) (z_j > 0 ? 1 : negative_slope);
  *   grad_feat[row_j, h, :] += a_j g[d, h, :];  grad_el[row_j, h] += t_j;  grad_er[d, r, h] = sum of t_j over relation r's slots.
  * grad_feat [P, heads, dim] and grad_el [P, heads] are accumulated with hardware float atomics: the caller zeroes them, and the order
@@ -639,7 +643,8 @@ int coala_block_rel_gat_aggregate_csr_backward(int device, const int64_t* indptr
  * memory first, then the chunk's source rows are read a second time (from the cache) for the weighted sum: no buffer of a size
  * proportional to the number of edges exists.  The forward is deterministic, and a fixed row whose valid entries come first, in CSC
  * order, gives the bits of the same CSR row (out, lse and the backward's grad_dst).
- * Backward, with g = grad_out [n_dst, heads, dim], out / lse from the forward, a_j = exp(e_j - lse) from recomputed scores,
+ * Backward, with g = grad_out [n_dst, heads, dim], out / lse from the forward, a_j = exp(e_j - lse) / S from recomputed scores (S the
+ * row's sum of exp(e_j - lse), as in the GAT entry; a row of more than 64 edges walks its scores once more for it),
  * t_j = a_j (<g[d, h, :], feat_src[s_j, h, :]> - <g[d, h, :], out[d, h, :]>) and k_jc = z_jc > 0 ? 1 : negative_slope:
  *   grad_src[s_j, h, c] += a_j g[d, h, c] + t_j attn[h, c] k_jc   hardware float atomics: the caller zeroes grad_src [n_src, heads, dim],
  *                                                                the order of the additions varies;
@@ -681,8 +686,11 @@ int coala_block_gatv2_aggregate_csr_backward(int device, const int64_t* indptr, 
  * without an edge gives out exactly 0 and lse -inf.  16-byte accesses when dim % 4 == 0 and v and out are 16-byte aligned, scalar ones
  * otherwise.  One wave takes a row 64 slots at a time, GAT's online max and rescale; per chunk the dot products are summed into on-chip
  * memory first, then the chunk's v rows are read for the weighted sum: no buffer of a size proportional to the number of edges exists.
- * Backward, with g = grad_out [n_dst, heads, dim], out / lse from the forward, a_j = exp(e_j - lse) from recomputed scores and
- * t_j = a_j (<g[d, h, :], v[row_j, h, :]> - <g[d, h, :], out[d, h, :]>):
+ * Backward, with g = grad_out [n_dst, heads, dim], out / lse from the forward, a_j = exp(e_j - lse) / S from recomputed scores (S the
+ * row's sum of exp(e_j - lse), as in the GAT entry; a row of more than 64 slots walks its scores once more for it) and
+ * t_j = a_j (<g[d, h, :], v[row_j, h, :]> - <g[d, h, :], out[d, h, :]>).  The recomputed e_j is the forward's bit for bit: scale times the
+ * finished dot product is one rounded product in both directions, never fused into the subtraction after it, so the a_j of a row sum to
+ * what lse says and sum_j t_j stays at rounding level whatever offset the row's scores share:
  *   grad_v[row_j, h, :] += a_j g[d, h, :]              hardware float atomics: the caller zeroes grad_v [P, heads, dim], the order varies;
  *   grad_k[row_j, h, :] += scale t_j q[d, h, :]        the same, grad_k [P, heads, dim];
  *   grad_q[d, h, :]      = scale sum_j t_j k[row_j, h, :]   [n_dst, heads, dim], written whole, summed in slot order: no atomics.

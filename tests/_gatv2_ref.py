@@ -23,6 +23,8 @@ absolute error of at most 6u |log l| for log.  Per row d and head h with k valid
             |out - ref| <= (expm1(2 eta) + gamma(k + nc) + gamma(6 + 2 nc) + 2u) sum_j a_j |feat_src_j|: the numerator sums k products
             and is rescaled at most nc - 1 times; the denominator is a 6-level tree per chunk plus nc sequential adds and nc - 1 rescales;
             then 1 / l and the product.  A row without a valid edge is exactly 0.
+  lse       m~ + log l~, the output the backward reads: eta + gamma(6 + 2 nc) + u (|m| + 8 log k + 1), the form of tests/_dot_gat_ref.py
+            (the weights, l's sum, 6u log k from log, u (|m| + log k) from the addition and one more u).  -inf on a row without a valid edge.
   backward  a_j = exp(e~_j - lse~) with the scores computed again (de_j once more).  lse~ = m~ + log l~ carries eta + gamma(6 + 2 nc)
             from l~, 6u log k from log, u (|m| + log k) from the addition; the subtraction e~_j - lse~ adds u (max|x| + log k) and exp 6u:
             a~_j / a_j within exp(+-eta_b), eta_b = eta + max_j de_j + gamma(6 + 2 nc) + u (|m| + 8 log k + max|x| + 6); r = expm1(eta_b).
@@ -143,9 +145,12 @@ def reference(rows, srcs, n_dst, n_src, nc, fs, fd, attn, g, parts, slope=SLOPE,
     emax = zero.scatter_reduce(0, rh, de, "amax")
     eta = emax + U * (2 * maxx + 6 * ncr)
     b_out = 1.01 * ((torch.expm1(2 * eta) + g_(k + ncr) + g_(6 + 2 * ncr) + 2 * U).unsqueeze(-1) * absout + TINY * absf)
-    # backward
     mm = torch.where(torch.isfinite(m), m, zero)
-    eta_b = eta + emax + g_(6 + 2 * ncr) + U * (mm.abs() + 8 * torch.log(k.clamp_min(1)) + maxx + 6)
+    logk = torch.log(k.clamp_min(1))
+    lse = torch.where(k > 0, mm + torch.log(l.clamp_min(1e-300)), torch.full_like(l, float("-inf")))
+    b_lse = 1.01 * (eta + g_(6 + 2 * ncr) + U * (mm.abs() + 8 * logk + 1)) + TINY
+    # backward
+    eta_b = eta + emax + g_(6 + 2 * ncr) + U * (mm.abs() + 8 * logk + maxx + 6)
     rb = torch.expm1(eta_b)[r]                                      # [E, H]
     gE = G[r]
     dot = (gE * fE).sum(-1)
@@ -168,7 +173,7 @@ def reference(rows, srcs, n_dst, n_src, nc, fs, fd, attn, g, parts, slope=SLOPE,
     chain = np.bincount(np.arange(n_dst) % waves, weights=kcnt.numpy() + np.asarray(nc, dtype=np.float64), minlength=1).max() if n_dst else 0.0
     b_ga = 1.01 * ((dt.unsqueeze(-1) * lz.abs()).sum(0) + (3 * U + float(gamma(chain + 3 + parts))) * (t.abs().unsqueeze(-1) * lz.abs()).sum(0)) + TINY
     return dict(out=(out.numpy(), b_out.numpy()), gs=(gs.numpy(), b_gs.numpy()), gd=(gd.numpy(), b_gd.numpy()), ga=(ga.numpy(), b_ga.numpy()),
-                empty=(kcnt == 0).numpy())
+                lse=(lse.numpy(), b_lse.numpy()), empty=(kcnt == 0).numpy())
 
 
 def outside(got, ref_bound):
@@ -192,6 +197,10 @@ def check(name, got, ref_bound, log=None):
 def check_all(got, ref, log=None):
     for k in ("out", "gs", "gd", "ga"):
         check(k, got[k], ref[k], log)
+    if "lse" in got:                                                # the kernels' output; the torch fallback keeps none
+        full = ~ref["empty"]
+        check("lse", got["lse"][full], (ref["lse"][0][full], ref["lse"][1][full]), log)
+        assert np.all(np.isneginf(got["lse"][ref["empty"]])), "lse of a row without a valid edge is not -inf"
     assert np.all(got["out"][ref["empty"]] == 0.0), "a row without a valid edge is not exactly 0"
     assert np.all(got["gd"][ref["empty"]] == 0.0), "grad_dst of a row without a valid edge is not exactly 0"
     assert all(np.isfinite(got[k]).all() for k in ("out", "gs", "gd", "ga"))

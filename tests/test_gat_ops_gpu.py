@@ -23,7 +23,10 @@ nc 64-edge chunks (1 for a fixed row), z_j = el + er, x_j = e_j - max e:
             64-float pass): gamma(P) sum |g f|.  <g, out> also carries out's forward bound.  t_j = a_j (dot_j - <g, out>) k_j:
             |dt_j| <= k_j (a_j (d dot_j + d <g, out>) + |a_j (dot_j - <g, out>)| (eta_b + 3u)).
             grad_feat[s]: sum over its K_s contributions of a_j g, atomics in any order: (eta_b + u + gamma(K_s)) sum a_j |g|.
-            grad_el[s]: sum |dt_j| + gamma(K_s) sum |t_j|.  grad_er[d]: sum |dt_j| + gamma(6 + nc) sum |t_j|."""
+            grad_el[s]: sum |dt_j| + gamma(K_s) sum |t_j|.  grad_er[d]: sum |dt_j| + gamma(6 + nc) sum |t_j|.
+  lse       m + log l, the output the backward reads: eta from the weights, gamma(6 + 2 nc) from l's sum, 6u log k from log, u (|m| + log k)
+            from the addition and one more u: eta + gamma(6 + 2 nc) + u (|m| + 8 log k + 1), the form of tests/_dot_gat_ref.py.  -inf on a
+            row without a valid edge."""
 import numpy as np
 import pytest
 
@@ -86,8 +89,11 @@ def reference(rows, srcs, n_dst, n_src, nc, el, er, feat, g, slope=SLOPE):
     g_ = lambda n: torch.from_numpy(_gamma(n.numpy()))    # noqa: E731
     eta = U * (2 * maxz + 2 * maxx + 6 * ncr)
     b_out = 1.01 * ((2 * eta + g_(k + ncr) + g_(6 + 2 * ncr) + 2 * U).unsqueeze(-1) * absout + 2.0 ** -100 * absf)
-    # backward
     mm = torch.where(torch.isfinite(m), m, zero)
+    logk = torch.log(k.clamp_min(1))
+    lse = torch.where(k > 0, mm + torch.log(l.clamp_min(1e-300)), torch.full_like(l, float("-inf")))
+    b_lse = 1.01 * (eta + g_(6 + 2 * ncr) + U * (mm.abs() + 8 * logk + 1)) + 2.0 ** -100
+    # backward
     eta_b = eta + g_(6 + 2 * ncr) + U * (4 * maxz + mm.abs() + 8 * torch.log(k.clamp_min(1)) + maxx + 6)
     P = -(-D // 64) + 8
     gE = g64[r]
@@ -107,13 +113,15 @@ def reference(rows, srcs, n_dst, n_src, nc, el, er, feat, g, slope=SLOPE):
     ger = zero.clone().index_add_(0, r, t)
     b_er = 1.01 * zero.clone().index_add_(0, r, dt + g_(6 + ncr)[r] * t.abs()) + 2.0 ** -100
     return dict(out=(out.numpy(), b_out.numpy()), gf=(gf.numpy(), b_gf.numpy()), gel=(gel.numpy(), b_el.numpy()),
-                ger=(ger.numpy(), b_er.numpy()), empty=(k.squeeze(1) == 0).numpy())
+                ger=(ger.numpy(), b_er.numpy()), lse=(lse.numpy(), b_lse.numpy()), empty=(k.squeeze(1) == 0).numpy())
 
 
 def _check(name, got, ref_bound):
     ref, bound = ref_bound
     err = np.abs(got.astype(np.float64) - ref)
     bad = ~(err <= bound)
+    if err.size:
+        print(f"{name}: largest error / bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
     if bad.any():
         i = tuple(np.argwhere(bad)[0])
         raise AssertionError(f"{name}: {int(bad.sum())} elements past the bound; at {i}: got {got[i]!r} want {ref[i]!r} bound {bound[i]!r}")
@@ -189,6 +197,10 @@ def _edges_csr(indptr, indices):
 def _check_all(got, ref):
     for k in ("out", "gf", "gel", "ger"):
         _check(k, got[k], ref[k])
+    if "lse" in got:                                                # the direct calls' output; autograd hands none out
+        full = ~ref["empty"]
+        _check("lse", got["lse"][full], (ref["lse"][0][full], ref["lse"][1][full]))
+        assert np.all(np.isneginf(got["lse"][ref["empty"]])), "lse of a row without a valid edge is not -inf"
     assert np.all(got["out"][ref["empty"]] == 0.0), "a row without a valid edge is not exactly 0"
     assert np.isfinite(got["out"]).all() and np.isfinite(got["gf"]).all() and np.isfinite(got["gel"]).all() and np.isfinite(got["ger"]).all()
 
