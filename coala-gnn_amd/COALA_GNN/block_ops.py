@@ -1,7 +1,8 @@
 """Autograd wrappers of the native block ops that `Block` (sampler.py) hands to a model: mean aggregation (SAGEConv's "mean"), weighted
 sum aggregation (DGL's u_mul_e_sum, the edge_weight= path of GraphConv / SAGEConv), max aggregation (DGL's fn.max: SAGEConv's "pool",
 GINConv's "max"), the relation-typed sum (RelGraphConv's message step), GAT / GATv2 attention aggregation, scaled dot-product
-attention (DotGatConv's and HGTConv's message step) and relation-typed GAT attention (RelGATConv's message step), on fixed blocks and on the ragged CSR blocks of full layers.  One kernel forward, one backward each; the kernels are in coala-gnn_amd/csrc/coala_block_ops.hip
+attention (DotGatConv's and HGTConv's message step) and relation-typed GAT attention (RelGATConv's message step), on fixed blocks and on the ragged CSR blocks of full layers.  pair_dot (DGL's u_dot_v on a pair graph: a link predictor's scores) is the one op here
+that takes no block.  One kernel forward, one backward each; the kernels are in coala-gnn_amd/csrc/coala_block_ops.hip
 (C ABI: coala_block_*).  Every op has one forward and one backward body for both block forms, which take the C entry and the block's
 index tensors -- (nbr,) or (indptr, indices); the two Function classes of an op are shells that name the entries, and they stay two
 because Block's callers and the tests tell by the class which form ran."""
@@ -454,3 +455,77 @@ class _DotGatAggregateCSR(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         return _dot_gat_backward(ctx, grad_out, _lib.coala_block_dot_gat_aggregate_csr_backward) + (None,) * 4
+
+
+class _PairDot(torch.autograd.Function):
+    """out[p, hd] = <h[src_p, hd, :], h[dst_p, hd, :]> (coala_block_pair_dot): one kernel forward, one backward that adds both
+    endpoints' gradients with float atomics into a zeroed grad_h.  h is [N, H, D] contiguous fp32, src / dst contiguous int32 [P]."""
+
+    @staticmethod
+    def forward(ctx, h, src, dst):
+        P, (_, H, D) = src.numel(), h.shape
+        out = torch.empty((P, H), dtype=torch.float32, device=h.device)
+        _capi.check(_lib.coala_block_pair_dot(h.device.index or 0, h.data_ptr(), src.data_ptr(), dst.data_ptr(), out.data_ptr(), P, H, D,
+                                              current_stream()))
+        ctx.save_for_backward(h, src, dst)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        h, src, dst = ctx.saved_tensors
+        g = grad_out.contiguous()
+        grad_h = torch.zeros_like(h)
+        _capi.check(_lib.coala_block_pair_dot_backward(h.device.index or 0, h.data_ptr(), src.data_ptr(), dst.data_ptr(), g.data_ptr(),
+                                                       grad_h.data_ptr(), src.numel(), h.shape[1], h.shape[2], current_stream()))
+        return grad_h, None, None
+
+
+def _pair_args(h, src, dst):
+    """The checks of pair_dot / pair_dot_torch."""
+    if h.dim() not in (2, 3):
+        raise ValueError(f"h of shape {tuple(h.shape)}: pair_dot takes [N, D] or [N, H, D]")
+    for name, t in (("src", src), ("dst", dst)):
+        if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError(f"{name} must be an integer tensor")
+    if src.dim() != 1 or tuple(src.shape) != tuple(dst.shape):
+        raise ValueError(f"src {tuple(src.shape)}, dst {tuple(dst.shape)}: one index each per pair, [P]")
+
+
+def _pair_bound(h, src, dst):
+    """IndexError when a pair index is >= N (one host read)."""
+    if src.numel():
+        top = int(torch.maximum(src.max(), dst.max()))
+        if top >= h.shape[0]:
+            raise IndexError(f"a pair index is {top}: h has {h.shape[0]} rows")
+
+
+def pair_dot(h, src, dst, validate=True):
+    """Scores of node pairs, DGL's fn.u_dot_v on a pair graph: h [N, D] -> [P], or h [N, H, D] -> [P, H], out[p] = <h[src_p], h[dst_p]>
+    (per head).  src, dst: integer tensors [P].  A pair with an index < 0 scores 0 and gets no gradient; an index >= N raises IndexError
+    (on the native path that check is one host read per call, which validate=False skips for a caller whose indices address h by
+    construction, as an EdgeBatch's do).  Native kernels (one forward; one backward, float atomics) for fp32 h on the GPU with D >= 1
+    and index tensors on the GPU; pair_dot_torch otherwise."""
+    _pair_args(h, src, dst)
+    native = (h.is_cuda and h.dtype == torch.float32 and src.is_cuda and dst.is_cuda and h.shape[-1] > 0 and h.numel() // max(h.shape[0], 1) < (1 << 31)
+              and h.shape[0] < (1 << 31) and (h.dim() == 2 or h.shape[1] > 0))
+    if not native:
+        return pair_dot_torch(h, src, dst)
+    if validate:
+        _pair_bound(h, src, dst)
+    s32, d32 = (t if t.dtype == torch.int32 else t.clamp(-1, (1 << 31) - 1).to(torch.int32) for t in (src, dst))
+    h3 = h.contiguous().view(h.shape[0], 1 if h.dim() == 2 else h.shape[1], h.shape[-1])
+    out = _PairDot.apply(h3, s32.contiguous(), d32.contiguous())
+    return out.view(-1) if h.dim() == 2 else out
+
+
+def pair_dot_torch(h, src, dst):
+    """pair_dot in plain torch, any device and dtype, the same index rules: two [P, ...] gathers, a product and a sum.  The fallback of
+    pair_dot, and its reference."""
+    _pair_args(h, src, dst)
+    s, d = src.to(device=h.device, dtype=torch.int64), dst.to(device=h.device, dtype=torch.int64)
+    _pair_bound(h, s, d)
+    keep = (s >= 0) & (d >= 0)
+    prod = (h[s.clamp_min(0)] * h[d.clamp_min(0)]).sum(-1)
+    return prod * keep.view((-1,) + (1,) * (prod.dim() - 1)).to(prod.dtype)

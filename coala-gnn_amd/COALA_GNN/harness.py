@@ -15,9 +15,9 @@ import time
 
 import torch
 
-from .nn import DotGatConv, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv, WeightedSAGEConv
+from .nn import DotGatConv, DotPredictor, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv, WeightedSAGEConv
 
-__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "PinSAGE", "train_steps", "FlatGradAllReduce"]
+__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "PinSAGE", "LinkPredictor", "link_loss", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -294,6 +294,30 @@ class PinSAGE(torch.nn.Module):
                 raise ValueError(f"PinSAGE needs block.edata[{self.weight_key!r}]: sample the blocks with RandomWalkNeighborSampler")
             h = layer(block, (h, block.dst_rows(h)), block.edata[self.weight_key])
         return self.linear(h)
+
+
+class LinkPredictor(torch.nn.Module):
+    """Link prediction on any encoder of this module: the encoder's output rows (one per destination node of blocks[-1], the seed nodes
+    of an EdgeBatch) are the node embeddings, and a pair's score is their dot product (DotPredictor), as in DGL's GraphSAGE
+    link-prediction example.  forward(blocks, x, batch) -> (pos_score [n], neg_score [n * k]); an encoder that returns [N, H, D] gives
+    [n, H] and [n * k, H]."""
+
+    def __init__(self, encoder):
+        super().__init__()
+        self.encoder = encoder
+        self.predictor = DotPredictor(validate=False)   # an EdgeBatch's pairs address the seed nodes by construction
+
+    def forward(self, blocks, x, batch):
+        h = self.encoder(blocks, x)
+        return self.predictor(h, batch.pos_src, batch.pos_dst), self.predictor(h, batch.neg_src, batch.neg_dst)
+
+
+def link_loss(pos_score, neg_score):
+    """Binary cross-entropy with logits over the positive pairs (label 1) and the negative pairs (label 0), the mean over all of them:
+    the loss of DGL's GraphSAGE link-prediction example."""
+    score = torch.cat([pos_score.reshape(-1), neg_score.reshape(-1)])
+    label = torch.cat([torch.ones_like(pos_score.reshape(-1)), torch.zeros_like(neg_score.reshape(-1))])
+    return torch.nn.functional.binary_cross_entropy_with_logits(score, label)
 
 
 class FlatGradAllReduce(object):

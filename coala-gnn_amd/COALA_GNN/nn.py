@@ -19,7 +19,7 @@ WeightedSAGEConv is the layer of DGL's PinSAGE example on blocks sampled by rand
 in block.edata['weights'] weigh the neighbours' rows through Block.weighted_sum_aggregate."""
 import torch
 
-__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv"]
+__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv", "DotPredictor"]
 
 
 class GATConv(torch.nn.Module):
@@ -720,3 +720,17 @@ class HGTConv(torch.nn.Module):
         res = h_dst if self.residual_w is None else h_dst @ self.residual_w
         out = y * alpha + res * (1 - alpha)
         return out if self.norm is None else self.norm(out)
+
+
+class DotPredictor(torch.nn.Module):
+    """The score of a node pair is the dot product of the two embeddings: DGL's link-prediction predictor (apply_edges(fn.u_dot_v) on a
+    pair graph), on block_ops.pair_dot.  h [N, D] -> [P], h [N, H, D] -> [P, H]; a pair with an index < 0 scores 0.  validate=False
+    skips pair_dot's host read of the largest index, for pairs that address h by construction (an EdgeBatch's)."""
+
+    def __init__(self, validate=True):
+        super().__init__()
+        self.validate = bool(validate)
+
+    def forward(self, h, src, dst):
+        from .block_ops import pair_dot
+        return pair_dot(h, src, dst, validate=self.validate)

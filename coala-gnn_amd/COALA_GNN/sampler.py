@@ -15,7 +15,8 @@ from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _GatAggregate, _G
                         _MeanAggregateCSR, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _WeightedSum, _WeightedSumCSR)
 
 __all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "RandomWalkNeighborSampler", "random_walk", "sort_csc_by_etype",
-           "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT", "EID"]
+           "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT", "EID", "EdgePredictionSampler", "as_edge_prediction_sampler",
+           "UniformNegativeSampler", "EdgeBatch", "edge_batch", "edge_batch_wait", "reverse_edge_ids", "MAX_NEGATIVES"]
 
 _lib = _capi.load()
 
@@ -644,6 +645,86 @@ class Block(object):
         out = torch.zeros((self.num_dst,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev)
         return out.index_add(0, dst, a.unsqueeze(-1).to(v.dtype) * v[row])
 
+    def _exclude_args(self, eids):
+        """The checks of exclude_edges / exclude_edges_torch -> the block's edge ids."""
+        if not isinstance(self.edata, _EdgeData) or not dict.__contains__(self.edata, EID):
+            raise ValueError("exclude_edges needs a block that carries edge ids (edata['_ID']): sample with edge_ids=True")
+        made = [k for k in dict.keys(self.edata) if k != EID]
+        if made:
+            raise RuntimeError(f"exclude_edges: edata already holds {made}, made for the edges before the exclusion; exclude first")
+        if not isinstance(eids, torch.Tensor) or eids.dtype != torch.int64 or eids.dim() != 1:
+            raise ValueError("exclude_edges takes a sorted int64 tensor of edge ids, [n]")
+        return self.edata[EID]
+
+    def _excluded(self, nbr, indptr, indices, eid):
+        """The block with its slots replaced: src_nodes, dst_in_src, owner_counts, srcdata and dstdata are this block's own (a source
+        node that only an excluded edge reached stays in the list, unreferenced); edata is derived anew -- '_ID', graph edata through
+        it, and LABOR's 'edge_weights' as 1 / surviving in-degree."""
+        lazy = None
+        if "edge_weights" in self.edata._lazy and indptr is not None:
+            def edge_weights():
+                deg = indptr[1:] - indptr[:-1]
+                return torch.repeat_interleave(1.0 / deg.to(torch.float32), deg, output_size=int(indices.numel()))
+            lazy = {"edge_weights": edge_weights}
+        # The exclusion ran on the current stream and read this block's slot arrays, which the loader's sampler allocated on another: tell
+        # the allocator, or it may hand them out again there while the kernels still read them (a no-op on the stream they came from).
+        for t in (self.nbr, self.indptr, self.indices, self.edata[EID]):
+            if t is not None and t.is_cuda:
+                t.record_stream(torch.cuda.current_stream(t.device))
+        b = Block(self.src_nodes, nbr, self.num_dst, dst_in_src=self.dst_in_src, owner_counts=self.owner_counts,
+                  owner_counts_host=self.owner_counts_host, indptr=indptr, indices=indices, eid=eid, edata_lazy=lazy)
+        b.edata._source = self.edata._source
+        b.srcdata, b.dstdata = self.srcdata, self.dstdata
+        return b
+
+    def exclude_edges(self, eids):
+        """-> a Block without the edges whose id (edata['_ID'], a CSC position) is in `eids`, a SORTED int64 tensor on the block's
+        device: DGL's exclude= of as_edge_prediction_sampler, applied to a sampled block.  Fixed form: the surviving slots of a row move
+        to its front in their old order and nbr and '_ID' hold -1 behind them; ragged form: a new indptr / indices / '_ID', the
+        surviving edges in their old order.  An id that is in no slot changes nothing.  The source list is not recompacted.  Needs a
+        block with edge ids (ValueError) whose edata holds no entry made for the old edges (RuntimeError).  Native kernels on the GPU
+        (fan-out <= 32, or the ragged form, whose new size costs one host read); exclude_edges_torch otherwise."""
+        eid = self._exclude_args(eids)
+        index = self._native_index() if eids.is_cuda and eid.is_cuda else None
+        if index is None:
+            return self.exclude_edges_torch(eids)
+        ex = eids.contiguous()
+        eid = eid.contiguous()
+        dev = eid.device.index or 0
+        if self.nbr is not None:
+            nbr, new_eid = torch.empty_like(index[0]), torch.empty_like(eid)
+            _capi.check(_lib.coala_block_exclude_edges(dev, index[0].data_ptr(), eid.data_ptr(), ex.data_ptr(), ex.numel(), nbr.data_ptr(),
+                                                       new_eid.data_ptr(), self.num_dst, index[0].shape[1], current_stream()))
+            return self._excluded(nbr, None, None, new_eid)
+        indptr, indices = index
+        new_indptr = torch.zeros(self.num_dst + 1, dtype=torch.int64, device=eid.device)
+        counts = torch.empty(self.num_dst, dtype=torch.int64, device=eid.device)
+        args = (dev, indptr.data_ptr(), indices.data_ptr(), eid.data_ptr(), ex.data_ptr(), ex.numel())
+        _capi.check(_lib.coala_block_exclude_edges_csr(*args, counts.data_ptr(), None, None, None, self.num_dst, current_stream()))
+        torch.cumsum(counts, 0, out=new_indptr[1:])
+        E = int(new_indptr[-1])
+        new_indices = torch.empty(E, dtype=torch.int32, device=eid.device)
+        new_eid = torch.empty(E, dtype=torch.int64, device=eid.device)
+        _capi.check(_lib.coala_block_exclude_edges_csr(*args, None, new_indptr.data_ptr(), new_indices.data_ptr(), new_eid.data_ptr(), self.num_dst,
+                                                       current_stream()))
+        return self._excluded(None, new_indptr, new_indices, new_eid)
+
+    def exclude_edges_torch(self, eids):
+        """exclude_edges in plain torch (torch.isin and a stable sort), any device, the same rule: its fallback, and its reference."""
+        eid = self._exclude_args(eids)
+        listed = torch.isin(eid, eids.to(eid.device))
+        if self.nbr is not None:
+            keep = (self.nbr >= 0) & ~listed
+            order = torch.sort((~keep).to(torch.int8), dim=1, stable=True).indices   # survivors first, each part in its old order
+            front = torch.arange(self.nbr.shape[1], device=keep.device).unsqueeze(0) < keep.sum(1, keepdim=True)
+            nbr = torch.where(front, self.nbr.gather(1, order), torch.full_like(self.nbr, -1))
+            return self._excluded(nbr, None, None, torch.where(front, eid.gather(1, order), torch.full_like(eid, -1)))
+        keep = ~listed
+        rows, _ = self._slots()
+        indptr = torch.zeros(self.num_dst + 1, dtype=torch.int64, device=eid.device)
+        torch.cumsum(torch.bincount(rows[keep], minlength=self.num_dst), 0, out=indptr[1:])
+        return self._excluded(None, indptr, self.indices[keep], eid[keep])
+
 
 class NeighborSampler(object):
     stream_safe = True  # every kernel and allocation of sample() goes to torch's current stream
@@ -987,3 +1068,156 @@ def random_walk(g, nodes, length, restart_prob=0.0, num_walks=1, seed=0, step=0)
     _capi.check(_lib.coala_sampler_random_walk(g._h, nodes.data_ptr(), nodes.numel(), num_walks, length, thr, int(seed) & ((1 << 64) - 1),
                                                int(step) & ((1 << 64) - 1), 0, out.data_ptr(), current_stream()))
     return out
+
+
+MAX_NEGATIVES = 64   # negative pairs per seed edge (coala_sampler.hip: kMaxNeg)
+
+
+class UniformNegativeSampler(object):
+    """DGL's dgl.dataloading.negative_sampler.Uniform(k): every seed edge (u, v) gets k pairs (u, v'), v' uniform over the nodes of the
+    graph; a pair that happens to be an edge, or v' == u, is kept.  Here the draws are a function of (seed, step, edge id, j): the rule
+    is in the header of coala_sampler.hip."""
+
+    def __init__(self, k):
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= MAX_NEGATIVES:
+            raise ValueError(f"k {k!r}: 0..{MAX_NEGATIVES} negative pairs per edge")
+        self.k = k
+
+
+class EdgeBatch(object):
+    """The pairs of one link-prediction minibatch.  eids: the seed edges (CSC positions); seed_nodes: int64 [n_nodes], the distinct
+    endpoints of the positive and negative pairs in order of first appearance -- the destination nodes of blocks[-1], so the rows of
+    the model's output; pos_src, pos_dst int32 [n] and neg_src, neg_dst int32 [n * k] index it.  The source of negative j of edge i
+    (entry i * k + j) is pos_src[i]: neg_src is made on first access."""
+
+    def __init__(self, eids, seed_nodes, pos_src, pos_dst, neg_dst, k):
+        self.eids, self.seed_nodes, self.pos_src, self.pos_dst, self.neg_dst, self.k = eids, seed_nodes, pos_src, pos_dst, neg_dst, k
+        self._neg_src = None
+
+    @property
+    def neg_src(self):
+        if self._neg_src is None:
+            self._neg_src = self.pos_src.repeat_interleave(self.k) if self.k else self.pos_src[:0]
+        return self._neg_src
+
+    def tensors(self):
+        """Every device tensor the batch holds (the loader's lifetime bookkeeping, as Block.tensors())."""
+        return [t for t in (self.eids, self.seed_nodes, self.pos_src, self.pos_dst, self.neg_dst, self._neg_src) if t is not None]
+
+
+def edge_batch(g, eids, num_neg, seed=0, step=0):
+    """Enqueue the edge-batch kernels for the seed edges `eids` (CSC positions) on the current stream, without waiting: -> the pending
+    call edge_batch_wait takes.  ValueError before any launch when n * (2 + num_neg) is over ITEM_LIMIT."""
+    if isinstance(num_neg, bool) or not isinstance(num_neg, int) or not 0 <= num_neg <= MAX_NEGATIVES:
+        raise ValueError(f"num_neg {num_neg!r}: 0..{MAX_NEGATIVES} negative pairs per edge")
+    eids = eids.to(g.device, dtype=torch.int64).contiguous()
+    n = eids.numel()
+    if eids.dim() != 1:
+        raise ValueError(f"seed edges of shape {tuple(eids.shape)}: a 1-D tensor of edge ids")
+    if n * (2 + num_neg) > ITEM_LIMIT:
+        raise ValueError(f"{n} seed edges with {num_neg} negatives each hold {n * (2 + num_neg)} items: over the limit of {ITEM_LIMIT}")
+    nodes = torch.empty(max(n * (2 + num_neg), 1), dtype=torch.int64, device=g.device)
+    pos = torch.empty((2, max(n, 1)), dtype=torch.int32, device=g.device)
+    neg = torch.empty(max(n * num_neg, 1), dtype=torch.int32, device=g.device)
+    out = _capi.EdgeBatchOut(nodes.data_ptr(), pos[0].data_ptr(), pos[1].data_ptr(), neg.data_ptr())
+    ticket = C.c_int64(-1)
+    mask = (1 << 64) - 1
+    _capi.check(_lib.coala_sampler_edge_batch(g._h, eids.data_ptr(), n, num_neg, int(seed) & mask, int(step) & mask, C.byref(out), C.byref(ticket),
+                                              current_stream()))
+    return (g, eids, n, num_neg, nodes, pos, neg, ticket.value)
+
+
+def edge_batch_wait(pending):
+    """Wait for the event behind an edge_batch call (only for its kernels) -> EdgeBatch.  IndexError when a seed edge was outside
+    [0, num_edges); the graph handle stays usable."""
+    g, eids, n, num_neg, nodes, pos, neg, ticket = pending
+    n_nodes, n_bad = C.c_int64(0), C.c_int64(0)
+    _capi.check(_lib.coala_sampler_edge_batch_wait(g._h, ticket, C.byref(n_nodes), C.byref(n_bad)))
+    if n_bad.value > 0:
+        raise IndexError(f"{n_bad.value} of the {n} seed edges are outside [0, {g.num_edges})")
+    return EdgeBatch(eids, nodes[: n_nodes.value], pos[0][:n], pos[1][:n], neg[: n * num_neg], num_neg)
+
+
+def reverse_edge_ids(indptr, indices):
+    """For a symmetric simple graph in CSC form: int64 [E], the position of every edge's reverse -- edge e = (u -> v) maps to the
+    position of (v -> u); a self-loop maps to itself.  What EdgePredictionSampler(exclude='reverse_id') takes as reverse_eids.  Plain
+    torch on the tensors' device.  ValueError when a row holds a neighbour twice, or an edge has no reverse."""
+    N, E = indptr.numel() - 1, indices.numel()
+    deg = indptr[1:] - indptr[:-1]
+    dst = torch.repeat_interleave(torch.arange(N, device=indptr.device), deg, output_size=E)
+    src = indices.to(torch.int64)
+    key, order = torch.sort(dst * N + src, stable=True)        # sorted (dst, src) keys, and the edge each one belongs to
+    if E > 1 and bool((key[1:] == key[:-1]).any()):
+        raise ValueError("reverse_edge_ids: a row holds the same neighbour twice; the graph must be simple")
+    want = src * N + dst                                         # the key of every edge's reverse
+    at = torch.searchsorted(key, want).clamp_max(max(E - 1, 0))
+    if E and bool((key[at] != want).any()):
+        raise ValueError("reverse_edge_ids: an edge has no reverse; the graph must be symmetric")
+    return order[at] if E else torch.zeros(0, dtype=torch.int64, device=indptr.device)
+
+
+class EdgePredictionSampler(object):
+    """Link-prediction minibatches, DGL's dgl.dataloading.as_edge_prediction_sampler: wraps a NeighborSampler, LaborSampler or
+    RelNeighborSampler.  sample / sample_begin / sample_end take seed EDGE ids (CSC positions) and return (input_nodes, EdgeBatch,
+    blocks): the endpoints of the seed edges and of k negative pairs per edge (negative_sampler, a UniformNegativeSampler) are made
+    the seed nodes of the inner sampler, and with exclude= the seed edges are taken out of every block so that the model cannot read
+    the answer: 'self' the batch's edges, 'reverse_id' those and reverse_eids[eids] (reverse_edge_ids gives that map for a symmetric
+    graph).  exclude needs edge ids on the blocks: it turns edge_ids on in the inner sampler.  The 3-tuple keeps batch[0] and batch[2]
+    where the loader and the manager read them: give the wrapper to COALA_GNN_DataLoader with a plain distributor over edge ids,
+    and self.fanouts (the inner fan-outs and one more entry, 1 + k) as its fan_out."""
+
+    def __init__(self, sampler, exclude=None, reverse_eids=None, negative_sampler=None):
+        if not isinstance(sampler, NeighborSampler) or isinstance(sampler, RandomWalkNeighborSampler) and exclude is not None:
+            raise ValueError("EdgePredictionSampler wraps a NeighborSampler, LaborSampler or RelNeighborSampler; RandomWalkNeighborSampler has no "
+                             "edge ids to exclude by")
+        if exclude not in (None, "self", "reverse_id"):
+            raise ValueError(f"exclude {exclude!r}: None, 'self' or 'reverse_id'")
+        if exclude == "reverse_id" and reverse_eids is None:
+            raise ValueError("exclude='reverse_id' needs reverse_eids (reverse_edge_ids(indptr, indices))")
+        if negative_sampler is not None and not isinstance(negative_sampler, UniformNegativeSampler):
+            raise ValueError("negative_sampler: a UniformNegativeSampler, or None")
+        self.sampler, self.exclude, self.reverse_eids = sampler, exclude, reverse_eids
+        self.num_neg = negative_sampler.k if negative_sampler is not None else 0
+        if exclude is not None:
+            sampler.edge_ids = True
+        # what the loader takes as fan_out: it sizes its fetch buffers as batch * prod(f + 1), and a batch of seed edges has up to
+        # batch * (2 + k) seed nodes -- one more entry, 1 + k, makes that product the bound of the input nodes
+        self.fanouts = list(sampler.fanouts) + [1 + self.num_neg]
+        self.bucket_by_owner = sampler.bucket_by_owner
+        self.stream_safe = sampler.stream_safe
+        self.completes_on_host = sampler.completes_on_host
+
+    def make_graph(self, indptr, indices, ndata=None, edata=None):
+        return CSCGraph(indptr, indices, ndata, edata)
+
+    def sample(self, g, eids, step=None):
+        """-> (input_nodes, EdgeBatch, blocks), blocks[0] the input layer; blocks[-1]'s destination nodes are batch.seed_nodes."""
+        return self.sample_end(self.sample_begin(g, eids, step))
+
+    def sample_begin(self, g, eids, step=None):
+        """Enqueue the edge batch, wait for its two counts (the one host wait of the wrapper), then enqueue the inner sample over the
+        batch's seed nodes.  -> the inner sampler's pending tuple, then the EdgeBatch."""
+        if isinstance(g, tuple):
+            g = CSCGraph(*g)
+        st = self.sampler.step if step is None else int(step)
+        batch = edge_batch_wait(edge_batch(g, eids, self.num_neg, self.sampler.seed, st))
+        return self.sampler.sample_begin(g, batch.seed_nodes, step) + (batch,)
+
+    def sample_end(self, pending):
+        batch = pending[-1]
+        input_nodes, _, blocks = self.sampler.sample_end(pending[:-1])
+        if self.exclude is not None:
+            ex = batch.eids
+            if self.exclude == "reverse_id":
+                ex = torch.cat([ex, self.reverse_eids.to(ex.device)[ex]])
+            ex = torch.sort(ex).values
+            blocks = [b.exclude_edges(ex) for b in blocks]
+        return input_nodes, batch, blocks
+
+
+def as_edge_prediction_sampler(sampler, exclude=None, reverse_eids=None, reverse_etypes=None, negative_sampler=None, prefetch_labels=None):
+    """DGL's dgl.dataloading.as_edge_prediction_sampler, same signature -> EdgePredictionSampler.  reverse_etypes (heterographs) and
+    prefetch_labels are not supported."""
+    if reverse_etypes is not None or prefetch_labels is not None:
+        raise ValueError("as_edge_prediction_sampler: reverse_etypes and prefetch_labels are not supported")
+    return EdgePredictionSampler(sampler, exclude=exclude, reverse_eids=reverse_eids, negative_sampler=negative_sampler)

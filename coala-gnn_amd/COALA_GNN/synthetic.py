@@ -117,6 +117,20 @@ def powerlaw_csc(num_nodes, avg_degree, seed=0, device="cuda", skew=3.0, max_deg
     return indptr, src
 
 
+def symmetrize_csc(indptr, indices):
+    """The symmetric simple graph of a CSC graph: every edge and its reverse once, no self-loops, each row sorted by source -- what
+    link prediction with exclude='reverse_id' wants (sampler.reverse_edge_ids).  numpy on the host; -> (indptr, indices) int64 tensors
+    on the inputs' device."""
+    ip, ix = indptr.cpu().numpy(), indices.cpu().numpy()
+    n = len(ip) - 1
+    dst = np.repeat(np.arange(n, dtype=np.int64), np.diff(ip))
+    keep = dst != ix
+    key = np.unique(np.concatenate([dst[keep] * n + ix[keep], ix[keep] * n + dst[keep]]))     # sorted by (dst, src)
+    new_ip = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // n, minlength=n), out=new_ip[1:])
+    return torch.from_numpy(new_ip).to(indptr.device), torch.from_numpy(key % n).to(indices.device)
+
+
 def edge_types_by_source(indices, num_rels):
     """int64 [E] synthetic edge types in CSC order: indices % num_rels.  The source node's "type" (its id modulo num_rels) fixes the
     relation of every edge leaving it, as in a homogenised heterograph whose relations are told apart by their source node type."""

@@ -51,6 +51,10 @@ class SamplerWalk(C.Structure):
     _fields_ = [("num_traversals", C.c_int32), ("num_random_walks", C.c_int32), ("term_threshold", C.c_uint64)]
 
 
+class EdgeBatchOut(C.Structure):
+    _fields_ = [("seed_nodes", C.c_void_p), ("pos_src", C.c_void_p), ("pos_dst", C.c_void_p), ("neg_dst", C.c_void_p)]
+
+
 class CommProfile(C.Structure):
     _fields_ = [("rows_ms", C.c_double), ("calls", C.c_uint64), ("remote_rows_in", C.c_uint64)]
 
@@ -165,6 +169,12 @@ SYMBOLS = {
     "coala_block_dot_gat_aggregate_backward": (_I, [_I] + [_VP] * 10 + [_I64, _I, _I, _I, C.c_float, _VP]),
     "coala_block_dot_gat_aggregate_csr": (_I, [_I] + [_VP] * 7 + [_I64, _I, _I, C.c_float, _VP]),
     "coala_block_dot_gat_aggregate_csr_backward": (_I, [_I] + [_VP] * 11 + [_I64, _I, _I, C.c_float, _VP]),
+    "coala_block_exclude_edges": (_I, [_I] + [_VP] * 3 + [_I64, _VP, _VP, _I64, _I, _VP]),
+    "coala_block_exclude_edges_csr": (_I, [_I] + [_VP] * 4 + [_I64] + [_VP] * 4 + [_I64, _VP]),
+    "coala_block_pair_dot": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _VP]),
+    "coala_block_pair_dot_backward": (_I, [_I] + [_VP] * 5 + [_I64, _I, _I, _VP]),
+    "coala_sampler_edge_batch": (_I, [_VP, _VP, _I64, _I, _U64, _U64, C.POINTER(EdgeBatchOut), C.POINTER(_I64), _VP]),
+    "coala_sampler_edge_batch_wait": (_I, [_VP, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
     "coala_shm_open":(_I, [C.c_char_p, _U64, _I, _I, C.POINTER(_VP)]),
     "coala_shm_host_ptr": (_VP, [_VP]),
     "coala_shm_device_ptr": (_VP, [_VP]),

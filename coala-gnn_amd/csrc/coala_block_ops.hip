@@ -3,7 +3,8 @@
 // (DGL's fn.max: SAGEConv "pool", GINConv "max"), the relation-typed sum (RelGraphConv's message step), GAT / GATv2 attention
 // aggregation (GATConv's and GATv2Conv's message steps), scaled dot-product attention (DotGatConv's and HGTConv's message step) and
 // relation-typed GAT attention (a softmax per destination and relation), forward and backward, on fixed blocks (nbr_local[n_dst, fanout], -1 = no
-// neighbour) and on the CSR blocks of full layers.  Stateless entry points: no handle, every launch on the caller's stream.
+// neighbour) and on the CSR blocks of full layers; and, for link prediction, edge exclusion on both block forms and the dot-product
+// scores of node pairs (forward and backward).  Stateless entry points: no handle, every launch on the caller's stream.
 //
 // Layout of the file: the device helpers every kernel walks a row with (which rows a wave takes, a row's bounds in either block form,
 // the 64-index chunk load, the wave reductions); then one `template <bool CSR>` kernel per op and direction, each written out top to
@@ -1570,6 +1571,183 @@ int rel_gat_backward_launch(int device, const int64_t* indptr, const int32_t* ro
     return COALA_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------ edge exclusion
+// Take edges out of a block by their edge id (link prediction: the seed edges must not be in the message-flow blocks).  excl is a
+// sorted int64 list of CSC positions, a few thousand at most: every slot binary-searches its id in it.  Survivors keep their order.
+
+__device__ __forceinline__ bool listed(const int64_t* __restrict__ list, int64_t n, int64_t e) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (list[mid] < e) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && list[lo] == e;
+}
+
+// Fixed form: 32 lanes per row (fan-out <= 32), a lane per slot; the survivors are ballot-compacted to the front of the row of the
+// output arrays and -1 fills both behind them ("valid entries first").  Out of place: nbr_out / eid_out are not the inputs.
+__global__ __launch_bounds__(kBlock) void exclude_edges_kernel(const int32_t* __restrict__ nbr, const int64_t* __restrict__ eid, int fanout,
+                                                               const int64_t* __restrict__ excl, int64_t n_excl, int32_t* __restrict__ nbr_out,
+                                                               int64_t* __restrict__ eid_out, int64_t n_dst) {
+    const auto [lane, wave, n_waves] = wave_rows();
+    const int gl = lane & 31, gbase = lane - gl;
+    for (int64_t d0 = wave * 2; d0 < n_dst; d0 += n_waves * 2) { // wave-uniform trip count: the ballot needs every lane
+        const int64_t d = d0 + (lane >> 5);
+        const bool slot = d < n_dst && gl < fanout;
+        const int64_t q = d * fanout + gl;
+        const int32_t s = slot ? nbr[q] : -1;
+        const int64_t e = s >= 0 ? eid[q] : -1;
+        const bool keep = s >= 0 && !listed(excl, n_excl, e);
+        const uint32_t m = (uint32_t)(__ballot(keep) >> gbase);
+        const int cnt = __builtin_popcount(m);
+        if (keep) {
+            const int64_t at = d * fanout + __builtin_popcount(m & ((1u << gl) - 1u));
+            nbr_out[at] = s;
+            eid_out[at] = e;
+        }
+        if (slot && gl >= cnt) {
+            nbr_out[q] = -1;
+            eid_out[q] = -1;
+        }
+    }
+}
+
+// CSR form, one wave per row, two passes of one kernel: COUNT writes the row's surviving edges to counts[d]; the caller scans them
+// into new_indptr, and the compact pass writes the survivors of row d from new_indptr[d] on.
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void exclude_edges_csr_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                                                                   const int64_t* __restrict__ eid, const int64_t* __restrict__ excl, int64_t n_excl,
+                                                                   int64_t* __restrict__ counts, const int64_t* __restrict__ new_indptr,
+                                                                   int32_t* __restrict__ indices_out, int64_t* __restrict__ eid_out, int64_t n_dst) {
+    const auto [lane, wave, n_waves] = wave_rows();
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        const int64_t beg = indptr[d], end = indptr[d + 1];
+        int64_t run = COUNT ? 0 : new_indptr[d];
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform
+            const int64_t i = e0 + lane;
+            const int64_t e = i < end ? eid[i] : -1;
+            const bool keep = i < end && !listed(excl, n_excl, e);
+            const uint64_t m = __ballot(keep);
+            if constexpr (!COUNT) {
+                if (keep) {
+                    const int64_t at = run + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+                    indices_out[at] = indices[i];
+                    eid_out[at] = e;
+                }
+            }
+            run += __builtin_popcountll(m);
+        }
+        if (COUNT && lane == 0) counts[d] = run;
+    }
+}
+
+int exclude_launch(int device, const int32_t* nbr, const int64_t* eid, int fanout, const int64_t* excl, int64_t n_excl, int32_t* nbr_out,
+                   int64_t* eid_out, int64_t n_dst, void* stream) {
+    if (n_dst < 0 || n_excl < 0 || !fanout_ok<false>(fanout)) return fail(COALA_EINVAL, "bad block shape (fan-out 1..32)");
+    if (n_dst == 0) return COALA_OK;
+    if (!nbr || !eid || !nbr_out || !eid_out || (n_excl > 0 && !excl)) return fail(COALA_EINVAL, "null buffer");
+    if (nbr == nbr_out || eid == eid_out) return fail(COALA_EINVAL, "edge exclusion is out of place");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(exclude_edges_kernel, dim3(grid1d(n_dst * 32, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, nbr, eid, fanout, excl,
+                       n_excl, nbr_out, eid_out, n_dst);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+int exclude_csr_launch(int device, const int64_t* indptr, const int32_t* indices, const int64_t* eid, const int64_t* excl, int64_t n_excl,
+                       int64_t* counts, const int64_t* new_indptr, int32_t* indices_out, int64_t* eid_out, int64_t n_dst, void* stream) {
+    if (n_dst < 0 || n_excl < 0) return fail(COALA_EINVAL, "bad block shape");
+    if (n_dst == 0) return COALA_OK;
+    const bool count = new_indptr == nullptr;
+    if (!indptr || !eid || (n_excl > 0 && !excl) || (count ? !counts : (!indices || !indices_out || !eid_out))) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    if (count)
+        hipLaunchKernelGGL(exclude_edges_csr_kernel<true>, row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, indices, eid, excl, n_excl,
+                           counts, new_indptr, indices_out, eid_out, n_dst);
+    else
+        hipLaunchKernelGGL(exclude_edges_csr_kernel<false>, row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, indices, eid, excl, n_excl,
+                           counts, new_indptr, indices_out, eid_out, n_dst);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- pair scores
+// out[p, hd] = <h[src_p, hd, :], h[dst_p, hd, :]> (DGL's fn.u_dot_v on a pair graph; a link predictor's score).  GS lanes -- a wave,
+// or a lane group for a small dim -- take one (pair, head): two row reads, lane gl multiplies the columns gl, gl + GS, ... with one
+// fma per term, then a butterfly sum, so every lane of the group ends with the same bits; no [P, dim] intermediate.  A pair with an
+// index < 0 scores 0.  The backward adds g h[dst_p] into grad_h[src_p] and g h[src_p] into grad_h[dst_p] with hardware float atomics
+// (grad_h zeroed by the caller; the order varies); a pair with an index < 0 adds nothing.
+template <int GS>
+__global__ __launch_bounds__(kBlock) void pair_dot_kernel(const float* __restrict__ h, const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
+                                                          float* __restrict__ out, int64_t n_units, int heads, int dim) {
+    constexpr int GPW = 64 / GS;
+    const auto [lane, wave, n_waves] = wave_rows();
+    const int gl = lane % GS;
+    const int64_t row = (int64_t)heads * dim;
+    for (int64_t u0 = wave * GPW; u0 < n_units; u0 += n_waves * GPW) { // wave-uniform trip count: the shuffles need every lane
+        const int64_t unit = u0 + lane / GS;
+        const bool ok = unit < n_units;
+        const int64_t p = ok ? unit / heads : 0;
+        const int hd = ok ? (int)(unit % heads) : 0;
+        const int32_t a = ok ? src[p] : -1, b = ok ? dst[p] : -1;
+        float acc = 0.0f;
+        if (a >= 0 && b >= 0) {
+            const float* ha = h + (int64_t)a * row + (int64_t)hd * dim;
+            const float* hb = h + (int64_t)b * row + (int64_t)hd * dim;
+            for (int c = gl; c < dim; c += GS) acc = __builtin_fmaf(ha[c], hb[c], acc);
+        }
+        for (int o = GS / 2; o; o >>= 1) acc += __shfl_xor(acc, o);
+        if (ok && gl == 0) out[unit] = acc;
+    }
+}
+
+template <int GS>
+__global__ __launch_bounds__(kBlock) void pair_dot_backward_kernel(const float* __restrict__ h, const int32_t* __restrict__ src,
+                                                                   const int32_t* __restrict__ dst, const float* __restrict__ grad_out,
+                                                                   float* __restrict__ grad_h, int64_t n_units, int heads, int dim) {
+    const int64_t group = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / GS, n_groups = (int64_t)gridDim.x * kBlock / GS;
+    const int gl = threadIdx.x % GS;
+    const int64_t row = (int64_t)heads * dim;
+    for (int64_t unit = group; unit < n_units; unit += n_groups) {
+        const int64_t p = unit / heads;
+        const int32_t a = src[p], b = dst[p];
+        if (a < 0 || b < 0) continue;
+        const int64_t oa = (int64_t)a * row + (unit % heads) * dim, ob = (int64_t)b * row + (unit % heads) * dim;
+        const float g = grad_out[unit];
+        for (int c = gl; c < dim; c += GS) {
+            unsafeAtomicAdd(grad_h + oa + c, g * h[ob + c]);
+            unsafeAtomicAdd(grad_h + ob + c, g * h[oa + c]);
+        }
+    }
+}
+
+template <typename F>
+void dispatch_pair_group(int dim, F&& f) { // lanes per (pair, head)
+    if (dim <= 16) f(std::integral_constant<int, 16>{});
+    else if (dim <= 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
+int pair_dot_launch(int device, const float* h, const int32_t* src, const int32_t* dst, const float* grad_out, float* out, int64_t n_pairs,
+                    int heads, int dim, void* stream) {
+    if (n_pairs < 0 || heads < 1 || dim < 1 || (int64_t)heads * dim > INT32_MAX) return fail(COALA_EINVAL, "bad pair shape (heads >= 1, dim >= 1, n_pairs >= 0)");
+    if (n_pairs == 0) return COALA_OK;
+    if (!h || !src || !dst || !out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const int64_t n_units = n_pairs * heads;
+    dispatch_pair_group(dim, [&](auto gs_c) {
+        constexpr int GS = decltype(gs_c)::value;
+        const dim3 grid(grid1d(n_units * GS, kBlock, 8192));
+        if (grad_out)
+            hipLaunchKernelGGL(pair_dot_backward_kernel<GS>, grid, dim3(kBlock), 0, (hipStream_t)stream, h, src, dst, grad_out, out, n_units, heads, dim);
+        else
+            hipLaunchKernelGGL(pair_dot_kernel<GS>, grid, dim3(kBlock), 0, (hipStream_t)stream, h, src, dst, out, n_units, heads, dim);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
 } // namespace
 
 // The C ABI (include/coala_hip.h): every entry forwards to its launch, the fixed form with <false>, a null indptr and its fan-out, the
@@ -1752,6 +1930,28 @@ int coala_block_rel_gat_aggregate_csr_backward(int device, const int64_t* indptr
                                                float negative_slope, void* stream) {
     return rel_gat_backward_launch<true>(device, indptr, row, etype, 0, el, er, feat, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, num_rels,
                                          heads, dim, negative_slope, stream);
+}
+
+int coala_block_exclude_edges(int device, const int32_t* nbr, const int64_t* eid, const int64_t* excluded, int64_t n_excluded, int32_t* nbr_out,
+                              int64_t* eid_out, int64_t n_dst, int fanout, void* stream) {
+    return exclude_launch(device, nbr, eid, fanout, excluded, n_excluded, nbr_out, eid_out, n_dst, stream);
+}
+
+int coala_block_exclude_edges_csr(int device, const int64_t* indptr, const int32_t* indices, const int64_t* eid, const int64_t* excluded,
+                                  int64_t n_excluded, int64_t* counts_out, const int64_t* new_indptr, int32_t* indices_out, int64_t* eid_out,
+                                  int64_t n_dst, void* stream) {
+    return exclude_csr_launch(device, indptr, indices, eid, excluded, n_excluded, counts_out, new_indptr, indices_out, eid_out, n_dst, stream);
+}
+
+int coala_block_pair_dot(int device, const float* h, const int32_t* src, const int32_t* dst, float* out, int64_t n_pairs, int heads, int dim,
+                         void* stream) {
+    return pair_dot_launch(device, h, src, dst, nullptr, out, n_pairs, heads, dim, stream);
+}
+
+int coala_block_pair_dot_backward(int device, const float* h, const int32_t* src, const int32_t* dst, const float* grad_out, float* grad_h,
+                                  int64_t n_pairs, int heads, int dim, void* stream) {
+    if (n_pairs > 0 && !grad_out) return fail(COALA_EINVAL, "null buffer");
+    return pair_dot_launch(device, h, src, dst, grad_out, grad_h, n_pairs, heads, dim, stream);
 }
 
 } // extern "C"

@@ -1302,6 +1302,72 @@ __global__ __launch_bounds__(kBlock) void bucket_reindex_kernel(const int64_t* _
         dst_in_src[d] = (int32_t)new_of_old[d]; // the dst nodes are the first n_dst entries of the unbucketed list
 }
 
+// ------------------------------------------------------------------------------------------------------- edge batches
+// Seed EDGES of a link-prediction minibatch (DGL's as_edge_prediction_sampler with negative_sampler.Uniform(k);
+// coala_sampler_edge_batch).  Seed edge e is a CSC position: its destination is the row v with indptr[v] <= e < indptr[v+1] (an
+// upper-bound search, so a run of degree-0 rows around v is never chosen), its source indices[e].  Negative j of e is the pair
+// (u, mulhi64(splitmix64(nkey + j), N)) with nkey = sample_key(seed, step, 0, e) ^ kNegStream: a function of (seed, step, e, j) alone.
+// The item list [src_0.. | dst_0.. | v'_{0,0}..] stands where a layer's (dst..., neighbours...) list stands: item p is hashed by
+// edge_items, scan_assign (as a layer of n(2+k) "destination nodes" and fan-out 0) gives the distinct ids in order of first
+// appearance, and edge_relabel_clear writes every item's index in that list and leaves the table clean, as relabel_clear does.  An e
+// outside [0, E) gives -1 in each of its items (no node) and is counted.
+constexpr uint64_t kNegStream = 0xA54FF53A5F1D36F1ull; // xor on sample_key: the negative pairs' own stream
+constexpr int kMaxNeg = 64;
+
+__device__ __forceinline__ int64_t edge_row(const Graph& g, int64_t e) { // 0 <= e < indptr[num_nodes]
+    int64_t lo = 0, hi = g.num_nodes; // indptr[lo] <= e < indptr[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (g.indptr[mid] > e) hi = mid;
+        else lo = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kBlock) void edge_items_kernel(Graph g, int64_t num_edges, const int64_t* __restrict__ eids, int64_t n, int k,
+                                                            uint64_t seed, uint64_t step, int64_t* __restrict__ items, Table tb,
+                                                            uint32_t* __restrict__ slot_of_item, unsigned long long* __restrict__ n_bad) {
+    const int64_t n_items = n * (2 + k);
+    const uint32_t mask = table_size(n_items) - 1;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_items; p += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = p < 2 * n ? (p < n ? p : p - n) : (p - 2 * n) / k;
+        const int64_t e = eids[i];
+        int64_t key = -1;
+        if (e >= 0 && e < num_edges) {
+            if (p < n) key = g.indices[e];
+            else if (p < 2 * n) key = edge_row(g, e);
+            else
+                key = (int64_t)__umul64hi(splitmix64((sample_key(seed, step, 0, (uint64_t)e) ^ kNegStream) + (uint64_t)((p - 2 * n) % k)),
+                                          (uint64_t)g.num_nodes);
+        } else if (p < n) {
+            atomicAdd(n_bad, 1ull);
+        }
+        items[p] = key;
+        hash_insert(tb, mask, key, p, slot_of_item);
+    }
+}
+
+// item -> index in seed_nodes (-1: the item of a bad edge); the table is cleared for the next call alongside, and the bad-edge count
+// goes to the host and back to 0.
+__global__ __launch_bounds__(kBlock) void edge_relabel_clear_kernel(int64_t n, int k, const uint32_t* __restrict__ slot_of_item, Table tb,
+                                                                    int32_t* __restrict__ pos_src, int32_t* __restrict__ pos_dst,
+                                                                    int32_t* __restrict__ neg_dst, unsigned long long* __restrict__ n_bad,
+                                                                    int64_t* __restrict__ n_bad_host, int64_t next_items) {
+    const int64_t n_items = n * (2 + k);
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_items; p += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t s = slot_of_item[p];
+        const int32_t local = (s == 0xFFFFFFFFu) ? -1 : (int32_t)tb.local_of_slot[s];
+        if (p < n) pos_src[p] = local;
+        else if (p < 2 * n) pos_dst[p - n] = local;
+        else neg_dst[p - 2 * n] = local;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *n_bad_host = (int64_t)*n_bad;
+        *n_bad = 0;
+    }
+    clear_table(tb, table_size(next_items));
+}
+
 } // namespace
 
 struct coala_sampler {
@@ -1309,6 +1375,7 @@ struct coala_sampler {
         int n_layers = 0, n_parts = 0;
         bool labor = false; // fixed fan-outs are LABOR layers: every layer of the call is ragged
         bool rel = false;   // relation layers (a fan-out per relation): every layer of the call is ragged
+        bool edge_batch = false; // coala_sampler_edge_batch: the slot holds n_nodes and n_bad, collected by coala_sampler_edge_batch_wait
         int64_t n_seeds = 0;
         bool ragged(int l) const { return labor || rel || fanouts[l] == -1; } // CSR block, sizes known on the device only
         int32_t fanouts[COALA_SAMPLER_MAX_LAYERS] = {}; // of a relation call: -1 for a layer whose fan-outs are all -1, else 0
@@ -1332,6 +1399,7 @@ struct coala_sampler {
     int64_t* hubs = nullptr;               // [hub_cap] destination indices, reused layer after layer
     int64_t hub_cap = 0;
     unsigned long long* hub_count = nullptr; // [COALA_SAMPLER_MAX_LAYERS] list lengths of the call in flight
+    unsigned long long* edge_bad = nullptr;  // out-of-range seed edges of the edge batch in flight; its last kernel puts it back to 0
     // pinned host ring: per call kSlot words (kPinEdges .. kPinParts), and an event recorded behind the last kernel
     int64_t* counts_pinned = nullptr; // host pointer
     int64_t* counts_pinned_dev = nullptr;
@@ -1419,6 +1487,7 @@ int wait_impl(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* 
     HIPCHK(hipEventSynchronize(s->done[slot])); // the kernels behind this event stored the counts into pinned host memory
     const int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
     const RingInfo& r = s->ring[slot];
+    if (r.edge_batch) return fail(COALA_EINVAL, "ticket %lld is an edge batch: collect it with coala_sampler_edge_batch_wait", (long long)ticket);
     if (n_src_host)
         for (int l = 0; l < r.n_layers; ++l) n_src_host[l] = pin[l];
     if (n_edges_host)
@@ -1775,9 +1844,91 @@ int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const
     if (n_src_host || n_edges_host) return wait_impl(s, (int64_t)ticket, n_src_host, n_edges_host, nullptr);
     return COALA_OK;
 }
+
+// An edge batch takes a ring slot and the handle's scratch exactly as a sample of one fixed layer over n (2 + k) items does: the same
+// stream hand-over, the same clean-table bookkeeping (launch_call), three launches, the counts into the slot's pinned words.
+int edge_batch_impl(coala_sampler_t* s, const int64_t* eids, int64_t n, int num_neg, uint64_t seed, uint64_t step, const coala_edge_batch_t* out,
+                    int64_t* ticket_out, void* stream) {
+    if (!s || !out || (!eids && n > 0)) return fail(COALA_EINVAL, "null argument");
+    if (num_neg < 0 || num_neg > kMaxNeg) return fail(COALA_EINVAL, "num_neg %d outside 0..%d", num_neg, kMaxNeg);
+    if (n < 0 || n > kItemLimit) return fail(COALA_EINVAL, "bad edge count");
+    const int64_t items = n * (2 + num_neg);
+    if (items > kItemLimit)
+        return fail(COALA_EINVAL, "an edge batch of %lld edges and %d negatives each holds %lld items (limit %lld)", (long long)n, num_neg,
+                    (long long)items, (long long)kItemLimit);
+    if (n > 0 && (!out->seed_nodes || !out->pos_src || !out->pos_dst || (num_neg > 0 && !out->neg_dst))) return fail(COALA_EINVAL, "null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(s->device));
+    if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
+    s->last_stream = st;
+    Plan p{};
+    p.st = st;
+    p.info.n_layers = 1;
+    p.info.n_seeds = items;
+    p.info.edge_batch = true;
+    p.items_cap[0] = items;
+    p.max_items = p.max_nbr = (uint64_t)items;
+    int rc;
+    if ((rc = grow_workspace(s, p))) return rc;
+    const uint64_t ticket = s->calls;
+    const int slot = (int)(ticket % kRing);
+    if (ticket >= kRing) HIPCHK(hipEventSynchronize(s->done[slot]));
+    int64_t* pin_dev = s->counts_pinned_dev + (size_t)slot * kSlot;
+    s->ring[slot] = p.info;
+    if (n == 0) {
+        int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
+        pin[0] = pin[kPinEdges] = 0;
+    } else {
+        const bool stale = s->clean_items == 0 || table_size(items) > table_size((int64_t)s->clean_items);
+        s->clean_items = 0;
+        if (stale) {
+            const uint32_t t0 = table_size(items);
+            HIPCHK(hipMemsetAsync(s->tb.keys, 0xFF, (size_t)t0 * sizeof(long long), st));
+            HIPCHK(hipMemsetAsync(s->tb.minpos, 0xFF, (size_t)t0 * sizeof(uint32_t), st));
+        }
+        const dim3 blk(kBlock);
+        hipLaunchKernelGGL(edge_items_kernel, dim3(grid1d(items, kBlock, 8192)), blk, 0, st, s->g, s->num_edges, eids, n, num_neg, seed, step,
+                           s->nbr_global, s->tb, s->slot_of_item, s->edge_bad);
+        if ((rc = next_gen(s, st))) return rc;
+        const int tiles = grid1d(items, kTile, kMaxTiles);
+        // the item list as the "destination nodes" of a layer of fan-out 0: n_items = items, item p is items[p]
+        hipLaunchKernelGGL(scan_assign_kernel<false>, dim3(tiles), blk, 0, st, (const int64_t*)s->nbr_global, (const int64_t*)s->nbr_global,
+                           (const int64_t*)nullptr, items, 0, (const uint32_t*)s->slot_of_item, s->tb, s->status, s->ticket, s->ticket_total,
+                           s->scan_gen & 0x3FFFFFFFull, out->seed_nodes, s->counts_dev + 1, pin_dev);
+        s->ticket_total += (unsigned long long)tiles;
+        hipLaunchKernelGGL(edge_relabel_clear_kernel, dim3(grid1d(std::max<int64_t>(items, table_size(items)), kBlock, 4096)), blk, 0, st, n, num_neg,
+                           (const uint32_t*)s->slot_of_item, s->tb, out->pos_src, out->pos_dst, out->neg_dst, s->edge_bad, pin_dev + kPinEdges,
+                           items);
+        s->clean_items = (uint64_t)items;
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(s->done[slot], st));
+    s->calls++;
+    if (ticket_out) *ticket_out = (int64_t)ticket;
+    return COALA_OK;
+}
 } // namespace
 
 extern "C" {
+
+int coala_sampler_edge_batch(coala_sampler_t* s, const int64_t* eids, int64_t n, int num_neg, uint64_t seed, uint64_t step,
+                             const coala_edge_batch_t* out, int64_t* ticket_out, void* stream) {
+    return edge_batch_impl(s, eids, n, num_neg, seed, step, out, ticket_out, stream);
+}
+
+int coala_sampler_edge_batch_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_nodes_host, int64_t* n_bad_host) {
+    if (!s) return fail(COALA_EINVAL, "null sampler");
+    if (ticket < 0 || (uint64_t)ticket >= s->calls || s->calls - (uint64_t)ticket > kRing)
+        return fail(COALA_EINVAL, "ticket %lld is not one of the last %d calls", (long long)ticket, kRing);
+    const int slot = (int)((uint64_t)ticket % kRing);
+    if (!s->ring[slot].edge_batch) return fail(COALA_EINVAL, "ticket %lld is not an edge batch", (long long)ticket);
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipEventSynchronize(s->done[slot]));
+    const int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
+    if (n_nodes_host) *n_nodes_host = pin[0];
+    if (n_bad_host) *n_bad_host = pin[kPinEdges];
+    return COALA_OK;
+}
 
 int coala_sampler_create(int device, const int64_t* indptr, const int64_t* indices, int64_t num_nodes, int64_t num_edges,
                          coala_sampler_t** out) {
@@ -1798,6 +1949,8 @@ int coala_sampler_create(int device, const int64_t* indptr, const int64_t* indic
               hipMalloc((void**)&s->hub_count, COALA_SAMPLER_MAX_LAYERS * sizeof(unsigned long long)) == hipSuccess &&
               hipMemset(s->hub_count, 0, COALA_SAMPLER_MAX_LAYERS * sizeof(unsigned long long)) == hipSuccess &&
               (s->hub_cap == 0 || hipMalloc((void**)&s->hubs, (size_t)s->hub_cap * sizeof(int64_t)) == hipSuccess) &&
+              hipMalloc((void**)&s->edge_bad, sizeof(unsigned long long)) == hipSuccess &&
+              hipMemset(s->edge_bad, 0, sizeof(unsigned long long)) == hipSuccess &&
               hipHostMalloc((void**)&s->counts_pinned, kRing * kSlot * sizeof(int64_t), hipHostMallocMapped) == hipSuccess &&
               hipHostGetDevicePointer((void**)&s->counts_pinned_dev, s->counts_pinned, 0) == hipSuccess;
     for (int i = 0; i < kRing && ok; ++i) ok = hipEventCreateWithFlags(&s->done[i], hipEventDisableTiming) == hipSuccess;
@@ -1814,7 +1967,7 @@ int coala_sampler_destroy(coala_sampler_t* s) {
     (void)hipSetDevice(s->device);
     (void)hipDeviceSynchronize();
     void* ptrs[] = {s->nbr_global, s->tb.keys, s->tb.local_of_slot, s->slot_of_item, s->wave_counts, s->new_of_old, s->status, s->ticket, s->counts_dev,
-                     s->hubs, s->hub_count};
+                     s->hubs, s->hub_count, s->edge_bad};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (s->counts_pinned) (void)hipHostFree(s->counts_pinned);

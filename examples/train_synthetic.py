@@ -16,6 +16,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --model_type rsage --num_rels 4
   python examples/train_synthetic.py --model_type hgt --num_heads 4 --num_rels 4 --num_ntypes 3
   python examples/train_synthetic.py --sampler pinsage --model_type pinsage --num_traversals 2 --termination_prob 0.5 --num_random_walks 10
+  python examples/train_synthetic.py --task link --num_negs 5 --exclude reverse_id
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -33,9 +34,62 @@ import torch  # noqa: E402
 
 from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
-from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, GATv2, PinSAGE, SageMean  # noqa: E402
-from COALA_GNN.sampler import LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler, sort_csc_by_etype  # noqa: E402
-from COALA_GNN.synthetic import alloc_pinned_table, edge_types_by_source, powerlaw_csc  # noqa: E402
+from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, GATv2, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
+from COALA_GNN.sampler import (EdgePredictionSampler, LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler,  # noqa: E402
+                               UniformNegativeSampler, reverse_edge_ids, sort_csc_by_etype)
+from COALA_GNN.synthetic import alloc_pinned_table, edge_types_by_source, powerlaw_csc, symmetrize_csc  # noqa: E402
+
+
+def train_link(args, comm, device, indptr, indices, feat, files, fan_out):
+    """--task link: GraphSAGE (or GAT) link prediction as in DGL's example -- minibatches of seed edges, --num_negs uniform negative pairs
+    per edge, the seed edges (and with --exclude reverse_id their reverses) taken out of the blocks, dot-product scores, BCE loss."""
+    rev = None
+    if args.exclude == "reverse_id":   # the reverse map needs a symmetric simple graph
+        indptr, indices = symmetrize_csc(indptr, indices)
+        rev = reverse_edge_ids(indptr, indices)
+    cls = LaborSampler if args.sampler == "labor" else NeighborSampler
+    sampler = EdgePredictionSampler(cls(fan_out), exclude=None if args.exclude == "none" else args.exclude, reverse_eids=rev,
+                                    negative_sampler=UniformNegativeSampler(args.num_negs))
+    g = sampler.make_graph(indptr, indices)
+    n_train = int(0.6 * indices.numel()) if args.num_train_edges is None else min(args.num_train_edges, indices.numel())
+    train_eids = torch.randperm(indices.numel(), generator=torch.Generator().manual_seed(0))[:n_train]
+    nd = Node_Distributor(comm, train_eids, args.batch_size, *files, parsing_method="baseline")   # the items are edge ids: no colour routing
+    loader = COALA_GNN_DataLoader(SSD_INFO(1, args.dim * 4, 1024, 0), nd, g, sampler, args.batch_size, args.dim, sampler.fanouts,
+                                  args.cache_size, device, refresh_counter=args.refresh_counter, cache_backend=args.cache_backend,
+                                  sim_buf=feat, shuffle=False, num_rows=args.nodes, prefetch=args.prefetch)
+    if args.seed >= 0:
+        torch.manual_seed(args.seed)
+    if args.model_type == "gat":
+        encoder = GAT(args.dim, args.hidden_channels, args.hidden_channels, len(fan_out), args.num_heads)
+    else:
+        encoder = SAGE(args.dim, args.hidden_channels, args.hidden_channels, len(fan_out), args.sage_aggregator)
+    model = LinkPredictor(encoder).to(device)
+    optimizer = torch.optim.Adam(model.parameters(), lr=args.learning_rate)
+    count = 0
+    model.train()
+    for epoch in range(args.epochs):
+        print(f"Epoch: {epoch}")
+        epoch_start = time.time()
+        for step, (input_nodes, batch, blocks, fetch_feature) in enumerate(loader):
+            if step % 100 == 0:
+                print(f"Rank: {comm.local_rank} step: {step}")
+            count += 1
+            pos_score, neg_score = model(blocks, fetch_feature, batch)
+            loss = link_loss(pos_score, neg_score)
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+            if count == 1:
+                first_loss = loss.item()
+        torch.cuda.synchronize()
+        print(f"Epoch Time: {time.time() - epoch_start}")
+        print(f"Total number of iterations: {count}")
+        loader.print_stats()
+    print(f"first loss {first_loss:.4f}")
+    print(f"final loss {loss.item():.4f}")
+    comm.global_comm.Barrier()
+    del loader
+    comm.destroy_process_group()
 
 
 def main():
@@ -64,6 +118,14 @@ def main():
     ap.add_argument("--use_edge_weight", action="store_true",
                     help="with --edge_weights random: the blocks carry their edge ids (NeighborSampler(edge_ids=True)) and the gcn / sage "
                          "layers multiply every message by its edge's weight, block.edata['w'] (DGL's edge_weight=); gat and gin ignore it")
+    ap.add_argument("--task", type=str, default="node", choices=["node", "link"],
+                    help="link: link prediction on the synthetic graph (EdgePredictionSampler over --sampler neighbor | labor, --model_type sage "
+                         "| gat as the encoder, dot-product scores, BCE loss); the training items are edge ids")
+    ap.add_argument("--num_negs", type=int, default=5, help="with --task link: uniform negative pairs per seed edge (0..64)")
+    ap.add_argument("--num_train_edges", type=int, default=None, help="with --task link: training edges per epoch (default: 60 %% of the edges)")
+    ap.add_argument("--exclude", type=str, default="self", choices=["none", "self", "reverse_id"],
+                    help="with --task link: take the seed edges out of the sampled blocks (self), and their reverses too (reverse_id: the "
+                         "synthetic graph is symmetrised first)")
     ap.add_argument("--batch_size", type=int, default=1024)
     ap.add_argument("--hidden_channels", type=int, default=128)
     ap.add_argument("--num_classes", type=int, default=19)
@@ -166,6 +228,10 @@ def main():
             tmp = comm.global_comm.allgather(tmp)[0]
     files = [os.path.join(tmp, f) for f in ("color.npy", "topk.npy", "score.npy")]
 
+    if args.task == "link":
+        if args.path or args.sampler not in ("neighbor", "labor") or args.model_type not in ("sage", "gat") or args.edge_weights != "none":
+            ap.error("--task link runs on the synthetic graph with --sampler neighbor | labor and --model_type sage | gat, without --edge_weights")
+        return train_link(args, comm, device, indptr, indices, feat, files, fan_out)
     train_nid = train_ids[torch.randperm(n_train, generator=torch.Generator().manual_seed(0))]               # :62-65
     nd = Node_Distributor(comm, train_nid, args.batch_size, *files, parsing_method=args.distribution)      # :68
     edata, prob = {}, None

@@ -478,6 +478,29 @@ int coala_sampler_random_walk(coala_sampler_t* s, const int64_t* nodes, int64_t 
                               uint64_t seed, uint64_t step, int layer, int64_t* traces_out, void* stream);
 /* Counts of an earlier call, with the edge counts of its layers; returns the device-side refusal of a full, LABOR or relation layer, if any. */
 int coala_sampler_wait_layers(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host);
+/* Edge minibatches for link prediction (DGL's as_edge_prediction_sampler with negative_sampler.Uniform(num_neg)).  eids: device
+ * int64[n], seed edges as CSC positions 0 <= e < num_edges.  Edge e has destination v, the row with indptr[v] <= e < indptr[v+1] (found
+ * by an upper-bound search: degree-0 rows around v are never chosen), and source u = indices[e].  It gets num_neg (0..64) negative
+ * pairs (u, v'_j), v'_j = mulhi64(splitmix64(nkey + j), num_nodes), nkey = sample_key(seed, step, 0, e) ^ 0xA54FF53A5F1D36F1 (a stream
+ * of its own; sample_key is in the header of coala_sampler.hip): a function of (seed, step, e, j) alone, not of the batch, the edge's
+ * place in it or the grid.  Negatives that are real edges, or equal u, are kept (as in DGL).
+ * Outputs (device): seed_nodes int64[n (2 + num_neg)] = the distinct ids of the item list [src_0.. | dst_0.. | v'_{0,0} .. v'_{n-1,k-1}]
+ * in order of first appearance (the source-list rule of the layers), n_nodes of them; pos_src, pos_dst int32[n] and neg_dst
+ * int32[n, num_neg]: where every item sits in seed_nodes.  The source of a negative is its edge's pos_src.  An e outside [0, num_edges)
+ * gives -1 in all of its entries, adds no node and is counted in n_bad.  Nothing is written past these capacities.
+ * Limit: n (2 + num_neg) <= 8,388,608 items; COALA_EINVAL (with a message) before any launch otherwise, and for num_neg outside 0..64.
+ * Three launches on `stream` (items + hash insert, the layers' scan_assign, relabel + table clear); no memset, copy or wait.  The call
+ * takes a ticket of the handle's ring like a sample; n_nodes and n_bad go to pinned host memory from the kernels and
+ * coala_sampler_edge_batch_wait collects them behind the call's event (coala_sampler_wait refuses such a ticket, and the reverse). */
+typedef struct coala_edge_batch {
+    int64_t* seed_nodes; /* int64[n (2 + num_neg)]                     */
+    int32_t* pos_src;    /* int32[n]                                   */
+    int32_t* pos_dst;    /* int32[n]                                   */
+    int32_t* neg_dst;    /* int32[n, num_neg]; may be NULL, num_neg 0  */
+} coala_edge_batch_t;
+int coala_sampler_edge_batch(coala_sampler_t* s, const int64_t* eids, int64_t n, int num_neg, uint64_t seed, uint64_t step,
+                             const coala_edge_batch_t* out, int64_t* ticket_out, void* stream);
+int coala_sampler_edge_batch_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_nodes_host, int64_t* n_bad_host);
 
 /* Block op for the consumer of these blocks (the native Block objects stand where DGL blocks stand in
  * examples/sbatch_ssd_gnn_train.py:138-141; dgl.nn.SAGEConv's "mean" reduces to this): out[d, :] = mean over the valid j of
@@ -712,6 +735,30 @@ int coala_block_dot_gat_aggregate_csr(int device, const int64_t* indptr, const i
 int coala_block_dot_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* row, const float* q, const float* k,
                                                const float* v, const float* out, const float* lse, const float* grad_out, float* grad_q,
                                                float* grad_k, float* grad_v, int64_t n_dst, int heads, int dim, float scale, void* stream);
+/* Edge exclusion (link prediction: the seed edges, and their reverses, leave the message-flow blocks).  excluded: device int64
+ * [n_excluded], SORTED ascending, CSC positions (a few thousand at most; every slot binary-searches its edge id in it).  eid is the
+ * block's edge-id array (coala_sampler_sample_layers_edge_ids), laid out like its index array.
+ *   fixed form: nbr int32 [n_dst, fanout], eid int64 [n_dst, fanout] -> nbr_out, eid_out of the same shapes (other buffers than the
+ *     inputs): the valid slots whose id is not listed, in their old order at the front of the row, -1 in both arrays behind them.
+ *   CSR form, two calls of one kernel with the row scan between them left to the caller: with new_indptr NULL the call writes
+ *     counts_out int64[n_dst], the surviving edges of every row; with new_indptr int64[n_dst + 1] (the exclusive scan of those counts)
+ *     it writes the survivors of row d to indices_out / eid_out from new_indptr[d] on, in their old order.
+ * An id that is in no slot changes nothing.  One launch each; "bad block shape" / "null buffer" as for the other block ops. */
+int coala_block_exclude_edges(int device, const int32_t* nbr, const int64_t* eid, const int64_t* excluded, int64_t n_excluded, int32_t* nbr_out,
+                              int64_t* eid_out, int64_t n_dst, int fanout, void* stream);
+int coala_block_exclude_edges_csr(int device, const int64_t* indptr, const int32_t* indices, const int64_t* eid, const int64_t* excluded,
+                                  int64_t n_excluded, int64_t* counts_out, const int64_t* new_indptr, int32_t* indices_out, int64_t* eid_out,
+                                  int64_t n_dst, void* stream);
+/* Pair scores (DGL's fn.u_dot_v on a pair graph; the score of a link predictor): out[p, hd] = <h[src_p, hd, :], h[dst_p, hd, :]>,
+ * h fp32 [N, heads, dim], src / dst int32 [n_pairs], out fp32 [n_pairs, heads].  A wave -- a group of 16 or 32 lanes for dim <= 16 /
+ * 32 -- takes one (pair, head): two row reads, one fma per term and a butterfly sum, no [n_pairs, dim] intermediate; bitwise
+ * reproducible.  A pair with an index < 0 scores 0 and gets no gradient; an index >= N is not checked here (the caller's duty).
+ * Backward, one launch: grad_h[src_p, hd, :] += g[p, hd] h[dst_p, hd, :] and grad_h[dst_p, hd, :] += g[p, hd] h[src_p, hd, :] with
+ * hardware float atomics (grad_h [N, heads, dim] zeroed by the caller; the order varies). */
+int coala_block_pair_dot(int device, const float* h, const int32_t* src, const int32_t* dst, float* out, int64_t n_pairs, int heads, int dim,
+                         void* stream);
+int coala_block_pair_dot_backward(int device, const float* h, const int32_t* src, const int32_t* dst, const float* grad_out, float* grad_h,
+                                  int64_t n_pairs, int heads, int dim, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Shared pinned-host ("UVA") region.  Replaces SharedUVAManager (COALA_GNN_Modules/shared_UVA.cuh:26-115):

@@ -1,0 +1,246 @@
+"""Link prediction end to end on the GPU: EdgePredictionSampler(exclude='reverse_id') on a symmetric graph, harness.LinkPredictor over
+the SAGE and GAT encoders on the native kernels, and a COALA_GNN_DataLoader over edge ids.
+
+In global ids (tests/_global_ref.py: edges_of): no block holds a seed edge or its reverse, and every other edge of the unexcluded call
+at the same seed and step is there, in the same order.
+
+The encoder on the excluded blocks is compared with _global_ref.Evaluation as in test_models_global_gpu.py (embeddings, every parameter
+gradient, grad_X; tolerance FACTOR * E32 from Evaluation.check_kernel).  Its loss matrix is Cmat = dLoss/dZ of harness.link_loss over
+the pair scores, computed in float64 from the float64 reference's embeddings: the reference's gradients are then those of the link
+loss itself.  The step of a case is the first of 0, 1, 2, ... whose float64 evaluation stays clear of a gradient discontinuity (kink gap
+>= 1.5 tau, the margin tests/_model_cases.py chose its steps with).
+
+Scores, loss and dLoss/dZ of the product path (block_ops.pair_dot and its backward, torch's BCE) are compared with float64 evaluated on
+the same fp32 embeddings, u = 2^-24, gamma(n) = n u / (1 - n u):
+  score   |err| <= sb = gamma(D + 1) sum |z_u z_v|                                     (the pair_dot bound of test_pair_dot_gpu.py)
+  loss    a BCE term t(s) has |dt/ds| <= 1, is a handful of fp32 operations on values of size |s| + log 2, and the mean of M terms is a
+          tree sum: |err| <= mean(sb) + 8 u mean(|s| + 1) + 32 u mean(t)
+  dL/dZ   row r sums m_r terms c_p z_other, c_p = (sigmoid(s_p) - y_p) / M: sigmoid has slope <= 1/4 and is itself within 2 u, the
+          subtraction and the division add u each, so |dc_p| <= (sb_p / 4 + 4 u) / M, and
+          |err_r| <= gamma(m_r + 1) sum |c_p z_other| + sum |dc_p| |z_other|
+
+Measured on the MI355X over the six cases (every one passes at step 0): error / E32 at most 3.33 (labor55-b0-gat layers.0.bias), scores
+at most 0.128 of their bound, the loss 0.008 and dLoss/dZ 0.048 of theirs."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import _edge_batch_ref as ER
+import _global_ref as R
+import _model_cases as MC
+from _util import ColorFiles
+from test_block_ops_gpu import U, _gamma
+
+pytestmark = pytest.mark.gpu
+
+N, IN, HID, EMB, HEADS = 3000, 20, 12, 16, 2
+N_EDGES, K = 256, 3
+FACTOR = 4.0
+SAMPLER_SEED = 21
+CASES = [("ns55", 0), ("labor55", 0), ("ns55", 4)]
+
+
+@pytest.fixture(scope="module")
+def setup(hiplib):
+    import torch
+    from COALA_GNN.sampler import NeighborSampler, reverse_edge_ids
+    ip, ix = ER.symmetric_graph(N, 8, seed=6)
+    rng = np.random.default_rng(6)
+    X = rng.standard_normal((N, IN)).astype(np.float32)
+    eids = rng.choice(len(ix), size=N_EDGES, replace=False).astype(np.int64)
+    d_ip, d_ix = torch.from_numpy(ip).cuda(), torch.from_numpy(ix).cuda()
+    g = NeighborSampler([1]).make_graph(d_ip, d_ix)
+    rev = reverse_edge_ids(d_ip, d_ix)
+    rows = ER.brute_force_rows(ip)
+    r = rev.cpu().numpy()
+    assert np.array_equal(ix[r], rows) and np.array_equal(rows[r], ix)
+    yield torch, g, ip, ix, X, eids, rev
+    g.close()
+
+
+def _inner(kind, G):
+    from COALA_GNN.sampler import LaborSampler, NeighborSampler
+    cls = LaborSampler if kind == "labor55" else NeighborSampler
+    return cls([5, 5], seed=SAMPLER_SEED, bucket_by_owner=G, edge_ids=True)
+
+
+def _encoder(torch, model, seed):
+    from COALA_GNN.harness import GAT, SAGE
+    torch.manual_seed(3000 + seed)
+    m = SAGE(IN, HID, EMB, 2, aggregator_type="mean") if model == "sage_mean" else GAT(IN, HID, EMB, 2, HEADS)
+    with torch.no_grad():
+        for p in m.parameters():
+            if p.dim() == 1:
+                p.normal_(0.0, 0.3)     # the biases are zero at initialisation: make them visible (tests/_model_cases.py)
+    return m
+
+
+def _link_loss64(torch, Z, batch):
+    """float64 on the CPU: Z [n, D] array -> (pos, neg, loss, dLoss/dZ, per-pair coefficient c, the pairs (a, b, y))"""
+    z = torch.tensor(Z, dtype=torch.float64, requires_grad=True)
+    a = torch.cat([batch["pos_src"], batch["neg_src"]]).long()
+    b = torch.cat([batch["pos_dst"], batch["neg_dst"]]).long()
+    y = torch.cat([torch.ones(len(batch["pos_src"])), torch.zeros(len(batch["neg_src"]))]).double()
+    s = (z[a] * z[b]).sum(-1)
+    loss = torch.nn.functional.binary_cross_entropy_with_logits(s, y)
+    loss.backward()
+    c = ((torch.sigmoid(s) - y) / len(y)).detach().numpy()
+    n = len(batch["pos_src"])
+    return s[:n].detach().numpy(), s[n:].detach().numpy(), float(loss.detach()), z.grad.numpy(), c, (a.numpy(), b.numpy(), y.numpy())
+
+
+def _sample(torch, g, kind, G, eids, rev, step):
+    from COALA_GNN.sampler import EdgePredictionSampler, UniformNegativeSampler
+    w = EdgePredictionSampler(_inner(kind, G), exclude="reverse_id", reverse_eids=rev, negative_sampler=UniformNegativeSampler(K))
+    input_nodes, batch, blocks = w.sample(g, torch.from_numpy(eids).cuda(), step=step)
+    _, _, plain = _inner(kind, G).sample(g, batch.seed_nodes, step=step)
+    return input_nodes, batch, blocks, plain
+
+
+@pytest.mark.parametrize("model", ["sage_mean", "gat"])
+@pytest.mark.parametrize("kind,G", CASES)
+def test_link_model_against_global_reference(setup, monkeypatch, kind, G, model):
+    torch, g, ip, ix, X, eids, rev = setup
+    from COALA_GNN import block_ops
+    from COALA_GNN import sampler as S
+    from COALA_GNN.harness import LinkPredictor, link_loss
+    excluded = np.unique(np.concatenate([eids, rev.cpu().numpy()[eids]]))
+    enc = _encoder(torch, model, 0)
+    for step in range(12):
+        input_nodes, batch, blocks, plain = _sample(torch, g, kind, G, eids, rev, step)
+        # ---- the integer part, in global ids
+        want = ER.edge_batch(ip, ix, eids, K, seed=SAMPLER_SEED, step=step)
+        assert np.array_equal(batch.seed_nodes.cpu().numpy(), want["seed_nodes"])
+        assert torch.equal(blocks[-1].dstdata["_ID"], batch.seed_nodes) and input_nodes is blocks[0].src_nodes
+        layers = [R.decode(b) for b in blocks]
+        removed = 0
+        for lay, p in zip(layers, plain):
+            tri = R.edges_of(p)
+            assert not np.isin(lay.tri[:, 2], excluded).any(), "a block holds a seed edge or its reverse"
+            assert np.array_equal(lay.tri, tri[~np.isin(tri[:, 2], excluded)]), "an edge of the unexcluded call is missing"
+            assert np.array_equal(lay.src, R.decode(p).src)
+            removed += len(tri) - len(lay.tri)
+        assert removed > 0
+        b64 = {k: getattr(batch, k).cpu() for k in ("pos_src", "pos_dst", "neg_src", "neg_dst")}
+        assert np.array_equal(want["seed_nodes"][b64["pos_src"].numpy()], ix[eids]) and b64["neg_src"].numel() == N_EDGES * K
+        # ---- the reference: embeddings in float64, then Cmat = dLoss/dZ from its scores
+        params = MC.params_of(enc)
+        z0 = R.run(model, params, X, np.zeros((len(want["seed_nodes"]), EMB)), layers, {}, heads=HEADS).logits
+        _, _, _, cmat, _, _ = _link_loss64(torch, z0, b64)
+        ev = R.Evaluation(model, params, X, cmat, layers, {}, heads=HEADS)
+        print(f"{kind}-b{G}-{model} step {step}: kink gap {ev.gap:.3e} tau {ev.tau:.3e}")
+        if ev.gap >= 1.5 * ev.tau:
+            break
+    else:
+        raise AssertionError("every step sits on a gradient discontinuity")
+    # ---- the product path on the native kernels
+    ran = []
+    for name in ("_MeanAggregate", "_MeanAggregateCSR", "_GatAggregate", "_GatAggregateCSR"):
+        real = getattr(S, name)
+        monkeypatch.setattr(S, name, type("Spy", (), {"apply": staticmethod(lambda *a, _r=real, _n=name: (ran.append(_n), _r.apply(*a))[1])}))
+    real_pair = block_ops._PairDot.apply
+    monkeypatch.setattr(block_ops._PairDot, "apply", staticmethod(lambda *a: (ran.append("_PairDot"), real_pair(*a))[1]))
+    for name in ("mean", "gat"):
+        monkeypatch.setattr(S.Block, name + "_aggregate_torch", lambda self, *a, **k: (_ for _ in ()).throw(AssertionError("a torch fallback ran")))
+    monkeypatch.setattr(block_ops, "pair_dot_torch", lambda *a, **k: (_ for _ in ()).throw(AssertionError("pair_dot_torch ran")))
+    enc = enc.cuda()
+    Xd = torch.from_numpy(X).cuda()
+    got = MC.run_model(enc, blocks, Xd, torch.from_numpy(cmat.astype(np.float32)).cuda())
+    base = ("_MeanAggregate" if model == "sage_mean" else "_GatAggregate")
+    assert ran == [base + ("CSR" if b.nbr is None else "") for b in blocks], ran
+    ev.check_kernel(got, f"{kind}-b{G}-{model}", FACTOR)
+    # ---- scores, loss and dLoss/dZ through LinkPredictor / link_loss / pair_dot
+    del ran[:]
+    lp = LinkPredictor(enc)
+    feat = Xd[input_nodes].clone().requires_grad_(True)
+    pos, neg = lp(blocks, feat, batch)
+    loss = link_loss(pos, neg)
+    enc.zero_grad()
+    loss.backward()
+    assert ran.count("_PairDot") == 2 and tuple(pos.shape) == (N_EDGES,) and tuple(neg.shape) == (N_EDGES * K,)
+    assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in enc.parameters()) and bool(torch.isfinite(feat.grad).all())
+    with torch.no_grad():
+        Z = enc(blocks, feat)
+    zd = Z.clone().requires_grad_(True)
+    p2, n2 = lp.predictor(zd, batch.pos_src, batch.pos_dst), lp.predictor(zd, batch.neg_src, batch.neg_dst)
+    assert torch.equal(p2, pos) and torch.equal(n2, neg), "the forward is not reproducible"
+    link_loss(p2, n2).backward()
+    z = Z.double().cpu().numpy()
+    pos64, neg64, loss64, grad64, c, (a, b, y) = _link_loss64(torch, z, b64)
+    s64 = np.concatenate([pos64, neg64])
+    sb = _gamma(EMB + 1) * (np.abs(z[a] * z[b])).sum(-1)
+    err = np.abs(np.concatenate([pos.detach().cpu().numpy(), neg.detach().cpu().numpy()]).astype(np.float64) - s64)
+    print(f"scores: worst err / bound {float((err / sb).max()):.3f}")
+    assert np.all(err <= sb)
+    t = np.maximum(s64, 0) - s64 * y + np.log1p(np.exp(-np.abs(s64)))
+    lbound = sb.mean() + 8 * U * (np.abs(s64) + 1).mean() + 32 * U * t.mean()
+    loss32 = float(loss.detach())
+    print(f"loss {loss32:.6f}: err {abs(loss32 - loss64):.3e} bound {lbound:.3e}")
+    assert abs(loss32 - loss64) <= lbound
+    dc = (sb / 4 + 4 * U) / len(y)
+    mag, extra, m = np.zeros_like(z), np.zeros_like(z), np.zeros(len(z))
+    for rows, other in ((a, b), (b, a)):
+        np.add.at(mag, rows, np.abs(c[:, None] * z[other]))
+        np.add.at(extra, rows, dc[:, None] * np.abs(z[other]))
+        np.add.at(m, rows, 1)
+    gbound = _gamma(m + 1)[:, None] * mag + extra
+    gerr = np.abs(zd.grad.double().cpu().numpy() - grad64)
+    print(f"dLoss/dZ: worst err / bound {float((gerr / np.maximum(gbound, 1e-300)).max()):.3f}")
+    assert np.all(gerr <= gbound)
+
+
+def test_loader_over_edge_ids(setup, tmp_path):
+    """COALA_GNN_DataLoader with the wrapper and a plain distributor whose items are edge ids: three steps; the delivered rows are the
+    table's rows of input_nodes, and the pair indices address the destination nodes of blocks[-1]."""
+    torch, g, ip, ix, X, eids, rev = setup
+    from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO
+    from COALA_GNN.sampler import EdgePredictionSampler, UniformNegativeSampler
+    from COALA_GNN.synthetic import alloc_pinned_table, block_colors, feature_rows_torch
+    dim, batch = 64, 64
+    table = alloc_pinned_table(N, dim, seed=4, device=0)
+    color, tk, sc, _ = block_colors(N, nodes_per_color=512)
+    files = ColorFiles(tmp_path, color, tk, sc)
+    comm = MPI_Comm_Manager(0)
+    comm.initialize_nested_process_group("isolated")
+    train_eids = torch.randperm(len(ix), generator=torch.Generator().manual_seed(1))[: batch * 4]
+    nd = Node_Distributor(comm, train_eids, batch, files.color_file, files.topk_file, files.score_file, parsing_method="baseline")
+    sampler = EdgePredictionSampler(_inner("ns55", 0), exclude="reverse_id", reverse_eids=rev, negative_sampler=UniformNegativeSampler(K))
+    loader = COALA_GNN_DataLoader(SSD_INFO(1, dim * 4, 1024, 0), nd, g, sampler, batch, dim, sampler.fanouts, 4, "cuda:0",
+                                  cache_backend="isolated", sim_buf=table, num_rows=N)
+    steps = 0
+    rows = ER.brute_force_rows(ip)
+    for input_nodes, eb, blocks, feat in loader:
+        e = train_eids[steps * batch: (steps + 1) * batch]
+        assert torch.equal(eb.eids.cpu(), e)
+        assert torch.equal(feat, feature_rows_torch(input_nodes, dim, 4)) and torch.equal(input_nodes, blocks[0].src_nodes)
+        out_nodes = blocks[-1].dstdata["_ID"]
+        assert torch.equal(out_nodes, eb.seed_nodes)
+        assert np.array_equal(out_nodes[eb.pos_src.long()].cpu().numpy(), ix[e.numpy()])
+        assert np.array_equal(out_nodes[eb.pos_dst.long()].cpu().numpy(), rows[e.numpy()])
+        assert eb.neg_dst.numel() == batch * K and int(eb.neg_dst.max()) < out_nodes.numel() and int(eb.neg_dst.min()) >= 0
+        assert torch.equal(out_nodes[eb.neg_src.long()], out_nodes[eb.pos_src.long()].repeat_interleave(K))
+        ex = torch.cat([e, rev.cpu()[e]])
+        for b in blocks:
+            assert not bool(torch.isin(b.edata["_ID"].cpu(), ex).any())
+        steps += 1
+    assert steps == 3
+    del loader
+    table.close()
+
+
+@pytest.mark.parametrize("more", [["--exclude", "reverse_id"], ["--sampler", "labor", "--model_type", "gat", "--num_heads", "2"]])
+def test_example_link_task(hiplib, more):
+    """examples/train_synthetic.py --task link: one short epoch through the loader, LinkPredictor and link_loss."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "examples", "train_synthetic.py"), "--task", "link", "--nodes", "20000", "--dim", "32",
+                          "--hidden_channels", "32", "--batch_size", "256", "--num_train_edges", str(256 * 12), "--epochs", "1", "--num_negs", "5",
+                          "--cache_size", "2"] + more,
+                         capture_output=True, text=True, timeout=300, env=dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0"))
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    assert "Total number of iterations: 11" in out.stdout and "GPU hit ratio:" in out.stdout
+    first, final = (float(re.search(name + r" loss ([0-9.eE+-]+)", out.stdout).group(1)) for name in ("first", "final"))
+    assert np.isfinite(first) and np.isfinite(final)
