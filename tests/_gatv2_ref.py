@@ -104,10 +104,11 @@ def edges_csr(indptr, indices):
     return rows[valid], indices[valid].astype(np.int64), -(-deg // 64)
 
 
-def reference(rows, srcs, n_dst, n_src, nc, fs, fd, attn, g, parts, slope=SLOPE, fault=None):
+def reference(rows, srcs, n_dst, n_src, nc, fs, fd, attn, g, parts, slope=SLOPE, fault=None, wave_rows=None):
     """float64 values and bounds (module docstring): dict name -> (value, bound) for out, gs (grad_src), gd (grad_dst), ga (grad_attn),
     and 'empty', the rows without a valid edge.  rows / srcs: the valid edges (int64), in row order; nc: chunks per row; parts: rows of
-    the grad_attn partials buffer."""
+    the grad_attn partials buffer.  wave_rows: the row numbers the kernel deals to its waves, when the n_dst rows given here are a
+    subset of a larger block whose other rows add exact zeros to grad_attn (default: 0 .. n_dst - 1)."""
     import torch
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))   # noqa: E731
     g_ = lambda n: torch.from_numpy(gamma(n.numpy()))    # noqa: E731
@@ -170,7 +171,7 @@ def reference(rows, srcs, n_dst, n_src, nc, fs, fd, attn, g, parts, slope=SLOPE,
     b_gd = 1.01 * torch.zeros_like(gd).index_add_(0, r, ak * (dt + t.abs() * (2 * U + g_(k + ncr)[r])).unsqueeze(-1)) + TINY * A.abs()
     ga = (t.unsqueeze(-1) * lz).sum(0)
     waves = parts * (4 if H * D <= 1024 else 1)
-    chain = np.bincount(np.arange(n_dst) % waves, weights=kcnt.numpy() + np.asarray(nc, dtype=np.float64), minlength=1).max() if n_dst else 0.0
+    chain = np.bincount((np.arange(n_dst) if wave_rows is None else np.asarray(wave_rows, dtype=np.int64)) % waves, weights=kcnt.numpy() + np.asarray(nc, dtype=np.float64), minlength=1).max() if n_dst else 0.0
     b_ga = 1.01 * ((dt.unsqueeze(-1) * lz.abs()).sum(0) + (3 * U + float(gamma(chain + 3 + parts))) * (t.abs().unsqueeze(-1) * lz.abs()).sum(0)) + TINY
     return dict(out=(out.numpy(), b_out.numpy()), gs=(gs.numpy(), b_gs.numpy()), gd=(gd.numpy(), b_gd.numpy()), ga=(ga.numpy(), b_ga.numpy()),
                 lse=(lse.numpy(), b_lse.numpy()), empty=(kcnt == 0).numpy())
