@@ -16,7 +16,8 @@ from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _GatAggregate, _G
 
 __all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "RandomWalkNeighborSampler", "random_walk", "sort_csc_by_etype",
            "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT", "EID", "EdgePredictionSampler", "as_edge_prediction_sampler",
-           "UniformNegativeSampler", "EdgeBatch", "edge_batch", "edge_batch_wait", "reverse_edge_ids", "MAX_NEGATIVES"]
+           "UniformNegativeSampler", "EdgeBatch", "edge_batch", "edge_batch_wait", "reverse_edge_ids", "MAX_NEGATIVES",
+           "TemporalNeighborSampler", "TemporalEdgePredictionSampler", "sort_csc_by_time", "check_time_sorted", "pair_code_bits"]
 
 _lib = _capi.load()
 
@@ -62,6 +63,42 @@ def check_etype_sorted(indptr, etype, num_rels, name="etype"):
                          f"COALA_GNN.sampler.sort_csc_by_etype(indptr, indices, etype)")
 
 
+def sort_csc_by_time(indptr, indices, ts):
+    """Sort the in-edges of every node by timestamp, the twin of sort_csc_by_etype: -> (indices_sorted, ts_sorted, perm).  Stable by
+    (row, time): simultaneous edges keep their CSC order.  perm (int64 [E]) maps new positions to old, indices_sorted = indices[perm],
+    so any other per-edge data is carried along as edata[key][perm].  Plain torch on the tensors' device; indptr is unchanged.
+    TemporalNeighborSampler needs a graph in this order."""
+    if ts.dim() != 1 or ts.numel() != indices.numel():
+        raise ValueError(f"edge times must have shape ({indices.numel()},) in CSC order, got {tuple(ts.shape)}")
+    if ts.is_floating_point() or ts.is_complex() or ts.dtype == torch.bool:
+        raise ValueError("edge times must be an integer tensor")
+    deg = indptr[1:] - indptr[:-1]
+    rows = torch.repeat_interleave(torch.arange(deg.numel(), device=indptr.device), deg, output_size=indices.numel())
+    by_time = torch.sort(ts.to(indptr.device), stable=True).indices
+    perm = by_time[torch.sort(rows[by_time], stable=True).indices]
+    return indices[perm], ts[perm], perm
+
+
+def check_time_sorted(indptr, ts, name="ts"):
+    """What TemporalNeighborSampler asks of a graph's edge timestamps, on the tensors' device: an integer tensor of num_edges values,
+    non-decreasing inside every row of the CSC.  ValueError (naming sort_csc_by_time) otherwise."""
+    E = int(indptr[-1].item()) if indptr.numel() else 0
+    if not isinstance(ts, torch.Tensor) or ts.is_floating_point() or ts.is_complex() or ts.dtype == torch.bool:
+        raise ValueError(f"edata[{name!r}]: edge times must be an integer tensor (floating-point timestamps are not supported)")
+    if ts.dim() != 1 or ts.numel() != E:
+        raise ValueError(f"edata[{name!r}]: edge times must have shape ({E},) in CSC order, got {tuple(ts.shape)}")
+    if E == 0:
+        return
+    t = ts.to(indptr.device)
+    drop = t[1:] < t[:-1]                                  # drop[p - 1]: the time falls from position p - 1 to p
+    starts = indptr[1:-1]
+    starts = starts[(starts > 0) & (starts < E)]           # ... which it may where a row starts
+    drop[starts - 1] = False
+    if bool(drop.any()):
+        raise ValueError(f"edata[{name!r}]: edge times must be non-decreasing inside every row of the CSC; sort the graph with "
+                         f"COALA_GNN.sampler.sort_csc_by_time(indptr, indices, ts)")
+
+
 class CSCGraph(object):
     """int64 CSC (indptr[N+1], indices[E]) resident on one GPU + per-node data (labels...) + per-edge data in CSC order (edge weights
     for NeighborSampler(prob=key))."""
@@ -77,6 +114,7 @@ class CSCGraph(object):
         self.edata = dict(edata or {})
         self._weights = {}   # edata key -> (the entry, its version, the validated fp32 device copy)
         self._etypes = {}    # edata key -> (the entry, its version, num_rels, the validated int32 device copy)
+        self._etimes = {}    # edata key -> (the entry, its version, the validated int64 device copy)
         self._max_in_degree = None
         self._h = C.c_void_p()
         dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
@@ -124,8 +162,24 @@ class CSCGraph(object):
         self._etypes[key] = (t, t._version, num_rels, t32)
         return t32
 
+    def edge_times(self, key):
+        """edata[key] as a contiguous int64 tensor on the graph's device for TemporalNeighborSampler, checked once on the device
+        (check_time_sorted: an integer tensor of num_edges values, non-decreasing inside every row) and cached until the entry is
+        replaced or modified in place, or close().  KeyError when the key is missing, ValueError (naming sort_csc_by_time) when bad."""
+        if key not in self.edata:
+            raise KeyError(f"edata has no {key!r}: the edge times of TemporalNeighborSampler(time={key!r}) (keys: {sorted(self.edata)})")
+        t = self.edata[key]
+        hit = self._etimes.get(key)
+        if hit is not None and hit[0] is t and hit[1] == t._version:
+            return hit[2]
+        check_time_sorted(self.indptr, t, key)
+        t64 = t.to(device=self.device, dtype=torch.int64).contiguous()
+        self._etimes[key] = (t, t._version, t64)
+        return t64
+
     def close(self):
         self._etypes = {}
+        self._etimes = {}
         if getattr(self, "_h", None):
             _lib.coala_sampler_destroy(self._h)
             self._h = C.c_void_p()
@@ -1070,6 +1124,137 @@ def random_walk(g, nodes, length, restart_prob=0.0, num_walks=1, seed=0, step=0)
     return out
 
 
+def pair_code_bits(num_nodes, n_slots):
+    """node_bits of the (node, time slot) pair code slot << node_bits | node: the bit length of num_nodes, so that the value
+    num_nodes itself fits the node field and names no node.  ValueError when the code would not fit 62 bits."""
+    node_bits = int(num_nodes).bit_length()
+    slot_bits = max(int(n_slots) - 1, 0).bit_length()
+    if node_bits + slot_bits > 62:
+        raise ValueError(f"{n_slots} distinct query times on a graph of {num_nodes} nodes: a (node, time) pair takes {node_bits} + {slot_bits} "
+                         f"bits, over the 62 of a code; sample fewer distinct times per call")
+    return node_bits
+
+
+class TemporalNeighborSampler(NeighborSampler):
+    """Temporal neighbour sampling (PyG's NeighborLoader(time_attr=, temporal_strategy=), GraphBolt's temporal_sample_neighbors, TGN's
+    most recent neighbours), in place of NeighborSampler: same loader.  graph.edata[time] holds an int64 timestamp per edge in CSC
+    order, non-decreasing inside every row (sort_csc_by_time; checked once per graph).  Every seed node comes with a query time t, and
+    every layer samples only among the in-edges with timestamp < t (inclusive=True: <= t, PyG's rule); a neighbour inherits the query
+    time of the row that reached it.  strategy 'uniform' draws `fanout` of the eligible edges without replacement (all when there are
+    no more), 'last' takes the `fanout` most recent.  The rule is in the header of coala_sampler.hip.
+
+    sample(g, seed_nodes, step=None, seed_times=None): the times are seed_times (int64, one per seed), else
+    g.ndata[seed_time][seed_nodes] when the sampler was given seed_time= (what lets the unchanged loader drive it), else ValueError.
+    The (seed node, time) pairs of a call must be distinct.  A node reached at two different times is two items: Block.src_nodes holds
+    node ids and may repeat one; Block.src_times / Block.dst_times (int64) hold the query time of every source / destination item.
+    Every block is fixed-stride.  With edge_ids (the default) block.edata carries '_ID', graph.edata through it (so edata[time]), and
+    'dt' (int64, shaped like nbr): the row's query time minus the edge's timestamp, 0 on padding -- what time-decay weights and time
+    encodings are made from.  Not provided (ValueError): fan-out -1, prob=, bucket_by_owner > 0 (the owner of a pair is not the owner of
+    its node), floating-point timestamps, node timestamps."""
+
+    STRATEGIES = ("uniform", "last")
+
+    def __init__(self, fanouts, time="ts", strategy="uniform", inclusive=False, seed_time=None, seed=0, edge_ids=True, prob=None,
+                 bucket_by_owner=0, node_time=None):
+        fanouts = [int(f) for f in fanouts]
+        if any(f == -1 for f in fanouts):
+            raise ValueError("TemporalNeighborSampler: fan-out -1 (every eligible in-edge) is not supported; each fan-out must be 1..32")
+        if prob is not None:
+            raise ValueError("TemporalNeighborSampler: prob= (weighted temporal draws) is not supported")
+        if bucket_by_owner:
+            raise ValueError("TemporalNeighborSampler: bucket_by_owner is not supported: the owner of a (node, time) pair is not the owner of its node")
+        if node_time is not None:
+            raise ValueError("TemporalNeighborSampler: node timestamps are not supported, only edge timestamps (time=)")
+        if strategy not in self.STRATEGIES:
+            raise ValueError(f"strategy {strategy!r}: 'uniform' or 'last'")
+        super().__init__(fanouts, seed=seed, edge_ids=edge_ids)
+        self.time, self.strategy, self.inclusive, self.seed_time = time, strategy, bool(inclusive), seed_time
+        self._ctx = None   # (edge times, slot_time, n_slots) of the call sample_begin is making, for _enqueue
+
+    def _seed_times(self, g, seeds, seed_times):
+        if seed_times is None:
+            if self.seed_time is None:
+                raise ValueError("TemporalNeighborSampler: no query times: pass seed_times=, or build the sampler with seed_time= "
+                                 "(a key of graph.ndata)")
+            if self.seed_time not in g.ndata:
+                raise KeyError(f"ndata has no {self.seed_time!r}: the query times of TemporalNeighborSampler(seed_time={self.seed_time!r})")
+            col = g.ndata[self.seed_time]
+            seed_times = col[seeds.to(col.device)]
+        if not isinstance(seed_times, torch.Tensor) or seed_times.is_floating_point() or seed_times.is_complex() or seed_times.dtype == torch.bool:
+            raise ValueError("seed times must be an integer tensor (floating-point timestamps are not supported)")
+        if seed_times.dim() != 1 or seed_times.numel() != seeds.numel():
+            raise ValueError(f"seed times of shape {tuple(seed_times.shape)}: one per seed node, ({seeds.numel()},)")
+        return seed_times.to(g.device, dtype=torch.int64)
+
+    def sample(self, g, seed_nodes, step=None, seed_times=None):
+        """-> (input_nodes, output_nodes, blocks), blocks[0] the input layer; input_nodes is blocks[0].src_nodes, repeated ids included."""
+        return self.sample_end(self.sample_begin(g, seed_nodes, step, seed_times))
+
+    def sample_begin(self, g, seed_nodes, step=None, seed_times=None):
+        """NeighborSampler.sample_begin over the codes of the (seed node, query time) pairs.  The table of distinct times and the codes
+        are made on the device; the one host read is the number of distinct times."""
+        if isinstance(g, tuple):
+            g = CSCGraph(*g)
+        ts = g.edge_times(self.time)   # raises before any launch
+        if seed_nodes.dim() != 1:
+            raise ValueError(f"seed nodes of shape {tuple(seed_nodes.shape)}: a 1-D tensor of node ids")
+        seeds = seed_nodes.to(g.device, dtype=torch.int64).contiguous()
+        times = self._seed_times(g, seeds, seed_times)
+        slot_time, slot = torch.unique(times, sorted=True, return_inverse=True)
+        n_slots = int(slot_time.numel())
+        bits = pair_code_bits(g.num_nodes, n_slots)
+        # a seed id outside the graph takes the node field num_nodes, which names no node: an empty row
+        codes = (slot << bits) | torch.where((seeds >= 0) & (seeds < g.num_nodes), seeds, g.num_nodes)
+        self._ctx = (ts, slot_time.contiguous(), n_slots)
+        try:
+            pending = super().sample_begin(g, codes, step)
+        finally:
+            self._ctx = None
+        return pending + ((seeds, slot_time, bits, ts),)
+
+    def _enqueue(self, g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket):
+        ts, slot_time, n_slots = self._ctx
+        lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), None, src_caps[l], edge_caps[l]) for l in range(L)])
+        eid_p = (C.c_void_p * L)(*[t.data_ptr() for t in eid]) if eid is not None else None
+        _capi.check(_lib.coala_sampler_sample_layers_temporal(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, ts.data_ptr(),
+                                                              slot_time.data_ptr(), n_slots, self.STRATEGIES.index(self.strategy),
+                                                              int(self.inclusive), eid_p, None, None, C.byref(ticket), current_stream()))
+
+    def sample_end(self, pending):
+        """Wait for the counts, decode every layer's source codes into node ids and query times, and build the blocks."""
+        g, codes, n, rev, src, nbr, _, ticket, _, _, eid = pending[:-1]
+        seeds, slot_time, bits, ts = pending[-1]
+        L = len(rev)
+        n_src = (C.c_int64 * L)()
+        n_edges = (C.c_int64 * L)()
+        _capi.check(_lib.coala_sampler_wait_layers(g._h, ticket, n_src, n_edges, None))
+        cur = torch.cuda.current_stream(g.device)
+        mask = (1 << bits) - 1
+        blocks = []
+        n_dst, dst_nodes, dst_times = n, seeds, slot_time[codes >> bits] if n else codes
+        for l in range(L):
+            ns, f = int(n_src[l]), rev[l]
+            code_l = src[l][:ns]
+            code_l.record_stream(cur)   # allocated on the stream of sample_begin, decoded on this one
+            src_nodes, src_times = code_l & mask, slot_time[code_l >> bits] if ns else code_l
+            src_nodes[:n] = seeds       # the seeds as they were given: an id outside the graph was coded as num_nodes
+            eid_l = eid[l][: n_dst * f].view(n_dst, f) if eid is not None else None
+            lazy = None
+            if eid_l is not None:
+                def dt(eid_l=eid_l, t_row=dst_times):
+                    return torch.where(eid_l >= 0, t_row.unsqueeze(1) - ts[eid_l.clamp_min(0)], 0)
+                lazy = {"dt": dt}
+            b = Block(src_nodes, nbr[l][: n_dst * f].view(n_dst, f), n_dst, edata_graph=g, eid=eid_l, edata_lazy=lazy)
+            b.src_times, b.dst_times = src_times, dst_times
+            b.srcdata["_TIME"], b.dstdata["_TIME"] = src_times, dst_times   # Block.tensors() reports what srcdata / dstdata hold
+            if l == 0:
+                for k, v in g.ndata.items():
+                    b.dstdata[k] = v[dst_nodes] if v.device == dst_nodes.device else v[dst_nodes.cpu()]
+            blocks.insert(0, b)
+            n_dst, dst_nodes, dst_times = ns, src_nodes, src_times
+        return blocks[0].src_nodes, seeds, blocks
+
+
 MAX_NEGATIVES = 64   # negative pairs per seed edge (coala_sampler.hip: kMaxNeg)
 
 
@@ -1088,10 +1273,12 @@ class EdgeBatch(object):
     """The pairs of one link-prediction minibatch.  eids: the seed edges (CSC positions); seed_nodes: int64 [n_nodes], the distinct
     endpoints of the positive and negative pairs in order of first appearance -- the destination nodes of blocks[-1], so the rows of
     the model's output; pos_src, pos_dst int32 [n] and neg_src, neg_dst int32 [n * k] index it.  The source of negative j of edge i
-    (entry i * k + j) is pos_src[i]: neg_src is made on first access."""
+    (entry i * k + j) is pos_src[i]: neg_src is made on first access.  seed_times (TemporalEdgePredictionSampler; None otherwise): int64
+    [n_nodes], the query time of every entry of seed_nodes -- the seeds are then distinct (node, time) pairs, and a node may repeat."""
 
-    def __init__(self, eids, seed_nodes, pos_src, pos_dst, neg_dst, k):
+    def __init__(self, eids, seed_nodes, pos_src, pos_dst, neg_dst, k, seed_times=None):
         self.eids, self.seed_nodes, self.pos_src, self.pos_dst, self.neg_dst, self.k = eids, seed_nodes, pos_src, pos_dst, neg_dst, k
+        self.seed_times = seed_times
         self._neg_src = None
 
     @property
@@ -1102,7 +1289,7 @@ class EdgeBatch(object):
 
     def tensors(self):
         """Every device tensor the batch holds (the loader's lifetime bookkeeping, as Block.tensors())."""
-        return [t for t in (self.eids, self.seed_nodes, self.pos_src, self.pos_dst, self.neg_dst, self._neg_src) if t is not None]
+        return [t for t in (self.eids, self.seed_nodes, self.pos_src, self.pos_dst, self.neg_dst, self._neg_src, self.seed_times) if t is not None]
 
 
 def edge_batch(g, eids, num_neg, seed=0, step=0):
@@ -1167,6 +1354,8 @@ class EdgePredictionSampler(object):
     and self.fanouts (the inner fan-outs and one more entry, 1 + k) as its fan_out."""
 
     def __init__(self, sampler, exclude=None, reverse_eids=None, negative_sampler=None):
+        if isinstance(sampler, TemporalNeighborSampler):
+            raise ValueError("EdgePredictionSampler: a TemporalNeighborSampler takes (node, time) seeds; wrap it in TemporalEdgePredictionSampler")
         if not isinstance(sampler, NeighborSampler) or isinstance(sampler, RandomWalkNeighborSampler) and exclude is not None:
             raise ValueError("EdgePredictionSampler wraps a NeighborSampler, LaborSampler or RelNeighborSampler; RandomWalkNeighborSampler has no "
                              "edge ids to exclude by")
@@ -1213,6 +1402,59 @@ class EdgePredictionSampler(object):
             ex = torch.sort(ex).values
             blocks = [b.exclude_edges(ex) for b in blocks]
         return input_nodes, batch, blocks
+
+
+class TemporalEdgePredictionSampler(object):
+    """Link-prediction minibatches on a graph with time (PyG's LinkNeighborLoader(edge_label_time=)): wraps a TemporalNeighborSampler,
+    same sample / sample_begin / sample_end / fanouts as EdgePredictionSampler.  Seed edge e is queried at t_e = its own timestamp: its
+    two endpoints and the destinations of its k uniform negatives (the edge_batch kernels, unchanged) become the pairs (node, t_e).
+    The distinct pairs -- ascending by time and then by node id -- are the inner sampler's seeds: batch.seed_nodes / batch.seed_times,
+    indexed by batch.pos_src / pos_dst / neg_dst.  No exclusion pass runs: with strict times (inclusive=False, required) the seed edge
+    and every edge not older than it are outside every block by construction."""
+
+    def __init__(self, sampler, negative_sampler=None):
+        if not isinstance(sampler, TemporalNeighborSampler):
+            raise ValueError("TemporalEdgePredictionSampler wraps a TemporalNeighborSampler")
+        if sampler.inclusive:
+            raise ValueError("TemporalEdgePredictionSampler needs inclusive=False: with ts <= t the seed edge itself would be eligible")
+        if negative_sampler is not None and not isinstance(negative_sampler, UniformNegativeSampler):
+            raise ValueError("negative_sampler: a UniformNegativeSampler, or None")
+        self.sampler = sampler
+        self.num_neg = negative_sampler.k if negative_sampler is not None else 0
+        self.fanouts = list(sampler.fanouts) + [1 + self.num_neg]   # EdgePredictionSampler's bound of the input nodes
+        self.bucket_by_owner = 0
+        self.stream_safe = sampler.stream_safe
+        self.completes_on_host = sampler.completes_on_host
+
+    def make_graph(self, indptr, indices, ndata=None, edata=None):
+        return CSCGraph(indptr, indices, ndata, edata)
+
+    def sample(self, g, eids, step=None):
+        """-> (input_nodes, EdgeBatch, blocks), blocks[0] the input layer; blocks[-1]'s destination items are the batch's seed pairs."""
+        return self.sample_end(self.sample_begin(g, eids, step))
+
+    def sample_begin(self, g, eids, step=None):
+        """Enqueue the edge batch and wait for its counts, make the distinct (node, t_e) pairs in plain torch, then enqueue the inner
+        sample over them.  -> the inner sampler's pending tuple, then the EdgeBatch."""
+        if isinstance(g, tuple):
+            g = CSCGraph(*g)
+        ts = g.edge_times(self.sampler.time)   # raises before any launch
+        st = self.sampler.step if step is None else int(step)
+        raw = edge_batch_wait(edge_batch(g, eids, self.num_neg, self.sampler.seed, st))
+        n, k = raw.eids.numel(), self.num_neg
+        t_e = ts[raw.eids]
+        at = torch.cat([raw.pos_src, raw.pos_dst, raw.neg_dst]).to(torch.int64)          # the items [src.. | dst.. | negatives..]
+        slot_time, slot = torch.unique(torch.cat([t_e, t_e, t_e.repeat_interleave(k)]), sorted=True, return_inverse=True)
+        bits = pair_code_bits(g.num_nodes, slot_time.numel())
+        pairs, where = torch.unique((slot << bits) | raw.seed_nodes[at], sorted=True, return_inverse=True)
+        where = where.to(torch.int32)
+        nodes, times = pairs & ((1 << bits) - 1), slot_time[pairs >> bits] if n else pairs
+        batch = EdgeBatch(raw.eids, nodes, where[:n], where[n: 2 * n], where[2 * n:], k, seed_times=times)
+        return self.sampler.sample_begin(g, nodes, step, seed_times=times) + (batch,)
+
+    def sample_end(self, pending):
+        input_nodes, _, blocks = self.sampler.sample_end(pending[:-1])
+        return input_nodes, pending[-1], blocks
 
 
 def as_edge_prediction_sampler(sampler, exclude=None, reverse_eids=None, reverse_etypes=None, negative_sampler=None, prefetch_labels=None):

@@ -139,6 +139,21 @@ def edge_types_by_source(indices, num_rels):
     return indices.to(torch.int64) % int(num_rels)
 
 
+def edge_times(indptr, seed=0, t_max=1 << 20):
+    """int64 [E] synthetic edge timestamps in CSC order for TemporalNeighborSampler: uniform over [0, t_max), seeded, and already
+    non-decreasing inside every row (the order sampler.sort_csc_by_time gives; the draws are independent of `indices`, so sorting the
+    times alone is sorting the edges).  Repeated timestamps inside a row are frequent once a row has more than sqrt(t_max) edges."""
+    if not 1 <= int(t_max) < (1 << 62):
+        raise ValueError("t_max must be in [1, 2^62)")
+    E = int(indptr[-1].item()) if indptr.numel() else 0
+    g = torch.Generator(device=indptr.device).manual_seed(int(seed))
+    ts = torch.randint(0, int(t_max), (E,), generator=g, device=indptr.device, dtype=torch.int64)
+    deg = indptr[1:] - indptr[:-1]
+    rows = torch.repeat_interleave(torch.arange(deg.numel(), device=indptr.device), deg, output_size=E)
+    by_time = torch.sort(ts, stable=True).indices
+    return ts[by_time[torch.sort(rows[by_time], stable=True).indices]]
+
+
 def community_csc(num_nodes, avg_degree, community=2048, p_in=0.9, seed=0, device="cuda", max_degree=None):
     """Seeded CSC graph with planted communities (blocks of `community` consecutive ids): an in-neighbour comes from the node's
     own block with probability p_in, from anywhere otherwise; in-degrees Pareto as in powerlaw_csc.  The power-law generator

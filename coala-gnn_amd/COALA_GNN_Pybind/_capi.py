@@ -139,7 +139,9 @@ SYMBOLS = {
                                         C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(SamplerBucketing), C.POINTER(_I64), _VP]),
     "coala_sampler_sample_layers_walk": (_I, [_VP, _VP, _I64, C.POINTER(C.c_int32), _I, _U64, _U64, C.POINTER(SamplerLayer), C.POINTER(SamplerWalk),
                                          C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(SamplerBucketing), C.POINTER(_I64), _VP]),
-    "coala_sampler_random_walk": (_I, [_VP, _VP, _I64, _I, _I, _U64, _U64, _U64, _I, _VP, _VP]),
+    "coala_sampler_sample_layers_temporal": (_I, [_VP, _VP, _I64, C.POINTER(C.c_int32), _I, _U64, _U64, C.POINTER(SamplerLayer), _VP, _VP, _I64,
+                                             _I, _I, C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _VP]),
+    "coala_sampler_random_walk":(_I, [_VP, _VP, _I64, _I, _I, _U64, _U64, _U64, _I, _VP, _VP]),
     "coala_block_weighted_sum": (_I, [_I, _VP, _VP, _VP, _VP, _I64, _I, _I, _VP]),
     "coala_block_weighted_sum_backward": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _VP]),
     "coala_block_weighted_sum_csr": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _I64, _I, _VP]),

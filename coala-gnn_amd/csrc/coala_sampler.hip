@@ -121,6 +121,30 @@
 //   a walk never scans a row, so there is no hub list and no ragged form.  scan_assign / relabel_clear / bucketing run unchanged:
 //   three launches per layer, no memset, no host wait.  coala_sampler_random_walk stores the traces of the same walks (walk_trace).
 //
+// Temporal layers (PyG's NeighborLoader(time_attr=, temporal_strategy='uniform' | 'last'), GraphBolt's temporal_sample_neighbors, TGN's
+// "most recent neighbours"; coala_sampler_sample_layers_temporal), fan-out f in 1..32.  The graph carries an int64 timestamp per edge in CSC
+// order, NON-DECREASING INSIDE EVERY ROW (the caller's duty; not verified here).  A destination item of a layer is a pair (v, t): node v
+// as of query time t (int64).
+//   * pair code: the n_slots distinct query times of a call sit in slot_time[n_slots], ascending; they never multiply, since a neighbour
+//     inherits the query time of the row that reached it.  The pair is the int64 code slot << node_bits | v, node_bits the bit length of
+//     num_nodes (so the value num_nodes fits the node field and names no node); the host refuses node_bits + bit_length(n_slots - 1) > 62.
+//     The kernel decodes a code and then checks it: a negative code, slot >= n_slots or v >= num_nodes give an empty row.  The
+//     destination's own hash insert follows the uniform rule: a negative code is not inserted, any other is, decoded or not;
+//   * eligible edges of (v, t): the prefix [indptr[v], indptr[v] + m) of the row, m = the number of the row's edges with ts < t (a lower
+//     bound; with `inclusive` ts <= t, an upper bound, PyG's rule).  Strict: an edge simultaneous with the query or later is out;
+//   * strategy uniform: m <= f takes the m eligible edges in CSC order, then -1; otherwise sample_insert_kernel's Floyd loop with deg := m,
+//     r(j) = splitmix64(key + j), key = sample_key(seed, step, layer, v) ^ splitmix64((uint64)t ^ kTemporalStream), kTemporalStream =
+//     0xBB67AE8584CAA73B, t_c = mulhi64(r(c), m - f + c + 1), duplicate resolution and slot order as there.  The draws depend on (seed,
+//     step, layer, v, t) only: not on the slot index, the batch, the grid or the order of the waves;
+//   * strategy last: the min(m, f) most recent eligible edges, positions m - min(m, f) .. m - 1 ascending, then -1; nothing is drawn;
+//   * the item of a slot is the code (the row's slot) << node_bits | indices[e], its edge id e (emit_fixed_slot); an indices[e] outside the
+//     graph (a broken CSC) leaves the slot empty.  Source list (of codes), first appearance, nbr_local, the item limit and its refusal are a
+//     uniform fixed layer's on codes; the destination codes of a call must be distinct, as seed nodes must be.  No owner bucketing (the
+//     owner of a code is not the owner of its node), no -1 layers, no weights.
+//   Launches: temporal_select<GS> replaces sample_insert (GS lanes per row find m by a GS-ary search over the timestamps, one ballot per
+//   step, about log_GS(deg) dependent loads: the row is never walked, so there is no hub list and no ragged form), then scan_assign /
+//   relabel_clear unchanged, which treat a key as opaque: three launches per layer, no memset, no host wait.
+//
 // Edge ids (coala_sampler_sample_layers_edge_ids), added to the contract of every layer kind above: with edge_ids_out[l] non-null the
 // kernel that reads a neighbour also stores where it read it, eid[slot] = indptr[v] + j (the edge's position in `indices`), int64,
 // laid out like the layer's nbr_local ([n_dst, f] or [E]); -1 where the slot holds no neighbour.  It is one 8-byte vector store from
@@ -327,6 +351,101 @@ __global__ __launch_bounds__(kBlock) void sample_insert_kernel(Graph g, const in
         int64_t p = -1;
         if (active && gl < fanout) { k = nb; p = n_dst + d * fanout + gl; }
         else if (active && gl == fanout) { k = v; p = d; }
+        if (p >= 0) hash_insert(tb, mask, k, p, slot_of_item);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- temporal layers
+constexpr uint64_t kTemporalStream = 0xBB67AE8584CAA73Bull; // hashed with the query time into sample_key: the temporal draws' own stream
+
+struct Temporal {
+    const int64_t* ts;        // [num_edges] edge timestamps in CSC order, non-decreasing inside every row
+    const int64_t* slot_time; // [n_slots] the distinct query times of the call, ascending
+    int64_t n_slots;
+    int node_bits;            // a pair is the code slot << node_bits | node
+    bool last, inclusive;     // strategy 'last'; ts <= t instead of ts < t
+};
+
+struct TimedRow { // destination item (v, t) of a temporal layer: Row's fields, and the row's time slot and query time
+    int64_t code, v;
+    bool ok;
+    int64_t start, deg, slot, t;
+};
+
+// Decode, then check: d >= n_dst, a negative code, a slot >= n_slots or a node >= num_nodes give an empty row.
+__device__ __forceinline__ TimedRow timed_row(const Graph& g, const Temporal& tp, const int64_t* __restrict__ dst, int64_t d, int64_t n_dst) {
+    const int64_t code = d < n_dst ? dst[d] : -1;
+    const int64_t slot = code >> tp.node_bits, v = code & ((1ll << tp.node_bits) - 1);
+    const bool ok = code >= 0 && slot < tp.n_slots && v < g.num_nodes;
+    const int64_t start = ok ? g.indptr[v] : 0;
+    return {code, v, ok, start, ok ? g.indptr[v + 1] - start : 0, slot, ok ? tp.slot_time[slot] : 0};
+}
+
+// Temporal fixed layer, in place of sample_insert_kernel: GS lanes (16/32/64 >= fanout + 1) per destination pair (v, t).  The group
+// finds m, the number of the row's edges with ts < t (<= t: inclusive), by a GS-ary search: the range [lo, hi) that holds the
+// boundary is cut into GS chunks of `step` positions, lane i probes the last position of chunk i, and one ballot counts the chunks
+// that lie wholly in front of the boundary -- a 10^6-edge row takes 4 steps at GS = 32, and the row is never walked.  Every probe is a
+// position of the row and lo <= hi <= deg whatever the timestamps hold, so unsorted times give a wrong m, never a read out of
+// bounds.  Then sample_insert_kernel's draw with deg := m (strategy last: the positions m - fanout + c, no draw), the same slots, the
+// same items and positions; a neighbour goes into the table as the code of (neighbour, the row's slot).
+template <int GS>
+__global__ __launch_bounds__(kBlock) void temporal_select_kernel(Graph g, Temporal tp, const int64_t* __restrict__ dst, const int64_t* __restrict__ n_dst_dev,
+                                                                 int64_t n_dst_value, int fanout, uint64_t seed, uint64_t step, int layer,
+                                                                 int64_t* __restrict__ nbr, Table tb, uint32_t* __restrict__ slot_of_item,
+                                                                 int64_t* __restrict__ eid) {
+    constexpr int GPW = 64 / GS;
+    const int64_t n_dst = layer_n_dst(n_dst_dev, n_dst_value);
+    const uint32_t mask = table_size(n_dst * (fanout + 1)) - 1;
+    const int lane = threadIdx.x & 63;
+    const auto [gl, gbase, gmask] = lane_group<GS>(lane);
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    for (int64_t d0 = wave * GPW; d0 < n_dst; d0 += n_waves * GPW) { // wave-uniform trip count: ballots below need every lane
+        const int64_t d = d0 + lane / GS;
+        const bool active = d < n_dst;
+        const TimedRow row = timed_row(g, tp, dst, d, n_dst);
+        const int64_t start = row.start, t = row.t;
+        int64_t lo = 0, hi = row.deg; // positions < lo are eligible, positions >= hi are not
+        while (__ballot(lo < hi)) {   // wave-uniform: a group that is done probes nothing and keeps lo == hi
+            const int64_t chunk = (hi - lo + GS - 1) / GS;
+            const int64_t first = lo + gl * chunk; // lane gl's chunk [first, first + chunk), cut off at hi
+            bool in = false;
+            if (first < hi) {
+                const int64_t x = tp.ts[start + min(first + chunk, hi) - 1];
+                in = tp.inclusive ? x <= t : x < t;
+            }
+            const int64_t k = __popcll(__ballot(in) & gmask); // chunks wholly eligible; chunk k holds the boundary
+            if (lo < hi) {
+                const int64_t nlo = min(lo + k * chunk, hi);
+                hi = min(nlo + chunk - 1, hi);
+                lo = nlo;
+            }
+        }
+        const int64_t m = lo;
+        // candidate of lane c = gl (Floyd step j = m - fanout + c), as sample_insert_kernel with deg := m
+        const uint64_t key = sample_key(seed, step, layer, (uint64_t)row.v) ^ splitmix64((uint64_t)t ^ kTemporalStream);
+        const bool draw = !tp.last && m > fanout;
+        const int64_t jmine = m - fanout + gl;
+        const int64_t tc0 = (draw && gl < fanout) ? (int64_t)__umul64hi(splitmix64(key + (uint64_t)gl), (uint64_t)(jmine + 1)) : -1;
+        int64_t chosen = -2;
+        if (__ballot(draw)) { // wave-uniform: strategy last draws nothing
+            for (int c = 0; c < fanout; ++c) {
+                const int64_t tc = __shfl(tc0, gbase + c);
+                const uint64_t dupm = __ballot(gl < c && chosen == tc) & gmask;
+                if (gl == c) chosen = dupm ? (m - fanout + c) : tc;
+            }
+        }
+        int64_t pick = -1;
+        if (gl < fanout) pick = (m <= fanout) ? (gl < m ? (int64_t)gl : -1) : (tp.last ? jmine : chosen);
+        const int64_t u = (row.ok && pick >= 0) ? g.indices[start + pick] : kEmpty;
+        // the slot's item is the code of (u, the row's slot); an id outside the graph (a broken CSC) has no code: the slot stays empty
+        const int64_t nb = (u >= 0 && u < g.num_nodes) ? (row.slot << tp.node_bits) | u : kEmpty;
+        if (active && gl < fanout) emit_fixed_slot(nbr, eid, d * fanout + gl, nb, start + pick);
+        // ---- hash insert: the neighbours' codes at positions n_dst + d*fanout + gl, the destination's own code at position d
+        int64_t k = kEmpty;
+        int64_t p = -1;
+        if (active && gl < fanout) { k = nb; p = n_dst + d * fanout + gl; }
+        else if (active && gl == fanout) { k = row.code; p = d; }
         if (p >= 0) hash_insert(tb, mask, k, p, slot_of_item);
     }
 }
@@ -1549,7 +1668,8 @@ struct Plan {
     const int32_t* etype;
     const coala_sampler_walk_t* walk;    // random-walk layers: every fixed layer of the call is one; null otherwise
     int32_t* const* visit_counts;        // walk layers: null, or per layer null or device int32[edge_cap], the visit count of every slot
-    RingInfo info;        // n_seeds, the fan-outs, n_parts and the caller's capacities
+    const Temporal* temporal;            // temporal layers: every layer of the call is one, and seeds / src_nodes hold pair codes; null otherwise
+    RingInfo info;       // n_seeds, the fan-outs, n_parts and the caller's capacities
     // layer l has at most dst_cap[l] dst nodes, items_cap[l] items (dst nodes + neighbour slots), nbr_cap[l] neighbour entries
     int64_t dst_cap[COALA_SAMPLER_MAX_LAYERS], items_cap[COALA_SAMPLER_MAX_LAYERS], nbr_cap[COALA_SAMPLER_MAX_LAYERS];
     uint64_t max_items, max_nbr;
@@ -1735,6 +1855,9 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
             const dim3 gs(grid1d(cap_l * GS, kBlock, 8192));
             if (p.walk)
                 launch_walk_select<GS>(s, p, l, gs, dst, n_dst_dev);
+            else if (p.temporal)
+                hipLaunchKernelGGL(temporal_select_kernel<GS>, gs, blk, 0, st, s->g, *p.temporal, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l,
+                                   s->nbr_global, s->tb, s->slot_of_item, eid);
             else if (p.weights)
                 hipLaunchKernelGGL(weighted_select_kernel<GS>, gs, blk, 0, st, s->g, p.weights, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l,
                                    s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap, eid);
@@ -1820,7 +1943,7 @@ int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const
                 const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
                 int64_t* ticket_out, void* stream, const float* weights, int64_t* const* edge_ids = nullptr, bool labor = false,
                 bool layer_dependency = false, const RelFan* rel = nullptr, const int32_t* etype = nullptr,
-                const coala_sampler_walk_t* walk = nullptr, int32_t* const* visit_counts = nullptr) {
+                const coala_sampler_walk_t* walk = nullptr, int32_t* const* visit_counts = nullptr, const Temporal* temporal = nullptr) {
     int rc;
     if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, layers, bucketing, labor, rel != nullptr))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1829,7 +1952,7 @@ int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const
     // first waits there for the previous call's last kernel
     if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
     s->last_stream = st;
-    Plan p{seeds, seed, step, layers, bucketing, weights, edge_ids, st, layer_dependency, rel, etype, walk, visit_counts};
+    Plan p{seeds, seed, step, layers, bucketing, weights, edge_ids, st, layer_dependency, rel, etype, walk, visit_counts, temporal};
     if ((rc = plan_call(p, n_seeds, fanouts, n_layers, bucketing ? bucketing->n_parts : 0, labor))) return rc;
     if ((rc = grow_workspace(s, p))) return rc;
     const uint64_t ticket = s->calls;
@@ -2077,6 +2200,31 @@ int coala_sampler_sample_layers_walk(coala_sampler_t* s, const int64_t* seeds, i
     }
     return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream, nullptr,
                        nullptr, false, false, nullptr, nullptr, walk, visit_counts_out);
+}
+
+int coala_sampler_sample_layers_temporal(coala_sampler_t* s, const int64_t* seed_codes, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                         uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const int64_t* edge_ts,
+                                         const int64_t* slot_time, int64_t n_slots, int strategy, int inclusive, int64_t* const* edge_ids_out,
+                                         int64_t* n_src_host, int64_t* n_edges_host, int64_t* ticket_out, void* stream) {
+    if (!fanouts || !layers) return fail(COALA_EINVAL, "null argument");
+    if (!edge_ts) return fail(COALA_EINVAL, "null edge_ts");
+    if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
+    if (strategy != 0 && strategy != 1) return fail(COALA_EINVAL, "strategy %d: 0 (uniform) or 1 (last)", strategy);
+    if (n_slots < 0 || (n_slots > 0 && !slot_time)) return fail(COALA_EINVAL, "slot_time: %lld query times and a null table", (long long)n_slots);
+    for (int l = 0; l < n_layers; ++l) {
+        if (fanouts[l] < 1 || fanouts[l] > 32) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (a temporal layer has a fixed fan-out)", fanouts[l]);
+        if (layers[l].indptr_local) return fail(COALA_EINVAL, "layer %d: a temporal layer is fixed-stride, indptr_local must be NULL", l);
+    }
+    if (!s) return fail(COALA_EINVAL, "null argument");
+    int node_bits = 0, slot_bits = 0; // bit lengths of num_nodes and of n_slots - 1
+    while ((s->g.num_nodes >> node_bits) != 0) ++node_bits;
+    while (n_slots > 1 && ((n_slots - 1) >> slot_bits) != 0) ++slot_bits;
+    if (node_bits + slot_bits > 62)
+        return fail(COALA_EINVAL, "%lld query times on a graph of %lld nodes: a (node, time) pair takes %d + %d bits, over the 62 of a code",
+                    (long long)n_slots, (long long)s->g.num_nodes, node_bits, slot_bits);
+    const Temporal tp{edge_ts, slot_time, n_slots, node_bits, strategy == 1, inclusive != 0};
+    return sample_impl(s, seed_codes, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, nullptr, ticket_out, stream, nullptr,
+                       edge_ids_out, false, false, nullptr, nullptr, nullptr, nullptr, &tp);
 }
 
 int coala_sampler_random_walk(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t term_threshold,

@@ -17,6 +17,8 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --model_type hgt --num_heads 4 --num_rels 4 --num_ntypes 3
   python examples/train_synthetic.py --sampler pinsage --model_type pinsage --num_traversals 2 --termination_prob 0.5 --num_random_walks 10
   python examples/train_synthetic.py --task link --num_negs 5 --exclude reverse_id
+  python examples/train_synthetic.py --sampler temporal --temporal_strategy last --time_decay 0.001
+  python examples/train_synthetic.py --task link --sampler temporal --num_negs 5
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -36,8 +38,21 @@ from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, 
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
 from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, GATv2, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
 from COALA_GNN.sampler import (EdgePredictionSampler, LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler,  # noqa: E402
-                               UniformNegativeSampler, reverse_edge_ids, sort_csc_by_etype)
-from COALA_GNN.synthetic import alloc_pinned_table, edge_types_by_source, powerlaw_csc, symmetrize_csc  # noqa: E402
+                               TemporalEdgePredictionSampler, TemporalNeighborSampler, UniformNegativeSampler, reverse_edge_ids,
+                               sort_csc_by_etype)
+from COALA_GNN.synthetic import alloc_pinned_table, edge_times, edge_types_by_source, powerlaw_csc, symmetrize_csc  # noqa: E402
+
+T_MAX = 1 << 20    # --sampler temporal: synthetic edge timestamps lie in [0, T_MAX)
+DECAY = "decay"    # --time_decay: the edata key the gcn / sage layers read their edge weights from
+
+
+def add_time_decay(blocks, lam):
+    """--time_decay LAMBDA: block.edata['decay'] = exp(-LAMBDA * dt) for every sampled edge (dt: the row's query time minus the edge's
+    timestamp, made by TemporalNeighborSampler; padding slots are not read), the weights of the layers' edge_weight= path."""
+    if lam is not None:
+        for b in blocks:
+            b.edata[DECAY] = torch.exp(-lam * b.edata["dt"].to(torch.float32))
+    return blocks
 
 
 def train_link(args, comm, device, indptr, indices, feat, files, fan_out):
@@ -47,10 +62,16 @@ def train_link(args, comm, device, indptr, indices, feat, files, fan_out):
     if args.exclude == "reverse_id":   # the reverse map needs a symmetric simple graph
         indptr, indices = symmetrize_csc(indptr, indices)
         rev = reverse_edge_ids(indptr, indices)
-    cls = LaborSampler if args.sampler == "labor" else NeighborSampler
-    sampler = EdgePredictionSampler(cls(fan_out), exclude=None if args.exclude == "none" else args.exclude, reverse_eids=rev,
-                                    negative_sampler=UniformNegativeSampler(args.num_negs))
-    g = sampler.make_graph(indptr, indices)
+    edata = {}
+    if args.sampler == "temporal":   # every seed edge is queried at its own timestamp: strict times keep it, and all later edges, out
+        edata = {"ts": edge_times(indptr, seed=1, t_max=T_MAX)}
+        sampler = TemporalEdgePredictionSampler(TemporalNeighborSampler(fan_out, strategy=args.temporal_strategy),
+                                                negative_sampler=UniformNegativeSampler(args.num_negs))
+    else:
+        cls = LaborSampler if args.sampler == "labor" else NeighborSampler
+        sampler = EdgePredictionSampler(cls(fan_out), exclude=None if args.exclude == "none" else args.exclude, reverse_eids=rev,
+                                        negative_sampler=UniformNegativeSampler(args.num_negs))
+    g = sampler.make_graph(indptr, indices, edata=edata)
     n_train = int(0.6 * indices.numel()) if args.num_train_edges is None else min(args.num_train_edges, indices.numel())
     train_eids = torch.randperm(indices.numel(), generator=torch.Generator().manual_seed(0))[:n_train]
     nd = Node_Distributor(comm, train_eids, args.batch_size, *files, parsing_method="baseline")   # the items are edge ids: no colour routing
@@ -62,7 +83,8 @@ def train_link(args, comm, device, indptr, indices, feat, files, fan_out):
     if args.model_type == "gat":
         encoder = GAT(args.dim, args.hidden_channels, args.hidden_channels, len(fan_out), args.num_heads)
     else:
-        encoder = SAGE(args.dim, args.hidden_channels, args.hidden_channels, len(fan_out), args.sage_aggregator)
+        encoder = SAGE(args.dim, args.hidden_channels, args.hidden_channels, len(fan_out), args.sage_aggregator,
+                       edge_weight=None if args.time_decay is None else DECAY)
     model = LinkPredictor(encoder).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=args.learning_rate)
     count = 0
@@ -74,7 +96,7 @@ def train_link(args, comm, device, indptr, indices, feat, files, fan_out):
             if step % 100 == 0:
                 print(f"Rank: {comm.local_rank} step: {step}")
             count += 1
-            pos_score, neg_score = model(blocks, fetch_feature, batch)
+            pos_score, neg_score = model(add_time_decay(blocks, args.time_decay), fetch_feature, batch)
             loss = link_loss(pos_score, neg_score)
             optimizer.zero_grad()
             loss.backward()
@@ -99,11 +121,18 @@ def main():
     ap.add_argument("--fan_out", type=str, default="5,5")
     ap.add_argument("--eval_fan_out", type=str, default=None,
                     help="fan-outs of the evaluation loader (default: --fan_out); -1 takes every in-edge, e.g. -1,-1 for full neighbourhoods")
-    ap.add_argument("--sampler", type=str, default="neighbor", choices=["neighbor", "labor", "rel", "pinsage"],
+    ap.add_argument("--sampler", type=str, default="neighbor", choices=["neighbor", "labor", "rel", "pinsage", "temporal"],
                     help="labor: layer-neighbour sampling (LaborSampler) -- the same expected fan-out per node, fewer input nodes to fetch; "
                          "rel: a fan-out per edge type (RelNeighborSampler, --rel_fan_out; needs --model_type rgcn, rgat, rsage or hgt); "
                          "pinsage: the --fan_out most visited nodes of short random walks, with their visit counts as edge weights "
-                         "(RandomWalkNeighborSampler; --num_traversals, --termination_prob, --num_random_walks)")
+                         "(RandomWalkNeighborSampler; --num_traversals, --termination_prob, --num_random_walks); "
+                         "temporal: synthetic edge timestamps and a query time per seed node, a row samples only among its edges older than "
+                         "its query time (TemporalNeighborSampler; --temporal_strategy, --time_decay)")
+    ap.add_argument("--temporal_strategy", type=str, default="uniform", choices=["uniform", "last"],
+                    help="with --sampler temporal: draw the fan-out uniformly among the eligible edges, or take the most recent ones")
+    ap.add_argument("--time_decay", type=float, default=None,
+                    help="with --sampler temporal: LAMBDA; the gcn / sage layers weigh every message by exp(-LAMBDA * dt), dt = the row's query "
+                         "time minus the edge's timestamp (block.edata['dt']), through their edge_weight= path")
     ap.add_argument("--num_traversals", type=int, default=2, help="with --sampler pinsage: hops per walk (1..16)")
     ap.add_argument("--termination_prob", type=float, default=0.5, help="with --sampler pinsage: a hop after the first ends the walk with this probability")
     ap.add_argument("--num_random_walks", type=int, default=10, help="with --sampler pinsage: walks per node (1..64)")
@@ -194,6 +223,12 @@ def main():
         ap.error("--num_ntypes must be at least 1")
     if (args.model_type == "pinsage") != (args.sampler == "pinsage"):
         ap.error("--model_type pinsage and --sampler pinsage go together: the model reads the visit counts the sampler puts on its blocks")
+    if args.sampler == "temporal" and (args.edge_weights != "none" or args.layer_dependency or eval_fan_out != fan_out or args.path
+                                       or any(f < 1 for f in fan_out)):
+        ap.error("--sampler temporal runs on the synthetic graph with fan-outs of 1..32 and takes neither --edge_weights, --layer_dependency "
+                 "nor --eval_fan_out")
+    if args.time_decay is not None and (args.sampler != "temporal" or args.model_type not in ("sage", "gcn")):
+        ap.error("--time_decay needs --sampler temporal and --model_type sage or gcn")
     if args.sampler == "pinsage" and (args.edge_weights != "none" or args.layer_dependency or eval_fan_out != fan_out):
         ap.error("--sampler pinsage takes neither --edge_weights, --layer_dependency nor --eval_fan_out")
 
@@ -229,8 +264,11 @@ def main():
     files = [os.path.join(tmp, f) for f in ("color.npy", "topk.npy", "score.npy")]
 
     if args.task == "link":
-        if args.path or args.sampler not in ("neighbor", "labor") or args.model_type not in ("sage", "gat") or args.edge_weights != "none":
-            ap.error("--task link runs on the synthetic graph with --sampler neighbor | labor and --model_type sage | gat, without --edge_weights")
+        if args.path or args.sampler not in ("neighbor", "labor", "temporal") or args.model_type not in ("sage", "gat") or args.edge_weights != "none":
+            ap.error("--task link runs on the synthetic graph with --sampler neighbor | labor | temporal and --model_type sage | gat, without "
+                     "--edge_weights")
+        if args.sampler == "temporal" and args.exclude == "reverse_id":
+            ap.error("--sampler temporal needs no exclusion pass (strict times leave the seed edges out): drop --exclude reverse_id")
         return train_link(args, comm, device, indptr, indices, feat, files, fan_out)
     train_nid = train_ids[torch.randperm(n_train, generator=torch.Generator().manual_seed(0))]               # :62-65
     nd = Node_Distributor(comm, train_nid, args.batch_size, *files, parsing_method=args.distribution)      # :68
@@ -243,6 +281,12 @@ def main():
     if args.use_edge_weight and prob is None:
         ap.error("--use_edge_weight needs --edge_weights random")
     ew = "w" if args.use_edge_weight and args.model_type not in ("gat", "gatv2", "gin", "rgcn", "rgat", "rsage", "hgt") else None
+    ndata = {"labels": labels}
+    if args.sampler == "temporal":   # a timestamp per edge (sorted inside every row) and a query time per node, which the sampler reads as seed_time
+        edata = dict(edata, ts=edge_times(indptr, seed=1, t_max=T_MAX))
+        ndata["t"] = T_MAX // 4 + (torch.arange(args.nodes, device=device) * 7919) % (3 * T_MAX // 4)
+        if args.time_decay is not None:
+            ew = DECAY
     typed = args.model_type in ("rgcn", "rgat", "rsage", "hgt")   # the models on typed edges
     if typed:   # the edge types of a homogenised heterograph, in CSC order; the blocks find theirs through their edge ids
         if not 1 <= args.num_rels <= 64:
@@ -259,11 +303,13 @@ def main():
         sampler = RelNeighborSampler(rel_fan_out, args.num_rels)
     elif args.sampler == "pinsage":
         sampler = RandomWalkNeighborSampler(fan_out, args.num_traversals, args.termination_prob, args.num_random_walks)
+    elif args.sampler == "temporal":
+        sampler = TemporalNeighborSampler(fan_out, strategy=args.temporal_strategy, seed_time="t", edge_ids=edge_ids or ew is not None)
     else:
         if args.layer_dependency:
             ap.error("--layer_dependency needs --sampler labor")
         sampler = NeighborSampler(fan_out, prob=prob, edge_ids=edge_ids)                            # :70-72
-    g = sampler.make_graph(indptr, indices, ndata={"labels": labels}, edata=edata)
+    g = sampler.make_graph(indptr, indices, ndata=ndata, edata=edata)
     train_loader = COALA_GNN_DataLoader(SSD_INFO(1, args.dim * 4, 1024, 0), nd, g, sampler, args.batch_size, args.dim, fan_out,
                                         args.cache_size, device, refresh_counter=args.refresh_counter,
                                         cache_backend=args.cache_backend, sim_buf=feat, shuffle=False, num_rows=args.nodes,
@@ -311,7 +357,7 @@ def main():
                 print(f"Rank: {comm.local_rank} step: {step}")
             count += 1
             batch_labels = blocks[-1].dstdata["labels"]
-            blocks = [block.int().to(device) for block in blocks]
+            blocks = add_time_decay([block.int().to(device) for block in blocks], args.time_decay)
             batch_labels = batch_labels.view(-1).to(device)
             batch_pred = model(blocks, fetch_feature)
             loss = loss_fcn(batch_pred, batch_labels)
@@ -342,7 +388,7 @@ def main():
         for step, (input_nodes, seeds, blocks, fetch_feature) in enumerate(test_loader):
             if step % 100 == 0:
                 print("Eval step: ", step)
-            blocks = [block.to(device) for block in blocks]
+            blocks = add_time_decay([block.to(device) for block in blocks], args.time_decay)
             batch_labels = blocks[-1].dstdata["labels"].view(-1)
             pred = model(blocks, fetch_feature).argmax(1)
             correct += int((pred == batch_labels).sum())

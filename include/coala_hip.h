@@ -476,6 +476,25 @@ int coala_sampler_sample_layers_walk(coala_sampler_t* s, const int64_t* seeds, i
  * step and term_threshold: repeated start nodes get identical traces.  One kernel on `stream`; nothing is waited for. */
 int coala_sampler_random_walk(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t term_threshold,
                               uint64_t seed, uint64_t step, int layer, int64_t* traces_out, void* stream);
+/* Temporal layers (PyG's NeighborLoader(time_attr=, temporal_strategy=), GraphBolt's temporal_sample_neighbors): as
+ * coala_sampler_sample_layers_edge_ids without bucketing, but a destination item is a pair (node v, query time t) and a row draws only
+ * from the edges with a timestamp before t.  edge_ts: device int64[num_edges] in CSC order, non-decreasing inside every row (the
+ * caller's duty).  slot_time: device int64[n_slots], the distinct query times of the call, ascending.  A pair is the int64 code
+ * slot << node_bits | v, node_bits the bit length of num_nodes; seed_codes (device int64[n_seeds], distinct) and every layer's src_nodes
+ * hold such codes: a neighbour inherits its row's slot.  A code that is negative, or decodes to slot >= n_slots or v >= num_nodes, gives
+ * an empty row.  Eligible edges of (v, t): the prefix of the row with ts < t (inclusive != 0: ts <= t), m edges, found by a search.
+ * strategy 0 (uniform): all of them when m <= fanout, else fanout distinct ones by the uniform layer's draw with deg := m on a stream
+ * keyed by (seed, step, layer, v, t) -- not by the slot, the batch or the grid; strategy 1 (last): the min(m, fanout) most recent, in
+ * ascending position, nothing drawn.  The exact rule is in the header of coala_sampler.hip.  Every layer is fixed-stride (fan-out 1..32,
+ * indptr_local NULL); capacities, the source-list rule, edge_ids_out and the ticket / wait protocol are a uniform fixed layer's, counts
+ * come back through coala_sampler_wait_layers, and the call leaves the hash table cleared for any call that follows on the handle.
+ * COALA_EINVAL (with a message) before any launch for a fan-out outside 1..32, a strategy outside 0..1, a NULL edge_ts or slot_time, or
+ * node_bits + bit_length(n_slots - 1) > 62.  One launch stands where a uniform layer's sample_insert stands; nothing is added. */
+int coala_sampler_sample_layers_temporal(coala_sampler_t* s, const int64_t* seed_codes, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                         uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const int64_t* edge_ts,
+                                         const int64_t* slot_time, int64_t n_slots, int strategy /* 0 uniform, 1 last */, int inclusive,
+                                         int64_t* const* edge_ids_out /* nullable */, int64_t* n_src_host, int64_t* n_edges_host,
+                                         int64_t* ticket, void* stream);
 /* Counts of an earlier call, with the edge counts of its layers; returns the device-side refusal of a full, LABOR or relation layer, if any. */
 int coala_sampler_wait_layers(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host);
 /* Edge minibatches for link prediction (DGL's as_edge_prediction_sampler with negative_sampler.Uniform(num_neg)).  eids: device
