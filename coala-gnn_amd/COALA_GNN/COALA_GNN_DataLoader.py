@@ -265,8 +265,9 @@ class COALA_GNN_DataLoader(torch.utils.data.DataLoader):
         with torch.cuda.stream(self._sample_stream):
             pending = self.sampler.sample_begin(self.g, seeds.to(self.device))
             xch = self.COALA_GNN_Manager.exchange
-            if self.counts_ahead and pending[6] is not None and hasattr(xch, "counts_begin"):
-                ticket = xch.counts_begin(pending[6][1].data_ptr())   # the owner counts the sampler just produced (device)
+            owner_counts = getattr(pending, "owner_counts", None)   # None too for a foreign sampler, whose sample_begin returns what it likes
+            if self.counts_ahead and owner_counts is not None and hasattr(xch, "counts_begin"):
+                ticket = xch.counts_begin(owner_counts.data_ptr())   # the owner counts the sampler just produced (device)
             ev = torch.cuda.Event()
             ev.record()
         return pending, ev, ticket

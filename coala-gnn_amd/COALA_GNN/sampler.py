@@ -25,42 +25,61 @@ EID = "_ID"   # DGL's dgl.EID: block.edata[EID] is the position of every sampled
 ITEM_LIMIT = 8192 * 1024   # items (destination nodes + neighbour slots) one layer may hold (coala_sampler.hip: kMaxTiles * kTile)
 
 
+def _is_int_tensor(t):
+    return isinstance(t, torch.Tensor) and not (t.is_floating_point() or t.is_complex() or t.dtype == torch.bool)
+
+
+def _as_graph(g):
+    return CSCGraph(*g) if isinstance(g, tuple) else g
+
+
+def _sort_csc_by_key(indptr, indices, key, what):
+    """sort_csc_by_etype / sort_csc_by_time: a stable sort of every row's in-edges by an integer key, `what` its name in the messages."""
+    if key.dim() != 1 or key.numel() != indices.numel():
+        raise ValueError(f"edge {what} must have shape ({indices.numel()},) in CSC order, got {tuple(key.shape)}")
+    if not _is_int_tensor(key):
+        raise ValueError(f"edge {what} must be an integer tensor")
+    deg = indptr[1:] - indptr[:-1]
+    rows = torch.repeat_interleave(torch.arange(deg.numel(), device=indptr.device), deg, output_size=indices.numel())
+    by_key = torch.sort(key.to(indptr.device), stable=True).indices
+    perm = by_key[torch.sort(rows[by_key], stable=True).indices]
+    return indices[perm], key[perm], perm
+
+
+def _check_sorted_in_rows(indptr, key, name, what, int_note, sort_call, num_rels=None):
+    """check_etype_sorted / check_time_sorted: an integer tensor of num_edges values (in [0, num_rels) when given), non-decreasing inside
+    every row of the CSC.  `what`, `int_note` and `sort_call` are the caller's words in the messages."""
+    E = int(indptr[-1].item()) if indptr.numel() else 0
+    if not _is_int_tensor(key):
+        raise ValueError(f"edata[{name!r}]: edge {what} must be an integer tensor{int_note}")
+    if key.dim() != 1 or key.numel() != E:
+        raise ValueError(f"edata[{name!r}]: edge {what} must have shape ({E},) in CSC order, got {tuple(key.shape)}")
+    if E == 0:
+        return
+    t = key.to(indptr.device)
+    if num_rels is not None and bool(((t < 0) | (t >= num_rels)).any()):
+        raise ValueError(f"edata[{name!r}]: edge {what} must lie in [0, {num_rels}) (num_rels={num_rels})")
+    drop = t[1:] < t[:-1]                                  # drop[p - 1]: the key falls from position p - 1 to p
+    starts = indptr[1:-1]
+    starts = starts[(starts > 0) & (starts < E)]           # ... which it may where a row starts
+    drop[starts - 1] = False
+    if bool(drop.any()):
+        raise ValueError(f"edata[{name!r}]: edge {what} must be non-decreasing inside every row of the CSC; sort the graph with "
+                         f"COALA_GNN.sampler.{sort_call}")
+
+
 def sort_csc_by_etype(indptr, indices, etype):
     """Sort the in-edges of every node by edge type, DGL's dgl.sort_csc_by_tag: -> (indices_sorted, etype_sorted, perm).  Stable by
     (row, type): edges of one type keep their CSC order.  perm (int64 [E]) maps new positions to old, indices_sorted = indices[perm],
     so any other per-edge data is carried along as edata[key][perm].  Plain torch on the tensors' device; indptr is unchanged.
     RelNeighborSampler needs a graph in this order."""
-    if etype.dim() != 1 or etype.numel() != indices.numel():
-        raise ValueError(f"edge types must have shape ({indices.numel()},) in CSC order, got {tuple(etype.shape)}")
-    if etype.is_floating_point() or etype.is_complex() or etype.dtype == torch.bool:
-        raise ValueError("edge types must be an integer tensor")
-    deg = indptr[1:] - indptr[:-1]
-    rows = torch.repeat_interleave(torch.arange(deg.numel(), device=indptr.device), deg, output_size=indices.numel())
-    by_type = torch.sort(etype.to(indptr.device), stable=True).indices
-    perm = by_type[torch.sort(rows[by_type], stable=True).indices]
-    return indices[perm], etype[perm], perm
+    return _sort_csc_by_key(indptr, indices, etype, "types")
 
 
 def check_etype_sorted(indptr, etype, num_rels, name="etype"):
     """What RelNeighborSampler asks of a graph's edge types, on the tensors' device: an integer tensor of num_edges values in
     [0, num_rels), non-decreasing inside every row of the CSC.  ValueError (naming sort_csc_by_etype) otherwise."""
-    E = int(indptr[-1].item()) if indptr.numel() else 0
-    if not isinstance(etype, torch.Tensor) or etype.is_floating_point() or etype.is_complex() or etype.dtype == torch.bool:
-        raise ValueError(f"edata[{name!r}]: edge types must be an integer tensor")
-    if etype.dim() != 1 or etype.numel() != E:
-        raise ValueError(f"edata[{name!r}]: edge types must have shape ({E},) in CSC order, got {tuple(etype.shape)}")
-    if E == 0:
-        return
-    t = etype.to(indptr.device)
-    if bool(((t < 0) | (t >= num_rels)).any()):
-        raise ValueError(f"edata[{name!r}]: edge types must lie in [0, {num_rels}) (num_rels={num_rels})")
-    drop = t[1:] < t[:-1]                                  # drop[p - 1]: the type falls from position p - 1 to p
-    starts = indptr[1:-1]
-    starts = starts[(starts > 0) & (starts < E)]           # ... which it may where a row starts
-    drop[starts - 1] = False
-    if bool(drop.any()):
-        raise ValueError(f"edata[{name!r}]: edge types must be non-decreasing inside every row of the CSC; sort the graph with "
-                         f"COALA_GNN.sampler.sort_csc_by_etype(indptr, indices, etype)")
+    _check_sorted_in_rows(indptr, etype, name, "types", "", "sort_csc_by_etype(indptr, indices, etype)", num_rels)
 
 
 def sort_csc_by_time(indptr, indices, ts):
@@ -68,35 +87,13 @@ def sort_csc_by_time(indptr, indices, ts):
     (row, time): simultaneous edges keep their CSC order.  perm (int64 [E]) maps new positions to old, indices_sorted = indices[perm],
     so any other per-edge data is carried along as edata[key][perm].  Plain torch on the tensors' device; indptr is unchanged.
     TemporalNeighborSampler needs a graph in this order."""
-    if ts.dim() != 1 or ts.numel() != indices.numel():
-        raise ValueError(f"edge times must have shape ({indices.numel()},) in CSC order, got {tuple(ts.shape)}")
-    if ts.is_floating_point() or ts.is_complex() or ts.dtype == torch.bool:
-        raise ValueError("edge times must be an integer tensor")
-    deg = indptr[1:] - indptr[:-1]
-    rows = torch.repeat_interleave(torch.arange(deg.numel(), device=indptr.device), deg, output_size=indices.numel())
-    by_time = torch.sort(ts.to(indptr.device), stable=True).indices
-    perm = by_time[torch.sort(rows[by_time], stable=True).indices]
-    return indices[perm], ts[perm], perm
+    return _sort_csc_by_key(indptr, indices, ts, "times")
 
 
 def check_time_sorted(indptr, ts, name="ts"):
     """What TemporalNeighborSampler asks of a graph's edge timestamps, on the tensors' device: an integer tensor of num_edges values,
     non-decreasing inside every row of the CSC.  ValueError (naming sort_csc_by_time) otherwise."""
-    E = int(indptr[-1].item()) if indptr.numel() else 0
-    if not isinstance(ts, torch.Tensor) or ts.is_floating_point() or ts.is_complex() or ts.dtype == torch.bool:
-        raise ValueError(f"edata[{name!r}]: edge times must be an integer tensor (floating-point timestamps are not supported)")
-    if ts.dim() != 1 or ts.numel() != E:
-        raise ValueError(f"edata[{name!r}]: edge times must have shape ({E},) in CSC order, got {tuple(ts.shape)}")
-    if E == 0:
-        return
-    t = ts.to(indptr.device)
-    drop = t[1:] < t[:-1]                                  # drop[p - 1]: the time falls from position p - 1 to p
-    starts = indptr[1:-1]
-    starts = starts[(starts > 0) & (starts < E)]           # ... which it may where a row starts
-    drop[starts - 1] = False
-    if bool(drop.any()):
-        raise ValueError(f"edata[{name!r}]: edge times must be non-decreasing inside every row of the CSC; sort the graph with "
-                         f"COALA_GNN.sampler.sort_csc_by_time(indptr, indices, ts)")
+    _check_sorted_in_rows(indptr, ts, name, "times", " (floating-point timestamps are not supported)", "sort_csc_by_time(indptr, indices, ts)")
 
 
 class CSCGraph(object):
@@ -112,9 +109,7 @@ class CSCGraph(object):
         self.device = self.indptr.device
         self.ndata = dict(ndata or {})
         self.edata = dict(edata or {})
-        self._weights = {}   # edata key -> (the entry, its version, the validated fp32 device copy)
-        self._etypes = {}    # edata key -> (the entry, its version, num_rels, the validated int32 device copy)
-        self._etimes = {}    # edata key -> (the entry, its version, the validated int64 device copy)
+        self._weights, self._etypes, self._etimes = {}, {}, {}   # edata key -> (the entry, its version, num_rels or None, the validated device copy): _edata
         self._max_in_degree = None
         self._h = C.c_void_p()
         dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
@@ -128,54 +123,50 @@ class CSCGraph(object):
             self._max_in_degree = int((self.indptr[1:] - self.indptr[:-1]).max().item()) if self.num_nodes > 0 else 0
         return self._max_in_degree
 
+    def _edata(self, cache, key, role, make, tag=None):
+        """edata[key] through `make` (validate, then the device copy the kernels read), kept in `cache` until the entry is replaced or
+        modified in place or `tag` changes.  `role` names the sampler argument in the KeyError of a missing key."""
+        if key not in self.edata:
+            raise KeyError(f"edata has no {key!r}: the edge {role}={key!r}) (keys: {sorted(self.edata)})")
+        t = self.edata[key]
+        hit = cache.get(key)
+        if hit is not None and hit[0] is t and hit[1] == t._version and hit[2] == tag:
+            return hit[3]
+        v = make(t)
+        cache[key] = (t, t._version, tag, v)
+        return v
+
     def edge_weights(self, key):
         """edata[key] as a contiguous fp32 tensor on the graph's device, validated once (num_edges values, finite, >= 0) and cached
         until the entry is replaced or modified in place.  KeyError when the key is missing, ValueError (naming it) when bad."""
-        if key not in self.edata:
-            raise KeyError(f"edata has no {key!r}: the edge weights of NeighborSampler(prob={key!r}) (keys: {sorted(self.edata)})")
-        t = self.edata[key]
-        hit = self._weights.get(key)
-        if hit is not None and hit[0] is t and hit[1] == t._version:
-            return hit[2]
-        if not isinstance(t, torch.Tensor) or t.is_complex():
-            raise ValueError(f"edata[{key!r}]: edge weights must be a real tensor")
-        if t.dim() != 1 or t.numel() != self.num_edges:
-            raise ValueError(f"edata[{key!r}]: edge weights must have shape ({self.num_edges},) in CSC order, got {tuple(t.shape)}")
-        w = t.to(device=self.device, dtype=torch.float32).contiguous()
-        if w.numel() and bool((~torch.isfinite(w) | (w < 0)).any()):
-            raise ValueError(f"edata[{key!r}]: edge weights must be finite and >= 0 (as fp32)")
-        self._weights[key] = (t, t._version, w)
-        return w
+        def make(t):
+            if not isinstance(t, torch.Tensor) or t.is_complex():
+                raise ValueError(f"edata[{key!r}]: edge weights must be a real tensor")
+            if t.dim() != 1 or t.numel() != self.num_edges:
+                raise ValueError(f"edata[{key!r}]: edge weights must have shape ({self.num_edges},) in CSC order, got {tuple(t.shape)}")
+            w = t.to(device=self.device, dtype=torch.float32).contiguous()
+            if w.numel() and bool((~torch.isfinite(w) | (w < 0)).any()):
+                raise ValueError(f"edata[{key!r}]: edge weights must be finite and >= 0 (as fp32)")
+            return w
+        return self._edata(self._weights, key, "weights of NeighborSampler(prob", make)
 
     def edge_types(self, key, num_rels):
         """edata[key] as a contiguous int32 tensor on the graph's device for RelNeighborSampler, checked once on the device
         (check_etype_sorted: num_edges values in [0, num_rels), non-decreasing inside every row) and cached until the entry is replaced or
         modified in place, or close().  KeyError when the key is missing, ValueError (naming sort_csc_by_etype) when bad."""
-        if key not in self.edata:
-            raise KeyError(f"edata has no {key!r}: the edge types of RelNeighborSampler(etype={key!r}) (keys: {sorted(self.edata)})")
-        t = self.edata[key]
-        hit = self._etypes.get(key)
-        if hit is not None and hit[0] is t and hit[1] == t._version and hit[2] == num_rels:
-            return hit[3]
-        check_etype_sorted(self.indptr, t, num_rels, key)
-        t32 = t.to(device=self.device, dtype=torch.int32).contiguous()
-        self._etypes[key] = (t, t._version, num_rels, t32)
-        return t32
+        def make(t):
+            check_etype_sorted(self.indptr, t, num_rels, key)
+            return t.to(device=self.device, dtype=torch.int32).contiguous()
+        return self._edata(self._etypes, key, "types of RelNeighborSampler(etype", make, num_rels)
 
     def edge_times(self, key):
         """edata[key] as a contiguous int64 tensor on the graph's device for TemporalNeighborSampler, checked once on the device
         (check_time_sorted: an integer tensor of num_edges values, non-decreasing inside every row) and cached until the entry is
         replaced or modified in place, or close().  KeyError when the key is missing, ValueError (naming sort_csc_by_time) when bad."""
-        if key not in self.edata:
-            raise KeyError(f"edata has no {key!r}: the edge times of TemporalNeighborSampler(time={key!r}) (keys: {sorted(self.edata)})")
-        t = self.edata[key]
-        hit = self._etimes.get(key)
-        if hit is not None and hit[0] is t and hit[1] == t._version:
-            return hit[2]
-        check_time_sorted(self.indptr, t, key)
-        t64 = t.to(device=self.device, dtype=torch.int64).contiguous()
-        self._etimes[key] = (t, t._version, t64)
-        return t64
+        def make(t):
+            check_time_sorted(self.indptr, t, key)
+            return t.to(device=self.device, dtype=torch.int64).contiguous()
+        return self._edata(self._etimes, key, "times of TemporalNeighborSampler(time", make)
 
     def close(self):
         self._etypes = {}
@@ -372,7 +363,7 @@ class Block(object):
         slots = self.indices if self.nbr is None else self.nbr
         if isinstance(num_rels, bool) or not isinstance(num_rels, int) or not 1 <= num_rels <= 64:
             raise ValueError(f"num_rels {num_rels!r}: 1..64 relations")
-        if not isinstance(etype, torch.Tensor) or etype.is_floating_point() or etype.is_complex() or etype.dtype == torch.bool:
+        if not _is_int_tensor(etype):
             raise ValueError("edge types must be an integer tensor")
         if tuple(etype.shape) != tuple(slots.shape):
             raise ValueError(f"edge types of shape {tuple(etype.shape)}: this block takes one per neighbour slot, {tuple(slots.shape)}")
@@ -565,7 +556,7 @@ class Block(object):
             ok = feat.dim() == 4 and tuple(feat.shape[:2]) == (self.num_src, R) and tuple(el.shape) == tuple(feat.shape[:3])
             want = f"[{self.num_src}, {R}, H], [{self.num_dst}, {R}, H] and [{self.num_src}, {R}, H, D]"
         else:
-            if not isinstance(rows, torch.Tensor) or rows.is_floating_point() or rows.is_complex() or rows.dtype == torch.bool:
+            if not _is_int_tensor(rows):
                 raise ValueError("rows must be an integer tensor")
             if tuple(rows.shape) != tuple(slots.shape):
                 raise ValueError(f"rows of shape {tuple(rows.shape)}: this block takes one per neighbour slot, {tuple(slots.shape)}")
@@ -640,7 +631,7 @@ class Block(object):
             raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}: this block takes [{self.num_dst}, H, D], "
                              f"[{P}, H, D] and [{P}, H, D]")
         if rows is not None:
-            if not isinstance(rows, torch.Tensor) or rows.is_floating_point() or rows.is_complex() or rows.dtype == torch.bool:
+            if not _is_int_tensor(rows):
                 raise ValueError("rows must be an integer tensor")
             if tuple(rows.shape) != tuple(slots.shape):
                 raise ValueError(f"rows of shape {tuple(rows.shape)}: this block takes one per neighbour slot, {tuple(slots.shape)}")
@@ -780,6 +771,20 @@ class Block(object):
         return self._excluded(None, indptr, self.indices[keep], eid[keep])
 
 
+class _Pending(object):
+    """A sample_begin call on its way to sample_end: the graph, the seeds as the kernels got them, their number n, the fan-outs in sampling
+    order (rev), per layer the src / nbr / indptr / eid buffers (an indptr entry is None for a fixed layer; eid is None without edge
+    ids), the edge weights of prob= or None, and the call's ticket.  bucketed / owner_counts / dst_in_src: the owner-bucketing buffers,
+    None when off.  extra: what one sampler kind carries besides (RandomWalkNeighborSampler's visit counts, TemporalNeighborSampler's decode
+    context).  batch: the EdgeBatch an edge-prediction wrapper adds."""
+    __slots__ = ("graph", "seeds", "n", "rev", "src", "nbr", "indptr", "eid", "weights", "ticket", "bucketed", "owner_counts", "dst_in_src",
+                 "extra", "batch")
+
+    def __init__(self, graph, seeds, n, rev, weights, extra):
+        self.graph, self.seeds, self.n, self.rev, self.weights, self.extra = graph, seeds, n, rev, weights, extra
+        self.eid = self.bucketed = self.owner_counts = self.dst_in_src = self.batch = None
+
+
 class NeighborSampler(object):
     stream_safe = True  # every kernel and allocation of sample() goes to torch's current stream
     completes_on_host = True  # sample() / sample_end() return after the host has seen the event behind the sample's last kernel (coala_sampler_wait)
@@ -803,7 +808,7 @@ class NeighborSampler(object):
         # every in-edge
         self.prob = prob
         # every block carries edata: '_ID' (DGL's dgl.EID; the CSC position of each sampled edge, written by the sampling kernels) and,
-        # through it, graph.edata.  Off: edata is empty and the calls that know nothing of edge ids are made
+        # through it, graph.edata.  Off: edata is empty and the call is given no edge-id buffers
         self.edge_ids = bool(edge_ids)
 
     @staticmethod
@@ -818,15 +823,16 @@ class NeighborSampler(object):
         """Enqueue the sample on the current stream and return without waiting (the kernels read their sizes from the device);
         sample_end(pending) collects the counts and builds the blocks.  A caller with something else to enqueue in between -- the
         loader launches step t+1's sample right behind step t's fetch -- never waits for the sampler at all."""
-        if isinstance(g, tuple):
-            g = CSCGraph(*g)
+        return self._begin(_as_graph(g), seed_nodes, step)
+
+    def _begin(self, g, seed_nodes, step, extra=None):
+        """sample_begin: the buffers, the one C ABI call (_entry says which) on the current stream -> the call's _Pending record."""
         weights = g.edge_weights(self.prob) if self.prob is not None else None   # raises before any launch
         ragged = self._ragged
         seeds = seed_nodes.to(g.device, dtype=torch.int64).contiguous()
         n = seeds.numel()
         rev = list(reversed(self.fanouts))          # DGL samples the output layer first
         L = len(rev)
-        full = any(ragged(f) for f in rev)
         # capacities (include/coala_hip.h, coala_sampler_layer_t): exact host bounds up to the first full layer; a full layer holds
         # at most cap * max_in_degree edges and never more than ITEM_LIMIT items, which bounds every layer behind it
         caps, src_caps, edge_caps = [n], [], []
@@ -844,27 +850,31 @@ class NeighborSampler(object):
                 src_caps.append(cap * (f + 1))
                 edge_caps.append(cap * f)
             caps.append(src_caps[-1])
-        src = [torch.empty(max(src_caps[l], 1), dtype=torch.int64, device=g.device) for l in range(L)]
-        nbr = [torch.empty(max(edge_caps[l], 1), dtype=torch.int32, device=g.device) for l in range(L)]
-        ind = [torch.empty(caps[l] + 1, dtype=torch.int64, device=g.device) if ragged(rev[l]) else None for l in range(L)]
-        fan = (C.c_int32 * L)(*rev)
-        st = self.step if step is None else int(step)
+        p = _Pending(g, seeds, n, rev, weights, extra)
+        p.src = [torch.empty(max(src_caps[l], 1), dtype=torch.int64, device=g.device) for l in range(L)]
+        p.nbr = [torch.empty(max(edge_caps[l], 1), dtype=torch.int32, device=g.device) for l in range(L)]
+        p.indptr = [torch.empty(caps[l] + 1, dtype=torch.int64, device=g.device) if ragged(rev[l]) else None for l in range(L)]
+        if self.edge_ids:
+            p.eid = [torch.empty(max(edge_caps[l], 1), dtype=torch.int64, device=g.device) for l in range(L)]
         G = self.bucket_by_owner
         bk = None
-        extra = None
         if G > 0:
-            bucketed = torch.empty(max(caps[L], 1), dtype=torch.int64, device=g.device)
-            counts = torch.empty(G, dtype=torch.int64, device=g.device)
-            dst_in_src = torch.empty(max(caps[L - 1], 1), dtype=torch.int32, device=g.device)
-            bk = _capi.SamplerBucketing(G, 0, bucketed.data_ptr(), counts.data_ptr(), dst_in_src.data_ptr())
-            extra = (bucketed, counts, dst_in_src)
+            p.bucketed = torch.empty(max(caps[L], 1), dtype=torch.int64, device=g.device)
+            p.owner_counts = torch.empty(G, dtype=torch.int64, device=g.device)
+            p.dst_in_src = torch.empty(max(caps[L - 1], 1), dtype=torch.int32, device=g.device)
+            bk = C.byref(_capi.SamplerBucketing(G, 0, p.bucketed.data_ptr(), p.owner_counts.data_ptr(), p.dst_in_src.data_ptr()))
+        lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(p.src[l].data_ptr(), p.nbr[l].data_ptr(), p.indptr[l].data_ptr() if p.indptr[l] is not None else None,
+                                                            src_caps[l], edge_caps[l]) for l in range(L)])
+        eid_p = (C.c_void_p * L)(*[t.data_ptr() for t in p.eid]) if p.eid is not None else None
+        fn, fans, kind = self._entry(p, (C.c_int32 * L)(*rev), eid_p)
         ticket = C.c_int64(-1)
-        eid = [torch.empty(max(edge_caps[l], 1), dtype=torch.int64, device=g.device) for l in range(L)] if self.edge_ids else None
-        # three launches per layer, nothing else: no host wait here (n_src_host = NULL)
-        self._enqueue(g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket)
+        # three launches per layer, nothing else: no host wait here (n_src_host = n_edges_host = NULL)
+        _capi.check(fn(g._h, seeds.data_ptr(), n, *fans, self.seed, self.step if step is None else int(step), lay, *kind, None, None,
+                       *((bk,) if self._takes_bucketing else ()), C.byref(ticket), current_stream()))
+        p.ticket = ticket.value
         if step is None:
             self.step += 1
-        return (g, seeds, n, rev, src, nbr, extra, ticket.value, ind, weights, eid)
+        return p
 
     def _ragged(self, f):
         """Whether a layer of fan-out f gives a ragged (CSR) block, whose size only the device knows."""
@@ -874,65 +884,48 @@ class NeighborSampler(object):
         """The most edges a row of a ragged layer of fan-out f can hold, known on the host."""
         return g.max_in_degree
 
-    def _enqueue(self, g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket):
-        """The C ABI call of sample_begin, on the current stream."""
-        if eid is not None:
-            lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr() if ind[l] is not None else None,
-                                                                src_caps[l], edge_caps[l]) for l in range(L)])
-            eid_p = (C.c_void_p * L)(*[t.data_ptr() for t in eid])
-            _capi.check(_lib.coala_sampler_sample_layers_edge_ids(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay,
-                                                                  weights.data_ptr() if weights is not None else None, eid_p, None, None,
-                                                                  C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
-        elif any(t is not None for t in ind) or weights is not None:
-            lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr() if ind[l] is not None else None,
-                                                                src_caps[l], edge_caps[l]) for l in range(L)])
-            if weights is not None:
-                _capi.check(_lib.coala_sampler_sample_layers_weighted(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, weights.data_ptr(), None,
-                                                                      None, C.byref(bk) if bk is not None else None, C.byref(ticket),
-                                                                      current_stream()))
-            else:
-                _capi.check(_lib.coala_sampler_sample_layers(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, None, None,
-                                                             C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
-        else:
-            src_p = (C.c_void_p * L)(*[t.data_ptr() for t in src])
-            nbr_p = (C.c_void_p * L)(*[t.data_ptr() for t in nbr])
-            _capi.check(_lib.coala_sampler_sample(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, src_p, nbr_p, None,
-                                                  C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
+    _takes_bucketing = True   # whether the C entry point of _entry has a bucketing argument
 
-    def sample_end(self, pending):
-        """Wait for the counts of a sample_begin (an event wait: only for that call's kernels) and build the blocks."""
-        g, seeds, n, rev, src, nbr, extra, ticket, ind, weights, eid = pending
-        L, G = len(rev), self.bucket_by_owner
+    def _entry(self, p, fan, eid_p):
+        """The C entry point of this sampler kind -> (function, its fan-out arguments, its arguments between `layers` and `n_src_host`).
+        A kind with buffers of its own allocates them here, into p.extra."""
+        return (_lib.coala_sampler_sample_layers_edge_ids, (fan, len(p.rev)), (p.weights.data_ptr() if p.weights is not None else None, eid_p))
+
+    def _wait(self, p):
+        """Wait for the counts of a sample_begin (an event wait: only for that call's kernels) -> per layer the source nodes and the
+        edges, and the owner counts or None.  Raises when the device refused a full layer (or the fixed layers behind it) for its size."""
+        L = len(p.rev)
         n_src = (C.c_int64 * L)()
         n_edges = (C.c_int64 * L)()
-        ch = (C.c_int64 * G)() if G > 0 else None
-        if any(t is not None for t in ind) or weights is not None or eid is not None:   # raises when the device refused a full layer (or the fixed layers behind it) for its size
-            _capi.check(_lib.coala_sampler_wait_layers(g._h, ticket, n_src, n_edges, ch))
-        else:
-            _capi.check(_lib.coala_sampler_wait(g._h, ticket, n_src, ch))
-        counts_host = list(ch) if G > 0 else None
-        if G > 0:
-            bucketed, counts, dst_in_src = extra
+        ch = (C.c_int64 * self.bucket_by_owner)() if p.owner_counts is not None else None
+        _capi.check(_lib.coala_sampler_wait_layers(p.graph._h, p.ticket, n_src, n_edges, ch))
+        return n_src, n_edges, list(ch) if ch is not None else None
+
+    def sample_end(self, pending):
+        """Wait for the counts of a sample_begin and build the blocks."""
+        p = pending
+        g, L = p.graph, len(p.rev)
+        n_src, n_edges, counts_host = self._wait(p)
         blocks = []
-        n_dst = n
+        n_dst = p.n
         for l in range(L):
-            ns = int(n_src[l])
-            if ind[l] is not None:   # ragged block: CSR over the destination nodes
+            ns, f = n_src[l], p.rev[l]
+            if p.indptr[l] is not None:   # ragged block: CSR over the destination nodes
                 nbr_l = None
-                csr = dict(indptr=ind[l][: n_dst + 1], indices=nbr[l][: int(n_edges[l])], **self._block_extras(ind[l][: n_dst + 1], int(n_edges[l]), rev[l]))
-                if eid is not None:
-                    csr["eid"] = eid[l][: int(n_edges[l])]
+                csr = dict(indptr=p.indptr[l][: n_dst + 1], indices=p.nbr[l][: n_edges[l]], **self._block_extras(p.indptr[l][: n_dst + 1], n_edges[l], f))
+                if p.eid is not None:
+                    csr["eid"] = p.eid[l][: n_edges[l]]
             else:
-                nbr_l = nbr[l][: n_dst * rev[l]].view(n_dst, rev[l])
-                csr = {} if eid is None else dict(eid=eid[l][: n_dst * rev[l]].view(n_dst, rev[l]))
-            if G > 0 and l == L - 1:   # the input layer: owner-bucketed source list
-                blocks.insert(0, Block(bucketed[:ns], nbr_l, n_dst, graph=g if l == 0 else None, edata_graph=g, dst_in_src=dst_in_src[:n_dst],
-                                       dst_nodes=src[l][:n_dst], owner_counts=counts, owner_counts_host=counts_host, **csr))
+                nbr_l = p.nbr[l][: n_dst * f].view(n_dst, f)
+                csr = {} if p.eid is None else dict(eid=p.eid[l][: n_dst * f].view(n_dst, f))
+            if p.owner_counts is not None and l == L - 1:   # the input layer: owner-bucketed source list
+                blocks.insert(0, Block(p.bucketed[:ns], nbr_l, n_dst, graph=g if l == 0 else None, edata_graph=g, dst_in_src=p.dst_in_src[:n_dst],
+                                       dst_nodes=p.src[l][:n_dst], owner_counts=p.owner_counts, owner_counts_host=counts_host, **csr))
             else:
-                blocks.insert(0, Block(src[l][:ns], nbr_l, n_dst, graph=g if l == 0 else None, edata_graph=g, **csr))
+                blocks.insert(0, Block(p.src[l][:ns], nbr_l, n_dst, graph=g if l == 0 else None, edata_graph=g, **csr))
             n_dst = ns
         input_nodes = blocks[0].src_nodes
-        return input_nodes, seeds, blocks
+        return input_nodes, p.seeds, blocks
 
     def _block_extras(self, indptr, n_edges, f):
         """More Block arguments for a ragged layer of fan-out f."""
@@ -965,13 +958,8 @@ class LaborSampler(NeighborSampler):
     def _ragged(self, f):
         return True
 
-    def _enqueue(self, g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket):
-        lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr(), src_caps[l], edge_caps[l])
-                                         for l in range(L)])
-        eid_p = (C.c_void_p * L)(*[t.data_ptr() for t in eid]) if eid is not None else None
-        _capi.check(_lib.coala_sampler_sample_layers_labor(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, eid_p, int(self.layer_dependency),
-                                                           None, None, C.byref(bk) if bk is not None else None, C.byref(ticket),
-                                                           current_stream()))
+    def _entry(self, p, fan, eid_p):
+        return _lib.coala_sampler_sample_layers_labor, (fan, len(p.rev)), (eid_p, int(self.layer_dependency))
 
     def _block_extras(self, indptr, n_edges, f):
         def edge_weights():
@@ -1025,15 +1013,11 @@ class RelNeighborSampler(NeighborSampler):
     def _row_bound(self, g, f):
         return g.max_in_degree if f == -1 else min(f, g.max_in_degree)
 
-    def _enqueue(self, g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket):
-        types = g.edge_types(self.etype, self.num_rels)   # raises before any launch
-        lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), ind[l].data_ptr(), src_caps[l], edge_caps[l])
-                                         for l in range(L)])
-        eid_p = (C.c_void_p * L)(*[t.data_ptr() for t in eid]) if eid is not None else None
+    def _entry(self, p, fan, eid_p):
+        types = p.graph.edge_types(self.etype, self.num_rels)   # raises before any launch
+        L = len(p.rev)
         rel_fan = (C.c_int32 * (L * self.num_rels))(*[f for per_rel in reversed(self.rel_fanouts) for f in per_rel])
-        _capi.check(_lib.coala_sampler_sample_layers_rel(g._h, seeds.data_ptr(), n, rel_fan, self.num_rels, L, self.seed, st, lay, types.data_ptr(),
-                                                         eid_p, None, None, C.byref(bk) if bk is not None else None, C.byref(ticket),
-                                                         current_stream()))
+        return _lib.coala_sampler_sample_layers_rel, (rel_fan, self.num_rels, L), (types.data_ptr(), eid_p)
 
 
 def _walk_threshold(prob, name):
@@ -1078,26 +1062,17 @@ class RandomWalkNeighborSampler(NeighborSampler):
         self.num_neighbors = list(self.fanouts)
         self.num_traversals, self.num_random_walks, self.termination_prob = num_traversals, num_random_walks, float(termination_prob)
         self.weight_column = weight_column
-        self._counts = None   # the count buffers of the call _enqueue just made, on their way into sample_begin's result
 
-    def sample_begin(self, g, seed_nodes, step=None):
-        pending = super().sample_begin(g, seed_nodes, step)
-        counts, self._counts = self._counts, None
-        return pending + (counts,)
-
-    def _enqueue(self, g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket):
-        lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), None, src_caps[l], edge_caps[l]) for l in range(L)])
-        self._counts = [torch.empty(max(edge_caps[l], 1), dtype=torch.int32, device=g.device) for l in range(L)]
-        cnt_p = (C.c_void_p * L)(*[t.data_ptr() for t in self._counts])
+    def _entry(self, p, fan, eid_p):
+        p.extra = [torch.empty_like(t) for t in p.nbr]   # int32 [edge_cap] per layer: the visit count of every neighbour slot
+        cnt_p = (C.c_void_p * len(p.extra))(*[t.data_ptr() for t in p.extra])
         walk = _capi.SamplerWalk(self.num_traversals, self.num_random_walks, self.term_threshold)
-        _capi.check(_lib.coala_sampler_sample_layers_walk(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, C.byref(walk), cnt_p, None, None,
-                                                          C.byref(bk) if bk is not None else None, C.byref(ticket), current_stream()))
+        return _lib.coala_sampler_sample_layers_walk, (fan, len(p.rev)), (C.byref(walk), cnt_p)
 
     def sample_end(self, pending):
-        counts = pending[-1]
-        input_nodes, seeds, blocks = super().sample_end(pending[:-1])
+        input_nodes, seeds, blocks = super().sample_end(pending)
         for l, b in enumerate(reversed(blocks)):   # counts are in sampling order, blocks in model order
-            c = counts[l][: b.nbr.numel()].view(b.nbr.shape)
+            c = pending.extra[l][: b.nbr.numel()].view(b.nbr.shape)
             b.edata = _EdgeData(None, None, {self.weight_column: lambda c=c: c.to(torch.float32)})
             b.edata["visit_counts"] = c   # the kernel's int32 counts: held by the block, so Block.tensors() reports their buffer
         return input_nodes, seeds, blocks
@@ -1115,8 +1090,7 @@ def random_walk(g, nodes, length, restart_prob=0.0, num_walks=1, seed=0, step=0)
         if isinstance(x, bool) or not isinstance(x, int) or not 1 <= x <= hi:
             raise ValueError(f"{name} {x!r}: 1..{hi}")
     thr = _walk_threshold(restart_prob, "restart_prob")
-    if isinstance(g, tuple):
-        g = CSCGraph(*g)
+    g = _as_graph(g)
     nodes = nodes.to(g.device, dtype=torch.int64).contiguous()
     out = torch.empty((nodes.numel(), num_walks, length + 1), dtype=torch.int64, device=g.device)
     _capi.check(_lib.coala_sampler_random_walk(g._h, nodes.data_ptr(), nodes.numel(), num_walks, length, thr, int(seed) & ((1 << 64) - 1),
@@ -1169,7 +1143,6 @@ class TemporalNeighborSampler(NeighborSampler):
             raise ValueError(f"strategy {strategy!r}: 'uniform' or 'last'")
         super().__init__(fanouts, seed=seed, edge_ids=edge_ids)
         self.time, self.strategy, self.inclusive, self.seed_time = time, strategy, bool(inclusive), seed_time
-        self._ctx = None   # (edge times, slot_time, n_slots) of the call sample_begin is making, for _enqueue
 
     def _seed_times(self, g, seeds, seed_times):
         if seed_times is None:
@@ -1180,7 +1153,7 @@ class TemporalNeighborSampler(NeighborSampler):
                 raise KeyError(f"ndata has no {self.seed_time!r}: the query times of TemporalNeighborSampler(seed_time={self.seed_time!r})")
             col = g.ndata[self.seed_time]
             seed_times = col[seeds.to(col.device)]
-        if not isinstance(seed_times, torch.Tensor) or seed_times.is_floating_point() or seed_times.is_complex() or seed_times.dtype == torch.bool:
+        if not _is_int_tensor(seed_times):
             raise ValueError("seed times must be an integer tensor (floating-point timestamps are not supported)")
         if seed_times.dim() != 1 or seed_times.numel() != seeds.numel():
             raise ValueError(f"seed times of shape {tuple(seed_times.shape)}: one per seed node, ({seeds.numel()},)")
@@ -1193,65 +1166,53 @@ class TemporalNeighborSampler(NeighborSampler):
     def sample_begin(self, g, seed_nodes, step=None, seed_times=None):
         """NeighborSampler.sample_begin over the codes of the (seed node, query time) pairs.  The table of distinct times and the codes
         are made on the device; the one host read is the number of distinct times."""
-        if isinstance(g, tuple):
-            g = CSCGraph(*g)
+        g = _as_graph(g)
         ts = g.edge_times(self.time)   # raises before any launch
         if seed_nodes.dim() != 1:
             raise ValueError(f"seed nodes of shape {tuple(seed_nodes.shape)}: a 1-D tensor of node ids")
         seeds = seed_nodes.to(g.device, dtype=torch.int64).contiguous()
         times = self._seed_times(g, seeds, seed_times)
         slot_time, slot = torch.unique(times, sorted=True, return_inverse=True)
-        n_slots = int(slot_time.numel())
-        bits = pair_code_bits(g.num_nodes, n_slots)
+        bits = pair_code_bits(g.num_nodes, slot_time.numel())
         # a seed id outside the graph takes the node field num_nodes, which names no node: an empty row
         codes = (slot << bits) | torch.where((seeds >= 0) & (seeds < g.num_nodes), seeds, g.num_nodes)
-        self._ctx = (ts, slot_time.contiguous(), n_slots)
-        try:
-            pending = super().sample_begin(g, codes, step)
-        finally:
-            self._ctx = None
-        return pending + ((seeds, slot_time, bits, ts),)
+        return self._begin(g, codes, step, extra=(seeds, slot_time.contiguous(), bits, ts))
 
-    def _enqueue(self, g, seeds, n, fan, L, st, src, nbr, ind, src_caps, edge_caps, weights, eid, bk, ticket):
-        ts, slot_time, n_slots = self._ctx
-        lay = (_capi.SamplerLayer * L)(*[_capi.SamplerLayer(src[l].data_ptr(), nbr[l].data_ptr(), None, src_caps[l], edge_caps[l]) for l in range(L)])
-        eid_p = (C.c_void_p * L)(*[t.data_ptr() for t in eid]) if eid is not None else None
-        _capi.check(_lib.coala_sampler_sample_layers_temporal(g._h, seeds.data_ptr(), n, fan, L, self.seed, st, lay, ts.data_ptr(),
-                                                              slot_time.data_ptr(), n_slots, self.STRATEGIES.index(self.strategy),
-                                                              int(self.inclusive), eid_p, None, None, C.byref(ticket), current_stream()))
+    _takes_bucketing = False
+
+    def _entry(self, p, fan, eid_p):
+        _, slot_time, _, ts = p.extra
+        return (_lib.coala_sampler_sample_layers_temporal, (fan, len(p.rev)),
+                (ts.data_ptr(), slot_time.data_ptr(), slot_time.numel(), self.STRATEGIES.index(self.strategy), int(self.inclusive), eid_p))
 
     def sample_end(self, pending):
         """Wait for the counts, decode every layer's source codes into node ids and query times, and build the blocks."""
-        g, codes, n, rev, src, nbr, _, ticket, _, _, eid = pending[:-1]
-        seeds, slot_time, bits, ts = pending[-1]
-        L = len(rev)
-        n_src = (C.c_int64 * L)()
-        n_edges = (C.c_int64 * L)()
-        _capi.check(_lib.coala_sampler_wait_layers(g._h, ticket, n_src, n_edges, None))
+        p = pending
+        g, n = p.graph, p.n
+        seeds, slot_time, bits, ts = p.extra
+        n_src, _, _ = self._wait(p)
         cur = torch.cuda.current_stream(g.device)
         mask = (1 << bits) - 1
         blocks = []
-        n_dst, dst_nodes, dst_times = n, seeds, slot_time[codes >> bits] if n else codes
-        for l in range(L):
-            ns, f = int(n_src[l]), rev[l]
-            code_l = src[l][:ns]
+        n_dst, dst_times = n, slot_time[p.seeds >> bits] if n else p.seeds
+        for l, f in enumerate(p.rev):
+            ns = n_src[l]
+            code_l = p.src[l][:ns]
             code_l.record_stream(cur)   # allocated on the stream of sample_begin, decoded on this one
             src_nodes, src_times = code_l & mask, slot_time[code_l >> bits] if ns else code_l
             src_nodes[:n] = seeds       # the seeds as they were given: an id outside the graph was coded as num_nodes
-            eid_l = eid[l][: n_dst * f].view(n_dst, f) if eid is not None else None
+            eid_l = p.eid[l][: n_dst * f].view(n_dst, f) if p.eid is not None else None
             lazy = None
             if eid_l is not None:
                 def dt(eid_l=eid_l, t_row=dst_times):
                     return torch.where(eid_l >= 0, t_row.unsqueeze(1) - ts[eid_l.clamp_min(0)], 0)
                 lazy = {"dt": dt}
-            b = Block(src_nodes, nbr[l][: n_dst * f].view(n_dst, f), n_dst, edata_graph=g, eid=eid_l, edata_lazy=lazy)
+            # the output layer's destination items are the seeds (src_nodes[:n]): Block gathers graph.ndata for them
+            b = Block(src_nodes, p.nbr[l][: n_dst * f].view(n_dst, f), n_dst, graph=g if l == 0 else None, edata_graph=g, eid=eid_l, edata_lazy=lazy)
             b.src_times, b.dst_times = src_times, dst_times
             b.srcdata["_TIME"], b.dstdata["_TIME"] = src_times, dst_times   # Block.tensors() reports what srcdata / dstdata hold
-            if l == 0:
-                for k, v in g.ndata.items():
-                    b.dstdata[k] = v[dst_nodes] if v.device == dst_nodes.device else v[dst_nodes.cpu()]
             blocks.insert(0, b)
-            n_dst, dst_nodes, dst_times = ns, src_nodes, src_times
+            n_dst, dst_times = ns, src_times
         return blocks[0].src_nodes, seeds, blocks
 
 
@@ -1385,16 +1346,17 @@ class EdgePredictionSampler(object):
 
     def sample_begin(self, g, eids, step=None):
         """Enqueue the edge batch, wait for its two counts (the one host wait of the wrapper), then enqueue the inner sample over the
-        batch's seed nodes.  -> the inner sampler's pending tuple, then the EdgeBatch."""
-        if isinstance(g, tuple):
-            g = CSCGraph(*g)
+        batch's seed nodes.  -> the inner sampler's pending record, its `batch` the EdgeBatch."""
+        g = _as_graph(g)
         st = self.sampler.step if step is None else int(step)
         batch = edge_batch_wait(edge_batch(g, eids, self.num_neg, self.sampler.seed, st))
-        return self.sampler.sample_begin(g, batch.seed_nodes, step) + (batch,)
+        pending = self.sampler.sample_begin(g, batch.seed_nodes, step)
+        pending.batch = batch
+        return pending
 
     def sample_end(self, pending):
-        batch = pending[-1]
-        input_nodes, _, blocks = self.sampler.sample_end(pending[:-1])
+        batch = pending.batch
+        input_nodes, _, blocks = self.sampler.sample_end(pending)
         if self.exclude is not None:
             ex = batch.eids
             if self.exclude == "reverse_id":
@@ -1435,9 +1397,8 @@ class TemporalEdgePredictionSampler(object):
 
     def sample_begin(self, g, eids, step=None):
         """Enqueue the edge batch and wait for its counts, make the distinct (node, t_e) pairs in plain torch, then enqueue the inner
-        sample over them.  -> the inner sampler's pending tuple, then the EdgeBatch."""
-        if isinstance(g, tuple):
-            g = CSCGraph(*g)
+        sample over them.  -> the inner sampler's pending record, its `batch` the EdgeBatch."""
+        g = _as_graph(g)
         ts = g.edge_times(self.sampler.time)   # raises before any launch
         st = self.sampler.step if step is None else int(step)
         raw = edge_batch_wait(edge_batch(g, eids, self.num_neg, self.sampler.seed, st))
@@ -1450,11 +1411,13 @@ class TemporalEdgePredictionSampler(object):
         where = where.to(torch.int32)
         nodes, times = pairs & ((1 << bits) - 1), slot_time[pairs >> bits] if n else pairs
         batch = EdgeBatch(raw.eids, nodes, where[:n], where[n: 2 * n], where[2 * n:], k, seed_times=times)
-        return self.sampler.sample_begin(g, nodes, step, seed_times=times) + (batch,)
+        pending = self.sampler.sample_begin(g, nodes, step, seed_times=times)
+        pending.batch = batch
+        return pending
 
     def sample_end(self, pending):
-        input_nodes, _, blocks = self.sampler.sample_end(pending[:-1])
-        return input_nodes, pending[-1], blocks
+        input_nodes, _, blocks = self.sampler.sample_end(pending)
+        return input_nodes, pending.batch, blocks
 
 
 def as_edge_prediction_sampler(sampler, exclude=None, reverse_eids=None, reverse_etypes=None, negative_sampler=None, prefetch_labels=None):

@@ -1492,11 +1492,10 @@ __global__ __launch_bounds__(kBlock) void edge_relabel_clear_kernel(int64_t n, i
 struct coala_sampler {
     struct RingInfo { // what coala_sampler_wait_layers needs of a call to read its counts and explain a refusal
         int n_layers = 0, n_parts = 0;
-        bool labor = false; // fixed fan-outs are LABOR layers: every layer of the call is ragged
-        bool rel = false;   // relation layers (a fan-out per relation): every layer of the call is ragged
+        bool all_ragged = false; // a LABOR or a relation call: every layer is ragged, whatever its fan-out
         bool edge_batch = false; // coala_sampler_edge_batch: the slot holds n_nodes and n_bad, collected by coala_sampler_edge_batch_wait
         int64_t n_seeds = 0;
-        bool ragged(int l) const { return labor || rel || fanouts[l] == -1; } // CSR block, sizes known on the device only
+        bool ragged(int l) const { return all_ragged || fanouts[l] == -1; } // CSR block, sizes known on the device only
         int32_t fanouts[COALA_SAMPLER_MAX_LAYERS] = {}; // of a relation call: -1 for a layer whose fan-outs are all -1, else 0
         int64_t src_cap[COALA_SAMPLER_MAX_LAYERS] = {}, edge_cap[COALA_SAMPLER_MAX_LAYERS] = {};
     };
@@ -1551,22 +1550,65 @@ int ilog2_exact(uint64_t v) {
     return s;
 }
 
-int check_call(const coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
-               const coala_sampler_layer_t* layers, const coala_sampler_bucketing_t* bucketing, bool labor, bool rel) {
-    if (!s || (!seeds && n_seeds > 0) || !fanouts) return fail(COALA_EINVAL, "null argument");
-    if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
-    if (n_seeds < 0 || n_seeds > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad n_seeds");
-    const int n_parts = bucketing ? bucketing->n_parts : 0;
-    if (n_parts < 0 || n_parts > kMaxParts) return fail(COALA_EINVAL, "bucketing: n_parts must be 0..%d", kMaxParts);
-    if (n_parts > 0 && (!bucketing->bucketed_nodes || !bucketing->counts || !bucketing->dst_in_src)) return fail(COALA_EINVAL, "bucketing: null buffer");
-    if (!layers) return fail(COALA_EINVAL, "null argument");
+// One sampling call, as its entry point hands it to sample_impl: its kind -- how a fixed layer picks its edges; the kinds exclude each
+// other --, the arguments every entry point has, in the ABI's order, and below them the kinds' payloads, which an entry point sets by name.
+enum class Kind { uniform, weighted, labor, rel, walk, temporal };
+struct Call {
+    Kind kind;
+    const int64_t* seeds;   int64_t n_seeds; // of a temporal call: pair codes, as layers[l].src_nodes
+    const int32_t* fanouts; int n_layers;    // of a relation call: -1 for a layer whose fan-outs are all -1, else 0
+    uint64_t seed, step;
+    const coala_sampler_layer_t* layers;
+    int64_t* const* edge_ids; // null, or per layer: null or device int64[edge_cap], the CSC position of every neighbour slot
+    int64_t *n_src_host, *n_edges_host;
+    const coala_sampler_bucketing_t* bucketing;
+    int64_t* ticket_out;
+    hipStream_t st;
+    const float* weights = nullptr;                                                   // weighted: the fp32 edge weights, CSC order
+    bool layer_dependency = false;                                                    // labor: one key for every layer of the call
+    const RelFan* rel = nullptr;                const int32_t* etype = nullptr;       // rel: every layer's fan-outs; the int32 edge types, CSC order
+    WalkParams walk{};                          int32_t* const* visit_counts = nullptr; // walk; null, or per layer null or device int32[edge_cap]
+    const Temporal* temporal = nullptr;                                               // temporal: seeds / src_nodes hold pair codes
+    bool all_ragged() const { return kind == Kind::labor || kind == Kind::rel; } // every layer is ragged, whatever its fan-out
+};
+
+int check_n_layers(int n) {
+    return n < 1 || n > COALA_SAMPLER_MAX_LAYERS ? fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS) : COALA_OK;
+}
+
+// The layers of a kind that has fixed-stride layers only ("a <noun> layer <rule>").
+int check_fixed_layers(const int32_t* fanouts, const coala_sampler_layer_t* layers, int n_layers, const char* noun, const char* rule) {
     for (int l = 0; l < n_layers; ++l) {
-        const int f = fanouts[l];
-        if (!rel && f != kFull && (f < 1 || f > 32)) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (or -1: every in-edge)", f);
-        const coala_sampler_layer_t& y = layers[l];
-        if (!y.src_nodes || !y.nbr_local || ((labor || rel || f == kFull) && !y.indptr_local)) return fail(COALA_EINVAL, "layer %d: null buffer", l);
+        if (fanouts[l] < 1 || fanouts[l] > 32) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (a %s layer %s)", fanouts[l], noun, rule);
+        if (layers[l].indptr_local) return fail(COALA_EINVAL, "layer %d: a %s layer is fixed-stride, indptr_local must be NULL", l, noun);
+    }
+    return COALA_OK;
+}
+
+int check_call(const coala_sampler_t* s, const Call& c) {
+    if (!s || (!c.seeds && c.n_seeds > 0) || !c.fanouts) return fail(COALA_EINVAL, "null argument");
+    if (int rc = check_n_layers(c.n_layers)) return rc;
+    if (c.n_seeds < 0 || c.n_seeds > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad n_seeds");
+    const int n_parts = c.bucketing ? c.bucketing->n_parts : 0;
+    if (n_parts < 0 || n_parts > kMaxParts) return fail(COALA_EINVAL, "bucketing: n_parts must be 0..%d", kMaxParts);
+    if (n_parts > 0 && (!c.bucketing->bucketed_nodes || !c.bucketing->counts || !c.bucketing->dst_in_src)) return fail(COALA_EINVAL, "bucketing: null buffer");
+    if (!c.layers) return fail(COALA_EINVAL, "null argument");
+    for (int l = 0; l < c.n_layers; ++l) {
+        const int f = c.fanouts[l];
+        if (c.kind != Kind::rel && f != kFull && (f < 1 || f > 32)) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (or -1: every in-edge)", f);
+        const coala_sampler_layer_t& y = c.layers[l];
+        if (!y.src_nodes || !y.nbr_local || ((c.all_ragged() || f == kFull) && !y.indptr_local)) return fail(COALA_EINVAL, "layer %d: null buffer", l);
         if (y.src_cap < 0 || y.edge_cap < 0) return fail(COALA_EINVAL, "layer %d: negative capacity", l);
     }
+    return COALA_OK;
+}
+
+// The ring slot of one of the last kRing calls.
+int ring_slot(const coala_sampler_t* s, int64_t ticket, int* slot) {
+    if (!s) return fail(COALA_EINVAL, "null sampler");
+    if (ticket < 0 || (uint64_t)ticket >= s->calls || s->calls - (uint64_t)ticket > kRing)
+        return fail(COALA_EINVAL, "ticket %lld is not one of the last %d calls", (long long)ticket, kRing);
+    *slot = (int)((uint64_t)ticket % kRing);
     return COALA_OK;
 }
 
@@ -1598,11 +1640,9 @@ int fixed_run_check(const RingInfo& r, int l, int64_t n_src, int64_t* items_out,
 }
 
 int wait_impl(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host) {
-    if (!s) return fail(COALA_EINVAL, "null sampler");
-    if (ticket < 0 || (uint64_t)ticket >= s->calls || s->calls - (uint64_t)ticket > kRing)
-        return fail(COALA_EINVAL, "ticket %lld is not one of the last %d calls", (long long)ticket, kRing);
+    int slot;
+    if (int rc = ring_slot(s, ticket, &slot)) return rc;
     HIPCHK(hipSetDevice(s->device));
-    const int slot = (int)((uint64_t)ticket % kRing);
     HIPCHK(hipEventSynchronize(s->done[slot])); // the kernels behind this event stored the counts into pinned host memory
     const int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
     const RingInfo& r = s->ring[slot];
@@ -1619,14 +1659,9 @@ int wait_impl(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* 
         const int64_t n_dst = l ? pin[l - 1] : r.n_seeds;
         if (pin[kPinRefused + l]) {
             const long long e = pin[kPinEdges + l], items = n_dst + e;
-            if (items > kItemLimit)
-                return fail(COALA_EINVAL, "layer %d holds %lld items (%lld destination nodes + %lld edges): over the limit of %lld", l, items,
-                            (long long)n_dst, e, (long long)kItemLimit);
-            if (items > r.src_cap[l])
-                return fail(COALA_EINVAL, "layer %d holds %lld items (%lld destination nodes + %lld edges): over its src_cap of %lld", l, items,
-                            (long long)n_dst, e, (long long)r.src_cap[l]);
-            return fail(COALA_EINVAL, "layer %d holds %lld items (%lld destination nodes + %lld edges): over its edge_cap of %lld", l, items,
-                        (long long)n_dst, e, (long long)r.edge_cap[l]);
+            const bool limit = items > kItemLimit, src = items > r.src_cap[l];
+            return fail(COALA_EINVAL, "layer %d holds %lld items (%lld destination nodes + %lld edges): over %s of %lld", l, items, (long long)n_dst, e,
+                        limit ? "the limit" : src ? "its src_cap" : "its edge_cap", (long long)(limit ? kItemLimit : src ? r.src_cap[l] : r.edge_cap[l]));
         }
         if (pin[kPinOver + l]) {
             int64_t items = 0, lim = 0;
@@ -1654,21 +1689,8 @@ void dispatch_bool(bool b, F&& f) {
     else f(std::false_type{});
 }
 
-// What the launches of a call are made from: its arguments, and the capacities the host derives from them (plan_call).
-struct Plan {
-    const int64_t* seeds;
-    uint64_t seed, step;
-    const coala_sampler_layer_t* layers;
-    const coala_sampler_bucketing_t* bucketing;
-    const float* weights; // null for uniform fixed layers, else the fp32 edge weights of weighted fixed layers (CSC order)
-    int64_t* const* edge_ids; // null, or per layer: null or device int64[edge_cap], the CSC position of every neighbour slot
-    hipStream_t st;
-    bool layer_dependency; // LABOR (info.labor): one key for every layer of the call
-    const RelFan* rel;     // relation layers (info.rel): the fan-outs of every layer, and the int32 edge types (CSC order)
-    const int32_t* etype;
-    const coala_sampler_walk_t* walk;    // random-walk layers: every fixed layer of the call is one; null otherwise
-    int32_t* const* visit_counts;        // walk layers: null, or per layer null or device int32[edge_cap], the visit count of every slot
-    const Temporal* temporal;            // temporal layers: every layer of the call is one, and seeds / src_nodes hold pair codes; null otherwise
+// What the launches of a call are made from: the call, and what the host derives from it (plan_call).
+struct Plan : Call {
     RingInfo info;       // n_seeds, the fan-outs, n_parts and the caller's capacities
     // layer l has at most dst_cap[l] dst nodes, items_cap[l] items (dst nodes + neighbour slots), nbr_cap[l] neighbour entries
     int64_t dst_cap[COALA_SAMPLER_MAX_LAYERS], items_cap[COALA_SAMPLER_MAX_LAYERS], nbr_cap[COALA_SAMPLER_MAX_LAYERS];
@@ -1679,17 +1701,16 @@ struct Plan {
 
 // Capacities.  Up to the first full layer they are exact host bounds (cap_l * (f + 1)) and checked here; a full layer and the fixed
 // layers behind it are checked on the device against the caller's capacities and the item limit.
-int plan_call(Plan& p, int64_t n_seeds, const int32_t* fanouts, int n_layers, int n_parts, bool labor) {
-    p.info.labor = labor;
-    p.info.rel = p.rel != nullptr;
-    p.info.n_layers = n_layers;
-    p.info.n_parts = n_parts;
-    p.info.n_seeds = n_seeds;
+int plan_call(Plan& p) {
+    p.info.all_ragged = p.all_ragged();
+    p.info.n_layers = p.n_layers;
+    p.info.n_parts = p.bucketing ? p.bucketing->n_parts : 0;
+    p.info.n_seeds = p.n_seeds;
     p.max_items = p.max_nbr = 0;
-    int64_t cap = n_seeds;
+    int64_t cap = p.n_seeds;
     bool host_bound = true;
-    for (int l = 0; l < n_layers; ++l) {
-        const int f = fanouts[l];
+    for (int l = 0; l < p.n_layers; ++l) {
+        const int f = p.fanouts[l];
         const coala_sampler_layer_t& y = p.layers[l];
         p.info.fanouts[l] = f;
         p.info.src_cap[l] = y.src_cap;
@@ -1718,20 +1739,19 @@ int plan_call(Plan& p, int64_t n_seeds, const int32_t* fanouts, int n_layers, in
     return COALA_OK;
 }
 
-int grow_workspace(coala_sampler_t* s, const Plan& p) {
+// The scratch of a call of at most max_items items and max_nbr neighbour entries in a layer, and cap source nodes in the last one.
+int grow_workspace(coala_sampler_t* s, hipStream_t st, int n_parts, uint64_t cap, uint64_t max_items, uint64_t max_nbr) {
     int rc;
-    const int n_parts = p.info.n_parts;
-    const uint64_t cap = (uint64_t)p.items_cap[p.info.n_layers - 1]; // source nodes of the last layer
-    const uint64_t table = table_size((int64_t)p.max_items);
+    const uint64_t table = table_size((int64_t)max_items);
     const uint64_t wave_tiles = (cap + kRouteTile - 1) / kRouteTile;
-    if ((rc = grow((void**)&s->nbr_global, &s->nbr_cap, p.max_nbr ? p.max_nbr : 1, sizeof(int64_t), p.st))) return rc;
-    if ((rc = grow((void**)&s->slot_of_item, &s->item_cap, p.max_items ? p.max_items : 1, sizeof(uint32_t), p.st))) return rc;
+    if ((rc = grow((void**)&s->nbr_global, &s->nbr_cap, max_nbr ? max_nbr : 1, sizeof(int64_t), st))) return rc;
+    if ((rc = grow((void**)&s->slot_of_item, &s->item_cap, max_items ? max_items : 1, sizeof(uint32_t), st))) return rc;
     if (n_parts > 0) {
-        if ((rc = grow((void**)&s->wave_counts, &s->wc_cap, (wave_tiles + 1) * (uint64_t)n_parts, sizeof(uint32_t), p.st))) return rc;
-        if ((rc = grow((void**)&s->new_of_old, &s->noo_cap, cap ? cap : 1, sizeof(uint32_t), p.st))) return rc;
+        if ((rc = grow((void**)&s->wave_counts, &s->wc_cap, (wave_tiles + 1) * (uint64_t)n_parts, sizeof(uint32_t), st))) return rc;
+        if ((rc = grow((void**)&s->new_of_old, &s->noo_cap, cap ? cap : 1, sizeof(uint32_t), st))) return rc;
     }
     if (table > s->table_cap) {
-        HIPCHK(hipStreamSynchronize(p.st));
+        HIPCHK(hipStreamSynchronize(st));
         for (void** q : {(void**)&s->tb.keys, (void**)&s->tb.local_of_slot})
             if (*q) { HIPCHK(hipFree(*q)); *q = nullptr; }
         HIPCHK(hipMalloc((void**)&s->tb.keys, table * (sizeof(long long) + sizeof(uint32_t)))); // keys, then the first-position words
@@ -1775,42 +1795,25 @@ int rel_group(const RelFan& fan) {
 // device words.
 int degree_scan(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, const int64_t* n_dst_dev) {
     if (int rc = next_gen(s, p.st)) return rc;
-    if (p.info.fanouts[l] != kFull) {
-        int rows = 64; // destination nodes per tile: the smallest power of two with which dst_cap fits kMaxTiles tiles
-        while (rows < kTile && (p.dst_cap[l] + rows - 1) / rows > kMaxTiles) rows <<= 1;
-        const int tiles = grid1d(p.dst_cap[l], rows, kMaxTiles);
-        if (p.rel)
-            dispatch_group(rel_group(p.rel[l]), [&](auto gs_c) {
-                hipLaunchKernelGGL(rel_count_scan_kernel<decltype(gs_c)::value>, dim3(tiles), dim3(kBlock), 0, p.st, s->g, p.etype, p.rel[l], dst,
-                                   n_dst_dev, p.info.n_seeds, rows, s->counts_dev + l, s->status, s->ticket, s->ticket_total,
-                                   s->scan_gen & 0x3FFFFFFFull, p.layers[l].indptr_local, p.items_cap[l],
-                                   std::min<int64_t>(kItemLimit, p.layers[l].edge_cap), p.pin_dev + l);
-            });
-        else
-            hipLaunchKernelGGL(labor_count_scan_kernel, dim3(tiles), dim3(kBlock), 0, p.st, s->g, dst, n_dst_dev, p.info.n_seeds, rows, p.info.fanouts[l],
-                               labor_key(p.seed, p.step, l, p.layer_dependency), s->counts_dev + l, s->status, s->ticket, s->ticket_total,
-                               s->scan_gen & 0x3FFFFFFFull, p.layers[l].indptr_local, p.items_cap[l],
-                               std::min<int64_t>(kItemLimit, p.layers[l].edge_cap), p.pin_dev + l);
-        s->ticket_total += (unsigned long long)tiles;
-        return COALA_OK;
-    }
-    const int tiles = grid1d(p.dst_cap[l], kTile, kMaxTiles);
-    hipLaunchKernelGGL(degree_scan_kernel, dim3(tiles), dim3(kBlock), 0, p.st, s->g, dst, n_dst_dev, p.info.n_seeds, s->counts_dev + l, s->status,
-                       s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, p.layers[l].indptr_local, p.items_cap[l],
-                       std::min<int64_t>(kItemLimit, p.layers[l].edge_cap), p.pin_dev + l);
+    const bool full = p.info.fanouts[l] == kFull;
+    int rows = full ? kTile : 64; // destination nodes per tile; LABOR, relations: the smallest power of two with which dst_cap fits kMaxTiles tiles
+    while (rows < kTile && (p.dst_cap[l] + rows - 1) / rows > kMaxTiles) rows <<= 1;
+    const int tiles = grid1d(p.dst_cap[l], rows, kMaxTiles);
+    auto launch = [&](auto kernel, auto... head) { // the three kernels end alike: the scan state, the layer's indptr and its limits
+        hipLaunchKernelGGL(kernel, dim3(tiles), dim3(kBlock), 0, p.st, s->g, head..., s->counts_dev + l, s->status, s->ticket, s->ticket_total,
+                           s->scan_gen & 0x3FFFFFFFull, p.layers[l].indptr_local, p.items_cap[l],
+                           std::min<int64_t>(kItemLimit, p.layers[l].edge_cap), p.pin_dev + l);
+    };
+    if (full)
+        launch(degree_scan_kernel, dst, n_dst_dev, p.info.n_seeds);
+    else if (p.kind == Kind::rel)
+        dispatch_group(rel_group(p.rel[l]), [&](auto gs_c) {
+            launch(rel_count_scan_kernel<decltype(gs_c)::value>, p.etype, p.rel[l], dst, n_dst_dev, p.info.n_seeds, rows);
+        });
+    else
+        launch(labor_count_scan_kernel, dst, n_dst_dev, p.info.n_seeds, rows, p.info.fanouts[l], labor_key(p.seed, p.step, l, p.layer_dependency));
     s->ticket_total += (unsigned long long)tiles;
     return COALA_OK;
-}
-
-WalkParams walk_params(const coala_sampler_walk_t& w) { return {w.num_traversals, w.num_random_walks, w.term_threshold}; }
-
-// walk_select_kernel for layer l: its dynamic LDS holds the visits (int64) and their counts (int32) of the kBlock / GS rows of a block.
-template <int GS>
-void launch_walk_select(coala_sampler_t* s, const Plan& p, int l, dim3 grid, const int64_t* dst, const int64_t* n_dst_dev) {
-    const WalkParams wp = walk_params(*p.walk);
-    const size_t lds = (size_t)(kBlock / GS) * (size_t)(wp.W * wp.T) * (sizeof(int64_t) + sizeof(int32_t));
-    hipLaunchKernelGGL(walk_select_kernel<GS>, grid, dim3(kBlock), lds, p.st, s->g, dst, n_dst_dev, p.info.n_seeds, p.info.fanouts[l], wp, p.seed,
-                       p.step, l, s->nbr_global, p.visit_counts ? p.visit_counts[l] : nullptr, s->tb, s->slot_of_item);
 }
 
 // Layer l over the destination nodes dst[0 .. *n_dst_dev) (n_dst_dev null: the seeds, whose count travels as a kernel argument).
@@ -1834,7 +1837,7 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
         if (f == kFull)
             hipLaunchKernelGGL(full_insert_kernel, dim3(grid1d(p.items_cap[l], kBlock, 8192)), blk, 0, st, s->g, dst, (const int64_t*)base,
                                (const int64_t*)p.layers[l].indptr_local, s->nbr_global, s->tb, s->slot_of_item, eid);
-        else if (p.rel)
+        else if (p.kind == Kind::rel)
             dispatch_group(rel_group(p.rel[l]), [&](auto gs_c) {
                 constexpr int GS = decltype(gs_c)::value;
                 hipLaunchKernelGGL(rel_insert_kernel<GS>, dim3(grid1d(cap_l * GS, kBlock, 8192)), blk, 0, st, s->g, p.etype, p.rel[l], dst,
@@ -1850,22 +1853,25 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
         fixed_run_check(p.info, l, -1, &unused_items, &max_src, &unused_what);
     } else {
         unsigned long long* nh = s->hub_count + l;
-        dispatch_group(p.walk ? std::max(f, p.walk->num_random_walks - 1) : f, [&](auto gs_c) { // a walk layer: a lane per walk too
+        dispatch_group(p.kind == Kind::walk ? std::max(f, p.walk.W - 1) : f, [&](auto gs_c) { // a walk layer: a lane per walk too
             constexpr int GS = decltype(gs_c)::value;
             const dim3 gs(grid1d(cap_l * GS, kBlock, 8192));
-            if (p.walk)
-                launch_walk_select<GS>(s, p, l, gs, dst, n_dst_dev);
-            else if (p.temporal)
+            // a walk layer's dynamic LDS holds the visits (int64) and their counts (int32) of the kBlock / GS rows of a block
+            const size_t walk_lds = (size_t)(kBlock / GS) * (size_t)(p.walk.W * p.walk.T) * (sizeof(int64_t) + sizeof(int32_t));
+            if (p.kind == Kind::walk)
+                hipLaunchKernelGGL(walk_select_kernel<GS>, gs, blk, walk_lds, st, s->g, dst, n_dst_dev, n_seeds, f, p.walk, p.seed, p.step, l,
+                                   s->nbr_global, p.visit_counts ? p.visit_counts[l] : nullptr, s->tb, s->slot_of_item);
+            else if (p.kind == Kind::temporal)
                 hipLaunchKernelGGL(temporal_select_kernel<GS>, gs, blk, 0, st, s->g, *p.temporal, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l,
                                    s->nbr_global, s->tb, s->slot_of_item, eid);
-            else if (p.weights)
+            else if (p.kind == Kind::weighted)
                 hipLaunchKernelGGL(weighted_select_kernel<GS>, gs, blk, 0, st, s->g, p.weights, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l,
                                    s->nbr_global, s->tb, s->slot_of_item, s->hubs, nh, s->hub_cap, eid);
             else
                 hipLaunchKernelGGL(sample_insert_kernel<GS>, gs, blk, 0, st, s->g, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l, s->nbr_global, s->tb,
                                    s->slot_of_item, eid);
         });
-        if (p.weights && s->hub_cap > 0) // no launch on a graph that cannot hold a row of more than kHubDegree in-edges
+        if (p.kind == Kind::weighted && s->hub_cap > 0) // no launch on a graph that cannot hold a row of more than kHubDegree in-edges
             hipLaunchKernelGGL(weighted_select_hub_kernel, dim3((unsigned)std::min<int64_t>(std::min<int64_t>(kHubGrid, s->hub_cap), std::max<int64_t>(cap_l, 1))),
                                dim3(kHubBlock), 0, st, s->g, p.weights, dst, n_dst_dev, n_seeds, f, p.seed, p.step, l, s->nbr_global, s->tb,
                                s->slot_of_item, (const int64_t*)s->hubs, (const unsigned long long*)nh, s->hub_cap, eid);
@@ -1910,68 +1916,83 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
     return COALA_OK;
 }
 
+// A new call's stream hand-over and ring slot.  The handle's scratch (hash table, scan state) is ordered by the stream of its calls.
+int begin_call(coala_sampler_t* s, hipStream_t st, uint64_t* ticket, int* slot) {
+    HIPCHK(hipSetDevice(s->device));
+    if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0)); // behind the previous call's last kernel
+    s->last_stream = st;
+    *ticket = s->calls;
+    *slot = (int)(*ticket % kRing);
+    if (*ticket >= kRing) HIPCHK(hipEventSynchronize(s->done[*slot])); // the ring slot's previous user has finished writing it
+    return COALA_OK;
+}
+
+// The event behind the call's last kernel, and its ticket.
+int end_call(coala_sampler_t* s, int slot, hipStream_t st, int64_t* ticket_out) {
+    HIPCHK(hipEventRecord(s->done[slot], st));
+    if (ticket_out) *ticket_out = (int64_t)s->calls;
+    s->calls++;
+    return COALA_OK;
+}
+
+// The table of a first layer of items0 items, a size the host knows: normally left clean by the previous call's last kernel.
+int prepare_table(coala_sampler_t* s, uint64_t items0, hipStream_t st) {
+    const bool stale = s->clean_items == 0 || table_size((int64_t)items0) > table_size((int64_t)s->clean_items);
+    s->clean_items = 0; // from here on the table is written: a call that fails half-way leaves no clean extent behind
+    if (stale) {
+        const uint32_t t0 = table_size((int64_t)items0);
+        HIPCHK(hipMemsetAsync(s->tb.keys, 0xFF, (size_t)t0 * sizeof(long long), st));
+        HIPCHK(hipMemsetAsync(s->tb.minpos, 0xFF, (size_t)t0 * sizeof(uint32_t), st));
+    }
+    return COALA_OK;
+}
+
 // Every launch of a call with seeds: the first layer's table, then the layers, each reading its destination nodes from the one before.
 int launch_call(coala_sampler_t* s, Plan& p) {
     int rc;
-    const int n_layers = p.info.n_layers;
     const bool first_full = p.info.ragged(0);
     // what the last kernel leaves clean for the next call: the first layer's table of this call, or -- when that size is known on
     // the device only -- the extent the previous call left clean
     p.items0 = first_full ? std::max<uint64_t>(s->clean_items, 1) : (uint64_t)p.info.n_seeds * (uint64_t)(p.info.fanouts[0] + 1);
-    // the first layer's table: normally left clean by the previous call's last kernel
-    const bool stale = !first_full && (s->clean_items == 0 || table_size((int64_t)p.items0) > table_size((int64_t)s->clean_items));
-    s->clean_items = 0; // from here on the table is written: a call that fails half-way leaves no clean extent behind
-    if (stale) {
-        const uint32_t t0 = table_size((int64_t)p.items0);
-        HIPCHK(hipMemsetAsync(s->tb.keys, 0xFF, (size_t)t0 * sizeof(long long), p.st));
-        HIPCHK(hipMemsetAsync(s->tb.minpos, 0xFF, (size_t)t0 * sizeof(uint32_t), p.st));
-    }
-    if (p.weights && s->hub_cap > 0) HIPCHK(hipMemsetAsync(s->hub_count, 0, (size_t)n_layers * sizeof(unsigned long long), p.st));
+    if (first_full) s->clean_items = 0; // table_clear_kernel below clears what the degree scan finds
+    else if ((rc = prepare_table(s, p.items0, p.st))) return rc;
+    if (p.kind == Kind::weighted && s->hub_cap > 0) HIPCHK(hipMemsetAsync(s->hub_count, 0, (size_t)p.n_layers * sizeof(unsigned long long), p.st));
     if (first_full) {
         if ((rc = degree_scan(s, p, 0, p.seeds, nullptr))) return rc;
         hipLaunchKernelGGL(table_clear_kernel, dim3(grid1d(table_size(p.items_cap[0]), kBlock, 4096)), dim3(kBlock), 0, p.st, s->tb,
                            (const int64_t*)(s->counts_dev + kItemsOff));
     }
-    for (int l = 0; l < n_layers; ++l) // layer l > 0 reads its destination nodes and their count from layer l - 1's outputs
+    for (int l = 0; l < p.n_layers; ++l) // layer l > 0 reads its destination nodes and their count from layer l - 1's outputs
         if ((rc = launch_layer(s, p, l, l ? p.layers[l - 1].src_nodes : p.seeds, l ? s->counts_dev + l : nullptr))) return rc;
     s->clean_items = p.items0;
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
 
-int sample_impl(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed, uint64_t step,
-                const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
-                int64_t* ticket_out, void* stream, const float* weights, int64_t* const* edge_ids = nullptr, bool labor = false,
-                bool layer_dependency = false, const RelFan* rel = nullptr, const int32_t* etype = nullptr,
-                const coala_sampler_walk_t* walk = nullptr, int32_t* const* visit_counts = nullptr, const Temporal* temporal = nullptr) {
-    int rc;
-    if ((rc = check_call(s, seeds, n_seeds, fanouts, n_layers, layers, bucketing, labor, rel != nullptr))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(s->device));
-    // the handle's scratch (hash table, scan state) is ordered by the stream of its calls: a caller that moves to another stream
-    // first waits there for the previous call's last kernel
-    if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
-    s->last_stream = st;
-    Plan p{seeds, seed, step, layers, bucketing, weights, edge_ids, st, layer_dependency, rel, etype, walk, visit_counts, temporal};
-    if ((rc = plan_call(p, n_seeds, fanouts, n_layers, bucketing ? bucketing->n_parts : 0, labor))) return rc;
-    if ((rc = grow_workspace(s, p))) return rc;
-    const uint64_t ticket = s->calls;
-    const int slot = (int)(ticket % kRing);
-    if (ticket >= kRing) HIPCHK(hipEventSynchronize(s->done[slot])); // the ring slot's previous user has finished writing it
+int sample_impl(coala_sampler_t* s, const Call& c) {
+    int rc, slot;
+    if ((rc = check_call(s, c))) return rc;
+    Plan p{c};
+    if ((rc = plan_call(p))) return rc;
+    uint64_t ticket;
+    if ((rc = begin_call(s, c.st, &ticket, &slot))) return rc;
+    if ((rc = grow_workspace(s, c.st, p.info.n_parts, (uint64_t)p.items_cap[c.n_layers - 1], p.max_items, p.max_nbr))) return rc;
     p.pin_dev = s->counts_pinned_dev + (size_t)slot * kSlot;
     s->ring[slot] = p.info;
-    if ((rc = n_seeds == 0 ? empty_call(p, s->counts_pinned + (size_t)slot * kSlot) : launch_call(s, p))) return rc;
-    HIPCHK(hipEventRecord(s->done[slot], st));
-    s->calls++;
-    if (ticket_out) *ticket_out = (int64_t)ticket;
-    if (n_src_host || n_edges_host) return wait_impl(s, (int64_t)ticket, n_src_host, n_edges_host, nullptr);
+    if ((rc = c.n_seeds == 0 ? empty_call(p, s->counts_pinned + (size_t)slot * kSlot) : launch_call(s, p))) return rc;
+    if ((rc = end_call(s, slot, c.st, c.ticket_out))) return rc;
+    if (c.n_src_host || c.n_edges_host) return wait_impl(s, (int64_t)ticket, c.n_src_host, c.n_edges_host, nullptr);
     return COALA_OK;
 }
 
-// An edge batch takes a ring slot and the handle's scratch exactly as a sample of one fixed layer over n (2 + k) items does: the same
-// stream hand-over, the same clean-table bookkeeping (launch_call), three launches, the counts into the slot's pinned words.
-int edge_batch_impl(coala_sampler_t* s, const int64_t* eids, int64_t n, int num_neg, uint64_t seed, uint64_t step, const coala_edge_batch_t* out,
-                    int64_t* ticket_out, void* stream) {
+} // namespace
+
+extern "C" {
+
+// An edge batch takes a ring slot and the handle's scratch as a sample of one fixed layer over n (2 + k) items does (begin_call,
+// prepare_table, end_call): three launches, the counts into the slot's pinned words.
+int coala_sampler_edge_batch(coala_sampler_t* s, const int64_t* eids, int64_t n, int num_neg, uint64_t seed, uint64_t step,
+                             const coala_edge_batch_t* out, int64_t* ticket_out, void* stream) {
     if (!s || !out || (!eids && n > 0)) return fail(COALA_EINVAL, "null argument");
     if (num_neg < 0 || num_neg > kMaxNeg) return fail(COALA_EINVAL, "num_neg %d outside 0..%d", num_neg, kMaxNeg);
     if (n < 0 || n > kItemLimit) return fail(COALA_EINVAL, "bad edge count");
@@ -1981,34 +2002,20 @@ int edge_batch_impl(coala_sampler_t* s, const int64_t* eids, int64_t n, int num_
                     (long long)items, (long long)kItemLimit);
     if (n > 0 && (!out->seed_nodes || !out->pos_src || !out->pos_dst || (num_neg > 0 && !out->neg_dst))) return fail(COALA_EINVAL, "null buffer");
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(s->device));
-    if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0));
-    s->last_stream = st;
-    Plan p{};
-    p.st = st;
-    p.info.n_layers = 1;
-    p.info.n_seeds = items;
-    p.info.edge_batch = true;
-    p.items_cap[0] = items;
-    p.max_items = p.max_nbr = (uint64_t)items;
-    int rc;
-    if ((rc = grow_workspace(s, p))) return rc;
-    const uint64_t ticket = s->calls;
-    const int slot = (int)(ticket % kRing);
-    if (ticket >= kRing) HIPCHK(hipEventSynchronize(s->done[slot]));
+    int rc, slot;
+    uint64_t ticket;
+    if ((rc = begin_call(s, st, &ticket, &slot))) return rc;
+    if ((rc = grow_workspace(s, st, 0, (uint64_t)items, (uint64_t)items, (uint64_t)items))) return rc;
     int64_t* pin_dev = s->counts_pinned_dev + (size_t)slot * kSlot;
-    s->ring[slot] = p.info;
+    RingInfo& r = s->ring[slot] = RingInfo{};
+    r.n_layers = 1;
+    r.n_seeds = items;
+    r.edge_batch = true;
     if (n == 0) {
         int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
         pin[0] = pin[kPinEdges] = 0;
     } else {
-        const bool stale = s->clean_items == 0 || table_size(items) > table_size((int64_t)s->clean_items);
-        s->clean_items = 0;
-        if (stale) {
-            const uint32_t t0 = table_size(items);
-            HIPCHK(hipMemsetAsync(s->tb.keys, 0xFF, (size_t)t0 * sizeof(long long), st));
-            HIPCHK(hipMemsetAsync(s->tb.minpos, 0xFF, (size_t)t0 * sizeof(uint32_t), st));
-        }
+        if ((rc = prepare_table(s, (uint64_t)items, st))) return rc;
         const dim3 blk(kBlock);
         hipLaunchKernelGGL(edge_items_kernel, dim3(grid1d(items, kBlock, 8192)), blk, 0, st, s->g, s->num_edges, eids, n, num_neg, seed, step,
                            s->nbr_global, s->tb, s->slot_of_item, s->edge_bad);
@@ -2025,25 +2032,12 @@ int edge_batch_impl(coala_sampler_t* s, const int64_t* eids, int64_t n, int num_
         s->clean_items = (uint64_t)items;
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(s->done[slot], st));
-    s->calls++;
-    if (ticket_out) *ticket_out = (int64_t)ticket;
-    return COALA_OK;
-}
-} // namespace
-
-extern "C" {
-
-int coala_sampler_edge_batch(coala_sampler_t* s, const int64_t* eids, int64_t n, int num_neg, uint64_t seed, uint64_t step,
-                             const coala_edge_batch_t* out, int64_t* ticket_out, void* stream) {
-    return edge_batch_impl(s, eids, n, num_neg, seed, step, out, ticket_out, stream);
+    return end_call(s, slot, st, ticket_out);
 }
 
 int coala_sampler_edge_batch_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_nodes_host, int64_t* n_bad_host) {
-    if (!s) return fail(COALA_EINVAL, "null sampler");
-    if (ticket < 0 || (uint64_t)ticket >= s->calls || s->calls - (uint64_t)ticket > kRing)
-        return fail(COALA_EINVAL, "ticket %lld is not one of the last %d calls", (long long)ticket, kRing);
-    const int slot = (int)((uint64_t)ticket % kRing);
+    int slot;
+    if (int rc = ring_slot(s, ticket, &slot)) return rc;
     if (!s->ring[slot].edge_batch) return fail(COALA_EINVAL, "ticket %lld is not an edge batch", (long long)ticket);
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipEventSynchronize(s->done[slot]));
@@ -2063,17 +2057,10 @@ int coala_sampler_create(int device, const int64_t* indptr, const int64_t* indic
     s->g = Graph{indptr, indices, num_nodes};
     s->num_edges = num_edges;
     s->hub_cap = std::min<int64_t>(num_nodes, num_edges / (kHubDegree + 1));
-    bool ok = hipMalloc((void**)&s->status, kMaxTiles * sizeof(unsigned long long)) == hipSuccess &&
-              hipMemset(s->status, 0, kMaxTiles * sizeof(unsigned long long)) == hipSuccess &&
-              hipMalloc((void**)&s->ticket, sizeof(unsigned long long)) == hipSuccess &&
-              hipMemset(s->ticket, 0, sizeof(unsigned long long)) == hipSuccess &&
-              hipMalloc((void**)&s->counts_dev, kCountsWords * sizeof(int64_t)) == hipSuccess &&
-              hipMemset(s->counts_dev, 0, kCountsWords * sizeof(int64_t)) == hipSuccess &&
-              hipMalloc((void**)&s->hub_count, COALA_SAMPLER_MAX_LAYERS * sizeof(unsigned long long)) == hipSuccess &&
-              hipMemset(s->hub_count, 0, COALA_SAMPLER_MAX_LAYERS * sizeof(unsigned long long)) == hipSuccess &&
+    auto zeroed = [](auto** p, size_t n) { return hipMalloc((void**)p, n * sizeof(**p)) == hipSuccess && hipMemset(*p, 0, n * sizeof(**p)) == hipSuccess; };
+    bool ok = zeroed(&s->status, kMaxTiles) && zeroed(&s->ticket, 1) && zeroed(&s->counts_dev, kCountsWords) &&
+              zeroed(&s->hub_count, COALA_SAMPLER_MAX_LAYERS) && zeroed(&s->edge_bad, 1) &&
               (s->hub_cap == 0 || hipMalloc((void**)&s->hubs, (size_t)s->hub_cap * sizeof(int64_t)) == hipSuccess) &&
-              hipMalloc((void**)&s->edge_bad, sizeof(unsigned long long)) == hipSuccess &&
-              hipMemset(s->edge_bad, 0, sizeof(unsigned long long)) == hipSuccess &&
               hipHostMalloc((void**)&s->counts_pinned, kRing * kSlot * sizeof(int64_t), hipHostMallocMapped) == hipSuccess &&
               hipHostGetDevicePointer((void**)&s->counts_pinned_dev, s->counts_pinned, 0) == hipSuccess;
     for (int i = 0; i < kRing && ok; ++i) ok = hipEventCreateWithFlags(&s->done[i], hipEventDisableTiming) == hipSuccess;
@@ -2122,13 +2109,15 @@ int coala_sampler_sample(coala_sampler_t* s, const int64_t* seeds, int64_t n_see
         layers[l] = coala_sampler_layer_t{src_nodes_out[l], nbr_local_out[l], nullptr, cap * (f + 1), cap * f};
         cap = std::min(cap * (f + 1), kItemLimit + 1);
     }
-    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, nullptr, bucketing, ticket_out, stream, nullptr);
+    return sample_impl(s, Call{Kind::uniform, seeds, n_seeds, fanouts, n_layers, seed, step, layers, nullptr, n_src_host, nullptr, bucketing, ticket_out,
+                               (hipStream_t)stream});
 }
 
 int coala_sampler_sample_layers(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed,
                                 uint64_t step, const coala_sampler_layer_t* layers, int64_t* n_src_host, int64_t* n_edges_host,
                                 const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
-    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream, nullptr);
+    return coala_sampler_sample_layers_edge_ids(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, nullptr, nullptr, n_src_host, n_edges_host,
+                                                bucketing, ticket_out, stream);
 }
 
 int coala_sampler_sample_layers_weighted(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
@@ -2136,24 +2125,28 @@ int coala_sampler_sample_layers_weighted(coala_sampler_t* s, const int64_t* seed
                                          int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
                                          int64_t* ticket_out, void* stream) {
     if (!edge_weights) return fail(COALA_EINVAL, "null edge_weights");
-    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream,
-                       edge_weights);
+    return coala_sampler_sample_layers_edge_ids(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, edge_weights, nullptr, n_src_host,
+                                                n_edges_host, bucketing, ticket_out, stream);
 }
 
 int coala_sampler_sample_layers_edge_ids(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
                                          uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const float* edge_weights,
                                          int64_t* const* edge_ids_out, int64_t* n_src_host, int64_t* n_edges_host,
                                          const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
-    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream,
-                       edge_weights, edge_ids_out);
+    Call c{edge_weights ? Kind::weighted : Kind::uniform, seeds, n_seeds, fanouts, n_layers, seed, step, layers, edge_ids_out, n_src_host, n_edges_host,
+           bucketing, ticket_out, (hipStream_t)stream};
+    c.weights = edge_weights;
+    return sample_impl(s, c);
 }
 
 int coala_sampler_sample_layers_labor(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
                                       uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, int64_t* const* edge_ids_out,
                                       int layer_dependency, int64_t* n_src_host, int64_t* n_edges_host,
                                       const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
-    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream,
-                       nullptr, edge_ids_out, true, layer_dependency != 0);
+    Call c{Kind::labor, seeds, n_seeds, fanouts, n_layers, seed, step, layers, edge_ids_out, n_src_host, n_edges_host, bucketing, ticket_out,
+           (hipStream_t)stream};
+    c.layer_dependency = layer_dependency != 0;
+    return sample_impl(s, c);
 }
 
 int coala_sampler_sample_layers_rel(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* rel_fanouts, int num_rels,
@@ -2163,7 +2156,7 @@ int coala_sampler_sample_layers_rel(coala_sampler_t* s, const int64_t* seeds, in
     if (!rel_fanouts) return fail(COALA_EINVAL, "null argument");
     if (!etype) return fail(COALA_EINVAL, "null etype");
     if (num_rels < 1 || num_rels > kMaxRels) return fail(COALA_EINVAL, "num_rels must be 1..%d", kMaxRels);
-    if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
+    if (int rc = check_n_layers(n_layers)) return rc;
     RelFan fan[COALA_SAMPLER_MAX_LAYERS] = {};
     int32_t kind[COALA_SAMPLER_MAX_LAYERS]; // what the rest of the call needs of a layer: -1 (all -1: the full layer), else 0
     for (int l = 0; l < n_layers; ++l) {
@@ -2179,8 +2172,11 @@ int coala_sampler_sample_layers_rel(coala_sampler_t* s, const int64_t* seeds, in
         if (!some) return fail(COALA_EINVAL, "layer %d: every relation has fan-out 0", l);
         kind[l] = all_full ? kFull : 0;
     }
-    return sample_impl(s, seeds, n_seeds, kind, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream, nullptr,
-                       edge_ids_out, false, false, fan, etype);
+    Call c{Kind::rel, seeds, n_seeds, kind, n_layers, seed, step, layers, edge_ids_out, n_src_host, n_edges_host, bucketing, ticket_out,
+           (hipStream_t)stream};
+    c.rel = fan;
+    c.etype = etype;
+    return sample_impl(s, c);
 }
 
 int coala_sampler_sample_layers_walk(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
@@ -2188,18 +2184,18 @@ int coala_sampler_sample_layers_walk(coala_sampler_t* s, const int64_t* seeds, i
                                      int32_t* const* visit_counts_out, int64_t* n_src_host, int64_t* n_edges_host,
                                      const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
     if (!fanouts || !layers || !walk) return fail(COALA_EINVAL, "null argument");
-    if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
+    if (int rc = check_n_layers(n_layers)) return rc;
     const int T = walk->num_traversals, W = walk->num_random_walks;
     if (T < 1 || T > kMaxWalkLength) return fail(COALA_EINVAL, "num_traversals %d outside 1..%d", T, kMaxWalkLength);
     if (W < 1 || W > kMaxWalks) return fail(COALA_EINVAL, "num_random_walks %d outside 1..%d", W, kMaxWalks);
     if (W * T > kMaxVisits) return fail(COALA_EINVAL, "num_random_walks * num_traversals = %d: over the limit of %d visits", W * T, kMaxVisits);
     if (walk->term_threshold >= kWalkThresholdMax) return fail(COALA_EINVAL, "term_threshold must be below 2^53 (termination_prob < 1)");
-    for (int l = 0; l < n_layers; ++l) {
-        if (fanouts[l] < 1 || fanouts[l] > 32) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (a walk layer keeps 1..32 neighbours)", fanouts[l]);
-        if (layers[l].indptr_local) return fail(COALA_EINVAL, "layer %d: a walk layer is fixed-stride, indptr_local must be NULL", l);
-    }
-    return sample_impl(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, bucketing, ticket_out, stream, nullptr,
-                       nullptr, false, false, nullptr, nullptr, walk, visit_counts_out);
+    if (int rc = check_fixed_layers(fanouts, layers, n_layers, "walk", "keeps 1..32 neighbours")) return rc;
+    Call c{Kind::walk, seeds, n_seeds, fanouts, n_layers, seed, step, layers, nullptr, n_src_host, n_edges_host, bucketing, ticket_out,
+           (hipStream_t)stream};
+    c.walk = WalkParams{T, W, walk->term_threshold};
+    c.visit_counts = visit_counts_out;
+    return sample_impl(s, c);
 }
 
 int coala_sampler_sample_layers_temporal(coala_sampler_t* s, const int64_t* seed_codes, int64_t n_seeds, const int32_t* fanouts, int n_layers,
@@ -2208,13 +2204,10 @@ int coala_sampler_sample_layers_temporal(coala_sampler_t* s, const int64_t* seed
                                          int64_t* n_src_host, int64_t* n_edges_host, int64_t* ticket_out, void* stream) {
     if (!fanouts || !layers) return fail(COALA_EINVAL, "null argument");
     if (!edge_ts) return fail(COALA_EINVAL, "null edge_ts");
-    if (n_layers < 1 || n_layers > COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "n_layers must be 1..%d", COALA_SAMPLER_MAX_LAYERS);
+    if (int rc = check_n_layers(n_layers)) return rc;
     if (strategy != 0 && strategy != 1) return fail(COALA_EINVAL, "strategy %d: 0 (uniform) or 1 (last)", strategy);
     if (n_slots < 0 || (n_slots > 0 && !slot_time)) return fail(COALA_EINVAL, "slot_time: %lld query times and a null table", (long long)n_slots);
-    for (int l = 0; l < n_layers; ++l) {
-        if (fanouts[l] < 1 || fanouts[l] > 32) return fail(COALA_EINVAL, "fan-out %d outside 1..32 (a temporal layer has a fixed fan-out)", fanouts[l]);
-        if (layers[l].indptr_local) return fail(COALA_EINVAL, "layer %d: a temporal layer is fixed-stride, indptr_local must be NULL", l);
-    }
+    if (int rc = check_fixed_layers(fanouts, layers, n_layers, "temporal", "has a fixed fan-out")) return rc;
     if (!s) return fail(COALA_EINVAL, "null argument");
     int node_bits = 0, slot_bits = 0; // bit lengths of num_nodes and of n_slots - 1
     while ((s->g.num_nodes >> node_bits) != 0) ++node_bits;
@@ -2223,8 +2216,10 @@ int coala_sampler_sample_layers_temporal(coala_sampler_t* s, const int64_t* seed
         return fail(COALA_EINVAL, "%lld query times on a graph of %lld nodes: a (node, time) pair takes %d + %d bits, over the 62 of a code",
                     (long long)n_slots, (long long)s->g.num_nodes, node_bits, slot_bits);
     const Temporal tp{edge_ts, slot_time, n_slots, node_bits, strategy == 1, inclusive != 0};
-    return sample_impl(s, seed_codes, n_seeds, fanouts, n_layers, seed, step, layers, n_src_host, n_edges_host, nullptr, ticket_out, stream, nullptr,
-                       edge_ids_out, false, false, nullptr, nullptr, nullptr, nullptr, &tp);
+    Call c{Kind::temporal, seed_codes, n_seeds, fanouts, n_layers, seed, step, layers, edge_ids_out, n_src_host, n_edges_host, nullptr, ticket_out,
+           (hipStream_t)stream};
+    c.temporal = &tp;
+    return sample_impl(s, c);
 }
 
 int coala_sampler_random_walk(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t term_threshold,
