@@ -308,6 +308,29 @@ class _CacheBase:
         else:
             check(_lib.coala_cache_read_feature(self._h, int(out_ptr), int(idx_ptr), int(n), current_stream()))
 
+    _WRITE_MODES = {"assign": 0, "add": 1}
+
+    def write_rows(self, ids_ptr, n, src_ptr, mode="assign", alpha=1.0):
+        """Write-through update of n table rows on the current stream (coala_cache_write_rows): 'assign' row(id) = src[i], 'add'
+        row(id) = fma(alpha, src[i], row(id)); the cold row and every cache line that holds the id get the new value.  ids (device
+        int64[n]) must be pairwise distinct.  An integer mode is passed through as it is."""
+        m = self._WRITE_MODES.get(mode, mode) if isinstance(mode, str) else mode
+        if isinstance(m, str):
+            raise ValueError(f"write_rows: mode must be 'assign' or 'add', not {mode!r}")
+        if native is not None:
+            native.cache_write_rows(self._h.value or 0, int(ids_ptr), int(n), int(src_ptr), int(m), float(alpha), current_stream())
+        else:
+            check(_lib.coala_cache_write_rows(self._h, int(ids_ptr) or None, int(n), int(src_ptr) or None, int(m), float(alpha), current_stream()))
+
+    def adagrad_rows(self, ids_ptr, n, grad_ptr, state_ptr, lr, eps=1e-10):
+        """Sparse Adagrad step on n table rows on the current stream (coala_cache_adagrad_rows): s = state[id] + g * g, state[id] = s,
+        row(id) -= lr * g / (sqrt(s) + eps).  state: device-visible fp32 [num_rows, dim], not cached."""
+        if native is not None:
+            native.cache_adagrad_rows(self._h.value or 0, int(ids_ptr), int(n), int(grad_ptr), int(state_ptr), float(lr), float(eps), current_stream())
+        else:
+            check(_lib.coala_cache_adagrad_rows(self._h, int(ids_ptr) or None, int(n), int(grad_ptr) or None, int(state_ptr) or None, float(lr),
+                                                float(eps), current_stream()))
+
     def _serve(self, out_ptr, ids_ptr, n):
         if native is not None:
             native.cache_serve(self._h.value or 0, int(out_ptr), int(ids_ptr), int(n), current_stream())

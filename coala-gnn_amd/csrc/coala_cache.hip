@@ -129,6 +129,11 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int src_lane) {
     return ((uint64_t)hi << 32) | lo;
 }
 
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
+    const uint32_t lo = __shfl((int)(uint32_t)v, src), hi = __shfl((int)(uint32_t)(v >> 32), src);
+    return ((uint64_t)hi << 32) | lo;
+}
+
 // native clang vectors (not HIP's float4 struct) so the in-flight rows stay in VGPRs
 typedef float vfloat4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long vu64x2 __attribute__((ext_vector_type(2)));
@@ -400,15 +405,128 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, kK1MinWaves) void probe_gather_ke
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------- KW
+// Write-through row update (coala_cache_write_rows / coala_cache_adagrad_rows): one kernel over (line size, VEC, tag width, op).
+// A wave takes the SPL rows whose tag sets one wave-wide 16-B load fetches (8 with 32-bit tags, 4 with 64-bit ones), exactly as a tag step of
+// K1: every lane compares its own KPL tags, and an OR over the LPS lanes of a row -- K1's DPP ladder with | in place of min -- leaves the row's
+// whole 32-way match mask in each of them.  The rows are then moved RPP at a time: the old value comes from the lowest matching line when there is
+// one (no host-link read) and from the cold row otherwise, the new one goes to the cold row and to EVERY line of the mask.  Nothing else of the
+// table is written: no tag, cursor, colour or hit / miss counter, and no float of a line past `dim`.  Rejected ids add to one counter of their own
+// (stats word kStatWriteBad: K2's per-block sums are tied to the rows a probe counted).
+// Latency is hidden across waves, not inside one (a wave has one row(-pair) in flight): the grid is one wave per chunk up to the caps at the launch.
+// Measured (tools/embedding_probe.py, profiles/r17_embedding_update.txt; pinned table, 24.6 k and 60.9 k rows): 512-B rows, all cached, go to the
+// host at 53.4-53.9 GB/s in all three ops, 97-101 % of a pinned hipMemcpy of the same bytes in the same process; 4-KiB rows at 55 GB/s (assign,
+// 97 %) and, with a third to three quarters of the old values read back over the link, 47-51 GB/s (add, Adagrad: 84-91 %).  An Adagrad state in
+// pinned host memory adds a read and a write of the link per element: 23-24 GB/s of rows (41-43 %).
+enum { kOpAssign = 0, kOpAdd = 1, kOpAdagrad = 2 };
+constexpr int kStatWriteBad = 2 * kStatBlocks + kFillSlots + 1;   // index into CacheDev::stats (64-bit words), behind K2's tickets and flags
+constexpr int kStatWords = kStatWriteBad + 1;
+
+template <int OP> __device__ __forceinline__ float write_op(float x, float old, float& st, float a, float eps) {
+    if (OP == kOpAssign) return x;
+    if (OP == kOpAdd) return __builtin_fmaf(a, x, old);
+    const float s = st + x * x;
+    st = s;
+    return old - a * x / (__builtin_sqrtf(s) + eps);
+}
+template <int OP> __device__ __forceinline__ vfloat4 write_op(vfloat4 x, vfloat4 old, vfloat4& st, float a, float eps) {
+    vfloat4 r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float s = st[k];
+        r[k] = write_op<OP>(x[k], old[k], s, a, eps);
+        st[k] = s;
+    }
+    return r;
+}
+
+template <int CD, int VEC, typename TAG, int OP>
+__global__ __launch_bounds__(256) void write_rows_kernel(const int64_t* __restrict__ ids, const float* __restrict__ src, float* __restrict__ state,
+                                                         int64_t n, float a, float eps, CacheDev c) {
+    using G = Geo<CD, VEC, 1>;
+    using V = typename VecT<VEC>::type;
+    using TG = TagGeo<TAG>;
+    using TV = typename TG::vec;
+    constexpr int R = TG::SPL;            // rows per chunk: the sets of one wave-wide tag load
+    static_assert(R % G::RPP == 0, "a chunk is a whole number of passes");
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    const int64_t n_chunks = (n + R - 1) / R;
+    const uint32_t nunits = c.dim / VEC;
+    const TAG* __restrict__ keys = reinterpret_cast<const TAG*>(c.keys);
+    float* cold = const_cast<float*>(c.cold);   // (the header: a handle that is written to fronts a writable table)
+    const int sub = (G::RPP == 2) ? (lane >> 5) : 0;
+    const int l_in = lane & (G::LPR - 1);
+    const uint32_t lane_way0 = (uint32_t)((lane % TG::LPS) * TG::KPL);
+
+    for (int64_t chunk = wave; chunk < n_chunks; chunk += n_waves) {   // (wave-uniform trip count: every lane is active at the DPP steps)
+        // ---- probe: lane l looks at row l / LPS of the chunk, tags KPL * (l % LPS) .. + KPL - 1 of that row's set
+        const int64_t i_l = chunk * R + lane / TG::LPS;
+        const bool valid = i_l < n;
+        const uint64_t id_l = valid ? (uint64_t)ids[i_l] : 0;
+        const bool ok = valid && id_l < c.num_rows;
+        const uint32_t set_l = ok ? (uint32_t)set_of(c, id_l) : 0u;
+        TV kk = TV(TG::EMPTY);
+        if (ok) kk = *reinterpret_cast<const TV*>(keys + (uint64_t)set_l * COALA_WAYS + lane_way0);
+        uint32_t mask = 0u;
+#pragma unroll
+        for (int k = 0; k < TG::KPL; ++k)
+            if (kk[k] == (TAG)id_l) mask |= 1u << (lane_way0 + (uint32_t)k);
+        if (!ok) mask = 0u;   // (an id outside the table may equal the empty tag)
+        mask |= dpp_u32<0xB1>(mask);    // lane ^ 1
+        mask |= dpp_u32<0x4E>(mask);    // lane ^ 2
+        mask |= dpp_u32<0x141>(mask);   // the other quad of the 8 lanes
+        if (TG::LPS == 16) mask |= dpp_u32<0x140>(mask);   // the other half of the 16 lanes
+        const uint64_t bad_b = __ballot(valid && !ok && (lane % TG::LPS) == 0);
+        if (bad_b && lane == 0) atomicAdd(c.stats + kStatWriteBad, (unsigned long long)__builtin_popcountll(bad_b));
+
+        // ---- rows, RPP at a time: row q of the chunk lives in lane LPS * q of the probe
+#pragma unroll 1
+        for (int p = 0; p < R / G::RPP; ++p) {
+            const int q = p * G::RPP + sub;
+            const uint32_t m = (uint32_t)__shfl((int)mask, TG::LPS * q);
+            const uint32_t set = (uint32_t)__shfl((int)set_l, TG::LPS * q);
+            const uint64_t id = shfl64(id_l, TG::LPS * q);
+            const bool live = __shfl((int)ok, TG::LPS * q) != 0;
+            if (!live) continue;
+            const int64_t i = chunk * R + q;
+            const V* xs = reinterpret_cast<const V*>(src + i * (int64_t)c.dim);
+            V* cold_row = reinterpret_cast<V*>(cold + id * (uint64_t)c.dim);   // (never partitioned: refused on the host)
+            V* st_row = OP == kOpAdagrad ? reinterpret_cast<V*>(state + id * (uint64_t)c.dim) : nullptr;
+            float* set_lines = c.lines + (uint64_t)set * COALA_WAYS * CD;
+            const V* old_row = m ? reinterpret_cast<const V*>(set_lines + (uint64_t)__builtin_ctz(m) * CD) : cold_row;
+            V x[G::VPL], old[G::VPL], st[G::VPL];
+#pragma unroll
+            for (int v = 0; v < G::VPL; ++v) {
+                const uint32_t u = v * G::LPR + l_in;
+                x[v] = V(0.0f); old[v] = V(0.0f); st[v] = V(0.0f);
+                if (u < nunits) {
+                    x[v] = nt_load(xs + u);
+                    if (OP != kOpAssign) old[v] = old_row[u];
+                    if (OP == kOpAdagrad) st[v] = st_row[u];
+                }
+            }
+#pragma unroll
+            for (int v = 0; v < G::VPL; ++v) {
+                const uint32_t u = v * G::LPR + l_in;
+                if (u < nunits) {
+                    const V nv = write_op<OP>(x[v], old[v], st[v], a, eps);
+                    if (OP == kOpAdagrad) st_row[u] = st[v];
+                    cold_row[u] = nv;
+                    for (uint32_t mm = m; mm; mm &= mm - 1)
+                        reinterpret_cast<V*>(set_lines + (uint64_t)__builtin_ctz(mm) * CD)[u] = nv;
+                }
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------- K2
-// Rank + fill.  isolated_cache.h:197-210 (round robin in batch order), :417-474 (miss path), :323-331 (cold read).
+// Rank + fill. isolated_cache.h:197-210 (round robin in batch order), :417-474 (miss path), :323-331 (cold read).
 // Hazard-free in ONE kernel: every reader of a set's cursor recovers the value before the batch whether or not the set's
 // first-ranked miss has already advanced it (generation tag), every way touched in this batch has exactly one winner, and only
 // winners touch keys / color_meta / lines.
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
-    const uint32_t lo = __shfl((int)(uint32_t)v, src), hi = __shfl((int)(uint32_t)(v >> 32), src);
-    return ((uint64_t)hi << 32) | lo;
-}
 
 template <int CD, int VEC, bool REDIR = false, int NP = 4>
 __global__ __launch_bounds__(256) void miss_fill_kernel(CacheDev c, const int64_t* __restrict__ idx, float* __restrict__ out,
@@ -888,6 +1006,7 @@ struct coala_cache {
     hipEvent_t order_ev = nullptr;
     uint64_t table_bytes = 0;
     LaunchShape shape;                    // K1 / K2 launch shapes (launch_shape)
+    bool host_tier = false;               // the cold table is host memory (behind the host link)
     int32_t* color_pin = nullptr;         // pinned staging for coala_cache_color_counts
     int32_t* color_pin_async = nullptr;   // pinned staging + event of a pending coala_cache_color_counts_async
     hipEvent_t color_ev = nullptr;
@@ -1102,12 +1221,12 @@ int coala_cache_create(const coala_cache_config_t* cfg, coala_cache_t** out) {
         if ((rc = alloc((void**)&d.set_cnt, sets * 8))) break;
         if ((rc = alloc((void**)&d.color_meta, slots * 4))) break;
         if ((rc = alloc((void**)&d.set_head, sets * 8))) break;
-        if ((rc = alloc((void**)&d.stats, (kStatBlocks * 2 + kFillSlots + 1) * 8))) break;   // (+ K2's ticket counters, 2 x kFillSlots x 4 B, and the two "something to fill" flags behind the per-block sums)
+        if ((rc = alloc((void**)&d.stats, kStatWords * 8))) break;   // (+ K2's ticket counters, 2 x kFillSlots x 4 B, the two "something to fill" flags and the write kernel's rejected ids behind the per-block sums)
         if ((rc = alloc((void**)&d.lines, slots * (uint64_t)cd * 4))) break;
         if ((rc = alloc((void**)&h->route_bases, 65 * 8))) break;
         if (hipMemset(d.keys, 0xFF, slots * tag_bytes) != hipSuccess || hipMemset(d.set_cnt, 0, sets * 8) != hipSuccess ||
             hipMemset(d.color_meta, 0, slots * 4) != hipSuccess || hipMemset(d.set_head, 0, sets * 8) != hipSuccess ||
-            hipMemset(d.stats, 0, (kStatBlocks * 2 + kFillSlots + 1) * 8) != hipSuccess) {
+            hipMemset(d.stats, 0, kStatWords * 8) != hipSuccess) {
             rc = fail(COALA_EHIP, "hipMemset failed");
             break;
         }
@@ -1136,6 +1255,7 @@ int coala_cache_create(const coala_cache_config_t* cfg, coala_cache_t** out) {
             hipPointerAttribute_t attr;
             const bool host_tier = hipPointerGetAttributes(&attr, cfg->cold_table) == hipSuccess && attr.type == hipMemoryTypeHost;
             (void)hipGetLastError(); // an unregistered pointer is reported as an error: not ours to keep
+            h->host_tier = host_tier;
             h->shape = launch_shape(d.cache_dim, host_tier);
 #ifdef COALA_DEV_KNOBS
             apply_dev_knobs(h->shape);
@@ -1538,6 +1658,57 @@ int coala_cache_scatter(coala_cache_t* h, float* out, const float* src, const in
     return coala_cache_scatter_ranges(h, out, src, map, &b, &n, 1, stream);
 }
 
+// coala_cache_write_rows / coala_cache_adagrad_rows: every refusal comes before the first launch; one kernel (write_rows_kernel).
+static int write_rows_impl(coala_cache_t* h, const int64_t* ids, int64_t n, const float* src, float* state, int op, float a, float eps,
+                           void* stream) {
+    if (!h) return fail(COALA_EINVAL, "null handle");
+    if (n < 0 || n > 0x7FFFFFFFll) return fail(COALA_EINVAL, "n=%lld out of range", (long long)n);
+    if (op < kOpAssign || op > kOpAdagrad) return fail(COALA_EINVAL, "write mode %d outside 0..1", op);
+    if (h->cfg.n_gpus != 1 || (h->cfg.flags & (COALA_FLAG_DISTRIBUTED | COALA_FLAG_COLD_PARTITIONED)))
+        return fail(COALA_EINVAL, "row writes need an isolated cache of one GPU (n_gpus=%d, flags=0x%x): a second cache over the same table would keep stale lines",
+                    h->cfg.n_gpus, h->cfg.flags);
+    if (h->open_batch_rows >= 0)
+        return fail(COALA_EINVAL, "a batch of %lld rows is still open (%lld filled): finish its serve_fill calls or call coala_cache_serve_abort",
+                    (long long)h->open_batch_rows, (long long)h->open_filled_rows);
+    if (n > 0 && (!ids || !src || (op == kOpAdagrad && !state))) return fail(COALA_EINVAL, "null buffer");
+    if (n == 0) return COALA_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc_ = follow_stream(h, s)) return rc_;
+    const CacheDev& d = h->d;
+    const bool vec4 = (d.dim % 4 == 0) && aligned16(d.cold) && aligned16(src) && (op != kOpAdagrad || aligned16(state));
+    int rc = dispatch_geo(d.cache_dim, vec4, [&](auto geo) -> int {
+        constexpr int CD = geo_cd(geo);
+        constexpr int VEC = geo_vec(geo);
+        auto launch = [&](auto tag_c) {
+            using TAG = decltype(tag_c);
+            const int64_t chunks = (n + TagGeo<TAG>::SPL - 1) / TagGeo<TAG>::SPL;
+            // one wave per chunk up to 4096 waves behind a host tier (a wave has at most two rows of reads and writes on the link), 32768 on HBM
+            const dim3 grid(grid_for(chunks, 4, h->host_tier ? 1024 : 8192)), block(256);
+            auto k = op == kOpAssign ? write_rows_kernel<CD, VEC, TAG, kOpAssign>
+                     : op == kOpAdd  ? write_rows_kernel<CD, VEC, TAG, kOpAdd>
+                                     : write_rows_kernel<CD, VEC, TAG, kOpAdagrad>;
+            hipLaunchKernelGGL(k, grid, block, 0, s, ids, src, state, n, a, eps, d);
+        };
+        if (d.tag32) launch(uint32_t{}); else launch(uint64_t{});
+        return COALA_OK;
+    });
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    if (h->cfg.flags & COALA_FLAG_SYNC) HIPCHK(hipStreamSynchronize(s));
+    return COALA_OK;
+}
+
+int coala_cache_write_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* src, int mode, float alpha, void* stream) {
+    if (h && mode != 0 && mode != 1) return fail(COALA_EINVAL, "write mode %d outside 0..1", mode);
+    return write_rows_impl(h, ids, n, src, nullptr, mode == 0 ? kOpAssign : kOpAdd, alpha, 0.0f, stream);
+}
+
+int coala_cache_adagrad_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* grad, float* state, float lr, float eps,
+                             void* stream) {
+    return write_rows_impl(h, ids, n, grad, state, kOpAdagrad, lr, eps, stream);
+}
+
 int coala_cache_color_counts(coala_cache_t* h, int32_t* dst, int32_t n_entries, void* stream) {
     if (!h || !dst) return fail(COALA_EINVAL, "null argument");
     if (n_entries < 0 || n_entries > h->cfg.num_colors + 1) return fail(COALA_EINVAL, "n_entries=%d exceeds num_colors+1=%d", n_entries, h->cfg.num_colors + 1);
@@ -1589,14 +1760,17 @@ int coala_cache_color_counts_finish(coala_cache_t* h, int32_t* dst, int32_t n_en
 }
 
 static int read_stats(coala_cache_t* h, hipStream_t s, uint64_t* hit, uint64_t* miss, uint64_t* bad, bool reset) {
-    std::vector<unsigned long long> part((size_t)kStatBlocks * 2);
+    std::vector<unsigned long long> part((size_t)kStatWords);   // (K2's tickets and flags come along: 72 bytes, and nothing here reads them)
     HIPCHK(hipMemcpyAsync(part.data(), h->d.stats, part.size() * 8, hipMemcpyDeviceToHost, s)); // end of epoch: a device-wide wait is fine
-    if (reset) HIPCHK(hipMemsetAsync(h->d.stats, 0, part.size() * 8, s));
+    if (reset) {
+        HIPCHK(hipMemsetAsync(h->d.stats, 0, (size_t)kStatBlocks * 2 * 8, s));
+        HIPCHK(hipMemsetAsync(h->d.stats + kStatWriteBad, 0, 8, s));
+    }
     HIPCHK(hipStreamSynchronize(s));
     uint64_t m = 0, b = 0;
     for (int i = 0; i < kStatBlocks; ++i) { m += part[2 * i]; b += part[2 * i + 1]; }
     *miss = m;
-    *bad = b;
+    *bad = b + part[kStatWriteBad];   // rejected ids of reads and of writes; only the reads' were counted in rows_total
     *hit = h->rows_total - m - b;
     if (reset) { h->cum_hit += *hit; h->cum_miss += m; h->rows_total = 0; }
     return COALA_OK;

@@ -345,6 +345,14 @@ PYBIND11_MODULE(_coala_pybind, m) {
         py::gil_scoped_release nogil;
         check(coala_cache_serve(ptr<coala_cache_t>(h), ptr<float>(out), ptr<const int64_t>(ids), n, stream_of(stream)));
     });
+    m.def("cache_write_rows", [](uint64_t h, uint64_t ids, int64_t n, uint64_t src, int mode, float alpha, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_cache_write_rows(ptr<coala_cache_t>(h), ptr<const int64_t>(ids), n, ptr<const float>(src), mode, alpha, stream_of(stream)));
+    });
+    m.def("cache_adagrad_rows", [](uint64_t h, uint64_t ids, int64_t n, uint64_t grad, uint64_t state, float lr, float eps, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_cache_adagrad_rows(ptr<coala_cache_t>(h), ptr<const int64_t>(ids), n, ptr<const float>(grad), ptr<float>(state), lr, eps, stream_of(stream)));
+    });
     m.def("cache_fetch_distributed", [](uint64_t h, uint64_t c, uint64_t out, uint64_t idx, int64_t n, uint64_t stream) {
         py::gil_scoped_release nogil;
         check(coala_cache_fetch_distributed(ptr<coala_cache_t>(h), ptr<coala_comm_t>(c), ptr<float>(out), ptr<const int64_t>(idx), n, stream_of(stream)));

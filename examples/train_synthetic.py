@@ -19,6 +19,8 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --task link --num_negs 5 --exclude reverse_id
   python examples/train_synthetic.py --sampler temporal --temporal_strategy last --time_decay 0.001
   python examples/train_synthetic.py --task link --sampler temporal --num_negs 5
+  python examples/train_synthetic.py --node_embedding --emb_dim 64 --model_type rgcn --num_rels 4
+  python examples/train_synthetic.py --node_embedding --emb_optimizer sgd --emb_lr 0.1 --task link
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -34,7 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "coala-gnn_amd"))
 
 import torch  # noqa: E402
 
-from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, SSD_INFO  # noqa: E402
+from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, NodeEmbedding, SparseAdagrad, SparseSGD, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
 from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, GATv2, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
 from COALA_GNN.sampler import (EdgePredictionSampler, LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler,  # noqa: E402
@@ -53,6 +55,17 @@ def add_time_decay(blocks, lam):
         for b in blocks:
             b.edata[DECAY] = torch.exp(-lam * b.edata["dt"].to(torch.float32))
     return blocks
+
+
+def make_embedding(args, loader):
+    """--node_embedding: the loader's table is the embedding table (random rows instead of features), its fetch is the lookup
+    (NodeEmbedding.from_manager + attach), and a sparse optimizer writes the rows a step used back through the cache, beside the dense one.
+    -> (embedding, sparse optimizer), or (None, None)."""
+    if not args.node_embedding:
+        return None, None
+    emb = NodeEmbedding.from_manager(loader.COALA_GNN_Manager)
+    cls = SparseAdagrad if args.emb_optimizer == "adagrad" else SparseSGD
+    return emb, cls([emb], lr=args.emb_lr)
 
 
 def train_link(args, comm, device, indptr, indices, feat, files, fan_out):
@@ -87,6 +100,7 @@ def train_link(args, comm, device, indptr, indices, feat, files, fan_out):
                        edge_weight=None if args.time_decay is None else DECAY)
     model = LinkPredictor(encoder).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=args.learning_rate)
+    emb, emb_optimizer = make_embedding(args, loader)
     count = 0
     model.train()
     for epoch in range(args.epochs):
@@ -96,11 +110,15 @@ def train_link(args, comm, device, indptr, indices, feat, files, fan_out):
             if step % 100 == 0:
                 print(f"Rank: {comm.local_rank} step: {step}")
             count += 1
+            if emb is not None:
+                fetch_feature = emb.attach(input_nodes, fetch_feature)
             pos_score, neg_score = model(add_time_decay(blocks, args.time_decay), fetch_feature, batch)
             loss = link_loss(pos_score, neg_score)
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()
+            if emb is not None:
+                emb_optimizer.step()   # (clears the embedding's trace)
             if count == 1:
                 first_loss = loss.item()
         torch.cuda.synchronize()
@@ -155,6 +173,13 @@ def main():
     ap.add_argument("--exclude", type=str, default="self", choices=["none", "self", "reverse_id"],
                     help="with --task link: take the seed edges out of the sampled blocks (self), and their reverses too (reverse_id: the "
                          "synthetic graph is symmetrised first)")
+    ap.add_argument("--node_embedding", action="store_true",
+                    help="featureless nodes: the input row of every node is a learned embedding (NodeEmbedding over the loader's table and "
+                         "cache, randomly initialised) updated by a sparse optimizer that touches only the minibatch's rows; synthetic graph, "
+                         "--cache_backend isolated, one GPU, --prefetch 0")
+    ap.add_argument("--emb_dim", type=int, default=None, help="with --node_embedding: floats per embedding row (default: --dim)")
+    ap.add_argument("--emb_optimizer", type=str, default="adagrad", choices=["adagrad", "sgd"], help="with --node_embedding: SparseAdagrad or SparseSGD")
+    ap.add_argument("--emb_lr", type=float, default=0.05, help="with --node_embedding: learning rate of the sparse optimizer")
     ap.add_argument("--batch_size", type=int, default=1024)
     ap.add_argument("--hidden_channels", type=int, default=128)
     ap.add_argument("--num_classes", type=int, default=19)
@@ -196,6 +221,11 @@ def main():
     if args.num_layers is not None and args.num_layers != len(args.fan_out.split(",")) and args.num_layers != 2:
         ap.error("--num_layers does not match --fan_out")   # (the reference's own scripts pass --num_layers 2 with a 3-entry fan-out: tolerated)
 
+    if args.node_embedding:
+        if args.path or args.cache_backend != "isolated" or args.prefetch or int(os.environ.get("WORLD_SIZE", 1)) != 1:
+            ap.error("--node_embedding runs on the synthetic graph with --cache_backend isolated, one GPU and --prefetch 0")
+        if args.emb_dim is not None:
+            args.dim = args.emb_dim
     local_rank = int(os.environ.get("LOCAL_RANK", os.environ.get("SLURM_LOCALID", 0)))
     node_rank = int(os.environ.get("SLURM_NODEID", 0))
     torch.cuda.set_device(local_rank)
@@ -246,6 +276,8 @@ def main():
         indptr, indices = powerlaw_csc(args.nodes, 10.0, seed=0, device=device)
         labels = (torch.arange(args.nodes, device=device) * 7) % args.num_classes
         feat = alloc_pinned_table(args.nodes, args.dim, seed=0, device=comm.local_rank)
+        if args.node_embedding:   # no input features: the table holds the embedding rows, randomly initialised
+            feat.cpu_tensor.uniform_(-1.0, 1.0, generator=torch.Generator().manual_seed(max(args.seed, 0)))
         train_ids = torch.arange(int(0.6 * args.nodes))
         test_ids = torch.arange(int(0.8 * args.nodes), args.nodes)
         meta = None
@@ -345,6 +377,7 @@ def main():
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[comm.local_rank])             # :112
     loss_fcn = torch.nn.CrossEntropyLoss().to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=args.learning_rate)
+    emb, emb_optimizer = make_embedding(args, train_loader)
 
     count = num_sampled_nodes = 0
     model.train()
@@ -359,11 +392,15 @@ def main():
             batch_labels = blocks[-1].dstdata["labels"]
             blocks = add_time_decay([block.int().to(device) for block in blocks], args.time_decay)
             batch_labels = batch_labels.view(-1).to(device)
+            if emb is not None:
+                fetch_feature = emb.attach(input_nodes, fetch_feature)
             batch_pred = model(blocks, fetch_feature)
             loss = loss_fcn(batch_pred, batch_labels)
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()
+            if emb is not None:
+                emb_optimizer.step()   # (clears the embedding's trace)
             if count == 1:
                 first_loss = loss.item()
         torch.cuda.synchronize()

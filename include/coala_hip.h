@@ -164,6 +164,38 @@ int coala_cache_scatter_ranges(coala_cache_t* h, float* out, const float* src, c
 int64_t coala_cache_row_dim(const coala_cache_t* h);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Write-through row updates: trainable rows (DGL's dgl.nn.NodeEmbedding under dgl.optim.SparseAdagrad) in the table the cache
+ * fronts.  Not in the reference, which only reads.  cfg.cold_table stays `const float*`; these calls cast it, so a handle that is
+ * written to needs a WRITABLE, device-visible table (pinned host or HBM).
+ *   ids   : device int64[n], pairwise distinct (the caller's duty).
+ *   src / grad : device-visible fp32 [n, dim].
+ *   state : device-visible fp32 [num_rows, dim], HBM or pinned host, addressed by id; it is not cached.
+ * What a write changes.  row(id) is the cold-table row `id` plus every cache line whose tag equals id.  A write stores the new value to
+ * the cold row and to EVERY way of the id's set whose tag matches, not only the lowest one: the same id can sit in several ways (a read
+ * inserts one copy per duplicate miss of a batch), reads take the lowest matching way, and once round robin evicts that copy the next
+ * one is read.
+ * Where the old value comes from (mode 1, Adagrad).  It is read once: on a hit from the lowest matching line (no host-link read),
+ * otherwise from the cold row.
+ * The invariant.  Before and after every call, every valid line holds the bytes of its cold row in floats [0, dim).
+ * What a write leaves alone.  It never inserts, evicts or ranks: keys, set_cnt, color_meta, the colour counters and the hit / miss
+ * counters are exactly as before, and line floats [dim, cache_dim) are not touched.
+ * Bad ids.  An id outside [0, num_rows) writes nothing and is counted in range_errors, as a rejected read is.  With a repeated id the
+ * row holds an unspecified mix of the writes; nothing out of bounds is read or written and the handle stays usable.
+ * Order and refusals.  The call takes the handle's program order across streams exactly as a read does, and synchronises only under
+ * COALA_FLAG_SYNC.  COALA_EINVAL with a message, before any launch, for: a null handle; n outside [0, 2^31 - 1]; a null buffer with
+ * n > 0; a mode outside 0..1; an open serve batch; cfg.n_gpus != 1, COALA_FLAG_DISTRIBUTED or COALA_FLAG_COLD_PARTITIONED (a second
+ * cache over the same table would keep stale lines; so the cold row is always `id`).  n == 0 returns COALA_OK and launches nothing.
+ * One kernel per call.  16-byte accesses when dim % 4 == 0 and the cold table, src / grad and state are 16-byte aligned, 4-byte
+ * accesses otherwise (the rule of coala_cache_read_feature).
+ * ------------------------------------------------------------------------------------------------------------ */
+/* mode 0 (assign): row(id) = src[i];  mode 1 (add): row(id) = fmaf(alpha, src[i], row(id)) */
+int coala_cache_write_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* src, int mode, float alpha, void* stream);
+/* s = state[id] + g*g;  state[id] = s;  row(id) -= lr * g / (sqrtf(s) + eps),  g = grad[i]  (torch.optim.Adagrad / DGL SparseAdagrad,
+ * element-wise state) */
+int coala_cache_adagrad_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* grad, float* state, float lr, float eps,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Native fused fetch of the owner-partitioned cache over RCCL (one process per GPU, one communicator per cache group).
  * Replaces, in one call: SSD_GNN_NVSHMEM_Cache::send_requests + read_feature (ssd_gnn_cache.cuh:111-174) and the "nccl"
  * orchestration of COALA_GNN_Manager.fetch_feature (COALA-GNN-Setup/COALA_GNN/COALA_GNN_Manager.py:143-211):
