@@ -15,8 +15,10 @@
 //                     row; hits are copied HBM line -> output row with nontemporal 16-B loads / plain stores, 4 row(-pair)s
 //                     in flight per wave, with the next chunk's ids/tags prefetched behind them.  A miss is pushed on its
 //                     set's chain (ONE atomicExch on the set's own head word, tagged with the batch generation so no
-//                     clearing pass is needed); every row's verdict + chain link is one 4-byte word written per position.
-//   K2 miss_fill    : same chunking.  For a missed row one lane walks the set's chain and counts the misses that precede
+//                     clearing pass is needed); every row's verdict + chain link is one 4-byte word written per position.  For a whole
+//                     read on a host tier the missed positions are also appended to the batch's miss list (64 lists, one atomic per chunk).
+//   K2 miss_fill    : same chunking (ranged fills, HBM tier: verdict tiles; whole reads on a host tier: groups of R entries of the miss
+//                     list, cold rows requested before the ranking).  For a missed row one lane walks the set's chain and counts the misses that precede
 //                     it in batch order: its rank k.  way = (set_cnt_before + k) % 32 -- the reference's round robin
 //                     executed in batch order, for any arrival order of the atomics; the first-ranked miss of a set advances
 //                     the set's cursor (a generation-tagged 64-bit word, so that late readers still recover the value
@@ -66,12 +68,31 @@ struct CacheDev {
     uint32_t distributed;
     uint32_t cold_partitioned; // cold row of id = id / n_gpus
     uint32_t tag32;            // 1: 32-bit tags (num_rows <= 2^32-1, empty = 0xFFFFFFFF); 0: 64-bit tags as in the reference
-    // per-batch scratch, indexed by the row's POSITION in the batch (no compaction, no list counter)
+    // per-batch scratch, indexed by the row's POSITION in the batch (ranking never needs a compacted list; streaming may use one: miss_list)
     uint64_t* set_head;    // [sets] : (gen << 32) | (position + 1) of the most recently pushed miss of this set
     uint32_t* miss_link;   // [cap] K1's verdict for every position of the batch, rewritten by every probe (nothing to clear):
                            //       0 = hit, kLinkBad = rejected id, kLinkMiss | (position + 1 of the previously pushed miss of the set; 0 = end)
     unsigned long long* stats; // [kStatBlocks][2] running sums owned by K2's blocks: misses, rejected ids
+    uint32_t* miss_list;   // [kListShards][list_sub] batch positions of the misses, appended by K1 in arrival order (read by K2's list form)
+    uint32_t list_sub;     // entries per shard of miss_list; 0 in the copy a launch gets = this batch keeps no list (its fills are ranged: tile form)
 };
+
+// The miss list of a batch (K1 appends, K2's list form streams from it).  One counter for the whole batch would take one returning atomic per
+// chunk with a miss on ONE word, and a word takes ~12 ns per atomic whoever sends it: 7 k chunks = 80 us under a 17-us probe.  So the list is
+// kListShards lists, chunk k appends to list k % kListShards, and every counter has a 256-B stretch of its own; K2 reads all the counters with
+// one load per lane and walks the lists as one dense index space through their prefix sums.  A shard holds the misses of at most
+// ceil(chunks / kListShards) chunks of up to 32 rows: list_sub = cap / kListShards + 32 entries.
+constexpr int kListShards = 64;        // = the lanes of a wave (K2's prefix sum)
+constexpr int kListStride = 64;        // uint32_t words between two counters
+// CacheDev::stats in 64-bit words: K2's per-block sums, its ticket counters (2 x kFillSlots x 4 B) and the two "something to fill" flags, then
+constexpr int kStatWriteBad = 2 * kStatBlocks + kFillSlots + 1;   // rejected ids of the write kernel
+constexpr int kStatProbeBad = kStatWriteBad + 1;                  // rejected ids of the batches that keep a list (K1 counts them: K2's list form never sees them)
+constexpr int kStatHostWords = kStatProbeBad + 1;                 // what coala_cache_stats reads back
+constexpr int kStatList = (kStatHostWords + 31) & ~31;            // the list counters: [2 parities of the generation][kListShards], kListStride words apart
+constexpr int kStatWords = kStatList + 2 * kListShards * kListStride / 2;
+__device__ __forceinline__ uint32_t* list_counter(const CacheDev& c, uint32_t parity, uint32_t shard) {
+    return reinterpret_cast<uint32_t*>(c.stats + kStatList) + (parity * kListShards + shard) * kListStride;
+}
 
 __device__ __forceinline__ uint64_t set_of(const CacheDev& c, uint64_t id) {
     // isolated_cache.h:183-195 ; nvshmem_cache.h:191-196
@@ -179,10 +200,11 @@ struct Geo {
 // tag sets of chunk k+1 are requested while the rows of chunk k are in flight, so a wave never sits on the
 // id -> tag -> line dependency chain with nothing outstanding.  Lines and output rows are touched once per batch:
 // nontemporal loads/stores keep them from displacing the tag sets in L2.
-// Misses are NOT compacted: every per-miss record is indexed by the row's position in the batch, and the per-set chain
+// Every per-miss record of the ranking is indexed by the row's position in the batch, and the per-set chain
 // that K2 walks is pushed with one atomicExch on the set's own head word.  (Measured alternatives: a miss-list append
-// per chunk or per wave serialises at ~12 ns per same-address atomic -- 4096 waves = 49 us, as long as the whole hit
-// gather; a block-level append needs LDS staging and a trailing barrier and still costs 5-7 us.)
+// per chunk or per wave on ONE counter serialises at ~12 ns per same-address atomic -- 4096 waves = 49 us, as long as the whole hit
+// gather; a block-level append needs LDS staging and a trailing barrier and still costs 5-7 us.  The list K2's list form
+// streams from is therefore kListShards lists with a counter each: ~110 atomics per counter on the default workload.)
 constexpr int kK1MinWaves = 4; // waves per SIMD the register allocator must leave room for (5 on 4-KiB lines spills: 17.5 -> 20.9 us on the default workload)
 // Row(-pair)s a wave keeps in flight (passes): 4 for every line size and both tag widths = 16 KiB of 4-KiB lines, 4 KiB of 512-B lines
 // (8 rows).  More passes on short lines were measured in situ on the configs[3] shape (512-B lines, 16 GiB cache, 315 k rows per
@@ -233,6 +255,9 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, kK1MinWaves) void probe_gather_ke
     // cleared here -- its last readers, the fills of the batch before this one, are done -- and this batch's was cleared by the previous probe
     uint32_t* fill_flag = reinterpret_cast<uint32_t*>(c.stats + 2 * kStatBlocks) + 2 * kFillSlots;
     if (blockIdx.x == 0 && threadIdx.x == kFillSlots) fill_flag[(gen + 1u) & 1u] = 0u;
+    // ... and the miss-list counters: this batch adds to the ones of its own parity and clears the next batch's, which the fill of the batch
+    // before this one was the last to read
+    if (blockIdx.x == 0 && threadIdx.x < kListShards) *list_counter(c, (gen + 1u) & 1u, threadIdx.x) = 0u;
     constexpr int TSTEPS = (R + TG::SPL - 1) / TG::SPL; // tag loads per chunk: SPL sets per wave-wide 16-B load (LPS lanes x KPL tags per set)
     int lane = threadIdx.x & 63;
 #ifdef COALA_DEV_KNOBS
@@ -335,6 +360,20 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, kK1MinWaves) void probe_gather_ke
             for (int t = 0; t < TSTEPS; ++t) any = any || imiss_l[t] || bad_l[t];
             if (__ballot(any) != 0 && lane == 0) fill_flag[gen & 1u] = 1u;   // (what the flag costs K1: profiles/r04_k2_dynamic_deal.txt)
         }
+        // ---- the batch's miss list (a whole read on a host tier): ONE atomic per chunk with misses reserves their slots in the chunk's shard
+        //      (the old count comes back behind the row loads; the positions are stored with the verdicts), and rejected ids are counted here
+        const uint32_t shard = (uint32_t)chunk & (kListShards - 1);
+        uint32_t list_at = 0;   // lane 0: the shard's count before this chunk
+        if (c.list_sub) {
+            uint32_t n_miss = 0, n_bad = 0;
+#pragma unroll
+            for (int t = 0; t < TSTEPS; ++t) {
+                n_miss += (uint32_t)__builtin_popcountll(__ballot(imiss_l[t]));
+                n_bad += (uint32_t)__builtin_popcountll(__ballot(bad_l[t] && lead_l[t]));
+            }
+            if (n_miss && lane == 0) list_at = atomicAdd(list_counter(c, gen & 1u, shard), n_miss);
+            if (n_bad && lane == 0) atomicAdd(c.stats + kStatProbeBad, (unsigned long long)n_bad);
+        }
         // row q of the chunk: its tag step, and the first of its lanes there
         auto row_slot = [&](int q) { return (uint32_t)__builtin_amdgcn_readlane((int)slot_v[q / TG::SPL], TG::LPS * (q % TG::SPL)); };
         auto row_hit = [&](int q) { return ((hit_b[q / TG::SPL] >> (TG::LPS * (q % TG::SPL))) & 1) != 0; };
@@ -401,6 +440,15 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, kK1MinWaves) void probe_gather_ke
                 c.miss_link[base + t * TG::SPL + lane / TG::LPS] = w;
             }
         }
+        if (c.list_sub) {   // the missed rows' positions, in the slots reserved above
+            uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)list_at);
+#pragma unroll
+            for (int t = 0; t < TSTEPS; ++t) {
+                const uint64_t mb = __ballot(imiss_l[t]);
+                if (imiss_l[t]) c.miss_list[shard * c.list_sub + at + (uint32_t)__builtin_popcountll(mb & ((1ull << lane) - 1ull))] = (uint32_t)(base + t * TG::SPL + lane / TG::LPS);
+                at += (uint32_t)__builtin_popcountll(mb);
+            }
+        }
         if (SINGLE) break;
     }
 }
@@ -419,8 +467,6 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, kK1MinWaves) void probe_gather_ke
 // 97 %) and, with a third to three quarters of the old values read back over the link, 47-51 GB/s (add, Adagrad: 84-91 %).  An Adagrad state in
 // pinned host memory adds a read and a write of the link per element: 23-24 GB/s of rows (41-43 %).
 enum { kOpAssign = 0, kOpAdd = 1, kOpAdagrad = 2 };
-constexpr int kStatWriteBad = 2 * kStatBlocks + kFillSlots + 1;   // index into CacheDev::stats (64-bit words), behind K2's tickets and flags
-constexpr int kStatWords = kStatWriteBad + 1;
 
 template <int OP> __device__ __forceinline__ float write_op(float x, float old, float& st, float a, float eps) {
     if (OP == kOpAssign) return x;
@@ -528,6 +574,85 @@ __global__ __launch_bounds__(256) void write_rows_kernel(const int64_t* __restri
 // first-ranked miss has already advanced it (generation tag), every way touched in this batch has exactly one winner, and only
 // winners touch keys / color_meta / lines.
 
+
+// Rank the missed row at batch position `pos` inside its set, by ONE lane: walk the set's chain, count the misses before it in batch order,
+// advance the set's cursor if it is the first of them, and publish tag and colour if it is the last writer of its way (the winner).
+__device__ __forceinline__ void rank_row(const CacheDev& c, uint32_t gen, uint32_t pos, uint64_t id, uint32_t& slot, uint32_t& win) {
+    const uint64_t set = set_of(c, id);
+    uint32_t cur = (uint32_t)c.set_head[set]; // tagged with this generation: this row was pushed on it by K1
+    uint32_t total = 0, rank = 0;
+    while (cur) {
+        const uint32_t p2 = cur - 1;
+        ++total;
+        rank += (p2 < pos) ? 1u : 0u;
+        cur = c.miss_link[p2] & ~kLinkMiss;
+    }
+    // the cursor before this batch: the set's first-ranked miss advances it below, tagged with the generation
+    const uint64_t cv = __hip_atomic_load(c.set_cnt + set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t cnt0 = ((uint32_t)(cv >> 32) == gen) ? (uint32_t)cv - total : (uint32_t)cv;
+    if (rank == 0) __hip_atomic_store(c.set_cnt + set, ((uint64_t)gen << 32) | (uint32_t)(cnt0 + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t way = (cnt0 + rank) & (COALA_WAYS - 1);              // isolated_cache.h:203
+    slot = (uint32_t)(set * COALA_WAYS) + way;
+    win = (rank + COALA_WAYS >= total) ? 1u : 0u;                       // nobody later in the batch lands here
+    if (win) {
+        if (c.tag32) reinterpret_cast<uint32_t*>(c.keys)[slot] = (uint32_t)id;   // isolated_cache.h:434 (a uniform branch)
+        else reinterpret_cast<uint64_t*>(c.keys)[slot] = id;
+        if (c.color_counters) {
+            // the pre-batch occupant leaves (:427-429), the winner enters (:437-441); rows that were inserted
+            // and overwritten again inside this batch cancel out
+            const int32_t col = c.node_color[id];
+            atomicSub(c.color_counters + c.color_meta[slot], 1);
+            atomicAdd(c.color_counters + col, 1);
+            c.color_meta[slot] = (uint32_t)col;
+        }
+    }
+}
+// The two halves of a group move (up to R missed rows, one per pass and half-wave): cold rows -> registers, registers -> output rows
+// and, for winners, lines.  Between them the loads are in flight.
+template <typename G, typename V>
+__device__ __forceinline__ void cold_load(const CacheDev& c, const uint64_t (&id)[G::PASSES], const bool (&live)[G::PASSES], int l_in, uint32_t nunits,
+                                          V (&val)[G::PASSES][G::VPL]) {
+#pragma unroll
+    for (int p = 0; p < G::PASSES; ++p) {
+        const V* src = reinterpret_cast<const V*>(c.cold + cold_row_of(c, id[p]) * (uint64_t)c.dim); // cold stride = dim
+#pragma unroll
+        for (int v = 0; v < G::VPL; ++v) {
+            const uint32_t u = v * G::LPR + l_in;
+            if (live[p] && u < nunits) val[p][v] = nt_load(src + u);
+        }
+    }
+}
+template <int CD, typename G, typename V>
+__device__ __forceinline__ void fill_store(const CacheDev& c, V* const (&dst)[G::PASSES], const uint32_t (&slot)[G::PASSES], const bool (&winner)[G::PASSES],
+                                           const bool (&live)[G::PASSES], int l_in, uint32_t nunits, const V (&val)[G::PASSES][G::VPL]) {
+#pragma unroll
+    for (int p = 0; p < G::PASSES; ++p) {
+        V* line = reinterpret_cast<V*>(c.lines + (uint64_t)slot[p] * CD);
+#pragma unroll
+        for (int v = 0; v < G::VPL; ++v) {
+            const uint32_t u = v * G::LPR + l_in;
+            if (live[p] && u < nunits) {
+                nt_store(val[p][v], dst[p] + u);
+                if (winner[p]) nt_store(val[p][v], line + u);
+            }
+        }
+    }
+}
+// miss / rejected totals of a fill launch (isolated_cache.h:471-472): a running sum per block, owned by that block -- no atomics
+__device__ __forceinline__ void add_block_stats(const CacheDev& c, uint32_t my_miss, uint32_t my_bad) {
+    __shared__ uint32_t s_m[256 / 64], s_b[256 / 64];
+    const int lane = threadIdx.x & 63;
+    for (int off = 32; off > 0; off >>= 1) { my_miss += __shfl_down(my_miss, off); my_bad += __shfl_down(my_bad, off); }
+    if (lane == 0) { s_m[threadIdx.x >> 6] = my_miss; s_b[threadIdx.x >> 6] = my_bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t m = 0, b = 0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { m += s_m[w]; b += s_b[w]; }
+        if (m) c.stats[2 * blockIdx.x] += m;
+        if (b) c.stats[2 * blockIdx.x + 1] += b;
+    }
+}
+
 template <int CD, int VEC, bool REDIR = false, int NP = 4>
 __global__ __launch_bounds__(256) void miss_fill_kernel(CacheDev c, const int64_t* __restrict__ idx, float* __restrict__ out,
                                                         int tile_rows, int sparse_max, uint32_t gen, RangeSet rs, Redirect rd, int dyn_slot) {
@@ -598,34 +723,7 @@ __global__ __launch_bounds__(256) void miss_fill_kernel(CacheDev c, const int64_
           drow_l = (int64_t)pos;
           if (REDIR && (int64_t)pos >= rd.begin && (int64_t)pos < rd.end)
               drow_l = -((rd.row_map ? rd.row_map[(int64_t)pos - rd.begin] : (int64_t)pos - rd.begin) + 1);
-          const uint64_t set = set_of(c, id_l);
-          uint32_t cur = (uint32_t)c.set_head[set]; // tagged with this generation: this row was pushed on it by K1
-          uint32_t total = 0, rank = 0;
-          while (cur) {
-              const uint32_t p2 = cur - 1;
-              ++total;
-              rank += (p2 < pos) ? 1u : 0u;
-              cur = c.miss_link[p2] & ~kLinkMiss;
-          }
-          // the cursor before this batch: the set's first-ranked miss advances it below, tagged with the generation
-          const uint64_t cv = __hip_atomic_load(c.set_cnt + set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const uint32_t cnt0 = ((uint32_t)(cv >> 32) == gen) ? (uint32_t)cv - total : (uint32_t)cv;
-          if (rank == 0) __hip_atomic_store(c.set_cnt + set, ((uint64_t)gen << 32) | (uint32_t)(cnt0 + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const uint32_t way = (cnt0 + rank) & (COALA_WAYS - 1);              // isolated_cache.h:203
-          slot_l = (uint32_t)(set * COALA_WAYS) + way;
-          win_l = (rank + COALA_WAYS >= total) ? 1u : 0u;                     // nobody later in the batch lands here
-          if (win_l) {
-              if (c.tag32) reinterpret_cast<uint32_t*>(c.keys)[slot_l] = (uint32_t)id_l;   // isolated_cache.h:434 (a uniform branch)
-              else reinterpret_cast<uint64_t*>(c.keys)[slot_l] = id_l;
-              if (c.color_counters) {
-                  // the pre-batch occupant leaves (:427-429), the winner enters (:437-441); rows that were inserted
-                  // and overwritten again inside this batch cancel out
-                  const int32_t col = c.node_color[id_l];
-                  atomicSub(c.color_counters + c.color_meta[slot_l], 1);
-                  atomicAdd(c.color_counters + col, 1);
-                  c.color_meta[slot_l] = (uint32_t)col;
-              }
-          }
+          rank_row(c, gen, pos, id_l, slot_l, win_l);
       };
       // ---- stream up to R missed rows: pass p of this lane's half-wave moves the row held by lane srcl[p]
       auto move_group = [&](const int (&srcl)[G::PASSES], const bool (&live)[G::PASSES]) {
@@ -634,6 +732,7 @@ __global__ __launch_bounds__(256) void miss_fill_kernel(CacheDev c, const int64_
           uint64_t id[G::PASSES];
           int64_t drow[G::PASSES];
           bool winner[G::PASSES];
+          V* dst[G::PASSES];
 #pragma unroll
           for (int p = 0; p < G::PASSES; ++p) {
               slot_[p] = (uint32_t)__shfl((int)slot_l, srcl[p]);
@@ -641,29 +740,12 @@ __global__ __launch_bounds__(256) void miss_fill_kernel(CacheDev c, const int64_
               id[p] = shfl64(id_l, srcl[p]);
               drow[p] = (int64_t)shfl64((uint64_t)drow_l, srcl[p]);
           }
+          cold_load<G>(c, id, live, l_in, nunits, val);
 #pragma unroll
-          for (int p = 0; p < G::PASSES; ++p) {
-              const V* src = reinterpret_cast<const V*>(c.cold + cold_row_of(c, id[p]) * (uint64_t)c.dim); // cold stride = dim
-#pragma unroll
-              for (int v = 0; v < G::VPL; ++v) {
-                  const uint32_t u = v * G::LPR + l_in;
-                  if (live[p] && u < nunits) val[p][v] = nt_load(src + u);
-              }
-          }
-#pragma unroll
-          for (int p = 0; p < G::PASSES; ++p) {
-              V* dst = (REDIR && drow[p] < 0) ? reinterpret_cast<V*>(rd.out + (uint64_t)(-(drow[p] + 1)) * c.dim)
+          for (int p = 0; p < G::PASSES; ++p)
+              dst[p] = (REDIR && drow[p] < 0) ? reinterpret_cast<V*>(rd.out + (uint64_t)(-(drow[p] + 1)) * c.dim)
                                               : reinterpret_cast<V*>(out + (uint64_t)drow[p] * c.dim);
-              V* line = reinterpret_cast<V*>(c.lines + (uint64_t)slot_[p] * CD);
-#pragma unroll
-              for (int v = 0; v < G::VPL; ++v) {
-                  const uint32_t u = v * G::LPR + l_in;
-                  if (live[p] && u < nunits) {
-                      nt_store(val[p][v], dst + u);
-                      if (winner[p]) nt_store(val[p][v], line + u);
-                  }
-              }
-          }
+          fill_store<CD, G>(c, dst, slot_, winner, live, l_in, nunits, val);
       };
       // the rows held by the lanes of `holders` (each already ranked), streamed R at a time, compacted
       auto stream_holders = [&](uint64_t holders) {
@@ -753,17 +835,81 @@ __global__ __launch_bounds__(256) void miss_fill_kernel(CacheDev c, const int64_
      }
       if (!dyn) break;           // static: the wave's own tiles are done
     }
-    // miss / rejected totals (isolated_cache.h:471-472): a running sum per block, owned by that block -- no atomics
-    __shared__ uint32_t s_m[256 / 64], s_b[256 / 64];
-    for (int off = 32; off > 0; off >>= 1) { my_miss += __shfl_down(my_miss, off); my_bad += __shfl_down(my_bad, off); }
-    if (lane == 0) { s_m[threadIdx.x >> 6] = my_miss; s_b[threadIdx.x >> 6] = my_bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t m = 0, b = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { m += s_m[w]; b += s_b[w]; }
-        if (m) c.stats[2 * blockIdx.x] += m;
-        if (b) c.stats[2 * blockIdx.x + 1] += b;
+    add_block_stats(c, my_miss, my_bad);
+}
+
+// K2, list form: every whole read on a host tier.  The probe has left the batch's misses in kListShards lists (list_counter); a wave reads all
+// the counters at once, and with their prefix sums the lists are one dense index space of `total` entries, dealt R at a time: a wave's first
+// group is its own index, the later ones come from the batch's first ticket counter.  For a group the cold rows are requested as soon as the ids
+// are known -- a host read needs nothing else -- and the rows are ranked (rank_row, lanes 0..R-1) while those reads are in flight.  No verdict
+// scan, no tiles, no sparse / dense split: every miss ratio takes this path, and a batch without misses leaves after the counter load.
+template <int CD, int VEC, int NP = 4>
+__global__ __launch_bounds__(256) void miss_fill_list_kernel(CacheDev c, const int64_t* __restrict__ idx, float* __restrict__ out, uint32_t gen) {
+    using G = Geo<CD, VEC, NP>;
+    using V = typename VecT<VEC>::type;
+    constexpr int R = G::R;
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint32_t n_waves = gridDim.x * (blockDim.x >> 6);
+    const uint32_t nunits = c.dim / VEC;
+    const int sub = (G::RPP == 2) ? (lane >> 5) : 0;
+    const int l_in = lane & (G::LPR - 1);
+    static_assert(kListShards == 64, "one list counter per lane");
+    const uint32_t cnt_l = __hip_atomic_load(list_counter(c, gen & 1u, (uint32_t)lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t incl = cnt_l;   // entries of the shards 0..lane
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
     }
+    const uint32_t excl = incl - cnt_l;
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    if (total == 0) return;   // nothing missed in this batch
+    const uint32_t n_groups = (total + R - 1) / R;
+    uint32_t* ticket = reinterpret_cast<uint32_t*>(c.stats + 2 * kStatBlocks) + (gen & 1u) * kFillSlots;   // zeroed by the batch's probe
+    uint32_t my_miss = 0;
+    for (uint32_t g = wave; g < n_groups;) {
+        // lane j < R holds entry g * R + j: its shard is the number of shards that end at or before it
+        uint32_t pos_l = 0;
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            const uint32_t e = g * R + j;
+            const uint32_t s = (uint32_t)__builtin_popcountll(__ballot(incl <= e)) & 63u;   // (e >= total: not read)
+            const uint32_t off = e - (uint32_t)__builtin_amdgcn_readlane((int)excl, (int)s);
+            if (lane == j && e < total) pos_l = c.miss_list[s * c.list_sub + off];
+        }
+        const bool have = lane < R && g * R + (uint32_t)lane < total;
+        const uint64_t id_l = have ? (uint64_t)idx[pos_l] : 0;
+        uint64_t id[G::PASSES];
+        uint32_t pos[G::PASSES];
+        bool live[G::PASSES];
+        V val[G::PASSES][G::VPL];
+#pragma unroll
+        for (int p = 0; p < G::PASSES; ++p) {
+            const int q = p * G::RPP + sub;   // the row of this half-wave in pass p is held by lane q
+            live[p] = g * R + (uint32_t)q < total;
+            id[p] = shfl64(id_l, q);
+            pos[p] = (uint32_t)__shfl((int)pos_l, q);
+        }
+        cold_load<G>(c, id, live, l_in, nunits, val);
+        uint32_t t = 0;   // the next group's ticket comes back behind the rows
+        if (lane == 0) t = atomicAdd(ticket, 1u);
+        uint32_t slot_l = 0, win_l = 0;
+        if (have) rank_row(c, gen, pos_l, id_l, slot_l, win_l);
+        uint32_t slot[G::PASSES];
+        bool winner[G::PASSES];
+        V* dst[G::PASSES];
+#pragma unroll
+        for (int p = 0; p < G::PASSES; ++p) {
+            const int q = p * G::RPP + sub;
+            slot[p] = (uint32_t)__shfl((int)slot_l, q);
+            winner[p] = __shfl((int)win_l, q) != 0;
+            dst[p] = reinterpret_cast<V*>(out + (uint64_t)pos[p] * c.dim);
+        }
+        fill_store<CD, G>(c, dst, slot, winner, live, l_in, nunits, val);
+        if (lane == 0) my_miss += (total - g * R < (uint32_t)R) ? total - g * R : (uint32_t)R;
+        g = n_waves + (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+    }
+    add_block_stats(c, my_miss, 0u);
 }
 
 // ---------------------------------------------------------------------------------------------------------- scatter
@@ -1060,6 +1206,10 @@ int ensure_scratch(coala_cache* h, uint64_t n, hipStream_t s) {
     if (h->d.miss_link) HIPCHK(hipFree(h->d.miss_link));
     h->d.miss_link = nullptr;
     HIPCHK(hipMalloc((void**)&h->d.miss_link, cap * sizeof(uint32_t))); // written by every probe before any fill reads it
+    if (h->d.miss_list) HIPCHK(hipFree(h->d.miss_list));
+    h->d.miss_list = nullptr;
+    h->d.list_sub = (uint32_t)(cap / kListShards) + 32u;                 // (cap is a power of two >= 1024; a chunk has at most 32 rows)
+    HIPCHK(hipMalloc((void**)&h->d.miss_list, (uint64_t)kListShards * h->d.list_sub * sizeof(uint32_t))); // entries below a shard's counter are written by the batch's probe
     h->cap = cap;
     return COALA_OK;
 }
@@ -1221,7 +1371,7 @@ int coala_cache_create(const coala_cache_config_t* cfg, coala_cache_t** out) {
         if ((rc = alloc((void**)&d.set_cnt, sets * 8))) break;
         if ((rc = alloc((void**)&d.color_meta, slots * 4))) break;
         if ((rc = alloc((void**)&d.set_head, sets * 8))) break;
-        if ((rc = alloc((void**)&d.stats, kStatWords * 8))) break;   // (+ K2's ticket counters, 2 x kFillSlots x 4 B, the two "something to fill" flags and the write kernel's rejected ids behind the per-block sums)
+        if ((rc = alloc((void**)&d.stats, kStatWords * 8))) break;   // (the per-block sums and what lies behind them: kStatWriteBad ... kStatList)
         if ((rc = alloc((void**)&d.lines, slots * (uint64_t)cd * 4))) break;
         if ((rc = alloc((void**)&h->route_bases, 65 * 8))) break;
         if (hipMemset(d.keys, 0xFF, slots * tag_bytes) != hipSuccess || hipMemset(d.set_cnt, 0, sets * 8) != hipSuccess ||
@@ -1282,7 +1432,7 @@ int coala_cache_destroy(coala_cache_t* h) {
         if (e) (void)hipEventDestroy(e);
     CacheDev& d = h->d;
     void* ptrs[] = {d.keys, d.set_cnt, d.color_meta, d.set_head, d.stats, d.lines, d.color_counters,
-                    h->node_color_dev, d.miss_link,
+                    h->node_color_dev, d.miss_link, d.miss_list,
                     h->wave_counts, h->route_bases};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -1413,6 +1563,7 @@ static int read_feature_impl(coala_cache_t* h, float* out, const int64_t* idx, i
         if (++h->gen == 0) { // generation wrapped: clear the chain heads and the generation tags of the cursors once
             HIPCHK(hipMemsetAsync(h->d.set_head, 0, h->d.num_sets * 8, s));
             HIPCHK(hipMemset2DAsync(reinterpret_cast<char*>(h->d.set_cnt) + 4, 8, 0, 4, h->d.num_sets, s));
+            HIPCHK(hipMemsetAsync(h->d.stats + kStatList, 0, (size_t)(kStatWords - kStatList) * 8, s));   // (generation 1 follows an odd one: its list counters were not cleared)
             h->gen = 1;
         }
         if (!(phases & kPhaseFill)) { // a probe alone leaves the batch open for its fills
@@ -1427,6 +1578,9 @@ static int read_feature_impl(coala_cache_t* h, float* out, const int64_t* idx, i
     const bool vec4 = (h->d.dim % 4 == 0) && aligned16(out) && aligned16(h->d.cold) && (!redir || aligned16(rd.out));
     CacheDev d = h->d;
     if (force_dist) d.distributed = 1u;
+    // a whole read on a host tier: the probe keeps the batch's miss list and the fill streams from it (ranged fills: the tile form, no list)
+    const bool list_form = phases == kPhaseBoth && h->host_tier;
+    if (!list_form) d.list_sub = 0;
     // a whole read (K1 + one K2 launch): its begin / end events ride on the two dispatches (see coala_cache_fetch_events)
     hipEvent_t fe_begin = nullptr, fe_end = nullptr;
     if (h->fetch_events && phases == kPhaseBoth && !(h->cfg.flags & COALA_FLAG_PROFILE)) {
@@ -1492,6 +1646,13 @@ static int read_feature_impl(coala_cache_t* h, float* out, const int64_t* idx, i
             else launch_k1(uint64_t{}, std::integral_constant<int, kK1Passes>{});
         }
         if ((phases & kPhaseFill) && fill_rows > 0) {
+            if (list_form) {
+                ProfScope ps(h, s, 2, 0, nullptr, fe_end);
+                if (rode) rode[1] = ps.on ? ps.b : fe_end;
+                h->fill_launches++;   // (the list form draws its groups from the batch's first ticket counter)
+                ps.launch(miss_fill_list_kernel<CD, VEC>, dim3(grid_for((n + G::R - 1) / G::R, 4, h->shape.k2_grid_cap)), dim3(256), d, idx, out, gen);
+                return COALA_OK;
+            }
             const int tile_rows = h->shape.k2_tile_rows > 0 ? h->shape.k2_tile_rows : G::R;
             return for_each_range_set(begins, ends, n_ranges, [&](const RangeSet& rs) -> int {
                 const bool last_set = ++set_no == n_sets;
@@ -1760,15 +1921,16 @@ int coala_cache_color_counts_finish(coala_cache_t* h, int32_t* dst, int32_t n_en
 }
 
 static int read_stats(coala_cache_t* h, hipStream_t s, uint64_t* hit, uint64_t* miss, uint64_t* bad, bool reset) {
-    std::vector<unsigned long long> part((size_t)kStatWords);   // (K2's tickets and flags come along: 72 bytes, and nothing here reads them)
+    std::vector<unsigned long long> part((size_t)kStatHostWords);   // (K2's tickets and flags come along: 72 bytes, and nothing here reads them)
     HIPCHK(hipMemcpyAsync(part.data(), h->d.stats, part.size() * 8, hipMemcpyDeviceToHost, s)); // end of epoch: a device-wide wait is fine
     if (reset) {
         HIPCHK(hipMemsetAsync(h->d.stats, 0, (size_t)kStatBlocks * 2 * 8, s));
-        HIPCHK(hipMemsetAsync(h->d.stats + kStatWriteBad, 0, 8, s));
+        HIPCHK(hipMemsetAsync(h->d.stats + kStatWriteBad, 0, 2 * 8, s));   // (and kStatProbeBad behind it)
     }
     HIPCHK(hipStreamSynchronize(s));
     uint64_t m = 0, b = 0;
     for (int i = 0; i < kStatBlocks; ++i) { m += part[2 * i]; b += part[2 * i + 1]; }
+    b += part[kStatProbeBad];   // rejected ids of the reads whose fill streamed from the miss list: counted by their probe
     *miss = m;
     *bad = b + part[kStatWriteBad];   // rejected ids of reads and of writes; only the reads' were counted in rows_total
     *hit = h->rows_total - m - b;
