@@ -1,16 +1,19 @@
 """Trainable node embeddings in the table the feature cache fronts, with sparse optimizers that touch only a minibatch's rows.
 
-NodeEmbedding stands where DGL's dgl.nn.NodeEmbedding stands, SparseAdagrad / SparseSGD where dgl.optim.SparseAdagrad / SparseSGD do:
-node types without input features get a learned row per node, too many to keep as a dense parameter in HBM.  The 'native' backend keeps
-the table in pinned host memory behind an Isolated_Cache: a lookup is the cache's read_feature, an optimizer step is ONE native call
-(coala_cache_adagrad_rows, or coala_cache_write_rows in 'add' mode for SGD) that updates the cold row and every cache line of each id
+NodeEmbedding stands where DGL's dgl.nn.NodeEmbedding stands, SparseAdagrad / SparseAdam / SparseSGD where dgl.optim's do, RowWiseAdagrad
+where DGL-KE's row-wise Adagrad does: node types without input features get a learned row per node, too many to keep as a dense parameter
+in HBM.  The 'native' backend keeps the table in pinned host memory behind an Isolated_Cache: a lookup is the cache's read_feature, an
+optimizer step is ONE native call (coala_cache_adagrad_rows / _adam_rows / _rowwise_adagrad_rows, or coala_cache_write_rows in 'add' mode
+for SGD) that updates the cold row and every cache line of each id
 (write-through: include/coala_hip.h).  The 'torch' backend keeps a plain tensor on any device and does the same with torch ops: the
 fallback for a machine without the GPU, and the reference the tests compare against.
 
 The trace / step protocol and the 'mean' rule of the optimizers follow DGL's, written from memory of DGL's source, not copied from it."""
+import math
+
 import torch
 
-__all__ = ["NodeEmbedding", "SparseAdagrad", "SparseSGD"]
+__all__ = ["NodeEmbedding", "SparseAdagrad", "SparseAdam", "RowWiseAdagrad", "SparseSGD"]
 
 
 def _as_ids(ids, device):
@@ -169,6 +172,54 @@ class NodeEmbedding(object):
             with torch.cuda.device(self.device):
                 self._cache.adagrad_rows(uniq.data_ptr(), uniq.numel(), grad.data_ptr(), int(state), float(lr), float(eps))
 
+    def _adam(self, uniq, grad, m, v, row_step, step, lr, betas, eps):
+        """One Adam step on pairwise distinct rows.  m, v: [num_rows, dim] tensors (torch backend) or device-visible pointers; row_step:
+        the int32 [num_rows] counter tensor (t = ++row_step[id] per row) or None (t = step for every row)."""
+        b1, b2 = betas
+        if self.backend == "torch":
+            f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))     # noqa: E731  (the scalars as the native call receives them)
+            b1, b2, lr, eps = f32(b1), f32(b2), f32(lr), f32(eps)
+            if row_step is not None:
+                t = torch.clamp(row_step[uniq].to(torch.int64) + 1, max=2 ** 31 - 1)
+                row_step[uniq] = t.to(torch.int32)
+                t = t.to(torch.float64)
+            else:
+                t = torch.full((uniq.numel(),), float(step), dtype=torch.float64, device=self.device)
+            # 1 - beta^t as -expm1(t ln beta), in float64, once per row (beta = 0: ln = -inf, no correction)
+            bc1 = -torch.expm1(t * (math.log(b1) if b1 > 0 else -math.inf))
+            bc2 = -torch.expm1(t * (math.log(b2) if b2 > 0 else -math.inf))
+            step_size = (lr / bc1).to(torch.float32)[:, None]
+            rsbc2 = bc2.rsqrt().to(torch.float32)[:, None]
+            # exp_avg is signed: its two terms can cancel, so they are added in float64 and rounded once (the kernel carries the
+            # product's rounding error to the same end)
+            mn = (b1 * m[uniq].to(torch.float64) + (1.0 - b1) * grad.to(torch.float64)).to(torch.float32)
+            vn = torch.addcmul(torch.tensor(1.0 - b2, dtype=torch.float32, device=self.device) * (grad * grad), v[uniq],
+                               torch.tensor(b2, dtype=torch.float32, device=self.device))
+            m[uniq] = mn
+            v[uniq] = vn
+            self.weight[uniq] = self.weight[uniq] - (step_size * mn) / (vn.sqrt() * rsbc2 + eps)
+        elif uniq.numel():
+            with torch.cuda.device(self.device):
+                self._cache.adam_rows(uniq.data_ptr(), uniq.numel(), grad.data_ptr(), int(m), int(v), float(lr), (float(b1), float(b2)), float(eps),
+                                      row_step_ptr=0 if row_step is None else row_step.data_ptr(), step=int(step))
+
+    def _rowwise_adagrad(self, uniq, grad, row_state, lr, eps):
+        """One row-wise Adagrad step on pairwise distinct rows; row_state: the fp32 [num_rows] tensor (both backends)."""
+        if self.backend == "torch":
+            # the row mean in fp32, summed pairwise (ceil(log2 dim) additions on any path), so that its rounding does not depend on the device
+            sq = grad * grad
+            width = 1 << max(self.dim - 1, 0).bit_length()
+            sq = torch.nn.functional.pad(sq, (0, width - self.dim))
+            while width > 1:
+                width //= 2
+                sq = sq[:, :width] + sq[:, width:]
+            s = row_state[uniq] + sq[:, 0] / float(self.dim)
+            row_state[uniq] = s
+            self.weight[uniq] = self.weight[uniq] - (lr / (s.sqrt() + eps))[:, None] * grad
+        elif uniq.numel():
+            with torch.cuda.device(self.device):
+                self._cache.rowwise_adagrad_rows(uniq.data_ptr(), uniq.numel(), grad.data_ptr(), row_state.data_ptr(), float(lr), float(eps))
+
     def close(self):
         if self._manager is None and self._cache is not None:
             self._cache.close()
@@ -256,3 +307,85 @@ class SparseAdagrad(_SparseOptimizer):
     def _update(self, emb, uniq, g):
         t, ptr = self.state_of(emb)
         emb._adagrad(uniq, g, t if emb.backend == "torch" else ptr, self.lr, self.eps)
+
+
+class SparseAdam(_SparseOptimizer):
+    """SparseAdam(params, lr, betas=(0.9, 0.999), eps=1e-8, reduce='mean' | 'sum', step='row' | 'global', state_device_bytes=1 GiB)
+
+    step='row' is DGL's SparseAdam: every row counts its own updates (int32, in HBM) and its bias corrections use that count -- lazy Adam.
+    step='global' uses the optimizer's step count for every row it touches, torch.optim.SparseAdam's rule.  One coala_cache_adam_rows
+    call per step with the native backend.  exp_avg, exp_avg_sq and the step vector of a native embedding are zeroed HBM tensors when
+    num_rows * (2 * dim + 1) * 4 bytes fit state_device_bytes; otherwise exp_avg and exp_avg_sq live in pinned host memory, which the
+    kernel reads and writes over the host link.  None of it is cached."""
+
+    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, reduce="mean", step="row", state_device_bytes=1 << 30):
+        super().__init__(params, lr, reduce)
+        try:
+            b1, b2 = (float(b) for b in betas)
+        except (TypeError, ValueError):
+            raise ValueError("betas must be a pair of floats")
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError("betas must lie in [0, 1)")
+        if step not in ("row", "global"):
+            raise ValueError("step must be 'row' or 'global'")
+        if not eps >= 0:
+            raise ValueError("eps must not be negative")
+        self.betas, self.eps, self.step_mode, self.state_device_bytes = (b1, b2), float(eps), step, int(state_device_bytes)
+        self.steps = 0          # step() calls so far: t of step='global'
+        self._state = {}
+
+    def state_bytes(self, emb):
+        """Bytes of exp_avg, exp_avg_sq and the step vector of emb."""
+        return emb.num_rows * (2 * emb.dim + 1) * 4
+
+    def state_of(self, emb):
+        """(exp_avg, exp_avg_sq, row_step, pointer of exp_avg, pointer of exp_avg_sq): [num_rows, dim] fp32 tensors -- on the device, or
+        the host views of pinned tables -- and the int32 [num_rows] step vector on the device."""
+        st = self._state.get(id(emb))
+        if st is None:
+            steps = torch.zeros(emb.num_rows, dtype=torch.int32, device=emb.device)
+            if emb.backend == "torch" or self.state_bytes(emb) <= self.state_device_bytes:
+                m, v = (torch.zeros((emb.num_rows, emb.dim), dtype=torch.float32, device=emb.device) for _ in range(2))
+                st = (m, v, steps, m.data_ptr(), v.data_ptr(), None)
+            else:
+                from .synthetic import PinnedFeatureTable
+                tabs = [PinnedFeatureTable(emb.num_rows, emb.dim, emb.device.index or 0) for _ in range(2)]
+                for tab in tabs:
+                    tab.cpu_tensor.zero_()
+                st = (tabs[0].cpu_tensor, tabs[1].cpu_tensor, steps, tabs[0].device_ptr, tabs[1].device_ptr, tabs)
+            self._state[id(emb)] = st
+        return st[:5]
+
+    def step(self):
+        self.steps += 1
+        super().step()
+
+    def _update(self, emb, uniq, g):
+        m, v, steps, m_ptr, v_ptr = self.state_of(emb)
+        native = emb.backend != "torch"
+        emb._adam(uniq, g, m_ptr if native else m, v_ptr if native else v, steps if self.step_mode == "row" else None, self.steps, self.lr,
+                  self.betas, self.eps)
+
+
+class RowWiseAdagrad(_SparseOptimizer):
+    """RowWiseAdagrad(params, lr, eps=1e-10, reduce='mean' | 'sum'): DGL-KE's Adagrad with ONE float of state per row, the mean of the
+    row's squared gradients summed over the steps -- 4 bytes per row where SparseAdagrad keeps 4 * dim, so the state of a table far larger
+    than HBM still lives in HBM (a zeroed fp32 [num_rows] tensor).  One coala_cache_rowwise_adagrad_rows call per step with the native
+    backend."""
+
+    def __init__(self, params, lr, eps=1e-10, reduce="mean"):
+        super().__init__(params, lr, reduce)
+        if not eps >= 0:
+            raise ValueError("eps must not be negative")
+        self.eps = float(eps)
+        self._state = {}
+
+    def state_of(self, emb):
+        """(tensor [num_rows] on the embedding's device, its pointer)"""
+        t = self._state.get(id(emb))
+        if t is None:
+            t = self._state[id(emb)] = torch.zeros(emb.num_rows, dtype=torch.float32, device=emb.device)
+        return t, t.data_ptr()
+
+    def _update(self, emb, uniq, g):
+        emb._rowwise_adagrad(uniq, g, self.state_of(emb)[0], self.lr, self.eps)

@@ -331,6 +331,28 @@ class _CacheBase:
             check(_lib.coala_cache_adagrad_rows(self._h, int(ids_ptr) or None, int(n), int(grad_ptr) or None, int(state_ptr) or None, float(lr),
                                                 float(eps), current_stream()))
 
+    def adam_rows(self, ids_ptr, n, grad_ptr, m_ptr, v_ptr, lr, betas=(0.9, 0.999), eps=1e-8, row_step_ptr=0, step=0):
+        """Sparse Adam step on n table rows on the current stream (coala_cache_adam_rows): m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g * g,
+        row(id) -= lr (m / bc1) / (sqrt(v / bc2) + eps), bc_i = 1 - b_i ** t.  m, v: device-visible fp32 [num_rows, dim], not cached.
+        row_step_ptr: int32 [num_rows], t = ++row_step[id] (DGL's lazy Adam); 0: t = step >= 1 for every row (torch's rule)."""
+        b1, b2 = betas
+        if native is not None:
+            native.cache_adam_rows(self._h.value or 0, int(ids_ptr), int(n), int(grad_ptr), int(m_ptr), int(v_ptr), int(row_step_ptr), int(step),
+                                   float(lr), float(b1), float(b2), float(eps), current_stream())
+        else:
+            check(_lib.coala_cache_adam_rows(self._h, int(ids_ptr) or None, int(n), int(grad_ptr) or None, int(m_ptr) or None, int(v_ptr) or None,
+                                             int(row_step_ptr) or None, int(step), float(lr), float(b1), float(b2), float(eps), current_stream()))
+
+    def rowwise_adagrad_rows(self, ids_ptr, n, grad_ptr, row_state_ptr, lr, eps=1e-10):
+        """Row-wise Adagrad step on n table rows on the current stream (coala_cache_rowwise_adagrad_rows): s = row_state[id] + mean(g * g),
+        row_state[id] = s, row(id) -= lr * g / (sqrt(s) + eps).  row_state: device-visible fp32 [num_rows]."""
+        if native is not None:
+            native.cache_rowwise_adagrad_rows(self._h.value or 0, int(ids_ptr), int(n), int(grad_ptr), int(row_state_ptr), float(lr), float(eps),
+                                              current_stream())
+        else:
+            check(_lib.coala_cache_rowwise_adagrad_rows(self._h, int(ids_ptr) or None, int(n), int(grad_ptr) or None, int(row_state_ptr) or None,
+                                                        float(lr), float(eps), current_stream()))
+
     def _serve(self, out_ptr, ids_ptr, n):
         if native is not None:
             native.cache_serve(self._h.value or 0, int(out_ptr), int(ids_ptr), int(n), current_stream())

@@ -82,6 +82,8 @@ SYMBOLS = {
     "coala_cache_row_dim": (_I64, [_VP]),
     "coala_cache_write_rows": (_I, [_VP, _VP, _I64, _VP, _I, C.c_float, _VP]),
     "coala_cache_adagrad_rows": (_I, [_VP, _VP, _I64, _VP, _VP, C.c_float, C.c_float, _VP]),
+    "coala_cache_adam_rows": (_I, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64, C.c_float, C.c_float, C.c_float, C.c_float, _VP]),
+    "coala_cache_rowwise_adagrad_rows": (_I, [_VP, _VP, _I64, _VP, _VP, C.c_float, C.c_float, _VP]),
     "coala_cache_fetch_events": (_I, [_VP, _I]),
     "coala_cache_last_fetch_events": (_I, [_VP, C.POINTER(_VP), C.POINTER(_VP)]),
     "coala_stream_wait_event": (_I, [_VP, _VP]),

@@ -29,6 +29,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -454,7 +455,8 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, kK1MinWaves) void probe_gather_ke
 }
 
 // ---------------------------------------------------------------------------------------------------------- KW
-// Write-through row update (coala_cache_write_rows / coala_cache_adagrad_rows): one kernel over (line size, VEC, tag width, op).
+// Write-through row update (coala_cache_write_rows / _adagrad_rows / _adam_rows / _rowwise_adagrad_rows): one kernel over (line size, VEC, tag
+// width, op); the ops are assign, add, element-wise Adagrad, Adam and row-wise Adagrad.
 // A wave takes the SPL rows whose tag sets one wave-wide 16-B load fetches (8 with 32-bit tags, 4 with 64-bit ones), exactly as a tag step of
 // K1: every lane compares its own KPL tags, and an OR over the LPS lanes of a row -- K1's DPP ladder with | in place of min -- leaves the row's
 // whole 32-way match mask in each of them.  The rows are then moved RPP at a time: the old value comes from the lowest matching line when there is
@@ -466,7 +468,66 @@ __global__ __launch_bounds__(64 * kK1MaxWaves, kK1MinWaves) void probe_gather_ke
 // host at 53.4-53.9 GB/s in all three ops, 97-101 % of a pinned hipMemcpy of the same bytes in the same process; 4-KiB rows at 55 GB/s (assign,
 // 97 %) and, with a third to three quarters of the old values read back over the link, 47-51 GB/s (add, Adagrad: 84-91 %).  An Adagrad state in
 // pinned host memory adds a read and a write of the link per element: 23-24 GB/s of rows (41-43 %).
-enum { kOpAssign = 0, kOpAdd = 1, kOpAdagrad = 2 };
+// Adam and row-wise Adagrad (profiles/r19_embedding_optimizers.txt, same shapes, alternating with Adagrad): 0.99-1.03 and 1.01-1.06 of Adagrad's time;
+// the reduction's wait between a row's loads and its stores is hidden by the other waves.
+// Adam (coala_cache_adam_rows) is a fourth element-wise op with two state rows; its step count t is the row's own counter (read by every lane
+// of the row, stored back by the first) or the caller's, and the bias corrections 1 - beta^t = -expm1(t ln beta) are taken once per row in double.
+// exp_avg is signed, so beta1 m and (1 - beta1) g can cancel: the product's rounding error is carried (one more fma) and added back after the
+// sum, which keeps the error of the new exp_avg -- and of the step -- relative to the value itself.
+// Row-wise Adagrad (coala_cache_rowwise_adagrad_rows) reduces over the row between its loads and its stores: every lane sums the squares of
+// its own floats in load order (fma chain), an xor butterfly over the row's LPR lanes (1, 2, .. LPR / 2) adds the partial sums -- both
+// partners of a step add the same two numbers, so all lanes end with the same bits and the result does not depend on the run.  The butterfly
+// runs with all 64 lanes active: with two rows per pass a rejected row does not leave the iteration (its loads and stores are predicated off
+// and it sums zeros), and a step never crosses the half-wave of its row.  Additions on the longest path from one square to the total:
+// VPL * VEC - 1 in the lane, log2(LPR) across lanes -- at most 21 (1024-float lines).
+enum { kOpAssign = 0, kOpAdd = 1, kOpAdagrad = 2, kOpAdam = 3, kOpRowAdagrad = 4 };
+
+// What the last two ops need beyond (state, a, eps).  It trails the kernel's arguments: those of the first three ops are where they were.
+struct WriteExtra {
+    float* state2;       // Adam: exp_avg_sq (state: exp_avg)
+    int32_t* row_step;   // Adam: per-row step counter, or null: t = step
+    double ln_b1, ln_b2; // Adam: ln beta_i, from the fp32 beta_i
+    double step;         // Adam: t of every row when row_step is null
+    float b1, b2;        // Adam
+    float omb1, omb1_lo; // Adam: 1 - beta1 as an fp32 pair (the low part is 0 for beta1 >= 0.5)
+    float omb2;          // Adam: 1 - beta2
+};
+struct AdamRow { float step_size, rsbc2; };   // lr / bc1 and 1 / sqrt(bc2) of one row
+
+__device__ __forceinline__ float adam_op(float g, float old, float& m, float& v, const WriteExtra& ex, const AdamRow& r, float eps) {
+    const float p = ex.omb1 * g;
+    float e = __builtin_fmaf(ex.omb1, g, -p);            // p + e == omb1 * g exactly
+    e = __builtin_fmaf(ex.omb1_lo, g, e);
+    const float mn = __builtin_fmaf(ex.b1, m, p) + e;
+    const float vn = __builtin_fmaf(ex.b2, v, ex.omb2 * (g * g));
+    m = mn;
+    v = vn;
+    return old - (r.step_size * mn) / __builtin_fmaf(__builtin_sqrtf(vn), r.rsbc2, eps);
+}
+__device__ __forceinline__ vfloat4 adam_op(vfloat4 g, vfloat4 old, vfloat4& m, vfloat4& v, const WriteExtra& ex, const AdamRow& r, float eps) {
+    vfloat4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float mk = m[k], vk = v[k];
+        o[k] = adam_op(g[k], old[k], mk, vk, ex, r, eps);
+        m[k] = mk;
+        v[k] = vk;
+    }
+    return o;
+}
+__device__ __forceinline__ float sq_acc(float x, float acc) { return __builtin_fmaf(x, x, acc); }
+__device__ __forceinline__ float sq_acc(vfloat4 x, float acc) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc = __builtin_fmaf(x[k], x[k], acc);
+    return acc;
+}
+__device__ __forceinline__ float scaled_sub(float x, float old, float scale) { return __builtin_fmaf(-scale, x, old); }
+__device__ __forceinline__ vfloat4 scaled_sub(vfloat4 x, vfloat4 old, float scale) {
+    vfloat4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = __builtin_fmaf(-scale, x[k], old[k]);
+    return o;
+}
 
 template <int OP> __device__ __forceinline__ float write_op(float x, float old, float& st, float a, float eps) {
     if (OP == kOpAssign) return x;
@@ -488,7 +549,7 @@ template <int OP> __device__ __forceinline__ vfloat4 write_op(vfloat4 x, vfloat4
 
 template <int CD, int VEC, typename TAG, int OP>
 __global__ __launch_bounds__(256) void write_rows_kernel(const int64_t* __restrict__ ids, const float* __restrict__ src, float* __restrict__ state,
-                                                         int64_t n, float a, float eps, CacheDev c) {
+                                                         int64_t n, float a, float eps, CacheDev c, WriteExtra ex) {
     using G = Geo<CD, VEC, 1>;
     using V = typename VecT<VEC>::type;
     using TG = TagGeo<TAG>;
@@ -535,30 +596,68 @@ __global__ __launch_bounds__(256) void write_rows_kernel(const int64_t* __restri
             const uint32_t set = (uint32_t)__shfl((int)set_l, TG::LPS * q);
             const uint64_t id = shfl64(id_l, TG::LPS * q);
             const bool live = __shfl((int)ok, TG::LPS * q) != 0;
-            if (!live) continue;
+            // (row-wise Adagrad: a wave-uniform exit only, so that the butterfly below runs with all 64 lanes; `act` predicates the dead half)
+            if (OP == kOpRowAdagrad ? __ballot(live) == 0 : !live) continue;
+            const bool act = OP == kOpRowAdagrad ? live : true;
             const int64_t i = chunk * R + q;
             const V* xs = reinterpret_cast<const V*>(src + i * (int64_t)c.dim);
             V* cold_row = reinterpret_cast<V*>(cold + id * (uint64_t)c.dim);   // (never partitioned: refused on the host)
-            V* st_row = OP == kOpAdagrad ? reinterpret_cast<V*>(state + id * (uint64_t)c.dim) : nullptr;
+            V* st_row = (OP == kOpAdagrad || OP == kOpAdam) ? reinterpret_cast<V*>(state + id * (uint64_t)c.dim) : nullptr;
+            V* st2_row = OP == kOpAdam ? reinterpret_cast<V*>(ex.state2 + id * (uint64_t)c.dim) : nullptr;
             float* set_lines = c.lines + (uint64_t)set * COALA_WAYS * CD;
             const V* old_row = m ? reinterpret_cast<const V*>(set_lines + (uint64_t)__builtin_ctz(m) * CD) : cold_row;
-            V x[G::VPL], old[G::VPL], st[G::VPL];
+            V x[G::VPL], old[G::VPL], st[G::VPL], st2[G::VPL];
 #pragma unroll
             for (int v = 0; v < G::VPL; ++v) {
                 const uint32_t u = v * G::LPR + l_in;
-                x[v] = V(0.0f); old[v] = V(0.0f); st[v] = V(0.0f);
-                if (u < nunits) {
+                x[v] = V(0.0f); old[v] = V(0.0f); st[v] = V(0.0f); st2[v] = V(0.0f);
+                if (u < nunits && act) {
                     x[v] = nt_load(xs + u);
                     if (OP != kOpAssign) old[v] = old_row[u];
-                    if (OP == kOpAdagrad) st[v] = st_row[u];
+                    if (OP == kOpAdagrad || OP == kOpAdam) st[v] = st_row[u];
+                    if (OP == kOpAdam) st2[v] = st2_row[u];
                 }
+            }
+            AdamRow ar = {0.0f, 0.0f};
+            if (OP == kOpAdam) {   // the row's step count and bias corrections, the same in every lane of the row
+                double t = ex.step;
+                if (ex.row_step) {
+                    const int32_t t0 = ex.row_step[id];
+                    const int32_t t1 = t0 < 0x7FFFFFFF ? t0 + 1 : t0;   // saturates
+                    if (l_in == 0) ex.row_step[id] = t1;                // (after the read: it waits for t0; distinct ids, so no other wave's word)
+                    t = (double)t1;
+                }
+                const double bc1 = -expm1(t * ex.ln_b1), bc2 = -expm1(t * ex.ln_b2);
+                ar.step_size = (float)((double)a / bc1);
+                ar.rsbc2 = (float)(1.0 / sqrt(bc2));
+            }
+            float scale = 0.0f;
+            if (OP == kOpRowAdagrad) {
+                float part = 0.0f;                                       // 0 in lanes past dim and in a dead half
+#pragma unroll
+                for (int v = 0; v < G::VPL; ++v) part = sq_acc(x[v], part);
+#pragma unroll
+                for (int d = 1; d < G::LPR; d <<= 1) part += __shfl_xor(part, d);   // all lanes active; d < LPR keeps a step inside the row
+                float s = 0.0f;
+                if (act) s = state[id] + part / (float)c.dim;
+                if (act && l_in == 0) state[id] = s;
+                scale = a / (__builtin_sqrtf(s) + eps);
             }
 #pragma unroll
             for (int v = 0; v < G::VPL; ++v) {
                 const uint32_t u = v * G::LPR + l_in;
-                if (u < nunits) {
-                    const V nv = write_op<OP>(x[v], old[v], st[v], a, eps);
-                    if (OP == kOpAdagrad) st_row[u] = st[v];
+                if (u < nunits && act) {
+                    V nv;
+                    if (OP == kOpAdam) {
+                        nv = adam_op(x[v], old[v], st[v], st2[v], ex, ar, eps);
+                        st_row[u] = st[v];
+                        st2_row[u] = st2[v];
+                    } else if (OP == kOpRowAdagrad) {
+                        nv = scaled_sub(x[v], old[v], scale);
+                    } else {
+                        nv = write_op<OP>(x[v], old[v], st[v], a, eps);
+                        if (OP == kOpAdagrad) st_row[u] = st[v];
+                    }
                     cold_row[u] = nv;
                     for (uint32_t mm = m; mm; mm &= mm - 1)
                         reinterpret_cast<V*>(set_lines + (uint64_t)__builtin_ctz(mm) * CD)[u] = nv;
@@ -1819,25 +1918,28 @@ int coala_cache_scatter(coala_cache_t* h, float* out, const float* src, const in
     return coala_cache_scatter_ranges(h, out, src, map, &b, &n, 1, stream);
 }
 
-// coala_cache_write_rows / coala_cache_adagrad_rows: every refusal comes before the first launch; one kernel (write_rows_kernel).
+// coala_cache_write_rows / _adagrad_rows / _adam_rows / _rowwise_adagrad_rows: every refusal comes before the first launch; one kernel
+// (write_rows_kernel).
 static int write_rows_impl(coala_cache_t* h, const int64_t* ids, int64_t n, const float* src, float* state, int op, float a, float eps,
-                           void* stream) {
+                           void* stream, const WriteExtra& ex = WriteExtra{}) {
     if (!h) return fail(COALA_EINVAL, "null handle");
     if (n < 0 || n > 0x7FFFFFFFll) return fail(COALA_EINVAL, "n=%lld out of range", (long long)n);
-    if (op < kOpAssign || op > kOpAdagrad) return fail(COALA_EINVAL, "write mode %d outside 0..1", op);
+    if (op < kOpAssign || op > kOpRowAdagrad) return fail(COALA_EINVAL, "write mode %d outside 0..1", op);
     if (h->cfg.n_gpus != 1 || (h->cfg.flags & (COALA_FLAG_DISTRIBUTED | COALA_FLAG_COLD_PARTITIONED)))
         return fail(COALA_EINVAL, "row writes need an isolated cache of one GPU (n_gpus=%d, flags=0x%x): a second cache over the same table would keep stale lines",
                     h->cfg.n_gpus, h->cfg.flags);
     if (h->open_batch_rows >= 0)
         return fail(COALA_EINVAL, "a batch of %lld rows is still open (%lld filled): finish its serve_fill calls or call coala_cache_serve_abort",
                     (long long)h->open_batch_rows, (long long)h->open_filled_rows);
-    if (n > 0 && (!ids || !src || (op == kOpAdagrad && !state))) return fail(COALA_EINVAL, "null buffer");
+    const bool elem_state = op == kOpAdagrad || op == kOpAdam;   // state tables of [num_rows, dim]
+    if (n > 0 && (!ids || !src || (op >= kOpAdagrad && !state) || (op == kOpAdam && !ex.state2))) return fail(COALA_EINVAL, "null buffer");
     if (n == 0) return COALA_OK;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->cfg.device));
     if (int rc_ = follow_stream(h, s)) return rc_;
     const CacheDev& d = h->d;
-    const bool vec4 = (d.dim % 4 == 0) && aligned16(d.cold) && aligned16(src) && (op != kOpAdagrad || aligned16(state));
+    const bool vec4 = (d.dim % 4 == 0) && aligned16(d.cold) && aligned16(src) && (!elem_state || aligned16(state)) &&
+                      (op != kOpAdam || aligned16(ex.state2));
     int rc = dispatch_geo(d.cache_dim, vec4, [&](auto geo) -> int {
         constexpr int CD = geo_cd(geo);
         constexpr int VEC = geo_vec(geo);
@@ -1846,10 +1948,12 @@ static int write_rows_impl(coala_cache_t* h, const int64_t* ids, int64_t n, cons
             const int64_t chunks = (n + TagGeo<TAG>::SPL - 1) / TagGeo<TAG>::SPL;
             // one wave per chunk up to 4096 waves behind a host tier (a wave has at most two rows of reads and writes on the link), 32768 on HBM
             const dim3 grid(grid_for(chunks, 4, h->host_tier ? 1024 : 8192)), block(256);
-            auto k = op == kOpAssign ? write_rows_kernel<CD, VEC, TAG, kOpAssign>
-                     : op == kOpAdd  ? write_rows_kernel<CD, VEC, TAG, kOpAdd>
-                                     : write_rows_kernel<CD, VEC, TAG, kOpAdagrad>;
-            hipLaunchKernelGGL(k, grid, block, 0, s, ids, src, state, n, a, eps, d);
+            auto k = op == kOpAssign    ? write_rows_kernel<CD, VEC, TAG, kOpAssign>
+                     : op == kOpAdd     ? write_rows_kernel<CD, VEC, TAG, kOpAdd>
+                     : op == kOpAdagrad ? write_rows_kernel<CD, VEC, TAG, kOpAdagrad>
+                     : op == kOpAdam    ? write_rows_kernel<CD, VEC, TAG, kOpAdam>
+                                        : write_rows_kernel<CD, VEC, TAG, kOpRowAdagrad>;
+            hipLaunchKernelGGL(k, grid, block, 0, s, ids, src, state, n, a, eps, d, ex);
         };
         if (d.tag32) launch(uint32_t{}); else launch(uint64_t{});
         return COALA_OK;
@@ -1868,6 +1972,31 @@ int coala_cache_write_rows(coala_cache_t* h, const int64_t* ids, int64_t n, cons
 int coala_cache_adagrad_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* grad, float* state, float lr, float eps,
                              void* stream) {
     return write_rows_impl(h, ids, n, grad, state, kOpAdagrad, lr, eps, stream);
+}
+
+int coala_cache_adam_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* grad, float* exp_avg, float* exp_avg_sq,
+                          int32_t* row_step, int64_t step, float lr, float beta1, float beta2, float eps, void* stream) {
+    if (h && !(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f))
+        return fail(COALA_EINVAL, "Adam: betas (%g, %g) outside [0, 1)", (double)beta1, (double)beta2);
+    if (h && !row_step && step < 1) return fail(COALA_EINVAL, "Adam: step=%lld without a row_step vector, steps count from 1", (long long)step);
+    WriteExtra ex{};
+    ex.state2 = exp_avg_sq;
+    ex.row_step = row_step;
+    ex.ln_b1 = std::log((double)beta1);   // (-inf for beta = 0: -expm1(-inf) = 1, no correction)
+    ex.ln_b2 = std::log((double)beta2);
+    ex.step = (double)step;
+    ex.b1 = beta1;
+    ex.b2 = beta2;
+    const double omb1 = 1.0 - (double)beta1;
+    ex.omb1 = (float)omb1;
+    ex.omb1_lo = (float)(omb1 - (double)ex.omb1);
+    ex.omb2 = (float)(1.0 - (double)beta2);
+    return write_rows_impl(h, ids, n, grad, exp_avg, kOpAdam, lr, eps, stream, ex);
+}
+
+int coala_cache_rowwise_adagrad_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* grad, float* row_state, float lr,
+                                     float eps, void* stream) {
+    return write_rows_impl(h, ids, n, grad, row_state, kOpRowAdagrad, lr, eps, stream);
 }
 
 int coala_cache_color_counts(coala_cache_t* h, int32_t* dst, int32_t n_entries, void* stream) {

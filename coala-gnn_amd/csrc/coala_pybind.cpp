@@ -353,6 +353,17 @@ PYBIND11_MODULE(_coala_pybind, m) {
         py::gil_scoped_release nogil;
         check(coala_cache_adagrad_rows(ptr<coala_cache_t>(h), ptr<const int64_t>(ids), n, ptr<const float>(grad), ptr<float>(state), lr, eps, stream_of(stream)));
     });
+    m.def("cache_adam_rows", [](uint64_t h, uint64_t ids, int64_t n, uint64_t grad, uint64_t exp_avg, uint64_t exp_avg_sq, uint64_t row_step,
+                                int64_t step, float lr, float beta1, float beta2, float eps, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_cache_adam_rows(ptr<coala_cache_t>(h), ptr<const int64_t>(ids), n, ptr<const float>(grad), ptr<float>(exp_avg),
+                                    ptr<float>(exp_avg_sq), ptr<int32_t>(row_step), step, lr, beta1, beta2, eps, stream_of(stream)));
+    });
+    m.def("cache_rowwise_adagrad_rows", [](uint64_t h, uint64_t ids, int64_t n, uint64_t grad, uint64_t row_state, float lr, float eps, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_cache_rowwise_adagrad_rows(ptr<coala_cache_t>(h), ptr<const int64_t>(ids), n, ptr<const float>(grad), ptr<float>(row_state), lr, eps,
+                                               stream_of(stream)));
+    });
     m.def("cache_fetch_distributed", [](uint64_t h, uint64_t c, uint64_t out, uint64_t idx, int64_t n, uint64_t stream) {
         py::gil_scoped_release nogil;
         check(coala_cache_fetch_distributed(ptr<coala_cache_t>(h), ptr<coala_comm_t>(c), ptr<float>(out), ptr<const int64_t>(idx), n, stream_of(stream)));

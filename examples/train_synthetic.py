@@ -36,7 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "coala-gnn_amd"))
 
 import torch  # noqa: E402
 
-from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, NodeEmbedding, SparseAdagrad, SparseSGD, SSD_INFO  # noqa: E402
+from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, NodeEmbedding, RowWiseAdagrad, SparseAdagrad, SparseAdam, SparseSGD, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
 from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, GATv2, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
 from COALA_GNN.sampler import (EdgePredictionSampler, LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler,  # noqa: E402
@@ -64,7 +64,9 @@ def make_embedding(args, loader):
     if not args.node_embedding:
         return None, None
     emb = NodeEmbedding.from_manager(loader.COALA_GNN_Manager)
-    cls = SparseAdagrad if args.emb_optimizer == "adagrad" else SparseSGD
+    if args.emb_optimizer == "adam":
+        return emb, SparseAdam([emb], lr=args.emb_lr, betas=tuple(args.emb_betas), step=args.emb_step)
+    cls = {"adagrad": SparseAdagrad, "rowwise_adagrad": RowWiseAdagrad, "sgd": SparseSGD}[args.emb_optimizer]
     return emb, cls([emb], lr=args.emb_lr)
 
 
@@ -178,7 +180,11 @@ def main():
                          "cache, randomly initialised) updated by a sparse optimizer that touches only the minibatch's rows; synthetic graph, "
                          "--cache_backend isolated, one GPU, --prefetch 0")
     ap.add_argument("--emb_dim", type=int, default=None, help="with --node_embedding: floats per embedding row (default: --dim)")
-    ap.add_argument("--emb_optimizer", type=str, default="adagrad", choices=["adagrad", "sgd"], help="with --node_embedding: SparseAdagrad or SparseSGD")
+    ap.add_argument("--emb_optimizer", type=str, default="adagrad", choices=["adagrad", "adam", "rowwise_adagrad", "sgd"],
+                    help="with --node_embedding: SparseAdagrad, SparseAdam, RowWiseAdagrad (one float of state per row) or SparseSGD")
+    ap.add_argument("--emb_betas", type=float, nargs=2, default=[0.9, 0.999], help="with --emb_optimizer adam: beta1 beta2")
+    ap.add_argument("--emb_step", type=str, default="row", choices=["row", "global"],
+                    help="with --emb_optimizer adam: bias corrections from each row's own update count (DGL) or from the optimizer's step count (torch)")
     ap.add_argument("--emb_lr", type=float, default=0.05, help="with --node_embedding: learning rate of the sparse optimizer")
     ap.add_argument("--batch_size", type=int, default=1024)
     ap.add_argument("--hidden_channels", type=int, default=128)

@@ -169,12 +169,13 @@ int64_t coala_cache_row_dim(const coala_cache_t* h);
  * written to needs a WRITABLE, device-visible table (pinned host or HBM).
  *   ids   : device int64[n], pairwise distinct (the caller's duty).
  *   src / grad : device-visible fp32 [n, dim].
- *   state : device-visible fp32 [num_rows, dim], HBM or pinned host, addressed by id; it is not cached.
+ *   state : device-visible fp32 [num_rows, dim], HBM or pinned host, addressed by id; it is not cached.  Adam has two (exp_avg,
+ *           exp_avg_sq) and an optional int32 [num_rows] step vector; row-wise Adagrad has one fp32 [num_rows] vector instead.
  * What a write changes.  row(id) is the cold-table row `id` plus every cache line whose tag equals id.  A write stores the new value to
  * the cold row and to EVERY way of the id's set whose tag matches, not only the lowest one: the same id can sit in several ways (a read
  * inserts one copy per duplicate miss of a batch), reads take the lowest matching way, and once round robin evicts that copy the next
  * one is read.
- * Where the old value comes from (mode 1, Adagrad).  It is read once: on a hit from the lowest matching line (no host-link read),
+ * Where the old value comes from (mode 1, Adagrad, Adam, row-wise Adagrad).  It is read once: on a hit from the lowest matching line (no host-link read),
  * otherwise from the cold row.
  * The invariant.  Before and after every call, every valid line holds the bytes of its cold row in floats [0, dim).
  * What a write leaves alone.  It never inserts, evicts or ranks: keys, set_cnt, color_meta, the colour counters and the hit / miss
@@ -185,8 +186,9 @@ int64_t coala_cache_row_dim(const coala_cache_t* h);
  * COALA_FLAG_SYNC.  COALA_EINVAL with a message, before any launch, for: a null handle; n outside [0, 2^31 - 1]; a null buffer with
  * n > 0; a mode outside 0..1; an open serve batch; cfg.n_gpus != 1, COALA_FLAG_DISTRIBUTED or COALA_FLAG_COLD_PARTITIONED (a second
  * cache over the same table would keep stale lines; so the cold row is always `id`).  n == 0 returns COALA_OK and launches nothing.
- * One kernel per call.  16-byte accesses when dim % 4 == 0 and the cold table, src / grad and state are 16-byte aligned, 4-byte
- * accesses otherwise (the rule of coala_cache_read_feature).
+ * Adam also refuses a beta outside [0, 1) and, without a row_step vector, step < 1.
+ * One kernel per call.  16-byte accesses when dim % 4 == 0 and the cold table, src / grad and every [num_rows, dim] state table are
+ * 16-byte aligned, 4-byte accesses otherwise (the rule of coala_cache_read_feature).
  * ------------------------------------------------------------------------------------------------------------ */
 /* mode 0 (assign): row(id) = src[i];  mode 1 (add): row(id) = fmaf(alpha, src[i], row(id)) */
 int coala_cache_write_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* src, int mode, float alpha, void* stream);
@@ -194,6 +196,18 @@ int coala_cache_write_rows(coala_cache_t* h, const int64_t* ids, int64_t n, cons
  * element-wise state) */
 int coala_cache_adagrad_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* grad, float* state, float lr, float eps,
                              void* stream);
+/* Adam, per element (DGL's SparseAdam; torch.optim.SparseAdam's rule up to rounding):
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g*g;  row(id) -= lr (m / bc1) / (sqrt(v / bc2) + eps),  bc_i = 1 - beta_i^t.
+ * t is the row's own count after the increment when row_step != NULL (t = ++row_step[id], saturating at INT32_MAX: lazy Adam, as DGL
+ * counts), else `step` >= 1 for every row (torch's rule).  bc_i = -expm1(t ln beta_i), once per row in double, ln beta_i from the fp32
+ * beta_i; 1 - beta^t itself loses four digits to cancellation at t = 1, beta2 = 0.999.  exp_avg / exp_avg_sq: [num_rows, dim] each. */
+int coala_cache_adam_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* grad, float* exp_avg, float* exp_avg_sq,
+                          int32_t* row_step, int64_t step, float lr, float beta1, float beta2, float eps, void* stream);
+/* Row-wise Adagrad (DGL-KE's rule; one float of state per row):
+ *   s = row_state[id] + (1 / dim) sum_k g_k^2;  row_state[id] = s;  row(id)_k -= lr g_k / (sqrtf(s) + eps).
+ * The sum has a fixed order (per lane, then an xor butterfly over the row's lanes): s is bitwise reproducible from run to run. */
+int coala_cache_rowwise_adagrad_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* grad, float* row_state, float lr,
+                                     float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Native fused fetch of the owner-partitioned cache over RCCL (one process per GPU, one communicator per cache group).
