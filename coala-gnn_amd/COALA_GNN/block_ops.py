@@ -529,3 +529,126 @@ def pair_dot_torch(h, src, dst):
     keep = (s >= 0) & (d >= 0)
     prod = (h[s.clamp_min(0)] * h[d.clamp_min(0)]).sum(-1)
     return prod * keep.view((-1,) + (1,) * (prod.dim() - 1)).to(prod.dtype)
+
+
+# ------------------------------------------------------------------------------------------------------------ skip-gram window loss
+SKIPGRAM_MAX_FLOATS = 16384   # (walk_length + 1) * dim a lane group stages in LDS (coala_block_ops.hip: kSkipMaxFloats, 64 KB)
+SKIPGRAM_MAX_LEN = 128
+
+
+class _SkipgramLoss(torch.autograd.Function):
+    """mean over the valid window pairs of pos of softplus(-<h[a], h[b]>) + the same mean of softplus(+<.,.>) over neg
+    (coala_block_skipgram_loss, one launch per table that has rows).  The kernel stores one partial sum and one pair count per row;
+    they are added up here in float64 and the loss is rounded to fp32 once: the same bits call after call.  The backward is one
+    launch per table, one double atomic per (position, element) into ONE float64 buffer shaped like h, rounded to fp32 once.
+    h [N, D] contiguous fp32; pos, neg contiguous int32 [R, L1]."""
+
+    @staticmethod
+    def forward(ctx, h, pos, neg, context):
+        dev = h.device.index or 0
+        total = torch.zeros((), dtype=torch.float64, device=h.device)
+        saved, signs = [], []
+        for rows, sign in ((pos, -1.0), (neg, 1.0)):
+            R, L1 = rows.shape
+            if R == 0:
+                continue
+            partial = torch.empty(R, dtype=torch.float32, device=h.device)
+            count = torch.empty(R, dtype=torch.int32, device=h.device)
+            _capi.check(_lib.coala_block_skipgram_loss(dev, h.data_ptr(), rows.data_ptr(), partial.data_ptr(), count.data_ptr(), R, L1, context,
+                                                       h.shape[1], sign, current_stream()))
+            n = count.sum(dtype=torch.int64).clamp_min(1)   # no valid pair: every partial is 0, and so is the mean
+            total = total + partial.sum(dtype=torch.float64) / n
+            saved += [rows, n]
+            signs.append(sign)
+        ctx.save_for_backward(h, *saved)
+        ctx.args = (context, signs)
+        return total.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        h, *saved = ctx.saved_tensors
+        context, signs = ctx.args
+        acc = torch.zeros(h.shape, dtype=torch.float64, device=h.device)   # the kernels add in double: a node collects hundreds of terms
+        for k, sign in enumerate(signs):
+            rows, n = saved[2 * k], saved[2 * k + 1]
+            scale = (grad_out.to(torch.float64) / n).contiguous()   # a device double: nothing waits for the host
+            _capi.check(_lib.coala_block_skipgram_loss_backward(h.device.index or 0, h.data_ptr(), rows.data_ptr(), acc.data_ptr(), scale.data_ptr(),
+                                                                rows.shape[0], rows.shape[1], context, h.shape[1], sign, current_stream()))
+        return acc.to(torch.float32), None, None, None
+
+
+def _skipgram_args(h, pos, neg, context_size):
+    """The checks of skipgram_loss / skipgram_loss_torch."""
+    if h.dim() != 2:
+        raise ValueError(f"h of shape {tuple(h.shape)}: skipgram_loss takes [N, D]")
+    for name, t in (("pos", pos), ("neg", neg)):
+        if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError(f"{name} must be an integer tensor")
+        if t.dim() != 2:
+            raise ValueError(f"{name} of shape {tuple(t.shape)}: a walk table [R, walk_length + 1]")
+        if isinstance(context_size, bool) or not isinstance(context_size, int) or not 2 <= context_size <= t.shape[1]:
+            raise ValueError(f"context_size {context_size!r}: 2..{t.shape[1]}, the columns of {name}")
+
+
+def _skipgram_bound(h, tables):
+    """IndexError when a table entry is >= N (one host read)."""
+    top = max([int(t.max()) for t in tables if t.numel()], default=-1)
+    if top >= h.shape[0]:
+        raise IndexError(f"a walk table entry is {top}: h has {h.shape[0]} rows")
+
+
+def skipgram_loss(h, pos, neg, context_size, validate=True):
+    """The skip-gram loss of walk tables, PyG's Node2Vec.loss: h fp32 [N, D]; pos, neg integer tables [R, L + 1] of rows of h, -1 = no
+    node (a walk that has ended; a WalkBatch's pos and neg).  For a table, every window start a in 0 .. L + 1 - C (C = context_size) and
+    every j in 1 .. C - 1 give the pair (rows[r, a], rows[r, a + j]), valid when both entries are >= 0, with the score s = <h[.], h[.]>;
+        loss = mean over pos's valid pairs of softplus(-s) + mean over neg's valid pairs of softplus(s),
+    a mean over no pair being 0.  softplus(-s) = -log(sigmoid(s)) stands in for PyG's -log(sigmoid(s) + 1e-15): the same value until
+    sigmoid(s) nears 1e-15, where PyG's saturates at 34.5 and this one keeps growing like -s, with a gradient that does not vanish.
+    Native kernels -- a walk's rows staged once in on-chip memory, every window dot formed from there; the backward adds one
+    atomic per (position, element), not one per pair, into a float64 buffer
+    rounded to fp32 once -- for fp32 h on the GPU with index tables on the GPU, L + 1 <= 128 and
+    (L + 1) * D <= 16384; skipgram_loss_torch otherwise.  The forward value is bitwise reproducible on the native path.  An entry >= N
+    raises IndexError (on the native path one host read per call, which validate=False skips for tables that address h by
+    construction, as a WalkBatch's do)."""
+    _skipgram_args(h, pos, neg, context_size)
+    native = (h.is_cuda and h.dtype == torch.float32 and pos.is_cuda and neg.is_cuda and h.shape[1] > 0 and h.shape[0] < (1 << 31)
+              and all(t.shape[1] <= SKIPGRAM_MAX_LEN and t.shape[1] * h.shape[1] <= SKIPGRAM_MAX_FLOATS for t in (pos, neg)))
+    if not native:
+        return skipgram_loss_torch(h, pos, neg, context_size)
+    if validate:
+        _skipgram_bound(h, (pos, neg))
+    if pos.shape[0] == 0 and neg.shape[0] == 0:
+        return h.sum() * 0.0
+    p32, n32 = ((t if t.dtype == torch.int32 else t.clamp(-1, (1 << 31) - 1).to(torch.int32)).contiguous() for t in (pos, neg))
+    return _SkipgramLoss.apply(h.contiguous(), p32, n32, context_size)
+
+
+def _skipgram_table_torch(h, rows, context, sign):
+    """One table's mean in plain torch: the window pairs as two [R, P] position lists, two gathers, a product and a sum."""
+    R, L1 = rows.shape
+    a = torch.arange(L1 - context + 1, device=h.device)
+    j = torch.arange(1, context, device=h.device)
+    first = a[:, None].expand(-1, context - 1).reshape(-1)
+    second = (a[:, None] + j[None, :]).reshape(-1)
+    total = h.new_zeros(())
+    n = torch.zeros((), dtype=torch.int64, device=h.device)
+    chunk = max(1, (1 << 24) // max(first.numel() * h.shape[1], 1))   # rows per pass: the gathers hold chunk * P * D elements
+    for r0 in range(0, R, chunk):
+        s, d = rows[r0: r0 + chunk][:, first], rows[r0: r0 + chunk][:, second]
+        keep = (s >= 0) & (d >= 0)
+        score = (h[s.clamp_min(0)] * h[d.clamp_min(0)]).sum(-1)
+        # softplus(x) as -logsigmoid(-x): torch's softplus switches to the identity above 20, which is off by 2e-9 there
+        total = total + (-torch.nn.functional.logsigmoid(-sign * score) * keep.to(score.dtype)).sum()
+        n = n + keep.sum()
+    return total / n.clamp_min(1).to(total.dtype)
+
+
+def skipgram_loss_torch(h, pos, neg, context_size):
+    """skipgram_loss in plain torch, any device and dtype, the same rules: built from gathers.  The fallback of skipgram_loss, and the
+    building block of its float64 reference."""
+    _skipgram_args(h, pos, neg, context_size)
+    tables = [t.to(device=h.device, dtype=torch.int64) for t in (pos, neg)]
+    _skipgram_bound(h, tables)
+    return _skipgram_table_torch(h, tables[0], context_size, -1.0) + _skipgram_table_torch(h, tables[1], context_size, 1.0)

@@ -17,7 +17,9 @@ from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _GatAggregate, _G
 __all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "RandomWalkNeighborSampler", "random_walk", "sort_csc_by_etype",
            "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT", "EID", "EdgePredictionSampler", "as_edge_prediction_sampler",
            "UniformNegativeSampler", "EdgeBatch", "edge_batch", "edge_batch_wait", "reverse_edge_ids", "MAX_NEGATIVES",
-           "TemporalNeighborSampler", "TemporalEdgePredictionSampler", "sort_csc_by_time", "check_time_sorted", "pair_code_bits"]
+           "TemporalNeighborSampler", "TemporalEdgePredictionSampler", "sort_csc_by_time", "check_time_sorted", "pair_code_bits",
+           "node2vec_random_walk", "node2vec_thresholds", "sort_csc_by_src", "check_src_sorted", "WalkBatch", "walk_batch", "walk_batch_begin",
+           "walk_batch_end", "MAX_WALK_LENGTH", "MAX_WALK_NEGATIVES"]
 
 _lib = _capi.load()
 
@@ -111,6 +113,7 @@ class CSCGraph(object):
         self.edata = dict(edata or {})
         self._weights, self._etypes, self._etimes = {}, {}, {}   # edata key -> (the entry, its version, num_rels or None, the validated device copy): _edata
         self._max_in_degree = None
+        self._src_sorted = None   # require_src_sorted: None = not checked yet, True = sorted, a ValueError = the refusal, kept
         self._h = C.c_void_p()
         dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _capi.check(_lib.coala_sampler_create(dev, self.indptr.data_ptr(), self.indices.data_ptr(), self.num_nodes,
@@ -122,6 +125,18 @@ class CSCGraph(object):
         if self._max_in_degree is None:
             self._max_in_degree = int((self.indptr[1:] - self.indptr[:-1]).max().item()) if self.num_nodes > 0 else 0
         return self._max_in_degree
+
+    def require_src_sorted(self):
+        """The second-order walks' demand at q != 1: rows sorted ascending by source id.  Checked once on the device (check_src_sorted)
+        and remembered either way (the CSC arrays of a CSCGraph are not meant to change); ValueError (naming sort_csc_by_src) otherwise."""
+        if self._src_sorted is None:
+            try:
+                check_src_sorted(self.indptr, self.indices)
+                self._src_sorted = True
+            except ValueError as e:
+                self._src_sorted = e
+        if self._src_sorted is not True:
+            raise ValueError(str(self._src_sorted))
 
     def _edata(self, cache, key, role, make, tag=None):
         """edata[key] through `make` (validate, then the device copy the kernels read), kept in `cache` until the entry is replaced or
@@ -1096,6 +1111,136 @@ def random_walk(g, nodes, length, restart_prob=0.0, num_walks=1, seed=0, step=0)
     _capi.check(_lib.coala_sampler_random_walk(g._h, nodes.data_ptr(), nodes.numel(), num_walks, length, thr, int(seed) & ((1 << 64) - 1),
                                                int(step) & ((1 << 64) - 1), 0, out.data_ptr(), current_stream()))
     return out
+
+
+MAX_WALK_LENGTH = 127      # hops of a second-order walk (coala_sampler.hip: kN2vMaxLength)
+MAX_WALK_NEGATIVES = 16    # negative rows per walk of a walk batch (kN2vMaxNeg)
+_MIN_ACCEPT = 1 << 28      # smallest threshold node2vec_random_walk takes: an acceptance ratio of 1/16
+
+
+def node2vec_thresholds(p, q):
+    """(thr_return, thr_near, thr_far) of node2vec's return parameter p and in-out parameter q, the three integers the walk kernel
+    compares 32 random bits with: m = max(1/p, 1, 1/q), int((1/p) / m * 2^32), int(1 / m * 2^32), int((1/q) / m * 2^32), in float64.
+    The largest is exactly 2^32.  ValueError unless p, q > 0 and finite."""
+    for name, x in (("p", p), ("q", q)):
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0.0 < float(x) < float("inf"):
+            raise ValueError(f"{name} {x!r}: a positive finite number")
+    a, b = 1.0 / float(p), 1.0 / float(q)
+    m = max(a, 1.0, b)
+    return int(a / m * 4294967296.0), int(1.0 / m * 4294967296.0), int(b / m * 4294967296.0)
+
+
+def sort_csc_by_src(indptr, indices):
+    """Sort the in-edges of every node by source id, the twin of sort_csc_by_etype / sort_csc_by_time: -> (indices_sorted, perm).  Stable:
+    repeated edges keep their CSC order.  perm (int64 [E]) maps new positions to old, indices_sorted = indices[perm], so per-edge data
+    is carried along as edata[key][perm].  Plain torch on the tensors' device; indptr is unchanged.  node2vec_random_walk and walk_batch
+    need a graph in this order when q != 1 (synthetic.symmetrize_csc already produces it)."""
+    srt, _, perm = _sort_csc_by_key(indptr, indices, indices, "sources")
+    return srt, perm
+
+
+def check_src_sorted(indptr, indices):
+    """What the second-order walks ask of a graph at q != 1, on the tensors' device: source ids non-decreasing inside every row of the
+    CSC.  ValueError (naming sort_csc_by_src) otherwise."""
+    E = indices.numel()
+    if E < 2:
+        return
+    drop = indices[1:] < indices[:-1]
+    starts = indptr[1:-1]
+    starts = starts[(starts > 0) & (starts < E)]
+    drop[starts - 1] = False
+    if bool(drop.any()):
+        raise ValueError("the rows of the graph must be sorted ascending by source id for a second-order walk with q != 1; sort it with "
+                         "COALA_GNN.sampler.sort_csc_by_src(indptr, indices)")
+
+
+def _walk_args(g, nodes, p, q, walk_length, num_walks, what):
+    """The checks node2vec_random_walk and walk_batch share -> (graph, start nodes on its device, thresholds)."""
+    for name, x, hi in (("walk_length", walk_length, MAX_WALK_LENGTH), ("num_walks", num_walks, 64)):
+        if isinstance(x, bool) or not isinstance(x, int) or not 1 <= x <= hi:
+            raise ValueError(f"{name} {x!r}: 1..{hi}")
+    thr = node2vec_thresholds(p, q)
+    if min(thr) < _MIN_ACCEPT:
+        raise ValueError(f"p={p!r}, q={q!r}: the smallest of 1/p, 1, 1/q is below 1/16 of the largest; a hop gives up after 256 rejected "
+                         f"candidates, which such a ratio would reach too often")
+    g = _as_graph(g)
+    if thr[1] != thr[2]:
+        g.require_src_sorted()
+    nodes = nodes.to(g.device, dtype=torch.int64).contiguous()
+    if nodes.dim() != 1:
+        raise ValueError(f"start nodes of shape {tuple(nodes.shape)}: {what} takes a 1-D tensor of node ids")
+    return g, nodes, thr
+
+
+def node2vec_random_walk(g, nodes, p, q, walk_length, num_walks=1, seed=0, step=0):
+    """node2vec's second-order random walks over a CSCGraph, DGL's dgl.sampling.node2vec_random_walk on a homogeneous graph: -> int64
+    [n, num_walks, walk_length + 1] on the graph's device.  [i, w, 0] is nodes[i], then the nodes walk w visits; from `cur`, having come
+    from `prev`, an in-neighbour x of cur is taken with a weight of 1/p when x == prev, 1 when x is an in-neighbour of prev, 1/q
+    otherwise (rejection sampling; the exact integer rule is in the header of coala_sampler.hip).  A node without an in-edge ends the
+    walk and -1 fills the rest; an out-of-range start node gives a row of -1.  A walk follows in-edges (DGL's walk on a symmetric
+    graph).  walk_length 1..127, num_walks 1..64, p, q > 0 with min(1/p, 1, 1/q) / max(1/p, 1, 1/q) >= 1/16 (the node2vec paper's grid
+    0.25 .. 4 just fits); with q != 1 the rows of the graph must be sorted by source id (sort_csc_by_src; checked once per graph).
+    The walks are a function of (seed, step, start node, w) on a stream of their own: at p = q = 1 they are valid uniform walks, but
+    NOT the traces random_walk gives for the same arguments; and a start node given twice gets the same traces twice."""
+    g, nodes, thr = _walk_args(g, nodes, p, q, walk_length, num_walks, "node2vec_random_walk")
+    out = torch.empty((nodes.numel(), num_walks, walk_length + 1), dtype=torch.int64, device=g.device)
+    mask = (1 << 64) - 1
+    _capi.check(_lib.coala_sampler_node2vec_walk(g._h, nodes.data_ptr(), nodes.numel(), num_walks, walk_length, thr[0], thr[1], thr[2],
+                                                 int(seed) & mask, int(step) & mask, out.data_ptr(), current_stream()))
+    return out
+
+
+class WalkBatch(object):
+    """One skip-gram minibatch of walks.  input_nodes: int64 [n_nodes], the distinct nodes of the batch in order of first appearance
+    (the start nodes first); pos int32 [n * W, L + 1]: every walk as indices into input_nodes, -1 once it has ended; neg int32
+    [n * W * K, L + 1]: K rows per walk, the walk's start node in column 0 and uniformly drawn nodes behind it (PyG's neg_sample);
+    traces: int64 [n, W, L + 1] global ids (node2vec_random_walk's, bit for bit), or None when not asked for.  n_bad: how many start
+    nodes were outside the graph; their rows of pos, neg and traces are -1 and they add no node."""
+
+    def __init__(self, nodes, input_nodes, pos, neg, traces=None, n_bad=0):
+        self.nodes, self.input_nodes, self.pos, self.neg, self.traces, self.n_bad = nodes, input_nodes, pos, neg, traces, n_bad
+
+    def tensors(self):
+        """Every device tensor the batch holds (the loader's lifetime bookkeeping, as Block.tensors())."""
+        return [t for t in (self.nodes, self.input_nodes, self.pos, self.neg, self.traces) if t is not None]
+
+
+def walk_batch_begin(g, nodes, p, q, walk_length, num_walks=1, num_neg=1, seed=0, step=0, traces=False):
+    """Enqueue the walk-batch kernels for the start nodes on the current stream, without waiting: -> the pending call walk_batch_end
+    takes.  ValueError before any launch for arguments node2vec_random_walk refuses, num_neg outside 0..16, or more than ITEM_LIMIT
+    = n * num_walks * (walk_length + 1) * (1 + num_neg) items."""
+    if isinstance(num_neg, bool) or not isinstance(num_neg, int) or not 0 <= num_neg <= MAX_WALK_NEGATIVES:
+        raise ValueError(f"num_neg {num_neg!r}: 0..{MAX_WALK_NEGATIVES} negative rows per walk")
+    g, nodes, thr = _walk_args(g, nodes, p, q, walk_length, num_walks, "walk_batch")
+    n, W, L1, K = nodes.numel(), num_walks, walk_length + 1, num_neg
+    items = n + n * W * L1 + n * W * K * walk_length
+    if max(n * W * L1 * (1 + K), items) > ITEM_LIMIT:
+        raise ValueError(f"{n} start nodes, {W} walks of {walk_length} hops and {K} negatives hold {max(n * W * L1 * (1 + K), items)} items: "
+                         f"over the limit of {ITEM_LIMIT}")
+    input_nodes = torch.empty(max(items, 1), dtype=torch.int64, device=g.device)
+    pos = torch.empty((n * W, L1), dtype=torch.int32, device=g.device)
+    neg = torch.empty((n * W * K, L1), dtype=torch.int32, device=g.device)
+    tr = torch.empty((n, W, L1), dtype=torch.int64, device=g.device) if traces else None
+    out = _capi.WalkBatchOut(input_nodes.data_ptr(), pos.data_ptr(), neg.data_ptr() if neg.numel() else None, tr.data_ptr() if traces and n else None)
+    ticket = C.c_int64(-1)
+    mask = (1 << 64) - 1
+    _capi.check(_lib.coala_sampler_walk_batch(g._h, nodes.data_ptr(), n, W, walk_length, thr[0], thr[1], thr[2], K, int(seed) & mask,
+                                              int(step) & mask, C.byref(out), C.byref(ticket), current_stream()))
+    return (g, nodes, input_nodes, pos, neg, tr, ticket.value)
+
+
+def walk_batch_end(pending):
+    """Wait for the event behind a walk_batch_begin call (only for its kernels) -> WalkBatch.  Start nodes outside [0, num_nodes) are
+    counted in its n_bad, as node2vec_random_walk gives them a row of -1."""
+    g, nodes, input_nodes, pos, neg, tr, ticket = pending
+    n_nodes, n_bad = C.c_int64(0), C.c_int64(0)
+    _capi.check(_lib.coala_sampler_walk_batch_wait(g._h, ticket, C.byref(n_nodes), C.byref(n_bad)))
+    return WalkBatch(nodes, input_nodes[: n_nodes.value], pos, neg, tr, n_bad.value)
+
+
+def walk_batch(g, nodes, p=1.0, q=1.0, walk_length=20, num_walks=1, num_neg=1, seed=0, step=0, traces=False):
+    """walk_batch_end(walk_batch_begin(...)): the skip-gram batch of node2vec walks from `nodes` (PyG's Node2Vec.sample)."""
+    return walk_batch_end(walk_batch_begin(g, nodes, p, q, walk_length, num_walks, num_neg, seed, step, traces))
 
 
 def pair_code_bits(num_nodes, n_slots):

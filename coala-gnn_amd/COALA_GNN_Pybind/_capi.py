@@ -55,6 +55,10 @@ class EdgeBatchOut(C.Structure):
     _fields_ = [("seed_nodes", C.c_void_p), ("pos_src", C.c_void_p), ("pos_dst", C.c_void_p), ("neg_dst", C.c_void_p)]
 
 
+class WalkBatchOut(C.Structure):
+    _fields_ = [("input_nodes", C.c_void_p), ("pos", C.c_void_p), ("neg", C.c_void_p), ("traces", C.c_void_p)]
+
+
 class CommProfile(C.Structure):
     _fields_ = [("rows_ms", C.c_double), ("calls", C.c_uint64), ("remote_rows_in", C.c_uint64)]
 
@@ -181,6 +185,11 @@ SYMBOLS = {
     "coala_block_pair_dot_backward": (_I, [_I] + [_VP] * 5 + [_I64, _I, _I, _VP]),
     "coala_sampler_edge_batch": (_I, [_VP, _VP, _I64, _I, _U64, _U64, C.POINTER(EdgeBatchOut), C.POINTER(_I64), _VP]),
     "coala_sampler_edge_batch_wait": (_I, [_VP, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
+    "coala_sampler_node2vec_walk": (_I, [_VP, _VP, _I64, _I, _I, _U64, _U64, _U64, _U64, _U64, _VP, _VP]),
+    "coala_sampler_walk_batch": (_I, [_VP, _VP, _I64, _I, _I, _U64, _U64, _U64, _I, _U64, _U64, C.POINTER(WalkBatchOut), C.POINTER(_I64), _VP]),
+    "coala_sampler_walk_batch_wait": (_I, [_VP, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
+    "coala_block_skipgram_loss": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _I, C.c_float, _VP]),
+    "coala_block_skipgram_loss_backward": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _I, C.c_float, _VP]),
     "coala_shm_open":(_I, [C.c_char_p, _U64, _I, _I, C.POINTER(_VP)]),
     "coala_shm_host_ptr": (_VP, [_VP]),
     "coala_shm_device_ptr": (_VP, [_VP]),

@@ -1748,6 +1748,190 @@ int pair_dot_launch(int device, const float* h, const int32_t* src, const int32_
     return COALA_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------- skip-gram window loss
+// Walk tables rows int32 [R, len] (-1 = no node) over h fp32 [N, dim]: the pairs of a row are (a, a + j) for every window start a in
+// 0 .. len - C and j in 1 .. C - 1, valid when both indices are >= 0; a pair's score is s = <h[rows[r, a]], h[rows[r, a + j]]> and its
+// loss softplus(sign * s) (PyG's Node2Vec.loss: sign -1 on the positive walks, +1 on the negatives).  GS lanes -- a wave, or a group of
+// 16 / 32 lanes for a small dim, as pair_dot -- take one row: together they copy its len embedding rows into LDS once (a row of no
+// node as zeros), a lane per column.  A block holds as many groups as fit 64 KB of LDS (len * dim <= 16384 floats: at least one; a
+// shape near that budget runs one wave per block).
+// Forward: a lane owns whole PAIRS, gl, gl + GS, ... in pair order: it forms its pair's dot product alone, one fma per column,
+// starting at column (its lane index) and wrapping round, so that the lanes of a wave read different LDS banks although they read
+// different rows, computes the softplus once, and sums its losses in a double; the group's sums are added by a butterfly: partial[r]
+// and count[r] are deterministic.
+// Backward: position t of a row is the start of the pairs (t, t + j) and the partner of the pairs (i, t), t - C < i < t, i <= len - C:
+// at most 254 partners.  Pass 1 recomputes the score of every partner m from LDS with all lanes of the group on one dot and a
+// butterfly sum (a position has a couple of dozen partners in practice: a lane per partner would leave most of a wave idle), and lane
+// m % GS keeps d loss / d s = sign * sigmoid(sign * s) in its register m / GS.  Pass 2 forms the position's whole gradient row,
+// sum_m coef_m h[partner_m], a lane per column with the coefficients going round by shuffle, in a double, multiplies it by the double
+// `scale` and adds it with ONE atomic per (position, element) -- not one per pair -- to the DOUBLE buffer grad_acc (zeroed by the
+// caller, who rounds it to fp32 once).  A node of a batch collects hundreds of such additions: in fp32 their rounding, not the
+// kernel's arithmetic, would set the gradient's error, and the order of the atomics would show in it; in a double neither does.  The
+// partner loops depend on (t, len, C) alone and a group's lanes agree on which positions hold a node, so every shuffle reads a lane
+// that runs the same code.
+constexpr int kSkipMaxLen = 128, kSkipMaxFloats = 16384;
+
+__device__ __forceinline__ float softplusf(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float sigmoidf(float x) {
+    const float e = expf(-fabsf(x));
+    return (x >= 0.0f ? 1.0f : e) / (1.0f + e);
+}
+
+struct SkipRow { // a group's row: its index (-1: the group is past the table) and which of its positions hold a node
+    int64_t r;
+    uint64_t m0, m1;
+    __device__ __forceinline__ bool has(int t) const { return ((t < 64 ? m0 >> t : m1 >> (t - 64)) & 1ull) != 0; }
+};
+
+// Stage row r0 + (the lane's group) into the group's LDS slice; -> the row and its validity mask.  Ends with the wave's LDS fence.
+template <int GS>
+__device__ __forceinline__ SkipRow skip_stage(const float* __restrict__ h, const int32_t* __restrict__ rows, int64_t r0, int64_t n_rows, int len,
+                                              int dim, float* __restrict__ sh, int gl) {
+    const int64_t r = r0 + (int)threadIdx.x / GS;
+    SkipRow row{r < n_rows ? r : -1, 0, 0};
+    if (row.r >= 0) {
+        for (int t = 0; t < len; ++t) {
+            const int32_t s = rows[row.r * len + t];
+            if (s >= 0) {
+                if (t < 64) row.m0 |= 1ull << t;
+                else row.m1 |= 1ull << (t - 64);
+            }
+            for (int c = gl; c < dim; c += GS) sh[t * dim + c] = s >= 0 ? h[(int64_t)s * dim + c] : 0.0f;
+        }
+    }
+    wave_lds_sync();
+    return row;
+}
+
+// <sh[a], sh[k]> by one lane: dim fmas from +0, the columns taken from `rot` on and wrapping round.
+__device__ __forceinline__ float skip_dot(const float* __restrict__ sh, int a, int k, int dim, int rot) {
+    const float* const x = sh + a * dim;
+    const float* const y = sh + k * dim;
+    float acc = 0.0f;
+    int c = rot % dim;
+    for (int i = 0; i < dim; ++i) {
+        acc = __builtin_fmaf(x[c], y[c], acc);
+        c = c + 1 == dim ? 0 : c + 1;
+    }
+    return acc;
+}
+
+// The same dot by the GS lanes of a group together: lane gl the columns gl, gl + GS, ..., then a butterfly sum, so every lane of the
+// group ends with the same bits.  Every lane of the group must call it (valid is group-uniform).
+template <int GS>
+__device__ __forceinline__ float skip_dot_group(const float* __restrict__ sh, int a, int k, int dim, int gl, bool valid) {
+    float acc = 0.0f;
+    if (valid)
+        for (int c = gl; c < dim; c += GS) acc = __builtin_fmaf(sh[a * dim + c], sh[k * dim + c], acc);
+    for (int o = GS / 2; o; o >>= 1) acc += __shfl_xor(acc, o);
+    return acc;
+}
+
+template <int GS>
+__global__ __launch_bounds__(kBlock) void skipgram_loss_kernel(const float* __restrict__ h, const int32_t* __restrict__ rows, float* __restrict__ partial,
+                                     int32_t* __restrict__ count, int64_t n_rows, int len, int C, int dim, float sign) {
+    extern __shared__ float s_skip[];
+    const int G = (int)blockDim.x / GS, gl = (int)threadIdx.x % GS;
+    float* const sh = s_skip + (size_t)((int)threadIdx.x / GS) * len * dim;
+    const int n_pairs = (len - C + 1) * (C - 1);
+    for (int64_t r0 = (int64_t)blockIdx.x * G; r0 < n_rows; r0 += (int64_t)gridDim.x * G) { // block-uniform trip count
+        const SkipRow row = skip_stage<GS>(h, rows, r0, n_rows, len, dim, sh, gl);
+        double sum = 0.0; // a lane adds up to 16129 / GS terms, the group 16129: a double keeps the row's sum at one fp32 rounding
+        int32_t cnt = 0;
+        if (row.r >= 0) {
+            for (int q = gl; q < n_pairs; q += GS) {
+                const int a = q / (C - 1), k = a + 1 + q % (C - 1);
+                if (row.has(a) && row.has(k)) {
+                    sum += (double)softplusf(sign * skip_dot(sh, a, k, dim, gl));
+                    ++cnt;
+                }
+            }
+        }
+        for (int o = GS / 2; o; o >>= 1) { // every lane of the wave: a group past the table adds zeros
+            sum += __shfl_xor(sum, o);
+            cnt += __shfl_xor(cnt, o);
+        }
+        if (row.r >= 0 && gl == 0) {
+            partial[row.r] = (float)sum;
+            count[row.r] = cnt;
+        }
+        wave_lds_sync(); // every lane has read the slice before the next row overwrites it
+    }
+}
+
+template <int GS>
+__global__ __launch_bounds__(kBlock) void skipgram_loss_backward_kernel(const float* __restrict__ h, const int32_t* __restrict__ rows, double* __restrict__ grad_acc,
+                                              const double* __restrict__ scale_dev, int64_t n_rows, int len, int C, int dim, float sign) {
+    constexpr int NCH = 256 / GS; // a position has at most 2 (C - 1) <= 254 partners: partner m's coefficient is coef[m / GS] of lane m % GS
+    extern __shared__ float s_skip[];
+    const int G = (int)blockDim.x / GS, gl = (int)threadIdx.x % GS, gbase = (int)(threadIdx.x & 63) - gl;
+    float* const sh = s_skip + (size_t)((int)threadIdx.x / GS) * len * dim;
+    const double scale = *scale_dev;
+    for (int64_t r0 = (int64_t)blockIdx.x * G; r0 < n_rows; r0 += (int64_t)gridDim.x * G) { // block-uniform trip count
+        const SkipRow row = skip_stage<GS>(h, rows, r0, n_rows, len, dim, sh, gl);
+        for (int t = 0; t < len; ++t) {
+            if (row.r < 0 || !row.has(t)) continue; // group-uniform: the shuffles below stay inside the group
+            const int nf = t + C <= len ? C - 1 : 0;                 // pairs (t, t + 1 + m)
+            const int lo = t - C + 1 > 0 ? t - C + 1 : 0;            // pairs (i, t), lo <= i <= hi
+            const int hi = t - 1 < len - C ? t - 1 : len - C;
+            const int n_part = nf + (hi >= lo ? hi - lo + 1 : 0);
+            auto partner = [&](int m) { return m < nf ? t + 1 + m : lo + (m - nf); };
+            float coef[NCH];
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) coef[ch] = 0.0f;
+            for (int m = 0; m < n_part; ++m) { // group-uniform
+                const int k = partner(m);
+                const bool valid = row.has(k);
+                const float s = skip_dot_group<GS>(sh, t, k, dim, gl, valid);
+                const float cf = valid ? sign * sigmoidf(sign * s) : 0.0f;
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch)
+                    if (m / GS == ch && m % GS == gl) coef[ch] = cf;
+            }
+            const int64_t node = rows[row.r * len + t];
+            for (int c0 = 0; c0 < dim; c0 += GS) { // group-uniform trip count: the shuffles below need every lane of the group
+                const int c = c0 + gl;
+                double g = 0.0;
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) {
+                    if (ch * GS < n_part) {
+                        const int n = n_part - ch * GS < GS ? n_part - ch * GS : GS;
+                        for (int j = 0; j < n; ++j) {
+                            const float cf = __shfl(coef[ch], gbase + j);
+                            if (c < dim) g = __builtin_fma((double)cf, (double)sh[partner(ch * GS + j) * dim + c], g);
+                        }
+                    }
+                }
+                if (c < dim) unsafeAtomicAdd(grad_acc + node * dim + c, g * scale);
+            }
+        }
+        wave_lds_sync(); // every lane has read the slice before the next row overwrites it
+    }
+}
+
+int skipgram_launch(int device, const float* h, const int32_t* rows, float* partial, int32_t* count, double* grad_h, const double* scale,
+                    int64_t n_rows, int len, int C, int dim, float sign, void* stream) {
+    if (n_rows < 0 || len < 2 || len > kSkipMaxLen || C < 2 || C > len || dim < 1 || (int64_t)len * dim > kSkipMaxFloats)
+        return fail(COALA_EINVAL, "bad walk table shape (len 2..%d, context 2..len, dim >= 1, len * dim <= %d)", kSkipMaxLen, kSkipMaxFloats);
+    if (sign != 1.0f && sign != -1.0f) return fail(COALA_EINVAL, "sign must be +1 or -1");
+    if (n_rows == 0) return COALA_OK;
+    if (!h || !rows || (grad_h ? !scale : (!partial || !count))) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    dispatch_pair_group(dim, [&](auto gs_c) {
+        constexpr int GS = decltype(gs_c)::value;
+        const int fit = kSkipMaxFloats / (len * dim);                          // groups whose slices fit 64 KB
+        const int G = fit < kBlock / GS ? fit : kBlock / GS;                    // >= 1 by the shape check
+        const size_t lds = (size_t)G * len * dim * sizeof(float);
+        const dim3 grid(grid1d(n_rows, G, 8192)), blk(G * GS);
+        if (grad_h)
+            hipLaunchKernelGGL(skipgram_loss_backward_kernel<GS>, grid, blk, lds, (hipStream_t)stream, h, rows, grad_h, scale, n_rows, len, C, dim, sign);
+        else
+            hipLaunchKernelGGL(skipgram_loss_kernel<GS>, grid, blk, lds, (hipStream_t)stream, h, rows, partial, count, n_rows, len, C, dim, sign);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
 } // namespace
 
 // The C ABI (include/coala_hip.h): every entry forwards to its launch, the fixed form with <false>, a null indptr and its fan-out, the
@@ -1952,6 +2136,17 @@ int coala_block_pair_dot_backward(int device, const float* h, const int32_t* src
                                   int64_t n_pairs, int heads, int dim, void* stream) {
     if (n_pairs > 0 && !grad_out) return fail(COALA_EINVAL, "null buffer");
     return pair_dot_launch(device, h, src, dst, grad_out, grad_h, n_pairs, heads, dim, stream);
+}
+
+int coala_block_skipgram_loss(int device, const float* h, const int32_t* rows, float* partial, int32_t* count, int64_t n_rows, int len,
+                              int context, int dim, float sign, void* stream) {
+    return skipgram_launch(device, h, rows, partial, count, nullptr, nullptr, n_rows, len, context, dim, sign, stream);
+}
+
+int coala_block_skipgram_loss_backward(int device, const float* h, const int32_t* rows, double* grad_acc, const double* scale, int64_t n_rows,
+                                       int len, int context, int dim, float sign, void* stream) {
+    if (n_rows > 0 && !grad_acc) return fail(COALA_EINVAL, "null buffer");
+    return skipgram_launch(device, h, rows, nullptr, nullptr, grad_acc, scale, n_rows, len, context, dim, sign, stream);
 }
 
 } // extern "C"

@@ -121,6 +121,31 @@
 //   a walk never scans a row, so there is no hub list and no ragged form.  scan_assign / relabel_clear / bucketing run unchanged:
 //   three launches per layer, no memset, no host wait.  coala_sampler_random_walk stores the traces of the same walks (walk_trace).
 //
+// Second-order walks (node2vec, Grover & Leskovec, KDD 2016; DGL's dgl.sampling.node2vec_random_walk on a homogeneous graph;
+// coala_sampler_node2vec_walk), walk_length L in 1..127, W = num_walks in 1..64, by rejection sampling in exact integer arithmetic:
+//   * thresholds: with m = max(1/p, 1, 1/q) the host passes thr_return = int((1/p) / m * 2^32), thr_near = int(1 / m * 2^32) and
+//     thr_far = int((1/q) / m * 2^32): three integers in [0, 2^32], the largest exactly 2^32;
+//   * keys: wkey = sample_key(seed, step, 0, v) ^ kN2vStream (0x1F83D9ABFB41BD6B: a stream of its own, not random_walk's), and walk w
+//     of start node v uses kw = splitmix64(wkey + w): a function of (seed, step, v, w) alone, not of the batch or the grid;
+//   * hop h (0-based) at node cur, having come from prev: deg(cur) == 0 ends the walk.  Attempts a = 0, 1, .. use c = 2 (256 h + a):
+//     the candidate is x = indices[indptr[cur] + mulhi64(splitmix64(kw + c), deg)].  At h = 0 attempt 0 is taken.  At h >= 1 the
+//     candidate's class picks the threshold t: return if x == prev, near if x occurs in row prev (indices[indptr[prev] ..
+//     indptr[prev + 1])), far otherwise; it is taken when (splitmix64(kw + c + 1) >> 32) < t.  The first taken attempt wins; if the
+//     attempts 0..255 all fail, attempt 255's candidate is taken: no walk loops without a bound.  A taken x outside [0, N) ends the
+//     walk; an ended walk is padded with -1, and an out-of-range start node gives a row of -1;
+//   * the near test is a binary search: ROWS MUST BE SORTED ASCENDING BY SOURCE ID when thr_near != thr_far (the caller's duty:
+//     COALA_GNN.sampler.sort_csc_by_src, checked once per graph by the Python wrapper); with thr_near == thr_far row prev is never read.
+//   Launch: node2vec_trace, a group of 16 lanes per walk: the group evaluates sixteen attempts of a hop at once and the first accepting
+//   lane of its ballot wins -- the same sequential rule, with the dependent loads indptr -> indices -> search of sixteen attempts in
+//   flight.  At p = q = 1 attempt 0 always wins and nothing is searched.
+// Skip-gram batches (PyG's Node2Vec.pos_sample / neg_sample; coala_sampler_walk_batch): the walks above from n start nodes, and for
+//   every walk K = num_neg (0..16) negative rows: column 0 is the walk's start node, column t >= 1 the node
+//   mulhi64(splitmix64((kw ^ 0x6A09E667F3BCC909) + 128 j + t), N) of negative j.  input_nodes = the distinct ids of the item list
+//   [start nodes | traces row-major | the negatives' columns 1.. row-major] in order of first appearance, an item of an invalid start
+//   node or behind a walk's end being no node; pos int32 [n W, L + 1] and neg int32 [n W K, L + 1] hold every entry's index in it,
+//   -1 for no node.  Three launches as an edge batch: walk_items (walks, negatives, hash insert), the layers' scan_assign, and
+//   walk_relabel_clear; no memset, copy or host wait.  Limit: n W (L + 1) (1 + K) <= 8,388,608.
+//
 // Temporal layers (PyG's NeighborLoader(time_attr=, temporal_strategy='uniform' | 'last'), GraphBolt's temporal_sample_neighbors, TGN's
 // "most recent neighbours"; coala_sampler_sample_layers_temporal), fan-out f in 1..32.  The graph carries an int64 timestamp per edge in CSC
 // order, NON-DECREASING INSIDE EVERY ROW (the caller's duty; not verified here).  A destination item of a layer is a pair (v, t): node v
@@ -749,6 +774,190 @@ __global__ __launch_bounds__(kBlock) void walk_trace_kernel(Graph g, const int64
             for (int h = 0; h <= wp.T; ++h) row[h] = kEmpty;
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------- second-order walks
+// node2vec's biased walk (the rule is in the header of this file).  kN2vGroup lanes run one walk.  A hop is a chain of dependent
+// loads -- indptr, the candidate, then a binary search in the row of `prev` -- so the group tries kN2vGroup attempts at once, lane gl
+// the attempt 16 r + gl of round r, and the first accepting lane of the group's ballot wins: the sequential rule, with the loads of
+// sixteen attempts in flight.  At h = 0, and whenever every threshold is 2^32 (p = q = 1), attempt 0 wins: every lane computes it and
+// nothing is searched or shuffled.  The row of `prev` is kept as (start, degree) from the hop before, and it is searched only when the
+// near and far thresholds differ.  Every loop is bounded: L hops of at most 16 rounds of at most 64 search steps.  The groups of a
+// wave diverge (their walks end, and accept, at different times); a ballot is read through the group's own bits and a shuffle reads
+// a lane of the own group, all of whose lanes run together.
+constexpr uint64_t kN2vStream = 0x1F83D9ABFB41BD6Bull;    // xor on sample_key: the second-order walks' own stream
+constexpr uint64_t kN2vNegStream = 0x6A09E667F3BCC909ull; // xor on a walk's key: its negatives
+constexpr int kN2vMaxLength = 127, kN2vAttempts = 256, kN2vMaxNeg = 16, kN2vGroup = 16;
+constexpr uint64_t kN2vOne = 1ull << 32; // a threshold that accepts every draw
+static_assert(kN2vAttempts % kN2vGroup == 0 && 64 % kN2vGroup == 0 && kBlock % kN2vGroup == 0, "a walk's lanes lie in one wave");
+
+struct N2vParams {
+    int L, W;                         // hops per walk, walks per start node
+    uint64_t thr_ret, thr_near, thr_far; // in [0, 2^32]: a candidate is taken when (draw >> 32) < its class's threshold
+};
+
+__device__ __forceinline__ uint64_t n2v_walk_key(uint64_t seed, uint64_t step, int64_t v, int w) {
+    return splitmix64((sample_key(seed, step, 0, (uint64_t)v) ^ kN2vStream) + (uint64_t)w);
+}
+
+// Does x occur in indices[start .. start + deg), a row sorted ascending?
+__device__ __forceinline__ bool row_has(const int64_t* __restrict__ indices, int64_t start, int64_t deg, int64_t x) {
+    int64_t lo = 0, hi = deg; // the first entry >= x lies in [lo, hi]
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (indices[start + mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < deg && indices[start + lo] == x;
+}
+
+// The walk with key kw from v (a node of the graph), run by the kN2vGroup lanes of a group together: every lane follows the walk, and
+// lane 0 calls visit(h, u) for every hop h < L, u the node reached or -1 once the walk has ended.
+template <typename F>
+__device__ __forceinline__ void node2vec_walk(const Graph& g, uint64_t kw, int64_t v, const N2vParams& np, F&& visit) {
+    const int gl = (int)threadIdx.x % kN2vGroup, gbase = (int)(threadIdx.x & 63) - gl;
+    const bool search = np.thr_near != np.thr_far;
+    const bool open = np.thr_ret == kN2vOne && np.thr_near == kN2vOne && np.thr_far == kN2vOne; // attempt 0 is always taken
+    int64_t cur = v, prev = -1, prev_start = 0, prev_deg = 0;
+    bool ended = false;
+    for (int h = 0; h < np.L; ++h) {
+        if (!ended) { // group-uniform: every lane of the group holds the same walk
+            const int64_t start = g.indptr[cur];
+            const int64_t deg = g.indptr[cur + 1] - start;
+            if (deg <= 0) {
+                ended = true;
+            } else {
+                int64_t x = kEmpty;
+                if (h == 0 || open) {
+                    x = g.indices[start + (int64_t)__umul64hi(splitmix64(kw + 2ull * (uint64_t)(kN2vAttempts * h)), (uint64_t)deg)];
+                } else {
+                    bool found = false;
+                    for (int r = 0; r < kN2vAttempts / kN2vGroup && !found; ++r) {
+                        const uint64_t c = 2ull * (uint64_t)(kN2vAttempts * h + r * kN2vGroup + gl);
+                        const int64_t cand = g.indices[start + (int64_t)__umul64hi(splitmix64(kw + c), (uint64_t)deg)];
+                        uint64_t t = np.thr_near;
+                        if (cand == prev) t = np.thr_ret;
+                        else if (search) t = row_has(g.indices, prev_start, prev_deg, cand) ? np.thr_near : np.thr_far;
+                        const bool take = (splitmix64(kw + c + 1) >> 32) < t;
+                        const uint32_t mine = (uint32_t)(__ballot(take) >> gbase) & ((1u << kN2vGroup) - 1u);
+                        found = mine != 0;
+                        // the first taking attempt; none: the round's last attempt, which in the last round is attempt 255
+                        x = __shfl(cand, gbase + (found ? __builtin_ctz(mine) : kN2vGroup - 1));
+                    }
+                }
+                if (x < 0 || x >= g.num_nodes) {
+                    ended = true;
+                } else {
+                    prev = cur; prev_start = start; prev_deg = deg;
+                    cur = x;
+                }
+            }
+        }
+        if (gl == 0) visit(h, ended ? kEmpty : cur);
+    }
+}
+
+// coala_sampler_node2vec_walk: a lane group per (start node, walk); traces[i, w, 0] is the start node, then the hops, -1 once ended.
+__global__ __launch_bounds__(kBlock) void node2vec_trace_kernel(Graph g, const int64_t* __restrict__ nodes, int64_t n, N2vParams np, uint64_t seed,
+                                                                uint64_t step, int64_t* __restrict__ traces) {
+    const int64_t total = n * np.W;
+    const int gl = (int)threadIdx.x % kN2vGroup;
+    for (int64_t t = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kN2vGroup; t < total; t += (int64_t)gridDim.x * blockDim.x / kN2vGroup) {
+        const int64_t v = nodes[t / np.W];
+        int64_t* const row = traces + t * (np.L + 1);
+        if (v >= 0 && v < g.num_nodes) {
+            if (gl == 0) row[0] = v;
+            node2vec_walk(g, n2v_walk_key(seed, step, v, (int)(t % np.W)), v, np, [&](int h, int64_t u) { row[1 + h] = u; });
+        } else {
+            for (int h = gl; h <= np.L; h += kN2vGroup) row[h] = kEmpty;
+        }
+    }
+}
+
+// Skip-gram batches (coala_sampler_walk_batch).  The item list is [start nodes (n) | traces row-major (n W (L + 1)) | the negatives'
+// columns 1..L row-major (n W K L)]; an item of an invalid start node is -1.  One launch makes the items and inserts them: a lane
+// group per walk first, then a thread per negative entry.  traces (nullable) receives the global-id traces of node2vec_trace_kernel.
+__host__ __device__ inline int64_t walk_batch_items(int64_t n, int W, int L, int K) { return n + n * W * (L + 1) + n * W * K * L; }
+
+__global__ __launch_bounds__(kBlock) void walk_items_kernel(Graph g, const int64_t* __restrict__ nodes, int64_t n, N2vParams np, int K, uint64_t seed,
+                                                            uint64_t step, int64_t* __restrict__ items, int64_t* __restrict__ traces, Table tb,
+                                                            uint32_t* __restrict__ slot_of_item, unsigned long long* __restrict__ n_bad) {
+    const int L = np.L, W = np.W;
+    const int64_t n_walks = n * W, n_neg = n_walks * K * L;
+    const int64_t pos0 = n, neg0 = n + n_walks * (L + 1);
+    const uint32_t mask = table_size(walk_batch_items(n, W, L, K)) - 1;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, n_thr = (int64_t)gridDim.x * blockDim.x;
+    const int gl = (int)threadIdx.x % kN2vGroup;
+    auto emit = [&](int64_t p, int64_t key) {
+        items[p] = key;
+        hash_insert(tb, mask, key, p, slot_of_item);
+    };
+    for (int64_t t = tid / kN2vGroup; t < n_walks; t += n_thr / kN2vGroup) {
+        const int64_t i = t / W;
+        const int w = (int)(t % W);
+        const int64_t v = nodes[i];
+        const bool ok = v >= 0 && v < g.num_nodes;
+        const int64_t base = pos0 + t * (L + 1);
+        int64_t* const row = traces ? traces + t * (L + 1) : nullptr;
+        if (gl == 0) {
+            if (w == 0) {
+                emit(i, ok ? v : kEmpty);
+                if (!ok) atomicAdd(n_bad, 1ull);
+            }
+            emit(base, ok ? v : kEmpty);
+            if (row) row[0] = ok ? v : kEmpty;
+        }
+        if (ok) {
+            node2vec_walk(g, n2v_walk_key(seed, step, v, w), v, np, [&](int h, int64_t u) {
+                emit(base + 1 + h, u);
+                if (row) row[1 + h] = u;
+            });
+        } else {
+            for (int h = gl; h < L; h += kN2vGroup) {
+                emit(base + 1 + h, kEmpty);
+                if (row) row[1 + h] = kEmpty;
+            }
+        }
+    }
+    for (int64_t q = tid; q < n_neg; q += n_thr) { // entry (walk t, negative j, column c + 1)
+        const int c = (int)(q % L);
+        const int j = (int)((q / L) % K);
+        const int64_t t = q / ((int64_t)L * K);
+        const int64_t v = nodes[t / W];
+        int64_t key = kEmpty;
+        if (v >= 0 && v < g.num_nodes)
+            key = (int64_t)__umul64hi(splitmix64((n2v_walk_key(seed, step, v, (int)(t % W)) ^ kN2vNegStream) + (uint64_t)(128 * j + c + 1)),
+                                      (uint64_t)g.num_nodes);
+        emit(neg0 + q, key);
+    }
+}
+
+// item -> index in input_nodes (-1: no node); column 0 of a negative row is its walk's start node, the item of that node.  The table
+// is cleared for the next call alongside, and the bad-start count goes to the host and back to 0.
+__global__ __launch_bounds__(kBlock) void walk_relabel_clear_kernel(int64_t n, int W, int L, int K, const uint32_t* __restrict__ slot_of_item, Table tb,
+                                                                    int32_t* __restrict__ pos, int32_t* __restrict__ neg,
+                                                                    unsigned long long* __restrict__ n_bad, int64_t* __restrict__ n_bad_host,
+                                                                    int64_t next_items) {
+    const int64_t n_pos = n * W * (L + 1), n_neg_out = n * W * K * (L + 1);
+    auto local = [&](int64_t p) {
+        const uint32_t s = slot_of_item[p];
+        return (s == 0xFFFFFFFFu) ? -1 : (int32_t)tb.local_of_slot[s];
+    };
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n_pos + n_neg_out; q += (int64_t)gridDim.x * blockDim.x) {
+        if (q < n_pos) {
+            pos[q] = local(n + q);
+        } else {
+            const int64_t r = q - n_pos;
+            const int c = (int)(r % (L + 1));
+            const int64_t row = r / (L + 1); // (walk t, negative j) = (row / K, row % K)
+            neg[r] = c == 0 ? local(row / K / W) : local(n + n_pos + row * L + (c - 1));
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *n_bad_host = (int64_t)*n_bad;
+        *n_bad = 0;
+    }
+    clear_table(tb, table_size(next_items));
 }
 
 // ---------------------------------------------------------------------------------------------------------- single-pass tile scan
@@ -1494,6 +1703,7 @@ struct coala_sampler {
         int n_layers = 0, n_parts = 0;
         bool all_ragged = false; // a LABOR or a relation call: every layer is ragged, whatever its fan-out
         bool edge_batch = false; // coala_sampler_edge_batch: the slot holds n_nodes and n_bad, collected by coala_sampler_edge_batch_wait
+        bool walk_batch = false; // coala_sampler_walk_batch: the same two words, collected by coala_sampler_walk_batch_wait
         int64_t n_seeds = 0;
         bool ragged(int l) const { return all_ragged || fanouts[l] == -1; } // CSR block, sizes known on the device only
         int32_t fanouts[COALA_SAMPLER_MAX_LAYERS] = {}; // of a relation call: -1 for a layer whose fan-outs are all -1, else 0
@@ -1647,6 +1857,7 @@ int wait_impl(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* 
     const int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
     const RingInfo& r = s->ring[slot];
     if (r.edge_batch) return fail(COALA_EINVAL, "ticket %lld is an edge batch: collect it with coala_sampler_edge_batch_wait", (long long)ticket);
+    if (r.walk_batch) return fail(COALA_EINVAL, "ticket %lld is a walk batch: collect it with coala_sampler_walk_batch_wait", (long long)ticket);
     if (n_src_host)
         for (int l = 0; l < r.n_layers; ++l) n_src_host[l] = pin[l];
     if (n_edges_host)
@@ -2235,6 +2446,90 @@ int coala_sampler_random_walk(coala_sampler_t* s, const int64_t* nodes, int64_t 
     hipLaunchKernelGGL(walk_trace_kernel, dim3(grid1d(n * num_walks, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, s->g, nodes, n,
                        WalkParams{length, num_walks, term_threshold}, seed, step, layer, traces_out);
     HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+// The three thresholds of a second-order walk: each in [0, 2^32], the largest exactly 2^32 (the host normalises by max(1/p, 1, 1/q)).
+static int check_n2v(int num_walks, int length, uint64_t thr_ret, uint64_t thr_near, uint64_t thr_far) {
+    if (num_walks < 1 || num_walks > kMaxWalks) return fail(COALA_EINVAL, "num_walks %d outside 1..%d", num_walks, kMaxWalks);
+    if (length < 1 || length > kN2vMaxLength) return fail(COALA_EINVAL, "walk_length %d outside 1..%d", length, kN2vMaxLength);
+    if (std::max(thr_ret, std::max(thr_near, thr_far)) != kN2vOne)
+        return fail(COALA_EINVAL, "thresholds %llu, %llu, %llu: each in [0, 2^32] and the largest 2^32", (unsigned long long)thr_ret,
+                    (unsigned long long)thr_near, (unsigned long long)thr_far);
+    return COALA_OK;
+}
+
+int coala_sampler_node2vec_walk(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t thr_return,
+                                uint64_t thr_near, uint64_t thr_far, uint64_t seed, uint64_t step, int64_t* traces_out, void* stream) {
+    if (!s || (n > 0 && (!nodes || !traces_out))) return fail(COALA_EINVAL, "null argument");
+    if (n < 0 || n > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad node count");
+    if (int rc = check_n2v(num_walks, length, thr_return, thr_near, thr_far)) return rc;
+    if (n == 0) return COALA_OK;
+    HIPCHK(hipSetDevice(s->device));
+    hipLaunchKernelGGL(node2vec_trace_kernel, dim3(grid1d(n * num_walks * kN2vGroup, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, s->g, nodes, n,
+                       N2vParams{length, num_walks, thr_return, thr_near, thr_far}, seed, step, traces_out);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+// A walk batch takes a ring slot and the handle's scratch as an edge batch does: three launches, the counts into the slot's pinned words.
+int coala_sampler_walk_batch(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t thr_return,
+                             uint64_t thr_near, uint64_t thr_far, int num_neg, uint64_t seed, uint64_t step, const coala_walk_batch_t* out,
+                             int64_t* ticket_out, void* stream) {
+    if (!s || !out || (!nodes && n > 0)) return fail(COALA_EINVAL, "null argument");
+    if (int rc = check_n2v(num_walks, length, thr_return, thr_near, thr_far)) return rc;
+    if (num_neg < 0 || num_neg > kN2vMaxNeg) return fail(COALA_EINVAL, "num_neg %d outside 0..%d", num_neg, kN2vMaxNeg);
+    if (n < 0 || n > kItemLimit) return fail(COALA_EINVAL, "bad node count");
+    const int64_t stated = n * num_walks * (length + 1) * (1 + num_neg); // the documented bound; the item list itself holds n more at num_neg 0
+    const int64_t items = walk_batch_items(n, num_walks, length, num_neg);
+    if (stated > kItemLimit || items > kItemLimit)
+        return fail(COALA_EINVAL, "a walk batch of %lld start nodes, %d walks of %d hops and %d negatives holds %lld items (limit %lld)",
+                    (long long)n, num_walks, length, num_neg, (long long)std::max(stated, items), (long long)kItemLimit);
+    if (n > 0 && (!out->input_nodes || !out->pos || (num_neg > 0 && !out->neg))) return fail(COALA_EINVAL, "null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    int rc, slot;
+    uint64_t ticket;
+    if ((rc = begin_call(s, st, &ticket, &slot))) return rc;
+    if ((rc = grow_workspace(s, st, 0, (uint64_t)items, (uint64_t)items, (uint64_t)items))) return rc;
+    int64_t* pin_dev = s->counts_pinned_dev + (size_t)slot * kSlot;
+    RingInfo& r = s->ring[slot] = RingInfo{};
+    r.n_layers = 1;
+    r.n_seeds = items;
+    r.walk_batch = true;
+    if (n == 0) {
+        int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
+        pin[0] = pin[kPinEdges] = 0;
+    } else {
+        if ((rc = prepare_table(s, (uint64_t)items, st))) return rc;
+        const dim3 blk(kBlock);
+        const N2vParams np{length, num_walks, thr_return, thr_near, thr_far};
+        const int64_t n_walks = n * num_walks;
+        hipLaunchKernelGGL(walk_items_kernel, dim3(grid1d(std::max<int64_t>(n_walks * kN2vGroup, n_walks * num_neg * length / 4), kBlock, 8192)), blk, 0, st, s->g,
+                           nodes, n, np, num_neg, seed, step, s->nbr_global, out->traces, s->tb, s->slot_of_item, s->edge_bad);
+        if ((rc = next_gen(s, st))) return rc;
+        const int tiles = grid1d(items, kTile, kMaxTiles);
+        // the item list as the "destination nodes" of a layer of fan-out 0, as in an edge batch
+        hipLaunchKernelGGL(scan_assign_kernel<false>, dim3(tiles), blk, 0, st, (const int64_t*)s->nbr_global, (const int64_t*)s->nbr_global,
+                           (const int64_t*)nullptr, items, 0, (const uint32_t*)s->slot_of_item, s->tb, s->status, s->ticket, s->ticket_total,
+                           s->scan_gen & 0x3FFFFFFFull, out->input_nodes, s->counts_dev + 1, pin_dev);
+        s->ticket_total += (unsigned long long)tiles;
+        hipLaunchKernelGGL(walk_relabel_clear_kernel, dim3(grid1d(std::max<int64_t>(items, table_size(items)), kBlock, 4096)), blk, 0, st, n, num_walks,
+                           length, num_neg, (const uint32_t*)s->slot_of_item, s->tb, out->pos, out->neg, s->edge_bad, pin_dev + kPinEdges, items);
+        s->clean_items = (uint64_t)items;
+        HIPCHK(hipGetLastError());
+    }
+    return end_call(s, slot, st, ticket_out);
+}
+
+int coala_sampler_walk_batch_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_nodes_host, int64_t* n_bad_host) {
+    int slot;
+    if (int rc = ring_slot(s, ticket, &slot)) return rc;
+    if (!s->ring[slot].walk_batch) return fail(COALA_EINVAL, "ticket %lld is not a walk batch", (long long)ticket);
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipEventSynchronize(s->done[slot]));
+    const int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
+    if (n_nodes_host) *n_nodes_host = pin[0];
+    if (n_bad_host) *n_bad_host = pin[kPinEdges];
     return COALA_OK;
 }
 

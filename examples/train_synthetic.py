@@ -21,6 +21,8 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --task link --sampler temporal --num_negs 5
   python examples/train_synthetic.py --node_embedding --emb_dim 64 --model_type rgcn --num_rels 4
   python examples/train_synthetic.py --node_embedding --emb_optimizer sgd --emb_lr 0.1 --task link
+  python examples/train_synthetic.py --task node2vec --walk_length 20 --context_size 10 --walks_per_node 10 --p 0.5 --q 2 --num_negs 1 \
+      --emb_dim 128 --emb_optimizer adam --emb_lr 0.01 --batch_size 128
   python examples/train_synthetic.py --path /data/IGB/ --data IGB --dataset_size medium --cache_size 4096
   python -m torch.distributed.run --nproc-per-node 8 examples/train_synthetic.py --cache_backend nccl ...
 
@@ -36,13 +38,13 @@ sys.path.insert(0, os.path.join(ROOT, "coala-gnn_amd"))
 
 import torch  # noqa: E402
 
-from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node_Distributor, NodeEmbedding, RowWiseAdagrad, SparseAdagrad, SparseAdam, SparseSGD, SSD_INFO  # noqa: E402
+from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node2Vec, Node_Distributor, NodeEmbedding, RowWiseAdagrad, SparseAdagrad, SparseAdam, SparseSGD, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
 from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, GATv2, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
 from COALA_GNN.sampler import (EdgePredictionSampler, LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler,  # noqa: E402
                                TemporalEdgePredictionSampler, TemporalNeighborSampler, UniformNegativeSampler, reverse_edge_ids,
                                sort_csc_by_etype)
-from COALA_GNN.synthetic import alloc_pinned_table, edge_times, edge_types_by_source, powerlaw_csc, symmetrize_csc  # noqa: E402
+from COALA_GNN.synthetic import alloc_pinned_table, community_csc, edge_times, edge_types_by_source, powerlaw_csc, symmetrize_csc  # noqa: E402
 
 T_MAX = 1 << 20    # --sampler temporal: synthetic edge timestamps lie in [0, T_MAX)
 DECAY = "decay"    # --time_decay: the edata key the gcn / sage layers read their edge weights from
@@ -68,6 +70,42 @@ def make_embedding(args, loader):
         return emb, SparseAdam([emb], lr=args.emb_lr, betas=tuple(args.emb_betas), step=args.emb_step)
     cls = {"adagrad": SparseAdagrad, "rowwise_adagrad": RowWiseAdagrad, "sgd": SparseSGD}[args.emb_optimizer]
     return emb, cls([emb], lr=args.emb_lr)
+
+
+def sparse_optimizer(args, emb):
+    """--emb_optimizer over one NodeEmbedding."""
+    if args.emb_optimizer == "adam":
+        return SparseAdam([emb], lr=args.emb_lr, betas=tuple(args.emb_betas), step=args.emb_step)
+    return {"adagrad": SparseAdagrad, "rowwise_adagrad": RowWiseAdagrad, "sgd": SparseSGD}[args.emb_optimizer]([emb], lr=args.emb_lr)
+
+
+def train_node2vec(args):
+    """--task node2vec: shallow embeddings of a graph without features, as PyG's Node2Vec example -- biased walks from every node,
+    skip-gram windows with --num_negs negative rows per walk, a sparse optimizer over the embedding table.  The graph is
+    symmetrize_csc(community_csc(..)): planted communities of 2,048 nodes, rows sorted by source id as the walks need at q != 1.  After
+    every epoch: the mean loss, and how much closer (cosine) a node's embedding is to a node of its own community than to a random one."""
+    device = f"cuda:{torch.cuda.current_device()}"
+    indptr, indices = symmetrize_csc(*community_csc(args.nodes, 10.0, seed=0, device=device))
+    torch.manual_seed(max(args.seed, 0))
+    model = Node2Vec((indptr, indices), args.emb_dim or args.dim, args.walk_length, args.context_size, walks_per_node=args.walks_per_node, p=args.p,
+                     q=args.q, num_negative_samples=args.num_negs, cache_mb=args.cache_size, device=device, seed=max(args.seed, 0))
+    opt = sparse_optimizer(args, model.embedding)
+    probe = torch.randperm(args.nodes, generator=torch.Generator().manual_seed(1))[:4096].to(device)
+    for epoch in range(args.epochs):
+        t0, total, steps = time.time(), 0.0, 0
+        for batch in model.loader(args.batch_size):
+            loss = model.loss(batch)
+            loss.backward()
+            opt.step()   # (clears the embedding's trace)
+            total += float(loss.detach())
+            steps += 1
+        z = torch.nn.functional.normalize(model(probe), dim=1)
+        same = (probe // 2048 * 2048 + (probe + 1) % 2048).clamp_max(args.nodes - 1)      # the next node of the same community
+        other = probe[torch.randperm(probe.numel(), device=device)]
+        gap = float(((z * torch.nn.functional.normalize(model(same), dim=1)).sum(1) - (z * torch.nn.functional.normalize(model(other), dim=1)).sum(1)).mean())
+        print(f"Epoch {epoch:05d} | Loss {total / max(steps, 1):.4f} | Steps {steps} | cos(same community) - cos(random) {gap:+.4f} | "
+              f"Time {time.time() - t0:.2f}s")
+    model.close()
 
 
 def train_link(args, comm, device, indptr, indices, feat, files, fan_out):
@@ -167,7 +205,12 @@ def main():
     ap.add_argument("--use_edge_weight", action="store_true",
                     help="with --edge_weights random: the blocks carry their edge ids (NeighborSampler(edge_ids=True)) and the gcn / sage "
                          "layers multiply every message by its edge's weight, block.edata['w'] (DGL's edge_weight=); gat and gin ignore it")
-    ap.add_argument("--task", type=str, default="node", choices=["node", "link"],
+    ap.add_argument("--walk_length", type=int, default=20, help="with --task node2vec: hops per walk (1..127; a walk holds walk_length + 1 nodes)")
+    ap.add_argument("--context_size", type=int, default=10, help="with --task node2vec: nodes per skip-gram window (2..walk_length + 1)")
+    ap.add_argument("--walks_per_node", type=int, default=10, help="with --task node2vec: walks per start node (1..64)")
+    ap.add_argument("--p", type=float, default=1.0, help="with --task node2vec: the return parameter")
+    ap.add_argument("--q", type=float, default=1.0, help="with --task node2vec: the in-out parameter (p = q = 1 is DeepWalk)")
+    ap.add_argument("--task", type=str, default="node", choices=["node", "link", "node2vec"],
                     help="link: link prediction on the synthetic graph (EdgePredictionSampler over --sampler neighbor | labor, --model_type sage "
                          "| gat as the encoder, dot-product scores, BCE loss); the training items are edge ids")
     ap.add_argument("--num_negs", type=int, default=5, help="with --task link: uniform negative pairs per seed edge (0..64)")
@@ -235,6 +278,10 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", os.environ.get("SLURM_LOCALID", 0)))
     node_rank = int(os.environ.get("SLURM_NODEID", 0))
     torch.cuda.set_device(local_rank)
+    if args.task == "node2vec":   # no features, no GNN, no loader: walks, an embedding table and a sparse optimizer
+        if args.path or args.node_embedding or int(os.environ.get("WORLD_SIZE", 1)) != 1 or not 0 <= args.num_negs <= 16:
+            ap.error("--task node2vec runs on the synthetic graph on one GPU, with --num_negs 0..16 and without --node_embedding (it owns its table)")
+        return train_node2vec(args)
     comm = MPI_Comm_Manager(node_rank)                                  # sbatch_ssd_gnn_train.py:262
     device = "cuda:" + str(comm.local_rank)
     comm.initialize_nested_process_group(args.cache_backend)            # :267

@@ -566,6 +566,43 @@ typedef struct coala_edge_batch {
 int coala_sampler_edge_batch(coala_sampler_t* s, const int64_t* eids, int64_t n, int num_neg, uint64_t seed, uint64_t step,
                              const coala_edge_batch_t* out, int64_t* ticket_out, void* stream);
 int coala_sampler_edge_batch_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_nodes_host, int64_t* n_bad_host);
+/* Second-order walks (node2vec; DGL's dgl.sampling.node2vec_random_walk on a homogeneous graph): traces_out device int64[n, num_walks,
+ * length + 1]; traces_out[i, w, 0] = nodes[i], then the nodes walk w visits, -1 once it has ended (a node without an in-edge, or a
+ * neighbour id outside the graph).  An out-of-range start node gives a row of -1.  num_walks 1..64, length 1..127.  A hop is drawn by
+ * rejection: a uniformly drawn in-edge of the current node is taken with probability thr / 2^32, thr = thr_return when it leads back
+ * to the previous node, thr_near when it leads to an in-neighbour of the previous node, thr_far otherwise; after 256 refused attempts
+ * the last candidate is taken.  The caller computes the thresholds from p and q (m = max(1/p, 1, 1/q): (1/p)/m, 1/m, (1/q)/m times
+ * 2^32): any three values in [0, 2^32] whose largest is 2^32; COALA_EINVAL (with a message) otherwise, and nothing is launched.  The
+ * exact rule, its keys and counters, is in the header of coala_sampler.hip; the walks are a function of (seed, step, start node, w)
+ * on a stream of their own -- not coala_sampler_random_walk's.  When thr_near != thr_far the rows of the graph MUST BE SORTED
+ * ASCENDING BY SOURCE ID (the near test is a binary search; not verified here: COALA_GNN.sampler.sort_csc_by_src sorts a graph);
+ * unsorted rows give walks that are not what the rule says, but nothing is read out of bounds.  One kernel on `stream`; nothing is
+ * waited for. */
+int coala_sampler_node2vec_walk(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t thr_return,
+                                uint64_t thr_near, uint64_t thr_far, uint64_t seed, uint64_t step, int64_t* traces_out, void* stream);
+/* Skip-gram batches (PyG's Node2Vec.pos_sample / neg_sample): the walks of coala_sampler_node2vec_walk from `nodes`, num_neg (0..16)
+ * negative rows per walk, and everything relabelled to one list of distinct nodes.  Outputs (device), W = num_walks, L = length:
+ *   pos int32[n W, L + 1]: every trace as indices into input_nodes, -1 where the walk has ended;
+ *   neg int32[n W num_neg, L + 1] (may be NULL with num_neg 0): row (walk, j) holds the walk's start node in column 0 and in column
+ *     t >= 1 the node mulhi64(splitmix64((kw ^ 0x6A09E667F3BCC909) + 128 j + t), num_nodes), kw the walk's key; an invalid start node
+ *     gives rows of -1;
+ *   input_nodes int64[n + n W (L + 1) + n W num_neg L]: the distinct ids of the item list [valid start nodes | pos rows row-major | neg
+ *     columns 1.. row-major] in order of first appearance, n_nodes of them;
+ *   traces int64[n, W, L + 1], nullable: the global-id traces, bit-identical to coala_sampler_node2vec_walk's.
+ * Nothing is written past these capacities.  Limit: n W (L + 1) (1 + num_neg) <= 8,388,608 items; COALA_EINVAL (with a message) before
+ * any launch otherwise, and for arguments coala_sampler_node2vec_walk refuses.  Three launches on `stream`; no memset, copy or wait.
+ * The call takes a ticket of the handle's ring; n_nodes and n_bad (out-of-range start nodes) go to pinned host memory from the kernels
+ * and coala_sampler_walk_batch_wait collects them behind the call's event.  Each kind of wait refuses the other kinds' tickets. */
+typedef struct coala_walk_batch {
+    int64_t* input_nodes;
+    int32_t* pos;
+    int32_t* neg;
+    int64_t* traces;
+} coala_walk_batch_t;
+int coala_sampler_walk_batch(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t thr_return,
+                             uint64_t thr_near, uint64_t thr_far, int num_neg, uint64_t seed, uint64_t step, const coala_walk_batch_t* out,
+                             int64_t* ticket_out, void* stream);
+int coala_sampler_walk_batch_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_nodes_host, int64_t* n_bad_host);
 
 /* Block op for the consumer of these blocks (the native Block objects stand where DGL blocks stand in
  * examples/sbatch_ssd_gnn_train.py:138-141; dgl.nn.SAGEConv's "mean" reduces to this): out[d, :] = mean over the valid j of
@@ -824,6 +861,24 @@ int coala_block_pair_dot(int device, const float* h, const int32_t* src, const i
                          void* stream);
 int coala_block_pair_dot_backward(int device, const float* h, const int32_t* src, const int32_t* dst, const float* grad_out, float* grad_h,
                                   int64_t n_pairs, int heads, int dim, void* stream);
+/* Skip-gram window loss of walk tables (PyG's Node2Vec.loss, with softplus for -log(sigmoid + 1e-15)).  rows int32 [R, L1], indices
+ * into h fp32 [N, dim] (contiguous), -1 = no node; context C in 2..L1.  For every row r, window start a in 0 .. L1 - C and j in
+ * 1 .. C - 1 the pair (a, a + j) scores s = <h[rows[r, a]], h[rows[r, a + j]]> when both indices are >= 0.  partial[r] = the sum
+ * over the row's valid pairs of softplus(sign * s) (sign = -1: positive walks, +1: negatives), count[r] (int32) their number; the
+ * caller adds them up.  One wave (a group of 16 or 32 lanes for dim <= 16 / 32) stages the row's L1 embedding rows in LDS once; a lane
+ * then forms the dots of its own pairs from there and sums their losses in a double, and the group's sums are added in a fixed
+ * butterfly: bitwise reproducible.  L1 * dim <= 16384 floats and L1 <= 128, COALA_EINVAL ("bad walk table shape") otherwise; R == 0
+ * launches nothing.  An index >= N is not checked here (the caller's duty).
+ * Backward: grad_acc is a DOUBLE buffer [N, dim], zeroed by the caller, and scale a DEVICE double (the upstream gradient over the
+ * number of valid pairs: nothing waits for the host).  grad_acc[rows[r, t], :] += scale * sum over the pairs that hold position t of
+ * sign * sigmoid(sign * s) * h[other]: the scores are recomputed from LDS (fp32, the group's lanes on one dot), their coefficients
+ * kept in registers, each position's gradient row is summed over all its pairs in a double and added with ONE hardware double atomic
+ * per (position, element), not one per pair.  The caller rounds grad_acc to fp32 once: the hundreds of additions a node of a batch
+ * collects leave no fp32 rounding and no visible trace of their order. */
+int coala_block_skipgram_loss(int device, const float* h, const int32_t* rows, float* partial, int32_t* count, int64_t n_rows, int len,
+                              int context, int dim, float sign, void* stream);
+int coala_block_skipgram_loss_backward(int device, const float* h, const int32_t* rows, double* grad_acc, const double* scale, int64_t n_rows,
+                                       int len, int context, int dim, float sign, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Shared pinned-host ("UVA") region.  Replaces SharedUVAManager (COALA_GNN_Modules/shared_UVA.cuh:26-115):
