@@ -1154,6 +1154,9 @@ __global__ __launch_bounds__(256) void route_scatter_kernel(const int64_t* __res
 
 // ============================================================================================================ host
 
+#define fail coala_fail_
+#define HIPCHK COALA_HIPCHK
+
 namespace {
 
 // How K1 and K2 are launched.  Fixed at handle creation: launch_shape() sets the product's choice, which development builds
@@ -1226,13 +1229,55 @@ void apply_dev_knobs(LaunchShape& s) {
 }
 #endif
 
+// A batch that was probed (serve_probe) and still waits for its fills.  Until every position of [0, rows) was handed to a fill, exactly once, it
+// owns the verdict words and the per-set miss chains: a second probe or a row write on top of it would overwrite them under the pending fills.
+struct OpenBatch {
+    using Ranges = std::vector<std::pair<int64_t, int64_t>>;
+    int64_t rows = -1;
+    Ranges filled;                               // position ranges already handed to a fill (sorted)
+    int64_t filled_rows = 0;
+    Redirect redirect{0, 0, nullptr, nullptr};   // set by the probe, reused by the fills
+
+    bool is_open() const { return rows >= 0; }
+    void open(int64_t n, const Redirect& rd) { rows = n; filled.clear(); filled_rows = 0; redirect = rd; }
+    void close() { rows = -1; filled.clear(); filled_rows = 0; }
+    int refuse_while_open() const {
+        return fail(COALA_EINVAL, "a batch of %lld rows is still open (%lld filled): finish its serve_fill calls or call coala_cache_serve_abort",
+                    (long long)rows, (long long)filled_rows);
+    }
+    // The ranges of one fill call: inside [0, rows), disjoint from each other and from earlier fills.  Refuses, or leaves in *claim what `filled`
+    // becomes once the call's launches are enqueued (commit) and in *claim_rows the rows the call fills.
+    int check_ranges(const int64_t* begins, const int64_t* ends, int n_ranges, Ranges* claim, int64_t* claim_rows) const {
+        if (n_ranges < 0 || (n_ranges > 0 && (!begins || !ends))) return fail(COALA_EINVAL, "bad fill ranges");
+        *claim = filled;
+        *claim_rows = 0;
+        for (int k = 0; k < n_ranges; ++k) {
+            if (begins[k] < 0 || begins[k] > ends[k] || ends[k] > rows)
+                return fail(COALA_EINVAL, "fill range [%lld, %lld) outside the batch of %lld rows", (long long)begins[k], (long long)ends[k], (long long)rows);
+            if (ends[k] > begins[k]) claim->emplace_back(begins[k], ends[k]);
+            *claim_rows += ends[k] - begins[k];
+        }
+        std::sort(claim->begin(), claim->end());
+        for (size_t k = 1; k < claim->size(); ++k)
+            if ((*claim)[k].first < (*claim)[k - 1].second)
+                return fail(COALA_EINVAL, "fill range [%lld, %lld) overlaps positions that were already filled in this batch", (long long)(*claim)[k].first, (long long)(*claim)[k].second);
+        return COALA_OK;
+    }
+    void commit(Ranges& claim, int64_t claim_rows) {
+        filled.swap(claim);
+        filled_rows += claim_rows;
+        if (filled_rows == rows) close(); // [0, rows) covered once: the batch is complete
+    }
+};
+
 } // namespace
 
 struct coala_cache {
     coala_cache_config_t cfg;
     CacheDev d;
     uint64_t cap = 0;           // scratch capacity (rows)
-    uint32_t gen = 0;
+    uint32_t gen = 0;           // generation: one per probe
+    int fill_launches = 0;      // fill launches of this generation so far: each takes its own ticket counter (kFillSlots per batch)
     int32_t* node_color_dev = nullptr;
     // route scratch
     uint32_t* wave_counts = nullptr;
@@ -1245,7 +1290,7 @@ struct coala_cache {
     coala_cache_profile_t prof{};
     hipStream_t last_stream = nullptr;    // stream of the last bracketed launch (for the empty-bracket calibration)
     // The handle's tables and scratch are ordered by the stream its calls are enqueued on.  A caller that moves to another stream
-    // keeps that order: the new stream first waits for what the handle enqueued last on the old one (follow_stream).
+    // keeps that order: the new stream first waits for what the handle enqueued last on the old one (enter).
     hipStream_t order_stream = nullptr;
     bool order_set = false;
     hipEvent_t order_ev = nullptr;
@@ -1256,11 +1301,7 @@ struct coala_cache {
     int32_t* color_pin_async = nullptr;   // pinned staging + event of a pending coala_cache_color_counts_async
     hipEvent_t color_ev = nullptr;
     int32_t color_pending = -1;           // entries of the pending snapshot, -1 = none
-    int64_t open_batch_rows = -1;         // rows of a batch that was probed (serve_probe) and still waits for its fills
-    std::vector<std::pair<int64_t, int64_t>> open_filled; // position ranges of the open batch already handed to a fill (sorted)
-    int64_t open_filled_rows = 0;
-    Redirect open_redirect{0, 0, nullptr, nullptr};       // the open batch's redirect (set by the probe, reused by its fills)
-    int fill_launches = 0;                // fill launches of the current batch so far: each takes its own ticket counter (kFillSlots per batch)
+    OpenBatch batch;                      // set by serve_probe, closed by its fills or by serve_abort
     uint64_t rows_total = 0;              // rows submitted since the last stats reset (hits = rows - misses - rejected)
     uint64_t cum_hit = 0, cum_miss = 0;   // totals folded in whenever coala_cache_stats resets the device counters
     uint64_t prof_hit0 = 0, prof_miss0 = 0; // totals at the last profile reset
@@ -1275,10 +1316,11 @@ struct coala_cache {
 
 namespace {
 
-#define fail coala_fail_
-#define HIPCHK COALA_HIPCHK
-
-int follow_stream(coala_cache* h, hipStream_t s) {
+// How an entry point that enqueues work begins: on the handle's device and, unless it touches nothing the handle orders (follow = false), behind
+// what the handle enqueued last, on whichever stream that was ...
+int enter(coala_cache* h, hipStream_t s, bool follow = true) {
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (!follow) return COALA_OK;
     if (h->order_set && h->order_stream != s) {
         if (!h->order_ev) HIPCHK(hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
         // (a stream the caller has destroyed in the meantime has nothing left to wait for)
@@ -1290,27 +1332,22 @@ int follow_stream(coala_cache* h, hipStream_t s) {
     return COALA_OK;
 }
 
-int ilog2_exact(uint64_t v) {
-    if (v == 0 || (v & (v - 1))) return -1;
-    int s = 0;
-    while ((1ull << s) != v) ++s;
-    return s;
+// ... and how one that launched kernels ends: a launch that failed is reported, and a COALA_FLAG_SYNC handle waits for its work.
+int leave(coala_cache* h, hipStream_t s) {
+    HIPCHK(hipGetLastError());
+    if (h->cfg.flags & COALA_FLAG_SYNC) HIPCHK(hipStreamSynchronize(s));
+    return COALA_OK;
 }
 
 int ensure_scratch(coala_cache* h, uint64_t n, hipStream_t s) {
-    if (n <= h->cap) return COALA_OK;
-    HIPCHK(hipStreamSynchronize(s));
-    uint64_t cap = h->cap ? h->cap : 1024;
-    while (cap < n) cap *= 2;
-    if (h->d.miss_link) HIPCHK(hipFree(h->d.miss_link));
-    h->d.miss_link = nullptr;
-    HIPCHK(hipMalloc((void**)&h->d.miss_link, cap * sizeof(uint32_t))); // written by every probe before any fill reads it
-    if (h->d.miss_list) HIPCHK(hipFree(h->d.miss_list));
-    h->d.miss_list = nullptr;
-    h->d.list_sub = (uint32_t)(cap / kListShards) + 32u;                 // (cap is a power of two >= 1024; a chunk has at most 32 rows)
-    HIPCHK(hipMalloc((void**)&h->d.miss_list, (uint64_t)kListShards * h->d.list_sub * sizeof(uint32_t))); // entries below a shard's counter are written by the batch's probe
-    h->cap = cap;
-    return COALA_OK;
+    const uint64_t cap_before = h->cap;
+    if (int rc = grow((void**)&h->d.miss_link, &h->cap, n, sizeof(uint32_t), s)) return rc;   // written by every probe before any fill reads it
+    if (h->cap == cap_before && h->d.miss_list) return COALA_OK;
+    // the miss list follows the new capacity (a power of two >= 1024; a chunk has at most 32 rows), whatever it held before
+    h->d.list_sub = (uint32_t)(h->cap / kListShards) + 32u;
+    const uint64_t list_words = (uint64_t)kListShards * h->d.list_sub;   // entries below a shard's counter are written by the batch's probe
+    uint64_t list_cap = 0;
+    return grow((void**)&h->d.miss_list, &list_cap, list_words, sizeof(uint32_t), s, list_words);
 }
 
 hipEvent_t take_event(coala_cache* h) {
@@ -1401,11 +1438,237 @@ int for_each_range_set(const int64_t* begins, const int64_t* ends, int count, F&
     return COALA_OK;
 }
 
-int grid_for(int64_t chunks, int waves_per_block, int max_blocks) {
-    int64_t blocks = (chunks + waves_per_block - 1) / waves_per_block;
-    if (blocks < 1) blocks = 1;
-    if (blocks > max_blocks) blocks = max_blocks;
-    return (int)blocks;
+// ---------------------------------------------------------------------------------------------------------- a read
+enum { kPhaseProbe = 1, kPhaseFill = 2, kPhaseBoth = 3 };
+
+// One read, as its entry point hands it to read_feature: the phases it runs and the arguments every entry point has, in the ABI's order, and
+// below them what an entry point sets by name; then what the steps of read_feature work out, each from what stands above it.
+struct FillRanges { const int64_t* begins; const int64_t* ends; int n; };
+struct ReadCall {
+    int phases;
+    coala_cache* h; float* out; const int64_t* idx; int64_t n; hipStream_t stream;
+    bool force_dist = true;                               // the owner-partitioned set index whatever the handle's flags say: every serve call
+                                                          // (coala_cache_read_feature alone clears it)
+    FillRanges ranges{nullptr, nullptr, 0};               // a fill alone: the batch positions it fills
+    const coala_row_redirect_t* redirect = nullptr;       // a probe alone
+    // Events to put ON the probe's launch (its begin) / on the LAST fill launch of this call (its end) instead of recording them behind it
+    // (library-internal callers: the distributed fetch).  rode_begin / rode_end: the event that really rides on that launch: the caller's, or -- a
+    // profiling handle uses the dispatches' event slots for its own pairs -- the handle's profiling event of that launch (good for a stream to wait
+    // on; it returns to a pool later, so not for timing), or null when the call launched nothing there: the caller then records its event the plain way.
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    hipEvent_t rode_begin = nullptr, rode_end = nullptr;
+    // check_read
+    bool nothing_to_do = false;
+    Redirect rd{0, 0, nullptr, nullptr};
+    int64_t whole[2] = {0, 0};                            // a whole read fills the one range [0, n)
+    OpenBatch::Ranges claim; int64_t fill_rows = 0;       // a fill alone: OpenBatch::check_ranges
+    // choose_events
+    bool own_ring = false;
+    // kernel_args
+    uint32_t gen; bool redir, vec4, list_form; CacheDev d;
+};
+
+// Every refusal, always in this order, and what the call fills.  No HIP call, and nothing of the handle's changes but last_begin / last_end.
+int check_read(ReadCall& c) {
+    coala_cache* h = c.h;
+    if (!h) return fail(COALA_EINVAL, "null handle");
+    h->last_begin = h->last_end = nullptr; // (set again by finish_read when this call launches a whole read with its events attached)
+    if (c.n < 0 || c.n > 0x7FFFFFFFll) return fail(COALA_EINVAL, "n=%lld out of range", (long long)c.n);
+    if (c.phases & kPhaseProbe) {
+        if (h->batch.is_open()) return h->batch.refuse_while_open();
+    } else if (h->batch.rows != c.n || h->gen == 0) {
+        return fail(COALA_EINVAL, "serve_fill without a matching serve_probe (batch of %lld rows, probe saw %lld)", (long long)c.n, (long long)h->batch.rows);
+    }
+    c.nothing_to_do = c.n == 0;
+    if (c.nothing_to_do) return COALA_OK;
+    if (!c.idx || (!c.out && !(c.redirect && c.redirect->begin == 0 && c.redirect->end == c.n))) return fail(COALA_EINVAL, "null buffer");
+    if (!(c.phases & kPhaseProbe)) {
+        c.rd = h->batch.redirect;
+    } else if (c.redirect && c.redirect->end > c.redirect->begin) {
+        if (c.redirect->begin < 0 || c.redirect->end > c.n || !c.redirect->out)
+            return fail(COALA_EINVAL, "redirect [%lld, %lld) outside the batch of %lld rows, or null destination", (long long)c.redirect->begin, (long long)c.redirect->end, (long long)c.n);
+        c.rd = Redirect{c.redirect->begin, c.redirect->end, c.redirect->out, c.redirect->row_map};
+    }
+    if (c.phases == kPhaseBoth) {
+        c.whole[1] = c.fill_rows = c.n;
+        c.ranges = FillRanges{&c.whole[0], &c.whole[1], 1};
+    } else if (c.phases == kPhaseFill) {
+        if (int rc = h->batch.check_ranges(c.ranges.begins, c.ranges.ends, c.ranges.n, &c.claim, &c.fill_rows)) return rc;
+        c.nothing_to_do = c.fill_rows == 0;
+    }
+    return COALA_OK;
+}
+
+// The events that ride on the launches: the handle's own pair of this call (coala_cache_fetch_events: a whole read = K1 + one K2 launch, begin on
+// the first dispatch, end on the second), else the caller's.  A profiling handle keeps the dispatches' event slots for itself (ProfScope).
+int choose_events(ReadCall& c) {
+    coala_cache* h = c.h;
+    if (h->cfg.flags & COALA_FLAG_PROFILE) {
+        c.ev_begin = c.ev_end = nullptr;
+    } else if (h->fetch_events && c.phases == kPhaseBoth) {
+        if (h->fev.empty()) h->fev.assign(2 * (size_t)coala_cache::kFetchRing, nullptr);
+        const size_t slot = (size_t)(h->fev_calls % coala_cache::kFetchRing);
+        for (size_t k = 2 * slot; k < 2 * slot + 2; ++k)
+            if (!h->fev[k]) HIPCHK(hipEventCreate(&h->fev[k]));
+        c.ev_begin = h->fev[2 * slot];
+        c.ev_end = h->fev[2 * slot + 1];
+        c.own_ring = true;
+    }
+    return COALA_OK;
+}
+
+// A probe starts a generation.  One that runs alone leaves its batch open for the fills.
+int next_generation(ReadCall& c) {
+    coala_cache* h = c.h;
+    h->fill_launches = 0;
+    if (++h->gen == 0) { // generation wrapped: clear the chain heads and the generation tags of the cursors once
+        HIPCHK(hipMemsetAsync(h->d.set_head, 0, h->d.num_sets * 8, c.stream));
+        HIPCHK(hipMemset2DAsync(reinterpret_cast<char*>(h->d.set_cnt) + 4, 8, 0, 4, h->d.num_sets, c.stream));
+        HIPCHK(hipMemsetAsync(h->d.stats + kStatList, 0, (size_t)(kStatWords - kStatList) * 8, c.stream));   // (generation 1 follows an odd one: its list counters were not cleared)
+        h->gen = 1;
+    }
+    if (c.phases == kPhaseProbe) h->batch.open(c.n, c.rd);
+    return COALA_OK;
+}
+
+// What the kernels of this call get, and which of them run: after ensure_scratch and next_generation, which change what is copied here.
+void kernel_args(ReadCall& c) {
+    const coala_cache* h = c.h;
+    c.gen = h->gen;
+    c.redir = c.rd.end > c.rd.begin;
+    c.vec4 = (h->d.dim % 4 == 0) && aligned16(c.out) && aligned16(h->d.cold) && (!c.redir || aligned16(c.rd.out));
+    c.d = h->d;
+    if (c.force_dist) c.d.distributed = 1u;
+    // a whole read on a host tier: the probe keeps the batch's miss list and the fill streams from it (ranged fills: the tile form, no list)
+    c.list_form = c.phases == kPhaseBoth && h->host_tier;
+    if (!c.list_form) c.d.list_sub = 0;
+}
+
+// K1's variants.  The redirecting one carries a destination per row: with 16 rows per chunk (512-B lines, 8 passes) it spills -> half the passes there.
+template <int CD, int VEC, int NP> constexpr int kRedirectPasses = (Geo<CD, VEC, NP>::R > 8) ? NP / 2 : NP;
+using ProbeKernel = void (*)(const int64_t*, float*, int64_t, uint32_t, uint32_t, CacheDev, Redirect);
+template <int CD, int VEC, typename TAG, int NP>
+ProbeKernel probe_kernel(bool full, bool redir, bool single) {
+    constexpr int NPR = kRedirectPasses<CD, VEC, NP>;
+    static constexpr ProbeKernel variant[2][2][2] = { // [redir][full][single]
+        {{probe_gather_kernel<CD, VEC, TAG, NP, false, false, false>, probe_gather_kernel<CD, VEC, TAG, NP, false, false, true>},
+         {probe_gather_kernel<CD, VEC, TAG, NP, true, false, false>, probe_gather_kernel<CD, VEC, TAG, NP, true, false, true>}},
+        {{probe_gather_kernel<CD, VEC, TAG, NPR, false, true, false>, probe_gather_kernel<CD, VEC, TAG, NPR, false, true, true>},
+         {probe_gather_kernel<CD, VEC, TAG, NPR, true, true, false>, probe_gather_kernel<CD, VEC, TAG, NPR, true, true, true>}}};
+    return variant[redir][full][single];
+}
+
+// K1: 2-wave blocks, every wave resident; one wave per chunk, or grid-stride over the chunks
+template <int CD, int VEC, typename TAG, int NP>
+int launch_probe_as(ReadCall& c) {
+    const LaunchShape& ls = c.h->shape;
+    const int rows = c.redir ? Geo<CD, VEC, kRedirectPasses<CD, VEC, NP>>::R : Geo<CD, VEC, NP>::R;   // per chunk
+    const int64_t chunks = (c.n + rows - 1) / rows;
+    const bool full = (VEC == 4) && ((int)c.d.dim == CD);
+    const bool single = ls.k1_single && chunks <= kK1SingleMaxChunks;
+    const dim3 grid(grid1d(chunks, ls.k1_waves, single ? (int)((kK1SingleMaxChunks + ls.k1_waves - 1) / ls.k1_waves) : ls.k1_grid_cap)), block(64 * ls.k1_waves);
+    ProfScope ps(c.h, c.stream, 0, (uint64_t)c.n, c.ev_begin, nullptr);
+    c.rode_begin = ps.on ? ps.a : c.ev_begin;
+    ps.launch(probe_kernel<CD, VEC, TAG, NP>(full, c.redir, single), grid, block, c.idx, c.out, c.n, c.gen, (uint32_t)grid.x, c.d, c.rd);
+    return COALA_OK;
+}
+
+template <int CD, int VEC, typename TAG>
+int launch_probe_of(ReadCall& c) {
+#ifdef COALA_DEV_KNOBS
+    switch (c.h->shape.k1_passes) { // development builds: rows in flight per wave from the environment
+        case 0: break;
+        case 2: return launch_probe_as<CD, VEC, TAG, 2>(c);
+        case 8: return launch_probe_as<CD, VEC, TAG, 8>(c);
+        case 16: return launch_probe_as<CD, VEC, TAG, (Geo<CD, VEC, 16>::R <= 32 ? 16 : 8)>(c);
+        default: return launch_probe_as<CD, VEC, TAG, 4>(c);
+    }
+#endif
+    return launch_probe_as<CD, VEC, TAG, kK1Passes>(c);
+}
+
+int launch_probe(ReadCall& c) {
+    return dispatch_geo(c.d.cache_dim, c.vec4, [&](auto geo) -> int {
+        constexpr int CD = geo_cd(geo);
+        constexpr int VEC = geo_vec(geo);
+        return c.d.tag32 ? launch_probe_of<CD, VEC, uint32_t>(c) : launch_probe_of<CD, VEC, uint64_t>(c);
+    });
+}
+
+// K2 streaming from the miss list the batch's probe kept: one launch, which draws its groups from the batch's first ticket counter
+template <int CD, int VEC>
+int launch_fill_list(ReadCall& c) {
+    constexpr int R = Geo<CD, VEC>::R;
+    ProfScope ps(c.h, c.stream, 2, 0, nullptr, c.ev_end);
+    c.rode_end = ps.on ? ps.b : c.ev_end;
+    c.h->fill_launches++;
+    ps.launch(miss_fill_list_kernel<CD, VEC>, dim3(grid1d((c.n + R - 1) / R, 4, c.h->shape.k2_grid_cap)), dim3(256), c.d, c.idx, c.out, c.gen);
+    return COALA_OK;
+}
+
+// K2 over verdict tiles of the call's ranges: one launch per kMaxRanges ranges, the end event on the last one
+template <int CD, int VEC>
+int launch_fill_tiles(ReadCall& c) {
+    coala_cache* h = c.h;
+    const int tile_rows = h->shape.k2_tile_rows > 0 ? h->shape.k2_tile_rows : Geo<CD, VEC>::R;
+    int live = 0, set_no = 0;
+    for (int k = 0; k < c.ranges.n; ++k) live += c.ranges.ends[k] > c.ranges.begins[k];
+    const int n_sets = (live + kMaxRanges - 1) / kMaxRanges;
+    return for_each_range_set(c.ranges.begins, c.ranges.ends, c.ranges.n, [&](const RangeSet& rs) -> int {
+        const bool last_set = ++set_no == n_sets;
+        ProfScope ps(h, c.stream, 2, 0, nullptr, last_set ? c.ev_end : nullptr);
+        if (last_set) c.rode_end = ps.on ? ps.b : c.ev_end;
+        const int64_t tiles = ((int64_t)rs.total + tile_rows - 1) / tile_rows;
+        const dim3 grid(grid1d(tiles, 4, h->shape.k2_grid_cap));
+        // dynamic deal (host tier, more tiles than waves, one of the batch's first kFillSlots fill launches): this launch's ticket counter
+        const int64_t waves = (int64_t)grid.x * 4;
+        int dyn_slot = -1;
+        if (h->shape.k2_unit_tiles > 0 && tiles > waves && tiles < 0x7FFFFFFF && h->fill_launches < kFillSlots)
+            dyn_slot = (int)((c.gen & 1u) * kFillSlots) + h->fill_launches;
+        h->fill_launches++;
+        ps.launch(c.redir ? miss_fill_kernel<CD, VEC, true> : miss_fill_kernel<CD, VEC, false>, grid, dim3(256), c.d, c.idx, c.out, tile_rows,
+                  h->shape.k2_sparse_max, c.gen, rs, c.rd, dyn_slot);
+        return COALA_OK;
+    });
+}
+
+// A whole read on a host tier fills from the list, every other one from verdict tiles (kernel_args)
+int launch_fill(ReadCall& c) {
+    return dispatch_geo(c.d.cache_dim, c.vec4, [&](auto geo) -> int {
+        constexpr int CD = geo_cd(geo);
+        constexpr int VEC = geo_vec(geo);
+        return c.list_form ? launch_fill_list<CD, VEC>(c) : launch_fill_tiles<CD, VEC>(c);
+    });
+}
+
+// What a read that was enqueued leaves on the handle.  (A fill's ranges count as filled from here on, not from check_read: a call that a HIP
+// error ends before its launches leaves the batch as it found it, and the same fill can be sent again.)
+int finish_read(ReadCall& c) {
+    coala_cache* h = c.h;
+    if (c.own_ring) {
+        h->last_begin = c.ev_begin;
+        h->last_end = c.ev_end;
+        h->fev_calls++;
+    }
+    if (c.phases & kPhaseProbe) h->rows_total += (uint64_t)c.n;
+    if (c.phases == kPhaseFill) h->batch.commit(c.claim, c.fill_rows);
+    return leave(h, c.stream);
+}
+
+int read_feature(ReadCall& c) {
+    if (int rc = check_read(c)) return rc;
+    if (c.nothing_to_do) return COALA_OK;
+    if (int rc = enter(c.h, c.stream)) return rc;
+    if (int rc = ensure_scratch(c.h, (uint64_t)c.n, c.stream)) return rc;
+    if (int rc = choose_events(c)) return rc;
+    if (c.phases & kPhaseProbe)
+        if (int rc = next_generation(c)) return rc;
+    kernel_args(c);
+    if (c.phases & kPhaseProbe)
+        if (int rc = launch_probe(c)) return rc;
+    if (c.fill_rows > 0)
+        if (int rc = launch_fill(c)) return rc;   // launch_fill_list or launch_fill_tiles
+    return finish_read(c);
 }
 
 } // namespace
@@ -1592,258 +1855,70 @@ int coala_cache_geometry(const coala_cache_t* h, coala_cache_geometry_t* out) {
     return COALA_OK;
 }
 
-enum { kPhaseProbe = 1, kPhaseFill = 2, kPhaseBoth = 3 };
-
-// ext_begin / ext_end (library-internal callers: the distributed fetch): events to put ON the probe's launch (its begin) / on the LAST fill
-// launch of this call (its end) instead of recording them behind it.  rode[0] / rode[1] receive the event that really rides on that launch:
-// the caller's, or -- a profiling handle uses the dispatches' event slots for its own pairs -- the handle's profiling event of that launch
-// (good for a stream to wait on; it returns to a pool later, so not for timing), or NULL when the call launched nothing there: the caller
-// then records its event the plain way.
-static int read_feature_impl(coala_cache_t* h, float* out, const int64_t* idx, int64_t n, void* stream, bool force_dist,
-                             int phases, const int64_t* begins, const int64_t* ends, int n_ranges,
-                             const coala_row_redirect_t* redirect, hipEvent_t ext_begin = nullptr, hipEvent_t ext_end = nullptr,
-                             hipEvent_t* rode = nullptr) {
-    if (rode) rode[0] = rode[1] = nullptr;
-    if (!h) return fail(COALA_EINVAL, "null handle");
-    h->last_begin = h->last_end = nullptr; // (set again below when this call launches a whole read with its events attached)
-    if (n < 0 || n > 0x7FFFFFFFll) return fail(COALA_EINVAL, "n=%lld out of range", (long long)n);
-    if (phases & kPhaseProbe) {
-        // a batch that was probed and not completely filled still owns the verdict words and the per-set miss chains: a second
-        // probe on top of it would overwrite them under the pending fills
-        if (h->open_batch_rows >= 0)
-            return fail(COALA_EINVAL, "a batch of %lld rows is still open (%lld filled): finish its serve_fill calls or call coala_cache_serve_abort",
-                        (long long)h->open_batch_rows, (long long)h->open_filled_rows);
-    } else if (h->open_batch_rows != n || h->gen == 0) {
-        return fail(COALA_EINVAL, "serve_fill without a matching serve_probe (batch of %lld rows, probe saw %lld)", (long long)n, (long long)h->open_batch_rows);
-    }
-    if (n == 0) return COALA_OK;
-    if (!idx || (!out && !(redirect && redirect->begin == 0 && redirect->end == n))) return fail(COALA_EINVAL, "null buffer");
-    Redirect rd{0, 0, nullptr, nullptr};
-    if (phases & kPhaseProbe) {
-        if (redirect && redirect->end > redirect->begin) {
-            if (redirect->begin < 0 || redirect->end > n || !redirect->out)
-                return fail(COALA_EINVAL, "redirect [%lld, %lld) outside the batch of %lld rows, or null destination", (long long)redirect->begin, (long long)redirect->end, (long long)n);
-            rd = Redirect{redirect->begin, redirect->end, redirect->out, redirect->row_map};
-        }
-    } else {
-        rd = h->open_redirect;
-    }
-    const int64_t whole_b = 0, whole_e = n;
-    if (phases == kPhaseBoth) { begins = &whole_b; ends = &whole_e; n_ranges = 1; }
-    int64_t fill_rows = 0;
-    if (phases & kPhaseFill) {
-        if (n_ranges < 0 || (n_ranges > 0 && (!begins || !ends))) return fail(COALA_EINVAL, "bad fill ranges");
-        // every position is filled exactly once per batch: ranges inside [0, n), disjoint from each other and from earlier fills
-        std::vector<std::pair<int64_t, int64_t>> add;
-        for (int k = 0; k < n_ranges; ++k) {
-            if (begins[k] < 0 || begins[k] > ends[k] || ends[k] > n)
-                return fail(COALA_EINVAL, "fill range [%lld, %lld) outside the batch of %lld rows", (long long)begins[k], (long long)ends[k], (long long)n);
-            if (ends[k] > begins[k]) add.emplace_back(begins[k], ends[k]);
-        }
-        if (phases == kPhaseFill) {
-            std::vector<std::pair<int64_t, int64_t>> all = h->open_filled;
-            all.insert(all.end(), add.begin(), add.end());
-            std::sort(all.begin(), all.end());
-            for (size_t k = 1; k < all.size(); ++k)
-                if (all[k].first < all[k - 1].second)
-                    return fail(COALA_EINVAL, "fill range [%lld, %lld) overlaps positions that were already filled in this batch", (long long)all[k].first, (long long)all[k].second);
-            h->open_filled.swap(all);
-        }
-        for (auto& r : add) fill_rows += r.second - r.first;
-        if (fill_rows == 0 && !(phases & kPhaseProbe)) return COALA_OK;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc_ = follow_stream(h, s)) return rc_;
-    int rc = ensure_scratch(h, (uint64_t)n, s);
-    if (rc) return rc;
-    if (phases & kPhaseProbe) {
-        h->fill_launches = 0;
-        if (++h->gen == 0) { // generation wrapped: clear the chain heads and the generation tags of the cursors once
-            HIPCHK(hipMemsetAsync(h->d.set_head, 0, h->d.num_sets * 8, s));
-            HIPCHK(hipMemset2DAsync(reinterpret_cast<char*>(h->d.set_cnt) + 4, 8, 0, 4, h->d.num_sets, s));
-            HIPCHK(hipMemsetAsync(h->d.stats + kStatList, 0, (size_t)(kStatWords - kStatList) * 8, s));   // (generation 1 follows an odd one: its list counters were not cleared)
-            h->gen = 1;
-        }
-        if (!(phases & kPhaseFill)) { // a probe alone leaves the batch open for its fills
-            h->open_batch_rows = n;
-            h->open_filled.clear();
-            h->open_filled_rows = 0;
-            h->open_redirect = rd;
-        }
-    }
-    const uint32_t gen = h->gen;
-    const bool redir = rd.end > rd.begin;
-    const bool vec4 = (h->d.dim % 4 == 0) && aligned16(out) && aligned16(h->d.cold) && (!redir || aligned16(rd.out));
-    CacheDev d = h->d;
-    if (force_dist) d.distributed = 1u;
-    // a whole read on a host tier: the probe keeps the batch's miss list and the fill streams from it (ranged fills: the tile form, no list)
-    const bool list_form = phases == kPhaseBoth && h->host_tier;
-    if (!list_form) d.list_sub = 0;
-    // a whole read (K1 + one K2 launch): its begin / end events ride on the two dispatches (see coala_cache_fetch_events)
-    hipEvent_t fe_begin = nullptr, fe_end = nullptr;
-    if (h->fetch_events && phases == kPhaseBoth && !(h->cfg.flags & COALA_FLAG_PROFILE)) {
-        if (h->fev.empty()) h->fev.assign(2 * (size_t)coala_cache::kFetchRing, nullptr);
-        const size_t slot = (size_t)(h->fev_calls % coala_cache::kFetchRing);
-        for (size_t k = 2 * slot; k < 2 * slot + 2; ++k)
-            if (!h->fev[k]) HIPCHK(hipEventCreate(&h->fev[k]));
-        fe_begin = h->fev[2 * slot];
-        fe_end = h->fev[2 * slot + 1];
-    }
-    const bool own_ring = fe_begin != nullptr;
-    if (!own_ring && !(h->cfg.flags & COALA_FLAG_PROFILE)) {
-        fe_begin = (phases & kPhaseProbe) ? ext_begin : nullptr;
-        fe_end = (phases & kPhaseFill) ? ext_end : nullptr;
-    }
-    int n_sets = 0, set_no = 0;   // fill launches of this call (one per 64 ranges): the end event rides on the last one
-    if ((phases & kPhaseFill) && fill_rows > 0) {
-        int live = 0;
-        for (int k = 0; k < n_ranges; ++k) live += ends[k] > begins[k];
-        n_sets = (live + kMaxRanges - 1) / kMaxRanges;
-    }
-    rc = dispatch_geo(d.cache_dim, vec4, [&](auto geo) -> int {
-        constexpr int CD = geo_cd(geo);
-        constexpr int VEC = geo_vec(geo);
-        using G = Geo<CD, VEC>;
-        // K1: 2-wave blocks, every wave resident; grid-stride over the chunks
-        if (phases & kPhaseProbe) {
-            ProfScope ps(h, s, 0, (uint64_t)n, fe_begin, nullptr);
-            if (rode) rode[0] = ps.on ? ps.a : fe_begin;
-            const bool full = (VEC == 4) && ((int)d.dim == CD);
-            auto launch_k1 = [&](auto tag_c, auto np_c) {
-                using TAG = decltype(tag_c);
-                constexpr int NP = decltype(np_c)::value;
-                // the redirecting variant carries a destination per row: with 16 rows per chunk (512-B lines, 8 passes) it spills -> 4 passes there
-                constexpr int NPR = (Geo<CD, VEC, NP>::R > 8) ? NP / 2 : NP;
-                using GK = Geo<CD, VEC, NP>;
-                using GR = Geo<CD, VEC, NPR>;
-                const int64_t chunks = redir ? (n + GR::R - 1) / GR::R : (n + GK::R - 1) / GK::R;
-                const LaunchShape& ls = h->shape;
-                const bool single = ls.k1_single && chunks <= kK1SingleMaxChunks;
-                const dim3 grid(grid_for(chunks, ls.k1_waves, single ? (int)((kK1SingleMaxChunks + ls.k1_waves - 1) / ls.k1_waves) : ls.k1_grid_cap)), block(64 * ls.k1_waves);
-                auto pick = [&](auto single_c) {
-                    constexpr bool S = decltype(single_c)::value;
-                    if (redir) return full ? probe_gather_kernel<CD, VEC, TAG, NPR, true, true, S> : probe_gather_kernel<CD, VEC, TAG, NPR, false, true, S>;
-                    return full ? probe_gather_kernel<CD, VEC, TAG, NP, true, false, S> : probe_gather_kernel<CD, VEC, TAG, NP, false, false, S>;
-                };
-                ps.launch(single ? pick(std::true_type{}) : pick(std::false_type{}), grid, block, idx, out, n, gen, (uint32_t)grid.x, d, rd);
-            };
-#ifdef COALA_DEV_KNOBS
-            if (h->shape.k1_passes) { // development builds: rows in flight per wave from the environment
-                auto by_np = [&](auto tag_c) {
-                    switch (h->shape.k1_passes) {
-                        case 2: launch_k1(tag_c, std::integral_constant<int, 2>{}); break;
-                        case 8: launch_k1(tag_c, std::integral_constant<int, 8>{}); break;
-                        case 16: launch_k1(tag_c, std::integral_constant<int, (Geo<CD, VEC, 16>::R <= 32 ? 16 : 8)>{}); break;
-                        default: launch_k1(tag_c, std::integral_constant<int, 4>{}); break;
-                    }
-                };
-                if (d.tag32) by_np(uint32_t{}); else by_np(uint64_t{});
-            } else
-#endif
-            if (d.tag32) launch_k1(uint32_t{}, std::integral_constant<int, kK1Passes>{});
-            else launch_k1(uint64_t{}, std::integral_constant<int, kK1Passes>{});
-        }
-        if ((phases & kPhaseFill) && fill_rows > 0) {
-            if (list_form) {
-                ProfScope ps(h, s, 2, 0, nullptr, fe_end);
-                if (rode) rode[1] = ps.on ? ps.b : fe_end;
-                h->fill_launches++;   // (the list form draws its groups from the batch's first ticket counter)
-                ps.launch(miss_fill_list_kernel<CD, VEC>, dim3(grid_for((n + G::R - 1) / G::R, 4, h->shape.k2_grid_cap)), dim3(256), d, idx, out, gen);
-                return COALA_OK;
-            }
-            const int tile_rows = h->shape.k2_tile_rows > 0 ? h->shape.k2_tile_rows : G::R;
-            return for_each_range_set(begins, ends, n_ranges, [&](const RangeSet& rs) -> int {
-                const bool last_set = ++set_no == n_sets;
-                ProfScope ps(h, s, 2, 0, nullptr, last_set ? fe_end : nullptr);
-                if (rode && last_set) rode[1] = ps.on ? ps.b : fe_end;
-                const int64_t tiles = ((int64_t)rs.total + tile_rows - 1) / tile_rows;
-                const dim3 grid(grid_for(tiles, 4, h->shape.k2_grid_cap));
-                // dynamic deal (host tier, more tiles than waves, one of the batch's first kFillSlots fill launches): this launch's ticket counter
-                const int64_t waves = (int64_t)grid.x * 4;
-                int dyn_slot = -1;
-                if (h->shape.k2_unit_tiles > 0 && tiles > waves && tiles < 0x7FFFFFFF && h->fill_launches < kFillSlots)
-                    dyn_slot = (int)((gen & 1u) * kFillSlots) + h->fill_launches;
-                h->fill_launches++;
-                if (redir) ps.launch(miss_fill_kernel<CD, VEC, true>, grid, dim3(256), d, idx, out, tile_rows, h->shape.k2_sparse_max, gen, rs, rd, dyn_slot);
-                else ps.launch(miss_fill_kernel<CD, VEC, false>, grid, dim3(256), d, idx, out, tile_rows, h->shape.k2_sparse_max, gen, rs, rd, dyn_slot);
-                return COALA_OK;
-            });
-        }
-        return COALA_OK;
-    });
-    if (rc) return rc;
-    if (own_ring) {
-        h->last_begin = fe_begin;
-        h->last_end = fe_end;
-        h->fev_calls++;
-    }
-    if (phases & kPhaseProbe) h->rows_total += (uint64_t)n;
-    if (phases == kPhaseFill) {
-        h->open_filled_rows += fill_rows;
-        if (h->open_filled_rows == h->open_batch_rows) { // [0, n) covered once: the batch is complete
-            h->open_batch_rows = -1;
-            h->open_filled.clear();
-            h->open_filled_rows = 0;
-        }
-    }
-    HIPCHK(hipGetLastError());
-    if (h->cfg.flags & COALA_FLAG_SYNC) HIPCHK(hipStreamSynchronize(s));
-    return COALA_OK;
-}
-
 int coala_cache_read_feature(coala_cache_t* h, float* out, const int64_t* idx, int64_t n, void* stream) {
-    return read_feature_impl(h, out, idx, n, stream, false, kPhaseBoth, nullptr, nullptr, 0, nullptr);
+    ReadCall c{kPhaseBoth, h, out, idx, n, (hipStream_t)stream};
+    c.force_dist = false;
+    return read_feature(c);
 }
 
 int coala_cache_serve(coala_cache_t* h, float* out, const int64_t* ids, int64_t n, void* stream) {
-    return read_feature_impl(h, out, ids, n, stream, true, kPhaseBoth, nullptr, nullptr, 0, nullptr);
+    ReadCall c{kPhaseBoth, h, out, ids, n, (hipStream_t)stream};
+    return read_feature(c);
 }
 
 int coala_cache_serve_probe(coala_cache_t* h, float* out, const int64_t* ids, int64_t n, void* stream) {
-    return read_feature_impl(h, out, ids, n, stream, true, kPhaseProbe, nullptr, nullptr, 0, nullptr);
+    ReadCall c{kPhaseProbe, h, out, ids, n, (hipStream_t)stream};
+    return read_feature(c);
 }
 
 int coala_cache_serve_probe_redirect(coala_cache_t* h, float* out, const int64_t* ids, int64_t n, const coala_row_redirect_t* redirect,
                                      void* stream) {
-    return read_feature_impl(h, out, ids, n, stream, true, kPhaseProbe, nullptr, nullptr, 0, redirect);
+    ReadCall c{kPhaseProbe, h, out, ids, n, (hipStream_t)stream};
+    c.redirect = redirect;
+    return read_feature(c);
 }
 
 // library-internal (coala_internal.h): the split-phase serve with events on its launches
 int coala_serve_probe_redirect_ev_(coala_cache_t* h, float* out, const int64_t* ids, int64_t n, const coala_row_redirect_t* redirect, void* stream,
                                    hipEvent_t begin_ev, hipEvent_t* rode) {
-    hipEvent_t r[2];
-    const int rc = read_feature_impl(h, out, ids, n, stream, true, kPhaseProbe, nullptr, nullptr, 0, redirect, begin_ev, nullptr, r);
-    if (rode) *rode = r[0];
+    ReadCall c{kPhaseProbe, h, out, ids, n, (hipStream_t)stream};
+    c.redirect = redirect;
+    c.ev_begin = begin_ev;
+    const int rc = read_feature(c);
+    if (rode) *rode = c.rode_begin;
     return rc;
 }
 int coala_serve_fill_ranges_ev_(coala_cache_t* h, float* out, const int64_t* ids, int64_t n, const int64_t* begins, const int64_t* ends, int n_ranges,
                                 void* stream, hipEvent_t end_ev, hipEvent_t* rode) {
-    hipEvent_t r[2];
-    const int rc = read_feature_impl(h, out, ids, n, stream, true, kPhaseFill, begins, ends, n_ranges, nullptr, nullptr, end_ev, r);
-    if (rode) *rode = r[1];
+    ReadCall c{kPhaseFill, h, out, ids, n, (hipStream_t)stream};
+    c.ranges = FillRanges{begins, ends, n_ranges};
+    c.ev_end = end_ev;
+    const int rc = read_feature(c);
+    if (rode) *rode = c.rode_end;
     return rc;
 }
 
 int coala_cache_serve_fill(coala_cache_t* h, float* out, const int64_t* ids, int64_t n, int64_t begin, int64_t end, void* stream) {
-    return read_feature_impl(h, out, ids, n, stream, true, kPhaseFill, &begin, &end, 1, nullptr);
+    ReadCall c{kPhaseFill, h, out, ids, n, (hipStream_t)stream};
+    c.ranges = FillRanges{&begin, &end, 1};
+    return read_feature(c);
 }
 
 int coala_cache_serve_fill_ranges(coala_cache_t* h, float* out, const int64_t* ids, int64_t n, const int64_t* begins, const int64_t* ends,
                                   int n_ranges, void* stream) {
-    return read_feature_impl(h, out, ids, n, stream, true, kPhaseFill, begins, ends, n_ranges, nullptr);
+    ReadCall c{kPhaseFill, h, out, ids, n, (hipStream_t)stream};
+    c.ranges = FillRanges{begins, ends, n_ranges};
+    return read_feature(c);
 }
 
 int coala_cache_serve_abort(coala_cache_t* h, void* stream) {
     if (!h) return fail(COALA_EINVAL, "null handle");
-    if (h->open_batch_rows < 0) return COALA_OK;
+    if (!h->batch.is_open()) return COALA_OK;
     HIPCHK(hipSetDevice(h->cfg.device));
     // nothing on the device to undo: the next probe starts a new generation and rewrites every verdict word it will read; rows
     // whose fill already ran are cached, the others are not
     (void)stream;
-    h->open_batch_rows = -1;
-    h->open_filled.clear();
-    h->open_filled_rows = 0;
+    h->batch.close();
     return COALA_OK;
 }
 
@@ -1854,19 +1929,10 @@ int coala_cache_route(coala_cache_t* h, const int64_t* idx, int64_t n, int n_par
     if (!node_out || !map_out || !counts_out || (n > 0 && !idx)) return fail(COALA_EINVAL, "null buffer");
     if (bucket_stride < 0) return fail(COALA_EINVAL, "negative bucket_stride");
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc_ = follow_stream(h, s)) return rc_;
+    if (int rc = enter(h, s)) return rc;
     const int64_t n_tiles = (n + kRouteTile - 1) / kRouteTile;
     const uint64_t need = (uint64_t)(n_tiles > 0 ? n_tiles : 1) * (uint64_t)n_parts;
-    if (need > h->wave_counts_cap) {
-        HIPCHK(hipStreamSynchronize(s));
-        if (h->wave_counts) HIPCHK(hipFree(h->wave_counts));
-        h->wave_counts = nullptr;
-        uint64_t cap = h->wave_counts_cap ? h->wave_counts_cap : 4096;
-        while (cap < need) cap *= 2;
-        HIPCHK(hipMalloc((void**)&h->wave_counts, cap * 4));
-        h->wave_counts_cap = cap;
-    }
+    if (int rc = grow((void**)&h->wave_counts, &h->wave_counts_cap, need, sizeof(uint32_t), s, 4096)) return rc;
     const int pshift = ilog2_exact((uint64_t)n_parts);
     const int blocks = (int)((n_tiles + 3) / 4);
     if (n_tiles > 0)
@@ -1876,9 +1942,7 @@ int coala_cache_route(coala_cache_t* h, const int64_t* idx, int64_t n, int n_par
     if (n_tiles > 0)
         hipLaunchKernelGGL(route_scatter_kernel, dim3(blocks), dim3(256), 0, s, idx, n, (uint32_t)n_parts, pshift, h->wave_counts,
                            h->route_bases, node_out, map_out, n_tiles);
-    HIPCHK(hipGetLastError());
-    if (h->cfg.flags & COALA_FLAG_SYNC) HIPCHK(hipStreamSynchronize(s));
-    return COALA_OK;
+    return leave(h, s);
 }
 
 int coala_cache_scatter_ranges(coala_cache_t* h, float* out, const float* src, const int64_t* map, const int64_t* begins,
@@ -1893,7 +1957,7 @@ int coala_cache_scatter_ranges(coala_cache_t* h, float* out, const float* src, c
     if (rows == 0) return COALA_OK;
     if (!out || !src || !map) return fail(COALA_EINVAL, "null buffer");
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = enter(h, s, false)) return rc;   // (touches nothing of the handle's on the device: no order to keep)
     const uint32_t dim = h->d.dim;
     const bool vec4 = (dim % 4 == 0) && aligned16(out) && aligned16(src);
     int rc = dispatch_geo(h->d.cache_dim, vec4, [&](auto geo) -> int {
@@ -1902,14 +1966,11 @@ int coala_cache_scatter_ranges(coala_cache_t* h, float* out, const float* src, c
         using G = Geo<CD, VEC>;
         return for_each_range_set(begins, ends, n_ranges, [&](const RangeSet& rs) -> int {
             const int64_t chunks = ((int64_t)rs.total + G::R - 1) / G::R;
-            hipLaunchKernelGGL((scatter_rows_kernel<CD, VEC>), dim3(grid_for(chunks, 4, 256 * 16)), dim3(256), 0, s, out, src, map, rs, dim);
+            hipLaunchKernelGGL((scatter_rows_kernel<CD, VEC>), dim3(grid1d(chunks, 4, 256 * 16)), dim3(256), 0, s, out, src, map, rs, dim);
             return COALA_OK;
         });
     });
-    if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    if (h->cfg.flags & COALA_FLAG_SYNC) HIPCHK(hipStreamSynchronize(s));
-    return COALA_OK;
+    return rc ? rc : leave(h, s);
 }
 
 int coala_cache_scatter(coala_cache_t* h, float* out, const float* src, const int64_t* map, int64_t n, void* stream) {
@@ -1928,15 +1989,12 @@ static int write_rows_impl(coala_cache_t* h, const int64_t* ids, int64_t n, cons
     if (h->cfg.n_gpus != 1 || (h->cfg.flags & (COALA_FLAG_DISTRIBUTED | COALA_FLAG_COLD_PARTITIONED)))
         return fail(COALA_EINVAL, "row writes need an isolated cache of one GPU (n_gpus=%d, flags=0x%x): a second cache over the same table would keep stale lines",
                     h->cfg.n_gpus, h->cfg.flags);
-    if (h->open_batch_rows >= 0)
-        return fail(COALA_EINVAL, "a batch of %lld rows is still open (%lld filled): finish its serve_fill calls or call coala_cache_serve_abort",
-                    (long long)h->open_batch_rows, (long long)h->open_filled_rows);
+    if (h->batch.is_open()) return h->batch.refuse_while_open();
     const bool elem_state = op == kOpAdagrad || op == kOpAdam;   // state tables of [num_rows, dim]
     if (n > 0 && (!ids || !src || (op >= kOpAdagrad && !state) || (op == kOpAdam && !ex.state2))) return fail(COALA_EINVAL, "null buffer");
     if (n == 0) return COALA_OK;
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc_ = follow_stream(h, s)) return rc_;
+    if (int rc = enter(h, s)) return rc;
     const CacheDev& d = h->d;
     const bool vec4 = (d.dim % 4 == 0) && aligned16(d.cold) && aligned16(src) && (!elem_state || aligned16(state)) &&
                       (op != kOpAdam || aligned16(ex.state2));
@@ -1947,7 +2005,7 @@ static int write_rows_impl(coala_cache_t* h, const int64_t* ids, int64_t n, cons
             using TAG = decltype(tag_c);
             const int64_t chunks = (n + TagGeo<TAG>::SPL - 1) / TagGeo<TAG>::SPL;
             // one wave per chunk up to 4096 waves behind a host tier (a wave has at most two rows of reads and writes on the link), 32768 on HBM
-            const dim3 grid(grid_for(chunks, 4, h->host_tier ? 1024 : 8192)), block(256);
+            const dim3 grid(grid1d(chunks, 4, h->host_tier ? 1024 : 8192)), block(256);
             auto k = op == kOpAssign    ? write_rows_kernel<CD, VEC, TAG, kOpAssign>
                      : op == kOpAdd     ? write_rows_kernel<CD, VEC, TAG, kOpAdd>
                      : op == kOpAdagrad ? write_rows_kernel<CD, VEC, TAG, kOpAdagrad>
@@ -1958,10 +2016,7 @@ static int write_rows_impl(coala_cache_t* h, const int64_t* ids, int64_t n, cons
         if (d.tag32) launch(uint32_t{}); else launch(uint64_t{});
         return COALA_OK;
     });
-    if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    if (h->cfg.flags & COALA_FLAG_SYNC) HIPCHK(hipStreamSynchronize(s));
-    return COALA_OK;
+    return rc ? rc : leave(h, s);
 }
 
 int coala_cache_write_rows(coala_cache_t* h, const int64_t* ids, int64_t n, const float* src, int mode, float alpha, void* stream) {
@@ -2004,8 +2059,7 @@ int coala_cache_color_counts(coala_cache_t* h, int32_t* dst, int32_t n_entries, 
     if (n_entries < 0 || n_entries > h->cfg.num_colors + 1) return fail(COALA_EINVAL, "n_entries=%d exceeds num_colors+1=%d", n_entries, h->cfg.num_colors + 1);
     if (!h->d.color_counters) { memset(dst, 0, (size_t)n_entries * 4); return COALA_OK; }
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc_ = follow_stream(h, s)) return rc_;
+    if (int rc = enter(h, s)) return rc;
     // staged through pinned memory owned by the handle: a D2H copy into pageable memory waits for every queue of the device
     // (measured: 11 ms per call when a prefetching loader had run ahead), this one only for `stream`
     if (!h->color_pin) HIPCHK(hipHostMalloc((void**)&h->color_pin, ((size_t)h->cfg.num_colors + 1) * 4, hipHostMallocDefault));
@@ -2023,8 +2077,7 @@ int coala_cache_color_counts_async(coala_cache_t* h, int32_t n_entries, void* st
     if (!h) return fail(COALA_EINVAL, "null argument");
     if (n_entries < 0 || n_entries > h->cfg.num_colors + 1) return fail(COALA_EINVAL, "n_entries=%d exceeds num_colors+1=%d", n_entries, h->cfg.num_colors + 1);
     if (h->color_pending >= 0) return fail(COALA_EINVAL, "a colour-counter snapshot is already pending: call coala_cache_color_counts_finish first");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc_ = follow_stream(h, (hipStream_t)stream)) return rc_;
+    if (int rc = enter(h, (hipStream_t)stream)) return rc;
     if (h->d.color_counters) {
         if (!h->color_pin_async) HIPCHK(hipHostMalloc((void**)&h->color_pin_async, ((size_t)h->cfg.num_colors + 1) * 4, hipHostMallocDefault));
         if (!h->color_ev) HIPCHK(hipEventCreateWithFlags(&h->color_ev, hipEventDisableTiming));
@@ -2069,8 +2122,7 @@ static int read_stats(coala_cache_t* h, hipStream_t s, uint64_t* hit, uint64_t* 
 
 int coala_cache_stats(coala_cache_t* h, uint64_t* hit, uint64_t* miss, uint64_t* range_errors, int reset, void* stream) {
     if (!h) return fail(COALA_EINVAL, "null handle");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc_ = follow_stream(h, (hipStream_t)stream)) return rc_;
+    if (int rc = enter(h, (hipStream_t)stream)) return rc;
     uint64_t v0, v1, v2;
     int rc = read_stats(h, (hipStream_t)stream, &v0, &v1, &v2, reset != 0);
     if (rc) return rc;
@@ -2083,8 +2135,7 @@ int coala_cache_stats(coala_cache_t* h, uint64_t* hit, uint64_t* miss, uint64_t*
 int coala_cache_dump(coala_cache_t* h, uint64_t* keys, uint32_t* set_cnt, uint32_t* color_meta, void* stream) {
     if (!h) return fail(COALA_EINVAL, "null handle");
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc_ = follow_stream(h, (hipStream_t)stream)) return rc_;
+    if (int rc = enter(h, s)) return rc;
     const uint64_t slots = h->d.num_sets * COALA_WAYS;
     HIPCHK(hipStreamSynchronize(s));
     if (keys) {

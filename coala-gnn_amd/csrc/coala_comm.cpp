@@ -241,7 +241,7 @@ struct InprocTransport : Transport {
     int size() override { return g->nranks; }
 };
 
-int grow(void** p, uint64_t* cap, uint64_t need, size_t elem, hipStream_t st) {
+int grow_workspace(void** p, uint64_t* cap, uint64_t need, size_t elem, hipStream_t st) {
     if (need <= *cap) return COALA_OK;
     HIPCHK(hipStreamSynchronize(st));
     if (*p) HIPCHK(hipFree(*p));
@@ -299,7 +299,7 @@ struct coala_comm {
     uint64_t ahead_calls = 0;
     // The workspaces (recv_ids, rows_send, node/map) are ordered by the stream the fetches are enqueued on.  A caller that moves to
     // another stream keeps that order: the new stream first waits (no host wait) for what the previous fetch enqueued on the old
-    // one -- the same rule as the cache handle's follow_stream.
+    // one -- the same rule as the cache handle's (enter, coala_cache.hip).
     hipStream_t order_stream = nullptr;
     bool order_set = false;
     hipEvent_t order_ev = nullptr;
@@ -647,14 +647,14 @@ static int fetch_impl(coala_cache_t* h, coala_comm_t* c, float* out, const int64
     if ((rc = follow_stream(c, st))) return rc;
     const uint64_t nb = (uint64_t)(n > 0 ? n : 1);
     if (!bucketed) {
-        if ((rc = grow((void**)&c->node, &c->node_cap, nb, sizeof(int64_t), st))) return rc;
-        if ((rc = grow((void**)&c->map, &c->map_cap, nb, sizeof(int64_t), st))) return rc;
-        if ((rc = grow((void**)&c->rows_recv, &c->rows_recv_cap, nb * (uint64_t)dim, sizeof(float), st))) return rc;
+        if ((rc = grow_workspace((void**)&c->node, &c->node_cap, nb, sizeof(int64_t), st))) return rc;
+        if ((rc = grow_workspace((void**)&c->map, &c->map_cap, nb, sizeof(int64_t), st))) return rc;
+        if ((rc = grow_workspace((void**)&c->rows_recv, &c->rows_recv_cap, nb * (uint64_t)dim, sizeof(float), st))) return rc;
     }
     // the usual step receives about as many ids as it sends: pre-size the owner-side buffers too, so that the grow after the
     // counts exchange (the one allocation that sits between collectives) only happens for skewed batches
-    if ((rc = grow((void**)&c->recv_ids, &c->recv_cap, nb + (nb >> 2), sizeof(int64_t), st))) return rc;
-    if ((rc = grow((void**)&c->rows_send, &c->rows_send_cap, (nb + (nb >> 2)) * (uint64_t)dim, sizeof(float), st))) return rc;
+    if ((rc = grow_workspace((void**)&c->recv_ids, &c->recv_cap, nb + (nb >> 2), sizeof(int64_t), st))) return rc;
+    if ((rc = grow_workspace((void**)&c->rows_send, &c->rows_send_cap, (nb + (nb >> 2)) * (uint64_t)dim, sizeof(float), st))) return rc;
     int64_t* send_cnt = c->counts_dev;
     int64_t* recv_cnt = c->counts_dev + G;
     int64_t* offsets = c->counts_dev + 2 * G; // [G+1]
@@ -699,8 +699,8 @@ static int fetch_impl(coala_cache_t* h, coala_comm_t* c, float* out, const int64
     if ((int64_t)acc != n) return broke(fail(COALA_ECOMM, "%s %zu ids for a batch of %lld", bucketed ? "the bucket counts sum to" : "route produced", acc, (long long)n));
     if (total_recv > 0x7FFFFFFFull) return broke(fail(COALA_ECOMM, "%zu ids routed to one owner in one step", total_recv));
     const uint64_t tr = total_recv ? total_recv : 1;
-    if ((rc = grow((void**)&c->recv_ids, &c->recv_cap, tr, sizeof(int64_t), st))) return broke(rc);
-    if ((rc = grow((void**)&c->rows_send, &c->rows_send_cap, tr * (uint64_t)dim, sizeof(float), st))) return broke(rc);
+    if ((rc = grow_workspace((void**)&c->recv_ids, &c->recv_cap, tr, sizeof(int64_t), st))) return broke(rc);
+    if ((rc = grow_workspace((void**)&c->rows_send, &c->rows_send_cap, tr * (uint64_t)dim, sizeof(float), st))) return broke(rc);
     // 4. ids to their owners (exact sizes); the own bucket is a device copy
     if ((rc = c->tr->all_to_all_v(node, scnt.data(), sdis.data(), c->recv_ids, rcnt.data(), rdis.data(), sizeof(int64_t), true, st)))
         return broke(rc);

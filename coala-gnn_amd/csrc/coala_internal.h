@@ -19,11 +19,36 @@ int coala_fail_(int code, const char* fmt, ...) __attribute__((format(printf, 2,
 constexpr int kBlock = 256; // threads per block
 constexpr int kWavesPerBlock = kBlock / 64;
 
+// blocks for n items at `block` items per block: at least one, at most `cap` (the cache's kernels: chunks or tiles at one per wave)
 inline int grid1d(int64_t n, int block, int cap) {
     int64_t g = (n + block - 1) / block;
     if (g < 1) g = 1;
     if (g > cap) g = cap;
     return (int)g;
+}
+
+// log2 of a power of two, -1 for every other value
+inline int ilog2_exact(uint64_t v) {
+    if (v == 0 || (v & (v - 1))) return -1;
+    int s = 0;
+    while ((1ull << s) != v) ++s;
+    return s;
+}
+
+// Device scratch *p of *cap elements that has to hold `need`: kept when it is large enough, else -- after everything enqueued on `st`, which
+// may still use it, has finished -- replaced by one of the capacity doubled (from `first`) until it fits.  The contents are not kept.  A
+// failure leaves *cap 0, so the next call tries again.
+inline int grow(void** p, uint64_t* cap, uint64_t need, size_t elem, hipStream_t st, uint64_t first = 1024) {
+    if (need <= *cap) return COALA_OK;
+    COALA_HIPCHK(hipStreamSynchronize(st));
+    uint64_t c = *cap ? *cap : first;
+    while (c < need) c *= 2;
+    *cap = 0;
+    if (*p) COALA_HIPCHK(hipFree(*p));
+    *p = nullptr;
+    COALA_HIPCHK(hipMalloc(p, c * elem));
+    *cap = c;
+    return COALA_OK;
 }
 
 // The split-phase serve calls with an event ON a launch instead of behind it (coala_cache.hip; used by the distributed fetch, coala_comm.cpp):

@@ -1741,25 +1741,6 @@ namespace {
 using RingInfo = coala_sampler::RingInfo;
 constexpr int kSlot = kPinParts + kMaxParts; // int64 words per ring slot
 
-int grow(void** p, uint64_t* cap, uint64_t need, size_t elem, hipStream_t st) {
-    if (need <= *cap) return COALA_OK;
-    HIPCHK(hipStreamSynchronize(st));
-    if (*p) HIPCHK(hipFree(*p));
-    *p = nullptr;
-    uint64_t c = *cap ? *cap : 1024;
-    while (c < need) c *= 2;
-    HIPCHK(hipMalloc(p, c * elem));
-    *cap = c;
-    return COALA_OK;
-}
-
-int ilog2_exact(uint64_t v) {
-    if (v == 0 || (v & (v - 1))) return -1;
-    int s = 0;
-    while ((1ull << s) != v) ++s;
-    return s;
-}
-
 // One sampling call, as its entry point hands it to sample_impl: its kind -- how a fixed layer picks its edges; the kinds exclude each
 // other --, the arguments every entry point has, in the ABI's order, and below them the kinds' payloads, which an entry point sets by name.
 enum class Kind { uniform, weighted, labor, rel, walk, temporal };

@@ -12,6 +12,53 @@ for p in (ROOT, os.path.join(ROOT, "coala-gnn_amd"), os.path.join(ROOT, "tests")
         sys.path.insert(0, p)
 
 
+def many_ranges_and_many_fills(cache, orc, oracle, feat, dim, bad_total, num_colors, where):
+    """Two split serves beyond what the random draws reach (at most nine ranges and three fill calls per batch), on a distributed cache
+    after its random batches.  A: one fill call of 130 ranges -- more than a launch's range set holds (64), so three launches, the call's
+    end on the last.  B: a redirected slice and ten fill calls -- more than the batch has ticket counters for the dynamic deal of tiles
+    (8), so the last two take the static deal.  num_colors: None when the cache tracks no colours."""
+    import torch
+    rng = np.random.default_rng(7)
+
+    def check(idx, got, tag):
+        orc.read_feature(idx, oracle.SCHED_HITS_FIRST, want_rows=False)
+        assert got.tobytes() == feat[idx].tobytes(), f"{where} {tag}"
+        assert cache.stats() == (orc.hit_cnt, orc.miss_cnt, bad_total), f"{where} {tag} (dim {dim})"
+        keys, cnt, meta = cache.dump()
+        assert np.array_equal(keys, orc.keys()) and np.array_equal(cnt, orc.set_cnt()), f"{where} {tag}"
+        if num_colors is not None:
+            cc = np.zeros(num_colors + 1, dtype=np.int32)
+            cache.get_cache_data(cc.ctypes.data, num_colors + 1)
+            assert np.array_equal(cc, orc.color_counters()) and np.array_equal(meta.astype(np.uint64), orc.color_meta()), f"{where} {tag}"
+
+    n = 390
+    idx = rng.choice(len(feat), size=n, replace=False).astype(np.int64)
+    d_idx = torch.from_numpy(idx).cuda()
+    out = torch.full((n, dim), -2.0, dtype=torch.float32, device="cuda")
+    cache.serve_probe(out.data_ptr(), d_idx.data_ptr(), n)
+    ranges = [(b, b + 3) for b in range(0, n, 3)]
+    rng.shuffle(ranges)
+    cache.serve_fill_ranges(out.data_ptr(), d_idx.data_ptr(), n, ranges)
+    check(idx, out.cpu().numpy(), "batch A (130 ranges in one fill)")
+
+    n, lo, hi = 400, 100, 200
+    idx = rng.choice(len(feat), size=n, replace=False).astype(np.int64)
+    d_idx = torch.from_numpy(idx).cuda()
+    out = torch.full((n, dim), -2.0, dtype=torch.float32, device="cuda")
+    perm = rng.permutation(hi - lo).astype(np.int64)
+    d_map = torch.from_numpy(perm).cuda()
+    other = torch.full((hi - lo, dim), -4.0, dtype=torch.float32, device="cuda")
+    cache.serve_probe_redirect(out.data_ptr(), d_idx.data_ptr(), n, lo, hi, other.data_ptr(), d_map.data_ptr())
+    ranges = [(b, b + 20) for b in range(0, n, 20)]
+    rng.shuffle(ranges)
+    for call in range(10):
+        cache.serve_fill_ranges(out.data_ptr(), d_idx.data_ptr(), n, ranges[2 * call:2 * call + 2])
+    got = out.cpu().numpy().copy()
+    assert np.all(got[lo:hi] == -2.0), f"{where} batch B: a redirected row was also written to the batch's own output"
+    got[lo:hi] = other.cpu().numpy()[perm]
+    check(idx, got, "batch B (ten fills, redirect)")
+
+
 def run(P, oracle, tmp_path, seed, cases=12):
     import torch
     from _util import ColorFiles, PinnedTable
@@ -97,6 +144,8 @@ def run(P, oracle, tmp_path, seed, cases=12):
                 cc = np.zeros(num_colors + 1, dtype=np.int32)
                 cache.get_cache_data(cc.ctypes.data, num_colors + 1)
                 assert np.array_equal(cc, orc.color_counters()) and np.array_equal(meta.astype(np.uint64), orc.color_meta())
+        if distributed:
+            many_ranges_and_many_fills(cache, orc, oracle, feat, dim, bad_total, num_colors if with_color else None, f"seed {seed} case {case}")
         cache.close()
         table.close()
 
