@@ -48,7 +48,8 @@ class NVShmem_Tensor_Manager(object):
 
 
 def _round_slices(cnt, dis, rounds, skip):
-    """[(begin, end)] per round: slice k of every peer's segment [dis[p], dis[p] + cnt[p]), peer `skip` left out."""
+    """[(begin, end)] per round: slice k of every peer's segment [dis[p], dis[p] + cnt[p]), peer `skip` left out.
+    The native call's Segments::slice (coala_comm.cpp) is the same rule and has to stay so: the two exchanges are interchangeable."""
     out = []
     for k in range(rounds):
         out.append([(dis[p] + cnt[p] * k // rounds, dis[p] + cnt[p] * (k + 1) // rounds) if p != skip else (dis[p], dis[p])
@@ -353,6 +354,9 @@ class NativeExchange(object):
         else:
             self._capi.check(self._lib.coala_cache_fetch_distributed(ops._h, self._h, int(out_ptr) or None, int(idx_ptr) or None, int(n),
                                                                       current_stream()))
+        self._read_last_counts()
+
+    def _read_last_counts(self):
         send = (self._C.c_int64 * self.world)()
         recv = (self._C.c_int64 * self.world)()
         self._lib.coala_comm_last_counts(self._h, send, recv)
@@ -381,10 +385,7 @@ class NativeExchange(object):
         else:
             self._capi.check(self._lib.coala_cache_fetch_distributed_bucketed(ops._h, self._h, int(out_ptr) or None, int(idx_ptr) or None, int(n),
                                                                                int(counts_ptr), current_stream()))
-        send = (self._C.c_int64 * self.world)()
-        recv = (self._C.c_int64 * self.world)()
-        self._lib.coala_comm_last_counts(self._h, send, recv)
-        self.last_send_counts, self.last_recv_counts = list(send), list(recv)
+        self._read_last_counts()
 
     # SSD_GNN_NVSHMEM_Cache.send_requests / read_feature keep the reference's two-call sequence: the second call does it all
     def send_requests(self, ops, idx_ptr, n, req_ptr, max_index):
@@ -407,11 +408,14 @@ class NativeExchange(object):
 
 
 def owner_counts_present(mgr, batch):
-    """Will fetch_feature take the bucketed road for this batch (the sampler delivered the input nodes bucketed by owner)?"""
+    """The per-owner counts of a batch for which fetch_feature takes the bucketed road (the sampler delivered the input nodes bucketed
+    by owner: NeighborSampler(bucket_by_owner=G)), else None."""
     if mgr.exchange is None or not hasattr(mgr.exchange, "fetch_bucketed") or len(batch) < 3 or not batch[2]:
-        return False
+        return None
     oc = getattr(batch[2][0], "owner_counts", None)
-    return oc is not None and oc.numel() == mgr.MPI_comm_manager.local_size and batch[2][0].src_nodes is batch[0]
+    if oc is not None and oc.numel() == mgr.MPI_comm_manager.local_size and batch[2][0].src_nodes is batch[0]:
+        return oc
+    return None
 
 
 SAMPLER_ITEM_LIMIT = 8192 * 1024   # items one sampled layer may hold (COALA_GNN.sampler.ITEM_LIMIT)
@@ -527,7 +531,10 @@ class COALA_GNN_Manager(object):
         fetch_start = time.time()
         ev_pair = None
         self.last_done_event = None
-        native_ev = (not self.sync_on_return) and index_size > 0 and self._native_exchange_events and owner_counts_present(self, batch)
+        # the sampler may have delivered the ids already bucketed by owner (NeighborSampler(bucket_by_owner=G)): the native exchange
+        # then skips its routing pass and receives the rows in place
+        owner_counts = owner_counts_present(self, batch)
+        native_ev = (not self.sync_on_return) and index_size > 0 and self._native_exchange_events and owner_counts is not None
         self._fetch_no += 1
         sampled = self.timing_stride >= 1 and self._fetch_no % self.timing_stride == 0
         if native_ev:
@@ -536,13 +543,6 @@ class COALA_GNN_Manager(object):
             ev_pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev_pair[0].record()
 
-        # the sampler may have delivered the ids already bucketed by owner (NeighborSampler(bucket_by_owner=G)): the native exchange
-        # then skips its routing pass and receives the rows in place
-        owner_counts = None
-        if self.exchange is not None and hasattr(self.exchange, "fetch_bucketed") and len(batch) >= 3 and batch[2]:
-            oc = getattr(batch[2][0], "owner_counts", None)
-            if oc is not None and oc.numel() == self.MPI_comm_manager.local_size and batch[2][0].src_nodes is batch[0]:
-                owner_counts = oc
         if owner_counts is not None:
             return_torch = torch.empty([index_size, self.dim], dtype=torch.float, device=self.device)
             ticket = getattr(batch[2][0], "counts_ticket", None)   # the count exchange was issued ahead (loader, counts_ahead=True)

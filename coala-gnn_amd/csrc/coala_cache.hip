@@ -1286,14 +1286,12 @@ struct coala_cache {
     // profiling
     struct EvPair { hipEvent_t a, b; int kind; uint64_t rows; };
     std::vector<EvPair> ev_live;
-    std::vector<hipEvent_t> ev_pool;
+    EventPool ev_pool;
     coala_cache_profile_t prof{};
     hipStream_t last_stream = nullptr;    // stream of the last bracketed launch (for the empty-bracket calibration)
     // The handle's tables and scratch are ordered by the stream its calls are enqueued on.  A caller that moves to another stream
     // keeps that order: the new stream first waits for what the handle enqueued last on the old one (enter).
-    hipStream_t order_stream = nullptr;
-    bool order_set = false;
-    hipEvent_t order_ev = nullptr;
+    StreamOrder order;
     uint64_t table_bytes = 0;
     LaunchShape shape;                    // K1 / K2 launch shapes (launch_shape)
     bool host_tier = false;               // the cold table is host memory (behind the host link)
@@ -1320,16 +1318,7 @@ namespace {
 // what the handle enqueued last, on whichever stream that was ...
 int enter(coala_cache* h, hipStream_t s, bool follow = true) {
     HIPCHK(hipSetDevice(h->cfg.device));
-    if (!follow) return COALA_OK;
-    if (h->order_set && h->order_stream != s) {
-        if (!h->order_ev) HIPCHK(hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
-        // (a stream the caller has destroyed in the meantime has nothing left to wait for)
-        if (hipEventRecord(h->order_ev, h->order_stream) == hipSuccess) HIPCHK(hipStreamWaitEvent(s, h->order_ev, 0));
-        else (void)hipGetLastError();
-    }
-    h->order_stream = s;
-    h->order_set = true;
-    return COALA_OK;
+    return follow ? h->order.follow(s) : COALA_OK;
 }
 
 // ... and how one that launched kernels ends: a launch that failed is reported, and a COALA_FLAG_SYNC handle waits for its work.
@@ -1350,17 +1339,6 @@ int ensure_scratch(coala_cache* h, uint64_t n, hipStream_t s) {
     return grow((void**)&h->d.miss_list, &list_cap, list_words, sizeof(uint32_t), s, list_words);
 }
 
-hipEvent_t take_event(coala_cache* h) {
-    if (!h->ev_pool.empty()) {
-        hipEvent_t e = h->ev_pool.back();
-        h->ev_pool.pop_back();
-        return e;
-    }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
-}
-
 void drain_events(coala_cache* h) {
     for (auto& p : h->ev_live) {
         float ms = 0.f;
@@ -1368,8 +1346,8 @@ void drain_events(coala_cache* h) {
             if (p.kind == 0) { h->prof.gather_ms += ms; h->prof.gather_launches++; h->prof.gather_rows += p.rows; }
             else { h->prof.fill_ms += ms; h->prof.fill_launches++; }
         }
-        h->ev_pool.push_back(p.a);
-        h->ev_pool.push_back(p.b);
+        h->ev_pool.give(p.a);
+        h->ev_pool.give(p.b);
     }
     h->ev_live.clear();
 }
@@ -1384,7 +1362,7 @@ struct ProfScope {
         on = (h->cfg.flags & COALA_FLAG_PROFILE) != 0;
         if (on) {
             if (h->ev_live.size() >= 8192) drain_events(h);
-            a = take_event(h); b = take_event(h);
+            a = h->ev_pool.take(); b = h->ev_pool.take();
             on = a && b;
             if (on) h->last_stream = s;
         }
@@ -1788,8 +1766,7 @@ int coala_cache_destroy(coala_cache_t* h) {
     if (!h) return COALA_OK;
     (void)hipSetDevice(h->cfg.device);
     (void)hipDeviceSynchronize();
-    drain_events(h);
-    for (auto e : h->ev_pool) (void)hipEventDestroy(e);
+    drain_events(h);   // (the pool's events, and the stream order's, go with the handle)
     for (auto e : h->fev)
         if (e) (void)hipEventDestroy(e);
     CacheDev& d = h->d;
@@ -1801,7 +1778,6 @@ int coala_cache_destroy(coala_cache_t* h) {
     if (h->color_pin) (void)hipHostFree(h->color_pin);
     if (h->color_pin_async) (void)hipHostFree(h->color_pin_async);
     if (h->color_ev) (void)hipEventDestroy(h->color_ev);
-    if (h->order_ev) (void)hipEventDestroy(h->order_ev);
     delete h;
     return COALA_OK;
 }
@@ -2165,14 +2141,14 @@ int coala_cache_profile(coala_cache_t* h, coala_cache_profile_t* out, int reset)
     if (h->cfg.flags & COALA_FLAG_PROFILE) { // empty brackets on the same stream: the cost of the measurement itself
         std::vector<float> gaps;
         for (int i = 0; i < 16; ++i) {
-            hipEvent_t a = take_event(h), b = take_event(h);
+            hipEvent_t a = h->ev_pool.take(), b = h->ev_pool.take();
             if (!a || !b) break;
             float ms = 0.f;
             if (hipEventRecord(a, h->last_stream) == hipSuccess && hipEventRecord(b, h->last_stream) == hipSuccess &&
                 hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess)
                 gaps.push_back(ms);
-            h->ev_pool.push_back(a);
-            h->ev_pool.push_back(b);
+            h->ev_pool.give(a);
+            h->ev_pool.give(b);
         }
         if (!gaps.empty()) {
             std::sort(gaps.begin(), gaps.end());

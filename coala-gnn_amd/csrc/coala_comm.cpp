@@ -199,8 +199,8 @@ bool peer_readable(coala_comm_group* g, int mine, int theirs) {
 struct InprocTransport : Transport {
     coala_comm_group* g = nullptr;
     int device = -1;
-    int exchange(const void* send, const size_t* scnt, const size_t* sdis, void* recv, const size_t* rcnt, const size_t* rdis,
-                 size_t elem_bytes, bool include_self, hipStream_t st) {
+    int all_to_all_v(const void* send, const size_t* scnt, const size_t* sdis, void* recv, const size_t* rcnt, const size_t* rdis,
+                     size_t elem_bytes, bool include_self, hipStream_t st) override {
         auto& me = g->slot[rank];
         me.send = send;
         me.scnt = scnt;
@@ -231,11 +231,7 @@ struct InprocTransport : Transport {
     int all_to_all_i64(const int64_t* send_dev, int64_t* recv_dev, hipStream_t st) override {
         std::vector<size_t> one((size_t)nranks, 1), dis((size_t)nranks);
         for (int p = 0; p < nranks; ++p) dis[p] = (size_t)p;
-        return exchange(send_dev, one.data(), dis.data(), recv_dev, one.data(), dis.data(), sizeof(int64_t), true, st);
-    }
-    int all_to_all_v(const void* send, const size_t* scnt, const size_t* sdis, void* recv, const size_t* rcnt, const size_t* rdis,
-                     size_t elem_bytes, bool include_self, hipStream_t st) override {
-        return exchange(send, scnt, sdis, recv, rcnt, rdis, elem_bytes, include_self, st);
+        return all_to_all_v(send_dev, one.data(), dis.data(), recv_dev, one.data(), dis.data(), sizeof(int64_t), true, st);
     }
     void abort() override { g->abort(); }
     int size() override { return g->nranks; }
@@ -258,6 +254,30 @@ int grow_workspace(void** p, uint64_t* cap, uint64_t need, size_t elem, hipStrea
     return COALA_OK;
 }
 
+struct Range { size_t begin, end; };
+
+// Who sends how many ids to whom in one fetch, and how every segment is cut into K rounds.  Two sides: kServed = the batch this rank serves as
+// an owner, the segments it received in source-rank order (positions of recv_ids / rows_send); kRequested = this rank's own batch in bucket
+// order (positions of node / rows_recv).
+struct Segments {
+    enum Side { kServed, kRequested };
+    int me = 0, K = 1;
+    bool loop = false; // self-loopback: no own-shard bypass, the own segment is a peer's like any other
+    std::vector<size_t> scnt, sdis, rcnt, rdis; // per peer: ids this rank sends to it / receives from it, and where its segment starts
+    size_t total_send = 0, total_recv = 0;
+    // the own segment never enters the exchange: its rows go straight from the probe and the fill into `out`
+    bool bypassed(int p) const { return p == me && !loop; }
+    // Round k of peer p's segment on either side.  A bypassed own segment is empty in every round of the exchange; `fill` asks for what the
+    // cold fill of round k covers instead, where it is whole in the last round: nobody waits for it on a link.  The same rule as
+    // _round_slices (COALA_GNN_Manager.py), which the torch exchange cuts its rounds with, and it has to stay so.
+    Range slice(Side side, int p, int k, bool fill = false) const {
+        const size_t cnt = side == kServed ? rcnt[p] : scnt[p], dis = side == kServed ? rdis[p] : sdis[p];
+        const size_t a = dis + cnt * (size_t)k / (size_t)K, b = dis + cnt * (size_t)(k + 1) / (size_t)K;
+        if (!bypassed(p)) return {a, b};
+        return (fill && k == K - 1) ? Range{dis, dis + cnt} : Range{a, a};
+    }
+};
+
 } // namespace
 
 struct coala_comm {
@@ -267,23 +287,19 @@ struct coala_comm {
     hipStream_t cs = nullptr;       // the communication stream of this rank
     hipEvent_t ev_fill[kMaxRounds] = {}, ev_x[kMaxRounds] = {};
     // workspace (device), grown on demand, persistent across steps
-    int64_t *node = nullptr, *map = nullptr;
-    uint64_t node_cap = 0, map_cap = 0;
-    int64_t* recv_ids = nullptr;
-    uint64_t recv_cap = 0;
+    int64_t *node = nullptr, *map = nullptr, *recv_ids = nullptr;
+    uint64_t node_cap = 0, map_cap = 0, recv_cap = 0;
     float *rows_send = nullptr, *rows_recv = nullptr;
     uint64_t rows_send_cap = 0, rows_recv_cap = 0; // in floats
     int64_t* counts_dev = nullptr;                 // [3G+1]: send counts, recv counts, offsets
     int64_t* counts_host = nullptr;                // pinned [2G]
-    // last step, for tests / diagnostics
-    std::vector<int64_t> last_send, last_recv;
+    Segments seg;                                  // the plan of the last fetch (its counts: coala_comm_last_counts)
     // profiling of the row exchange (coala_comm_profile)
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_live;
-    std::vector<hipEvent_t> prof_pool;
+    EventPool prof_pool;
     coala_comm_profile_t prof{};
     bool broken = false;
-    bool loopback = false;          // coala_comm_set_self_loopback
     // coala_comm_fetch_events: begin / end events of a bucketed fetch without packets of their own on the caller's stream; a ring of triples
     // (begin on the probe's launch, end on the last fill launch of the caller's stream, end behind the last row round on the communicator's stream)
     int fetch_events = 0;           // 0 off, 1 end events only, 2 begin event too (coala_comm_fetch_events)
@@ -299,17 +315,29 @@ struct coala_comm {
     uint64_t ahead_calls = 0;
     // The workspaces (recv_ids, rows_send, node/map) are ordered by the stream the fetches are enqueued on.  A caller that moves to
     // another stream keeps that order: the new stream first waits (no host wait) for what the previous fetch enqueued on the old
-    // one -- the same rule as the cache handle's (enter, coala_cache.hip).
-    hipStream_t order_stream = nullptr;
-    bool order_set = false;
-    hipEvent_t order_ev = nullptr;
+    // one -- the cache handle's rule (StreamOrder, coala_internal.h).
+    StreamOrder order;
 };
 
 namespace {
 
-int finish_create(coala_comm* c) {
-    c->rank = c->tr->rank;
-    c->nranks = c->tr->nranks;
+// How both constructors begin: the handle around its transport (null, both freed, when the host is out of memory) ...
+coala_comm* new_comm(Transport* t, int rank, int nranks, int device) {
+    coala_comm* c = new (std::nothrow) coala_comm();
+    if (!c || !t) {
+        delete c;
+        delete t;
+        return nullptr;
+    }
+    c->tr = t;
+    c->device = device;
+    c->rank = t->rank = rank;
+    c->nranks = t->nranks = nranks;
+    return c;
+}
+
+// ... and what they give it once the transport stands: stream, events, workspaces.
+int equip(coala_comm* c) {
     if (const char* e = getenv("COALA_EXCHANGE_ROUNDS")) {
         const int r = atoi(e);
         if (r >= 1 && r <= kMaxRounds) c->rounds = r;
@@ -324,33 +352,16 @@ int finish_create(coala_comm* c) {
         c->cs = nullptr;
         if (hipStreamCreateWithFlags(&c->cs, hipStreamNonBlocking) != hipSuccess) return fail(COALA_EHIP, "hipStreamCreate failed");
     }
-    for (int k = 0; k < kMaxRounds; ++k)
-        if (hipEventCreateWithFlags(&c->ev_fill[k], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_x[k], hipEventDisableTiming) != hipSuccess)
-            return fail(COALA_EHIP, "hipEventCreate failed");
-    if (hipMalloc((void**)&c->counts_dev, (3 * (size_t)c->nranks + 1) * sizeof(int64_t)) != hipSuccess ||
-        hipHostMalloc((void**)&c->counts_host, 2 * (size_t)c->nranks * sizeof(int64_t)) != hipSuccess)
-        return fail(COALA_ENOMEM, "communicator workspace allocation failed");
-    c->last_send.assign(c->nranks, 0);
-    c->last_recv.assign(c->nranks, 0);
-    const size_t ring_words = (size_t)coala_comm::kCountsRing * 2 * (size_t)c->nranks;
-    if (hipMalloc((void**)&c->ahead_dev, ring_words * sizeof(int64_t)) != hipSuccess ||
-        hipHostMalloc((void**)&c->ahead_host, ring_words * sizeof(int64_t)) != hipSuccess)
-        return fail(COALA_ENOMEM, "communicator workspace allocation failed");
-    for (int k = 0; k < coala_comm::kCountsRing; ++k)
-        if (hipEventCreateWithFlags(&c->ahead_ev[k], hipEventDisableTiming) != hipSuccess) return fail(COALA_EHIP, "hipEventCreate failed");
-    return COALA_OK;
-}
-
-int follow_stream(coala_comm* c, hipStream_t s) {
-    if (c->order_set && c->order_stream != s) {
-        if (!c->order_ev) HIPCHK(hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming));
-        // (a stream the caller has destroyed in the meantime has nothing left to wait for)
-        if (hipEventRecord(c->order_ev, c->order_stream) == hipSuccess) HIPCHK(hipStreamWaitEvent(s, c->order_ev, 0));
-        else (void)hipGetLastError();
+    for (int k = 0; k < 2 * kMaxRounds + coala_comm::kCountsRing; ++k) {
+        hipEvent_t* e = k < kMaxRounds ? &c->ev_fill[k] : k < 2 * kMaxRounds ? &c->ev_x[k - kMaxRounds] : &c->ahead_ev[k - 2 * kMaxRounds];
+        if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return fail(COALA_EHIP, "hipEventCreate failed");
     }
-    c->order_stream = s;
-    c->order_set = true;
+    for (auto* v : {&c->seg.scnt, &c->seg.sdis, &c->seg.rcnt, &c->seg.rdis}) v->assign(c->nranks, 0);
+    const size_t ring_words = (size_t)coala_comm::kCountsRing * 2 * (size_t)c->nranks;
+    if (hipMalloc((void**)&c->counts_dev, (3 * (size_t)c->nranks + 1) * sizeof(int64_t)) != hipSuccess ||
+        hipHostMalloc((void**)&c->counts_host, 2 * (size_t)c->nranks * sizeof(int64_t)) != hipSuccess ||
+        hipMalloc((void**)&c->ahead_dev, ring_words * sizeof(int64_t)) != hipSuccess || hipHostMalloc((void**)&c->ahead_host, ring_words * sizeof(int64_t)) != hipSuccess)
+        return fail(COALA_ENOMEM, "communicator workspace allocation failed");
     return COALA_OK;
 }
 
@@ -358,21 +369,288 @@ void drain_profile(coala_comm* c) {
     for (auto& p : c->prof_live) {
         float ms = 0.f;
         if (hipEventSynchronize(p.second) == hipSuccess && hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) c->prof.rows_ms += ms;
-        c->prof_pool.push_back(p.first);
-        c->prof_pool.push_back(p.second);
+        c->prof_pool.give(p.first);
+        c->prof_pool.give(p.second);
     }
     c->prof_live.clear();
 }
 
-hipEvent_t take_timing_event(coala_comm* c) {
-    if (!c->prof_pool.empty()) {
-        hipEvent_t e = c->prof_pool.back();
-        c->prof_pool.pop_back();
-        return e;
+// A communicator that went through abandon() takes no further calls.
+int refuse_abandoned(const coala_comm* c) {
+    return c->broken ? fail(COALA_ECOMM, "this communicator failed in an earlier fetch and was aborted: destroy it") : COALA_OK;
+}
+
+// The one way out of a call that fails locally once its peers may be inside (or about to enter) a collective this rank will not join: the
+// transport is aborted, so that they error out instead of waiting for this rank.  -> code
+int abandon(coala_comm* c, int code) {
+    c->broken = true;
+    c->tr->abort();
+    return code;
+}
+
+// Slot of the counts-ahead ring that ticket `t` uses: device [2G] (send counts, recv counts), its pinned host copy, the event behind that copy.
+struct CountsSlot { int64_t *dev, *host; hipEvent_t ev; };
+CountsSlot counts_slot(const coala_comm* c, uint64_t t) {
+    const size_t s = (size_t)(t % coala_comm::kCountsRing), words = s * 2 * (size_t)c->nranks;
+    return {c->ahead_dev + words, c->ahead_host + words, c->ahead_ev[s]};
+}
+
+// Slot of the fetch-event ring that call number `call` uses: {begin, end on the caller's stream, end on the communicator's}, created on first
+// use; nullptr when that fails.
+hipEvent_t* fetch_event_slot(coala_comm* c, uint64_t call) {
+    if (c->fev.empty()) c->fev.assign(3 * (size_t)coala_comm::kFetchRing, nullptr);
+    hipEvent_t* slot = c->fev.data() + 3 * (size_t)(call % coala_comm::kFetchRing);
+    for (int k = 0; k < 3; ++k)
+        if (!slot[k] && hipEventCreate(&slot[k]) != hipSuccess) return nullptr;
+    return slot;
+}
+
+// ------------------------------------------------------------------------------------------------------------ the fetch
+struct FetchCall {
+    coala_cache_t* h; coala_comm* c; float* out; const int64_t* idx; int64_t n; hipStream_t st;
+    // device [G], not null: idx is already bucketed by owner -- the batch in bucket order is idx itself, the map is the identity, the rows of every
+    // peer are received straight into `out` and nothing is un-permuted.  Null: route here, into the communicator's node / map / rows_recv.
+    const int64_t* bucket_counts_dev = nullptr;
+    // host [2G], not null: the counts were exchanged ahead (coala_comm_counts_begin) -- no count exchange, no host synchronisation in this call
+    const int64_t* counts_host = nullptr;
+    // check_call: what the steps share
+    int G = 0, me = 0, K = 1; // K: row-exchange rounds of this fetch
+    int64_t dim = 0;
+    bool bucketed = false, loop = false, exchange_rows = false;
+    // Events of this fetch.  Every hipEventRecord on the caller's stream is one more barrier packet between the kernels of a saturated stream
+    // (6-12 us each: DESIGN.md section 6), so whatever can ride ON a launch does: the hand-over events of the fill rounds always, and -- opt-in,
+    // bucketed fetches: coala_comm_fetch_events -- the begin / end events a caller needs for timing and for its consumer's stream.
+    hipEvent_t ev_begin = nullptr, ev_end_st = nullptr, ev_end_cs = nullptr; // choose_events; ev_end_st set = this fetch hands events out
+    hipEvent_t fill_evs[kMaxRounds] = {}, x_evs[kMaxRounds] = {}; // what round k of the rows waits for / what it leaves behind
+};
+
+// 1. Everything that can be refused without touching the device.
+int check_call(FetchCall& f) {
+    if (!f.h || !f.c) return fail(COALA_EINVAL, "null handle");
+    coala_comm* c = f.c;
+    c->last_ev[0] = c->last_ev[1] = c->last_ev[2] = nullptr;
+    if (int rc = refuse_abandoned(c)) return rc;
+    if (f.n < 0 || f.n > 0x7FFFFFFFll || (f.n > 0 && (!f.out || !f.idx))) return fail(COALA_EINVAL, "bad batch");
+    coala_cache_geometry_t geo;
+    if (int rc = coala_cache_geometry(f.h, &geo)) return rc;
+    f.G = c->nranks, f.me = c->rank, f.dim = coala_cache_row_dim(f.h);
+    f.bucketed = f.bucket_counts_dev != nullptr;
+    f.loop = c->tr->self_loopback;
+    f.exchange_rows = f.G > 1 || f.loop; // a lone rank without loopback has nobody to exchange rows with: one fill round, no row rounds
+    f.K = f.exchange_rows ? c->rounds : 1;
+    return COALA_OK;
+}
+
+// 2. Behind whatever the previous fetch enqueued, on whichever stream; workspaces for a batch of n.
+int follow_and_presize(FetchCall& f) {
+    coala_comm* c = f.c;
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = c->order.follow(f.st)) return rc;
+    const uint64_t nb = (uint64_t)(f.n > 0 ? f.n : 1), dim = (uint64_t)f.dim;
+    if (!f.bucketed) {
+        if (int rc = grow_workspace((void**)&c->node, &c->node_cap, nb, sizeof(int64_t), f.st)) return rc;
+        if (int rc = grow_workspace((void**)&c->map, &c->map_cap, nb, sizeof(int64_t), f.st)) return rc;
+        if (int rc = grow_workspace((void**)&c->rows_recv, &c->rows_recv_cap, nb * dim, sizeof(float), f.st)) return rc;
     }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
+    // the usual step receives about as many ids as it sends: pre-size the owner-side buffers too, so that the grow after the
+    // counts exchange (the one allocation that sits between collectives) only happens for skewed batches
+    if (int rc = grow_workspace((void**)&c->recv_ids, &c->recv_cap, nb + (nb >> 2), sizeof(int64_t), f.st)) return rc;
+    return grow_workspace((void**)&c->rows_send, &c->rows_send_cap, (nb + (nb >> 2)) * dim, sizeof(float), f.st);
+}
+
+// 3. Bucket by owner (stable), packed layout -- unless the sampler already delivered the ids that way.  counts_dev: [G] send counts, [G] recv
+//    counts, [G+1] offsets.
+int bucket_ids(FetchCall& f) {
+    coala_comm* c = f.c;
+    if (!f.bucketed) return coala_cache_route(f.h, f.idx, f.n, f.G, 0, c->node, c->map, c->counts_dev, c->counts_dev + 2 * f.G, f.st);
+    if (!f.counts_host) HIPCHK(hipMemcpyAsync(c->counts_dev, f.bucket_counts_dev, (size_t)f.G * sizeof(int64_t), hipMemcpyDeviceToDevice, f.st));
+    return COALA_OK;
+}
+
+// 4. Counts: every rank tells every owner how many ids follow; then the one host read of the step.
+int exchange_counts(FetchCall& f) {
+    coala_comm* c = f.c;
+    if (f.counts_host) return COALA_OK;
+    if (int rc = c->tr->all_to_all_i64(c->counts_dev, c->counts_dev + f.G, f.st)) return rc;
+    if (hipMemcpyAsync(c->counts_host, c->counts_dev, 2 * (size_t)f.G * sizeof(int64_t), hipMemcpyDeviceToHost, f.st) != hipSuccess ||
+        hipStreamSynchronize(f.st) != hipSuccess)
+        return fail(COALA_EHIP, "reading the exchange counts failed: %s", hipGetErrorString(hipGetLastError()));
+    f.counts_host = c->counts_host;
+    return COALA_OK;
+}
+
+// 5. The segments of this fetch; the counts must add up to the batch.
+int plan_segments(FetchCall& f) {
+    Segments& s = f.c->seg;
+    s.me = f.me, s.K = f.K, s.loop = f.loop, s.total_send = s.total_recv = 0;
+    for (int p = 0; p < f.G; ++p) {
+        s.scnt[p] = (size_t)f.counts_host[p], s.rcnt[p] = (size_t)f.counts_host[f.G + p];
+        s.sdis[p] = s.total_send, s.rdis[p] = s.total_recv;
+        s.total_send += s.scnt[p], s.total_recv += s.rcnt[p];
+    }
+    if ((int64_t)s.total_send != f.n)
+        return fail(COALA_ECOMM, "%s %zu ids for a batch of %lld", f.bucketed ? "the bucket counts sum to" : "route produced", s.total_send, (long long)f.n);
+    if (s.total_recv > 0x7FFFFFFFull) return fail(COALA_ECOMM, "%zu ids routed to one owner in one step", s.total_recv);
+    return COALA_OK;
+}
+
+// 6. The owner-side buffers at their exact size (the one allocation between collectives: skewed batches only, see follow_and_presize).
+int grow_owner_buffers(FetchCall& f) {
+    coala_comm* c = f.c;
+    const uint64_t tr = f.c->seg.total_recv ? f.c->seg.total_recv : 1;
+    if (int rc = grow_workspace((void**)&c->recv_ids, &c->recv_cap, tr, sizeof(int64_t), f.st)) return rc;
+    return grow_workspace((void**)&c->rows_send, &c->rows_send_cap, tr * (uint64_t)f.dim, sizeof(float), f.st);
+}
+
+// 7. Ids to their owners (exact sizes); the own bucket is a device copy.
+int send_ids(FetchCall& f) {
+    const Segments& s = f.c->seg;
+    return f.c->tr->all_to_all_v(f.bucketed ? f.idx : f.c->node, s.scnt.data(), s.sdis.data(), f.c->recv_ids, s.rcnt.data(), s.rdis.data(), sizeof(int64_t), true, f.st);
+}
+
+// 8. The begin / end events this fetch hands out, when the caller asked for them.
+int choose_events(FetchCall& f) {
+    coala_comm* c = f.c;
+    if (!c->fetch_events || !f.bucketed || f.n == 0) return COALA_OK;
+    hipEvent_t* slot = fetch_event_slot(c, c->fev_calls);
+    if (!slot) return fail(COALA_EHIP, "hipEventCreate failed");
+    f.ev_begin = c->fetch_events >= 2 ? slot[0] : nullptr; // (an event on the probe's launch costs that launch ~5 us: only when asked for)
+    f.ev_end_st = slot[1], f.ev_end_cs = slot[2];
+    return COALA_OK;
+}
+
+// 9. Owner side: ONE batch = the concatenation in source-rank order (DESIGN.md "Determinism contract").  Probe all of it; the own segment is
+//    delivered straight to out[map[..]] -- it never sees rows_send, the exchange or rows_recv.  (Self-loopback, diagnostics: no own-shard bypass
+//    -- the own segment is served, shipped and un-permuted like a peer's, so that a communicator of ONE rank drives every line of the row
+//    exchange through the transport.)
+int probe(FetchCall& f) {
+    coala_comm* c = f.c;
+    const Segments& s = c->seg;
+    coala_row_redirect_t rd; // the own segment's rows, unless it takes the road of a peer's
+    rd.begin = (int64_t)s.rdis[s.me];
+    rd.end = rd.begin + (int64_t)(s.bypassed(s.me) ? s.rcnt[s.me] : 0);
+    rd.out = f.bucketed ? f.out + s.sdis[s.me] * (size_t)f.dim : f.out; // bucketed: the own bucket sits at its offset, in order
+    rd.row_map = f.bucketed ? nullptr : c->map + s.sdis[s.me];
+    hipEvent_t rode = nullptr;
+    if (int rc = coala_serve_probe_redirect_ev_(f.h, c->rows_send, c->recv_ids, (int64_t)s.total_recv, &rd, f.st, f.ev_begin, &rode)) return rc;
+    if (f.ev_begin && rode != f.ev_begin && hipEventRecord(f.ev_begin, f.st) != hipSuccess) return fail(COALA_EHIP, "hipEventRecord failed");
+    return COALA_OK;
+}
+
+// The event that round k's fill hands to the communicator's stream: the fetch's end event on the caller's stream in the last round, else the
+// round's own when rows are exchanged at all.
+hipEvent_t fill_event(const FetchCall& f, int k) {
+    if (k == f.K - 1 && f.ev_end_st) return f.ev_end_st;
+    return f.exchange_rows ? f.c->ev_fill[k] : nullptr;
+}
+
+// ... and what became of it: `rode` is the event that really rides on round k's last fill launch -- fill_event(k), or the one a profiling cache
+// handle lends in its place, or none when the round launched nothing.  Recorded the plain way when nothing rode, or when the event is handed
+// out to the caller and a borrowed one will not do.  -> fill_evs[k]
+int hand_over_fill(FetchCall& f, int k, hipEvent_t rode) {
+    const hipEvent_t ev = fill_event(f, k);
+    const bool must_be_mine = ev && ev == f.ev_end_st;
+    if (ev && (rode == nullptr || (must_be_mine && rode != ev)) && hipEventRecord(ev, f.st) != hipSuccess) return fail(COALA_EHIP, "hipEventRecord failed");
+    f.fill_evs[k] = (rode && !must_be_mine) ? rode : ev;
+    return COALA_OK;
+}
+
+// 10. Fill slice k of every peer's segment on the caller's stream; the row round k ships it on the communicator's stream while slice k+1
+//     fills.  A round without rows to fill (this rank serves nothing, or a segment has fewer ids than rounds) still hands its event over:
+//     the row rounds run all the same -- peers may owe this rank rows.
+int fill_rounds(FetchCall& f) {
+    const Segments& s = f.c->seg;
+    std::vector<int64_t> fb(f.G), fe(f.G);
+    for (int k = 0; k < f.K; ++k) {
+        int nr = 0;
+        for (int p = 0; p < f.G; ++p) {
+            const Range r = s.slice(Segments::kServed, p, k, true);
+            if (r.end > r.begin) { fb[nr] = (int64_t)r.begin; fe[nr] = (int64_t)r.end; ++nr; }
+        }
+        hipEvent_t rode = nullptr;
+        int rc = nr ? coala_serve_fill_ranges_ev_(f.h, f.c->rows_send, f.c->recv_ids, (int64_t)s.total_recv, fb.data(), fe.data(), nr, f.st, fill_event(f, k), &rode) : COALA_OK;
+        if (!rc) rc = hand_over_fill(f, k, rode);
+        if (rc) return rc;
+    }
+    return COALA_OK;
+}
+
+// 11. Row round k on the communicator's stream, behind fill round k.  (coala_comm_profile: one event pair around all rounds.)
+int row_rounds(FetchCall& f) {
+    if (!f.exchange_rows) return COALA_OK;
+    coala_comm* c = f.c;
+    const Segments& s = f.c->seg;
+    if (c->profile && c->prof_live.size() >= 4096) drain_profile(c);
+    const hipEvent_t t0 = c->profile ? c->prof_pool.take() : nullptr, t1 = c->profile ? c->prof_pool.take() : nullptr;
+    std::vector<size_t> xs_cnt(f.G), xs_dis(f.G), xr_cnt(f.G), xr_dis(f.G);
+    float* rows_recv = f.bucketed ? f.out : c->rows_recv; // bucket order IS the caller's order
+    for (int k = 0; k < f.K; ++k) {
+        for (int p = 0; p < f.G; ++p) {
+            const Range mine = s.slice(Segments::kServed, p, k), theirs = s.slice(Segments::kRequested, p, k); // what I serve to p, what p serves to me
+            xs_cnt[p] = mine.end - mine.begin, xs_dis[p] = mine.begin;
+            xr_cnt[p] = theirs.end - theirs.begin, xr_dis[p] = theirs.begin;
+        }
+        if (hipStreamWaitEvent(c->cs, f.fill_evs[k], 0) != hipSuccess) return fail(COALA_EHIP, "hipStreamWaitEvent failed");
+        if (k == 0 && t0) (void)hipEventRecord(t0, c->cs);
+        if (int rc = c->tr->all_to_all_v(c->rows_send, xs_cnt.data(), xs_dis.data(), rows_recv, xr_cnt.data(), xr_dis.data(), (size_t)f.dim * sizeof(float), f.loop, c->cs))
+            return rc;
+        f.x_evs[k] = (k == f.K - 1 && f.ev_end_cs) ? f.ev_end_cs : c->ev_x[k];
+        if (hipEventRecord(f.x_evs[k], c->cs) != hipSuccess) return fail(COALA_EHIP, "hipEventRecord failed");
+    }
+    if (t0 && t1) {
+        (void)hipEventRecord(t1, c->cs);
+        c->prof_live.emplace_back(t0, t1);
+        c->prof.calls++;
+        c->prof.remote_rows_in += (uint64_t)(f.n - (int64_t)s.scnt[f.me]);
+    }
+    return COALA_OK;
+}
+
+// 12. Un-permute round by round as the rows arrive.  (Bucketed: nothing to un-permute, and the communicator's stream completes its rounds in
+//     order -- the caller's stream waits for the last one only; the workspaces are safe to reuse behind that wait.)
+int unpermute(FetchCall& f) {
+    if (!f.exchange_rows) return COALA_OK;
+    std::vector<int64_t> sb(f.G), se(f.G); // ranges of rows_recv that round k filled
+    for (int k = f.bucketed ? f.K - 1 : 0; k < f.K; ++k) {
+        if (hipStreamWaitEvent(f.st, f.x_evs[k], 0) != hipSuccess) return fail(COALA_EHIP, "hipStreamWaitEvent failed");
+        if (f.bucketed) continue;
+        for (int p = 0; p < f.G; ++p) {
+            const Range r = f.c->seg.slice(Segments::kRequested, p, k);
+            sb[p] = (int64_t)r.begin, se[p] = (int64_t)r.end;
+        }
+        if (int rc = coala_cache_scatter_ranges(f.h, f.out, f.c->rows_recv, f.c->map, sb.data(), se.data(), f.G, f.st)) return rc;
+    }
+    return COALA_OK;
+}
+
+// 13. What coala_comm_last_fetch_events hands out.
+void publish_events(FetchCall& f) {
+    if (!f.ev_end_st) return;
+    f.c->last_ev[0] = f.ev_begin;
+    f.c->last_ev[1] = f.ev_end_st;
+    f.c->last_ev[2] = f.exchange_rows ? f.ev_end_cs : nullptr;
+    f.c->fev_calls++;
+}
+
+int fetch(FetchCall& f) {
+    // every check that can fail locally comes BEFORE the first collective: a rank that returns between collectives strands its peers
+    if (int rc = check_call(f)) return rc;
+    if (int rc = follow_and_presize(f)) return rc;
+    if (int rc = bucket_ids(f)) return rc;
+    // from here on a local failure aborts the transport so that the peers error out instead of waiting for this rank
+    int (*const steps[])(FetchCall&) = {exchange_counts, plan_segments, grow_owner_buffers, send_ids, choose_events, probe, fill_rounds, row_rounds, unpermute};
+    for (auto step : steps)
+        if (int rc = step(f)) return abandon(f.c, rc);
+    publish_events(f);
+    return COALA_OK;
+}
+
+// How both constructors end: a communicator that cannot be equipped is destroyed.
+int finish_create(coala_comm* c, coala_comm_t** out) {
+    const int rc = equip(c);
+    if (rc) coala_comm_destroy(c);
+    else *out = c;
+    return rc;
 }
 
 } // namespace
@@ -391,17 +669,9 @@ int coala_comm_create(const void* id_bytes, int rank, int nranks, int device, co
     if (!id_bytes || !out || nranks < 1 || rank < 0 || rank >= nranks || nranks > 64) return fail(COALA_EINVAL, "bad communicator arguments");
     *out = nullptr;
     HIPCHK(hipSetDevice(device));
-    coala_comm* c = new (std::nothrow) coala_comm();
     RcclTransport* t = new (std::nothrow) RcclTransport();
-    if (!c || !t) {
-        delete c;
-        delete t;
-        return fail(COALA_ENOMEM, "out of host memory");
-    }
-    c->tr = t;
-    c->device = device;
-    t->rank = rank;
-    t->nranks = nranks;
+    coala_comm* c = new_comm(t, rank, nranks, device);
+    if (!c) return fail(COALA_ENOMEM, "out of host memory");
     ncclUniqueId id;
     memcpy(&id, id_bytes, NCCL_UNIQUE_ID_BYTES);
     ncclResult_t r = ncclCommInitRank(&t->comm, nranks, id, rank);
@@ -418,12 +688,7 @@ int coala_comm_create(const void* id_bytes, int rank, int nranks, int device, co
                         cnt, urank, dev, nranks, rank, device);
         }
     }
-    if (int rc = finish_create(c)) {
-        coala_comm_destroy(c);
-        return rc;
-    }
-    *out = c;
-    return COALA_OK;
+    return finish_create(c, out);
 }
 
 int coala_comm_group_create(int nranks, coala_comm_group_t** out) {
@@ -451,18 +716,10 @@ int coala_comm_create_inproc(coala_comm_group_t* g, int rank, int device, coala_
     if (!g || !out || rank < 0 || rank >= g->nranks) return fail(COALA_EINVAL, "bad in-process communicator arguments");
     *out = nullptr;
     HIPCHK(hipSetDevice(device));
-    coala_comm* c = new (std::nothrow) coala_comm();
     InprocTransport* t = new (std::nothrow) InprocTransport();
-    if (!c || !t) {
-        delete c;
-        delete t;
-        return fail(COALA_ENOMEM, "out of host memory");
-    }
-    c->tr = t;
-    c->device = device;
+    coala_comm* c = new_comm(t, rank, g->nranks, device);
+    if (!c) return fail(COALA_ENOMEM, "out of host memory");
     t->g = g;
-    t->rank = rank;
-    t->nranks = g->nranks;
     t->device = device;
     auto& sl = g->slot[rank];
     sl.device = device;
@@ -476,20 +733,14 @@ int coala_comm_create_inproc(coala_comm_group_t* g, int rank, int device, coala_
         std::lock_guard<std::mutex> lk(g->m);
         g->attached++;
     }
-    if (int rc = finish_create(c)) {
-        coala_comm_destroy(c);
-        return rc;
-    }
-    *out = c;
-    return COALA_OK;
+    return finish_create(c, out);
 }
 
 int coala_comm_destroy(coala_comm_t* c) {
     if (!c) return COALA_OK;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    drain_profile(c);
-    for (auto e : c->prof_pool) (void)hipEventDestroy(e);
+    drain_profile(c); // (the pool's events, and the stream order's, go with the handle)
     if (auto* t = dynamic_cast<InprocTransport*>(c->tr)) {
         auto& sl = t->g->slot[t->rank];
         if (sl.ready) (void)hipEventDestroy(sl.ready);
@@ -499,16 +750,12 @@ int coala_comm_destroy(coala_comm_t* c) {
         t->g->attached--;
     }
     delete c->tr;
-    for (int k = 0; k < kMaxRounds; ++k) {
-        if (c->ev_fill[k]) (void)hipEventDestroy(c->ev_fill[k]);
-        if (c->ev_x[k]) (void)hipEventDestroy(c->ev_x[k]);
-    }
     if (c->cs) (void)hipStreamDestroy(c->cs);
-    if (c->order_ev) (void)hipEventDestroy(c->order_ev);
-    for (auto e : c->fev)
+    std::vector<hipEvent_t> evs(c->fev);
+    for (auto* a : {c->ev_fill, c->ev_x}) evs.insert(evs.end(), a, a + kMaxRounds);
+    evs.insert(evs.end(), c->ahead_ev, c->ahead_ev + coala_comm::kCountsRing);
+    for (auto e : evs)
         if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < coala_comm::kCountsRing; ++k)
-        if (c->ahead_ev[k]) (void)hipEventDestroy(c->ahead_ev[k]);
     if (c->ahead_host) (void)hipHostFree(c->ahead_host);
     void* dev[] = {c->node, c->map, c->recv_ids, c->rows_send, c->rows_recv, c->counts_dev, c->ahead_dev};
     for (void* p : dev)
@@ -546,16 +793,15 @@ int coala_comm_last_fetch_events(const coala_comm_t* c, void** begin_ev, void** 
 
 int coala_comm_set_self_loopback(coala_comm_t* c, int on) {
     if (!c || !c->tr) return fail(COALA_EINVAL, "null communicator");
-    c->loopback = on != 0;
-    c->tr->self_loopback = c->loopback;
+    c->tr->self_loopback = on != 0;
     return COALA_OK;
 }
 
 int coala_comm_last_counts(const coala_comm_t* c, int64_t* send, int64_t* recv) {
     if (!c) return fail(COALA_EINVAL, "null communicator");
     for (int p = 0; p < c->nranks; ++p) {
-        if (send) send[p] = c->last_send[p];
-        if (recv) recv[p] = c->last_recv[p];
+        if (send) send[p] = (int64_t)c->seg.scnt[p];
+        if (recv) recv[p] = (int64_t)c->seg.rcnt[p];
     }
     return COALA_OK;
 }
@@ -570,46 +816,34 @@ int coala_comm_profile(coala_comm_t* c, int enable, coala_comm_profile_t* out, i
     return COALA_OK;
 }
 
-static int fetch_impl(coala_cache_t* h, coala_comm_t* c, float* out, const int64_t* idx, int64_t n, const int64_t* bucket_counts_dev,
-                      const int64_t* counts_host, void* stream);
-
 int coala_cache_fetch_distributed(coala_cache_t* h, coala_comm_t* c, float* out, const int64_t* idx, int64_t n, void* stream) {
-    return fetch_impl(h, c, out, idx, n, nullptr, nullptr, stream);
+    FetchCall f{h, c, out, idx, n, (hipStream_t)stream};
+    return fetch(f);
 }
 
 int coala_cache_fetch_distributed_bucketed(coala_cache_t* h, coala_comm_t* c, float* out, const int64_t* idx, int64_t n,
                                            const int64_t* counts_dev, void* stream) {
     if (!counts_dev) return fail(COALA_EINVAL, "null bucket counts");
-    return fetch_impl(h, c, out, idx, n, counts_dev, nullptr, stream);
+    FetchCall f{h, c, out, idx, n, (hipStream_t)stream};
+    f.bucket_counts_dev = counts_dev;
+    return fetch(f);
 }
 
 int coala_comm_counts_begin(coala_comm_t* c, const int64_t* counts_dev, void* stream, int64_t* ticket_out) {
     if (!c || !counts_dev || !ticket_out) return fail(COALA_EINVAL, "null argument");
-    if (c->broken) return fail(COALA_ECOMM, "this communicator failed in an earlier fetch and was aborted: destroy it");
+    if (int rc = refuse_abandoned(c)) return rc;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    const int G = c->nranks;
-    const int slot = (int)(c->ahead_calls % coala_comm::kCountsRing);
-    if (c->ahead_calls >= coala_comm::kCountsRing) HIPCHK(hipEventSynchronize(c->ahead_ev[slot])); // the slot's previous exchange has landed
-    int64_t* dev = c->ahead_dev + (size_t)slot * 2 * G;
-    int64_t* host = c->ahead_host + (size_t)slot * 2 * G;
-    if (hipMemcpyAsync(dev, counts_dev, (size_t)G * sizeof(int64_t), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        c->broken = true; // the peers are about to enter the collective this rank will not join
-        c->tr->abort();
-        return fail(COALA_EHIP, "count exchange issued ahead: staging the counts failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    if (int rc = c->tr->all_to_all_i64(dev, dev + G, st)) { // a collective: a failure here strands the peers -> abort
-        c->broken = true;
-        c->tr->abort();
-        return rc;
-    }
-    // behind the collective a local failure must not leave this rank's ticket counter behind its peers': same path as fetch_impl
-    if (hipMemcpyAsync(host, dev, 2 * (size_t)G * sizeof(int64_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipEventRecord(c->ahead_ev[slot], st) != hipSuccess) {
-        c->broken = true;
-        c->tr->abort();
-        return fail(COALA_EHIP, "count exchange issued ahead: reading the counts back failed: %s", hipGetErrorString(hipGetLastError()));
-    }
+    const size_t G = (size_t)c->nranks;
+    const CountsSlot slot = counts_slot(c, c->ahead_calls);
+    if (c->ahead_calls >= coala_comm::kCountsRing) HIPCHK(hipEventSynchronize(slot.ev)); // the slot's previous exchange has landed
+    // the peers are about to enter the collective: from here on a rank that fails abandons the communicator, as in fetch.  (Behind the
+    // collective too: a local failure must not leave this rank's ticket counter behind its peers'.)
+    if (hipMemcpyAsync(slot.dev, counts_dev, G * sizeof(int64_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return abandon(c, fail(COALA_EHIP, "count exchange issued ahead: staging the counts failed: %s", hipGetErrorString(hipGetLastError())));
+    if (int rc = c->tr->all_to_all_i64(slot.dev, slot.dev + G, st)) return abandon(c, rc);
+    if (hipMemcpyAsync(slot.host, slot.dev, 2 * G * sizeof(int64_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(slot.ev, st) != hipSuccess)
+        return abandon(c, fail(COALA_EHIP, "count exchange issued ahead: reading the counts back failed: %s", hipGetErrorString(hipGetLastError())));
     *ticket_out = (int64_t)c->ahead_calls++;
     return COALA_OK;
 }
@@ -620,202 +854,11 @@ int coala_cache_fetch_distributed_bucketed_ahead(coala_cache_t* h, coala_comm_t*
     if (ticket < 0 || (uint64_t)ticket >= c->ahead_calls || c->ahead_calls - (uint64_t)ticket > (uint64_t)coala_comm::kCountsRing)
         return fail(COALA_EINVAL, "ticket %lld is not one of the last %d count exchanges", (long long)ticket, coala_comm::kCountsRing);
     HIPCHK(hipSetDevice(c->device));
-    const int slot = (int)((uint64_t)ticket % coala_comm::kCountsRing);
-    HIPCHK(hipEventSynchronize(c->ahead_ev[slot])); // issued a step or two ago: normally complete long since
-    return fetch_impl(h, c, out, idx, n, c->ahead_dev + (size_t)slot * 2 * c->nranks, c->ahead_host + (size_t)slot * 2 * c->nranks, stream);
-}
-
-// bucket_counts_dev == nullptr: route here.  Otherwise idx is already bucketed by owner: node = idx, the map is the identity,
-// the rows of every peer are received straight into `out` and nothing is un-permuted.
-// counts_host != nullptr: the 2G counts were exchanged ahead (coala_comm_counts_begin) and are on the host already -- no count
-// exchange, no host synchronisation in this call.
-static int fetch_impl(coala_cache_t* h, coala_comm_t* c, float* out, const int64_t* idx, int64_t n, const int64_t* bucket_counts_dev,
-                      const int64_t* counts_host, void* stream) {
-    if (!h || !c) return fail(COALA_EINVAL, "null handle");
-    c->last_ev[0] = c->last_ev[1] = c->last_ev[2] = nullptr;
-    const bool bucketed = bucket_counts_dev != nullptr;
-    if (c->broken) return fail(COALA_ECOMM, "this communicator failed in an earlier fetch and was aborted: destroy it");
-    // every check that can fail locally comes BEFORE the first collective: a rank that returns between collectives strands its peers
-    if (n < 0 || n > 0x7FFFFFFFll || (n > 0 && (!out || !idx))) return fail(COALA_EINVAL, "bad batch");
-    coala_cache_geometry_t geo;
-    int rc = coala_cache_geometry(h, &geo);
-    if (rc) return rc;
-    const int G = c->nranks, me = c->rank;
-    const int64_t dim = coala_cache_row_dim(h);
-    hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(c->device));
-    if ((rc = follow_stream(c, st))) return rc;
-    const uint64_t nb = (uint64_t)(n > 0 ? n : 1);
-    if (!bucketed) {
-        if ((rc = grow_workspace((void**)&c->node, &c->node_cap, nb, sizeof(int64_t), st))) return rc;
-        if ((rc = grow_workspace((void**)&c->map, &c->map_cap, nb, sizeof(int64_t), st))) return rc;
-        if ((rc = grow_workspace((void**)&c->rows_recv, &c->rows_recv_cap, nb * (uint64_t)dim, sizeof(float), st))) return rc;
-    }
-    // the usual step receives about as many ids as it sends: pre-size the owner-side buffers too, so that the grow after the
-    // counts exchange (the one allocation that sits between collectives) only happens for skewed batches
-    if ((rc = grow_workspace((void**)&c->recv_ids, &c->recv_cap, nb + (nb >> 2), sizeof(int64_t), st))) return rc;
-    if ((rc = grow_workspace((void**)&c->rows_send, &c->rows_send_cap, (nb + (nb >> 2)) * (uint64_t)dim, sizeof(float), st))) return rc;
-    int64_t* send_cnt = c->counts_dev;
-    int64_t* recv_cnt = c->counts_dev + G;
-    int64_t* offsets = c->counts_dev + 2 * G; // [G+1]
-    // 1. bucket by owner (stable), packed layout -- unless the sampler already delivered the ids that way
-    const int64_t* node = c->node;
-    float* rows_recv = c->rows_recv;
-    if (bucketed) {
-        if (!counts_host) HIPCHK(hipMemcpyAsync(send_cnt, bucket_counts_dev, (size_t)G * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-        node = idx;
-        rows_recv = out; // bucket order IS the caller's order
-    } else if ((rc = coala_cache_route(h, idx, n, G, 0, c->node, c->map, send_cnt, offsets, st))) {
-        return rc;
-    }
-
-    // from here on a local failure aborts the transport so that the peers error out instead of waiting for this rank
-    auto broke = [&](int code) {
-        c->broken = true;
-        c->tr->abort();
-        return code;
-    };
-    if (!counts_host) {
-        // 2. counts: every rank tells every owner how many ids follow
-        if ((rc = c->tr->all_to_all_i64(send_cnt, recv_cnt, st))) return broke(rc);
-        // 3. the one host read of the step
-        if (hipMemcpyAsync(c->counts_host, c->counts_dev, 2 * (size_t)G * sizeof(int64_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return broke(fail(COALA_EHIP, "reading the exchange counts failed: %s", hipGetErrorString(hipGetLastError())));
-        counts_host = c->counts_host;
-    }
-    std::vector<size_t> scnt(G), sdis(G), rcnt(G), rdis(G);
-    size_t total_recv = 0, acc = 0;
-    for (int p = 0; p < G; ++p) {
-        scnt[p] = (size_t)counts_host[p];
-        rcnt[p] = (size_t)counts_host[G + p];
-        sdis[p] = acc;
-        rdis[p] = total_recv;
-        acc += scnt[p];
-        total_recv += rcnt[p];
-        c->last_send[p] = (int64_t)scnt[p];
-        c->last_recv[p] = (int64_t)rcnt[p];
-    }
-    if ((int64_t)acc != n) return broke(fail(COALA_ECOMM, "%s %zu ids for a batch of %lld", bucketed ? "the bucket counts sum to" : "route produced", acc, (long long)n));
-    if (total_recv > 0x7FFFFFFFull) return broke(fail(COALA_ECOMM, "%zu ids routed to one owner in one step", total_recv));
-    const uint64_t tr = total_recv ? total_recv : 1;
-    if ((rc = grow_workspace((void**)&c->recv_ids, &c->recv_cap, tr, sizeof(int64_t), st))) return broke(rc);
-    if ((rc = grow_workspace((void**)&c->rows_send, &c->rows_send_cap, tr * (uint64_t)dim, sizeof(float), st))) return broke(rc);
-    // 4. ids to their owners (exact sizes); the own bucket is a device copy
-    if ((rc = c->tr->all_to_all_v(node, scnt.data(), sdis.data(), c->recv_ids, rcnt.data(), rdis.data(), sizeof(int64_t), true, st)))
-        return broke(rc);
-    // 5. owner side: ONE batch = the concatenation in source-rank order (DESIGN.md "Determinism contract").  Probe all of it;
-    //    the own segment is delivered straight to out[map[..]] -- it never sees rows_send, the exchange or rows_recv.
-    //    (self-loopback, diagnostics: no own-shard bypass -- the own segment is served, shipped and un-permuted like a peer's, so that a
-    //    communicator of ONE rank drives every line of the row exchange below through the transport)
-    const bool loop = c->loopback;
-    coala_row_redirect_t rd;
-    rd.begin = (int64_t)rdis[me];
-    rd.end = loop ? rd.begin : (int64_t)(rdis[me] + rcnt[me]);
-    rd.out = bucketed ? out + sdis[me] * (size_t)dim : out; // bucketed: the own bucket sits at its offset, in order
-    rd.row_map = bucketed ? nullptr : c->map + sdis[me];
-    // Events of this fetch.  Every hipEventRecord on the caller's stream is one more barrier packet between the kernels of a saturated
-    // stream (6-12 us each: DESIGN.md section 6), so whatever can ride ON a launch does: the hand-over events of the fill rounds always, and
-    // -- opt-in, bucketed fetches: coala_comm_fetch_events -- the begin / end events a caller needs for timing and for its consumer's stream.
-    const bool ev_mode = c->fetch_events && bucketed && n > 0;
-    hipEvent_t ev_begin = nullptr, ev_end_st = nullptr, ev_end_cs = nullptr;
-    if (ev_mode) {
-        if (c->fev.empty()) c->fev.assign(3 * (size_t)coala_comm::kFetchRing, nullptr);
-        const size_t slot = (size_t)(c->fev_calls % coala_comm::kFetchRing);
-        for (size_t k = 3 * slot; k < 3 * slot + 3; ++k)
-            if (!c->fev[k] && hipEventCreate(&c->fev[k]) != hipSuccess) return broke(fail(COALA_EHIP, "hipEventCreate failed"));
-        ev_begin = c->fetch_events >= 2 ? c->fev[3 * slot] : nullptr;   // (an event on the probe's launch costs that launch ~5 us: only when asked for)
-        ev_end_st = c->fev[3 * slot + 1];
-        ev_end_cs = c->fev[3 * slot + 2];
-    }
-    hipEvent_t rode = nullptr;
-    if ((rc = coala_serve_probe_redirect_ev_(h, c->rows_send, c->recv_ids, (int64_t)total_recv, &rd, st, ev_begin, &rode))) return broke(rc);
-    if (ev_begin && rode != ev_begin && hipEventRecord(ev_begin, st) != hipSuccess) return broke(fail(COALA_EHIP, "hipEventRecord failed"));
-    // 6. rounds: fill slice k of every peer's segment on the caller's stream, ship it on the comm stream while slice k+1 fills
-    const int K = (G == 1 && !loop) ? 1 : c->rounds;
-    const bool exchange_rows = G > 1 || loop;
-    const size_t row_bytes = (size_t)dim * sizeof(float);
-    std::vector<int64_t> fb(G), fe(G);
-    std::vector<size_t> xs_cnt(G), xs_dis(G), xr_cnt(G), xr_dis(G);
-    std::vector<int64_t> sb((size_t)G * K), se((size_t)G * K); // requester-side ranges of rows_recv, per round
-    hipEvent_t fill_evs[kMaxRounds] = {};
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (c->profile && exchange_rows) {
-        if (c->prof_live.size() >= 4096) drain_profile(c);
-        t0 = take_timing_event(c);
-        t1 = take_timing_event(c);
-    }
-    for (int k = 0; k < K && total_recv > 0; ++k) {
-        int nr = 0;
-        for (int p = 0; p < G; ++p) {
-            int64_t b, e;
-            if (p == me && !loop) { // own segment: nobody waits for it on a link -> last round
-                if (k != K - 1) continue;
-                b = (int64_t)rdis[p];
-                e = (int64_t)(rdis[p] + rcnt[p]);
-            } else {
-                b = (int64_t)(rdis[p] + rcnt[p] * (size_t)k / (size_t)K);
-                e = (int64_t)(rdis[p] + rcnt[p] * (size_t)(k + 1) / (size_t)K);
-            }
-            if (e > b) { fb[nr] = b; fe[nr] = e; ++nr; }
-        }
-        // the event the row round k waits for rides on this round's fill launch (a profiling cache handle lends its own event of that launch);
-        // the last round's is the fetch's end event on this stream
-        const bool last = k == K - 1;
-        hipEvent_t fill_ev = (last && ev_end_st) ? ev_end_st : (exchange_rows ? c->ev_fill[k] : nullptr);
-        if ((rc = coala_serve_fill_ranges_ev_(h, c->rows_send, c->recv_ids, (int64_t)total_recv, fb.data(), fe.data(), nr, st, fill_ev, &rode))) return broke(rc);
-        const bool must_be_mine = fill_ev && fill_ev == ev_end_st;    // handed out to the caller: a borrowed event will not do
-        if (fill_ev && (rode == nullptr || (must_be_mine && rode != fill_ev)) && hipEventRecord(fill_ev, st) != hipSuccess)
-            return broke(fail(COALA_EHIP, "hipEventRecord failed"));
-        fill_evs[k] = (rode && !must_be_mine) ? rode : fill_ev;
-    }
-    if (total_recv == 0) // nothing to serve: the rounds below still run (peers may owe this rank rows)
-        for (int k = 0; k < K; ++k) {
-            fill_evs[k] = (k == K - 1 && ev_end_st) ? ev_end_st : (exchange_rows ? c->ev_fill[k] : nullptr);
-            if (fill_evs[k] && hipEventRecord(fill_evs[k], st) != hipSuccess) return broke(fail(COALA_EHIP, "hipEventRecord failed"));
-        }
-    hipEvent_t x_evs[kMaxRounds] = {};
-    if (exchange_rows) {
-        for (int k = 0; k < K; ++k) {
-            for (int p = 0; p < G; ++p) {
-                const size_t a = rcnt[p] * (size_t)k / (size_t)K, b = rcnt[p] * (size_t)(k + 1) / (size_t)K;     // what I serve to p
-                const size_t u = scnt[p] * (size_t)k / (size_t)K, v = scnt[p] * (size_t)(k + 1) / (size_t)K;     // what p serves to me
-                const bool skip = p == me && !loop;
-                xs_cnt[p] = skip ? 0 : b - a;
-                xs_dis[p] = rdis[p] + a;
-                xr_cnt[p] = skip ? 0 : v - u;
-                xr_dis[p] = sdis[p] + u;
-                sb[(size_t)k * G + p] = (int64_t)(sdis[p] + u);
-                se[(size_t)k * G + p] = skip ? (int64_t)(sdis[p] + u) : (int64_t)(sdis[p] + v);
-            }
-            if (hipStreamWaitEvent(c->cs, fill_evs[k], 0) != hipSuccess) return broke(fail(COALA_EHIP, "hipStreamWaitEvent failed"));
-            if (k == 0 && t0) (void)hipEventRecord(t0, c->cs);
-            if ((rc = c->tr->all_to_all_v(c->rows_send, xs_cnt.data(), xs_dis.data(), rows_recv, xr_cnt.data(), xr_dis.data(), row_bytes, loop, c->cs)))
-                return broke(rc);
-            x_evs[k] = (k == K - 1 && ev_end_cs) ? ev_end_cs : c->ev_x[k];
-            if (hipEventRecord(x_evs[k], c->cs) != hipSuccess) return broke(fail(COALA_EHIP, "hipEventRecord failed"));
-        }
-        if (t0 && t1) {
-            (void)hipEventRecord(t1, c->cs);
-            c->prof_live.emplace_back(t0, t1);
-            c->prof.calls++;
-            c->prof.remote_rows_in += (uint64_t)(n - (int64_t)scnt[me]);
-        }
-        // 7. un-permute round by round as the rows arrive (bucketed: nothing to un-permute, and the communicator's stream completes its rounds
-        //    in order -- the caller's stream waits for the last one only; the workspaces are safe to reuse behind that wait)
-        for (int k = bucketed ? K - 1 : 0; k < K; ++k) {
-            if (hipStreamWaitEvent(st, x_evs[k], 0) != hipSuccess) return broke(fail(COALA_EHIP, "hipStreamWaitEvent failed"));
-            if (!bucketed && (rc = coala_cache_scatter_ranges(h, out, c->rows_recv, c->map, sb.data() + (size_t)k * G, se.data() + (size_t)k * G, G, st)))
-                return broke(rc);
-        }
-    }
-    if (ev_mode) {
-        c->last_ev[0] = ev_begin;
-        c->last_ev[1] = ev_end_st;
-        c->last_ev[2] = exchange_rows ? ev_end_cs : nullptr;
-        c->fev_calls++;
-    }
-    return COALA_OK;
+    const CountsSlot slot = counts_slot(c, (uint64_t)ticket);
+    HIPCHK(hipEventSynchronize(slot.ev)); // issued a step or two ago: normally complete long since
+    FetchCall f{h, c, out, idx, n, (hipStream_t)stream};
+    f.bucket_counts_dev = slot.dev, f.counts_host = slot.host;
+    return fetch(f);
 }
 
 } // extern "C"

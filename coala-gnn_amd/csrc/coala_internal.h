@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 // Records a thread-local message for coala_last_error() and returns `code`.
 int coala_fail_(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
@@ -50,6 +52,38 @@ inline int grow(void** p, uint64_t* cap, uint64_t need, size_t elem, hipStream_t
     *cap = c;
     return COALA_OK;
 }
+
+// What a handle (cache, communicator) owns on the device is ordered by the stream its calls are enqueued on.  A caller that moves to another
+// stream keeps that order: the new stream first waits (no host wait) for what the handle enqueued last on the old one.
+struct StreamOrder {
+    hipStream_t stream = nullptr;
+    bool set = false;
+    hipEvent_t ev = nullptr; // created on the first move
+    ~StreamOrder() { if (ev) (void)hipEventDestroy(ev); }
+    int follow(hipStream_t s) {
+        if (set && stream != s) {
+            if (!ev) COALA_HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            // (a stream the caller has destroyed in the meantime has nothing left to wait for)
+            if (hipEventRecord(ev, stream) == hipSuccess) COALA_HIPCHK(hipStreamWaitEvent(s, ev, 0));
+            else (void)hipGetLastError();
+        }
+        stream = s, set = true;
+        return COALA_OK;
+    }
+};
+
+// Timing events of a profiling handle, reused: take() hands out a free one or creates one (nullptr when that fails), give() returns it.
+struct EventPool {
+    std::vector<hipEvent_t> idle;
+    ~EventPool() { for (hipEvent_t e : idle) (void)hipEventDestroy(e); }
+    hipEvent_t take() {
+        hipEvent_t e = idle.empty() ? nullptr : idle.back();
+        if (e) idle.pop_back();
+        else if (hipEventCreate(&e) != hipSuccess) e = nullptr;
+        return e;
+    }
+    void give(hipEvent_t e) { idle.push_back(e); }
+};
 
 // The split-phase serve calls with an event ON a launch instead of behind it (coala_cache.hip; used by the distributed fetch, coala_comm.cpp):
 // begin_ev rides on the probe's launch, end_ev on the last fill launch of the call.  *rode = the event that really rides there: the caller's, or

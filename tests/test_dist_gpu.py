@@ -965,3 +965,132 @@ def test_native_fetch_local_failure_does_not_strand_the_peers(hiplib, oracle, mo
         c.close()
     for t in set(tables):
         t.close()
+
+
+@pytest.mark.parametrize("dim", [100, 128])
+def test_native_fetch_random_call_sequence_on_one_group(hiplib, oracle, dim, monkeypatch):
+    """A seeded sequence of a dozen fetches on ONE in-process group of three ranks, every kind interleaved on the same communicators: routed,
+    bucketed, and bucketed with the counts exchanged ahead (one step ahead, i.e. in front of another fetch); `rounds` changed between the
+    fetches over 1..4; a rank with an empty batch beside peers with full ones; a step in which nobody asks rank 2 for anything, so that it
+    serves nothing and still receives its own rows; a peer's segment of 2 ids cut into 4 rounds (empty slices); a move of every rank to
+    another stream; fetch_events(2) for the bucketed fetches of the second half, where a consumer that waits for the two end events and
+    for nothing else must see every row.  Rows bit for bit against the oracle, per-peer counts against the host's."""
+    import ctypes as C
+    import threading
+    import torch
+    from COALA_GNN.COALA_GNN_Manager import NativeExchange
+    from COALA_GNN_Pybind import _capi
+    monkeypatch.setenv("COALA_INPROC_TIMEOUT_S", "20")   # a wait that never ends finishes the test, not the job
+    L = _capi.load()
+    G, num_rows = 3, 6000
+    modes = ["routed", "bucketed", "ahead", "bucketed", "routed", "ahead", "ahead", "bucketed", "routed", "ahead", "bucketed", "routed"]
+    steps, move_at = len(modes), 6                                                  # events on, and the other stream, from step 6 on
+    EMPTY_RANK, NOBODY_ASKS_2, TINY_SEGMENT = 3, 7, 9
+    rng = np.random.default_rng(2024 + dim)
+    rounds = [int(k) for k in rng.permutation([1, 2, 3, 4] * 3)]
+    rounds[TINY_SEGMENT] = 4
+    plan = []
+    for step in range(steps):
+        batch = []
+        for r in range(G):
+            ids = rng.choice(num_rows, size=int(rng.integers(200, 901)), replace=False).astype(np.int64)
+            if step == EMPTY_RANK and r == 1:
+                ids = ids[:0]
+            if step == NOBODY_ASKS_2:
+                ids = ids[ids % G != 2]
+            if step == TINY_SEGMENT and r == 0:
+                ids = np.concatenate([ids[ids % G != 1], ids[ids % G == 1][:2]])      # 2 ids for owner 1, 4 rounds
+            if modes[step] != "routed":
+                ids = np.concatenate([ids[ids % G == o] for o in range(G)])          # as the sampler delivers them: bucketed by owner
+            batch.append(ids)
+        plan.append(batch)
+    assert len(plan[EMPTY_RANK][1]) == 0 and all(len(plan[EMPTY_RANK][r]) for r in (0, 2))
+    assert all((plan[NOBODY_ASKS_2][r] % G != 2).all() for r in range(G)) and len(plan[NOBODY_ASKS_2][2])
+    assert int((plan[TINY_SEGMENT][0] % G == 1).sum()) == 2
+    assert all(len(i) <= 900 for b in plan for i in b) and len(set(rounds)) == 4
+
+    feat, tables, caches, orcs = _dist_fixture(hiplib, oracle, G, dim, 1, True, num_rows, seed=31, cls="Isolated_Cache")
+    group = C.c_void_p()
+    _capi.check(L.coala_comm_group_create(G, C.byref(group)))
+    exs = [NativeExchange(None, 0, r, G, 0, inproc_group=group) for r in range(G)]
+    got = [[None] * G for _ in range(steps)]
+    counts = [[None] * G for _ in range(steps)]
+    errors = []
+    bar = threading.Barrier(G, timeout=60)
+
+    def worker(r):
+        try:
+            torch.cuda.set_device(0)
+            streams, side = [torch.cuda.Stream(), torch.cuda.Stream()], torch.cuda.Stream()
+            ex, dev, tickets = exs[r], [], {}
+            for step in range(steps):
+                ids = plan[step][r]
+                cnt = torch.tensor([int((ids % G == o).sum()) for o in range(G)], dtype=torch.int64).cuda()
+                dev.append((torch.from_numpy(ids).cuda() if len(ids) else torch.zeros(0, dtype=torch.int64, device="cuda"), cnt))
+            torch.cuda.synchronize()
+            for step in range(steps):
+                with torch.cuda.stream(streams[step >= move_at]):
+                    stream = torch.cuda.current_stream()
+                    ids, (idx, cnt), n, mode = plan[step][r], dev[step], len(plan[step][r]), modes[step]
+                    if step + 1 < steps and modes[step + 1] == "ahead":               # the next fetch's counts go out in front of this fetch
+                        tickets[step + 1] = ex.counts_begin(dev[step + 1][1].data_ptr())
+                    ex.rounds = rounds[step]
+                    out = torch.full((max(n, 1), dim), -9.0, dtype=torch.float32, device="cuda")
+                    copy = torch.full((max(n, 1), dim), -5.0, dtype=torch.float32, device="cuda")
+                    stream.synchronize()
+                    out_ptr, idx_ptr = (out.data_ptr(), idx.data_ptr()) if n else (0, 0)
+                    if mode == "routed":
+                        ex.fetch(caches[r], out_ptr, idx_ptr, n)
+                        assert ex.last_fetch_events() == (None, None, None)
+                    else:
+                        ex.fetch_events(2 if step >= move_at else 0)
+                        ex.fetch_bucketed(caches[r], out_ptr, idx_ptr, n, cnt.data_ptr(), ticket=tickets.get(step))
+                    counts[step][r] = (list(ex.last_send_counts), list(ex.last_recv_counts))
+                    if mode != "routed" and step >= move_at and n:
+                        begin, end_st, end_cs = ex.last_fetch_events()
+                        assert begin and end_st and end_cs
+                        with torch.cuda.stream(side):                                 # a consumer that waits for the end events only
+                            hiplib.stream_wait_event(end_st)
+                            hiplib.stream_wait_event(end_cs)
+                            copy[:n].copy_(out[:n])
+                        side.synchronize()
+                        got[step][r] = copy[:n].cpu().numpy()
+                        ms = hiplib.event_elapsed_ms(begin, end_cs, wait=False)       # complete by now: the rows have been read
+                        assert ms is not None and ms >= 0.0, f"rank {r} step {step}: end event {ms}"
+                    else:
+                        if mode != "routed":
+                            assert ex.last_fetch_events() == (None, None, None)
+                        stream.synchronize()
+                        got[step][r] = out[:n].cpu().numpy()
+                    stream.synchronize()
+                bar.wait()
+        except BaseException as e:  # noqa: BLE001
+            errors.append((r, repr(e)))
+            bar.abort()
+
+    threads = [threading.Thread(target=worker, args=(r,)) for r in range(G)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=120)
+    assert not any(t.is_alive() for t in threads) and not errors, errors
+    for step in range(steps):
+        want = oracle.dist_fetch(orcs, plan[step], oracle.SCHED_HITS_FIRST)
+        for r in range(G):
+            assert got[step][r].tobytes() == feat[plan[step][r]].tobytes() == want[r].tobytes(), f"rank {r} step {step} ({modes[step]}): rows differ"
+            send, recv = counts[step][r]
+            assert send == [int((plan[step][r] % G == o).sum()) for o in range(G)], f"rank {r} step {step}"
+            assert recv == [int((plan[step][s] % G == r).sum()) for s in range(G)], f"rank {r} step {step}"
+    assert counts[NOBODY_ASKS_2][2][1] == [0] * G and sum(counts[NOBODY_ASKS_2][2][0]) > 0
+    for r in range(G):
+        assert caches[r].stats()[:2] == (orcs[r].hit_cnt, orcs[r].miss_cnt)
+        keys, cnt_, _ = caches[r].dump()
+        assert np.array_equal(keys, orcs[r].keys()) and np.array_equal(cnt_, orcs[r].set_cnt())
+    assert sum(o.hit_cnt for o in orcs) > 0 and sum(o.miss_cnt for o in orcs) > 0
+    for e in exs:
+        e.close()
+    _capi.check(L.coala_comm_group_destroy(group))
+    for c in caches:
+        c.close()
+    for t in set(tables):
+        t.close()
