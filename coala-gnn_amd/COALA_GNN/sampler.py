@@ -35,6 +35,11 @@ def _as_graph(g):
     return CSCGraph(*g) if isinstance(g, tuple) else g
 
 
+def _u64(x):
+    """A seed or a step as the uint64 the C entries take: any Python integer, modulo 2^64."""
+    return int(x) & ((1 << 64) - 1)
+
+
 def _sort_csc_by_key(indptr, indices, key, what):
     """sort_csc_by_etype / sort_csc_by_time: a stable sort of every row's in-edges by an integer key, `what` its name in the messages."""
     if key.dim() != 1 or key.numel() != indices.numel():
@@ -1108,8 +1113,8 @@ def random_walk(g, nodes, length, restart_prob=0.0, num_walks=1, seed=0, step=0)
     g = _as_graph(g)
     nodes = nodes.to(g.device, dtype=torch.int64).contiguous()
     out = torch.empty((nodes.numel(), num_walks, length + 1), dtype=torch.int64, device=g.device)
-    _capi.check(_lib.coala_sampler_random_walk(g._h, nodes.data_ptr(), nodes.numel(), num_walks, length, thr, int(seed) & ((1 << 64) - 1),
-                                               int(step) & ((1 << 64) - 1), 0, out.data_ptr(), current_stream()))
+    _capi.check(_lib.coala_sampler_random_walk(g._h, nodes.data_ptr(), nodes.numel(), num_walks, length, thr, _u64(seed), _u64(step), 0,
+                                               out.data_ptr(), current_stream()))
     return out
 
 
@@ -1184,10 +1189,23 @@ def node2vec_random_walk(g, nodes, p, q, walk_length, num_walks=1, seed=0, step=
     NOT the traces random_walk gives for the same arguments; and a start node given twice gets the same traces twice."""
     g, nodes, thr = _walk_args(g, nodes, p, q, walk_length, num_walks, "node2vec_random_walk")
     out = torch.empty((nodes.numel(), num_walks, walk_length + 1), dtype=torch.int64, device=g.device)
-    mask = (1 << 64) - 1
-    _capi.check(_lib.coala_sampler_node2vec_walk(g._h, nodes.data_ptr(), nodes.numel(), num_walks, walk_length, thr[0], thr[1], thr[2],
-                                                 int(seed) & mask, int(step) & mask, out.data_ptr(), current_stream()))
+    _capi.check(_lib.coala_sampler_node2vec_walk(g._h, nodes.data_ptr(), nodes.numel(), num_walks, walk_length, *thr, _u64(seed), _u64(step),
+                                                 out.data_ptr(), current_stream()))
     return out
+
+
+def _batch_begin(entry, g, *args):
+    """One batch call on the current stream, without waiting -> its ticket.  args: `entry`'s, between the handle and ticket_out."""
+    ticket = C.c_int64(-1)
+    _capi.check(entry(g._h, *args, C.byref(ticket), current_stream()))
+    return ticket.value
+
+
+def _batch_collect(wait, g, ticket):
+    """Wait for the event behind a batch call (only for its kernels) -> (n_nodes, n_bad)."""
+    n_nodes, n_bad = C.c_int64(0), C.c_int64(0)
+    _capi.check(wait(g._h, ticket, C.byref(n_nodes), C.byref(n_bad)))
+    return n_nodes.value, n_bad.value
 
 
 class WalkBatch(object):
@@ -1222,20 +1240,16 @@ def walk_batch_begin(g, nodes, p, q, walk_length, num_walks=1, num_neg=1, seed=0
     neg = torch.empty((n * W * K, L1), dtype=torch.int32, device=g.device)
     tr = torch.empty((n, W, L1), dtype=torch.int64, device=g.device) if traces else None
     out = _capi.WalkBatchOut(input_nodes.data_ptr(), pos.data_ptr(), neg.data_ptr() if neg.numel() else None, tr.data_ptr() if traces and n else None)
-    ticket = C.c_int64(-1)
-    mask = (1 << 64) - 1
-    _capi.check(_lib.coala_sampler_walk_batch(g._h, nodes.data_ptr(), n, W, walk_length, thr[0], thr[1], thr[2], K, int(seed) & mask,
-                                              int(step) & mask, C.byref(out), C.byref(ticket), current_stream()))
-    return (g, nodes, input_nodes, pos, neg, tr, ticket.value)
+    ticket = _batch_begin(_lib.coala_sampler_walk_batch, g, nodes.data_ptr(), n, W, walk_length, *thr, K, _u64(seed), _u64(step), C.byref(out))
+    return (g, nodes, input_nodes, pos, neg, tr, ticket)
 
 
 def walk_batch_end(pending):
     """Wait for the event behind a walk_batch_begin call (only for its kernels) -> WalkBatch.  Start nodes outside [0, num_nodes) are
     counted in its n_bad, as node2vec_random_walk gives them a row of -1."""
     g, nodes, input_nodes, pos, neg, tr, ticket = pending
-    n_nodes, n_bad = C.c_int64(0), C.c_int64(0)
-    _capi.check(_lib.coala_sampler_walk_batch_wait(g._h, ticket, C.byref(n_nodes), C.byref(n_bad)))
-    return WalkBatch(nodes, input_nodes[: n_nodes.value], pos, neg, tr, n_bad.value)
+    n_nodes, n_bad = _batch_collect(_lib.coala_sampler_walk_batch_wait, g, ticket)
+    return WalkBatch(nodes, input_nodes[:n_nodes], pos, neg, tr, n_bad)
 
 
 def walk_batch(g, nodes, p=1.0, q=1.0, walk_length=20, num_walks=1, num_neg=1, seed=0, step=0, traces=False):
@@ -1413,22 +1427,18 @@ def edge_batch(g, eids, num_neg, seed=0, step=0):
     pos = torch.empty((2, max(n, 1)), dtype=torch.int32, device=g.device)
     neg = torch.empty(max(n * num_neg, 1), dtype=torch.int32, device=g.device)
     out = _capi.EdgeBatchOut(nodes.data_ptr(), pos[0].data_ptr(), pos[1].data_ptr(), neg.data_ptr())
-    ticket = C.c_int64(-1)
-    mask = (1 << 64) - 1
-    _capi.check(_lib.coala_sampler_edge_batch(g._h, eids.data_ptr(), n, num_neg, int(seed) & mask, int(step) & mask, C.byref(out), C.byref(ticket),
-                                              current_stream()))
-    return (g, eids, n, num_neg, nodes, pos, neg, ticket.value)
+    ticket = _batch_begin(_lib.coala_sampler_edge_batch, g, eids.data_ptr(), n, num_neg, _u64(seed), _u64(step), C.byref(out))
+    return (g, eids, n, num_neg, nodes, pos, neg, ticket)
 
 
 def edge_batch_wait(pending):
     """Wait for the event behind an edge_batch call (only for its kernels) -> EdgeBatch.  IndexError when a seed edge was outside
     [0, num_edges); the graph handle stays usable."""
     g, eids, n, num_neg, nodes, pos, neg, ticket = pending
-    n_nodes, n_bad = C.c_int64(0), C.c_int64(0)
-    _capi.check(_lib.coala_sampler_edge_batch_wait(g._h, ticket, C.byref(n_nodes), C.byref(n_bad)))
-    if n_bad.value > 0:
-        raise IndexError(f"{n_bad.value} of the {n} seed edges are outside [0, {g.num_edges})")
-    return EdgeBatch(eids, nodes[: n_nodes.value], pos[0][:n], pos[1][:n], neg[: n * num_neg], num_neg)
+    n_nodes, n_bad = _batch_collect(_lib.coala_sampler_edge_batch_wait, g, ticket)
+    if n_bad > 0:
+        raise IndexError(f"{n_bad} of the {n} seed edges are outside [0, {g.num_edges})")
+    return EdgeBatch(eids, nodes[:n_nodes], pos[0][:n], pos[1][:n], neg[: n * num_neg], num_neg)
 
 
 def reverse_edge_ids(indptr, indices):
@@ -1449,7 +1459,34 @@ def reverse_edge_ids(indptr, indices):
     return order[at] if E else torch.zeros(0, dtype=torch.int64, device=indptr.device)
 
 
-class EdgePredictionSampler(object):
+class _EdgePrediction(object):
+    """What the two edge-prediction wrappers share: the negative sampler, the attributes the loader reads, make_graph, sample, and the
+    edge batch of the seed edges.  A wrapper checks its inner sampler, then adds sample_begin / sample_end."""
+
+    def __init__(self, sampler, negative_sampler, bucket_by_owner):
+        if negative_sampler is not None and not isinstance(negative_sampler, UniformNegativeSampler):
+            raise ValueError("negative_sampler: a UniformNegativeSampler, or None")
+        self.sampler = sampler
+        self.num_neg = negative_sampler.k if negative_sampler is not None else 0
+        # what the loader takes as fan_out: it sizes its fetch buffers as batch * prod(f + 1), and a batch of seed edges has up to
+        # batch * (2 + k) seed nodes -- one more entry, 1 + k, makes that product the bound of the input nodes
+        self.fanouts = list(sampler.fanouts) + [1 + self.num_neg]
+        self.bucket_by_owner = bucket_by_owner
+        self.stream_safe = sampler.stream_safe
+        self.completes_on_host = sampler.completes_on_host
+
+    make_graph = staticmethod(NeighborSampler.make_graph)
+
+    def sample(self, g, eids, step=None):
+        """-> (input_nodes, EdgeBatch, blocks), blocks[0] the input layer; blocks[-1]'s destination nodes (items) are the batch's seeds."""
+        return self.sample_end(self.sample_begin(g, eids, step))
+
+    def _edge_batch(self, g, eids, step):
+        """The edge batch of the seed edges at the inner sampler's seed and step, waited for: the one host wait of a wrapper."""
+        return edge_batch_wait(edge_batch(g, eids, self.num_neg, self.sampler.seed, self.sampler.step if step is None else int(step)))
+
+
+class EdgePredictionSampler(_EdgePrediction):
     """Link-prediction minibatches, DGL's dgl.dataloading.as_edge_prediction_sampler: wraps a NeighborSampler, LaborSampler or
     RelNeighborSampler.  sample / sample_begin / sample_end take seed EDGE ids (CSC positions) and return (input_nodes, EdgeBatch,
     blocks): the endpoints of the seed edges and of k negative pairs per edge (negative_sampler, a UniformNegativeSampler) are made
@@ -1469,32 +1506,16 @@ class EdgePredictionSampler(object):
             raise ValueError(f"exclude {exclude!r}: None, 'self' or 'reverse_id'")
         if exclude == "reverse_id" and reverse_eids is None:
             raise ValueError("exclude='reverse_id' needs reverse_eids (reverse_edge_ids(indptr, indices))")
-        if negative_sampler is not None and not isinstance(negative_sampler, UniformNegativeSampler):
-            raise ValueError("negative_sampler: a UniformNegativeSampler, or None")
-        self.sampler, self.exclude, self.reverse_eids = sampler, exclude, reverse_eids
-        self.num_neg = negative_sampler.k if negative_sampler is not None else 0
+        super().__init__(sampler, negative_sampler, sampler.bucket_by_owner)
+        self.exclude, self.reverse_eids = exclude, reverse_eids
         if exclude is not None:
             sampler.edge_ids = True
-        # what the loader takes as fan_out: it sizes its fetch buffers as batch * prod(f + 1), and a batch of seed edges has up to
-        # batch * (2 + k) seed nodes -- one more entry, 1 + k, makes that product the bound of the input nodes
-        self.fanouts = list(sampler.fanouts) + [1 + self.num_neg]
-        self.bucket_by_owner = sampler.bucket_by_owner
-        self.stream_safe = sampler.stream_safe
-        self.completes_on_host = sampler.completes_on_host
-
-    def make_graph(self, indptr, indices, ndata=None, edata=None):
-        return CSCGraph(indptr, indices, ndata, edata)
-
-    def sample(self, g, eids, step=None):
-        """-> (input_nodes, EdgeBatch, blocks), blocks[0] the input layer; blocks[-1]'s destination nodes are batch.seed_nodes."""
-        return self.sample_end(self.sample_begin(g, eids, step))
 
     def sample_begin(self, g, eids, step=None):
         """Enqueue the edge batch, wait for its two counts (the one host wait of the wrapper), then enqueue the inner sample over the
         batch's seed nodes.  -> the inner sampler's pending record, its `batch` the EdgeBatch."""
         g = _as_graph(g)
-        st = self.sampler.step if step is None else int(step)
-        batch = edge_batch_wait(edge_batch(g, eids, self.num_neg, self.sampler.seed, st))
+        batch = self._edge_batch(g, eids, step)
         pending = self.sampler.sample_begin(g, batch.seed_nodes, step)
         pending.batch = batch
         return pending
@@ -1511,7 +1532,7 @@ class EdgePredictionSampler(object):
         return input_nodes, batch, blocks
 
 
-class TemporalEdgePredictionSampler(object):
+class TemporalEdgePredictionSampler(_EdgePrediction):
     """Link-prediction minibatches on a graph with time (PyG's LinkNeighborLoader(edge_label_time=)): wraps a TemporalNeighborSampler,
     same sample / sample_begin / sample_end / fanouts as EdgePredictionSampler.  Seed edge e is queried at t_e = its own timestamp: its
     two endpoints and the destinations of its k uniform negatives (the edge_batch kernels, unchanged) become the pairs (node, t_e).
@@ -1524,29 +1545,14 @@ class TemporalEdgePredictionSampler(object):
             raise ValueError("TemporalEdgePredictionSampler wraps a TemporalNeighborSampler")
         if sampler.inclusive:
             raise ValueError("TemporalEdgePredictionSampler needs inclusive=False: with ts <= t the seed edge itself would be eligible")
-        if negative_sampler is not None and not isinstance(negative_sampler, UniformNegativeSampler):
-            raise ValueError("negative_sampler: a UniformNegativeSampler, or None")
-        self.sampler = sampler
-        self.num_neg = negative_sampler.k if negative_sampler is not None else 0
-        self.fanouts = list(sampler.fanouts) + [1 + self.num_neg]   # EdgePredictionSampler's bound of the input nodes
-        self.bucket_by_owner = 0
-        self.stream_safe = sampler.stream_safe
-        self.completes_on_host = sampler.completes_on_host
-
-    def make_graph(self, indptr, indices, ndata=None, edata=None):
-        return CSCGraph(indptr, indices, ndata, edata)
-
-    def sample(self, g, eids, step=None):
-        """-> (input_nodes, EdgeBatch, blocks), blocks[0] the input layer; blocks[-1]'s destination items are the batch's seed pairs."""
-        return self.sample_end(self.sample_begin(g, eids, step))
+        super().__init__(sampler, negative_sampler, 0)
 
     def sample_begin(self, g, eids, step=None):
         """Enqueue the edge batch and wait for its counts, make the distinct (node, t_e) pairs in plain torch, then enqueue the inner
         sample over them.  -> the inner sampler's pending record, its `batch` the EdgeBatch."""
         g = _as_graph(g)
         ts = g.edge_times(self.sampler.time)   # raises before any launch
-        st = self.sampler.step if step is None else int(step)
-        raw = edge_batch_wait(edge_batch(g, eids, self.num_neg, self.sampler.seed, st))
+        raw = self._edge_batch(g, eids, step)
         n, k = raw.eids.numel(), self.num_neg
         t_e = ts[raw.eids]
         at = torch.cat([raw.pos_src, raw.pos_dst, raw.neg_dst]).to(torch.int64)          # the items [src.. | dst.. | negatives..]

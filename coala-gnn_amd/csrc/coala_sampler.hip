@@ -1700,10 +1700,10 @@ __global__ __launch_bounds__(kBlock) void edge_relabel_clear_kernel(int64_t n, i
 
 struct coala_sampler {
     struct RingInfo { // what coala_sampler_wait_layers needs of a call to read its counts and explain a refusal
+        // a batch's slot holds n_nodes and n_bad, collected by coala_sampler_edge_batch_wait / coala_sampler_walk_batch_wait
+        enum class Holds { sample, edge_batch, walk_batch } holds = Holds::sample;
         int n_layers = 0, n_parts = 0;
         bool all_ragged = false; // a LABOR or a relation call: every layer is ragged, whatever its fan-out
-        bool edge_batch = false; // coala_sampler_edge_batch: the slot holds n_nodes and n_bad, collected by coala_sampler_edge_batch_wait
-        bool walk_batch = false; // coala_sampler_walk_batch: the same two words, collected by coala_sampler_walk_batch_wait
         int64_t n_seeds = 0;
         bool ragged(int l) const { return all_ragged || fanouts[l] == -1; } // CSR block, sizes known on the device only
         int32_t fanouts[COALA_SAMPLER_MAX_LAYERS] = {}; // of a relation call: -1 for a layer whose fan-outs are all -1, else 0
@@ -1739,6 +1739,7 @@ struct coala_sampler {
 
 namespace {
 using RingInfo = coala_sampler::RingInfo;
+using Holds = RingInfo::Holds;
 constexpr int kSlot = kPinParts + kMaxParts; // int64 words per ring slot
 
 // One sampling call, as its entry point hands it to sample_impl: its kind -- how a fixed layer picks its edges; the kinds exclude each
@@ -1794,12 +1795,23 @@ int check_call(const coala_sampler_t* s, const Call& c) {
     return COALA_OK;
 }
 
-// The ring slot of one of the last kRing calls.
-int ring_slot(const coala_sampler_t* s, int64_t ticket, int* slot) {
+// A batch kind in the words of a refusal: "an edge batch" / "a walk batch", and the "edge" / "walk" of its entry points' names.
+const char* batch_noun(Holds k) { return k == Holds::edge_batch ? "an edge batch" : "a walk batch"; }
+const char* batch_stem(Holds k) { return k == Holds::edge_batch ? "edge" : "walk"; }
+
+// What every wait begins with: the ring slot of one of the last kRing calls, which has to be a call of the kind this wait collects, and
+// the event behind that call's last kernel.  A refused wait has waited for nothing.
+int wait_slot(coala_sampler_t* s, int64_t ticket, Holds kind, int* slot) {
     if (!s) return fail(COALA_EINVAL, "null sampler");
     if (ticket < 0 || (uint64_t)ticket >= s->calls || s->calls - (uint64_t)ticket > kRing)
         return fail(COALA_EINVAL, "ticket %lld is not one of the last %d calls", (long long)ticket, kRing);
     *slot = (int)((uint64_t)ticket % kRing);
+    const Holds holds = s->ring[*slot].holds;
+    if (holds != kind && kind != Holds::sample) return fail(COALA_EINVAL, "ticket %lld is not %s", (long long)ticket, batch_noun(kind));
+    if (holds != kind)
+        return fail(COALA_EINVAL, "ticket %lld is %s: collect it with coala_sampler_%s_batch_wait", (long long)ticket, batch_noun(holds), batch_stem(holds));
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipEventSynchronize(s->done[*slot])); // the kernels behind this event stored the counts into pinned host memory
     return COALA_OK;
 }
 
@@ -1830,15 +1842,20 @@ int fixed_run_check(const RingInfo& r, int l, int64_t n_src, int64_t* items_out,
     return -1;
 }
 
+int batch_wait(coala_sampler_t* s, int64_t ticket, Holds kind, int64_t* n_nodes_host, int64_t* n_bad_host) {
+    int slot;
+    if (int rc = wait_slot(s, ticket, kind, &slot)) return rc;
+    const int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
+    if (n_nodes_host) *n_nodes_host = pin[0];
+    if (n_bad_host) *n_bad_host = pin[kPinEdges];
+    return COALA_OK;
+}
+
 int wait_impl(coala_sampler_t* s, int64_t ticket, int64_t* n_src_host, int64_t* n_edges_host, int64_t* bucket_counts_host) {
     int slot;
-    if (int rc = ring_slot(s, ticket, &slot)) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipEventSynchronize(s->done[slot])); // the kernels behind this event stored the counts into pinned host memory
+    if (int rc = wait_slot(s, ticket, Holds::sample, &slot)) return rc;
     const int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
     const RingInfo& r = s->ring[slot];
-    if (r.edge_batch) return fail(COALA_EINVAL, "ticket %lld is an edge batch: collect it with coala_sampler_edge_batch_wait", (long long)ticket);
-    if (r.walk_batch) return fail(COALA_EINVAL, "ticket %lld is a walk batch: collect it with coala_sampler_walk_batch_wait", (long long)ticket);
     if (n_src_host)
         for (int l = 0; l < r.n_layers; ++l) n_src_host[l] = pin[l];
     if (n_edges_host)
@@ -2109,19 +2126,20 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
 }
 
 // A new call's stream hand-over and ring slot.  The handle's scratch (hash table, scan state) is ordered by the stream of its calls.
-int begin_call(coala_sampler_t* s, hipStream_t st, uint64_t* ticket, int* slot) {
+int begin_call(coala_sampler_t* s, hipStream_t st, int* slot) {
     HIPCHK(hipSetDevice(s->device));
     if (s->calls > 0 && s->last_stream != st) HIPCHK(hipStreamWaitEvent(st, s->done[(s->calls - 1) % kRing], 0)); // behind the previous call's last kernel
     s->last_stream = st;
-    *ticket = s->calls;
-    *slot = (int)(*ticket % kRing);
-    if (*ticket >= kRing) HIPCHK(hipEventSynchronize(s->done[*slot])); // the ring slot's previous user has finished writing it
+    *slot = (int)(s->calls % kRing);
+    if (s->calls >= kRing) HIPCHK(hipEventSynchronize(s->done[*slot])); // the ring slot's previous user has finished writing it
     return COALA_OK;
 }
 
-// The event behind the call's last kernel, and its ticket.
-int end_call(coala_sampler_t* s, int slot, hipStream_t st, int64_t* ticket_out) {
+// The call is committed: the event behind its last kernel, its record on the ring, and its ticket.  Until here the slot still describes
+// ticket calls - kRing, which wait_slot accepts.
+int end_call(coala_sampler_t* s, int slot, hipStream_t st, const RingInfo& info, int64_t* ticket_out) {
     HIPCHK(hipEventRecord(s->done[slot], st));
+    s->ring[slot] = info;
     if (ticket_out) *ticket_out = (int64_t)s->calls;
     s->calls++;
     return COALA_OK;
@@ -2139,15 +2157,17 @@ int prepare_table(coala_sampler_t* s, uint64_t items0, hipStream_t st) {
     return COALA_OK;
 }
 
-// Every launch of a call with seeds: the first layer's table, then the layers, each reading its destination nodes from the one before.
+// Every launch of a call with seeds: the layers, each reading its destination nodes from the one before.  The table of a fixed first
+// layer is ring_call's business (p.items0); that of a ragged one is cleared here, by what its degree scan finds.
 int launch_call(coala_sampler_t* s, Plan& p) {
     int rc;
     const bool first_full = p.info.ragged(0);
-    // what the last kernel leaves clean for the next call: the first layer's table of this call, or -- when that size is known on
-    // the device only -- the extent the previous call left clean
-    p.items0 = first_full ? std::max<uint64_t>(s->clean_items, 1) : (uint64_t)p.info.n_seeds * (uint64_t)(p.info.fanouts[0] + 1);
-    if (first_full) s->clean_items = 0; // table_clear_kernel below clears what the degree scan finds
-    else if ((rc = prepare_table(s, p.items0, p.st))) return rc;
+    if (first_full) {
+        // what the last kernel leaves clean for the next call: the first layer's table of this call, or -- when that size is known on
+        // the device only, as here -- the extent the previous call left clean
+        p.items0 = std::max<uint64_t>(s->clean_items, 1);
+        s->clean_items = 0;
+    }
     if (p.kind == Kind::weighted && s->hub_cap > 0) HIPCHK(hipMemsetAsync(s->hub_count, 0, (size_t)p.n_layers * sizeof(unsigned long long), p.st));
     if (first_full) {
         if ((rc = degree_scan(s, p, 0, p.seeds, nullptr))) return rc;
@@ -2161,19 +2181,86 @@ int launch_call(coala_sampler_t* s, Plan& p) {
     return COALA_OK;
 }
 
-int sample_impl(coala_sampler_t* s, const Call& c) {
+// One call on the handle's ring, the only place that takes and commits a slot: the stream hand-over and the slot, the scratch (cap,
+// max_items, max_nbr: grow_workspace's) and the table of a first layer of items0 items (0: an empty call, or a ragged first layer, whose
+// size the host does not know), then body(pin, pin_dev) -- every launch of the call, or the words an empty call writes from the host,
+// given the slot's pinned words as the host and the device see them -- and the commit.  A call that fails on the way leaves the ring's
+// records as they were.
+template <typename F>
+int ring_call(coala_sampler_t* s, hipStream_t st, const RingInfo& info, uint64_t cap, uint64_t max_items, uint64_t max_nbr, uint64_t items0,
+              int64_t* ticket_out, F&& body) {
     int rc, slot;
+    if ((rc = begin_call(s, st, &slot))) return rc;
+    if ((rc = grow_workspace(s, st, info.n_parts, cap, max_items, max_nbr))) return rc;
+    if (items0 > 0 && (rc = prepare_table(s, items0, st))) return rc;
+    if ((rc = body(s->counts_pinned + (size_t)slot * kSlot, s->counts_pinned_dev + (size_t)slot * kSlot))) return rc;
+    return end_call(s, slot, st, info, ticket_out);
+}
+
+int sample_impl(coala_sampler_t* s, const Call& c) {
+    int rc;
     if ((rc = check_call(s, c))) return rc;
     Plan p{c};
     if ((rc = plan_call(p))) return rc;
-    uint64_t ticket;
-    if ((rc = begin_call(s, c.st, &ticket, &slot))) return rc;
-    if ((rc = grow_workspace(s, c.st, p.info.n_parts, (uint64_t)p.items_cap[c.n_layers - 1], p.max_items, p.max_nbr))) return rc;
-    p.pin_dev = s->counts_pinned_dev + (size_t)slot * kSlot;
-    s->ring[slot] = p.info;
-    if ((rc = c.n_seeds == 0 ? empty_call(p, s->counts_pinned + (size_t)slot * kSlot) : launch_call(s, p))) return rc;
-    if ((rc = end_call(s, slot, c.st, c.ticket_out))) return rc;
-    if (c.n_src_host || c.n_edges_host) return wait_impl(s, (int64_t)ticket, c.n_src_host, c.n_edges_host, nullptr);
+    p.items0 = p.info.ragged(0) ? 0 : (uint64_t)c.n_seeds * (uint64_t)(c.fanouts[0] + 1);
+    rc = ring_call(s, c.st, p.info, (uint64_t)p.items_cap[c.n_layers - 1], p.max_items, p.max_nbr, p.items0, c.ticket_out,
+                   [&](int64_t* pin, int64_t* pin_dev) {
+                       p.pin_dev = pin_dev;
+                       return c.n_seeds == 0 ? empty_call(p, pin) : launch_call(s, p);
+                   });
+    if (rc == COALA_OK && (c.n_src_host || c.n_edges_host)) return wait_impl(s, (int64_t)s->calls - 1, c.n_src_host, c.n_edges_host, nullptr);
+    return rc;
+}
+
+// What an edge batch and a walk batch have in common.  The batch's kernel writes an item list (endpoints and negatives; start nodes,
+// traces and negatives); the list then goes through the handle's hash table and scan as the destination nodes of one fixed layer of
+// fan-out 0 do, and comes out as the list of its distinct nodes and every item's place in it.
+struct ItemBatch {
+    Holds kind;
+    int64_t items;      // 0: an empty batch, nothing is launched
+    hipStream_t st;
+    int64_t* nodes_out; // device int64[items]: the distinct nodes in order of first appearance
+    int64_t* ticket_out;
+};
+
+// The batch takes a ring slot, the handle's scratch and its table as a sample of one fixed layer over `items` items does (what it records
+// on the ring: no parts, one layer, `items` seeds): three launches -- the kind's items kernel (launch_items()), the layers' scan_assign,
+// the kind's relabel-and-clear kernel (launch_relabel(grid, the slot's device word for n_bad)) --, n_nodes and n_bad into the slot's
+// pinned words, and the table left clean for `items` items.
+template <typename Items, typename Relabel>
+int item_batch(coala_sampler_t* s, const ItemBatch& b, Items&& launch_items, Relabel&& launch_relabel) {
+    const RingInfo info{b.kind, 1, 0, false, b.items};
+    const uint64_t items = (uint64_t)b.items;
+    return ring_call(s, b.st, info, items, items, items, items, b.ticket_out, [&](int64_t* pin, int64_t* pin_dev) -> int {
+        if (b.items == 0) {
+            pin[0] = pin[kPinEdges] = 0;
+            return COALA_OK;
+        }
+        launch_items();
+        if (int rc = next_gen(s, b.st)) return rc;
+        const int tiles = grid1d(b.items, kTile, kMaxTiles);
+        // the item list as the "destination nodes" of a layer of fan-out 0: n_items = items, item p is items[p]
+        hipLaunchKernelGGL(scan_assign_kernel<false>, dim3(tiles), dim3(kBlock), 0, b.st, (const int64_t*)s->nbr_global,
+                           (const int64_t*)s->nbr_global, (const int64_t*)nullptr, b.items, 0, (const uint32_t*)s->slot_of_item, s->tb, s->status,
+                           s->ticket, s->ticket_total, s->scan_gen & 0x3FFFFFFFull, b.nodes_out, s->counts_dev + 1, pin_dev);
+        s->ticket_total += (unsigned long long)tiles;
+        launch_relabel(dim3(grid1d(std::max<int64_t>(b.items, table_size(b.items)), kBlock, 4096)), pin_dev + kPinEdges);
+        s->clean_items = items;
+        HIPCHK(hipGetLastError());
+        return COALA_OK;
+    });
+}
+
+// The frame of the two trace entry points around their own range checks: a kernel on the caller's stream, off the ring.
+template <typename Check, typename Launch>
+int trace_call(coala_sampler_t* s, const int64_t* nodes, int64_t n, const int64_t* traces_out, Check&& check_ranges, Launch&& launch) {
+    if (!s || (n > 0 && (!nodes || !traces_out))) return fail(COALA_EINVAL, "null argument");
+    if (n < 0 || n > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad node count");
+    if (int rc = check_ranges()) return rc;
+    if (n == 0) return COALA_OK;
+    HIPCHK(hipSetDevice(s->device));
+    launch();
+    HIPCHK(hipGetLastError());
     return COALA_OK;
 }
 
@@ -2181,8 +2268,6 @@ int sample_impl(coala_sampler_t* s, const Call& c) {
 
 extern "C" {
 
-// An edge batch takes a ring slot and the handle's scratch as a sample of one fixed layer over n (2 + k) items does (begin_call,
-// prepare_table, end_call): three launches, the counts into the slot's pinned words.
 int coala_sampler_edge_batch(coala_sampler_t* s, const int64_t* eids, int64_t n, int num_neg, uint64_t seed, uint64_t step,
                              const coala_edge_batch_t* out, int64_t* ticket_out, void* stream) {
     if (!s || !out || (!eids && n > 0)) return fail(COALA_EINVAL, "null argument");
@@ -2194,49 +2279,19 @@ int coala_sampler_edge_batch(coala_sampler_t* s, const int64_t* eids, int64_t n,
                     (long long)items, (long long)kItemLimit);
     if (n > 0 && (!out->seed_nodes || !out->pos_src || !out->pos_dst || (num_neg > 0 && !out->neg_dst))) return fail(COALA_EINVAL, "null buffer");
     hipStream_t st = (hipStream_t)stream;
-    int rc, slot;
-    uint64_t ticket;
-    if ((rc = begin_call(s, st, &ticket, &slot))) return rc;
-    if ((rc = grow_workspace(s, st, 0, (uint64_t)items, (uint64_t)items, (uint64_t)items))) return rc;
-    int64_t* pin_dev = s->counts_pinned_dev + (size_t)slot * kSlot;
-    RingInfo& r = s->ring[slot] = RingInfo{};
-    r.n_layers = 1;
-    r.n_seeds = items;
-    r.edge_batch = true;
-    if (n == 0) {
-        int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
-        pin[0] = pin[kPinEdges] = 0;
-    } else {
-        if ((rc = prepare_table(s, (uint64_t)items, st))) return rc;
-        const dim3 blk(kBlock);
-        hipLaunchKernelGGL(edge_items_kernel, dim3(grid1d(items, kBlock, 8192)), blk, 0, st, s->g, s->num_edges, eids, n, num_neg, seed, step,
-                           s->nbr_global, s->tb, s->slot_of_item, s->edge_bad);
-        if ((rc = next_gen(s, st))) return rc;
-        const int tiles = grid1d(items, kTile, kMaxTiles);
-        // the item list as the "destination nodes" of a layer of fan-out 0: n_items = items, item p is items[p]
-        hipLaunchKernelGGL(scan_assign_kernel<false>, dim3(tiles), blk, 0, st, (const int64_t*)s->nbr_global, (const int64_t*)s->nbr_global,
-                           (const int64_t*)nullptr, items, 0, (const uint32_t*)s->slot_of_item, s->tb, s->status, s->ticket, s->ticket_total,
-                           s->scan_gen & 0x3FFFFFFFull, out->seed_nodes, s->counts_dev + 1, pin_dev);
-        s->ticket_total += (unsigned long long)tiles;
-        hipLaunchKernelGGL(edge_relabel_clear_kernel, dim3(grid1d(std::max<int64_t>(items, table_size(items)), kBlock, 4096)), blk, 0, st, n, num_neg,
-                           (const uint32_t*)s->slot_of_item, s->tb, out->pos_src, out->pos_dst, out->neg_dst, s->edge_bad, pin_dev + kPinEdges,
-                           items);
-        s->clean_items = (uint64_t)items;
-        HIPCHK(hipGetLastError());
-    }
-    return end_call(s, slot, st, ticket_out);
+    return item_batch(s, ItemBatch{Holds::edge_batch, items, st, out->seed_nodes, ticket_out},
+        [&] {
+            hipLaunchKernelGGL(edge_items_kernel, dim3(grid1d(items, kBlock, 8192)), dim3(kBlock), 0, st, s->g, s->num_edges, eids, n, num_neg, seed,
+                               step, s->nbr_global, s->tb, s->slot_of_item, s->edge_bad);
+        },
+        [&](dim3 grid, int64_t* n_bad_pin) {
+            hipLaunchKernelGGL(edge_relabel_clear_kernel, grid, dim3(kBlock), 0, st, n, num_neg, (const uint32_t*)s->slot_of_item, s->tb, out->pos_src,
+                               out->pos_dst, out->neg_dst, s->edge_bad, n_bad_pin, items);
+        });
 }
 
 int coala_sampler_edge_batch_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_nodes_host, int64_t* n_bad_host) {
-    int slot;
-    if (int rc = ring_slot(s, ticket, &slot)) return rc;
-    if (!s->ring[slot].edge_batch) return fail(COALA_EINVAL, "ticket %lld is not an edge batch", (long long)ticket);
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipEventSynchronize(s->done[slot]));
-    const int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
-    if (n_nodes_host) *n_nodes_host = pin[0];
-    if (n_bad_host) *n_bad_host = pin[kPinEdges];
-    return COALA_OK;
+    return batch_wait(s, ticket, Holds::edge_batch, n_nodes_host, n_bad_host);
 }
 
 int coala_sampler_create(int device, const int64_t* indptr, const int64_t* indices, int64_t num_nodes, int64_t num_edges,
@@ -2416,18 +2471,17 @@ int coala_sampler_sample_layers_temporal(coala_sampler_t* s, const int64_t* seed
 
 int coala_sampler_random_walk(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t term_threshold,
                               uint64_t seed, uint64_t step, int layer, int64_t* traces_out, void* stream) {
-    if (!s || (n > 0 && (!nodes || !traces_out))) return fail(COALA_EINVAL, "null argument");
-    if (n < 0 || n > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad node count");
-    if (num_walks < 1 || num_walks > kMaxWalks) return fail(COALA_EINVAL, "num_walks %d outside 1..%d", num_walks, kMaxWalks);
-    if (length < 1 || length > kMaxWalkLength) return fail(COALA_EINVAL, "length %d outside 1..%d", length, kMaxWalkLength);
-    if (term_threshold >= kWalkThresholdMax) return fail(COALA_EINVAL, "term_threshold must be below 2^53 (restart_prob < 1)");
-    if (layer < 0 || layer >= COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "layer must be 0..%d", COALA_SAMPLER_MAX_LAYERS - 1);
-    if (n == 0) return COALA_OK;
-    HIPCHK(hipSetDevice(s->device));
-    hipLaunchKernelGGL(walk_trace_kernel, dim3(grid1d(n * num_walks, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, s->g, nodes, n,
-                       WalkParams{length, num_walks, term_threshold}, seed, step, layer, traces_out);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
+    auto check_ranges = [&] {
+        if (num_walks < 1 || num_walks > kMaxWalks) return fail(COALA_EINVAL, "num_walks %d outside 1..%d", num_walks, kMaxWalks);
+        if (length < 1 || length > kMaxWalkLength) return fail(COALA_EINVAL, "length %d outside 1..%d", length, kMaxWalkLength);
+        if (term_threshold >= kWalkThresholdMax) return fail(COALA_EINVAL, "term_threshold must be below 2^53 (restart_prob < 1)");
+        if (layer < 0 || layer >= COALA_SAMPLER_MAX_LAYERS) return fail(COALA_EINVAL, "layer must be 0..%d", COALA_SAMPLER_MAX_LAYERS - 1);
+        return COALA_OK;
+    };
+    return trace_call(s, nodes, n, traces_out, check_ranges, [&] {
+        hipLaunchKernelGGL(walk_trace_kernel, dim3(grid1d(n * num_walks, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, s->g, nodes, n,
+                           WalkParams{length, num_walks, term_threshold}, seed, step, layer, traces_out);
+    });
 }
 
 // The three thresholds of a second-order walk: each in [0, 2^32], the largest exactly 2^32 (the host normalises by max(1/p, 1, 1/q)).
@@ -2442,18 +2496,12 @@ static int check_n2v(int num_walks, int length, uint64_t thr_ret, uint64_t thr_n
 
 int coala_sampler_node2vec_walk(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t thr_return,
                                 uint64_t thr_near, uint64_t thr_far, uint64_t seed, uint64_t step, int64_t* traces_out, void* stream) {
-    if (!s || (n > 0 && (!nodes || !traces_out))) return fail(COALA_EINVAL, "null argument");
-    if (n < 0 || n > 0x7FFFFFFF) return fail(COALA_EINVAL, "bad node count");
-    if (int rc = check_n2v(num_walks, length, thr_return, thr_near, thr_far)) return rc;
-    if (n == 0) return COALA_OK;
-    HIPCHK(hipSetDevice(s->device));
-    hipLaunchKernelGGL(node2vec_trace_kernel, dim3(grid1d(n * num_walks * kN2vGroup, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, s->g, nodes, n,
-                       N2vParams{length, num_walks, thr_return, thr_near, thr_far}, seed, step, traces_out);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
+    return trace_call(s, nodes, n, traces_out, [&] { return check_n2v(num_walks, length, thr_return, thr_near, thr_far); }, [&] {
+        hipLaunchKernelGGL(node2vec_trace_kernel, dim3(grid1d(n * num_walks * kN2vGroup, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, s->g, nodes,
+                           n, N2vParams{length, num_walks, thr_return, thr_near, thr_far}, seed, step, traces_out);
+    });
 }
 
-// A walk batch takes a ring slot and the handle's scratch as an edge batch does: three launches, the counts into the slot's pinned words.
 int coala_sampler_walk_batch(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t thr_return,
                              uint64_t thr_near, uint64_t thr_far, int num_neg, uint64_t seed, uint64_t step, const coala_walk_batch_t* out,
                              int64_t* ticket_out, void* stream) {
@@ -2468,50 +2516,21 @@ int coala_sampler_walk_batch(coala_sampler_t* s, const int64_t* nodes, int64_t n
                     (long long)n, num_walks, length, num_neg, (long long)std::max(stated, items), (long long)kItemLimit);
     if (n > 0 && (!out->input_nodes || !out->pos || (num_neg > 0 && !out->neg))) return fail(COALA_EINVAL, "null buffer");
     hipStream_t st = (hipStream_t)stream;
-    int rc, slot;
-    uint64_t ticket;
-    if ((rc = begin_call(s, st, &ticket, &slot))) return rc;
-    if ((rc = grow_workspace(s, st, 0, (uint64_t)items, (uint64_t)items, (uint64_t)items))) return rc;
-    int64_t* pin_dev = s->counts_pinned_dev + (size_t)slot * kSlot;
-    RingInfo& r = s->ring[slot] = RingInfo{};
-    r.n_layers = 1;
-    r.n_seeds = items;
-    r.walk_batch = true;
-    if (n == 0) {
-        int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
-        pin[0] = pin[kPinEdges] = 0;
-    } else {
-        if ((rc = prepare_table(s, (uint64_t)items, st))) return rc;
-        const dim3 blk(kBlock);
-        const N2vParams np{length, num_walks, thr_return, thr_near, thr_far};
-        const int64_t n_walks = n * num_walks;
-        hipLaunchKernelGGL(walk_items_kernel, dim3(grid1d(std::max<int64_t>(n_walks * kN2vGroup, n_walks * num_neg * length / 4), kBlock, 8192)), blk, 0, st, s->g,
-                           nodes, n, np, num_neg, seed, step, s->nbr_global, out->traces, s->tb, s->slot_of_item, s->edge_bad);
-        if ((rc = next_gen(s, st))) return rc;
-        const int tiles = grid1d(items, kTile, kMaxTiles);
-        // the item list as the "destination nodes" of a layer of fan-out 0, as in an edge batch
-        hipLaunchKernelGGL(scan_assign_kernel<false>, dim3(tiles), blk, 0, st, (const int64_t*)s->nbr_global, (const int64_t*)s->nbr_global,
-                           (const int64_t*)nullptr, items, 0, (const uint32_t*)s->slot_of_item, s->tb, s->status, s->ticket, s->ticket_total,
-                           s->scan_gen & 0x3FFFFFFFull, out->input_nodes, s->counts_dev + 1, pin_dev);
-        s->ticket_total += (unsigned long long)tiles;
-        hipLaunchKernelGGL(walk_relabel_clear_kernel, dim3(grid1d(std::max<int64_t>(items, table_size(items)), kBlock, 4096)), blk, 0, st, n, num_walks,
-                           length, num_neg, (const uint32_t*)s->slot_of_item, s->tb, out->pos, out->neg, s->edge_bad, pin_dev + kPinEdges, items);
-        s->clean_items = (uint64_t)items;
-        HIPCHK(hipGetLastError());
-    }
-    return end_call(s, slot, st, ticket_out);
+    return item_batch(s, ItemBatch{Holds::walk_batch, items, st, out->input_nodes, ticket_out},
+        [&] {
+            const N2vParams np{length, num_walks, thr_return, thr_near, thr_far};
+            const int64_t n_walks = n * num_walks;
+            hipLaunchKernelGGL(walk_items_kernel, dim3(grid1d(std::max<int64_t>(n_walks * kN2vGroup, n_walks * num_neg * length / 4), kBlock, 8192)),
+                               dim3(kBlock), 0, st, s->g, nodes, n, np, num_neg, seed, step, s->nbr_global, out->traces, s->tb, s->slot_of_item, s->edge_bad);
+        },
+        [&](dim3 grid, int64_t* n_bad_pin) {
+            hipLaunchKernelGGL(walk_relabel_clear_kernel, grid, dim3(kBlock), 0, st, n, num_walks, length, num_neg, (const uint32_t*)s->slot_of_item, s->tb,
+                               out->pos, out->neg, s->edge_bad, n_bad_pin, items);
+        });
 }
 
 int coala_sampler_walk_batch_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_nodes_host, int64_t* n_bad_host) {
-    int slot;
-    if (int rc = ring_slot(s, ticket, &slot)) return rc;
-    if (!s->ring[slot].walk_batch) return fail(COALA_EINVAL, "ticket %lld is not a walk batch", (long long)ticket);
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipEventSynchronize(s->done[slot]));
-    const int64_t* pin = s->counts_pinned + (size_t)slot * kSlot;
-    if (n_nodes_host) *n_nodes_host = pin[0];
-    if (n_bad_host) *n_bad_host = pin[kPinEdges];
-    return COALA_OK;
+    return batch_wait(s, ticket, Holds::walk_batch, n_nodes_host, n_bad_host);
 }
 
 } // extern "C"

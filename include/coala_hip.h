@@ -554,9 +554,11 @@ int coala_sampler_wait_layers(coala_sampler_t* s, int64_t ticket, int64_t* n_src
  * int32[n, num_neg]: where every item sits in seed_nodes.  The source of a negative is its edge's pos_src.  An e outside [0, num_edges)
  * gives -1 in all of its entries, adds no node and is counted in n_bad.  Nothing is written past these capacities.
  * Limit: n (2 + num_neg) <= 8,388,608 items; COALA_EINVAL (with a message) before any launch otherwise, and for num_neg outside 0..64.
- * Three launches on `stream` (items + hash insert, the layers' scan_assign, relabel + table clear); no memset, copy or wait.  The call
- * takes a ticket of the handle's ring like a sample; n_nodes and n_bad go to pinned host memory from the kernels and
- * coala_sampler_edge_batch_wait collects them behind the call's event (coala_sampler_wait refuses such a ticket, and the reverse). */
+ * Three launches on `stream` (items + hash insert, the layers' scan_assign, relabel + table clear); no memset, copy or wait.
+ * The batch contract, which coala_sampler_walk_batch shares: the call takes a ticket of the handle's ring like a sample; n_nodes and n_bad
+ * go to pinned host memory from the kernels, and the batch kind's own wait (coala_sampler_edge_batch_wait, coala_sampler_walk_batch_wait)
+ * collects them behind the call's event.  Each kind of wait -- these two, coala_sampler_wait and coala_sampler_wait_layers -- refuses the
+ * other kinds' tickets with COALA_EINVAL, without waiting. */
 typedef struct coala_edge_batch {
     int64_t* seed_nodes; /* int64[n (2 + num_neg)]                     */
     int32_t* pos_src;    /* int32[n]                                   */
@@ -591,8 +593,7 @@ int coala_sampler_node2vec_walk(coala_sampler_t* s, const int64_t* nodes, int64_
  *   traces int64[n, W, L + 1], nullable: the global-id traces, bit-identical to coala_sampler_node2vec_walk's.
  * Nothing is written past these capacities.  Limit: n W (L + 1) (1 + num_neg) <= 8,388,608 items; COALA_EINVAL (with a message) before
  * any launch otherwise, and for arguments coala_sampler_node2vec_walk refuses.  Three launches on `stream`; no memset, copy or wait.
- * The call takes a ticket of the handle's ring; n_nodes and n_bad (out-of-range start nodes) go to pinned host memory from the kernels
- * and coala_sampler_walk_batch_wait collects them behind the call's event.  Each kind of wait refuses the other kinds' tickets. */
+ * Ticket, pinned words and wait: the batch contract of coala_sampler_edge_batch; n_bad counts the out-of-range start nodes. */
 typedef struct coala_walk_batch {
     int64_t* input_nodes;
     int32_t* pos;
