@@ -46,6 +46,19 @@ def negatives(num_nodes, eids, k, seed, step):
     return out
 
 
+def negatives_vec(num_nodes, eids, k, seed, step):
+    """negatives() in numpy uint64 (wrapping arithmetic), for batches of millions of draws; test_item_batch_large_cpu.py holds it to the
+    Python-integer form above, which stays the definition."""
+    from _labor_ref import mulhi64, splitmix64 as mix
+    e = np.asarray(eids, dtype=np.int64).astype(np.uint64)
+    h = splitmix64((seed & M64) ^ 0x9E3779B97F4A7C15)                  # sample_key's first two rounds do not depend on e
+    h = splitmix64(h ^ (((step & M64) * 0xD1B54A32D192ED03) & M64))
+    with np.errstate(over="ignore"):
+        nkey = mix(np.uint64(h) ^ e) ^ np.uint64(K_NEG)
+        draws = mix(nkey[:, None] + np.arange(k, dtype=np.uint64)[None, :])
+    return mulhi64(draws, np.uint64(num_nodes)).astype(np.int64).reshape(len(e), k)
+
+
 def compact(items):
     """items int64 (-1: none) -> (the distinct ids >= 0 in order of first appearance, every item's index in that list or -1)."""
     items = np.asarray(items, dtype=np.int64)
@@ -59,12 +72,13 @@ def compact(items):
     return uniq[order], local
 
 
-def edge_batch(indptr, indices, eids, k, seed, step):
-    """-> dict(seed_nodes int64, pos_src, pos_dst int32 [n], neg_dst int32 [n, k], n_bad)."""
+def edge_batch(indptr, indices, eids, k, seed, step, draw=negatives):
+    """-> dict(seed_nodes int64, pos_src, pos_dst int32 [n], neg_dst int32 [n, k], n_bad).  draw: negatives, or negatives_vec for a
+    batch too large for Python integers."""
     eids = np.asarray(eids, dtype=np.int64)
     n, N = len(eids), len(indptr) - 1
     src, dst = endpoints(indptr, indices, eids)
-    neg = negatives(N, eids, k, seed, step)
+    neg = draw(N, eids, k, seed, step)
     neg[src < 0] = -1
     nodes, local = compact(np.concatenate([src, dst, neg.reshape(-1)]))
     return dict(seed_nodes=nodes, pos_src=local[:n].astype(np.int32), pos_dst=local[n: 2 * n].astype(np.int32),
@@ -134,5 +148,22 @@ def symmetric_graph(num_nodes, avg_degree, seed=0):
     return indptr, src.astype(np.int64)
 
 
-__all__ = ["splitmix64", "sample_key", "endpoints", "negatives", "compact", "edge_batch", "exclude_fixed", "exclude_csr", "with_zero_runs",
+def large_graph(num_nodes=300_007, avg_degree=6, hub_degree=4000, seed=0):
+    """The graph of the item-batch limit tests: symmetric_graph, then a few nodes lose every in-edge (the first, the last, three in the
+    middle) and one hub gains in-edges up to about hub_degree; rows rebuilt sorted by source.  Large enough that the negatives of a batch
+    of millions are mostly distinct.  -> (indptr, indices, hub node, the degree-0 nodes)."""
+    ip, ix = symmetric_graph(num_nodes, avg_degree, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    zeros = np.array([0, num_nodes // 3, num_nodes // 3 + 1, num_nodes // 2, num_nodes - 1], dtype=np.int64)
+    hub = num_nodes // 5
+    dst = np.repeat(np.arange(num_nodes, dtype=np.int64), np.diff(ip))
+    keep = ~np.isin(dst, zeros)
+    extra = rng.choice(num_nodes, size=hub_degree, replace=False).astype(np.int64)
+    key = np.unique(np.concatenate([dst[keep] * num_nodes + ix[keep], hub * num_nodes + extra]))     # sorted by (dst, src), no repeats
+    indptr = np.zeros(num_nodes + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // num_nodes, minlength=num_nodes), out=indptr[1:])
+    return indptr, (key % num_nodes).astype(np.int64), hub, zeros
+
+
+__all__ = ["splitmix64", "sample_key", "endpoints", "negatives", "negatives_vec", "compact", "edge_batch", "large_graph", "exclude_fixed", "exclude_csr", "with_zero_runs",
            "brute_force_rows", "link_graph", "symmetric_graph", "csc_from_columns", "K_NEG", "K_OTHERS", "CHI2_63_BOUND"]

@@ -143,6 +143,109 @@ def walk_batch(indptr, indices, nodes, L, W, K, thr, seed, step):
     return dict(input_nodes=input_nodes, pos=pos, neg=neg, traces=tr, n_bad=int((~ok).sum()))
 
 
+# ------------------------------------------------------------------------------------------------------------ vectorised forms
+# The same rules in numpy uint64 (wrapping arithmetic), for batches of millions of items.  The Python-integer forms above stay the
+# definition; test_item_batch_large_cpu.py holds these to them bit for bit.
+def _walk_keys_vec(nodes, W, seed, step):
+    """kw of every (start node, walk): uint64 [n, W]."""
+    from _labor_ref import splitmix64
+    v = np.asarray(nodes, dtype=np.int64).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        wkey = splitmix64(np.uint64(_outer_key(seed, step)) ^ v) ^ np.uint64(STREAM)
+        return splitmix64(wkey[:, None] + np.arange(W, dtype=np.uint64)[None, :])
+
+
+def traces_vec(indptr, indices, nodes, L, W, thr, seed, step, swap_classes=False):
+    """traces() for every walk at once: per hop, over the walks still alive, an attempt loop over the walks still undecided.  The near
+    test is a binary search in the keys row * span + source of the whole CSC, so every row must be sorted by source (what the device
+    needs at q != 1 as well)."""
+    from _labor_ref import mulhi64, splitmix64
+    indptr, indices = np.asarray(indptr, dtype=np.int64), np.asarray(indices, dtype=np.int64)
+    nodes = np.asarray(nodes, dtype=np.int64)
+    n, N = len(nodes), len(indptr) - 1
+    t_ret, t_near, t_far = (np.uint64(t) for t in thr)
+    if swap_classes:
+        t_ret, t_near = t_near, t_ret
+    lo = int(indices.min()) if len(indices) else 0
+    span = (int(indices.max()) - lo + 1) if len(indices) else 1
+    edge_key = np.repeat(np.arange(N, dtype=np.int64), np.diff(indptr)) * span + (indices - lo)
+    assert np.all(np.diff(edge_key) >= 0), "traces_vec needs every row sorted by source"
+
+    def in_row(row, x):                                     # does x occur in row `row`?
+        inside = (x >= lo) & (x < lo + span)
+        want = row * span + (np.where(inside, x, lo) - lo)
+        at = np.minimum(np.searchsorted(edge_key, want), max(len(edge_key) - 1, 0))
+        return inside & (edge_key[at] == want) if len(edge_key) else np.zeros(len(x), dtype=bool)
+
+    ok = np.repeat((nodes >= 0) & (nodes < N), W)
+    kw = _walk_keys_vec(nodes, W, seed, step).reshape(-1)
+    out = np.full((n * W, L + 1), -1, dtype=np.int64)
+    cur = np.where(ok, np.repeat(nodes, W), 0)
+    out[ok, 0] = cur[ok]
+    prev = np.full(n * W, -1, dtype=np.int64)
+    alive = ok.copy()
+    with np.errstate(over="ignore"):
+        for h in range(L):
+            idx = np.flatnonzero(alive)
+            start = indptr[cur[idx]]
+            deg = indptr[cur[idx] + 1] - start
+            alive[idx[deg <= 0]] = False
+            idx, start, deg = idx[deg > 0], start[deg > 0], deg[deg > 0]
+            x = np.full(len(idx), -1, dtype=np.int64)
+            und = np.arange(len(idx))                      # the walks of idx that have taken no candidate yet
+            for a in range(ATTEMPTS):
+                if len(und) == 0:
+                    break
+                c = np.uint64(2 * (ATTEMPTS * h + a))
+                k = kw[idx[und]]
+                cand = indices[start[und] + mulhi64(splitmix64(k + c), deg[und].astype(np.uint64)).astype(np.int64)]
+                x[und] = cand                              # attempt 255's candidate stays when every attempt fails
+                if h == 0:
+                    break
+                p = prev[idx[und]]
+                t = np.where(cand == p, t_ret, np.where(in_row(p, cand), t_near, t_far))
+                und = und[~((splitmix64(k + c + np.uint64(1)) >> np.uint64(32)) < t)]
+            good = (x >= 0) & (x < N)
+            alive[idx[~good]] = False
+            g = idx[good]
+            prev[g], cur[g] = cur[g], x[good]
+            out[g, h + 1] = x[good]
+    return out.reshape(n, W, L + 1)
+
+
+def negatives_vec(nodes, N, L, W, K, seed, step):
+    """negatives() (keep_start=True) for every row at once."""
+    from _labor_ref import mulhi64, splitmix64
+    nodes = np.asarray(nodes, dtype=np.int64)
+    n = len(nodes)
+    ok = (nodes >= 0) & (nodes < N)
+    nk = _walk_keys_vec(nodes, W, seed, step) ^ np.uint64(NEG_STREAM)
+    out = np.empty((n, W, K, L + 1), dtype=np.int64)
+    with np.errstate(over="ignore"):
+        c = (np.uint64(128) * np.arange(K, dtype=np.uint64))[:, None] + np.arange(L + 1, dtype=np.uint64)[None, :]
+        out[...] = mulhi64(splitmix64(nk[:, :, None, None] + c[None, None]), np.uint64(N)).astype(np.int64)
+    out[..., 0] = nodes[:, None, None]
+    out[~ok] = -1
+    return out.reshape(n * W * K, L + 1)
+
+
+def walk_batch_vec(indptr, indices, nodes, L, W, K, thr, seed, step):
+    """walk_batch() from traces_vec, negatives_vec and _edge_batch_ref.compact."""
+    from _edge_batch_ref import compact
+    nodes = np.asarray(nodes, dtype=np.int64)
+    n, N = len(nodes), len(indptr) - 1
+    tr = traces_vec(indptr, indices, nodes, L, W, thr, seed, step)
+    ng = negatives_vec(nodes, N, L, W, K, seed, step)
+    ok = (nodes >= 0) & (nodes < N)
+    input_nodes, local = compact(np.concatenate([np.where(ok, nodes, -1), tr.reshape(-1), ng[:, 1:].reshape(-1)]))
+    local = local.astype(np.int32)
+    n_pos = n * W * (L + 1)
+    neg = np.empty((n * W * K, L + 1), dtype=np.int32)
+    neg[:, 0] = np.repeat(local[:n], W * K)               # column 0: the item of the walk's start node
+    neg[:, 1:] = local[n + n_pos:].reshape(n * W * K, L)
+    return dict(input_nodes=input_nodes, pos=local[n: n + n_pos].reshape(n * W, L + 1), neg=neg, traces=tr, n_bad=int((~ok).sum()))
+
+
 # ----------------------------------------------------------------------------------------------------- exact transition probabilities
 def transition_probs(G, prev, cur, p, q):
     """node2vec's second-order transition distribution at `cur` having come from `prev`, over the entries of row cur: {next: prob}."""

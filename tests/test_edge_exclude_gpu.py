@@ -173,3 +173,120 @@ def test_blocks_without_edge_ids_are_refused(setup):
     for s in (NeighborSampler([3]), RandomWalkNeighborSampler(3, 2, 0.5, 4)):
         with pytest.raises(ValueError, match="edge ids"):
             s.sample(g, seeds)[2][0].exclude_edges(torch.zeros(1, dtype=torch.int64, device="cuda"))
+
+
+# ------------------------------------------------------------------------------------------- the kernels past one pass of their grid
+# Hand-made blocks at the C ABI, with more rows than the largest grid has lane groups (exclude_edges_kernel: 32 lanes per row, 65,536
+# rows a pass; exclude_edges_csr_kernel: a wave per row, 32,768 rows a pass), sentinel guards around every output.
+PAD = 37
+S64, S32 = -0x0123456789ABCDEF, -0x01234567
+
+
+def _padded(torch, m, dtype, fill):
+    buf = torch.full((m + 2 * PAD,), fill, dtype=dtype, device="cuda")
+    return buf, buf.data_ptr() + PAD * buf.element_size()
+
+
+def _inside(buf, m, fill):
+    """The output's m entries, after checking the guards around them."""
+    assert bool((buf[:PAD] == fill).all()) and bool((buf[PAD + m:] == fill).all()), "a write outside an output's capacity"
+    return buf[PAD: PAD + m].cpu().numpy()
+
+
+def _exclusion_lists(rng, eid_rows, all_ids, one):
+    """Sorted lists of 0, 1 (the id `one`) and 2,048 ids; the long one holds every id of the given rows (they lose every slot)."""
+    rows = np.unique(np.concatenate([e[e >= 0] for e in eid_rows]))
+    assert 0 < len(rows) < 1500
+    rest = np.setdiff1d(all_ids, rows)
+    long = np.unique(np.concatenate([rows, rng.choice(rest, 2048 - len(rows), replace=False)]))
+    assert len(long) == 2048
+    return {"empty": np.zeros(0, np.int64), "one": np.array([one], dtype=np.int64), "2048": long}
+
+
+@pytest.mark.parametrize("fanout", [5, 32])
+def test_fixed_kernel_past_one_grid_pass(hiplib, fanout):
+    import torch
+    from COALA_GNN_Pybind import _capi, current_stream
+    L = _capi.load()
+    n_dst = 70_001
+    assert n_dst * 32 > 8192 * 256
+    rng = np.random.default_rng(fanout)
+    nbr = rng.integers(0, 1 << 20, size=(n_dst, fanout)).astype(np.int32)
+    nbr[rng.random((n_dst, fanout)) < 0.2] = -1                      # -1 anywhere in a row
+    nbr[[5, 65_540]] = -1                                            # rows without a slot
+    nbr[[0, 65_535, 65_536, 65_537, n_dst - 1], 0] = 7               # ... and the rows the long list empties have one for sure
+    eid = rng.permutation(2 * n_dst * fanout)[: n_dst * fanout].reshape(n_dst, fanout).astype(np.int64)
+    eid[nbr < 0] = -1
+    emptied = [0, 65_535, 65_536, 65_537, n_dst - 1]                 # around the first row of the second pass, and the last row
+    lists = _exclusion_lists(rng, [eid[r] for r in emptied], eid[eid >= 0], one=eid[-1][nbr[-1] >= 0][0])
+    d_nbr, d_eid = torch.from_numpy(nbr).cuda(), torch.from_numpy(eid).cuda()
+    for name, ex in lists.items():
+        d_ex = torch.from_numpy(ex).cuda()
+        out_n, p_n = _padded(torch, n_dst * fanout, torch.int32, S32)
+        out_e, p_e = _padded(torch, n_dst * fanout, torch.int64, S64)
+        _capi.check(L.coala_block_exclude_edges(0, d_nbr.data_ptr(), d_eid.data_ptr(), d_ex.data_ptr() if len(ex) else None, len(ex), p_n, p_e,
+                                                n_dst, fanout, current_stream()))
+        got_n = _inside(out_n, n_dst * fanout, S32).reshape(n_dst, fanout)
+        got_e = _inside(out_e, n_dst * fanout, S64).reshape(n_dst, fanout)
+        keep = (nbr >= 0) & ~np.isin(eid, ex)
+        order = np.argsort(~keep, axis=1, kind="stable")            # survivors first, in their old order
+        want_n = np.take_along_axis(np.where(keep, nbr, -1), order, axis=1)
+        want_e = np.take_along_axis(np.where(keep, eid, -1), order, axis=1)
+        ends = np.r_[0:1500, n_dst - 1500: n_dst]                    # ... which is exclude_fixed, row by row
+        ref_n, ref_e = R.exclude_fixed(nbr[ends], eid[ends], ex)
+        assert np.array_equal(want_n[ends], ref_n) and np.array_equal(want_e[ends], ref_e)
+        assert got_n.dtype == want_n.dtype and np.array_equal(got_n, want_n), name
+        assert np.array_equal(got_e, want_e), name
+        if name == "2048":
+            assert np.all(got_n[emptied] == -1) and np.all(got_e[emptied] == -1) and (nbr[emptied] >= 0).any(axis=1).all()
+        if name == "one":
+            assert (got_n[-1] >= 0).sum() == (nbr[-1] >= 0).sum() - 1
+        if name == "empty":
+            assert (got_n >= 0).sum() == (nbr >= 0).sum()
+
+
+def test_csr_kernel_past_one_grid_pass(hiplib):
+    import torch
+    from COALA_GNN_Pybind import _capi, current_stream
+    L = _capi.load()
+    n_dst, wide = 40_003, 33_000
+    assert n_dst * 64 > 8192 * 256 and wide > 32_768
+    rng = np.random.default_rng(40)
+    deg = rng.integers(0, 131, size=n_dst)
+    deg[[0, 1, 2]], deg[wide], deg[-1] = [0, 130, 64], 3000, 65       # the degrees 0 .. 130 and one row of a few thousand, in the second pass
+    indptr = np.zeros(n_dst + 1, dtype=np.int64)
+    np.cumsum(deg, out=indptr[1:])
+    E = int(indptr[-1])
+    indices = rng.integers(0, 1 << 20, size=E).astype(np.int32)
+    eid = rng.permutation(2 * E)[:E].astype(np.int64)
+    rows = np.repeat(np.arange(n_dst), deg)
+    emptied = [1, 32_768, n_dst - 1]
+    lists = _exclusion_lists(rng, [eid[indptr[r]: indptr[r + 1]] for r in emptied] + [eid[indptr[wide]: indptr[wide] + 700]], eid, one=eid[-1])
+    d_ip, d_ix, d_eid = torch.from_numpy(indptr).cuda(), torch.from_numpy(indices).cuda(), torch.from_numpy(eid).cuda()
+    for name, ex in lists.items():
+        d_ex = torch.from_numpy(ex).cuda()
+        ex_ptr = d_ex.data_ptr() if len(ex) else None
+        counts, p_c = _padded(torch, n_dst, torch.int64, S64)
+        _capi.check(L.coala_block_exclude_edges_csr(0, d_ip.data_ptr(), d_ix.data_ptr(), d_eid.data_ptr(), ex_ptr, len(ex), p_c, None, None, None,
+                                                    n_dst, current_stream()))
+        got_c = _inside(counts, n_dst, S64)
+        keep = ~np.isin(eid, ex)
+        assert np.array_equal(got_c, np.bincount(rows[keep], minlength=n_dst)), name
+        new_ip = np.zeros(n_dst + 1, dtype=np.int64)                  # the host scan between the two passes
+        np.cumsum(got_c, out=new_ip[1:])
+        left = int(new_ip[-1])
+        d_new = torch.from_numpy(new_ip).cuda()
+        out_x, p_x = _padded(torch, left, torch.int32, S32)
+        out_e, p_e = _padded(torch, left, torch.int64, S64)
+        _capi.check(L.coala_block_exclude_edges_csr(0, d_ip.data_ptr(), d_ix.data_ptr(), d_eid.data_ptr(), ex_ptr, len(ex), None, d_new.data_ptr(),
+                                                    p_x, p_e, n_dst, current_stream()))
+        want_ip, want_x, want_e = R.exclude_csr(indptr, indices, eid, ex)
+        assert np.array_equal(new_ip, want_ip) and left == int(keep.sum())
+        got_x, got_e = _inside(out_x, left, S32), _inside(out_e, left, S64)
+        assert got_x.dtype == want_x.dtype and np.array_equal(got_x, want_x) and np.array_equal(got_e, want_e), name
+        if name == "2048":
+            assert np.all(got_c[emptied] == 0) and got_c[wide] == 2300
+        if name == "one":
+            assert left == E - 1 and got_c[-1] == 64
+        if name == "empty":
+            assert left == E

@@ -44,48 +44,92 @@ def _reference(h, src, dst, g):
     return prod.sum(-1), np.abs(prod).sum(-1), grad, mag, m
 
 
-@pytest.mark.parametrize("H", [None, 1, 4])
-@pytest.mark.parametrize("D", [1, 3, 64, 100, 128, 257])
-def test_pair_dot_abi(hiplib, D, H):
-    import torch
+def _check_case(torch, L, rng, d_h, h, src, dst, D, H):
+    """One forward and one backward call at the C ABI over the given pairs, held to the bounds of the module docstring; -> endpoints per
+    row of h."""
     from COALA_GNN_Pybind import _capi, current_stream
-    L = _capi.load()
-    heads = H or 1
-    rng = np.random.default_rng(1000 * D + heads)
+    heads, P = H or 1, len(src)
+    g = rng.standard_normal((P, heads)).astype(np.float32)
+    d_s, d_d = torch.from_numpy(src).cuda(), torch.from_numpy(dst).cuda()
+    d_out = Guarded(torch, P, heads, off=3)
+    d_g = Guarded(torch, P, heads, off=1, fill=g) if P else Guarded(torch, 0, heads)
+    d_gh = Guarded(torch, N, heads * D, off=1, fill=0.0)
+    _capi.check(L.coala_block_pair_dot(0, d_h.ptr, d_s.data_ptr(), d_d.data_ptr(), d_out.ptr, P, heads, D, current_stream()))
+    _capi.check(L.coala_block_pair_dot_backward(0, d_h.ptr, d_s.data_ptr(), d_d.data_ptr(), d_g.ptr, d_gh.ptr, P, heads, D, current_stream()))
+    torch.cuda.synchronize()
+    out, gh = d_out.region().astype(np.float64), d_gh.region().reshape(N, heads, D)
+    d_h.region()                                            # the input's padding too
+    ref, mag, gref, gmag, m = _reference(h, src, dst, g.astype(np.float64))
+    err = np.abs(out - ref)
+    bound = _gamma(D + 1) * mag
+    print(f"D={D} H={H} P={P}: forward worst err/bound {float((err / np.maximum(bound, 1e-300)).max()) if P else 0:.3f}")
+    assert np.all(err <= bound)
+    none = (src < 0) | (dst < 0)
+    assert np.all(out[none] == 0)
+    gerr = np.abs(gh.astype(np.float64) - gref)
+    gbound = _gamma(m + 1)[:, None, None] * gmag
+    print(f"D={D} H={H} P={P}: grad_h worst err/bound {float((gerr / np.maximum(gbound, 1e-300)).max()):.3f}")
+    assert np.all(gerr <= gbound)
+    assert np.all(gh[m == 0] == 0) and np.all(m[N - UNREFERENCED:] == 0)
+    if P:                                                   # bitwise reproducible forward
+        d_out2 = Guarded(torch, P, heads, off=0)
+        _capi.check(L.coala_block_pair_dot(0, d_h.ptr, d_s.data_ptr(), d_d.data_ptr(), d_out2.ptr, P, heads, D, current_stream()))
+        assert d_out2.region().tobytes() == d_out.region().tobytes()
+    return m
+
+
+def _table(torch, rng, D, heads):
     h = rng.standard_normal((N, heads, D)).astype(np.float32)
     h[[3, 50, 51]] *= np.float32(1e6)
     d_h = Guarded(torch, N, heads * D, off=1, fill=h.reshape(N, -1))
     assert d_h.ptr % 16 == 4
+    return h, d_h
+
+
+@pytest.mark.parametrize("H", [None, 1, 4])
+@pytest.mark.parametrize("D", [1, 3, 64, 100, 128, 257])
+def test_pair_dot_abi(hiplib, D, H):
+    import torch
+    from COALA_GNN_Pybind import _capi
+    L = _capi.load()
+    heads = H or 1
+    rng = np.random.default_rng(1000 * D + heads)
+    h, d_h = _table(torch, rng, D, heads)
     for P in (0, 1, 65, 6144):
         src, dst = _pairs(rng, P)
-        g = rng.standard_normal((P, heads)).astype(np.float32)
-        d_s, d_d = torch.from_numpy(src).cuda(), torch.from_numpy(dst).cuda()
-        d_out = Guarded(torch, P, heads, off=3)
-        d_g = Guarded(torch, P, heads, off=1, fill=g) if P else Guarded(torch, 0, heads)
-        d_gh = Guarded(torch, N, heads * D, off=1, fill=0.0)
-        _capi.check(L.coala_block_pair_dot(0, d_h.ptr, d_s.data_ptr(), d_d.data_ptr(), d_out.ptr, P, heads, D, current_stream()))
-        _capi.check(L.coala_block_pair_dot_backward(0, d_h.ptr, d_s.data_ptr(), d_d.data_ptr(), d_g.ptr, d_gh.ptr, P, heads, D, current_stream()))
-        torch.cuda.synchronize()
-        out, gh = d_out.region().astype(np.float64), d_gh.region().reshape(N, heads, D)
-        d_h.region()                                            # the input's padding too
-        ref, mag, gref, gmag, m = _reference(h, src, dst, g.astype(np.float64))
-        err = np.abs(out - ref)
-        bound = _gamma(D + 1) * mag
-        print(f"D={D} H={H} P={P}: forward worst err/bound {float((err / np.maximum(bound, 1e-300)).max()) if P else 0:.3f}")
-        assert np.all(err <= bound)
-        none = (src < 0) | (dst < 0)
-        assert np.all(out[none] == 0)
-        gerr = np.abs(gh.astype(np.float64) - gref)
-        gbound = _gamma(m + 1)[:, None, None] * gmag
-        print(f"D={D} H={H} P={P}: grad_h worst err/bound {float((gerr / np.maximum(gbound, 1e-300)).max()):.3f}")
-        assert np.all(gerr <= gbound)
-        assert np.all(gh[m == 0] == 0) and np.all(m[N - UNREFERENCED:] == 0)
+        m = _check_case(torch, L, rng, d_h, h, src, dst, D, H)
         if P >= 6144:
             assert m[17] >= 300 and m[3] >= 100
-        if P:                                                   # bitwise reproducible forward
-            d_out2 = Guarded(torch, P, heads, off=0)
-            _capi.check(L.coala_block_pair_dot(0, d_h.ptr, d_s.data_ptr(), d_d.data_ptr(), d_out2.ptr, P, heads, D, current_stream()))
-            assert d_out2.region().tobytes() == d_out.region().tobytes()
+
+
+GRID_THREADS = 8192 * 256      # the largest grid of the pair kernels (coala_block_ops.hip: pair_dot_launch)
+
+
+def _pairs_past_the_grid(rng, P, heads, GS):
+    """_pairs' specials scaled to P pairs: one row named 3,000 times, and the pairs without a score placed behind unit GRID_THREADS / GS,
+    where only the second pass of the grid-stride loop meets them."""
+    src, dst = _pairs(rng, P)
+    first_pass = GRID_THREADS // GS // heads                # pairs the first pass covers
+    assert P > first_pass + 8
+    dst[P - 3100: P - 100] = 17                             # one row 3,000 times, most of it in the second pass
+    src[P - 100: P - 40] = 3                                # ... and a scaled row
+    src[first_pass + 1], dst[first_pass + 2] = -1, -1
+    src[P - 5], dst[P - 3], src[P - 1], dst[P - 1] = -1, -1, -1, -1
+    return src, dst
+
+
+@pytest.mark.parametrize("D,H,P,GS", [(64, 1, 40_000, 64), (24, 1, 70_001, 32), (3, 4, 35_003, 16)])
+def test_pair_dot_past_one_grid_pass(hiplib, D, H, P, GS):
+    """More (pair, head) units than lane groups in the largest grid, for each group size: the units of the second pass of the
+    grid-stride loop, forward and backward, on the same reference and bounds."""
+    import torch
+    from COALA_GNN_Pybind import _capi
+    assert P * H * GS > GRID_THREADS and GS == (16 if D <= 16 else 32 if D <= 32 else 64)
+    rng = np.random.default_rng(P)
+    h, d_h = _table(torch, rng, D, H)
+    src, dst = _pairs_past_the_grid(rng, P, H, GS)
+    m = _check_case(torch, _capi.load(), rng, d_h, h, src, dst, D, H)
+    assert m[17] >= 2990 and m[3] >= 60 and ((src < 0) | (dst < 0))[GRID_THREADS // GS // H:].sum() >= 5
 
 
 INPUTS = ("native", "colslice", "int64", "fp64", "fp16", "cpu_index")
