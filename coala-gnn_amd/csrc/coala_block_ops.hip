@@ -145,8 +145,9 @@ __global__ __launch_bounds__(kBlock) void mean_aggregate_backward_kernel(const i
 // One wave per destination row, in both block forms.  Per chunk a lane per edge computes its edge's score for every head once, into
 // LDS; the feature lanes then sum the rows with those weights, never writing a [n_dst, fanout, H, D] intermediate.  The softmax runs
 // online over the chunks: running max m and sum l per head; the partial sum is rescaled by exp(m_old - m_new) when the max grows, and
-// it waits in `out`, unnormalised, between the chunks of a row of more than 64 edges.  GATv2 below differs only in how a chunk's
-// scores come about, so the softmax step, the weighted sum and the two ends of a row are the functions that follow, for both.
+// it waits in `out`, unnormalised, between the chunks of a row of more than 64 edges.  GATv2 and dot-product attention below differ
+// only in how a chunk's scores come about and in which table is summed: the three are one kernel, attention_aggregate_kernel, over a
+// score policy, and the softmax step, the weighted sum and the two ends of a row are the functions that follow.
 constexpr int kGatMaxHeads = 16;
 constexpr float kNegInf = -__builtin_inff();
 
@@ -207,8 +208,9 @@ __device__ __forceinline__ void softmax_chunk_step(const SoftmaxLds& s, int h, f
 }
 
 // out_row[h, :] = (first chunk ? 0 : out_row[h, :] * scl[h]) + sum over the chunk's valid edges j of w[j][h] * feat[s_j, h, :], divided
-// by the row's sum on the last chunk.  A lane per VEC floats of the [H * dim] row.
-template <int VEC>
+// by the row's sum on the last chunk.  A lane per VEC floats of the [H * dim] row.  FINAL: w holds finished weights a_j (RelGAT's second
+// pass): nothing to rescale and nothing to divide, and of s only w is read.
+template <int VEC, bool FINAL>
 __device__ __forceinline__ void softmax_accumulate(const SoftmaxLds& s, float* out_row, const float* __restrict__ feat, int32_t mine, int n,
                                                    bool first, bool last, int lane, int hd, int units, int upl) {
     typedef float vf __attribute__((ext_vector_type(VEC)));
@@ -217,13 +219,13 @@ __device__ __forceinline__ void softmax_accumulate(const SoftmaxLds& s, float* o
         const int hu = u < units ? u / upl : 0;
         float* o = out_row + (int64_t)u * VEC;
         vf acc = vf(0.0f);
-        if (!first && u < units) acc = *reinterpret_cast<const vf*>(o) * s.scl[hu];
+        if (!first && u < units) acc = FINAL ? *reinterpret_cast<const vf*>(o) : *reinterpret_cast<const vf*>(o) * s.scl[hu];
         for (int j = 0; j < n; ++j) {
             const int32_t src = __shfl(mine, j);
             if (src >= 0 && u < units) acc += s.w[j * kGatMaxHeads + hu] * *reinterpret_cast<const vf*>(feat + (int64_t)src * hd + (int64_t)u * VEC);
         }
         if (u < units) {
-            if (last) acc *= s.l_run[hu] > 0.0f ? 1.0f / s.l_run[hu] : 0.0f;
+            if (!FINAL && last) acc *= s.l_run[hu] > 0.0f ? 1.0f / s.l_run[hu] : 0.0f;
             *reinterpret_cast<vf*>(o) = acc;
         }
     }
@@ -248,140 +250,12 @@ __device__ __forceinline__ void head_dots(float* gout, const float* __restrict__
     }
 }
 
-template <int VEC, bool CSR>
-__global__ __launch_bounds__(kBlock) void gat_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
-                                                               const float* __restrict__ el, const float* __restrict__ er,
-                                                               const float* __restrict__ feat, float* __restrict__ out, float* __restrict__ lse,
-                                                               int64_t n_dst, int heads, int dim, float slope) {
-    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];
-    __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];
-    const auto [lane, wave, n_waves] = wave_rows();
-    const SoftmaxLds s = softmax_lds(w_lds[threadIdx.x >> 6], st_lds[threadIdx.x >> 6]);
-    const int hd = heads * dim, units = hd / VEC, upl = dim / VEC;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        int64_t beg, end;
-        row_range<CSR>(indptr, fanout, d, &beg, &end);
-        softmax_row_begin(s, lane, heads);
-        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
-            int32_t mine;
-            const int n = load_chunk(idx, e0, end, lane, &mine);
-            wave_lds_sync(); // the previous chunk has read w and scl; m_run / l_run are set
-            for (int h = 0; h < heads; ++h) { // the score is a scalar per edge and head: straight into the softmax step
-                float e = kNegInf;
-                if (mine >= 0) e = leaky_score(el[(int64_t)mine * heads + h] + er[d * heads + h], slope);
-                softmax_chunk_step(s, h, e, mine >= 0, lane);
-            }
-            wave_lds_sync();
-            softmax_accumulate<VEC>(s, out + d * hd, feat, mine, n, e0 == beg, e0 + 64 >= end, lane, hd, units, upl);
-        }
-        softmax_row_end<VEC>(s, out + d * hd, lse + d * heads, beg == end, lane, heads, units);
-    }
-}
-
-// The backward kernels of the four attention ops recompute a weight as exp(e_j - lse) from the saved fp32 log-sum-exp.  Those sum over a
-// softmax group to S = 1 + O(u |lse|), not to 1: lse is rounded at the scores' common offset.  Every backward therefore divides by the
-// group's own S, summed in a fixed order (a wave_sum per 64-slot chunk, chunk after chunk), so that the weights sum to 1 within a few u
-// whatever the offset, grad_feat / grad_v / grad_src add up over the table to grad_out, and an error of lse itself cancels.  A row of
-// one chunk -- every fixed row -- takes S from the chunk already in registers; a longer row walks its scores once more in front.
-__device__ __forceinline__ float normalised(float a, float sum) { return sum > 0.0f ? a / sum : 0.0f; }
-
-// Backward, a_j = exp(e_j - lse[d, h]) / S recomputed from the saved log-sum-exp, S the row's sum of exp(e_j - lse[d, h]):
-//   grad_feat[s_j, h, :] += a_j g[d, h, :],  t_j = a_j (<g[d, h, :], feat[s_j, h, :]> - <g[d, h, :], out[d, h, :]>) (z_j > 0 ? 1 : slope),
-//   grad_el[s_j, h] += t_j,  grad_er[d, h] = sum_j t_j.
-// A lane per float of the [H * dim] row, 64 at a time; the per-head dot products are summed by head_segment_add into LDS in a fixed
-// order.  grad_feat and grad_el take hardware float atomics (zeroed by the caller); grad_er is written whole, one tree per chunk.
-template <bool CSR>
-__global__ __launch_bounds__(kBlock) void gat_aggregate_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
-                                                                        int fanout, const float* __restrict__ el, const float* __restrict__ er,
-                                                                        const float* __restrict__ feat, const float* __restrict__ out,
-                                                                        const float* __restrict__ lse, const float* __restrict__ grad_out,
-                                                                        float* __restrict__ grad_feat, float* __restrict__ grad_el,
-                                                                        float* __restrict__ grad_er, int64_t n_dst, int heads, int dim, float slope) {
-    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // a_j of the chunk, [edge][head]
-    __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g, feat_j>, [edge][head]
-    __shared__ float hs_lds[kWavesPerBlock][3 * kGatMaxHeads];   // per head: <g, out>, the sum of t_j so far, S of a row of several chunks
-    const auto [lane, wave, n_waves] = wave_rows();
-    float* w = w_lds[threadIdx.x >> 6];
-    float* dot = dot_lds[threadIdx.x >> 6];
-    float* gout = hs_lds[threadIdx.x >> 6];
-    float* ter = gout + kGatMaxHeads;
-    float* ssum = ter + kGatMaxHeads;
-    const int hd = heads * dim;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        int64_t beg, end;
-        row_range<CSR>(indptr, fanout, d, &beg, &end);
-        const float* g = grad_out + d * hd;
-        wave_lds_sync(); // the previous row has read gout / ter
-        if (lane < heads) {
-            gout[lane] = 0.0f;
-            ter[lane] = 0.0f;
-            ssum[lane] = 0.0f;
-        }
-        wave_lds_sync();
-        head_dots(gout, g, out + d * hd, lane, dim, hd);
-        const bool one = end - beg <= 64; // wave-uniform: the row is one chunk
-        if (!one) {                       // S per head, chunk after chunk (lane 0 alone touches ssum)
-            for (int64_t e0 = beg; e0 < end; e0 += 64) {
-                int32_t mine;
-                load_chunk(idx, e0, end, lane, &mine);
-                for (int h = 0; h < heads; ++h) {
-                    float a = 0.0f;
-                    if (mine >= 0) a = expf(leaky_score(el[(int64_t)mine * heads + h] + er[d * heads + h], slope) - lse[d * heads + h]);
-                    const float sum = wave_sum(a);
-                    if (lane == 0) ssum[h] += sum;
-                }
-            }
-            wave_lds_sync();
-        }
-        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
-            int32_t mine;
-            const int n = load_chunk(idx, e0, end, lane, &mine);
-            wave_lds_sync(); // the previous chunk has read w and dot
-            for (int h = 0; h < heads; ++h) {
-                float a = 0.0f;
-                if (mine >= 0) a = expf(leaky_score(el[(int64_t)mine * heads + h] + er[d * heads + h], slope) - lse[d * heads + h]);
-                w[lane * kGatMaxHeads + h] = normalised(a, one ? wave_sum(a) : ssum[h]);
-                dot[lane * kGatMaxHeads + h] = 0.0f;
-            }
-            wave_lds_sync();
-            for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: head_segment_add shuffles across every lane
-                const int c = c0 + lane;
-                const int hc = c < hd ? c / dim : 0;
-                const float gc = c < hd ? g[c] : 0.0f;
-                for (int j = 0; j < n; ++j) {
-                    const int32_t s = __shfl(mine, j);
-                    if (s < 0) continue; // wave-uniform
-                    float x = 0.0f;
-                    if (c < hd) {
-                        x = gc * feat[(int64_t)s * hd + c];
-                        unsafeAtomicAdd(grad_feat + (int64_t)s * hd + c, w[j * kGatMaxHeads + hc] * gc);
-                    }
-                    head_segment_add(dot + j * kGatMaxHeads, x, lane, c0, dim, hd);
-                }
-            }
-            wave_lds_sync();
-            for (int h = 0; h < heads; ++h) {
-                float t = 0.0f;
-                if (mine >= 0) {
-                    const float z = el[(int64_t)mine * heads + h] + er[d * heads + h];
-                    t = w[lane * kGatMaxHeads + h] * (dot[lane * kGatMaxHeads + h] - gout[h]) * (z > 0.0f ? 1.0f : slope);
-                    unsafeAtomicAdd(grad_el + (int64_t)mine * heads + h, t);
-                }
-                const float ts = wave_sum(t);
-                if (lane == 0) ter[h] += ts;
-            }
-        }
-        wave_lds_sync();
-        if (lane < heads) grad_er[d * heads + lane] = ter[lane];
-    }
-}
-
 // GATv2 attention on a block (DGL GATv2Conv's message step; the projections fc_src / fc_dst stay in torch).  For dst d, head h and the
 // valid in-edges j of d (source s_j):
 //   z_jc = feat_src[s_j, h, c] + feat_dst[d, h, c],  e_j = sum_c attn[h, c] leaky_relu(z_jc, slope),  a_j = softmax of e over the row,
 //   out[d, h, :] = sum_j a_j feat_src[s_j, h, :]
 // The score does not split into a per-source and a per-destination scalar as GAT's does: it is a dot product over the [H * D] row per
-// edge.  gat_aggregate_kernel's mapping and its online softmax, with one step in front of every chunk, the score pass: a lane per
+// edge.  GAT's mapping and its online softmax, with one step in front of every chunk, the score pass: a lane per
 // float of the row, 64 floats at a time, attn and feat_dst[d] of the pass in registers, the chunk's edges in the inner loop, and the
 // per-head sums added into the LDS [edge][head] array by head_segment_add in a fixed order.  The weighted sum then reads the chunk's
 // source rows a second time (at most 64 rows: from the cache), so the HBM bytes are GAT's plus feat_dst, and nothing of size E is
@@ -408,12 +282,109 @@ __device__ __forceinline__ void gatv2_score_pass(float* e, float* dot, int32_t m
     }
 }
 
-template <int VEC, bool CSR>
-__global__ __launch_bounds__(kBlock) void gatv2_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
-                                                                 const float* __restrict__ feat_src, const float* __restrict__ feat_dst,
-                                                                 const float* __restrict__ attn, float* __restrict__ out,
-                                                                 float* __restrict__ lse, int64_t n_dst, int heads, int dim, float slope) {
-    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads]; // the chunk's scores e_j first, [edge][head]
+// Scaled dot-product attention on a block (the message step of DGL's DotGatConv and HGTConv, PyG's TransformerConv without edge
+// features; the projections stay in torch).  Every slot carries the row of k / v its edge reads (row, -1 = no edge; the block's own
+// index array in the dense form).  For dst d, head h and the slots j of d with row_j >= 0:
+//   e_j = scale <q[d, h, :], k[row_j, h, :]>,  a_j = softmax of e over the row,  out[d, h, :] = sum_j a_j v[row_j, h, :]
+// GATv2's layout with another score pass: a lane per float of the [H * D] row, 64 floats at a time, q[d] of the pass in
+// registers, the chunk's edges in the inner loop, the per-head sums added into the LDS [edge][head] array by head_segment_add in a
+// fixed order; the scale is applied to the finished sum by dot_score, in both directions.  The weighted sum then reads the chunk's v rows.
+// Nothing of size E is written.
+//
+// A slot's score from its finished dot product: one rounded product, never contracted into the subtraction that follows it (e - m in
+// the forward, e - lse in the backward).  Fused, the backward's fma(scale, qk, -lse) would take the product unrounded while the
+// forward's maximum and lse are made of rounded scores: a_j = exp(e_j - lse) is then off by u |e_j|, edge by edge, the a_j of a row no
+// longer sum to what lse says, and sum_j t_j, zero in exact arithmetic, grows with the scores' common offset.
+__device__ __forceinline__ float dot_score(float scale, float qk) {
+#pragma clang fp contract(off)
+    return scale * qk;
+}
+
+// e[j * kGatMaxHeads + h] += <q[d, h, :], k[row_j, h, :]> for the n slots of a chunk; with DOT also dot[..] += <g[h, :], v[row_j, h, :]>.
+template <bool DOT>
+__device__ __forceinline__ void dot_score_pass(float* e, float* dot, int32_t mine, int n, const float* __restrict__ k,
+                                               const float* __restrict__ qd, const float* __restrict__ v, const float* __restrict__ g, int lane,
+                                               int hd, int dim) {
+    for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: head_segment_add shuffles across every lane
+        const int c = c0 + lane;
+        const bool in = c < hd;
+        const float qc = in ? qd[c] : 0.0f;
+        const float gc = DOT && in ? g[c] : 0.0f;
+        for (int j = 0; j < n; ++j) {
+            const int32_t s = __shfl(mine, j);
+            if (s < 0) continue; // wave-uniform
+            head_segment_add(e + j * kGatMaxHeads, in ? qc * k[(int64_t)s * hd + c] : 0.0f, lane, c0, dim, hd);
+            if (DOT) head_segment_add(dot + j * kGatMaxHeads, in ? gc * v[(int64_t)s * hd + c] : 0.0f, lane, c0, dim, hd);
+        }
+    }
+}
+
+// What tells GAT, GATv2 and dot-product attention apart, in the forward kernel and in the row front of their backward kernels: how a
+// slot's score comes about, and which table holds the rows that are summed.  The kernels take an op's three tables as (a, b, c) and
+// its one float as `param`.  A policy with kRowPass makes a chunk's scores by a pass over the [H * dim] rows into the LDS [edge][head]
+// array (row_pass; with DOT also the dots <g, value row>), and score(e, lane, h, param) finishes lane j's own word e[lane][h]; one without
+// makes the score from scalars, score(a, b, mine, d, heads, h, param).  Either way score() is where the rounding rule of leaky_score / dot_score is applied, forward and backward.
+struct GatScore { // a = el, b = er, c = feat, param = slope
+    static constexpr bool kRowPass = false;
+    static __host__ __device__ const float* values(const float*, const float*, const float* feat) { return feat; }
+    static __device__ __forceinline__ float score(const float* __restrict__ el, const float* __restrict__ er, int32_t mine, int64_t d, int heads, int h,
+                                                  float slope) {
+        return leaky_score(el[(int64_t)mine * heads + h] + er[d * heads + h], slope);
+    }
+};
+
+struct Gatv2Score { // a = feat_src, b = feat_dst, c = attn, param = slope
+    static constexpr bool kRowPass = true;
+    static __host__ __device__ const float* values(const float* feat_src, const float*, const float*) { return feat_src; }
+    template <bool DOT>
+    static __device__ __forceinline__ void row_pass(float* e, float* dot, int32_t mine, int n, const float* __restrict__ feat_src,
+                                                    const float* __restrict__ feat_dst, const float* __restrict__ attn, int64_t d,
+                                                    const float* __restrict__ g, int lane, int hd, int dim, float slope) {
+        gatv2_score_pass<DOT>(e, dot, mine, n, feat_src, feat_dst + d * hd, attn, g, lane, hd, dim, slope);
+    }
+    static __device__ __forceinline__ float score(const float* e, int lane, int h, float) {
+        return e[lane * kGatMaxHeads + h]; // the finished sum
+    }
+};
+
+struct DotScore { // a = q, b = k, c = v, param = scale
+    static constexpr bool kRowPass = true;
+    static __host__ __device__ const float* values(const float*, const float*, const float* v) { return v; }
+    template <bool DOT>
+    static __device__ __forceinline__ void row_pass(float* e, float* dot, int32_t mine, int n, const float* __restrict__ q,
+                                                    const float* __restrict__ k, const float* __restrict__ v, int64_t d,
+                                                    const float* __restrict__ g, int lane, int hd, int dim, float) {
+        dot_score_pass<DOT>(e, dot, mine, n, k, q + d * hd, v, g, lane, hd, dim);
+    }
+    static __device__ __forceinline__ float score(const float* e, int lane, int h, float scale) {
+        return dot_score(scale, e[lane * kGatMaxHeads + h]);
+    }
+};
+
+// A chunk's row pass: lane j zeroes edge j's words of w (with DOT of dot too), then Score's pass adds into them.  The caller has
+// synchronised: the previous chunk's readers of w / dot are done.
+template <typename Score, bool DOT>
+__device__ __forceinline__ void score_pass_chunk(float* w, float* dot, int32_t mine, int n, const float* __restrict__ a,
+                                                 const float* __restrict__ b, const float* __restrict__ c, int64_t d,
+                                                 const float* __restrict__ g, int lane, int heads, int hd, int dim, float param) {
+    for (int h = 0; h < heads; ++h) {
+        w[lane * kGatMaxHeads + h] = 0.0f;
+        if (DOT) dot[lane * kGatMaxHeads + h] = 0.0f;
+    }
+    wave_lds_sync();
+    Score::template row_pass<DOT>(w, dot, mine, n, a, b, c, d, g, lane, hd, dim, param);
+    wave_lds_sync();
+}
+
+// The forward kernel of the three ops: out[d, h, :] = sum_j a_j values[s_j, h, :], a_j the softmax over row d of Score's e_j, and
+// lse[d, h].  Without a row pass the score is a scalar per edge and head and goes straight into the softmax step; with one, w holds the
+// chunk's scores first, and lane j reads and rewrites only edge j's words.
+template <typename Score, int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void attention_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
+                                                                     const float* __restrict__ a, const float* __restrict__ b,
+                                                                     const float* __restrict__ c, float* __restrict__ out,
+                                                                     float* __restrict__ lse, int64_t n_dst, int heads, int dim, float param) {
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];
     __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];
     const auto [lane, wave, n_waves] = wave_rows();
     const SoftmaxLds s = softmax_lds(w_lds[threadIdx.x >> 6], st_lds[threadIdx.x >> 6]);
@@ -426,20 +397,148 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_kernel(const int64_t* 
             int32_t mine;
             const int n = load_chunk(idx, e0, end, lane, &mine);
             wave_lds_sync(); // the previous chunk has read w and scl; m_run / l_run are set
-            for (int h = 0; h < heads; ++h) s.w[lane * kGatMaxHeads + h] = 0.0f;
+            if constexpr (Score::kRowPass) score_pass_chunk<Score, false>(s.w, nullptr, mine, n, a, b, c, d, nullptr, lane, heads, hd, dim, param);
+            for (int h = 0; h < heads; ++h) {
+                float e = kNegInf;
+                if (mine >= 0) {
+                    if constexpr (Score::kRowPass) e = Score::score(s.w, lane, h, param);
+                    else e = Score::score(a, b, mine, d, heads, h, param);
+                }
+                softmax_chunk_step(s, h, e, mine >= 0, lane);
+            }
             wave_lds_sync();
-            gatv2_score_pass<false>(s.w, nullptr, mine, n, feat_src, feat_dst + d * hd, attn, nullptr, lane, hd, dim, slope);
-            wave_lds_sync();
-            for (int h = 0; h < heads; ++h) // lane j reads and rewrites only edge j's words
-                softmax_chunk_step(s, h, mine >= 0 ? s.w[lane * kGatMaxHeads + h] : kNegInf, mine >= 0, lane);
-            wave_lds_sync();
-            softmax_accumulate<VEC>(s, out + d * hd, feat_src, mine, n, e0 == beg, e0 + 64 >= end, lane, hd, units, upl);
+            softmax_accumulate<VEC, false>(s, out + d * hd, Score::values(a, b, c), mine, n, e0 == beg, e0 + 64 >= end, lane, hd, units, upl);
         }
         softmax_row_end<VEC>(s, out + d * hd, lse + d * heads, beg == end, lane, heads, units);
     }
 }
 
-// Backward, all three gradients in one launch, each of them optional (null).  a_j = exp(e_j - lse[d, h]) / S (`normalised` above) with e_j
+// The backward kernels of the four attention ops recompute a weight as exp(e_j - lse) from the saved fp32 log-sum-exp.  Those sum over a
+// softmax group to S = 1 + O(u |lse|), not to 1: lse is rounded at the scores' common offset.  Every backward therefore divides by the
+// group's own S, summed in a fixed order (a wave_sum per 64-slot chunk, chunk after chunk), so that the weights sum to 1 within a few u
+// whatever the offset, grad_feat / grad_v / grad_src add up over the table to grad_out, and an error of lse itself cancels.  A row of
+// one chunk -- every fixed row -- takes S from the chunk already in registers; a longer row walks its scores once more in front.
+__device__ __forceinline__ float normalised(float a, float sum) { return sum > 0.0f ? a / sum : 0.0f; }
+
+// A row's front in the backward kernels of GAT and dot-product attention: gout[h] = <g[h, :], out[d, h, :]> (head_dots), and for a
+// row of several chunks ssum[h] = S from a walk over its scores -- with a row pass of its own where Score has one, through w -- chunk
+// after chunk, lane 0 alone touching ssum.  -> whether the row is one chunk (wave-uniform); its S is then the wave_sum of the a_j.
+// The GATv2 backward has the same steps written out: moved in here, its RP = 8 CSR instantiation takes one VGPR more.
+template <typename Score>
+__device__ __forceinline__ bool backward_row_front(float* w, float* gout, float* ssum, const int32_t* __restrict__ idx, int64_t beg, int64_t end,
+                                                   const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c,
+                                                   const float* __restrict__ out_row, const float* __restrict__ lse_row,
+                                                   const float* __restrict__ g, int64_t d, int lane, int heads, int hd, int dim, float param) {
+    wave_lds_sync(); // the previous row has read gout
+    if (lane < heads) gout[lane] = ssum[lane] = 0.0f;
+    wave_lds_sync();
+    head_dots(gout, g, out_row, lane, dim, hd);
+    const bool one = end - beg <= 64;
+    if (!one) {
+        for (int64_t e0 = beg; e0 < end; e0 += 64) {
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
+            if constexpr (Score::kRowPass) {
+                wave_lds_sync(); // the previous chunk has read w
+                score_pass_chunk<Score, false>(w, nullptr, mine, n, a, b, c, d, nullptr, lane, heads, hd, dim, param);
+            }
+            for (int h = 0; h < heads; ++h) {
+                float p = 0.0f;
+                if (mine >= 0) {
+                    if constexpr (Score::kRowPass) p = expf(Score::score(w, lane, h, param) - lse_row[h]);
+                    else p = expf(Score::score(a, b, mine, d, heads, h, param) - lse_row[h]);
+                }
+                const float sum = wave_sum(p);
+                if (lane == 0) ssum[h] += sum;
+            }
+        }
+        wave_lds_sync();
+    }
+    return one;
+}
+
+// dot[j][h] += <g[h, :], feat[s_j, h, :]> for the n slots of a chunk whose weights a_j are in w: a lane per float of the [H * dim] row, 64
+// at a time, the per-head sums by head_segment_add in a fixed order; with ADD also grad_feat[s_j, h, :] += a_j g[h, :] from the same
+// lanes (GAT's and RelGAT's backward).
+template <bool ADD>
+__device__ __forceinline__ void dot_grad_feat_walk(const float* w, float* dot, int32_t mine, int n, const float* __restrict__ feat,
+                                                   const float* __restrict__ g, float* __restrict__ grad_feat, int lane, int dim, int hd) {
+    for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: head_segment_add shuffles across every lane
+        const int c = c0 + lane;
+        const int hc = c < hd ? c / dim : 0;
+        const float gc = c < hd ? g[c] : 0.0f;
+        for (int j = 0; j < n; ++j) {
+            const int32_t s = __shfl(mine, j);
+            if (s < 0) continue; // wave-uniform
+            float x = 0.0f;
+            if (c < hd) {
+                x = gc * feat[(int64_t)s * hd + c];
+                if (ADD) unsafeAtomicAdd(grad_feat + (int64_t)s * hd + c, w[j * kGatMaxHeads + hc] * gc);
+            }
+            head_segment_add(dot + j * kGatMaxHeads, x, lane, c0, dim, hd);
+        }
+    }
+}
+
+// GAT backward, a_j = exp(e_j - lse[d, h]) / S recomputed from the saved log-sum-exp, S the row's sum of exp(e_j - lse[d, h]):
+//   grad_feat[s_j, h, :] += a_j g[d, h, :],  t_j = a_j (<g[d, h, :], feat[s_j, h, :]> - <g[d, h, :], out[d, h, :]>) (z_j > 0 ? 1 : slope),
+//   grad_el[s_j, h] += t_j,  grad_er[d, h] = sum_j t_j.
+// A lane per float of the [H * dim] row, 64 at a time; the per-head dot products are summed by head_segment_add into LDS in a fixed
+// order.  grad_feat and grad_el take hardware float atomics (zeroed by the caller); grad_er is written whole, one tree per chunk.
+template <bool CSR>
+__global__ __launch_bounds__(kBlock) void gat_aggregate_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                        int fanout, const float* __restrict__ el, const float* __restrict__ er,
+                                                                        const float* __restrict__ feat, const float* __restrict__ out,
+                                                                        const float* __restrict__ lse, const float* __restrict__ grad_out,
+                                                                        float* __restrict__ grad_feat, float* __restrict__ grad_el,
+                                                                        float* __restrict__ grad_er, int64_t n_dst, int heads, int dim, float slope) {
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // a_j of the chunk, [edge][head]
+    __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g, feat_j>, [edge][head]
+    __shared__ float hs_lds[kWavesPerBlock][3 * kGatMaxHeads];   // per head: <g, out>, the sum of t_j so far, S of a row of several chunks
+    const auto [lane, wave, n_waves] = wave_rows();
+    float* w = w_lds[threadIdx.x >> 6];
+    float* dot = dot_lds[threadIdx.x >> 6];
+    float* gout = hs_lds[threadIdx.x >> 6];
+    float* ter = gout + kGatMaxHeads;
+    float* ssum = ter + kGatMaxHeads;
+    const int hd = heads * dim;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        const float* g = grad_out + d * hd;
+        const bool one = backward_row_front<GatScore>(w, gout, ssum, idx, beg, end, el, er, feat, out + d * hd, lse + d * heads, g, d, lane, heads,
+                                                      hd, dim, slope);
+        if (lane < heads) ter[lane] = 0.0f; // the previous row's reader is past the front's syncs
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
+            wave_lds_sync(); // the previous chunk has read w and dot
+            for (int h = 0; h < heads; ++h) {
+                float a = 0.0f;
+                if (mine >= 0) a = expf(GatScore::score(el, er, mine, d, heads, h, slope) - lse[d * heads + h]);
+                w[lane * kGatMaxHeads + h] = normalised(a, one ? wave_sum(a) : ssum[h]);
+                dot[lane * kGatMaxHeads + h] = 0.0f;
+            }
+            wave_lds_sync();
+            dot_grad_feat_walk<true>(w, dot, mine, n, feat, g, grad_feat, lane, dim, hd);
+            wave_lds_sync();
+            for (int h = 0; h < heads; ++h) {
+                float t = 0.0f;
+                if (mine >= 0) {
+                    const float z = el[(int64_t)mine * heads + h] + er[d * heads + h];
+                    t = w[lane * kGatMaxHeads + h] * (dot[lane * kGatMaxHeads + h] - gout[h]) * (z > 0.0f ? 1.0f : slope);
+                    unsafeAtomicAdd(grad_el + (int64_t)mine * heads + h, t);
+                }
+                const float ts = wave_sum(t);
+                if (lane == 0) ter[h] += ts;
+            }
+        }
+        wave_lds_sync();
+        if (lane < heads) grad_er[d * heads + lane] = ter[lane];
+    }
+}
+
+// GATv2 backward, all three gradients in one launch, each of them optional (null).  a_j = exp(e_j - lse[d, h]) / S (`normalised` above) with e_j
 // recomputed by a second score pass, which also sums dot_j = <g[d, h, :], feat_src[s_j, h, :]>; then per edge and head
 // t_j = a_j (dot_j - <g, out>), and a third walk over the chunk's rows, a lane per float c, with k_jc = z_jc > 0 ? 1 : slope:
 //   grad_src[s_j, c] += a_j g[d, c] + t_j attn[c] k_jc   hardware float atomics (zeroed by the caller), 256 contiguous bytes per wave
@@ -575,75 +674,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_aggregate_backward_kernel(const 
     }
 }
 
-// Scaled dot-product attention on a block (the message step of DGL's DotGatConv and HGTConv, PyG's TransformerConv without edge
-// features; the projections stay in torch).  Every slot carries the row of k / v its edge reads (row, -1 = no edge; the block's own
-// index array in the dense form).  For dst d, head h and the slots j of d with row_j >= 0:
-//   e_j = scale <q[d, h, :], k[row_j, h, :]>,  a_j = softmax of e over the row,  out[d, h, :] = sum_j a_j v[row_j, h, :]
-// gatv2_aggregate_kernel with another score pass: a lane per float of the [H * D] row, 64 floats at a time, q[d] of the pass in
-// registers, the chunk's edges in the inner loop, the per-head sums added into the LDS [edge][head] array by head_segment_add in a
-// fixed order; the scale is applied to the finished sum by dot_score, in both directions.  The weighted sum then reads the chunk's v rows.
-// Nothing of size E is written.
-//
-// A slot's score from its finished dot product: one rounded product, never contracted into the subtraction that follows it (e - m in
-// the forward, e - lse in the backward).  Fused, the backward's fma(scale, qk, -lse) would take the product unrounded while the
-// forward's maximum and lse are made of rounded scores: a_j = exp(e_j - lse) is then off by u |e_j|, edge by edge, the a_j of a row no
-// longer sum to what lse says, and sum_j t_j, zero in exact arithmetic, grows with the scores' common offset.
-__device__ __forceinline__ float dot_score(float scale, float qk) {
-#pragma clang fp contract(off)
-    return scale * qk;
-}
-
-// e[j * kGatMaxHeads + h] += <q[d, h, :], k[row_j, h, :]> for the n slots of a chunk; with DOT also dot[..] += <g[h, :], v[row_j, h, :]>.
-template <bool DOT>
-__device__ __forceinline__ void dot_score_pass(float* e, float* dot, int32_t mine, int n, const float* __restrict__ k,
-                                               const float* __restrict__ qd, const float* __restrict__ v, const float* __restrict__ g, int lane,
-                                               int hd, int dim) {
-    for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: head_segment_add shuffles across every lane
-        const int c = c0 + lane;
-        const bool in = c < hd;
-        const float qc = in ? qd[c] : 0.0f;
-        const float gc = DOT && in ? g[c] : 0.0f;
-        for (int j = 0; j < n; ++j) {
-            const int32_t s = __shfl(mine, j);
-            if (s < 0) continue; // wave-uniform
-            head_segment_add(e + j * kGatMaxHeads, in ? qc * k[(int64_t)s * hd + c] : 0.0f, lane, c0, dim, hd);
-            if (DOT) head_segment_add(dot + j * kGatMaxHeads, in ? gc * v[(int64_t)s * hd + c] : 0.0f, lane, c0, dim, hd);
-        }
-    }
-}
-
-template <int VEC, bool CSR>
-__global__ __launch_bounds__(kBlock) void dot_gat_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ row, int fanout,
-                                                                   const float* __restrict__ q, const float* __restrict__ k,
-                                                                   const float* __restrict__ v, float* __restrict__ out, float* __restrict__ lse,
-                                                                   int64_t n_dst, int heads, int dim, float scale) {
-    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads]; // the chunk's dot products first, [edge][head]
-    __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];
-    const auto [lane, wave, n_waves] = wave_rows();
-    const SoftmaxLds s = softmax_lds(w_lds[threadIdx.x >> 6], st_lds[threadIdx.x >> 6]);
-    const int hd = heads * dim, units = hd / VEC, upl = dim / VEC;
-    for (int64_t d = wave; d < n_dst; d += n_waves) {
-        int64_t beg, end;
-        row_range<CSR>(indptr, fanout, d, &beg, &end);
-        softmax_row_begin(s, lane, heads);
-        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
-            int32_t mine;
-            const int n = load_chunk(row, e0, end, lane, &mine);
-            wave_lds_sync(); // the previous chunk has read w and scl; m_run / l_run are set
-            for (int h = 0; h < heads; ++h) s.w[lane * kGatMaxHeads + h] = 0.0f;
-            wave_lds_sync();
-            dot_score_pass<false>(s.w, nullptr, mine, n, k, q + d * hd, nullptr, nullptr, lane, hd, dim);
-            wave_lds_sync();
-            for (int h = 0; h < heads; ++h) // lane j reads and rewrites only edge j's words
-                softmax_chunk_step(s, h, mine >= 0 ? dot_score(scale, s.w[lane * kGatMaxHeads + h]) : kNegInf, mine >= 0, lane);
-            wave_lds_sync();
-            softmax_accumulate<VEC>(s, out + d * hd, v, mine, n, e0 == beg, e0 + 64 >= end, lane, hd, units, upl);
-        }
-        softmax_row_end<VEC>(s, out + d * hd, lse + d * heads, beg == end, lane, heads, units);
-    }
-}
-
-// Backward, all three gradients in one launch, each of them optional (null).  A second score pass gives the dot products again and
+// Dot-product backward, all three gradients in one launch, each of them optional (null).  A second score pass gives the dot products again and
 // dot_j = <g[d, h, :], v[row_j, h, :]>; then per edge and head a_j = exp(e_j - lse[d, h]) / S (`normalised` above), e_j the forward's bit for bit (dot_score), and
 // t_j = a_j (dot_j - <g, out>), and a third walk over the chunk's rows, a lane per float c:
 //   grad_v[row_j, c] += a_j g[d, c]             hardware float atomics (zeroed by the caller), 256 contiguous bytes per wave instruction;
@@ -672,38 +703,13 @@ __global__ __launch_bounds__(kBlock) void dot_gat_aggregate_backward_kernel(cons
         row_range<CSR>(indptr, fanout, d, &beg, &end);
         const float* g = grad_out + d * hd;
         const float* qd = q + d * hd;
-        wave_lds_sync(); // the previous row has read gout
-        if (lane < heads) gout[lane] = ssum[lane] = 0.0f;
-        wave_lds_sync();
-        head_dots(gout, g, out + d * hd, lane, dim, hd);
-        const bool one = end - beg <= 64; // wave-uniform: the row is one chunk
-        if (!one) {                       // S per head from a score pass of its own, chunk after chunk (lane 0 alone touches ssum)
-            for (int64_t e0 = beg; e0 < end; e0 += 64) {
-                int32_t mine;
-                const int n = load_chunk(row, e0, end, lane, &mine);
-                wave_lds_sync(); // the previous chunk has read w
-                for (int h = 0; h < heads; ++h) w[lane * kGatMaxHeads + h] = 0.0f;
-                wave_lds_sync();
-                dot_score_pass<false>(w, nullptr, mine, n, k, qd, nullptr, nullptr, lane, hd, dim);
-                wave_lds_sync();
-                for (int h = 0; h < heads; ++h) {
-                    const float sum = wave_sum(mine >= 0 ? expf(dot_score(scale, w[lane * kGatMaxHeads + h]) - lse[d * heads + h]) : 0.0f);
-                    if (lane == 0) ssum[h] += sum;
-                }
-            }
-            wave_lds_sync();
-        }
+        const bool one = backward_row_front<DotScore>(w, gout, ssum, row, beg, end, q, k, v, out + d * hd, lse + d * heads, g, d, lane, heads, hd, dim,
+                                                      scale);
         for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts
             int32_t mine;
             const int n = load_chunk(row, e0, end, lane, &mine);
             wave_lds_sync(); // the previous chunk has read w and dot
-            for (int h = 0; h < heads; ++h) {
-                w[lane * kGatMaxHeads + h] = 0.0f;
-                dot[lane * kGatMaxHeads + h] = 0.0f;
-            }
-            wave_lds_sync();
-            dot_score_pass<true>(w, dot, mine, n, k, qd, v, g, lane, hd, dim);
-            wave_lds_sync();
+            score_pass_chunk<DotScore, true>(w, dot, mine, n, q, k, v, d, g, lane, heads, hd, dim, scale);
             for (int h = 0; h < heads; ++h) { // lane j reads and rewrites only edge j's words
                 float a = 0.0f, t = 0.0f;
                 if (mine >= 0) a = expf(dot_score(scale, w[lane * kGatMaxHeads + h]) - lse[d * heads + h]);
@@ -1022,7 +1028,7 @@ __global__ __launch_bounds__(kBlock) void rel_sum_backward_kernel(const int64_t*
 // traffic: it keeps the running max and sum of every (relation, head) in LDS (hence R * H <= kRelGatMaxStates), visiting per chunk
 // only the relations present in it -- a ballot on the first live lane's type peels them off one by one -- with a masked wave_max /
 // wave_sum each.  The second pass then knows every group's max m and sum l: a_j = exp(e_j - m) / l, and the sum over edges and
-// relations is one plain weighted sum into out[d], with softmax_accumulate's lane mapping and nothing to rescale.  A row of at most 64
+// relations is one plain weighted sum into out[d]: softmax_accumulate with FINAL weights, nothing to rescale.  A row of at most 64
 // slots (every fixed row) keeps its (row, type) words in registers between the passes.  A slot whose type is outside [0, R) is
 // treated as padding.  lse[d, r, h] = m + log(l), -inf where (d, r) has no edge, is all the backward keeps.
 constexpr int kRelGatMaxStates = 256;
@@ -1104,25 +1110,14 @@ __global__ __launch_bounds__(kBlock) void rel_gat_aggregate_kernel(const int64_t
                 w[lane * kGatMaxHeads + h] = a;
             }
             wave_lds_sync();
-            for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
-                const int u = u0 + lane;
-                const int hu = u < units ? u / upl : 0;
-                float* o = out + d * hd + (int64_t)u * VEC;
-                vf acc = vf(0.0f);
-                if (e0 != beg && u < units) acc = *reinterpret_cast<const vf*>(o);
-                for (int j = 0; j < n; ++j) {
-                    const int32_t s = __shfl(mine, j);
-                    if (s >= 0 && u < units) acc += w[j * kGatMaxHeads + hu] * *reinterpret_cast<const vf*>(feat + (int64_t)s * hd + (int64_t)u * VEC);
-                }
-                if (u < units) *reinterpret_cast<vf*>(o) = acc;
-            }
+            softmax_accumulate<VEC, true>(SoftmaxLds{w, nullptr, nullptr, nullptr}, out + d * hd, feat, mine, n, e0 == beg, false, lane, hd, units, upl);
         }
     }
 }
 
 // One chunk of the backward below: lane j takes slot e0 + j's (row, type), and leaves in LDS, for every head, a_j = exp(e_j - lse) in w,
-// divided by its group's S[type_j, h] where S is given, and <g[h, :], feat[row_j, h, :]> in dot (gat_aggregate_backward_kernel's walk: a lane per float of the [H * dim] row, the per-head
-// sums by head_segment_add in a fixed order); with ADD also grad_feat[row_j, h, :] += a_j g[h, :].  -> the chunk's length.
+// divided by its group's S[type_j, h] where S is given, and <g[h, :], feat[row_j, h, :]> in dot (dot_grad_feat_walk, GAT's); with ADD
+// also grad_feat[row_j, h, :] += a_j g[h, :].  -> the chunk's length.
 template <bool ADD>
 __device__ __forceinline__ int rel_gat_chunk_dots(float* w, float* dot, const int32_t* __restrict__ row, const int32_t* __restrict__ etype,
                                                   int64_t e0, int64_t end, int lane, int num_rels, int heads, int dim,
@@ -1130,7 +1125,6 @@ __device__ __forceinline__ int rel_gat_chunk_dots(float* w, float* dot, const in
                                                   const float* __restrict__ lse_d, const float* S, const float* __restrict__ feat,
                                                   const float* __restrict__ g, float* __restrict__ grad_feat, float slope, int32_t* mine_out,
                                                   int32_t* t_out) {
-    const int hd = heads * dim;
     int32_t mine, t;
     const int n = load_rel_chunk(row, etype, e0, end, lane, num_rels, &mine, &t);
     wave_lds_sync(); // the previous chunk has read w and dot
@@ -1144,21 +1138,7 @@ __device__ __forceinline__ int rel_gat_chunk_dots(float* w, float* dot, const in
         dot[lane * kGatMaxHeads + h] = 0.0f;
     }
     wave_lds_sync();
-    for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: head_segment_add shuffles across every lane
-        const int c = c0 + lane;
-        const int hc = c < hd ? c / dim : 0;
-        const float gc = c < hd ? g[c] : 0.0f;
-        for (int j = 0; j < n; ++j) {
-            const int32_t s = __shfl(mine, j);
-            if (s < 0) continue; // wave-uniform
-            float x = 0.0f;
-            if (c < hd) {
-                x = gc * feat[(int64_t)s * hd + c];
-                if (ADD) unsafeAtomicAdd(grad_feat + (int64_t)s * hd + c, w[j * kGatMaxHeads + hc] * gc);
-            }
-            head_segment_add(dot + j * kGatMaxHeads, x, lane, c0, dim, hd);
-        }
-    }
+    dot_grad_feat_walk<ADD>(w, dot, mine, n, feat, g, grad_feat, lane, dim, heads * dim);
     wave_lds_sync();
     *mine_out = mine, *t_out = t;
     return n;
@@ -1352,16 +1332,17 @@ int mean_backward_launch(int device, const int64_t* indptr, const int32_t* idx, 
     return COALA_OK;
 }
 
-template <bool CSR>
-int gat_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* el, const float* er, const float* feat, float* out,
-               float* lse, int64_t n_dst, int heads, int dim, float slope, void* stream) {
+// The forward of GAT, GATv2 and dot-product attention: (a, b, c) and param as Score names them; 16-B accesses go to Score's value table.
+template <typename Score, bool CSR>
+int attention_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* a, const float* b, const float* c, float* out,
+                     float* lse, int64_t n_dst, int heads, int dim, float param, void* stream) {
     if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
     if (n_dst == 0) return COALA_OK;
-    if ((CSR && !indptr) || !idx || !el || !er || !feat || !out || !lse) return fail(COALA_EINVAL, "null buffer");
+    if ((CSR && !indptr) || !idx || !a || !b || !c || !out || !lse) return fail(COALA_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(device));
-    dispatch_vec(vec4_ok(dim, feat, out), [&](auto vec) {
-        hipLaunchKernelGGL((gat_aggregate_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx,
-                           fanout, el, er, feat, out, lse, n_dst, heads, dim, slope);
+    dispatch_vec(vec4_ok(dim, Score::values(a, b, c), out), [&](auto vec) {
+        hipLaunchKernelGGL((attention_aggregate_kernel<Score, decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream,
+                           indptr, idx, fanout, a, b, c, out, lse, n_dst, heads, dim, param);
     });
     HIPCHK(hipGetLastError());
     return COALA_OK;
@@ -1378,21 +1359,6 @@ int gat_backward_launch(int device, const int64_t* indptr, const int32_t* idx, i
     HIPCHK(hipSetDevice(device));
     hipLaunchKernelGGL(gat_aggregate_backward_kernel<CSR>, row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx, fanout, el, er, feat,
                        out, lse, grad_out, grad_feat, grad_el, grad_er, n_dst, heads, dim, slope);
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-template <bool CSR>
-int gatv2_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* feat_src, const float* feat_dst,
-                 const float* attn, float* out, float* lse, int64_t n_dst, int heads, int dim, float slope, void* stream) {
-    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
-    if (n_dst == 0) return COALA_OK;
-    if ((CSR && !indptr) || !idx || !feat_src || !feat_dst || !attn || !out || !lse) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    dispatch_vec(vec4_ok(dim, feat_src, out), [&](auto vec) {
-        hipLaunchKernelGGL((gatv2_aggregate_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx,
-                           fanout, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, slope);
-    });
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
@@ -1422,21 +1388,6 @@ int gatv2_backward_launch(int device, const int64_t* indptr, const int32_t* idx,
     else if (passes <= 4) launch(std::integral_constant<int, 4>{});
     else if (passes <= 8) launch(std::integral_constant<int, 8>{});
     else launch(std::integral_constant<int, 16>{});
-    HIPCHK(hipGetLastError());
-    return COALA_OK;
-}
-
-template <bool CSR>
-int dot_gat_launch(int device, const int64_t* indptr, const int32_t* row, int fanout, const float* q, const float* k, const float* v, float* out,
-                   float* lse, int64_t n_dst, int heads, int dim, float scale, void* stream) {
-    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
-    if (n_dst == 0) return COALA_OK;
-    if ((CSR && !indptr) || !row || !q || !k || !v || !out || !lse) return fail(COALA_EINVAL, "null buffer");
-    HIPCHK(hipSetDevice(device));
-    dispatch_vec(vec4_ok(dim, v, out), [&](auto vec) {
-        hipLaunchKernelGGL((dot_gat_aggregate_kernel<decltype(vec)::value, CSR>), row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, row,
-                           fanout, q, k, v, out, lse, n_dst, heads, dim, scale);
-    });
     HIPCHK(hipGetLastError());
     return COALA_OK;
 }
@@ -1959,7 +1910,7 @@ int coala_block_mean_aggregate_csr_backward(int device, const int64_t* indptr, c
 
 int coala_block_gat_aggregate(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, float* out, float* lse,
                               int64_t n_dst, int fanout, int heads, int dim, float negative_slope, void* stream) {
-    return gat_launch<false>(device, nullptr, nbr, fanout, el, er, feat, out, lse, n_dst, heads, dim, negative_slope, stream);
+    return attention_launch<GatScore, false>(device, nullptr, nbr, fanout, el, er, feat, out, lse, n_dst, heads, dim, negative_slope, stream);
 }
 
 int coala_block_gat_aggregate_backward(int device, const int32_t* nbr, const float* el, const float* er, const float* feat, const float* out,
@@ -1971,7 +1922,7 @@ int coala_block_gat_aggregate_backward(int device, const int32_t* nbr, const flo
 
 int coala_block_gat_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er, const float* feat,
                                   float* out, float* lse, int64_t n_dst, int heads, int dim, float negative_slope, void* stream) {
-    return gat_launch<true>(device, indptr, indices, 0, el, er, feat, out, lse, n_dst, heads, dim, negative_slope, stream);
+    return attention_launch<GatScore, true>(device, indptr, indices, 0, el, er, feat, out, lse, n_dst, heads, dim, negative_slope, stream);
 }
 
 int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* el, const float* er,
@@ -1983,7 +1934,7 @@ int coala_block_gat_aggregate_csr_backward(int device, const int64_t* indptr, co
 
 int coala_block_gatv2_aggregate(int device, const int32_t* nbr, const float* feat_src, const float* feat_dst, const float* attn, float* out,
                                 float* lse, int64_t n_dst, int fanout, int heads, int dim, float negative_slope, void* stream) {
-    return gatv2_launch<false>(device, nullptr, nbr, fanout, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, negative_slope, stream);
+    return attention_launch<Gatv2Score, false>(device, nullptr, nbr, fanout, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, negative_slope, stream);
 }
 
 int coala_block_gatv2_aggregate_backward(int device, const int32_t* nbr, const float* feat_src, const float* feat_dst, const float* attn,
@@ -1997,7 +1948,7 @@ int coala_block_gatv2_aggregate_backward(int device, const int32_t* nbr, const f
 int coala_block_gatv2_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* feat_src, const float* feat_dst,
                                     const float* attn, float* out, float* lse, int64_t n_dst, int heads, int dim, float negative_slope,
                                     void* stream) {
-    return gatv2_launch<true>(device, indptr, indices, 0, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, negative_slope, stream);
+    return attention_launch<Gatv2Score, true>(device, indptr, indices, 0, feat_src, feat_dst, attn, out, lse, n_dst, heads, dim, negative_slope, stream);
 }
 
 int coala_block_gatv2_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const float* feat_src,
@@ -2010,7 +1961,7 @@ int coala_block_gatv2_aggregate_csr_backward(int device, const int64_t* indptr, 
 
 int coala_block_dot_gat_aggregate(int device, const int32_t* row, const float* q, const float* k, const float* v, float* out, float* lse,
                                   int64_t n_dst, int fanout, int heads, int dim, float scale, void* stream) {
-    return dot_gat_launch<false>(device, nullptr, row, fanout, q, k, v, out, lse, n_dst, heads, dim, scale, stream);
+    return attention_launch<DotScore, false>(device, nullptr, row, fanout, q, k, v, out, lse, n_dst, heads, dim, scale, stream);
 }
 
 int coala_block_dot_gat_aggregate_backward(int device, const int32_t* row, const float* q, const float* k, const float* v, const float* out,
@@ -2022,7 +1973,7 @@ int coala_block_dot_gat_aggregate_backward(int device, const int32_t* row, const
 
 int coala_block_dot_gat_aggregate_csr(int device, const int64_t* indptr, const int32_t* row, const float* q, const float* k, const float* v,
                                       float* out, float* lse, int64_t n_dst, int heads, int dim, float scale, void* stream) {
-    return dot_gat_launch<true>(device, indptr, row, 0, q, k, v, out, lse, n_dst, heads, dim, scale, stream);
+    return attention_launch<DotScore, true>(device, indptr, row, 0, q, k, v, out, lse, n_dst, heads, dim, scale, stream);
 }
 
 int coala_block_dot_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* row, const float* q, const float* k,
