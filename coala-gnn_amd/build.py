@@ -7,7 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("coala_cache.hip", "coala_sampler.hip", "coala_block_ops.hip", "coala_host.cpp", "coala_coloring.cpp", "coala_comm.cpp")]
 PYBIND_SRC = os.path.join(_HERE, "csrc", "coala_pybind.cpp")
-HEADERS = [os.path.join(_ROOT, "include", "coala_hip.h"), os.path.join(_HERE, "csrc", "coala_internal.h")]
+HEADERS = [os.path.join(_ROOT, "include", "coala_hip.h")] + [os.path.join(_HERE, "csrc", f) for f in ("coala_internal.h", "coala_partition.h")]
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libcoala_hip.so")
 

@@ -41,6 +41,7 @@
 
 #include "../../include/coala_hip.h"
 #include "coala_internal.h"
+#include "coala_partition.h"
 
 namespace {
 
@@ -1056,59 +1057,26 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(float* __restrict__ o
 }
 
 // ---------------------------------------------------------------------------------------------------------- route
-// Stable bucketing by owner = id % n_parts (cache_kernel.cu:79-91, :4-17) with wave ballots + prefix sums instead of
-// atomics, so the slot order inside a bucket is the batch order on every run.
-constexpr int kRouteItems = 4;            // ids per lane
-constexpr int kRouteTile = 64 * kRouteItems; // ids per wave
+// Stable bucketing by owner = id % n_parts: thin kernels over the per-tile bodies of coala_partition.h, grid-stride over the wave tiles.  A
+// routed id goes to node_out with its position in the batch beside it in map_out.
+struct RouteSink {
+    int64_t* __restrict__ node_out;
+    int64_t* __restrict__ map_out;
+    __device__ __forceinline__ void operator()(int64_t dest, int64_t i, int64_t id) const { node_out[dest] = id, map_out[dest] = i; }
+};
 
-__device__ __forceinline__ uint32_t owner_of(uint64_t id, uint32_t n_parts, int pshift) {
-    if (pshift >= 0) return (uint32_t)id & (n_parts - 1);
-    if ((id >> 32) == 0) return (uint32_t)id % n_parts;
-    return (uint32_t)(id % n_parts);
+__global__ __launch_bounds__(kBlock) void route_count_kernel(const int64_t* __restrict__ idx, int64_t n, uint32_t n_parts, int pshift,
+                                                             uint32_t* __restrict__ wave_counts) {
+    const int64_t n_tiles = partition_tiles(n), n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    for (int64_t tile = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); tile < n_tiles; tile += n_waves)
+        partition_count_tile(idx, n, tile, n_parts, pshift, wave_counts);
 }
 
-__global__ __launch_bounds__(256) void route_count_kernel(const int64_t* __restrict__ idx, int64_t n, uint32_t n_parts,
-                                                          int pshift, uint32_t* __restrict__ wave_counts, int64_t n_tiles) {
-    const int lane = threadIdx.x & 63;
-    const int64_t tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (tile >= n_tiles) return;
-    uint32_t mine = 0; // lane g accumulates the count of owner g
-    for (int j = 0; j < kRouteItems; ++j) {
-        const int64_t i = tile * kRouteTile + j * 64 + lane;
-        const bool valid = i < n;
-        const uint32_t o = valid ? owner_of((uint64_t)idx[i], n_parts, pshift) : 0xFFFFFFFFu;
-        for (uint32_t g = 0; g < n_parts; ++g) {
-            const uint64_t mask = __ballot(o == g);
-            if ((uint32_t)lane == g) mine += (uint32_t)__builtin_popcountll(mask);
-        }
-    }
-    if ((uint32_t)lane < n_parts) wave_counts[tile * n_parts + lane] = mine;
-}
-
-// One block, one wave per owner column (looping when there are more owners than waves): wave-level exclusive scan of
-// wave_counts over the tiles with a running carry, then bucket totals and bucket bases.
-__global__ __launch_bounds__(1024) void route_scan_kernel(uint32_t* __restrict__ wave_counts, int64_t n_tiles, uint32_t n_parts,
-                                                          int64_t bucket_stride, int64_t* __restrict__ counts_out,
-                                                          int64_t* __restrict__ offsets_out, int64_t* __restrict__ bases) {
-    __shared__ int64_t totals[64];
-    const int lane = threadIdx.x & 63;
-    const uint32_t n_waves = blockDim.x >> 6;
-    for (uint32_t g = threadIdx.x >> 6; g < n_parts; g += n_waves) {
-        uint32_t carry = 0;
-        for (int64_t t0 = 0; t0 < n_tiles; t0 += 64) {
-            const int64_t t = t0 + lane;
-            const uint32_t c = (t < n_tiles) ? wave_counts[t * n_parts + g] : 0u;
-            uint32_t incl = c;
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t v = __shfl_up(incl, off);
-                if (lane >= off) incl += v;
-            }
-            if (t < n_tiles) wave_counts[t * n_parts + g] = carry + incl - c; // exclusive offset of this tile inside bucket g
-            carry += __shfl(incl, 63);
-        }
-        if (lane == 0) totals[g] = (int64_t)carry;
-    }
-    __syncthreads();
+// thread 0: bucket totals and bases; bucket_stride > 0 places bucket g at g * bucket_stride (the [G][stride] layout) instead of packing
+__global__ __launch_bounds__(1024) void route_scan_kernel(uint32_t* __restrict__ wave_counts, int64_t n, uint32_t n_parts, int64_t bucket_stride,
+                                                          int64_t* __restrict__ counts_out, int64_t* __restrict__ offsets_out, int64_t* __restrict__ bases) {
+    __shared__ int64_t totals[kMaxParts];
+    partition_scan_columns(wave_counts, partition_tiles(n), n_parts, totals);
     if (threadIdx.x == 0) {
         int64_t acc = 0;
         for (uint32_t g = 0; g < n_parts; ++g) {
@@ -1122,32 +1090,12 @@ __global__ __launch_bounds__(1024) void route_scan_kernel(uint32_t* __restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void route_scatter_kernel(const int64_t* __restrict__ idx, int64_t n, uint32_t n_parts,
-                                                            int pshift, const uint32_t* __restrict__ wave_offsets,
-                                                            const int64_t* __restrict__ bases, int64_t* __restrict__ node_out,
-                                                            int64_t* __restrict__ map_out, int64_t n_tiles) {
-    const int lane = threadIdx.x & 63;
-    const int64_t tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (tile >= n_tiles) return;
-    int64_t off = 0; // lane g: next free slot of bucket g for this wave
-    if ((uint32_t)lane < n_parts) off = bases[lane] + (int64_t)wave_offsets[tile * n_parts + lane];
-    for (int j = 0; j < kRouteItems; ++j) {
-        const int64_t i = tile * kRouteTile + j * 64 + lane;
-        const bool valid = i < n;
-        const int64_t id = valid ? idx[i] : 0;
-        const uint32_t o = valid ? owner_of((uint64_t)id, n_parts, pshift) : 0xFFFFFFFFu;
-        int64_t dest = -1;
-        for (uint32_t g = 0; g < n_parts; ++g) {
-            const uint64_t mask = __ballot(o == g);
-            const int64_t bg = __shfl(off, (int)g);
-            if (o == g) dest = bg + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
-            if ((uint32_t)lane == g) off += __builtin_popcountll(mask);
-        }
-        if (valid) {
-            node_out[dest] = id;
-            map_out[dest] = i;
-        }
-    }
+__global__ __launch_bounds__(kBlock) void route_scatter_kernel(const int64_t* __restrict__ idx, int64_t n, uint32_t n_parts, int pshift,
+                                                               const uint32_t* __restrict__ wave_offsets, const int64_t* __restrict__ bases,
+                                                               int64_t* __restrict__ node_out, int64_t* __restrict__ map_out) {
+    const int64_t n_tiles = partition_tiles(n), n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    for (int64_t tile = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); tile < n_tiles; tile += n_waves)
+        partition_scatter_tile(idx, n, tile, n_parts, pshift, wave_offsets, bases, RouteSink{node_out, map_out});
 }
 
 } // namespace
@@ -1713,7 +1661,7 @@ int coala_cache_create(const coala_cache_config_t* cfg, coala_cache_t** out) {
         if ((rc = alloc((void**)&d.set_head, sets * 8))) break;
         if ((rc = alloc((void**)&d.stats, kStatWords * 8))) break;   // (the per-block sums and what lies behind them: kStatWriteBad ... kStatList)
         if ((rc = alloc((void**)&d.lines, slots * (uint64_t)cd * 4))) break;
-        if ((rc = alloc((void**)&h->route_bases, 65 * 8))) break;
+        if ((rc = alloc((void**)&h->route_bases, (kMaxParts + 1) * sizeof(int64_t)))) break;
         if (hipMemset(d.keys, 0xFF, slots * tag_bytes) != hipSuccess || hipMemset(d.set_cnt, 0, sets * 8) != hipSuccess ||
             hipMemset(d.color_meta, 0, slots * 4) != hipSuccess || hipMemset(d.set_head, 0, sets * 8) != hipSuccess ||
             hipMemset(d.stats, 0, kStatWords * 8) != hipSuccess) {
@@ -1901,23 +1849,22 @@ int coala_cache_serve_abort(coala_cache_t* h, void* stream) {
 int coala_cache_route(coala_cache_t* h, const int64_t* idx, int64_t n, int n_parts, int64_t bucket_stride,
                       int64_t* node_out, int64_t* map_out, int64_t* counts_out, int64_t* offsets_out, void* stream) {
     if (!h) return fail(COALA_EINVAL, "null handle");
-    if (n < 0 || n_parts < 1 || n_parts > 64) return fail(COALA_EINVAL, "bad n or n_parts (1..64)");
+    if (n < 0 || n_parts < 1 || n_parts > kMaxParts) return fail(COALA_EINVAL, "bad n or n_parts (1..64)");
     if (!node_out || !map_out || !counts_out || (n > 0 && !idx)) return fail(COALA_EINVAL, "null buffer");
     if (bucket_stride < 0) return fail(COALA_EINVAL, "negative bucket_stride");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = enter(h, s)) return rc;
-    const int64_t n_tiles = (n + kRouteTile - 1) / kRouteTile;
+    const int64_t n_tiles = partition_tiles(n);
     const uint64_t need = (uint64_t)(n_tiles > 0 ? n_tiles : 1) * (uint64_t)n_parts;
     if (int rc = grow((void**)&h->wave_counts, &h->wave_counts_cap, need, sizeof(uint32_t), s, 4096)) return rc;
     const int pshift = ilog2_exact((uint64_t)n_parts);
-    const int blocks = (int)((n_tiles + 3) / 4);
-    if (n_tiles > 0)
-        hipLaunchKernelGGL(route_count_kernel, dim3(blocks), dim3(256), 0, s, idx, n, (uint32_t)n_parts, pshift, h->wave_counts, n_tiles);
-    hipLaunchKernelGGL(route_scan_kernel, dim3(1), dim3(64 * (n_parts < 16 ? n_parts : 16)), 0, s, h->wave_counts, n_tiles, (uint32_t)n_parts, bucket_stride,
+    const dim3 grid = partition_grid(n_tiles), blk(kBlock);
+    if (n_tiles > 0) hipLaunchKernelGGL(route_count_kernel, grid, blk, 0, s, idx, n, (uint32_t)n_parts, pshift, h->wave_counts);
+    hipLaunchKernelGGL(route_scan_kernel, dim3(1), partition_scan_block((uint32_t)n_parts), 0, s, h->wave_counts, n, (uint32_t)n_parts, bucket_stride,
                        counts_out, offsets_out, h->route_bases);
     if (n_tiles > 0)
-        hipLaunchKernelGGL(route_scatter_kernel, dim3(blocks), dim3(256), 0, s, idx, n, (uint32_t)n_parts, pshift, h->wave_counts,
-                           h->route_bases, node_out, map_out, n_tiles);
+        hipLaunchKernelGGL(route_scatter_kernel, grid, blk, 0, s, idx, n, (uint32_t)n_parts, pshift, (const uint32_t*)h->wave_counts,
+                           (const int64_t*)h->route_bases, node_out, map_out);
     return leave(h, s);
 }
 

@@ -197,6 +197,7 @@
 
 #include "../../include/coala_hip.h"
 #include "coala_internal.h"
+#include "coala_partition.h"
 
 #define fail coala_fail_
 #define HIPCHK COALA_HIPCHK
@@ -208,8 +209,6 @@ constexpr int kItems = 4;                   // items per thread in the scan phas
 constexpr int kTile = kBlock * kItems;      // items per block tile
 constexpr int kMaxTiles = 8192;             // tiles per layer (8.4 M items): status words of the single-pass scan
 constexpr int kRing = 8;                    // calls whose counts may be outstanding at once
-constexpr int kMaxParts = 64;
-constexpr int kRouteTile = 64 * kItems;     // ids per wave step of the bucketing phases
 constexpr int64_t kItemLimit = (int64_t)kMaxTiles * kTile;
 constexpr int kFull = -1;                   // fan-out of a full layer: every in-edge
 // device count words of layer l, relative to its base counts_dev + l: [0] n_dst, [kItemsOff] items, [kEdgesOff] edges of a full
@@ -1521,59 +1520,27 @@ __global__ __launch_bounds__(kBlock) void relabel_clear_kernel(const int64_t* __
 }
 
 // ---------------------------------------------------------------------------------------------------------- owner bucketing
-// Stable partition of the input nodes by owner = id % n_parts (same ballot / prefix-sum scheme as the cache's route kernels), then
-// the last block is re-indexed through the permutation.
-// (A copy of the cache's owner_of / route_count / route_scan / route_scatter, kept apart on purpose: coala_cache.hip's recorded PMC passes hold
-// only while that file's bytes do.  Merge them with the next change that re-takes those passes.)
-__device__ __forceinline__ uint32_t owner_of(uint64_t id, uint32_t n_parts, int pshift) {
-    if (pshift >= 0) return (uint32_t)id & (n_parts - 1);
-    if ((id >> 32) == 0) return (uint32_t)id % n_parts;
-    return (uint32_t)(id % n_parts);
-}
+// Stable partition of the input nodes by owner = id % n_parts, then the last block is re-indexed through the permutation new_of_old.  The
+// per-tile bodies are coala_partition.h's; the kernels here are the sampler's own shells over them: the list's length comes from the device
+// (the layer's scan wrote it), and the bucket sizes also go to the call's pinned host words.
+struct BucketSink {
+    int64_t* __restrict__ bucketed;
+    uint32_t* __restrict__ new_of_old;
+    __device__ __forceinline__ void operator()(int64_t dest, int64_t i, int64_t id) const { bucketed[dest] = id, new_of_old[i] = (uint32_t)dest; }
+};
 
 __global__ __launch_bounds__(kBlock) void bucket_count_kernel(const int64_t* __restrict__ src, const int64_t* __restrict__ n_src_dev, uint32_t P,
                                                               int pshift, uint32_t* __restrict__ wave_counts) {
-    const int lane = threadIdx.x & 63;
     const int64_t n_src = *n_src_dev;
-    const int64_t n_wt = (n_src + kRouteTile - 1) / kRouteTile;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    for (int64_t wt = wave; wt < n_wt; wt += n_waves) {
-        uint32_t mine = 0; // lane g accumulates the count of owner g
-        for (int j = 0; j < kItems; ++j) {
-            const int64_t i = wt * kRouteTile + j * 64 + lane;
-            const uint32_t o = (i < n_src) ? owner_of((uint64_t)src[i], P, pshift) : 0xFFFFFFFFu;
-            for (uint32_t g = 0; g < P; ++g) {
-                const uint64_t m = __ballot(o == g);
-                if ((uint32_t)lane == g) mine += (uint32_t)__builtin_popcountll(m);
-            }
-        }
-        if ((uint32_t)lane < P) wave_counts[wt * P + lane] = mine;
-    }
+    const int64_t n_wt = partition_tiles(n_src), n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    for (int64_t wt = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); wt < n_wt; wt += n_waves)
+        partition_count_tile(src, n_src, wt, P, pshift, wave_counts);
 }
 
-// one block, one wave per owner column: exclusive scan over the wave tiles with a running carry, bucket sizes and bases
 __global__ __launch_bounds__(1024) void bucket_scan_kernel(uint32_t* __restrict__ wave_counts, const int64_t* __restrict__ n_src_dev, uint32_t P,
                                                            int64_t* __restrict__ counts_out, int64_t* __restrict__ counts_host, int64_t* __restrict__ bases) {
     __shared__ int64_t totals[kMaxParts];
-    const int lane = threadIdx.x & 63;
-    const int64_t n_wt = (*n_src_dev + kRouteTile - 1) / kRouteTile;
-    for (uint32_t g = threadIdx.x >> 6; g < P; g += blockDim.x >> 6) {
-        uint32_t carry = 0;
-        for (int64_t t0 = 0; t0 < n_wt; t0 += 64) {
-            const int64_t t = t0 + lane;
-            const uint32_t c = (t < n_wt) ? wave_counts[t * P + g] : 0u;
-            uint32_t incl = c;
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t v = __shfl_up(incl, off);
-                if (lane >= off) incl += v;
-            }
-            if (t < n_wt) wave_counts[t * P + g] = carry + incl - c;
-            carry += __shfl(incl, 63);
-        }
-        if (lane == 0) totals[g] = (int64_t)carry;
-    }
-    __syncthreads();
+    partition_scan_columns(wave_counts, partition_tiles(*n_src_dev), P, totals);
     if (threadIdx.x == 0) {
         int64_t acc = 0;
         for (uint32_t g = 0; g < P; ++g) {
@@ -1588,32 +1555,10 @@ __global__ __launch_bounds__(1024) void bucket_scan_kernel(uint32_t* __restrict_
 __global__ __launch_bounds__(kBlock) void bucket_scatter_kernel(const int64_t* __restrict__ src, const int64_t* __restrict__ n_src_dev, uint32_t P,
                                                                 int pshift, const uint32_t* __restrict__ wave_offsets, const int64_t* __restrict__ bases,
                                                                 int64_t* __restrict__ bucketed, uint32_t* __restrict__ new_of_old) {
-    const int lane = threadIdx.x & 63;
     const int64_t n_src = *n_src_dev;
-    const int64_t n_wt = (n_src + kRouteTile - 1) / kRouteTile;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    for (int64_t wt = wave; wt < n_wt; wt += n_waves) {
-        int64_t off = 0; // lane g: next free slot of bucket g for this wave tile
-        if ((uint32_t)lane < P) off = bases[lane] + (int64_t)wave_offsets[wt * P + lane];
-        for (int j = 0; j < kItems; ++j) {
-            const int64_t i = wt * kRouteTile + j * 64 + lane;
-            const bool valid = i < n_src;
-            const int64_t id = valid ? src[i] : 0;
-            const uint32_t o = valid ? owner_of((uint64_t)id, P, pshift) : 0xFFFFFFFFu;
-            int64_t dest = -1;
-            for (uint32_t g = 0; g < P; ++g) {
-                const uint64_t m = __ballot(o == g);
-                const int64_t bg = __shfl(off, (int)g);
-                if (o == g) dest = bg + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-                if ((uint32_t)lane == g) off += __builtin_popcountll(m);
-            }
-            if (valid) {
-                bucketed[dest] = id;
-                new_of_old[i] = (uint32_t)dest;
-            }
-        }
-    }
+    const int64_t n_wt = partition_tiles(n_src), n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    for (int64_t wt = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); wt < n_wt; wt += n_waves)
+        partition_scatter_tile(src, n_src, wt, P, pshift, wave_offsets, bases, BucketSink{bucketed, new_of_old});
 }
 
 template <bool FULL>
@@ -1952,7 +1897,7 @@ int plan_call(Plan& p) {
 int grow_workspace(coala_sampler_t* s, hipStream_t st, int n_parts, uint64_t cap, uint64_t max_items, uint64_t max_nbr) {
     int rc;
     const uint64_t table = table_size((int64_t)max_items);
-    const uint64_t wave_tiles = (cap + kRouteTile - 1) / kRouteTile;
+    const uint64_t wave_tiles = (uint64_t)partition_tiles((int64_t)cap);
     if ((rc = grow((void**)&s->nbr_global, &s->nbr_cap, max_nbr ? max_nbr : 1, sizeof(int64_t), st))) return rc;
     if ((rc = grow((void**)&s->slot_of_item, &s->item_cap, max_items ? max_items : 1, sizeof(uint32_t), st))) return rc;
     if (n_parts > 0) {
@@ -2110,11 +2055,11 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
         const uint32_t P = (uint32_t)p.info.n_parts;
         const int pshift = ilog2_exact((uint64_t)P);
         int64_t* bases = s->counts_dev + COALA_SAMPLER_MAX_LAYERS + 1;
-        const dim3 gw(grid1d(((p.items_cap[l] + kRouteTile - 1) / kRouteTile) * 64, kBlock, 4096));
+        const dim3 gw = partition_grid(partition_tiles(p.items_cap[l]));
         hipLaunchKernelGGL(bucket_count_kernel, gw, blk, 0, st, src_out, n_src_dev, P, pshift, s->wave_counts);
-        hipLaunchKernelGGL(bucket_scan_kernel, dim3(1), dim3(64 * (P < 16 ? P : 16)), 0, st, s->wave_counts, n_src_dev, P, p.bucketing->counts,
+        hipLaunchKernelGGL(bucket_scan_kernel, dim3(1), partition_scan_block(P), 0, st, s->wave_counts, n_src_dev, P, p.bucketing->counts,
                            p.pin_dev + kPinParts, bases);
-        hipLaunchKernelGGL(bucket_scatter_kernel, gw, blk, 0, st, src_out, n_src_dev, P, pshift, s->wave_counts, bases,
+        hipLaunchKernelGGL(bucket_scatter_kernel, gw, blk, 0, st, src_out, n_src_dev, P, pshift, (const uint32_t*)s->wave_counts, (const int64_t*)bases,
                            p.bucketing->bucketed_nodes, s->new_of_old);
         const dim3 gb(grid1d(full ? std::max(p.nbr_cap[l], cap_l) : cap_l * f, kBlock, 4096));
         dispatch_bool(full, [&](auto full_c) {

@@ -212,6 +212,68 @@ def test_route_and_scatter_match_oracle(hiplib, oracle, torch_cuda, n, parts):
     table.close()
 
 
+def _route_equals_numpy_partition(torch, cache, idx, parts, strided):
+    """route (packed layout with offsets) and, when asked, split_node_list at max_sample = n (the [parts][n] layout) against numpy's
+    stable partition by idx % parts: counts, offsets, node_out and map_out, and no slot written outside a bucket."""
+    n = len(idx)
+    owner = idx % parts
+    order = np.argsort(owner, kind="stable")
+    counts = np.bincount(owner, minlength=parts)
+    offsets = np.concatenate([[0], np.cumsum(counts)])
+    d_idx = torch.from_numpy(idx).cuda()
+    node = torch.full((n,), -1, dtype=torch.int64, device="cuda")
+    mp = torch.full((n,), -1, dtype=torch.int64, device="cuda")
+    cnt = torch.full((parts,), -1, dtype=torch.int64, device="cuda")
+    offs = torch.full((parts + 1,), -1, dtype=torch.int64, device="cuda")
+    cache.route(d_idx.data_ptr(), n, parts, node.data_ptr(), mp.data_ptr(), cnt.data_ptr(), offs.data_ptr(), 0)
+    assert np.array_equal(cnt.cpu().numpy(), counts) and np.array_equal(offs.cpu().numpy(), offsets)
+    assert np.array_equal(node.cpu().numpy(), idx[order]) and np.array_equal(mp.cpu().numpy(), order)
+    if not strided:
+        return
+    node = torch.full((parts, n), -1, dtype=torch.int64, device="cuda")
+    mp = torch.full((parts, n), -1, dtype=torch.int64, device="cuda")
+    cnt.fill_(-1)
+    cache.split_node_list(d_idx.data_ptr(), n, node.data_ptr(), mp.data_ptr(), cnt.data_ptr(), parts, n)
+    assert np.array_equal(cnt.cpu().numpy(), counts)
+    want_node, want_map = np.full((parts, n), -1, dtype=np.int64), np.full((parts, n), -1, dtype=np.int64)
+    for g in range(parts):
+        want_node[g, : counts[g]] = idx[order[offsets[g]: offsets[g + 1]]]
+        want_map[g, : counts[g]] = order[offsets[g]: offsets[g + 1]]
+    assert np.array_equal(node.cpu().numpy(), want_node) and np.array_equal(mp.cpu().numpy(), want_map)
+
+
+@pytest.fixture(scope="module")
+def route_cache(hiplib, torch_cuda):
+    table = PinnedTable(hiplib, np.zeros((64, 128), dtype=np.float32))
+    cache, _ = _make_cache(hiplib, table, 1)
+    yield cache
+    cache.close()
+    table.close()
+
+
+@pytest.mark.parametrize("parts", [3, 17, 33, 64])
+def test_route_wide_owners_and_wide_ids(torch_cuda, route_cache, parts):
+    """66 wave tiles, the last one partial: the scan carries into a second pass of 64 tiles, and above 16 owners a scan wave takes more
+    than one owner column.  Half of the ids lie below 2^32 and half in [2^32, 2^62): both modulo branches of owner_of at 3, 17 and 33
+    parts, the mask at 64."""
+    n = 64 * 256 + 257
+    rng = np.random.default_rng(parts)
+    low = rng.integers(0, 2**32, size=n // 2, dtype=np.int64)
+    high = rng.integers(2**32, 2**62, size=n - n // 2, dtype=np.int64)
+    if parts == 3:
+        assert all((low % 3 == o).any() and (high % 3 == o).any() for o in range(3))
+    idx = rng.permutation(np.concatenate([low, high]))
+    assert idx.min() >= 0 and (idx < 2**32).any() and (idx >= 2**32).any()
+    _route_equals_numpy_partition(torch_cuda, route_cache, idx, parts, strided=True)
+
+
+def test_route_second_tile_per_wave(torch_cuda, route_cache):
+    """257 ids past 4096 blocks x 4 waves x 256 ids: the grid is at its cap, and the first two waves take a second tile each."""
+    n = 4096 * 1024 + 257
+    idx = np.random.default_rng(5).integers(0, 2**40, size=n, dtype=np.int64)
+    _route_equals_numpy_partition(torch_cuda, route_cache, idx, 5, strided=False)
+
+
 def test_full_size_config2_properties(hiplib, torch_cuda):
     """BASELINE config 2 geometry (4 GiB cache, dim 1024, N = 36,864 rows per minibatch) checked through
     size-independent properties: rows equal the procedural table bit for bit, hits + misses == N, a second pass over the

@@ -238,6 +238,41 @@ def test_sampler_owner_bucketing_many_parts(hiplib, oracle, bucket_graph, G):
     g.close()
 
 
+@pytest.mark.parametrize("G", [3, 64])
+def test_sampler_owner_bucketing_equals_cache_route(hiplib, bucket_graph, G):
+    """The sampler's bucketing and the cache's route run the same per-tile code (coala_partition.h): the bucketed input nodes, the bucket sizes
+    and dst_in_src of a bucket_by_owner=G call equal what a cache handle's route gives for the unbucketed source list of the same
+    call (more than 64 wave tiles)."""
+    import torch
+    from COALA_GNN.sampler import NeighborSampler
+    from _util import PinnedTable
+    P = hiplib
+    ip, _, d_ip, d_ix = bucket_graph
+    plain = NeighborSampler([10, 10], seed=3)
+    buck = NeighborSampler([10, 10], seed=3, bucket_by_owner=G)
+    g = plain.make_graph(d_ip, d_ix)
+    seeds = torch.from_numpy(np.random.default_rng(0).permutation(len(ip) - 1)[:400].astype(np.int64)).cuda()
+    in_p, _, bl_p = plain.sample(g, seeds, step=0)
+    _, _, bl_b = buck.sample(g, seeds, step=0)
+    src, b = bl_p[0].src_nodes.contiguous(), bl_b[0]
+    n = src.numel()
+    assert n > 64 * 256 and torch.equal(src, in_p)
+    table = PinnedTable(P, np.zeros((64, 128), dtype=np.float32))
+    cache = P.Isolated_Cache(P.SSD_GNN_SSD_Controllers(1, 4096, 1024, 0, 0, table.dim, True), None, 0, 1, 1, table.device_ptr, num_rows=table.rows)
+    node = torch.full((n,), -1, dtype=torch.int64, device="cuda")
+    mp = torch.full((n,), -1, dtype=torch.int64, device="cuda")
+    cnt = torch.full((G,), -1, dtype=torch.int64, device="cuda")
+    cache.route(src.data_ptr(), n, G, node.data_ptr(), mp.data_ptr(), cnt.data_ptr())
+    assert b.src_nodes.numel() == n and torch.equal(node[:n], b.src_nodes)
+    assert torch.equal(cnt, b.owner_counts) and cnt.cpu().tolist() == b.owner_counts_host
+    pos = torch.full((n,), -1, dtype=torch.int64, device="cuda")
+    pos[mp] = torch.arange(n, device="cuda")                                        # pos[d] = the p with map_out[p] == d
+    assert b.num_dst > 0 and torch.equal(b.dst_in_src.long(), pos[: b.num_dst])
+    cache.close()
+    table.close()
+    g.close()
+
+
 def test_sampler_owner_bucketing_refuses_65_parts(hiplib, bucket_graph):
     import torch
     from COALA_GNN.sampler import NeighborSampler

@@ -15,7 +15,7 @@ txt = subprocess.run(cmd, capture_output=True, text=True).stderr
 blocks = re.split(r"remark: [^\n]*Function Name: ", txt)[1:]
 names = [b.split()[0] for b in blocks]
 dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
-VG, AG, SG, SC, OC = "VGPRs", "AGPRs", "SGPRs", r"ScratchSize \[bytes/lane\]", r"Occupancy \[waves/SIMD\]"
+VG, AG, SG, SC, OC, LD = "VGPRs", "AGPRs", "SGPRs", r"ScratchSize \[bytes/lane\]", r"Occupancy \[waves/SIMD\]", r"LDS Size \[bytes/block\]"
 for b, d in zip(blocks, dem):
     def g(k):
         m = re.search(k + r": (\d+)", b)
@@ -23,4 +23,4 @@ for b, d in zip(blocks, dem):
     d2 = re.sub(r"\(anonymous namespace\)::", "", d)
     d2 = re.sub(r"^void ", "", re.sub(r"\(.*", "", d2))
     if any(w in d2 for w in want):
-        print(f"{d2:100s} VGPR {g(VG):>3s} AGPR {g(AG):>3s} SGPR {g(SG):>3s} scratch {g(SC):>4s} occupancy {g(OC)}")
+        print(f"{d2:100s} VGPR {g(VG):>3s} AGPR {g(AG):>3s} SGPR {g(SG):>3s} scratch {g(SC):>4s} occupancy {g(OC)} LDS {g(LD):>5s}")
