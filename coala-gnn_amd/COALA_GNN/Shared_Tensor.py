@@ -18,7 +18,7 @@ import torch
 import torch.distributed as dist
 from torch.utils.data import DataLoader, Dataset
 
-from COALA_GNN_Pybind import SharedUVAManager
+from COALA_GNN_Pybind import PinnedRegion, SharedUVAManager, host_register_supported
 
 __all__ = ["NumpyDataset", "MPI_Comm_Manager", "Shared_UVA_Tensor_Manager", "tensor_from_pointer"]
 
@@ -179,14 +179,22 @@ class MemoryOwner:
 
 
 class Shared_UVA_Tensor_Manager(object):
-    """Shared_Tensor.py:118-179.  A POSIX shm region pinned by every local rank; get_tensor() returns the GPU alias."""
+    """Shared_Tensor.py:118-179.  A POSIX shm region pinned by every local rank; get_tensor() returns the GPU alias.
+    On a host without hipHostRegister, a machine's only local rank holds the region in pinned memory of its own instead."""
 
     def __init__(self, comm_manager, path, tensor_size: int):
         self.comm_manager = comm_manager
         # the GPU this rank drives: its local rank (:129), unless the topology object pins another ordinal (several ranks on one GPU)
         dev = int(getattr(comm_manager, "device_index", comm_manager.local_rank))
-        self.memory_handle = SharedUVAManager(path, int(tensor_size), comm_manager.node_id, 0, 0,
-                                              local_rank=comm_manager.local_rank, device=dev, barrier=comm_manager.local_comm.Barrier)
+        if getattr(comm_manager, "local_size", None) == 1 and not host_register_supported(dev):
+            # nobody to share with, and this host cannot pin a mapping the process already has: the same bytes, zero-filled, host and
+            # device pointers alike, in pinned memory of the rank's own.  (Several local ranks do need the segment: they get its error.)
+            self.memory_handle = PinnedRegion(int(tensor_size), dev, zero=True)
+            self.memory_kind = "private"
+        else:
+            self.memory_kind = "shm"     # (`path` names a segment under /dev/shm only for this kind)
+            self.memory_handle = SharedUVAManager(path, int(tensor_size), comm_manager.node_id, 0, 0,
+                                                  local_rank=comm_manager.local_rank, device=dev, barrier=comm_manager.local_comm.Barrier)
         self.tensor_size = int(tensor_size)
         self.device_ptr = self.memory_handle.get_device_ptr()
         self.host_ptr = self.memory_handle.get_host_ptr()

@@ -34,13 +34,11 @@ class PinnedFeatureTable:
     """fp32 [rows, dim] cold tier in pinned host memory mapped into the GPU's address space (zero-copy reads)."""
 
     def __init__(self, num_rows, dim, device=0):
-        from COALA_GNN_Pybind import _capi
-        self._capi = _capi
+        from COALA_GNN_Pybind import PinnedRegion
         self.rows, self.dim, self.device = int(num_rows), int(dim), int(device)
         self.nbytes = self.rows * self.dim * 4
-        hp, dp = C.c_void_p(), C.c_void_p()
-        _capi.check(_capi.load().coala_pinned_alloc(self.nbytes, self.device, C.byref(hp), C.byref(dp)))
-        self.host_ptr, self.device_ptr = hp.value, dp.value
+        self._region = PinnedRegion(self.nbytes, self.device)
+        self.host_ptr, self.device_ptr = self._region.get_host_ptr(), self._region.get_device_ptr()
         buf = (C.c_float * (self.rows * self.dim)).from_address(self.host_ptr)
         self.array = np.frombuffer(buf, dtype=np.float32).reshape(self.rows, self.dim)
         self.cpu_tensor = torch.from_numpy(self.array)
@@ -52,14 +50,8 @@ class PinnedFeatureTable:
         if getattr(self, "host_ptr", 0):
             self.cpu_tensor = None
             self.array = None
-            self._capi.load().coala_pinned_free(self.host_ptr)
+            self._region.cleanup()
             self.host_ptr = 0
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def fill_table(cpu_tensor, seed, device="cuda", chunk_rows=1 << 18, row0=0):

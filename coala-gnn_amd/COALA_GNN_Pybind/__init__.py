@@ -37,7 +37,7 @@ if os.path.realpath(_capi.LIB_PATH) == os.path.realpath(os.path.join(os.path.dir
 
 __all__ = [
     "SharedUVAManager", "SSD_GNN_SSD_Controllers", "SSD_GNN_NVSHMEM_Cache", "Isolated_Cache", "Node_distributor_pybind",
-    "NVSHMEM_Manager", "Graph_Coloring", "current_stream", "set_stream_provider", "native",
+    "NVSHMEM_Manager", "Graph_Coloring", "current_stream", "set_stream_provider", "native", "host_register_supported", "PinnedRegion", "can_pin",
 ]
 
 
@@ -126,6 +126,69 @@ class SharedUVAManager:
             self.cleanup()
         except Exception:
             pass
+
+
+_host_register = {}
+
+
+def host_register_supported(device=0):
+    """Whether this host lets the runtime pin memory the process already has (hipHostRegister) -- what SharedUVAManager needs.
+    Virtual machines that reach the GPU through a proxy may not.  Found by opening and closing one page-sized segment, once per
+    device: coala_shm_open answers COALA_ENOTSUP there; any other failure is raised and not remembered."""
+    device = int(device)
+    if device not in _host_register:
+        h = C.c_void_p()
+        rc = _lib.coala_shm_open(f"/coala_register_probe_{os.getpid()}".encode(), 4096, 1, device, C.byref(h))
+        if rc not in (_capi.OK, _capi.ENOTSUP):
+            check(rc)
+        if rc == _capi.OK:
+            _lib.coala_shm_close(h, 1)
+        _host_register[device] = rc == _capi.OK
+    return _host_register[device]
+
+
+class PinnedRegion:
+    """Pinned host memory of this process alone, mapped into the device's address space (coala_pinned_alloc: hipHostMalloc), with the
+    get_host_ptr / get_device_ptr / cleanup of SharedUVAManager.  zero=True fills it with zeros, like a fresh shm segment: what a
+    machine's only local rank uses in place of the segment where host_register_supported() is False."""
+
+    def __init__(self, size, device=0, zero=False):
+        self.size, self.device = int(size), int(device)
+        hp, dp = C.c_void_p(), C.c_void_p()
+        check(_lib.coala_pinned_alloc(self.size, self.device, C.byref(hp), C.byref(dp)))
+        self._host, self._dev = hp.value, dp.value
+        if zero:
+            C.memset(self._host, 0, self.size)
+
+    def get_host_ptr(self):
+        return int(self._host or 0)
+
+    def get_device_ptr(self):
+        return int(self._dev or 0)
+
+    def cleanup(self):
+        if self._host:
+            host, self._host, self._dev = self._host, None, None
+            _lib.coala_pinned_free(host)
+
+    def __del__(self):
+        try:
+            self.cleanup()
+        except Exception:
+            pass
+
+
+def can_pin(size, device=0):
+    """Whether one process may pin `size` bytes of host memory on this host right now: one allocation of that size, freed at once
+    (untouched pages: no time spent).  Hosts cap pinned memory well below their RAM without saying so anywhere a guest can read
+    (64 GiB per process behind one virtual machine's GPU proxy, with 309 GB of RAM free): asking is the only way to know."""
+    hp, dp = C.c_void_p(), C.c_void_p()
+    rc = _lib.coala_pinned_alloc(int(size), int(device), C.byref(hp), C.byref(dp))
+    if rc == _capi.ENOMEM:
+        return False
+    check(rc)
+    check(_lib.coala_pinned_free(hp))
+    return True
 
 
 # ------------------------------------------------------------------------------------------------------------ geometry

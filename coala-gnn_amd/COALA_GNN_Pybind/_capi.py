@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COALA_HIP_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libcoala_hip.so"))
 
-OK, EINVAL, EHIP, ENOMEM, EIO, EFORMAT, ERANGE, ECOMM = 0, -1, -2, -3, -4, -5, -6, -7
+OK, EINVAL, EHIP, ENOMEM, EIO, EFORMAT, ERANGE, ECOMM, ENOTSUP = 0, -1, -2, -3, -4, -5, -6, -7, -8
 FLAG_SYNC, FLAG_DISTRIBUTED, FLAG_PROFILE, FLAG_COLD_PARTITIONED, FLAG_TAG64 = 1, 2, 4, 8, 16
 WAYS = 32
 COUNTS_RING = 8   # COALA_COUNTS_RING: count exchanges issued ahead that a communicator keeps (include/coala_hip.h)

@@ -129,10 +129,23 @@ int coala_shm_open(const char* name, uint64_t bytes, int is_creator, int device,
         s->host = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, s->fd, 0); // shared_UVA.cuh:83-87
         if (s->host == MAP_FAILED) { s->host = nullptr; rc = fail(COALA_EIO, "mmap failed: %s", strerror(errno)); break; }
         hipError_t e = hipHostRegister(s->host, bytes, hipHostRegisterMapped); // shared_UVA.cuh:89-93
-        if (e != hipSuccess) { rc = fail(COALA_EHIP, "hipHostRegister(%llu bytes) failed: %s", (unsigned long long)bytes, hipGetErrorString(e)); break; }
+        if (e != hipSuccess) {
+            // the runtime also keeps the failure as the thread's last error, where the next kernel launch (ours or torch's) would
+            // find and report it: the failure is reported here, so take it back
+            (void)hipGetLastError();
+            // a fresh page-aligned mapping and a valid flag: "invalid value" can only mean that this host does not pin memory a
+            // process already has (a GPU reached through a virtual machine); anything else (no memory, a locked-memory limit) may pass
+            const bool lacking = e == hipErrorInvalidValue || e == hipErrorNotSupported;
+            rc = fail(lacking ? COALA_ENOTSUP : COALA_EHIP, "hipHostRegister(%llu bytes) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+            break;
+        }
         s->registered = true;
         e = hipHostGetDevicePointer(&s->dev, s->host, 0); // shared_UVA.cuh:94-98
-        if (e != hipSuccess) { rc = fail(COALA_EHIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e)); break; }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail(COALA_EHIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
+            break;
+        }
         // The reference memsets the whole mapping from every rank (shared_UVA.cuh:99); the creator made a fresh object above,
         // which the kernel zero-fills page by page on first touch.
     } while (0);
@@ -164,10 +177,14 @@ int coala_pinned_alloc(uint64_t bytes, int device, void** host_ptr, void** devic
     HIPCHK(hipSetDevice(device));
     void* hp = nullptr;
     hipError_t e = hipHostMalloc(&hp, bytes, hipHostMallocMapped | hipHostMallocPortable);
-    if (e != hipSuccess) return fail(COALA_ENOMEM, "hipHostMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); // reported here, not by the next launch
+        return fail(COALA_ENOMEM, "hipHostMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+    }
     void* dp = nullptr;
     e = hipHostGetDevicePointer(&dp, hp, 0);
     if (e != hipSuccess) {
+        (void)hipGetLastError();
         (void)hipHostFree(hp);
         return fail(COALA_EHIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
     }

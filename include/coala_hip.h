@@ -31,6 +31,7 @@ extern "C" {
 #define COALA_EFORMAT (-5)  /* malformed .npy                                  */
 #define COALA_ERANGE (-6)   /* an index was outside [0, num_rows)              */
 #define COALA_ECOMM (-7)    /* an RCCL call failed                             */
+#define COALA_ENOTSUP (-8)  /* the host lacks the facility (hipHostRegister)   */
 
 #define COALA_WAYS 32u /* COALA_GNN_Modules/ssd_gnn_cache.cuh:61,204 */
 #define COALA_COUNTS_RING 8 /* count exchanges issued ahead (coala_comm_counts_begin) whose tickets stay valid */
@@ -885,6 +886,7 @@ int coala_block_skipgram_loss_backward(int device, const float* h, const int32_t
  * Shared pinned-host ("UVA") region.  Replaces SharedUVAManager (COALA_GNN_Modules/shared_UVA.cuh:26-115):
  * creator shm_open+ftruncate, everybody mmap + hipHostRegister + hipHostGetDevicePointer.  The MPI barrier between
  * create and open (shared_UVA.cuh:76,79) is the caller's job (torch.distributed barrier): is_creator selects the role.
+ * COALA_ENOTSUP (and no segment left behind) on a host whose runtime cannot pin memory the process already has.
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct coala_shm coala_shm_t;
 int coala_shm_open(const char* name, uint64_t bytes, int is_creator, int device, coala_shm_t** out);

@@ -822,7 +822,9 @@ def test_full_size_eight_inproc_ranks(hiplib, oracle, name, dim, num_rows, cache
     batch never exceeds the reference's max_sample (123,904 / 1,081,344 rows), owner counters and whole tag tables equal the
     tag-only oracle fed with the same id lists, a second pass over the same minibatches is (almost) all hits.  configs[4], IGB-large,
     runs in the same distributed form with the node count scaled by 0.5 (8 shards of 25.6 GB = 204.8 GB pinned; the full 409.6 GB
-    table is beyond the host memory a job may hold on the box): max_sample 1,362,944 rows = 5.58 GB of output per rank and step."""
+    table is beyond the host memory a job may hold on the box): max_sample 1,362,944 rows = 5.58 GB of output per rank and step.
+    IGB-large alone first asks the host whether one process may pin 204.8 GB (COALA_GNN_Pybind.can_pin) and skips where it may not: some
+    hosts cap pinned memory far below their RAM (64 GiB per process behind a virtual machine's GPU proxy)."""
     import ctypes as C
     import threading
     import torch
@@ -834,6 +836,9 @@ def test_full_size_eight_inproc_ranks(hiplib, oracle, name, dim, num_rows, cache
     L = _capi.load()
     G, batch = 8, 1024
     max_sample = batch * int(np.prod([f + 1 for f in fanout]))
+    if name.startswith("IGB-large") and not P.can_pin(num_rows * dim * 4):
+        # asked before any work, and of this configuration alone: the other two fail when their allocations do
+        pytest.skip(f"this host does not let one process pin {num_rows * dim * 4 / 1e9:.1f} GB of host memory")
     shards = []
     for r in range(G):
         t = PinnedFeatureTable((num_rows - r + G - 1) // G, dim, 0)

@@ -14,7 +14,14 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def test_shared_uva_two_processes_one_gpu():
+def _needs_host_register(P):
+    """The shared segment is POSIX shm pinned by hipHostRegister: nothing to test on a host whose runtime cannot do that."""
+    if not P.host_register_supported(0):
+        pytest.skip("hipHostRegister is not supported here")
+
+
+def test_shared_uva_two_processes_one_gpu(hiplib):
+    _needs_host_register(hiplib)
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     procs = []
     for r in range(2):
@@ -276,6 +283,7 @@ def test_shm_creator_never_reuses_a_stale_segment(hiplib):
     import ctypes as C
     import mmap
     P = hiplib
+    _needs_host_register(P)
     name = f"/coala_stale_test_{os.getpid()}"
     size = 1 << 20
     fd = os.open("/dev/shm" + name, os.O_CREAT | os.O_RDWR, 0o600)   # the "crashed run": junk left in the segment
@@ -439,3 +447,50 @@ def test_example_training_script_on_a_dataset_directory(tmp_path):
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     assert out.stdout.count("Epoch Time:") == 1 and "GPU hit ratio:" in out.stdout and "final loss" in out.stdout and "Test Acc" in out.stdout
     assert f"Total number of iterations: {int(0.6 * n) // 128 - 1}" in out.stdout
+
+
+def test_pinned_region_stands_in_for_the_segment_of_a_single_local_rank(hiplib, oracle, monkeypatch):
+    """PinnedRegion: zero-filled on request, one set of bytes behind the host and the device pointer, cleanup twice is harmless.  And
+    Shared_UVA_Tensor_Manager on a host that reports no hipHostRegister (here: told so), one local rank: the region is private pinned
+    memory, nothing appears under /dev/shm, and the manager's tensor, host array and writers behave as over the segment."""
+    import ctypes as C
+    import torch
+    import COALA_GNN.Shared_Tensor as ST
+    P = hiplib
+    assert P.host_register_supported(0) is P.host_register_supported(0)      # asked once, then remembered
+    size = (1 << 20) + 4096
+    reg = P.PinnedRegion(size, 0, zero=True)
+    host = np.frombuffer((C.c_ubyte * size).from_address(reg.get_host_ptr()), dtype=np.uint8)
+    assert not host.any()
+    dev = ST.tensor_from_pointer(reg.get_device_ptr(), (size,), np.uint8, "cuda:0")
+    pattern = (np.arange(size) * 7 % 251).astype(np.uint8)
+    host[:] = pattern
+    assert np.array_equal(dev.cpu().numpy(), pattern)                        # the device reads what the host wrote
+    dev.copy_(torch.from_numpy(pattern[::-1].copy()).cuda())
+    torch.cuda.synchronize()
+    assert np.array_equal(host, pattern[::-1])                               # and the host what the device wrote
+    del dev, host
+    reg.cleanup()
+    reg.cleanup()
+    assert reg.get_host_ptr() == 0 and reg.get_device_ptr() == 0
+
+    monkeypatch.setattr(ST, "host_register_supported", lambda device: False)
+
+    class Comm:
+        node_id, local_rank, local_size, device_index = 0, 0, 1, 0
+        local_comm = type("C", (), {"Barrier": staticmethod(lambda: None)})()
+    rows, dim = 3001, 48
+    name = f"/coala_private_region_{os.getpid()}"
+    mgr = ST.Shared_UVA_Tensor_Manager(Comm(), name, rows * dim * 4)
+    assert mgr.memory_kind == "private" and isinstance(mgr.memory_handle, P.PinnedRegion) and not os.path.exists("/dev/shm" + name)
+    uva = mgr.get_tensor(np.float32, "cuda:0", (rows, dim))
+    assert uva.is_cuda and uva.data_ptr() == mgr.device_ptr and not mgr.get_host_array(np.float32, (rows, dim)).any()
+    feat = oracle.make_features(rows, dim, seed=4)
+    mgr.write_np_array(uva, feat)
+    assert np.array_equal(uva.cpu().numpy(), feat)
+    feat2 = oracle.make_features(rows, dim, seed=5)
+    mgr.write_np_array_gpu(uva, feat2, "cuda:0")
+    torch.cuda.synchronize()
+    assert np.array_equal(mgr.get_host_array(np.float32, (rows, dim)), feat2)
+    del uva
+    mgr.cleanup()
