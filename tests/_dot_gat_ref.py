@@ -87,7 +87,8 @@ def csr_rows(rng, n_dst, f, P):
     """Degrees 0..2f, 5 % of the rows at 65..200 edges, row 0 empty (unless it is the only one)."""
     deg = rng.integers(0, 2 * f + 1, size=n_dst)
     if n_dst:
-        deg[rng.random(n_dst) < 0.05] = rng.integers(65, 200)
+        long = rng.random(n_dst) < 0.05
+        deg[long] = rng.integers(65, 200, size=int(long.sum()))       # a degree per long row
     if n_dst > 1:
         deg[0] = 0
     indptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)

@@ -244,7 +244,8 @@ def test_gat_csr_against_float64(hiplib, n_dst, f, H, D, off, big):
     n_src = max(64, min(5000, n_dst // 4))
     deg = rng.integers(0, 2 * f + 1, size=n_dst)
     if n_dst:
-        deg[rng.random(n_dst) < 0.05] = rng.integers(65, 200)
+        long = rng.random(n_dst) < 0.05
+        deg[long] = rng.integers(65, 200, size=int(long.sum()))       # a degree per long row
         deg[0] = 0
     indptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
     indices = rng.integers(0, n_src, size=int(indptr[-1])).astype(np.int32)
