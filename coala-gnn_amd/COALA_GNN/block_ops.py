@@ -652,3 +652,123 @@ def skipgram_loss_torch(h, pos, neg, context_size):
     tables = [t.to(device=h.device, dtype=torch.int64) for t in (pos, neg)]
     _skipgram_bound(h, tables)
     return _skipgram_table_torch(h, tables[0], context_size, -1.0) + _skipgram_table_torch(h, tables[1], context_size, 1.0)
+
+
+# ------------------------------------------------------------------------------------------------------------ typed linear
+GATHER_MM_MAX_TYPES = 64      # coala_typed_mm.hip: kMaxTypes
+GATHER_MM_MAX_WIDTH = 65535 * 64
+
+
+class _GatherMM(torch.autograd.Function):
+    """y[i] = x[rows[i]] @ op(W[types[i]]) on the fp32 matrix units (coala_block_gather_mm*): a plan (three small launches: order,
+    seg) and one product kernel forward; backward, each only when needed, the same kernel on grad_y for grad_x (stored directly with
+    rows None, added with float atomics into zeros otherwise) and one chunked kernel for grad_W (float atomics into zeros).  The plan
+    is saved and reused.  x [N, in] and W contiguous fp32, types / rows contiguous int32 [M] (rows may be None: M == N)."""
+
+    @staticmethod
+    def forward(ctx, x, W, types, rows, transposed):
+        M, T = types.numel(), W.shape[0]
+        K, N = (W.shape[2], W.shape[1]) if transposed else (W.shape[1], W.shape[2])
+        dev, st = x.device.index or 0, current_stream()
+        i32 = dict(dtype=torch.int32, device=x.device)
+        y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+        order, seg = torch.empty(M, **i32), torch.empty(T + 1, **i32)
+        if M:
+            work = torch.empty(_lib.coala_block_gather_mm_plan_work(M, T), **i32)
+            _capi.check(_lib.coala_block_gather_mm_plan(dev, types.data_ptr(), _ptr(rows), M, T, order.data_ptr(), seg.data_ptr(), work.data_ptr(), st))
+            _capi.check(_lib.coala_block_gather_mm(dev, x.data_ptr(), W.data_ptr(), order.data_ptr(), seg.data_ptr(), _ptr(rows), None, y.data_ptr(),
+                                                   M, T, K, N, int(transposed), st))
+        ctx.save_for_backward(x, W, order, seg, rows)
+        ctx.transposed = transposed
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, W, order, seg, rows = ctx.saved_tensors
+        M, T, tr = order.numel(), W.shape[0], ctx.transposed
+        K, N = (W.shape[2], W.shape[1]) if tr else (W.shape[1], W.shape[2])
+        dev, st = x.device.index or 0, current_stream()
+        g = grad_y.contiguous()
+        grad_x = grad_w = None
+        if ctx.needs_input_grad[0]:
+            grad_x = torch.empty_like(x) if rows is None and M else torch.zeros_like(x)
+            _capi.check(_lib.coala_block_gather_mm(dev, g.data_ptr(), W.data_ptr(), order.data_ptr(), seg.data_ptr(), None, _ptr(rows),
+                                                   grad_x.data_ptr(), M, T, N, K, int(not tr), st))
+        if ctx.needs_input_grad[1]:
+            grad_w = torch.zeros_like(W)
+            (p, p_rows, pk), (q, q_rows, qn) = ((g, None, N), (x, rows, K)) if tr else ((x, rows, K), (g, None, N))
+            _capi.check(_lib.coala_block_gather_mm_backward_w(dev, p.data_ptr(), _ptr(p_rows), q.data_ptr(), _ptr(q_rows), order.data_ptr(),
+                                                              seg.data_ptr(), grad_w.data_ptr(), M, T, pk, qn, st))
+        return grad_x, grad_w, None, None, None
+
+
+def _gather_mm_args(x, W, types, rows):
+    """The checks of gather_mm / gather_mm_torch."""
+    if x.dim() != 2 or W.dim() != 3:
+        raise ValueError(f"x of shape {tuple(x.shape)}, W of shape {tuple(W.shape)}: gather_mm takes x [N, in] and W [T, ., .]")
+    for name, t in (("types", types), ("rows", rows)):
+        if t is None and name == "rows":
+            continue
+        if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError(f"{name} must be an integer tensor")
+        if t.dim() != 1 or t.shape != types.shape:
+            raise ValueError(f"{name} of shape {tuple(t.shape)}: one value per output row, [M]")
+    if rows is None and types.shape[0] != x.shape[0]:
+        raise ValueError(f"{types.shape[0]} types for the {x.shape[0]} rows of x: without rows, one type per row of x")
+
+
+def _rows_bound(x, rows):
+    """IndexError when a row index is >= N (one host read)."""
+    if rows is not None and rows.numel():
+        top = int(rows.max())
+        if top >= x.shape[0]:
+            raise IndexError(f"a row index is {top}: x has {x.shape[0]} rows")
+
+
+def gather_mm(x, W, types, rows=None, transposed=False, validate=True):
+    """The typed linear step, DGL's gather_mm / segment_mm (dgl.nn.TypedLinear's product) as one operation: -> y [M, out],
+        y[i] = x[rows[i]] @ W[types[i]]       (rows=None: x[i];  transposed=True: W is [T, out, in] and W[types[i]].T is applied)
+    x [N, in]; W [T, in, out]; types an integer tensor [M] in any order; rows an integer tensor [M] or None.  A row whose type lies
+    outside [0, T) or whose rows[i] < 0 gives y[i] == 0 exactly and takes no gradient; rows[i] >= N raises IndexError (on the native
+    path one host read per call, which validate=False skips for a caller whose rows address x by construction).  Native kernels
+    (coala_typed_mm.hip: rows grouped by type on the device, one launch for all types on the fp32 matrix instructions, no sorted copy
+    of x, no host read of its own) for fp32 x and W on the GPU, index tensors on the GPU, 1 <= T <= 64, in, out >= 1 and M, N < 2^31;
+    gather_mm_torch otherwise.  The forward is bitwise reproducible and a row's bits do not depend on the other rows; grad_x with rows
+    and grad_W are added with float atomics and are not.  grad_x and grad_W are each computed only when needed."""
+    _gather_mm_args(x, W, types, rows)
+    T, (d_in, d_out) = W.shape[0], ((W.shape[2], W.shape[1]) if transposed else (W.shape[1], W.shape[2]))
+    native = (x.is_cuda and all(t is None or t.device == x.device for t in (W, types, rows)) and x.dtype == torch.float32
+              and W.dtype == torch.float32 and 1 <= T <= GATHER_MM_MAX_TYPES and 1 <= d_in <= GATHER_MM_MAX_WIDTH
+              and 1 <= d_out <= GATHER_MM_MAX_WIDTH and x.shape[1] == d_in and types.numel() < (1 << 31) and x.shape[0] < (1 << 31))
+    if not native:
+        return gather_mm_torch(x, W, types, rows, transposed, validate)
+    if validate:
+        _rows_bound(x, rows)
+    t32 = types if types.dtype == torch.int32 else types.clamp(-1, T).to(torch.int32)
+    r32 = rows if rows is None or rows.dtype == torch.int32 else rows.clamp(-1, (1 << 31) - 1).to(torch.int32)
+    return _GatherMM.apply(x.contiguous(), W.contiguous(), t32.contiguous(), None if r32 is None else r32.contiguous(), bool(transposed))
+
+
+def gather_mm_torch(x, W, types, rows=None, transposed=False, validate=True):
+    """gather_mm in plain torch, any device and dtype, the same rules: a stable sort of the rows by type, one GEMM per type on its
+    slice, the inverse permutation (one host read: the rows per type).  The fallback of gather_mm, and its reference."""
+    _gather_mm_args(x, W, types, rows)
+    T = W.shape[0]
+    t = types.to(device=x.device, dtype=torch.int64)
+    r = None if rows is None else rows.to(device=x.device, dtype=torch.int64)
+    _rows_bound(x, r)
+    Wm = W.transpose(1, 2) if transposed else W
+    sends = (t >= 0) & (t < T) if r is None else (t >= 0) & (t < T) & (r >= 0)
+    t = torch.where(sends, t, T)
+    order = torch.argsort(t, stable=True)
+    counts = torch.bincount(t, minlength=T + 1).tolist()                 # the host read
+    parts, off = [], 0
+    for ty, c in enumerate(counts[:T]):
+        if c:
+            idx = order[off:off + c]
+            parts.append(x[idx if r is None else r[idx]] @ Wm[ty])
+            off += c
+    parts.append(x.new_zeros((counts[T], Wm.shape[2])))                  # the rows that send nothing
+    back = torch.empty_like(order)
+    back[order] = torch.arange(order.numel(), device=order.device)
+    return torch.cat(parts)[back]

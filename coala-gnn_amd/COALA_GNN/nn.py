@@ -19,7 +19,9 @@ WeightedSAGEConv is the layer of DGL's PinSAGE example on blocks sampled by rand
 in block.edata['weights'] weigh the neighbours' rows through Block.weighted_sum_aggregate."""
 import torch
 
-__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv", "DotPredictor"]
+from .block_ops import gather_mm
+
+__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv", "TypedLinear", "DotPredictor"]
 
 
 class GATConv(torch.nn.Module):
@@ -624,6 +626,29 @@ def _typed_linear(x, W, types, counts):
     back = torch.empty_like(order)
     back[order] = torch.arange(order.numel(), device=order.device)
     return ys[back]
+
+
+class TypedLinear(torch.nn.Module):
+    """Linear layer with one weight matrix per type, DGL 1.x dgl.nn.TypedLinear without its regularizers: y[i] = x[i] @ W[x_type[i]],
+    W [num_types, in_size, out_size], initialised as DGL does (uniform in +-1/sqrt(in_size)).  forward(x, x_type, sorted_by_type=False)
+    runs on block_ops.gather_mm, which groups the rows by type on the device whatever their order: the flag is accepted and ignored.  A
+    row whose type lies outside [0, num_types) gives a zero row.  regularizer / num_bases are not provided."""
+
+    def __init__(self, in_size, out_size, num_types, regularizer=None, num_bases=None):
+        super().__init__()
+        if regularizer is not None or num_bases is not None:
+            raise ValueError("TypedLinear: regularizer and num_bases are not provided")
+        self.in_size, self.out_size, self.num_types = in_size, out_size, num_types
+        self.W = torch.nn.Parameter(torch.empty(num_types, in_size, out_size))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            bound = 1.0 / self.in_size ** 0.5
+            self.W.uniform_(-bound, bound)
+
+    def forward(self, x, x_type, sorted_by_type=False):
+        return gather_mm(x, self.W, x_type)
 
 
 class HGTConv(torch.nn.Module):

@@ -190,6 +190,10 @@ SYMBOLS = {
     "coala_sampler_walk_batch_wait": (_I, [_VP, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
     "coala_block_skipgram_loss": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _I, C.c_float, _VP]),
     "coala_block_skipgram_loss_backward": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _I, C.c_float, _VP]),
+    "coala_block_gather_mm_plan_work": (_I64, [_I64, _I]),
+    "coala_block_gather_mm_plan": (_I, [_I, _VP, _VP, _I64, _I, _VP, _VP, _VP, _VP]),
+    "coala_block_gather_mm": (_I, [_I] + [_VP] * 7 + [_I64, _I, _I, _I, _I, _VP]),
+    "coala_block_gather_mm_backward_w": (_I, [_I] + [_VP] * 7 + [_I64, _I, _I, _I, _VP]),
     "coala_shm_open":(_I, [C.c_char_p, _U64, _I, _I, C.POINTER(_VP)]),
     "coala_shm_host_ptr": (_VP, [_VP]),
     "coala_shm_device_ptr": (_VP, [_VP]),

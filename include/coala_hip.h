@@ -881,6 +881,34 @@ int coala_block_skipgram_loss(int device, const float* h, const int32_t* rows, f
                               int context, int dim, float sign, void* stream);
 int coala_block_skipgram_loss_backward(int device, const float* h, const int32_t* rows, double* grad_acc, const double* scale, int64_t n_rows,
                                        int len, int context, int dim, float sign, void* stream);
+/* Typed linear on the fp32 matrix units (DGL's gather_mm / segment_mm, dgl.nn.TypedLinear): C[i] = A[g(i)] @ op(W[types[i]]) for a
+ * list of M rows, 1 <= T <= 64 types, fp32 throughout, any 4-byte aligned pointers (16-byte loads are used only where both operands
+ * allow them).  COALA_EINVAL ("bad typed product shape") for T outside 1..64, K or N < 1 or > 65535 * 64, M < 0 or >= 2^31; M == 0
+ * launches nothing; "null buffer" as for the other block ops.  Indices are not range-checked here (the caller's duty).
+ *   plan: types int32 [M] in any order, rows int32 [M] or NULL -> order int32 [M], the list positions grouped by type and in list
+ *     order inside a type, and seg int32 [T + 1], the groups' offsets.  An entry whose type is outside [0, T) or whose rows[i] < 0
+ *     sends nothing: it lies behind seg[T].  Ballot ranks and prefix sums, no atomics: the same order on every run.  work: int32
+ *     scratch of coala_block_gather_mm_plan_work(M, T) = ceil(M / 256) * (T + 1) elements.  Three launches, no host read.
+ *   product: a [., K], w [T, K, N] (transposed != 0: [T, N, K], applied as its transpose), c [., N].  For list position m of type t,
+ *     c[c_rows ? c_rows[m] : m] = a[a_rows ? a_rows[m] : m] @ op(w[t]).  With c_rows NULL every c[m] is stored, exact zeros for an
+ *     entry that sends nothing (c need not be initialised).  With c_rows the products are ADDED with hardware float atomics into c,
+ *     which the caller zeroes, and an entry that sends nothing adds nothing (several entries may name one row; the order varies).
+ *     The forward is (a = x, a_rows = rows, c_rows = NULL); grad_x is (a = grad_y, w with `transposed` flipped, K and N swapped,
+ *     a_rows = NULL, c_rows = rows).  One block per (type, 64 gathered rows, 128 columns), launched for the host-known bound
+ *     M / 64 + T + 1 row tiles; v_mfma_f32_32x32x2_f32, accumulators in registers over the whole K loop.  One output element is one
+ *     chain of fused multiply-adds over k = 0, 1, ... in that order: the direct-store form is bitwise reproducible, and an element's
+ *     bits do not depend on which other rows share its tile, on the list's order or on the other entries' types.
+ *   backward_w: grad_w[t][k][n] += sum over the entries m of type t of p[p_rows ? p_rows[m] : m][k] * q[q_rows ? q_rows[m] : m][n],
+ *     p [., K], q [., N], grad_w [T, K, N] zeroed by the caller.  (w [T, in, out]: p = x through rows, q = grad_y; w [T, out, in]:
+ *     p = grad_y, q = x through rows.)  A type's entries are cut into chunks of 2048, one block per (type, chunk, 64 x 128 tile),
+ *     added with hardware float atomics: NOT bitwise reproducible.  A type without entries keeps its zeros. */
+int64_t coala_block_gather_mm_plan_work(int64_t M, int T);
+int coala_block_gather_mm_plan(int device, const int32_t* types, const int32_t* rows, int64_t M, int T, int32_t* order, int32_t* seg,
+                               int32_t* work, void* stream);
+int coala_block_gather_mm(int device, const float* a, const float* w, const int32_t* order, const int32_t* seg, const int32_t* a_rows,
+                          const int32_t* c_rows, float* c, int64_t M, int T, int K, int N, int transposed, void* stream);
+int coala_block_gather_mm_backward_w(int device, const float* p, const int32_t* p_rows, const float* q, const int32_t* q_rows,
+                                     const int32_t* order, const int32_t* seg, float* grad_w, int64_t M, int T, int K, int N, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Shared pinned-host ("UVA") region.  Replaces SharedUVAManager (COALA_GNN_Modules/shared_UVA.cuh:26-115):
