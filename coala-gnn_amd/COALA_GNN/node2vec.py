@@ -10,19 +10,24 @@ Written from the papers and the public behaviour of PyG's class, not copied from
   * walk_length counts HOPS: a walk holds walk_length + 1 nodes (PyG subtracts one from its argument and counts nodes);
   * the loss uses softplus where PyG adds 1e-15 inside the logarithm (block_ops.skipgram_loss);
   * the walks follow in-edges, as every sampler here: on a symmetric graph that is the usual walk;
-  * one GPU, walks of at most 127 hops, no metapaths, no edge weights."""
+  * one GPU, walks of at most 127 hops, no edge weights.
+
+MetaPath2Vec (Dong et al., "metapath2vec: Scalable Representation Learning for Heterogeneous Networks", KDD 2017; PyG's MetaPath2Vec) is
+Node2Vec with a metapath at p = q = 1: on a typed graph sorted by edge type, hop h follows an in-edge of type metapath[h % M].  The
+negatives are drawn from all nodes whatever their type, the original metapath2vec (not metapath2vec++), and one embedding table holds
+every node type."""
 import torch
 
 from . import block_ops
 from .embedding import NodeEmbedding
-from .sampler import MAX_WALK_LENGTH, MAX_WALK_NEGATIVES, _as_graph, node2vec_thresholds, walk_batch
+from .sampler import MAX_WALK_LENGTH, MAX_WALK_NEGATIVES, _as_graph, _check_metapath, node2vec_thresholds, walk_batch
 
-__all__ = ["Node2Vec"]
+__all__ = ["Node2Vec", "MetaPath2Vec"]
 
 
 class Node2Vec(object):
     """Node2Vec(g, embedding_dim, walk_length, context_size, walks_per_node=1, p=1.0, q=1.0, num_negative_samples=1, cache_mb=64,
-             device='cuda', seed=0, backend='native' | 'torch')
+             device='cuda', seed=0, backend='native' | 'torch', metapath=None, etype='etype')
 
     g: a CSCGraph (or an (indptr, indices) pair of device tensors); with q != 1 its rows must be sorted by source id
     (sampler.sort_csc_by_src; synthetic.symmetrize_csc produces that order).  The model owns self.embedding, a NodeEmbedding of
@@ -35,10 +40,13 @@ class Node2Vec(object):
         z = model()                      # every row, untracked
 
     The walks of a batch are a function of (seed, the batch's number in the epoch order, start node, walk): with the same seed, two
-    runs see the same batches."""
+    runs see the same batches.
+
+    metapath: first-order typed walks (p = q = 1 only; sampler.walk_batch(metapath=)): g.edata[etype] holds the edge types and the rows
+    are sorted by type.  The walks follow IN-edges: name the in-edge types of the path."""
 
     def __init__(self, g, embedding_dim, walk_length, context_size, walks_per_node=1, p=1.0, q=1.0, num_negative_samples=1, cache_mb=64,
-                 device="cuda", seed=0, backend="native"):
+                 device="cuda", seed=0, backend="native", metapath=None, etype="etype"):
         for name, x, lo, hi in (("embedding_dim", embedding_dim, 1, 1 << 20), ("walk_length", walk_length, 1, MAX_WALK_LENGTH),
                                 ("walks_per_node", walks_per_node, 1, 64), ("num_negative_samples", num_negative_samples, 0, MAX_WALK_NEGATIVES)):
             if isinstance(x, bool) or not isinstance(x, int) or not lo <= x <= hi:
@@ -46,6 +54,9 @@ class Node2Vec(object):
         if isinstance(context_size, bool) or not isinstance(context_size, int) or not 2 <= context_size <= walk_length + 1:
             raise ValueError(f"context_size {context_size!r}: 2..walk_length + 1 = {walk_length + 1} (a walk holds walk_length + 1 nodes)")
         node2vec_thresholds(p, q)
+        self.metapath, self.etype = None if metapath is None else _check_metapath(metapath, q=q), etype
+        if metapath is not None and float(p) != 1.0:
+            raise ValueError(f"metapath= with p={p!r}: a metapath walk is first-order, p = q = 1")
         self.graph = _as_graph(g)
         self.embedding_dim, self.walk_length, self.context_size = embedding_dim, walk_length, context_size
         self.walks_per_node, self.p, self.q, self.num_negative_samples = walks_per_node, float(p), float(q), num_negative_samples
@@ -58,7 +69,7 @@ class Node2Vec(object):
         if step is None:
             step, self.step = self.step, self.step + 1
         return walk_batch(self.graph, nodes, self.p, self.q, self.walk_length, self.walks_per_node, self.num_negative_samples, seed=self.seed,
-                          step=step)
+                          step=step, metapath=self.metapath, etype=self.etype)
 
     def loader(self, batch_size, shuffle=True):
         """One epoch: a generator of WalkBatch objects over all nodes, batch_size start nodes each, in an order shuffled by (seed, the
@@ -91,3 +102,14 @@ class Node2Vec(object):
 
     def close(self):
         self.embedding.close()
+
+
+class MetaPath2Vec(Node2Vec):
+    """MetaPath2Vec(g, embedding_dim, metapath, walk_length, context_size, walks_per_node=1, num_negative_samples=1, etype='etype', ...):
+    Node2Vec with a metapath and p = q = 1, where PyG's MetaPath2Vec stands on a homogenised graph."""
+
+    def __init__(self, g, embedding_dim, metapath, walk_length, context_size, walks_per_node=1, num_negative_samples=1, etype="etype", **kw):
+        if metapath is None:
+            raise ValueError("MetaPath2Vec needs a metapath; Node2Vec is the untyped model")
+        super().__init__(g, embedding_dim, walk_length, context_size, walks_per_node, 1.0, 1.0, num_negative_samples, metapath=metapath,
+                         etype=etype, **kw)

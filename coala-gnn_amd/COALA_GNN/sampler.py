@@ -14,7 +14,7 @@ from COALA_GNN_Pybind import _capi, current_stream
 from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
                         _MeanAggregateCSR, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _WeightedSum, _WeightedSumCSR)
 
-__all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "RandomWalkNeighborSampler", "random_walk", "sort_csc_by_etype",
+__all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "RandomWalkNeighborSampler", "PinSAGESampler", "random_walk", "sort_csc_by_etype",
            "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT", "EID", "EdgePredictionSampler", "as_edge_prediction_sampler",
            "UniformNegativeSampler", "EdgeBatch", "edge_batch", "edge_batch_wait", "reverse_edge_ids", "MAX_NEGATIVES",
            "TemporalNeighborSampler", "TemporalEdgePredictionSampler", "sort_csc_by_time", "check_time_sorted", "pair_code_bits",
@@ -116,7 +116,7 @@ class CSCGraph(object):
         self.device = self.indptr.device
         self.ndata = dict(ndata or {})
         self.edata = dict(edata or {})
-        self._weights, self._etypes, self._etimes = {}, {}, {}   # edata key -> (the entry, its version, num_rels or None, the validated device copy): _edata
+        self._weights, self._etypes, self._etimes, self._walk_types = {}, {}, {}, {}   # edata key -> (the entry, its version, num_rels or None, the validated device copy): _edata
         self._max_in_degree = None
         self._src_sorted = None   # require_src_sorted: None = not checked yet, True = sorted, a ValueError = the refusal, kept
         self._h = C.c_void_p()
@@ -179,6 +179,21 @@ class CSCGraph(object):
             return t.to(device=self.device, dtype=torch.int32).contiguous()
         return self._edata(self._etypes, key, "types of RelNeighborSampler(etype", make, num_rels)
 
+    def walk_types(self, key):
+        """edata[key] for the metapath walks -> (a contiguous int32 tensor on the graph's device, num_rels = the largest type + 1), checked
+        once on the device (check_etype_sorted: num_edges non-negative integers, non-decreasing inside every row) and cached until the
+        entry is replaced or modified in place, or close().  ValueError when the key is missing or the types are bad."""
+        if key not in self.edata:
+            raise ValueError(f"edata has no {key!r}: a metapath walk reads the edge types there (etype={key!r}; keys: {sorted(self.edata)})")
+
+        def make(t):
+            num_rels = int(t.max().item()) + 1 if _is_int_tensor(t) and t.numel() else 1
+            check_etype_sorted(self.indptr, t, max(num_rels, 1), key)
+            if num_rels > 0x7FFFFFFF:
+                raise ValueError(f"edata[{key!r}]: edge types must fit an int32")
+            return t.to(device=self.device, dtype=torch.int32).contiguous(), num_rels
+        return self._edata(self._walk_types, key, "types of a metapath walk(etype", make)
+
     def edge_times(self, key):
         """edata[key] as a contiguous int64 tensor on the graph's device for TemporalNeighborSampler, checked once on the device
         (check_time_sorted: an integer tensor of num_edges values, non-decreasing inside every row) and cached until the entry is
@@ -190,6 +205,7 @@ class CSCGraph(object):
 
     def close(self):
         self._etypes = {}
+        self._walk_types = {}
         self._etimes = {}
         if getattr(self, "_h", None):
             _lib.coala_sampler_destroy(self._h)
@@ -1047,6 +1063,34 @@ def _walk_threshold(prob, name):
     return int(float(prob) * 9007199254740992.0)
 
 
+MAX_METAPATH = 16   # edge types of a metapath (coala_sampler.hip: kMaxMetapath)
+
+
+def _check_metapath(metapath, prob=None, q=1.0):
+    """A metapath as a list of 1..16 non-negative ints; what a typed walk cannot be combined with.  ValueError otherwise."""
+    if prob is not None:
+        raise ValueError("metapath= with prob= (weighted typed walks) is not supported")
+    if float(q) != 1.0:
+        raise ValueError(f"metapath= with q={q!r}: a metapath walk is first-order, p = q = 1")
+    mp = list(metapath) if hasattr(metapath, "__iter__") and not isinstance(metapath, (str, bytes)) else None
+    if mp is None or not 1 <= len(mp) <= MAX_METAPATH:
+        raise ValueError(f"metapath {metapath!r}: a sequence of 1..{MAX_METAPATH} edge types")
+    for r in mp:
+        if isinstance(r, bool) or not isinstance(r, int) or r < 0:
+            raise ValueError(f"metapath {metapath!r}: every edge type is a non-negative int")
+    return mp
+
+
+def _metapath_args(g, mp, etype):
+    """The typed entry points' arguments between the untyped ones and the outputs: (etype pointer, num_rels, metapath, M).  The
+    graph's types are checked once per CSCGraph (CSCGraph.walk_types); ValueError before any launch."""
+    types, num_rels = g.walk_types(etype)
+    for r in mp:
+        if r >= num_rels:
+            raise ValueError(f"metapath {mp}: edge type {r} outside [0, {num_rels}), the types of edata[{etype!r}]")
+    return types.data_ptr(), num_rels, (C.c_int32 * len(mp))(*mp), len(mp)
+
+
 class RandomWalkNeighborSampler(NeighborSampler):
     """Importance-based neighbour sampling by random walks, DGL's dgl.sampling.RandomWalkNeighborSampler / PinSAGESampler on a homogeneous
     graph (Ying et al., "Graph Convolutional Neural Networks for Web-Scale Recommender Systems", KDD 2018), in place of NeighborSampler:
@@ -1060,10 +1104,18 @@ class RandomWalkNeighborSampler(NeighborSampler):
     Every block is fixed-stride (Block.nbr [num_dst, k], -1 padded).  block.edata[weight_column] is fp32 [num_dst, k], the visit count
     of every slot (0 on padding), made on first access from the int32 counts the kernel wrote (block.edata['visit_counts']): what
     Block.weighted_sum_aggregate and SAGEConv / GraphConv (edge_weight=) take.  A chosen neighbour is a node the walks reached, not an edge of the graph: there are no
-    edge ids, and prob= is not supported."""
+    edge ids, and prob= is not supported.
+
+    metapath: a sequence of 1..16 edge types, for a typed graph whose in-edges are sorted by type (sort_csc_by_etype) with the types in
+    graph.edata[etype]; checked once per graph, ValueError before any launch otherwise.  Hop h of a walk then draws among the in-edges of
+    type metapath[h % M] of the node it stands on (none: the walk ends); num_traversals counts repetitions of the metapath, DGL's
+    meaning, so a walk makes M * num_traversals <= 16 hops, may terminate where a repetition starts, and only the hops that complete a
+    repetition -- nodes of the start type -- are visits.  A walk follows IN-edges: for item <- user <- item name the in-edge types
+    (the type of the edges that point at an item first).  On a graph of one relation, metapath=[0] gives the untyped blocks bit for bit."""
 
     def __init__(self, num_neighbors, num_traversals, termination_prob, num_random_walks, seed=0, bucket_by_owner=0, weight_column="weights",
-                 prob=None, edge_ids=False):
+                 prob=None, edge_ids=False, metapath=None, etype="etype"):
+        self.metapath, self.etype = None if metapath is None else _check_metapath(metapath, prob), etype
         if prob is not None:
             raise ValueError("RandomWalkNeighborSampler: prob= (weighted walks) is not supported")
         if edge_ids:
@@ -1077,6 +1129,8 @@ class RandomWalkNeighborSampler(NeighborSampler):
                 raise ValueError(f"{name} {x!r}: 1..{hi}")
         if num_traversals * num_random_walks > 512:
             raise ValueError(f"num_random_walks * num_traversals = {num_traversals * num_random_walks}: at most 512 visits per node")
+        if self.metapath is not None and len(self.metapath) * num_traversals > 16:
+            raise ValueError(f"{num_traversals} traversals of a metapath of {len(self.metapath)} edge types: at most 16 hops per walk")
         self.term_threshold = _walk_threshold(termination_prob, "termination_prob")
         super().__init__(ks, seed=seed, bucket_by_owner=bucket_by_owner)
         self.num_neighbors = list(self.fanouts)
@@ -1087,6 +1141,9 @@ class RandomWalkNeighborSampler(NeighborSampler):
         p.extra = [torch.empty_like(t) for t in p.nbr]   # int32 [edge_cap] per layer: the visit count of every neighbour slot
         cnt_p = (C.c_void_p * len(p.extra))(*[t.data_ptr() for t in p.extra])
         walk = _capi.SamplerWalk(self.num_traversals, self.num_random_walks, self.term_threshold)
+        if self.metapath is not None:   # raises before any launch
+            return (_lib.coala_sampler_sample_layers_walk_metapath, (fan, len(p.rev)),
+                    (C.byref(walk), *_metapath_args(p.graph, self.metapath, self.etype), cnt_p))
         return _lib.coala_sampler_sample_layers_walk, (fan, len(p.rev)), (C.byref(walk), cnt_p)
 
     def sample_end(self, pending):
@@ -1098,14 +1155,35 @@ class RandomWalkNeighborSampler(NeighborSampler):
         return input_nodes, seeds, blocks
 
 
-def random_walk(g, nodes, length, restart_prob=0.0, num_walks=1, seed=0, step=0):
+class PinSAGESampler(RandomWalkNeighborSampler):
+    """DGL's dgl.sampling.PinSAGESampler(g, ntype, other_type, ...) on a homogenised bipartite graph: RandomWalkNeighborSampler with a
+    metapath of at least two edge types, item <- other <- item as in-edge types -- with synthetic.bipartite_csc, [0, 1] from an item."""
+
+    def __init__(self, num_neighbors, num_traversals, termination_prob, num_random_walks, metapath, etype="etype", seed=0, bucket_by_owner=0,
+                 weight_column="weights"):
+        if len(_check_metapath(metapath)) < 2:
+            raise ValueError(f"PinSAGESampler: metapath {metapath!r} needs at least two edge types (item <- other <- item); "
+                             f"RandomWalkNeighborSampler takes any")
+        super().__init__(num_neighbors, num_traversals, termination_prob, num_random_walks, seed=seed, bucket_by_owner=bucket_by_owner,
+                         weight_column=weight_column, metapath=metapath, etype=etype)
+
+
+def random_walk(g, nodes, length=None, restart_prob=0.0, num_walks=1, seed=0, step=0, metapath=None, etype="etype"):
     """Random walks over a CSCGraph, DGL's dgl.sampling.random_walk on a homogeneous graph: -> int64 [n, num_walks, length + 1] on the
     graph's device.  [i, w, 0] is nodes[i], then the nodes walk w visits; a hop after the first ends the walk with probability
     restart_prob, a node without an in-edge ends it, and -1 fills the rest.  An out-of-range start node gives a row of -1.  A walk
     follows in-edges (DGL's walk on a symmetric graph).  length 1..16, num_walks 1..64.
     Unlike DGL's, the walks are a function of (seed, step, start node, w) -- they are walk w of that node in the first sampled layer of
     RandomWalkNeighborSampler(num_traversals=length, termination_prob=restart_prob, seed=seed) at that step -- so a start node given
-    twice gets the same traces twice: ask for num_walks independent walks from one node instead of repeating it."""
+    twice gets the same traces twice: ask for num_walks independent walks from one node instead of repeating it.
+    metapath (DGL's random_walk(metapath=)): a sequence of M edge types on a typed graph sorted by type, as RandomWalkNeighborSampler's;
+    hop h follows an in-edge of type metapath[h % M], length defaults to M and must be a multiple of it, and a walk may end with
+    restart_prob only where a repetition of the metapath starts.  Name the IN-edge types of the path you mean."""
+    mp = None if metapath is None else _check_metapath(metapath)
+    if mp is not None:
+        length = len(mp) if length is None else length
+        if isinstance(length, int) and length % len(mp) != 0:
+            raise ValueError(f"length {length!r}: a multiple of the metapath's {len(mp)} edge types")
     for name, x, hi in (("length", length, 16), ("num_walks", num_walks, 64)):
         if isinstance(x, bool) or not isinstance(x, int) or not 1 <= x <= hi:
             raise ValueError(f"{name} {x!r}: 1..{hi}")
@@ -1113,8 +1191,11 @@ def random_walk(g, nodes, length, restart_prob=0.0, num_walks=1, seed=0, step=0)
     g = _as_graph(g)
     nodes = nodes.to(g.device, dtype=torch.int64).contiguous()
     out = torch.empty((nodes.numel(), num_walks, length + 1), dtype=torch.int64, device=g.device)
-    _capi.check(_lib.coala_sampler_random_walk(g._h, nodes.data_ptr(), nodes.numel(), num_walks, length, thr, _u64(seed), _u64(step), 0,
-                                               out.data_ptr(), current_stream()))
+    args = (g._h, nodes.data_ptr(), nodes.numel(), num_walks, length, thr, _u64(seed), _u64(step), 0)
+    if mp is not None:
+        _capi.check(_lib.coala_sampler_random_walk_metapath(*args, *_metapath_args(g, mp, etype), out.data_ptr(), current_stream()))
+    else:
+        _capi.check(_lib.coala_sampler_random_walk(*args, out.data_ptr(), current_stream()))
     return out
 
 
@@ -1223,10 +1304,16 @@ class WalkBatch(object):
         return [t for t in (self.nodes, self.input_nodes, self.pos, self.neg, self.traces) if t is not None]
 
 
-def walk_batch_begin(g, nodes, p, q, walk_length, num_walks=1, num_neg=1, seed=0, step=0, traces=False):
+def walk_batch_begin(g, nodes, p, q, walk_length, num_walks=1, num_neg=1, seed=0, step=0, traces=False, metapath=None, etype="etype"):
     """Enqueue the walk-batch kernels for the start nodes on the current stream, without waiting: -> the pending call walk_batch_end
     takes.  ValueError before any launch for arguments node2vec_random_walk refuses, num_neg outside 0..16, or more than ITEM_LIMIT
-    = n * num_walks * (walk_length + 1) * (1 + num_neg) items."""
+    = n * num_walks * (walk_length + 1) * (1 + num_neg) items.  metapath: first-order typed walks (metapath2vec), p = q = 1 only, on a
+    typed graph sorted by type as for random_walk(metapath=); the negatives stay type-blind, the original metapath2vec."""
+    mp = None
+    if metapath is not None:
+        mp = _check_metapath(metapath, q=q)
+        if float(p) != 1.0:
+            raise ValueError(f"metapath= with p={p!r}: a metapath walk is first-order, p = q = 1")
     if isinstance(num_neg, bool) or not isinstance(num_neg, int) or not 0 <= num_neg <= MAX_WALK_NEGATIVES:
         raise ValueError(f"num_neg {num_neg!r}: 0..{MAX_WALK_NEGATIVES} negative rows per walk")
     g, nodes, thr = _walk_args(g, nodes, p, q, walk_length, num_walks, "walk_batch")
@@ -1240,7 +1327,11 @@ def walk_batch_begin(g, nodes, p, q, walk_length, num_walks=1, num_neg=1, seed=0
     neg = torch.empty((n * W * K, L1), dtype=torch.int32, device=g.device)
     tr = torch.empty((n, W, L1), dtype=torch.int64, device=g.device) if traces else None
     out = _capi.WalkBatchOut(input_nodes.data_ptr(), pos.data_ptr(), neg.data_ptr() if neg.numel() else None, tr.data_ptr() if traces and n else None)
-    ticket = _batch_begin(_lib.coala_sampler_walk_batch, g, nodes.data_ptr(), n, W, walk_length, *thr, K, _u64(seed), _u64(step), C.byref(out))
+    args = (nodes.data_ptr(), n, W, walk_length, *thr, K, _u64(seed), _u64(step))
+    if mp is not None:
+        ticket = _batch_begin(_lib.coala_sampler_walk_batch_metapath, g, *args, *_metapath_args(g, mp, etype), C.byref(out))
+    else:
+        ticket = _batch_begin(_lib.coala_sampler_walk_batch, g, *args, C.byref(out))
     return (g, nodes, input_nodes, pos, neg, tr, ticket)
 
 
@@ -1252,9 +1343,10 @@ def walk_batch_end(pending):
     return WalkBatch(nodes, input_nodes[:n_nodes], pos, neg, tr, n_bad)
 
 
-def walk_batch(g, nodes, p=1.0, q=1.0, walk_length=20, num_walks=1, num_neg=1, seed=0, step=0, traces=False):
-    """walk_batch_end(walk_batch_begin(...)): the skip-gram batch of node2vec walks from `nodes` (PyG's Node2Vec.sample)."""
-    return walk_batch_end(walk_batch_begin(g, nodes, p, q, walk_length, num_walks, num_neg, seed, step, traces))
+def walk_batch(g, nodes, p=1.0, q=1.0, walk_length=20, num_walks=1, num_neg=1, seed=0, step=0, traces=False, metapath=None, etype="etype"):
+    """walk_batch_end(walk_batch_begin(...)): the skip-gram batch of node2vec walks from `nodes` (PyG's Node2Vec.sample), or with a
+    metapath of typed first-order walks (PyG's MetaPath2Vec)."""
+    return walk_batch_end(walk_batch_begin(g, nodes, p, q, walk_length, num_walks, num_neg, seed, step, traces, metapath, etype))
 
 
 def pair_code_bits(num_nodes, n_slots):

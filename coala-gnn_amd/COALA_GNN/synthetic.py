@@ -131,6 +131,27 @@ def edge_types_by_source(indices, num_rels):
     return indices.to(torch.int64) % int(num_rels)
 
 
+def bipartite_csc(n_users, n_items, deg, seed=0, device="cpu"):
+    """A homogenised user-item graph for the metapath walks: users are nodes 0 .. n_users - 1, items n_users .. n_users + n_items - 1.
+    Every item has `deg` in-edges from seeded random users (relation 0: user -> item), and every such edge has its reverse (relation
+    1: item -> user), so a user's in-edges come from the items it points at.  -> (indptr, indices, etype) int64 tensors on `device`;
+    every row holds one relation, so the rows are sorted by type as they are.  An item-to-item walk item <- user <- item is the
+    in-edge metapath [0, 1] from an item; [1, 0] from a user."""
+    n_users, n_items, deg = int(n_users), int(n_items), int(deg)
+    if n_users < 1 or n_items < 1 or deg < 1:
+        raise ValueError("bipartite_csc: n_users, n_items and deg must be positive")
+    rng = np.random.default_rng(int(seed))
+    users = rng.integers(0, n_users, size=(n_items, deg))                          # item i's in-neighbours
+    items = np.repeat(np.arange(n_users, n_users + n_items, dtype=np.int64), deg)
+    order = np.argsort(users.reshape(-1), kind="stable")                           # the reverse edges, grouped by user
+    user_deg = np.bincount(users.reshape(-1), minlength=n_users)
+    indptr = np.zeros(n_users + n_items + 1, dtype=np.int64)
+    np.cumsum(np.concatenate([user_deg, np.full(n_items, deg, dtype=np.int64)]), out=indptr[1:])
+    indices = np.concatenate([items[order], users.reshape(-1).astype(np.int64)])
+    etype = np.concatenate([np.ones(n_items * deg, dtype=np.int64), np.zeros(n_items * deg, dtype=np.int64)])
+    return tuple(torch.from_numpy(a).to(device) for a in (indptr, indices, etype))
+
+
 def edge_times(indptr, seed=0, t_max=1 << 20):
     """int64 [E] synthetic edge timestamps in CSC order for TemporalNeighborSampler: uniform over [0, t_max), seeded, and already
     non-decreasing inside every row (the order sampler.sort_csc_by_time gives; the draws are independent of `indices`, so sorting the

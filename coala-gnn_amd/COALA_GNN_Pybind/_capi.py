@@ -188,6 +188,12 @@ SYMBOLS = {
     "coala_sampler_node2vec_walk": (_I, [_VP, _VP, _I64, _I, _I, _U64, _U64, _U64, _U64, _U64, _VP, _VP]),
     "coala_sampler_walk_batch": (_I, [_VP, _VP, _I64, _I, _I, _U64, _U64, _U64, _I, _U64, _U64, C.POINTER(WalkBatchOut), C.POINTER(_I64), _VP]),
     "coala_sampler_walk_batch_wait": (_I, [_VP, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
+    "coala_sampler_random_walk_metapath": (_I, [_VP, _VP, _I64, _I, _I, _U64, _U64, _U64, _I, _VP, _I, C.POINTER(C.c_int32), _I, _VP, _VP]),
+    "coala_sampler_sample_layers_walk_metapath": (_I, [_VP, _VP, _I64, C.POINTER(C.c_int32), _I, _U64, _U64, C.POINTER(SamplerLayer),
+                                                  C.POINTER(SamplerWalk), _VP, _I, C.POINTER(C.c_int32), _I, C.POINTER(_VP), C.POINTER(_I64),
+                                                  C.POINTER(_I64), C.POINTER(SamplerBucketing), C.POINTER(_I64), _VP]),
+    "coala_sampler_walk_batch_metapath": (_I, [_VP, _VP, _I64, _I, _I, _U64, _U64, _U64, _I, _U64, _U64, _VP, _I, C.POINTER(C.c_int32), _I,
+                                          C.POINTER(WalkBatchOut), C.POINTER(_I64), _VP]),
     "coala_block_skipgram_loss": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _I, C.c_float, _VP]),
     "coala_block_skipgram_loss_backward": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _I, C.c_float, _VP]),
     "coala_block_gather_mm_plan_work": (_I64, [_I64, _I]),

@@ -146,6 +146,23 @@
 //   -1 for no node.  Three launches as an edge batch: walk_items (walks, negatives, hash insert), the layers' scan_assign, and
 //   walk_relabel_clear; no memset, copy or host wait.  Limit: n W (L + 1) (1 + K) <= 8,388,608.
 //
+// Metapath walks (DGL's random_walk(metapath=) and PinSAGESampler on a bipartite graph, PyG's MetaPath2Vec; the *_metapath entry points):
+// the three walk families above on a typed graph.  etype holds an int32 type in [0, num_rels) per edge, NON-DECREASING INSIDE EVERY ROW
+// (the caller's duty, checked once per graph by the Python wrapper); the metapath is M edge types, 1 <= M <= 16.
+//   * hop h of a walk standing on u uses r = metapath[h % M]: lo = the first position of u's row whose type is >= r, hi = the first whose
+//     type is >= r + 1, deg_r = max(hi - lo, 0).  deg_r == 0 ends the walk as an empty row does; otherwise the next node is
+//     indices[lo + mulhi64(draw, deg_r)], `draw` being the untyped walk's draw for that hop: same key, same stream, same counter;
+//   * short walks (random-walk layers, random_walk): the termination draw is taken only where a repetition of the metapath starts, at
+//     h >= M with h % M == 0 (DGL's restart_prob; the untyped rule at M == 1).  random_walk makes length = M * repetitions <= 16 hops, so
+//     the counters c = 2 (16 w + h) stay.  A layer's num_traversals counts repetitions: a walk makes M * num_traversals <= 16 hops and
+//     only the hops with (h + 1) % M == 0, the nodes of the start type, are recorded visits (W * num_traversals <= 512);
+//   * walk batches: first-order walks (every threshold 2^32), L <= 127, hop h takes attempt 0's draw, counter 2 (256 h); the negatives
+//     are drawn as above, whatever their type (the original metapath2vec);
+//   * on a graph of one relation, metapath {0} gives the untyped traces, blocks and batches bit for bit.
+//   A walk follows IN-edges: for item <- user <- item the metapath names the in-edge types.  Launches: metapath_select<GS>,
+//   metapath_trace and metapath_items stand where walk_select<GS>, walk_trace and walk_items stand; the segment search is described at
+//   the kernels.
+//
 // Temporal layers (PyG's NeighborLoader(time_attr=, temporal_strategy='uniform' | 'last'), GraphBolt's temporal_sample_neighbors, TGN's
 // "most recent neighbours"; coala_sampler_sample_layers_temporal), fan-out f in 1..32.  The graph carries an int64 timestamp per edge in CSC
 // order, NON-DECREASING INSIDE EVERY ROW (the caller's duty; not verified here).  A destination item of a layer is a pair (v, t): node v
@@ -878,10 +895,11 @@ __global__ __launch_bounds__(kBlock) void node2vec_trace_kernel(Graph g, const i
 // group per walk first, then a thread per negative entry.  traces (nullable) receives the global-id traces of node2vec_trace_kernel.
 __host__ __device__ inline int64_t walk_batch_items(int64_t n, int W, int L, int K) { return n + n * W * (L + 1) + n * W * K * L; }
 
-__global__ __launch_bounds__(kBlock) void walk_items_kernel(Graph g, const int64_t* __restrict__ nodes, int64_t n, N2vParams np, int K, uint64_t seed,
-                                                            uint64_t step, int64_t* __restrict__ items, int64_t* __restrict__ traces, Table tb,
-                                                            uint32_t* __restrict__ slot_of_item, unsigned long long* __restrict__ n_bad) {
-    const int L = np.L, W = np.W;
+// walk(kw, v, visit) runs the walk with key kw from v on the lanes of the group, lane 0 calling visit(h, u) for every hop h < L.
+template <typename Walk>
+__device__ __forceinline__ void walk_items(const Graph& g, const int64_t* __restrict__ nodes, int64_t n, int L, int W, int K, uint64_t seed,
+                                           uint64_t step, int64_t* __restrict__ items, int64_t* __restrict__ traces, const Table& tb,
+                                           uint32_t* __restrict__ slot_of_item, unsigned long long* __restrict__ n_bad, Walk&& walk) {
     const int64_t n_walks = n * W, n_neg = n_walks * K * L;
     const int64_t pos0 = n, neg0 = n + n_walks * (L + 1);
     const uint32_t mask = table_size(walk_batch_items(n, W, L, K)) - 1;
@@ -907,7 +925,7 @@ __global__ __launch_bounds__(kBlock) void walk_items_kernel(Graph g, const int64
             if (row) row[0] = ok ? v : kEmpty;
         }
         if (ok) {
-            node2vec_walk(g, n2v_walk_key(seed, step, v, w), v, np, [&](int h, int64_t u) {
+            walk(n2v_walk_key(seed, step, v, w), v, [&](int h, int64_t u) {
                 emit(base + 1 + h, u);
                 if (row) row[1 + h] = u;
             });
@@ -929,6 +947,13 @@ __global__ __launch_bounds__(kBlock) void walk_items_kernel(Graph g, const int64
                                       (uint64_t)g.num_nodes);
         emit(neg0 + q, key);
     }
+}
+
+__global__ __launch_bounds__(kBlock) void walk_items_kernel(Graph g, const int64_t* __restrict__ nodes, int64_t n, N2vParams np, int K, uint64_t seed,
+                                                            uint64_t step, int64_t* __restrict__ items, int64_t* __restrict__ traces, Table tb,
+                                                            uint32_t* __restrict__ slot_of_item, unsigned long long* __restrict__ n_bad) {
+    walk_items(g, nodes, n, np.L, np.W, K, seed, step, items, traces, tb, slot_of_item, n_bad,
+               [&](uint64_t kw, int64_t v, auto&& visit) { node2vec_walk(g, kw, v, np, visit); });
 }
 
 // item -> index in input_nodes (-1: no node); column 0 of a negative row is its walk's start node, the item of that node.  The table
@@ -957,6 +982,279 @@ __global__ __launch_bounds__(kBlock) void walk_relabel_clear_kernel(int64_t n, i
         *n_bad = 0;
     }
     clear_table(tb, table_size(next_items));
+}
+
+// ---------------------------------------------------------------------------------------------------------- metapath walks
+// Typed walks (the rule is in the header of this file): hop h of a walk draws inside the segment of edge type metapath[h % M] of the
+// row it stands on.  The rows are sorted by type, so the segment is [first position of type >= r, first position of type >= r + 1):
+// two boundaries, and the row is never walked.  A hop is a chain of dependent loads -- indptr, the search, the neighbour -- so the
+// search is what a typed hop costs over an untyped one.  Two forms, both looking for the two boundaries in ONE descent for as long as
+// they lie in the same range:
+//   * type_segment_group<GS>, where GS lanes stand on the same row and ask for the same type (every hop of a walk batch, whose 16-lane
+//     group owns the walk; hop 0 of a walk layer, where the W walks of a node start on the node's row): the range is cut into GS
+//     chunks, lane i probes the last position of chunk i, and two ballots of that one load (type < r, type <= r) say which chunk holds
+//     each boundary -- temporal_select's prefix search with two keys.  While both fall into the same chunk the range shrinks GS-fold per
+//     step; once they part, the lower half of the group searches for the first boundary and the upper half for the second, GS/2-fold
+//     per step and still one load per lane and step.  Every lane derives the result from the ballots: nothing is shuffled.  Dependent
+//     loads per hop: from ceil(log_GS(deg)) to about log_{GS/2}(deg) -- a row of 10^6 edges at GS = 16 takes 5 to 7, a row of 30
+//     takes 2, against 40 and 10 of two binary searches;
+//   * type_segment_lane, where the lanes have diverged (the later hops of a walk layer, every hop of the trace kernel): a binary
+//     descent that serves both boundaries until a probe meets type r itself; from there the first boundary lies below the probe and the
+//     second above it, and the two remaining searches advance together, their loads independent and issued side by side.  Dependent
+//     load steps per hop: at most ceil(log2(deg + 1)) + 1, with one load in flight before the split and two behind it (at most
+//     2 ceil(log2(deg + 1)) loads in all, what two bounded binary searches read, in half the chain).
+// Every probe is a position of the row, every range shrinks in every step and the boundaries stay inside the row whatever the types
+// hold: unsorted types give a wrong segment or an empty one, never a read outside the row, and no loop without a bound.
+constexpr int kMaxMetapath = 16;
+
+struct Metapath { // by value in the kernel arguments
+    int32_t len;            // M, 1..16
+    int32_t t[kMaxMetapath]; // edge types, each in [0, num_rels)
+};
+
+struct TypeSeg { // the in-edges of one type of a row: indices[s .. s + deg)
+    int64_t s, deg;
+};
+
+// Range [lo, hi) holds a boundary; its `parts` chunks of `chunk` positions were probed at their last positions, and the first k of them
+// lie wholly in front of the boundary: chunk k holds it, and its last position lies behind it.
+__device__ __forceinline__ void narrow_to_chunk(int64_t& lo, int64_t& hi, int64_t k, int64_t chunk) {
+    if (lo < hi) {
+        const int64_t nlo = min(lo + k * chunk, hi);
+        hi = min(nlo + chunk - 1, hi);
+        lo = nlo;
+    }
+}
+
+// The GS lanes [gbase, gbase + GS) of a wave, standing together on the row indices[start .. start + deg), find its segment of type r.
+// The trip count is the same on every lane of the group; groups of a wave may differ, a ballot is read through the group's own bits.
+template <int GS>
+__device__ __forceinline__ TypeSeg type_segment_group(const int32_t* __restrict__ etype, int64_t start, int64_t deg, int32_t r, int gl, int gbase) {
+    constexpr int H = GS / 2;
+    constexpr uint64_t kHalf = (1ull << H) - 1ull, kGroup = (kHalf << H) | kHalf;
+    int64_t lo1 = 0, hi1 = deg, lo2 = 0, hi2 = deg; // row positions; the boundary of r lies in [lo1, hi1], that of r + 1 in [lo2, hi2]
+    while (lo1 < hi1 || lo2 < hi2) {
+        const bool shared = lo1 == lo2 && hi1 == hi2;
+        const int parts = shared ? GS : H;
+        const bool upper = !shared && gl >= H; // this lane probes for the second boundary
+        const int64_t chunk1 = (hi1 - lo1 + parts - 1) / parts, chunk2 = (hi2 - lo2 + parts - 1) / parts;
+        const int64_t lo = upper ? lo2 : lo1, hi = upper ? hi2 : hi1, chunk = upper ? chunk2 : chunk1;
+        const int64_t first = lo + (int64_t)(shared ? gl : gl % H) * chunk; // this lane's chunk [first, first + chunk), cut off at hi
+        int32_t x = INT32_MAX; // no chunk: in front of no boundary
+        if (first < hi) x = etype[start + min(first + chunk, hi) - 1];
+        const uint64_t below = __ballot(x < r) >> gbase, upto = __ballot(x <= r) >> gbase; // x <= r: below type r + 1
+        const uint64_t mine = shared ? kGroup : kHalf; // the lanes that probed for each boundary: all of them, or its half of the group
+        const int64_t k1 = __popcll(below & mine), k2 = __popcll((shared ? upto : upto >> H) & mine);
+        narrow_to_chunk(lo1, hi1, k1, chunk1);
+        narrow_to_chunk(lo2, hi2, k2, chunk2);
+    }
+    return {start + lo1, max(lo2 - lo1, (int64_t)0)};
+}
+
+// One lane finds the segment of type r of the row indices[start .. start + deg).
+__device__ __forceinline__ TypeSeg type_segment_lane(const int32_t* __restrict__ etype, int64_t start, int64_t deg, int32_t r) {
+    int64_t lo1 = start, hi1 = start + max(deg, (int64_t)0), lo2 = hi1, hi2 = hi1; // as above, in CSC positions
+    bool split = false;
+    while (lo1 < hi1 && !split) { // both boundaries lie in [lo1, hi1]
+        const int64_t mid = lo1 + ((hi1 - lo1) >> 1);
+        const int32_t x = etype[mid];
+        if (x < r) {
+            lo1 = mid + 1;
+        } else if (x > r) {
+            hi1 = mid;
+        } else { // an edge of type r: the first boundary lies in [lo1, mid], the second in [mid + 1, hi1]
+            lo2 = mid + 1; hi2 = hi1; hi1 = mid;
+            split = true;
+        }
+    }
+    if (!split) return {lo1, 0}; // the descent met no edge of type r
+    while (lo1 < hi1 || lo2 < hi2) { // two searches, one step of each per trip: their loads do not wait for each other
+        const int64_t m1 = lo1 + ((hi1 - lo1) >> 1), m2 = lo2 + ((hi2 - lo2) >> 1);
+        const bool go1 = lo1 < hi1, go2 = lo2 < hi2;
+        const int32_t x1 = go1 ? etype[m1] : 0, x2 = go2 ? etype[m2] : 0;
+        if (go1) { if (x1 < r) lo1 = m1 + 1; else hi1 = m1; }
+        if (go2) { if (x2 <= r) lo2 = m2 + 1; else hi2 = m2; }
+    }
+    return {lo1, lo2 - lo1}; // lo1 <= mid < lo2
+}
+
+// The draw of a hop inside its segment; false: the walk ends (an empty segment, or a neighbour id outside the graph).
+__device__ __forceinline__ bool typed_step(const Graph& g, const TypeSeg& seg, uint64_t draw, int64_t& u) {
+    if (seg.deg <= 0) return false;
+    const int64_t x = g.indices[seg.s + (int64_t)__umul64hi(draw, (uint64_t)seg.deg)];
+    if (x < 0 || x >= g.num_nodes) return false;
+    u = x;
+    return true;
+}
+
+// random_walk's typed twin: walk w of node v with wp.T = M * repetitions hops, the same counters and the same draws.  The termination
+// draw is taken at the start of a repetition of the metapath only (h >= M, h % M == 0: DGL's restart_prob; h >= 1 at M == 1).
+// FIRST: hop 0's segment was found by the group and comes in `first`.
+template <bool FIRST, typename F>
+__device__ __forceinline__ void metapath_walk(const Graph& g, const int32_t* __restrict__ etype, const Metapath& mp, uint64_t wkey, int64_t v, int w,
+                                              const WalkParams& wp, const TypeSeg& first, F&& visit) {
+    int64_t u = v;
+    bool ended = false;
+    int m = 0; // h % M
+    for (int h = 0; h < wp.T; ++h) {
+        const uint64_t c = 2ull * (uint64_t)(kMaxWalkLength * w + h);
+        if (!ended && h >= 1 && m == 0 && (splitmix64(wkey + c) >> 11) < wp.thr) ended = true;
+        if (!ended) {
+            TypeSeg seg = first;
+            if (!FIRST || h > 0) {
+                const int64_t start = g.indptr[u];
+                seg = type_segment_lane(etype, start, g.indptr[u + 1] - start, mp.t[m]);
+            }
+            ended = !typed_step(g, seg, splitmix64(wkey + c + 1), u);
+        }
+        visit(h, ended ? kEmpty : u);
+        m = m + 1 == mp.len ? 0 : m + 1;
+    }
+}
+
+// The selection of a typed walk layer, behind the barrier that follows the walks -- walk_select_kernel's, statement for statement (that
+// kernel keeps its own text: sharing this function changed its scalar register count): the group's LDS array vis[n_vis] holds the recorded visits of
+// row d (-1: none).  Every lane counts, for its entries i = gl, gl + GS, ..., how often the node occurs among all n_vis entries; the
+// entry that is the node's first occurrence keeps the count, the others 0.  Then `fanout` rounds of a group arg-max on (count, -id) over
+// the entries still standing: round j's winner goes to lane j, and its owner retires it.  Lanes < fanout write and insert their slots,
+// lane `fanout` inserts the node itself -- the items and positions of sample_insert_kernel.  The rounds and their shuffles run for every
+// lane of the wave.
+template <int GS>
+__device__ __forceinline__ void walk_select_row(const int64_t* vis, int32_t* cnt, int n_vis, int gl, int fanout, bool active, int64_t d, int64_t v,
+                                                int64_t n_dst, uint32_t mask, int64_t* __restrict__ nbr, int32_t* __restrict__ visit_counts,
+                                                const Table& tb, uint32_t* __restrict__ slot_of_item) {
+    for (int i = gl; i < n_vis; i += GS) {
+        const int64_t x = vis[i];
+        int32_t c = 0;
+        if (x >= 0) {
+            bool first = true;
+            for (int j = 0; j < n_vis; ++j) {
+                const bool same = vis[j] == x;
+                c += same ? 1 : 0;
+                first = first && !(same && j < i);
+            }
+            if (!first) c = 0;
+        }
+        cnt[i] = c;
+    }
+    // fanout rounds of arg-max on (count, -id); an entry of count 0 never wins
+    int64_t my_id = kEmpty;
+    int32_t my_cnt = 0;
+    for (int r = 0; r < fanout; ++r) { // wave-uniform: fanout is a kernel argument
+        int32_t bc = 0;
+        int64_t bid = kEmpty;
+        int bi = -1;
+        for (int i = gl; i < n_vis; i += GS) {
+            const int32_t c = cnt[i];
+            const int64_t x = vis[i];
+            if (c > bc || (c == bc && c > 0 && x < bid)) { bc = c; bid = x; bi = i; }
+        }
+        for (int m = GS >> 1; m > 0; m >>= 1) {
+            const int32_t oc = __shfl_xor(bc, m);
+            const int64_t oid = __shfl_xor(bid, m);
+            const int oi = __shfl_xor(bi, m);
+            if (oc > bc || (oc == bc && oc > 0 && oid < bid)) { bc = oc; bid = oid; bi = oi; }
+        }
+        if (bi >= 0 && bi % GS == gl) cnt[bi] = 0; // the owner retires the winner: only this lane reads cnt[bi]
+        if (gl == r) { my_id = bc > 0 ? bid : kEmpty; my_cnt = bc; }
+    }
+    if (active && gl < fanout) {
+        const int64_t q = d * fanout + gl;
+        emit_fixed_slot(nbr, nullptr, q, my_id, 0);
+        if (visit_counts) visit_counts[q] = my_cnt;
+        hash_insert(tb, mask, my_id, n_dst + q, slot_of_item);
+    } else if (active && gl == fanout) {
+        hash_insert(tb, mask, v, d, slot_of_item);
+    }
+}
+
+// walk_select_kernel's typed twin (coala_sampler_sample_layers_walk_metapath): wp.T = M * num_traversals hops per walk, of which the
+// hops that complete a repetition of the metapath -- the nodes of the start type -- are the recorded visits: vis[w R + rep] with
+// R = num_traversals, so the LDS arrays, the counts and the rounds run over W R <= 512 entries.  Hop 0 of a row's W walks stands on
+// the row itself and asks for metapath[0]: the whole group searches that segment once (type_segment_group<GS>); the later hops have
+// diverged and search per lane.  Dynamic LDS: RPB * W R int64 visits, then RPB * W R int32 counts.
+template <int GS>
+__global__ __launch_bounds__(kBlock) void metapath_select_kernel(Graph g, const int32_t* __restrict__ etype, Metapath mp, const int64_t* __restrict__ dst,
+                                                                 const int64_t* __restrict__ n_dst_dev, int64_t n_dst_value, int fanout, WalkParams wp,
+                                                                 uint64_t seed, uint64_t step, int layer, int64_t* __restrict__ nbr,
+                                                                 int32_t* __restrict__ visit_counts, Table tb, uint32_t* __restrict__ slot_of_item) {
+    constexpr int RPB = kBlock / GS; // rows per block step
+    extern __shared__ int64_t s_walk[];
+    const int R = wp.T / mp.len, n_vis = wp.W * R;
+    const int grp = (int)threadIdx.x / GS;
+    int64_t* const vis = s_walk + (size_t)grp * n_vis;
+    int32_t* const cnt = reinterpret_cast<int32_t*>(s_walk + (size_t)RPB * n_vis) + (size_t)grp * n_vis;
+    const int64_t n_dst = layer_n_dst(n_dst_dev, n_dst_value);
+    const uint32_t mask = table_size(n_dst * (fanout + 1)) - 1;
+    const int gl = (int)threadIdx.x % GS, gbase = (int)(threadIdx.x & 63) - gl;
+    for (int64_t d0 = (int64_t)blockIdx.x * RPB; d0 < n_dst; d0 += (int64_t)gridDim.x * RPB) { // block-uniform
+        const int64_t d = d0 + grp;
+        const bool active = d < n_dst;
+        const Row row = dst_row(g, dst, d, n_dst); // an empty row when d is past the layer or the id outside the graph: nothing is probed
+        const int64_t v = row.v;
+        const TypeSeg first = type_segment_group<GS>(etype, row.start, row.deg, mp.t[0], gl, gbase);
+        if (gl < wp.W) {
+            if (row.ok) {
+                const uint64_t wkey = sample_key(seed, step, layer, (uint64_t)v) ^ kWalkStream;
+                int m = 0, rep = 0;
+                metapath_walk<true>(g, etype, mp, wkey, v, gl, wp, first, [&](int, int64_t u) {
+                    if (++m == mp.len) { vis[gl * R + rep++] = u; m = 0; }
+                });
+            } else {
+                for (int i = 0; i < R; ++i) vis[gl * R + i] = kEmpty;
+            }
+        }
+        __syncthreads();
+        walk_select_row<GS>(vis, cnt, n_vis, gl, fanout, active, d, v, n_dst, mask, nbr, visit_counts, tb, slot_of_item);
+        __syncthreads(); // every lane has read vis before the next step's walks overwrite it
+    }
+}
+
+// walk_trace_kernel's typed twin (coala_sampler_random_walk_metapath): one thread per (start node, walk), every search per lane.
+__global__ __launch_bounds__(kBlock) void metapath_trace_kernel(Graph g, const int32_t* __restrict__ etype, Metapath mp, const int64_t* __restrict__ nodes,
+                                                                int64_t n, WalkParams wp, uint64_t seed, uint64_t step, int layer,
+                                                                int64_t* __restrict__ traces) {
+    const int64_t total = n * wp.W;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t v = nodes[t / wp.W];
+        int64_t* const row = traces + t * (wp.T + 1);
+        if (v >= 0 && v < g.num_nodes) {
+            row[0] = v;
+            metapath_walk<false>(g, etype, mp, sample_key(seed, step, layer, (uint64_t)v) ^ kWalkStream, v, (int)(t % wp.W), wp, TypeSeg{0, 0},
+                                 [&](int h, int64_t u) { row[1 + h] = u; });
+        } else {
+            for (int h = 0; h <= wp.T; ++h) row[h] = kEmpty;
+        }
+    }
+}
+
+// node2vec_walk's typed twin at p = q = 1, a first-order walk: hop h takes attempt 0's draw, counter 2 (256 h), inside the segment of
+// type metapath[h % M], which the walk's kN2vGroup lanes find together at every hop.  Lane 0 calls visit(h, u).
+template <typename F>
+__device__ __forceinline__ void metapath_group_walk(const Graph& g, const int32_t* __restrict__ etype, const Metapath& mp, uint64_t kw, int64_t v, int L,
+                                                    F&& visit) {
+    const int gl = (int)threadIdx.x % kN2vGroup, gbase = (int)(threadIdx.x & 63) - gl;
+    int64_t cur = v;
+    bool ended = false;
+    int m = 0; // h % M
+    for (int h = 0; h < L; ++h) {
+        if (!ended) { // group-uniform: every lane of the group holds the same walk
+            const int64_t start = g.indptr[cur];
+            const TypeSeg seg = type_segment_group<kN2vGroup>(etype, start, g.indptr[cur + 1] - start, mp.t[m], gl, gbase);
+            ended = !typed_step(g, seg, splitmix64(kw + 2ull * (uint64_t)(kN2vAttempts * h)), cur);
+        }
+        if (gl == 0) visit(h, ended ? kEmpty : cur);
+        m = m + 1 == mp.len ? 0 : m + 1;
+    }
+}
+
+// walk_items_kernel's typed twin (coala_sampler_walk_batch_metapath): the same items, negatives (type-blind) and inserts.
+__global__ __launch_bounds__(kBlock) void metapath_items_kernel(Graph g, const int32_t* __restrict__ etype, Metapath mp, const int64_t* __restrict__ nodes,
+                                                                int64_t n, int L, int W, int K, uint64_t seed, uint64_t step, int64_t* __restrict__ items,
+                                                                int64_t* __restrict__ traces, Table tb, uint32_t* __restrict__ slot_of_item,
+                                                                unsigned long long* __restrict__ n_bad) {
+    walk_items(g, nodes, n, L, W, K, seed, step, items, traces, tb, slot_of_item, n_bad,
+               [&](uint64_t kw, int64_t v, auto&& visit) { metapath_group_walk(g, etype, mp, kw, v, L, visit); });
 }
 
 // ---------------------------------------------------------------------------------------------------------- single-pass tile scan
@@ -1705,6 +2003,7 @@ struct Call {
     bool layer_dependency = false;                                                    // labor: one key for every layer of the call
     const RelFan* rel = nullptr;                const int32_t* etype = nullptr;       // rel: every layer's fan-outs; the int32 edge types, CSC order
     WalkParams walk{};                          int32_t* const* visit_counts = nullptr; // walk; null, or per layer null or device int32[edge_cap]
+    const Metapath* metapath = nullptr;                                               // walk, typed: walk.T = M * num_traversals hops over `etype`
     const Temporal* temporal = nullptr;                                               // temporal: seeds / src_nodes hold pair codes
     bool all_ragged() const { return kind == Kind::labor || kind == Kind::rel; } // every layer is ragged, whatever its fan-out
 };
@@ -2011,8 +2310,12 @@ int launch_layer(coala_sampler_t* s, const Plan& p, int l, const int64_t* dst, c
             constexpr int GS = decltype(gs_c)::value;
             const dim3 gs(grid1d(cap_l * GS, kBlock, 8192));
             // a walk layer's dynamic LDS holds the visits (int64) and their counts (int32) of the kBlock / GS rows of a block
-            const size_t walk_lds = (size_t)(kBlock / GS) * (size_t)(p.walk.W * p.walk.T) * (sizeof(int64_t) + sizeof(int32_t));
-            if (p.kind == Kind::walk)
+            // (a typed walk records the hops that complete a repetition of its metapath only)
+            const size_t walk_lds = (size_t)(kBlock / GS) * (size_t)(p.walk.W * p.walk.T / (p.metapath ? p.metapath->len : 1)) * (sizeof(int64_t) + sizeof(int32_t));
+            if (p.kind == Kind::walk && p.metapath)
+                hipLaunchKernelGGL(metapath_select_kernel<GS>, gs, blk, walk_lds, st, s->g, p.etype, *p.metapath, dst, n_dst_dev, n_seeds, f, p.walk,
+                                   p.seed, p.step, l, s->nbr_global, p.visit_counts ? p.visit_counts[l] : nullptr, s->tb, s->slot_of_item);
+            else if (p.kind == Kind::walk)
                 hipLaunchKernelGGL(walk_select_kernel<GS>, gs, blk, walk_lds, st, s->g, dst, n_dst_dev, n_seeds, f, p.walk, p.seed, p.step, l,
                                    s->nbr_global, p.visit_counts ? p.visit_counts[l] : nullptr, s->tb, s->slot_of_item);
             else if (p.kind == Kind::temporal)
@@ -2371,23 +2674,60 @@ int coala_sampler_sample_layers_rel(coala_sampler_t* s, const int64_t* seeds, in
     return sample_impl(s, c);
 }
 
-int coala_sampler_sample_layers_walk(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
-                                     uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const coala_sampler_walk_t* walk,
-                                     int32_t* const* visit_counts_out, int64_t* n_src_host, int64_t* n_edges_host,
-                                     const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
+// The metapath arguments of the three typed entry points -> the kernels' by-value form.
+static int check_metapath(const int32_t* etype, int num_rels, const int32_t* metapath, int metapath_len, Metapath* mp) {
+    if (!etype) return fail(COALA_EINVAL, "null etype");
+    if (!metapath) return fail(COALA_EINVAL, "null metapath");
+    if (metapath_len < 1 || metapath_len > kMaxMetapath) return fail(COALA_EINVAL, "metapath of %d edge types: 1..%d", metapath_len, kMaxMetapath);
+    if (num_rels < 1) return fail(COALA_EINVAL, "num_rels must be at least 1");
+    mp->len = metapath_len;
+    for (int i = 0; i < metapath_len; ++i) {
+        if (metapath[i] < 0 || metapath[i] >= num_rels) return fail(COALA_EINVAL, "metapath[%d] = %d outside [0, %d)", i, metapath[i], num_rels);
+        mp->t[i] = metapath[i];
+    }
+    return COALA_OK;
+}
+
+// Both walk-layer entry points; mp null: untyped.  A walk makes M * num_traversals hops and records num_traversals visits.
+static int walk_layers(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers, uint64_t seed, uint64_t step,
+                       const coala_sampler_layer_t* layers, const coala_sampler_walk_t* walk, const int32_t* etype, const Metapath* mp,
+                       int32_t* const* visit_counts_out, int64_t* n_src_host, int64_t* n_edges_host, const coala_sampler_bucketing_t* bucketing,
+                       int64_t* ticket_out, void* stream) {
     if (!fanouts || !layers || !walk) return fail(COALA_EINVAL, "null argument");
     if (int rc = check_n_layers(n_layers)) return rc;
-    const int T = walk->num_traversals, W = walk->num_random_walks;
+    const int T = walk->num_traversals, W = walk->num_random_walks, M = mp ? mp->len : 1;
     if (T < 1 || T > kMaxWalkLength) return fail(COALA_EINVAL, "num_traversals %d outside 1..%d", T, kMaxWalkLength);
+    if (M * T > kMaxWalkLength) return fail(COALA_EINVAL, "%d traversals of a metapath of %d edge types: over the limit of %d hops", T, M, kMaxWalkLength);
     if (W < 1 || W > kMaxWalks) return fail(COALA_EINVAL, "num_random_walks %d outside 1..%d", W, kMaxWalks);
     if (W * T > kMaxVisits) return fail(COALA_EINVAL, "num_random_walks * num_traversals = %d: over the limit of %d visits", W * T, kMaxVisits);
     if (walk->term_threshold >= kWalkThresholdMax) return fail(COALA_EINVAL, "term_threshold must be below 2^53 (termination_prob < 1)");
     if (int rc = check_fixed_layers(fanouts, layers, n_layers, "walk", "keeps 1..32 neighbours")) return rc;
     Call c{Kind::walk, seeds, n_seeds, fanouts, n_layers, seed, step, layers, nullptr, n_src_host, n_edges_host, bucketing, ticket_out,
            (hipStream_t)stream};
-    c.walk = WalkParams{T, W, walk->term_threshold};
+    c.walk = WalkParams{M * T, W, walk->term_threshold};
     c.visit_counts = visit_counts_out;
+    c.etype = etype;
+    c.metapath = mp;
     return sample_impl(s, c);
+}
+
+int coala_sampler_sample_layers_walk(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                     uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const coala_sampler_walk_t* walk,
+                                     int32_t* const* visit_counts_out, int64_t* n_src_host, int64_t* n_edges_host,
+                                     const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
+    return walk_layers(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, walk, nullptr, nullptr, visit_counts_out, n_src_host, n_edges_host,
+                       bucketing, ticket_out, stream);
+}
+
+int coala_sampler_sample_layers_walk_metapath(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                              uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const coala_sampler_walk_t* walk,
+                                              const int32_t* etype, int num_rels, const int32_t* metapath, int metapath_len,
+                                              int32_t* const* visit_counts_out, int64_t* n_src_host, int64_t* n_edges_host,
+                                              const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream) {
+    Metapath mp{};
+    if (int rc = check_metapath(etype, num_rels, metapath, metapath_len, &mp)) return rc;
+    return walk_layers(s, seeds, n_seeds, fanouts, n_layers, seed, step, layers, walk, etype, &mp, visit_counts_out, n_src_host, n_edges_host,
+                       bucketing, ticket_out, stream);
 }
 
 int coala_sampler_sample_layers_temporal(coala_sampler_t* s, const int64_t* seed_codes, int64_t n_seeds, const int32_t* fanouts, int n_layers,
@@ -2414,8 +2754,9 @@ int coala_sampler_sample_layers_temporal(coala_sampler_t* s, const int64_t* seed
     return sample_impl(s, c);
 }
 
-int coala_sampler_random_walk(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t term_threshold,
-                              uint64_t seed, uint64_t step, int layer, int64_t* traces_out, void* stream) {
+// Both trace entry points of the short walks; mp null: untyped.
+static int short_walk_traces(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t term_threshold, uint64_t seed,
+                             uint64_t step, int layer, const int32_t* etype, const Metapath* mp, int64_t* traces_out, void* stream) {
     auto check_ranges = [&] {
         if (num_walks < 1 || num_walks > kMaxWalks) return fail(COALA_EINVAL, "num_walks %d outside 1..%d", num_walks, kMaxWalks);
         if (length < 1 || length > kMaxWalkLength) return fail(COALA_EINVAL, "length %d outside 1..%d", length, kMaxWalkLength);
@@ -2424,9 +2765,29 @@ int coala_sampler_random_walk(coala_sampler_t* s, const int64_t* nodes, int64_t 
         return COALA_OK;
     };
     return trace_call(s, nodes, n, traces_out, check_ranges, [&] {
-        hipLaunchKernelGGL(walk_trace_kernel, dim3(grid1d(n * num_walks, kBlock, 8192)), dim3(kBlock), 0, (hipStream_t)stream, s->g, nodes, n,
-                           WalkParams{length, num_walks, term_threshold}, seed, step, layer, traces_out);
+        const dim3 grid(grid1d(n * num_walks, kBlock, 8192));
+        const WalkParams wp{length, num_walks, term_threshold};
+        if (mp)
+            hipLaunchKernelGGL(metapath_trace_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, s->g, etype, *mp, nodes, n, wp, seed, step, layer,
+                               traces_out);
+        else
+            hipLaunchKernelGGL(walk_trace_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, s->g, nodes, n, wp, seed, step, layer, traces_out);
     });
+}
+
+int coala_sampler_random_walk(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t term_threshold,
+                              uint64_t seed, uint64_t step, int layer, int64_t* traces_out, void* stream) {
+    return short_walk_traces(s, nodes, n, num_walks, length, term_threshold, seed, step, layer, nullptr, nullptr, traces_out, stream);
+}
+
+int coala_sampler_random_walk_metapath(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t term_threshold,
+                                       uint64_t seed, uint64_t step, int layer, const int32_t* etype, int num_rels, const int32_t* metapath,
+                                       int metapath_len, int64_t* traces_out, void* stream) {
+    Metapath mp{};
+    if (int rc = check_metapath(etype, num_rels, metapath, metapath_len, &mp)) return rc;
+    if (length < 1 || length > kMaxWalkLength) return fail(COALA_EINVAL, "length %d outside 1..%d", length, kMaxWalkLength);
+    if (length % mp.len != 0) return fail(COALA_EINVAL, "length %d is no multiple of the metapath's %d edge types", length, mp.len);
+    return short_walk_traces(s, nodes, n, num_walks, length, term_threshold, seed, step, layer, etype, &mp, traces_out, stream);
 }
 
 // The three thresholds of a second-order walk: each in [0, 2^32], the largest exactly 2^32 (the host normalises by max(1/p, 1, 1/q)).
@@ -2447,9 +2808,10 @@ int coala_sampler_node2vec_walk(coala_sampler_t* s, const int64_t* nodes, int64_
     });
 }
 
-int coala_sampler_walk_batch(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t thr_return,
-                             uint64_t thr_near, uint64_t thr_far, int num_neg, uint64_t seed, uint64_t step, const coala_walk_batch_t* out,
-                             int64_t* ticket_out, void* stream) {
+// Both walk-batch entry points; mp null: the second-order walks.
+static int walk_batch_call(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t thr_return, uint64_t thr_near,
+                           uint64_t thr_far, int num_neg, uint64_t seed, uint64_t step, const int32_t* etype, const Metapath* mp,
+                           const coala_walk_batch_t* out, int64_t* ticket_out, void* stream) {
     if (!s || !out || (!nodes && n > 0)) return fail(COALA_EINVAL, "null argument");
     if (int rc = check_n2v(num_walks, length, thr_return, thr_near, thr_far)) return rc;
     if (num_neg < 0 || num_neg > kN2vMaxNeg) return fail(COALA_EINVAL, "num_neg %d outside 0..%d", num_neg, kN2vMaxNeg);
@@ -2465,13 +2827,36 @@ int coala_sampler_walk_batch(coala_sampler_t* s, const int64_t* nodes, int64_t n
         [&] {
             const N2vParams np{length, num_walks, thr_return, thr_near, thr_far};
             const int64_t n_walks = n * num_walks;
-            hipLaunchKernelGGL(walk_items_kernel, dim3(grid1d(std::max<int64_t>(n_walks * kN2vGroup, n_walks * num_neg * length / 4), kBlock, 8192)),
-                               dim3(kBlock), 0, st, s->g, nodes, n, np, num_neg, seed, step, s->nbr_global, out->traces, s->tb, s->slot_of_item, s->edge_bad);
+            const dim3 grid(grid1d(std::max<int64_t>(n_walks * kN2vGroup, n_walks * num_neg * length / 4), kBlock, 8192));
+            if (mp)
+                hipLaunchKernelGGL(metapath_items_kernel, grid, dim3(kBlock), 0, st, s->g, etype, *mp, nodes, n, length, num_walks, num_neg, seed, step,
+                                   s->nbr_global, out->traces, s->tb, s->slot_of_item, s->edge_bad);
+            else
+                hipLaunchKernelGGL(walk_items_kernel, grid, dim3(kBlock), 0, st, s->g, nodes, n, np, num_neg, seed, step, s->nbr_global, out->traces,
+                                   s->tb, s->slot_of_item, s->edge_bad);
         },
         [&](dim3 grid, int64_t* n_bad_pin) {
             hipLaunchKernelGGL(walk_relabel_clear_kernel, grid, dim3(kBlock), 0, st, n, num_walks, length, num_neg, (const uint32_t*)s->slot_of_item, s->tb,
                                out->pos, out->neg, s->edge_bad, n_bad_pin, items);
         });
+}
+
+int coala_sampler_walk_batch(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t thr_return,
+                             uint64_t thr_near, uint64_t thr_far, int num_neg, uint64_t seed, uint64_t step, const coala_walk_batch_t* out,
+                             int64_t* ticket_out, void* stream) {
+    return walk_batch_call(s, nodes, n, num_walks, length, thr_return, thr_near, thr_far, num_neg, seed, step, nullptr, nullptr, out, ticket_out, stream);
+}
+
+int coala_sampler_walk_batch_metapath(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t thr_return,
+                                      uint64_t thr_near, uint64_t thr_far, int num_neg, uint64_t seed, uint64_t step, const int32_t* etype,
+                                      int num_rels, const int32_t* metapath, int metapath_len, const coala_walk_batch_t* out, int64_t* ticket_out,
+                                      void* stream) {
+    Metapath mp{};
+    if (int rc = check_metapath(etype, num_rels, metapath, metapath_len, &mp)) return rc;
+    if (int rc = check_n2v(num_walks, length, thr_return, thr_near, thr_far)) return rc;
+    if (thr_return != kN2vOne || thr_near != kN2vOne || thr_far != kN2vOne)
+        return fail(COALA_EINVAL, "a metapath walk is first-order: every threshold must be 2^32 (p = q = 1)");
+    return walk_batch_call(s, nodes, n, num_walks, length, thr_return, thr_near, thr_far, num_neg, seed, step, etype, &mp, out, ticket_out, stream);
 }
 
 int coala_sampler_walk_batch_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_nodes_host, int64_t* n_bad_host) {

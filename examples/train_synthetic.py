@@ -38,13 +38,13 @@ sys.path.insert(0, os.path.join(ROOT, "coala-gnn_amd"))
 
 import torch  # noqa: E402
 
-from COALA_GNN import COALA_GNN_DataLoader, MPI_Comm_Manager, Node2Vec, Node_Distributor, NodeEmbedding, RowWiseAdagrad, SparseAdagrad, SparseAdam, SparseSGD, SSD_INFO  # noqa: E402
+from COALA_GNN import COALA_GNN_DataLoader, MetaPath2Vec, MPI_Comm_Manager, Node2Vec, Node_Distributor, NodeEmbedding, RowWiseAdagrad, SparseAdagrad, SparseAdam, SparseSGD, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
 from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, GATv2, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
-from COALA_GNN.sampler import (EdgePredictionSampler, LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler,  # noqa: E402
+from COALA_GNN.sampler import (CSCGraph, EdgePredictionSampler, LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler,  # noqa: E402
                                TemporalEdgePredictionSampler, TemporalNeighborSampler, UniformNegativeSampler, reverse_edge_ids,
                                sort_csc_by_etype)
-from COALA_GNN.synthetic import alloc_pinned_table, community_csc, edge_times, edge_types_by_source, powerlaw_csc, symmetrize_csc  # noqa: E402
+from COALA_GNN.synthetic import alloc_pinned_table, bipartite_csc, community_csc, edge_times, edge_types_by_source, powerlaw_csc, symmetrize_csc  # noqa: E402
 
 T_MAX = 1 << 20    # --sampler temporal: synthetic edge timestamps lie in [0, T_MAX)
 DECAY = "decay"    # --time_decay: the edata key the gcn / sage layers read their edge weights from
@@ -83,12 +83,19 @@ def train_node2vec(args):
     """--task node2vec: shallow embeddings of a graph without features, as PyG's Node2Vec example -- biased walks from every node,
     skip-gram windows with --num_negs negative rows per walk, a sparse optimizer over the embedding table.  The graph is
     symmetrize_csc(community_csc(..)): planted communities of 2,048 nodes, rows sorted by source id as the walks need at q != 1.  After
-    every epoch: the mean loss, and how much closer (cosine) a node's embedding is to a node of its own community than to a random one."""
+    every epoch: the mean loss, and how much closer (cosine) a node's embedding is to a node of its own community than to a random one.
+    With --metapath (metapath2vec): typed first-order walks on bipartite_csc(nodes / 2 users, nodes / 2 items), one table for both node
+    types; the community figure has no meaning there and is not printed."""
     device = f"cuda:{torch.cuda.current_device()}"
-    indptr, indices = symmetrize_csc(*community_csc(args.nodes, 10.0, seed=0, device=device))
     torch.manual_seed(max(args.seed, 0))
-    model = Node2Vec((indptr, indices), args.emb_dim or args.dim, args.walk_length, args.context_size, walks_per_node=args.walks_per_node, p=args.p,
-                     q=args.q, num_negative_samples=args.num_negs, cache_mb=args.cache_size, device=device, seed=max(args.seed, 0))
+    common = dict(walks_per_node=args.walks_per_node, num_negative_samples=args.num_negs, cache_mb=args.cache_size, device=device, seed=max(args.seed, 0))
+    if args.metapath is not None:
+        indptr, indices, etype = bipartite_csc(args.nodes // 2, args.nodes - args.nodes // 2, 10, seed=0, device=device)
+        model = MetaPath2Vec(CSCGraph(indptr, indices, edata={"etype": etype}), args.emb_dim or args.dim, args.metapath, args.walk_length,
+                             args.context_size, **common)
+    else:
+        indptr, indices = symmetrize_csc(*community_csc(args.nodes, 10.0, seed=0, device=device))
+        model = Node2Vec((indptr, indices), args.emb_dim or args.dim, args.walk_length, args.context_size, p=args.p, q=args.q, **common)
     opt = sparse_optimizer(args, model.embedding)
     probe = torch.randperm(args.nodes, generator=torch.Generator().manual_seed(1))[:4096].to(device)
     for epoch in range(args.epochs):
@@ -99,6 +106,9 @@ def train_node2vec(args):
             opt.step()   # (clears the embedding's trace)
             total += float(loss.detach())
             steps += 1
+        if args.metapath is not None:
+            print(f"Epoch {epoch:05d} | Loss {total / max(steps, 1):.4f} | Steps {steps} | Time {time.time() - t0:.2f}s")
+            continue
         z = torch.nn.functional.normalize(model(probe), dim=1)
         same = (probe // 2048 * 2048 + (probe + 1) % 2048).clamp_max(args.nodes - 1)      # the next node of the same community
         other = probe[torch.randperm(probe.numel(), device=device)]
@@ -194,6 +204,9 @@ def main():
     ap.add_argument("--num_traversals", type=int, default=2, help="with --sampler pinsage: hops per walk (1..16)")
     ap.add_argument("--termination_prob", type=float, default=0.5, help="with --sampler pinsage: a hop after the first ends the walk with this probability")
     ap.add_argument("--num_random_walks", type=int, default=10, help="with --sampler pinsage: walks per node (1..64)")
+    ap.add_argument("--metapath", type=lambda t: [int(x) for x in t.split(",")], default=None,
+                    help="with --sampler pinsage or --task node2vec on the synthetic graph: in-edge types of a typed walk, e.g. 0,1 (item <- user "
+                         "<- item on the bipartite user-item graph that then stands in); --num_traversals counts repetitions of it")
     ap.add_argument("--rel_fan_out", type=str, default=None,
                     help="with --sampler rel, in place of --fan_out: layers separated by ';', the --num_rels relations of a layer by ',' "
                          "(-1: every in-edge of the type, 0: none); a single number per layer applies to every relation, "
@@ -282,6 +295,8 @@ def main():
         if args.path or args.node_embedding or int(os.environ.get("WORLD_SIZE", 1)) != 1 or not 0 <= args.num_negs <= 16:
             ap.error("--task node2vec runs on the synthetic graph on one GPU, with --num_negs 0..16 and without --node_embedding (it owns its table)")
         return train_node2vec(args)
+    if args.metapath is not None and (args.path or args.sampler != "pinsage" or args.task != "node"):
+        ap.error("--metapath goes with --sampler pinsage or --task node2vec, on the synthetic graph")
     comm = MPI_Comm_Manager(node_rank)                                  # sbatch_ssd_gnn_train.py:262
     device = "cuda:" + str(comm.local_rank)
     comm.initialize_nested_process_group(args.cache_backend)            # :267
@@ -334,6 +349,12 @@ def main():
         train_ids = torch.arange(int(0.6 * args.nodes))
         test_ids = torch.arange(int(0.8 * args.nodes), args.nodes)
         meta = None
+        if args.metapath is not None:   # a user-item graph, users first; the items are classified (a walk of [0, 1] from an item reaches items)
+            n_users = args.nodes // 2
+            n_items = args.nodes - n_users
+            indptr, indices, etype = bipartite_csc(n_users, n_items, 10, seed=0, device=device)
+            train_ids = n_users + torch.arange(int(0.6 * n_items))
+            test_ids = n_users + torch.arange(int(0.8 * n_items), n_items)
     n_train = len(train_ids)
     if meta is not None and all(os.path.exists(os.path.join(meta, f)) for f in ("color.npy", "topk.npy", "score.npy")):
         tmp = meta  # the colouring tool's output next to the dataset, where the reference looks for it
@@ -387,7 +408,9 @@ def main():
     elif rel_fan_out is not None:
         sampler = RelNeighborSampler(rel_fan_out, args.num_rels)
     elif args.sampler == "pinsage":
-        sampler = RandomWalkNeighborSampler(fan_out, args.num_traversals, args.termination_prob, args.num_random_walks)
+        if args.metapath is not None:
+            edata = dict(edata, etype=etype)
+        sampler = RandomWalkNeighborSampler(fan_out, args.num_traversals, args.termination_prob, args.num_random_walks, metapath=args.metapath)
     elif args.sampler == "temporal":
         sampler = TemporalNeighborSampler(fan_out, strategy=args.temporal_strategy, seed_time="t", edge_ids=edge_ids or ew is not None)
     else:

@@ -605,6 +605,35 @@ int coala_sampler_walk_batch(coala_sampler_t* s, const int64_t* nodes, int64_t n
                              uint64_t thr_near, uint64_t thr_far, int num_neg, uint64_t seed, uint64_t step, const coala_walk_batch_t* out,
                              int64_t* ticket_out, void* stream);
 int coala_sampler_walk_batch_wait(coala_sampler_t* s, int64_t ticket, int64_t* n_nodes_host, int64_t* n_bad_host);
+/* Metapath walks on a typed graph (DGL's random_walk(metapath=) and PinSAGESampler on a bipartite graph, PyG's MetaPath2Vec): the three
+ * walk entry points above with an edge type per hop.  etype: device int32[num_edges] in CSC order, values in [0, num_rels), NON-DECREASING
+ * INSIDE EVERY ROW (the caller's duty, as for coala_sampler_sample_layers_rel; unsorted types give wrong segments, never a read outside
+ * the row).  metapath: host int32[metapath_len], M = metapath_len in 1..16, copied into the kernel arguments.  Hop h of a walk standing
+ * on u uses r = metapath[h % M]: lo = the first position of u's row whose type is >= r, hi = the first whose type is >= r + 1, deg_r =
+ * max(hi - lo, 0); deg_r == 0 ends the walk, else the next node is indices[lo + mulhi64(draw, deg_r)], `draw` being the draw the untyped
+ * entry point takes for that hop (same key, stream and counter).  A walk follows IN-edges: for item <- user <- item name the in-edge
+ * types.  On a graph of one relation, metapath {0} gives the untyped entry point's output bit for bit.
+ *   coala_sampler_random_walk_metapath: `length` hops, a multiple of M, at most 16.  The termination draw is taken at the start of a
+ *     repetition of the metapath only (h >= M and h % M == 0: DGL's restart_prob).
+ *   coala_sampler_sample_layers_walk_metapath: walk->num_traversals counts repetitions of the metapath (DGL's meaning): a walk makes
+ *     M * num_traversals <= 16 hops, terminates as above, and only the hops that complete a repetition -- nodes of the start type -- are
+ *     recorded visits (num_random_walks * num_traversals <= 512).  Everything else is coala_sampler_sample_layers_walk's.
+ *   coala_sampler_walk_batch_metapath: first-order walks of `length` (1..127) hops, any length; the three thresholds must be 2^32
+ *     (p = q = 1).  Negatives are drawn as in coala_sampler_walk_batch, whatever their type.  Collected by coala_sampler_walk_batch_wait.
+ * COALA_EINVAL (with a message) before any launch for a NULL etype or metapath, M outside 1..16, a type outside [0, num_rels), and the
+ * limits above; otherwise the refusals, launches and outputs are those of the untyped entry points. */
+int coala_sampler_random_walk_metapath(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t term_threshold,
+                                       uint64_t seed, uint64_t step, int layer, const int32_t* etype, int num_rels, const int32_t* metapath,
+                                       int metapath_len, int64_t* traces_out, void* stream);
+int coala_sampler_sample_layers_walk_metapath(coala_sampler_t* s, const int64_t* seeds, int64_t n_seeds, const int32_t* fanouts, int n_layers,
+                                              uint64_t seed, uint64_t step, const coala_sampler_layer_t* layers, const coala_sampler_walk_t* walk,
+                                              const int32_t* etype, int num_rels, const int32_t* metapath, int metapath_len,
+                                              int32_t* const* visit_counts_out, int64_t* n_src_host, int64_t* n_edges_host,
+                                              const coala_sampler_bucketing_t* bucketing, int64_t* ticket_out, void* stream);
+int coala_sampler_walk_batch_metapath(coala_sampler_t* s, const int64_t* nodes, int64_t n, int num_walks, int length, uint64_t thr_return,
+                                      uint64_t thr_near, uint64_t thr_far, int num_neg, uint64_t seed, uint64_t step, const int32_t* etype,
+                                      int num_rels, const int32_t* metapath, int metapath_len, const coala_walk_batch_t* out, int64_t* ticket_out,
+                                      void* stream);
 
 /* Block op for the consumer of these blocks (the native Block objects stand where DGL blocks stand in
  * examples/sbatch_ssd_gnn_train.py:138-141; dgl.nn.SAGEConv's "mean" reduces to this): out[d, :] = mean over the valid j of
