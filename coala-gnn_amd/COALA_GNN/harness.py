@@ -15,7 +15,7 @@ import time
 
 import torch
 
-from .nn import DotGatConv, DotPredictor, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv, WeightedSAGEConv
+from .nn import DotGatConv, DotPredictor, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, LSTMSAGEConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv, WeightedSAGEConv
 
 __all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "PinSAGE", "LinkPredictor", "link_loss", "train_steps", "FlatGradAllReduce"]
 
@@ -98,19 +98,27 @@ class GCN(torch.nn.Module):
 
 class SAGE(torch.nn.Module):
     """GraphSAGE on COALA_GNN.nn.SAGEConv ('mean', 'gcn' as the reference's RSAGE model uses, or 'pool', the max-pooling aggregator),
-    relu between the layers; with edge_weight=<edata key> every layer weighs its messages by block.edata[key]."""
+    relu between the layers; with edge_weight=<edata key> every layer weighs its messages by block.edata[key].  'lstm' builds the
+    layers from COALA_GNN.nn.LSTMSAGEConv (the native LSTM aggregation, Block.lstm_aggregate), which takes no edge weights."""
 
     def __init__(self, in_feats, h_feats, num_classes, num_layers=2, aggregator_type="mean", edge_weight=None):
         super().__init__()
         dims = [in_feats] + [h_feats] * (num_layers - 1) + [num_classes]
-        self.layers = torch.nn.ModuleList(SAGEConv(dims[i], dims[i + 1], aggregator_type) for i in range(num_layers))
+        if aggregator_type == "lstm":
+            if edge_weight is not None:
+                raise ValueError("the 'lstm' aggregator takes no edge weights")
+            self.layers = torch.nn.ModuleList(LSTMSAGEConv(dims[i], dims[i + 1]) for i in range(num_layers))
+        else:
+            self.layers = torch.nn.ModuleList(SAGEConv(dims[i], dims[i + 1], aggregator_type) for i in range(num_layers))
         self.edge_weight = edge_weight
 
     def forward(self, blocks, x):
         h = x
         for i, (layer, block) in enumerate(zip(self.layers, blocks)):
-            w = None if self.edge_weight is None else block.edata[self.edge_weight]
-            h = layer(block, (h, block.dst_rows(h)), edge_weight=w)
+            if self.edge_weight is None:
+                h = layer(block, (h, block.dst_rows(h)))
+            else:
+                h = layer(block, (h, block.dst_rows(h)), edge_weight=block.edata[self.edge_weight])
             if i + 1 < len(self.layers):
                 h = torch.relu(h)
         return h

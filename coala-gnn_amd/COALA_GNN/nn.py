@@ -16,12 +16,14 @@ DotGatConv and HGTConv (the Heterogeneous Graph Transformer, on a homogenised bl
 scaled dot product, Block.dot_gat_aggregate, a native kernel without [E, H, D] intermediates; HGTConv applies its per-relation D x D
 matrices per (source, relation) pair, not per edge, and folds the relation prior into the attention matrix.
 WeightedSAGEConv is the layer of DGL's PinSAGE example on blocks sampled by random walks (RandomWalkNeighborSampler): the visit counts
-in block.edata['weights'] weigh the neighbours' rows through Block.weighted_sum_aggregate."""
+in block.edata['weights'] weigh the neighbours' rows through Block.weighted_sum_aggregate.
+LSTMSAGEConv is DGL's SAGEConv with aggregator_type='lstm' as a class of its own: the recurrence over a destination's neighbours is
+Block.lstm_aggregate, a native kernel on the matrix units, and the input projection is made once per source node."""
 import torch
 
 from .block_ops import gather_mm
 
-__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv", "TypedLinear", "DotPredictor"]
+__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "LSTMSAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv", "TypedLinear", "DotPredictor"]
 
 
 class GATConv(torch.nn.Module):
@@ -187,7 +189,7 @@ class SAGEConv(torch.nn.Module):
     does ('pool' always projects after it, as in DGL).  feat is h_src or (h_src, h_dst); without h_dst the destination rows are
     block.dst_rows(h_src).  A destination without an in-edge gets fc_self(h_dst) + bias ('mean', 'pool': its maximum is 0, DGL's
     reducer) or fc_neigh(h_dst) + bias ('gcn').  The maximum is Block.max_aggregate: ties give their gradient to the first edge.
-    The 'lstm' aggregator, feat_drop and norm are not provided."""
+    The 'lstm' aggregator is a class of its own, LSTMSAGEConv; feat_drop and norm are not provided."""
 
     def __init__(self, in_feats, out_feats, aggregator_type="mean", bias=True, activation=None):
         super().__init__()
@@ -244,6 +246,46 @@ class SAGEConv(torch.nn.Module):
         if self.activation is not None:
             rst = self.activation(rst)
         return rst
+
+
+class LSTMSAGEConv(torch.nn.Module):
+    """DGL's SAGEConv(aggregator_type='lstm') on a block, with its parameter names so that such a state_dict loads with strict=True:
+        out[d] = fc_self(h_dst[d]) + fc_neigh(LSTM(h_src[s_1], ..., h_src[s_k])) + bias,   then activation, if any
+    the LSTM (input and hidden size in_src, from h = c = 0) run over the valid in-edges of d in slot order, DGL's mailbox order, and
+    read at its last step.  lstm is a torch.nn.LSTM(in_src, in_src, batch_first=True) held for its parameters (lstm.weight_ih_l0,
+    lstm.weight_hh_l0 [4 in_src, in_src], lstm.bias_ih_l0, lstm.bias_hh_l0 [4 in_src], torch's initialisation); fc_self.weight /
+    fc_neigh.weight [out_feats, in] (no bias of their own, Xavier-uniform with the gain of relu), bias [out_feats] (zero).  The input
+    side of the gates, h_src @ weight_ih^T + bias_ih + bias_hh, is one GEMM over the source NODES; the recurrence is
+    Block.lstm_aggregate, native for fp32 on the GPU and in_src a multiple of 32 up to 256, plain torch otherwise (project a wider
+    feature down first).  A destination without an in-edge gets fc_self(h_dst) + bias.  feat is h_src or (h_src, h_dst)."""
+
+    def __init__(self, in_feats, out_feats, bias=True, activation=None):
+        super().__init__()
+        in_src, in_dst = in_feats if isinstance(in_feats, (tuple, list)) else (in_feats, in_feats)
+        self._in_src_feats, self._out_feats = in_src, out_feats
+        self.lstm = torch.nn.LSTM(in_src, in_src, batch_first=True)
+        self.fc_self = torch.nn.Linear(in_dst, out_feats, bias=False)
+        self.fc_neigh = torch.nn.Linear(in_src, out_feats, bias=False)
+        self.bias = torch.nn.Parameter(torch.empty(out_feats)) if bias else None
+        self.activation = activation
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        self.lstm.reset_parameters()
+        torch.nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
+        torch.nn.init.xavier_uniform_(self.fc_neigh.weight, gain=gain)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, block, feat):
+        h_src, h_dst = feat if isinstance(feat, (tuple, list)) else (feat, block.dst_rows(feat))
+        lstm = self.lstm
+        xg = torch.addmm(lstm.bias_ih_l0 + lstm.bias_hh_l0, h_src, lstm.weight_ih_l0.t())        # [num_src, 4 in_src]: once per node
+        rst = self.fc_self(h_dst) + self.fc_neigh(block.lstm_aggregate(xg, lstm.weight_hh_l0))
+        if self.bias is not None:
+            rst = rst + self.bias
+        return rst if self.activation is None else self.activation(rst)
 
 
 class WeightedSAGEConv(torch.nn.Module):

@@ -12,7 +12,7 @@ import torch
 from COALA_GNN_Pybind import _capi, current_stream
 
 from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
-                        _MeanAggregateCSR, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _WeightedSum, _WeightedSumCSR)
+                        _MeanAggregateCSR, _LSTMAggregate, _LSTMAggregateCSR, LSTM_HIDDEN_STEP, LSTM_MAX_HIDDEN, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _WeightedSum, _WeightedSumCSR)
 
 __all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "RandomWalkNeighborSampler", "PinSAGESampler", "random_walk", "sort_csc_by_etype",
            "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT", "EID", "EdgePredictionSampler", "as_edge_prediction_sampler",
@@ -493,6 +493,56 @@ class Block(object):
             return out
         arg = torch.where(some, src.view((E,) + ones).expand_as(v).gather(0, first), torch.full_like(first, -1)).to(torch.int32)
         return out, arg
+
+    @staticmethod
+    def _lstm_args(xg, w_hh):
+        """The checks of lstm_aggregate / lstm_aggregate_torch -> H."""
+        if xg.dim() != 2 or w_hh.dim() != 2 or w_hh.shape[0] != 4 * w_hh.shape[1] or xg.shape[1] != w_hh.shape[0]:
+            raise ValueError(f"xg of shape {tuple(xg.shape)}, w_hh of shape {tuple(w_hh.shape)}: lstm_aggregate takes xg [num_src, 4H] and w_hh [4H, H]")
+        return w_hh.shape[1]
+
+    def lstm_aggregate(self, xg, w_hh):
+        """LSTM aggregation of the sampled neighbours for every dst node: [num_dst, H] (DGL's SAGEConv 'lstm' reducer, PyG's
+        LSTMAggregation).  xg [num_src, 4H]: the input-side gate pre-activations of every SOURCE NODE, x @ W_ih^T + b_ih + b_hh in
+        torch's gate order i, f, g, o -- projected once per node by the caller, not per edge; w_hh [4H, H]: torch's weight_hh_l0.
+        Row d starts from h = c = 0 and takes its valid slots in slot order (DGL's mailbox order; a -1 is skipped wherever it
+        stands), a step with source s being z = xg[s] + h @ w_hh^T, i, f, o = sigmoid(z_i, z_f, z_o), g = tanh(z_g), c = f c + i g,
+        h = o tanh(c); the result is the last h.  A dst node without an in-edge gets exact zeros and sends no gradient (DGL's rule
+        for in-degree 0).  Native kernels on the matrix units (coala_lstm.hip), with gradients for xg and w_hh, for fp32 tensors on
+        the GPU with H a multiple of 32 up to 256, under the block conditions of mean_aggregate; lstm_aggregate_torch otherwise (a
+        wider feature is projected down first).  The native forward is bitwise reproducible and the same on both block forms; its
+        backward can run once per forward."""
+        H = self._lstm_args(xg, w_hh)
+        native = (xg.is_cuda and w_hh.device == xg.device and xg.dtype == torch.float32 and w_hh.dtype == torch.float32
+                  and H % LSTM_HIDDEN_STEP == 0 and H <= LSTM_MAX_HIDDEN)
+        index = self._native_index() if native else None
+        if index is not None:
+            return (_LSTMAggregateCSR if self.nbr is None else _LSTMAggregate).apply(xg, w_hh, *index)
+        return self.lstm_aggregate_torch(xg, w_hh)
+
+    def lstm_aggregate_torch(self, xg, w_hh):
+        """lstm_aggregate in plain torch, any device and dtype, both block forms: its fallback, and in float64 its reference.  The
+        valid slots of every row are packed to the front of a [num_dst, longest row] table (one host read: its width), then one
+        masked step per column: a row whose slots are used up keeps h and c."""
+        H = self._lstm_args(xg, w_hh)
+        dev = xg.device
+        w_t = w_hh.to(device=dev, dtype=xg.dtype).t()
+        rows, src = self._slots(dev)
+        rows, src = rows[src >= 0], src[src >= 0]
+        counts = torch.bincount(rows, minlength=self.num_dst)
+        rank = torch.arange(rows.numel(), device=dev) - (counts.cumsum(0) - counts)[rows]      # rows ascends in slot order
+        steps = int(counts.max()) if self.num_dst and rows.numel() else 0
+        table = torch.full((self.num_dst, steps), -1, dtype=torch.int64, device=dev)
+        table[rows, rank] = src
+        h = c = xg.new_zeros((self.num_dst, H))
+        for t in range(steps):
+            s = table[:, t]
+            live = (s >= 0).unsqueeze(1)
+            i, f, g, o = (xg[s.clamp_min(0)] + h @ w_t).chunk(4, dim=1)
+            c_new = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+            h = torch.where(live, torch.sigmoid(o) * torch.tanh(c_new), h)
+            c = torch.where(live, c_new, c)
+        return h
 
     def num_src_nodes(self):   # DGL's block API (examples/models.py calls block.num_dst_nodes())
         return self.num_src

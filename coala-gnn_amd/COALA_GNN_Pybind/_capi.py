@@ -200,6 +200,10 @@ SYMBOLS = {
     "coala_block_gather_mm_plan": (_I, [_I, _VP, _VP, _I64, _I, _VP, _VP, _VP, _VP]),
     "coala_block_gather_mm": (_I, [_I] + [_VP] * 7 + [_I64, _I, _I, _I, _I, _VP]),
     "coala_block_gather_mm_backward_w": (_I, [_I] + [_VP] * 7 + [_I64, _I, _I, _I, _VP]),
+    "coala_block_lstm_aggregate": (_I, [_I] + [_VP] * 6 + [_I64, _I, _I, _VP]),
+    "coala_block_lstm_aggregate_csr": (_I, [_I] + [_VP] * 7 + [_I64, _I, _VP]),
+    "coala_block_lstm_aggregate_backward": (_I, [_I] + [_VP] * 7 + [_I64, _I, _I, _VP]),
+    "coala_block_lstm_aggregate_backward_csr": (_I, [_I] + [_VP] * 8 + [_I64, _I, _VP]),
     "coala_shm_open":(_I, [C.c_char_p, _U64, _I, _I, C.POINTER(_VP)]),
     "coala_shm_host_ptr": (_VP, [_VP]),
     "coala_shm_device_ptr": (_VP, [_VP]),

@@ -9,6 +9,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --model_type gcn --edge_weights random --use_edge_weight
   python examples/train_synthetic.py --sampler labor --fan_out 10,10
   python examples/train_synthetic.py --sage_aggregator pool
+  python examples/train_synthetic.py --sage_aggregator lstm --dim 128
   python examples/train_synthetic.py --model_type gin --gin_aggregator max
   python examples/train_synthetic.py --model_type rgcn --num_rels 4 --rgcn_regularizer basis --num_bases 2
   python examples/train_synthetic.py --model_type rgcn --num_rels 4 --sampler rel --rel_fan_out "10,3,0,-1;5,5,5,5"
@@ -264,8 +265,9 @@ def main():
                          "type (--num_rels synthetic types, the source node's id modulo --num_rels; native relation-typed sum); rgat: RelGATConv layers, "
                          "a GATConv of --num_heads heads per edge type, summed (native relation-typed attention); rsage: RelSAGEConv layers, a SAGEConv "
                          "'gcn' per edge type, summed; pinsage: WeightedSAGEConv layers on the visit counts of --sampler pinsage")
-    ap.add_argument("--sage_aggregator", type=str, default="mean", choices=["mean", "gcn", "pool"],
-                    help="aggregator of --model_type sage; pool: the maximum of relu(fc_pool(h)) over the neighbours (native max aggregation)")
+    ap.add_argument("--sage_aggregator", type=str, default="mean", choices=["mean", "gcn", "pool", "lstm"],
+                    help="aggregator of --model_type sage; pool: the maximum of relu(fc_pool(h)) over the neighbours (native max aggregation); "
+                         "lstm: an LSTM over the neighbours in slot order (LSTMSAGEConv, native for feature widths that are multiples of 32 up to 256)")
     ap.add_argument("--gin_aggregator", type=str, default="sum", choices=["sum", "max", "mean"], help="aggregator of --model_type gin")
     ap.add_argument("--seed", type=int, default=0,
                     help="seed of torch's generators, set before the model is built: its initial weights (and dropout masks) are the same "

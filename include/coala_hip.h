@@ -938,6 +938,34 @@ int coala_block_gather_mm(int device, const float* a, const float* w, const int3
                           const int32_t* c_rows, float* c, int64_t M, int T, int K, int N, int transposed, void* stream);
 int coala_block_gather_mm_backward_w(int device, const float* p, const int32_t* p_rows, const float* q, const int32_t* q_rows,
                                      const int32_t* order, const int32_t* seg, float* grad_w, int64_t M, int T, int K, int N, void* stream);
+/* LSTM neighbour aggregation on the fp32 matrix units (DGL's SAGEConv 'lstm', PyG's LSTMAggregation; coala_lstm.hip).  xg fp32
+ * [n_src, 4 H]: the input-side gate pre-activations of every source node, x @ W_ih^T + b_ih + b_hh, torch's gate order i, f, g, o;
+ * w_hh fp32 [4 H, H], torch's weight_hh_l0; out fp32 [n_dst, H], written whole.  Row d starts from h = c = 0 and takes its valid
+ * slots in ascending slot order -- the entries >= 0 of nbr[d, :] (a -1 is skipped wherever it stands), or of
+ * indices[indptr[d] : indptr[d + 1]] -- each with source s as
+ *   z = xg[s] + h @ w_hh^T;  i, f, o = sigmoid(z_i, z_f, z_o);  g = tanh(z_g);  c = f c + i g;  h = o tanh(c);
+ * out[d] is the last h, exact zeros for a row without a valid slot.  Every element of z is one chain of fused multiply-adds over k in a
+ * fixed order from 0, plus xg[s]: bitwise reproducible, the same bits in both forms, independent of the other rows.  A hub row of a
+ * ragged block is walked serially by its 32-row tile.  Any 4-byte aligned pointers.
+ * Saved state, both NULL (nothing of size S is written) or both given: gates fp32 [S, 4 H] and cell fp32 [S, H], S the block's slots
+ * (n_dst * fanout, or indptr[n_dst]): the activated i, f, g, o and c of every valid slot; the rows of -1 slots are not written.
+ * Backward, one launch: grad_out fp32 [n_dst, H]; gates is OVERWRITTEN with dz, the gradient of every slot's z (zeros on -1 slots);
+ * h_prev fp32 [S, H] or NULL receives the h every slot started from (zeros on -1 slots and on a row's first slot), so that
+ * grad_w_hh = dz^T @ h_prev is one dense product for the caller (in slices of S / 64 slots if S is large: one fp32 chain
+ * over all S rounds at the magnitude of the whole sum); grad_xg fp32 [n_src, 4 H] or NULL, zeroed by the caller, gets
+ * grad_xg[s] += dz of every valid slot with source s, with hardware float atomics (the order varies).  A row without a valid slot
+ * sends no gradient.
+ * COALA_EINVAL before any launch: hidden not a multiple of 32 in 32..256 ("bad lstm hidden size"), fan-out outside 1..32, n_dst < 0,
+ * a null required pointer; n_dst == 0 launches nothing.  Indices are not range-checked here (the caller's duty). */
+int coala_block_lstm_aggregate(int device, const int32_t* nbr, const float* xg, const float* w_hh, float* out, float* gates, float* cell,
+                               int64_t n_dst, int fanout, int hidden, void* stream);
+int coala_block_lstm_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* xg, const float* w_hh, float* out,
+                                   float* gates, float* cell, int64_t n_dst, int hidden, void* stream);
+int coala_block_lstm_aggregate_backward(int device, const int32_t* nbr, const float* w_hh, const float* grad_out, float* gates,
+                                        const float* cell, float* h_prev, float* grad_xg, int64_t n_dst, int fanout, int hidden, void* stream);
+int coala_block_lstm_aggregate_backward_csr(int device, const int64_t* indptr, const int32_t* indices, const float* w_hh,
+                                            const float* grad_out, float* gates, const float* cell, float* h_prev, float* grad_xg,
+                                            int64_t n_dst, int hidden, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Shared pinned-host ("UVA") region.  Replaces SharedUVAManager (COALA_GNN_Modules/shared_UVA.cuh:26-115):
