@@ -1,7 +1,8 @@
 """Autograd wrappers of the native block ops that `Block` (sampler.py) hands to a model: mean aggregation (SAGEConv's "mean"), weighted
 sum aggregation (DGL's u_mul_e_sum, the edge_weight= path of GraphConv / SAGEConv), max aggregation (DGL's fn.max: SAGEConv's "pool",
 GINConv's "max"), LSTM aggregation (SAGEConv's "lstm": coala_lstm.hip, on the matrix units), the relation-typed sum (RelGraphConv's message step), GAT / GATv2 attention aggregation, scaled dot-product
-attention (DotGatConv's and HGTConv's message step) and relation-typed GAT attention (RelGATConv's message step), on fixed blocks and on the ragged CSR blocks of full layers.  pair_dot (DGL's u_dot_v on a pair graph: a link predictor's scores) is the one op here
+attention (DotGatConv's and HGTConv's message step), temporal attention over a fused time encoding (TGATConv's message step, fixed
+blocks alone) and relation-typed GAT attention (RelGATConv's message step), on fixed blocks and on the ragged CSR blocks of full layers.  pair_dot (DGL's u_dot_v on a pair graph: a link predictor's scores) is the one op here
 that takes no block.  One kernel forward, one backward each; the kernels are in coala-gnn_amd/csrc/coala_block_ops.hip
 (C ABI: coala_block_*).  Every op has one forward and one backward body for both block forms, which take the C entry and the block's
 index tensors -- (nbr,) or (indptr, indices); the two Function classes of an op are shells that name the entries, and they stay two
@@ -534,6 +535,59 @@ class _DotGatAggregateCSR(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         return _dot_gat_backward(ctx, grad_out, _lib.coala_block_dot_gat_aggregate_csr_backward) + (None,) * 4
+
+
+def _time_attn_parts(n_dst):
+    """Rows of the grad_omega / grad_phase partials buffer, which is also the backward's grid: one block per four destination rows, 1024
+    at the most (_gatv2_parts' rule)."""
+    return max(1, min(-(-n_dst // 4), 1024))
+
+
+class _TimeAttnAggregate(torch.autograd.Function):
+    """Temporal attention on a fixed block (coala_block_time_attn_aggregate): per head, a softmax over row d's valid slots of
+    scale * (<q[d], k[s]> + <qt[d], cos(omega * dt + phase)>), then out = the weighted sum of v[s] and tagg = the weighted sum of the
+    time encodings; no [E, T] or [E, H, D] intermediate.  One kernel forward, one backward: gradients for q, k, v, qt, omega and phase
+    (the last two as [parts, 2, T] partial sums, one row per block of the launch, summed here), none for dt; a gradient nobody asked for
+    is neither computed nor allocated."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, qt, omega, phase, dt, scale, nbr):
+        qc, kc, vc, tc, om, ph = (t.contiguous() for t in (q, k, v, qt, omega, phase))
+        n_dst, fan = nbr.shape
+        H, D, T = kc.shape[1], kc.shape[2], tc.shape[2]
+        out = torch.empty((n_dst, H, D), dtype=torch.float32, device=kc.device)
+        tagg = torch.empty((n_dst, H, T), dtype=torch.float32, device=kc.device)
+        lse = torch.empty((n_dst, H), dtype=torch.float32, device=kc.device)
+        _capi.check(_lib.coala_block_time_attn_aggregate(kc.device.index or 0, nbr.data_ptr(), dt.data_ptr(), qc.data_ptr(), kc.data_ptr(),
+                                                         vc.data_ptr(), tc.data_ptr(), om.data_ptr(), ph.data_ptr(), out.data_ptr(),
+                                                         tagg.data_ptr(), lse.data_ptr(), n_dst, fan, H, D, T, scale, current_stream()))
+        if any(ctx.needs_input_grad[:6]):
+            ctx.save_for_backward(qc, kc, vc, tc, om, ph, dt, out, tagg, lse, nbr)
+        ctx.scale = scale
+        return out, tagg
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_tagg):
+        need = ctx.needs_input_grad[:6]
+        if not any(need):
+            return (None,) * 9
+        q, k, v, qt, om, ph, dt, out, tagg, lse, nbr = ctx.saved_tensors
+        n_dst, fan = nbr.shape
+        H, D, T = k.shape[1], k.shape[2], qt.shape[2]
+        g, gt = grad_out.contiguous(), grad_tagg.contiguous()
+        grad_q = torch.empty_like(q) if need[0] else None
+        grad_k = torch.zeros_like(k) if need[1] else None
+        grad_v = torch.zeros_like(v) if need[2] else None
+        grad_qt = torch.empty_like(qt) if need[3] else None
+        parts = _time_attn_parts(n_dst)
+        partials = (torch.zeros if n_dst == 0 else torch.empty)((parts, 2, T), dtype=torch.float32, device=k.device) if need[4] or need[5] else None
+        _capi.check(_lib.coala_block_time_attn_aggregate_backward(
+            k.device.index or 0, nbr.data_ptr(), dt.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), qt.data_ptr(), om.data_ptr(),
+            ph.data_ptr(), out.data_ptr(), tagg.data_ptr(), lse.data_ptr(), g.data_ptr(), gt.data_ptr(), _ptr(grad_q), _ptr(grad_k), _ptr(grad_v),
+            _ptr(grad_qt), _ptr(partials), parts, n_dst, fan, H, D, T, ctx.scale, current_stream()))
+        sums = partials.sum(0) if partials is not None else None
+        return (grad_q, grad_k, grad_v, grad_qt, sums[0].view_as(om) if need[4] else None, sums[1].view_as(ph) if need[5] else None, None, None,
+                None)
 
 
 class _PairDot(torch.autograd.Function):

@@ -10,14 +10,16 @@ native relation-typed sum (Block.rel_sum_aggregate).  RGAT and RSAGE (--model_ty
 the same way, on RelGATConv (the native relation-typed attention, Block.rel_gat_aggregate) and RelSAGEConv.  HGT (--model_type hgt) is the
 Heterogeneous Graph Transformer on HGTConv layers, and DotGAT is GAT's shape on DotGatConv layers; both attend with the native scaled
 dot-product kernel (Block.dot_gat_aggregate).  PinSAGE (--model_type pinsage) is the network of DGL's PinSAGE example on WeightedSAGEConv
-layers, for blocks sampled by random walks (RandomWalkNeighborSampler): the visit counts weigh the neighbours."""
+layers, for blocks sampled by random walks (RandomWalkNeighborSampler): the visit counts weigh the neighbours.  TGAT (--model_type tgat) is
+temporal graph attention on TGATConv layers, for blocks sampled by TemporalNeighborSampler: attention over the neighbours' rows and the
+time encoding of block.edata['dt'], on the native temporal attention kernel (Block.time_attn_aggregate)."""
 import time
 
 import torch
 
-from .nn import DotGatConv, DotPredictor, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, LSTMSAGEConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv, WeightedSAGEConv
+from .nn import DotGatConv, DotPredictor, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, LSTMSAGEConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv, TGATConv, WeightedSAGEConv
 
-__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "PinSAGE", "LinkPredictor", "link_loss", "train_steps", "FlatGradAllReduce"]
+__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "PinSAGE", "TGAT", "LinkPredictor", "link_loss", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -301,6 +303,27 @@ class PinSAGE(torch.nn.Module):
             if self.weight_key not in block.edata:
                 raise ValueError(f"PinSAGE needs block.edata[{self.weight_key!r}]: sample the blocks with RandomWalkNeighborSampler")
             h = layer(block, (h, block.dst_rows(h)), block.edata[self.weight_key])
+        return self.linear(h)
+
+
+class TGAT(torch.nn.Module):
+    """Temporal graph attention (Xu et al.'s TGAT) on blocks sampled by TemporalNeighborSampler with edge ids: num_layers TGATConv layers
+    of h_feats features and num_heads heads, every one attending over its neighbours' rows and the time encoding of block.edata['dt'] *
+    time_scale, with a Linear(h_feats, num_classes) on top.  Every layer ends in TGAT's merge MLP, so nothing stands between the layers."""
+
+    def __init__(self, in_feats, h_feats, num_classes, num_layers=2, num_heads=2, time_dim=100, time_scale=1.0, dropout=0.0):
+        super().__init__()
+        dims = [in_feats] + [h_feats] * (num_layers - 1)
+        self.layers = torch.nn.ModuleList(TGATConv(dims[i], h_feats, num_heads, time_dim, time_scale=time_scale, feat_drop=dropout)
+                                          for i in range(num_layers))
+        self.linear = torch.nn.Linear(h_feats, num_classes)
+
+    def forward(self, blocks, x):
+        h = x
+        for layer, block in zip(self.layers, blocks):
+            if "dt" not in block.edata:
+                raise ValueError("TGAT needs block.edata['dt']: sample the blocks with TemporalNeighborSampler(edge_ids=True)")
+            h = layer(block, (h, block.dst_rows(h)))
         return self.linear(h)
 
 

@@ -18,12 +18,14 @@ matrices per (source, relation) pair, not per edge, and folds the relation prior
 WeightedSAGEConv is the layer of DGL's PinSAGE example on blocks sampled by random walks (RandomWalkNeighborSampler): the visit counts
 in block.edata['weights'] weigh the neighbours' rows through Block.weighted_sum_aggregate.
 LSTMSAGEConv is DGL's SAGEConv with aggregator_type='lstm' as a class of its own: the recurrence over a destination's neighbours is
-Block.lstm_aggregate, a native kernel on the matrix units, and the input projection is made once per source node."""
+Block.lstm_aggregate, a native kernel on the matrix units, and the input projection is made once per source node.
+TGATConv is TGAT's temporal attention layer on the blocks of TemporalNeighborSampler: attention over [h_src || Phi(dt)] with the learnable
+time encoding TimeEncode, whose attention step is Block.time_attn_aggregate, a native kernel that computes Phi(dt) in registers."""
 import torch
 
 from .block_ops import gather_mm
 
-__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "LSTMSAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv", "TypedLinear", "DotPredictor"]
+__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "LSTMSAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv", "TypedLinear", "DotPredictor", "TimeEncode", "TGATConv"]
 
 
 class GATConv(torch.nn.Module):
@@ -650,6 +652,73 @@ class DotGatConv(torch.nn.Module):
         else:
             q = fc_dst(h_dst).view(-1, H, D)
         return block.dot_gat_aggregate(q, k, k, scale=float(D) ** -0.5)
+
+
+class TimeEncode(torch.nn.Module):
+    """TGAT's learnable time encoding (Xu et al., "Inductive Representation Learning on Temporal Graphs"; TGN's TimeEncoder):
+    Phi(dt)[t] = cos(omega[t] * dt + phase[t]).  omega starts at 1 / 10 ** linspace(0, 9, dim) and phase at 0, as in the TGAT code; both
+    are learnable.  forward(dt [...]) -> [..., dim] is the dense form, for use outside blocks: on a block TGATConv hands omega and phase
+    to Block.time_attn_aggregate, which never writes Phi."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.omega = torch.nn.Parameter(1.0 / 10.0 ** torch.linspace(0, 9, dim))
+        self.phase = torch.nn.Parameter(torch.zeros(dim))
+
+    def forward(self, dt):
+        return torch.cos(dt.to(self.omega.dtype).unsqueeze(-1) * self.omega + self.phase)
+
+
+class TGATConv(torch.nn.Module):
+    """TGAT's temporal attention layer on a block of TemporalNeighborSampler (the attention of TGN's embedding module is the same step).
+    forward(block, feat, dt=None) -> [num_dst, out_feats]; feat is h_src or (h_src, h_dst); dt is one time gap per neighbour slot,
+    block.edata['dt'] by default, multiplied by time_scale (timestamps in other units than the encoder's frequencies expect).  With
+    H = num_heads, D = out_feats / H, Phi = time_encoder, for destination d and its sampled edges j (source s_j, time gap dt_j):
+        q[d] = w_q [h_dst[d] || Phi(0)]      k_j = w_k [h_src[s_j] || Phi(dt_j)]      v_j = w_v [h_src[s_j] || Phi(dt_j)]      (H heads of D)
+        a_j = softmax over d's edges of <q[d, h], k_j[h]> / sqrt(D);      attn[d, h, :] = sum_j a_j v_j[h]
+        out[d] = fc2(relu(fc1([attn[d] || h_dst[d]])))                       TGAT's merge layer
+    k_j and v_j are never formed per edge: w_k = [W_kx | W_kt] and w_v = [W_vx | W_vt] are split by input, W_kx h_src and W_vx h_src are
+    projected once per source node, the time part of the score is <W_kt[h]^T q[d, h], Phi(dt_j)>, and that of the value W_vt[h] applied
+    to sum_j a_j Phi(dt_j), which Block.time_attn_aggregate returns beside the attention output: a native kernel that computes Phi in
+    registers.  Parameters: w_q, w_k, w_v [out_feats, in_feats + time_dim], no bias (the linear maps of TGAT's MultiHeadAttention),
+    Xavier-uniform; time_encoder.omega / .phase; fc1 Linear(out_feats + in_feats, out_feats), fc2 Linear(out_feats, out_feats).  A
+    destination without an edge attends to nothing: attn is zero.  TGAT's output projection, layer norm and attention dropout, and edge
+    features beside the time encoding, are not provided."""
+
+    def __init__(self, in_feats, out_feats, num_heads, time_dim, time_scale=1.0, feat_drop=0.0):
+        super().__init__()
+        if out_feats % num_heads:
+            raise ValueError(f"out_feats {out_feats} is not a multiple of num_heads {num_heads}")
+        self._in_feats, self._num_heads, self._head_feats, self.time_scale = in_feats, num_heads, out_feats // num_heads, float(time_scale)
+        self.time_encoder = TimeEncode(time_dim)
+        self.w_q = torch.nn.Parameter(torch.empty(out_feats, in_feats + time_dim))
+        self.w_k = torch.nn.Parameter(torch.empty(out_feats, in_feats + time_dim))
+        self.w_v = torch.nn.Parameter(torch.empty(out_feats, in_feats + time_dim))
+        self.fc1 = torch.nn.Linear(out_feats + in_feats, out_feats)
+        self.fc2 = torch.nn.Linear(out_feats, out_feats)
+        self.feat_drop = torch.nn.Dropout(feat_drop)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for w in (self.w_q, self.w_k, self.w_v):
+            torch.nn.init.xavier_uniform_(w)
+        self.fc1.reset_parameters()
+        self.fc2.reset_parameters()
+
+    def forward(self, block, feat, dt=None):
+        h_src, h_dst = feat if isinstance(feat, (tuple, list)) else (feat, None)
+        h_src = self.feat_drop(h_src)
+        h_dst = block.dst_rows(h_src) if h_dst is None else self.feat_drop(h_dst)
+        F, H, D = self._in_feats, self._num_heads, self._head_feats
+        enc = self.time_encoder
+        dt = (block.edata["dt"] if dt is None else dt).to(h_src.dtype) * self.time_scale
+        q = (h_dst @ self.w_q[:, :F].t() + torch.cos(enc.phase) @ self.w_q[:, F:].t()).view(-1, H, D)   # w_q [h_dst || Phi(0)]
+        k = (h_src @ self.w_k[:, :F].t()).view(-1, H, D)
+        v = (h_src @ self.w_v[:, :F].t()).view(-1, H, D)
+        qt = torch.einsum("nhd,hdt->nht", q, self.w_k[:, F:].view(H, D, -1))
+        out, tagg = block.time_attn_aggregate(q, k, v, qt, dt, enc.omega, enc.phase)
+        attn = out + torch.einsum("nht,hdt->nhd", tagg, self.w_v[:, F:].view(H, D, -1))
+        return self.fc2(torch.relu(self.fc1(torch.cat([attn.flatten(1), h_dst], dim=1))))
 
 
 def _typed_linear(x, W, types, counts):

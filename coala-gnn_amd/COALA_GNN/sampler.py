@@ -12,7 +12,8 @@ import torch
 from COALA_GNN_Pybind import _capi, current_stream
 
 from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
-                        _MeanAggregateCSR, _LSTMAggregate, _LSTMAggregateCSR, LSTM_HIDDEN_STEP, LSTM_MAX_HIDDEN, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _WeightedSum, _WeightedSumCSR)
+                        _MeanAggregateCSR, _LSTMAggregate, _LSTMAggregateCSR, LSTM_HIDDEN_STEP, LSTM_MAX_HIDDEN, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _TimeAttnAggregate,
+                        _WeightedSum, _WeightedSumCSR)
 
 __all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "RandomWalkNeighborSampler", "PinSAGESampler", "random_walk", "sort_csc_by_etype",
            "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT", "EID", "EdgePredictionSampler", "as_edge_prediction_sampler",
@@ -775,6 +776,62 @@ class Block(object):
         a = p / l[dst]
         out = torch.zeros((self.num_dst,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev)
         return out.index_add(0, dst, a.unsqueeze(-1).to(v.dtype) * v[row])
+
+    def _time_attn_args(self, q, k, v, qt, dt, omega, phase, scale):
+        """The checks of time_attn_aggregate / time_attn_aggregate_torch -> the scale as a float (None: D ** -0.5)."""
+        slots = self.indices if self.nbr is None else self.nbr
+        ok = (k.dim() == 3 and tuple(v.shape) == tuple(k.shape) and k.shape[0] == self.num_src and tuple(q.shape) == (self.num_dst,) + tuple(k.shape[1:])
+              and qt.dim() == 3 and tuple(qt.shape[:2]) == (self.num_dst, k.shape[1]) and omega.dim() == 1 and omega.shape[0] == qt.shape[2] >= 1
+              and tuple(phase.shape) == tuple(omega.shape))
+        if not ok:
+            raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, qt {tuple(qt.shape)}, omega {tuple(omega.shape)}, "
+                             f"phase {tuple(phase.shape)}: this block takes [{self.num_dst}, H, D], [{self.num_src}, H, D] twice, "
+                             f"[{self.num_dst}, H, T], [T] and [T]")
+        if tuple(dt.shape) != tuple(slots.shape) or dt.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise ValueError(f"dt of shape {tuple(dt.shape)} and dtype {dt.dtype}: this block takes one number per neighbour slot, {tuple(slots.shape)}")
+        return float(k.shape[2]) ** -0.5 if scale is None else float(scale)
+
+    def time_attn_aggregate(self, q, k, v, qt, dt, omega, phase, scale=None):
+        """Temporal attention (TGAT's attention step; the embedding module of TGN, PyG's TransformerConv(edge_dim=) over a TimeEncoder):
+        dot-product attention over keys and values [h_src || Phi(dt)], Phi(dt)[t] = cos(omega[t] * dt + phase[t]), with the key and value
+        projections split by input, W_k = [W_kx | W_kt] and W_v = [W_vx | W_vt].  q is [num_dst, H, D]; k = W_kx h_src and v = W_vx h_src are
+        [num_src, H, D], projected once per source node; qt[d, h, :] = W_kt[h]^T q[d, h, :] is [num_dst, H, T]; dt has one number per
+        neighbour slot (block.edata['dt'] of TemporalNeighborSampler, times a scale of the caller's; any integer or float dtype, not
+        read in a padding slot); omega and phase are [T].  For dst node d, head h and d's slots j with an edge (source s_j, phi_j = Phi(dt_j)):
+            e_j = scale * (<q[d, h], k[s_j, h]> + <qt[d, h], phi_j>),  a = softmax_j(e),  scale=None means D ** -0.5
+            out[d, h, :] = sum_j a_j v[s_j, h, :]      tagg[d, h, :] = sum_j a_j phi_j
+        -> (out [num_dst, H, D], tagg [num_dst, H, T]); the value side's time part is einsum(tagg, W_vt), added by the caller.  A dst node
+        without an edge gets zeros in both and sends no gradient.  Gradients for q, k, v, qt, omega and phase, none for dt.  Native kernels
+        (one forward, one backward, Phi never in memory) for fp32 GPU tensors on a fixed-stride block of fan-out <= 64 with H <= 16 and
+        T <= 128; time_attn_aggregate_torch otherwise (a ragged block, other dtypes, the CPU, T > 128)."""
+        scale = self._time_attn_args(q, k, v, qt, dt, omega, phase, scale)
+        native = (all(t.is_cuda and t.dtype == torch.float32 for t in (q, k, v, qt, omega, phase)) and dt.is_cuda and self.nbr is not None
+                  and self.nbr.is_cuda and self.nbr.is_contiguous() and 1 <= self.nbr.shape[1] <= 64 and 0 < k.shape[1] <= 16 and k.shape[2] > 0
+                  and qt.shape[2] <= 128 and 0 < k.shape[0] < (1 << 31))
+        if not native:
+            return self.time_attn_aggregate_torch(q, k, v, qt, dt, omega, phase, scale)
+        return _TimeAttnAggregate.apply(q, k, v, qt, omega, phase, dt.to(torch.float32).contiguous(), scale, self.nbr)
+
+    def time_attn_aggregate_torch(self, q, k, v, qt, dt, omega, phase, scale=None):
+        """time_attn_aggregate in plain torch, any device and dtype, both block forms: an edge-list softmax that materialises Phi(dt) as
+        [E, T], the gathered [E, H, D] rows of k and v and the [E, H, T] products with qt and the weights.  The fallback of
+        time_attn_aggregate, and its reference."""
+        scale = self._time_attn_args(q, k, v, qt, dt, omega, phase, scale)
+        dev = k.device
+        dst, src = self._slots(dev)
+        keep = src >= 0
+        dst, src = dst[keep], src[keep]
+        phi = torch.cos(dt.reshape(-1).to(device=dev, dtype=k.dtype)[keep].unsqueeze(1) * omega + phase)   # [E, T]
+        H = k.shape[1]
+        e = ((q[dst] * k[src]).sum(-1) + (qt[dst] * phi.unsqueeze(1)).sum(-1)) * scale            # [E, H]
+        m = torch.full((self.num_dst, H), float("-inf"), dtype=e.dtype, device=dev)
+        m = m.scatter_reduce(0, dst.unsqueeze(1).expand(-1, H), e.detach(), "amax").detach()      # the shift cancels in the softmax
+        p = torch.exp(e - m[dst])
+        l = torch.zeros((self.num_dst, H), dtype=e.dtype, device=dev).index_add(0, dst, p)
+        a = p / l[dst]
+        out = torch.zeros((self.num_dst,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev).index_add(0, dst, a.unsqueeze(-1).to(v.dtype) * v[src])
+        tagg = torch.zeros((self.num_dst, H, phi.shape[1]), dtype=phi.dtype, device=dev).index_add(0, dst, a.unsqueeze(-1) * phi.unsqueeze(1))
+        return out, tagg
 
     def _exclude_args(self, eids):
         """The checks of exclude_edges / exclude_edges_torch -> the block's edge ids."""

@@ -1,7 +1,8 @@
 // coala_block_ops.hip -- what a model computes on a sampled block (coala_sampler.hip makes the blocks), for gfx950: mean aggregation
 // (DGL's SAGEConv "mean"), weighted sum aggregation (DGL's u_mul_e_sum: GraphConv / SAGEConv with edge_weight=), max aggregation
 // (DGL's fn.max: SAGEConv "pool", GINConv "max"), the relation-typed sum (RelGraphConv's message step), GAT / GATv2 attention
-// aggregation (GATConv's and GATv2Conv's message steps), scaled dot-product attention (DotGatConv's and HGTConv's message step) and
+// aggregation (GATConv's and GATv2Conv's message steps), scaled dot-product attention (DotGatConv's and HGTConv's message step), temporal
+// attention over a fused time encoding (TGATConv's message step; fixed blocks alone) and
 // relation-typed GAT attention (a softmax per destination and relation), forward and backward, on fixed blocks (nbr_local[n_dst, fanout], -1 = no
 // neighbour) and on the CSR blocks of full layers; and, for link prediction, edge exclusion on both block forms and the dot-product
 // scores of node pairs (forward and backward).  Stateless entry points: no handle, every launch on the caller's stream.
@@ -743,6 +744,242 @@ __global__ __launch_bounds__(kBlock) void dot_gat_aggregate_backward_kernel(cons
     }
 }
 
+// Temporal attention on a fixed block (TGAT's attention step, and TGN's embedding module: PyG's TransformerConv(edge_dim=) over a time
+// encoding): dot-product attention whose keys and values carry phi_j[t] = cos(omega[t] dt_j + phase[t]), the time encoding of slot j's
+// time gap dt_j, beside the source's row.  With the key and value projections split by input the time part enters the score through a
+// vector per destination, qt[d, h, :] = W_kt[h]^T q[d, h, :], and leaves as a second output, so for dst d, head h and the slots j of d with nbr >= 0:
+//   e_j = scale (<q[d, h, :], k[s_j, h, :]> + <qt[d, h, :], phi_j>),  a_j = softmax of e over the row,
+//   out[d, h, :] = sum_j a_j v[s_j, h, :],  tagg[d, h, :] = sum_j a_j phi_j
+// phi is never in memory.  A temporal block is fixed-stride, so a row is one chunk of at most 64 slots and the softmax needs no
+// rescale.  The two sums over phi take opposite lane mappings, so that neither reduces across lanes:
+//   score: a lane per slot.  Loop over t; omega[t], phase[t] and qt[d, h, t] are the same in every lane (scalar loads: the row's
+//     address is made wave-uniform for the compiler), one cos per (slot, t), an fma per head into the lane's registers.  <q, k_j> is
+//     dot_score_pass's; dot_score scales the finished sum of the two, in both directions.
+//   tagg: a lane per time channel, 64 at a time.  Loop over the row's slots, dt_j broadcast by shuffle, the weights read from the LDS
+//     [slot][head] array, phi_j[t] computed a second time (a row's phi, up to 64 x 128 floats a wave, does not fit the LDS of four
+//     waves beside the weights), an accumulator per head, stored once.
+// The argument is formed in fp32 as the rounded product plus the phase (torch's omega * dt + phase), and cos / sin are the accurate
+// library functions: arguments of 1e3 .. 1e4 are ordinary here, where the error of the fast ones is that of the argument's size.
+__device__ __forceinline__ float time_arg(float omega, float dt, float phase) {
+#pragma clang fp contract(off)
+    return omega * dt + phase;
+}
+
+// x is the same in every lane: say so, and what it addresses is read by scalar loads.
+__device__ __forceinline__ int64_t wave_uniform(int64_t x) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// A lane's slot: te[h] = <qt_row[h, :], phi>, with DOT also tr[h] = <gt_row[h, :], phi>, phi[t] = cos(omega[t] dt + phase[t]); every
+// head's sum runs over t in order, one fma per term, so the backward's te is the forward's bit for bit.  heads <= HB.
+template <int HB, bool DOT>
+__device__ __forceinline__ void time_score_pass(float (&te)[HB], float (&tr)[HB], float dt, const float* __restrict__ qt_row,
+                                                const float* __restrict__ gt_row, const float* __restrict__ omega,
+                                                const float* __restrict__ phase, int heads, int tdim) {
+#pragma unroll
+    for (int h = 0; h < HB; ++h) te[h] = tr[h] = 0.0f;
+    for (int t = 0; t < tdim; ++t) {
+        const float phi = cosf(time_arg(omega[t], dt, phase[t]));
+#pragma unroll
+        for (int h = 0; h < HB; ++h) {
+            if (h < heads) { // wave-uniform
+                te[h] = __builtin_fmaf(qt_row[h * tdim + t], phi, te[h]);
+                if (DOT) tr[h] = __builtin_fmaf(gt_row[h * tdim + t], phi, tr[h]);
+            }
+        }
+    }
+}
+
+// HB: the head count rounded up to 1, 2, 4, 8 or 16, the length of the per-head register arrays.
+template <int HB, int VEC>
+__global__ __launch_bounds__(kBlock) void time_attn_aggregate_kernel(const int32_t* __restrict__ nbr, const float* __restrict__ dt, int fanout,
+                                                                     const float* __restrict__ q, const float* __restrict__ k,
+                                                                     const float* __restrict__ v, const float* __restrict__ qt,
+                                                                     const float* __restrict__ omega, const float* __restrict__ phase,
+                                                                     float* __restrict__ out, float* __restrict__ tagg, float* __restrict__ lse,
+                                                                     int64_t n_dst, int heads, int dim, int tdim, float scale) {
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];
+    __shared__ float st_lds[kWavesPerBlock][3 * kGatMaxHeads];
+    const auto [lane, wave, n_waves] = wave_rows();
+    const SoftmaxLds s = softmax_lds(w_lds[threadIdx.x >> 6], st_lds[threadIdx.x >> 6]);
+    const int hd = heads * dim, ht = heads * tdim, units = hd / VEC, upl = dim / VEC;
+    for (int64_t d0 = wave; d0 < n_dst; d0 += n_waves) {
+        const int64_t d = wave_uniform(d0);
+        const int64_t beg = d * fanout;
+        int32_t mine;
+        const int n = load_chunk(nbr, beg, beg + fanout, lane, &mine);
+        const float dtj = lane < fanout ? dt[beg + lane] : 0.0f;
+        softmax_row_begin(s, lane, heads);
+        wave_lds_sync(); // m_run / l_run are set
+        score_pass_chunk<DotScore, false>(s.w, nullptr, mine, n, q, k, v, d, nullptr, lane, heads, hd, dim, scale);
+        float te[HB], unused[HB];
+        time_score_pass<HB, false>(te, unused, dtj, qt + d * ht, nullptr, omega, phase, heads, tdim);
+#pragma unroll
+        for (int h = 0; h < HB; ++h) {
+            if (h < heads) // wave-uniform: softmax_chunk_step shuffles across every lane
+                softmax_chunk_step(s, h, mine >= 0 ? dot_score(scale, s.w[lane * kGatMaxHeads + h] + te[h]) : kNegInf, mine >= 0, lane);
+        }
+        wave_lds_sync();
+        softmax_accumulate<VEC, false>(s, out + d * hd, v, mine, n, true, true, lane, hd, units, upl);
+        for (int t0 = 0; t0 < tdim; t0 += 64) { // wave-uniform trip count: the shuffles below need every lane
+            const int t = t0 + lane;
+            const float om = t < tdim ? omega[t] : 0.0f, ph = t < tdim ? phase[t] : 0.0f;
+            float acc[HB];
+#pragma unroll
+            for (int h = 0; h < HB; ++h) acc[h] = 0.0f;
+            for (int j = 0; j < n; ++j) {
+                const int32_t src = __shfl(mine, j);
+                const float dj = __shfl(dtj, j);
+                if (src < 0) continue; // wave-uniform
+                const float phi = cosf(time_arg(om, dj, ph));
+#pragma unroll
+                for (int h = 0; h < HB; ++h)
+                    if (h < heads) acc[h] = __builtin_fmaf(s.w[j * kGatMaxHeads + h], phi, acc[h]);
+            }
+#pragma unroll
+            for (int h = 0; h < HB; ++h)
+                if (h < heads && t < tdim) tagg[d * ht + h * tdim + t] = acc[h] * (s.l_run[h] > 0.0f ? 1.0f / s.l_run[h] : 0.0f);
+        }
+        softmax_row_end<VEC>(s, out + d * hd, lse + d * heads, false, lane, heads, units);
+    }
+}
+
+// Temporal attention backward, every gradient in one launch, each of them optional (null).  gout[h] = <g_out[h], out[d, h]> +
+// <g_tagg[h], tagg[d, h]>; the score pass gives <q, k_j> and <g_out, v_j> again, the time pass <qt, phi_j> and <g_tagg, phi_j>; per slot
+// and head a_j = exp(e_j - lse[d, h]) / S (`normalised`), e_j the forward's bit for bit, and t_j = a_j (<g_out, v_j> + <g_tagg, phi_j> -
+// gout).  Then the dot-product backward's walk over the chunk's rows, a lane per float c:
+//   grad_v[s_j, c] += a_j g_out[d, c]   grad_k[s_j, c] += scale t_j q[d, c]   (float atomics)   grad_q[d, c] = scale sum_j t_j k[s_j, c]
+// and the time walk, a lane per time channel t, over the row's slots with sin and cos of the slot's argument:
+//   grad_qt[d, h, t] = scale sum_j t_j[h] phi_j[t]      an accumulator per head, stored once;
+//   dphi = sum_h (a_j[h] g_tagg[d, h, t] + scale t_j[h] qt[d, h, t]),  grad_phase[t] += -sin dphi,  grad_omega[t] += -sin dt_j dphi
+//     in two registers per 64 channels over ALL rows the wave takes; at the end the block's waves are summed through LDS in wave order
+//     and block b stores row b of the partials [gridDim.x, 2, tdim] (omega's row, then phase's), which the caller sums: GATv2's
+//     grad_attn scheme.  No atomics, and the same grid gives the same bits.
+constexpr int kTimeMaxDim = 128, kTimePasses = kTimeMaxDim / 64;
+
+template <int HB>
+__global__ __launch_bounds__(kBlock) void time_attn_aggregate_backward_kernel(
+    const int32_t* __restrict__ nbr, const float* __restrict__ dt, int fanout, const float* __restrict__ q, const float* __restrict__ k,
+    const float* __restrict__ v, const float* __restrict__ qt, const float* __restrict__ omega, const float* __restrict__ phase,
+    const float* __restrict__ out, const float* __restrict__ tagg, const float* __restrict__ lse, const float* __restrict__ grad_out,
+    const float* __restrict__ grad_tagg, float* __restrict__ grad_q, float* __restrict__ grad_k, float* __restrict__ grad_v,
+    float* __restrict__ grad_qt, float* __restrict__ grad_time_parts, int64_t n_dst, int heads, int dim, int tdim, float scale) {
+    __shared__ float w_lds[kWavesPerBlock][64 * kGatMaxHeads];   // the chunk's dot products <q, k_j>, then a_j, [slot][head]
+    __shared__ float dot_lds[kWavesPerBlock][64 * kGatMaxHeads]; // <g_out, v_j>, then t_j, [slot][head]
+    __shared__ float hs_lds[kWavesPerBlock][2 * kGatMaxHeads];   // per head: gout (and backward_row_front's S, unused: one chunk)
+    static_assert(2 * kTimeMaxDim <= 64 * kGatMaxHeads, "the waves' grad_omega / grad_phase sums are combined through w_lds");
+    const auto [lane, wave, n_waves] = wave_rows();
+    float* w = w_lds[threadIdx.x >> 6];
+    float* dot = dot_lds[threadIdx.x >> 6];
+    float* gout = hs_lds[threadIdx.x >> 6];
+    const int hd = heads * dim, ht = heads * tdim;
+    float g_om[kTimePasses], g_ph[kTimePasses];
+#pragma unroll
+    for (int p = 0; p < kTimePasses; ++p) g_om[p] = g_ph[p] = 0.0f;
+    for (int64_t d0 = wave; d0 < n_dst; d0 += n_waves) {
+        const int64_t d = wave_uniform(d0);
+        const int64_t beg = d * fanout;
+        const float* g = grad_out + d * hd;
+        const float* gt = grad_tagg + d * ht;
+        const float* qd = q + d * hd;
+        int32_t mine;
+        const int n = load_chunk(nbr, beg, beg + fanout, lane, &mine);
+        const float dtj = lane < fanout ? dt[beg + lane] : 0.0f;
+        backward_row_front<DotScore>(w, gout, gout + kGatMaxHeads, nbr, beg, beg + fanout, q, k, v, out + d * hd, lse + d * heads, g, d, lane, heads,
+                                     hd, dim, scale);
+        wave_lds_sync();
+        head_dots(gout, gt, tagg + d * ht, lane, tdim, ht);
+        wave_lds_sync(); // the previous row has read w and dot
+        score_pass_chunk<DotScore, true>(w, dot, mine, n, q, k, v, d, g, lane, heads, hd, dim, scale);
+        float te[HB], tr[HB];
+        time_score_pass<HB, true>(te, tr, dtj, qt + d * ht, gt, omega, phase, heads, tdim);
+#pragma unroll
+        for (int h = 0; h < HB; ++h) { // lane j reads and rewrites only slot j's words
+            if (h < heads) {           // wave-uniform: wave_sum shuffles across every lane
+                float a = 0.0f, t = 0.0f;
+                if (mine >= 0) a = expf(dot_score(scale, w[lane * kGatMaxHeads + h] + te[h]) - lse[d * heads + h]);
+                a = normalised(a, wave_sum(a));
+                if (mine >= 0) t = a * (dot[lane * kGatMaxHeads + h] + tr[h] - gout[h]);
+                w[lane * kGatMaxHeads + h] = a;
+                dot[lane * kGatMaxHeads + h] = t;
+            }
+        }
+        wave_lds_sync();
+        for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: the shuffles below need every lane
+            const int c = c0 + lane;
+            const bool in = c < hd;
+            const int hc = in ? c / dim : 0;
+            const float gc = in ? g[c] : 0.0f;
+            const float qc = in ? qd[c] : 0.0f;
+            float gq = 0.0f;
+            for (int j = 0; j < n; ++j) {
+                const int32_t s = __shfl(mine, j);
+                if (s >= 0 && in) { // every lane takes the shuffle above
+                    const float tj = dot[j * kGatMaxHeads + hc];
+                    if (grad_v) unsafeAtomicAdd(grad_v + (int64_t)s * hd + c, w[j * kGatMaxHeads + hc] * gc);
+                    if (grad_k) unsafeAtomicAdd(grad_k + (int64_t)s * hd + c, scale * tj * qc);
+                    if (grad_q) gq = __builtin_fmaf(tj, k[(int64_t)s * hd + c], gq);
+                }
+            }
+            if (in && grad_q) grad_q[d * hd + c] = scale * gq;
+        }
+        if (!grad_qt && !grad_time_parts) continue; // grid-uniform
+#pragma unroll
+        for (int p = 0; p < kTimePasses; ++p) {
+            if (p * 64 >= tdim) break; // wave-uniform
+            const int t = p * 64 + lane;
+            const bool in = t < tdim;
+            const float om = in ? omega[t] : 0.0f, ph = in ? phase[t] : 0.0f;
+            float qtr[HB], gtr[HB], gq[HB];
+#pragma unroll
+            for (int h = 0; h < HB; ++h) {
+                qtr[h] = in && h < heads ? qt[d * ht + h * tdim + t] : 0.0f;
+                gtr[h] = in && h < heads ? gt[h * tdim + t] : 0.0f;
+                gq[h] = 0.0f;
+            }
+            for (int j = 0; j < n; ++j) {
+                const int32_t s = __shfl(mine, j);
+                const float dj = __shfl(dtj, j);
+                if (s < 0) continue; // wave-uniform
+                float sn, cs;
+                sincosf(time_arg(om, dj, ph), &sn, &cs);
+                float dphi = 0.0f;
+#pragma unroll
+                for (int h = 0; h < HB; ++h) {
+                    if (h < heads) {
+                        const float tj = dot[j * kGatMaxHeads + h];
+                        gq[h] = __builtin_fmaf(tj, cs, gq[h]);
+                        dphi += w[j * kGatMaxHeads + h] * gtr[h] + scale * tj * qtr[h];
+                    }
+                }
+                g_ph[p] -= sn * dphi;
+                g_om[p] -= sn * dj * dphi;
+            }
+            if (grad_qt) {
+#pragma unroll
+                for (int h = 0; h < HB; ++h)
+                    if (h < heads && in) grad_qt[d * ht + h * tdim + t] = scale * gq[h];
+            }
+        }
+    }
+    if (!grad_time_parts) return; // grid-uniform
+    __syncthreads(); // every wave of the block is past its rows: w_lds is free
+#pragma unroll
+    for (int p = 0; p < kTimePasses; ++p) {
+        w[p * 64 + lane] = g_om[p];
+        w[kTimeMaxDim + p * 64 + lane] = g_ph[p];
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < 2 * tdim; c += kBlock) {
+        const int at = (c < tdim ? c : kTimeMaxDim + c - tdim);
+        float sum = w_lds[0][at];
+        for (int i = 1; i < kWavesPerBlock; ++i) sum += w_lds[i][at];
+        grad_time_parts[(int64_t)blockIdx.x * 2 * tdim + c] = sum;
+    }
+}
+
 // Weighted sum aggregation (DGL's u_mul_e_sum, what GraphConv / SAGEConv compute with edge_weight=): out[d] = sum over the valid edges
 // j of row d of w_j * h_src[s_j], one weight per neighbour slot (w is laid out like the block's index array).  The mean kernel's
 // mapping: one wave per destination row, a lane per 16 bytes of the row, the row's indices and weights read 64 at a time (a fixed row
@@ -1406,6 +1643,67 @@ int dot_gat_backward_launch(int device, const int64_t* indptr, const int32_t* ro
     return COALA_OK;
 }
 
+// Temporal attention: fixed blocks alone, of fan-out 1..64 (a row is one chunk).  The grid is one block per four rows, 1024 at the
+// most: what the backward's partials buffer has rows for.
+constexpr int kTimeMaxGrid = 1024;
+
+int time_attn_shape_check(int64_t n_dst, int fanout, int heads, int dim, int tdim) {
+    if (fanout < 1 || fanout > 64) return fail(COALA_EINVAL, "bad block shape (fan-out 1..64)");
+    if (n_dst < 0 || heads < 1 || heads > kGatMaxHeads || dim < 1 || (int64_t)heads * dim > INT32_MAX || tdim < 1 || tdim > kTimeMaxDim)
+        return fail(COALA_EINVAL, "bad block shape (heads 1..%d, dim >= 1, time_dim 1..%d, n_dst >= 0)", kGatMaxHeads, kTimeMaxDim);
+    return COALA_OK;
+}
+
+// f(std::integral_constant<int, HB>): the instantiation for `heads` heads
+template <typename F>
+void dispatch_heads(int heads, F&& f) {
+    if (heads <= 1) f(std::integral_constant<int, 1>{});
+    else if (heads <= 2) f(std::integral_constant<int, 2>{});
+    else if (heads <= 4) f(std::integral_constant<int, 4>{});
+    else if (heads <= 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
+}
+
+int time_attn_launch(int device, const int32_t* nbr, const float* dt, const float* q, const float* k, const float* v, const float* qt,
+                     const float* omega, const float* phase, float* out, float* tagg, float* lse, int64_t n_dst, int fanout, int heads, int dim,
+                     int tdim, float scale, void* stream) {
+    if (int rc = time_attn_shape_check(n_dst, fanout, heads, dim, tdim)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if (!nbr || !dt || !q || !k || !v || !qt || !omega || !phase || !out || !tagg || !lse) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grid1d(n_dst * 64, kBlock, kTimeMaxGrid));
+    dispatch_heads(heads, [&](auto hb) {
+        dispatch_vec(vec4_ok(dim, v, out), [&](auto vec) {
+            hipLaunchKernelGGL((time_attn_aggregate_kernel<decltype(hb)::value, decltype(vec)::value>), grid, dim3(kBlock), 0, (hipStream_t)stream,
+                               nbr, dt, fanout, q, k, v, qt, omega, phase, out, tagg, lse, n_dst, heads, dim, tdim, scale);
+        });
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+// With a partials buffer the grid is exactly `parts` blocks and block b stores row b (the grad_attn rule of gatv2_backward_launch).
+int time_attn_backward_launch(int device, const int32_t* nbr, const float* dt, const float* q, const float* k, const float* v, const float* qt,
+                              const float* omega, const float* phase, const float* out, const float* tagg, const float* lse,
+                              const float* grad_out, const float* grad_tagg, float* grad_q, float* grad_k, float* grad_v, float* grad_qt,
+                              float* grad_time_parts, int parts, int64_t n_dst, int fanout, int heads, int dim, int tdim, float scale,
+                              void* stream) {
+    if (int rc = time_attn_shape_check(n_dst, fanout, heads, dim, tdim)) return rc;
+    if (grad_time_parts && (parts < 1 || parts > kTimeMaxGrid)) return fail(COALA_EINVAL, "bad block shape (parts 1..%d)", kTimeMaxGrid);
+    if (n_dst == 0 || (!grad_q && !grad_k && !grad_v && !grad_qt && !grad_time_parts)) return COALA_OK;
+    if (!nbr || !dt || !q || !k || !v || !qt || !omega || !phase || !out || !tagg || !lse || !grad_out || !grad_tagg)
+        return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid(grad_time_parts ? parts : grid1d(n_dst * 64, kBlock, kTimeMaxGrid));
+    dispatch_heads(heads, [&](auto hb) {
+        hipLaunchKernelGGL(time_attn_aggregate_backward_kernel<decltype(hb)::value>, grid, dim3(kBlock), 0, (hipStream_t)stream, nbr, dt, fanout, q, k,
+                           v, qt, omega, phase, out, tagg, lse, grad_out, grad_tagg, grad_q, grad_k, grad_v, grad_qt, grad_time_parts, n_dst,
+                           heads, dim, tdim, scale);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
 template <bool CSR>
 int weighted_sum_launch(int device, const int64_t* indptr, const int32_t* idx, const float* w, int fanout, const float* h_src, float* out,
                         int64_t n_dst, int dim, void* stream) {
@@ -1981,6 +2279,21 @@ int coala_block_dot_gat_aggregate_csr_backward(int device, const int64_t* indptr
                                                float* grad_k, float* grad_v, int64_t n_dst, int heads, int dim, float scale, void* stream) {
     return dot_gat_backward_launch<true>(device, indptr, row, 0, q, k, v, out, lse, grad_out, grad_q, grad_k, grad_v, n_dst, heads, dim, scale,
                                          stream);
+}
+
+int coala_block_time_attn_aggregate(int device, const int32_t* nbr, const float* dt, const float* q, const float* k, const float* v,
+                                    const float* qt, const float* omega, const float* phase, float* out, float* tagg, float* lse, int64_t n_dst,
+                                    int fanout, int heads, int dim, int time_dim, float scale, void* stream) {
+    return time_attn_launch(device, nbr, dt, q, k, v, qt, omega, phase, out, tagg, lse, n_dst, fanout, heads, dim, time_dim, scale, stream);
+}
+
+int coala_block_time_attn_aggregate_backward(int device, const int32_t* nbr, const float* dt, const float* q, const float* k, const float* v,
+                                             const float* qt, const float* omega, const float* phase, const float* out, const float* tagg,
+                                             const float* lse, const float* grad_out, const float* grad_tagg, float* grad_q, float* grad_k,
+                                             float* grad_v, float* grad_qt, float* grad_time_parts, int parts, int64_t n_dst, int fanout,
+                                             int heads, int dim, int time_dim, float scale, void* stream) {
+    return time_attn_backward_launch(device, nbr, dt, q, k, v, qt, omega, phase, out, tagg, lse, grad_out, grad_tagg, grad_q, grad_k, grad_v, grad_qt,
+                                     grad_time_parts, parts, n_dst, fanout, heads, dim, time_dim, scale, stream);
 }
 
 int coala_block_weighted_sum(int device, const int32_t* nbr, const float* w, const float* h_src, float* out, int64_t n_dst, int fanout, int dim,

@@ -403,4 +403,27 @@ PYBIND11_MODULE(_coala_pybind, m) {
                                                          ptr<const float>(grad_out), ptr<float>(grad_q), ptr<float>(grad_k), ptr<float>(grad_v),
                                                          n_dst, heads, dim, scale, stream_of(stream)));
     });
+    // temporal attention on a fixed block (coala_block_time_attn_aggregate*); a gradient that is not wanted is passed as 0
+    m.def("block_time_attn_aggregate", [](int device, uint64_t nbr, uint64_t dt, uint64_t q, uint64_t k, uint64_t v, uint64_t qt, uint64_t omega,
+                                          uint64_t phase, uint64_t out, uint64_t tagg, uint64_t lse, int64_t n_dst, int fanout, int heads, int dim,
+                                          int time_dim, float scale, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_time_attn_aggregate(device, ptr<const int32_t>(nbr), ptr<const float>(dt), ptr<const float>(q), ptr<const float>(k),
+                                              ptr<const float>(v), ptr<const float>(qt), ptr<const float>(omega), ptr<const float>(phase),
+                                              ptr<float>(out), ptr<float>(tagg), ptr<float>(lse), n_dst, fanout, heads, dim, time_dim, scale,
+                                              stream_of(stream)));
+    });
+    m.def("block_time_attn_aggregate_backward", [](int device, uint64_t nbr, uint64_t dt, uint64_t q, uint64_t k, uint64_t v, uint64_t qt,
+                                                   uint64_t omega, uint64_t phase, uint64_t out, uint64_t tagg, uint64_t lse, uint64_t grad_out,
+                                                   uint64_t grad_tagg, uint64_t grad_q, uint64_t grad_k, uint64_t grad_v, uint64_t grad_qt,
+                                                   uint64_t grad_time_parts, int parts, int64_t n_dst, int fanout, int heads, int dim,
+                                                   int time_dim, float scale, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_time_attn_aggregate_backward(
+            device, ptr<const int32_t>(nbr), ptr<const float>(dt), ptr<const float>(q), ptr<const float>(k), ptr<const float>(v),
+            ptr<const float>(qt), ptr<const float>(omega), ptr<const float>(phase), ptr<const float>(out), ptr<const float>(tagg),
+            ptr<const float>(lse), ptr<const float>(grad_out), ptr<const float>(grad_tagg), ptr<float>(grad_q), ptr<float>(grad_k),
+            ptr<float>(grad_v), ptr<float>(grad_qt), ptr<float>(grad_time_parts), parts, n_dst, fanout, heads, dim, time_dim, scale,
+            stream_of(stream)));
+    });
 }

@@ -20,6 +20,8 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --task link --num_negs 5 --exclude reverse_id
   python examples/train_synthetic.py --sampler temporal --temporal_strategy last --time_decay 0.001
   python examples/train_synthetic.py --task link --sampler temporal --num_negs 5
+  python examples/train_synthetic.py --model_type tgat --sampler temporal --num_heads 2 --time_dim 100 --time_scale 0.001
+  python examples/train_synthetic.py --task link --model_type tgat --sampler temporal --num_heads 2
   python examples/train_synthetic.py --node_embedding --emb_dim 64 --model_type rgcn --num_rels 4
   python examples/train_synthetic.py --node_embedding --emb_optimizer sgd --emb_lr 0.1 --task link
   python examples/train_synthetic.py --task node2vec --walk_length 20 --context_size 10 --walks_per_node 10 --p 0.5 --q 2 --num_negs 1 \
@@ -41,7 +43,7 @@ import torch  # noqa: E402
 
 from COALA_GNN import COALA_GNN_DataLoader, MetaPath2Vec, MPI_Comm_Manager, Node2Vec, Node_Distributor, NodeEmbedding, RowWiseAdagrad, SparseAdagrad, SparseAdam, SparseSGD, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
-from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, GATv2, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
+from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, TGAT, GATv2, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
 from COALA_GNN.sampler import (CSCGraph, EdgePredictionSampler, LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler,  # noqa: E402
                                TemporalEdgePredictionSampler, TemporalNeighborSampler, UniformNegativeSampler, reverse_edge_ids,
                                sort_csc_by_etype)
@@ -146,6 +148,8 @@ def train_link(args, comm, device, indptr, indices, feat, files, fan_out):
         torch.manual_seed(args.seed)
     if args.model_type == "gat":
         encoder = GAT(args.dim, args.hidden_channels, args.hidden_channels, len(fan_out), args.num_heads)
+    elif args.model_type == "tgat":
+        encoder = TGAT(args.dim, args.hidden_channels, args.hidden_channels, len(fan_out), args.num_heads, args.time_dim, args.time_scale)
     else:
         encoder = SAGE(args.dim, args.hidden_channels, args.hidden_channels, len(fan_out), args.sage_aggregator,
                        edge_weight=None if args.time_decay is None else DECAY)
@@ -259,12 +263,18 @@ def main():
     # accepted so that the reference's command lines (examples/4GB_script.sh, Cache_compare_script.sh, Distribution_compare_script.sh) run as they are
     ap.add_argument("--num_layers", type=int, default=None, help="must equal the number of fan-outs when given")
     ap.add_argument("--feat_cpu", action="store_true", help="features in pinned host memory: always the case here (the NVMe tier is out of scope)")
-    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "gatv2", "sage", "gcn", "gin", "rgcn", "rgat", "rsage", "hgt", "pinsage"],
+    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "gatv2", "sage", "gcn", "gin", "rgcn", "rgat", "rsage", "hgt", "pinsage", "tgat"],
                     help="sage: GraphSAGE (--sage_aggregator); gat: GAT with --num_heads heads (native attention aggregation); gatv2: the same model on GATv2Conv layers (--share_weights); gcn: GraphConv, "
                          "norm='both'; gin: GINConv layers (--gin_aggregator), an MLP in each; rgcn: RelGraphConv layers, one weight matrix per edge "
                          "type (--num_rels synthetic types, the source node's id modulo --num_rels; native relation-typed sum); rgat: RelGATConv layers, "
                          "a GATConv of --num_heads heads per edge type, summed (native relation-typed attention); rsage: RelSAGEConv layers, a SAGEConv "
-                         "'gcn' per edge type, summed; pinsage: WeightedSAGEConv layers on the visit counts of --sampler pinsage")
+                         "'gcn' per edge type, summed; pinsage: WeightedSAGEConv layers on the visit counts of --sampler pinsage; tgat: TGATConv layers of "
+                         "--num_heads heads on the blocks of --sampler temporal, attention over the neighbours' rows and a learnable encoding of "
+                         "the time gaps (--time_dim, --time_scale; native temporal attention)")
+    ap.add_argument("--time_dim", type=int, default=100, help="--model_type tgat: channels of the time encoding (1..128 run natively)")
+    ap.add_argument("--time_scale", type=float, default=1.0,
+                    help="--model_type tgat: the time gaps are multiplied by this before they are encoded (the encoder's frequencies run "
+                         "from 1 down to 1e-9 per time unit)")
     ap.add_argument("--sage_aggregator", type=str, default="mean", choices=["mean", "gcn", "pool", "lstm"],
                     help="aggregator of --model_type sage; pool: the maximum of relu(fc_pool(h)) over the neighbours (native max aggregation); "
                          "lstm: an LSTM over the neighbours in slot order (LSTMSAGEConv, native for feature widths that are multiples of 32 up to 256)")
@@ -317,10 +327,12 @@ def main():
     eval_fan_out = fan_out if args.eval_fan_out is None else [int(f) for f in args.eval_fan_out.split(",")]
     if len(eval_fan_out) != len(fan_out):
         ap.error("--eval_fan_out needs as many layers as --fan_out")
-    if args.model_type in ("rgat", "hgt") and (args.num_heads < 1 or args.hidden_channels % args.num_heads):
+    if args.model_type in ("rgat", "hgt", "tgat") and (args.num_heads < 1 or args.hidden_channels % args.num_heads):
         ap.error(f"--model_type {args.model_type} needs --hidden_channels to be a multiple of --num_heads")
     if args.model_type == "hgt" and args.num_ntypes < 1:
         ap.error("--num_ntypes must be at least 1")
+    if args.model_type == "tgat" and (args.sampler != "temporal" or args.time_dim < 1):
+        ap.error("--model_type tgat needs --sampler temporal (the model reads the time gaps the sampler puts on its blocks) and --time_dim >= 1")
     if (args.model_type == "pinsage") != (args.sampler == "pinsage"):
         ap.error("--model_type pinsage and --sampler pinsage go together: the model reads the visit counts the sampler puts on its blocks")
     if args.sampler == "temporal" and (args.edge_weights != "none" or args.layer_dependency or eval_fan_out != fan_out or args.path
@@ -372,8 +384,8 @@ def main():
     files = [os.path.join(tmp, f) for f in ("color.npy", "topk.npy", "score.npy")]
 
     if args.task == "link":
-        if args.path or args.sampler not in ("neighbor", "labor", "temporal") or args.model_type not in ("sage", "gat") or args.edge_weights != "none":
-            ap.error("--task link runs on the synthetic graph with --sampler neighbor | labor | temporal and --model_type sage | gat, without "
+        if args.path or args.sampler not in ("neighbor", "labor", "temporal") or args.model_type not in ("sage", "gat", "tgat") or args.edge_weights != "none":
+            ap.error("--task link runs on the synthetic graph with --sampler neighbor | labor | temporal and --model_type sage | gat | tgat, without "
                      "--edge_weights")
         if args.sampler == "temporal" and args.exclude == "reverse_id":
             ap.error("--sampler temporal needs no exclusion pass (strict times leave the seed edges out): drop --exclude reverse_id")
@@ -414,7 +426,7 @@ def main():
             edata = dict(edata, etype=etype)
         sampler = RandomWalkNeighborSampler(fan_out, args.num_traversals, args.termination_prob, args.num_random_walks, metapath=args.metapath)
     elif args.sampler == "temporal":
-        sampler = TemporalNeighborSampler(fan_out, strategy=args.temporal_strategy, seed_time="t", edge_ids=edge_ids or ew is not None)
+        sampler = TemporalNeighborSampler(fan_out, strategy=args.temporal_strategy, seed_time="t", edge_ids=edge_ids or ew is not None or args.model_type == "tgat")
     else:
         if args.layer_dependency:
             ap.error("--layer_dependency needs --sampler labor")
@@ -442,6 +454,8 @@ def main():
                     ntype=ntype).to(device)
     elif args.model_type == "rsage":
         model = RSAGE(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_rels).to(device)
+    elif args.model_type == "tgat":
+        model = TGAT(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads, args.time_dim, args.time_scale).to(device)
     elif args.model_type == "pinsage":
         model = PinSAGE(args.dim, args.hidden_channels, args.num_classes, len(fan_out)).to(device)
     elif args.model_type == "rgcn":

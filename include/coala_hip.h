@@ -868,6 +868,38 @@ int coala_block_dot_gat_aggregate_csr(int device, const int64_t* indptr, const i
 int coala_block_dot_gat_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* row, const float* q, const float* k,
                                                const float* v, const float* out, const float* lse, const float* grad_out, float* grad_q,
                                                float* grad_k, float* grad_v, int64_t n_dst, int heads, int dim, float scale, void* stream);
+/* Temporal attention on a fixed block (TGAT's attention step; TGN's embedding module): dot-product attention whose keys and values
+ * carry the time encoding phi_j[t] = cos(omega[t] dt_j + phase[t]) of slot j's time gap beside the source's row, with the key and value
+ * projections split by input so that phi is never in memory.  nbr int32 [n_dst, fanout] (-1 = no edge, wherever it stands), dt fp32
+ * [n_dst, fanout] (not read at a -1), q [n_dst, heads, dim], k and v [n_src, heads, dim], qt [n_dst, heads, time_dim] (the destination's
+ * query carried through the time columns of the key projection), omega and phase [time_dim].  For dst d, head h and the valid slots j:
+ *   e_j = scale (<q[d, h, :], k[s_j, h, :]> + <qt[d, h, :], phi_j>),  a_j = softmax of e over the row,
+ *   out[d, h, :] = sum_j a_j v[s_j, h, :]  [n_dst, heads, dim],   tagg[d, h, :] = sum_j a_j phi_j  [n_dst, heads, time_dim],
+ *   lse[d, h] the log-sum-exp of e (-inf for a row without an edge, whose out and tagg are zeros): the state of the backward.
+ * The argument omega[t] dt_j + phase[t] is formed in fp32, the product rounded before the sum, and cos / sin are the accurate library
+ * functions.  The scale is applied to the finished sum as one rounded product, forward and backward.
+ * Backward, one launch, with r_j = <grad_out[d, h], v_j> + <grad_tagg[d, h], phi_j> and
+ * t_j = a_j (r_j - <grad_out[d, h], out[d, h]> - <grad_tagg[d, h], tagg[d, h]>), a_j recomputed from lse and divided by its row sum:
+ *   grad_q[d, h, :] = scale sum_j t_j k_j        grad_qt[d, h, :] = scale sum_j t_j phi_j        written whole, slot order, no atomics;
+ *   grad_k[s_j, h, :] += scale t_j q[d, h, :]     grad_v[s_j, h, :] += a_j grad_out[d, h, :]       float atomics: the caller zeroes them;
+ *   dphi_j[t] = sum_h (a_j[h] grad_tagg[d, h, t] + scale t_j[h] qt[d, h, t]),
+ *   grad_omega[t] = sum over edges of -sin(omega[t] dt_j + phase[t]) dt_j dphi_j[t],  grad_phase[t] the same without dt_j:
+ *     grad_time_parts fp32 [parts, 2, time_dim], block b of a grid of exactly `parts` blocks storing row b (omega's sums, then phase's);
+ *     the caller sums over the rows.  parts is 1..1024; min(ceil(n_dst / 4), 1024) gives every wave a row.
+ * Each of the five outputs may be NULL (not wanted); with all five NULL nothing is launched.  There is no gradient for dt.
+ * Determinism: out, tagg, lse, grad_q, grad_qt and the partials (so grad_omega and grad_phase, for one `parts`) are bitwise
+ * reproducible; grad_k and grad_v depend on the order of the atomics.
+ * Refused with COALA_EINVAL and nothing launched: "bad block shape" (fan-out outside 1..64, heads outside 1..16, dim < 1, time_dim
+ * outside 1..128, n_dst < 0, parts outside 1..1024 with a partials buffer), "null buffer"; n_dst == 0 launches nothing and reads no
+ * pointer.  The forward's grid is one block per four rows, 1024 at the most.  There is no CSR form: temporal blocks are fixed-stride. */
+int coala_block_time_attn_aggregate(int device, const int32_t* nbr, const float* dt, const float* q, const float* k, const float* v,
+                                    const float* qt, const float* omega, const float* phase, float* out, float* tagg, float* lse, int64_t n_dst,
+                                    int fanout, int heads, int dim, int time_dim, float scale, void* stream);
+int coala_block_time_attn_aggregate_backward(int device, const int32_t* nbr, const float* dt, const float* q, const float* k, const float* v,
+                                             const float* qt, const float* omega, const float* phase, const float* out, const float* tagg,
+                                             const float* lse, const float* grad_out, const float* grad_tagg, float* grad_q, float* grad_k,
+                                             float* grad_v, float* grad_qt, float* grad_time_parts, int parts, int64_t n_dst, int fanout,
+                                             int heads, int dim, int time_dim, float scale, void* stream);
 /* Edge exclusion (link prediction: the seed edges, and their reverses, leave the message-flow blocks).  excluded: device int64
  * [n_excluded], SORTED ascending, CSC positions (a few thousand at most; every slot binary-searches its edge id in it).  eid is the
  * block's edge-id array (coala_sampler_sample_layers_edge_ids), laid out like its index array.
