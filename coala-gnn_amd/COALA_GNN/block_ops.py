@@ -304,6 +304,77 @@ class _MaxAggregateCSR(torch.autograd.Function):
         return _max_backward(ctx, grad_out), None, None
 
 
+MULTI_AGGREGATORS = ("sum", "mean", "max", "min", "var", "std")   # the canonical order of the kernel's `planes` word
+
+
+def multi_planes(aggregators):
+    """The checked tuple of aggregator names -> the kernel's `planes` word: 4 bits per aggregator in the canonical order, holding
+    its position in `aggregators` (its output plane), 15 where it is not wanted."""
+    names = tuple(aggregators)
+    for a in names:
+        if a not in MULTI_AGGREGATORS:
+            raise ValueError(f"aggregator {a!r}: multi_aggregate has {', '.join(MULTI_AGGREGATORS)}")
+    if not names or len(set(names)) != len(names):
+        raise ValueError(f"aggregators {names!r}: at least one name, each at most once")
+    return sum((names.index(a) if a in names else 15) << (4 * k) for k, a in enumerate(MULTI_AGGREGATORS))
+
+
+def _multi_forward(ctx, h_src, entry, index, planes, n_aggr, eps):
+    """out[d, a, :] = the a-th wanted statistic of the rows h_src[s] over row d's valid entries (coala_block_multi_aggregate[_csr]).
+    The kernel also saves the winning slots (with max or min) and the centred mean and std (with var or std) for the backward, which
+    is skipped when h_src needs no gradient."""
+    h = h_src.contiguous()
+    idx, n_dst, fan = _block(index)
+    dim = h.shape[1]
+    grad = ctx.needs_input_grad[0]
+    out = torch.empty((n_dst, n_aggr, dim), dtype=torch.float32, device=h.device)
+    arg = torch.empty((n_dst, 2, dim), dtype=torch.int32, device=h.device) if grad and (planes >> 8 & 0xFF) != 0xFF else None
+    mom = torch.empty((n_dst, 2, dim), dtype=torch.float32, device=h.device) if grad and (planes >> 16 & 0xFF) != 0xFF else None
+    _capi.check(entry(h.device.index or 0, *idx, h.data_ptr(), out.data_ptr(), _ptr(arg), _ptr(mom), n_dst, *fan, dim, n_aggr, planes, eps,
+                      current_stream()))
+    ctx.save_for_backward(h if mom is not None else None, arg, mom, *index)
+    ctx.src_shape, ctx.planes = h.shape, planes
+    return out
+
+
+def _multi_backward(ctx, grad_out, entry):
+    """Every plane's gradient in one launch, one float atomic per (edge, element) (coala_block_multi_aggregate_backward[_csr]): not
+    bitwise reproducible."""
+    if not ctx.needs_input_grad[0]:
+        return None
+    h, arg, mom, *index = ctx.saved_tensors
+    idx, n_dst, fan = _block(index)
+    g = grad_out.contiguous()
+    grad_src = torch.zeros(ctx.src_shape, dtype=torch.float32, device=g.device)
+    _capi.check(entry(g.device.index or 0, *idx, _ptr(h), g.data_ptr(), _ptr(arg), _ptr(mom), grad_src.data_ptr(), n_dst, *fan, g.shape[2],
+                      g.shape[1], ctx.planes, current_stream()))
+    return grad_src
+
+
+class _MultiAggregate(torch.autograd.Function):
+    """Several statistics of h_src[nbr[d, j]] over the valid j at once (coala_block_multi_aggregate): one kernel forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, h_src, nbr, planes, n_aggr, eps):
+        return _multi_forward(ctx, h_src, _lib.coala_block_multi_aggregate, (nbr,), planes, n_aggr, eps)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (_multi_backward(ctx, grad_out, _lib.coala_block_multi_aggregate_backward),) + (None,) * 4
+
+
+class _MultiAggregateCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_multi_aggregate_csr): row d reduces h_src[indices[indptr[d]:indptr[d+1]]]."""
+
+    @staticmethod
+    def forward(ctx, h_src, indptr, indices, planes, n_aggr, eps):
+        return _multi_forward(ctx, h_src, _lib.coala_block_multi_aggregate_csr, (indptr, indices), planes, n_aggr, eps)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (_multi_backward(ctx, grad_out, _lib.coala_block_multi_aggregate_backward_csr),) + (None,) * 5
+
+
 def _gat_forward(ctx, el, er, feat_src, entry, index, negative_slope):
     """Per head, a softmax of leaky_relu(el[s] + er[d]) over row d's valid entries, then the weighted sum of feat_src[s]
     (coala_block_gat_aggregate[_csr]).  out and the log-sum-exp per (row, head) are the state of the backward."""

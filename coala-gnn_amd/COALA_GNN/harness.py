@@ -17,9 +17,9 @@ import time
 
 import torch
 
-from .nn import DotGatConv, DotPredictor, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, LSTMSAGEConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv, TGATConv, WeightedSAGEConv
+from .nn import DotGatConv, DotPredictor, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, LSTMSAGEConv, PNAConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv, TGATConv, WeightedSAGEConv
 
-__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "PinSAGE", "TGAT", "LinkPredictor", "link_loss", "train_steps", "FlatGradAllReduce"]
+__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "PNA", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "PinSAGE", "TGAT", "LinkPredictor", "link_loss", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -136,6 +136,27 @@ class GIN(torch.nn.Module):
         self.layers = torch.nn.ModuleList(
             GINConv(torch.nn.Sequential(torch.nn.Linear(dims[i], h_feats), torch.nn.ReLU(), torch.nn.Linear(h_feats, dims[i + 1])),
                     aggregator_type, learn_eps=learn_eps) for i in range(num_layers))
+
+    def forward(self, blocks, x):
+        h = x
+        for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+            h = layer(block, (h, block.dst_rows(h)))
+            if i + 1 < len(self.layers):
+                h = torch.relu(h)
+        return h
+
+
+class PNA(torch.nn.Module):
+    """num_layers PNAConv layers (Block.multi_aggregate: every aggregator from one native pass), relu between the layers; delta is
+    COALA_GNN.nn.pna_delta(graph).  A layer keeps PNAConv's residual where its input and output widths agree."""
+
+    def __init__(self, in_feats, h_feats, num_classes, num_layers=2, aggregators=("mean", "max", "min", "std"),
+                 scalers=("identity", "amplification", "attenuation"), delta=1.0, num_towers=1, dropout=0.0):
+        super().__init__()
+        dims = [in_feats] + [h_feats] * (num_layers - 1) + [num_classes]
+        self.layers = torch.nn.ModuleList(
+            PNAConv(dims[i], dims[i + 1], aggregators, scalers, delta, dropout, 1 if dims[i] % num_towers or dims[i + 1] % num_towers else num_towers,
+                    residual=dims[i] == dims[i + 1]) for i in range(num_layers))
 
     def forward(self, blocks, x):
         h = x

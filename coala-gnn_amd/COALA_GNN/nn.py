@@ -20,12 +20,14 @@ in block.edata['weights'] weigh the neighbours' rows through Block.weighted_sum_
 LSTMSAGEConv is DGL's SAGEConv with aggregator_type='lstm' as a class of its own: the recurrence over a destination's neighbours is
 Block.lstm_aggregate, a native kernel on the matrix units, and the input projection is made once per source node.
 TGATConv is TGAT's temporal attention layer on the blocks of TemporalNeighborSampler: attention over [h_src || Phi(dt)] with the learnable
-time encoding TimeEncode, whose attention step is Block.time_attn_aggregate, a native kernel that computes Phi(dt) in registers."""
+time encoding TimeEncode, whose attention step is Block.time_attn_aggregate, a native kernel that computes Phi(dt) in registers.
+PNAConv is DGL's Principal Neighbourhood Aggregation layer: all its aggregators (mean, max, min, std, var, sum) come from one pass of
+Block.multi_aggregate, a native kernel, over a per-source projection -- no per-edge tensor."""
 import torch
 
 from .block_ops import gather_mm
 
-__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "LSTMSAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv", "TypedLinear", "DotPredictor", "TimeEncode", "TGATConv"]
+__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "LSTMSAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv", "TypedLinear", "DotPredictor", "TimeEncode", "TGATConv", "PNAConv", "pna_delta"]
 
 
 class GATConv(torch.nn.Module):
@@ -870,3 +872,90 @@ class DotPredictor(torch.nn.Module):
     def forward(self, h, src, dst):
         from .block_ops import pair_dot
         return pair_dot(h, src, dst, validate=self.validate)
+
+
+PNA_AGGREGATORS = ("mean", "max", "min", "std", "var", "sum")
+PNA_SCALERS = ("identity", "amplification", "attenuation")
+
+
+def pna_delta(g):
+    """PNA's normaliser delta for a graph: the mean of log(in_degree + 1) over its nodes (a Python float).  g: a CSCGraph, or any
+    object with an int64 CSC `indptr`."""
+    deg = (g.indptr[1:] - g.indptr[:-1]).to(torch.float64)
+    return float(torch.log(deg + 1.0).mean())
+
+
+class _PNATower(torch.nn.Module):
+    """One tower's parameters under DGL's names: M, the pre-transform of cat[h_src, h_dst]; U, the post-transform of
+    cat[h_dst, scaled aggregates]; batchnorm on U's output."""
+
+    def __init__(self, in_size, out_size, n_aggr, n_scalers, dropout):
+        super().__init__()
+        self.M = torch.nn.Linear(2 * in_size, in_size)
+        self.U = torch.nn.Linear((n_aggr * n_scalers + 1) * in_size, out_size)
+        self.dropout = torch.nn.Dropout(dropout)
+        self.batchnorm = torch.nn.BatchNorm1d(out_size)
+
+
+class PNAConv(torch.nn.Module):
+    """Principal Neighbourhood Aggregation layer on a block: DGL PNAConv's signature and parameter names (towers.<t>.M, towers.<t>.U,
+    towers.<t>.batchnorm, mixing_layer.0), stated from memory of DGL's source.  Per tower t, on its slice of in_size / num_towers
+    input columns, for destination d and its valid in-edges j (source s_j) in the block:
+        msg_j = M(cat[h_src[s_j], h_dst[d]]);   agg = cat over `aggregators` of the reduction of msg over j
+        scaled = cat over `scalers` of agg * scale(D),   D = max(in-degree of d, 1) (PyG's clamp): identity 1, amplification
+        log(D + 1) / delta, attenuation delta / log(D + 1);   out_t = dropout(batchnorm(U(cat[h_dst[d], scaled])))
+    and the layer's output is mixing_layer(cat over t of out_t) (Linear, LeakyReLU), plus h_dst when residual (in_size == out_size).
+    aggregators: mean, max, min, std, var, sum; scalers: identity, amplification, attenuation; delta: pna_delta(graph).
+    M is linear, so no per-edge tensor is made: a = h_src @ W_s^T once per source and c = h_dst @ W_d^T + b once per destination,
+    W_s and W_d the two halves of M.weight; Block.multi_aggregate(a), one native kernel for all aggregators, is then corrected on the
+    rows with an edge -- mean, max and min get + c, sum gets + n c, std and var are unchanged.  var is the population variance and
+    std = sqrt(relu(var) + eps) with eps = self.eps = 1e-5 (PyG's; DGL's is 1e-30, from memory).  A destination without an in-edge
+    aggregates zeros.  moment3..moment5 and edge features (edge_feat_size > 0) are not provided: ValueError."""
+
+    def __init__(self, in_size, out_size, aggregators, scalers, delta, dropout=0.0, num_towers=1, edge_feat_size=0, residual=True):
+        super().__init__()
+        aggregators, scalers = tuple(aggregators), tuple(scalers)
+        for a in aggregators:
+            if a not in PNA_AGGREGATORS:
+                raise ValueError(f"aggregator {a!r}: PNAConv has {', '.join(PNA_AGGREGATORS)} (the moments 3..5 are not provided)")
+        for s in scalers:
+            if s not in PNA_SCALERS:
+                raise ValueError(f"scaler {s!r}: PNAConv has {', '.join(PNA_SCALERS)}")
+        if not aggregators or not scalers or len(set(aggregators)) != len(aggregators) or len(set(scalers)) != len(scalers):
+            raise ValueError("PNAConv takes at least one aggregator and one scaler, each at most once")
+        if edge_feat_size:
+            raise ValueError("PNAConv: edge features (edge_feat_size > 0) are not provided")
+        if in_size % num_towers or out_size % num_towers:
+            raise ValueError(f"in_size {in_size} and out_size {out_size} must be multiples of num_towers {num_towers}")
+        if residual and in_size != out_size:
+            raise ValueError(f"residual=True needs in_size == out_size, got {in_size} and {out_size}")
+        self.aggregators, self.scalers, self.delta, self.residual, self.eps = aggregators, scalers, float(delta), residual, 1e-5
+        self.tower_in_size, self.tower_out_size = in_size // num_towers, out_size // num_towers
+        self.towers = torch.nn.ModuleList(_PNATower(self.tower_in_size, self.tower_out_size, len(aggregators), len(scalers), dropout)
+                                          for _ in range(num_towers))
+        self.mixing_layer = torch.nn.Sequential(torch.nn.Linear(out_size, out_size), torch.nn.LeakyReLU())
+
+    def forward(self, block, feat):
+        h_src, h_dst = feat if isinstance(feat, (tuple, list)) else (feat, block.dst_rows(feat))
+        ti = self.tower_in_size
+        a, c = [], []
+        for t, tower in enumerate(self.towers):
+            w = tower.M.weight
+            a.append(h_src[:, t * ti:(t + 1) * ti] @ w[:, :ti].t())
+            c.append(h_dst[:, t * ti:(t + 1) * ti] @ w[:, ti:].t() + tower.M.bias)
+        agg = block.multi_aggregate(torch.cat(a, 1), self.aggregators, self.eps)                  # [num_dst, A, in_size]
+        deg = block.in_degrees().to(device=agg.device, dtype=agg.dtype)
+        once, never = (deg > 0).to(agg.dtype), torch.zeros_like(deg)
+        times_c = {"sum": deg, "mean": once, "max": once, "min": once, "std": never, "var": never}
+        times_c = torch.stack([times_c[name] for name in self.aggregators], 1)                    # [num_dst, A]: how often c enters
+        agg = agg + times_c.unsqueeze(-1) * torch.cat(c, 1).unsqueeze(1)
+        log_d = torch.log(deg.clamp_min(1) + 1)
+        scale = {"identity": torch.ones_like(log_d), "amplification": log_d / self.delta, "attenuation": self.delta / log_d}
+        scale = torch.stack([scale[s] for s in self.scalers], 1)                                  # [num_dst, S]
+        outs = []
+        for t, tower in enumerate(self.towers):
+            scaled = agg[:, None, :, t * ti:(t + 1) * ti] * scale[:, :, None, None]               # [num_dst, S, A, ti]
+            h = tower.U(torch.cat([h_dst[:, t * ti:(t + 1) * ti], scaled.flatten(1)], 1))
+            outs.append(tower.dropout(tower.batchnorm(h)))
+        out = self.mixing_layer(torch.cat(outs, 1))
+        return out + h_dst if self.residual else out

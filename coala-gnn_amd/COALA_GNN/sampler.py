@@ -13,7 +13,7 @@ from COALA_GNN_Pybind import _capi, current_stream
 
 from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
                         _MeanAggregateCSR, _LSTMAggregate, _LSTMAggregateCSR, LSTM_HIDDEN_STEP, LSTM_MAX_HIDDEN, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _TimeAttnAggregate,
-                        _WeightedSum, _WeightedSumCSR)
+                        _WeightedSum, _WeightedSumCSR, _MultiAggregate, _MultiAggregateCSR, multi_planes)
 
 __all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "RandomWalkNeighborSampler", "PinSAGESampler", "random_walk", "sort_csc_by_etype",
            "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT", "EID", "EdgePredictionSampler", "as_edge_prediction_sampler",
@@ -494,6 +494,55 @@ class Block(object):
             return out
         arg = torch.where(some, src.view((E,) + ones).expand_as(v).gather(0, first), torch.full_like(first, -1)).to(torch.int32)
         return out, arg
+
+    def multi_aggregate(self, h_src, aggregators=("mean", "max", "min", "std"), eps=1e-5):
+        """Several statistics of the sampled neighbours' rows at once, for every dst node: fp32 [num_dst, A, dim], plane a the a-th
+        name of `aggregators` -- names from sum, mean, max, min, var, std, each at most once (what PNAConv reduces with).  One kernel
+        reads every source row once and forms all of them in registers; its backward issues one atomic per (edge, element) instead
+        of one per aggregator.  mean is mean_aggregate bit for bit, max and min follow max_aggregate's rule (ties keep the first slot,
+        which alone receives the gradient, even when its source stands twice in the row; a NaN propagates).  var is the population
+        variance, accumulated around the row's first value so that it survives |mean| >> std and is exactly 0 on a row of one
+        neighbour or of equal values; std = sqrt(relu(var) + eps), with PyG's eps = 1e-5 as the default (DGL's PNAConv uses 1e-30, as
+        far as memory of its source goes).  A dst node without an in-edge gets zeros in every plane.  Native kernels under the
+        conditions of mean_aggregate (fp32 2-D rows on the GPU; fan-out <= 32, or the ragged form); multi_aggregate_torch otherwise.
+        The native backward adds with float atomics: not bitwise reproducible."""
+        names = tuple(aggregators)
+        planes = multi_planes(names)
+        index = self._native_index() if h_src.is_cuda and h_src.dtype == torch.float32 and h_src.dim() == 2 else None
+        if index is not None:
+            return (_MultiAggregateCSR if self.nbr is None else _MultiAggregate).apply(h_src, *index, planes, len(names), float(eps))
+        return self.multi_aggregate_torch(h_src, names, eps)
+
+    def multi_aggregate_torch(self, h_src, aggregators=("mean", "max", "min", "std"), eps=1e-5):
+        """multi_aggregate in plain torch, any device and dtype, h_src [num_src, ...] -> [num_dst, A, ...]: its fallback, and in
+        float64 its reference.  The variance is the two-pass centred form -- the mean first, then the mean of (x - mean)^2 -- and
+        max and min go through max_aggregate_torch.  The divisor is mean_aggregate_torch's: the valid entries of a fixed row, the
+        length of a ragged one."""
+        names = tuple(aggregators)
+        multi_planes(names)
+        dev = h_src.device
+        ones = (1,) * (h_src.dim() - 1)
+        rows, src = self._slots(dev)
+        keep = src >= 0
+        rows, src = rows[keep], src[keep]
+        count = torch.bincount(rows, minlength=self.num_dst)
+        has = (count > 0).view((-1,) + ones)
+        n = count if self.nbr is not None else (self.indptr[1:] - self.indptr[:-1]).to(dev)
+        n = n.clamp_min(1).view((-1,) + ones).to(h_src.dtype)
+        zeros = torch.zeros((self.num_dst,) + tuple(h_src.shape[1:]), dtype=h_src.dtype, device=dev)
+        planes = {}
+        if {"sum", "mean", "var", "std"} & set(names):
+            x = h_src[src]
+            planes["sum"] = zeros.index_add(0, rows, x)
+            planes["mean"] = planes["sum"] / n
+            if {"var", "std"} & set(names):
+                planes["var"] = zeros.index_add(0, rows, (x - planes["mean"][rows]) ** 2) / n
+                planes["std"] = torch.where(has, torch.sqrt(torch.relu(planes["var"]) + eps), zeros)
+        if "max" in names:
+            planes["max"] = self.max_aggregate_torch(h_src)
+        if "min" in names:
+            planes["min"] = -self.max_aggregate_torch(-h_src)
+        return torch.stack([planes[a] for a in names], dim=1)
 
     @staticmethod
     def _lstm_args(xg, w_hh):

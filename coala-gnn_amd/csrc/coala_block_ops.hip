@@ -1134,6 +1134,206 @@ __global__ __launch_bounds__(kBlock) void max_aggregate_backward_kernel(const in
         }
 }
 
+// Which output plane each aggregator of the multi-statistic aggregation writes: 4 bits each in the canonical order sum, mean, max,
+// min, var, std, kNoPlane = not wanted.  The caller's order of aggregators is a matter of these fields: nothing is permuted afterwards.
+constexpr int kMultiAggregators = 6;
+constexpr uint32_t kNoPlane = 15;
+
+struct MultiPlanes {
+    uint32_t sum, mean, max, min, var, std;
+    __host__ __device__ bool moments() const { return var != kNoPlane || std != kNoPlane; }
+    __host__ __device__ bool extrema() const { return max != kNoPlane || min != kNoPlane; }
+};
+
+__host__ __device__ __forceinline__ MultiPlanes multi_planes(uint32_t p) {
+    return {p & 15u, p >> 4 & 15u, p >> 8 & 15u, p >> 12 & 15u, p >> 16 & 15u, p >> 20 & 15u};
+}
+
+// Multi-statistic aggregation (what PNAConv reduces with; DGL's fn.sum / mean / max / min and PyG's var / std aggregations): every
+// wanted statistic of row d's valid neighbour rows from one read of them, out[d, plane, :].  The mean kernel's mapping -- one wave per
+// destination row, a lane per 16 bytes, the row's indices read 64 at a time and broadcast by shuffle -- with, per (lane, element) and
+// over the valid slots in slot order, in registers:
+//   s                 the plain sum from +0, one add per term: the `sum` plane, and s * inv the `mean` plane, inv the mean kernel's (valid
+//                     count on fixed rows, row length on CSR rows) -- the mean plane has mean_aggregate_kernel's bits;
+//   K, m1, m2         (MOMENTS) K the value at the first valid slot, and the running moments of y = x - K: at the k-th valid slot
+//                     dx = y - m1, m1 += dx / k, m2 = fma(dx, y - m1, m2) (Welford's update, 1 / k once per slot for the wave); then
+//                     var = max(m2 * inv, 0), std = sqrt(var + eps).  The shift is what keeps the variance: x - K is exact or
+//                     nearly so for values of like magnitude, so a table with mean 1e3 and spread 1 loses nothing to E[x^2] - E[x]^2
+//                     or to a running mean of 1e3; the running form on top of it keeps the error at a few ulps of var where
+//                     sum y^2 / n - (sum y / n)^2 loses ulps of (K - mean)^2.  A row of one neighbour or of equal values has every
+//                     dx == 0: var == 0 and std == sqrt(eps) exactly;
+//   hi, lo, at_hi,    (EXTREMA) max_aggregate_kernel's rule and its mirror image: the first valid slot starts both, a later one wins
+//   at_lo             when greater (less), or NaN while the best is not; `at` is the winner's slot offset inside the row, not its
+//                     source index, so that a source standing twice in a row is told apart in the fused backward.
+// A row without a valid slot stores 0 in every plane (DGL's reducers), at = -1.  State for the backward, stored only where the pointer
+// is given: arg[d, 0 / 1, :] = at_hi / at_lo; mom[d, 0, :] = m1, the mean less the row's first value, and mom[d, 1, :] = std with its
+// sign set where var == 0 (torch's relu subgradient: no gradient through the std of such an element).  Per row: reads deg * (4 dim + 4)
+// bytes, writes 4 dim A, and 16 dim of state.
+template <int VEC, bool CSR, bool MOMENTS, bool EXTREMA>
+__global__ __launch_bounds__(kBlock) void multi_aggregate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
+                                                                 const float* __restrict__ h_src, float* __restrict__ out,
+                                                                 int32_t* __restrict__ arg, float* __restrict__ mom, int64_t n_dst, int dim,
+                                                                 int n_aggr, uint32_t planes, float eps) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    typedef int32_t vi __attribute__((ext_vector_type(VEC)));
+    const auto [lane, wave, n_waves] = wave_rows();
+    const int units = dim / VEC;
+    const MultiPlanes p = multi_planes(planes);
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        int32_t mine0;
+        const int n0 = load_chunk(idx, beg, end, lane, &mine0);
+        const float cnt = CSR ? (float)(end - beg) : (float)__builtin_popcountll(__ballot(mine0 >= 0));
+        const float inv = cnt > 0.0f ? 1.0f / cnt : 0.0f;
+        float* const out_d = out + d * n_aggr * dim;
+        for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+            const int u = u0 + lane;
+            vf s = vf(0.0f), K = vf(0.0f), m1 = vf(0.0f), m2 = vf(0.0f), hi = vf(0.0f), lo = vf(0.0f);
+            vi at_hi = vi(-1), at_lo = vi(-1);
+            int seen = 0; // wave-uniform: the valid slots so far
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                int32_t mine = mine0;
+                int n = n0;
+                if (e0 != beg) n = load_chunk(idx, e0, end, lane, &mine); // wave-uniform
+                const int32_t j0 = (int32_t)(e0 - beg);
+                for (int j = 0; j < n; ++j) {
+                    const int32_t src = __shfl(mine, j);
+                    if (src < 0) continue; // wave-uniform
+                    const bool any = seen > 0;
+                    const float inv_seen = 1.0f / (float)++seen;
+                    if (u < units) {
+                        const vf v = *reinterpret_cast<const vf*>(h_src + (int64_t)src * dim + (int64_t)u * VEC);
+                        s += v;
+                        if (MOMENTS) {
+                            K = any ? K : v;
+                            const vf x = v - K, dx = x - m1;
+                            m1 += dx * inv_seen;
+                            const vf rest = x - m1;
+                            for (int i = 0; i < VEC; ++i) m2[i] = __builtin_fmaf(dx[i], rest[i], m2[i]);
+                        }
+                        if (EXTREMA)
+                            for (int i = 0; i < VEC; ++i) { // selects, no branches: the lanes of a wave disagree element by element
+                                const bool up = !any | (v[i] > hi[i]) | ((v[i] != v[i]) & (hi[i] == hi[i]));
+                                const bool down = !any | (v[i] < lo[i]) | ((v[i] != v[i]) & (lo[i] == lo[i]));
+                                hi[i] = up ? v[i] : hi[i];
+                                at_hi[i] = up ? j0 + j : at_hi[i];
+                                lo[i] = down ? v[i] : lo[i];
+                                at_lo[i] = down ? j0 + j : at_lo[i];
+                            }
+                    }
+                }
+            }
+            if (u < units) {
+                const int64_t c = (int64_t)u * VEC;
+                const bool any = seen > 0;
+                const auto put = [&](uint32_t plane, const vf& v) {
+                    if (plane != kNoPlane) *reinterpret_cast<vf*>(out_d + (int64_t)plane * dim + c) = v;
+                };
+                put(p.sum, s);
+                put(p.mean, s * inv);
+                if (EXTREMA) {
+                    put(p.max, hi);
+                    put(p.min, lo);
+                    if (arg) {
+                        *reinterpret_cast<vi*>(arg + d * 2 * dim + c) = at_hi;
+                        *reinterpret_cast<vi*>(arg + (d * 2 + 1) * dim + c) = at_lo;
+                    }
+                }
+                if (MOMENTS) {
+                    vf var, sd, sd_gate;
+                    for (int i = 0; i < VEC; ++i) {
+                        const float t = m2[i] * inv;
+                        var[i] = t < 0.0f ? 0.0f : t; // a NaN stays
+                        sd[i] = any ? __builtin_sqrtf(var[i] + eps) : 0.0f;
+                        sd_gate[i] = var[i] > 0.0f ? sd[i] : -sd[i];
+                    }
+                    put(p.var, var);
+                    put(p.std, sd);
+                    if (mom) {
+                        *reinterpret_cast<vf*>(mom + d * 2 * dim + c) = m1;
+                        *reinterpret_cast<vf*>(mom + (d * 2 + 1) * dim + c) = sd_gate;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// The backward of all planes in one launch: for every valid slot j of row d (source s, value x = h_src[s, c]) and element c,
+//   grad_src[s, c] += g_sum + g_mean / n + g_var * 2 (x - mean) / n + [var > 0] g_std * (x - mean) / (n std) + [j == at_hi] g_max + [j == at_lo] g_min
+// with the g_* the planes of grad_out[d] that were asked for, n the forward's divisor, std from `mom` (its sign is the [var > 0] gate)
+// and at_* from `arg`: one atomic per (valid edge, element) where the composed path issues one per aggregator.  x - mean is formed as
+// (x - K) - m1, K the value at the first valid slot as the walk meets it again and m1 from `mom`: a mean rounded to fp32 would cost an
+// ulp of |mean| in every term, which autograd's own centring of the two-pass variance does not.  The mean
+// backward's mapping, a lane per float: an atomic instruction of the wave covers 256 contiguous bytes; per 64-column chunk the row's
+// gradients and state are read once into registers.  x is read again only when a var or std plane was asked for; with max / min alone
+// only the winning slots issue an atomic.  grad_src zeroed by the caller; hardware float atomics: summation order varies.
+template <bool CSR>
+__global__ __launch_bounds__(kBlock) void multi_aggregate_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                          int fanout, const float* __restrict__ h_src,
+                                                                          const float* __restrict__ grad_out, const int32_t* __restrict__ arg,
+                                                                          const float* __restrict__ mom, float* __restrict__ grad_src,
+                                                                          int64_t n_dst, int dim, int n_aggr, uint32_t planes) {
+    const auto [lane, wave, n_waves] = wave_rows();
+    const MultiPlanes p = multi_planes(planes);
+    const bool need_x = p.moments(), extrema = p.extrema();
+    const bool every_slot = need_x || p.sum != kNoPlane || p.mean != kNoPlane;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        int32_t mine0;
+        const int n0 = load_chunk(idx, beg, end, lane, &mine0);
+        const float cnt = CSR ? (float)(end - beg) : (float)__builtin_popcountll(__ballot(mine0 >= 0));
+        if (!(cnt > 0.0f)) continue;
+        const float inv = 1.0f / cnt;
+        const float* const g_d = grad_out + d * n_aggr * dim;
+        for (int c0 = 0; c0 < dim; c0 += 64) { // wave-uniform trip count: the shuffles below read lanes that are past `dim`
+            const int c = c0 + lane;
+            float base = 0.0f, coef = 0.0f, m1 = 0.0f, K = 0.0f, g_hi = 0.0f, g_lo = 0.0f;
+            bool any = false; // wave-uniform: a valid slot has been seen
+            int32_t at_hi = -1, at_lo = -1;
+            if (c < dim) {
+                const auto g = [&](uint32_t plane) { return plane != kNoPlane ? g_d[(int64_t)plane * dim + c] : 0.0f; };
+                base = __builtin_fmaf(g(p.mean), inv, g(p.sum));
+                if (need_x) {
+                    m1 = mom[d * 2 * dim + c];
+                    const float sd = mom[(d * 2 + 1) * dim + c];
+                    coef = 2.0f * inv * g(p.var);
+                    if (p.std != kNoPlane && !__builtin_signbit(sd)) coef += g(p.std) * inv / sd;
+                }
+                if (extrema) {
+                    at_hi = p.max != kNoPlane ? arg[d * 2 * dim + c] : -1;
+                    at_lo = p.min != kNoPlane ? arg[(d * 2 + 1) * dim + c] : -1;
+                    g_hi = g(p.max);
+                    g_lo = g(p.min);
+                }
+            }
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                int32_t mine = mine0;
+                int n = n0;
+                if (e0 != beg) n = load_chunk(idx, e0, end, lane, &mine); // wave-uniform
+                const int32_t j0 = (int32_t)(e0 - beg);
+                for (int j = 0; j < n; ++j) {
+                    const int32_t src = __shfl(mine, j);
+                    const bool top = j0 + j == at_hi, bottom = j0 + j == at_lo;
+                    if (src >= 0 && c < dim && (every_slot || top || bottom)) {
+                        float v = base;
+                        if (need_x) {
+                            const float x = h_src[(int64_t)src * dim + c];
+                            K = any ? K : x;
+                            v = __builtin_fmaf(coef, (x - K) - m1, v);
+                        }
+                        v += (top ? g_hi : 0.0f) + (bottom ? g_lo : 0.0f);
+                        unsafeAtomicAdd(grad_src + (int64_t)src * dim + c, v);
+                    }
+                    any |= src >= 0;
+                }
+            }
+        }
+    }
+}
+
 // Relation-typed sum (DGL RelGraphConv's message step, before its weights): out[d, r, :] = sum over the valid edges j of row d with
 // etype_j == r of w_j * h_src[s_j, :], so that out.view(n_dst, R * dim) @ W.view(R * dim, out_dim) is sum_j w_j W[etype_j] h[s_j] in one
 // GEMM.  etype is laid out like the block's index array, and so is w (null: every weight is 1).  The weighted sum's mapping and its
@@ -1759,6 +1959,65 @@ int max_backward_launch(int device, const int32_t* arg, const float* grad_out, f
     return COALA_OK;
 }
 
+// f(std::true_type / std::false_type): a kernel's instantiation with or without a statistic
+template <typename F>
+void dispatch_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// planes of n_aggr output planes: at least one aggregator, every wanted one on a plane of its own below n_aggr
+int planes_check(uint32_t planes, int n_aggr) {
+    if (n_aggr < 1 || n_aggr > kMultiAggregators) return fail(COALA_EINVAL, "bad plane count (1..%d)", kMultiAggregators);
+    uint32_t seen = 0;
+    for (int k = 0; k < kMultiAggregators; ++k) {
+        const uint32_t p = planes >> (4 * k) & 15u;
+        if (p == kNoPlane) continue;
+        if (p >= (uint32_t)n_aggr || (seen >> p & 1u)) return fail(COALA_EINVAL, "bad planes (an output plane >= %d, or used twice)", n_aggr);
+        seen |= 1u << p;
+    }
+    return seen ? COALA_OK : fail(COALA_EINVAL, "bad planes (no aggregator)");
+}
+
+template <bool CSR>
+int multi_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* h_src, float* out, int32_t* arg, float* mom,
+                 int64_t n_dst, int dim, int n_aggr, uint32_t planes, float eps, void* stream) {
+    if (int rc = shape_check<CSR>(n_dst, fanout, dim)) return rc;
+    if (int rc = planes_check(planes, n_aggr)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !h_src || !out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const MultiPlanes p = multi_planes(planes);
+    dispatch_vec(vec4_ok(dim, h_src, out) && vec4_ok(dim, arg, mom), [&](auto vec) {
+        dispatch_bool(p.moments(), [&](auto moments) {
+            dispatch_bool(p.extrema(), [&](auto extrema) {
+                hipLaunchKernelGGL((multi_aggregate_kernel<decltype(vec)::value, CSR, decltype(moments)::value, decltype(extrema)::value>),
+                                   row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx, fanout, h_src, out, arg, mom, n_dst, dim,
+                                   n_aggr, planes, eps);
+            });
+        });
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+template <bool CSR>
+int multi_backward_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* h_src, const float* grad_out,
+                          const int32_t* arg, const float* mom, float* grad_src, int64_t n_dst, int dim, int n_aggr, uint32_t planes,
+                          void* stream) {
+    if (int rc = shape_check<CSR>(n_dst, fanout, dim)) return rc;
+    if (int rc = planes_check(planes, n_aggr)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    const MultiPlanes p = multi_planes(planes);
+    if ((CSR && !indptr) || !idx || !grad_out || !grad_src || (p.moments() && (!h_src || !mom)) || (p.extrema() && !arg))
+        return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(multi_aggregate_backward_kernel<CSR>, row_grid(n_dst), dim3(kBlock), 0, (hipStream_t)stream, indptr, idx, fanout, h_src,
+                       grad_out, arg, mom, grad_src, n_dst, dim, n_aggr, planes);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
 template <bool CSR>
 int rel_sum_launch(int device, const int64_t* indptr, const int32_t* idx, const int32_t* etype, const float* w, int fanout, const float* h_src,
                    float* out, int64_t n_dst, int num_rels, int dim, void* stream) {
@@ -2329,6 +2588,28 @@ int coala_block_max_aggregate_csr(int device, const int64_t* indptr, const int32
 int coala_block_max_aggregate_backward(int device, const int32_t* arg, const float* grad_out, float* grad_src, int64_t n_dst, int dim,
                                        void* stream) {
     return max_backward_launch(device, arg, grad_out, grad_src, n_dst, dim, stream);
+}
+
+int coala_block_multi_aggregate(int device, const int32_t* nbr, const float* h_src, float* out, int32_t* arg, float* mom, int64_t n_dst,
+                                int fanout, int dim, int n_aggr, uint32_t planes, float eps, void* stream) {
+    return multi_launch<false>(device, nullptr, nbr, fanout, h_src, out, arg, mom, n_dst, dim, n_aggr, planes, eps, stream);
+}
+
+int coala_block_multi_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int32_t* arg,
+                                    float* mom, int64_t n_dst, int dim, int n_aggr, uint32_t planes, float eps, void* stream) {
+    return multi_launch<true>(device, indptr, indices, 0, h_src, out, arg, mom, n_dst, dim, n_aggr, planes, eps, stream);
+}
+
+int coala_block_multi_aggregate_backward(int device, const int32_t* nbr, const float* h_src, const float* grad_out, const int32_t* arg,
+                                         const float* mom, float* grad_src, int64_t n_dst, int fanout, int dim, int n_aggr, uint32_t planes,
+                                         void* stream) {
+    return multi_backward_launch<false>(device, nullptr, nbr, fanout, h_src, grad_out, arg, mom, grad_src, n_dst, dim, n_aggr, planes, stream);
+}
+
+int coala_block_multi_aggregate_backward_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src,
+                                             const float* grad_out, const int32_t* arg, const float* mom, float* grad_src, int64_t n_dst,
+                                             int dim, int n_aggr, uint32_t planes, void* stream) {
+    return multi_backward_launch<true>(device, indptr, indices, 0, h_src, grad_out, arg, mom, grad_src, n_dst, dim, n_aggr, planes, stream);
 }
 
 int coala_block_rel_sum(int device, const int32_t* nbr, const int32_t* etype, const float* w, const float* h_src, float* out, int64_t n_dst,

@@ -426,4 +426,34 @@ PYBIND11_MODULE(_coala_pybind, m) {
             ptr<float>(grad_v), ptr<float>(grad_qt), ptr<float>(grad_time_parts), parts, n_dst, fanout, heads, dim, time_dim, scale,
             stream_of(stream)));
     });
+    // multi-statistic aggregation on a block (coala_block_multi_aggregate*); state or a table that is not wanted is passed as 0
+    m.def("block_multi_aggregate", [](int device, uint64_t nbr, uint64_t h_src, uint64_t out, uint64_t arg, uint64_t mom, int64_t n_dst,
+                                      int fanout, int dim, int n_aggr, uint32_t planes, float eps, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_multi_aggregate(device, ptr<const int32_t>(nbr), ptr<const float>(h_src), ptr<float>(out), ptr<int32_t>(arg),
+                                          ptr<float>(mom), n_dst, fanout, dim, n_aggr, planes, eps, stream_of(stream)));
+    });
+    m.def("block_multi_aggregate_csr", [](int device, uint64_t indptr, uint64_t indices, uint64_t h_src, uint64_t out, uint64_t arg,
+                                          uint64_t mom, int64_t n_dst, int dim, int n_aggr, uint32_t planes, float eps, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_multi_aggregate_csr(device, ptr<const int64_t>(indptr), ptr<const int32_t>(indices), ptr<const float>(h_src),
+                                              ptr<float>(out), ptr<int32_t>(arg), ptr<float>(mom), n_dst, dim, n_aggr, planes, eps,
+                                              stream_of(stream)));
+    });
+    m.def("block_multi_aggregate_backward", [](int device, uint64_t nbr, uint64_t h_src, uint64_t grad_out, uint64_t arg, uint64_t mom,
+                                               uint64_t grad_src, int64_t n_dst, int fanout, int dim, int n_aggr, uint32_t planes,
+                                               uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_multi_aggregate_backward(device, ptr<const int32_t>(nbr), ptr<const float>(h_src), ptr<const float>(grad_out),
+                                                   ptr<const int32_t>(arg), ptr<const float>(mom), ptr<float>(grad_src), n_dst, fanout, dim,
+                                                   n_aggr, planes, stream_of(stream)));
+    });
+    m.def("block_multi_aggregate_backward_csr", [](int device, uint64_t indptr, uint64_t indices, uint64_t h_src, uint64_t grad_out,
+                                                   uint64_t arg, uint64_t mom, uint64_t grad_src, int64_t n_dst, int dim, int n_aggr,
+                                                   uint32_t planes, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_multi_aggregate_backward_csr(device, ptr<const int64_t>(indptr), ptr<const int32_t>(indices), ptr<const float>(h_src),
+                                                       ptr<const float>(grad_out), ptr<const int32_t>(arg), ptr<const float>(mom),
+                                                       ptr<float>(grad_src), n_dst, dim, n_aggr, planes, stream_of(stream)));
+    });
 }

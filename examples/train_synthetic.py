@@ -11,6 +11,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --sage_aggregator pool
   python examples/train_synthetic.py --sage_aggregator lstm --dim 128
   python examples/train_synthetic.py --model_type gin --gin_aggregator max
+  python examples/train_synthetic.py --model_type pna --pna_aggregators mean,max,min,std --num_towers 2
   python examples/train_synthetic.py --model_type rgcn --num_rels 4 --rgcn_regularizer basis --num_bases 2
   python examples/train_synthetic.py --model_type rgcn --num_rels 4 --sampler rel --rel_fan_out "10,3,0,-1;5,5,5,5"
   python examples/train_synthetic.py --model_type rgat --num_rels 4 --num_heads 4 --sampler rel --rel_fan_out "10,3,0,-1;5,5,5,5"
@@ -43,7 +44,8 @@ import torch  # noqa: E402
 
 from COALA_GNN import COALA_GNN_DataLoader, MetaPath2Vec, MPI_Comm_Manager, Node2Vec, Node_Distributor, NodeEmbedding, RowWiseAdagrad, SparseAdagrad, SparseAdam, SparseSGD, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
-from COALA_GNN.harness import GAT, GCN, GIN, HGT, RGAT, RGCN, RSAGE, SAGE, TGAT, GATv2, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
+from COALA_GNN.nn import pna_delta  # noqa: E402
+from COALA_GNN.harness import GAT, GCN, GIN, HGT, PNA, RGAT, RGCN, RSAGE, SAGE, TGAT, GATv2, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
 from COALA_GNN.sampler import (CSCGraph, EdgePredictionSampler, LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler,  # noqa: E402
                                TemporalEdgePredictionSampler, TemporalNeighborSampler, UniformNegativeSampler, reverse_edge_ids,
                                sort_csc_by_etype)
@@ -263,9 +265,10 @@ def main():
     # accepted so that the reference's command lines (examples/4GB_script.sh, Cache_compare_script.sh, Distribution_compare_script.sh) run as they are
     ap.add_argument("--num_layers", type=int, default=None, help="must equal the number of fan-outs when given")
     ap.add_argument("--feat_cpu", action="store_true", help="features in pinned host memory: always the case here (the NVMe tier is out of scope)")
-    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "gatv2", "sage", "gcn", "gin", "rgcn", "rgat", "rsage", "hgt", "pinsage", "tgat"],
+    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "gatv2", "sage", "gcn", "gin", "pna", "rgcn", "rgat", "rsage", "hgt", "pinsage", "tgat"],
                     help="sage: GraphSAGE (--sage_aggregator); gat: GAT with --num_heads heads (native attention aggregation); gatv2: the same model on GATv2Conv layers (--share_weights); gcn: GraphConv, "
-                         "norm='both'; gin: GINConv layers (--gin_aggregator), an MLP in each; rgcn: RelGraphConv layers, one weight matrix per edge "
+                         "norm='both'; gin: GINConv layers (--gin_aggregator), an MLP in each; pna: PNAConv layers (--pna_aggregators, --pna_scalers, --num_towers; "
+                         "every aggregator from one native multi-statistic pass); rgcn: RelGraphConv layers, one weight matrix per edge "
                          "type (--num_rels synthetic types, the source node's id modulo --num_rels; native relation-typed sum); rgat: RelGATConv layers, "
                          "a GATConv of --num_heads heads per edge type, summed (native relation-typed attention); rsage: RelSAGEConv layers, a SAGEConv "
                          "'gcn' per edge type, summed; pinsage: WeightedSAGEConv layers on the visit counts of --sampler pinsage; tgat: TGATConv layers of "
@@ -279,6 +282,10 @@ def main():
                     help="aggregator of --model_type sage; pool: the maximum of relu(fc_pool(h)) over the neighbours (native max aggregation); "
                          "lstm: an LSTM over the neighbours in slot order (LSTMSAGEConv, native for feature widths that are multiples of 32 up to 256)")
     ap.add_argument("--gin_aggregator", type=str, default="sum", choices=["sum", "max", "mean"], help="aggregator of --model_type gin")
+    ap.add_argument("--pna_aggregators", type=str, default="mean,max,min,std", help="--model_type pna: comma-separated, from mean, max, min, std, var, sum")
+    ap.add_argument("--pna_scalers", type=str, default="identity,amplification,attenuation",
+                    help="--model_type pna: comma-separated, from identity, amplification, attenuation")
+    ap.add_argument("--num_towers", type=int, default=1, help="--model_type pna: towers of every layer whose widths they divide")
     ap.add_argument("--seed", type=int, default=0,
                     help="seed of torch's generators, set before the model is built: its initial weights (and dropout masks) are the same "
                          "from run to run, as the synthetic data and the samplers' draws already are; negative: not seeded")
@@ -400,7 +407,7 @@ def main():
         edata, prob = {"w": w}, "w"
     if args.use_edge_weight and prob is None:
         ap.error("--use_edge_weight needs --edge_weights random")
-    ew = "w" if args.use_edge_weight and args.model_type not in ("gat", "gatv2", "gin", "rgcn", "rgat", "rsage", "hgt") else None
+    ew = "w" if args.use_edge_weight and args.model_type not in ("gat", "gatv2", "gin", "pna", "rgcn", "rgat", "rsage", "hgt") else None
     ndata = {"labels": labels}
     if args.sampler == "temporal":   # a timestamp per edge (sorted inside every row) and a query time per node, which the sampler reads as seed_time
         edata = dict(edata, ts=edge_times(indptr, seed=1, t_max=T_MAX))
@@ -446,6 +453,9 @@ def main():
         model = GCN(args.dim, args.hidden_channels, args.num_classes, len(fan_out), edge_weight=ew).to(device)
     elif args.model_type == "gin":
         model = GIN(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.gin_aggregator).to(device)
+    elif args.model_type == "pna":
+        model = PNA(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.pna_aggregators.split(","), args.pna_scalers.split(","),
+                    pna_delta(g), args.num_towers).to(device)
     elif args.model_type == "rgat":
         model = RGAT(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_rels, args.num_heads).to(device)
     elif args.model_type == "hgt":

@@ -688,6 +688,41 @@ int coala_block_max_aggregate_csr(int device, const int64_t* indptr, const int32
                                   int64_t n_dst, int dim, void* stream);
 int coala_block_max_aggregate_backward(int device, const int32_t* arg, const float* grad_out, float* grad_src, int64_t n_dst, int dim,
                                        void* stream);
+/* Multi-statistic aggregation (what PNAConv reduces with): any of sum, mean, max, min, var, std of row d's valid neighbour rows from
+ * one read of them, out fp32 [n_dst, n_aggr, dim].  `planes` names the output plane of each aggregator, 4 bits each in the canonical
+ * order sum, mean, max, min, var, std (bits 0..3 = sum, ..., 20..23 = std), 15 = not wanted: the caller's order of aggregators is
+ * honoured without a permuting copy.  Refused with COALA_EINVAL: n_aggr outside 1..6, no aggregator, a plane >= n_aggr, a plane named
+ * twice, and the bad shapes of the mean (fan-out 1..32, dim >= 1, n_dst >= 0); n_dst == 0 launches nothing.  nbr / indptr / indices and
+ * h_src as for the mean; one wave per row in both forms, the same code on the same lanes: bit-identical on a row both can express.
+ *   sum, mean   the plain sum from +0 in slot order, and that sum times 1 / n, n the mean's divisor (valid entries of a fixed row,
+ *               the length of a CSR row): the mean plane has the bits of coala_block_mean_aggregate.
+ *   var, std    shifted running moments: with K the value at the row's first valid slot and y = x - K, the k-th valid slot updates
+ *               dx = y - m1, m1 += dx / k, m2 += dx (y - m1) (Welford's update, by fma); var = max(m2 / n, 0) (the population
+ *               variance), std = sqrt(var + eps).  A row of one neighbour or of equal values gives var == 0 and std == sqrt(eps)
+ *               exactly; a table of mean 1e3 and spread 1 keeps its variance to fp32 accuracy, which E[x^2] - E[x]^2 does not.
+ *   max, min    the rule of coala_block_max_aggregate and its mirror image: the first slot wins ties, a NaN propagates.
+ * A row without a valid entry gives 0 in every plane.  State for the backward, either may be NULL (inference, or no such plane):
+ * arg int32 [n_dst, 2, dim] = the slot offset inside the row of the max and of the min winner (-1: no valid entry) -- the slot, not
+ * the source, so that a source standing twice in a row receives an extremum's gradient once; mom fp32 [n_dst, 2, dim] = m1, the mean
+ * less the value at the row's first valid slot (the backward meets that value again on its walk and forms x - mean as (x - K) - m1,
+ * without an ulp of |mean|), and std with its sign bit set where var == 0.
+ * Backward, all planes in one launch; grad_out fp32 [n_dst, n_aggr, dim], the same `planes`; for a valid slot j (source s, x = h_src[s, c]):
+ *   grad_src[s, c] += g_sum + g_mean / n + g_var 2 (x - mean) / n + [var > 0] g_std (x - mean) / (n std) + [j == at_hi] g_max + [j == at_lo] g_min
+ * ([var > 0] is torch's relu subgradient), one hardware float atomic per (valid edge, element): the caller zeroes grad_src [n_src, dim],
+ * the order varies, so the gradient is not bitwise reproducible.  h_src and mom are read only with a var or std plane, arg only with a
+ * max or min plane (NULL otherwise).
+ * Bytes per row of deg valid edges: forward reads deg * (4 dim + 4), writes 4 dim n_aggr and 16 dim of state; backward reads
+ * 4 dim n_aggr + 16 dim + 4 deg (+ 4 dim deg with var or std) and adds 4 dim deg through atomics (at most 8 dim with max / min alone). */
+int coala_block_multi_aggregate(int device, const int32_t* nbr, const float* h_src, float* out, int32_t* arg, float* mom, int64_t n_dst,
+                                int fanout, int dim, int n_aggr, uint32_t planes, float eps, void* stream);
+int coala_block_multi_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src, float* out, int32_t* arg,
+                                    float* mom, int64_t n_dst, int dim, int n_aggr, uint32_t planes, float eps, void* stream);
+int coala_block_multi_aggregate_backward(int device, const int32_t* nbr, const float* h_src, const float* grad_out, const int32_t* arg,
+                                         const float* mom, float* grad_src, int64_t n_dst, int fanout, int dim, int n_aggr, uint32_t planes,
+                                         void* stream);
+int coala_block_multi_aggregate_backward_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src,
+                                             const float* grad_out, const int32_t* arg, const float* mom, float* grad_src, int64_t n_dst,
+                                             int dim, int n_aggr, uint32_t planes, void* stream);
 /* Relation-typed sum (the message step of DGL's RelGraphConv, before its weights): out[d, r, :] = sum over the valid j of row d with
  * etype[d, j] == r of w[d, j] * h_src[nbr[d, j], :], so that out viewed as [n_dst, num_rels * dim] times W viewed as [num_rels * dim, o]
  * is sum_j w_j W[etype_j] h_src[s_j] in one GEMM.  etype int32, one value per neighbour slot, laid out like nbr ([n_dst, fanout]) or
