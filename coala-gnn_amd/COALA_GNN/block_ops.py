@@ -2,7 +2,8 @@
 sum aggregation (DGL's u_mul_e_sum, the edge_weight= path of GraphConv / SAGEConv), max aggregation (DGL's fn.max: SAGEConv's "pool",
 GINConv's "max"), LSTM aggregation (SAGEConv's "lstm": coala_lstm.hip, on the matrix units), the relation-typed sum (RelGraphConv's message step), GAT / GATv2 attention aggregation, scaled dot-product
 attention (DotGatConv's and HGTConv's message step), temporal attention over a fused time encoding (TGATConv's message step, fixed
-blocks alone) and relation-typed GAT attention (RelGATConv's message step), on fixed blocks and on the ragged CSR blocks of full layers.  pair_dot (DGL's u_dot_v on a pair graph: a link predictor's scores) is the one op here
+blocks alone) and relation-typed GAT attention (RelGATConv's message step), on fixed blocks and on the ragged CSR blocks of full layers; and the
+message-passing primitives on per-edge tensors (DGL's u_dot_v, edge_softmax, u_mul_e_sum: one Function each for both block forms).  pair_dot (DGL's u_dot_v on a pair graph: a link predictor's scores) is the one op here
 that takes no block.  One kernel forward, one backward each; the kernels are in coala-gnn_amd/csrc/coala_block_ops.hip
 (C ABI: coala_block_*).  Every op has one forward and one backward body for both block forms, which take the C entry and the block's
 index tensors -- (nbr,) or (indptr, indices); the two Function classes of an op are shells that name the entries, and they stay two
@@ -373,6 +374,105 @@ class _MultiAggregateCSR(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         return (_multi_backward(ctx, grad_out, _lib.coala_block_multi_aggregate_backward_csr),) + (None,) * 5
+
+
+def _edge_entry(name, index):
+    """The C entry of a message-passing primitive for the block form of `index`: name, or name_csr."""
+    return getattr(_lib, name if len(index) == 1 else name + "_csr")
+
+
+def _edge_shape(index, heads):
+    """A per-edge tensor of this block: [n_dst, fanout, H] beside nbr, [E, H] beside indices."""
+    return tuple(index[-1].shape) + (heads,)
+
+
+def _u_dot_v(u, v, index):
+    """e[slot, h] = <u[s, h, :], v[d, h, :]>, 0 on a padding slot (coala_block_u_dot_v[_csr]); u, v contiguous fp32."""
+    idx, n_dst, fan = _block(index)
+    e = torch.empty(_edge_shape(index, u.shape[1]), dtype=torch.float32, device=u.device)
+    _capi.check(_edge_entry("coala_block_u_dot_v", index)(u.device.index or 0, *idx, u.data_ptr(), v.data_ptr(), e.data_ptr(), n_dst, *fan,
+                                                          u.shape[1], u.shape[2], current_stream()))
+    return e
+
+
+def _u_mul_e_sum(u, e, index):
+    """out[d, h, :] = sum over row d's valid slots of e[slot, h] * u[s, h, :] (coala_block_u_mul_e_sum[_csr]); u, e contiguous fp32."""
+    idx, n_dst, fan = _block(index)
+    out = torch.empty((n_dst,) + tuple(u.shape[1:]), dtype=torch.float32, device=u.device)
+    _capi.check(_edge_entry("coala_block_u_mul_e_sum", index)(u.device.index or 0, *idx, u.data_ptr(), e.data_ptr(), out.data_ptr(), n_dst, *fan,
+                                                              u.shape[1], u.shape[2], current_stream()))
+    return out
+
+
+def _e_mul_v_scatter(w, x, n_src, index):
+    """grad_u[s, h, :] = sum over the valid slots with source s of w[slot, h] * x[d, h, :] (coala_block_e_mul_v_scatter[_csr]): float
+    atomics, not bitwise reproducible."""
+    idx, n_dst, fan = _block(index)
+    grad_u = torch.zeros((n_src,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    _capi.check(_edge_entry("coala_block_e_mul_v_scatter", index)(x.device.index or 0, *idx, w.data_ptr(), x.data_ptr(), grad_u.data_ptr(), n_dst,
+                                                                  *fan, x.shape[1], x.shape[2], current_stream()))
+    return grad_u
+
+
+class _UDotV(torch.autograd.Function):
+    """Block.u_dot_v on either block form, index = (nbr,) or (indptr, indices).  The primitives are each other's gradients: grad_v is
+    u_mul_e_sum(u, grad_e), grad_u the reverse scatter of grad_e * v."""
+
+    @staticmethod
+    def forward(ctx, u, v, *index):
+        u, v = u.contiguous(), v.contiguous()
+        ctx.save_for_backward(u, v, *index)
+        return _u_dot_v(u, v, index)
+
+    @staticmethod
+    def backward(ctx, grad_e):
+        u, v, *index = ctx.saved_tensors
+        g = grad_e.contiguous()
+        grad_u = _e_mul_v_scatter(g, v, u.shape[0], index) if ctx.needs_input_grad[0] else None
+        grad_v = _u_mul_e_sum(u, g, index) if ctx.needs_input_grad[1] else None
+        return (grad_u, grad_v) + (None,) * len(index)
+
+
+class _UMulESum(torch.autograd.Function):
+    """Block.u_mul_e_sum on either block form: grad_e is u_dot_v(u, grad_out), grad_u the reverse scatter of e * grad_out."""
+
+    @staticmethod
+    def forward(ctx, u, e, *index):
+        u, e = u.contiguous(), e.contiguous()
+        ctx.save_for_backward(u, e, *index)
+        return _u_mul_e_sum(u, e, index)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        u, e, *index = ctx.saved_tensors
+        g = grad_out.contiguous()
+        grad_u = _e_mul_v_scatter(e, g, u.shape[0], index) if ctx.needs_input_grad[0] else None
+        grad_e = _u_dot_v(u, g, index) if ctx.needs_input_grad[1] else None
+        return (grad_u, grad_e) + (None,) * len(index)
+
+
+def _edge_softmax(name, index, *tensors):
+    """coala_block_edge_softmax[_backward][_csr] on contiguous fp32 per-edge tensors -> a new one of their shape."""
+    idx, n_dst, fan = _block(index)
+    out = torch.empty_like(tensors[0])
+    _capi.check(_edge_entry(name, index)(out.device.index or 0, *idx, *(t.data_ptr() for t in tensors), out.data_ptr(), n_dst, *fan,
+                                         out.shape[-1], current_stream()))
+    return out
+
+
+class _EdgeSoftmax(torch.autograd.Function):
+    """Block.edge_softmax on either block form; the backward reads the saved output alone."""
+
+    @staticmethod
+    def forward(ctx, e, *index):
+        a = _edge_softmax("coala_block_edge_softmax", index, e.contiguous())
+        ctx.save_for_backward(a, *index)
+        return a
+
+    @staticmethod
+    def backward(ctx, grad_a):
+        a, *index = ctx.saved_tensors
+        return (_edge_softmax("coala_block_edge_softmax_backward", index, a, grad_a.contiguous()),) + (None,) * len(index)
 
 
 def _gat_forward(ctx, el, er, feat_src, entry, index, negative_slope):

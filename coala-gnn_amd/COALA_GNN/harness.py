@@ -39,13 +39,13 @@ class SageMean(torch.nn.Module):
 
 class GAT(torch.nn.Module):
     """examples/models.py:GAT: n_layers GATConv layers of num_heads heads, no activation between them (as in the reference), the
-    heads flattened between layers; the last layer's heads are averaged and passed through log_softmax."""
+    heads flattened between layers; the last layer's heads are averaged and passed through log_softmax.  attn_drop is every layer's."""
 
-    def __init__(self, in_feats, n_hidden, n_classes, n_layers, num_heads):
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, num_heads, attn_drop=0.0):
         super().__init__()
         dims = [in_feats] + [n_hidden * num_heads] * (n_layers - 1)
         outs = [n_hidden] * (n_layers - 1) + [n_classes]
-        self.layers = torch.nn.ModuleList(GATConv((dims[i], dims[i]), outs[i], num_heads) for i in range(n_layers))
+        self.layers = torch.nn.ModuleList(GATConv((dims[i], dims[i]), outs[i], num_heads, attn_drop=attn_drop) for i in range(n_layers))
 
     def forward(self, blocks, x):
         h = x
@@ -289,13 +289,13 @@ class HGT(torch.nn.Module):
 
 class DotGAT(torch.nn.Module):
     """GAT's shape on DotGatConv layers: n_layers layers of num_heads heads, no activation between them, the heads flattened between
-    layers; the last layer's heads are averaged and passed through log_softmax."""
+    layers; the last layer's heads are averaged and passed through log_softmax.  attn_drop is every layer's."""
 
-    def __init__(self, in_feats, n_hidden, n_classes, n_layers, num_heads):
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, num_heads, attn_drop=0.0):
         super().__init__()
         dims = [in_feats] + [n_hidden * num_heads] * (n_layers - 1)
         outs = [n_hidden] * (n_layers - 1) + [n_classes]
-        self.layers = torch.nn.ModuleList(DotGatConv(dims[i], outs[i], num_heads) for i in range(n_layers))
+        self.layers = torch.nn.ModuleList(DotGatConv(dims[i], outs[i], num_heads, attn_drop=attn_drop) for i in range(n_layers))
 
     def forward(self, blocks, x):
         h = x

@@ -43,9 +43,12 @@ class GATConv(torch.nn.Module):
         fc_src.weight [H * D, in_src], fc_dst.weight [H * D, in_dst] (no bias), attn_l [1, H, D], attn_r [1, H, D], bias [H * D].
     Initialisation: Xavier-normal with the gain of relu for fc_src, fc_dst, attn_l and attn_r; bias zero.
     h_dst must be the destination rows of h_src: block.dst_rows(h_src) (h_src[:num_dst] unless the block is owner-bucketed).
-    Attention dropout and residual connections are not provided."""
+    attn_drop (DGL's argument; the GAT paper trains with 0.6) drops attention weights: with attn_drop > 0 in training mode the fused
+    kernel gives way to the chain u_add_v -> leaky_relu -> Block.edge_softmax -> dropout -> Block.u_mul_e_sum, whose only per-edge
+    tensors are [slots, H] scalars; in eval mode, or with attn_drop == 0, the layer runs the fused call exactly as without the argument.
+    Residual connections are not provided."""
 
-    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, negative_slope=0.2, bias=True, activation=None):
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, negative_slope=0.2, bias=True, activation=None, attn_drop=0.0):
         super().__init__()
         in_src, in_dst = in_feats if isinstance(in_feats, (tuple, list)) else (in_feats, in_feats)
         self._num_heads, self._out_feats = num_heads, out_feats
@@ -55,6 +58,7 @@ class GATConv(torch.nn.Module):
         self.attn_r = torch.nn.Parameter(torch.empty(1, num_heads, out_feats))
         self.bias = torch.nn.Parameter(torch.empty(num_heads * out_feats)) if bias else None
         self.feat_drop = torch.nn.Dropout(feat_drop)
+        self.attn_drop = float(attn_drop)
         self.negative_slope = negative_slope
         self.activation = activation
         self.reset_parameters()
@@ -73,7 +77,11 @@ class GATConv(torch.nn.Module):
         feat_dst = self.fc_dst(self.feat_drop(h_dst)).view(-1, H, D)
         el = (feat_src * self.attn_l).sum(-1)
         er = (feat_dst * self.attn_r).sum(-1)
-        rst = block.gat_aggregate(el, er, feat_src, self.negative_slope)
+        if self.training and self.attn_drop > 0.0:
+            e = torch.nn.functional.leaky_relu(block.u_add_v(el, er), self.negative_slope)
+            rst = block.u_mul_e_sum(feat_src, torch.nn.functional.dropout(block.edge_softmax(e), self.attn_drop))
+        else:
+            rst = block.gat_aggregate(el, er, feat_src, self.negative_slope)
         if self.bias is not None:
             rst = rst + self.bias.view(1, H, D)
         if self.activation is not None:
@@ -98,7 +106,8 @@ class GATv2Conv(torch.nn.Module):
     the layer takes feat_dst = block.dst_rows(feat_src) -- DGL's feat_src[:num_dst], right on owner-bucketed blocks too -- instead
     of a second projection; h_dst is then not read.  Otherwise h_dst must be the destination rows of h_src: block.dst_rows(h_src).
     Initialisation: Xavier-normal with the gain of relu for fc_src.weight, fc_dst.weight and attn; biases zero.
-    Attention dropout and residual connections are not provided."""
+    Attention dropout is not provided: the score is not one of Block's edge primitives (u_dot_v, u_add_v), so there is no chain to drop weights in;
+    residual connections are not provided either."""
 
     def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, negative_slope=0.2, bias=True, share_weights=False, activation=None):
         super().__init__()
@@ -506,7 +515,8 @@ class RelGATConv(torch.nn.Module):
     Block.rel_gat_aggregate reads them in its packed form.  The per-relation pair counts cost one host read per layer call, and the packed form's row check a second.  The
     destination side is one [num_dst, in] x [in, R * H] GEMM with the vectors fc_weight[r, h]^T attn_r[r, h].
     One difference from DGL: HeteroGraphConv skips a relation that has no edge anywhere in the block, bias included; this layer adds
-    every relation's bias always.  Attention dropout and residual connections are not provided."""
+    every relation's bias always.  Attention dropout is not provided: the score is not one of Block's edge primitives (u_dot_v, u_add_v), so there is no chain to drop weights in (the
+    softmax runs per relation); residual connections are not provided either."""
 
     def __init__(self, in_feats, out_feats, num_heads, num_rels, feat_drop=0.0, negative_slope=0.2, bias=True, activation=None):
         super().__init__()
@@ -633,11 +643,13 @@ class DotGatConv(torch.nn.Module):
     A destination without an in-edge gets zeros (DGL's allow_zero_in_degree=True).  Parameters, DGL's names and shapes: fc.weight
     [H * D, in_feats] for an int in_feats (one projection for both sides), fc_src.weight [H * D, in_src] and fc_dst.weight
     [H * D, in_dst] for a pair; no bias.  Initialisation: torch.nn.Linear's default, as in DGL.  The attention step is
-    Block.dot_gat_aggregate, a native kernel.  get_attention is not provided."""
+    Block.dot_gat_aggregate, a native kernel.  attn_drop > 0 in training mode replaces it by the chain Block.u_dot_v * scale ->
+    Block.edge_softmax -> dropout -> Block.u_mul_e_sum (per-edge tensors of [slots, H] scalars alone); in eval mode, or with
+    attn_drop == 0, the fused call runs exactly as without the argument.  get_attention is not provided."""
 
-    def __init__(self, in_feats, out_feats, num_heads):
+    def __init__(self, in_feats, out_feats, num_heads, attn_drop=0.0):
         super().__init__()
-        self._num_heads, self._out_feats = num_heads, out_feats
+        self._num_heads, self._out_feats, self.attn_drop = num_heads, out_feats, float(attn_drop)
         if isinstance(in_feats, (tuple, list)):
             self.fc_src = torch.nn.Linear(in_feats[0], out_feats * num_heads, bias=False)
             self.fc_dst = torch.nn.Linear(in_feats[1], out_feats * num_heads, bias=False)
@@ -653,6 +665,9 @@ class DotGatConv(torch.nn.Module):
             q = block.dst_rows(k) if fc_dst is fc_src else fc_dst(block.dst_rows(h_src)).view(-1, H, D)
         else:
             q = fc_dst(h_dst).view(-1, H, D)
+        if self.training and self.attn_drop > 0.0:
+            a = block.edge_softmax(block.u_dot_v(k, q) * float(D) ** -0.5)
+            return block.u_mul_e_sum(k, torch.nn.functional.dropout(a, self.attn_drop))
         return block.dot_gat_aggregate(q, k, k, scale=float(D) ** -0.5)
 
 
@@ -792,7 +807,8 @@ class HGTConv(torch.nn.Module):
     (the score is linear in K).  One Block.dot_gat_aggregate call in its packed form then does the softmax over all of a node's
     in-edges and the weighted sum, in a native kernel that needs no edge types.  Host reads per call: the node counts per type (source
     and destination side together, one read; they also carry the range check) and the pair counts per relation (one read).
-    Attention dropout is not provided."""
+    Attention dropout is not provided: the score is not one of Block's edge primitives (u_dot_v, u_add_v), so there is no chain to drop weights in
+    (it is typed through a per-relation matrix)."""
 
     def __init__(self, in_size, head_size, num_heads, num_ntypes, num_etypes, dropout=0.2, use_norm=False):
         super().__init__()

@@ -13,7 +13,7 @@ from COALA_GNN_Pybind import _capi, current_stream
 
 from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
                         _MeanAggregateCSR, _LSTMAggregate, _LSTMAggregateCSR, LSTM_HIDDEN_STEP, LSTM_MAX_HIDDEN, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _TimeAttnAggregate,
-                        _WeightedSum, _WeightedSumCSR, _MultiAggregate, _MultiAggregateCSR, multi_planes)
+                        _WeightedSum, _WeightedSumCSR, _MultiAggregate, _MultiAggregateCSR, multi_planes, _UDotV, _UMulESum, _EdgeSoftmax)
 
 __all__ = ["NeighborSampler", "LaborSampler", "RelNeighborSampler", "RandomWalkNeighborSampler", "PinSAGESampler", "random_walk", "sort_csc_by_etype",
            "check_etype_sorted", "CSCGraph", "Block", "ITEM_LIMIT", "EID", "EdgePredictionSampler", "as_edge_prediction_sampler",
@@ -260,7 +260,10 @@ class _EdgeData(dict):
 class Block(object):
     """One message-flow block: dst node d aggregates src rows nbr[d, j] >= 0 (fixed-stride form, a fixed fan-out), or
     indices[indptr[d]:indptr[d+1]] (ragged CSR form, a full layer: nbr is None).
-    The first num_dst source nodes ARE the destination nodes (DGL's to_block convention)."""
+    The first num_dst source nodes ARE the destination nodes (DGL's to_block convention).
+    A per-edge tensor (what u_dot_v, u_add_v and edge_softmax return and u_mul_e_sum takes) has one value per neighbour slot and head,
+    in the order of edata['_ID']: [num_dst, fanout, H] on a fixed block, [E, H] on a ragged one.  Padding slots (nbr < 0) hold 0 on
+    output and are never read on input."""
 
     def __init__(self, src_nodes, nbr, num_dst, graph=None, dst_in_src=None, dst_nodes=None, owner_counts=None, owner_counts_host=None,
                  indptr=None, indices=None, eid=None, edata_graph=None, edata_lazy=None):
@@ -394,6 +397,96 @@ class Block(object):
         valid = (self.nbr >= 0).to(device=dev, dtype=h_src.dtype)
         idx = self.nbr.clamp_min(0).to(device=dev, dtype=torch.int64)
         return (h_src[idx] * (w * valid).view(tuple(valid.shape) + ones)).sum(1)
+
+    # ---- message-passing primitives (DGL's dgl.ops): scores, a softmax over them and a sum with them, as per-edge tensors
+    def _edge_check(self, e, heads=None):
+        """e must be a per-edge tensor of this block, with `heads` heads when given."""
+        slots = self.indices if self.nbr is None else self.nbr
+        if e.dim() != slots.dim() + 1 or tuple(e.shape[:-1]) != tuple(slots.shape) or heads not in (None, e.shape[-1]):
+            raise ValueError(f"a per-edge tensor of shape {tuple(e.shape)}: this block takes {tuple(slots.shape) + (heads or 'H',)}")
+
+    def _edge_slots(self, dev):
+        """(row, local source index, slot position) of every valid edge, int64 on `dev`."""
+        rows, src = self._slots(dev)
+        at = (src >= 0).nonzero().squeeze(1)
+        return rows[at], src[at], at
+
+    def _edge_tensor(self, at, values):
+        """values [valid edges, H] -> the per-edge tensor with them at the slots `at` and 0 on padding."""
+        slots = self.indices if self.nbr is None else self.nbr
+        flat = torch.zeros((slots.numel(), values.shape[1]), dtype=values.dtype, device=values.device)
+        return flat.index_put((at,), values).view(tuple(slots.shape) + (values.shape[1],))
+
+    def _edge_native(self, *tensors):
+        """The native index when every tensor is contiguous fp32 on the GPU with 1..16 heads (the axis before the last of a
+        [.., H, D] table, the last of a per-edge tensor: pass those as (e, -1)), and the block has one; None otherwise."""
+        for t in tensors:
+            t, axis = t if isinstance(t, tuple) else (t, 1)
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and 1 <= t.shape[axis] <= 16 and t.shape[-1] >= 1):
+                return None
+        return self._native_index() if self.num_src < (1 << 31) else None
+
+    def u_dot_v(self, u, v):
+        """DGL's u_dot_v (an SDDMM): e[j, h] = <u[s_j, h, :], v[d, h, :]> for every neighbour slot j of every dst node d, u [num_src, H,
+        D], v [num_dst, H, D] -> a per-edge tensor (see the class docstring), 0 on padding.  Gradients for both.  Native kernels for
+        contiguous fp32 GPU tensors, H <= 16, fan-out <= 32 or the ragged form; u_dot_v_torch otherwise.  Bitwise reproducible; the
+        gradient of u adds with float atomics and is not."""
+        if u.dim() != 3 or tuple(v.shape) != (self.num_dst,) + tuple(u.shape[1:]) or u.shape[0] != self.num_src:
+            raise ValueError(f"u {tuple(u.shape)}, v {tuple(v.shape)}: this block takes [{self.num_src}, H, D] and [{self.num_dst}, H, D]")
+        index = self._edge_native(u, v)
+        return _UDotV.apply(u, v, *index) if index is not None else self.u_dot_v_torch(u, v)
+
+    def u_dot_v_torch(self, u, v):
+        """u_dot_v in plain torch, any device and dtype (it materialises the gathered [E, H, D] rows): its fallback, and in float64
+        its reference."""
+        rows, src, at = self._edge_slots(u.device)
+        return self._edge_tensor(at, (u[src] * v[rows]).sum(-1))
+
+    def u_add_v(self, a, b):
+        """DGL's u_add_v on per-head scalars: e[j, h] = a[s_j, h] + b[d, h], a [num_src, H], b [num_dst, H] -> a per-edge tensor, 0 on
+        padding.  Plain torch on [slots, H] gathers, no kernel: it is here so that GAT's score can be written."""
+        rows, src, at = self._edge_slots(a.device)
+        return self._edge_tensor(at, a[src] + b[rows])
+
+    def edge_softmax(self, e):
+        """DGL's edge_softmax: per dst node and head, the softmax of e over the row's valid slots, 0 on padding (a row without an
+        edge yields nothing).  The row maximum is subtracted first, so a common offset of a row's scores changes nothing.  The
+        gradient a * (g - sum_j a_j g_j) comes from the saved output alone.  Native kernels under the conditions of u_dot_v,
+        edge_softmax_torch otherwise.  Bitwise reproducible, gradient included."""
+        self._edge_check(e)
+        index = self._edge_native((e, -1))
+        return _EdgeSoftmax.apply(e, *index) if index is not None else self.edge_softmax_torch(e)
+
+    def edge_softmax_torch(self, e):
+        """edge_softmax in plain torch (scatter max, exp, index_add), any device and dtype: its fallback, and in float64 its reference."""
+        self._edge_check(e)
+        rows, _, at = self._edge_slots(e.device)
+        H = e.shape[-1]
+        x = e.reshape(-1, H)[at]
+        m = torch.full((self.num_dst, H), float("-inf"), dtype=e.dtype, device=e.device)
+        m = m.scatter_reduce(0, rows.unsqueeze(1).expand(-1, H), x.detach(), "amax")   # the shift cancels in the softmax
+        p = torch.exp(x - m[rows])
+        l = torch.zeros((self.num_dst, H), dtype=e.dtype, device=e.device).index_add(0, rows, p)
+        return self._edge_tensor(at, p / l[rows])
+
+    def u_mul_e_sum(self, u, e):
+        """DGL's u_mul_e_sum (an SpMM) with one weight per edge and head: out[d, h, :] = sum_j e[j, h] * u[s_j, h, :] over row d's valid
+        slots in slot order, u [num_src, H, D], e a per-edge tensor (padding is not read) -> [num_dst, H, D].  Gradients for both.
+        Native kernels under the conditions of u_dot_v, u_mul_e_sum_torch otherwise; with H = 1 the result has
+        weighted_sum_aggregate's bits.  Bitwise reproducible; the gradient of u is not."""
+        if u.dim() != 3 or u.shape[0] != self.num_src:
+            raise ValueError(f"u {tuple(u.shape)}: this block takes [{self.num_src}, H, D]")
+        self._edge_check(e, u.shape[1])
+        index = self._edge_native(u, (e, -1))
+        return _UMulESum.apply(u, e, *index) if index is not None else self.u_mul_e_sum_torch(u, e)
+
+    def u_mul_e_sum_torch(self, u, e):
+        """u_mul_e_sum in plain torch, any device and dtype (it materialises the weighted [E, H, D] rows): its fallback, and in
+        float64 its reference."""
+        self._edge_check(e, u.shape[1])
+        rows, src, at = self._edge_slots(u.device)
+        out = torch.zeros((self.num_dst,) + tuple(u.shape[1:]), dtype=u.dtype, device=u.device)
+        return out.index_add(0, rows, e.reshape(-1, e.shape[-1])[at].unsqueeze(-1).to(u.dtype) * u[src])
 
     def _rel_args(self, etype, num_rels, w):
         """The checks of rel_sum_aggregate / rel_sum_aggregate_torch / rel_in_degrees -> the block's slot array."""

@@ -161,6 +161,16 @@ SYMBOLS = {
     "coala_block_multi_aggregate_csr": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, C.c_uint32, C.c_float, _VP]),
     "coala_block_multi_aggregate_backward": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _I, C.c_uint32, _VP]),
     "coala_block_multi_aggregate_backward_csr": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, C.c_uint32, _VP]),
+    "coala_block_u_dot_v": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _I, _VP]),
+    "coala_block_u_dot_v_csr": (_I, [_I] + [_VP] * 5 + [_I64, _I, _I, _VP]),
+    "coala_block_u_mul_e_sum": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _I, _VP]),
+    "coala_block_u_mul_e_sum_csr": (_I, [_I] + [_VP] * 5 + [_I64, _I, _I, _VP]),
+    "coala_block_e_mul_v_scatter": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _I, _VP]),
+    "coala_block_e_mul_v_scatter_csr": (_I, [_I] + [_VP] * 5 + [_I64, _I, _I, _VP]),
+    "coala_block_edge_softmax": (_I, [_I] + [_VP] * 3 + [_I64, _I, _I, _VP]),
+    "coala_block_edge_softmax_csr": (_I, [_I] + [_VP] * 4 + [_I64, _I, _VP]),
+    "coala_block_edge_softmax_backward": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _VP]),
+    "coala_block_edge_softmax_backward_csr": (_I, [_I] + [_VP] * 5 + [_I64, _I, _VP]),
     "coala_block_rel_sum": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _I, _VP]),
     "coala_block_rel_sum_backward": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _I, _VP]),
     "coala_block_rel_sum_csr": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _VP]),

@@ -4,7 +4,8 @@
 // aggregation (GATConv's and GATv2Conv's message steps), scaled dot-product attention (DotGatConv's and HGTConv's message step), temporal
 // attention over a fused time encoding (TGATConv's message step; fixed blocks alone) and
 // relation-typed GAT attention (a softmax per destination and relation), forward and backward, on fixed blocks (nbr_local[n_dst, fanout], -1 = no
-// neighbour) and on the CSR blocks of full layers; and, for link prediction, edge exclusion on both block forms and the dot-product
+// neighbour) and on the CSR blocks of full layers; the message-passing primitives on per-edge tensors (DGL's dgl.ops u_dot_v,
+// edge_softmax, u_mul_e_sum and the reverse scatter that is their gradient); and, for link prediction, edge exclusion on both block forms and the dot-product
 // scores of node pairs (forward and backward).  Stateless entry points: no handle, every launch on the caller's stream.
 //
 // Layout of the file: the device helpers every kernel walks a row with (which rows a wave takes, a row's bounds in either block form,
@@ -1334,6 +1335,277 @@ __global__ __launch_bounds__(kBlock) void multi_aggregate_backward_kernel(const 
     }
 }
 
+// ------------------------------------------------------------------------------------------------- message-passing primitives
+// DGL's dgl.ops on a block: u_dot_v (an SDDMM), edge_softmax, u_mul_e_sum (an SpMM with a weight per edge and head) and the reverse
+// scatter that is the gradient of both with respect to u.  A per-edge tensor has one value per neighbour slot and head, laid out like
+// the block's index array with a trailing head axis: e[slot * H + h], slot = d * fanout + j on a fixed block, the position in
+// `indices` on a CSR block.  Padding slots (index < 0) hold 0 on output and their values are never used on input.  One wave per
+// destination row in every kernel; a wave's LDS is carved from one dynamic array: a tile of a chunk's [<= 64, H] per-edge values,
+// then what the kernel adds (v[d] for the SDDMM, two words per head for the softmax).
+
+// tile[j * heads + h] = e[(e0 + j) * heads + h] for the n slots of the chunk at e0: 256 contiguous bytes per instruction.  The caller
+// synchronises on both sides.
+__device__ __forceinline__ void load_edge_tile(float* tile, const float* __restrict__ e, int64_t e0, int n, int heads, int lane) {
+    for (int i = lane; i < n * heads; i += 64) tile[i] = e[e0 * heads + i];
+}
+
+// <a[0 .. dim), b[0 .. dim)> over a group of GS lanes: lane gl takes the VEC-float pieces gl, gl + GS, ... with one fma per term; the
+// caller's butterfly finishes.
+template <int VEC, int GS>
+__device__ __forceinline__ float group_dot(const float* __restrict__ a, const float* b, int dim, int gl) {
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    float acc = 0.0f;
+    for (int c = gl * VEC; c < dim; c += GS * VEC) {
+        const vf x = *reinterpret_cast<const vf*>(a + c), y = *reinterpret_cast<const vf*>(b + c);
+        for (int i = 0; i < VEC; ++i) acc = __builtin_fmaf(x[i], y[i], acc);
+    }
+    return acc;
+}
+
+// SDDMM: e[slot, h] = <u[s_j, h, :], v[d, h, :]>.  v[d] is staged once per row in LDS (v_lds floats per wave; 0: the row is too long
+// for LDS and comes from the cache).  The work unit is a (slot, head) pair: a group of GS lanes -- the power of two covering D / VEC,
+// 8 at the least -- reads u[s_j, h, :] in VEC-float pieces, fma-sums against the LDS copy, and a GS-wide butterfly finishes, so 64 / GS
+// pairs are in flight per wave and a pair costs log2(GS) shuffles, not a 64-lane scan per slot.  A chunk's scores gather in the LDS
+// tile and leave coalesced.  The same lanes take the same pair in both block forms, and the sums have a fixed order: reproducible.
+template <int VEC, int GS, bool CSR>
+__global__ __launch_bounds__(kBlock) void u_dot_v_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
+                                                         const float* __restrict__ u, const float* __restrict__ v, float* __restrict__ e,
+                                                         int64_t n_dst, int heads, int dim, int v_lds) {
+    extern __shared__ __attribute__((aligned(16))) float edge_lds[];
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    constexpr int GPW = 64 / GS;
+    const auto [lane, wave, n_waves] = wave_rows();
+    const int hd = heads * dim, gl = lane % GS, grp = lane / GS;
+    float* const tile = edge_lds + (threadIdx.x >> 6) * (64 * heads + v_lds);
+    float* const vd = tile + 64 * heads;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        if (beg == end) continue; // wave-uniform
+        const float* const v_row = v + d * hd;
+        if (v_lds) {
+            wave_lds_sync(); // the previous row has read vd
+            for (int c = lane * VEC; c < hd; c += 64 * VEC) *reinterpret_cast<vf*>(vd + c) = *reinterpret_cast<const vf*>(v_row + c);
+        }
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
+            const int pairs = n * heads;
+            wave_lds_sync(); // vd is whole; the previous chunk's tile has been stored
+            for (int p0 = 0; p0 < pairs; p0 += GPW) {
+                const int p = p0 + grp;
+                const bool ok = p < pairs;
+                const int j = ok ? p / heads : 0;
+                const int h = ok ? p - j * heads : 0;
+                const int32_t s = __shfl(mine, j);
+                float acc = 0.0f;
+                if (ok && s >= 0) {
+                    const float* us = u + (int64_t)s * hd + h * dim;
+                    acc = v_lds ? group_dot<VEC, GS>(us, vd + h * dim, dim, gl) : group_dot<VEC, GS>(us, v_row + h * dim, dim, gl);
+                }
+                for (int o = GS / 2; o; o >>= 1) acc += __shfl_xor(acc, o);
+                if (ok && gl == 0) tile[p] = acc; // 0 on a padding slot
+            }
+            wave_lds_sync();
+            for (int i = lane; i < pairs; i += 64) e[e0 * heads + i] = tile[i];
+        }
+    }
+}
+
+// SpMM with a weight per (edge, head): out[d, h, :] = sum over the valid slots j of e[j, h] * u[s_j, h, :].  weighted_sum_kernel's
+// mapping -- a lane per VEC floats of the [H * D] row, slot order, one fma per term from +0, so H = 1 has that kernel's bits -- with
+// the chunk's [n, H] weights staged in LDS; VEC divides D, so a lane's piece lies in one head and it reads that head's weight.  A row
+// of one chunk stages its weights once for all passes over a long row.
+template <int VEC, bool CSR>
+__global__ __launch_bounds__(kBlock) void u_mul_e_sum_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
+                                                             const float* __restrict__ u, const float* __restrict__ e, float* __restrict__ out,
+                                                             int64_t n_dst, int heads, int dim) {
+    extern __shared__ __attribute__((aligned(16))) float edge_lds[];
+    typedef float vf __attribute__((ext_vector_type(VEC)));
+    const auto [lane, wave, n_waves] = wave_rows();
+    const int hd = heads * dim, units = hd / VEC, upl = dim / VEC;
+    float* const tile = edge_lds + (threadIdx.x >> 6) * 64 * heads;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        const bool one = end - beg <= 64;
+        for (int u0 = 0; u0 < units; u0 += 64) { // wave-uniform trip counts: the shuffles below need every lane
+            const int un = u0 + lane;
+            const int hu = un < units ? un / upl : 0;
+            vf acc = vf(0.0f);
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                int32_t mine;
+                const int n = load_chunk(idx, e0, end, lane, &mine);
+                if (u0 == 0 || !one) { // wave-uniform
+                    wave_lds_sync(); // the tile's readers are done
+                    load_edge_tile(tile, e, e0, n, heads, lane);
+                    wave_lds_sync();
+                }
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && un < units)
+                        axpy<VEC>(acc, tile[j * heads + hu], *reinterpret_cast<const vf*>(u + (int64_t)s * hd + (int64_t)un * VEC));
+                }
+            }
+            if (un < units) *reinterpret_cast<vf*>(out + d * hd + (int64_t)un * VEC) = acc;
+        }
+    }
+}
+
+// The reverse scatter, the gradient of both ops above with respect to u: grad_u[s_j, h, :] += w[j, h] * x[d, h, :] over the valid
+// slots (u_mul_e_sum's backward with x = grad_out, w = e; u_dot_v's with x = v, w = grad_e).  The mean backward's mapping, a lane per
+// float: an atomic instruction of the wave covers 256 contiguous bytes; x[d] of the pass in a register, the chunk's weights in LDS.
+// grad_u zeroed by the caller; hardware float atomics: summation order varies.
+template <bool CSR>
+__global__ __launch_bounds__(kBlock) void e_mul_v_scatter_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
+                                                                 const float* __restrict__ w, const float* __restrict__ x,
+                                                                 float* __restrict__ grad_u, int64_t n_dst, int heads, int dim) {
+    extern __shared__ __attribute__((aligned(16))) float edge_lds[];
+    const auto [lane, wave, n_waves] = wave_rows();
+    const int hd = heads * dim;
+    float* const tile = edge_lds + (threadIdx.x >> 6) * 64 * heads;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        const bool one = end - beg <= 64;
+        for (int c0 = 0; c0 < hd; c0 += 64) { // wave-uniform trip count: the shuffles below read lanes that are past the row
+            const int c = c0 + lane;
+            const bool in = c < hd;
+            const float xc = in ? x[d * hd + c] : 0.0f;
+            const int h = in ? c / dim : 0;
+            for (int64_t e0 = beg; e0 < end; e0 += 64) {
+                int32_t mine;
+                const int n = load_chunk(idx, e0, end, lane, &mine);
+                if (c0 == 0 || !one) { // wave-uniform
+                    wave_lds_sync(); // the tile's readers are done
+                    load_edge_tile(tile, w, e0, n, heads, lane);
+                    wave_lds_sync();
+                }
+                for (int j = 0; j < n; ++j) {
+                    const int32_t s = __shfl(mine, j);
+                    if (s >= 0 && in) unsafeAtomicAdd(grad_u + (int64_t)s * hd + c, tile[j * heads + h] * xc);
+                }
+            }
+        }
+    }
+}
+
+// edge_softmax: a[j, h] = exp(e[j, h] - m_h) / l_h over the valid slots j of row d, m_h their maximum and l_h the sum of the
+// exponentials; 0 on a padding slot.  A chunk's [n, H] scores are staged in LDS (-inf on padding), a lane per (slot, head) element
+// for the loads, the exponentials and the stores; lane h < H owns head h's running maximum and sum and walks its column of the tile in
+// slot order.  The sum is kept in double, and so is the factor exp(m_old - m_new) that carries it over a growing maximum: l is the
+// sum of the fp32 exponentials to a rounding, so a row's weights add up to 1 within an ulp or two whatever its length.  A row of one
+// chunk -- every fixed row -- divides the exponentials it already holds; a longer one (a hub) has streamed with the running pair and
+// takes a second pass over global memory.  Fixed order throughout: reproducible, and the same bits in both block forms.
+template <bool CSR>
+__global__ __launch_bounds__(kBlock) void edge_softmax_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int fanout,
+                                                              const float* __restrict__ e, float* __restrict__ a, int64_t n_dst, int heads) {
+    extern __shared__ __attribute__((aligned(16))) float edge_lds[];
+    const auto [lane, wave, n_waves] = wave_rows();
+    float* const tile = edge_lds + (threadIdx.x >> 6) * (64 * heads + 2 * kGatMaxHeads);
+    float* const m_of = tile + 64 * heads;   // per head: the maximum,
+    float* const l_of = m_of + kGatMaxHeads; // and the row's sum
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        float m_run = kNegInf;
+        double l_run = 0.0;
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts here and below: the shuffles need every lane
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
+            const int cnt = n * heads;
+            wave_lds_sync(); // the previous chunk, or the previous row, has read the tile and m_of
+            for (int i0 = 0; i0 < cnt; i0 += 64) {
+                const int i = i0 + lane;
+                const bool valid = __shfl(mine, i < cnt ? i / heads : 0) >= 0;
+                if (i < cnt) tile[i] = valid ? e[e0 * heads + i] : kNegInf;
+            }
+            wave_lds_sync();
+            float m_new = m_run;
+            if (lane < heads) {
+                for (int j = 0; j < n; ++j) m_new = fmaxf(m_new, tile[j * heads + lane]);
+                m_of[lane] = m_new;
+            }
+            wave_lds_sync();
+            for (int i0 = 0; i0 < cnt; i0 += 64) {
+                const int i = i0 + lane;
+                const bool valid = __shfl(mine, i < cnt ? i / heads : 0) >= 0;
+                if (i < cnt) tile[i] = valid ? expf(tile[i] - m_of[i % heads]) : 0.0f;
+            }
+            wave_lds_sync();
+            if (lane < heads) {
+                double sum = 0.0;
+                for (int j = 0; j < n; ++j) sum += (double)tile[j * heads + lane];
+                l_run = l_run * (m_run == m_new ? 1.0 : exp((double)m_run - (double)m_new)) + sum;
+                m_run = m_new;
+            }
+        }
+        if (beg == end) continue; // wave-uniform
+        if (lane < heads) l_of[lane] = (float)l_run; // m_of holds the last chunk's maximum, the row's
+        wave_lds_sync();
+        if (end - beg <= 64) { // the tile holds the row's exponentials at the row's maximum
+            const int cnt = (int)(end - beg) * heads;
+            for (int i = lane; i < cnt; i += 64) a[beg * heads + i] = tile[i] == 0.0f ? 0.0f : tile[i] / l_of[i % heads];
+            continue;
+        }
+        for (int64_t e0 = beg; e0 < end; e0 += 64) {
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
+            const int cnt = n * heads;
+            for (int i0 = 0; i0 < cnt; i0 += 64) {
+                const int i = i0 + lane;
+                const bool valid = __shfl(mine, i < cnt ? i / heads : 0) >= 0;
+                if (i < cnt) a[e0 * heads + i] = valid ? expf(e[e0 * heads + i] - m_of[i % heads]) / l_of[i % heads] : 0.0f;
+            }
+        }
+    }
+}
+
+// Its backward from the saved output alone: grad_e[j, h] = a[j, h] * (g[j, h] - sum_k a[k, h] g[k, h]), 0 on a padding slot.  The
+// forward's mapping: the products a * g of a chunk go through the LDS tile, lane h < H sums head h's column in slot order, in double;
+// a second walk over the row writes.  Reproducible.
+template <bool CSR>
+__global__ __launch_bounds__(kBlock) void edge_softmax_backward_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                       int fanout, const float* __restrict__ a, const float* __restrict__ g,
+                                                                       float* __restrict__ grad_e, int64_t n_dst, int heads) {
+    extern __shared__ __attribute__((aligned(16))) float edge_lds[];
+    const auto [lane, wave, n_waves] = wave_rows();
+    float* const tile = edge_lds + (threadIdx.x >> 6) * (64 * heads + 2 * kGatMaxHeads);
+    float* const dot_of = tile + 64 * heads;
+    for (int64_t d = wave; d < n_dst; d += n_waves) {
+        int64_t beg, end;
+        row_range<CSR>(indptr, fanout, d, &beg, &end);
+        double dot = 0.0;
+        for (int64_t e0 = beg; e0 < end; e0 += 64) { // wave-uniform trip counts here and below: the shuffles need every lane
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
+            const int cnt = n * heads;
+            wave_lds_sync(); // the previous chunk, or the previous row, has read the tile and dot_of
+            for (int i0 = 0; i0 < cnt; i0 += 64) {
+                const int i = i0 + lane;
+                const bool valid = __shfl(mine, i < cnt ? i / heads : 0) >= 0;
+                if (i < cnt) tile[i] = valid ? a[e0 * heads + i] * g[e0 * heads + i] : 0.0f;
+            }
+            wave_lds_sync();
+            if (lane < heads)
+                for (int j = 0; j < n; ++j) dot += (double)tile[j * heads + lane];
+        }
+        if (beg == end) continue; // wave-uniform
+        if (lane < heads) dot_of[lane] = (float)dot;
+        wave_lds_sync();
+        for (int64_t e0 = beg; e0 < end; e0 += 64) {
+            int32_t mine;
+            const int n = load_chunk(idx, e0, end, lane, &mine);
+            const int cnt = n * heads;
+            for (int i0 = 0; i0 < cnt; i0 += 64) {
+                const int i = i0 + lane;
+                const bool valid = __shfl(mine, i < cnt ? i / heads : 0) >= 0;
+                if (i < cnt) grad_e[e0 * heads + i] = valid ? a[e0 * heads + i] * (g[e0 * heads + i] - dot_of[i % heads]) : 0.0f;
+            }
+        }
+    }
+}
+
 // Relation-typed sum (DGL RelGraphConv's message step, before its weights): out[d, r, :] = sum over the valid edges j of row d with
 // etype_j == r of w_j * h_src[s_j, :], so that out.view(n_dst, R * dim) @ W.view(R * dim, out_dim) is sum_j w_j W[etype_j] h[s_j] in one
 // GEMM.  etype is laid out like the block's index array, and so is w (null: every weight is 1).  The weighted sum's mapping and its
@@ -2018,6 +2290,99 @@ int multi_backward_launch(int device, const int64_t* indptr, const int32_t* idx,
     return COALA_OK;
 }
 
+// The piece a lane reads of a head's D floats in the message-passing primitives: 16, 8 or 4 bytes, by D and the tables' alignment
+int edge_vec(int dim, const void* a, const void* b) {
+    const uintptr_t at = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b);
+    return dim % 4 == 0 && at % 16 == 0 ? 4 : dim % 2 == 0 && at % 8 == 0 ? 2 : 1;
+}
+
+// f(std::integral_constant<int, VEC>) for VEC = 4, 2, 1
+template <typename F>
+void dispatch_edge_vec(int vec, F&& f) {
+    if (vec == 4) f(std::integral_constant<int, 4>{});
+    else if (vec == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 1>{});
+}
+
+// f(std::integral_constant<int, GS>): the lanes per (slot, head) pair, the power of two covering the head's pieces
+template <typename F>
+void dispatch_edge_group(int pieces, F&& f) {
+    if (pieces <= 8) f(std::integral_constant<int, 8>{});
+    else if (pieces <= 16) f(std::integral_constant<int, 16>{});
+    else if (pieces <= 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
+constexpr int kEdgeMaxLdsBytes = 64 * 1024; // a block's dynamic LDS
+size_t edge_lds_bytes(int floats_per_wave) { return sizeof(float) * kWavesPerBlock * (size_t)floats_per_wave; }
+
+template <bool CSR>
+int u_dot_v_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* u, const float* v, float* e, int64_t n_dst,
+                   int heads, int dim, void* stream) {
+    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !u || !v || !e) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const int vec = edge_vec(dim, u, v);
+    int v_lds = (heads * dim + 3) & ~3; // v[d] in LDS when four waves' rows and tiles fit
+    if (edge_lds_bytes(64 * heads + v_lds) > kEdgeMaxLdsBytes) v_lds = 0;
+    dispatch_edge_vec(vec, [&](auto vec_c) {
+        dispatch_edge_group(dim / vec, [&](auto gs_c) {
+            hipLaunchKernelGGL((u_dot_v_kernel<decltype(vec_c)::value, decltype(gs_c)::value, CSR>), row_grid(n_dst), dim3(kBlock),
+                               edge_lds_bytes(64 * heads + v_lds), (hipStream_t)stream, indptr, idx, fanout, u, v, e, n_dst, heads, dim, v_lds);
+        });
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+template <bool CSR>
+int u_mul_e_sum_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* u, const float* e, float* out,
+                       int64_t n_dst, int heads, int dim, void* stream) {
+    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !u || !e || !out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    dispatch_edge_vec(edge_vec(dim, u, out), [&](auto vec_c) {
+        hipLaunchKernelGGL((u_mul_e_sum_kernel<decltype(vec_c)::value, CSR>), row_grid(n_dst), dim3(kBlock), edge_lds_bytes(64 * heads),
+                           (hipStream_t)stream, indptr, idx, fanout, u, e, out, n_dst, heads, dim);
+    });
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+template <bool CSR>
+int e_mul_v_scatter_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* w, const float* x, float* grad_u,
+                           int64_t n_dst, int heads, int dim, void* stream) {
+    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, dim)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !w || !x || !grad_u) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(e_mul_v_scatter_kernel<CSR>, row_grid(n_dst), dim3(kBlock), edge_lds_bytes(64 * heads), (hipStream_t)stream, indptr, idx,
+                       fanout, w, x, grad_u, n_dst, heads, dim);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
+// edge_softmax (g == nullptr: in = e, out = a) and its backward (in = a, g, out = grad_e)
+template <bool CSR>
+int edge_softmax_launch(int device, const int64_t* indptr, const int32_t* idx, int fanout, const float* in, const float* g, bool backward,
+                        float* out, int64_t n_dst, int heads, void* stream) {
+    if (int rc = gat_shape_check<CSR>(n_dst, fanout, heads, 1)) return rc;
+    if (n_dst == 0) return COALA_OK;
+    if ((CSR && !indptr) || !idx || !in || (backward && !g) || !out) return fail(COALA_EINVAL, "null buffer");
+    HIPCHK(hipSetDevice(device));
+    const size_t lds = edge_lds_bytes(64 * heads + 2 * kGatMaxHeads);
+    if (backward)
+        hipLaunchKernelGGL(edge_softmax_backward_kernel<CSR>, row_grid(n_dst), dim3(kBlock), lds, (hipStream_t)stream, indptr, idx, fanout, in, g,
+                           out, n_dst, heads);
+    else
+        hipLaunchKernelGGL(edge_softmax_kernel<CSR>, row_grid(n_dst), dim3(kBlock), lds, (hipStream_t)stream, indptr, idx, fanout, in, out, n_dst,
+                           heads);
+    HIPCHK(hipGetLastError());
+    return COALA_OK;
+}
+
 template <bool CSR>
 int rel_sum_launch(int device, const int64_t* indptr, const int32_t* idx, const int32_t* etype, const float* w, int fanout, const float* h_src,
                    float* out, int64_t n_dst, int num_rels, int dim, void* stream) {
@@ -2610,6 +2975,55 @@ int coala_block_multi_aggregate_backward_csr(int device, const int64_t* indptr, 
                                              const float* grad_out, const int32_t* arg, const float* mom, float* grad_src, int64_t n_dst,
                                              int dim, int n_aggr, uint32_t planes, void* stream) {
     return multi_backward_launch<true>(device, indptr, indices, 0, h_src, grad_out, arg, mom, grad_src, n_dst, dim, n_aggr, planes, stream);
+}
+
+int coala_block_u_dot_v(int device, const int32_t* nbr, const float* u, const float* v, float* e, int64_t n_dst, int fanout, int heads, int dim,
+                        void* stream) {
+    return u_dot_v_launch<false>(device, nullptr, nbr, fanout, u, v, e, n_dst, heads, dim, stream);
+}
+
+int coala_block_u_dot_v_csr(int device, const int64_t* indptr, const int32_t* indices, const float* u, const float* v, float* e, int64_t n_dst,
+                            int heads, int dim, void* stream) {
+    return u_dot_v_launch<true>(device, indptr, indices, 0, u, v, e, n_dst, heads, dim, stream);
+}
+
+int coala_block_u_mul_e_sum(int device, const int32_t* nbr, const float* u, const float* e, float* out, int64_t n_dst, int fanout, int heads,
+                            int dim, void* stream) {
+    return u_mul_e_sum_launch<false>(device, nullptr, nbr, fanout, u, e, out, n_dst, heads, dim, stream);
+}
+
+int coala_block_u_mul_e_sum_csr(int device, const int64_t* indptr, const int32_t* indices, const float* u, const float* e, float* out,
+                                int64_t n_dst, int heads, int dim, void* stream) {
+    return u_mul_e_sum_launch<true>(device, indptr, indices, 0, u, e, out, n_dst, heads, dim, stream);
+}
+
+int coala_block_e_mul_v_scatter(int device, const int32_t* nbr, const float* w, const float* x, float* grad_u, int64_t n_dst, int fanout,
+                                int heads, int dim, void* stream) {
+    return e_mul_v_scatter_launch<false>(device, nullptr, nbr, fanout, w, x, grad_u, n_dst, heads, dim, stream);
+}
+
+int coala_block_e_mul_v_scatter_csr(int device, const int64_t* indptr, const int32_t* indices, const float* w, const float* x, float* grad_u,
+                                    int64_t n_dst, int heads, int dim, void* stream) {
+    return e_mul_v_scatter_launch<true>(device, indptr, indices, 0, w, x, grad_u, n_dst, heads, dim, stream);
+}
+
+int coala_block_edge_softmax(int device, const int32_t* nbr, const float* e, float* a, int64_t n_dst, int fanout, int heads, void* stream) {
+    return edge_softmax_launch<false>(device, nullptr, nbr, fanout, e, nullptr, false, a, n_dst, heads, stream);
+}
+
+int coala_block_edge_softmax_csr(int device, const int64_t* indptr, const int32_t* indices, const float* e, float* a, int64_t n_dst, int heads,
+                                 void* stream) {
+    return edge_softmax_launch<true>(device, indptr, indices, 0, e, nullptr, false, a, n_dst, heads, stream);
+}
+
+int coala_block_edge_softmax_backward(int device, const int32_t* nbr, const float* a, const float* grad_a, float* grad_e, int64_t n_dst,
+                                      int fanout, int heads, void* stream) {
+    return edge_softmax_launch<false>(device, nullptr, nbr, fanout, a, grad_a, true, grad_e, n_dst, heads, stream);
+}
+
+int coala_block_edge_softmax_backward_csr(int device, const int64_t* indptr, const int32_t* indices, const float* a, const float* grad_a,
+                                          float* grad_e, int64_t n_dst, int heads, void* stream) {
+    return edge_softmax_launch<true>(device, indptr, indices, 0, a, grad_a, true, grad_e, n_dst, heads, stream);
 }
 
 int coala_block_rel_sum(int device, const int32_t* nbr, const int32_t* etype, const float* w, const float* h_src, float* out, int64_t n_dst,

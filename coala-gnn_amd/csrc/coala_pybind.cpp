@@ -456,4 +456,47 @@ PYBIND11_MODULE(_coala_pybind, m) {
                                                        ptr<const float>(grad_out), ptr<const int32_t>(arg), ptr<const float>(mom),
                                                        ptr<float>(grad_src), n_dst, dim, n_aggr, planes, stream_of(stream)));
     });
+    // message-passing primitives on a block (coala_block_u_dot_v, _u_mul_e_sum, _e_mul_v_scatter, _edge_softmax[_backward]): the three
+    // ops over (u, per-dst rows, per-edge values) share a signature, and so do their CSR forms
+    using EdgeOp = int (*)(int, const int32_t*, const float*, const float*, float*, int64_t, int, int, int, void*);
+    using EdgeOpCsr = int (*)(int, const int64_t*, const int32_t*, const float*, const float*, float*, int64_t, int, int, void*);
+    const auto edge_op = [&m](const char* name, EdgeOp fn, EdgeOpCsr fn_csr) {
+        m.def(name, [fn](int device, uint64_t nbr, uint64_t a, uint64_t b, uint64_t out, int64_t n_dst, int fanout, int heads, int dim,
+                         uint64_t stream) {
+            py::gil_scoped_release nogil;
+            check(fn(device, ptr<const int32_t>(nbr), ptr<const float>(a), ptr<const float>(b), ptr<float>(out), n_dst, fanout, heads, dim,
+                     stream_of(stream)));
+        });
+        m.def((std::string(name) + "_csr").c_str(), [fn_csr](int device, uint64_t indptr, uint64_t indices, uint64_t a, uint64_t b, uint64_t out,
+                                                             int64_t n_dst, int heads, int dim, uint64_t stream) {
+            py::gil_scoped_release nogil;
+            check(fn_csr(device, ptr<const int64_t>(indptr), ptr<const int32_t>(indices), ptr<const float>(a), ptr<const float>(b), ptr<float>(out),
+                         n_dst, heads, dim, stream_of(stream)));
+        });
+    };
+    edge_op("block_u_dot_v", coala_block_u_dot_v, coala_block_u_dot_v_csr);
+    edge_op("block_u_mul_e_sum", coala_block_u_mul_e_sum, coala_block_u_mul_e_sum_csr);
+    edge_op("block_e_mul_v_scatter", coala_block_e_mul_v_scatter, coala_block_e_mul_v_scatter_csr);
+    m.def("block_edge_softmax", [](int device, uint64_t nbr, uint64_t e, uint64_t a, int64_t n_dst, int fanout, int heads, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_edge_softmax(device, ptr<const int32_t>(nbr), ptr<const float>(e), ptr<float>(a), n_dst, fanout, heads, stream_of(stream)));
+    });
+    m.def("block_edge_softmax_csr", [](int device, uint64_t indptr, uint64_t indices, uint64_t e, uint64_t a, int64_t n_dst, int heads,
+                                       uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_edge_softmax_csr(device, ptr<const int64_t>(indptr), ptr<const int32_t>(indices), ptr<const float>(e), ptr<float>(a),
+                                           n_dst, heads, stream_of(stream)));
+    });
+    m.def("block_edge_softmax_backward", [](int device, uint64_t nbr, uint64_t a, uint64_t grad_a, uint64_t grad_e, int64_t n_dst, int fanout,
+                                            int heads, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_edge_softmax_backward(device, ptr<const int32_t>(nbr), ptr<const float>(a), ptr<const float>(grad_a),
+                                                ptr<float>(grad_e), n_dst, fanout, heads, stream_of(stream)));
+    });
+    m.def("block_edge_softmax_backward_csr", [](int device, uint64_t indptr, uint64_t indices, uint64_t a, uint64_t grad_a, uint64_t grad_e,
+                                                int64_t n_dst, int heads, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_edge_softmax_backward_csr(device, ptr<const int64_t>(indptr), ptr<const int32_t>(indices), ptr<const float>(a),
+                                                    ptr<const float>(grad_a), ptr<float>(grad_e), n_dst, heads, stream_of(stream)));
+    });
 }

@@ -149,7 +149,7 @@ def train_link(args, comm, device, indptr, indices, feat, files, fan_out):
     if args.seed >= 0:
         torch.manual_seed(args.seed)
     if args.model_type == "gat":
-        encoder = GAT(args.dim, args.hidden_channels, args.hidden_channels, len(fan_out), args.num_heads)
+        encoder = GAT(args.dim, args.hidden_channels, args.hidden_channels, len(fan_out), args.num_heads, attn_drop=args.attn_drop)
     elif args.model_type == "tgat":
         encoder = TGAT(args.dim, args.hidden_channels, args.hidden_channels, len(fan_out), args.num_heads, args.time_dim, args.time_scale)
     else:
@@ -290,6 +290,8 @@ def main():
                     help="seed of torch's generators, set before the model is built: its initial weights (and dropout masks) are the same "
                          "from run to run, as the synthetic data and the samplers' draws already are; negative: not seeded")
     ap.add_argument("--num_heads", type=int, default=4, help="attention heads of --model_type gat, gatv2 and rgat")
+    ap.add_argument("--attn_drop", type=float, default=0.0,
+                    help="attention dropout of --model_type gat (the GAT paper's 0.6): the layers then run Block's edge primitives in training")
     ap.add_argument("--share_weights", action="store_true",
                     help="--model_type gatv2: one projection for the source and the destination rows of every layer (GATv2Conv's share_weights)")
     ap.add_argument("--num_rels", type=int, default=4, help="edge types of --model_type rgcn, rgat, rsage and hgt (1..64)")
@@ -446,7 +448,7 @@ def main():
     if args.seed >= 0:
         torch.manual_seed(args.seed)
     if args.model_type == "gat":                                                                            # :220-231
-        model = GAT(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads).to(device)
+        model = GAT(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads, attn_drop=args.attn_drop).to(device)
     elif args.model_type == "gatv2":
         model = GATv2(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads, args.share_weights).to(device)
     elif args.model_type == "gcn":

@@ -723,6 +723,43 @@ int coala_block_multi_aggregate_backward(int device, const int32_t* nbr, const f
 int coala_block_multi_aggregate_backward_csr(int device, const int64_t* indptr, const int32_t* indices, const float* h_src,
                                              const float* grad_out, const int32_t* arg, const float* mom, float* grad_src, int64_t n_dst,
                                              int dim, int n_aggr, uint32_t planes, void* stream);
+/* Message-passing primitives (DGL's dgl.ops u_dot_v, edge_softmax, u_mul_e_sum) on a block.  A per-edge tensor is fp32 with one value
+ * per neighbour slot and head: [n_dst, fanout, heads] beside nbr, [E, heads] beside indices.  Padding slots (index < 0) hold 0 on
+ * output and are never used on input.  u is [n_src, heads, dim], v / x / out are [n_dst, heads, dim].  Refused with COALA_EINVAL:
+ * heads outside 1..16, dim < 1, n_dst < 0, a fan-out outside 1..32, a null buffer; n_dst == 0 launches nothing.  One wave per
+ * destination row, the same code on the same lanes in both forms: bit-identical on a row both can express.
+ *   u_dot_v           e[j, h] = <u[s_j, h, :], v[d, h, :]>: v[d] staged in LDS, a group of 8 .. 64 lanes per (slot, head) pair reading
+ *                     16-, 8- or 4-byte pieces (by dim and alignment), fma sums and a butterfly: fixed order.
+ *   u_mul_e_sum       out[d, h, :] = sum_j e[j, h] u[s_j, h, :] over the valid slots in slot order from +0, one fma per term: with
+ *                     heads == 1 the bits of coala_block_weighted_sum.
+ *   e_mul_v_scatter   grad_u[s_j, h, :] += w[j, h] x[d, h, :] over the valid slots: the gradient of both ops above with respect to u
+ *                     (w = e, x = grad_out; w = grad_e, x = v).  The caller zeroes grad_u; hardware float atomics, a lane per float:
+ *                     the order varies, the one result here that is not bitwise reproducible.
+ *   edge_softmax      a[j, h] = exp(e[j, h] - m_h) / l_h over the valid slots of a row, m_h their maximum, l_h the sum of the
+ *                     exponentials kept in double: a row's weights sum to 1 within an ulp or two.  A row longer than 64 slots streams
+ *                     with a running maximum and sum and reads e a second time.
+ *   edge_softmax_backward   grad_e[j, h] = a[j, h] (grad_a[j, h] - sum_k a[k, h] grad_a[k, h]), from the saved output.
+ * Bytes per row of deg slots: u_dot_v and u_mul_e_sum read deg * (4 heads dim + 4) and 4 heads dim or 4 heads deg, and write the other;
+ * the scatter adds 4 heads dim deg through atomics; the softmax moves 8 heads deg (16 on a hub row), its backward 20 heads deg. */
+int coala_block_u_dot_v(int device, const int32_t* nbr, const float* u, const float* v, float* e, int64_t n_dst, int fanout, int heads, int dim,
+                        void* stream);
+int coala_block_u_dot_v_csr(int device, const int64_t* indptr, const int32_t* indices, const float* u, const float* v, float* e, int64_t n_dst,
+                            int heads, int dim, void* stream);
+int coala_block_u_mul_e_sum(int device, const int32_t* nbr, const float* u, const float* e, float* out, int64_t n_dst, int fanout, int heads,
+                            int dim, void* stream);
+int coala_block_u_mul_e_sum_csr(int device, const int64_t* indptr, const int32_t* indices, const float* u, const float* e, float* out,
+                                int64_t n_dst, int heads, int dim, void* stream);
+int coala_block_e_mul_v_scatter(int device, const int32_t* nbr, const float* w, const float* x, float* grad_u, int64_t n_dst, int fanout,
+                                int heads, int dim, void* stream);
+int coala_block_e_mul_v_scatter_csr(int device, const int64_t* indptr, const int32_t* indices, const float* w, const float* x, float* grad_u,
+                                    int64_t n_dst, int heads, int dim, void* stream);
+int coala_block_edge_softmax(int device, const int32_t* nbr, const float* e, float* a, int64_t n_dst, int fanout, int heads, void* stream);
+int coala_block_edge_softmax_csr(int device, const int64_t* indptr, const int32_t* indices, const float* e, float* a, int64_t n_dst, int heads,
+                                 void* stream);
+int coala_block_edge_softmax_backward(int device, const int32_t* nbr, const float* a, const float* grad_a, float* grad_e, int64_t n_dst,
+                                      int fanout, int heads, void* stream);
+int coala_block_edge_softmax_backward_csr(int device, const int64_t* indptr, const int32_t* indices, const float* a, const float* grad_a,
+                                          float* grad_e, int64_t n_dst, int heads, void* stream);
 /* Relation-typed sum (the message step of DGL's RelGraphConv, before its weights): out[d, r, :] = sum over the valid j of row d with
  * etype[d, j] == r of w[d, j] * h_src[nbr[d, j], :], so that out viewed as [n_dst, num_rels * dim] times W viewed as [num_rels * dim, o]
  * is sum_j w_j W[etype_j] h_src[s_j] in one GEMM.  etype int32, one value per neighbour slot, laid out like nbr ([n_dst, fanout]) or
