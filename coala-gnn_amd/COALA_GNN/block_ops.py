@@ -2,7 +2,7 @@
 sum aggregation (DGL's u_mul_e_sum, the edge_weight= path of GraphConv / SAGEConv), max aggregation (DGL's fn.max: SAGEConv's "pool",
 GINConv's "max"), LSTM aggregation (SAGEConv's "lstm": coala_lstm.hip, on the matrix units), the relation-typed sum (RelGraphConv's message step), GAT / GATv2 attention aggregation, scaled dot-product
 attention (DotGatConv's and HGTConv's message step), temporal attention over a fused time encoding (TGATConv's message step, fixed
-blocks alone) and relation-typed GAT attention (RelGATConv's message step), on fixed blocks and on the ragged CSR blocks of full layers; and the
+blocks alone), attention over edge features (TransformerConv's message step: coala_edge_attn.hip) and relation-typed GAT attention (RelGATConv's message step), on fixed blocks and on the ragged CSR blocks of full layers; and the
 message-passing primitives on per-edge tensors (DGL's u_dot_v, edge_softmax, u_mul_e_sum: one Function each for both block forms).  pair_dot (DGL's u_dot_v on a pair graph: a link predictor's scores) is the one op here
 that takes no block.  One kernel forward, one backward each; the kernels are in coala-gnn_amd/csrc/coala_block_ops.hip
 (C ABI: coala_block_*).  Every op has one forward and one backward body for both block forms, which take the C entry and the block's
@@ -759,6 +759,71 @@ class _TimeAttnAggregate(torch.autograd.Function):
         sums = partials.sum(0) if partials is not None else None
         return (grad_q, grad_k, grad_v, grad_qt, sums[0].view_as(om) if need[4] else None, sums[1].view_as(ph) if need[5] else None, None, None,
                 None)
+
+
+def _edge_attn_forward(ctx, q, k, v, qe, efeat, eids, scale, entry, index):
+    """Per head, a softmax over row d's edges of scale * (<q[d], k[s]> + <qe[d], x_j>), x_j = efeat[eids_j] (eids None: the slot's own
+    row of efeat), then out = the weighted sum of v[s] and eagg = the weighted sum of the edge rows (coala_block_edge_attn_aggregate[_csr],
+    csrc/coala_edge_attn.hip); no [E, H, D] intermediate.  eids is contiguous int32 or int64, read as it is."""
+    qc, kc, vc, tc, xc = (t.contiguous() for t in (q, k, v, qe, efeat))
+    idx, n_dst, fan = _block(index)
+    H, D, F = kc.shape[1], kc.shape[2], tc.shape[2]
+    out = torch.empty((n_dst, H, D), dtype=torch.float32, device=kc.device)
+    eagg = torch.empty((n_dst, H, F), dtype=torch.float32, device=kc.device)
+    lse = torch.empty((n_dst, H), dtype=torch.float32, device=kc.device)
+    ctx.eid64 = int(eids is not None and eids.dtype == torch.int64)
+    _capi.check(entry(kc.device.index or 0, *idx, _ptr(eids), ctx.eid64, qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), tc.data_ptr(), xc.data_ptr(),
+                      out.data_ptr(), eagg.data_ptr(), lse.data_ptr(), n_dst, *fan, H, D, F, scale, current_stream()))
+    if any(ctx.needs_input_grad[:5]):
+        ctx.save_for_backward(qc, kc, vc, tc, xc, out, eagg, lse, *index, *(() if eids is None else (eids,)))
+    ctx.scale, ctx.table = scale, eids is not None
+    return out, eagg
+
+
+def _edge_attn_backward(ctx, grad_out, grad_eagg, entry):
+    """-> (grad_q, grad_k, grad_v, grad_qe, grad_efeat), one launch; a gradient nobody asked for is neither computed nor allocated.  The
+    slot form's grad_efeat is written whole by the kernel, the table form's is zeroed here and takes float atomics."""
+    need = ctx.needs_input_grad[:5]
+    if not any(need):
+        return (None,) * 5
+    q, k, v, qe, x, out, eagg, lse, *rest = ctx.saved_tensors
+    eids = rest.pop() if ctx.table else None
+    idx, n_dst, fan = _block(rest)
+    g, ge = grad_out.contiguous(), grad_eagg.contiguous()
+    grad_q = torch.empty_like(q) if need[0] else None
+    grad_k = torch.zeros_like(k) if need[1] else None
+    grad_v = torch.zeros_like(v) if need[2] else None
+    grad_qe = torch.empty_like(qe) if need[3] else None
+    grad_x = (torch.zeros_like if ctx.table else torch.empty_like)(x) if need[4] else None
+    _capi.check(entry(k.device.index or 0, *idx, _ptr(eids), ctx.eid64, q.data_ptr(), k.data_ptr(), v.data_ptr(), qe.data_ptr(), x.data_ptr(),
+                      out.data_ptr(), eagg.data_ptr(), lse.data_ptr(), g.data_ptr(), ge.data_ptr(), _ptr(grad_q), _ptr(grad_k), _ptr(grad_v),
+                      _ptr(grad_qe), _ptr(grad_x), n_dst, *fan, k.shape[1], k.shape[2], qe.shape[2], ctx.scale, current_stream()))
+    return grad_q, grad_k, grad_v, grad_qe, grad_x
+
+
+class _EdgeAttnAggregate(torch.autograd.Function):
+    """Edge-feature attention on a fixed block of any fan-out (coala_block_edge_attn_aggregate): one kernel forward, one backward
+    (gradients for q, k, v, qe and efeat).  efeat is 2-D: the table, or the slot form's rows viewed as [num_dst * fanout, F]."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, qe, efeat, eids, scale, nbr):
+        return _edge_attn_forward(ctx, q, k, v, qe, efeat, eids, scale, _lib.coala_block_edge_attn_aggregate, (nbr,))
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_eagg):
+        return _edge_attn_backward(ctx, grad_out, grad_eagg, _lib.coala_block_edge_attn_aggregate_backward) + (None,) * 3
+
+
+class _EdgeAttnAggregateCSR(torch.autograd.Function):
+    """The same on a ragged block (coala_block_edge_attn_aggregate_csr): eids and the slot form's rows have one entry per entry of indices."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, qe, efeat, eids, scale, indptr, indices):
+        return _edge_attn_forward(ctx, q, k, v, qe, efeat, eids, scale, _lib.coala_block_edge_attn_aggregate_csr, (indptr, indices))
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_eagg):
+        return _edge_attn_backward(ctx, grad_out, grad_eagg, _lib.coala_block_edge_attn_aggregate_csr_backward) + (None,) * 4
 
 
 class _PairDot(torch.autograd.Function):

@@ -12,14 +12,16 @@ Heterogeneous Graph Transformer on HGTConv layers, and DotGAT is GAT's shape on 
 dot-product kernel (Block.dot_gat_aggregate).  PinSAGE (--model_type pinsage) is the network of DGL's PinSAGE example on WeightedSAGEConv
 layers, for blocks sampled by random walks (RandomWalkNeighborSampler): the visit counts weigh the neighbours.  TGAT (--model_type tgat) is
 temporal graph attention on TGATConv layers, for blocks sampled by TemporalNeighborSampler: attention over the neighbours' rows and the
-time encoding of block.edata['dt'], on the native temporal attention kernel (Block.time_attn_aggregate)."""
+time encoding of block.edata['dt'], on the native temporal attention kernel (Block.time_attn_aggregate).  GraphTransformer
+(--model_type transformer) is GAT's shape on TransformerConv layers, whose attention reads a feature row per edge through the native
+edge-feature attention kernel (Block.edge_attn_aggregate)."""
 import time
 
 import torch
 
-from .nn import DotGatConv, DotPredictor, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, LSTMSAGEConv, PNAConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv, TGATConv, WeightedSAGEConv
+from .nn import DotGatConv, DotPredictor, GATConv, GATv2Conv, GINConv, GraphConv, HGTConv, LSTMSAGEConv, PNAConv, RelGATConv, RelGraphConv, RelSAGEConv, SAGEConv, TGATConv, TransformerConv, WeightedSAGEConv
 
-__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "PNA", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "PinSAGE", "TGAT", "LinkPredictor", "link_loss", "train_steps", "FlatGradAllReduce"]
+__all__ = ["SageMean", "SAGE", "GAT", "GATv2", "GCN", "GIN", "PNA", "RGCN", "RGAT", "RSAGE", "HGT", "DotGAT", "PinSAGE", "TGAT", "GraphTransformer", "LinkPredictor", "link_loss", "train_steps", "FlatGradAllReduce"]
 
 
 class SageMean(torch.nn.Module):
@@ -346,6 +348,27 @@ class TGAT(torch.nn.Module):
                 raise ValueError("TGAT needs block.edata['dt']: sample the blocks with TemporalNeighborSampler(edge_ids=True)")
             h = layer(block, (h, block.dst_rows(h)))
         return self.linear(h)
+
+
+class GraphTransformer(torch.nn.Module):
+    """GAT's shape on TransformerConv layers: n_layers layers of num_heads heads, no activation between them, the heads concatenated
+    between layers; the last layer averages its heads and is passed through log_softmax.  edge_dim given: forward takes edge_attr, a
+    [num_edges, edge_dim] table that every layer reads through its block's edata['_ID'] (blocks sampled with edge_ids=True), or the
+    constructor does and keeps it (a plain attribute on the graph's device: neither a parameter nor part of the state_dict)."""
+
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, num_heads, edge_dim=None, edge_attr=None):
+        super().__init__()
+        self.edge_attr = edge_attr
+        dims = [in_feats] + [n_hidden * num_heads] * (n_layers - 1)
+        outs = [n_hidden] * (n_layers - 1) + [n_classes]
+        self.layers = torch.nn.ModuleList(TransformerConv(dims[i], outs[i], num_heads, edge_dim=edge_dim, concat=i + 1 < n_layers)
+                                          for i in range(n_layers))
+
+    def forward(self, blocks, x, edge_attr=None):
+        h, edge_attr = x, self.edge_attr if edge_attr is None else edge_attr
+        for layer, block in zip(self.layers, blocks):
+            h = layer(block, h, edge_attr, None if edge_attr is None else block.edata["_ID"])
+        return h.log_softmax(dim=-1)
 
 
 class LinkPredictor(torch.nn.Module):

@@ -21,13 +21,15 @@ LSTMSAGEConv is DGL's SAGEConv with aggregator_type='lstm' as a class of its own
 Block.lstm_aggregate, a native kernel on the matrix units, and the input projection is made once per source node.
 TGATConv is TGAT's temporal attention layer on the blocks of TemporalNeighborSampler: attention over [h_src || Phi(dt)] with the learnable
 time encoding TimeEncode, whose attention step is Block.time_attn_aggregate, a native kernel that computes Phi(dt) in registers.
+TransformerConv is PyG's graph transformer layer with edge features: lin_edge(x_j) joins the key and the value of every edge through
+Block.edge_attn_aggregate, a native kernel on the raw edge rows (fixed blocks of any fan-out, and ragged ones).
 PNAConv is DGL's Principal Neighbourhood Aggregation layer: all its aggregators (mean, max, min, std, var, sum) come from one pass of
 Block.multi_aggregate, a native kernel, over a per-source projection -- no per-edge tensor."""
 import torch
 
 from .block_ops import gather_mm
 
-__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "LSTMSAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv", "TypedLinear", "DotPredictor", "TimeEncode", "TGATConv", "PNAConv", "pna_delta"]
+__all__ = ["GATConv", "GATv2Conv", "DotGatConv", "GraphConv", "SAGEConv", "LSTMSAGEConv", "WeightedSAGEConv", "GINConv", "RelGraphConv", "RelGATConv", "RelSAGEConv", "HGTConv", "TypedLinear", "DotPredictor", "TimeEncode", "TGATConv", "TransformerConv", "PNAConv", "pna_delta"]
 
 
 class GATConv(torch.nn.Module):
@@ -636,7 +638,7 @@ class RelSAGEConv(torch.nn.Module):
 
 class DotGatConv(torch.nn.Module):
     """Dot-product attention layer (DGL 1.x DotGatConv; PyG's TransformerConv without edge features, bias, root weight and a separate
-    value projection).  forward(block, feat) -> [num_dst, H, out_feats]; feat is h_src or (h_src, h_dst) -- without h_dst the destination
+    value projection -- TransformerConv below is that layer, edge features included).  forward(block, feat) -> [num_dst, H, out_feats]; feat is h_src or (h_src, h_dst) -- without h_dst the destination
     rows are block.dst_rows(h_src).  For destination d, head h and the valid in-edges j of d (source s_j):
         q = fc_dst(h_dst).view(-1, H, D);   k = v = fc_src(h_src).view(-1, H, D)
         a_j = softmax over d's in-edges of <q[d, h], k[s_j, h]> / sqrt(D);   out[d, h, :] = sum_j a_j v[s_j, h, :]
@@ -736,6 +738,70 @@ class TGATConv(torch.nn.Module):
         out, tagg = block.time_attn_aggregate(q, k, v, qt, dt, enc.omega, enc.phase)
         attn = out + torch.einsum("nht,hdt->nhd", tagg, self.w_v[:, F:].view(H, D, -1))
         return self.fc2(torch.relu(self.fc1(torch.cat([attn.flatten(1), h_dst], dim=1))))
+
+
+class TransformerConv(torch.nn.Module):
+    """Graph transformer layer with edge features (Shi et al., "Masked Label Prediction: Unified Message Passing Model for Semi-Supervised
+    Classification"; PyG's TransformerConv).  forward(block, feat, edge_attr=None, eids=None) -> [num_dst, H * out_feats] with concat,
+    [num_dst, out_feats] (the mean over heads) without; feat is h_src or (h_src, h_dst) -- without h_dst the destination rows are
+    block.dst_rows(h_src).  With H = num_heads, D = out_feats, for destination d and its edges j (source s_j, edge row x_j):
+        q = lin_query(h_dst).view(-1, H, D);   k = lin_key(h_src).view(-1, H, D);   v = lin_value(h_src).view(-1, H, D)
+        e = lin_edge(x_j).view(H, D), added to the key AND to the value;   a_j = softmax over d's edges of <q[d, h], k[s_j, h] + e[h]> / sqrt(D)
+        out[d, h, :] = sum_j a_j (v[s_j, h, :] + e[h, :]);   r = lin_skip(h_dst)
+        out = beta_d r + (1 - beta_d) out, beta_d = sigmoid(lin_beta([out || r || out - r])) with beta=True, out + r without (root_weight)
+    edge_attr is a table [M, edge_dim] read through eids (one id per neighbour slot; block.edata['_ID'] by default when the table has
+    the length of the graph's edge list the block was sampled from), or one row per slot ([num_dst, fanout, edge_dim] or [E, edge_dim]).
+    lin_edge(x_j) is never formed per edge: qe = einsum(q, W_e) goes into the score and einsum(eagg, W_e) is added to the output, both
+    through Block.edge_attn_aggregate, a native kernel that works on the raw edge rows.  With edge_dim=None the step is
+    Block.dot_gat_aggregate.  A destination without an edge attends to nothing.  Parameters, with PyG's names: lin_query, lin_key,
+    lin_value (Linear(in, H * D, bias=bias)), lin_edge (Linear(edge_dim, H * D, bias=False)), lin_skip (Linear(in_dst, H * D or D,
+    bias=bias)), lin_beta (Linear(3 * (H * D or D), 1, bias=False)).  PyG is not installed where this was written: names and shapes are
+    those of PyG's source as remembered, and they are what this layer fixes.  Attention dropout is not provided."""
+
+    def __init__(self, in_feats, out_feats, num_heads, edge_dim=None, concat=True, beta=False, root_weight=True, bias=True):
+        super().__init__()
+        in_src, in_dst = in_feats if isinstance(in_feats, (tuple, list)) else (in_feats, in_feats)
+        self._num_heads, self._out_feats, self.edge_dim, self.concat = num_heads, out_feats, edge_dim, concat
+        width = num_heads * out_feats
+        self.lin_key = torch.nn.Linear(in_src, width, bias=bias)
+        self.lin_query = torch.nn.Linear(in_dst, width, bias=bias)
+        self.lin_value = torch.nn.Linear(in_src, width, bias=bias)
+        self.lin_edge = torch.nn.Linear(edge_dim, width, bias=False) if edge_dim is not None else None
+        final = width if concat else out_feats
+        self.lin_skip = torch.nn.Linear(in_dst, final, bias=bias) if root_weight else None
+        self.lin_beta = torch.nn.Linear(3 * final, 1, bias=False) if root_weight and beta else None
+
+    def forward(self, block, feat, edge_attr=None, eids=None):
+        h_src, h_dst = feat if isinstance(feat, (tuple, list)) else (feat, None)
+        if h_dst is None:
+            h_dst = block.dst_rows(h_src)
+        H, D = self._num_heads, self._out_feats
+        q, k, v = self.lin_query(h_dst).view(-1, H, D), self.lin_key(h_src).view(-1, H, D), self.lin_value(h_src).view(-1, H, D)
+        if self.lin_edge is None:
+            if edge_attr is not None:
+                raise ValueError("TransformerConv: edge_attr given to a layer built with edge_dim=None")
+            out = block.dot_gat_aggregate(q, k, v)
+        else:
+            if edge_attr is None:
+                raise ValueError(f"TransformerConv(edge_dim={self.edge_dim}) needs edge_attr")
+            if eids is None and edge_attr.dim() == 2 and block.nbr is None and edge_attr.shape[0] == block.indices.numel():
+                pass   # one row per slot of a ragged block
+            elif eids is None and edge_attr.dim() == 2:
+                if "_ID" not in block.edata:
+                    raise ValueError("TransformerConv: an edge_attr table needs eids, or a block that carries edge ids (edge_ids=True)")
+                eids = block.edata["_ID"]
+            w_e = self.lin_edge.weight.view(H, D, -1)
+            out, eagg = block.edge_attn_aggregate(q, k, v, torch.einsum("nhd,hdf->nhf", q, w_e), edge_attr, eids)
+            out = out + torch.einsum("nhf,hdf->nhd", eagg, w_e)
+        out = out.flatten(1) if self.concat else out.mean(1)
+        if self.lin_skip is not None:
+            r = self.lin_skip(h_dst)
+            if self.lin_beta is not None:
+                b = torch.sigmoid(self.lin_beta(torch.cat([out, r, out - r], dim=-1)))
+                out = b * r + (1.0 - b) * out
+            else:
+                out = out + r
+        return out
 
 
 def _typed_linear(x, W, types, counts):

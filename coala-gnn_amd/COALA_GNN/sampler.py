@@ -11,7 +11,7 @@ import torch
 
 from COALA_GNN_Pybind import _capi, current_stream
 
-from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
+from .block_ops import (_DotGatAggregate, _DotGatAggregateCSR, _EdgeAttnAggregate, _EdgeAttnAggregateCSR, _GatAggregate, _GatAggregateCSR, _Gatv2Aggregate, _Gatv2AggregateCSR, _MaxAggregate, _MaxAggregateCSR, _MeanAggregate,
                         _MeanAggregateCSR, _LSTMAggregate, _LSTMAggregateCSR, LSTM_HIDDEN_STEP, LSTM_MAX_HIDDEN, _RelGatAggregate, _RelGatAggregateCSR, _RelSum, _RelSumCSR, _TimeAttnAggregate,
                         _WeightedSum, _WeightedSumCSR, _MultiAggregate, _MultiAggregateCSR, multi_planes, _UDotV, _UMulESum, _EdgeSoftmax)
 
@@ -867,8 +867,8 @@ class Block(object):
         return float(k.shape[2]) ** -0.5 if scale is None else float(scale)
 
     def dot_gat_aggregate(self, q, k, v, rows=None, scale=None, validate=True):
-        """Scaled dot-product attention (the message step of DGL's DotGatConv and HGTConv, PyG's TransformerConv without edge features):
-        for every dst node d and head h, a softmax over d's in-edges j of scale * <q[d, h, :], k[.., h, :]>, then sum_j a_j v[.., h, :]
+        """Scaled dot-product attention (the message step of DGL's DotGatConv and HGTConv, PyG's TransformerConv with edge_dim=None; edge_attn_aggregate
+        is the step with edge features): for every dst node d and head h, a softmax over d's in-edges j of scale * <q[d, h, :], k[.., h, :]>, then sum_j a_j v[.., h, :]
         -> [num_dst, H, D]; scale=None means D ** -0.5.  q is [num_dst, H, D].  Which row of k / v an edge reads:
           rows=None (dense): k and v are [num_src, H, D] and the edge in a slot reads the row of its source, the block's own index;
           rows given (packed): k and v are [P, H, D]; rows has one integer per neighbour slot -- rel_gat_aggregate's packed form -- and
@@ -974,6 +974,85 @@ class Block(object):
         out = torch.zeros((self.num_dst,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev).index_add(0, dst, a.unsqueeze(-1).to(v.dtype) * v[src])
         tagg = torch.zeros((self.num_dst, H, phi.shape[1]), dtype=phi.dtype, device=dev).index_add(0, dst, a.unsqueeze(-1) * phi.unsqueeze(1))
         return out, tagg
+
+    def _edge_attn_args(self, q, k, v, qe, efeat, eids, scale):
+        """The checks of edge_attn_aggregate / edge_attn_aggregate_torch -> the scale as a float (None: D ** -0.5)."""
+        slots = self.indices if self.nbr is None else self.nbr
+        ok = (k.dim() == 3 and tuple(v.shape) == tuple(k.shape) and k.shape[0] == self.num_src and tuple(q.shape) == (self.num_dst,) + tuple(k.shape[1:])
+              and qe.dim() == 3 and tuple(qe.shape[:2]) == (self.num_dst, k.shape[1]) and qe.shape[2] >= 1)
+        if ok:
+            ok = (efeat.dim() == 2 and efeat.shape[1] == qe.shape[2]) if eids is not None else tuple(efeat.shape) == tuple(slots.shape) + (qe.shape[2],)
+        if not ok:
+            rows = "[M, F] with eids" if eids is not None else f"{list(slots.shape) + ['F']} (a row per neighbour slot)".replace("'", "")
+            raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, qe {tuple(qe.shape)}, efeat {tuple(efeat.shape)}: this block "
+                             f"takes [{self.num_dst}, H, D], [{self.num_src}, H, D] twice, [{self.num_dst}, H, F] and {rows}")
+        if eids is not None:
+            if not _is_int_tensor(eids):
+                raise ValueError("eids must be an integer tensor")
+            if tuple(eids.shape) != tuple(slots.shape):
+                raise ValueError(f"eids of shape {tuple(eids.shape)}: this block takes one per neighbour slot, {tuple(slots.shape)}")
+        return float(k.shape[2]) ** -0.5 if scale is None else float(scale)
+
+    def edge_attn_aggregate(self, q, k, v, qe, efeat, eids=None, scale=None, validate=True):
+        """Dot-product attention over edges that carry a feature row (PyG's TransformerConv(edge_dim=), TGN's raw messages): the same
+        lin_edge(x_j) is added to the key and to the value of edge j, and with that projection W_e split off --
+        <q, k_s + W_e x_j> = <q, k_s> + <W_e^T q, x_j>, sum_j a_j (v_s + W_e x_j) = sum_j a_j v_s + W_e sum_j a_j x_j -- the per-edge work is on
+        the raw F-float row.  q is [num_dst, H, D]; k and v are [num_src, H, D]; qe[d, h] = W_e[h]^T q[d, h] is [num_dst, H, F], one dense
+        product of the caller's.  For dst node d, head h and d's slots j with an edge (source s_j, edge row x_j):
+            e_j = scale * (<q[d, h], k[s_j, h]> + <qe[d, h], x_j>),  a = softmax_j(e),  scale=None means D ** -0.5
+            out[d, h, :] = sum_j a_j v[s_j, h, :]      eagg[d, h, :] = sum_j a_j x_j
+        -> (out [num_dst, H, D], eagg [num_dst, H, F]); the value side's edge part is einsum(eagg, W_e), added by the caller.  x_j is
+          eids given (table form): efeat[eids_j], efeat [M, F], eids one integer per neighbour slot in the layout of edata['_ID'].  A slot
+            is an edge exactly when the block's own index is >= 0, and eids is not read on padding.  An id >= M, or < 0 on an edge,
+            raises IndexError: on the native path that is one host read per call, which validate=False skips.  Contiguous int64 or
+            int32 eids reach the kernel as they are;
+          eids=None (slot form): the slot's own row of efeat, [num_dst, fanout, F] on a fixed block, [E, F] on a ragged one.
+        A dst node without an edge gets zeros in both outputs and sends no gradient; a -1 slot is skipped wherever it stands.
+        Gradients for q, k, v, qe and efeat, each computed only if required.  out, eagg, grad_q and grad_qe are bitwise reproducible and
+        the same in the fixed and the ragged form of a block, as is the slot form's grad_efeat (a store per slot, 0 on padding);
+        grad_k, grad_v and the table form's grad_efeat take float atomics.  Native kernels (one forward, one backward, no [E, H, D]
+        intermediate) for fp32 GPU tensors with H <= 16, F <= 128 and num_src < 2^31, on fixed blocks of ANY fan-out and on ragged
+        blocks; edge_attn_aggregate_torch otherwise."""
+        scale = self._edge_attn_args(q, k, v, qe, efeat, eids, scale)
+        index = (self.indptr, self.indices) if self.nbr is None else (self.nbr,)
+        native = (all(t.is_cuda and t.dtype == torch.float32 for t in (q, k, v, qe, efeat)) and all(t.is_cuda for t in index)
+                  and (eids is None or eids.is_cuda) and 0 < k.shape[1] <= 16 and k.shape[2] > 0 and qe.shape[2] <= 128
+                  and 0 < k.shape[0] < (1 << 31) and efeat.shape[0] > 0 and (self.nbr is None or (self.nbr.is_contiguous() and self.nbr.shape[1] > 0)))
+        if not native:
+            return self.edge_attn_aggregate_torch(q, k, v, qe, efeat, eids, scale)
+        index = tuple(t.contiguous() for t in index)
+        if eids is not None:
+            if eids.dtype not in (torch.int32, torch.int64):
+                eids = eids.to(torch.int64)
+            eids = eids.contiguous()
+            if validate and bool((((eids < 0) | (eids >= efeat.shape[0])) & (index[-1] >= 0)).any()):   # one host read: the kernels do not check an id
+                raise IndexError(f"eids holds an id outside [0, {efeat.shape[0]}): efeat has {efeat.shape[0]} rows")
+        return (_EdgeAttnAggregateCSR if self.nbr is None else _EdgeAttnAggregate).apply(q, k, v, qe, efeat, eids, scale, *index)
+
+    def edge_attn_aggregate_torch(self, q, k, v, qe, efeat, eids=None, scale=None):
+        """edge_attn_aggregate in plain torch, any device and dtype, both block forms, the table and the slot form: an edge-list softmax
+        that materialises the gathered [E, F] edge rows, the gathered [E, H, D] rows of k and v and the [E, H, F] products with qe and the
+        weights.  The fallback of edge_attn_aggregate, and its reference."""
+        scale = self._edge_attn_args(q, k, v, qe, efeat, eids, scale)
+        dev = k.device
+        dst, src = self._slots(dev)
+        keep = src >= 0
+        row = torch.arange(src.numel(), device=dev) if eids is None else eids.reshape(-1).to(device=dev, dtype=torch.int64)
+        dst, src, row = dst[keep], src[keep], row[keep]
+        table = efeat.reshape(-1, efeat.shape[-1])
+        if eids is not None and row.numel() and (int(row.max()) >= table.shape[0] or int(row.min()) < 0):
+            raise IndexError(f"eids holds an id outside [0, {table.shape[0]}): efeat has {table.shape[0]} rows")
+        x = table[row]                                                                           # [E, F]
+        H = k.shape[1]
+        e = ((q[dst] * k[src]).sum(-1) + (qe[dst] * x.unsqueeze(1)).sum(-1)) * scale             # [E, H]
+        m = torch.full((self.num_dst, H), float("-inf"), dtype=e.dtype, device=dev)
+        m = m.scatter_reduce(0, dst.unsqueeze(1).expand(-1, H), e.detach(), "amax").detach()     # the shift cancels in the softmax
+        p = torch.exp(e - m[dst])
+        l = torch.zeros((self.num_dst, H), dtype=e.dtype, device=dev).index_add(0, dst, p)
+        a = p / l[dst]
+        out = torch.zeros((self.num_dst,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev).index_add(0, dst, a.unsqueeze(-1).to(v.dtype) * v[src])
+        eagg = torch.zeros((self.num_dst, H, x.shape[1]), dtype=x.dtype, device=dev).index_add(0, dst, a.unsqueeze(-1).to(x.dtype) * x.unsqueeze(1))
+        return out, eagg
 
     def _exclude_args(self, eids):
         """The checks of exclude_edges / exclude_edges_torch -> the block's edge ids."""

@@ -195,6 +195,10 @@ SYMBOLS = {
     "coala_block_dot_gat_aggregate_csr_backward": (_I, [_I] + [_VP] * 11 + [_I64, _I, _I, C.c_float, _VP]),
     "coala_block_time_attn_aggregate": (_I, [_I] + [_VP] * 11 + [_I64, _I, _I, _I, _I, C.c_float, _VP]),
     "coala_block_time_attn_aggregate_backward": (_I, [_I] + [_VP] * 18 + [_I, _I64, _I, _I, _I, _I, C.c_float, _VP]),
+    "coala_block_edge_attn_aggregate": (_I, [_I, _VP, _VP, _I] + [_VP] * 8 + [_I64, _I, _I, _I, _I, C.c_float, _VP]),
+    "coala_block_edge_attn_aggregate_backward": (_I, [_I, _VP, _VP, _I] + [_VP] * 15 + [_I64, _I, _I, _I, _I, C.c_float, _VP]),
+    "coala_block_edge_attn_aggregate_csr": (_I, [_I, _VP, _VP, _VP, _I] + [_VP] * 8 + [_I64, _I, _I, _I, C.c_float, _VP]),
+    "coala_block_edge_attn_aggregate_csr_backward": (_I, [_I, _VP, _VP, _VP, _I] + [_VP] * 15 + [_I64, _I, _I, _I, C.c_float, _VP]),
     "coala_block_exclude_edges":(_I, [_I] + [_VP] * 3 + [_I64, _VP, _VP, _I64, _I, _VP]),
     "coala_block_exclude_edges_csr": (_I, [_I] + [_VP] * 4 + [_I64] + [_VP] * 4 + [_I64, _VP]),
     "coala_block_pair_dot": (_I, [_I] + [_VP] * 4 + [_I64, _I, _I, _VP]),

@@ -426,6 +426,49 @@ PYBIND11_MODULE(_coala_pybind, m) {
             ptr<float>(grad_v), ptr<float>(grad_qt), ptr<float>(grad_time_parts), parts, n_dst, fanout, heads, dim, time_dim, scale,
             stream_of(stream)));
     });
+    // edge-feature attention on a block (coala_block_edge_attn_aggregate*): eids 0 for the slot form; a gradient that is not wanted is 0
+    m.def("block_edge_attn_aggregate", [](int device, uint64_t nbr, uint64_t eids, int eid_is_64, uint64_t q, uint64_t k, uint64_t v, uint64_t qe,
+                                          uint64_t efeat, uint64_t out, uint64_t eagg, uint64_t lse, int64_t n_dst, int fanout, int heads, int dim,
+                                          int edge_dim, float scale, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_edge_attn_aggregate(device, ptr<const int32_t>(nbr), ptr<const void>(eids), eid_is_64, ptr<const float>(q),
+                                              ptr<const float>(k), ptr<const float>(v), ptr<const float>(qe), ptr<const float>(efeat),
+                                              ptr<float>(out), ptr<float>(eagg), ptr<float>(lse), n_dst, fanout, heads, dim, edge_dim, scale,
+                                              stream_of(stream)));
+    });
+    m.def("block_edge_attn_aggregate_backward", [](int device, uint64_t nbr, uint64_t eids, int eid_is_64, uint64_t q, uint64_t k, uint64_t v,
+                                                   uint64_t qe, uint64_t efeat, uint64_t out, uint64_t eagg, uint64_t lse, uint64_t grad_out,
+                                                   uint64_t grad_eagg, uint64_t grad_q, uint64_t grad_k, uint64_t grad_v, uint64_t grad_qe,
+                                                   uint64_t grad_efeat, int64_t n_dst, int fanout, int heads, int dim, int edge_dim, float scale,
+                                                   uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_edge_attn_aggregate_backward(
+            device, ptr<const int32_t>(nbr), ptr<const void>(eids), eid_is_64, ptr<const float>(q), ptr<const float>(k), ptr<const float>(v),
+            ptr<const float>(qe), ptr<const float>(efeat), ptr<const float>(out), ptr<const float>(eagg), ptr<const float>(lse),
+            ptr<const float>(grad_out), ptr<const float>(grad_eagg), ptr<float>(grad_q), ptr<float>(grad_k), ptr<float>(grad_v),
+            ptr<float>(grad_qe), ptr<float>(grad_efeat), n_dst, fanout, heads, dim, edge_dim, scale, stream_of(stream)));
+    });
+    m.def("block_edge_attn_aggregate_csr", [](int device, uint64_t indptr, uint64_t indices, uint64_t eids, int eid_is_64, uint64_t q, uint64_t k,
+                                              uint64_t v, uint64_t qe, uint64_t efeat, uint64_t out, uint64_t eagg, uint64_t lse, int64_t n_dst,
+                                              int heads, int dim, int edge_dim, float scale, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_edge_attn_aggregate_csr(device, ptr<const int64_t>(indptr), ptr<const int32_t>(indices), ptr<const void>(eids), eid_is_64,
+                                                  ptr<const float>(q), ptr<const float>(k), ptr<const float>(v), ptr<const float>(qe),
+                                                  ptr<const float>(efeat), ptr<float>(out), ptr<float>(eagg), ptr<float>(lse), n_dst, heads, dim,
+                                                  edge_dim, scale, stream_of(stream)));
+    });
+    m.def("block_edge_attn_aggregate_csr_backward", [](int device, uint64_t indptr, uint64_t indices, uint64_t eids, int eid_is_64, uint64_t q,
+                                                       uint64_t k, uint64_t v, uint64_t qe, uint64_t efeat, uint64_t out, uint64_t eagg,
+                                                       uint64_t lse, uint64_t grad_out, uint64_t grad_eagg, uint64_t grad_q, uint64_t grad_k,
+                                                       uint64_t grad_v, uint64_t grad_qe, uint64_t grad_efeat, int64_t n_dst, int heads, int dim,
+                                                       int edge_dim, float scale, uint64_t stream) {
+        py::gil_scoped_release nogil;
+        check(coala_block_edge_attn_aggregate_csr_backward(
+            device, ptr<const int64_t>(indptr), ptr<const int32_t>(indices), ptr<const void>(eids), eid_is_64, ptr<const float>(q),
+            ptr<const float>(k), ptr<const float>(v), ptr<const float>(qe), ptr<const float>(efeat), ptr<const float>(out), ptr<const float>(eagg),
+            ptr<const float>(lse), ptr<const float>(grad_out), ptr<const float>(grad_eagg), ptr<float>(grad_q), ptr<float>(grad_k),
+            ptr<float>(grad_v), ptr<float>(grad_qe), ptr<float>(grad_efeat), n_dst, heads, dim, edge_dim, scale, stream_of(stream)));
+    });
     // multi-statistic aggregation on a block (coala_block_multi_aggregate*); state or a table that is not wanted is passed as 0
     m.def("block_multi_aggregate", [](int device, uint64_t nbr, uint64_t h_src, uint64_t out, uint64_t arg, uint64_t mom, int64_t n_dst,
                                       int fanout, int dim, int n_aggr, uint32_t planes, float eps, uint64_t stream) {

@@ -22,6 +22,7 @@ objects, same loop, same printed lines), without DGL / mpi4py: on seeded synthet
   python examples/train_synthetic.py --sampler temporal --temporal_strategy last --time_decay 0.001
   python examples/train_synthetic.py --task link --sampler temporal --num_negs 5
   python examples/train_synthetic.py --model_type tgat --sampler temporal --num_heads 2 --time_dim 100 --time_scale 0.001
+  python examples/train_synthetic.py --model_type transformer --num_heads 4 --edge_feat_dim 16 --fan_out 5,5 --eval_fan_out=-1,-1
   python examples/train_synthetic.py --task link --model_type tgat --sampler temporal --num_heads 2
   python examples/train_synthetic.py --node_embedding --emb_dim 64 --model_type rgcn --num_rels 4
   python examples/train_synthetic.py --node_embedding --emb_optimizer sgd --emb_lr 0.1 --task link
@@ -45,7 +46,7 @@ import torch  # noqa: E402
 from COALA_GNN import COALA_GNN_DataLoader, MetaPath2Vec, MPI_Comm_Manager, Node2Vec, Node_Distributor, NodeEmbedding, RowWiseAdagrad, SparseAdagrad, SparseAdam, SparseSGD, SSD_INFO  # noqa: E402
 from COALA_GNN.color_info_gen import color_graph, save_color_files  # noqa: E402
 from COALA_GNN.nn import pna_delta  # noqa: E402
-from COALA_GNN.harness import GAT, GCN, GIN, HGT, PNA, RGAT, RGCN, RSAGE, SAGE, TGAT, GATv2, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
+from COALA_GNN.harness import GAT, GCN, GIN, HGT, PNA, RGAT, RGCN, RSAGE, SAGE, TGAT, GATv2, GraphTransformer, LinkPredictor, PinSAGE, SageMean, link_loss  # noqa: E402
 from COALA_GNN.sampler import (CSCGraph, EdgePredictionSampler, LaborSampler, NeighborSampler, RandomWalkNeighborSampler, RelNeighborSampler,  # noqa: E402
                                TemporalEdgePredictionSampler, TemporalNeighborSampler, UniformNegativeSampler, reverse_edge_ids,
                                sort_csc_by_etype)
@@ -265,7 +266,7 @@ def main():
     # accepted so that the reference's command lines (examples/4GB_script.sh, Cache_compare_script.sh, Distribution_compare_script.sh) run as they are
     ap.add_argument("--num_layers", type=int, default=None, help="must equal the number of fan-outs when given")
     ap.add_argument("--feat_cpu", action="store_true", help="features in pinned host memory: always the case here (the NVMe tier is out of scope)")
-    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "gatv2", "sage", "gcn", "gin", "pna", "rgcn", "rgat", "rsage", "hgt", "pinsage", "tgat"],
+    ap.add_argument("--model_type", type=str, default="sage", choices=["gat", "gatv2", "sage", "gcn", "gin", "pna", "rgcn", "rgat", "rsage", "hgt", "pinsage", "tgat", "transformer"],
                     help="sage: GraphSAGE (--sage_aggregator); gat: GAT with --num_heads heads (native attention aggregation); gatv2: the same model on GATv2Conv layers (--share_weights); gcn: GraphConv, "
                          "norm='both'; gin: GINConv layers (--gin_aggregator), an MLP in each; pna: PNAConv layers (--pna_aggregators, --pna_scalers, --num_towers; "
                          "every aggregator from one native multi-statistic pass); rgcn: RelGraphConv layers, one weight matrix per edge "
@@ -274,6 +275,9 @@ def main():
                          "'gcn' per edge type, summed; pinsage: WeightedSAGEConv layers on the visit counts of --sampler pinsage; tgat: TGATConv layers of "
                          "--num_heads heads on the blocks of --sampler temporal, attention over the neighbours' rows and a learnable encoding of "
                          "the time gaps (--time_dim, --time_scale; native temporal attention)")
+    ap.add_argument("--edge_feat_dim", type=int, default=0,
+                    help="--model_type transformer (TransformerConv layers): width of a synthetic fp32 feature row per edge, kept on the graph's "
+                         "device and read through the blocks' edge ids by the native edge-feature attention (1..128 run natively); 0: no edge features")
     ap.add_argument("--time_dim", type=int, default=100, help="--model_type tgat: channels of the time encoding (1..128 run natively)")
     ap.add_argument("--time_scale", type=float, default=1.0,
                     help="--model_type tgat: the time gaps are multiplied by this before they are encoded (the encoder's frequencies run "
@@ -423,7 +427,7 @@ def main():
         edata = dict(edata, etype=edge_types_by_source(indices, args.num_rels))
         if rel_fan_out is not None:   # RelNeighborSampler wants every node's in-edges sorted by type (no other edata to carry along here)
             indices, edata["etype"], _ = sort_csc_by_etype(indptr, indices, edata["etype"])
-    edge_ids = ew is not None or typed
+    edge_ids = ew is not None or typed or (args.model_type == "transformer" and args.edge_feat_dim > 0)
     if args.sampler == "labor":
         if prob is not None:
             ap.error("--sampler labor does not sample by edge weight (--edge_weights)")
@@ -468,6 +472,11 @@ def main():
         model = RSAGE(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_rels).to(device)
     elif args.model_type == "tgat":
         model = TGAT(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads, args.time_dim, args.time_scale).to(device)
+    elif args.model_type == "transformer":
+        efeat = None
+        if args.edge_feat_dim > 0:   # in CSC order, aligned with `indices`: the blocks find their rows through edata['_ID']
+            efeat = torch.randn(indices.numel(), args.edge_feat_dim, generator=torch.Generator(device=indices.device).manual_seed(2), device=indices.device)
+        model = GraphTransformer(args.dim, args.hidden_channels, args.num_classes, len(fan_out), args.num_heads, args.edge_feat_dim or None, efeat).to(device)
     elif args.model_type == "pinsage":
         model = PinSAGE(args.dim, args.hidden_channels, args.num_classes, len(fan_out)).to(device)
     elif args.model_type == "rgcn":

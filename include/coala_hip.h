@@ -972,7 +972,45 @@ int coala_block_time_attn_aggregate_backward(int device, const int32_t* nbr, con
                                              const float* lse, const float* grad_out, const float* grad_tagg, float* grad_q, float* grad_k,
                                              float* grad_v, float* grad_qt, float* grad_time_parts, int parts, int64_t n_dst, int fanout,
                                              int heads, int dim, int time_dim, float scale, void* stream);
-/* Edge exclusion (link prediction: the seed edges, and their reverses, leave the message-flow blocks).  excluded: device int64
+/* Dot-product attention over edges that carry a feature row (csrc/coala_edge_attn.hip; PyG's TransformerConv(edge_dim=) with the edge
+ * projection split off: the caller brings qe[d, h] = W_e[h]^T q[d, h] and takes eagg back, so nothing of shape [E, heads, dim] exists).
+ * Fixed form: nbr int32 [n_dst, fanout] (-1 = no edge, wherever it stands), any fanout >= 1; CSR form: indptr int64 [n_dst + 1], indices
+ * int32 [E] (a -1 is skipped).  q [n_dst, heads, dim], k and v [n_src, heads, dim], qe [n_dst, heads, edge_dim], efeat [M, edge_dim].
+ * eids: one id per slot, laid out like the index array, int64 when eid_is_64 and int32 otherwise, not read where the index is -1: slot
+ * j's edge row is x_j = efeat[eids_j] (ids are NOT checked against M; a negative id on an edge makes it a slot without an edge row);
+ * eids NULL: x_j is efeat's row of the slot itself, efeat [n_dst * fanout, edge_dim] or [E, edge_dim].  For dst d, head h, the slots j
+ * with an edge:
+ *   e_j = scale (<q[d, h, :], k[s_j, h, :]> + <qe[d, h, :], x_j>),  a_j = softmax of e over the row,
+ *   out[d, h, :] = sum_j a_j v[s_j, h, :]  [n_dst, heads, dim],   eagg[d, h, :] = sum_j a_j x_j  [n_dst, heads, edge_dim],
+ *   lse[d, h] the log-sum-exp of e (-inf for a row without an edge, whose out and eagg are zeros): the state of the backward.
+ * Backward, one launch, with ds_j = a_j (<grad_out[d, h], v_j> + <grad_eagg[d, h], x_j> - <grad_out[d, h], out[d, h]> - <grad_eagg[d, h],
+ * eagg[d, h]>), a_j recomputed from lse and divided by its row sum:
+ *   grad_q[d, h, :] = scale sum_j ds_j k_j       grad_qe[d, h, :] = scale sum_j ds_j x_j         written whole, slot order, no atomics;
+ *   grad_k[s_j, h, :] += scale ds_j q[d, h, :]   grad_v[s_j, h, :] += a_j grad_out[d, h, :]       float atomics: the caller zeroes them;
+ *   grad_x_j = sum_h (scale ds_j[h] qe[d, h, :] + a_j[h] grad_eagg[d, h, :]): without eids stored at the slot's own row of grad_efeat
+ *     (every slot is written, 0 where there is no edge); with eids added to row eids_j by float atomics (the caller zeroes grad_efeat).
+ * Each of the five outputs may be NULL (not wanted); with all five NULL nothing is launched.
+ * Determinism: out, eagg, lse, grad_q, grad_qe and the slot form's grad_efeat are bitwise reproducible, and a CSR row gives the bits of
+ * the same row padded with -1 to any fan-out; grad_k, grad_v and the table form's grad_efeat depend on the order of the atomics.
+ * Refused with COALA_EINVAL and nothing launched: "bad block shape" (fan-out < 1, heads outside 1..16, dim < 1, edge_dim outside 1..128,
+ * n_dst < 0), "null buffer"; n_dst == 0 launches nothing and reads no pointer.  One wave per row, at most 2048 blocks of four waves. */
+int coala_block_edge_attn_aggregate(int device, const int32_t* nbr, const void* eids, int eid_is_64, const float* q, const float* k,
+                                    const float* v, const float* qe, const float* efeat, float* out, float* eagg, float* lse, int64_t n_dst,
+                                    int fanout, int heads, int dim, int edge_dim, float scale, void* stream);
+int coala_block_edge_attn_aggregate_backward(int device, const int32_t* nbr, const void* eids, int eid_is_64, const float* q, const float* k,
+                                             const float* v, const float* qe, const float* efeat, const float* out, const float* eagg,
+                                             const float* lse, const float* grad_out, const float* grad_eagg, float* grad_q, float* grad_k,
+                                             float* grad_v, float* grad_qe, float* grad_efeat, int64_t n_dst, int fanout, int heads, int dim,
+                                             int edge_dim, float scale, void* stream);
+int coala_block_edge_attn_aggregate_csr(int device, const int64_t* indptr, const int32_t* indices, const void* eids, int eid_is_64,
+                                        const float* q, const float* k, const float* v, const float* qe, const float* efeat, float* out,
+                                        float* eagg, float* lse, int64_t n_dst, int heads, int dim, int edge_dim, float scale, void* stream);
+int coala_block_edge_attn_aggregate_csr_backward(int device, const int64_t* indptr, const int32_t* indices, const void* eids, int eid_is_64,
+                                                 const float* q, const float* k, const float* v, const float* qe, const float* efeat,
+                                                 const float* out, const float* eagg, const float* lse, const float* grad_out,
+                                                 const float* grad_eagg, float* grad_q, float* grad_k, float* grad_v, float* grad_qe,
+                                                 float* grad_efeat, int64_t n_dst, int heads, int dim, int edge_dim, float scale, void* stream);
+/* Edge exclusion(link prediction: the seed edges, and their reverses, leave the message-flow blocks).  excluded: device int64
  * [n_excluded], SORTED ascending, CSC positions (a few thousand at most; every slot binary-searches its edge id in it).  eid is the
  * block's edge-id array (coala_sampler_sample_layers_edge_ids), laid out like its index array.
  *   fixed form: nbr int32 [n_dst, fanout], eid int64 [n_dst, fanout] -> nbr_out, eid_out of the same shapes (other buffers than the
